@@ -1,7 +1,13 @@
 #!/usr/bin/env python3
 """Headline benchmark: edges/sec of a train-seq-len=15 RGCN+GRU window encoder, forward+backward.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload S-gdelt]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload S-gdelt] [--full] [--dump-outputs DIR]
+
+A plain run sets up, warms up, times K steps and prints the JSON line (`value`, `ms_per_step` = milliseconds of one timed step);
+the secondary measurements below (roofline, cpu_baseline, extra, config.train_loop, config.fp32_mfma_ms_per_step,
+config.ms_per_step_400_replays, north_star_sharded of --shard both) run only with --full, after the timed region.
+--dump-outputs DIR writes the last timed step's forward output and parameter gradients as DIR/*.npy; the inputs are seeded, so
+two builds run with the same arguments can be compared array by array.
 
 One "step" = one forward+backward pass of the snapshot encoder (2 RGCN layers + GRU/BiGRU chain,
 BiGRRGCN with --rec-only-last-layer) over one batch of bsz windows of synthetic GDELT-shaped
@@ -14,7 +20,7 @@ Multi-GPU (one process per GPU, torch.distributed over RCCL): every rank encodes
 windows (weak scaling, the reference's DDP axis) and the parameter gradients are all-reduced in
 one bucket after backward.
 
-Extra objects on the JSON line:
+Extra objects on the JSON line (with --full; null / absent without it):
   extra         short secondary measurements of the same process (never the headline): the step with the link-prediction loss,
                 the self-attention encoder (config 5), the snapshot-sharded north-star step on one RCCL rank, BASELINE configs 1-3
                 at their own sizes (static RGCN; GRRGCN with the reference's default flags; post-ensemble BiGRRGCN), and the FULL
@@ -572,12 +578,13 @@ def shbm_main(a, lib, device):
 
 class GraphStep:
     """One forward+backward of `run()` with upstream gradient = ones, captured once into a HIP graph and replayed (eager when the
-    capture fails or graph=False).  `grads` = the gradient tensors every replay writes."""
+    capture fails or graph=False).  `grads` = the gradient tensors every replay writes; `out` = the forward output of the last
+    step (detached; under replay the tensor the graph writes)."""
 
     def __init__(self, run, params, graph=True):
         self.run, self.params = run, params
         self._ones = {}
-        self.graph = self.grads = None
+        self.graph = self.grads = self.out = None
         if graph:
             self._capture()
 
@@ -593,7 +600,9 @@ class GraphStep:
     def eager(self):
         for p in self.params:
             p.grad = None
-        self._backward_ones(self.run())
+        out = self.run()
+        self.out = out.detach()
+        self._backward_ones(out)
 
     def _capture(self):
         try:
@@ -606,9 +615,13 @@ class GraphStep:
             torch.cuda.synchronize()
             for p in self.params:
                 p.grad = None
+            self.out = None
             g = torch.cuda.CUDAGraph()
             with torch.cuda.graph(g, capture_error_mode="thread_local"):     # RCCL's watchdog thread polls events meanwhile
-                self._backward_ones(self.run())
+                out = self.run()
+                self.out = out.detach()
+                self._backward_ones(out)
+                del out
             torch.cuda.synchronize()
             self.graph, self.grads = g, [p.grad for p in self.params]
         except Exception as e:                      # capture is an optimisation only
@@ -951,19 +964,41 @@ def emit(obj):
     f.flush()
 
 
+DUMP_LIMIT_BYTES = 64 * 10 ** 6     # --dump-outputs: all files together
+
+
+def dump_outputs(path, arrays):
+    """--dump-outputs: every tensor of `arrays` as <path>/<name>.npy, float32 (float64 stays float64), in the tensor's shape.  When
+    the whole would exceed DUMP_LIMIT_BYTES, an array larger than an equal share of the budget is written as a fixed sample of its
+    elements instead: the flattened array at indices drawn by np.random.default_rng(0) without replacement, in ascending order (the
+    same indices for the same shape in every run)."""
+    os.makedirs(path, exist_ok=True)
+    host = {}
+    for name, t in arrays.items():
+        t = t.detach()
+        host[name] = (t if t.dtype == torch.float64 else t.float()).cpu().numpy()
+    share = (DUMP_LIMIT_BYTES - 256 * len(host)) // max(len(host), 1)          # (256 bytes: room for each file's .npy header)
+    over = sum(x.nbytes for x in host.values()) > DUMP_LIMIT_BYTES - 256 * len(host)
+    for name, x in host.items():
+        if over and x.nbytes > share:
+            idx = np.sort(np.random.default_rng(0).choice(x.size, size=share // x.itemsize, replace=False))
+            x = x.reshape(-1)[idx]
+        np.save(os.path.join(path, name + ".npy"), x)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=200, help="timed steps (0.5 s of replays at the headline shape: boxes differ by a few per cent)")
     ap.add_argument("--warmup", type=int, default=20)
     ap.add_argument("--workload", default="S-gdelt")
-    ap.add_argument("--trace-steps", type=int, default=3)
+    ap.add_argument("--trace-steps", type=int, default=3, help="--full: eager steps traced per kernel after the timed region (roofline)")
     ap.add_argument("--shard", choices=("both", "windows", "snapshots"), default="both",
                     help="N>1: 'windows' = each rank encodes its own windows (+ gradient all-reduce), the reference's DDP axis, HIP-graph "
                          "replay; 'snapshots' = the distinct snapshots of a global batch of bsz*N windows sharded across ranks with a "
                          "direct all-gather of per-snapshot node states before the recurrent chain (BASELINE north_star; three HIP graphs around the two exchanges); "
-                         "'both' (default) = the headline `value` is the windows mode and the snapshot-sharded measurement rides along "
-                         "under `north_star_sharded`")
+                         "'both' (default) = the headline `value` is the windows mode and, with --full, the snapshot-sharded measurement rides "
+                         "along under `north_star_sharded`")
     ap.add_argument("--sharded-timeout", type=int, default=240, help="N > 1, --shard both: seconds the snapshot-sharded measurement may take "
                                                                        "before the headline line is printed without it")
     ap.add_argument("--no-cpu-baseline", action="store_true")
@@ -977,7 +1012,7 @@ def main():
     ap.add_argument("--with-loss", action="store_true",
                     help="also run the all-entity pass + scorer + cross-entropy (negative_rate 500, fixed negatives) in the step "
                          "(reported separately from the headline encoder-only metric, SURVEY 8d)")
-    ap.add_argument("--kernel-table", action="store_true", help="print the per-kernel trace table to stderr")
+    ap.add_argument("--kernel-table", action="store_true", help="--full: print the per-kernel trace table to stderr")
     ap.add_argument("--encoder", choices=("gru", "attention"), default="gru",
                     help="gru: the headline RGCN+GRU window models; attention: SelfAttentionRGCN / BiSelfAttentionRGCN (config 5, "
                          "secondary measurement: no cpu_baseline leg)")
@@ -996,6 +1031,14 @@ def main():
     ap.add_argument("--extra-child", default="", help="(internal) child process of one `extra.config*` measurement: prints its JSON object")
     ap.add_argument("--rendezvous-only", action="store_true",
                     help="(test hook) join the process group (nccl with a GPU, gloo without), all-reduce the rank ids, print one line and exit")
+    ap.add_argument("--full", action="store_true",
+                    help="also run everything beside the headline, after the timed region: the event-traced eager steps (roofline, "
+                         "--kernel-table), the 400-replay timing, the CPU baseline, `extra`, the training loop, the fp32-MFMA "
+                         "comparison and, with N > 1 and --shard both, the snapshot-sharded measurement.  Without it a run sets up, "
+                         "warms up, times --steps steps, writes --dump-outputs and prints the line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default="",
+                    help="after the timed region, write what its last step computed as DIR/<name>.npy (float32): output.npy = the "
+                         "step's forward output, grad.<parameter>.npy = the gradients; at most 64 MB in all (rank 0's arrays)")
     a = ap.parse_args()
     if a.cpu_probe:
         return cpu_probe_main(a)
@@ -1136,7 +1179,17 @@ def main():
         dist.all_reduce(e)
         edges = float(e.item())
     value = edges * a.steps / elapsed
-    if dist is not None and a.shard == "both" and a.encoder == "gru" and not a.with_loss:
+    if a.dump_outputs and rank == 0:
+        # what the last timed step left: the forward output and the gradients (all-reduced across ranks when N > 1)
+        if sharded:
+            out_t, grads = sharded_step.out, [p.grad for p in params]
+        else:
+            out_t, grads = gs.out, (graph_grads if graph is not None else [p.grad for p in params])
+        names = [n for n, _ in model.named_parameters()]
+        arrays = {"output": out_t}
+        arrays.update(("grad." + n, g) for n, g in zip(names, grads) if g is not None)
+        dump_outputs(a.dump_outputs, arrays)
+    if a.full and dist is not None and a.shard == "both" and a.encoder == "gru" and not a.with_loss:
         # The snapshot-sharded measurement (north_star's variant) runs AFTER the headline, under a watchdog: its point-to-point
         # exchange has never met more than one GPU (one-GPU boxes), and a rank stuck in it must not cost the headline line.  When
         # the timer fires, every rank is stuck in the same place: rank 0 prints the line with what it has and all ranks leave.
@@ -1175,7 +1228,7 @@ def main():
 
     roof = None
     cpu = None
-    if rank == 0 and a.trace_steps > 0 and not sharded:
+    if a.full and rank == 0 and a.trace_steps > 0 and not sharded:
         tr = traced_steps(step_eager_local, a.trace_steps, lib)  # per-kernel events need eager launches; this rank's kernels only (no all-reduce: the peers have left)
         costs = algorithmic_costs(wb, w["D"], bi, w["D"] // w["B"])
         total_ms = sum(v["ms_per_step"] for v in tr.values())
@@ -1300,7 +1353,7 @@ def main():
     # a longer replay of the same graph when the timed region was short (the driver's 20 steps are 50 ms: box-to-box noise is larger
     # than the 1-3 % steps a round works on); reported beside the headline, never instead of it
     long_ms = None
-    if rank == 0 and world == 1 and not sharded and a.steps < 200 and a.trace_steps > 0 and not a.no_graph:      # (not in counter / eager runs)
+    if a.full and rank == 0 and world == 1 and not sharded and a.steps < 200 and a.trace_steps > 0 and not a.no_graph:      # (not in counter / eager runs)
         for _ in range(5):
             step()
         torch.cuda.synchronize()
@@ -1309,20 +1362,20 @@ def main():
             step()
         torch.cuda.synchronize()
         long_ms = 1e3 * (time.perf_counter() - tl) / 400
-    if rank == 0 and not a.no_cpu_baseline:
+    if a.full and rank == 0 and not a.no_cpu_baseline:
         cpu = cpu_baseline(model, w, targets)
     extra = None
-    if rank == 0 and world == 1 and not sharded and not a.no_extras and a.workload == "S-gdelt" and a.encoder == "gru" and not a.with_loss:
+    if a.full and rank == 0 and world == 1 and not sharded and not a.no_extras and a.workload == "S-gdelt" and a.encoder == "gru" and not a.with_loss:
         extra = extra_measurements(a, w, model, wb, targets, device, lib)
     loop = None
-    if rank == 0 and world == 1 and a.train_loop_steps > 0 and not sharded:
+    if a.full and rank == 0 and world == 1 and a.train_loop_steps > 0 and not sharded:
         try:
             loop = train_loop(model, w, a.train_loop_steps)
         except Exception as e:                      # an extra, never the headline
             print("bench: training-loop probe failed (%s: %s)" % (type(e).__name__, e), file=sys.stderr)
 
     fp32_ms = None
-    if rank == 0 and world == 1 and not sharded and MFMA_MODE in ("bf16x3", "f16x2") and not a.no_fp32_mfma_compare:
+    if a.full and rank == 0 and world == 1 and not sharded and MFMA_MODE in ("bf16x3", "f16x2") and not a.no_fp32_mfma_compare:
         # the same step with every product on the fp32 MFMA kernels: one library switch, same process, same batch, graph re-captured
         try:
             lib.temp_set_option(OPT_MFMA_BF16X3, 0)
@@ -1371,7 +1424,7 @@ def main():
                                      "matrix pipe as six products of an exact 3-way operand split (fp32-equivalent accuracy, gemm_bx.hpp); "
                                      "small products (< 16384 rows) on the fp32 MFMA pipe" if MFMA_MODE == "bf16x3"
                                      else "fp32 MFMA everywhere (TEMP_OPT_MFMA_BF16X3 = 0)"),
-                               fp32_mfma_ms_per_step=fp32_ms, ms_per_step_400_replays=long_ms),
+                               fp32_mfma_ms_per_step=fp32_ms, ms_per_step_400_replays=long_ms, full=a.full),
                    roofline=roof, cpu_baseline=cpu, north_star_sharded=ns_result, extra=extra)
         # the end-to-end figures a reader of the line's TAIL must see (the driver keeps the parsed head and the last characters):
         # value_distinct and the training loop (a NEW batch every step) also as the LAST keys of `extra`
