@@ -447,7 +447,14 @@ typedef struct TempGruChain {
   const int32_t* gi_index;               /* nullable [N_total]: row of `gi` that holds row i's input gates.  Chain rows that read the
                                           * same input row share one gi row (temp_gru_input_gates_gather_multi computes each once);
                                           * NULL: gi has N_total rows, row i's gates in row i.  Forward only: dgi stays per row. */
+  int32_t pack_layout;                   /* TEMP_CHAIN_PACK_*: the layout `packed` was written in -- temp_gru_chain_pack_layout(d) at the
+                                          * time of temp_gru_chain_pack / _pack_multi, TEMP_CHAIN_PACK_HX_X for temp_gru_chain_pack_x_multi.
+                                          * The kernels follow it (not the options at launch time); a layout this width cannot have:
+                                          * TEMP_E_BADARG. */
 } TempGruChain;
+enum { TEMP_CHAIN_PACK_F32 = 1, TEMP_CHAIN_PACK_BX = 2, TEMP_CHAIN_PACK_HX = 3, TEMP_CHAIN_PACK_HX_X = 4 };
+/* the layout temp_gru_chain_pack / _pack_multi write for width d under the current options (TEMP_OPT_MFMA_*) */
+int temp_gru_chain_pack_layout(int d);
 int temp_gru_chain_supported(int d);
 size_t temp_gru_chain_pack_floats(int d);                                   /* floats of one packed W_hh */
 int temp_gru_chain_pack(int d, const float* w_hh, float* packed, void* stream);
@@ -455,6 +462,19 @@ int temp_gru_chain_pack(int d, const float* w_hh, float* packed, void* stream);
  * temp_gru_chain_pack_floats(d) floats) */
 int temp_gru_chain_pack_multi(int count, int d, const float* const* w_hh, float* const* packed, void* stream);
 int temp_gru_chain_fwd(const TempGruChain* c, const float* gi, float* h_out, float* saved, void* stream);
+/* The forward with the input gates computed inside (nn.GRU gate layout, f16 arithmetic): x rows instead of gi, no gate GEMM.
+ *   x [x rows][d], x_index [N_total]: x row of chain row i; b_ih: HOST array of n_rnn device pointers; c->packed[i] from
+ *   temp_gru_chain_pack_x_multi (W_hh laid out as temp_gru_chain_pack_multi lays it out -- the backward takes the same buffer --
+ *   followed by W_ih's planes).  h_out / saved as temp_gru_chain_fwd (saved[4] = the decayed previous state, as there).
+ * temp_gru_chain_fwd_x_supported: 1 when this entry takes the width, variant and c->max_steps (the f16 route is selected, the
+ * LDS images fit, TEMP_DEBUG bit 22 -- the A/B switch to the gi route -- is clear); otherwise the call returns TEMP_E_UNSUPPORTED.
+ * temp_gru_chain_fwd_x_launches: launches of the kernel since the library was loaded (diagnostic). */
+int temp_gru_chain_fwd_x_supported(int d, int variant, int max_steps);
+size_t temp_gru_chain_pack_x_floats(int d);
+int temp_gru_chain_pack_x_multi(int count, int d, const float* const* w_hh, const float* const* w_ih, float* const* packed, void* stream);
+int temp_gru_chain_fwd_x(const TempGruChain* c, const float* x, const int32_t* x_index, const float* const* b_ih, float* h_out, float* saved,
+                         void* stream);
+long long temp_gru_chain_fwd_x_launches(void);
 int temp_gru_chain_bwd(const TempGruChain* c, const float* saved, int n_up, const float* const* up /* HOST array of device pointers */,
                        float* dgi, float* dgh, void* stream);
 /* The same backward with the gate gradients written ONCE (round 5; nn.GRU gate layout only):

@@ -57,13 +57,14 @@ CHAIN_TRACKS = 32
 CHAIN_MAX_RNN = 4
 CHAIN_MAX_UP = 8
 CHAIN_MAX_STEPS = 64
+CHAIN_PACK_F32, CHAIN_PACK_BX, CHAIN_PACK_HX, CHAIN_PACK_HX_X = 1, 2, 3, 4     # TempGruChain.pack_layout
 
 
 class TempGruChain(ctypes.Structure):
     _fields_ = [("d", ctypes.c_int32), ("variant", ctypes.c_int32), ("n_panels", ctypes.c_int32), ("n_steps", ctypes.c_int32),
                 ("max_steps", ctypes.c_int32), ("panel", c_vp), ("rows", c_vp), ("sinfo", c_vp), ("dt", c_vp), ("lambda_", ctypes.c_float),
                 ("saved_plane", ctypes.c_size_t), ("n_rnn", ctypes.c_int32), ("packed", c_vp * CHAIN_MAX_RNN), ("b_hh", c_vp * CHAIN_MAX_RNN),
-                ("gi_index", c_vp)]
+                ("gi_index", c_vp), ("pack_layout", ctypes.c_int32)]
 
 
 class TempSubsampleJob(ctypes.Structure):
@@ -139,6 +140,12 @@ SYMBOLS = {
     "temp_gru_chain_pack": (_I, [_I, c_vp, c_vp, c_vp]),
     "temp_gru_chain_pack_multi": (_I, [_I, _I, ctypes.POINTER(c_vp), ctypes.POINTER(c_vp), c_vp]),
     "temp_gru_chain_fwd": (_I, [ctypes.POINTER(TempGruChain), c_vp, c_vp, c_vp, c_vp]),
+    "temp_gru_chain_pack_layout": (_I, [_I]),
+    "temp_gru_chain_fwd_x_supported": (_I, [_I, _I, _I]),
+    "temp_gru_chain_pack_x_floats": (_SZ, [_I]),
+    "temp_gru_chain_pack_x_multi": (_I, [_I, _I, ctypes.POINTER(c_vp), ctypes.POINTER(c_vp), ctypes.POINTER(c_vp), c_vp]),
+    "temp_gru_chain_fwd_x": (_I, [ctypes.POINTER(TempGruChain), c_vp, c_vp, ctypes.POINTER(c_vp), c_vp, c_vp, c_vp]),
+    "temp_gru_chain_fwd_x_launches": (ctypes.c_longlong, []),
     "temp_gru_chain_bwd": (_I, [ctypes.POINTER(TempGruChain), c_vp, _I, ctypes.POINTER(c_vp), c_vp, c_vp, c_vp]),
     "temp_gru_chain_bwd_g4": (_I, [ctypes.POINTER(TempGruChain), c_vp, _I, ctypes.POINTER(c_vp), c_vp, c_vp]),
     "temp_gru_chain_keys_supported": (_I, [_I]),

@@ -343,7 +343,9 @@ class HipBackend:
         w_hh = _f32(w_hh, "w_hh")
         d = w_hh.shape[1]
         out = torch.empty(self.lib.temp_gru_chain_pack_floats(d), dtype=torch.float32, device=w_hh.device)
+        layout = self.lib.temp_gru_chain_pack_layout(d)
         _lib.check(self.lib.temp_gru_chain_pack(d, _ptr(w_hh), _ptr(out), _stream()), "temp_gru_chain_pack")
+        out.chain_pack_layout = layout                   # (TempGruChain.pack_layout: the kernels follow the pack, not the options)
         return out
 
     def gru_chain_pack_multi(self, w_hhs):
@@ -354,14 +356,24 @@ class HipBackend:
         buf = torch.empty(len(w_hhs), n, dtype=torch.float32, device=w_hhs[0].device)
         src = (ctypes.c_void_p * len(w_hhs))(*[w.data_ptr() for w in w_hhs])
         dst = (ctypes.c_void_p * len(w_hhs))(*[buf[i].data_ptr() for i in range(len(w_hhs))])
+        layout = self.lib.temp_gru_chain_pack_layout(d)
         _lib.check(self.lib.temp_gru_chain_pack_multi(len(w_hhs), d, src, dst, _stream()), "temp_gru_chain_pack_multi")
-        return [buf[i] for i in range(len(w_hhs))]
+        return self._tagged([buf[i] for i in range(len(w_hhs))], layout)
+
+    @staticmethod
+    def _tagged(packs, layout):
+        for pk in packs:
+            pk.chain_pack_layout = layout
+        return packs
 
     def _chain_desc(self, tabs, d, variant, lam, plane, packs, b_hhs):
         c = _lib.TempGruChain()
         c.d, c.variant, c.n_panels, c.n_steps, c.max_steps = d, variant, tabs["n_panels"], tabs["n_steps"], tabs["max_steps"]
         c.panel, c.rows, c.sinfo, c.dt = (_i32(tabs[k], k).data_ptr() for k in ("panel", "rows", "sinfo", "dt_bits"))
         c.lambda_, c.saved_plane, c.n_rnn = float(lam), plane, len(packs)
+        layouts = {getattr(pk, "chain_pack_layout", None) for pk in packs}
+        assert len(layouts) == 1 and None not in layouts, "chain packs without one common layout tag (gru_chain_pack*)"
+        c.pack_layout = layouts.pop()
         keep = []
         for i, (pk, b) in enumerate(zip(packs, b_hhs)):
             pk, b = _f32(pk, "packed"), _f32(b, "b_hh")
@@ -377,6 +389,35 @@ class HipBackend:
             c.gi_index = _i32(gi_index, "gi_index").data_ptr()
         rc = self.lib.temp_gru_chain_fwd(ctypes.byref(c), _ptr(_f32(gi, "gi")), _ptr(h_out), _ptr(saved_all), _stream())
         _lib.check(rc, "temp_gru_chain_fwd")
+
+    def gru_chain_fwd_x_supported(self, d, variant, max_steps):
+        """True when temp_gru_chain_fwd_x takes this width, variant and longest panel (the input gates computed inside the chain
+        forward; TEMP_DEBUG bit 22 turns it off)."""
+        return bool(self.lib.temp_gru_chain_fwd_x_supported(int(d), int(variant), int(max_steps)))
+
+    def gru_chain_pack_x_multi(self, w_hhs, w_ihs):
+        """W_hh and W_ih of several GRUs -> temp_gru_chain_fwd_x's packed weights in ONE launch (list of views of one buffer; the
+        chain backward takes them like gru_chain_pack_multi's)."""
+        w_hhs, w_ihs = [_f32(w, "w_hh") for w in w_hhs], [_f32(w, "w_ih") for w in w_ihs]
+        d = w_hhs[0].shape[1]
+        k = len(w_hhs)
+        n = self.lib.temp_gru_chain_pack_x_floats(d)
+        buf = torch.empty(k, n, dtype=torch.float32, device=w_hhs[0].device)
+        arr = lambda ts: (ctypes.c_void_p * k)(*[t.data_ptr() for t in ts])
+        _lib.check(self.lib.temp_gru_chain_pack_x_multi(k, d, arr(w_hhs), arr(w_ihs), arr([buf[i] for i in range(k)]), _stream()),
+                   "temp_gru_chain_pack_x_multi")
+        return self._tagged([buf[i] for i in range(k)], _lib.CHAIN_PACK_HX_X)
+
+    def gru_chain_fwd_x(self, tabs, x, x_index, lam, variant, packs, b_hhs, b_ihs, h_out, saved_all):
+        """The chain forward from the x rows (x_index: int32 [N_total], x row of every chain row): no gi (temp_gru_chain_fwd_x)."""
+        d = saved_all.shape[2]
+        c, keep = self._chain_desc(tabs, d, variant, lam, saved_all.shape[1] * d, packs, b_hhs)
+        x = _f32(x, "x")
+        assert x.shape[1] == d and x_index.shape[0] == saved_all.shape[1]
+        b_ihs = [_f32(b, "b_ih") for b in b_ihs]
+        barr = (ctypes.c_void_p * len(b_ihs))(*[b.data_ptr() for b in b_ihs])
+        rc = self.lib.temp_gru_chain_fwd_x(ctypes.byref(c), _ptr(x), _ptr(_i32(x_index, "x_index")), barr, _ptr(h_out), _ptr(saved_all), _stream())
+        _lib.check(rc, "temp_gru_chain_fwd_x")
 
     def gru_chain_bwd(self, tabs, saved_all, ups, lam, variant, packs, b_hhs, dgi, dgh):
         d = saved_all.shape[2]

@@ -14,6 +14,7 @@
 //              after the hand-over barrier these waves apply the gates, write the saved planes / gate gradients with
 //              row-contiguous float4 stores and put the new state (resp. d_prev) back into LDS.
 // The matrix waves never wait on HBM: their only global loads are L2 hits on the packed weights.
+#include <atomic>
 #include "common.hpp"
 #include "gru_math.hpp"
 #include "gemm_bx.hpp"
@@ -28,6 +29,7 @@ namespace temp {
 struct ChainRnn { const float4* wf; const float4* wb; const float* b_hh; const unsigned* kf; const unsigned* kb; };   // kf / kb: column keys of the f16 planes (gru_chain_hx.hpp)
 struct ChainArgs {
   int D, n_panels, max_steps, dbg;
+  int layout;                            // TEMP_CHAIN_PACK_*: the arithmetic the packed weights were written for (the kernels follow it)
   int n_rnn_keys;                        // GRUs of the chain (rows of the column-key result in front of the per-panel partials)
   const int32_t* panel; const int32_t* rows; const int32_t* sinfo;
   const float* dt;
@@ -630,6 +632,7 @@ __global__ void __launch_bounds__(256 + 64 * MW) k_gru_chain_bwd(ChainArgs a, Ch
   }
 }
 
+static bool chain_layout_ok(int layout, int d);
 static int chain_check(const TempGruChain* c) {
   if (!c || c->d <= 0 || c->n_panels < 0 || c->n_steps < 0 || c->n_rnn <= 0 || c->n_rnn > TEMP_CHAIN_MAX_RNN) return TEMP_E_BADARG;
   if (c->variant != TEMP_GRU_TORCH && c->variant != TEMP_GRU_TYPE1) return TEMP_E_BADARG;
@@ -637,29 +640,41 @@ static int chain_check(const TempGruChain* c) {
   for (int i = 0; i < c->n_rnn; ++i) if (!c->packed[i] || !c->b_hh[i]) return TEMP_E_BADARG;
   if (c->max_steps <= 0 || c->max_steps > CH_MAX_STEPS) return TEMP_E_BADARG;
   if (!temp_gru_chain_supported(c->d)) return TEMP_E_UNSUPPORTED;
+  if (!chain_layout_ok(c->pack_layout, c->d)) return TEMP_E_BADARG;    // (a layout the packs cannot have been written in for this width)
   return TEMP_OK;
 }
 
 // the products of the chain run on the bf16 matrix pipe (three-way split) unless TEMP_MFMA=f32 or d is not a multiple of 8
 static bool chain_bx(int d) { return bx_enabled() && d % 8 == 0; }
 // ... and on the f16 pipe as three products of the scaled two-way split (gru_chain_hx.hpp) unless TEMP_MFMA=bf16x3 or its LDS images do not fit
-static bool chain_hx(int d) {
-  if (!chain_bx(d) || !hx_enabled()) return false;
+// (the width's part of it: the f16 kernels' LDS images fit and their tiles fit the waves' registers)
+static bool chain_hx_fits(int d) {
+  if (d % 8) return false;
   const ChainGeomHx g = chain_geom_hx(d);
   return chain_lds_fwd_hx(d, CH_MAX_STEPS) <= CH_LDS_LIMIT && chain_lds_bwd_hx(d, CH_MAX_STEPS) <= CH_LDS_LIMIT && g.NT <= 20 && g.NTb <= 8;   // (six tiles per matrix wave: the two register sets spill)
 }
+static bool chain_hx(int d) { return chain_bx(d) && hx_enabled() && chain_hx_fits(d); }
+// the layout temp_gru_chain_pack / _pack_multi write now (the options select it); the packs carry it from then on (TempGruChain.pack_layout)
+static int chain_pack_layout(int d) { return chain_hx(d) ? TEMP_CHAIN_PACK_HX : chain_bx(d) ? TEMP_CHAIN_PACK_BX : TEMP_CHAIN_PACK_F32; }
+static bool chain_layout_ok(int layout, int d) {
+  if (layout == TEMP_CHAIN_PACK_F32) return true;
+  if (layout == TEMP_CHAIN_PACK_BX) return d % 8 == 0;
+  return (layout == TEMP_CHAIN_PACK_HX || layout == TEMP_CHAIN_PACK_HX_X) && chain_hx_fits(d);
+}
+static bool layout_hx(int layout) { return layout == TEMP_CHAIN_PACK_HX || layout == TEMP_CHAIN_PACK_HX_X; }
 
 static ChainArgs chain_args(const TempGruChain* c) {
   ChainArgs a = {};
   const ChainGeom g = chain_geom(c->d);
   a.D = c->d; a.n_panels = c->n_panels; a.max_steps = c->max_steps; a.panel = c->panel; a.rows = c->rows; a.sinfo = c->sinfo; a.dt = c->dt;
+  a.layout = c->pack_layout;
   a.n_rnn_keys = c->n_rnn; a.lambda = c->lambda; a.plane = c->saved_plane; a.gi_index = c->gi_index; a.dbg = option(TEMP_OPT_DEBUG) >> 8;      // development A/B switches (bit 6: no per-block rotation of the slab walk); 0 in every product run
   for (int i = 0; i < c->n_rnn; ++i) {
     a.rnn[i].wf = (const float4*)c->packed[i];
-    a.rnn[i].wb = (const float4*)c->packed[i] + (chain_bx(c->d) ? (size_t)(g.NQ >> 1) * g.NT * 192 : (size_t)g.NT * g.NQ * 64);
+    a.rnn[i].wb = (const float4*)c->packed[i] + (a.layout == TEMP_CHAIN_PACK_BX ? (size_t)(g.NQ >> 1) * g.NT * 192 : (size_t)g.NT * g.NQ * 64);
     a.rnn[i].b_hh = c->b_hh[i];
     a.rnn[i].kf = a.rnn[i].kb = nullptr;
-    if (chain_hx(c->d)) {
+    if (layout_hx(a.layout)) {
       const ChainGeomHx gx = chain_geom_hx(c->d);
       a.rnn[i].wb = (const float4*)c->packed[i] + chain_hx_fwd_items(c->d);
       a.rnn[i].kf = (const unsigned*)((const float4*)c->packed[i] + chain_hx_fwd_items(c->d) + chain_hx_bwd_items(c->d));
@@ -683,7 +698,7 @@ static int launch_chain_fwd(const ChainArgs& a, const float* gi, float* h, float
   static bool attr = false;
   static bool attr_bx = false;
   static bool attr_hx = false;
-  if (chain_hx(a.D)) {
+  if (layout_hx(a.layout)) {
     const size_t lds_hx = chain_lds_fwd_hx(a.D, a.max_steps);
     // 8 + 8 waves (two matrix and two memory waves per SIMD, 128 registers each): a memory wave then has 28 stores + 12 loads
     // in flight per position instead of 56 + 24 -- beyond the 63 a wave's counter can track, every further access waits for the oldest
@@ -717,7 +732,7 @@ static int launch_chain_fwd(const ChainArgs& a, const float* gi, float* h, float
     return launch_status();
   }
   const size_t lds = chain_lds_fwd(a.D, a.max_steps);
-  if (chain_bx(a.D)) {
+  if (a.layout == TEMP_CHAIN_PACK_BX) {
     auto kernel = k_gru_chain_fwd<VARIANT, TPW, 4, 1>;
     int rc = chain_lds_attr(kernel, lds, &attr_bx);
     if (rc) return rc;
@@ -731,13 +746,26 @@ static int launch_chain_fwd(const ChainArgs& a, const float* gi, float* h, float
   return launch_status();
 }
 
+// ---- the forward with the input gates inside (gru_chain_hx.hpp: k_gru_chain_fwd_x) ------------------------------------
+#define CH_FWD_X_OFF 0x400000        // TEMP_DEBUG bit 22: development A/B, callers take the gi route (temp_gru_chain_fwd + its GEMM)
+static std::atomic<long long> g_fwd_x_launches{0};
+// the W_ih planes behind the W_hh layout of chain_args() (floats)
+static size_t chain_x_ih_offset(int d) { return chain_hx_pack_floats(d); }
+// the kernel takes this width and panel length (its LDS images: at d = 200, 158 848 + 260 max_steps bytes -- max_steps <= 19)
+static bool chain_fwd_x_fits(int d, int max_steps) {
+  return chain_hx_fits(d) && d / 4 <= 64 && max_steps > 0 && max_steps <= CH_MAX_STEPS && chain_lds_fwd_x(d, max_steps) <= CH_LDS_LIMIT &&
+         (chain_geom_hx(d).NT + 7) / 8 <= 3;
+}
+// ... and callers should take it: f16 arithmetic selected, TEMP_DEBUG bit 22 clear
+static bool chain_fwd_x_ok(int d, int max_steps) { return chain_hx(d) && !(option(TEMP_OPT_DEBUG) & CH_FWD_X_OFF) && chain_fwd_x_fits(d, max_steps); }
+
 template <int VARIANT, int TPWB, int G4 = 0>
 static int launch_chain_bwd(const ChainArgs& a, const ChainUps& ups, const float* saved, float* dgi, float* dgh, hipStream_t st,
                             unsigned* row_keys = nullptr, unsigned* col_keys = nullptr) {
   static bool attr = false;
   static bool attr_bx = false;
   static bool attr_hx = false;
-  if (chain_hx(a.D)) {
+  if (layout_hx(a.layout)) {
     const size_t lds_hx = chain_lds_bwd_hx(a.D, a.max_steps);
     constexpr int TPWB8 = (TPWB * 4 + 7) / 8 < 1 ? 1 : (TPWB * 4 + 7) / 8;
     // 4 + 8 waves (168 registers); 8 + 8 waves with a ring of eight slabs -- two matrix waves per SIMD covering each other's L2
@@ -767,7 +795,7 @@ static int launch_chain_bwd(const ChainArgs& a, const ChainUps& ups, const float
   }
   if (row_keys || col_keys) return TEMP_E_UNSUPPORTED;          // (only the f16 kernels produce keys: ask temp_gru_chain_keys_supported first)
   const size_t lds = chain_lds_bwd(a.D, a.max_steps);
-  if (chain_bx(a.D)) {
+  if (a.layout == TEMP_CHAIN_PACK_BX) {
     auto kernel = k_gru_chain_bwd<VARIANT, TPWB, 8, 1, G4>;
     int rc = chain_lds_attr(kernel, lds, &attr_bx);
     if (rc) return rc;
@@ -884,6 +912,79 @@ int temp_gru_chain_fwd(const TempGruChain* c, const float* gi, float* h_out, flo
 #undef TEMP_CHAIN_FWD
 }
 
+int temp_gru_chain_fwd_x_supported(int d, int variant, int max_steps) {
+  return d > 0 && d % 8 == 0 && variant == TEMP_GRU_TORCH && chain_fwd_x_ok(d, max_steps) ? 1 : 0;
+}
+
+size_t temp_gru_chain_pack_x_floats(int d) {
+  if (d <= 0) return 0;
+  return chain_x_ih_offset(d) + chain_hx_fwd_items(d) * 4;
+}
+
+int temp_gru_chain_pack_x_multi(int count, int d, const float* const* w_hh, const float* const* w_ih, float* const* packed, void* stream) {
+  if (count <= 0 || count > TEMP_CHAIN_MAX_RNN || d <= 0 || !w_hh || !w_ih || !packed) return TEMP_E_BADARG;
+  for (int i = 0; i < count; ++i) if (!w_hh[i] || !w_ih[i] || !packed[i]) return TEMP_E_BADARG;
+  if (d % 8 || !chain_hx(d)) return TEMP_E_UNSUPPORTED;
+  // per GRU: W_hh laid out as temp_gru_chain_pack_multi lays it out, then W_ih's two f16 planes in the same forward layout (gate
+  // column x k: W_ih as stored, [3d][d]).  The forward planes of both are scaled by the keys of their JOINT column maxima (kf);
+  // the backward planes and keys are temp_gru_chain_pack_multi's.
+  const ChainGeomHx gx = chain_geom_hx(d);
+  HxPackJobs jobs = {};
+  for (int i = 0; i < count; ++i) {
+    hx_u32x4* pf = reinterpret_cast<hx_u32x4*>(packed[i]);
+    hx_u32x4* pb = pf + chain_hx_fwd_items(d);
+    unsigned* kf = reinterpret_cast<unsigned*>(pb + chain_hx_bwd_items(d));
+    hx_u32x4* pi = reinterpret_cast<hx_u32x4*>(packed[i] + chain_x_ih_offset(d));
+    if (jobs.count + 2 > HX_PACK_JOBS) { hx_pack_launch(jobs, K_GRU_CHAIN_PACK, (hipStream_t)stream); jobs = HxPackJobs{}; }
+    hx_pack_jobs_add_joint(jobs, w_hh[i], pf, w_ih[i], pi, kf, d, 3 * d, d, 1);
+    hx_pack_jobs_add(jobs, w_hh[i], pb, kf + gx.NT * 32, 3 * d, d, d, 0, gx.NSb);
+  }
+  hx_pack_launch(jobs, K_GRU_CHAIN_PACK, (hipStream_t)stream);
+  return launch_status();
+}
+
+int temp_gru_chain_fwd_x(const TempGruChain* c, const float* x, const int32_t* x_index, const float* const* b_ih, float* h_out, float* saved, void* stream) {
+  int rc = chain_check(c);
+  if (rc) return rc;
+  if (c->pack_layout != TEMP_CHAIN_PACK_HX_X) return TEMP_E_BADARG;        // (the W_ih planes sit behind temp_gru_chain_pack_x_multi's packs only)
+  if (c->variant != TEMP_GRU_TORCH || !chain_fwd_x_fits(c->d, c->max_steps)) return TEMP_E_UNSUPPORTED;
+  if (c->n_panels == 0) return TEMP_OK;
+  if (!x || !x_index || !b_ih || !h_out || !saved) return TEMP_E_BADARG;
+  for (int i = 0; i < c->n_rnn; ++i) if (!b_ih[i]) return TEMP_E_BADARG;
+  const ChainArgs a = chain_args(c);
+  ChainX X = {};
+  X.x = x; X.x_index = x_index;
+  const ChainGeomHx gx = chain_geom_hx(c->d);
+  for (int i = 0; i < c->n_rnn; ++i) {
+    X.b_ih[i] = b_ih[i];
+    X.wi[i] = reinterpret_cast<const hx_u32x4*>(c->packed[i] + chain_x_ih_offset(c->d));
+  }
+  static bool attr = false;
+  const size_t lds = chain_lds_fwd_x(c->d, c->max_steps);
+  // 8 + 8 waves as k_gru_chain_fwd_hx's default configuration: two matrix waves per SIMD, 128 registers each
+  hipStream_t st = (hipStream_t)stream;
+  if ((gx.NT + 7) / 8 == 3) {
+    auto kernel = k_gru_chain_fwd_x<3, 8, 8>;
+    if ((rc = chain_lds_attr(kernel, lds, &attr))) return rc;
+    TEMP_LAUNCH(K_GRU_CHAIN_FWD, kernel, dim3(a.n_panels), dim3(1024), lds, st, a, X, h_out, saved);
+  } else if ((gx.NT + 7) / 8 == 2) {
+    static bool attr2 = false;
+    auto kernel = k_gru_chain_fwd_x<2, 8, 8>;
+    if ((rc = chain_lds_attr(kernel, lds, &attr2))) return rc;
+    TEMP_LAUNCH(K_GRU_CHAIN_FWD, kernel, dim3(a.n_panels), dim3(1024), lds, st, a, X, h_out, saved);
+  } else {
+    static bool attr1 = false;
+    auto kernel = k_gru_chain_fwd_x<1, 8, 8>;
+    if ((rc = chain_lds_attr(kernel, lds, &attr1))) return rc;
+    TEMP_LAUNCH(K_GRU_CHAIN_FWD, kernel, dim3(a.n_panels), dim3(1024), lds, st, a, X, h_out, saved);
+  }
+  hx_count();
+  g_fwd_x_launches.fetch_add(1, std::memory_order_relaxed);
+  return launch_status();
+}
+
+long long temp_gru_chain_fwd_x_launches(void) { return g_fwd_x_launches.load(std::memory_order_relaxed); }
+
 int temp_gru_chain_bwd_g4(const TempGruChain* c, const float* saved, int n_up, const float* const* up, float* g4, void* stream) {
   int rc = chain_check(c);
   if (rc) return rc;
@@ -901,6 +1002,8 @@ int temp_gru_chain_bwd_g4(const TempGruChain* c, const float* saved, int n_up, c
   return TEMP_E_UNSUPPORTED;
 }
 
+int temp_gru_chain_pack_layout(int d) { return d > 0 ? chain_pack_layout(d) : 0; }
+
 int temp_gru_chain_keys_supported(int d) { return d > 0 && chain_hx(d) ? 1 : 0; }
 
 int temp_gru_chain_bwd_g4_keys(const TempGruChain* c, const float* saved, int n_up, const float* const* up, float* g4, uint32_t* row_keys,
@@ -908,7 +1011,7 @@ int temp_gru_chain_bwd_g4_keys(const TempGruChain* c, const float* saved, int n_
   int rc = chain_check(c);
   if (rc) return rc;
   if (n_up < 0 || n_up > TEMP_CHAIN_MAX_UP || (n_up > 0 && !up)) return TEMP_E_BADARG;
-  if (c->variant != TEMP_GRU_TORCH || !chain_hx(c->d)) return TEMP_E_UNSUPPORTED;
+  if (c->variant != TEMP_GRU_TORCH || !layout_hx(c->pack_layout)) return TEMP_E_UNSUPPORTED;
   if (c->n_panels == 0) return TEMP_OK;
   if (!saved || !g4) return TEMP_E_BADARG;
   const ChainArgs a = chain_args(c);

@@ -265,6 +265,315 @@ __global__ void __launch_bounds__(64 * (NMW + MW)) k_gru_chain_fwd_hx(ChainArgs 
   }
 }
 
+// ---- forward with the input gates computed inside (nn.GRU gate layout) -----------------------------------------------
+// k_gru_chain_fwd_hx reads gi = x . W_ih^T + b_ih, written by a GEMM launch of its own, once per row and position (2 400 bytes
+// at d = 200).  This kernel takes the chain's x rows instead (800 bytes) and runs x . W_ih on its matrix waves in the window where
+// they used to wait for the gates of the previous position:
+//   after barrier A of position s   x(s+1) . W_ih  -> acc           (the x planes of s+1 were written before A by the memory waves)
+//   before barrier B                acc . 2^14 / (row scale): the units of the recurrent product (W_ih and W_hh share their column
+//                                   scales, see below; exact: a power of two)
+//   after barrier B                 n columns -> gin (LDS) and out of acc; acc += h(s+1) . W_hh on the r / z / n columns: the r and z
+//                                   columns are one K-concatenated sum [x | h] . [W_ih | W_hh], n keeps gi_n apart (n = tanh(gi_n +
+//                                   b_in + r (gh_n + b_hn)))
+//   before barrier A of s+1         acc -> accb, as in k_gru_chain_fwd_hx
+// The decay of the previous state moves INTO the state planes (the memory wave writes dec(s+1) . h(s), or zeros when the row of
+// s+1 has no previous state), because the product now also carries gi.  The fp32 state lives in the memory waves' registers (a
+// lane owns the same columns of the same tracks throughout), which, with 800 instead of 2 400 bytes of prefetch per row, frees
+// the LDS for the x planes and gin.
+// W_ih arrives like W_hh, as two f16 planes, and both are scaled per column by the power of two of the JOINT column maximum
+// max(|W_hh[c]|, |W_ih[c]|) (temp_gru_chain_pack_x_multi; kf holds those keys); the x planes carry a scale per row (split_f16.hpp,
+// from the row maximum, which the memory wave holding the row takes with one DPP reduction).
+struct ChainX {
+  const float* x;                            // [x rows][d]
+  const int32_t* x_index;                    // [N_total] x row of chain row i
+  const float* b_ih[TEMP_CHAIN_MAX_RNN];
+  const hx_u32x4* wi[TEMP_CHAIN_MAX_RNN];    // W_ih planes (the forward layout of W_hh's, scaled by the joint keys kf)
+};
+inline size_t chain_lds_fwd_x(int D, int ms) {
+  const ChainGeomHx g = chain_geom_hx(D);
+  return (size_t)CH_SLOTS * (3 * D + 4) * 4 + 4 * (size_t)CH_SLOTS * g.ldp + (size_t)CH_SLOTS * (D + 4) * 4 + CH_SLOTS * 4 + (2 * CH_SLOTS + 1) * (size_t)ms * 4;
+}
+// NMW matrix waves with TPW tiles each (NMW * TPW >= NT), MW memory waves; one register set of weight planes (two matrix waves
+// per SIMD cover each other's L2 latency)
+template <int TPW, int MW, int NMW>
+__global__ void __launch_bounds__(64 * (NMW + MW)) k_gru_chain_fwd_x(ChainArgs a, ChainX X, float* __restrict__ H, float* __restrict__ saved) {
+  extern __shared__ __attribute__((aligned(16))) float lds[];
+  constexpr int PASSES = CH_SLOTS / MW;
+  const int D = a.D, D4 = D >> 2, G3 = 3 * D;
+  const ChainGeomHx g = chain_geom_hx(D);
+  const int NT = g.NT, NS = g.NS, ldp = g.ldp;
+  const int lda = G3 + 4, ldn = D + 4;                           // (odd numbers of 16-byte units: d % 8 == 0)
+  float* accb = lds;                                             // [32][lda]  products of the position: [x | h] . [W_ih | W_hh] (r, z), h . W_hh (n)
+  char* hpl = (char*)(accb + CH_SLOTS * lda);                    // [2 planes][32][ldp bytes]  the decayed previous state, split
+  char* xpl = hpl + 2 * CH_SLOTS * ldp;                          // [2 planes][32][ldp bytes]  x of the NEXT position, split
+  float* gin = (float*)(xpl + 2 * CH_SLOTS * ldp);               // [32][ldn]  gi_n (without b_in, in the product's units) of the position
+  unsigned* xkey = (unsigned*)(gin + CH_SLOTS * ldn);            // [32] row keys of the x planes
+  int* tabb = (int*)(xkey + CH_SLOTS);                           // [ms][32] the panel's row table
+  float* decb = (float*)(tabb + CH_SLOTS * a.max_steps);         // [ms][32] decay factor of every row
+  int* flagb = (int*)(decb + CH_SLOTS * a.max_steps);            // [ms] step flags
+  const int tid = threadIdx.x, wave = __builtin_amdgcn_readfirstlane(tid >> 6), lane = tid & 63;
+  const size_t plane = a.plane;
+
+  // (each role runs its own panel loop: the loop invariants of one role are not hoisted above the role branch next to the
+  //  other's, where both sets would be live at once)
+  if (wave < NMW) {
+  for (int p = blockIdx.x; p < a.n_panels; p += gridDim.x) {
+    const int rnn_id = a.panel[4 * p], s0 = a.panel[4 * p + 1], ns = a.panel[4 * p + 2];
+    const ChainRnn R = a.rnn[rnn_id];
+    for (int i = tid; i < 4 * CH_SLOTS * ldp / 16; i += blockDim.x) reinterpret_cast<hx_u32x4*>(hpl)[i] = hx_u32x4{0u, 0u, 0u, 0u};   // (k padding)
+    for (int i = tid; i < ns * CH_SLOTS; i += blockDim.x) {
+      const int e = a.rows[(size_t)s0 * CH_SLOTS + i];
+      tabb[i] = e;
+      decb[i] = e >= 0 ? expf(-a.dt[e & CH_ROW_MASK] * a.lambda) : 0.f;
+    }
+    if (tid < ns) flagb[tid] = a.sinfo[4 * (size_t)(s0 + tid)];
+    __syncthreads();
+
+      // ------------------------------------------------------------------ matrix role
+      const int li = lane & 31, hh = lane >> 5;
+      bool tval[TPW];
+      int tidx[TPW];
+#pragma unroll
+      for (int j = 0; j < TPW; ++j) { tidx[j] = wave + NMW * j; tval[j] = tidx[j] < NT; if (!tval[j]) tidx[j] = NT - 1; }
+      f32x16 acc[TPW];
+#pragma unroll
+      for (int j = 0; j < TPW; ++j)
+#pragma unroll
+        for (int r = 0; r < 16; ++r) acc[j][r] = 0.f;
+      const hx_u32x4* wph = reinterpret_cast<const hx_u32x4*>(R.wf);
+      const hx_u32x4* wpi = X.wi[rnn_id];
+      hx_u32x4 w[2][TPW] = {};                                   // [plane h, l][tile]: one slab of the stream being walked
+      const std::integral_constant<int, 0> P0;
+      const std::integral_constant<int, 1> P1;
+      auto wload = [&](const hx_u32x4* wp, int sl, auto pl_c) __attribute__((always_inline)) {
+        constexpr int pl = decltype(pl_c)::value;
+#pragma unroll
+        for (int j = 0; j < TPW; ++j)
+          if (tval[j]) w[pl][j] = *reinterpret_cast<const hx_u32x4*>(reinterpret_cast<const char*>(wp) + (unsigned)((((sl * NT + tidx[j]) * 2 + pl) * 64 + lane) * 16));
+      };
+      const int rot = (a.dbg & 64) ? 0 : (int)(blockIdx.x >> 3) % NS;
+      auto at = [&](int j) { const int v = rot + j; return v < NS ? v : v - NS; };
+      // the walks issue ahead of the memory waves' gate arithmetic on the same SIMD (dbg bit 12: development A/B, equal priority)
+      const bool prio = !(a.dbg & 4096);
+      // a walk over the NS slabs of one stream (wcur) with the fragments of `pl0` (the state or the x planes); behind its last slab
+      // the registers are refilled with the first slab of the stream walked next (wnext)
+      bool holds_ih = true;
+      wload(wpi, rot, P0); wload(wpi, rot, P1);
+      // prod = false (development probe, dbg bits 0 / 11): the weights stream, no products issue
+      auto walk = [&](const bool prod, const char* pl0, const hx_u32x4* wcur, const hx_u32x4* wnext) __attribute__((always_inline)) {
+        const char* arow = pl0 + (size_t)li * ldp + 16 * hh;
+        const int pl1 = CH_SLOTS * ldp;
+        hx_u32x4 FH = *reinterpret_cast<const hx_u32x4*>(arow + 32 * rot), FL = *reinterpret_cast<const hx_u32x4*>(arow + pl1 + 32 * rot), NH, NL;
+        if (prio) __builtin_amdgcn_s_setprio(2);
+        for (int j = 0; j < NS; ++j) {
+          const bool last = j + 1 == NS;
+          const int sn = at(last ? 0 : j + 1);
+          const hx_u32x4* wn = last ? wnext : wcur;
+          NH = *reinterpret_cast<const hx_u32x4*>(arow + 32 * sn);
+          NL = *reinterpret_cast<const hx_u32x4*>(arow + pl1 + 32 * sn);
+          const hx_f16x8 ah = hx_frag(FH), al = hx_frag(FL);
+          __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+          for (int t = 0; t < TPW; ++t) {
+            if (prod) acc[t] = __builtin_amdgcn_mfma_f32_32x32x16_f16(hx_frag(w[1][t]), ah, acc[t], 0, 0, 0);
+            else asm volatile("" : : "v"(w[1][t]));
+          }
+          __builtin_amdgcn_sched_barrier(0);
+          wload(wn, sn, P1);
+          __builtin_amdgcn_sched_barrier(0);
+          if (prod) {
+#pragma unroll
+            for (int t = 0; t < TPW; ++t) acc[t] = __builtin_amdgcn_mfma_f32_32x32x16_f16(hx_frag(w[0][t]), al, acc[t], 0, 0, 0);
+#pragma unroll
+            for (int t = 0; t < TPW; ++t) acc[t] = __builtin_amdgcn_mfma_f32_32x32x16_f16(hx_frag(w[0][t]), ah, acc[t], 0, 0, 0);
+          } else {
+#pragma unroll
+            for (int t = 0; t < TPW; ++t) asm volatile("" : : "v"(w[0][t]));
+          }
+          __builtin_amdgcn_sched_barrier(0);
+          wload(wn, sn, P0);
+          FH = NH; FL = NL;
+        }
+        if (prio) __builtin_amdgcn_s_setprio(0);
+      };
+      // x . W_ih of the next position into acc, then into the units the rest of the position expects
+      auto xprod = [&]() __attribute__((always_inline)) {
+        if (!holds_ih) { wload(wpi, rot, P0); wload(wpi, rot, P1); }
+        walk(!(a.dbg & (1 | 2048)), xpl, wpi, wph);
+        holds_ih = false;
+        const float f = hx_inv_scale(xkey[li]) * CHX_STATE_SCALE;       // (x . s_row) -> (x . 2^14): the units of the state's planes
+#pragma unroll
+        for (int j = 0; j < TPW; ++j)
+#pragma unroll
+          for (int r = 0; r < 16; ++r) acc[j][r] *= f;
+      };
+      if (ns > 0) {
+        __syncthreads();      // P: the x planes of position 0 are in LDS
+        xprod();
+        __syncthreads();      // Q
+      }
+      for (int s = 0; s < ns; ++s) {
+        const int flags = flagb[s];
+        // gi_n of position s -> gin, out of the accumulators
+#pragma unroll
+        for (int j = 0; j < TPW; ++j) {
+          if (!tval[j]) continue;
+#pragma unroll
+          for (int qq = 0; qq < 4; ++qq) {
+            const int c = tidx[j] * 32 + 8 * qq + 4 * hh;
+            if (c < 2 * D || c >= G3) continue;
+            st4(gin + (size_t)li * ldn + (c - 2 * D), make_float4(acc[j][4 * qq], acc[j][4 * qq + 1], acc[j][4 * qq + 2], acc[j][4 * qq + 3]));
+            acc[j][4 * qq] = 0.f; acc[j][4 * qq + 1] = 0.f; acc[j][4 * qq + 2] = 0.f; acc[j][4 * qq + 3] = 0.f;
+          }
+        }
+        if ((flags & 1) && !(a.dbg & 1)) {
+          if (holds_ih) { wload(wph, rot, P0); wload(wph, rot, P1); }
+          walk(true, hpl, wph, wpi);
+          holds_ih = true;
+        }
+        // lane (li, hh) owns track li and, per register quad qq, gate columns tile*32 + 8qq + 4hh .. +3
+#pragma unroll
+        for (int j = 0; j < TPW; ++j) {
+          if (!tval[j]) continue;
+          float* dst = accb + (size_t)li * lda + tidx[j] * 32 + 4 * hh;
+#pragma unroll
+          for (int qq = 0; qq < 4; ++qq) {
+            if (tidx[j] * 32 + 8 * qq + 4 * hh < G3) st4(dst + 8 * qq, make_float4(acc[j][4 * qq], acc[j][4 * qq + 1], acc[j][4 * qq + 2], acc[j][4 * qq + 3]));
+            acc[j][4 * qq] = 0.f; acc[j][4 * qq + 1] = 0.f; acc[j][4 * qq + 2] = 0.f; acc[j][4 * qq + 3] = 0.f;
+          }
+        }
+        __syncthreads();      // A: products of position s (and gin) are in LDS; the x planes of s + 1 too
+        if (s + 1 < ns) xprod();
+        __syncthreads();      // B: the split (decayed) state of position s is in LDS
+      }
+    __syncthreads();          // LDS is re-initialised for the next panel
+  }
+  } else {
+  for (int p = blockIdx.x; p < a.n_panels; p += gridDim.x) {
+    const int rnn_id = a.panel[4 * p], s0 = a.panel[4 * p + 1], ns = a.panel[4 * p + 2];
+    const ChainRnn R = a.rnn[rnn_id];
+    for (int i = tid; i < 4 * CH_SLOTS * ldp / 16; i += blockDim.x) reinterpret_cast<hx_u32x4*>(hpl)[i] = hx_u32x4{0u, 0u, 0u, 0u};   // (k padding)
+    for (int i = tid; i < ns * CH_SLOTS; i += blockDim.x) {
+      const int e = a.rows[(size_t)s0 * CH_SLOTS + i];
+      tabb[i] = e;
+      decb[i] = e >= 0 ? expf(-a.dt[e & CH_ROW_MASK] * a.lambda) : 0.f;
+    }
+    if (tid < ns) flagb[tid] = a.sinfo[4 * (size_t)(s0 + tid)];
+    __syncthreads();
+
+      // ------------------------------------------------------------------ memory role
+      const int mw = wave - NMW, c4 = lane, col = 4 * c4;
+      const bool cact = c4 < D4;
+      const int colc = cact ? col : 0;
+      const float* bih = X.b_ih[rnn_id];
+      const float4 br = add4(ld4(bih + colc), ld4(R.b_hh + colc)), bz = add4(ld4(bih + D + colc), ld4(R.b_hh + D + colc));
+      const float4 bhn = ld4(R.b_hh + 2 * D + colc), bin = ld4(bih + 2 * D + colc);
+      float4 ivr, ivz, ivn;                                      // 1 / (column scale . state scale)
+      {
+        const hx_u32x4 kr = *reinterpret_cast<const hx_u32x4*>(R.kf + colc), kz = *reinterpret_cast<const hx_u32x4*>(R.kf + D + colc);
+        const hx_u32x4 kn = *reinterpret_cast<const hx_u32x4*>(R.kf + 2 * D + colc);
+        auto iv = [](const hx_u32x4 k) { return make_float4(hx_inv_scale(k[0]) * CHX_STATE_INV, hx_inv_scale(k[1]) * CHX_STATE_INV,
+                                                            hx_inv_scale(k[2]) * CHX_STATE_INV, hx_inv_scale(k[3]) * CHX_STATE_INV); };
+        ivr = iv(kr); ivz = iv(kz); ivn = iv(kn);
+      }
+      float4 hdr[PASSES];                                        // dec(s + 1) . h(s) of this lane's columns of its tracks (the fp32 state)
+      float4 xr[PASSES];                                         // x rows of a coming position
+#pragma unroll
+      for (int ps = 0; ps < PASSES; ++ps) hdr[ps] = zero4();
+      auto xload = [&](int s) __attribute__((always_inline)) {
+#pragma unroll
+        for (int ps = 0; ps < PASSES; ++ps) {
+          const int e = tabb[s * CH_SLOTS + ps * MW + mw];
+          const bool ok = e >= 0 && cact && !(a.dbg & 4);       // (dbg bit 2: development ablation, no x loads)
+          const size_t xrow = ok ? (size_t)X.x_index[e & CH_ROW_MASK] : 0;
+          xr[ps] = ok ? ld4(X.x + xrow * D + col) : zero4();
+        }
+      };
+      // the loaded rows -> the x planes (scaled per row) and their keys
+      auto xsplit = [&]() __attribute__((always_inline)) {
+#pragma unroll
+        for (int ps = 0; ps < PASSES; ++ps) {
+          const int slot = ps * MW + mw;
+          const unsigned key = hx_wave_max(cact ? hx_abs_bits4(xr[ps]) : 0u);
+          if (cact) {
+            hx_u32x2 SH, SL;
+            hx_split4(xr[ps], hx_scale(key), SH, SL);
+            char* xd = xpl + (size_t)slot * ldp + 2 * col;
+            *reinterpret_cast<hx_u32x2*>(xd) = SH;
+            *reinterpret_cast<hx_u32x2*>(xd + CH_SLOTS * ldp) = SL;
+          }
+          if (lane == 0) xkey[slot] = key;
+        }
+      };
+      if (ns > 0) {
+        xload(0);
+        xsplit();
+        __syncthreads();      // P
+        if (ns > 1) xload(1);
+        __syncthreads();      // Q
+      }
+      for (int s = 0; s < ns; ++s) {
+        const int flags = flagb[s];
+        if (s + 1 < ns) xsplit();                                // x(s + 1) for the matrix waves' window behind A
+        __syncthreads();      // A
+        if (s + 2 < ns) xload(s + 2);                            // in flight during the gates of s
+#pragma unroll
+        for (int ps = 0; ps < PASSES; ++ps) {
+          const int slot = ps * MW + mw;
+          const int e = tabb[s * CH_SLOTS + slot];
+          if (!cact) continue;
+          int en = -1;
+          if (s + 1 < ns) en = tabb[(s + 1) * CH_SLOTS + slot];
+          const bool hpn = en >= 0 && (en & CH_HAS_PREV);
+          float4 h4 = zero4();
+          if (e >= 0) {
+            const size_t row = (size_t)(e & CH_ROW_MASK);
+            const bool hp = (e & CH_HAS_PREV) != 0;
+            const float* ab = accb + (size_t)slot * lda + col;
+            const float4 pr = ld4(ab), pz = ld4(ab + D), pn = ld4(ab + 2 * D), gn = ld4(gin + (size_t)slot * ldn + col);
+            const float4 hd = hp ? hdr[ps] : zero4();
+            float o_h[4], o_r[4], o_z[4], o_n[4], o_hn[4];
+            const float prv[4] = {pr.x, pr.y, pr.z, pr.w}, pzv[4] = {pz.x, pz.y, pz.z, pz.w}, pnv[4] = {pn.x, pn.y, pn.z, pn.w};
+            const float ivrv[4] = {ivr.x, ivr.y, ivr.z, ivr.w}, ivzv[4] = {ivz.x, ivz.y, ivz.z, ivz.w}, ivnv[4] = {ivn.x, ivn.y, ivn.z, ivn.w};
+            const float gnv[4] = {gn.x, gn.y, gn.z, gn.w}, hdv[4] = {hd.x, hd.y, hd.z, hd.w};
+            const float brv[4] = {br.x, br.y, br.z, br.w}, bzv[4] = {bz.x, bz.y, bz.z, bz.w}, bnv[4] = {bhn.x, bhn.y, bhn.z, bhn.w};
+            const float binv[4] = {bin.x, bin.y, bin.z, bin.w};
+#pragma unroll
+            for (int k = 0; k < 4; ++k) {
+              const float rg = gate_sigmoid(prv[k] * ivrv[k] + brv[k]);
+              const float zg = gate_sigmoid(pzv[k] * ivzv[k] + bzv[k]);
+              const float hn = pnv[k] * ivnv[k] + bnv[k];
+              const float ng = gate_tanh((gnv[k] * ivnv[k] + binv[k]) + rg * hn);
+              o_h[k] = (1.f - zg) * ng + zg * hdv[k];
+              o_r[k] = rg; o_z[k] = zg; o_n[k] = ng; o_hn[k] = hn;
+            }
+            h4 = make_float4(o_h[0], o_h[1], o_h[2], o_h[3]);
+            const size_t o = row * D + col;
+            if (!(a.dbg & 2)) {                                  // (development ablation: no global stores)
+              if (flags & 2) st4(H + o, h4);
+              st4(saved + o, make_float4(o_r[0], o_r[1], o_r[2], o_r[3]));
+              st4(saved + plane + o, make_float4(o_z[0], o_z[1], o_z[2], o_z[3]));
+              st4(saved + 2 * plane + o, make_float4(o_n[0], o_n[1], o_n[2], o_n[3]));
+              st4(saved + 3 * plane + o, make_float4(o_hn[0], o_hn[1], o_hn[2], o_hn[3]));
+              st4(saved + 4 * plane + o, hd);
+            }
+          }
+          if (s + 1 < ns) {                                      // the state the next position's product reads: decayed, or 0
+            hdr[ps] = hpn ? scale4(h4, decb[(s + 1) * CH_SLOTS + slot]) : zero4();
+            hx_u32x2 SH, SL;
+            hx_split4(hdr[ps], CHX_STATE_SCALE, SH, SL);
+            char* hdst = hpl + (size_t)slot * ldp + 2 * col;
+            *reinterpret_cast<hx_u32x2*>(hdst) = SH;
+            *reinterpret_cast<hx_u32x2*>(hdst + CH_SLOTS * ldp) = SL;
+          }
+        }
+        __syncthreads();      // B
+      }
+    __syncthreads();          // LDS is re-initialised for the next panel
+  }
+  }
+}
+
 // ---- backward -------------------------------------------------------------------------------------------------------
 // row_keys (nullable): [N_total] key of max |[dr dz dn_i]| of every row; col_keys (nullable): [n_rnn + n_panels][4d]: the kernel writes row
 // n_rnn + p (panel p's column maxima), k_keys_reduce (hx_pack.hpp) reduces them into rows 0 .. n_rnn - 1

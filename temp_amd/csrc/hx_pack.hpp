@@ -13,7 +13,9 @@
 namespace temp {
 
 #define HX_PACK_JOBS 8
-struct HxPackJob { const float* B; hx_u32x4* out; unsigned* keys; int K, N, n_tiles, n_slabs, ldb, trans, unit0, kblock0; };
+// B2 / out2 (nullable, hx_pack_jobs_add_joint): a second matrix of B's shape and layout, packed with the keys of the JOINT column
+// maxima of B and B2 (both products then share their column scales: temp_gru_chain_pack_x_multi)
+struct HxPackJob { const float* B; hx_u32x4* out; unsigned* keys; int K, N, n_tiles, n_slabs, ldb, trans, unit0, kblock0; const float* B2; hx_u32x4* out2; };
 struct HxPackJobs { HxPackJob j[HX_PACK_JOBS]; int count, total_units, total_kblocks; };
 
 inline size_t hx_packed_items(int N, int K) { return (size_t)ceil_div(K, 16) * ceil_div(N, 32) * 128; }   // 16-byte items
@@ -25,6 +27,11 @@ inline void hx_pack_jobs_add(HxPackJobs& jobs, const float* B, hx_u32x4* out, un
   j.unit0 = jobs.total_units; j.kblock0 = jobs.total_kblocks;
   jobs.total_units += j.n_tiles * j.n_slabs;
   jobs.total_kblocks += j.n_tiles;
+}
+
+inline void hx_pack_jobs_add_joint(HxPackJobs& jobs, const float* B, hx_u32x4* out, const float* B2, hx_u32x4* out2, unsigned* keys, int K, int N, int ldb, int trans) {
+  hx_pack_jobs_add(jobs, B, out, keys, K, N, ldb, trans);
+  jobs.j[jobs.count - 1].B2 = B2; jobs.j[jobs.count - 1].out2 = out2;
 }
 
 __device__ __forceinline__ const HxPackJob& hx_job_of(const HxPackJobs& jobs, int idx, bool by_kblock, int& local) {
@@ -45,9 +52,10 @@ static __global__ void __launch_bounds__(1024) k_hx_keys_pack(HxPackJobs jobs) {
   int t;
   const HxPackJob& jb = hx_job_of(jobs, blockIdx.x, true, t);
   const int K = jb.K, N = jb.N, ldb = jb.ldb;
-  const float* __restrict__ B = jb.B;
   unsigned key = 0;
   int c, g;
+  for (int m = 0; m < (jb.B2 ? 2 : 1); ++m) {
+  const float* __restrict__ B = m ? jb.B2 : jb.B;
   if (jb.trans) {
     c = threadIdx.x >> 5; g = threadIdx.x & 31;
     const int n = 32 * t + c;
@@ -79,6 +87,7 @@ static __global__ void __launch_bounds__(1024) k_hx_keys_pack(HxPackJobs jobs) {
       }
     }
   }
+  }
   sm[g][c] = key;
   __syncthreads();
   if (threadIdx.x < 32) {
@@ -92,6 +101,8 @@ static __global__ void __launch_bounds__(1024) k_hx_keys_pack(HxPackJobs jobs) {
   const int lane = threadIdx.x & 63, hh = lane >> 5, li = lane & 31, wave = threadIdx.x >> 6;
   const int n = 32 * t + li;
   const float sc = scale_l[li];
+  for (int m = 0; m < (jb.B2 ? 2 : 1); ++m) {
+  const float* __restrict__ B = m ? jb.B2 : jb.B;
   for (int s0 = wave; s0 < jb.n_slabs; s0 += 16) {
     const int k = 16 * s0 + 8 * hh;
     float4 v0 = zero4(), v1 = zero4();
@@ -110,8 +121,9 @@ static __global__ void __launch_bounds__(1024) k_hx_keys_pack(HxPackJobs jobs) {
     }
     hx_u32x4 H, L;
     hx_split8(v0, v1, sc, H, L);
-    hx_u32x4* d = jb.out + ((size_t)s0 * jb.n_tiles + t) * 128 + lane;
+    hx_u32x4* d = (m ? jb.out2 : jb.out) + ((size_t)s0 * jb.n_tiles + t) * 128 + lane;
     d[0] = H; d[64] = L;
+  }
   }
 }
 

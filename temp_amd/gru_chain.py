@@ -24,6 +24,7 @@ CHAIN_KERNELS = True        # A/B switch: False keeps the per-position launches 
 WEIGHT_GRADS_MULTI = True   # A/B switch: False computes each GRU's weight gradients with its own launches (temp_gru_weight_grads)
 KEYED_GRADS = True          # A/B switch: False keeps the consumers of g4 on the six-product bf16 split (no keys from the chain backward)
 GATE_GRADS_ONCE = True      # A/B switch: False keeps dgi + dgh as two matrices (temp_gru_chain_bwd + temp_gru_weight_grads_multi)
+FUSED_INPUT_GATES = True    # A/B switch: False keeps the gate GEMM + gi route where temp_gru_chain_fwd_x applies (so does TEMP_DEBUG bit 22)
 
 
 class GruInstance:
@@ -253,6 +254,16 @@ class GruProgram:
         self._gi_shared = (str(device), res)
         return res
 
+    def x_index(self, device):
+        """int32 device table [n_total]: the x row of every chain row (instance i maps rows h0 .. h0 + n to x0 .. x0 + n).  Cached."""
+        c = getattr(self, "_x_index", None)
+        if c is None or c[0] != str(device):
+            idx = np.zeros(self.n_total, dtype=np.int32)
+            for it in self.inst:
+                idx[it.h0:it.h0 + it.n] = it.x0 + np.arange(it.n, dtype=np.int32)
+            c = self._x_index = (str(device), _lib.to_device(idx, device))
+        return c[1]
+
     def constants(self, device, d):
         """(zero previous-state row, all -1 row map long enough for any first-position instance), created once per program."""
         key = (str(device), int(d))
@@ -300,13 +311,19 @@ class _GruChainFn(torch.autograd.Function):
         tabs = None
         if CHAIN_KERNELS and hasattr(be, "gru_chain_fwd") and n_rnn <= _lib.CHAIN_MAX_RNN and be.gru_chain_supported(d):
             tabs = prog.chain_tables(dev, want)
-        share = prog.gi_shared(dev) if tabs is not None else None        # gates once per distinct x row (chain kernels only)
+        # nn.GRU cells on the f16 route: the chain forward computes the input gates itself from the x rows (temp_gru_chain_fwd_x) --
+        # no gi, no gate GEMM.  (Independent of x_src: a labelled and an unlabelled program take the same kernel.)
+        fused = bool(tabs is not None and FUSED_INPUT_GATES and variant == _lib.GRU_TORCH and hasattr(be, "gru_chain_fwd_x")
+                     and be.gru_chain_fwd_x_supported(d, variant, tabs["max_steps"]))
+        share = prog.gi_shared(dev) if (tabs is not None and not fused) else None        # gates once per distinct x row (chain kernels only)
         # x_keys = (row keys [x rows], column keys [d]) of x_all from its producer (functional.gather_rows(keys=True)): the input-gate
         # product and the weight gradients then run on the f16 pipe without a pass over x of their own
         ctx.x_keys = x_keys if (x_keys is not None and tabs is not None) else None
         gk = (lambda: dict(x_keys=[ctx.x_keys[0][g["x0"]:g["x1"]] for g in prog.groups])) if ctx.x_keys is not None else dict
         gi_index = None
-        if share is not None:
+        if fused:
+            gi = None
+        elif share is not None:
             gi_index = share["gi_index"]
             gi = torch.empty(share["rows"], G, dtype=torch.float32, device=dev)
             cut = share["g0"] + [share["rows"]]
@@ -315,7 +332,7 @@ class _GruChainFn(torch.autograd.Function):
                                      x_idx=share["rep"], **gk())
         else:
             gi = torch.empty(N, G, dtype=torch.float32, device=dev)
-        if share is not None:
+        if share is not None or fused:
             pass
         elif len(prog.groups) > 1 and hasattr(be, "gru_input_gates_multi"):    # both directions' input gates in one launch
             be.gru_input_gates_multi([x_all[g["x0"]:g["x1"]] for g in prog.groups], [W[g["rnn"]][0] for g in prog.groups],
@@ -327,7 +344,11 @@ class _GruChainFn(torch.autograd.Function):
         H = torch.empty(N, d, dtype=torch.float32, device=dev)
         saved = torch.empty(5, N, d, dtype=torch.float32, device=dev)
         packs = None
-        if tabs is not None:
+        if fused:
+            packs = be.gru_chain_pack_x_multi([W[r][1] for r in range(n_rnn)], [W[r][0] for r in range(n_rnn)])
+            be.gru_chain_fwd_x(tabs, x_all, prog.x_index(dev), lam, variant, packs, [W[r][3] for r in range(n_rnn)], [W[r][2] for r in range(n_rnn)],
+                               H, saved)
+        elif tabs is not None:
             packs = be.gru_chain_pack_multi([W[r][1] for r in range(n_rnn)]) if hasattr(be, "gru_chain_pack_multi") else \
                 [be.gru_chain_pack(W[r][1]) for r in range(n_rnn)]
             be.gru_chain_fwd(tabs, gi, lam, variant, packs, [W[r][3] for r in range(n_rnn)], H, saved, gi_index=gi_index)
@@ -474,6 +495,7 @@ def prepare_program(prog, device, d, n_rnn, want):
     if chain_kernels_usable(d, n_rnn) and prog.chain_tables(device, tuple(want) if want is not None else None) is not None:
         _lib.pause_point()
         prog.gi_shared(device)
+        prog.x_index(device)
         return
     prog.upload(device)
 
