@@ -601,6 +601,44 @@ int temp_bilinear_query_bwd(int P, int d, int kind, const float* ent_rows, const
                             const int32_t* is_tail, const float* d_q, float* d_known_rows, float* d_rel_rows, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * Gated loss of the post-aggregation models (PostDynamicRGCN / PostBiDynamicRGCN.train_link_prediction,
+ * models/PostDynamicRGCN.py:261-282): the known entity and the candidates are per-triple mixes w * local + (1 - w) * temporal
+ * of the two embedding streams.  Both scorers are linear in the candidate, so the candidate mix is taken on the two score
+ * matrices s_a = q . all_loc^T and s_b = q . all_rec^T (temp_linear_multi) at the candidate columns only.
+ *
+ * Gated folded query (the fold of temp_bilinear_query_fwd on a mixed known row; A, B, rel [*, d] row-major):
+ *   known[p] = w[p] * A[ia[p]] + (1 - w[p]) * B[ib[p]]          when ia[p] >= 0
+ *   known[p] = B[ib[p]]  (exactly; w[p] is not read)            when ia[p] <  0   -- TEMPORAL-ONLY row: the reference's head rows,
+ *            whose "local" known object is the temporal row too (models/PostDynamicRGCN.py:276-277), so w[p] has no effect
+ *   q[p]     = fold(known[p], rel[rel_idx[p]]) for kind / is_tail as in temp_bilinear_query_fwd.
+ *   bwd (d_k = the gradient of known[p] from d_q[p]):
+ *     d_a_rows[p] = w[p] d_k, d_b_rows[p] = (1 - w[p]) d_k, d_w[p] = <d_k, A[ia[p]] - B[ib[p]]>     (ia[p] >= 0)
+ *     d_a_rows[p] = 0,        d_b_rows[p] = d_k,            d_w[p] = 0                            (ia[p] <  0)
+ *     d_rel_rows[p] = the relation row's gradient.  All outputs fully written ([P, d] and [P]); the caller sums the rows over the
+ *     index lists (temp_segment_sum_rows; ia's negative entries are left out of its segmentation).
+ *   d % 4 == 0 (complex: d % 8 == 0), else TEMP_E_UNSUPPORTED.  One wave per row; d_w is a wave reduction in fixed order.
+ *
+ * Gated candidate cross-entropy (label 0 over cand[P, C], column 0 = the true entity, entries in [0, N)):
+ *   m[p, e] = w[p] * s_a[p, e] + (1 - w[p]) * s_b[p, e]   (s_a, s_b [P, N]; formed at the candidate columns only)
+ *   fwd: loss_rows[p] = logsumexp_k m[p, cand[p,k]] - m[p, cand[p,0]];  lse_rows saved
+ *   bwd: G[p, e] = scale[0] * (row_scale ? row_scale[p] : inv_rows) * sum_k (softmax_k - [k == 0]) [cand[p,k] == e]
+ *        (duplicate candidates accumulate, as in temp_gather_ce_bwd);  d_s_a = w G, d_s_b = (1 - w) G  ([P, N] each, fully written,
+ *        zero off-candidate);  d_w[p] = sum_e G[p, e] (s_a - s_b)[p, e].  N * 4 bytes must fit the LDS (N <= 40704), else
+ *        TEMP_E_UNSUPPORTED.
+ * fp32; no floating-point atomics (candidate multiplicities are integer LDS counters) and no workspace: results are bit-repeatable.
+ * ---------------------------------------------------------------------------------------------- */
+int temp_gated_query_fwd(int P, int d, int kind, const float* A, const int32_t* ia, const float* B, const int32_t* ib, const float* w,
+                         const float* rel, const int32_t* rel_idx, const int32_t* is_tail, float* q, void* stream);
+int temp_gated_query_bwd(int P, int d, int kind, const float* A, const int32_t* ia, const float* B, const int32_t* ib, const float* w,
+                         const float* rel, const int32_t* rel_idx, const int32_t* is_tail, const float* d_q, float* d_a_rows, float* d_b_rows,
+                         float* d_rel_rows, float* d_w, void* stream);
+int temp_gather_ce_mix_fwd(int P, int C, int N, const float* s_a, const float* s_b, const float* w, const int32_t* cand, float* loss_rows,
+                           float* lse_rows, void* stream);
+int temp_gather_ce_mix_bwd(int P, int C, int N, const float* s_a, const float* s_b, const float* w, const int32_t* cand, const float* lse_rows,
+                           const float* scale, float inv_rows, const float* row_scale /* nullable [P] */, float* d_s_a, float* d_s_b,
+                           float* d_w, void* stream);
+
+/* ------------------------------------------------------------------------------------------------
  * Snapshot store (build_interpolation_graphs / get_train_val_test_graph_at_t keep one DGL graph per timestamp,
  * utils/dataset.py:151-232,268-305; dgl.batch rebuilds the union every call, models/DynamicRGCN.py:92).  Here every
  * snapshot's sorted / chunked edge views stay resident on the device; a batch's TempGraph arrays are assembled from them

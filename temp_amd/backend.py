@@ -614,6 +614,51 @@ class HipBackend:
         _lib.check(rc, "temp_bilinear_query_bwd")
         return dk, dr
 
+    def gated_query_fwd(self, kind, a_rows, a_idx, b_rows, b_idx, w, rel, rel_idx, is_tail):
+        """Folded query of the mixed known rows w * a_rows[a_idx] + (1 - w) * b_rows[b_idx] (a_idx < 0: b_rows[b_idx] alone)."""
+        a_rows, b_rows, w, rel = _f32(a_rows, "a_rows"), _f32(b_rows, "b_rows"), _f32(w, "w"), _f32(rel, "rel")
+        a_idx, b_idx, rel_idx, is_tail = _i32(a_idx, "a_idx"), _i32(b_idx, "b_idx"), _i32(rel_idx, "rel_idx"), _i32(is_tail, "is_tail")
+        P, d = b_idx.shape[0], b_rows.shape[1]
+        q = torch.empty(P, d, dtype=torch.float32, device=b_rows.device)
+        rc = self.lib.temp_gated_query_fwd(P, d, _lib.SCORE_KINDS[kind], _ptr(a_rows), _ptr(a_idx), _ptr(b_rows), _ptr(b_idx), _ptr(w), _ptr(rel),
+                                           _ptr(rel_idx), _ptr(is_tail), _ptr(q), _stream())
+        _lib.check(rc, "temp_gated_query_fwd")
+        return q
+
+    def gated_query_bwd(self, kind, a_rows, a_idx, b_rows, b_idx, w, rel, rel_idx, is_tail, d_q):
+        """-> per-row (d_a_rows, d_b_rows, d_rel_rows) [P, d] and d_w [P] (include/temp_amd.h: temp_gated_query_bwd)."""
+        a_rows, b_rows, w, rel, d_q = _f32(a_rows, "a_rows"), _f32(b_rows, "b_rows"), _f32(w, "w"), _f32(rel, "rel"), _f32(d_q, "d_q")
+        a_idx, b_idx, rel_idx, is_tail = _i32(a_idx, "a_idx"), _i32(b_idx, "b_idx"), _i32(rel_idx, "rel_idx"), _i32(is_tail, "is_tail")
+        P, d = b_idx.shape[0], b_rows.shape[1]
+        da, db, dr = (torch.empty(P, d, dtype=torch.float32, device=b_rows.device) for _ in range(3))
+        dw = torch.empty(P, dtype=torch.float32, device=b_rows.device)
+        rc = self.lib.temp_gated_query_bwd(P, d, _lib.SCORE_KINDS[kind], _ptr(a_rows), _ptr(a_idx), _ptr(b_rows), _ptr(b_idx), _ptr(w), _ptr(rel),
+                                           _ptr(rel_idx), _ptr(is_tail), _ptr(d_q), _ptr(da), _ptr(db), _ptr(dr), _ptr(dw), _stream())
+        _lib.check(rc, "temp_gated_query_bwd")
+        return da, db, dr, dw
+
+    def gather_ce_mix_fwd(self, s_a, s_b, w, cand):
+        """Candidate CE over the mixed scores w * s_a + (1 - w) * s_b (w [P]) -> (loss_rows, lse)."""
+        s_a, s_b, w, cand = _f32(s_a, "s_a"), _f32(s_b, "s_b"), _f32(w, "w"), _i32(cand, "cand")
+        P, N = s_a.shape
+        loss = torch.empty(P, dtype=torch.float32, device=s_a.device)
+        lse = torch.empty(P, dtype=torch.float32, device=s_a.device)
+        rc = self.lib.temp_gather_ce_mix_fwd(P, cand.shape[1], N, _ptr(s_a), _ptr(s_b), _ptr(w), _ptr(cand), _ptr(loss), _ptr(lse), _stream())
+        _lib.check(rc, "temp_gather_ce_mix_fwd")
+        return loss, lse
+
+    def gather_ce_mix_bwd(self, s_a, s_b, w, cand, lse, scale, inv_rows, row_scale=None):
+        """-> (d_s_a, d_s_b, d_w) of the mixed candidate CE (include/temp_amd.h: temp_gather_ce_mix_bwd)."""
+        s_a, s_b, w, cand, lse, scale = _f32(s_a, "s_a"), _f32(s_b, "s_b"), _f32(w, "w"), _i32(cand, "cand"), _f32(lse, "lse"), _f32(scale, "scale")
+        row_scale = _f32(row_scale, "row_scale")
+        P, N = s_a.shape
+        d_a, d_b = torch.empty_like(s_a), torch.empty_like(s_b)
+        d_w = torch.empty(P, dtype=torch.float32, device=s_a.device)
+        rc = self.lib.temp_gather_ce_mix_bwd(P, cand.shape[1], N, _ptr(s_a), _ptr(s_b), _ptr(w), _ptr(cand), _ptr(lse), _ptr(scale), float(inv_rows),
+                                             _ptr(row_scale), _ptr(d_a), _ptr(d_b), _ptr(d_w), _stream())
+        _lib.check(rc, "temp_gather_ce_mix_bwd")
+        return d_a, d_b, d_w
+
     def linear_tn(self, a, b, out=None):
         """a[M,Ka]^T . b[M,Nb] -> [Ka,Nb] (written into `out`, a contiguous (Ka, Nb) view, when given)."""
         a, b = _f32(a, "a"), _f32(b, "b")

@@ -406,6 +406,141 @@ def batched_ensemble_link_prediction(loc_rows, rec_rows, rel, big_loc, big_rec, 
                                                   w.reshape(-1, 1).to(loc_rows.dtype).contiguous(), kind, inputs)
 
 
+def _gated_query_fwd(be, kind, a_rows, a_idx, b_rows, b_idx, w, rel, rel_idx, is_tail):
+    if hasattr(be, "gated_query_fwd"):
+        return be.gated_query_fwd(kind, a_rows, a_idx, b_rows, b_idx, w, rel, rel_idx, is_tail)
+    # backends without the gated kernels (the CPU test backend): the mix in torch, the fold through bilinear_query
+    known = _gated_known(a_rows, a_idx, b_rows, b_idx, w)[0]
+    rows = torch.arange(known.shape[0], dtype=torch.int32, device=known.device)
+    return be.bilinear_query_fwd(kind, known, rows, rel, rel_idx, is_tail)
+
+
+def _gated_known(a_rows, a_idx, b_rows, b_idx, w):
+    gated = (a_idx >= 0).view(-1, 1)
+    b = b_rows[b_idx.long()]
+    a = a_rows[a_idx.long().clamp(min=0)]
+    wc = w.reshape(-1, 1)
+    return torch.where(gated, wc * a + (1 - wc) * b, b), a, b, gated
+
+
+def _gated_query_bwd(be, kind, a_rows, a_idx, b_rows, b_idx, w, rel, rel_idx, is_tail, d_q):
+    if hasattr(be, "gated_query_bwd"):
+        return be.gated_query_bwd(kind, a_rows, a_idx, b_rows, b_idx, w, rel, rel_idx, is_tail, d_q)
+    known, a, b, gated = _gated_known(a_rows, a_idx, b_rows, b_idx, w)
+    rows = torch.arange(known.shape[0], dtype=torch.int32, device=known.device)
+    dk, dr = be.bilinear_query_bwd(kind, known, rows, rel, rel_idx, is_tail, d_q)
+    wc = w.reshape(-1, 1)
+    zero = torch.zeros_like(dk)
+    return (torch.where(gated, wc * dk, zero), torch.where(gated, (1 - wc) * dk, dk), dr,
+            torch.where(gated, dk * (a - b), zero).sum(dim=1))
+
+
+def _gather_ce_mix_fwd(be, s_a, s_b, w, cand):
+    if hasattr(be, "gather_ce_mix_fwd"):
+        return be.gather_ce_mix_fwd(s_a, s_b, w, cand)
+    return be.gather_ce_fwd(torch.lerp(s_b, s_a, w.reshape(-1, 1)), cand)
+
+
+def _gather_ce_mix_bwd(be, s_a, s_b, w, cand, lse, scale, inv_rows, row_scale):
+    if hasattr(be, "gather_ce_mix_bwd"):
+        return be.gather_ce_mix_bwd(s_a, s_b, w, cand, lse, scale, inv_rows, row_scale)
+    wc = w.reshape(-1, 1)
+    g = be.gather_ce_bwd(torch.lerp(s_b, s_a, wc), cand, lse, scale, inv_rows, row_scale)
+    d_a = g * wc
+    return d_a, g - d_a, (g * (s_a - s_b)).sum(dim=1)
+
+
+class _BatchedGatedLinkPredictionFn(torch.autograd.Function):
+    """The embedding-level gated loss of the post-aggregation models (PostDynamicRGCN / PostBiDynamicRGCN.train_link_prediction,
+    models/PostDynamicRGCN.py:261-282) over ALL windows as one autograd node:
+        q      = fold(w_known * loc_rows[known_a] + (1 - w_known) * rec_rows[known], rel)      (temp_gated_query_fwd; known_a < 0:
+                                                                                             the temporal row alone -- the head rows)
+        s_a/b  = q[rows of window b] . big_loc_b^T / big_rec_b^T                             (temp_linear_multi, same q for both)
+        loss   = sum_rows w_row * CE(w_cand * s_a + (1 - w_cand) * s_b at cand, label 0)     (temp_gather_ce_mix_fwd)
+    The candidate mix is linear in the candidate, so it lives on the two score matrices; the backward is one mixed-CE pass (both
+    score gradients and d_w_cand), two d_q products, two d_big products, one gated-query pass and three deterministic segment sums."""
+
+    @staticmethod
+    def forward(ctx, loc_rows, rec_rows, rel, big_loc, big_rec, w_known, w_cand, kind, inp):
+        be = get_backend()
+        N = big_loc.shape[0] // len(inp["splits"])
+        live = [(b, a0, a1) for b, (a0, a1) in enumerate(inp["splits"]) if a1 > a0]
+        q = _gated_query_fwd(be, kind, loc_rows, inp["known_a"], rec_rows, inp["known"], w_known, rel, inp["rel"], inp["is_tail"])
+        sc = []
+        for big in (big_loc, big_rec):
+            s = torch.empty(q.shape[0], N, dtype=torch.float32, device=q.device)
+            be.linear_multi([q[a0:a1] for _, a0, a1 in live], [big[b * N:(b + 1) * N] for b, _, _ in live], True, s)
+            sc.append(s)
+        loss_rows, lse = _gather_ce_mix_fwd(be, sc[0], sc[1], w_cand, inp["cand"])
+        ctx.save_for_backward(loc_rows, rec_rows, rel, big_loc, big_rec, w_known, w_cand, q, sc[0], sc[1], lse)
+        ctx.kind, ctx.inp, ctx.live, ctx.N = kind, inp, live, N
+        return (loss_rows * inp["weights"]).sum()
+
+    @staticmethod
+    def backward(ctx, d_loss):
+        loc_rows, rec_rows, rel, big_loc, big_rec, w_known, w_cand, q, s_a, s_b, lse = ctx.saved_tensors
+        inp, live, N = ctx.inp, ctx.live, ctx.N
+        be = get_backend()
+        d_sa, d_sb, d_wc = _gather_ce_mix_bwd(be, s_a, s_b, w_cand, inp["cand"], lse, d_loss.reshape(1).contiguous(), 1.0, inp["weights"])
+        d_q = torch.empty_like(q)
+        d_q2 = torch.empty_like(q)
+        be.linear_multi([d_sa[a0:a1] for _, a0, a1 in live], [big_loc[b * N:(b + 1) * N] for b, _, _ in live], False, d_q)
+        be.linear_multi([d_sb[a0:a1] for _, a0, a1 in live], [big_rec[b * N:(b + 1) * N] for b, _, _ in live], False, d_q2)
+        d_q += d_q2
+        d_bigs = []
+        for big, d_s in ((big_loc, d_sa), (big_rec, d_sb)):
+            d_big = torch.empty_like(big) if len(live) == len(inp["splits"]) else torch.zeros_like(big)
+            if hasattr(be, "linear_tn_multi"):
+                be.linear_tn_multi([d_s[a0:a1] for _, a0, a1 in live], [q[a0:a1] for _, a0, a1 in live], [d_big[b * N:(b + 1) * N] for b, _, _ in live])
+            else:
+                for b, a0, a1 in live:
+                    be.linear_tn(d_s[a0:a1], q[a0:a1], out=d_big[b * N:(b + 1) * N])
+            d_bigs.append(d_big)
+        da, db, dr, d_wk = _gated_query_bwd(be, ctx.kind, loc_rows, inp["known_a"], rec_rows, inp["known"], w_known, rel, inp["rel"],
+                                            inp["is_tail"], d_q)
+        d_loc = be.segment_sum_rows(da, inp["known_a_inv"][0], inp["known_a_inv"][1], loc_rows.shape[0])
+        d_rec = be.segment_sum_rows(db, inp["known_inv"][0], inp["known_inv"][1], rec_rows.shape[0])
+        d_rel = be.segment_sum_rows(dr, inp["rel_inv"][0], inp["rel_inv"][1], rel.shape[0])
+        return (d_loc, d_rec, d_rel, d_bigs[0], d_bigs[1], d_wk.reshape(w_known.shape) if ctx.needs_input_grad[5] else None,
+                d_wc.reshape(w_cand.shape) if ctx.needs_input_grad[6] else None, None, None)
+
+
+def gated_loss_inputs(inp, n_loc_rows, device):
+    """The loss inputs of TKG_Module.loss_inputs (head rows NOT scored as tails) completed for the gated node: known_a = the row of
+    the LOCAL stream every query row mixes in -- the known subject's for tail rows, -1 (temporal only) for head rows, whose known
+    object is the temporal row alone in the reference (models/PostDynamicRGCN.py:276-277) -- and its segment-sum inverse."""
+    if inp is None:
+        return None
+    out = dict(inp)
+    ka = torch.where(inp["is_tail"] != 0, inp["known"], torch.full_like(inp["known"], -1)).contiguous()
+    out["known_a"] = ka
+    out["known_a_inv"] = gather_inverse(ka.cpu().numpy(), n_loc_rows, device)
+    return out
+
+
+def batched_gated_link_prediction(loc_rows, rec_rows, rel, big_loc, big_rec, w_known, w_cand, kind, inputs):
+    """sum over windows of the post-aggregation CE_tail + CE_head (see _BatchedGatedLinkPredictionFn).  w_known / w_cand (rows, 1):
+    per window [tail rows: w_oqs / w_oqo ; head rows: w_sqo / w_sqs]; `inputs` = gated_loss_inputs(TKG_Module.loss_inputs(...)).
+    big_loc / big_rec: the (B * N_ents, D) stacks of the windows' all-entity matrices."""
+    f = lambda t: t.reshape(-1, 1).to(loc_rows.dtype).contiguous()
+    return _BatchedGatedLinkPredictionFn.apply(loc_rows.contiguous(), rec_rows.contiguous(), rel, big_loc.contiguous(), big_rec.contiguous(),
+                                               f(w_known), f(w_cand), kind, inputs)
+
+
+def gated_link_prediction(loc, rec, rel, all_loc, all_rec, triplets, neg_tail, neg_head, w_sqs, w_sqo, w_oqs, w_oqo, kind):
+    """loss_tail + loss_head of ONE target graph (models/PostDynamicRGCN.py:200-202): the per-window form of
+    batched_gated_link_prediction for the unbatched path (one window, its own all-entity matrices)."""
+    from .tkg_module import TKG_Module
+    dev = loc.device
+    smp = [(triplets.to(torch.int64), neg_tail, neg_head)]
+    inp = gated_loss_inputs(TKG_Module.loss_inputs([0], smp, dev, loc.shape[0], rel.shape[0]), loc.shape[0], dev)
+    if inp is None:
+        return loc.sum() * 0.0
+    w_known = torch.cat([w_oqs.reshape(-1, 1), w_sqo.reshape(-1, 1)])
+    w_cand = torch.cat([w_oqo.reshape(-1, 1), w_sqs.reshape(-1, 1)])
+    return batched_gated_link_prediction(loc, rec, rel, all_loc, all_rec, w_known, w_cand, kind, inp)
+
+
 def batched_link_prediction(ent_rows, rel, big, kind, inputs):
     """sum over windows of CE_tail + CE_head (models/DynamicRGCN.py:186-193) for a bilinear scorer `kind`
     ('distmult' | 'complex'); `inputs` = TKG_Module.loss_inputs(...)."""

@@ -550,3 +550,208 @@ class PostEnsembleBiDynamicRGCN(ImputeBiDynamicRGCN):
     def forward(self, t_list, reverse=False, target_edge_ids=None, samples=None, ensemble_weights=None):
         wb = self.prepare(t_list, self.train_seq_len, True, target_edge_ids)
         return self.run_loss(wb, samples, ensemble_weights)
+
+
+# =====================================================================================================================
+# post-aggregation (embedding-level gate)
+# =====================================================================================================================
+def _post_aggregation_evaluate(self, t_list, val):
+    from .evaluation import PostEvaluationFilter
+    if not isinstance(getattr(self, "evaluater", None), PostEvaluationFilter):
+        self.evaluater = PostEvaluationFilter(self.args, self.calc_score, self.graph_dict_train, self.graph_dict_val, self.graph_dict_test)
+    graph_dict = self.graph_dict_val if val else self.graph_dict_test
+    dev = self._device()
+    with torch.no_grad():
+        wb = self.prepare(t_list, self.test_seq_len, train=False)
+        out, hist = self.run(wb)
+        ranks = []
+        for i, (loc, rec) in enumerate(zip(wb.out_loc.split(wb.target.sizes), out.split(wb.target.sizes))):
+            t = wb.rows[i][-1]
+            g = graph_dict[t]
+            if g.number_of_edges() == 0:
+                continue
+            all_loc, all_rec = self.get_all_embeds_Gt(loc, rec, g, t, wb.plan, i, hist, wb.hist_loc)
+            index_sample = torch.from_numpy(np.stack([g.src, g.rel, g.dst], axis=1)).to(dev)
+            w_sqs, w_sqo, w_oqs, w_oqo = self.calc_ensemble_ratio(index_sample, t, g)
+            ranks.append(self.evaluater.calc_metrics_single_graph(loc, rec, self.rel_embeds, all_loc, all_rec, index_sample,
+                                                                  w_sqs, w_sqo, w_oqs, w_oqo, g, t))
+    ranks = torch.cat(ranks) if ranks else torch.zeros(0, dtype=torch.int64, device=dev)
+    return ranks, float("nan")
+
+
+class _PostAggregationMixin:
+    """What PostDynamicRGCN and PostBiDynamicRGCN add to the impute window models (models/PostDynamicRGCN.py:146-321,
+    models/PostBiDynamicRGCN.py:179-282): four frequency MLPs, the EMBEDDING-level gate of the training loss and of evaluate().
+
+    Loss per target graph (PostDynamicRGCN.train_link_prediction, models/PostDynamicRGCN.py:261-282), loss_tail + loss_head:
+      tail rows: known subject w_oqs * s_loc + (1 - w_oqs) * s_rec, candidates w_oqo * all_loc[c] + (1 - w_oqo) * all_rec[c]
+      head rows: known object = the TEMPORAL row alone (the reference's o_loc = o_rec = ent_embed_rec[o], :276-277: w_sqo has no
+                 effect and no gradient), candidates w_sqs * all_loc[c] + (1 - w_sqs) * all_rec[c]
+    Both scorers are linear in the candidate: the fused node (functional.batched_gated_link_prediction) mixes the two score matrices
+    at the candidate columns.  Reference quirk kept: w_sqo comes from subject_query_SUBJECT_embed_linear and w_oqo from
+    object_query_SUBJECT_embed_linear (calc_ensemble_ratio, :284-321), so the two *_object_embed_linear MLPs never get a gradient."""
+
+    def init_freq_mlp(self):
+        """PostDynamicRGCN.init_freq_mlp, models/PostDynamicRGCN.py:152-172 (same module names => same state_dict keys)."""
+        mk = lambda: nn.Sequential(nn.Linear(3, 3), nn.ReLU(), nn.Linear(3, 1))
+        self.subject_query_subject_embed_linear = mk()
+        self.object_query_subject_embed_linear = mk()
+        self.subject_query_object_embed_linear = mk()
+        self.object_query_object_embed_linear = mk()
+
+    def calc_ensemble_ratio(self, triples, t, g, features=None):
+        """models/PostDynamicRGCN.py:284-321 -> (w_sqs, w_sqo, w_oqs, w_oqo), each (n, 1); empty tensors for no triples.
+        features: the (subject (n, 3), object (n, 3)) device rows of ensemble_features, when the caller has them cached."""
+        if len(triples) == 0:
+            e = torch.zeros(0, dtype=torch.int64, device=self._device())
+            return e, e, e, e
+        sub_f, obj_f = features if features is not None else self.ensemble_features(triples, t, g)
+        w_sqs = torch.sigmoid(self.subject_query_subject_embed_linear(sub_f))
+        w_sqo = torch.sigmoid(self.subject_query_subject_embed_linear(sub_f))     # (sic: the subject-embed MLP)
+        w_oqs = torch.sigmoid(self.object_query_subject_embed_linear(obj_f))
+        w_oqo = torch.sigmoid(self.object_query_subject_embed_linear(obj_f))      # (sic)
+        return w_sqs, w_sqo, w_oqs, w_oqo
+
+    def _agg_features(self, wb, samples):
+        """Per window the frequency feature rows of the sampled triples, computed and uploaded ONCE per (prepared batch, sample set):
+        a step with fixed samples then issues no host-to-device copy and can be captured as a HIP graph."""
+        c = getattr(wb, "_agg_feats", None)
+        if c is None or c[0] is not samples:
+            feats = [self.ensemble_features(samples[i][0], wb.rows[i][-1], g) if samples[i][0].shape[0] > 0 else None
+                     for i, g in enumerate(wb.graphs)]
+            c = wb._agg_feats = (samples, feats)
+        return c[1]
+
+    def _batched_gates(self, wb, samples):
+        """(w_known, w_cand) of the stacked rows of the fused node ([tail rows ; head rows] per window) from the model's own MLPs.
+        w_sqs / w_sqo (and w_oqs / w_oqo) are the same MLP on the same features, so each MLP runs once over every window's rows
+        and one tensor serves both roles (the gradient is the sum of the two roles', as for the reference's two graph nodes)."""
+        feats = self._agg_features(wb, samples)
+        c = getattr(wb, "_agg_gate_rows", None)
+        if c is None or c[0] is not samples:
+            sizes = [f[0].shape[0] for f in feats if f is not None]
+            tot, off, perm = int(sum(sizes)), 0, []
+            for n in sizes:
+                perm.append(np.arange(off, off + n))              # tail rows: the object-query weight (w_oqs / w_oqo)
+                perm.append(tot + np.arange(off, off + n))        # head rows: the subject-query weight (w_sqo / w_sqs)
+                off += n
+            sub = torch.cat([f[0] for f in feats if f is not None])
+            obj = torch.cat([f[1] for f in feats if f is not None])
+            c = wb._agg_gate_rows = (samples, torch.from_numpy(np.concatenate(perm)).to(self._device()), sub, obj)
+        _, perm, sub, obj = c
+        w_s = torch.sigmoid(self.subject_query_subject_embed_linear(sub))
+        w_o = torch.sigmoid(self.object_query_subject_embed_linear(obj))
+        w = torch.cat([w_o, w_s]).index_select(0, perm)
+        return w, w
+
+    def _gated_fused_ok(self):
+        name = self.args.score_function
+        D = self.embed_size
+        return self.fused_loss and name in ("distmult", "complex") and self.num_ents % 4 == 0 and D % (8 if name == "complex" else 4) == 0
+
+    def batched_gated_loss(self, wb, locs, recs, alls, samples, gates):
+        """The gated loss of ALL windows as one fused node, or None when the scorer / shapes need the per-window path.
+        alls: per window (all_loc, all_rec), or the pair of (B, N_ents, D) tensors of batched_all_embeds_post; gates: per window
+        (w_sqs, w_sqo, w_oqs, w_oqo), or None for the model's own MLPs."""
+        if not self._gated_fused_ok():
+            return None
+        dev, D = self._device(), self.embed_size
+        cache = getattr(wb, "_agg_inputs", None)
+        if cache is None or cache[0] is not samples:                 # index tensors are static for a given sample set
+            offs = np.concatenate([[0], np.cumsum(wb.target.sizes)])[:-1]
+            n_rows = int(sum(wb.target.sizes))
+            inp = self.loss_inputs([int(o) for o in offs], samples, dev, n_rows, self.rel_embeds.shape[0])
+            cache = wb._agg_inputs = (samples, TF.gated_loss_inputs(inp, n_rows, dev))
+        inp = cache[1]
+        if inp is None:
+            return torch.cat(locs).sum() * 0.0
+        if gates is None:
+            w_known, w_cand = self._batched_gates(wb, samples)
+        else:
+            live = [gw for gw, smp in zip(gates, samples) if smp[0].shape[0] > 0]
+            w_known = torch.cat([torch.cat([oqs.reshape(-1, 1), sqo.reshape(-1, 1)]) for sqs, sqo, oqs, oqo in live]).to(dev)
+            w_cand = torch.cat([torch.cat([oqo.reshape(-1, 1), sqs.reshape(-1, 1)]) for sqs, sqo, oqs, oqo in live]).to(dev)
+        if isinstance(alls, tuple):
+            big_loc, big_rec = alls[0].reshape(-1, D), alls[1].reshape(-1, D)
+        else:
+            big_loc, big_rec = torch.cat([a for a, _ in alls], dim=0), torch.cat([a for _, a in alls], dim=0)
+        return TF.batched_gated_link_prediction(torch.cat(locs), torch.cat(recs), self.rel_embeds, big_loc, big_rec, w_known, w_cand,
+                                                self.args.score_function, inp)
+
+    def gated_loss(self, loc, rec, all_loc, all_rec, triplets, neg_tail, neg_head, w_sqs, w_sqo, w_oqs, w_oqo):
+        """loss_tail + loss_head of one target graph, models/PostDynamicRGCN.py:200-202 + train_link_prediction :261-282."""
+        if self._gated_fused_ok() and triplets.shape[0] > 0 and all_loc.shape[0] % 4 == 0:
+            return TF.gated_link_prediction(loc, rec, self.rel_embeds, all_loc, all_rec, triplets, neg_tail, neg_head,
+                                            w_sqs, w_sqo, w_oqs, w_oqo, self.args.score_function)
+        labels = torch.zeros(triplets.shape[0], dtype=torch.int64, device=triplets.device)
+        r = self.rel_embeds[triplets[:, 1]]
+        s = w_oqs * loc[triplets[:, 0]] + (1 - w_oqs) * rec[triplets[:, 0]]
+        neg_o = w_oqo.unsqueeze(-1) * all_loc[neg_tail] + (1 - w_oqo).unsqueeze(-1) * all_rec[neg_tail]
+        loss_tail = F.cross_entropy(self.calc_score(s, r, neg_o, mode='tail'), labels)
+        o_rec = rec[triplets[:, 2]]
+        o = w_sqo * o_rec + (1 - w_sqo) * o_rec                                 # (sic: o_loc = o_rec, :276-277)
+        neg_s = w_sqs.unsqueeze(-1) * all_loc[neg_head] + (1 - w_sqs).unsqueeze(-1) * all_rec[neg_head]
+        loss_head = F.cross_entropy(self.calc_score(neg_s, r, o, mode='head'), labels)
+        return loss_tail + loss_head
+
+    def run_loss(self, wb, samples=None, gate_weights=None):
+        """Post(Bi)DynamicRGCN.forward, models/PostDynamicRGCN.py:189-208 / models/PostBiDynamicRGCN.py:199-223.  gate_weights:
+        optional per-window (w_sqs, w_sqo, w_oqs, w_oqo) in place of the frequency MLPs' (tests)."""
+        dev = self._device()
+        out, hist = self.run(wb)
+        recs, locs = list(out.split(wb.target.sizes)), list(wb.out_loc.split(wb.target.sizes))
+        if samples is None:
+            samples = self.draw_samples(wb)
+        both = self.batched_all_embeds_post(wb, out, hist, self._window_base)
+        if both is not None:
+            fused = self.batched_gated_loss(wb, locs, recs, both, samples, gate_weights)
+            if fused is not None:
+                return fused
+        alls = [(both[0][i], both[1][i]) if both is not None else self.get_all_embeds_Gt(locs[i], recs[i], g, wb.rows[i][-1], wb.plan, i, hist, wb.hist_loc)
+                for i, g in enumerate(wb.graphs)]
+        if both is None:
+            fused = self.batched_gated_loss(wb, locs, recs, alls, samples, gate_weights)
+            if fused is not None:
+                return fused
+        feats = self._agg_features(wb, samples) if gate_weights is None else None
+        loss = 0
+        for i, g in enumerate(wb.graphs):
+            triplets, neg_tail, neg_head = (x.to(dev) for x in samples[i])
+            if gate_weights is not None:
+                gw = [x.to(dev) for x in gate_weights[i]]
+            else:
+                gw = self.calc_ensemble_ratio(triplets, wb.rows[i][-1], g, feats[i])
+            a_loc, a_rec = alls[i]
+            loss = loss + self.gated_loss(locs[i], recs[i], a_loc, a_rec, triplets, neg_tail, neg_head, *gw)
+        return loss
+
+    def forward(self, t_list, reverse=False, target_edge_ids=None, samples=None, gate_weights=None):
+        wb = self.prepare(t_list, self.train_seq_len, True, target_edge_ids)
+        return self.run_loss(wb, samples, gate_weights)
+
+    def evaluate(self, t_list, val=True):
+        """Post(Bi)DynamicRGCN.evaluate / calc_metrics (models/PostDynamicRGCN.py:224-259, models/PostBiDynamicRGCN.py:244-282): window
+        loop with the local stream on the full train graphs, (local, temporal) all-entity matrices, embedding-level gated ranks
+        (PostEvaluationFilter, which mixes the known object of the head rows with its own local row).  No classification loss (nan)."""
+        return _post_aggregation_evaluate(self, t_list, val)
+
+
+class PostDynamicRGCN(_PostAggregationMixin, ImputeDynamicRGCN):
+    """models/PostDynamicRGCN.py:146-321 (`--post-aggregation` with GRRGCN / RRGCN)."""
+    _window_base = DynamicRGCN
+    get_all_embeds_Gt = PostEnsembleDynamicRGCN.get_all_embeds_Gt
+
+    def __init__(self, args, num_ents, num_rels, graph_dict_train, graph_dict_val, graph_dict_test, evaluater_type=None):
+        super().__init__(args, num_ents, num_rels, graph_dict_train, graph_dict_val, graph_dict_test, evaluater_type)
+        self.init_freq_mlp()
+
+
+class PostBiDynamicRGCN(_PostAggregationMixin, ImputeBiDynamicRGCN):
+    """models/PostBiDynamicRGCN.py:179-282 (`--post-aggregation` with BiGRRGCN / BiRRGCN).  Its training head is the unidirectional
+    class's train_link_prediction with the real corrupt_tail flag: unlike PostEnsembleBiDynamicRGCN there is no head-as-tail quirk."""
+    _window_base = BiDynamicRGCN
+    get_all_embeds_Gt = PostEnsembleBiDynamicRGCN.get_all_embeds_Gt
+
+    def __init__(self, args, num_ents, num_rels, graph_dict_train, graph_dict_val, graph_dict_test, evaluater_type=None):
+        super().__init__(args, num_ents, num_rels, graph_dict_train, graph_dict_val, graph_dict_test, evaluater_type)
+        self.init_freq_mlp()
