@@ -585,11 +585,7 @@ class DynamicRGCN(TKG_Module):
         if samples is None:
             samples = self._samples_from_plan(wb) if getattr(wb, "loss_plan", None) is not None else self.draw_samples(wb)
         if batched:
-            cache = getattr(wb, "_loss_inputs", None)
-            if cache is None or cache[0] is not samples:          # index tensors are static for a given sample set
-                offs = np.concatenate([[0], np.cumsum(wb.target.sizes)])[:-1]
-                cache = wb._loss_inputs = (samples, self.loss_inputs([int(o) for o in offs], samples, dev, out.shape[0], self.rel_embeds.shape[0]))
-            fused = self.batched_link_prediction(out, cache[1], all_list)
+            fused = self.batched_link_prediction(out, self.cached_loss_inputs(wb, "_loss_inputs", samples, wb.target.sizes), all_list)
             if fused is not None:
                 return fused
         loss = 0

@@ -292,6 +292,43 @@ class _BatchedCandidateCEFn(torch.autograd.Function):
 _TALL_SCORES = __import__("os").environ.get("TEMP_LOSS_TALL", "0") == "1"
 
 
+# -- the per-window products of the three batched loss nodes ------------------------------------------------------------------
+# `big` is the (B * N, D) stack of the windows' all-entity matrices, `splits` the [row_begin, row_end) of every window's block of
+# the stacked query rows, `live` the windows that have rows.
+def _live_windows(splits):
+    return [(b, a0, a1) for b, (a0, a1) in enumerate(splits) if a1 > a0]
+
+
+def _window_scores(be, q, big, live, N):
+    """scores = q[rows of window b] . big_b^T for every live window -> (rows, N), one multi-problem launch."""
+    scores = torch.empty(q.shape[0], N, dtype=torch.float32, device=q.device)
+    be.linear_multi([q[a0:a1] for _, a0, a1 in live], [big[b * N:(b + 1) * N] for b, _, _ in live], True, scores)
+    return scores
+
+
+def _window_dq(be, d_s, big, live, N, like):
+    """d_q = d_scores_b . big_b for every live window, one launch."""
+    d_q = torch.empty_like(like)
+    be.linear_multi([d_s[a0:a1] for _, a0, a1 in live], [big[b * N:(b + 1) * N] for b, _, _ in live], False, d_q)
+    return d_q
+
+
+def _dbig_like(big, live, n_windows):
+    """The gradient buffer of `big`: every live window's block is written whole, so only a batch with an empty window needs zeros."""
+    return torch.empty_like(big) if len(live) == n_windows else torch.zeros_like(big)
+
+
+def _window_dbig(be, d_s, q, big, live, N, n_windows):
+    """d_big_b = d_scores_b^T . q_b for every live window."""
+    d_big = _dbig_like(big, live, n_windows)
+    if hasattr(be, "linear_tn_multi"):                                                        # one launch
+        be.linear_tn_multi([d_s[a0:a1] for _, a0, a1 in live], [q[a0:a1] for _, a0, a1 in live], [d_big[b * N:(b + 1) * N] for b, _, _ in live])
+    else:
+        for b, a0, a1 in live:
+            be.linear_tn(d_s[a0:a1], q[a0:a1], out=d_big[b * N:(b + 1) * N])
+    return d_big
+
+
 class _BatchedLinkPredictionFn(torch.autograd.Function):
     """The whole batched link-prediction loss as ONE autograd node:
         q      = bilinear_query(ent_rows[known], rel[rel_idx])                 (gathers fused, temp_bilinear_query_fwd)
@@ -305,17 +342,17 @@ class _BatchedLinkPredictionFn(torch.autograd.Function):
         be = get_backend()
         N = big.shape[0] // len(inp["splits"])
         q = be.bilinear_query_fwd(kind, ent_rows, inp["known"], rel, inp["rel"], inp["is_tail"])
-        live = [(b, a0, a1) for b, (a0, a1) in enumerate(inp["splits"]) if a1 > a0]
+        live = _live_windows(inp["splits"])
         # few positives against many entities (ICEWS-like: ~200 rows x 10 000 entities per window): the ENTITY axis is made the
         # tall one of every GEMM -- scores = (all_b . q_b^T)^T through a transposed-store epilogue, and the backward products
         # from d_scores^T.  (The planner pads every window's block to a multiple of 4 rows so it can be an N / K extent.)
         tall = _TALL_SCORES and all((a1 - a0) % 4 == 0 and 8 * (a1 - a0) <= N for _, a0, a1 in live)
-        scores = torch.empty(q.shape[0], N, dtype=torch.float32, device=q.device)
         if tall:
+            scores = torch.empty(q.shape[0], N, dtype=torch.float32, device=q.device)
             for b, a0, a1 in live:
                 be.linear_t(big[b * N:(b + 1) * N], q[a0:a1], True, scores[a0:a1])
         else:
-            be.linear_multi([q[a0:a1] for _, a0, a1 in live], [big[b * N:(b + 1) * N] for b, _, _ in live], True, scores)
+            scores = _window_scores(be, q, big, live, N)
         loss_rows, lse = be.gather_ce_fwd(scores, inp["cand"])
         ctx.save_for_backward(ent_rows, rel, big, q, scores, lse)
         ctx.kind, ctx.inp, ctx.live, ctx.N, ctx.tall = kind, inp, live, N, tall
@@ -327,21 +364,16 @@ class _BatchedLinkPredictionFn(torch.autograd.Function):
         inp, live, N = ctx.inp, ctx.live, ctx.N
         be = get_backend()
         d_scores = be.gather_ce_bwd(scores, inp["cand"], lse, d_loss.reshape(1).contiguous(), 1.0, inp["weights"])
-        d_q = torch.empty_like(q)
-        d_big = torch.empty_like(big) if len(live) == len(inp["splits"]) else torch.zeros_like(big)
         if ctx.tall:
+            d_q = torch.empty_like(q)
+            d_big = _dbig_like(big, live, len(inp["splits"]))
             for b, a0, a1 in live:
                 dst = d_scores[a0:a1].t().contiguous()                                        # (N, rows of window b)
                 be.linear_tn(dst, big[b * N:(b + 1) * N], out=d_q[a0:a1])                     # d_q   = d_scores . all_b
                 d_big[b * N:(b + 1) * N].copy_(be.linear(dst, q[a0:a1], False))               # d_all = d_scores^T . q
         else:
-            be.linear_multi([d_scores[a0:a1] for _, a0, a1 in live], [big[b * N:(b + 1) * N] for b, _, _ in live], False, d_q)
-            if hasattr(be, "linear_tn_multi"):                                                # d_all_b = d_scores_b^T . q_b, one launch
-                be.linear_tn_multi([d_scores[a0:a1] for _, a0, a1 in live], [q[a0:a1] for _, a0, a1 in live],
-                                   [d_big[b * N:(b + 1) * N] for b, _, _ in live])
-            else:
-                for b, a0, a1 in live:
-                    be.linear_tn(d_scores[a0:a1], q[a0:a1], out=d_big[b * N:(b + 1) * N])
+            d_q = _window_dq(be, d_scores, big, live, N, q)
+            d_big = _window_dbig(be, d_scores, q, big, live, N, len(inp["splits"]))
         dk, dr = be.bilinear_query_bwd(ctx.kind, ent_rows, inp["known"], rel, inp["rel"], inp["is_tail"], d_q)
         d_ent = be.segment_sum_rows(dk, inp["known_inv"][0], inp["known_inv"][1], ent_rows.shape[0])
         d_rel = be.segment_sum_rows(dr, inp["rel_inv"][0], inp["rel_inv"][1], rel.shape[0])
@@ -359,14 +391,12 @@ class _BatchedEnsembleLinkPredictionFn(torch.autograd.Function):
     def forward(ctx, loc_rows, rec_rows, rel, big_loc, big_rec, w, kind, inp):
         be = get_backend()
         N = big_loc.shape[0] // len(inp["splits"])
-        live = [(b, a0, a1) for b, (a0, a1) in enumerate(inp["splits"]) if a1 > a0]
+        live = _live_windows(inp["splits"])
         qs, sc = [], []
         for rows, big in ((loc_rows, big_loc), (rec_rows, big_rec)):
             q = be.bilinear_query_fwd(kind, rows, inp["known"], rel, inp["rel"], inp["is_tail"])
-            s = torch.empty(q.shape[0], N, dtype=torch.float32, device=q.device)
-            be.linear_multi([q[a0:a1] for _, a0, a1 in live], [big[b * N:(b + 1) * N] for b, _, _ in live], True, s)
             qs.append(q)
-            sc.append(s)
+            sc.append(_window_scores(be, q, big, live, N))
         mixed = torch.lerp(sc[1], sc[0], w)                          # w (rows, 1): w * local + (1 - w) * temporal
         loss_rows, lse = be.gather_ce_fwd(mixed, inp["cand"])
         ctx.save_for_backward(loc_rows, rec_rows, rel, big_loc, big_rec, w, qs[0], qs[1], sc[0], sc[1], mixed, lse)
@@ -384,14 +414,8 @@ class _BatchedEnsembleLinkPredictionFn(torch.autograd.Function):
         d_w = (d_m * (s_l - s_r)).sum(dim=1, keepdim=True) if ctx.needs_input_grad[5] else None
         outs, d_rel = [], None
         for rows, big, q, d_s in ((loc_rows, big_loc, q_l, d_sl), (rec_rows, big_rec, q_r, d_sr)):
-            d_q = torch.empty_like(q)
-            d_big = torch.empty_like(big) if len(live) == len(inp["splits"]) else torch.zeros_like(big)
-            be.linear_multi([d_s[a0:a1] for _, a0, a1 in live], [big[b * N:(b + 1) * N] for b, _, _ in live], False, d_q)
-            if hasattr(be, "linear_tn_multi"):
-                be.linear_tn_multi([d_s[a0:a1] for _, a0, a1 in live], [q[a0:a1] for _, a0, a1 in live], [d_big[b * N:(b + 1) * N] for b, _, _ in live])
-            else:
-                for b, a0, a1 in live:
-                    be.linear_tn(d_s[a0:a1], q[a0:a1], out=d_big[b * N:(b + 1) * N])
+            d_q = _window_dq(be, d_s, big, live, N, q)
+            d_big = _window_dbig(be, d_s, q, big, live, N, len(inp["splits"]))
             dk, dr = be.bilinear_query_bwd(ctx.kind, rows, inp["known"], rel, inp["rel"], inp["is_tail"], d_q)
             outs.append((be.segment_sum_rows(dk, inp["known_inv"][0], inp["known_inv"][1], rows.shape[0]), d_big))
             d_rel = dr if d_rel is None else d_rel + dr
@@ -464,13 +488,9 @@ class _BatchedGatedLinkPredictionFn(torch.autograd.Function):
     def forward(ctx, loc_rows, rec_rows, rel, big_loc, big_rec, w_known, w_cand, kind, inp):
         be = get_backend()
         N = big_loc.shape[0] // len(inp["splits"])
-        live = [(b, a0, a1) for b, (a0, a1) in enumerate(inp["splits"]) if a1 > a0]
+        live = _live_windows(inp["splits"])
         q = _gated_query_fwd(be, kind, loc_rows, inp["known_a"], rec_rows, inp["known"], w_known, rel, inp["rel"], inp["is_tail"])
-        sc = []
-        for big in (big_loc, big_rec):
-            s = torch.empty(q.shape[0], N, dtype=torch.float32, device=q.device)
-            be.linear_multi([q[a0:a1] for _, a0, a1 in live], [big[b * N:(b + 1) * N] for b, _, _ in live], True, s)
-            sc.append(s)
+        sc = [_window_scores(be, q, big, live, N) for big in (big_loc, big_rec)]
         loss_rows, lse = _gather_ce_mix_fwd(be, sc[0], sc[1], w_cand, inp["cand"])
         ctx.save_for_backward(loc_rows, rec_rows, rel, big_loc, big_rec, w_known, w_cand, q, sc[0], sc[1], lse)
         ctx.kind, ctx.inp, ctx.live, ctx.N = kind, inp, live, N
@@ -482,20 +502,10 @@ class _BatchedGatedLinkPredictionFn(torch.autograd.Function):
         inp, live, N = ctx.inp, ctx.live, ctx.N
         be = get_backend()
         d_sa, d_sb, d_wc = _gather_ce_mix_bwd(be, s_a, s_b, w_cand, inp["cand"], lse, d_loss.reshape(1).contiguous(), 1.0, inp["weights"])
-        d_q = torch.empty_like(q)
-        d_q2 = torch.empty_like(q)
-        be.linear_multi([d_sa[a0:a1] for _, a0, a1 in live], [big_loc[b * N:(b + 1) * N] for b, _, _ in live], False, d_q)
-        be.linear_multi([d_sb[a0:a1] for _, a0, a1 in live], [big_rec[b * N:(b + 1) * N] for b, _, _ in live], False, d_q2)
+        d_q = _window_dq(be, d_sa, big_loc, live, N, q)
+        d_q2 = _window_dq(be, d_sb, big_rec, live, N, q)
         d_q += d_q2
-        d_bigs = []
-        for big, d_s in ((big_loc, d_sa), (big_rec, d_sb)):
-            d_big = torch.empty_like(big) if len(live) == len(inp["splits"]) else torch.zeros_like(big)
-            if hasattr(be, "linear_tn_multi"):
-                be.linear_tn_multi([d_s[a0:a1] for _, a0, a1 in live], [q[a0:a1] for _, a0, a1 in live], [d_big[b * N:(b + 1) * N] for b, _, _ in live])
-            else:
-                for b, a0, a1 in live:
-                    be.linear_tn(d_s[a0:a1], q[a0:a1], out=d_big[b * N:(b + 1) * N])
-            d_bigs.append(d_big)
+        d_bigs = [_window_dbig(be, d_s, q, big, live, N, len(inp["splits"])) for big, d_s in ((big_loc, d_sa), (big_rec, d_sb))]
         da, db, dr, d_wk = _gated_query_bwd(be, ctx.kind, loc_rows, inp["known_a"], rec_rows, inp["known"], w_known, rel, inp["rel"],
                                             inp["is_tail"], d_q)
         d_loc = be.segment_sum_rows(da, inp["known_a_inv"][0], inp["known_a_inv"][1], loc_rows.shape[0])

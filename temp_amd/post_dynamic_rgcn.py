@@ -14,7 +14,12 @@ row maps into the last executed position (window.ChainPlan), never dense (bsz, N
 The learned score-mixing weights of PostEnsemble* (`calc_ensemble_ratio`, models/PostDynamicRGCN.py:425-461): two MLPs
 `subject_linear` / `object_linear` (3 -> 3 -> 1, sigmoid; same parameter names as the reference, so its checkpoints load) over
 per-timestamp frequency features of every triple (temp_amd/frequency.py restates the tables of utils/DropEdge.py:34-82).
-`forward(..., ensemble_weights=...)` still accepts injected weights (parity tests that replay the reference's)."""
+`forward(..., ensemble_weights=...)` still accepts injected weights (parity tests that replay the reference's).
+
+Layout: _PostWindowMixin is the impute model of either direction (the classes below it add only what depends on the
+direction: the reference-granular walk); _TwoStreamMixin is the training step and all-entity pass of the models that score with
+both streams, and its two families (_PostEnsembleMixin: score-level mix, _PostAggregationMixin: embedding-level gate) add their
+loss and their ranks."""
 import numpy as np
 import torch
 import torch.nn as nn
@@ -61,57 +66,14 @@ def _rows_or_zero(rows, idx_t, n, d, like):
     return like.new_zeros(n, d) if rows is None else TF.gather_rows(rows, idx_t)
 
 
-def _impute_evaluate(self, t_list, val):
-    from .evaluation import EvaluationFilter
-    if not hasattr(self, "evaluater"):
-        self.evaluater = EvaluationFilter(self.args, self.calc_score, self.graph_dict_train, self.graph_dict_val, self.graph_dict_test)
-    graph_dict = self.graph_dict_val if val else self.graph_dict_test
-    dev = self._device()
-    with torch.no_grad():
-        wb = self.prepare(t_list, self.test_seq_len, train=False)
-        out, hist = self.run(wb)
-        ranks, losses = [], []
-        for i, ent_embed in enumerate(out.split(wb.target.sizes)):
-            t = wb.rows[i][-1]
-            g = graph_dict[t]
-            if g.number_of_edges() == 0:
-                continue
-            all_embeds_g = self.get_all_embeds_Gt(ent_embed, g, t, wb.plan, i, hist, wb.hist_loc)
-            index_sample = torch.from_numpy(np.stack([g.src, g.rel, g.dst], axis=1)).to(dev)
-            label = torch.ones(index_sample.shape[0], device=dev)
-            ranks.append(self.evaluater.calc_metrics_single_graph(ent_embed, self.rel_embeds, all_embeds_g, index_sample, g, t))
-            losses.append(self.link_classification_loss(ent_embed, self.rel_embeds, index_sample, label))
-    ranks = torch.cat(ranks) if ranks else torch.zeros(0, dtype=torch.int64, device=dev)
-    return ranks, (float(torch.stack(losses).mean().item()) if losses else float("nan"))
-
-
-def _post_ensemble_evaluate(self, t_list, val):
-    from .evaluation import PostEnsembleEvaluationFilter
-    if not isinstance(getattr(self, "evaluater", None), PostEnsembleEvaluationFilter):
-        self.evaluater = PostEnsembleEvaluationFilter(self.args, self.calc_score, self.graph_dict_train, self.graph_dict_val, self.graph_dict_test)
-    graph_dict = self.graph_dict_val if val else self.graph_dict_test
-    dev = self._device()
-    with torch.no_grad():
-        wb = self.prepare(t_list, self.test_seq_len, train=False)
-        out, hist = self.run(wb)
-        ranks = []
-        for i, (loc, rec) in enumerate(zip(wb.out_loc.split(wb.target.sizes), out.split(wb.target.sizes))):
-            t = wb.rows[i][-1]
-            g = graph_dict[t]
-            if g.number_of_edges() == 0:
-                continue
-            all_loc, all_rec = self.get_all_embeds_Gt(loc, rec, g, t, wb.plan, i, hist, wb.hist_loc)
-            index_sample = torch.from_numpy(np.stack([g.src, g.rel, g.dst], axis=1)).to(dev)
-            w_subject, w_object = self.calc_ensemble_ratio(index_sample, t, g)
-            ranks.append(self.evaluater.calc_metrics_single_graph(loc, rec, self.rel_embeds, all_loc, all_rec, w_subject, w_object,
-                                                                  index_sample, g, t))
-    ranks = torch.cat(ranks) if ranks else torch.zeros(0, dtype=torch.int64, device=dev)
-    return ranks, float("nan")
-
-
 class _PostWindowMixin:
-    """What the uni- and bidirectional post models share: slicing the local stream out of a batched run and the
-    score-level ensemble loss."""
+    """What the uni- and bidirectional post models share: slicing the local stream out of a batched run, the impute models' loss,
+    all-entity pass and evaluate(), and the score-level ensemble loss.  A direction is one ChainPlan: the bidirectional classes
+    carry a pair of everything that is per plan (wb.plan, the histories, wb.hist_loc)."""
+
+    _window_base = None                   # DynamicRGCN | BiDynamicRGCN: the window model whose batched all-entity pass applies
+    _evaluater = "EvaluationFilter"       # the class of temp_amd.evaluation that ranks for evaluate()
+    _two_stream = False                   # get_all_embeds_Gt takes (local, temporal) target rows and returns both matrices
 
     def _chain_input_rows(self, wb, inst_id=None, step=None):
         """GRU-input rows (= local layer-2 states) of one chain instance / step of a batched run."""
@@ -120,6 +82,117 @@ class _PostWindowMixin:
             it = wb.program.inst[inst_id]
             return x[it.x0:it.x0 + it.n]
         return x[step.row0:step.row0 + step.n_rows]
+
+    def _run_batched(self, wb):
+        out, hist = super()._run_batched(wb)
+        bi = isinstance(wb.plan, tuple)
+        if wb.program is not None:
+            wb.out_loc = self._chain_input_rows(wb, wb.out_inst[0])
+            loc = [self._chain_input_rows(wb, i) if i >= 0 else None for i in (wb.hist_inst if bi else (wb.hist_inst,))]
+        else:
+            wb.out_loc = self._chain_input_rows(wb, step=wb.target)
+            loc = [self._chain_input_rows(wb, step=p.steps[-1]) if p.steps else None for p in (wb.plan if bi else (wb.plan,))]
+        wb.hist_loc = tuple(loc) if bi else loc[0]
+        return out, hist
+
+    def _fused_all_entity_ok(self, wb):
+        return False                     # the all-entity pass of these models mixes in the local history: per window, below
+
+    def _plan_loss(self, wb):
+        wb.loss_plan = None
+
+    # -- all-entity pass ---------------------------------------------------------------------------------------------------
+    def _final_prevs(self, plan, b, hist, hist_loc):
+        """(previous first-layer state, previous second-layer state, previous local state, time gaps) of every entity for window
+        b; a pair of them (forward, backward) for a pair of plans."""
+        dev, N, D = self._device(), self.num_ents, self.embed_size
+        bi = isinstance(plan, tuple)
+        if not bi:
+            plan, hist, hist_loc = (plan,), (hist,), (hist_loc,)
+        out = []
+        for p, h, loc in zip(plan, hist, hist_loc if hist_loc is not None else (None, None)):
+            idx, dt = _final_index(p, b, dev)
+            p1 = _rows_or_zero(h[0], idx, N, D, self.ent_embeds)
+            p2 = p1 if h[1] is h[0] else _rows_or_zero(h[1], idx, N, D, self.ent_embeds)
+            out.append((p1, p2, _rows_or_zero(loc, idx, N, D, self.ent_embeds), dt))
+        return out if bi else out[0]
+
+    def _isolated_args(self, t, plan, b, hist, hist_loc):
+        """What the encoder's forward_isolated_impute / forward_post_ensemble_isolated take after the entity table: per direction
+        (first, second, time gaps), the timestamp, then per direction the local state."""
+        prevs = self._final_prevs(plan, b, hist, hist_loc)
+        prevs = prevs if isinstance(plan, tuple) else [prevs]
+        return [x for p1, p2, _, dt in prevs for x in (p1, p2, dt)] + [t] + [pl for _, _, pl, _ in prevs]
+
+    def get_all_embeds_Gt(self, convoluted_embeds, g, t, plan, b, hist, hist_loc=None):
+        """ImputeDynamicRGCN.get_all_embeds_Gt, models/PostDynamicRGCN.py:24-31; ImputeBiDynamicRGCN.get_all_embeds_Gt,
+        models/PostBiDynamicRGCN.py:29-39."""
+        all_embeds = self.ent_encoder.forward_isolated_impute(self.ent_embeds, *self._isolated_args(t, plan, b, hist, hist_loc))
+        return all_embeds.index_copy(0, _gids_dev(g, self._device()), convoluted_embeds)
+
+    def run_loss(self, wb, samples=None):
+        """ImputeDynamicRGCN.forward, models/PostDynamicRGCN.py:80-96; ImputeBiDynamicRGCN.forward,
+        models/PostBiDynamicRGCN.py:103-124."""
+        dev = self._device()
+        out, hist = self.run(wb)
+        per_graph = list(out.split(wb.target.sizes))
+        if samples is None:
+            samples = self.draw_samples(wb)
+        loss = 0
+        for i, (g, ent_embed) in enumerate(zip(wb.graphs, per_graph)):
+            t = wb.rows[i][-1]
+            triplets, neg_tail, neg_head = (x.to(dev) for x in samples[i])
+            labels = torch.zeros(triplets.shape[0], dtype=torch.int64, device=dev)
+            all_embeds_g = self.get_all_embeds_Gt(ent_embed, g, t, wb.plan, i, hist, wb.hist_loc)
+            loss = loss + self.train_link_prediction_both(ent_embed, triplets, neg_tail, neg_head, labels, all_embeds_g)
+        return loss
+
+    def encode_post(self, t_list, seq_len, train=True, target_edge_ids=None):
+        """-> (per-window local embeddings, per-window temporal embeddings, prepared batch, final histories)."""
+        wb = self.prepare(t_list, seq_len, train, target_edge_ids)
+        out, hist = self.run(wb)
+        return list(wb.out_loc.split(wb.target.sizes)), list(out.split(wb.target.sizes)), wb, hist
+
+    def evaluate(self, t_list, val=True):
+        """The window loop with the local history stream on the full train graphs, the all-entity matrices of every target
+        timestamp that has valid (or test) triples, then the family's filtered ranks (_graph_metrics):
+          impute         ImputeDynamicRGCN.evaluate / calc_metrics, models/PostDynamicRGCN.py:101-143 (bidirectional:
+                         models/PostBiDynamicRGCN.py:126-176)
+          post-ensemble  PostEnsemble(Bi)DynamicRGCN.evaluate / calc_metrics, models/PostDynamicRGCN.py:367-423,
+                         models/PostBiDynamicRGCN.py:297-360
+          post-aggregation  Post(Bi)DynamicRGCN.evaluate / calc_metrics, models/PostDynamicRGCN.py:224-259,
+                         models/PostBiDynamicRGCN.py:244-282
+        As in the reference only the impute models compute a classification loss (nan otherwise)."""
+        from . import evaluation
+        cls = getattr(evaluation, self._evaluater)
+        if not isinstance(getattr(self, "evaluater", None), cls):
+            self.evaluater = cls(self.args, self.calc_score, self.graph_dict_train, self.graph_dict_val, self.graph_dict_test)
+        graph_dict = self.graph_dict_val if val else self.graph_dict_test
+        dev = self._device()
+        with torch.no_grad():
+            wb = self.prepare(t_list, self.test_seq_len, train=False)
+            out, hist = self.run(wb)
+            ranks, losses = [], []
+            for i, (loc, rec) in enumerate(zip(wb.out_loc.split(wb.target.sizes), out.split(wb.target.sizes))):
+                t = wb.rows[i][-1]
+                g = graph_dict[t]
+                if g.number_of_edges() == 0:
+                    continue
+                alls = self.get_all_embeds_Gt(*((loc, rec) if self._two_stream else (rec,)), g, t, wb.plan, i, hist, wb.hist_loc)
+                index_sample = torch.from_numpy(np.stack([g.src, g.rel, g.dst], axis=1)).to(dev)
+                r, loss = self._graph_metrics(loc, rec, alls, index_sample, g, t)
+                ranks.append(r)
+                if loss is not None:
+                    losses.append(loss)
+        ranks = torch.cat(ranks) if ranks else torch.zeros(0, dtype=torch.int64, device=dev)
+        return ranks, (float(torch.stack(losses).mean().item()) if losses else float("nan"))
+
+    def _graph_metrics(self, loc, rec, all_embeds_g, index_sample, g, t):
+        """-> (ranks, classification loss | None) of one target graph: the IMPUTED all-entity matrix, the standard filtered ranks
+        (temp_amd.evaluation.EvaluationFilter) and the classification loss of the valid (or test) triples."""
+        label = torch.ones(index_sample.shape[0], device=index_sample.device)
+        return (self.evaluater.calc_metrics_single_graph(rec, self.rel_embeds, all_embeds_g, index_sample, g, t),
+                self.link_classification_loss(rec, self.rel_embeds, index_sample, label))
 
     # Reference quirk kept for parity (pinned by golden G19_post_ratio_bi): PostEnsembleBiDynamicRGCN.train_link_prediction forwards
     # to the uni-directional class with `corrupt_tail=True` hard-coded (models/PostBiDynamicRGCN.py:294-295), so its "head" scores
@@ -164,13 +237,14 @@ class _PostWindowMixin:
             return self.calc_score(ent_embed[triplets[:, 0]], r, all_embeds_g[neg_samples], mode='tail')
         return self.calc_score(all_embeds_g[neg_samples], r, ent_embed[triplets[:, 2]], mode='head')
 
-    def batched_all_embeds_post(self, wb, out, hist, base):
+    def batched_all_embeds_post(self, wb, out, hist, base=None):
         """(all_loc, all_rec) of EVERY window in one pass, or None (per-window get_all_embeds_Gt then).  Without imputation the
         temporal all-entity matrix is the base model's (models/BiRRGCN.py:259-293 runs the same isolated trunk + GRUs as
         forward_isolated), so base.all_embeds_batched applies -- zero-state GRU rows once per entity, own rows only for the
         (window, entity) pairs that carry a state; the local one is the isolated trunk Iso2(Iso1(E)) -- the same N rows for every
-        window -- with each window's target rows written over it (one static row map)."""
+        window -- with each window's target rows written over it (one static row map).  base: the class's _window_base."""
         enc = self.ent_encoder
+        base = base or self._window_base
         if getattr(enc, "impute", False) or not wb.batched or not base._fused_all_entity_ok(self, wb):
             return None
         dev = self._device()
@@ -195,32 +269,28 @@ class _PostWindowMixin:
         big_loc = TF.gather_rows(torch.cat([wb.out_loc, x], dim=0), m[0], m[1]).view(B, N, D)
         return big_loc, big_rec
 
+    def _stacked_alls(self, alls):
+        """The (B * N_ents, D) stacks of the two streams' all-entity matrices for a fused node.  alls: per window (all_loc,
+        all_rec), or the pair of (B, N_ents, D) tensors of batched_all_embeds_post as they are (no per-window slices: every slice
+        is a zero-filled (B, N_ents, D) gradient and an addition in the backward)."""
+        if isinstance(alls, tuple):
+            return alls[0].reshape(-1, self.embed_size), alls[1].reshape(-1, self.embed_size)
+        return torch.cat([a for a, _ in alls], dim=0), torch.cat([a for _, a in alls], dim=0)
+
     def batched_ensemble_loss(self, wb, locs, recs, alls, samples, weights):
         """The ensemble loss of ALL windows as one fused node (functional.batched_ensemble_link_prediction), or None when the scorer
-        / shapes need the per-window path.  locs / recs: per-window target rows of the two streams; alls: per window (all_loc,
-        all_rec), or the pair of (B, N_ents, D) tensors of batched_all_embeds_post as they are (no per-window slices: every slice
-        is a zero-filled (B, N_ents, D) gradient and an addition in the backward); weights: per window (weight_subject (P, 1),
-        weight_object (P, 1))."""
-        name = self.args.score_function
-        D = self.embed_size
-        if not (self.fused_loss and name in ("distmult", "complex") and self.num_ents % 4 == 0 and D % (8 if name == "complex" else 4) == 0):
+        / shapes need the per-window path.  locs / recs: per-window target rows of the two streams; alls: see _stacked_alls;
+        weights: per window (weight_subject (P, 1), weight_object (P, 1))."""
+        if not self.fused_loss_ok(self.embed_size):
             return None
-        dev = self._device()
-        cache = getattr(wb, "_ens_inputs", None)
-        if cache is None or cache[0] is not samples:                 # index tensors are static for a given sample set
-            offs = np.concatenate([[0], np.cumsum(wb.target.sizes)])[:-1]
-            n_rows = int(sum(wb.target.sizes))
-            cache = wb._ens_inputs = (samples, self.loss_inputs([int(o) for o in offs], samples, dev, n_rows, self.rel_embeds.shape[0],
-                                                                head_as_tail=self.head_scored_as_tail))
-        inp = cache[1]
+        inp = self.cached_loss_inputs(wb, "_ens_inputs", samples, wb.target.sizes, head_as_tail=self.head_scored_as_tail)
         if inp is None:
             return torch.cat(locs).sum() * 0.0
-        w = torch.cat([torch.cat([wo.reshape(-1, 1), ws.reshape(-1, 1)]) for (ws, wo), smp in zip(weights, samples) if smp[0].shape[0] > 0]).to(dev)
-        if isinstance(alls, tuple):
-            big_loc, big_rec = alls[0].reshape(-1, D), alls[1].reshape(-1, D)
-        else:
-            big_loc, big_rec = torch.cat([a for a, _ in alls], dim=0), torch.cat([a for _, a in alls], dim=0)
-        return TF.batched_ensemble_link_prediction(torch.cat(locs), torch.cat(recs), self.rel_embeds, big_loc, big_rec, w, name, inp)
+        w = torch.cat([torch.cat([wo.reshape(-1, 1), ws.reshape(-1, 1)]) for (ws, wo), smp in zip(weights, samples)
+                       if smp[0].shape[0] > 0]).to(self._device())
+        big_loc, big_rec = self._stacked_alls(alls)
+        return TF.batched_ensemble_link_prediction(torch.cat(locs), torch.cat(recs), self.rel_embeds, big_loc, big_rec, w,
+                                                   self.args.score_function, inp)
 
     def ensemble_loss(self, loc, rec, all_loc, all_rec, triplets, neg_tail, neg_head, w_subject, w_object):
         """loss_tail + loss_head of one target graph, models/PostDynamicRGCN.py:335-349 + combined_scores :404-406."""
@@ -253,10 +323,11 @@ class _PostWindowMixin:
 
 
 # =====================================================================================================================
-# unidirectional
+# impute: unidirectional, bidirectional
 # =====================================================================================================================
 class ImputeDynamicRGCN(_PostWindowMixin, DynamicRGCN):
     """models/PostDynamicRGCN.py:20-128."""
+    _window_base = DynamicRGCN
 
     def _can_batch(self):
         enc = self.ent_encoder
@@ -280,125 +351,10 @@ class ImputeDynamicRGCN(_PostWindowMixin, DynamicRGCN):
         wb.out_loc, wb.hist_loc = out_loc, loc
         return out, (first, second)
 
-    def _run_batched(self, wb):
-        out, hist = super()._run_batched(wb)
-        if wb.program is not None:
-            wb.out_loc = self._chain_input_rows(wb, wb.out_inst[0])
-            wb.hist_loc = self._chain_input_rows(wb, wb.hist_inst) if wb.hist_inst >= 0 else None
-        else:
-            wb.out_loc = self._chain_input_rows(wb, step=wb.target)
-            wb.hist_loc = self._chain_input_rows(wb, step=wb.plan.steps[-1]) if wb.plan.steps else None
-        return out, hist
 
-    def _fused_all_entity_ok(self, wb):
-        return False                     # the all-entity pass of these models mixes in the local history: per window, below
-
-    def _plan_loss(self, wb):
-        wb.loss_plan = None
-
-    # -- all-entity pass ---------------------------------------------------------------------------------------------------
-    def _final_prevs(self, plan, b, hist, loc):
-        dev, N, D = self._device(), self.num_ents, self.embed_size
-        idx, dt = _final_index(plan, b, dev)
-        p1 = _rows_or_zero(hist[0], idx, N, D, self.ent_embeds)
-        p2 = p1 if hist[1] is hist[0] else _rows_or_zero(hist[1], idx, N, D, self.ent_embeds)
-        pl = _rows_or_zero(loc, idx, N, D, self.ent_embeds)
-        return p1, p2, pl, dt
-
-    def get_all_embeds_Gt(self, convoluted_embeds, g, t, plan, b, hist, hist_loc=None):
-        """ImputeDynamicRGCN.get_all_embeds_Gt, models/PostDynamicRGCN.py:24-31."""
-        p1, p2, pl, dt = self._final_prevs(plan, b, hist, hist_loc)
-        all_embeds = self.ent_encoder.forward_isolated_impute(self.ent_embeds, p1, p2, dt, t, pl)
-        return all_embeds.index_copy(0, _gids_dev(g, self._device()), convoluted_embeds)
-
-    def run_loss(self, wb, samples=None):
-        """ImputeDynamicRGCN.forward, models/PostDynamicRGCN.py:80-96."""
-        dev = self._device()
-        out, hist = self.run(wb)
-        per_graph = list(out.split(wb.target.sizes))
-        if samples is None:
-            samples = self.draw_samples(wb)
-        loss = 0
-        for i, (g, ent_embed) in enumerate(zip(wb.graphs, per_graph)):
-            t = wb.rows[i][-1]
-            triplets, neg_tail, neg_head = (x.to(dev) for x in samples[i])
-            labels = torch.zeros(triplets.shape[0], dtype=torch.int64, device=dev)
-            all_embeds_g = self.get_all_embeds_Gt(ent_embed, g, t, wb.plan, i, hist, wb.hist_loc)
-            loss = loss + self.train_link_prediction_both(ent_embed, triplets, neg_tail, neg_head, labels, all_embeds_g)
-        return loss
-
-    def encode_post(self, t_list, seq_len, train=True, target_edge_ids=None):
-        """-> (per-window local embeddings, per-window temporal embeddings, prepared batch, final histories)."""
-        wb = self.prepare(t_list, seq_len, train, target_edge_ids)
-        out, hist = self.run(wb)
-        return list(wb.out_loc.split(wb.target.sizes)), list(out.split(wb.target.sizes)), wb, hist
-
-    def evaluate(self, t_list, val=True):
-        """ImputeDynamicRGCN.evaluate / calc_metrics, models/PostDynamicRGCN.py:101-143 (bidirectional:
-        models/PostBiDynamicRGCN.py:126-176): the window loop with the local history stream on the full train graphs, the
-        IMPUTED all-entity matrix, then the standard filtered ranks (temp_amd.evaluation.EvaluationFilter) and classification
-        loss of the valid (or test) triples of every target timestamp."""
-        return _impute_evaluate(self, t_list, val)
-
-
-class PostEnsembleDynamicRGCN(ImputeDynamicRGCN):
-    """models/PostDynamicRGCN.py:323-461 (PostEnsembleDynamicRGCN: score-level ensemble with the frequency MLPs)."""
-
-    def __init__(self, args, num_ents, num_rels, graph_dict_train, graph_dict_val, graph_dict_test, evaluater_type=None):
-        super().__init__(args, num_ents, num_rels, graph_dict_train, graph_dict_val, graph_dict_test, evaluater_type)
-        self.init_freq_mlp()
-
-    def evaluate(self, t_list, val=True):
-        """PostEnsemble(Bi)DynamicRGCN.evaluate / calc_metrics (models/PostDynamicRGCN.py:367-423, models/PostBiDynamicRGCN.py:297-360):
-        window loop with the local stream on the full train graphs, (local, temporal) all-entity matrices, score-level ensemble
-        ranks (PostEnsembleEvaluationFilter).  The mixing weights come from calc_ensemble_ratio(index_sample, t, g) (frequency MLPs).
-        As in the reference no classification loss is computed (nan)."""
-        return _post_ensemble_evaluate(self, t_list, val)
-
-    def get_all_embeds_Gt(self, convoluted_loc, convoluted_rec, g, t, plan, b, hist, hist_loc=None):
-        """PostDynamicRGCN.get_all_embeds_Gt, models/PostDynamicRGCN.py:160-174 -> (all_loc, all_rec)."""
-        p1, p2, pl, dt = self._final_prevs(plan, b, hist, hist_loc)
-        a_loc, a_rec = self.ent_encoder.forward_post_ensemble_isolated(self.ent_embeds, p1, p2, dt, t, pl)
-        gid = _gids_dev(g, self._device())
-        return a_loc.index_copy(0, gid, convoluted_loc), a_rec.index_copy(0, gid, convoluted_rec)
-
-    def run_loss(self, wb, samples=None, ensemble_weights=None):
-        """PostEnsembleDynamicRGCN.forward, models/PostDynamicRGCN.py:375-397."""
-        dev = self._device()
-        out, hist = self.run(wb)
-        recs, locs = list(out.split(wb.target.sizes)), list(wb.out_loc.split(wb.target.sizes))
-        if samples is None:
-            samples = self.draw_samples(wb)
-        loss = 0
-        wts = [ensemble_weights[i] if ensemble_weights is not None else self.calc_ensemble_ratio(samples[i][0].to(dev), wb.rows[i][-1], g)
-               for i, g in enumerate(wb.graphs)]
-        both = self.batched_all_embeds_post(wb, out, hist, DynamicRGCN)
-        if both is not None:
-            fused = self.batched_ensemble_loss(wb, locs, recs, both, samples, wts)      # all windows' losses as one node, on the (B, N, D) tensors
-            if fused is not None:
-                return fused
-        alls = [(both[0][i], both[1][i]) if both is not None else self.get_all_embeds_Gt(locs[i], recs[i], g, wb.rows[i][-1], wb.plan, i, hist, wb.hist_loc)
-                for i, g in enumerate(wb.graphs)]
-        if both is None:
-            fused = self.batched_ensemble_loss(wb, locs, recs, alls, samples, wts)
-            if fused is not None:
-                return fused
-        for i, g in enumerate(wb.graphs):
-            triplets, neg_tail, neg_head = (x.to(dev) for x in samples[i])
-            (a_loc, a_rec), (ws, wo) = alls[i], wts[i]
-            loss = loss + self.ensemble_loss(locs[i], recs[i], a_loc, a_rec, triplets, neg_tail, neg_head, ws.to(dev), wo.to(dev))
-        return loss
-
-    def forward(self, t_list, reverse=False, target_edge_ids=None, samples=None, ensemble_weights=None):
-        wb = self.prepare(t_list, self.train_seq_len, True, target_edge_ids)
-        return self.run_loss(wb, samples, ensemble_weights)
-
-
-# =====================================================================================================================
-# bidirectional
-# =====================================================================================================================
 class ImputeBiDynamicRGCN(_PostWindowMixin, BiDynamicRGCN):
     """models/PostBiDynamicRGCN.py:22-167."""
+    _window_base = BiDynamicRGCN
 
     def _can_batch(self):
         enc = self.ent_encoder
@@ -434,152 +390,95 @@ class ImputeBiDynamicRGCN(_PostWindowMixin, BiDynamicRGCN):
         wb.out_loc, wb.hist_loc = out_loc, (loc_f, loc_b)
         return out, (hf, hb)
 
-    def _run_batched(self, wb):
-        out, hist = super()._run_batched(wb)
-        plan_f, plan_b = wb.plan
-        if wb.program is not None:
-            wb.out_loc = self._chain_input_rows(wb, wb.out_inst[0])
-            wb.hist_loc = tuple(self._chain_input_rows(wb, i) if i >= 0 else None for i in wb.hist_inst)
-        else:
-            wb.out_loc = self._chain_input_rows(wb, step=wb.target)
-            wb.hist_loc = tuple(self._chain_input_rows(wb, step=p.steps[-1]) if p.steps else None for p in (plan_f, plan_b))
-        return out, hist
 
-    def _fused_all_entity_ok(self, wb):
-        return False
-
-    def _plan_loss(self, wb):
-        wb.loss_plan = None
-
-    # -- all-entity pass ---------------------------------------------------------------------------------------------------
-    def _final_prevs(self, plans, b, hist, hist_loc):
-        dev, N, D = self._device(), self.num_ents, self.embed_size
-        out = []
-        for plan, h, loc in zip(plans, hist, hist_loc if hist_loc is not None else (None, None)):
-            idx, dt = _final_index(plan, b, dev)
-            p1 = _rows_or_zero(h[0], idx, N, D, self.ent_embeds)
-            p2 = p1 if h[1] is h[0] else _rows_or_zero(h[1], idx, N, D, self.ent_embeds)
-            out.append((p1, p2, _rows_or_zero(loc, idx, N, D, self.ent_embeds), dt))
-        return out
-
-    def get_all_embeds_Gt(self, convoluted_embeds, g, t, plans, b, hist, hist_loc=None):
-        """ImputeBiDynamicRGCN.get_all_embeds_Gt, models/PostBiDynamicRGCN.py:29-39."""
-        (f1, f2, fl, dtf), (b1, b2, bl, dtb) = self._final_prevs(plans, b, hist, hist_loc)
-        all_embeds = self.ent_encoder.forward_isolated_impute(self.ent_embeds, f1, f2, dtf, b1, b2, dtb, t, fl, bl)
-        return all_embeds.index_copy(0, _gids_dev(g, self._device()), convoluted_embeds)
-
-    def run_loss(self, wb, samples=None):
-        """ImputeBiDynamicRGCN.forward, models/PostBiDynamicRGCN.py:103-124."""
-        dev = self._device()
-        out, hist = self.run(wb)
-        per_graph = list(out.split(wb.target.sizes))
-        if samples is None:
-            samples = self.draw_samples(wb)
-        loss = 0
-        for i, (g, ent_embed) in enumerate(zip(wb.graphs, per_graph)):
-            t = wb.rows[i][-1]
-            triplets, neg_tail, neg_head = (x.to(dev) for x in samples[i])
-            labels = torch.zeros(triplets.shape[0], dtype=torch.int64, device=dev)
-            all_embeds_g = self.get_all_embeds_Gt(ent_embed, g, t, wb.plan, i, hist, wb.hist_loc)
-            loss = loss + self.train_link_prediction_both(ent_embed, triplets, neg_tail, neg_head, labels, all_embeds_g)
-        return loss
-
-    def encode_post(self, t_list, seq_len, train=True, target_edge_ids=None):
-        """-> (per-window local embeddings, per-window temporal embeddings, prepared batch, final histories)."""
-        wb = self.prepare(t_list, seq_len, train, target_edge_ids)
-        out, hist = self.run(wb)
-        return list(wb.out_loc.split(wb.target.sizes)), list(out.split(wb.target.sizes)), wb, hist
-
-    def evaluate(self, t_list, val=True):
-        """ImputeDynamicRGCN.evaluate / calc_metrics, models/PostDynamicRGCN.py:101-143 (bidirectional:
-        models/PostBiDynamicRGCN.py:126-176): the window loop with the local history stream on the full train graphs, the
-        IMPUTED all-entity matrix, then the standard filtered ranks (temp_amd.evaluation.EvaluationFilter) and classification
-        loss of the valid (or test) triples of every target timestamp."""
-        return _impute_evaluate(self, t_list, val)
-
-
-class PostEnsembleBiDynamicRGCN(ImputeBiDynamicRGCN):
-    """models/PostBiDynamicRGCN.py:283-372 (score-level ensemble with the frequency MLPs) -- BASELINE config 3's model."""
-    head_scored_as_tail = True            # models/PostBiDynamicRGCN.py:294-295, see _PostWindowMixin
+# =====================================================================================================================
+# two streams: post-ensemble (score-level mix) and post-aggregation (embedding-level gate)
+# =====================================================================================================================
+class _TwoStreamMixin:
+    """The training step and the all-entity pass of the models that score with the local AND the temporal stream, in front of an
+    Impute* class.  A family adds its frequency MLPs (init_freq_mlp, calc_ensemble_ratio) and its loss: _step_weights (what is
+    computed before the all-entity pass), _fused_windows_loss (all windows as one node, or None) and _window_losses."""
+    _two_stream = True
 
     def __init__(self, args, num_ents, num_rels, graph_dict_train, graph_dict_val, graph_dict_test, evaluater_type=None):
         super().__init__(args, num_ents, num_rels, graph_dict_train, graph_dict_val, graph_dict_test, evaluater_type)
-        self.init_freq_mlp()
+        self.init_freq_mlp()              # after everything the base constructor registers: the order of parameters()
 
-    def evaluate(self, t_list, val=True):
-        """PostEnsemble(Bi)DynamicRGCN.evaluate / calc_metrics (models/PostDynamicRGCN.py:367-423, models/PostBiDynamicRGCN.py:297-360):
-        window loop with the local stream on the full train graphs, (local, temporal) all-entity matrices, score-level ensemble
-        ranks (PostEnsembleEvaluationFilter).  The mixing weights come from calc_ensemble_ratio(index_sample, t, g) (frequency MLPs).
-        As in the reference no classification loss is computed (nan)."""
-        return _post_ensemble_evaluate(self, t_list, val)
-
-    def get_all_embeds_Gt(self, convoluted_loc, convoluted_rec, g, t, plans, b, hist, hist_loc=None):
-        """PostBiDynamicRGCN.get_all_embeds_Gt, models/PostBiDynamicRGCN.py:176-190 -> (all_loc, all_rec)."""
-        (f1, f2, fl, dtf), (b1, b2, bl, dtb) = self._final_prevs(plans, b, hist, hist_loc)
-        a_loc, a_rec = self.ent_encoder.forward_post_ensemble_isolated(self.ent_embeds, f1, f2, dtf, b1, b2, dtb, t, fl, bl)
+    def get_all_embeds_Gt(self, convoluted_loc, convoluted_rec, g, t, plan, b, hist, hist_loc=None):
+        """PostDynamicRGCN.get_all_embeds_Gt, models/PostDynamicRGCN.py:160-174; PostBiDynamicRGCN.get_all_embeds_Gt,
+        models/PostBiDynamicRGCN.py:176-190 -> (all_loc, all_rec)."""
+        a_loc, a_rec = self.ent_encoder.forward_post_ensemble_isolated(self.ent_embeds, *self._isolated_args(t, plan, b, hist, hist_loc))
         gid = _gids_dev(g, self._device())
         return a_loc.index_copy(0, gid, convoluted_loc), a_rec.index_copy(0, gid, convoluted_rec)
 
-    def run_loss(self, wb, samples=None, ensemble_weights=None):
-        """PostEnsembleBiDynamicRGCN.forward, models/PostBiDynamicRGCN.py:329-354."""
-        dev = self._device()
+    def run_loss(self, wb, samples=None, weights=None):
+        """PostEnsembleDynamicRGCN.forward, models/PostDynamicRGCN.py:375-397; PostEnsembleBiDynamicRGCN.forward,
+        models/PostBiDynamicRGCN.py:329-354; Post(Bi)DynamicRGCN.forward, models/PostDynamicRGCN.py:189-208 /
+        models/PostBiDynamicRGCN.py:199-223.  weights: optional per-window weights in place of the frequency MLPs' (tests) --
+        (weight_subject, weight_object) for the post-ensemble classes, (w_sqs, w_sqo, w_oqs, w_oqo) for the post-aggregation ones."""
         out, hist = self.run(wb)
         recs, locs = list(out.split(wb.target.sizes)), list(wb.out_loc.split(wb.target.sizes))
         if samples is None:
             samples = self.draw_samples(wb)
-        loss = 0
-        wts = [ensemble_weights[i] if ensemble_weights is not None else self.calc_ensemble_ratio(samples[i][0].to(dev), wb.rows[i][-1], g)
-               for i, g in enumerate(wb.graphs)]
-        both = self.batched_all_embeds_post(wb, out, hist, BiDynamicRGCN)
+        wts = self._step_weights(wb, samples, weights)
+        both = self.batched_all_embeds_post(wb, out, hist)
         if both is not None:
-            fused = self.batched_ensemble_loss(wb, locs, recs, both, samples, wts)      # all windows' losses as one node, on the (B, N, D) tensors
+            fused = self._fused_windows_loss(wb, locs, recs, both, samples, wts)        # all windows' losses as one node, on the (B, N, D) tensors
             if fused is not None:
                 return fused
         alls = [(both[0][i], both[1][i]) if both is not None else self.get_all_embeds_Gt(locs[i], recs[i], g, wb.rows[i][-1], wb.plan, i, hist, wb.hist_loc)
                 for i, g in enumerate(wb.graphs)]
         if both is None:
-            fused = self.batched_ensemble_loss(wb, locs, recs, alls, samples, wts)
+            fused = self._fused_windows_loss(wb, locs, recs, alls, samples, wts)
             if fused is not None:
                 return fused
+        return self._window_losses(wb, locs, recs, alls, samples, wts)
+
+    def forward(self, t_list, reverse=False, target_edge_ids=None, samples=None, ensemble_weights=None, gate_weights=None):
+        wb = self.prepare(t_list, self.train_seq_len, True, target_edge_ids)
+        return self.run_loss(wb, samples, ensemble_weights if gate_weights is None else gate_weights)
+
+
+class _PostEnsembleMixin(_TwoStreamMixin):
+    """The score-level ensemble (models/PostDynamicRGCN.py:323-461, models/PostBiDynamicRGCN.py:283-372): the two MLPs and the
+    losses are _PostWindowMixin's (init_freq_mlp, calc_ensemble_ratio, batched_ensemble_loss, ensemble_loss)."""
+    _evaluater = "PostEnsembleEvaluationFilter"
+
+    def _step_weights(self, wb, samples, ensemble_weights):
+        dev = self._device()
+        return [ensemble_weights[i] if ensemble_weights is not None else self.calc_ensemble_ratio(samples[i][0].to(dev), wb.rows[i][-1], g)
+                for i, g in enumerate(wb.graphs)]
+
+    def _fused_windows_loss(self, *args):
+        return self.batched_ensemble_loss(*args)
+
+    def _window_losses(self, wb, locs, recs, alls, samples, wts):
+        dev = self._device()
+        loss = 0
         for i, g in enumerate(wb.graphs):
             triplets, neg_tail, neg_head = (x.to(dev) for x in samples[i])
             (a_loc, a_rec), (ws, wo) = alls[i], wts[i]
             loss = loss + self.ensemble_loss(locs[i], recs[i], a_loc, a_rec, triplets, neg_tail, neg_head, ws.to(dev), wo.to(dev))
         return loss
 
-    def forward(self, t_list, reverse=False, target_edge_ids=None, samples=None, ensemble_weights=None):
-        wb = self.prepare(t_list, self.train_seq_len, True, target_edge_ids)
-        return self.run_loss(wb, samples, ensemble_weights)
+    def _graph_metrics(self, loc, rec, alls, index_sample, g, t):
+        """Score-level ensemble ranks (PostEnsembleEvaluationFilter) of the (local, temporal) all-entity matrices.  The mixing
+        weights come from calc_ensemble_ratio(index_sample, t, g) (frequency MLPs).  As in the reference no classification loss."""
+        w_subject, w_object = self.calc_ensemble_ratio(index_sample, t, g)
+        return self.evaluater.calc_metrics_single_graph(loc, rec, self.rel_embeds, alls[0], alls[1], w_subject, w_object,
+                                                        index_sample, g, t), None
 
 
-# =====================================================================================================================
-# post-aggregation (embedding-level gate)
-# =====================================================================================================================
-def _post_aggregation_evaluate(self, t_list, val):
-    from .evaluation import PostEvaluationFilter
-    if not isinstance(getattr(self, "evaluater", None), PostEvaluationFilter):
-        self.evaluater = PostEvaluationFilter(self.args, self.calc_score, self.graph_dict_train, self.graph_dict_val, self.graph_dict_test)
-    graph_dict = self.graph_dict_val if val else self.graph_dict_test
-    dev = self._device()
-    with torch.no_grad():
-        wb = self.prepare(t_list, self.test_seq_len, train=False)
-        out, hist = self.run(wb)
-        ranks = []
-        for i, (loc, rec) in enumerate(zip(wb.out_loc.split(wb.target.sizes), out.split(wb.target.sizes))):
-            t = wb.rows[i][-1]
-            g = graph_dict[t]
-            if g.number_of_edges() == 0:
-                continue
-            all_loc, all_rec = self.get_all_embeds_Gt(loc, rec, g, t, wb.plan, i, hist, wb.hist_loc)
-            index_sample = torch.from_numpy(np.stack([g.src, g.rel, g.dst], axis=1)).to(dev)
-            w_sqs, w_sqo, w_oqs, w_oqo = self.calc_ensemble_ratio(index_sample, t, g)
-            ranks.append(self.evaluater.calc_metrics_single_graph(loc, rec, self.rel_embeds, all_loc, all_rec, index_sample,
-                                                                  w_sqs, w_sqo, w_oqs, w_oqo, g, t))
-    ranks = torch.cat(ranks) if ranks else torch.zeros(0, dtype=torch.int64, device=dev)
-    return ranks, float("nan")
+class PostEnsembleDynamicRGCN(_PostEnsembleMixin, ImputeDynamicRGCN):
+    """models/PostDynamicRGCN.py:323-461 (PostEnsembleDynamicRGCN: score-level ensemble with the frequency MLPs)."""
 
 
-class _PostAggregationMixin:
+class PostEnsembleBiDynamicRGCN(_PostEnsembleMixin, ImputeBiDynamicRGCN):
+    """models/PostBiDynamicRGCN.py:283-372 (score-level ensemble with the frequency MLPs) -- BASELINE config 3's model."""
+    head_scored_as_tail = True            # models/PostBiDynamicRGCN.py:294-295, see _PostWindowMixin
+
+
+class _PostAggregationMixin(_TwoStreamMixin):
     """What PostDynamicRGCN and PostBiDynamicRGCN add to the impute window models (models/PostDynamicRGCN.py:146-321,
     models/PostBiDynamicRGCN.py:179-282): four frequency MLPs, the EMBEDDING-level gate of the training loss and of evaluate().
 
@@ -590,6 +489,7 @@ class _PostAggregationMixin:
     Both scorers are linear in the candidate: the fused node (functional.batched_gated_link_prediction) mixes the two score matrices
     at the candidate columns.  Reference quirk kept: w_sqo comes from subject_query_SUBJECT_embed_linear and w_oqo from
     object_query_SUBJECT_embed_linear (calc_ensemble_ratio, :284-321), so the two *_object_embed_linear MLPs never get a gradient."""
+    _evaluater = "PostEvaluationFilter"
 
     def init_freq_mlp(self):
         """PostDynamicRGCN.init_freq_mlp, models/PostDynamicRGCN.py:152-172 (same module names => same state_dict keys)."""
@@ -615,20 +515,17 @@ class _PostAggregationMixin:
     def _agg_features(self, wb, samples):
         """Per window the frequency feature rows of the sampled triples, computed and uploaded ONCE per (prepared batch, sample set):
         a step with fixed samples then issues no host-to-device copy and can be captured as a HIP graph."""
-        c = getattr(wb, "_agg_feats", None)
-        if c is None or c[0] is not samples:
-            feats = [self.ensemble_features(samples[i][0], wb.rows[i][-1], g) if samples[i][0].shape[0] > 0 else None
-                     for i, g in enumerate(wb.graphs)]
-            c = wb._agg_feats = (samples, feats)
-        return c[1]
+        return self.per_sample_set(wb, "_agg_feats", samples, lambda: [
+            self.ensemble_features(samples[i][0], wb.rows[i][-1], g) if samples[i][0].shape[0] > 0 else None
+            for i, g in enumerate(wb.graphs)])
 
     def _batched_gates(self, wb, samples):
         """(w_known, w_cand) of the stacked rows of the fused node ([tail rows ; head rows] per window) from the model's own MLPs.
         w_sqs / w_sqo (and w_oqs / w_oqo) are the same MLP on the same features, so each MLP runs once over every window's rows
         and one tensor serves both roles (the gradient is the sum of the two roles', as for the reference's two graph nodes)."""
         feats = self._agg_features(wb, samples)
-        c = getattr(wb, "_agg_gate_rows", None)
-        if c is None or c[0] is not samples:
+
+        def gate_rows():
             sizes = [f[0].shape[0] for f in feats if f is not None]
             tot, off, perm = int(sum(sizes)), 0, []
             for n in sizes:
@@ -637,32 +534,23 @@ class _PostAggregationMixin:
                 off += n
             sub = torch.cat([f[0] for f in feats if f is not None])
             obj = torch.cat([f[1] for f in feats if f is not None])
-            c = wb._agg_gate_rows = (samples, torch.from_numpy(np.concatenate(perm)).to(self._device()), sub, obj)
-        _, perm, sub, obj = c
+            return torch.from_numpy(np.concatenate(perm)).to(self._device()), sub, obj
+        perm, sub, obj = self.per_sample_set(wb, "_agg_gate_rows", samples, gate_rows)
         w_s = torch.sigmoid(self.subject_query_subject_embed_linear(sub))
         w_o = torch.sigmoid(self.object_query_subject_embed_linear(obj))
         w = torch.cat([w_o, w_s]).index_select(0, perm)
         return w, w
 
     def _gated_fused_ok(self):
-        name = self.args.score_function
-        D = self.embed_size
-        return self.fused_loss and name in ("distmult", "complex") and self.num_ents % 4 == 0 and D % (8 if name == "complex" else 4) == 0
+        return self.fused_loss_ok(self.embed_size)
 
     def batched_gated_loss(self, wb, locs, recs, alls, samples, gates):
         """The gated loss of ALL windows as one fused node, or None when the scorer / shapes need the per-window path.
-        alls: per window (all_loc, all_rec), or the pair of (B, N_ents, D) tensors of batched_all_embeds_post; gates: per window
-        (w_sqs, w_sqo, w_oqs, w_oqo), or None for the model's own MLPs."""
+        alls: see _stacked_alls; gates: per window (w_sqs, w_sqo, w_oqs, w_oqo), or None for the model's own MLPs."""
         if not self._gated_fused_ok():
             return None
-        dev, D = self._device(), self.embed_size
-        cache = getattr(wb, "_agg_inputs", None)
-        if cache is None or cache[0] is not samples:                 # index tensors are static for a given sample set
-            offs = np.concatenate([[0], np.cumsum(wb.target.sizes)])[:-1]
-            n_rows = int(sum(wb.target.sizes))
-            inp = self.loss_inputs([int(o) for o in offs], samples, dev, n_rows, self.rel_embeds.shape[0])
-            cache = wb._agg_inputs = (samples, TF.gated_loss_inputs(inp, n_rows, dev))
-        inp = cache[1]
+        dev = self._device()
+        inp = self.cached_loss_inputs(wb, "_agg_inputs", samples, wb.target.sizes, finish=TF.gated_loss_inputs)
         if inp is None:
             return torch.cat(locs).sum() * 0.0
         if gates is None:
@@ -671,10 +559,7 @@ class _PostAggregationMixin:
             live = [gw for gw, smp in zip(gates, samples) if smp[0].shape[0] > 0]
             w_known = torch.cat([torch.cat([oqs.reshape(-1, 1), sqo.reshape(-1, 1)]) for sqs, sqo, oqs, oqo in live]).to(dev)
             w_cand = torch.cat([torch.cat([oqo.reshape(-1, 1), sqs.reshape(-1, 1)]) for sqs, sqo, oqs, oqo in live]).to(dev)
-        if isinstance(alls, tuple):
-            big_loc, big_rec = alls[0].reshape(-1, D), alls[1].reshape(-1, D)
-        else:
-            big_loc, big_rec = torch.cat([a for a, _ in alls], dim=0), torch.cat([a for _, a in alls], dim=0)
+        big_loc, big_rec = self._stacked_alls(alls)
         return TF.batched_gated_link_prediction(torch.cat(locs), torch.cat(recs), self.rel_embeds, big_loc, big_rec, w_known, w_cand,
                                                 self.args.score_function, inp)
 
@@ -694,25 +579,14 @@ class _PostAggregationMixin:
         loss_head = F.cross_entropy(self.calc_score(neg_s, r, o, mode='head'), labels)
         return loss_tail + loss_head
 
-    def run_loss(self, wb, samples=None, gate_weights=None):
-        """Post(Bi)DynamicRGCN.forward, models/PostDynamicRGCN.py:189-208 / models/PostBiDynamicRGCN.py:199-223.  gate_weights:
-        optional per-window (w_sqs, w_sqo, w_oqs, w_oqo) in place of the frequency MLPs' (tests)."""
+    def _step_weights(self, wb, samples, gate_weights):
+        return gate_weights               # the model's own gates run inside the fused node's hook (or per window, below)
+
+    def _fused_windows_loss(self, *args):
+        return self.batched_gated_loss(*args)
+
+    def _window_losses(self, wb, locs, recs, alls, samples, gate_weights):
         dev = self._device()
-        out, hist = self.run(wb)
-        recs, locs = list(out.split(wb.target.sizes)), list(wb.out_loc.split(wb.target.sizes))
-        if samples is None:
-            samples = self.draw_samples(wb)
-        both = self.batched_all_embeds_post(wb, out, hist, self._window_base)
-        if both is not None:
-            fused = self.batched_gated_loss(wb, locs, recs, both, samples, gate_weights)
-            if fused is not None:
-                return fused
-        alls = [(both[0][i], both[1][i]) if both is not None else self.get_all_embeds_Gt(locs[i], recs[i], g, wb.rows[i][-1], wb.plan, i, hist, wb.hist_loc)
-                for i, g in enumerate(wb.graphs)]
-        if both is None:
-            fused = self.batched_gated_loss(wb, locs, recs, alls, samples, gate_weights)
-            if fused is not None:
-                return fused
         feats = self._agg_features(wb, samples) if gate_weights is None else None
         loss = 0
         for i, g in enumerate(wb.graphs):
@@ -725,33 +599,18 @@ class _PostAggregationMixin:
             loss = loss + self.gated_loss(locs[i], recs[i], a_loc, a_rec, triplets, neg_tail, neg_head, *gw)
         return loss
 
-    def forward(self, t_list, reverse=False, target_edge_ids=None, samples=None, gate_weights=None):
-        wb = self.prepare(t_list, self.train_seq_len, True, target_edge_ids)
-        return self.run_loss(wb, samples, gate_weights)
-
-    def evaluate(self, t_list, val=True):
-        """Post(Bi)DynamicRGCN.evaluate / calc_metrics (models/PostDynamicRGCN.py:224-259, models/PostBiDynamicRGCN.py:244-282): window
-        loop with the local stream on the full train graphs, (local, temporal) all-entity matrices, embedding-level gated ranks
-        (PostEvaluationFilter, which mixes the known object of the head rows with its own local row).  No classification loss (nan)."""
-        return _post_aggregation_evaluate(self, t_list, val)
+    def _graph_metrics(self, loc, rec, alls, index_sample, g, t):
+        """Embedding-level gated ranks (PostEvaluationFilter, which mixes the known object of the head rows with its own local
+        row) of the (local, temporal) all-entity matrices.  No classification loss."""
+        w_sqs, w_sqo, w_oqs, w_oqo = self.calc_ensemble_ratio(index_sample, t, g)
+        return self.evaluater.calc_metrics_single_graph(loc, rec, self.rel_embeds, alls[0], alls[1], index_sample,
+                                                        w_sqs, w_sqo, w_oqs, w_oqo, g, t), None
 
 
 class PostDynamicRGCN(_PostAggregationMixin, ImputeDynamicRGCN):
     """models/PostDynamicRGCN.py:146-321 (`--post-aggregation` with GRRGCN / RRGCN)."""
-    _window_base = DynamicRGCN
-    get_all_embeds_Gt = PostEnsembleDynamicRGCN.get_all_embeds_Gt
-
-    def __init__(self, args, num_ents, num_rels, graph_dict_train, graph_dict_val, graph_dict_test, evaluater_type=None):
-        super().__init__(args, num_ents, num_rels, graph_dict_train, graph_dict_val, graph_dict_test, evaluater_type)
-        self.init_freq_mlp()
 
 
 class PostBiDynamicRGCN(_PostAggregationMixin, ImputeBiDynamicRGCN):
     """models/PostBiDynamicRGCN.py:179-282 (`--post-aggregation` with BiGRRGCN / BiRRGCN).  Its training head is the unidirectional
     class's train_link_prediction with the real corrupt_tail flag: unlike PostEnsembleBiDynamicRGCN there is no head-as-tail quirk."""
-    _window_base = BiDynamicRGCN
-    get_all_embeds_Gt = PostEnsembleBiDynamicRGCN.get_all_embeds_Gt
-
-    def __init__(self, args, num_ents, num_rels, graph_dict_train, graph_dict_val, graph_dict_test, evaluater_type=None):
-        super().__init__(args, num_ents, num_rels, graph_dict_train, graph_dict_val, graph_dict_test, evaluater_type)
-        self.init_freq_mlp()

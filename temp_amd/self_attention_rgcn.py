@@ -209,11 +209,7 @@ class SelfAttentionRGCN(DynamicRGCN):
                 return fused
         if samples is None:
             samples = self._samples_from_plan(wb) if getattr(wb, "loss_plan", None) is not None else self.draw_samples(wb)
-        cache = getattr(wb, "_loss_inputs", None)
-        if cache is None or cache[0] is not samples:
-            offs = np.concatenate([[0], np.cumsum(wb.target_sizes)])[:-1]
-            cache = wb._loss_inputs = (samples, self.loss_inputs([int(o) for o in offs], samples, dev, out.shape[0], self.rel_embeds.shape[0]))
-        fused = self.batched_link_prediction(out, cache[1], all_list)
+        fused = self.batched_link_prediction(out, self.cached_loss_inputs(wb, "_loss_inputs", samples, wb.target_sizes), all_list)
         if fused is not None:
             return fused
         loss = 0

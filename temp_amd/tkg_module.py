@@ -148,6 +148,33 @@ class TKG_Module(nn.Module):
             out["rel_inv"] = TF.gather_inverse(out["rel"].cpu().numpy(), n_rel_rows, dev)
         return out
 
+    @staticmethod
+    def per_sample_set(wb, attr, samples, build):
+        """wb.<attr> = build(), kept on the prepared batch `wb` for as long as the caller passes the SAME sample set: index tensors
+        and feature rows are static for a given one, so a step with fixed samples uploads nothing.  (Identity, not equality:
+        `samples` is a list of tensor tuples.)"""
+        c = getattr(wb, attr, None)
+        if c is None or c[0] is not samples:
+            c = (samples, build())
+            setattr(wb, attr, c)
+        return c[1]
+
+    def cached_loss_inputs(self, wb, attr, samples, sizes, finish=None, **kw):
+        """loss_inputs(...) of a prepared batch whose target graphs have `sizes` rows, cached per sample set (per_sample_set);
+        **kw goes to loss_inputs (head_as_tail), `finish(inputs, n_rows, device)` completes them for the node that reads them."""
+        def build():
+            dev = self.rel_embeds.device
+            offs = np.concatenate([[0], np.cumsum(sizes)])[:-1]
+            n_rows = int(sum(sizes))
+            inp = self.loss_inputs([int(o) for o in offs], samples, dev, n_rows, self.rel_embeds.shape[0], **kw)
+            return inp if finish is None else finish(inp, n_rows, dev)
+        return self.per_sample_set(wb, attr, samples, build)
+
+    def fused_loss_ok(self, D):
+        """The batched loss nodes apply: a bilinear scorer, and shapes inside the kernels' alignment (D = width of the query rows)."""
+        name = self.args.score_function
+        return self.fused_loss and name in ("distmult", "complex") and self.num_ents % 4 == 0 and D % (8 if name == "complex" else 4) == 0
+
     def batched_link_prediction(self, ent_rows, inputs, all_embeds):
         """Sum over the target graphs of loss_tail + loss_head (models/DynamicRGCN.py:186-193) as one fused node
         (functional.batched_link_prediction): `ent_rows` is the concatenation of the per-graph target embeddings,
@@ -156,7 +183,7 @@ class TKG_Module(nn.Module):
         outside the kernels' alignment (the caller takes the per-graph path)."""
         name = self.args.score_function
         D = ent_rows.shape[1]
-        if not (self.fused_loss and name in ("distmult", "complex") and self.num_ents % 4 == 0 and D % (8 if name == "complex" else 4) == 0):
+        if not self.fused_loss_ok(D):
             return None
         if inputs is None:
             return ent_rows.sum() * 0.0
