@@ -95,7 +95,12 @@ enum {
                                split (split_f16.hpp: per-row / per-column power-of-two scales, residual <= one fp32 rounding);
                                0: six bf16 MFMA products of the exact three-way split everywhere (gemm_bx.hpp)
                                                                                            [TEMP_MFMA=bf16x3 -> 0]    default 1 */
-  TEMP_OPT_COUNT = 10
+  TEMP_OPT_RGCN_PAIR = 10,  /* pair route of a table-fed layer (temp_rgcn_pair_fwd / _bwd).  Low two bits: 0 never, 1 where it pays
+                               (n_edges >= TEMP_PAIR_MIN_RATIO * n_rel_rows * n_table), 2 wherever the shapes are supported.
+                               Bit 2 (+4): the forward keeps the table route; bit 3 (+8): the backward keeps it.  Read by the
+                               callers that choose between temp_rgcn_table_* and temp_rgcn_pair_* (the Python package), not
+                               by the entry points themselves                                  [TEMP_RGCN_PAIR=<n>]    default 1 */
+  TEMP_OPT_COUNT = 11
 };
 int temp_set_option(int key, int value);
 int temp_get_option(int key);
@@ -107,6 +112,8 @@ long long temp_scratch_refused(void);
 long long temp_f16_launches(void);
 /* Diagnostic: edge-kernel launches (aggregation, d/dh, d/dweight) that took the LDS-tiled path (TempMembers present, member fits). */
 long long temp_tile_launches(void);
+/* Diagnostic: calls of temp_rgcn_pair_fwd / temp_rgcn_pair_bwd that launched their kernels. */
+long long temp_pair_launches(void);
 /* Development only: a device buffer of `words` int64 into which instrumented kernels write cycle-counter stamps (NULL: off).
  * Not used by the product path or the tests. */
 void temp_set_debug_buffer(void* device_ptr, size_t words);
@@ -256,6 +263,52 @@ int temp_rgcn_table_bwd(const TempGraph* g, const float* table, const int32_t* i
                         const float* out, const float* d_out_grad, int d_in, int d_out, int num_bases, int n_rel_rows, const float* weight,
                         const float* loop_w, int has_bias, int act, float* d_table, float* d_weight, float* d_loop_w, float* d_bias,
                         void* workspace, size_t workspace_bytes, const TempDropout* drop, void* stream);
+
+/* ------------------------------------------------------------------------------------------------
+ * Pair route of the table-fed layer.  The message of an edge (u, r, v) of a layer whose input is table[ids] is
+ * table[ids[u]] . BD(W[r]): it depends on the PAIR (r, ids[u]) only, not on the snapshot or the destination.  When a graph has
+ * many more edges than the n_rel_rows * n_table pairs (a union of many snapshots over a small entity set: GDELT), the block
+ * products run once per pair and the edge passes become plain row gathers:
+ *   fwd:  M[r, e] = table[e] . BD(W[r])                                 P = n_rel_rows * n_table rows
+ *         out[v]  = act( nnorm[v]^2 * sum_{(u,r) in In(v)} M[r, ids[u]]  [+ bias]  +  drop((table . W_loop)[ids[v]]) )
+ *   bwd:  G[r, e] = sum over the edges (u, r, v) with ids[u] = e of nnorm[v]^2 * dz[v]
+ *         d_table[e] = sum_r G[r, e] . BD(W[r])^T + (segsum(dzm) . W_loop^T)[e],   d_W[r] = sum_e table[e]^T (x) G[r, e] blockwise
+ * Every sum runs in a fixed order (no atomics): results are bitwise repeatable and equal temp_rgcn_table_fwd / _bwd up to fp32
+ * summation order.
+ *
+ * TempPairView is built once per (graph, ids) by the caller (temp_amd/pair_view.py), on the device:
+ *   fwd_row [by_dst.n_edges]: per position of the by_dst view's edge arrays the row of M it reads, b * n_table + ids[a]
+ *                             (positions that no chunk covers -- a device-subsampled member -- are never read)
+ *   by_pair: the edges grouped by pair in a reproducible order (stable sort of the by_dst positions by pair), as a
+ *            TempEdgeView: a = destination node, b unused (may be NULL), chunks of at most TEMP_CHUNK_PAIR edges with ordered
+ *            partial slots, n_seg = P + 1.  EVERY pair owns at least one chunk (an empty one for a pair without edges: its G
+ *            row is written as zeros).  The lists are sized from upper bounds so that no count has to reach the host:
+ *            trailing chunks are { seg = P, beg = end, slot = -1 } and trailing fix entries { seg = P, cnt = 0 }; row P of
+ *            G absorbs them.  n_partial bounds the slots in use.
+ * temp_expand_chunk_segments: seg_of[p] = chunk_seg[c] for every position p in [chunk_beg[c], chunk_end[c]) of a view, -1 for
+ * positions no chunk covers (seg_of: [n_pos], fully written) -- the per-edge segment ids the builder sorts by.
+ * Supported (temp_rgcn_pair_supported): d_in == d_out, d % 4 == 0, d <= 256, si == so in {1, 2, 4}; else TEMP_E_UNSUPPORTED.
+ * ---------------------------------------------------------------------------------------------- */
+#define TEMP_CHUNK_PAIR 128
+#define TEMP_PAIR_MIN_RATIO 4
+typedef struct TempPairView {
+  int32_t n_table;
+  int32_t n_rel_rows;
+  const int32_t* fwd_row;
+  TempEdgeView by_pair;
+} TempPairView;
+int temp_expand_chunk_segments(int n_chunks, const int32_t* chunk_seg, const int32_t* chunk_beg, const int32_t* chunk_end, int n_pos,
+                               int32_t* seg_of, void* stream);
+int temp_rgcn_pair_supported(int d_in, int d_out, int num_bases);
+size_t temp_rgcn_pair_fwd_workspace(const TempGraph* g, const TempPairView* pv, int d_out);
+int temp_rgcn_pair_fwd(const TempGraph* g, const TempPairView* pv, const float* table, const int32_t* ids, int n_table, int d_in, int d_out,
+                       int num_bases, int n_rel_rows, const float* weight, const float* loop_w, const float* bias, int act, float* out,
+                       void* workspace, size_t workspace_bytes, const TempDropout* drop, void* stream);
+size_t temp_rgcn_pair_bwd_workspace(const TempGraph* g, const TempPairView* pv, int d_in, int d_out, int num_bases);
+int temp_rgcn_pair_bwd(const TempGraph* g, const TempPairView* pv, const float* table, const int32_t* ids, const int32_t* inv_ptr,
+                       const int32_t* inv_order, int n_table, const float* out, const float* d_out_grad, int d_in, int d_out, int num_bases,
+                       int n_rel_rows, const float* weight, const float* loop_w, int has_bias, int act, float* d_table, float* d_weight,
+                       float* d_loop_w, float* d_bias, void* workspace, size_t workspace_bytes, const TempDropout* drop, void* stream);
 
 /* Isolated-entity variant (RGCNLayer.forward_isolated, models/RGCN.py:78-89):
  *   out = act( e + e . loop_w [+ bias] )          e: [n, d]                                    */

@@ -38,8 +38,12 @@ class TempGraph(ctypes.Structure):
                 ("members", TempMembers)]
 
 
+class TempPairView(ctypes.Structure):
+    _fields_ = [("n_table", ctypes.c_int32), ("n_rel_rows", ctypes.c_int32), ("fwd_row", c_vp), ("by_pair", TempEdgeView)]
+
+
 ABI_VERSION = 2            # include/temp_amd.h: TEMP_ABI_VERSION (2: TempGraph.members, chain pipeline option)
-OPT_MFMA_BF16X3, OPT_TN_SPLIT, OPT_RGCN_SCALAR, OPT_GEMM_STREAM, OPT_GRU_STREAM, OPT_RGCN_TILE, OPT_DEBUG, OPT_OVERLAP, OPT_GEMM_RESIDENT, OPT_MFMA_F16X2 = range(10)
+OPT_MFMA_BF16X3, OPT_TN_SPLIT, OPT_RGCN_SCALAR, OPT_GEMM_STREAM, OPT_GRU_STREAM, OPT_RGCN_TILE, OPT_DEBUG, OPT_OVERLAP, OPT_GEMM_RESIDENT, OPT_MFMA_F16X2, OPT_RGCN_PAIR = range(11)
 
 
 class TempGruCellFwd(ctypes.Structure):
@@ -95,6 +99,7 @@ SCORE_KINDS = {"distmult": 0, "complex": 1}
 
 # name -> (restype, argtypes); mirrors include/temp_amd.h one to one
 _G = ctypes.POINTER(TempGraph)
+_PV = ctypes.POINTER(TempPairView)
 _I, _F, _SZ = ctypes.c_int, ctypes.c_float, ctypes.c_size_t
 SYMBOLS = {
     "temp_abi_version": (_I, []),
@@ -116,6 +121,14 @@ SYMBOLS = {
     "temp_rgcn_table_bwd_workspace": (_SZ, [_G, _I, _I, _I, _I]),
     "temp_rgcn_table_bwd": (_I, [_G, c_vp, c_vp, c_vp, c_vp, _I, c_vp, c_vp, _I, _I, _I, _I, c_vp, c_vp, _I, _I, c_vp, c_vp, c_vp, c_vp,
                                  c_vp, _SZ, c_vp, c_vp]),
+    "temp_pair_launches": (ctypes.c_longlong, []),
+    "temp_expand_chunk_segments": (_I, [_I, c_vp, c_vp, c_vp, _I, c_vp, c_vp]),
+    "temp_rgcn_pair_supported": (_I, [_I, _I, _I]),
+    "temp_rgcn_pair_fwd_workspace": (_SZ, [_G, _PV, _I]),
+    "temp_rgcn_pair_fwd": (_I, [_G, _PV, c_vp, c_vp, _I, _I, _I, _I, _I, c_vp, c_vp, c_vp, _I, c_vp, c_vp, _SZ, c_vp, c_vp]),
+    "temp_rgcn_pair_bwd_workspace": (_SZ, [_G, _PV, _I, _I, _I]),
+    "temp_rgcn_pair_bwd": (_I, [_G, _PV, c_vp, c_vp, c_vp, c_vp, _I, c_vp, c_vp, _I, _I, _I, _I, c_vp, c_vp, _I, _I, c_vp, c_vp, c_vp, c_vp,
+                                c_vp, _SZ, c_vp, c_vp]),
     "temp_rgcn_isolated_fwd": (_I, [_I, _I, c_vp, c_vp, c_vp, _I, c_vp, c_vp, c_vp]),
     "temp_rgcn_isolated_bwd_workspace": (_SZ, [_I, _I]),
     "temp_rgcn_isolated_bwd": (_I, [_I, _I, c_vp, c_vp, c_vp, c_vp, _I, _I, c_vp, c_vp, c_vp, c_vp, _SZ, c_vp, c_vp]),

@@ -170,6 +170,52 @@ class HipBackend:
         _lib.check(rc, "temp_rgcn_table_bwd")
         return d_table, d_w, d_loop, d_bias
 
+    # ---- pair route of the table-fed layer (include/temp_amd.h: TempPairView) -------------------------------------------------
+    def pair_mode(self):
+        """TEMP_OPT_RGCN_PAIR: (0 never / 1 where it pays / 2 wherever supported, forward allowed, backward allowed)."""
+        o = self.lib.temp_get_option(_lib.OPT_RGCN_PAIR)
+        return o & 3, not (o & 4), not (o & 8)
+
+    def pair_supported(self, d_in, d_out, num_bases):
+        return bool(self.lib.temp_rgcn_pair_supported(int(d_in), int(d_out), int(num_bases)))
+
+    def expand_chunk_segments(self, chunk_seg, chunk_beg, chunk_end, n_pos):
+        seg_of = torch.empty(n_pos, dtype=torch.int32, device=chunk_seg.device)
+        rc = self.lib.temp_expand_chunk_segments(int(chunk_seg.shape[0]), _ptr(_i32(chunk_seg, "chunk_seg")), _ptr(_i32(chunk_beg, "chunk_beg")),
+                                                 _ptr(_i32(chunk_end, "chunk_end")), int(n_pos), _ptr(seg_of), _stream())
+        _lib.check(rc, "temp_expand_chunk_segments")
+        return seg_of
+
+    def rgcn_pair_fwd(self, dg, pv, table, ids, weight, loop_w, bias, num_bases, act, drop=None):
+        """rgcn_table_fwd through the pair view `pv` of (dg, ids) (include/temp_amd.h: temp_rgcn_pair_fwd)."""
+        table, weight, loop_w, bias = _f32(table, "table"), _f32(weight, "weight"), _f32(loop_w, "loop_weight"), _f32(bias, "bias")
+        ids = _i32(ids, "ids")
+        d_in, d_out = loop_w.shape
+        out = torch.empty(dg.n_nodes, d_out, dtype=torch.float32, device=table.device)
+        ws = self._ws(self.lib.temp_rgcn_pair_fwd_workspace(dg.ref(), pv.ref(), d_out), table.device)
+        rc = self.lib.temp_rgcn_pair_fwd(dg.ref(), pv.ref(), _ptr(table), _ptr(ids), table.shape[0], d_in, d_out, num_bases, weight.shape[0],
+                                         _ptr(weight), _ptr(loop_w), _ptr(bias), act, _ptr(out), _ptr(ws), ws.numel(), _drop(drop), _stream())
+        _lib.check(rc, "temp_rgcn_pair_fwd")
+        return out
+
+    def rgcn_pair_bwd(self, dg, pv, table, ids, inverse, out, d_out_grad, weight, loop_w, has_bias, num_bases, act, drop=None):
+        """rgcn_table_bwd through the pair view -> (d_table, d_weight, d_loop_w, d_bias)."""
+        table, out, g = _f32(table, "table"), _f32(out, "out"), _f32(d_out_grad, "d_out")
+        weight, loop_w = _f32(weight, "weight"), _f32(loop_w, "loop_weight")
+        ids, inv_ptr, inv_order = _i32(ids, "ids"), _i32(inverse[0], "inv_ptr"), _i32(inverse[1], "inv_order")
+        d_in, d_out = loop_w.shape
+        dev = table.device
+        d_table = torch.empty_like(table)
+        d_w = torch.empty_like(weight)
+        d_loop = torch.empty_like(loop_w)
+        d_bias = torch.empty(d_out, dtype=torch.float32, device=dev) if has_bias else None
+        ws = self._ws(self.lib.temp_rgcn_pair_bwd_workspace(dg.ref(), pv.ref(), d_in, d_out, num_bases), dev)
+        rc = self.lib.temp_rgcn_pair_bwd(dg.ref(), pv.ref(), _ptr(table), _ptr(ids), _ptr(inv_ptr), _ptr(inv_order), table.shape[0], _ptr(out), _ptr(g),
+                                         d_in, d_out, num_bases, weight.shape[0], _ptr(weight), _ptr(loop_w), int(has_bias), act,
+                                         _ptr(d_table), _ptr(d_w), _ptr(d_loop), _ptr(d_bias), _ptr(ws), ws.numel(), _drop(drop), _stream())
+        _lib.check(rc, "temp_rgcn_pair_bwd")
+        return d_table, d_w, d_loop, d_bias
+
     def rgcn_isolated_fwd(self, e, loop_w, bias, act, drop=None):
         e, loop_w, bias = _f32(e, "e"), _f32(loop_w, "loop_weight"), _f32(bias, "bias")
         out = torch.empty_like(e)

@@ -1198,6 +1198,7 @@ static const bool g_options_init = [] {
   g_options[TEMP_OPT_MFMA_BF16X3] = 1; g_options[TEMP_OPT_TN_SPLIT] = 1; g_options[TEMP_OPT_RGCN_SCALAR] = 1;
   g_options[TEMP_OPT_GEMM_STREAM] = 0; g_options[TEMP_OPT_GRU_STREAM] = 0; g_options[TEMP_OPT_RGCN_TILE] = 1; g_options[TEMP_OPT_DEBUG] = 0; g_options[TEMP_OPT_OVERLAP] = 1; g_options[TEMP_OPT_GEMM_RESIDENT] = 1;
   g_options[TEMP_OPT_MFMA_F16X2] = 1;
+  g_options[TEMP_OPT_RGCN_PAIR] = 1;
   const char* e;
   if ((e = getenv("TEMP_MFMA")) && e[0] == 'f' && e[1] == '3') g_options[TEMP_OPT_MFMA_BF16X3] = 0;      // f32
   if ((e = getenv("TEMP_MFMA")) && e[0] == 'b') g_options[TEMP_OPT_MFMA_F16X2] = 0;                       // bf16x3
@@ -1209,6 +1210,7 @@ static const bool g_options_init = [] {
   if ((e = getenv("TEMP_OVERLAP")) && e[0] == '0') g_options[TEMP_OPT_OVERLAP] = 0;
   if ((e = getenv("TEMP_GEMM_RESIDENT")) && e[0] == '0') g_options[TEMP_OPT_GEMM_RESIDENT] = 0;
   if ((e = getenv("TEMP_DEBUG"))) g_options[TEMP_OPT_DEBUG] = atoi(e);
+  if ((e = getenv("TEMP_RGCN_PAIR")) && e[0] >= '0' && e[0] <= '9') g_options[TEMP_OPT_RGCN_PAIR] = atoi(e);
   return true;
 }();
 int option(int key) { return (key >= 0 && key < TEMP_OPT_COUNT) ? g_options[key].load(std::memory_order_relaxed) : -1; }
@@ -1226,7 +1228,9 @@ const char* temp_trace_kernel_name(int id) {
                                 "k_scatter_add_rows", "k_decay_grad", "k_copy", "k_gemm_panel<isolated>", "k_gemm_panel<gru_gi>",
                                 "k_gemm_panel<linear>", "k_gather_ce", "k_sa_attn_fwd", "k_sa_attn_bwd", "k_gru_chain_fwd", "k_gru_chain_bwd",
                                 "k_gru_chain_pack", "k_bx_pack", "k_gemm_tn_bx8", "k_gemm_tn_bx", "k_gru_wgrad", "k_segment_sum_rows", "k_absmax_keys",
-                                "k_gated_query", "k_gather_ce_mix"};
+                                "k_gated_query", "k_gather_ce_mix", "k_pair_msg", "k_pair_gather<fwd>", "k_pair_fix_epi", "k_pair_gather<bwd>",
+                                "k_pair_dtable", "k_pair_dw"};
+  static_assert(sizeof(names) / sizeof(names[0]) == K_COUNT, "one name per KernelId");
   return (id >= 0 && id < K_COUNT) ? names[id] : "?";
 }
 

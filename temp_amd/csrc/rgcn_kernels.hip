@@ -894,6 +894,272 @@ static int dw_forked(SideScope& sc, const TempEdgeView& v, const TempMembers* mb
   return dw_forked(sc, v, mb, x, x_ids, dz, nnorm, d_in, d_out, num_bases, n_rel_rows, dW, partial, [](hipStream_t) { return (int)TEMP_OK; });
 }
 
+// ---------------------------------------------------------------------------------------------
+// Pair route of the table-fed layer (include/temp_amd.h: TempPairView).  The message of an edge depends on (relation, table
+// row of its source) only, so the block products run once per pair -- P = n_rel_rows * n_table rows instead of one per edge --
+// and both edge passes are row gathers with ordered sums: no weights, no LDS, no products.
+// ---------------------------------------------------------------------------------------------
+static std::atomic<long long> g_pair_launches{0};           // diagnostic (temp_pair_launches)
+
+// M[r * n_table + e] = table[e] . BD(W[r]); one thread per float4 of M
+template <int S>
+__global__ void __launch_bounds__(256) k_pair_msg(int n_rows, int n_table, int D, const float* __restrict__ table, const float* __restrict__ W,
+                                                  float* __restrict__ M) {
+  const int D4 = D >> 2;
+  const size_t total = (size_t)n_rows * D4;
+  for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (size_t)gridDim.x * blockDim.x) {
+    const int row = (int)(i / (unsigned)D4), f = ((int)(i - (size_t)row * D4)) << 2;
+    const int r = row / n_table, e = row - r * n_table;
+    const float* wr = W + (size_t)r * (D * S) + f * S;
+    float4 w[S];
+#pragma unroll
+    for (int j = 0; j < S; ++j) w[j] = ld4(wr + 4 * j);
+    float4 acc = zero4();
+    block_mac<S, MODE_FWD>(acc, ld4(table + (size_t)e * D + f), w, 1.f);
+    st4(M + (size_t)row * D + f, acc);
+  }
+}
+
+// Ordered sum of the rows a chunk lists: rows[idx[p]] for p in [beg, end), SCALE: each times nnorm[idx[p]]^2.  One wave; the lane
+// owns 4 features; the ids of 64 edges are loaded at once and handed out through SGPRs (v_readlane), eight rows in flight.
+template <bool SCALE>
+__device__ __forceinline__ float4 pair_rows_sum(const int32_t* __restrict__ idx, int beg, int end, const float* __restrict__ rows, int D,
+                                                const float* __restrict__ nnorm, int lane, bool active) {
+  float4 acc = zero4();
+  const int f = lane << 2;
+  for (int b0 = beg; b0 < end; b0 += 64) {
+    const int cnt = min(64, end - b0);
+    int r_l = 0;
+    float s_l = 0.f;
+    if (lane < cnt) {
+      r_l = idx[b0 + lane];
+      if (SCALE) { const float nn = nnorm[r_l]; s_l = nn * nn; }
+    }
+    if (active) {                                              // lanes past the row only hold ids: they issue no row loads
+      auto row = [&](int i) { return ld4(rows + (size_t)__builtin_amdgcn_readlane(r_l, i) * D + f); };
+      auto add = [&](int i, const float4 x) {
+        if (SCALE) acc = fma4(__builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, s_l), i)), x, acc);
+        else acc = add4(acc, x);
+      };
+      int e = 0;
+      for (; e + 8 <= cnt; e += 8) {
+        float4 x[8];
+#pragma unroll
+        for (int u = 0; u < 8; ++u) x[u] = row(e + u);
+#pragma unroll
+        for (int u = 0; u < 8; ++u) add(e + u, x[u]);
+      }
+      for (; e + 2 <= cnt; e += 2) {
+        const float4 x0 = row(e), x1 = row(e + 1);
+        add(e, x0);
+        add(e + 1, x1);
+      }
+      if (e < cnt) add(e, row(e));
+    }
+  }
+  return acc;
+}
+
+// what k_loop_gather_epi does to a finished aggregation row: + the (dropped-out) self-loop row of the node's table row, + bias, act
+__device__ __forceinline__ float4 pair_epilogue(float4 v, int node, int f, int D, const int32_t* __restrict__ ids, const float* __restrict__ t_loop,
+                                                const float* __restrict__ bias, int act, const DropSpec& drop) {
+  float4 lm = ld4(t_loop + (size_t)ids[node] * D + f);
+  if (drop.p > 0.f) lm = drop4(drop, (unsigned)node, (unsigned)f, lm);
+  v = add4(v, lm);
+  if (bias) v = add4(v, ld4(bias + f));
+  if (act == TEMP_ACT_RELU) v = make_float4(fmaxf(v.x, 0.f), fmaxf(v.y, 0.f), fmaxf(v.z, 0.f), fmaxf(v.w, 0.f));
+  return v;
+}
+
+// Forward: view = by-dst; fwd_row[p] = the row of M that edge position p reads.  A chunk that is its whole segment is finished
+// here (epilogue included); chunks of a multi-chunk segment go to their partial slots and k_pair_fix_epi.
+__global__ void __launch_bounds__(256) k_pair_gather_fwd(TempEdgeView v, const int32_t* __restrict__ fwd_row, const float* __restrict__ M,
+                                                         const float* __restrict__ nnorm, int D, const int32_t* __restrict__ ids,
+                                                         const float* __restrict__ t_loop, const float* __restrict__ bias, int act, DropSpec drop,
+                                                         float* __restrict__ out, float* __restrict__ partial) {
+  const int lane = threadIdx.x & 63;
+  const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), wpb = blockDim.x >> 6;
+  const int f = lane << 2;
+  const bool active = lane < (D >> 2);
+  ItemRange it = xcd_chunks(v.n_chunks, v.n_edges, v.chunk_beg, wpb);
+  for (int c = it.beg + wave; c < it.end; c += it.stride) {
+    const int seg = __builtin_amdgcn_readfirstlane(v.chunk_seg[c]), beg = __builtin_amdgcn_readfirstlane(v.chunk_beg[c]);
+    const int end = __builtin_amdgcn_readfirstlane(v.chunk_end[c]), slot = __builtin_amdgcn_readfirstlane(v.chunk_slot[c]);
+    float4 acc = pair_rows_sum<false>(fwd_row, beg, end, M, D, nullptr, lane, active);
+    if (!active) continue;
+    const float nn = nnorm[seg];
+    acc = scale4(acc, nn * nn);
+    if (slot < 0) st4(out + (size_t)seg * D + f, pair_epilogue(acc, seg, f, D, ids, t_loop, bias, act, drop));
+    else st4(partial + (size_t)slot * D + f, acc);
+  }
+}
+
+// The rows k_pair_gather_fwd did not finish: the multi-chunk segments (ordered sum of their partial slots, then the epilogue) and
+// the nodes without an incoming edge (no chunk: the epilogue of a zero row).  One wave per item.
+// A node of a device-subsampled member whose edges were all dropped keeps its (now empty) chunks: its row is then written here as
+// well as by the chunk's wave / the fix loop -- the same bits (0 + epilogue) both times, so the double store is harmless and intended.
+__global__ void __launch_bounds__(256) k_pair_fix_epi(int n_fix, const int32_t* __restrict__ fix_seg, const int32_t* __restrict__ fix_slot,
+                                                      const int32_t* __restrict__ fix_cnt, const float* __restrict__ partial, int n_nodes,
+                                                      const int32_t* __restrict__ in_deg, int D, const int32_t* __restrict__ ids,
+                                                      const float* __restrict__ t_loop, const float* __restrict__ bias, int act, DropSpec drop,
+                                                      float* __restrict__ out) {
+  const int lane = threadIdx.x & 63, wpb = blockDim.x >> 6;
+  const int gw = blockIdx.x * wpb + (threadIdx.x >> 6), waves = gridDim.x * wpb;
+  const int f = lane << 2;
+  if (f >= D) return;
+  for (int i = gw; i < n_fix; i += waves) {
+    const int seg = fix_seg[i];
+    st4(out + (size_t)seg * D + f, pair_epilogue(fixup_walk(partial + (size_t)fix_slot[i] * D + f, 0, fix_cnt[i], D), seg, f, D, ids, t_loop, bias, act, drop));
+  }
+  for (int node = gw; node < n_nodes; node += waves)
+    if (in_deg[node] <= 0) st4(out + (size_t)node * D + f, pair_epilogue(zero4(), node, f, D, ids, t_loop, bias, act, drop));
+}
+
+// Backward: view = by-pair (a = destination node).  G[pair] = sum over the pair's edges of nnorm[dst]^2 * dz[dst], in list order.
+__global__ void __launch_bounds__(256) k_pair_gather_bwd(TempEdgeView v, const float* __restrict__ dz, const float* __restrict__ nnorm, int D,
+                                                         float* __restrict__ G, float* __restrict__ partial) {
+  const int lane = threadIdx.x & 63;
+  const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), wpb = blockDim.x >> 6;
+  const int f = lane << 2;
+  const bool active = lane < (D >> 2);
+  for (int c = blockIdx.x * wpb + wave; c < v.n_chunks; c += gridDim.x * wpb) {
+    const int seg = __builtin_amdgcn_readfirstlane(v.chunk_seg[c]), beg = __builtin_amdgcn_readfirstlane(v.chunk_beg[c]);
+    const int end = __builtin_amdgcn_readfirstlane(v.chunk_end[c]), slot = __builtin_amdgcn_readfirstlane(v.chunk_slot[c]);
+    const float4 acc = pair_rows_sum<true>(v.a, beg, end, dz, D, nnorm, lane, active);
+    if (active) st4((slot < 0 ? G + (size_t)seg * D : partial + (size_t)slot * D) + f, acc);
+  }
+}
+
+// d_table[e] = sum_r G[r * n_table + e] . BD(W[r])^T, relations in order; one thread per float4 of d_table
+template <int S>
+__global__ void __launch_bounds__(64) k_pair_dtable(int n_table, int n_rel_rows, int D, const float* __restrict__ G, const float* __restrict__ W,
+                                                    float* __restrict__ d_table) {
+  const int D4 = D >> 2;
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n_table * D4) return;
+  const int e = i / D4, f = (i - e * D4) << 2;
+  float4 acc = zero4();
+#pragma unroll 4
+  for (int r = 0; r < n_rel_rows; ++r) {
+    const float* wr = W + (size_t)r * (D * S) + f * S;
+    float4 w[S];
+#pragma unroll
+    for (int j = 0; j < S; ++j) w[j] = ld4(wr + 4 * j);
+    block_mac<S, MODE_DX>(acc, ld4(G + ((size_t)r * n_table + e) * D + f), w, 1.f);
+  }
+  st4(d_table + (size_t)e * D + f, acc);
+}
+
+// d_W[r] = sum_e table[e]^T (x) G[r * n_table + e] blockwise.  One 16-wave block per relation row: wave w sums its contiguous share
+// of the table rows in order, the shares are added in wave order.
+template <int S>
+__global__ void __launch_bounds__(1024) k_pair_dw(int n_table, int D, const float* __restrict__ table, const float* __restrict__ G,
+                                                  float* __restrict__ dW) {
+  __shared__ float4 share[16][64];
+  const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  const int r = blockIdx.x, f = lane << 2;
+  const bool active = f < D;
+  const int per = (n_table + 15) >> 4;
+  const int e0 = min(n_table, wave * per), e1 = min(n_table, e0 + per);
+  float4 acc[S];
+#pragma unroll
+  for (int j = 0; j < S; ++j) acc[j] = zero4();
+  if (active) {
+    const float* g = G + (size_t)r * n_table * D + f;
+#pragma unroll 4
+    for (int e = e0; e < e1; ++e) {
+      const float4 xx = ld4(table + (size_t)e * D + f), gg = ld4(g + (size_t)e * D);
+      if (S == 1) {
+        acc[0].x = fmaf(xx.x, gg.x, acc[0].x);
+        acc[0].y = fmaf(xx.y, gg.y, acc[0].y);
+        acc[0].z = fmaf(xx.z, gg.z, acc[0].z);
+        acc[0].w = fmaf(xx.w, gg.w, acc[0].w);
+      } else if (S == 2) {
+        acc[0].x = fmaf(xx.x, gg.x, acc[0].x);
+        acc[0].y = fmaf(xx.x, gg.y, acc[0].y);
+        acc[0].z = fmaf(xx.y, gg.x, acc[0].z);
+        acc[0].w = fmaf(xx.y, gg.y, acc[0].w);
+        acc[1].x = fmaf(xx.z, gg.z, acc[1].x);
+        acc[1].y = fmaf(xx.z, gg.w, acc[1].y);
+        acc[1].z = fmaf(xx.w, gg.z, acc[1].z);
+        acc[1].w = fmaf(xx.w, gg.w, acc[1].w);
+      } else {
+        acc[0] = fma4(xx.x, gg, acc[0]);
+        acc[1] = fma4(xx.y, gg, acc[1]);
+        acc[2] = fma4(xx.z, gg, acc[2]);
+        acc[3] = fma4(xx.w, gg, acc[3]);
+      }
+    }
+  }
+#pragma unroll
+  for (int j = 0; j < S; ++j) {
+    share[wave][lane] = acc[j];
+    __syncthreads();
+    if (wave == 0 && active) {
+      float4 t = share[0][lane];
+#pragma unroll
+      for (int u = 1; u < 16; ++u) t = add4(t, share[u][lane]);
+      st4(dW + (size_t)r * (D * S) + f * S + 4 * j, t);
+    }
+    __syncthreads();
+  }
+}
+
+// seg_of[p] = chunk_seg[c] for p in [chunk_beg[c], chunk_end[c]); one wave per chunk (seg_of was filled with -1)
+__global__ void __launch_bounds__(256) k_expand_chunk_seg(int n_chunks, const int32_t* __restrict__ chunk_seg, const int32_t* __restrict__ chunk_beg,
+                                                          const int32_t* __restrict__ chunk_end, int n_pos, int32_t* __restrict__ seg_of) {
+  const int lane = threadIdx.x & 63, wpb = blockDim.x >> 6;
+  for (int c = blockIdx.x * wpb + (threadIdx.x >> 6); c < n_chunks; c += gridDim.x * wpb) {
+    const int seg = chunk_seg[c], beg = max(0, chunk_beg[c]), end = min(n_pos, chunk_end[c]);
+    for (int p = beg + lane; p < end; p += 64) seg_of[p] = seg;
+  }
+}
+
+static bool pair_view_ok(const TempGraph* g, const TempPairView* pv, int n_table, int n_rel_rows) {
+  if (!g || !pv || pv->n_table != n_table || pv->n_rel_rows != n_rel_rows) return false;
+  const TempEdgeView& v = pv->by_pair;
+  if (v.n_seg != n_rel_rows * n_table + 1 || v.n_chunks < 0 || v.n_partial < 0 || v.n_fix < 0) return false;
+  if ((v.n_edges > 0 && !v.a) || !v.chunk_seg || !v.chunk_beg || !v.chunk_end || !v.chunk_slot) return false;     // (every pair owns a chunk)
+  if (v.n_fix > 0 && (!v.fix_seg || !v.fix_slot || !v.fix_cnt)) return false;
+  return g->by_dst.n_edges == 0 || pv->fwd_row != nullptr;
+}
+
+struct PairFwdWs { float *partial, *t_loop, *M; size_t total; };
+static PairFwdWs carve_pair_fwd(const TempGraph* g, const TempPairView* pv, int d_out, char* base) {
+  PairFwdWs w;
+  size_t off = 0;
+  auto take = [&](size_t bytes) { char* p = base ? base + off : nullptr; off += align_up(bytes, 256); return p; };
+  w.partial = (float*)take((size_t)g->by_dst.n_partial * d_out * sizeof(float));
+  w.t_loop = (float*)take((size_t)pv->n_table * d_out * sizeof(float));
+  w.M = (float*)take((size_t)pv->n_rel_rows * pv->n_table * d_out * sizeof(float));
+  w.total = off + 256;
+  return w;
+}
+
+struct PairBwdWs {
+  float *dz, *dzm, *G, *part, *seg_dz;
+  void *ss, *tn, *cs;
+  size_t ss_bytes, tn_bytes, cs_bytes, total;
+};
+static PairBwdWs carve_pair_bwd(const TempGraph* g, const TempPairView* pv, int d_in, int d_out, char* base) {
+  PairBwdWs w;
+  size_t off = 0;
+  auto take = [&](size_t bytes) { char* p = base ? base + off : nullptr; off += align_up(bytes, 256); return p; };
+  w.dz = (float*)take((size_t)g->n_nodes * d_out * sizeof(float));
+  w.dzm = (float*)take((size_t)g->n_nodes * d_out * sizeof(float));
+  w.G = (float*)take((size_t)pv->by_pair.n_seg * d_out * sizeof(float));
+  w.part = (float*)take(partial_bytes(pv->by_pair.n_partial, d_out));
+  w.seg_dz = (float*)take((size_t)pv->n_table * d_out * sizeof(float));
+  w.ss_bytes = segment_sum_rows_workspace(pv->n_table, g->n_nodes, d_out);
+  w.ss = take(w.ss_bytes);
+  w.tn_bytes = gemm_tn_workspace(pv->n_table, d_in, d_out);
+  w.tn = take(w.tn_bytes);
+  w.cs_bytes = colsum_workspace(g->n_nodes, d_out);
+  w.cs = take(w.cs_bytes);
+  w.total = off + 256;
+  return w;
+}
+
 struct TableBwdWs {
   float *dz, *dzm, *d_h, *part_dx, *part_dw, *seg_dz;
   void *tn, *cs;
@@ -1023,6 +1289,144 @@ int temp_rgcn_table_bwd(const TempGraph* g, const float* table, const int32_t* i
     if (rc) return rc;
   }
   return side.join();
+}
+
+long long temp_pair_launches(void) { return g_pair_launches.load(std::memory_order_relaxed); }
+
+int temp_expand_chunk_segments(int n_chunks, const int32_t* chunk_seg, const int32_t* chunk_beg, const int32_t* chunk_end, int n_pos,
+                               int32_t* seg_of, void* stream) {
+  if (n_chunks < 0 || n_pos < 0 || (n_pos > 0 && !seg_of) || (n_chunks > 0 && (!chunk_seg || !chunk_beg || !chunk_end))) return TEMP_E_BADARG;
+  if (n_pos == 0) return TEMP_OK;
+  hipStream_t st = (hipStream_t)stream;
+  if (hipMemsetAsync(seg_of, 0xff, (size_t)n_pos * sizeof(int32_t), st) != hipSuccess) return TEMP_E_LAUNCH;
+  if (n_chunks == 0) return TEMP_OK;
+  int grid = ceil_div(n_chunks, 4);
+  if (grid > 4096) grid = 4096;
+  TEMP_LAUNCH(K_COPY, k_expand_chunk_seg, dim3(grid), dim3(256), 0, st, n_chunks, chunk_seg, chunk_beg, chunk_end, n_pos, seg_of);
+  return launch_status();
+}
+
+int temp_rgcn_pair_supported(int d_in, int d_out, int num_bases) {
+  int S = 0;
+  return fast_shape(d_in, d_out, num_bases, &S) ? 1 : 0;
+}
+
+size_t temp_rgcn_pair_fwd_workspace(const TempGraph* g, const TempPairView* pv, int d_out) {
+  if (!g || !pv || d_out <= 0 || pv->n_table < 0 || pv->n_rel_rows < 0) return 0;
+  return carve_pair_fwd(g, pv, d_out, nullptr).total;
+}
+
+int temp_rgcn_pair_fwd(const TempGraph* g, const TempPairView* pv, const float* table, const int32_t* ids, int n_table, int d_in, int d_out,
+                       int num_bases, int n_rel_rows, const float* weight, const float* loop_w, const float* bias, int act, float* out,
+                       void* workspace, size_t workspace_bytes, const TempDropout* drop, void* stream) {
+  if (!g || !pv || !table || !weight || !loop_w || !out || n_table <= 0 || d_in <= 0 || d_out <= 0 || num_bases <= 0 || n_rel_rows <= 0) return TEMP_E_BADARG;
+  int S = 0;
+  if (!fast_shape(d_in, d_out, num_bases, &S)) return TEMP_E_UNSUPPORTED;
+  if ((long long)n_rel_rows * n_table >= (1LL << 31) / d_out) return TEMP_E_UNSUPPORTED;
+  if (g->n_nodes < 0 || !view_ok(g->by_dst) || !pair_view_ok(g, pv, n_table, n_rel_rows) || (g->n_nodes > 0 && (!g->nnorm || !g->in_deg || !ids))) return TEMP_E_BADARG;
+  if (act != TEMP_ACT_NONE && act != TEMP_ACT_RELU) return TEMP_E_BADARG;
+  if (!workspace || workspace_bytes < temp_rgcn_pair_fwd_workspace(g, pv, d_out)) return TEMP_E_WORKSPACE;
+  if (g->n_nodes == 0) return TEMP_OK;
+  hipStream_t st = (hipStream_t)stream;
+  const PairFwdWs w = carve_pair_fwd(g, pv, d_out, (char*)workspace);
+  const int D = d_in, P = n_rel_rows * n_table;
+  int grid = ceil_div((long long)P * (D / 4), 256);
+  if (grid > 8192) grid = 8192;
+  if (S == 1) TEMP_LAUNCH(K_PAIR_MSG, k_pair_msg<1>, dim3(grid), dim3(256), 0, st, P, n_table, D, table, weight, w.M);
+  else if (S == 2) TEMP_LAUNCH(K_PAIR_MSG, k_pair_msg<2>, dim3(grid), dim3(256), 0, st, P, n_table, D, table, weight, w.M);
+  else TEMP_LAUNCH(K_PAIR_MSG, k_pair_msg<4>, dim3(grid), dim3(256), 0, st, P, n_table, D, table, weight, w.M);
+  int rc = gemm_add_bias_act(K_GEMM_ISO, n_table, d_out, d_in, table, d_in, nullptr, loop_w, d_out, 0, nullptr, 0, nullptr, nullptr, TEMP_ACT_NONE,
+                             w.t_loop, d_out, st);
+  if (rc) return rc;
+  const DropSpec ds = drop_spec(drop);
+  const TempEdgeView& v = g->by_dst;
+  if (v.n_chunks > 0) {
+    grid = (v.n_chunks + 3) / 4;
+    grid = grid < 8 ? 8 : (grid > 4096 ? 4096 : (grid + 7) / 8 * 8);
+    TEMP_LAUNCH(K_PAIR_GATHER_FWD, k_pair_gather_fwd, dim3(grid), dim3(256), 0, st, v, pv->fwd_row, w.M, g->nnorm, D, ids, w.t_loop, bias, act, ds, out,
+                w.partial);
+  }
+  const int items = v.n_fix > (g->n_nodes + 7) / 8 ? v.n_fix : (g->n_nodes + 7) / 8;
+  grid = (items + 3) / 4;
+  if (grid > 4096) grid = 4096;
+  TEMP_LAUNCH(K_PAIR_FIX_EPI, k_pair_fix_epi, dim3(grid), dim3(256), 0, st, v.n_fix, v.fix_seg, v.fix_slot, v.fix_cnt, w.partial, g->n_nodes, g->in_deg, D,
+              ids, w.t_loop, bias, act, ds, out);
+  g_pair_launches.fetch_add(1, std::memory_order_relaxed);
+  return launch_status();
+}
+
+size_t temp_rgcn_pair_bwd_workspace(const TempGraph* g, const TempPairView* pv, int d_in, int d_out, int num_bases) {
+  if (!g || !pv || num_bases <= 0 || d_in <= 0 || d_out <= 0 || pv->n_table < 0 || pv->by_pair.n_seg < 0) return 0;
+  return carve_pair_bwd(g, pv, d_in, d_out, nullptr).total;
+}
+
+int temp_rgcn_pair_bwd(const TempGraph* g, const TempPairView* pv, const float* table, const int32_t* ids, const int32_t* inv_ptr,
+                       const int32_t* inv_order, int n_table, const float* out, const float* d_out_grad, int d_in, int d_out, int num_bases,
+                       int n_rel_rows, const float* weight, const float* loop_w, int has_bias, int act, float* d_table, float* d_weight,
+                       float* d_loop_w, float* d_bias, void* workspace, size_t workspace_bytes, const TempDropout* drop, void* stream) {
+  if (!g || !pv || !table || !d_out_grad || !weight || !loop_w || !d_table || !d_weight || !d_loop_w || !inv_ptr) return TEMP_E_BADARG;
+  if (n_table <= 0 || d_in <= 0 || d_out <= 0 || num_bases <= 0 || n_rel_rows <= 0) return TEMP_E_BADARG;
+  int S = 0;
+  if (!fast_shape(d_in, d_out, num_bases, &S)) return TEMP_E_UNSUPPORTED;
+  if ((long long)n_rel_rows * n_table >= (1LL << 31) / d_out) return TEMP_E_UNSUPPORTED;
+  if (act == TEMP_ACT_RELU && !out) return TEMP_E_BADARG;
+  if (act != TEMP_ACT_NONE && act != TEMP_ACT_RELU) return TEMP_E_BADARG;
+  if (has_bias && !d_bias) return TEMP_E_BADARG;
+  if (g->n_nodes < 0 || !pair_view_ok(g, pv, n_table, n_rel_rows) || (g->n_nodes > 0 && (!g->nnorm || !ids || !inv_order))) return TEMP_E_BADARG;
+  if (!workspace || workspace_bytes < temp_rgcn_pair_bwd_workspace(g, pv, d_in, d_out, num_bases)) return TEMP_E_WORKSPACE;
+  hipStream_t st = (hipStream_t)stream;
+  const size_t wrow = (size_t)d_in * S;
+  if (g->n_nodes == 0) {
+    if (hipMemsetAsync(d_table, 0, (size_t)n_table * d_in * sizeof(float), st) != hipSuccess) return TEMP_E_LAUNCH;
+    if (hipMemsetAsync(d_weight, 0, (size_t)n_rel_rows * wrow * sizeof(float), st) != hipSuccess) return TEMP_E_LAUNCH;
+    if (hipMemsetAsync(d_loop_w, 0, (size_t)d_in * d_out * sizeof(float), st) != hipSuccess) return TEMP_E_LAUNCH;
+    if (has_bias && hipMemsetAsync(d_bias, 0, (size_t)d_out * sizeof(float), st) != hipSuccess) return TEMP_E_LAUNCH;
+    return TEMP_OK;
+  }
+  const PairBwdWs w = carve_pair_bwd(g, pv, d_in, d_out, (char*)workspace);
+  const int D = d_in;
+  const float* dz = d_out_grad;
+  int rc;
+  if (act == TEMP_ACT_RELU) {
+    rc = relu_bwd((size_t)g->n_nodes * d_out, out, d_out_grad, w.dz, st);
+    if (rc) return rc;
+    dz = w.dz;
+  }
+  // G: one ordered gather-sum by pair (every pair owns a chunk, so every row of G is written), then the multi-chunk pairs
+  const TempEdgeView& v = pv->by_pair;
+  int grid = (v.n_chunks + 3) / 4;
+  grid = grid < 1 ? 1 : (grid > 4096 ? 4096 : grid);
+  TEMP_LAUNCH(K_PAIR_GATHER_BWD, k_pair_gather_bwd, dim3(grid), dim3(256), 0, st, v, dz, g->nnorm, D, w.G, w.part);
+  launch_fixup(v, w.part, D, w.G, st);
+  // the two P-row products: d_table (aggregation part) and the relation weights
+  grid = ceil_div((long long)n_table * (D / 4), 64);
+  if (S == 1) TEMP_LAUNCH(K_PAIR_DTABLE, k_pair_dtable<1>, dim3(grid), dim3(64), 0, st, n_table, n_rel_rows, D, w.G, weight, d_table);
+  else if (S == 2) TEMP_LAUNCH(K_PAIR_DTABLE, k_pair_dtable<2>, dim3(grid), dim3(64), 0, st, n_table, n_rel_rows, D, w.G, weight, d_table);
+  else TEMP_LAUNCH(K_PAIR_DTABLE, k_pair_dtable<4>, dim3(grid), dim3(64), 0, st, n_table, n_rel_rows, D, w.G, weight, d_table);
+  if (S == 1) TEMP_LAUNCH(K_PAIR_DW, k_pair_dw<1>, dim3(n_rel_rows), dim3(1024), 0, st, n_table, D, table, w.G, d_weight);
+  else if (S == 2) TEMP_LAUNCH(K_PAIR_DW, k_pair_dw<2>, dim3(n_rel_rows), dim3(1024), 0, st, n_table, D, table, w.G, d_weight);
+  else TEMP_LAUNCH(K_PAIR_DW, k_pair_dw<4>, dim3(n_rel_rows), dim3(1024), 0, st, n_table, D, table, w.G, d_weight);
+  // the self-loop part as in temp_rgcn_table_bwd:  d_table += segsum(dzm) . loop_w^T,  d_loop_w = table^T . segsum(dzm)
+  const DropSpec ds = drop_spec(drop);
+  const float* dzm = dz;
+  if (ds.p > 0.f) {
+    rc = mask_rows(g->n_nodes, d_out, dz, w.dzm, ds, st);
+    if (rc) return rc;
+    dzm = w.dzm;
+  }
+  rc = segment_sum_rows(n_table, d_out, inv_ptr, inv_order, dzm, nullptr, w.seg_dz, st, g->n_nodes, w.ss, w.ss_bytes);
+  if (rc) return rc;
+  rc = gemm_add_bias_act(K_GEMM_LOOP_DX, n_table, d_in, d_out, w.seg_dz, d_out, nullptr, loop_w, d_out, 1, d_table, d_in, nullptr, nullptr,
+                         TEMP_ACT_NONE, d_table, d_in, st);
+  if (rc) return rc;
+  rc = gemm_tn(n_table, d_in, d_out, table, d_in, w.seg_dz, d_out, d_loop_w, d_out, w.tn, w.tn_bytes, st);
+  if (rc) return rc;
+  if (has_bias) {
+    rc = colsum(g->n_nodes, d_out, dz, d_out, d_bias, w.cs, w.cs_bytes, st);
+    if (rc) return rc;
+  }
+  g_pair_launches.fetch_add(1, std::memory_order_relaxed);
+  return launch_status();
 }
 
 size_t temp_rgcn_fwd_workspace(const TempGraph* g, int d_out) {

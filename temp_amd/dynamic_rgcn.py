@@ -267,7 +267,7 @@ class DynamicRGCN(TKG_Module):
             wb.ids_all = _lib.to_device(wb.g_all.gids.astype(np.int32), dev)
             wb.ids_inv = TF.gather_inverse(wb.g_all.gids, self.num_ents, dev)        # static ids: deterministic embedding gradient
             _lib.pause_point()
-            wb.g_all.device_graph(dev, 2 * self.num_rels)
+            self.ent_encoder.layer_1.prepare_table(wb.g_all, self.ent_embeds.shape[0], wb.ids_all)
             _lib.pause_point()
             if getattr(wb, "stack", False):          # layer 2 runs per position: every position's own union graph as well
                 for st in wb.steps:

@@ -48,24 +48,61 @@ def rgcn_layer(h, dg, weight, loop_w, bias, num_bases, act=None, drop=None, grad
 
 class _RGCNTableLayerFn(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, table, weight, loop_w, bias, ids, inverse, dg, num_bases, act, drop):
-        out = get_backend().rgcn_table_fwd(dg, table, ids, weight, loop_w, bias, num_bases, act, drop)
+    def forward(ctx, table, weight, loop_w, bias, ids, inverse, dg, num_bases, act, drop, pv):
+        be = get_backend()
+        if pv is not None and be.pair_mode()[1]:
+            out = be.rgcn_pair_fwd(dg, pv, table, ids, weight, loop_w, bias, num_bases, act, drop)
+        else:
+            out = be.rgcn_table_fwd(dg, table, ids, weight, loop_w, bias, num_bases, act, drop)
         ctx.save_for_backward(table, weight, loop_w, out, ids)
-        ctx.dg, ctx.num_bases, ctx.act, ctx.has_bias, ctx.inverse, ctx.drop = dg, num_bases, act, bias is not None, inverse, drop
+        ctx.dg, ctx.num_bases, ctx.act, ctx.has_bias, ctx.inverse, ctx.drop, ctx.pv = dg, num_bases, act, bias is not None, inverse, drop, pv
         return out
 
     @staticmethod
     def backward(ctx, d_out):
         table, weight, loop_w, out, ids = ctx.saved_tensors
-        d_t, d_w, d_loop, d_bias = get_backend().rgcn_table_bwd(ctx.dg, table, ids, ctx.inverse, out, d_out.contiguous(), weight, loop_w,
-                                                               ctx.has_bias, ctx.num_bases, ctx.act, ctx.drop)
-        return d_t, d_w, d_loop, d_bias, None, None, None, None, None, None
+        be = get_backend()
+        if ctx.pv is not None and be.pair_mode()[2]:
+            d_t, d_w, d_loop, d_bias = be.rgcn_pair_bwd(ctx.dg, ctx.pv, table, ids, ctx.inverse, out, d_out.contiguous(), weight, loop_w,
+                                                        ctx.has_bias, ctx.num_bases, ctx.act, ctx.drop)
+        else:
+            d_t, d_w, d_loop, d_bias = be.rgcn_table_bwd(ctx.dg, table, ids, ctx.inverse, out, d_out.contiguous(), weight, loop_w,
+                                                         ctx.has_bias, ctx.num_bases, ctx.act, ctx.drop)
+        return d_t, d_w, d_loop, d_bias, None, None, None, None, None, None, None
+
+
+def pair_view_for(dg, ids, n_table, d_in, d_out, num_bases, build=False):
+    """The pair view (pair_view.DevicePairView) of device graph `dg` under the node -> table row map `ids` when a table-fed layer
+    of this shape takes the pair route on it (include/temp_amd.h: TempPairView; the switch is TEMP_OPT_RGCN_PAIR), else None:
+      - the backend has the route (the HIP backend; test backends without it keep the table route);
+      - the kernels take the shape;
+      - the graph has at least PAIR_MIN_RATIO edges per (relation row, table row) pair -- or the option forces the route.
+    The view is cached on `dg` under the address of `ids`, which it keeps alive: `ids` must not be rewritten in place afterwards
+    (the node -> table row map of a prepared batch is static).  It is built here only with build=True -- prepare time (RGCNLayer.prepare_table) -- or when the
+    option forces the route outside a graph capture: a step never sorts edges."""
+    from . import pair_view as PV
+    be = get_backend()
+    if not hasattr(be, "rgcn_pair_fwd") or ids is None or not ids.is_cuda:
+        return None
+    mode = be.pair_mode()[0]
+    if mode == 0 or not be.pair_supported(d_in, d_out, num_bases):
+        return None
+    if mode == 1 and dg.n_edges < PV.PAIR_MIN_RATIO * dg.n_rel_rows * int(n_table):
+        return None
+    cache = dg.__dict__.setdefault("_pair_views", {})
+    key = (ids.data_ptr(), int(ids.shape[0]), int(n_table))
+    pv = cache.get(key)
+    if pv is None and (build or mode == 2) and not torch.cuda.is_current_stream_capturing():
+        pv = cache[key] = PV.DevicePairView(dg, ids, n_table, dg.n_rel_rows, expand=be.expand_chunk_segments)
+    return pv
 
 
 def rgcn_layer_table(table, ids, inverse, dg, weight, loop_w, bias, num_bases, act=None, drop=None):
     """rgcn_layer on h = table[ids] (ids int32, static; inverse = gather_inverse(ids, rows)) without materialising h:
-    the self-loop product and its gradients run over the table's rows, not over every node row."""
-    return _RGCNTableLayerFn.apply(table, weight, loop_w, bias, ids, inverse, dg, num_bases, ACTS[act], drop)
+    the self-loop product and its gradients run over the table's rows, not over every node row.  Where pair_view_for finds a
+    prepared pair view the relational term runs over (relation, table row) pairs as well."""
+    pv = pair_view_for(dg, ids, table.shape[0], loop_w.shape[0], loop_w.shape[1], num_bases)
+    return _RGCNTableLayerFn.apply(table, weight, loop_w, bias, ids, inverse, dg, num_bases, ACTS[act], drop, pv)
 
 
 class _RGCNIsolatedFn(torch.autograd.Function):

@@ -94,6 +94,13 @@ class RGCNLayer(nn.Module):
         out = TF.rgcn_layer_table(table, ids, inverse, dg, self.weight, self.loop_weight, self._bias(), self.num_bases, self._act, self._drop())
         return self._post_act(out) if self._post_act is not None else out
 
+    def prepare_table(self, g, table_rows, ids):
+        """Prepare-time half of conv_table(g, table, ids, .) for a table of `table_rows` rows: the device graph and, where the layer
+        takes the pair route on it (TF.pair_view_for), its pair view -- so that the step itself never builds one."""
+        dg = g.device_graph(ids.device, self.num_rels)
+        TF.pair_view_for(dg, ids, table_rows, self.in_feat, self.out_feat, self.num_bases, build=True)
+        return dg
+
     def conv_isolated(self, e):
         out = TF.rgcn_isolated(e, self.loop_weight, self._bias(), self._act, self._drop())
         return self._post_act(out) if self._post_act is not None else out
