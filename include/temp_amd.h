@@ -481,7 +481,8 @@ int temp_gru_grads_g4_keys(int count, const int* ns, int d, const float* const* 
  *                           up: index into `up` of the upstream gradient block of the step's rows or -1,
  *                           up_row0: first row of that block in the [N_total] row space, 0 }
  * Steps of a panel are consecutive table rows in chain order.  gi / saved / dgi / dgh / h: as for temp_gru_cell_*.
- * Fixed decay only.  d % 4 == 0 and d <= TEMP_CHAIN_MAX_D (LDS), else TEMP_E_UNSUPPORTED.
+ * The calls below decay the previous state by exp(-dt lambda) (c->lambda); the temp_gru_chain_*_decay calls further down take a
+ * learnable decay instead.  d % 4 == 0 and d <= TEMP_CHAIN_MAX_D (LDS), else TEMP_E_UNSUPPORTED.
  * ---------------------------------------------------------------------------------------------- */
 #define TEMP_CHAIN_HAS_PREV (1 << 30)
 #define TEMP_CHAIN_TRACKS 32
@@ -546,6 +547,27 @@ int temp_gru_chain_bwd_g4(const TempGruChain* c, const float* saved, int n_up, c
 int temp_gru_chain_keys_supported(int d);
 int temp_gru_chain_bwd_g4_keys(const TempGruChain* c, const float* saved, int n_up, const float* const* up, float* g4,
                                uint32_t* row_keys, uint32_t* col_keys, void* stream);
+/* Learnable decay (--learnable-lambda; RGCNLayer.decay_hidden, models/RGCN.py:106-107): the previous state of a row with time gap dt
+ * is scaled by exp(-max(w dt + b, 0)) instead of exp(-dt lambda); c->lambda is not read.  wb[i]: DEVICE {w, b} of GRU i (no host
+ * read, no sync: capturable); the GRUs may share one pair.  The same launch code as the calls above, which are its decay == NULL case.
+ *   temp_gru_chain_decay_supported: 1 where the chain kernels of this width and cell variant take a learnable decay.
+ *   temp_gru_chain_bwd_decay: the three backward routes in one call -- g4 == NULL: (dgi, dgh) as temp_gru_chain_bwd; g4 with dgi ==
+ *     dgh == NULL: temp_gru_chain_bwd_g4, or with row_keys / col_keys temp_gru_chain_bwd_g4_keys.  Also writes
+ *     d_arg [N_total] = dL / d(w dt + b) of every row that has a previous state (0 where the clamp is active; the other rows are
+ *     not written):  d_arg[rho] = -[w dt_rho + b > 0] <d_prev_rho, h_pi>,  pi = the row of the same track one position earlier.
+ *   temp_gru_chain_decay_reduce: d_wb [n_rnn][2] = per GRU { sum d_arg dt, sum d_arg } over its rows with a previous state, in a
+ *     fixed order (per-panel partials in `ws`, temp_gru_chain_decay_reduce_workspace(c) bytes; no atomics: bit-repeatable).
+ *   temp_gru_chain_decay_launches: chain forward / backward launches with a learnable decay since the library was loaded (diagnostic). */
+typedef struct TempChainDecay { const float* wb[TEMP_CHAIN_MAX_RNN]; } TempChainDecay;
+int temp_gru_chain_decay_supported(int d, int variant);
+int temp_gru_chain_fwd_decay(const TempGruChain* c, const TempChainDecay* decay, const float* gi, float* h_out, float* saved, void* stream);
+int temp_gru_chain_fwd_x_decay(const TempGruChain* c, const TempChainDecay* decay, const float* x, const int32_t* x_index,
+                               const float* const* b_ih, float* h_out, float* saved, void* stream);
+int temp_gru_chain_bwd_decay(const TempGruChain* c, const TempChainDecay* decay, const float* saved, int n_up, const float* const* up,
+                             float* dgi, float* dgh, float* g4, uint32_t* row_keys, uint32_t* col_keys, float* d_arg, void* stream);
+size_t temp_gru_chain_decay_reduce_workspace(const TempGruChain* c);
+int temp_gru_chain_decay_reduce(const TempGruChain* c, const float* d_arg, float* d_wb, void* ws, size_t ws_bytes, void* stream);
+long long temp_gru_chain_decay_launches(void);
 
 /* ------------------------------------------------------------------------------------------------
  * Row gather / scatter helpers of the window loop

@@ -71,6 +71,10 @@ class TempGruChain(ctypes.Structure):
                 ("gi_index", c_vp), ("pack_layout", ctypes.c_int32)]
 
 
+class TempChainDecay(ctypes.Structure):
+    _fields_ = [("wb", c_vp * CHAIN_MAX_RNN)]      # device {w, b} of every GRU's learnable decay
+
+
 class TempSubsampleJob(ctypes.Structure):
     _fields_ = [("n_nodes", ctypes.c_int32), ("n_edges", ctypes.c_int32), ("keep", ctypes.c_int32), ("seed", ctypes.c_uint64),
                 ("parent", c_vp), ("child", c_vp), ("eid", c_vp),
@@ -163,6 +167,14 @@ SYMBOLS = {
     "temp_gru_chain_bwd_g4": (_I, [ctypes.POINTER(TempGruChain), c_vp, _I, ctypes.POINTER(c_vp), c_vp, c_vp]),
     "temp_gru_chain_keys_supported": (_I, [_I]),
     "temp_gru_chain_bwd_g4_keys": (_I, [ctypes.POINTER(TempGruChain), c_vp, _I, ctypes.POINTER(c_vp), c_vp, c_vp, c_vp, c_vp]),
+    "temp_gru_chain_decay_supported": (_I, [_I, _I]),
+    "temp_gru_chain_fwd_decay": (_I, [ctypes.POINTER(TempGruChain), ctypes.POINTER(TempChainDecay), c_vp, c_vp, c_vp, c_vp]),
+    "temp_gru_chain_fwd_x_decay": (_I, [ctypes.POINTER(TempGruChain), ctypes.POINTER(TempChainDecay), c_vp, c_vp, ctypes.POINTER(c_vp), c_vp, c_vp, c_vp]),
+    "temp_gru_chain_bwd_decay": (_I, [ctypes.POINTER(TempGruChain), ctypes.POINTER(TempChainDecay), c_vp, _I, ctypes.POINTER(c_vp), c_vp, c_vp, c_vp, c_vp, c_vp,
+                                      c_vp, c_vp]),
+    "temp_gru_chain_decay_reduce_workspace": (_SZ, [ctypes.POINTER(TempGruChain)]),
+    "temp_gru_chain_decay_reduce": (_I, [ctypes.POINTER(TempGruChain), c_vp, c_vp, c_vp, _SZ, c_vp]),
+    "temp_gru_chain_decay_launches": (ctypes.c_longlong, []),
     "temp_gru_grads_g4_keys": (_I, [_I, c_vp, _I, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, ctypes.c_size_t, c_vp]),
     "temp_gru_grads_g4_workspace": (ctypes.c_size_t, [_I, c_vp, _I]),
     "temp_gru_grads_g4": (_I, [_I, c_vp, _I, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, ctypes.c_size_t, c_vp]),

@@ -427,12 +427,47 @@ class HipBackend:
             c.packed[i], c.b_hh[i] = pk.data_ptr(), b.data_ptr()
         return c, keep
 
-    def gru_chain_fwd(self, tabs, gi, lam, variant, packs, b_hhs, h_out, saved_all, gi_index=None):
+    # Learnable decay (include/temp_amd.h: TempChainDecay): `decay` = a float32 device tensor {w, b} shared by all GRUs of the chain
+    # (`lam` is not read then); the backward also takes `d_arg` float32 [N_total] for the per-row gradient of w dt + b.
+    def gru_chain_decay_supported(self, d, variant):
+        return bool(self.lib.temp_gru_chain_decay_supported(int(d), int(variant)))
+
+    def gru_chain_decay_launches(self):
+        return int(self.lib.temp_gru_chain_decay_launches())
+
+    @staticmethod
+    def _chain_decay(decay, n_rnn):
+        decay = _f32(decay, "decay")
+        assert decay.numel() == 2
+        cd = _lib.TempChainDecay()
+        for i in range(n_rnn):
+            cd.wb[i] = decay.data_ptr()
+        return cd
+
+    def gru_chain_decay_reduce(self, tabs, d, variant, d_arg, n_rnn):
+        """d_arg [N_total] of gru_chain_bwd*(decay=, d_arg=) -> float32 [n_rnn, 2]: per GRU (sum d_arg dt, sum d_arg) over its rows
+        with a previous state, in a fixed order (temp_gru_chain_decay_reduce)."""
+        c = _lib.TempGruChain()
+        c.d, c.variant, c.n_panels, c.n_steps, c.max_steps, c.n_rnn = d, variant, tabs["n_panels"], tabs["n_steps"], tabs["max_steps"], n_rnn
+        c.panel, c.rows, c.sinfo, c.dt = (_i32(tabs[k], k).data_ptr() for k in ("panel", "rows", "sinfo", "dt_bits"))
+        d_arg = _f32(d_arg, "d_arg")
+        out = torch.empty(n_rnn, 2, dtype=torch.float32, device=d_arg.device)
+        nb = int(self.lib.temp_gru_chain_decay_reduce_workspace(ctypes.byref(c)))
+        ws = torch.empty(max(nb, 4) // 4, dtype=torch.float32, device=d_arg.device)
+        _lib.check(self.lib.temp_gru_chain_decay_reduce(ctypes.byref(c), _ptr(d_arg), _ptr(out), _ptr(ws), nb, _stream()), "temp_gru_chain_decay_reduce")
+        return out
+
+    def gru_chain_fwd(self, tabs, gi, lam, variant, packs, b_hhs, h_out, saved_all, gi_index=None, decay=None):
         d = saved_all.shape[2]
         c, keep = self._chain_desc(tabs, d, variant, lam, saved_all.shape[1] * d, packs, b_hhs)
         if gi_index is not None:
             assert gi_index.shape[0] == saved_all.shape[1]
             c.gi_index = _i32(gi_index, "gi_index").data_ptr()
+        if decay is not None:
+            cd = self._chain_decay(decay, len(packs))
+            rc = self.lib.temp_gru_chain_fwd_decay(ctypes.byref(c), ctypes.byref(cd), _ptr(_f32(gi, "gi")), _ptr(h_out), _ptr(saved_all), _stream())
+            _lib.check(rc, "temp_gru_chain_fwd_decay")
+            return
         rc = self.lib.temp_gru_chain_fwd(ctypes.byref(c), _ptr(_f32(gi, "gi")), _ptr(h_out), _ptr(saved_all), _stream())
         _lib.check(rc, "temp_gru_chain_fwd")
 
@@ -454,7 +489,7 @@ class HipBackend:
                    "temp_gru_chain_pack_x_multi")
         return self._tagged([buf[i] for i in range(k)], _lib.CHAIN_PACK_HX_X)
 
-    def gru_chain_fwd_x(self, tabs, x, x_index, lam, variant, packs, b_hhs, b_ihs, h_out, saved_all):
+    def gru_chain_fwd_x(self, tabs, x, x_index, lam, variant, packs, b_hhs, b_ihs, h_out, saved_all, decay=None):
         """The chain forward from the x rows (x_index: int32 [N_total], x row of every chain row): no gi (temp_gru_chain_fwd_x)."""
         d = saved_all.shape[2]
         c, keep = self._chain_desc(tabs, d, variant, lam, saved_all.shape[1] * d, packs, b_hhs)
@@ -462,14 +497,26 @@ class HipBackend:
         assert x.shape[1] == d and x_index.shape[0] == saved_all.shape[1]
         b_ihs = [_f32(b, "b_ih") for b in b_ihs]
         barr = (ctypes.c_void_p * len(b_ihs))(*[b.data_ptr() for b in b_ihs])
+        if decay is not None:
+            cd = self._chain_decay(decay, len(packs))
+            rc = self.lib.temp_gru_chain_fwd_x_decay(ctypes.byref(c), ctypes.byref(cd), _ptr(x), _ptr(_i32(x_index, "x_index")), barr, _ptr(h_out),
+                                                     _ptr(saved_all), _stream())
+            _lib.check(rc, "temp_gru_chain_fwd_x_decay")
+            return
         rc = self.lib.temp_gru_chain_fwd_x(ctypes.byref(c), _ptr(x), _ptr(_i32(x_index, "x_index")), barr, _ptr(h_out), _ptr(saved_all), _stream())
         _lib.check(rc, "temp_gru_chain_fwd_x")
 
-    def gru_chain_bwd(self, tabs, saved_all, ups, lam, variant, packs, b_hhs, dgi, dgh):
+    def gru_chain_bwd(self, tabs, saved_all, ups, lam, variant, packs, b_hhs, dgi, dgh, decay=None, d_arg=None):
         d = saved_all.shape[2]
         c, keep = self._chain_desc(tabs, d, variant, lam, saved_all.shape[1] * d, packs, b_hhs)
         ups = [_f32(u, "upstream") if u is not None else None for u in ups]      # (None: that block of rows has no upstream gradient)
         arr = (ctypes.c_void_p * max(len(ups), 1))(*[u.data_ptr() if u is not None else None for u in ups])
+        if decay is not None:
+            cd = self._chain_decay(decay, len(packs))
+            rc = self.lib.temp_gru_chain_bwd_decay(ctypes.byref(c), ctypes.byref(cd), _ptr(saved_all), len(ups), arr, _ptr(dgi), _ptr(dgh), None, None, None,
+                                                   _ptr(_f32(d_arg, "d_arg")), _stream())
+            _lib.check(rc, "temp_gru_chain_bwd_decay")
+            return
         rc = self.lib.temp_gru_chain_bwd(ctypes.byref(c), _ptr(saved_all), len(ups), arr, _ptr(dgi), _ptr(dgh), _stream())
         _lib.check(rc, "temp_gru_chain_bwd")
 
@@ -477,7 +524,7 @@ class HipBackend:
         """True when the chain backward of this width hands out the row / column keys of g4 (f16 two-way split selected)."""
         return bool(self.lib.temp_gru_chain_keys_supported(int(d)))
 
-    def gru_chain_bwd_g4(self, tabs, saved_all, ups, lam, variant, packs, b_hhs, g4, keys=None):
+    def gru_chain_bwd_g4(self, tabs, saved_all, ups, lam, variant, packs, b_hhs, g4, keys=None, decay=None, d_arg=None):
         """The chain backward with the gate gradients written once: g4 [N, 4d] = [dr | dz | dn_i | dn_h] (include/temp_amd.h:
         temp_gru_chain_bwd_g4; nn.GRU gate layout).  keys = (row_keys int32 [N], col_keys int32 [n_rnn + n_panels, 4d]; rows 0 .. n_rnn - 1 are the result): also the
         magnitude keys the consumers of g4 split it with (temp_gru_chain_bwd_g4_keys)."""
@@ -489,6 +536,14 @@ class HipBackend:
             row_keys, col_keys = keys
             assert row_keys.dtype == torch.int32 and col_keys.dtype == torch.int32 and col_keys.is_contiguous()
             assert row_keys.numel() == saved_all.shape[1] and col_keys.numel() == (len(packs) + tabs["n_panels"]) * 4 * d
+        if decay is not None:
+            cd = self._chain_decay(decay, len(packs))
+            rk, ck = (_ptr(keys[0]), _ptr(keys[1])) if keys is not None else (None, None)
+            rc = self.lib.temp_gru_chain_bwd_decay(ctypes.byref(c), ctypes.byref(cd), _ptr(saved_all), len(ups), arr, None, None, _ptr(g4), rk, ck,
+                                                   _ptr(_f32(d_arg, "d_arg")), _stream())
+            _lib.check(rc, "temp_gru_chain_bwd_decay")
+            return
+        if keys is not None:
             rc = self.lib.temp_gru_chain_bwd_g4_keys(ctypes.byref(c), _ptr(saved_all), len(ups), arr, _ptr(g4), _ptr(row_keys), _ptr(col_keys),
                                                      _stream())
             _lib.check(rc, "temp_gru_chain_bwd_g4_keys")

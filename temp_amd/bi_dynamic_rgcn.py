@@ -109,7 +109,7 @@ class BiDynamicRGCN(DynamicRGCN):
             else:
                 wb.last_x = TF.gather_rows(y2, wb.chain_rows, wb.chain_inv, relu_table=fold)      # GRU input rows in chain order
             got = dict(zip(want, gru_chain(wb.last_x, prog, [l2.forward_rnn, l2.backward_rnn], lam,
-                                           isinstance(l2.forward_rnn, GRUCell), want=want, x_keys=x_keys)))
+                                           isinstance(l2.forward_rnn, GRUCell), want=want, x_keys=x_keys, decay=dec)))
             out = got[wb.out_inst[0]] + got[wb.out_inst[1]]
             Hf, Hb = got.get(wb.hist_inst[0]), got.get(wb.hist_inst[1])
             return out, ((Hf, Hf), (Hb, Hb))
@@ -144,6 +144,10 @@ class BiDynamicRGCN(DynamicRGCN):
         if enc.use_time_embedding:
             out = out + l2.get_time_embedding(tf.times, tf.sizes)
         return out, ((Hf, Hf), (Hb, Hb))
+
+    def _chain_rnns(self):
+        l2 = self.ent_encoder.layer_2
+        return [l2.forward_rnn, l2.backward_rnn]
 
     def _chain_want(self, wb):
         return [i for i in (wb.out_inst[0], wb.out_inst[1], wb.hist_inst[0], wb.hist_inst[1]) if i >= 0]

@@ -26,7 +26,10 @@ namespace temp {
 #define CH_ROW_MASK (TEMP_CHAIN_HAS_PREV - 1)
 #define CH_LDS_LIMIT (160 * 1024)
 
-struct ChainRnn { const float4* wf; const float4* wb; const float* b_hh; const unsigned* kf; const unsigned* kb; };   // kf / kb: column keys of the f16 planes (gru_chain_hx.hpp)
+struct ChainRnn {
+  const float4* wf; const float4* wb; const float* b_hh; const unsigned* kf; const unsigned* kb;   // kf / kb: column keys of the f16 planes (gru_chain_hx.hpp)
+  const float* decay_wb;                 // nullable: device {w, b} of the learnable decay exp(-max(w dt + b, 0)) (gru_math.hpp: decay_factor)
+};
 struct ChainArgs {
   int D, n_panels, max_steps, dbg;
   int layout;                            // TEMP_CHAIN_PACK_*: the arithmetic the packed weights were written for (the kernels follow it)
@@ -37,6 +40,7 @@ struct ChainArgs {
   float lambda;
   size_t plane;
   ChainRnn rnn[TEMP_CHAIN_MAX_RNN];
+  float* d_arg;                          // nullable (backward, learnable decay): [N_total] dL / d(w dt + b) of every row with a previous state
 };
 struct ChainUps { const float* p[TEMP_CHAIN_MAX_UP]; };
 
@@ -58,6 +62,35 @@ __host__ __device__ inline ChainGeom chain_geom(int D) {
 // `ms` = the longest panel of the launch (<= CH_MAX_STEPS)
 inline size_t chain_lds_fwd(int D, int ms) { ChainGeom g = chain_geom(D); return ((size_t)CH_SLOTS * g.lda + 2 * CH_SLOTS * g.ldh + (2 * CH_SLOTS + 1) * (size_t)ms) * 4; }
 inline size_t chain_lds_bwd(int D, int ms) { ChainGeom g = chain_geom(D); return ((size_t)CH_SLOTS * g.ldA + 2 * CH_SLOTS * g.ldz + (2 * CH_SLOTS + 3) * (size_t)ms) * 4; }
+
+
+// Learnable decay, backward: the row rho that continues track `slot` at the next position has hd = dec . h_pi, dec = exp(-max(arg, 0)),
+// arg = w dt_rho + b, so dL/d arg_rho = -[arg_rho > 0] <d_hd . dec, h_pi> = -[arg_rho > 0] <d_prev_rho, h_pi>  (d_prev_rho is what the
+// matrix waves left in dpb; h_pi = (1 - z) n + z hd from the saved planes of pi -- both cells' output equation).  Every lane of the
+// wave hands in its partial dot product; the 64 partials are summed in a fixed order (a DPP butterfly inside each row of 16 lanes,
+// then the four rows), so the result is bit-repeatable.
+__device__ __forceinline__ float chain_wave_sum(float v) {
+  auto dpp = [](float x, auto ctrl) { return __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(x), decltype(ctrl)::value, 0xf, 0xf, true)); };
+  v += dpp(v, std::integral_constant<int, 0xB1>());     // quad_perm [1, 0, 3, 2]
+  v += dpp(v, std::integral_constant<int, 0x4E>());     // quad_perm [2, 3, 0, 1]
+  v += dpp(v, std::integral_constant<int, 0x141>());    // row_half_mirror
+  v += dpp(v, std::integral_constant<int, 0x140>());    // row_mirror
+  const float r0 = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), 0)), r1 = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), 16));
+  const float r2 = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), 32)), r3 = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), 48));
+  return (r0 + r1) + (r2 + r3);
+}
+__device__ __forceinline__ float chain_dot_prev(const float4 dp, const float4 z, const float4 n, const float4 hd) {
+  const float4 h = make_float4((1.f - z.x) * n.x + z.x * hd.x, (1.f - z.y) * n.y + z.y * hd.y, (1.f - z.z) * n.z + z.z * hd.z, (1.f - z.w) * n.w + z.w * hd.w);
+  return (dp.x * h.x + dp.y * h.y) + (dp.z * h.z + dp.w * h.w);
+}
+// (all 64 lanes call it; `en` = the table entry of rho)
+__device__ __forceinline__ void chain_store_d_arg(const ChainArgs& a, const ChainRnn& R, int en, float part, int lane) {
+  const float dot = chain_wave_sum(part);
+  if (lane == 0) {
+    const int row = en & CH_ROW_MASK;
+    a.d_arg[row] = fmaf(R.decay_wb[0], a.dt[row], R.decay_wb[1]) > 0.f ? -dot : 0.f;
+  }
+}
 
 }  // namespace temp
 #include "gru_chain_hx.hpp"
@@ -116,7 +149,7 @@ __global__ void __launch_bounds__(256 + 64 * MW) k_gru_chain_fwd(ChainArgs a, co
     for (int i = tid; i < ns * CH_SLOTS; i += blockDim.x) {
       const int e = a.rows[(size_t)s0 * CH_SLOTS + i];
       tabb[i] = e;
-      decb[i] = e >= 0 ? expf(-a.dt[e & CH_ROW_MASK] * a.lambda) : 0.f;
+      decb[i] = e >= 0 ? decay_factor(a.dt[e & CH_ROW_MASK], a.lambda, R.decay_wb) : 0.f;
     }
     if (tid < ns) flagb[tid] = a.sinfo[4 * (size_t)(s0 + tid)];
     __syncthreads();
@@ -386,7 +419,7 @@ __global__ void __launch_bounds__(256 + 64 * MW) k_gru_chain_bwd(ChainArgs a, Ch
     for (int i = tid; i < ns * CH_SLOTS; i += blockDim.x) {
       const int e = a.rows[(size_t)s0 * CH_SLOTS + i];
       tabb[i] = e;
-      decb[i] = e >= 0 ? expf(-a.dt[e & CH_ROW_MASK] * a.lambda) : 0.f;
+      decb[i] = e >= 0 ? decay_factor(a.dt[e & CH_ROW_MASK], a.lambda, R.decay_wb) : 0.f;
     }
     if (tid < ns) flagb[tid] = a.sinfo[4 * (size_t)(s0 + tid)];
     __syncthreads();
@@ -562,7 +595,7 @@ __global__ void __launch_bounds__(256 + 64 * MW) k_gru_chain_bwd(ChainArgs a, Ch
       const int mw = wave - 4, c4 = lane, col = 4 * c4;
       const bool cact = c4 < D4;
       int erow[PASSES];
-      bool nxt[PASSES];
+      int enx[PASSES];                                            // the track's entry at the next position when that row continues this one's state, else -1
       float4 sr[PASSES], sz[PASSES], sn[PASSES], shn[PASSES], shd[PASSES];
       auto prefetch = [&](int s) {
 #pragma unroll
@@ -572,7 +605,7 @@ __global__ void __launch_bounds__(256 + 64 * MW) k_gru_chain_bwd(ChainArgs a, Ch
           erow[ps] = e;
           int en = -1;
           if (s + 1 < ns) en = tabb[(s + 1) * CH_SLOTS + slot];
-          nxt[ps] = en >= 0 && (en & CH_HAS_PREV);
+          enx[ps] = (en >= 0 && (en & CH_HAS_PREV)) ? en : -1;
           const bool ok = e >= 0 && cact;
           const size_t row = ok ? (size_t)(e & CH_ROW_MASK) : 0;
           const float* src = saved + row * D + (ok ? col : 0);
@@ -591,11 +624,15 @@ __global__ void __launch_bounds__(256 + 64 * MW) k_gru_chain_bwd(ChainArgs a, Ch
         for (int ps = 0; ps < PASSES; ++ps) {
           const int slot = ps * MW + mw;
           const int e = erow[ps];
-          if (!cact) continue;
           if (e < 0) continue;                 // idle track: whatever its LDS rows hold only reaches its own, unread, d_prev row
+          if (a.d_arg && enx[ps] >= 0) {       // (wave-uniform; lanes past the width take part in the sum with zeros)
+            const float part = cact ? chain_dot_prev(ld4(dpb + (size_t)slot * ldz + col), sz[ps], sn[ps], shd[ps]) : 0.f;
+            chain_store_d_arg(a, R, enx[ps], part, lane);
+          }
+          if (!cact) continue;
           const size_t row = (size_t)(e & CH_ROW_MASK);
           float4 gd = upp ? ld4(upp + (row - (size_t)up_row0) * D + col) : zero4();
-          if (nxt[ps]) gd = add4(gd, ld4(dpb + (size_t)slot * ldz + col));
+          if (enx[ps] >= 0) gd = add4(gd, ld4(dpb + (size_t)slot * ldz + col));
           const float4 rg = sr[ps], zg = sz[ps], ng = sn[ps], hn = shn[ps], hd = shd[ps];
           float4 dr_pre, dz_pre, dn_pre, dhn, gz;
 #define TEMP_GATE(c)                                          \
@@ -632,6 +669,52 @@ __global__ void __launch_bounds__(256 + 64 * MW) k_gru_chain_bwd(ChainArgs a, Ch
   }
 }
 
+// ---- learnable decay: d_arg -> (d_w, d_b) of every GRU -----------------------------------------------------------------
+// arg = w dt + b per row, so d_w = sum d_arg . dt and d_b = sum d_arg over the rows with a previous state (the others have no
+// decay and their d_arg is never written).  One block per panel walks the panel's part of the row table: thread t takes entries
+// t, t + 256, ... in order, the block sums its 256 partials as a fixed tree -> part[p] = {d_w, d_b} of the panel.
+// k_chain_decay_final then adds the panels of every GRU in index order.  No floating-point atomics: bit-repeatable.
+#define CH_DECAY_THREADS 256
+__global__ void __launch_bounds__(CH_DECAY_THREADS) k_chain_decay_reduce(int n_panels, const int32_t* __restrict__ panel, const int32_t* __restrict__ rows,
+                                                                       const float* __restrict__ dt, const float* __restrict__ d_arg, float2* __restrict__ part) {
+  __shared__ float2 red[CH_DECAY_THREADS];
+  const int p = blockIdx.x;
+  if (p >= n_panels) return;
+  const int s0 = panel[4 * p + 1], ns = panel[4 * p + 2];
+  float dw = 0.f, db = 0.f;
+  for (int i = threadIdx.x; i < ns * CH_SLOTS; i += CH_DECAY_THREADS) {
+    const int e = rows[(size_t)s0 * CH_SLOTS + i];
+    if (e >= 0 && (e & CH_HAS_PREV)) {
+      const int row = e & CH_ROW_MASK;
+      const float g = d_arg[row];
+      dw = fmaf(g, dt[row], dw);
+      db += g;
+    }
+  }
+  red[threadIdx.x] = make_float2(dw, db);
+  __syncthreads();
+  for (int w = CH_DECAY_THREADS / 2; w > 0; w >>= 1) {
+    if ((int)threadIdx.x < w) { red[threadIdx.x].x += red[threadIdx.x + w].x; red[threadIdx.x].y += red[threadIdx.x + w].y; }
+    __syncthreads();
+  }
+  if (threadIdx.x == 0) part[p] = red[0];
+}
+// one wave per GRU: lane l adds panels l, l + 64, ... of its GRU in order, then the 64 lanes as a fixed tree
+__global__ void __launch_bounds__(64) k_chain_decay_final(int n_panels, const int32_t* __restrict__ panel, const float2* __restrict__ part, float2* __restrict__ d_wb) {
+  __shared__ float2 red[64];
+  const int r = blockIdx.x;
+  float dw = 0.f, db = 0.f;
+  for (int p = threadIdx.x; p < n_panels; p += 64)
+    if (panel[4 * p] == r) { dw += part[p].x; db += part[p].y; }
+  red[threadIdx.x] = make_float2(dw, db);
+  __syncthreads();
+  for (int w = 32; w > 0; w >>= 1) {
+    if ((int)threadIdx.x < w) { red[threadIdx.x].x += red[threadIdx.x + w].x; red[threadIdx.x].y += red[threadIdx.x + w].y; }
+    __syncthreads();
+  }
+  if (threadIdx.x == 0) d_wb[r] = red[0];
+}
+
 static bool chain_layout_ok(int layout, int d);
 static int chain_check(const TempGruChain* c) {
   if (!c || c->d <= 0 || c->n_panels < 0 || c->n_steps < 0 || c->n_rnn <= 0 || c->n_rnn > TEMP_CHAIN_MAX_RNN) return TEMP_E_BADARG;
@@ -663,8 +746,10 @@ static bool chain_layout_ok(int layout, int d) {
 }
 static bool layout_hx(int layout) { return layout == TEMP_CHAIN_PACK_HX || layout == TEMP_CHAIN_PACK_HX_X; }
 
-static ChainArgs chain_args(const TempGruChain* c) {
+// decay: nullable -- the learnable decay of every GRU of the chain (c->lambda is not read then); d_arg: nullable, backward only
+static ChainArgs chain_args(const TempGruChain* c, const TempChainDecay* decay = nullptr, float* d_arg = nullptr) {
   ChainArgs a = {};
+  a.d_arg = d_arg;
   const ChainGeom g = chain_geom(c->d);
   a.D = c->d; a.n_panels = c->n_panels; a.max_steps = c->max_steps; a.panel = c->panel; a.rows = c->rows; a.sinfo = c->sinfo; a.dt = c->dt;
   a.layout = c->pack_layout;
@@ -673,6 +758,7 @@ static ChainArgs chain_args(const TempGruChain* c) {
     a.rnn[i].wf = (const float4*)c->packed[i];
     a.rnn[i].wb = (const float4*)c->packed[i] + (a.layout == TEMP_CHAIN_PACK_BX ? (size_t)(g.NQ >> 1) * g.NT * 192 : (size_t)g.NT * g.NQ * 64);
     a.rnn[i].b_hh = c->b_hh[i];
+    a.rnn[i].decay_wb = decay ? decay->wb[i] : nullptr;
     a.rnn[i].kf = a.rnn[i].kb = nullptr;
     if (layout_hx(a.layout)) {
       const ChainGeomHx gx = chain_geom_hx(c->d);
@@ -889,12 +975,24 @@ int temp_gru_chain_pack_multi(int count, int d, const float* const* w_hh, float*
   return launch_status();
 }
 
-int temp_gru_chain_fwd(const TempGruChain* c, const float* gi, float* h_out, float* saved, void* stream) {
+}  // extern "C"
+
+// launches of a chain forward / backward kernel with a learnable decay since the library was loaded (diagnostic)
+static std::atomic<long long> g_decay_launches{0};
+static int chain_decay_check(const TempGruChain* c, const TempChainDecay* decay) {
+  if (!decay) return TEMP_OK;
+  for (int i = 0; i < c->n_rnn; ++i) if (!decay->wb[i]) return TEMP_E_BADARG;
+  return temp_gru_chain_decay_supported(c->d, c->variant) ? TEMP_OK : TEMP_E_UNSUPPORTED;
+}
+
+static int chain_fwd(const TempGruChain* c, const TempChainDecay* decay, const float* gi, float* h_out, float* saved, void* stream) {
   int rc = chain_check(c);
   if (rc) return rc;
+  if ((rc = chain_decay_check(c, decay))) return rc;
   if (c->n_panels == 0) return TEMP_OK;
   if (!gi || !h_out || !saved) return TEMP_E_BADARG;
-  const ChainArgs a = chain_args(c);
+  const ChainArgs a = chain_args(c, decay);
+  if (decay) g_decay_launches.fetch_add(1, std::memory_order_relaxed);
   hipStream_t st = (hipStream_t)stream;
   const int tpw = ceil_div(chain_geom(c->d).NT, 4);
 #define TEMP_CHAIN_FWD(V)                                                            \
@@ -911,6 +1009,20 @@ int temp_gru_chain_fwd(const TempGruChain* c, const float* gi, float* h_out, flo
   TEMP_CHAIN_FWD(TEMP_GRU_TYPE1)
 #undef TEMP_CHAIN_FWD
 }
+
+extern "C" {
+
+int temp_gru_chain_fwd(const TempGruChain* c, const float* gi, float* h_out, float* saved, void* stream) {
+  return chain_fwd(c, nullptr, gi, h_out, saved, stream);
+}
+int temp_gru_chain_fwd_decay(const TempGruChain* c, const TempChainDecay* decay, const float* gi, float* h_out, float* saved, void* stream) {
+  if (!decay) return TEMP_E_BADARG;
+  return chain_fwd(c, decay, gi, h_out, saved, stream);
+}
+int temp_gru_chain_decay_supported(int d, int variant) {
+  return (variant == TEMP_GRU_TORCH || variant == TEMP_GRU_TYPE1) && temp_gru_chain_supported(d) ? 1 : 0;
+}
+long long temp_gru_chain_decay_launches(void) { return g_decay_launches.load(std::memory_order_relaxed); }
 
 int temp_gru_chain_fwd_x_supported(int d, int variant, int max_steps) {
   return d > 0 && d % 8 == 0 && variant == TEMP_GRU_TORCH && chain_fwd_x_ok(d, max_steps) ? 1 : 0;
@@ -943,15 +1055,20 @@ int temp_gru_chain_pack_x_multi(int count, int d, const float* const* w_hh, cons
   return launch_status();
 }
 
-int temp_gru_chain_fwd_x(const TempGruChain* c, const float* x, const int32_t* x_index, const float* const* b_ih, float* h_out, float* saved, void* stream) {
+}  // extern "C"
+
+static int chain_fwd_x(const TempGruChain* c, const TempChainDecay* decay, const float* x, const int32_t* x_index, const float* const* b_ih, float* h_out,
+                       float* saved, void* stream) {
   int rc = chain_check(c);
   if (rc) return rc;
+  if ((rc = chain_decay_check(c, decay))) return rc;
   if (c->pack_layout != TEMP_CHAIN_PACK_HX_X) return TEMP_E_BADARG;        // (the W_ih planes sit behind temp_gru_chain_pack_x_multi's packs only)
   if (c->variant != TEMP_GRU_TORCH || !chain_fwd_x_fits(c->d, c->max_steps)) return TEMP_E_UNSUPPORTED;
   if (c->n_panels == 0) return TEMP_OK;
   if (!x || !x_index || !b_ih || !h_out || !saved) return TEMP_E_BADARG;
   for (int i = 0; i < c->n_rnn; ++i) if (!b_ih[i]) return TEMP_E_BADARG;
-  const ChainArgs a = chain_args(c);
+  const ChainArgs a = chain_args(c, decay);
+  if (decay) g_decay_launches.fetch_add(1, std::memory_order_relaxed);
   ChainX X = {};
   X.x = x; X.x_index = x_index;
   const ChainGeomHx gx = chain_geom_hx(c->d);
@@ -983,58 +1100,47 @@ int temp_gru_chain_fwd_x(const TempGruChain* c, const float* x, const int32_t* x
   return launch_status();
 }
 
+extern "C" {
+
+int temp_gru_chain_fwd_x(const TempGruChain* c, const float* x, const int32_t* x_index, const float* const* b_ih, float* h_out, float* saved, void* stream) {
+  return chain_fwd_x(c, nullptr, x, x_index, b_ih, h_out, saved, stream);
+}
+int temp_gru_chain_fwd_x_decay(const TempGruChain* c, const TempChainDecay* decay, const float* x, const int32_t* x_index, const float* const* b_ih,
+                               float* h_out, float* saved, void* stream) {
+  if (!decay) return TEMP_E_BADARG;
+  return chain_fwd_x(c, decay, x, x_index, b_ih, h_out, saved, stream);
+}
+
 long long temp_gru_chain_fwd_x_launches(void) { return g_fwd_x_launches.load(std::memory_order_relaxed); }
 
-int temp_gru_chain_bwd_g4(const TempGruChain* c, const float* saved, int n_up, const float* const* up, float* g4, void* stream) {
+}  // extern "C"
+
+// The three backward routes in one place: CH_BWD_GATES -> (dgi, dgh); CH_BWD_G4 -> the gate gradients written once (nn.GRU layout);
+// CH_BWD_G4_KEYS -> the same on the f16 kernels, which also hand out row_keys / col_keys (each nullable).  decay / d_arg: the
+// learnable decay and its per-row gradient (both or neither).
+enum { CH_BWD_GATES, CH_BWD_G4, CH_BWD_G4_KEYS };
+static int chain_bwd(int route, const TempGruChain* c, const TempChainDecay* decay, const float* saved, int n_up, const float* const* up, float* dgi,
+                     float* dgh, float* g4, uint32_t* row_keys, uint32_t* col_keys, float* d_arg, void* stream) {
   int rc = chain_check(c);
   if (rc) return rc;
+  if ((rc = chain_decay_check(c, decay))) return rc;
   if (n_up < 0 || n_up > TEMP_CHAIN_MAX_UP || (n_up > 0 && !up)) return TEMP_E_BADARG;
-  if (c->variant != TEMP_GRU_TORCH) return TEMP_E_UNSUPPORTED;        // (the type-1 cell's dgi is [n, d])
+  if ((decay != nullptr) != (d_arg != nullptr)) return TEMP_E_BADARG;
+  if (route != CH_BWD_GATES && c->variant != TEMP_GRU_TORCH) return TEMP_E_UNSUPPORTED;    // (the type-1 cell's dgi is [n, d])
+  if (route == CH_BWD_G4_KEYS && !layout_hx(c->pack_layout)) return TEMP_E_UNSUPPORTED;
   if (c->n_panels == 0) return TEMP_OK;
-  if (!saved || !g4) return TEMP_E_BADARG;
-  const ChainArgs a = chain_args(c);
+  if (!saved || (route == CH_BWD_GATES ? (!dgi || !dgh) : !g4)) return TEMP_E_BADARG;
+  const ChainArgs a = chain_args(c, decay, d_arg);
+  if (decay) g_decay_launches.fetch_add(1, std::memory_order_relaxed);
   ChainUps ups = {};
   for (int i = 0; i < n_up; ++i) ups.p[i] = up[i];
   hipStream_t st = (hipStream_t)stream;
   const int tpw = ceil_div(chain_geom(c->d).NTb, 4);
-  if (tpw == 1) return launch_chain_bwd<TEMP_GRU_TORCH, 1, 1>(a, ups, saved, g4, nullptr, st);
-  if (tpw == 2) return launch_chain_bwd<TEMP_GRU_TORCH, 2, 1>(a, ups, saved, g4, nullptr, st);
-  return TEMP_E_UNSUPPORTED;
-}
-
-int temp_gru_chain_pack_layout(int d) { return d > 0 ? chain_pack_layout(d) : 0; }
-
-int temp_gru_chain_keys_supported(int d) { return d > 0 && chain_hx(d) ? 1 : 0; }
-
-int temp_gru_chain_bwd_g4_keys(const TempGruChain* c, const float* saved, int n_up, const float* const* up, float* g4, uint32_t* row_keys,
-                               uint32_t* col_keys, void* stream) {
-  int rc = chain_check(c);
-  if (rc) return rc;
-  if (n_up < 0 || n_up > TEMP_CHAIN_MAX_UP || (n_up > 0 && !up)) return TEMP_E_BADARG;
-  if (c->variant != TEMP_GRU_TORCH || !layout_hx(c->pack_layout)) return TEMP_E_UNSUPPORTED;
-  if (c->n_panels == 0) return TEMP_OK;
-  if (!saved || !g4) return TEMP_E_BADARG;
-  const ChainArgs a = chain_args(c);
-  ChainUps ups = {};
-  for (int i = 0; i < n_up; ++i) ups.p[i] = up[i];
-  hipStream_t st = (hipStream_t)stream;
-  const int tpw = ceil_div(chain_geom(c->d).NTb, 4);
-  if (tpw == 1) return launch_chain_bwd<TEMP_GRU_TORCH, 1, 1>(a, ups, saved, g4, nullptr, st, row_keys, col_keys);
-  if (tpw == 2) return launch_chain_bwd<TEMP_GRU_TORCH, 2, 1>(a, ups, saved, g4, nullptr, st, row_keys, col_keys);
-  return TEMP_E_UNSUPPORTED;
-}
-
-int temp_gru_chain_bwd(const TempGruChain* c, const float* saved, int n_up, const float* const* up, float* dgi, float* dgh, void* stream) {
-  int rc = chain_check(c);
-  if (rc) return rc;
-  if (n_up < 0 || n_up > TEMP_CHAIN_MAX_UP || (n_up > 0 && !up)) return TEMP_E_BADARG;
-  if (c->n_panels == 0) return TEMP_OK;
-  if (!saved || !dgi || !dgh) return TEMP_E_BADARG;
-  const ChainArgs a = chain_args(c);
-  ChainUps ups = {};
-  for (int i = 0; i < n_up; ++i) ups.p[i] = up[i];
-  hipStream_t st = (hipStream_t)stream;
-  const int tpw = ceil_div(chain_geom(c->d).NTb, 4);
+  if (route != CH_BWD_GATES) {
+    if (tpw == 1) return launch_chain_bwd<TEMP_GRU_TORCH, 1, 1>(a, ups, saved, g4, nullptr, st, row_keys, col_keys);
+    if (tpw == 2) return launch_chain_bwd<TEMP_GRU_TORCH, 2, 1>(a, ups, saved, g4, nullptr, st, row_keys, col_keys);
+    return TEMP_E_UNSUPPORTED;
+  }
   if (c->variant == TEMP_GRU_TORCH) {
     if (tpw == 1) return launch_chain_bwd<TEMP_GRU_TORCH, 1>(a, ups, saved, dgi, dgh, st);
     if (tpw == 2) return launch_chain_bwd<TEMP_GRU_TORCH, 2>(a, ups, saved, dgi, dgh, st);
@@ -1043,6 +1149,48 @@ int temp_gru_chain_bwd(const TempGruChain* c, const float* saved, int n_up, cons
     if (tpw == 2) return launch_chain_bwd<TEMP_GRU_TYPE1, 2>(a, ups, saved, dgi, dgh, st);
   }
   return TEMP_E_UNSUPPORTED;
+}
+
+extern "C" {
+
+int temp_gru_chain_bwd_g4(const TempGruChain* c, const float* saved, int n_up, const float* const* up, float* g4, void* stream) {
+  return chain_bwd(CH_BWD_G4, c, nullptr, saved, n_up, up, nullptr, nullptr, g4, nullptr, nullptr, nullptr, stream);
+}
+
+int temp_gru_chain_pack_layout(int d) { return d > 0 ? chain_pack_layout(d) : 0; }
+
+int temp_gru_chain_keys_supported(int d) { return d > 0 && chain_hx(d) ? 1 : 0; }
+
+int temp_gru_chain_bwd_g4_keys(const TempGruChain* c, const float* saved, int n_up, const float* const* up, float* g4, uint32_t* row_keys,
+                               uint32_t* col_keys, void* stream) {
+  return chain_bwd(CH_BWD_G4_KEYS, c, nullptr, saved, n_up, up, nullptr, nullptr, g4, row_keys, col_keys, nullptr, stream);
+}
+
+int temp_gru_chain_bwd(const TempGruChain* c, const float* saved, int n_up, const float* const* up, float* dgi, float* dgh, void* stream) {
+  return chain_bwd(CH_BWD_GATES, c, nullptr, saved, n_up, up, dgi, dgh, nullptr, nullptr, nullptr, nullptr, stream);
+}
+
+int temp_gru_chain_bwd_decay(const TempGruChain* c, const TempChainDecay* decay, const float* saved, int n_up, const float* const* up, float* dgi,
+                             float* dgh, float* g4, uint32_t* row_keys, uint32_t* col_keys, float* d_arg, void* stream) {
+  if (!decay || !d_arg || (g4 && (dgi || dgh))) return TEMP_E_BADARG;
+  const int route = !g4 ? CH_BWD_GATES : (row_keys || col_keys) ? CH_BWD_G4_KEYS : CH_BWD_G4;
+  return chain_bwd(route, c, decay, saved, n_up, up, dgi, dgh, g4, row_keys, col_keys, d_arg, stream);
+}
+
+size_t temp_gru_chain_decay_reduce_workspace(const TempGruChain* c) {
+  if (!c || c->n_panels <= 0) return 0;
+  return (size_t)c->n_panels * sizeof(float2);
+}
+
+int temp_gru_chain_decay_reduce(const TempGruChain* c, const float* d_arg, float* d_wb, void* ws, size_t ws_bytes, void* stream) {
+  if (!c || c->n_panels < 0 || c->n_rnn <= 0 || c->n_rnn > TEMP_CHAIN_MAX_RNN || !d_wb) return TEMP_E_BADARG;
+  hipStream_t st = (hipStream_t)stream;
+  if (c->n_panels == 0) return hipMemsetAsync(d_wb, 0, (size_t)c->n_rnn * 2 * sizeof(float), st) == hipSuccess ? TEMP_OK : TEMP_E_LAUNCH;
+  if (!c->panel || !c->rows || !c->dt || !d_arg) return TEMP_E_BADARG;
+  if (!ws || ws_bytes < temp_gru_chain_decay_reduce_workspace(c)) return TEMP_E_WORKSPACE;
+  TEMP_LAUNCH(K_GRU_CHAIN_PACK, k_chain_decay_reduce, dim3(c->n_panels), dim3(CH_DECAY_THREADS), 0, st, c->n_panels, c->panel, c->rows, c->dt, d_arg, (float2*)ws);
+  TEMP_LAUNCH(K_GRU_CHAIN_PACK, k_chain_decay_final, dim3(c->n_rnn), dim3(64), 0, st, c->n_panels, c->panel, (const float2*)ws, (float2*)d_wb);
+  return launch_status();
 }
 
 }  // extern "C"

@@ -85,7 +85,7 @@ __global__ void __launch_bounds__(64 * (NMW + MW)) k_gru_chain_fwd_hx(ChainArgs 
     for (int i = tid; i < ns * CH_SLOTS; i += blockDim.x) {
       const int e = a.rows[(size_t)s0 * CH_SLOTS + i];
       tabb[i] = e;
-      decb[i] = e >= 0 ? expf(-a.dt[e & CH_ROW_MASK] * a.lambda) : 0.f;
+      decb[i] = e >= 0 ? decay_factor(a.dt[e & CH_ROW_MASK], a.lambda, R.decay_wb) : 0.f;
     }
     if (tid < ns) flagb[tid] = a.sinfo[4 * (size_t)(s0 + tid)];
     __syncthreads();
@@ -324,7 +324,7 @@ __global__ void __launch_bounds__(64 * (NMW + MW)) k_gru_chain_fwd_x(ChainArgs a
     for (int i = tid; i < ns * CH_SLOTS; i += blockDim.x) {
       const int e = a.rows[(size_t)s0 * CH_SLOTS + i];
       tabb[i] = e;
-      decb[i] = e >= 0 ? expf(-a.dt[e & CH_ROW_MASK] * a.lambda) : 0.f;
+      decb[i] = e >= 0 ? decay_factor(a.dt[e & CH_ROW_MASK], a.lambda, R.decay_wb) : 0.f;
     }
     if (tid < ns) flagb[tid] = a.sinfo[4 * (size_t)(s0 + tid)];
     __syncthreads();
@@ -456,7 +456,7 @@ __global__ void __launch_bounds__(64 * (NMW + MW)) k_gru_chain_fwd_x(ChainArgs a
     for (int i = tid; i < ns * CH_SLOTS; i += blockDim.x) {
       const int e = a.rows[(size_t)s0 * CH_SLOTS + i];
       tabb[i] = e;
-      decb[i] = e >= 0 ? expf(-a.dt[e & CH_ROW_MASK] * a.lambda) : 0.f;
+      decb[i] = e >= 0 ? decay_factor(a.dt[e & CH_ROW_MASK], a.lambda, R.decay_wb) : 0.f;
     }
     if (tid < ns) flagb[tid] = a.sinfo[4 * (size_t)(s0 + tid)];
     __syncthreads();
@@ -608,7 +608,7 @@ __global__ void __launch_bounds__(64 * (NMW + MW)) k_gru_chain_bwd_hx(ChainArgs 
     for (int i = tid; i < ns * CH_SLOTS; i += blockDim.x) {
       const int e = a.rows[(size_t)s0 * CH_SLOTS + i];
       tabb[i] = e;
-      decb[i] = e >= 0 ? expf(-a.dt[e & CH_ROW_MASK] * a.lambda) : 0.f;
+      decb[i] = e >= 0 ? decay_factor(a.dt[e & CH_ROW_MASK], a.lambda, R.decay_wb) : 0.f;
     }
     if (tid < ns) flagb[tid] = a.sinfo[4 * (size_t)(s0 + tid)];
     __syncthreads();
@@ -691,7 +691,7 @@ __global__ void __launch_bounds__(64 * (NMW + MW)) k_gru_chain_bwd_hx(ChainArgs 
       const bool cact = c4 < D4;
       const int colc = cact ? col : 0;
       int erow[PASSES];
-      bool nxt[PASSES];
+      int enx[PASSES];                                           // the track's entry at the next position when that row continues this one's state, else -1
       float4 sr[PASSES], sz[PASSES], sn[PASSES], shn[PASSES], shd[PASSES];
       unsigned ck[4][4] = {};                                    // running maxima of this lane's four columns of dr, dz, dn_i, dn_h
       auto prefetch = [&](int s) {
@@ -702,7 +702,7 @@ __global__ void __launch_bounds__(64 * (NMW + MW)) k_gru_chain_bwd_hx(ChainArgs 
           erow[ps] = e;
           int en = -1;
           if (s + 1 < ns) en = tabb[(s + 1) * CH_SLOTS + slot];
-          nxt[ps] = en >= 0 && (en & CH_HAS_PREV);
+          enx[ps] = (en >= 0 && (en & CH_HAS_PREV)) ? en : -1;
           const bool ok = e >= 0 && cact && !(a.dbg & 4);       // (dbg bit 2: development ablation, every lane reads row 0)
           const size_t row = ok ? (size_t)(e & CH_ROW_MASK) : 0;
           const float* src = saved + row * D + (ok ? col : 0);
@@ -722,8 +722,12 @@ __global__ void __launch_bounds__(64 * (NMW + MW)) k_gru_chain_bwd_hx(ChainArgs 
           const size_t row = (size_t)(e & CH_ROW_MASK);
           // every lane runs the arithmetic (the row maxima are wave reductions); lanes past the width compute on zeros
           float4 gd = (upp && cact) ? ld4(upp + (row - (size_t)up_row0) * D + col) : zero4();
-          if (nxt[ps] && cact) gd = add4(gd, ld4(dpb + (size_t)slot * ldz + col));
+          if (enx[ps] >= 0 && cact) gd = add4(gd, ld4(dpb + (size_t)slot * ldz + col));
           const float4 rg = sr[ps], zg = sz[ps], ng = sn[ps], hn = shn[ps], hd = shd[ps];
+          if (a.d_arg && enx[ps] >= 0) {       // (wave-uniform) learnable decay: dL/d arg of the row that continues this track (gru_chain.hip)
+            const float part = cact ? chain_dot_prev(ld4(dpb + (size_t)slot * ldz + col), zg, ng, hd) : 0.f;
+            chain_store_d_arg(a, R, enx[ps], part, lane);
+          }
           float4 dr_pre, dz_pre, dn_pre, dhn, gz;
 #define TEMP_GATE(c)                                          \
           {                                                   \

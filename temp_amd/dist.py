@@ -247,6 +247,8 @@ class SnapshotShardedEncoder:
         self.world = dist.get_world_size(group)
         self.rank = dist.get_rank(group)
         assert model._can_batch() and model._can_chain(), "snapshot sharding needs the batched GRU + rec-only-last-layer path"
+        assert model.ent_encoder.layer_2.decay_spec() is None, \
+            "snapshot sharding runs the fixed decay only: --learnable-lambda (a learnable decay) is not sharded"
 
     # ---------------------------------------------------------------------------------------------
     def prepare(self, t_list, seq_len, train=True, target_edge_ids=None):

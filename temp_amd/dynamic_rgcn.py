@@ -21,7 +21,7 @@ from . import _hostlib
 from . import snapshot as S
 from .rrgcn import RRGCN, GRRGCNLayer, run_rnn
 from .tkg_module import TKG_Module
-from .gru_chain import GruInstance, GruProgram, gru_chain, prepare_program, zero_state_program
+from .gru_chain import GruInstance, GruProgram, chain_decay_usable, gru_chain, prepare_program, program_on_chain_kernels, zero_state_program
 from .gru_cell import GRUCell
 from .window import ChainPlan, Step, concat_steps, concat_steps_dedup, window_times
 
@@ -178,11 +178,21 @@ class DynamicRGCN(TKG_Module):
     # batched path
     # ---------------------------------------------------------------------------------------------
     def _can_chain(self):
-        """The whole recurrence as one autograd node (gru_chain): fixed decay, single GRU layer,
-        no per-position time embedding."""
+        """The whole recurrence as one autograd node (gru_chain): single GRU layer, no per-position time embedding; a
+        learnable decay (--learnable-lambda) only where the backend's chain kernels take one (a backend without
+        gru_chain_decay_supported keeps the per-position loop for it)."""
         enc = self.ent_encoder
         l2 = enc.layer_2
-        return (self.use_gru_chain and l2.decay_spec() is None and not enc.use_time_embedding and getattr(l2, "num_layers", 1) == 1)
+        if not (self.use_gru_chain and not enc.use_time_embedding and getattr(l2, "num_layers", 1) == 1):
+            return False
+        return l2.decay_spec() is None or self._chain_takes_decay()
+
+    def _chain_rnns(self):
+        return [self.ent_encoder.layer_2.rnn]
+
+    def _chain_takes_decay(self):
+        rnns = self._chain_rnns()
+        return chain_decay_usable(self.embed_size, _lib.GRU_TYPE1 if isinstance(rnns[0], GRUCell) else _lib.GRU_TORCH, len(rnns))
 
     def _visit_rows_on_device(self):
         return True
@@ -210,7 +220,7 @@ class DynamicRGCN(TKG_Module):
         wb.last_x = y2                                # GRU input rows of the step (= the "local" states of the post models)
         if wb.program is not None:
             want = self._chain_want(wb)
-            got = gru_chain(y2, wb.program, [l2.rnn], l2.inv_temperature, isinstance(l2.rnn, GRUCell), want=want)
+            got = gru_chain(y2, wb.program, [l2.rnn], l2.inv_temperature, isinstance(l2.rnn, GRUCell), want=want, decay=l2.decay_spec())
             hist = got[1] if wb.hist_inst >= 0 else None
             return got[0], (hist, hist)
         H, hist = None, None
@@ -283,6 +293,13 @@ class DynamicRGCN(TKG_Module):
                 self._build_program(wb)
                 _lib.pause_point()
                 prepare_program(wb.program, dev, self.embed_size, len(wb.out_inst), self._chain_want(wb))
+                # a learnable decay runs on the chain kernels only: a program they refuse (no chain tables, a panel longer than
+                # their step limit) stays on the per-position loop -- decided here, not in `run`
+                if self.ent_encoder.layer_2.decay_spec() is not None and not program_on_chain_kernels(wb.program, dev, self._chain_want(wb)):
+                    wb.program = None
+                    if wb.visit_rows_host is not None and wb.visit_rows is None:      # (the loop gathers by the visit rows on the device)
+                        wb.visit_rows = _lib.to_device(wb.visit_rows_host, dev)
+                        wb.visit_inv = TF.gather_inverse(wb.visit_rows_host, int(wb.g_all.n), dev)
         else:
             for st in wb.steps:
                 st.batched().device_graph(dev, 2 * self.num_rels)

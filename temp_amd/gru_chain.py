@@ -299,7 +299,7 @@ class GruProgram:
 
 class _GruChainFn(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, x_all, prog, lam, variant, n_rnn, want, x_keys, *weights):
+    def forward(ctx, x_all, prog, lam, variant, n_rnn, want, x_keys, dec_w, dec_b, *weights):
         be = get_backend()
         dev = x_all.device
         d = x_all.shape[1]
@@ -311,6 +311,16 @@ class _GruChainFn(torch.autograd.Function):
         tabs = None
         if CHAIN_KERNELS and hasattr(be, "gru_chain_fwd") and n_rnn <= _lib.CHAIN_MAX_RNN and be.gru_chain_supported(d):
             tabs = prog.chain_tables(dev, want)
+        # learnable decay (dec_w, dec_b = the layer's Linear(1, 1)): the chain kernels read {w, b} from device memory -- no host read
+        dk = {}
+        if dec_w is not None:
+            if tabs is None or not chain_decay_usable(d, variant, n_rnn):
+                raise _lib.TempAmdError("gru_chain: a learnable decay runs on the persistent chain kernels only, and %s" % (
+                    "this backend / width / cell has none that take it" if not chain_decay_usable(d, variant, n_rnn) else
+                    "they refuse this program (not a set of one-GRU chains, a panel longer than %d steps, or more than %d consumed "
+                    "instances): use the per-position loop (run_rnn with decay_spec())" % (_lib.CHAIN_MAX_STEPS, _lib.CHAIN_MAX_UP)))
+            dk = dict(decay=torch.cat([dec_w.detach().reshape(1), dec_b.detach().reshape(1)]).to(torch.float32))
+        ctx.decay = dk
         # nn.GRU cells on the f16 route: the chain forward computes the input gates itself from the x rows (temp_gru_chain_fwd_x) --
         # no gi, no gate GEMM.  (Independent of x_src: a labelled and an unlabelled program take the same kernel.)
         fused = bool(tabs is not None and FUSED_INPUT_GATES and variant == _lib.GRU_TORCH and hasattr(be, "gru_chain_fwd_x")
@@ -347,11 +357,11 @@ class _GruChainFn(torch.autograd.Function):
         if fused:
             packs = be.gru_chain_pack_x_multi([W[r][1] for r in range(n_rnn)], [W[r][0] for r in range(n_rnn)])
             be.gru_chain_fwd_x(tabs, x_all, prog.x_index(dev), lam, variant, packs, [W[r][3] for r in range(n_rnn)], [W[r][2] for r in range(n_rnn)],
-                               H, saved)
+                               H, saved, **dk)
         elif tabs is not None:
             packs = be.gru_chain_pack_multi([W[r][1] for r in range(n_rnn)]) if hasattr(be, "gru_chain_pack_multi") else \
                 [be.gru_chain_pack(W[r][1]) for r in range(n_rnn)]
-            be.gru_chain_fwd(tabs, gi, lam, variant, packs, [W[r][3] for r in range(n_rnn)], H, saved, gi_index=gi_index)
+            be.gru_chain_fwd(tabs, gi, lam, variant, packs, [W[r][3] for r in range(n_rnn)], H, saved, gi_index=gi_index, **dk)
         else:
             tens = prog.upload(dev)
             zero, none_idx = prog.constants(dev, d)
@@ -395,6 +405,14 @@ class _GruChainFn(torch.autograd.Function):
             given = {i: g.contiguous() for i, g in zip(ctx.want, d_outs) if g is not None}
             up = lambda i, it: given.get(i)                  # None: no upstream gradient for this instance's rows
         groups = list(prog.groups)
+        # learnable decay: the chain backward also writes dL / d(w dt + b) per row, reduced to (d_w, d_b) per GRU afterwards
+        dk = dict(ctx.decay, d_arg=torch.empty(N, dtype=torch.float32, device=dev)) if ctx.decay else {}
+
+        def decay_grads():
+            if not dk:
+                return None, None
+            d_wb = be.gru_chain_decay_reduce(ctx.tabs, d, variant, dk["d_arg"], ctx.n_rnn)        # [n_rnn, 2]: all GRUs share the one Linear
+            return d_wb[:, 0].sum().reshape(1, 1), d_wb[:, 1].sum().reshape(1)
         zero_state = [all(it.prev < 0 for it in prog.inst if it.group == gi) for gi in range(len(groups))]    # hdec = 0 on every row
         # GRUs with disjoint x rows (the two directions of a bidirectional chain, or the one GRU of a uni-directional one): ONE
         # weight-gradient launch for all d_W_ih / d_W_hh products, ONE reduction and ONE d_x launch
@@ -411,7 +429,7 @@ class _GruChainFn(torch.autograd.Function):
             #  weight-gradient and d_x products split it with; integer maxima, so bit-repeatable)
             keyed = bool(KEYED_GRADS and hasattr(be, "gru_chain_keys_supported") and be.gru_chain_keys_supported(d))
             keys = (torch.empty(N, dtype=torch.int32, device=dev), torch.empty(ctx.n_rnn + ctx.tabs["n_panels"], 4 * d, dtype=torch.int32, device=dev)) if keyed else None
-            be.gru_chain_bwd_g4(ctx.tabs, saved, ups, lam, variant, ctx.packs, [W[r][3] for r in range(ctx.n_rnn)], g4, **({"keys": keys} if keyed else {}))
+            be.gru_chain_bwd_g4(ctx.tabs, saved, ups, lam, variant, ctx.packs, [W[r][3] for r in range(ctx.n_rnn)], g4, **({"keys": keys} if keyed else {}), **dk)
             d_x_all = torch.empty_like(x_all)
             xsl = [slice(g["x0"], g["x1"]) for g in groups]
             hsl = [slice(g["h0"], g["h1"]) for g in groups]
@@ -428,12 +446,12 @@ class _GruChainFn(torch.autograd.Function):
                     grads[4 * g["rnn"] + k] = gw[k]
             if not covered.all():
                 d_x_all[torch.from_numpy(~covered).to(dev)] = 0
-            return (d_x_all, None, None, None, None, None, None) + tuple(grads)
+            return (d_x_all, None, None, None, None, None, None) + decay_grads() + tuple(grads)
         dgi = torch.empty(N, G, dtype=torch.float32, device=dev)
         dgh = torch.empty(N, 3 * d, dtype=torch.float32, device=dev)
         if ctx.tabs is not None:
             ups = [dH] if ctx.want is None else [given.get(i) for i in ctx.want]
-            be.gru_chain_bwd(ctx.tabs, saved, ups, lam, variant, ctx.packs, [W[r][3] for r in range(ctx.n_rnn)], dgi, dgh)
+            be.gru_chain_bwd(ctx.tabs, saved, ups, lam, variant, ctx.packs, [W[r][3] for r in range(ctx.n_rnn)], dgi, dgh, **dk)
         else:
             tens = prog.upload(dev)
             decv = torch.empty(N, dtype=torch.float32, device=dev)
@@ -479,13 +497,24 @@ class _GruChainFn(torch.autograd.Function):
                 grads[j] = gw[k] if grads[j] is None else grads[j] + gw[k]
         if not written.all():
             d_x_all[torch.from_numpy(~written).to(dev)] = 0
-        return (d_x_all, None, None, None, None, None, None) + tuple(grads)
+        return (d_x_all, None, None, None, None, None, None) + decay_grads() + tuple(grads)
 
 
 def chain_kernels_usable(d, n_rnn=1):
     """True when gru_chain() will run a program of this width through the persistent chain kernels."""
     be = get_backend()
     return bool(CHAIN_KERNELS and hasattr(be, "gru_chain_fwd") and n_rnn <= _lib.CHAIN_MAX_RNN and be.gru_chain_supported(d))
+
+
+def chain_decay_usable(d, variant, n_rnn=1):
+    """True when the chain kernels of this backend, width and cell variant take a learnable decay (gru_chain(decay=...))."""
+    be = get_backend()
+    return bool(chain_kernels_usable(d, n_rnn) and hasattr(be, "gru_chain_decay_supported") and be.gru_chain_decay_supported(d, variant))
+
+
+def program_on_chain_kernels(prog, device, want):
+    """True when the chain kernels take this program for this `want` set (its tables exist; prepare_program has built them)."""
+    return prog.chain_tables(device, tuple(want) if want is not None else None) is not None
 
 
 def prepare_program(prog, device, d, n_rnn, want):
@@ -506,8 +535,9 @@ def zero_state_program(n):
     return GruProgram([GruInstance(n, 0, 0, -1, np.full(n, -1, dtype=np.int32), np.zeros(n, dtype=np.float32))])
 
 
-def gru_chain(x_all, prog, rnns, lam, type1=False, want=None, x_keys=None):
-    """Run a GruProgram.  x_keys: (row keys, column keys) of x_all from functional.gather_rows(keys=True), or None.  `rnns`: list of modules holding (weight_ih, weight_hh, bias_ih, bias_hh)
+def gru_chain(x_all, prog, rnns, lam, type1=False, want=None, x_keys=None, decay=None):
+    """Run a GruProgram.  decay: None = exp(-dt lam), or the layer's decay_spec() = (weight (1, 1), bias (1,)) of --learnable-lambda:
+    exp(-max(w dt + b, 0)), shared by all `rnns` (`lam` is not read; chain kernels only: anything they refuse raises).  x_keys: (row keys, column keys) of x_all from functional.gather_rows(keys=True), or None.  `rnns`: list of modules holding (weight_ih, weight_hh, bias_ih, bias_hh)
     (nn.GRU layer 0 or the type-1 GRUCell).  Returns H_all (prog.n_total, d), or -- with `want` = a list of instance ids --
     the states of just those instances (a tuple of (n_i, d) tensors; instances with 0 rows give empty tensors)."""
     ws = []
@@ -517,4 +547,5 @@ def gru_chain(x_all, prog, rnns, lam, type1=False, want=None, x_keys=None):
         else:
             ws += [r.weight_ih_l0, r.weight_hh_l0, r.bias_ih_l0, r.bias_hh_l0]
     return _GruChainFn.apply(x_all, prog, float(lam), _lib.GRU_TYPE1 if type1 else _lib.GRU_TORCH, len(rnns),
-                             tuple(want) if want is not None else None, x_keys, *ws)
+                             tuple(want) if want is not None else None, x_keys, decay[0] if decay is not None else None,
+                             decay[1] if decay is not None else None, *ws)
