@@ -972,11 +972,17 @@ __device__ __forceinline__ float4 pair_epilogue(float4 v, int node, int f, int D
 }
 
 // Forward: view = by-dst; fwd_row[p] = the row of M that edge position p reads.  A chunk that is its whole segment is finished
-// here (epilogue included); chunks of a multi-chunk segment go to their partial slots and k_pair_fix_epi.
+// here (epilogue included); chunks of a multi-chunk segment go to their partial slots and k_pair_fix_epi.  The nodes without an
+// incoming edge own no chunk: their row is the epilogue of a zero row, written behind the wave's chunks (it reads nothing a chunk
+// writes) -- a wave tests 64 in_deg words with one load and walks the set bits.
+// A node of a device-subsampled member whose edges were all dropped keeps its (now empty) chunks: its row is then written by the
+// chunk's wave (or k_pair_fix_epi) as well as by the in_deg loop -- the same bits (0 + epilogue) both times, so the double store is
+// harmless and intended.
 __global__ void __launch_bounds__(256) k_pair_gather_fwd(TempEdgeView v, const int32_t* __restrict__ fwd_row, const float* __restrict__ M,
                                                          const float* __restrict__ nnorm, int D, const int32_t* __restrict__ ids,
                                                          const float* __restrict__ t_loop, const float* __restrict__ bias, int act, DropSpec drop,
-                                                         float* __restrict__ out, float* __restrict__ partial) {
+                                                         float* __restrict__ out, float* __restrict__ partial, int n_nodes,
+                                                         const int32_t* __restrict__ in_deg) {
   const int lane = threadIdx.x & 63;
   const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), wpb = blockDim.x >> 6;
   const int f = lane << 2;
@@ -992,17 +998,23 @@ __global__ void __launch_bounds__(256) k_pair_gather_fwd(TempEdgeView v, const i
     if (slot < 0) st4(out + (size_t)seg * D + f, pair_epilogue(acc, seg, f, D, ids, t_loop, bias, act, drop));
     else st4(partial + (size_t)slot * D + f, acc);
   }
+  const int gw = blockIdx.x * wpb + wave, waves = gridDim.x * wpb;
+  for (int n0 = gw * 64; n0 < n_nodes; n0 += waves * 64) {
+    unsigned long long m = __ballot(n0 + lane < n_nodes && in_deg[n0 + lane] <= 0);
+    while (m) {
+      const int node = n0 + __ffsll((long long)m) - 1;
+      m &= m - 1;
+      if (active) st4(out + (size_t)node * D + f, pair_epilogue(zero4(), node, f, D, ids, t_loop, bias, act, drop));
+    }
+  }
 }
 
-// The rows k_pair_gather_fwd did not finish: the multi-chunk segments (ordered sum of their partial slots, then the epilogue) and
-// the nodes without an incoming edge (no chunk: the epilogue of a zero row).  One wave per item.
-// A node of a device-subsampled member whose edges were all dropped keeps its (now empty) chunks: its row is then written here as
-// well as by the chunk's wave / the fix loop -- the same bits (0 + epilogue) both times, so the double store is harmless and intended.
+// The rows k_pair_gather_fwd did not finish: the multi-chunk segments (ordered sum of their partial slots, then the epilogue).
+// One wave per entry; launched only for a view that has such segments.
 __global__ void __launch_bounds__(256) k_pair_fix_epi(int n_fix, const int32_t* __restrict__ fix_seg, const int32_t* __restrict__ fix_slot,
-                                                      const int32_t* __restrict__ fix_cnt, const float* __restrict__ partial, int n_nodes,
-                                                      const int32_t* __restrict__ in_deg, int D, const int32_t* __restrict__ ids,
-                                                      const float* __restrict__ t_loop, const float* __restrict__ bias, int act, DropSpec drop,
-                                                      float* __restrict__ out) {
+                                                      const int32_t* __restrict__ fix_cnt, const float* __restrict__ partial, int D,
+                                                      const int32_t* __restrict__ ids, const float* __restrict__ t_loop,
+                                                      const float* __restrict__ bias, int act, DropSpec drop, float* __restrict__ out) {
   const int lane = threadIdx.x & 63, wpb = blockDim.x >> 6;
   const int gw = blockIdx.x * wpb + (threadIdx.x >> 6), waves = gridDim.x * wpb;
   const int f = lane << 2;
@@ -1011,8 +1023,6 @@ __global__ void __launch_bounds__(256) k_pair_fix_epi(int n_fix, const int32_t* 
     const int seg = fix_seg[i];
     st4(out + (size_t)seg * D + f, pair_epilogue(fixup_walk(partial + (size_t)fix_slot[i] * D + f, 0, fix_cnt[i], D), seg, f, D, ids, t_loop, bias, act, drop));
   }
-  for (int node = gw; node < n_nodes; node += waves)
-    if (in_deg[node] <= 0) st4(out + (size_t)node * D + f, pair_epilogue(zero4(), node, f, D, ids, t_loop, bias, act, drop));
 }
 
 // Backward: view = by-pair (a = destination node).  G[pair] = sum over the pair's edges of nnorm[dst]^2 * dz[dst], in list order.
@@ -1030,79 +1040,104 @@ __global__ void __launch_bounds__(256) k_pair_gather_bwd(TempEdgeView v, const f
   }
 }
 
-// d_table[e] = sum_r G[r * n_table + e] . BD(W[r])^T, relations in order; one thread per float4 of d_table
+// acc (the lane's S float4 of one relation's weight row) += x^T (x) g blockwise, for the 4 features of a lane
 template <int S>
-__global__ void __launch_bounds__(64) k_pair_dtable(int n_table, int n_rel_rows, int D, const float* __restrict__ G, const float* __restrict__ W,
-                                                    float* __restrict__ d_table) {
-  const int D4 = D >> 2;
-  const int i = blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= n_table * D4) return;
-  const int e = i / D4, f = (i - e * D4) << 2;
-  float4 acc = zero4();
-#pragma unroll 4
-  for (int r = 0; r < n_rel_rows; ++r) {
-    const float* wr = W + (size_t)r * (D * S) + f * S;
-    float4 w[S];
-#pragma unroll
-    for (int j = 0; j < S; ++j) w[j] = ld4(wr + 4 * j);
-    block_mac<S, MODE_DX>(acc, ld4(G + ((size_t)r * n_table + e) * D + f), w, 1.f);
+__device__ __forceinline__ void block_outer(float4* acc, const float4 xx, const float4 gg) {
+  if (S == 1) {
+    acc[0].x = fmaf(xx.x, gg.x, acc[0].x);
+    acc[0].y = fmaf(xx.y, gg.y, acc[0].y);
+    acc[0].z = fmaf(xx.z, gg.z, acc[0].z);
+    acc[0].w = fmaf(xx.w, gg.w, acc[0].w);
+  } else if (S == 2) {
+    acc[0].x = fmaf(xx.x, gg.x, acc[0].x);
+    acc[0].y = fmaf(xx.x, gg.y, acc[0].y);
+    acc[0].z = fmaf(xx.y, gg.x, acc[0].z);
+    acc[0].w = fmaf(xx.y, gg.y, acc[0].w);
+    acc[1].x = fmaf(xx.z, gg.z, acc[1].x);
+    acc[1].y = fmaf(xx.z, gg.w, acc[1].y);
+    acc[1].z = fmaf(xx.w, gg.z, acc[1].z);
+    acc[1].w = fmaf(xx.w, gg.w, acc[1].w);
+  } else {
+    acc[0] = fma4(xx.x, gg, acc[0]);
+    acc[1] = fma4(xx.y, gg, acc[1]);
+    acc[2] = fma4(xx.z, gg, acc[2]);
+    acc[3] = fma4(xx.w, gg, acc[3]);
   }
-  st4(d_table + (size_t)e * D + f, acc);
 }
 
-// d_W[r] = sum_e table[e]^T (x) G[r * n_table + e] blockwise.  One 16-wave block per relation row: wave w sums its contiguous share
-// of the table rows in order, the shares are added in wave order.
+// The two P-row products of the backward in ONE pass over G: every row G[r, e] is loaded once and feeds
+//   d_table[e] = sum_r G[r, e] . BD(W[r])^T (+ add[e], the self-loop part)      and      d_W[r] = sum_e table[e]^T (x) G[r, e].
+// A block owns PT_TE consecutive table rows at a time (tiles_per_block such tiles, consecutive); its waves split the relation rows
+// into contiguous shares, so a wave has PT_TE independent row loads in flight per relation (its table rows stay in registers).  d_table: the waves' shares are added
+// through LDS in wave (= relation) order.  d_W: block b keeps its sum over its table rows, in row order, in dw_part[b]; the
+// blocks' sums are added in block order by reduce_slices (a single block writes d_W itself).  Every order is fixed.
+#define PT_TE 8
+#define PT_WAVES 8
+#define PT_MAX_BLOCKS 128
 template <int S>
-__global__ void __launch_bounds__(1024) k_pair_dw(int n_table, int D, const float* __restrict__ table, const float* __restrict__ G,
-                                                  float* __restrict__ dW) {
-  __shared__ float4 share[16][64];
+__global__ void __launch_bounds__(PT_WAVES * 64) k_pair_tail(int n_table, int n_rel_rows, int D, int tiles_per_block, const float* __restrict__ G,
+                                                             const float* __restrict__ W, const float* __restrict__ table,
+                                                             const float* __restrict__ add, float* __restrict__ d_table,
+                                                             float* __restrict__ dw_part) {
+  __shared__ float4 share[PT_WAVES][PT_TE][64];                 // 64 KB
   const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-  const int r = blockIdx.x, f = lane << 2;
+  const int f = lane << 2;
   const bool active = f < D;
-  const int per = (n_table + 15) >> 4;
-  const int e0 = min(n_table, wave * per), e1 = min(n_table, e0 + per);
-  float4 acc[S];
+  const int per = (n_rel_rows + PT_WAVES - 1) / PT_WAVES;
+  const int r0 = min(n_rel_rows, wave * per), r1 = min(n_rel_rows, r0 + per);
+  const int n_act = (n_rel_rows + per - 1) / per;               // waves that own a relation row
+  const size_t wrow = (size_t)D * S;
+  float* my_part = dw_part + (size_t)blockIdx.x * n_rel_rows * wrow;
+  for (int t = 0; t < tiles_per_block; ++t) {
+    const int e0 = (blockIdx.x * tiles_per_block + t) * PT_TE;
+    if (e0 >= n_table) break;                                   // (the same for the whole block)
+    float4 acc[PT_TE], x[PT_TE];
 #pragma unroll
-  for (int j = 0; j < S; ++j) acc[j] = zero4();
-  if (active) {
-    const float* g = G + (size_t)r * n_table * D + f;
-#pragma unroll 4
-    for (int e = e0; e < e1; ++e) {
-      const float4 xx = ld4(table + (size_t)e * D + f), gg = ld4(g + (size_t)e * D);
-      if (S == 1) {
-        acc[0].x = fmaf(xx.x, gg.x, acc[0].x);
-        acc[0].y = fmaf(xx.y, gg.y, acc[0].y);
-        acc[0].z = fmaf(xx.z, gg.z, acc[0].z);
-        acc[0].w = fmaf(xx.w, gg.w, acc[0].w);
-      } else if (S == 2) {
-        acc[0].x = fmaf(xx.x, gg.x, acc[0].x);
-        acc[0].y = fmaf(xx.x, gg.y, acc[0].y);
-        acc[0].z = fmaf(xx.y, gg.x, acc[0].z);
-        acc[0].w = fmaf(xx.y, gg.y, acc[0].w);
-        acc[1].x = fmaf(xx.z, gg.z, acc[1].x);
-        acc[1].y = fmaf(xx.z, gg.w, acc[1].y);
-        acc[1].z = fmaf(xx.w, gg.z, acc[1].z);
-        acc[1].w = fmaf(xx.w, gg.w, acc[1].w);
-      } else {
-        acc[0] = fma4(xx.x, gg, acc[0]);
-        acc[1] = fma4(xx.y, gg, acc[1]);
-        acc[2] = fma4(xx.z, gg, acc[2]);
-        acc[3] = fma4(xx.w, gg, acc[3]);
+    for (int u = 0; u < PT_TE; ++u) acc[u] = zero4();
+    if (active) {
+#pragma unroll
+      for (int u = 0; u < PT_TE; ++u) x[u] = e0 + u < n_table ? ld4(table + (size_t)(e0 + u) * D + f) : zero4();
+      for (int r = r0; r < r1; ++r) {
+        const float* wr = W + (size_t)r * wrow + f * S;
+        const float* gr = G + ((size_t)r * n_table + e0) * D + f;
+        float4 w[S], dw[S], g[PT_TE];
+#pragma unroll
+        for (int u = 0; u < PT_TE; ++u) g[u] = e0 + u < n_table ? ld4(gr + (size_t)u * D) : zero4();
+#pragma unroll
+        for (int j = 0; j < S; ++j) { w[j] = ld4(wr + 4 * j); dw[j] = zero4(); }
+#pragma unroll
+        for (int u = 0; u < PT_TE; ++u) {
+          block_mac<S, MODE_DX>(acc[u], g[u], w, 1.f);
+          block_outer<S>(dw, x[u], g[u]);
+        }
+        float* p = my_part + (size_t)r * wrow + f * S;
+#pragma unroll
+        for (int j = 0; j < S; ++j) st4(p + 4 * j, t > 0 ? add4(ld4(p + 4 * j), dw[j]) : dw[j]);      // (the lane's own earlier store)
       }
     }
-  }
+    if (wave < n_act) {
 #pragma unroll
-  for (int j = 0; j < S; ++j) {
-    share[wave][lane] = acc[j];
+      for (int u = 0; u < PT_TE; ++u) share[wave][u][lane] = acc[u];
+    }
     __syncthreads();
-    if (wave == 0 && active) {
-      float4 t = share[0][lane];
-#pragma unroll
-      for (int u = 1; u < 16; ++u) t = add4(t, share[u][lane]);
-      st4(dW + (size_t)r * (D * S) + f * S + 4 * j, t);
+    const int e = e0 + wave;                                    // (PT_WAVES == PT_TE: wave u finishes row u of the tile)
+    if (active && e < n_table) {
+      float4 s = share[0][wave][lane];
+      for (int q = 1; q < n_act; ++q) s = add4(s, share[q][wave][lane]);
+      if (add) s = add4(s, ld4(add + (size_t)e * D + f));
+      st4(d_table + (size_t)e * D + f, s);
     }
     __syncthreads();
   }
+}
+static_assert(PT_WAVES == PT_TE, "k_pair_tail: one wave per table row of the tile in the d_table reduction");
+struct PairTailGrid { int blocks, tiles_per_block; };
+static PairTailGrid pair_tail_grid(int n_table) {
+  const int tiles = ceil_div(n_table > 0 ? n_table : 1, PT_TE);
+  PairTailGrid t;
+  t.tiles_per_block = ceil_div(tiles, PT_MAX_BLOCKS);
+  t.blocks = ceil_div(tiles, t.tiles_per_block);
+  return t;
 }
 
 // seg_of[p] = chunk_seg[c] for p in [chunk_beg[c], chunk_end[c]); one wave per chunk (seg_of was filled with -1)
@@ -1137,11 +1172,12 @@ static PairFwdWs carve_pair_fwd(const TempGraph* g, const TempPairView* pv, int 
 }
 
 struct PairBwdWs {
-  float *dz, *dzm, *G, *part, *seg_dz;
+  float *dz, *dzm, *G, *part, *seg_dz, *loop_dt, *dw_part;
   void *ss, *tn, *cs;
   size_t ss_bytes, tn_bytes, cs_bytes, total;
 };
-static PairBwdWs carve_pair_bwd(const TempGraph* g, const TempPairView* pv, int d_in, int d_out, char* base) {
+// S: block size of the relation weights (fast_shape); loop_dt: the self-loop part of d_table, dw_part: k_pair_tail's per-block d_W
+static PairBwdWs carve_pair_bwd(const TempGraph* g, const TempPairView* pv, int d_in, int d_out, int S, char* base) {
   PairBwdWs w;
   size_t off = 0;
   auto take = [&](size_t bytes) { char* p = base ? base + off : nullptr; off += align_up(bytes, 256); return p; };
@@ -1150,6 +1186,8 @@ static PairBwdWs carve_pair_bwd(const TempGraph* g, const TempPairView* pv, int 
   w.G = (float*)take((size_t)pv->by_pair.n_seg * d_out * sizeof(float));
   w.part = (float*)take(partial_bytes(pv->by_pair.n_partial, d_out));
   w.seg_dz = (float*)take((size_t)pv->n_table * d_out * sizeof(float));
+  w.loop_dt = (float*)take((size_t)pv->n_table * d_in * sizeof(float));
+  w.dw_part = (float*)take((size_t)pair_tail_grid(pv->n_table).blocks * pv->n_rel_rows * d_in * S * sizeof(float));
   w.ss_bytes = segment_sum_rows_workspace(pv->n_table, g->n_nodes, d_out);
   w.ss = take(w.ss_bytes);
   w.tn_bytes = gemm_tn_workspace(pv->n_table, d_in, d_out);
@@ -1340,24 +1378,27 @@ int temp_rgcn_pair_fwd(const TempGraph* g, const TempPairView* pv, const float* 
   if (rc) return rc;
   const DropSpec ds = drop_spec(drop);
   const TempEdgeView& v = g->by_dst;
-  if (v.n_chunks > 0) {
-    grid = (v.n_chunks + 3) / 4;
-    grid = grid < 8 ? 8 : (grid > 4096 ? 4096 : (grid + 7) / 8 * 8);
-    TEMP_LAUNCH(K_PAIR_GATHER_FWD, k_pair_gather_fwd, dim3(grid), dim3(256), 0, st, v, pv->fwd_row, w.M, g->nnorm, D, ids, w.t_loop, bias, act, ds, out,
-                w.partial);
-  }
-  const int items = v.n_fix > (g->n_nodes + 7) / 8 ? v.n_fix : (g->n_nodes + 7) / 8;
+  // (a view without chunks still takes the launch: the rows of the nodes without an incoming edge; one wave per 64 nodes)
+  const int items = v.n_chunks > (g->n_nodes + 63) / 64 ? v.n_chunks : (g->n_nodes + 63) / 64;
   grid = (items + 3) / 4;
-  if (grid > 4096) grid = 4096;
-  TEMP_LAUNCH(K_PAIR_FIX_EPI, k_pair_fix_epi, dim3(grid), dim3(256), 0, st, v.n_fix, v.fix_seg, v.fix_slot, v.fix_cnt, w.partial, g->n_nodes, g->in_deg, D,
-              ids, w.t_loop, bias, act, ds, out);
+  grid = grid < 8 ? 8 : (grid > 4096 ? 4096 : (grid + 7) / 8 * 8);
+  TEMP_LAUNCH(K_PAIR_GATHER_FWD, k_pair_gather_fwd, dim3(grid), dim3(256), 0, st, v, pv->fwd_row, w.M, g->nnorm, D, ids, w.t_loop, bias, act, ds, out,
+              w.partial, g->n_nodes, g->in_deg);
+  if (v.n_fix > 0) {
+    grid = (v.n_fix + 3) / 4;
+    if (grid > 4096) grid = 4096;
+    TEMP_LAUNCH(K_PAIR_FIX_EPI, k_pair_fix_epi, dim3(grid), dim3(256), 0, st, v.n_fix, v.fix_seg, v.fix_slot, v.fix_cnt, w.partial, D, ids, w.t_loop,
+                bias, act, ds, out);
+  }
   g_pair_launches.fetch_add(1, std::memory_order_relaxed);
   return launch_status();
 }
 
 size_t temp_rgcn_pair_bwd_workspace(const TempGraph* g, const TempPairView* pv, int d_in, int d_out, int num_bases) {
-  if (!g || !pv || num_bases <= 0 || d_in <= 0 || d_out <= 0 || pv->n_table < 0 || pv->by_pair.n_seg < 0) return 0;
-  return carve_pair_bwd(g, pv, d_in, d_out, nullptr).total;
+  if (!g || !pv || num_bases <= 0 || d_in <= 0 || d_out <= 0 || pv->n_table < 0 || pv->n_rel_rows < 0 || pv->by_pair.n_seg < 0) return 0;
+  int S = 0;
+  if (!fast_shape(d_in, d_out, num_bases, &S)) S = 4;          // (the call itself refuses such a shape)
+  return carve_pair_bwd(g, pv, d_in, d_out, S, nullptr).total;
 }
 
 int temp_rgcn_pair_bwd(const TempGraph* g, const TempPairView* pv, const float* table, const int32_t* ids, const int32_t* inv_ptr,
@@ -1383,7 +1424,7 @@ int temp_rgcn_pair_bwd(const TempGraph* g, const TempPairView* pv, const float* 
     if (has_bias && hipMemsetAsync(d_bias, 0, (size_t)d_out * sizeof(float), st) != hipSuccess) return TEMP_E_LAUNCH;
     return TEMP_OK;
   }
-  const PairBwdWs w = carve_pair_bwd(g, pv, d_in, d_out, (char*)workspace);
+  const PairBwdWs w = carve_pair_bwd(g, pv, d_in, d_out, S, (char*)workspace);
   const int D = d_in;
   const float* dz = d_out_grad;
   int rc;
@@ -1392,39 +1433,42 @@ int temp_rgcn_pair_bwd(const TempGraph* g, const TempPairView* pv, const float* 
     if (rc) return rc;
     dz = w.dz;
   }
+  // The self-loop part as in temp_rgcn_table_bwd:  loop_dt = segsum(dzm) . loop_w^T,  d_loop_w = table^T . segsum(dzm),  d_bias.
+  // It reads dz, table and loop_w only -- nothing the gather below writes -- and its kernels are small (a tenth of the machine or
+  // less), so it runs on the side stream beside the gather; k_pair_tail adds loop_dt.  No side stream (TEMP_OPT_OVERLAP = 0, every
+  // entry busy): the same launches ahead of the gather in the caller's stream, the same bits.
+  SideScope side(st);
+  const bool beside = !(option(TEMP_OPT_DEBUG) & 0x800000) && side_fork(side);      // (TEMP_DEBUG bit 23: A/B, in-stream)
+  hipStream_t sl = beside ? side.ss->s : st;
+  const DropSpec ds = drop_spec(drop);
+  const float* dzm = dz;
+  rc = TEMP_OK;
+  if (ds.p > 0.f) {
+    rc = mask_rows(g->n_nodes, d_out, dz, w.dzm, ds, sl);
+    dzm = w.dzm;
+  }
+  if (!rc) rc = segment_sum_rows(n_table, d_out, inv_ptr, inv_order, dzm, nullptr, w.seg_dz, sl, g->n_nodes, w.ss, w.ss_bytes);
+  if (!rc) rc = gemm_add_bias_act(K_GEMM_LOOP_DX, n_table, d_in, d_out, w.seg_dz, d_out, nullptr, loop_w, d_out, 1, nullptr, 0, nullptr, nullptr,
+                                  TEMP_ACT_NONE, w.loop_dt, d_in, sl);
+  if (!rc) rc = gemm_tn(n_table, d_in, d_out, table, d_in, w.seg_dz, d_out, d_loop_w, d_out, w.tn, w.tn_bytes, sl);
+  if (!rc && has_bias) rc = colsum(g->n_nodes, d_out, dz, d_out, d_bias, w.cs, w.cs_bytes, sl);
+  if (beside && !side_done(side) && !rc) rc = TEMP_E_LAUNCH;
+  if (rc) return rc;                             // (SideScope joins a forked branch)
   // G: one ordered gather-sum by pair (every pair owns a chunk, so every row of G is written), then the multi-chunk pairs
   const TempEdgeView& v = pv->by_pair;
   int grid = (v.n_chunks + 3) / 4;
   grid = grid < 1 ? 1 : (grid > 4096 ? 4096 : grid);
   TEMP_LAUNCH(K_PAIR_GATHER_BWD, k_pair_gather_bwd, dim3(grid), dim3(256), 0, st, v, dz, g->nnorm, D, w.G, w.part);
   launch_fixup(v, w.part, D, w.G, st);
-  // the two P-row products: d_table (aggregation part) and the relation weights
-  grid = ceil_div((long long)n_table * (D / 4), 64);
-  if (S == 1) TEMP_LAUNCH(K_PAIR_DTABLE, k_pair_dtable<1>, dim3(grid), dim3(64), 0, st, n_table, n_rel_rows, D, w.G, weight, d_table);
-  else if (S == 2) TEMP_LAUNCH(K_PAIR_DTABLE, k_pair_dtable<2>, dim3(grid), dim3(64), 0, st, n_table, n_rel_rows, D, w.G, weight, d_table);
-  else TEMP_LAUNCH(K_PAIR_DTABLE, k_pair_dtable<4>, dim3(grid), dim3(64), 0, st, n_table, n_rel_rows, D, w.G, weight, d_table);
-  if (S == 1) TEMP_LAUNCH(K_PAIR_DW, k_pair_dw<1>, dim3(n_rel_rows), dim3(1024), 0, st, n_table, D, table, w.G, d_weight);
-  else if (S == 2) TEMP_LAUNCH(K_PAIR_DW, k_pair_dw<2>, dim3(n_rel_rows), dim3(1024), 0, st, n_table, D, table, w.G, d_weight);
-  else TEMP_LAUNCH(K_PAIR_DW, k_pair_dw<4>, dim3(n_rel_rows), dim3(1024), 0, st, n_table, D, table, w.G, d_weight);
-  // the self-loop part as in temp_rgcn_table_bwd:  d_table += segsum(dzm) . loop_w^T,  d_loop_w = table^T . segsum(dzm)
-  const DropSpec ds = drop_spec(drop);
-  const float* dzm = dz;
-  if (ds.p > 0.f) {
-    rc = mask_rows(g->n_nodes, d_out, dz, w.dzm, ds, st);
-    if (rc) return rc;
-    dzm = w.dzm;
-  }
-  rc = segment_sum_rows(n_table, d_out, inv_ptr, inv_order, dzm, nullptr, w.seg_dz, st, g->n_nodes, w.ss, w.ss_bytes);
+  rc = side.join();
   if (rc) return rc;
-  rc = gemm_add_bias_act(K_GEMM_LOOP_DX, n_table, d_in, d_out, w.seg_dz, d_out, nullptr, loop_w, d_out, 1, d_table, d_in, nullptr, nullptr,
-                         TEMP_ACT_NONE, d_table, d_in, st);
-  if (rc) return rc;
-  rc = gemm_tn(n_table, d_in, d_out, table, d_in, w.seg_dz, d_out, d_loop_w, d_out, w.tn, w.tn_bytes, st);
-  if (rc) return rc;
-  if (has_bias) {
-    rc = colsum(g->n_nodes, d_out, dz, d_out, d_bias, w.cs, w.cs_bytes, st);
-    if (rc) return rc;
-  }
+  // the two P-row products in one pass over G: d_table (aggregation part + loop_dt) and the relation weights
+  const PairTailGrid tg = pair_tail_grid(n_table);
+  float* dwp = tg.blocks > 1 ? w.dw_part : d_weight;
+  if (S == 1) TEMP_LAUNCH(K_PAIR_TAIL, k_pair_tail<1>, dim3(tg.blocks), dim3(PT_WAVES * 64), 0, st, n_table, n_rel_rows, D, tg.tiles_per_block, w.G, weight, table, w.loop_dt, d_table, dwp);
+  else if (S == 2) TEMP_LAUNCH(K_PAIR_TAIL, k_pair_tail<2>, dim3(tg.blocks), dim3(PT_WAVES * 64), 0, st, n_table, n_rel_rows, D, tg.tiles_per_block, w.G, weight, table, w.loop_dt, d_table, dwp);
+  else TEMP_LAUNCH(K_PAIR_TAIL, k_pair_tail<4>, dim3(tg.blocks), dim3(PT_WAVES * 64), 0, st, n_table, n_rel_rows, D, tg.tiles_per_block, w.G, weight, table, w.loop_dt, d_table, dwp);
+  if (tg.blocks > 1) reduce_slices(tg.blocks, (size_t)n_rel_rows * wrow, (int)wrow, w.dw_part, d_weight, (int)wrow, st);
   g_pair_launches.fetch_add(1, std::memory_order_relaxed);
   return launch_status();
 }
