@@ -113,12 +113,22 @@ __device__ __forceinline__ float4 drop4(const DropSpec& d, unsigned row, unsigne
                      v.w * drop_scale(d, row, col + 3));
 }
 
-// process-wide kernel-selection switches (include/temp_amd.h: temp_set_option); definition in gemm_kernels.hip
+// process-wide kernel-selection switches (include/temp_amd.h: temp_set_option); definition in runtime.hip
 int option(int key);
 void hx_count();                            // diagnostic counter of f16-split kernel launches (temp_f16_launches)
 
 inline int ceil_div(long long a, long long b) { return (int)((a + b - 1) / b); }
 inline size_t align_up(size_t x, size_t a) { return (x + a - 1) / a * a; }
+
+// Workspace carver: consecutive 256-byte-aligned pieces of one caller-supplied buffer.  Without a base it only counts, which is
+// how the *_workspace queries size what the calls then carve.
+struct Carver {
+  char* base;
+  size_t off;
+  explicit Carver(void* b) : base((char*)b), off(0) {}
+  char* take(size_t bytes) { char* p = base ? base + off : nullptr; off += align_up(bytes, 256); return p; }
+  size_t total() const { return off + 256; }                   // (slack for a base that is not itself 256-byte aligned)
+};
 
 // ---- optional per-kernel timing (bench only): HIP events recorded on the launch stream around
 // every kernel launch between temp_trace_begin() and temp_trace_end().  Off by default; the only
@@ -144,7 +154,8 @@ inline int launch_status() {
   return e == hipSuccess ? TEMP_OK : TEMP_E_LAUNCH;
 }
 
-// --- internal launch helpers shared across translation units (definitions in the .hip files) -----
+// --- internal launch helpers shared across translation units: the GEMMs, reductions and element-wise passes are defined in
+// gemm_kernels.hip, the segment sums in rows_kernels.hip -----
 struct EpiAddBiasAct;   // gemm_kernels.hip
 
 // C[M,N] = act( (row_mask==NULL || row_mask[m] > 0 ? addend[m,n] : 0) + bias[n] + A[M,K] . B )

@@ -517,18 +517,17 @@ __global__ void __launch_bounds__(256) k_decay_rows(int n, int D, const float* _
 struct GruBwdWs { float* dgi; float* dgh; float* decv; void* tn; size_t tn_bytes; void* cs; size_t cs_bytes; size_t total; };
 static GruBwdWs carve_gru(int n, int d, int variant, char* base) {
   GruBwdWs w;
-  size_t off = 0;
-  auto take = [&](size_t bytes) { char* p = base ? base + off : nullptr; off += align_up(bytes, 256); return p; };
+  Carver c(base);
   const int gi_w = (variant == TEMP_GRU_TORCH) ? 3 * d : d;
-  w.dgi = (float*)take((size_t)n * gi_w * sizeof(float));
-  w.dgh = (float*)take((size_t)n * 3 * d * sizeof(float));
-  w.decv = (float*)take((size_t)(n > 0 ? n : 1) * sizeof(float));
+  w.dgi = (float*)c.take((size_t)n * gi_w * sizeof(float));
+  w.dgh = (float*)c.take((size_t)n * 3 * d * sizeof(float));
+  w.decv = (float*)c.take((size_t)(n > 0 ? n : 1) * sizeof(float));
   w.tn_bytes = gemm_tn_workspace(n, 3 * d, d);
   if (gemm_tn_workspace(n, gi_w, d) > w.tn_bytes) w.tn_bytes = gemm_tn_workspace(n, gi_w, d);
-  w.tn = take(w.tn_bytes);
+  w.tn = c.take(w.tn_bytes);
   w.cs_bytes = colsum_workspace(n, 3 * d);
-  w.cs = take(w.cs_bytes);
-  w.total = off + 256;
+  w.cs = c.take(w.cs_bytes);
+  w.total = c.total();
   return w;
 }
 

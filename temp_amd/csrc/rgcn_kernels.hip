@@ -1150,6 +1150,13 @@ __global__ void __launch_bounds__(256) k_expand_chunk_seg(int n_chunks, const in
   }
 }
 
+// sizes of the pair route: the block sizes of fast_shape (-> *S), P * d_out within 32-bit element offsets
+static int pair_shape(int n_table, int d_in, int d_out, int num_bases, int n_rel_rows, int* S) {
+  if (n_table <= 0 || d_in <= 0 || d_out <= 0 || num_bases <= 0 || n_rel_rows <= 0) return TEMP_E_BADARG;
+  if (!fast_shape(d_in, d_out, num_bases, S)) return TEMP_E_UNSUPPORTED;
+  return (long long)n_rel_rows * n_table >= (1LL << 31) / d_out ? TEMP_E_UNSUPPORTED : TEMP_OK;
+}
+
 static bool pair_view_ok(const TempGraph* g, const TempPairView* pv, int n_table, int n_rel_rows) {
   if (!g || !pv || pv->n_table != n_table || pv->n_rel_rows != n_rel_rows) return false;
   const TempEdgeView& v = pv->by_pair;
@@ -1159,66 +1166,106 @@ static bool pair_view_ok(const TempGraph* g, const TempPairView* pv, int n_table
   return g->by_dst.n_edges == 0 || pv->fwd_row != nullptr;
 }
 
+// ---- host scaffolding shared by the layer's entry points (whole, split, table-fed, pair and isolated) ------------------------
+static size_t weight_row(int d_in, int d_out, int num_bases) { return (size_t)num_bases * (d_in / num_bases) * (d_out / num_bases); }   // floats
+// sizes every route takes: TEMP_E_BADARG for one that is not positive, TEMP_E_UNSUPPORTED for widths the kernels do not divide
+static int layer_shape(int d_in, int d_out, int num_bases, int n_rel_rows) {
+  if (d_in <= 0 || d_out <= 0 || num_bases <= 0 || n_rel_rows <= 0) return TEMP_E_BADARG;
+  return (d_in % num_bases || d_out % num_bases || d_in % 4 || d_out % 4) ? TEMP_E_UNSUPPORTED : TEMP_OK;
+}
+// what a backward needs beyond its operands: the forward's output under a ReLU, somewhere to put the bias gradient
+static int grad_args(int act, const float* out, int has_bias, const float* d_bias) { return ((act == TEMP_ACT_RELU && !out) || (has_bias && !d_bias)) ? TEMP_E_BADARG : TEMP_OK; }
+static bool act_ok(int act) { return act == TEMP_ACT_NONE || act == TEMP_ACT_RELU; }
+static bool rel_view_ok(const TempGraph* g, int n_rel_rows) { return view_ok(g->by_rel) && g->by_rel.n_seg == n_rel_rows; }   // one segment per relation row
+
+// a graph without nodes: every parameter gradient (and d_table, for the table-fed routes) is zero
+static int zero_grads(int d_in, int d_out, int n_rel_rows, size_t wrow, int has_bias, float* d_weight, float* d_loop_w, float* d_bias,
+                      hipStream_t st, float* d_table = nullptr, int n_table = 0) {
+  if (d_table && hipMemsetAsync(d_table, 0, (size_t)n_table * d_in * sizeof(float), st) != hipSuccess) return TEMP_E_LAUNCH;
+  if (hipMemsetAsync(d_weight, 0, (size_t)n_rel_rows * wrow * sizeof(float), st) != hipSuccess) return TEMP_E_LAUNCH;
+  if (hipMemsetAsync(d_loop_w, 0, (size_t)d_in * d_out * sizeof(float), st) != hipSuccess) return TEMP_E_LAUNCH;
+  if (has_bias && hipMemsetAsync(d_bias, 0, (size_t)d_out * sizeof(float), st) != hipSuccess) return TEMP_E_LAUNCH;
+  return TEMP_OK;
+}
+
+// *dz = the gradient behind the activation: (out > 0 ? d_out : 0) written to buf under a ReLU, d_out itself otherwise
+static int grad_dz(int act, size_t elems, const float* out, const float* d_out_grad, float* buf, hipStream_t st, const float** dz) {
+  *dz = act == TEMP_ACT_RELU ? buf : d_out_grad;
+  return act == TEMP_ACT_RELU ? relu_bwd(elems, out, d_out_grad, buf, st) : (int)TEMP_OK;
+}
+// *dzm = the gradient of the self-loop message: dz masked like the forward's dropout, written to buf; dz itself without dropout
+static int grad_dzm(const DropSpec& ds, int n, int d_out, const float* dz, float* buf, hipStream_t st, const float** dzm) {
+  *dzm = ds.p > 0.f ? buf : dz;
+  return ds.p > 0.f ? mask_rows(n, d_out, dz, buf, ds, st) : (int)TEMP_OK;
+}
+
+// d_loop_w = x^T . gm over `rows` rows (x: the layer's input rows and gm the self-loop gradient dzm, or the table and dzm summed
+// per table row), d_bias = the column sums of dz over the graph's nodes; their workspaces are the last two pieces of every carve
+struct LoopWs { void *tn, *cs; size_t tn_bytes, cs_bytes; };
+static LoopWs carve_loop(Carver& c, int rows, int n_nodes, int d_in, int d_out) {
+  LoopWs l;
+  l.tn_bytes = gemm_tn_workspace(rows, d_in, d_out);
+  l.tn = c.take(l.tn_bytes);
+  l.cs_bytes = colsum_workspace(n_nodes, d_out);
+  l.cs = c.take(l.cs_bytes);
+  return l;
+}
+static int loop_grads(const LoopWs& l, int rows, int d_in, int d_out, const float* x, const float* gm, int n_nodes, const float* dz, int has_bias,
+                      float* d_loop_w, float* d_bias, hipStream_t st) {
+  int rc = gemm_tn(rows, d_in, d_out, x, d_in, gm, d_out, d_loop_w, d_out, l.tn, l.tn_bytes, st);
+  if (!rc && has_bias) rc = colsum(n_nodes, d_out, dz, d_out, d_bias, l.cs, l.cs_bytes, st);
+  return rc;
+}
+
+// one launch of a kernel templated on the relation weights' block size S (fast_shape: 1, 2 or 4)
+#define TEMP_LAUNCH_S(KID, kernel, S, ...)                                                                            \
+  do {                                                                                                                \
+    if ((S) == 1) TEMP_LAUNCH(KID, kernel<1>, __VA_ARGS__); else if ((S) == 2) TEMP_LAUNCH(KID, kernel<2>, __VA_ARGS__); \
+    else TEMP_LAUNCH(KID, kernel<4>, __VA_ARGS__);                                                                    \
+  } while (0)
+
 struct PairFwdWs { float *partial, *t_loop, *M; size_t total; };
 static PairFwdWs carve_pair_fwd(const TempGraph* g, const TempPairView* pv, int d_out, char* base) {
   PairFwdWs w;
-  size_t off = 0;
-  auto take = [&](size_t bytes) { char* p = base ? base + off : nullptr; off += align_up(bytes, 256); return p; };
-  w.partial = (float*)take((size_t)g->by_dst.n_partial * d_out * sizeof(float));
-  w.t_loop = (float*)take((size_t)pv->n_table * d_out * sizeof(float));
-  w.M = (float*)take((size_t)pv->n_rel_rows * pv->n_table * d_out * sizeof(float));
-  w.total = off + 256;
+  Carver c(base);
+  w.partial = (float*)c.take((size_t)g->by_dst.n_partial * d_out * sizeof(float));
+  w.t_loop = (float*)c.take((size_t)pv->n_table * d_out * sizeof(float));
+  w.M = (float*)c.take((size_t)pv->n_rel_rows * pv->n_table * d_out * sizeof(float));
+  w.total = c.total();
   return w;
 }
 
-struct PairBwdWs {
-  float *dz, *dzm, *G, *part, *seg_dz, *loop_dt, *dw_part;
-  void *ss, *tn, *cs;
-  size_t ss_bytes, tn_bytes, cs_bytes, total;
-};
+struct PairBwdWs { float *dz, *dzm, *G, *part, *seg_dz, *loop_dt, *dw_part; void* ss; size_t ss_bytes; LoopWs loop; size_t total; };
 // S: block size of the relation weights (fast_shape); loop_dt: the self-loop part of d_table, dw_part: k_pair_tail's per-block d_W
 static PairBwdWs carve_pair_bwd(const TempGraph* g, const TempPairView* pv, int d_in, int d_out, int S, char* base) {
   PairBwdWs w;
-  size_t off = 0;
-  auto take = [&](size_t bytes) { char* p = base ? base + off : nullptr; off += align_up(bytes, 256); return p; };
-  w.dz = (float*)take((size_t)g->n_nodes * d_out * sizeof(float));
-  w.dzm = (float*)take((size_t)g->n_nodes * d_out * sizeof(float));
-  w.G = (float*)take((size_t)pv->by_pair.n_seg * d_out * sizeof(float));
-  w.part = (float*)take(partial_bytes(pv->by_pair.n_partial, d_out));
-  w.seg_dz = (float*)take((size_t)pv->n_table * d_out * sizeof(float));
-  w.loop_dt = (float*)take((size_t)pv->n_table * d_in * sizeof(float));
-  w.dw_part = (float*)take((size_t)pair_tail_grid(pv->n_table).blocks * pv->n_rel_rows * d_in * S * sizeof(float));
+  Carver c(base);
+  w.dz = (float*)c.take((size_t)g->n_nodes * d_out * sizeof(float));
+  w.dzm = (float*)c.take((size_t)g->n_nodes * d_out * sizeof(float));
+  w.G = (float*)c.take((size_t)pv->by_pair.n_seg * d_out * sizeof(float));
+  w.part = (float*)c.take(partial_bytes(pv->by_pair.n_partial, d_out));
+  w.seg_dz = (float*)c.take((size_t)pv->n_table * d_out * sizeof(float));
+  w.loop_dt = (float*)c.take((size_t)pv->n_table * d_in * sizeof(float));
+  w.dw_part = (float*)c.take((size_t)pair_tail_grid(pv->n_table).blocks * pv->n_rel_rows * d_in * S * sizeof(float));
   w.ss_bytes = segment_sum_rows_workspace(pv->n_table, g->n_nodes, d_out);
-  w.ss = take(w.ss_bytes);
-  w.tn_bytes = gemm_tn_workspace(pv->n_table, d_in, d_out);
-  w.tn = take(w.tn_bytes);
-  w.cs_bytes = colsum_workspace(g->n_nodes, d_out);
-  w.cs = take(w.cs_bytes);
-  w.total = off + 256;
+  w.ss = c.take(w.ss_bytes);
+  w.loop = carve_loop(c, pv->n_table, g->n_nodes, d_in, d_out);
+  w.total = c.total();
   return w;
 }
 
-struct TableBwdWs {
-  float *dz, *dzm, *d_h, *part_dx, *part_dw, *seg_dz;
-  void *tn, *cs;
-  size_t tn_bytes, cs_bytes, total;
-};
+struct TableBwdWs { float *dz, *dzm, *d_h, *part_dx, *part_dw, *seg_dz; LoopWs loop; size_t total; };
 static TableBwdWs carve_table_bwd(const TempGraph* g, int n_table, int d_in, int d_out, int num_bases, char* base) {
   TableBwdWs w;
-  size_t off = 0;
-  auto take = [&](size_t bytes) { char* p = base ? base + off : nullptr; off += align_up(bytes, 256); return p; };
-  const size_t wrow = (size_t)num_bases * (d_in / num_bases) * (d_out / num_bases);
-  w.dz = (float*)take((size_t)g->n_nodes * d_out * sizeof(float));
-  w.dzm = (float*)take((size_t)g->n_nodes * d_out * sizeof(float));
-  w.d_h = (float*)take((size_t)g->n_nodes * d_in * sizeof(float));
-  w.part_dx = (float*)take(partial_bytes(g->by_src.n_partial, d_in));
-  w.part_dw = (float*)take(partial_bytes(g->by_rel.n_partial, wrow));
-  w.seg_dz = (float*)take((size_t)n_table * d_out * sizeof(float));
-  w.tn_bytes = gemm_tn_workspace(n_table, d_in, d_out);
-  w.tn = take(w.tn_bytes);
-  w.cs_bytes = colsum_workspace(g->n_nodes, d_out);
-  w.cs = take(w.cs_bytes);
-  w.total = off + 256;
+  Carver c(base);
+  w.dz = (float*)c.take((size_t)g->n_nodes * d_out * sizeof(float));
+  w.dzm = (float*)c.take((size_t)g->n_nodes * d_out * sizeof(float));
+  w.d_h = (float*)c.take((size_t)g->n_nodes * d_in * sizeof(float));
+  w.part_dx = (float*)c.take(partial_bytes(g->by_src.n_partial, d_in));
+  w.part_dw = (float*)c.take(partial_bytes(g->by_rel.n_partial, weight_row(d_in, d_out, num_bases)));
+  w.seg_dz = (float*)c.take((size_t)n_table * d_out * sizeof(float));
+  w.loop = carve_loop(c, n_table, g->n_nodes, d_in, d_out);
+  w.total = c.total();
   return w;
 }
 
@@ -1233,23 +1280,27 @@ void temp_set_debug_buffer(void* device_ptr, size_t words) { g_debug_buf.store((
 
 size_t temp_rgcn_table_fwd_workspace(const TempGraph* g, int n_table, int d_out) {
   if (!g || n_table < 0) return 0;
-  return partial_bytes(g->by_dst.n_partial, d_out) + align_up((size_t)n_table * d_out * sizeof(float), 256) + 256;
+  Carver c(nullptr);
+  c.take(partial_bytes(g->by_dst.n_partial, d_out));
+  c.take((size_t)n_table * d_out * sizeof(float));
+  return c.total();
 }
 
 int temp_rgcn_table_fwd(const TempGraph* g, const float* table, const int32_t* ids, int n_table, int d_in, int d_out, int num_bases,
                         int n_rel_rows, const float* weight, const float* loop_w, const float* bias, int act, float* out, void* workspace,
                         size_t workspace_bytes, const TempDropout* drop, void* stream) {
-  if (!g || !table || !weight || !loop_w || !out || n_table <= 0 || d_in <= 0 || d_out <= 0 || num_bases <= 0 || n_rel_rows <= 0) return TEMP_E_BADARG;
-  if (d_in % num_bases || d_out % num_bases || d_in % 4 || d_out % 4) return TEMP_E_UNSUPPORTED;
-  if (g->n_nodes < 0 || !view_ok(g->by_dst) || (g->n_nodes > 0 && (!g->nnorm || !g->in_deg || !ids))) return TEMP_E_BADARG;
-  if (act != TEMP_ACT_NONE && act != TEMP_ACT_RELU) return TEMP_E_BADARG;
+  if (!g || !table || !weight || !loop_w || !out || n_table <= 0) return TEMP_E_BADARG;
+  int rc = layer_shape(d_in, d_out, num_bases, n_rel_rows);
+  if (rc) return rc;
+  if (g->n_nodes < 0 || !view_ok(g->by_dst) || (g->n_nodes > 0 && (!g->nnorm || !g->in_deg || !ids)) || !act_ok(act)) return TEMP_E_BADARG;
   if (!workspace || workspace_bytes < temp_rgcn_table_fwd_workspace(g, n_table, d_out)) return TEMP_E_WORKSPACE;
   if (g->n_nodes == 0) return TEMP_OK;
   hipStream_t st = (hipStream_t)stream;
-  float* partial = (float*)workspace;
-  float* t_loop = (float*)((char*)workspace + partial_bytes(g->by_dst.n_partial, d_out));
-  int rc = gemm_add_bias_act(K_GEMM_ISO, n_table, d_out, d_in, table, d_in, nullptr, loop_w, d_out, 0, nullptr, 0, nullptr, nullptr, TEMP_ACT_NONE,
-                             t_loop, d_out, st);
+  Carver c(workspace);
+  float* partial = (float*)c.take(partial_bytes(g->by_dst.n_partial, d_out));
+  float* t_loop = (float*)c.take((size_t)n_table * d_out * sizeof(float));
+  rc = gemm_add_bias_act(K_GEMM_ISO, n_table, d_out, d_in, table, d_in, nullptr, loop_w, d_out, 0, nullptr, 0, nullptr, nullptr, TEMP_ACT_NONE,
+                         t_loop, d_out, st);
   if (rc) return rc;
   rc = run_agg(MODE_FWD, g->by_dst, members_of(g), table, d_in, ids, weight, n_rel_rows, g->nnorm, d_in, d_out, num_bases, out, partial, st);
   if (rc) return rc;
@@ -1269,31 +1320,19 @@ int temp_rgcn_table_bwd(const TempGraph* g, const float* table, const int32_t* i
                         const float* out, const float* d_out_grad, int d_in, int d_out, int num_bases, int n_rel_rows, const float* weight,
                         const float* loop_w, int has_bias, int act, float* d_table, float* d_weight, float* d_loop_w, float* d_bias,
                         void* workspace, size_t workspace_bytes, const TempDropout* drop, void* stream) {
-  if (!g || !table || !d_out_grad || !weight || !loop_w || !d_table || !d_weight || !d_loop_w || !inv_ptr) return TEMP_E_BADARG;
-  if (n_table <= 0 || d_in <= 0 || d_out <= 0 || num_bases <= 0 || n_rel_rows <= 0) return TEMP_E_BADARG;
-  if (d_in % num_bases || d_out % num_bases || d_in % 4 || d_out % 4 || d_in > 256 || d_out > 256) return TEMP_E_UNSUPPORTED;
-  if (act == TEMP_ACT_RELU && !out) return TEMP_E_BADARG;
-  if (has_bias && !d_bias) return TEMP_E_BADARG;
-  if (!view_ok(g->by_src) || !view_ok(g->by_rel) || (g->n_nodes > 0 && (!g->nnorm || !g->out_deg || !ids || !inv_order))) return TEMP_E_BADARG;
-  if (g->by_rel.n_seg != n_rel_rows) return TEMP_E_BADARG;
+  if (!g || !table || !d_out_grad || !weight || !loop_w || !d_table || !d_weight || !d_loop_w || !inv_ptr || n_table <= 0) return TEMP_E_BADARG;
+  int rc = layer_shape(d_in, d_out, num_bases, n_rel_rows);
+  if (rc) return rc;
+  if (d_in > 256 || d_out > 256) return TEMP_E_UNSUPPORTED;
+  if (grad_args(act, out, has_bias, d_bias)) return TEMP_E_BADARG;
+  if (!view_ok(g->by_src) || !rel_view_ok(g, n_rel_rows) || (g->n_nodes > 0 && (!g->nnorm || !g->out_deg || !ids || !inv_order))) return TEMP_E_BADARG;
   if (!workspace || workspace_bytes < temp_rgcn_table_bwd_workspace(g, n_table, d_in, d_out, num_bases)) return TEMP_E_WORKSPACE;
   hipStream_t st = (hipStream_t)stream;
-  const size_t wrow = (size_t)num_bases * (d_in / num_bases) * (d_out / num_bases);
-  if (g->n_nodes == 0) {
-    if (hipMemsetAsync(d_table, 0, (size_t)n_table * d_in * sizeof(float), st) != hipSuccess) return TEMP_E_LAUNCH;
-    if (hipMemsetAsync(d_weight, 0, (size_t)n_rel_rows * wrow * sizeof(float), st) != hipSuccess) return TEMP_E_LAUNCH;
-    if (hipMemsetAsync(d_loop_w, 0, (size_t)d_in * d_out * sizeof(float), st) != hipSuccess) return TEMP_E_LAUNCH;
-    if (has_bias && hipMemsetAsync(d_bias, 0, (size_t)d_out * sizeof(float), st) != hipSuccess) return TEMP_E_LAUNCH;
-    return TEMP_OK;
-  }
+  if (g->n_nodes == 0) return zero_grads(d_in, d_out, n_rel_rows, weight_row(d_in, d_out, num_bases), has_bias, d_weight, d_loop_w, d_bias, st, d_table, n_table);
   TableBwdWs w = carve_table_bwd(g, n_table, d_in, d_out, num_bases, (char*)workspace);
-  const float* dz = d_out_grad;
-  int rc;
-  if (act == TEMP_ACT_RELU) {
-    rc = relu_bwd((size_t)g->n_nodes * d_out, out, d_out_grad, w.dz, st);
-    if (rc) return rc;
-    dz = w.dz;
-  }
+  const float *dz, *dzm;
+  rc = grad_dz(act, (size_t)g->n_nodes * d_out, out, d_out_grad, w.dz, st, &dz);
+  if (rc) return rc;
   SideScope side(st);                            // relation-weight gradient beside the rest of the backward (see SideStream)
   SideStream* ss = side.ss;
   if (ss) {
@@ -1304,13 +1343,8 @@ int temp_rgcn_table_bwd(const TempGraph* g, const float* table, const int32_t* i
   //   d_table = segsum(out_deg > 0 ? d_h : 0) + segsum(dz) . loop_w^T        d_loop_w = table^T . segsum(dz)
   rc = run_agg(MODE_DX, g->by_src, members_of(g), dz, d_out, nullptr, weight, n_rel_rows, g->nnorm, d_in, d_out, num_bases, w.d_h, w.part_dx, st);
   if (rc) return rc;
-  const DropSpec ds = drop_spec(drop);
-  const float* dzm = dz;                       // gradient of the (dropped-out) self-loop message
-  if (ds.p > 0.f) {
-    rc = mask_rows(g->n_nodes, d_out, dz, w.dzm, ds, st);
-    if (rc) return rc;
-    dzm = w.dzm;
-  }
+  rc = grad_dzm(drop_spec(drop), g->n_nodes, d_out, dz, w.dzm, st, &dzm);
+  if (rc) return rc;
   rc = segment_sum_rows2(n_table, inv_ptr, inv_order, d_in, w.d_h, g->out_deg, d_table, d_out, dzm, w.seg_dz, st, g->n_nodes);
   if (rc) return rc;
   rc = gemm_add_bias_act(K_GEMM_LOOP_DX, n_table, d_in, d_out, w.seg_dz, d_out, nullptr, loop_w, d_out, 1, d_table, d_in, nullptr, nullptr,
@@ -1320,13 +1354,8 @@ int temp_rgcn_table_bwd(const TempGraph* g, const float* table, const int32_t* i
     rc = run_dw(g->by_rel, members_of(g), table, ids, dz, g->nnorm, d_in, d_out, num_bases, n_rel_rows, d_weight, w.part_dw, st);
     if (rc) return rc;
   }
-  rc = gemm_tn(n_table, d_in, d_out, table, d_in, w.seg_dz, d_out, d_loop_w, d_out, w.tn, w.tn_bytes, st);
-  if (rc) return rc;
-  if (has_bias) {
-    rc = colsum(g->n_nodes, d_out, dz, d_out, d_bias, w.cs, w.cs_bytes, st);
-    if (rc) return rc;
-  }
-  return side.join();
+  rc = loop_grads(w.loop, n_table, d_in, d_out, table, w.seg_dz, g->n_nodes, dz, has_bias, d_loop_w, d_bias, st);
+  return rc ? rc : side.join();
 }
 
 long long temp_pair_launches(void) { return g_pair_launches.load(std::memory_order_relaxed); }
@@ -1357,12 +1386,11 @@ size_t temp_rgcn_pair_fwd_workspace(const TempGraph* g, const TempPairView* pv, 
 int temp_rgcn_pair_fwd(const TempGraph* g, const TempPairView* pv, const float* table, const int32_t* ids, int n_table, int d_in, int d_out,
                        int num_bases, int n_rel_rows, const float* weight, const float* loop_w, const float* bias, int act, float* out,
                        void* workspace, size_t workspace_bytes, const TempDropout* drop, void* stream) {
-  if (!g || !pv || !table || !weight || !loop_w || !out || n_table <= 0 || d_in <= 0 || d_out <= 0 || num_bases <= 0 || n_rel_rows <= 0) return TEMP_E_BADARG;
+  if (!g || !pv || !table || !weight || !loop_w || !out) return TEMP_E_BADARG;
   int S = 0;
-  if (!fast_shape(d_in, d_out, num_bases, &S)) return TEMP_E_UNSUPPORTED;
-  if ((long long)n_rel_rows * n_table >= (1LL << 31) / d_out) return TEMP_E_UNSUPPORTED;
-  if (g->n_nodes < 0 || !view_ok(g->by_dst) || !pair_view_ok(g, pv, n_table, n_rel_rows) || (g->n_nodes > 0 && (!g->nnorm || !g->in_deg || !ids))) return TEMP_E_BADARG;
-  if (act != TEMP_ACT_NONE && act != TEMP_ACT_RELU) return TEMP_E_BADARG;
+  int rc = pair_shape(n_table, d_in, d_out, num_bases, n_rel_rows, &S);
+  if (rc) return rc;
+  if (g->n_nodes < 0 || !view_ok(g->by_dst) || !pair_view_ok(g, pv, n_table, n_rel_rows) || (g->n_nodes > 0 && (!g->nnorm || !g->in_deg || !ids)) || !act_ok(act)) return TEMP_E_BADARG;
   if (!workspace || workspace_bytes < temp_rgcn_pair_fwd_workspace(g, pv, d_out)) return TEMP_E_WORKSPACE;
   if (g->n_nodes == 0) return TEMP_OK;
   hipStream_t st = (hipStream_t)stream;
@@ -1370,11 +1398,9 @@ int temp_rgcn_pair_fwd(const TempGraph* g, const TempPairView* pv, const float* 
   const int D = d_in, P = n_rel_rows * n_table;
   int grid = ceil_div((long long)P * (D / 4), 256);
   if (grid > 8192) grid = 8192;
-  if (S == 1) TEMP_LAUNCH(K_PAIR_MSG, k_pair_msg<1>, dim3(grid), dim3(256), 0, st, P, n_table, D, table, weight, w.M);
-  else if (S == 2) TEMP_LAUNCH(K_PAIR_MSG, k_pair_msg<2>, dim3(grid), dim3(256), 0, st, P, n_table, D, table, weight, w.M);
-  else TEMP_LAUNCH(K_PAIR_MSG, k_pair_msg<4>, dim3(grid), dim3(256), 0, st, P, n_table, D, table, weight, w.M);
-  int rc = gemm_add_bias_act(K_GEMM_ISO, n_table, d_out, d_in, table, d_in, nullptr, loop_w, d_out, 0, nullptr, 0, nullptr, nullptr, TEMP_ACT_NONE,
-                             w.t_loop, d_out, st);
+  TEMP_LAUNCH_S(K_PAIR_MSG, k_pair_msg, S, dim3(grid), dim3(256), 0, st, P, n_table, D, table, weight, w.M);
+  rc = gemm_add_bias_act(K_GEMM_ISO, n_table, d_out, d_in, table, d_in, nullptr, loop_w, d_out, 0, nullptr, 0, nullptr, nullptr, TEMP_ACT_NONE,
+                         w.t_loop, d_out, st);
   if (rc) return rc;
   const DropSpec ds = drop_spec(drop);
   const TempEdgeView& v = g->by_dst;
@@ -1406,33 +1432,20 @@ int temp_rgcn_pair_bwd(const TempGraph* g, const TempPairView* pv, const float* 
                        int n_rel_rows, const float* weight, const float* loop_w, int has_bias, int act, float* d_table, float* d_weight,
                        float* d_loop_w, float* d_bias, void* workspace, size_t workspace_bytes, const TempDropout* drop, void* stream) {
   if (!g || !pv || !table || !d_out_grad || !weight || !loop_w || !d_table || !d_weight || !d_loop_w || !inv_ptr) return TEMP_E_BADARG;
-  if (n_table <= 0 || d_in <= 0 || d_out <= 0 || num_bases <= 0 || n_rel_rows <= 0) return TEMP_E_BADARG;
   int S = 0;
-  if (!fast_shape(d_in, d_out, num_bases, &S)) return TEMP_E_UNSUPPORTED;
-  if ((long long)n_rel_rows * n_table >= (1LL << 31) / d_out) return TEMP_E_UNSUPPORTED;
-  if (act == TEMP_ACT_RELU && !out) return TEMP_E_BADARG;
-  if (act != TEMP_ACT_NONE && act != TEMP_ACT_RELU) return TEMP_E_BADARG;
-  if (has_bias && !d_bias) return TEMP_E_BADARG;
+  int rc = pair_shape(n_table, d_in, d_out, num_bases, n_rel_rows, &S);
+  if (rc) return rc;
+  if (grad_args(act, out, has_bias, d_bias) || !act_ok(act)) return TEMP_E_BADARG;
   if (g->n_nodes < 0 || !pair_view_ok(g, pv, n_table, n_rel_rows) || (g->n_nodes > 0 && (!g->nnorm || !ids || !inv_order))) return TEMP_E_BADARG;
   if (!workspace || workspace_bytes < temp_rgcn_pair_bwd_workspace(g, pv, d_in, d_out, num_bases)) return TEMP_E_WORKSPACE;
   hipStream_t st = (hipStream_t)stream;
-  const size_t wrow = (size_t)d_in * S;
-  if (g->n_nodes == 0) {
-    if (hipMemsetAsync(d_table, 0, (size_t)n_table * d_in * sizeof(float), st) != hipSuccess) return TEMP_E_LAUNCH;
-    if (hipMemsetAsync(d_weight, 0, (size_t)n_rel_rows * wrow * sizeof(float), st) != hipSuccess) return TEMP_E_LAUNCH;
-    if (hipMemsetAsync(d_loop_w, 0, (size_t)d_in * d_out * sizeof(float), st) != hipSuccess) return TEMP_E_LAUNCH;
-    if (has_bias && hipMemsetAsync(d_bias, 0, (size_t)d_out * sizeof(float), st) != hipSuccess) return TEMP_E_LAUNCH;
-    return TEMP_OK;
-  }
+  const size_t wrow = weight_row(d_in, d_out, num_bases);        // (= d_in * S)
+  if (g->n_nodes == 0) return zero_grads(d_in, d_out, n_rel_rows, wrow, has_bias, d_weight, d_loop_w, d_bias, st, d_table, n_table);
   const PairBwdWs w = carve_pair_bwd(g, pv, d_in, d_out, S, (char*)workspace);
   const int D = d_in;
-  const float* dz = d_out_grad;
-  int rc;
-  if (act == TEMP_ACT_RELU) {
-    rc = relu_bwd((size_t)g->n_nodes * d_out, out, d_out_grad, w.dz, st);
-    if (rc) return rc;
-    dz = w.dz;
-  }
+  const float *dz, *dzm;
+  rc = grad_dz(act, (size_t)g->n_nodes * d_out, out, d_out_grad, w.dz, st, &dz);
+  if (rc) return rc;
   // The self-loop part as in temp_rgcn_table_bwd:  loop_dt = segsum(dzm) . loop_w^T,  d_loop_w = table^T . segsum(dzm),  d_bias.
   // It reads dz, table and loop_w only -- nothing the gather below writes -- and its kernels are small (a tenth of the machine or
   // less), so it runs on the side stream beside the gather; k_pair_tail adds loop_dt.  No side stream (TEMP_OPT_OVERLAP = 0, every
@@ -1440,18 +1453,11 @@ int temp_rgcn_pair_bwd(const TempGraph* g, const TempPairView* pv, const float* 
   SideScope side(st);
   const bool beside = !(option(TEMP_OPT_DEBUG) & 0x800000) && side_fork(side);      // (TEMP_DEBUG bit 23: A/B, in-stream)
   hipStream_t sl = beside ? side.ss->s : st;
-  const DropSpec ds = drop_spec(drop);
-  const float* dzm = dz;
-  rc = TEMP_OK;
-  if (ds.p > 0.f) {
-    rc = mask_rows(g->n_nodes, d_out, dz, w.dzm, ds, sl);
-    dzm = w.dzm;
-  }
+  rc = grad_dzm(drop_spec(drop), g->n_nodes, d_out, dz, w.dzm, sl, &dzm);
   if (!rc) rc = segment_sum_rows(n_table, d_out, inv_ptr, inv_order, dzm, nullptr, w.seg_dz, sl, g->n_nodes, w.ss, w.ss_bytes);
   if (!rc) rc = gemm_add_bias_act(K_GEMM_LOOP_DX, n_table, d_in, d_out, w.seg_dz, d_out, nullptr, loop_w, d_out, 1, nullptr, 0, nullptr, nullptr,
                                   TEMP_ACT_NONE, w.loop_dt, d_in, sl);
-  if (!rc) rc = gemm_tn(n_table, d_in, d_out, table, d_in, w.seg_dz, d_out, d_loop_w, d_out, w.tn, w.tn_bytes, sl);
-  if (!rc && has_bias) rc = colsum(g->n_nodes, d_out, dz, d_out, d_bias, w.cs, w.cs_bytes, sl);
+  if (!rc) rc = loop_grads(w.loop, n_table, d_in, d_out, table, w.seg_dz, g->n_nodes, dz, has_bias, d_loop_w, d_bias, sl);
   if (beside && !side_done(side) && !rc) rc = TEMP_E_LAUNCH;
   if (rc) return rc;                             // (SideScope joins a forked branch)
   // G: one ordered gather-sum by pair (every pair owns a chunk, so every row of G is written), then the multi-chunk pairs
@@ -1465,9 +1471,8 @@ int temp_rgcn_pair_bwd(const TempGraph* g, const TempPairView* pv, const float* 
   // the two P-row products in one pass over G: d_table (aggregation part + loop_dt) and the relation weights
   const PairTailGrid tg = pair_tail_grid(n_table);
   float* dwp = tg.blocks > 1 ? w.dw_part : d_weight;
-  if (S == 1) TEMP_LAUNCH(K_PAIR_TAIL, k_pair_tail<1>, dim3(tg.blocks), dim3(PT_WAVES * 64), 0, st, n_table, n_rel_rows, D, tg.tiles_per_block, w.G, weight, table, w.loop_dt, d_table, dwp);
-  else if (S == 2) TEMP_LAUNCH(K_PAIR_TAIL, k_pair_tail<2>, dim3(tg.blocks), dim3(PT_WAVES * 64), 0, st, n_table, n_rel_rows, D, tg.tiles_per_block, w.G, weight, table, w.loop_dt, d_table, dwp);
-  else TEMP_LAUNCH(K_PAIR_TAIL, k_pair_tail<4>, dim3(tg.blocks), dim3(PT_WAVES * 64), 0, st, n_table, n_rel_rows, D, tg.tiles_per_block, w.G, weight, table, w.loop_dt, d_table, dwp);
+  TEMP_LAUNCH_S(K_PAIR_TAIL, k_pair_tail, S, dim3(tg.blocks), dim3(PT_WAVES * 64), 0, st, n_table, n_rel_rows, D, tg.tiles_per_block, w.G, weight, table,
+                w.loop_dt, d_table, dwp);
   if (tg.blocks > 1) reduce_slices(tg.blocks, (size_t)n_rel_rows * wrow, (int)wrow, w.dw_part, d_weight, (int)wrow, st);
   g_pair_launches.fetch_add(1, std::memory_order_relaxed);
   return launch_status();
@@ -1481,15 +1486,15 @@ size_t temp_rgcn_fwd_workspace(const TempGraph* g, int d_out) {
 int temp_rgcn_fwd(const TempGraph* g, const float* h, const int32_t* h_ids, int d_in, int d_out, int num_bases, int n_rel_rows,
                   const float* weight, const float* loop_w, const float* bias, int act, float* out, void* workspace,
                   size_t workspace_bytes, const TempDropout* drop, void* stream) {
-  if (!g || !h || !weight || !loop_w || !out || d_in <= 0 || d_out <= 0 || num_bases <= 0 || n_rel_rows <= 0) return TEMP_E_BADARG;
-  if (d_in % num_bases || d_out % num_bases || d_in % 4 || d_out % 4) return TEMP_E_UNSUPPORTED;
-  if (g->n_nodes < 0 || !view_ok(g->by_dst) || (g->n_nodes > 0 && (!g->nnorm || !g->in_deg))) return TEMP_E_BADARG;
-  if (act != TEMP_ACT_NONE && act != TEMP_ACT_RELU) return TEMP_E_BADARG;
+  if (!g || !h || !weight || !loop_w || !out) return TEMP_E_BADARG;
+  int rc = layer_shape(d_in, d_out, num_bases, n_rel_rows);
+  if (rc) return rc;
+  if (g->n_nodes < 0 || !view_ok(g->by_dst) || (g->n_nodes > 0 && (!g->nnorm || !g->in_deg)) || !act_ok(act)) return TEMP_E_BADARG;
   if (workspace_bytes < temp_rgcn_fwd_workspace(g, d_out) || (!workspace && g->by_dst.n_partial > 0)) return TEMP_E_WORKSPACE;
   if (g->n_nodes == 0) return TEMP_OK;
   hipStream_t st = (hipStream_t)stream;
   float* partial = (float*)workspace;
-  int rc = run_agg(MODE_FWD, g->by_dst, members_of(g), h, d_in, h_ids, weight, n_rel_rows, g->nnorm, d_in, d_out, num_bases, out, partial, st);
+  rc = run_agg(MODE_FWD, g->by_dst, members_of(g), h, d_in, h_ids, weight, n_rel_rows, g->nnorm, d_in, d_out, num_bases, out, partial, st);
   if (rc) return rc;
   // out = act( (in_deg>0 ? out : 0) + bias + h . loop_w )       (MFMA fp32 GEMM, fused epilogue)
   const DropSpec ds = drop_spec(drop);
@@ -1501,26 +1506,18 @@ struct BwdWs {
   float* dzm;       // [n, d_out]  dz masked like the forward self-loop message (only with dropout)
   float* part_dx;   // by_src partial slots [n_partial, d_in]
   float* part_dw;   // by_rel partial slots [n_partial, wrow]
-  void* tn;         // gemm_tn workspace
-  size_t tn_bytes;
-  void* cs;         // colsum workspace
-  size_t cs_bytes;
+  LoopWs loop;      // gemm_tn and colsum workspaces
   size_t total;
 };
 static BwdWs carve_bwd(const TempGraph* g, int d_in, int d_out, int num_bases, char* base) {
   BwdWs w;
-  size_t off = 0;
-  auto take = [&](size_t bytes) { char* p = base ? base + off : nullptr; off += align_up(bytes, 256); return p; };
-  const size_t wrow = (size_t)num_bases * (d_in / num_bases) * (d_out / num_bases);
-  w.dz = (float*)take((size_t)g->n_nodes * d_out * sizeof(float));
-  w.dzm = (float*)take((size_t)g->n_nodes * d_out * sizeof(float));
-  w.part_dx = (float*)take(partial_bytes(g->by_src.n_partial, d_in));
-  w.part_dw = (float*)take(partial_bytes(g->by_rel.n_partial, wrow));
-  w.tn_bytes = gemm_tn_workspace(g->n_nodes, d_in, d_out);
-  w.tn = take(w.tn_bytes);
-  w.cs_bytes = colsum_workspace(g->n_nodes, d_out);
-  w.cs = take(w.cs_bytes);
-  w.total = off + 256;
+  Carver c(base);
+  w.dz = (float*)c.take((size_t)g->n_nodes * d_out * sizeof(float));
+  w.dzm = (float*)c.take((size_t)g->n_nodes * d_out * sizeof(float));
+  w.part_dx = (float*)c.take(partial_bytes(g->by_src.n_partial, d_in));
+  w.part_dw = (float*)c.take(partial_bytes(g->by_rel.n_partial, weight_row(d_in, d_out, num_bases)));
+  w.loop = carve_loop(c, g->n_nodes, g->n_nodes, d_in, d_out);
+  w.total = c.total();
   return w;
 }
 
@@ -1534,29 +1531,17 @@ int temp_rgcn_bwd(const TempGraph* g, const float* h, const float* out, const fl
                   int n_rel_rows, const float* weight, const float* loop_w, int has_bias, int act, float* d_h, float* d_weight,
                   float* d_loop_w, float* d_bias, void* workspace, size_t workspace_bytes, const TempDropout* drop, void* stream) {
   if (!g || !h || !d_out_grad || !weight || !loop_w || !d_h || !d_weight || !d_loop_w) return TEMP_E_BADARG;
-  if (d_in <= 0 || d_out <= 0 || num_bases <= 0 || n_rel_rows <= 0) return TEMP_E_BADARG;
-  if (d_in % num_bases || d_out % num_bases || d_in % 4 || d_out % 4) return TEMP_E_UNSUPPORTED;
-  if (act == TEMP_ACT_RELU && !out) return TEMP_E_BADARG;
-  if (has_bias && !d_bias) return TEMP_E_BADARG;
-  if (!view_ok(g->by_src) || !view_ok(g->by_rel) || (g->n_nodes > 0 && (!g->nnorm || !g->out_deg))) return TEMP_E_BADARG;
-  if (g->by_rel.n_seg != n_rel_rows) return TEMP_E_BADARG;
+  int rc = layer_shape(d_in, d_out, num_bases, n_rel_rows);
+  if (rc) return rc;
+  if (grad_args(act, out, has_bias, d_bias)) return TEMP_E_BADARG;
+  if (!view_ok(g->by_src) || !rel_view_ok(g, n_rel_rows) || (g->n_nodes > 0 && (!g->nnorm || !g->out_deg))) return TEMP_E_BADARG;
   if (!workspace || workspace_bytes < temp_rgcn_bwd_workspace(g, d_in, d_out, num_bases, n_rel_rows)) return TEMP_E_WORKSPACE;
   hipStream_t st = (hipStream_t)stream;
-  const size_t wrow = (size_t)num_bases * (d_in / num_bases) * (d_out / num_bases);
-  if (g->n_nodes == 0) {
-    if (hipMemsetAsync(d_weight, 0, (size_t)n_rel_rows * wrow * sizeof(float), st) != hipSuccess) return TEMP_E_LAUNCH;
-    if (hipMemsetAsync(d_loop_w, 0, (size_t)d_in * d_out * sizeof(float), st) != hipSuccess) return TEMP_E_LAUNCH;
-    if (has_bias && hipMemsetAsync(d_bias, 0, (size_t)d_out * sizeof(float), st) != hipSuccess) return TEMP_E_LAUNCH;
-    return TEMP_OK;
-  }
+  if (g->n_nodes == 0) return zero_grads(d_in, d_out, n_rel_rows, weight_row(d_in, d_out, num_bases), has_bias, d_weight, d_loop_w, d_bias, st);
   BwdWs w = carve_bwd(g, d_in, d_out, num_bases, (char*)workspace);
-  const float* dz = d_out_grad;
-  int rc;
-  if (act == TEMP_ACT_RELU) {
-    rc = relu_bwd((size_t)g->n_nodes * d_out, out, d_out_grad, w.dz, st);
-    if (rc) return rc;
-    dz = w.dz;
-  }
+  const float *dz, *dzm;
+  rc = grad_dz(act, (size_t)g->n_nodes * d_out, out, d_out_grad, w.dz, st, &dz);
+  if (rc) return rc;
   SideScope side(st);                            // relation-weight gradient beside the rest of the backward (see SideStream)
   SideStream* ss = side.ss;
   const DropSpec ds = drop_spec(drop);
@@ -1568,21 +1553,15 @@ int temp_rgcn_bwd(const TempGraph* g, const float* h, const float* out, const fl
     rc = dw_forked(side, g->by_rel, members_of(g), h, nullptr, dz, g->nnorm, d_in, d_out, num_bases, n_rel_rows, d_weight, w.part_dw,
                    [&](hipStream_t s2) {
                      if (!tail_beside) return (int)TEMP_OK;
-                     int r2 = gemm_tn(g->n_nodes, d_in, d_out, h, d_in, dz, d_out, d_loop_w, d_out, w.tn, w.tn_bytes, s2);
-                     if (!r2 && has_bias) r2 = colsum(g->n_nodes, d_out, dz, d_out, d_bias, w.cs, w.cs_bytes, s2);
-                     return r2;
+                     return loop_grads(w.loop, g->n_nodes, d_in, d_out, h, dz, g->n_nodes, dz, has_bias, d_loop_w, d_bias, s2);   // (dzm == dz)
                    });
     if (rc) return rc;
   }
   // d_h (aggregation part) over the by-src view, then d_h = (out_deg>0 ? d_h : 0) + dz . loop_w^T
   rc = run_agg(MODE_DX, g->by_src, members_of(g), dz, d_out, nullptr, weight, n_rel_rows, g->nnorm, d_in, d_out, num_bases, d_h, w.part_dx, st);
   if (rc) return rc;
-  const float* dzm = dz;                       // gradient of the (dropped-out) self-loop message
-  if (ds.p > 0.f) {
-    rc = mask_rows(g->n_nodes, d_out, dz, w.dzm, ds, st);
-    if (rc) return rc;
-    dzm = w.dzm;
-  }
+  rc = grad_dzm(ds, g->n_nodes, d_out, dz, w.dzm, st, &dzm);
+  if (rc) return rc;
   rc = gemm_add_bias_act(K_GEMM_LOOP_DX, g->n_nodes, d_in, d_out, dzm, d_out, nullptr, loop_w, d_out, 1, d_h, d_in, g->out_deg, nullptr, TEMP_ACT_NONE,
                          d_h, d_in, st);
   if (rc) return rc;
@@ -1590,15 +1569,8 @@ int temp_rgcn_bwd(const TempGraph* g, const float* h, const float* out, const fl
     rc = run_dw(g->by_rel, members_of(g), h, nullptr, dz, g->nnorm, d_in, d_out, num_bases, n_rel_rows, d_weight, w.part_dw, st);
     if (rc) return rc;
   }
-  if (!tail_beside) {
-    rc = gemm_tn(g->n_nodes, d_in, d_out, h, d_in, dzm, d_out, d_loop_w, d_out, w.tn, w.tn_bytes, st);
-    if (rc) return rc;
-    if (has_bias) {
-      rc = colsum(g->n_nodes, d_out, dz, d_out, d_bias, w.cs, w.cs_bytes, st);
-      if (rc) return rc;
-    }
-  }
-  return side.join();
+  rc = tail_beside ? (int)TEMP_OK : loop_grads(w.loop, g->n_nodes, d_in, d_out, h, dzm, g->n_nodes, dz, has_bias, d_loop_w, d_bias, st);
+  return rc ? rc : side.join();
 }
 
 // The two halves of temp_rgcn_bwd for a layer that sits INSIDE a recurrence (both layers recurrent, models/RRGCN.py:179-204):
@@ -1609,32 +1581,23 @@ int temp_rgcn_bwd_dh(const TempGraph* g, const float* out, const float* d_out_gr
                      const float* weight, const float* loop_w, int act, float* d_h, float* dz_out, float* dzm_out, void* workspace,
                      size_t workspace_bytes, const TempDropout* drop, void* stream) {
   if (!g || !d_out_grad || !weight || !loop_w || !d_h) return TEMP_E_BADARG;
-  if (d_in <= 0 || d_out <= 0 || num_bases <= 0 || n_rel_rows <= 0) return TEMP_E_BADARG;
-  if (d_in % num_bases || d_out % num_bases || d_in % 4 || d_out % 4) return TEMP_E_UNSUPPORTED;
-  if (act != TEMP_ACT_NONE && act != TEMP_ACT_RELU) return TEMP_E_BADARG;
-  if (act == TEMP_ACT_RELU && (!out || !dz_out)) return TEMP_E_BADARG;       // the masked gradient is an output: the weight pass reads it
+  int rc = layer_shape(d_in, d_out, num_bases, n_rel_rows);
+  if (rc) return rc;
+  if (!act_ok(act) || (act == TEMP_ACT_RELU && (!out || !dz_out))) return TEMP_E_BADARG;       // the masked gradient is an output: the weight pass reads it
   if (!view_ok(g->by_src) || (g->n_nodes > 0 && (!g->nnorm || !g->out_deg))) return TEMP_E_BADARG;
   if (!workspace || workspace_bytes < temp_rgcn_bwd_workspace(g, d_in, d_out, num_bases, n_rel_rows)) return TEMP_E_WORKSPACE;
   if (g->n_nodes == 0) return TEMP_OK;
+  const DropSpec ds = drop_spec(drop);
+  if (ds.p > 0.f && !dzm_out) return TEMP_E_BADARG;              // (the weight pass needs the masked gradient of the self-loop message)
   hipStream_t st = (hipStream_t)stream;
   BwdWs w = carve_bwd(g, d_in, d_out, num_bases, (char*)workspace);
-  const float* dz = d_out_grad;
-  int rc;
-  if (act == TEMP_ACT_RELU) {
-    rc = relu_bwd((size_t)g->n_nodes * d_out, out, d_out_grad, dz_out, st);
-    if (rc) return rc;
-    dz = dz_out;
-  }
+  const float *dz, *dzm;
+  rc = grad_dz(act, (size_t)g->n_nodes * d_out, out, d_out_grad, dz_out, st, &dz);
+  if (rc) return rc;
   rc = run_agg(MODE_DX, g->by_src, members_of(g), dz, d_out, nullptr, weight, n_rel_rows, g->nnorm, d_in, d_out, num_bases, d_h, w.part_dx, st);
   if (rc) return rc;
-  const DropSpec ds = drop_spec(drop);
-  const float* dzm = dz;
-  if (ds.p > 0.f) {
-    if (!dzm_out) return TEMP_E_BADARG;                          // (the weight pass needs the masked gradient of the self-loop message)
-    rc = mask_rows(g->n_nodes, d_out, dz, dzm_out, ds, st);
-    if (rc) return rc;
-    dzm = dzm_out;
-  }
+  rc = grad_dzm(ds, g->n_nodes, d_out, dz, dzm_out, st, &dzm);
+  if (rc) return rc;
   return gemm_add_bias_act(K_GEMM_LOOP_DX, g->n_nodes, d_in, d_out, dzm, d_out, nullptr, loop_w, d_out, 1, d_h, d_in, g->out_deg, nullptr, TEMP_ACT_NONE,
                            d_h, d_in, st);
 }
@@ -1642,27 +1605,63 @@ int temp_rgcn_bwd_dh(const TempGraph* g, const float* out, const float* d_out_gr
 int temp_rgcn_bwd_weights(const TempGraph* g, const float* h, const float* dz, const float* dzm, int d_in, int d_out, int num_bases, int n_rel_rows,
                           int has_bias, float* d_weight, float* d_loop_w, float* d_bias, void* workspace, size_t workspace_bytes, void* stream) {
   if (!g || !h || !dz || !d_weight || !d_loop_w) return TEMP_E_BADARG;
-  if (d_in <= 0 || d_out <= 0 || num_bases <= 0 || n_rel_rows <= 0) return TEMP_E_BADARG;
-  if (d_in % num_bases || d_out % num_bases || d_in % 4 || d_out % 4) return TEMP_E_UNSUPPORTED;
+  int rc = layer_shape(d_in, d_out, num_bases, n_rel_rows);
+  if (rc) return rc;
   if (has_bias && !d_bias) return TEMP_E_BADARG;
-  if (!view_ok(g->by_rel) || (g->n_nodes > 0 && !g->nnorm)) return TEMP_E_BADARG;
-  if (g->by_rel.n_seg != n_rel_rows) return TEMP_E_BADARG;
+  if (!rel_view_ok(g, n_rel_rows) || (g->n_nodes > 0 && !g->nnorm)) return TEMP_E_BADARG;
   if (!workspace || workspace_bytes < temp_rgcn_bwd_workspace(g, d_in, d_out, num_bases, n_rel_rows)) return TEMP_E_WORKSPACE;
   hipStream_t st = (hipStream_t)stream;
-  const size_t wrow = (size_t)num_bases * (d_in / num_bases) * (d_out / num_bases);
-  if (g->n_nodes == 0) {
-    if (hipMemsetAsync(d_weight, 0, (size_t)n_rel_rows * wrow * sizeof(float), st) != hipSuccess) return TEMP_E_LAUNCH;
-    if (hipMemsetAsync(d_loop_w, 0, (size_t)d_in * d_out * sizeof(float), st) != hipSuccess) return TEMP_E_LAUNCH;
-    if (has_bias && hipMemsetAsync(d_bias, 0, (size_t)d_out * sizeof(float), st) != hipSuccess) return TEMP_E_LAUNCH;
-    return TEMP_OK;
-  }
+  if (g->n_nodes == 0) return zero_grads(d_in, d_out, n_rel_rows, weight_row(d_in, d_out, num_bases), has_bias, d_weight, d_loop_w, d_bias, st);
   BwdWs w = carve_bwd(g, d_in, d_out, num_bases, (char*)workspace);
-  int rc = run_dw(g->by_rel, members_of(g), h, nullptr, dz, g->nnorm, d_in, d_out, num_bases, n_rel_rows, d_weight, w.part_dw, st);
+  rc = run_dw(g->by_rel, members_of(g), h, nullptr, dz, g->nnorm, d_in, d_out, num_bases, n_rel_rows, d_weight, w.part_dw, st);
   if (rc) return rc;
-  rc = gemm_tn(g->n_nodes, d_in, d_out, h, d_in, dzm ? dzm : dz, d_out, d_loop_w, d_out, w.tn, w.tn_bytes, st);
-  if (rc) return rc;
-  if (has_bias) rc = colsum(g->n_nodes, d_out, dz, d_out, d_bias, w.cs, w.cs_bytes, st);
+  rc = loop_grads(w.loop, g->n_nodes, d_in, d_out, h, dzm ? dzm : dz, g->n_nodes, dz, has_bias, d_loop_w, d_bias, st);
   return rc ? rc : launch_status();
+}
+
+// The layer on nodes without edges (an isolated snapshot): the self-loop message alone.
+int temp_rgcn_isolated_fwd(int n, int d, const float* e, const float* loop_w, const float* bias, int act, float* out, const TempDropout* drop,
+                           void* stream) {
+  if (n < 0 || d <= 0 || !loop_w || (n > 0 && (!e || !out))) return TEMP_E_BADARG;
+  if (d % 4) return TEMP_E_UNSUPPORTED;
+  const DropSpec ds = drop_spec(drop);
+  return gemm_add_bias_act(K_GEMM_ISO, n, d, d, e, d, nullptr, loop_w, d, 0, e, d, nullptr, bias, act, out, d, (hipStream_t)stream, &ds);
+}
+
+struct IsoBwdWs { float *dz, *dzm; LoopWs loop; size_t total; };
+static IsoBwdWs carve_iso_bwd(int n, int d, char* base) {
+  IsoBwdWs w;
+  Carver c(base);
+  w.dz = (float*)c.take((size_t)n * d * sizeof(float));
+  w.dzm = (float*)c.take((size_t)n * d * sizeof(float));
+  w.loop = carve_loop(c, n, n, d, d);
+  w.total = c.total();
+  return w;
+}
+
+size_t temp_rgcn_isolated_bwd_workspace(int n, int d) {
+  if (n < 0 || d <= 0) return 0;
+  return carve_iso_bwd(n, d, nullptr).total;
+}
+
+int temp_rgcn_isolated_bwd(int n, int d, const float* e, const float* out, const float* d_out_grad, const float* loop_w, int has_bias,
+                           int act, float* d_e, float* d_loop_w, float* d_bias, void* workspace, size_t workspace_bytes, const TempDropout* drop,
+                           void* stream) {
+  if (n < 0 || d <= 0 || !loop_w || !d_loop_w || (n > 0 && (!e || !d_out_grad || !d_e))) return TEMP_E_BADARG;
+  if (d % 4) return TEMP_E_UNSUPPORTED;
+  if (grad_args(act, out, has_bias, d_bias)) return TEMP_E_BADARG;
+  if (!workspace || workspace_bytes < temp_rgcn_isolated_bwd_workspace(n, d)) return TEMP_E_WORKSPACE;
+  hipStream_t st = (hipStream_t)stream;
+  const IsoBwdWs w = carve_iso_bwd(n, d, (char*)workspace);
+  const float *dz, *dzm;
+  int rc = grad_dz(act, (size_t)n * d, out, d_out_grad, w.dz, st, &dz);
+  if (rc) return rc;
+  // d_e = dz + dzm . loop_w^T,  d_loop_w = e^T . dzm   (dzm = dz masked like the forward loop message; = dz without dropout)
+  rc = grad_dzm(drop_spec(drop), n, d, dz, w.dzm, st, &dzm);
+  if (rc) return rc;
+  rc = gemm_add_bias_act(K_GEMM_ISO, n, d, d, dzm, d, nullptr, loop_w, d, 1, dz, d, nullptr, nullptr, TEMP_ACT_NONE, d_e, d, st);
+  if (rc) return rc;
+  return loop_grads(w.loop, n, d, d, e, dzm, n, dz, has_bias, d_loop_w, d_bias, st);
 }
 
 }  // extern "C"

@@ -1,0 +1,451 @@
+// Row gather, atomic scatter-add and the deterministic segment sums (the adjoint of a row gather whose index list is known in
+// advance), with their entry points.
+#include "common.hpp"
+#include "hx_pack.hpp"
+
+namespace temp {
+
+__global__ void __launch_bounds__(256) k_gather_rows(int n, int d4, const float4* __restrict__ table, const int32_t* __restrict__ idx,
+                                                     float4* __restrict__ out) {
+  const size_t total = (size_t)n * d4;
+  for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (size_t)gridDim.x * blockDim.x) {
+    const int r = (int)(i / d4), c = (int)(i - (size_t)r * d4);
+    const int s = idx[r];
+    out[i] = (s >= 0) ? table[(size_t)s * d4 + c] : zero4();
+  }
+}
+
+__global__ void __launch_bounds__(256) k_scatter_add_rows(int n, int d, const float* __restrict__ src, const int32_t* __restrict__ idx,
+                                                          float* __restrict__ table) {
+  const size_t total = (size_t)n * d;
+  for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (size_t)gridDim.x * blockDim.x) {
+    const int r = (int)(i / d), c = (int)(i - (size_t)r * d);
+    const int s = idx[r];
+    if (s >= 0) atomicAdd(table + (size_t)s * d + c, src[i]);
+  }
+}
+
+// out[s] = sum over j in [seg_ptr[s], seg_ptr[s+1]) of src[order[j]]  -- the adjoint of a row gather whose index
+// list is known in advance (its inverse, grouped by table row, is built once on the host).  Deterministic
+// replacement of the atomic scatter for hot tables: GDELT has 500 entities and ~100 k gathered rows per step,
+// i.e. ~200 atomic adds per table element.  One wave per segment, one float4 per lane, 4 row loads in flight;
+// the d/4-lane groups of a wave (LPR lanes each) take every (64/LPR)-th row and are summed by shuffles.
+template <int LPR>
+__global__ void __launch_bounds__(256) k_segment_sum_rows(int n_seg, int d4, const int32_t* __restrict__ seg_ptr,
+                                                          const int32_t* __restrict__ order, const float4* __restrict__ src,
+                                                          const int32_t* __restrict__ row_mask, const float4* __restrict__ relu_of,
+                                                          float4* __restrict__ out) {
+  constexpr int G = 64 / LPR;
+  const int lane = threadIdx.x & 63, grp = lane / LPR, lr = lane - grp * LPR;
+  const int wave = (blockIdx.x * blockDim.x + threadIdx.x) >> 6, nwaves = (gridDim.x * blockDim.x) >> 6;
+  const bool col_ok = lr < d4;
+  for (int s = wave; s < n_seg; s += nwaves) {
+    const int beg = seg_ptr[s], end = seg_ptr[s + 1];
+    float4 acc = zero4();
+    int j = beg + grp;
+    for (; j + 3 * G < end; j += 4 * G) {
+      const int r0 = order[j], r1 = order[j + G], r2 = order[j + 2 * G], r3 = order[j + 3 * G];
+      const bool m0 = !row_mask || row_mask[r0] > 0, m1 = !row_mask || row_mask[r1] > 0, m2 = !row_mask || row_mask[r2] > 0,
+                 m3 = !row_mask || row_mask[r3] > 0;          // masked rows were never written by their producer
+      float4 v0 = zero4(), v1 = zero4(), v2 = zero4(), v3 = zero4();
+      if (col_ok) {
+        if (m0) v0 = src[(size_t)r0 * d4 + lr];
+        if (m1) v1 = src[(size_t)r1 * d4 + lr];
+        if (m2) v2 = src[(size_t)r2 * d4 + lr];
+        if (m3) v3 = src[(size_t)r3 * d4 + lr];
+      }
+      acc = add4(add4(acc, v0), add4(v1, add4(v2, v3)));
+    }
+    for (; j < end; j += G) {
+      const int r = order[j];
+      if (col_ok && (!row_mask || row_mask[r] > 0)) acc = add4(acc, src[(size_t)r * d4 + lr]);
+    }
+#pragma unroll
+    for (int m = LPR; m < 64; m <<= 1) acc = add4(acc, shfl_xor4(acc, m));
+    if (grp == 0 && col_ok) out[(size_t)s * d4 + lr] = relu_of ? relu_gate4(relu_of[(size_t)s * d4 + lr], acc) : acc;
+  }
+}
+
+// The same for segments of one or two rows (the adjoint of a gather whose rows are mostly distinct).
+template <int LPR>
+__global__ void __launch_bounds__(256) k_segment_sum_rows_short(int n_seg, int d4, const int32_t* __restrict__ seg_ptr,
+                                                          const int32_t* __restrict__ order, const float4* __restrict__ src,
+                                                          const int32_t* __restrict__ row_mask, const float4* __restrict__ relu_of,
+                                                          float4* __restrict__ out) {
+  // A wave takes FOUR consecutive segments at a time and walks them in lockstep: the three dependent round trips of a segment
+  // (seg_ptr -> order -> row) are then shared by four segments instead of paid by each (the gather adjoints have 1-2 rows per
+  // segment: the walk is all latency).
+  constexpr int G = 64 / LPR, U = 4;
+  const int lane = threadIdx.x & 63, grp = lane / LPR, lr = lane - grp * LPR;
+  const int wave = (blockIdx.x * blockDim.x + threadIdx.x) >> 6, nwaves = (gridDim.x * blockDim.x) >> 6;
+  const bool col_ok = lr < d4;
+  for (int s0 = wave * U; s0 < n_seg; s0 += nwaves * U) {
+    int beg[U], len[U], maxlen = 0;
+#pragma unroll
+    for (int u = 0; u < U; ++u) {
+      const bool ok = s0 + u < n_seg;
+      beg[u] = ok ? seg_ptr[s0 + u] : 0;
+      len[u] = ok ? seg_ptr[s0 + u + 1] - beg[u] : 0;
+      maxlen = max(maxlen, len[u]);
+    }
+    float4 acc[U];
+#pragma unroll
+    for (int u = 0; u < U; ++u) acc[u] = zero4();
+    for (int k = grp; k < maxlen; k += G) {
+      int r[U];
+#pragma unroll
+      for (int u = 0; u < U; ++u) r[u] = k < len[u] ? order[beg[u] + k] : -1;
+      float4 v[U];
+#pragma unroll
+      for (int u = 0; u < U; ++u) {
+        v[u] = zero4();
+        if (r[u] >= 0 && col_ok && (!row_mask || row_mask[r[u]] > 0)) v[u] = src[(size_t)r[u] * d4 + lr];   // masked rows were never written
+      }
+#pragma unroll
+      for (int u = 0; u < U; ++u) acc[u] = add4(acc[u], v[u]);
+    }
+#pragma unroll
+    for (int u = 0; u < U; ++u) {
+#pragma unroll
+      for (int m = LPR; m < 64; m <<= 1) acc[u] = add4(acc[u], shfl_xor4(acc[u], m));
+      if (grp == 0 && col_ok && s0 + u < n_seg)
+        out[(size_t)(s0 + u) * d4 + lr] = relu_of ? relu_gate4(relu_of[(size_t)(s0 + u) * d4 + lr], acc[u]) : acc[u];
+    }
+  }
+}
+
+// Long segments (a hot table: hundreds of gathered rows per table row): one BLOCK per segment, its 4 waves take every
+// 4th row with 8 row loads in flight each, partial sums meet in LDS in a fixed order.
+template <int WAVES>
+__global__ void __launch_bounds__(WAVES * 64) k_segment_sum_rows_blk(int n_seg, int d4, const int32_t* __restrict__ seg_ptr,
+                                                                     const int32_t* __restrict__ order, const float4* __restrict__ src,
+                                                                     const int32_t* __restrict__ row_mask, const float4* __restrict__ relu_of,
+                                                                     float4* __restrict__ out) {
+  // one block per segment: wave w takes rows w, w + WAVES, ... eight at a time; the waves' sums are added in wave order.
+  // WAVES = 16 for segments of a hundred rows and more (500 entities gathered 82 000 times: 164 rows each -- four waves walk
+  // them in five dependent round trips of order[] -> row, sixteen in two)
+  __shared__ float4 red[WAVES][64];
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const bool col_ok = lane < d4;
+  for (int s = blockIdx.x; s < n_seg; s += gridDim.x) {
+    const int beg = seg_ptr[s], end = seg_ptr[s + 1];
+    float4 acc = zero4();
+    for (int j0 = beg + wave; j0 < end; j0 += 8 * WAVES) {
+      float4 v[8];
+#pragma unroll
+      for (int u = 0; u < 8; ++u) {
+        const int j = j0 + WAVES * u;
+        v[u] = zero4();
+        if (j < end && col_ok) {
+          const int r = order[j];
+          if (!row_mask || row_mask[r] > 0) v[u] = src[(size_t)r * d4 + lane];
+        }
+      }
+#pragma unroll
+      for (int u = 0; u < 8; ++u) acc = add4(acc, v[u]);
+    }
+    red[wave][lane] = acc;
+    __syncthreads();
+    if (wave == 0 && col_ok) {
+      float4 t = red[0][lane];
+#pragma unroll
+      for (int w = 1; w < WAVES; ++w) t = add4(t, red[w][lane]);
+      out[(size_t)s * d4 + lane] = relu_of ? relu_gate4(relu_of[(size_t)s * d4 + lane], t) : t;
+    }
+    __syncthreads();
+  }
+}
+
+// Two sources over the SAME segmentation in one launch (the table layer's backward sums the aggregation part of d_h and dz per
+// table row: same inverse map, one walk of order[] instead of two; a stays masked by row_mask as in the single-source kernels).
+template <int WAVES>
+__global__ void __launch_bounds__(WAVES * 64) k_segment_sum_rows_blk2(int n_seg, int d4a, int d4b, const int32_t* __restrict__ seg_ptr,
+                                                                      const int32_t* __restrict__ order, const float4* __restrict__ src_a,
+                                                                      const int32_t* __restrict__ mask_a, const float4* __restrict__ src_b,
+                                                                      float4* __restrict__ out_a, float4* __restrict__ out_b) {
+  __shared__ float4 red[2][WAVES][64];
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const bool a_ok = lane < d4a, b_ok = lane < d4b;
+  for (int s = blockIdx.x; s < n_seg; s += gridDim.x) {
+    const int beg = seg_ptr[s], end = seg_ptr[s + 1];
+    float4 acc_a = zero4(), acc_b = zero4();
+    for (int j0 = beg + wave; j0 < end; j0 += 4 * WAVES) {
+      float4 va[4], vb[4];
+#pragma unroll
+      for (int u = 0; u < 4; ++u) {
+        const int j = j0 + WAVES * u;
+        va[u] = zero4(); vb[u] = zero4();
+        if (j < end) {
+          const int r = order[j];
+          if (a_ok && (!mask_a || mask_a[r] > 0)) va[u] = src_a[(size_t)r * d4a + lane];
+          if (b_ok) vb[u] = src_b[(size_t)r * d4b + lane];
+        }
+      }
+#pragma unroll
+      for (int u = 0; u < 4; ++u) { acc_a = add4(acc_a, va[u]); acc_b = add4(acc_b, vb[u]); }
+    }
+    red[0][wave][lane] = acc_a;
+    red[1][wave][lane] = acc_b;
+    __syncthreads();
+    if (wave < 2) {
+      const bool ok = wave == 0 ? a_ok : b_ok;
+      if (ok) {
+        float4 t = red[wave][0][lane];
+#pragma unroll
+        for (int w = 1; w < WAVES; ++w) t = add4(t, red[wave][w][lane]);
+        if (wave == 0) out_a[(size_t)s * d4a + lane] = t; else out_b[(size_t)s * d4b + lane] = t;
+      }
+    }
+    __syncthreads();
+  }
+}
+
+int segment_sum_rows2(int n_seg, const int32_t* seg_ptr, const int32_t* order, int d_a, const float* src_a, const int32_t* mask_a, float* out_a,
+                      int d_b, const float* src_b, float* out_b, hipStream_t st, long long n_rows_hint) {
+  if (d_a % 4 == 0 && d_b % 4 == 0 && d_a <= 256 && d_b <= 256 && n_rows_hint >= 96LL * n_seg) {
+    TEMP_LAUNCH(K_SEGMENT_SUM, k_segment_sum_rows_blk2<16>, dim3(n_seg < 4096 ? n_seg : 4096), dim3(16 * 64), 0, st, n_seg, d_a / 4, d_b / 4, seg_ptr, order,
+                (const float4*)src_a, mask_a, (const float4*)src_b, (float4*)out_a, (float4*)out_b);
+    return launch_status();
+  }
+  int rc = segment_sum_rows(n_seg, d_a, seg_ptr, order, src_a, mask_a, out_a, st, n_rows_hint);
+  if (rc) return rc;
+  return segment_sum_rows(n_seg, d_b, seg_ptr, order, src_b, nullptr, out_b, st, n_rows_hint);
+}
+
+// Very long segments (a 40-row relation table gathered 48 000 times by the loss): every segment is cut into S equal
+// parts, one block per part writes its partial sum into the workspace, a second kernel adds the S partials in order.
+__global__ void __launch_bounds__(256) k_segment_sum_part(int S, int d4, const int32_t* __restrict__ seg_ptr, const int32_t* __restrict__ order,
+                                                          const float4* __restrict__ src, const int32_t* __restrict__ row_mask,
+                                                          float4* __restrict__ part) {
+  __shared__ float4 red[4][64];
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const bool col_ok = lane < d4;
+  const int s = blockIdx.y, p = blockIdx.x;
+  const int beg0 = seg_ptr[s], end0 = seg_ptr[s + 1];
+  const int chunk = (end0 - beg0 + S - 1) / S;
+  const int beg = beg0 + p * chunk, end = min(end0, beg + chunk);
+  float4 acc = zero4();
+  for (int j0 = beg + wave; j0 < end; j0 += 32) {
+    float4 v[8];
+#pragma unroll
+    for (int u = 0; u < 8; ++u) {
+      const int j = j0 + 4 * u;
+      v[u] = zero4();
+      if (j < end && col_ok) {
+        const int r = order[j];
+        if (!row_mask || row_mask[r] > 0) v[u] = src[(size_t)r * d4 + lane];
+      }
+    }
+#pragma unroll
+    for (int u = 0; u < 8; ++u) acc = add4(acc, v[u]);
+  }
+  red[wave][lane] = acc;
+  __syncthreads();
+  if (wave == 0 && col_ok) part[((size_t)s * S + p) * d4 + lane] = add4(add4(red[0][lane], red[1][lane]), add4(red[2][lane], red[3][lane]));
+}
+
+__global__ void __launch_bounds__(256) k_segment_sum_fin(int n_seg, int S, int d4, const float4* __restrict__ part, const float4* __restrict__ relu_of,
+                                                         float4* __restrict__ out) {
+  const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= (size_t)n_seg * d4) return;
+  const size_t s = i / d4, c = i - s * d4;
+  float4 acc = zero4();
+  for (int p = 0; p < S; ++p) acc = add4(acc, part[(s * S + p) * d4 + c]);
+  out[i] = relu_of ? relu_gate4(relu_of[i], acc) : acc;
+}
+
+// Segment sum over FIXED PIECES of the row list (skewed segmentations: the adjoint of a gather of Zipf-distributed entity rows has
+// a few segments of hundreds to thousands of rows among thousands of short ones, and a wave per segment takes as long as the
+// longest).  Wave c sums the rows order[32 c .. 32 c + 32) segment by segment, in row order -- all 32 row loads are issued before
+// the first addition: one memory round trip per piece -- a segment that lies inside the piece is written to `out`; the FIRST and
+// the LAST segment of the piece, when they reach beyond it, go to part[c][0] / part[c][1].  k_segment_sum_pieces_fin then adds the
+// pieces of every such segment in piece order (and zero-fills the empty segments): fixed pieces, fixed order => bit-repeatable.
+// Lanes = float4 columns (d4 <= 64).
+#define SEGSUM_PIECE 32
+#define SEGSUM_PIECE_LOG2 5
+__global__ void __launch_bounds__(256) k_segment_sum_pieces(int n_seg, int n_rows, int d4, const int32_t* __restrict__ seg_ptr,
+                                                            const int32_t* __restrict__ order, const float4* __restrict__ src,
+                                                            const int32_t* __restrict__ row_mask, const float4* __restrict__ relu_of,
+                                                            float4* __restrict__ out, float4* __restrict__ part) {
+  const int lane = threadIdx.x & 63;
+  const int c = (blockIdx.x * blockDim.x + threadIdx.x) >> 6;
+  const int r0 = c * SEGSUM_PIECE;
+  n_rows = min(n_rows, seg_ptr[n_seg]);                                    // (the rows there are: order[] holds exactly seg_ptr[n_seg])
+  if (r0 >= n_rows) return;
+  const int r1 = min(r0 + SEGSUM_PIECE, n_rows);
+  const bool col_ok = lane < d4;
+  const int col = col_ok ? lane : 0;
+  int mine = (r0 + lane < r1) ? order[r0 + lane] : -1;
+  if (row_mask && mine >= 0 && row_mask[mine] <= 0) mine = -1;             // masked rows were never written by their producer
+  float4 v[SEGSUM_PIECE];
+#pragma unroll
+  for (int u = 0; u < SEGSUM_PIECE; ++u) {
+    const int r = __builtin_amdgcn_readlane(mine, u);
+    v[u] = r >= 0 ? src[(size_t)r * d4 + col] : zero4();
+  }
+  // the segment of row r0 (wave-uniform binary search: seg_ptr is non-decreasing)
+  int lo = 0, hi = n_seg - 1;
+  while (lo < hi) {
+    const int mid = (lo + hi) >> 1;
+    if (seg_ptr[mid + 1] > r0) hi = mid; else lo = mid + 1;
+  }
+  int sg = lo, sb = seg_ptr[sg], se = seg_ptr[sg + 1];
+  float4 acc = zero4();
+  auto flush = [&]() {
+    if (!col_ok) return;
+    if (sb >= r0 && se <= r1) out[(size_t)sg * d4 + lane] = relu_of ? relu_gate4(relu_of[(size_t)sg * d4 + lane], acc) : acc;
+    else part[((size_t)c * 2 + (sb <= r0 ? 0 : 1)) * d4 + lane] = acc;
+  };
+#pragma unroll
+  for (int u = 0; u < SEGSUM_PIECE; ++u) {
+    const int row = r0 + u;
+    if (row < r1) {
+      if (row == se) {                                                     // (wave-uniform) the next non-empty segment starts here
+        flush();
+        do { ++sg; se = seg_ptr[sg + 1]; } while (se <= row);
+        sb = seg_ptr[sg];
+        acc = zero4();
+      }
+      acc = add4(acc, v[u]);
+    }
+  }
+  flush();
+}
+
+__global__ void __launch_bounds__(256) k_segment_sum_pieces_fin(int n_seg, int d4, const int32_t* __restrict__ seg_ptr, const float4* __restrict__ part,
+                                                                const float4* __restrict__ relu_of, float4* __restrict__ out) {
+  const int lane = threadIdx.x & 63;
+  const int wave = (blockIdx.x * blockDim.x + threadIdx.x) >> 6, nwaves = (gridDim.x * blockDim.x) >> 6;
+  const bool col_ok = lane < d4;
+  for (int s = wave; s < n_seg; s += nwaves) {
+    const int beg = seg_ptr[s], end = seg_ptr[s + 1];
+    if (end <= beg) {
+      if (col_ok) out[(size_t)s * d4 + lane] = zero4();
+      continue;
+    }
+    const int cb = beg >> SEGSUM_PIECE_LOG2, ce = (end - 1) >> SEGSUM_PIECE_LOG2;
+    if (cb == ce) continue;                                                // inside one piece: written by the walk
+    float4 acc = zero4();
+    if (col_ok) {
+      acc = part[((size_t)cb * 2 + ((beg & (SEGSUM_PIECE - 1)) == 0 ? 0 : 1)) * d4 + lane];  // first piece: its last segment, unless it starts the piece
+      int c = cb + 1;
+      for (; c + 16 <= ce + 1; c += 16) {
+        float4 q[16];
+#pragma unroll
+        for (int u = 0; u < 16; ++u) q[u] = part[(size_t)(c + u) * 2 * d4 + lane];
+#pragma unroll
+        for (int u = 0; u < 16; ++u) acc = add4(acc, q[u]);
+      }
+      for (; c <= ce; ++c) acc = add4(acc, part[(size_t)c * 2 * d4 + lane]);
+      out[(size_t)s * d4 + lane] = relu_of ? relu_gate4(relu_of[(size_t)s * d4 + lane], acc) : acc;
+    }
+  }
+}
+
+// rows per segment between the short-segment kernel's and the block-per-segment kernels' ranges: fixed pieces (robust to skew)
+static bool segsum_pieces(int n_seg, long long n_rows, int d4) { return d4 <= 64 && n_rows > 2LL * n_seg && n_rows <= 32LL * n_seg && n_rows < (1LL << 31) - 64; }
+
+static int segsum_splits(int n_seg, long long n_rows) {
+  if (n_seg <= 0 || n_rows < 512LL * n_seg) return 1;
+  int S = 2048 / n_seg;
+  if (S > 64) S = 64;
+  return S < 2 ? 1 : S;
+}
+
+size_t segment_sum_rows_workspace(int n_seg, long long n_rows, int d) {
+  const int S = segsum_splits(n_seg, n_rows);
+  if (S > 1) return (size_t)n_seg * S * d * sizeof(float);
+  if (segsum_pieces(n_seg, n_rows, d / 4)) return (size_t)ceil_div(n_rows, (long long)SEGSUM_PIECE) * 2 * d * sizeof(float);
+  return 0;
+}
+
+int segment_sum_rows(int n_seg, int d, const int32_t* seg_ptr, const int32_t* order, const float* src, const int32_t* row_mask, float* out,
+                     hipStream_t st, long long n_rows_hint, void* ws, size_t ws_bytes, const float* relu_src) {
+  const int d4 = d / 4;
+  const float4* relu_of = (const float4*)relu_src;           // out = (relu_src > 0) ? sum : 0, element by element (nullable)
+  const int S = segsum_splits(n_seg, n_rows_hint);
+  if (S > 1 && d4 <= 64 && ws && ws_bytes >= segment_sum_rows_workspace(n_seg, n_rows_hint, d)) {
+    TEMP_LAUNCH(K_SEGMENT_SUM, k_segment_sum_part, dim3(S, n_seg), dim3(256), 0, st, S, d4, seg_ptr, order, (const float4*)src, row_mask, (float4*)ws);
+    TEMP_LAUNCH(K_SEGMENT_SUM, k_segment_sum_fin, dim3(ceil_div((long long)n_seg * d4, 256)), dim3(256), 0, st, n_seg, S, d4, (const float4*)ws, relu_of, (float4*)out);
+    return launch_status();
+  }
+  if (S <= 1 && segsum_pieces(n_seg, n_rows_hint, d4) && ws && ws_bytes >= segment_sum_rows_workspace(n_seg, n_rows_hint, d)) {
+    const int n_pieces = (int)ceil_div(n_rows_hint, (long long)SEGSUM_PIECE);
+    TEMP_LAUNCH(K_SEGMENT_SUM, k_segment_sum_pieces, dim3(ceil_div(n_pieces, 4)), dim3(256), 0, st, n_seg, (int)n_rows_hint, d4, seg_ptr, order,
+                (const float4*)src, row_mask, relu_of, (float4*)out, (float4*)ws);
+    int grid = ceil_div(n_seg, 4);
+    if (grid > 2048) grid = 2048;
+    TEMP_LAUNCH(K_SEGMENT_SUM, k_segment_sum_pieces_fin, dim3(grid), dim3(256), 0, st, n_seg, d4, seg_ptr, (const float4*)ws, relu_of, (float4*)out);
+    return launch_status();
+  }
+  if (n_rows_hint > 32LL * n_seg && d4 <= 64) {
+    if (n_rows_hint >= 96LL * n_seg)
+      TEMP_LAUNCH(K_SEGMENT_SUM, k_segment_sum_rows_blk<16>, dim3(n_seg < 4096 ? n_seg : 4096), dim3(16 * 64), 0, st, n_seg, d4, seg_ptr, order,
+                  (const float4*)src, row_mask, relu_of, (float4*)out);
+    else
+      TEMP_LAUNCH(K_SEGMENT_SUM, k_segment_sum_rows_blk<4>, dim3(n_seg < 4096 ? n_seg : 4096), dim3(4 * 64), 0, st, n_seg, d4, seg_ptr, order,
+                  (const float4*)src, row_mask, relu_of, (float4*)out);
+    return launch_status();
+  }
+  const bool short_segs = n_rows_hint > 0 && n_rows_hint <= 2LL * n_seg;      // four segments per wave in lockstep
+  int grid = ceil_div(n_seg, short_segs ? 16 : 4);
+  if (grid > 2048) grid = 2048;
+#define TEMP_SEGSUM(L)                                                                                                                      \
+  do {                                                                                                                                      \
+    if (short_segs) TEMP_LAUNCH(K_SEGMENT_SUM, (k_segment_sum_rows_short<L>), dim3(grid), dim3(256), 0, st, n_seg, d4, seg_ptr, order,      \
+                                (const float4*)src, row_mask, relu_of, (float4*)out);                                                       \
+    else TEMP_LAUNCH(K_SEGMENT_SUM, (k_segment_sum_rows<L>), dim3(grid), dim3(256), 0, st, n_seg, d4, seg_ptr, order, (const float4*)src,   \
+                     row_mask, relu_of, (float4*)out);                                                                                      \
+  } while (0)
+  if (d4 <= 8) TEMP_SEGSUM(8); else if (d4 <= 16) TEMP_SEGSUM(16); else if (d4 <= 32) TEMP_SEGSUM(32); else TEMP_SEGSUM(64);
+#undef TEMP_SEGSUM
+  return launch_status();
+}
+}  // namespace temp
+
+using namespace temp;
+
+extern "C" {
+
+int temp_gather_rows(int n, int d, const float* table, const int32_t* idx, float* out, void* stream) {
+  if (n < 0 || d <= 0 || (n > 0 && (!table || !idx || !out))) return TEMP_E_BADARG;
+  if (d % 4) return TEMP_E_UNSUPPORTED;
+  if (n == 0) return TEMP_OK;
+  int grid = ceil_div((long long)n * (d / 4), 256);
+  if (grid > 4096) grid = 4096;
+  TEMP_LAUNCH(K_GATHER_ROWS, k_gather_rows, dim3(grid), dim3(256), 0, (hipStream_t)stream, n, d / 4, (const float4*)table, idx, (float4*)out);
+  return launch_status();
+}
+
+int temp_scatter_add_rows(int n, int d, const float* src, const int32_t* idx, float* table, void* stream) {
+  if (n < 0 || d <= 0 || (n > 0 && (!table || !idx || !src))) return TEMP_E_BADARG;
+  if (n == 0) return TEMP_OK;
+  int grid = ceil_div((long long)n * d, 256);
+  if (grid > 4096) grid = 4096;
+  TEMP_LAUNCH(K_SCATTER_ADD, k_scatter_add_rows, dim3(grid), dim3(256), 0, (hipStream_t)stream, n, d, src, idx, table);
+  return launch_status();
+}
+
+size_t temp_segment_sum_rows_workspace(int n_seg, int n_rows, int d) { return (n_seg <= 0 || d <= 0) ? 0 : segment_sum_rows_workspace(n_seg, n_rows, d); }
+
+int temp_segment_sum_rows(int n_seg, int n_rows, int d, const int32_t* seg_ptr, const int32_t* order, const float* src, float* out,
+                          void* workspace, size_t workspace_bytes, void* stream) {
+  if (n_seg < 0 || d <= 0 || (n_seg > 0 && (!seg_ptr || !src || !out))) return TEMP_E_BADARG;
+  return segment_sum_rows(n_seg, d, seg_ptr, order, src, nullptr, out, (hipStream_t)stream, n_rows, workspace, workspace_bytes);
+}
+
+int temp_segment_sum_rows_relu(int n_seg, int n_rows, int d, const int32_t* seg_ptr, const int32_t* order, const float* src, const float* relu_of,
+                               float* out, void* workspace, size_t workspace_bytes, void* stream) {
+  if (n_seg < 0 || d <= 0 || (n_seg > 0 && (!seg_ptr || !src || !out || !relu_of))) return TEMP_E_BADARG;
+  return segment_sum_rows(n_seg, d, seg_ptr, order, src, nullptr, out, (hipStream_t)stream, n_rows, workspace, workspace_bytes, relu_of);
+}
+
+int temp_gather_rows_keys(int n, int d, const float* table, const int32_t* idx, float* out, uint32_t* row_keys, uint32_t* col_keys, void* stream) {
+  if (n < 0 || d <= 0 || (n > 0 && (!table || !idx || !out))) return TEMP_E_BADARG;
+  if (d % 4 || d > 256) return TEMP_E_UNSUPPORTED;
+  if (n == 0) return TEMP_OK;
+  launch_gather_rows_keys(n, d, table, idx, out, row_keys, col_keys, col_keys ? col_keys + d : nullptr, (hipStream_t)stream);
+  return launch_status();
+}
+
+}  // extern "C"

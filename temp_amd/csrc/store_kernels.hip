@@ -1,4 +1,5 @@
-// Device-side edge subsample of a resident snapshot (include/temp_amd.h: temp_subsample_views).
+// Device-side edge subsample of a resident snapshot (include/temp_amd.h: temp_subsample_views), and the one-launch assembly of a
+// batch's edge views from its members' resident views (temp_assemble_views, at the end).
 //
 // In training the target snapshot of every window is message-passed on a uniformly random 50 % of its edges (80 % for
 // history snapshots under --random-dropout) with norms recomputed from the subgraph's in-degrees
@@ -121,6 +122,31 @@ __global__ void __launch_bounds__(256) k_subsample_norm(SubBatch batch) {
     nn[i] = deg[i] > 0 ? 1.0f / (float)deg[i] : 0.f;                     // comp_deg_norm: 1 / in_deg, inf -> 0
 }
 
+// ---------------------------------------------------------------------------------------------
+// Snapshot store: the edge views of a batch (a disjoint union of member snapshots whose sorted / chunked views are
+// resident on the device) are the members' arrays back to back with per-member offsets added.  One launch copies every
+// array of every member: a descriptor names a member array, its place in the packed output and how to shift it;
+// a piece is up to TEMP_ASSEMBLE_PIECE elements of one descriptor (one workgroup each).
+//   mode 0: out = v + add        mode 1: out = v >= 0 ? v + add : v   (partial-sum slots, -1 = none)
+//   mode 2: t = table[add + aux[i]];  out = t >= 0 ? t + v : t        (by-relation slots: base of the member x relation + rank)
+// ---------------------------------------------------------------------------------------------
+__global__ void __launch_bounds__(256) k_assemble_views(const int32_t* __restrict__ piece_desc, const int32_t* __restrict__ piece_start,
+                                                        const TempCopyDesc* __restrict__ descs, const int32_t* __restrict__ table,
+                                                        int32_t* __restrict__ out) {
+  const TempCopyDesc d = descs[piece_desc[blockIdx.x]];
+  const int start = piece_start[blockIdx.x];
+  const int end = min(d.len, start + TEMP_ASSEMBLE_PIECE);
+  int32_t* __restrict__ o = out + d.dst_off;
+  for (int i = start + threadIdx.x; i < end; i += 256) {
+    const int v = d.src[i];
+    int r;
+    if (d.mode == 0) r = v + d.add;
+    else if (d.mode == 1) r = v >= 0 ? v + d.add : v;
+    else { const int t = table[d.add + d.aux[i]]; r = t >= 0 ? t + v : t; }
+    o[i] = r;
+  }
+}
+
 }  // namespace temp
 
 using namespace temp;
@@ -166,6 +192,14 @@ int temp_subsample_views(int n_jobs, const TempSubsampleJob* jobs, void* stream)
     if (rc) return rc;
   }
   return TEMP_OK;
+}
+
+int temp_assemble_views(int n_pieces, const int32_t* piece_desc, const int32_t* piece_start, const TempCopyDesc* descs, const int32_t* table,
+                        int32_t* out, void* stream) {
+  if (n_pieces < 0 || (n_pieces > 0 && (!piece_desc || !piece_start || !descs || !out))) return TEMP_E_BADARG;
+  if (n_pieces == 0) return TEMP_OK;
+  TEMP_LAUNCH(K_COPY, k_assemble_views, dim3(n_pieces), dim3(256), 0, (hipStream_t)stream, piece_desc, piece_start, descs, table, out);
+  return launch_status();
 }
 
 }  // extern "C"

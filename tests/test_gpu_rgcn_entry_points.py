@@ -1,0 +1,133 @@
+"""Host scaffolding of the RGCN layer's backward entry points (temp_rgcn_bwd, temp_rgcn_bwd_dh, temp_rgcn_bwd_weights,
+temp_rgcn_table_bwd) on the GPU: a graph without nodes zeroes every gradient output and returns TEMP_OK, and the two halves of
+the backward (d_h, then the weight pass over the gradients the first half wrote) give the bits of the whole backward, with and
+without self-loop dropout, with the relation-weight gradient beside the d/dh aggregation (TEMP_OPT_OVERLAP = 1) and behind it."""
+import ctypes
+
+import numpy as np
+import pytest
+import torch
+
+from temp_amd import _lib
+from temp_amd import backend as TB
+from temp_amd import functional as TF
+from temp_amd.snapshot import Snapshot
+
+pytestmark = pytest.mark.gpu
+DEV = torch.device("cuda:0")
+TEMP_OK = 0                                                 # include/temp_amd.h
+
+
+@pytest.fixture
+def hip_backend():
+    TB.set_backend(None)
+    be = TB.get_backend()
+    assert be.name == "hip"
+    return be
+
+
+def _p(t):
+    return ctypes.c_void_p(t.data_ptr()) if t is not None else None
+
+
+def test_empty_graph_zeroes_every_gradient(hip_backend):
+    """n_nodes = 0: d_weight, d_loop_w, d_bias (and d_table of the table route) come back all zero -- the outputs are prefilled
+    with NaN here, so memory the call left alone would show -- and every call returns TEMP_OK."""
+    lib = hip_backend.lib
+    z = np.zeros(0, np.int64)
+    g = Snapshot(0, z, z, z, np.arange(0))
+    D, B, R2, n_table = 16, 4, 6, 20
+    wrow = B * (D // B) ** 2
+    dg = g.device_graph(DEV, R2)
+    assert dg.n_nodes == 0
+    rng = np.random.default_rng(11)
+    f = lambda *s: torch.from_numpy(rng.standard_normal(s).astype(np.float32)).to(DEV)
+    nan = lambda *s: torch.full(s, float("nan"), dtype=torch.float32, device=DEV)
+    rows = torch.zeros(1, D, device=DEV)                    # stands for every (0, D) node array: an empty tensor has a NULL pointer
+    table, w, lw = f(n_table, D), f(R2, wrow), f(D, D)
+    inv_ptr, inv_order = TF.gather_inverse(np.zeros(0, np.int64), n_table, DEV)
+    st = TB._stream()
+    ws = torch.empty(max(256, int(lib.temp_rgcn_bwd_workspace(dg.ref(), D, D, B, R2))), dtype=torch.uint8, device=DEV)
+
+    d_h, d_w, d_loop, d_bias = nan(1, D), nan(R2, wrow), nan(D, D), nan(D)
+    rc = lib.temp_rgcn_bwd(dg.ref(), _p(rows), _p(rows), _p(rows), D, D, B, R2, _p(w), _p(lw), 1, _lib.ACT_RELU, _p(d_h), _p(d_w), _p(d_loop),
+                           _p(d_bias), _p(ws), ws.numel(), None, st)
+    assert rc == TEMP_OK, "temp_rgcn_bwd: %d" % rc
+    for name, t in (("d_weight", d_w), ("d_loop_w", d_loop), ("d_bias", d_bias)):
+        assert torch.equal(t, torch.zeros_like(t)), "temp_rgcn_bwd, no nodes: %s not zeroed" % name
+
+    d_w, d_loop, d_bias = nan(R2, wrow), nan(D, D), nan(D)
+    rc = lib.temp_rgcn_bwd_weights(dg.ref(), _p(rows), _p(rows), None, D, D, B, R2, 1, _p(d_w), _p(d_loop), _p(d_bias), _p(ws), ws.numel(), st)
+    assert rc == TEMP_OK, "temp_rgcn_bwd_weights: %d" % rc
+    for name, t in (("d_weight", d_w), ("d_loop_w", d_loop), ("d_bias", d_bias)):
+        assert torch.equal(t, torch.zeros_like(t)), "temp_rgcn_bwd_weights, no nodes: %s not zeroed" % name
+
+    wt = torch.empty(max(256, int(lib.temp_rgcn_table_bwd_workspace(dg.ref(), n_table, D, D, B))), dtype=torch.uint8, device=DEV)
+    d_table, d_w, d_loop, d_bias = nan(n_table, D), nan(R2, wrow), nan(D, D), nan(D)
+    rc = lib.temp_rgcn_table_bwd(dg.ref(), _p(table), None, _p(inv_ptr), _p(inv_order) if inv_order.numel() else None, n_table, _p(rows), _p(rows),
+                                 D, D, B, R2, _p(w), _p(lw), 1, _lib.ACT_RELU, _p(d_table), _p(d_w), _p(d_loop), _p(d_bias), _p(wt), wt.numel(),
+                                 None, st)
+    assert rc == TEMP_OK, "temp_rgcn_table_bwd: %d" % rc
+    for name, t in (("d_table", d_table), ("d_weight", d_w), ("d_loop_w", d_loop), ("d_bias", d_bias)):
+        assert torch.equal(t, torch.zeros_like(t)), "temp_rgcn_table_bwd, no nodes: %s not zeroed" % name
+
+
+def _hub_graph(chunked):
+    """70 nodes (just over one wave of rows), 400 edges, 6 relation rows, the first 150 edges into 4 hub nodes.  At these counts a
+    hub has ~37 incoming edges and a relation ~67, fewer than a chunk of any view (64 / 128 edges), so the second graph also sends
+    150 edges out of 2 nodes and gives 200 edges one relation: segments of several chunks in the by-src and by-rel views, whose
+    partial sums the fix-up adds."""
+    rng = np.random.default_rng(7)
+    n, E, R2 = 70, 400, 6
+    src, dst, rel = rng.integers(0, n, E), rng.integers(0, n, E), rng.integers(0, R2, E)
+    dst[:150] = rng.integers(0, 4, 150)
+    if chunked:
+        src[100:250] = rng.integers(0, 2, 150)
+        rel[:200] = 3
+    return Snapshot(n, src, dst, rel, np.arange(n)), R2
+
+
+GRAPHS = {}
+
+
+@pytest.fixture(params=[False, True], ids=["hubs", "hubs+chunks"])
+def hub_graph(request):
+    if request.param not in GRAPHS:
+        GRAPHS[request.param] = _hub_graph(request.param)
+    g, R2 = GRAPHS[request.param]
+    v = g.device_graph(DEV, R2).c
+    assert (v.by_src.n_fix > 0 and v.by_rel.n_fix > 0) == request.param
+    return g, R2
+
+
+@pytest.mark.parametrize("overlap", [1, 0])
+@pytest.mark.parametrize("p", [0.0, 0.25])
+@pytest.mark.parametrize("D,B", [(16, 4), (200, 100)])
+def test_split_backward_equals_whole_backward(D, B, p, overlap, hub_graph, hip_backend):
+    """temp_rgcn_bwd_dh followed by temp_rgcn_bwd_weights against temp_rgcn_bwd, ReLU and bias on: the same kernels over the same
+    operands with ordered reductions, so the same bits."""
+    g, R2 = hub_graph
+    lib = hip_backend.lib
+    rng = np.random.default_rng(100 * D + int(100 * p))
+    f = lambda *s: torch.from_numpy(rng.standard_normal(s).astype(np.float32)).to(DEV)
+    n, Sb = g.n, D // B
+    h, w, lw, b, gy = f(n, D), f(R2, B * Sb * Sb) * 0.5, f(D, D) * 0.2, f(D), f(n, D)
+    drop = (p, 0x5EED1234) if p > 0 else None
+    dg = g.device_graph(DEV, R2)
+    prev = lib.temp_set_option(_lib.OPT_OVERLAP, overlap)
+    try:
+        out = hip_backend.rgcn_fwd(dg, h, None, w, lw, b, B, _lib.ACT_RELU, drop)
+        whole = hip_backend.rgcn_bwd(dg, h, out, gy, w, lw, True, B, _lib.ACT_RELU, drop)
+        dz, dzm = torch.empty_like(gy), (torch.empty_like(gy) if drop else None)
+        d_h = hip_backend.rgcn_bwd_dh(dg, out, gy, w, lw, B, _lib.ACT_RELU, drop, dz_out=dz, dzm_out=dzm)
+        split = (d_h,) + tuple(hip_backend.rgcn_bwd_weights(dg, h, dz, dzm, w, lw, True, B))
+        torch.cuda.synchronize()
+    finally:
+        lib.temp_set_option(_lib.OPT_OVERLAP, prev)
+    names = ("d_h", "d_weight", "d_loop_w", "d_bias")
+    for name, a, c in zip(names, split, whole):
+        print("split vs whole D=%d B=%d p=%g overlap=%d %s: max|diff| = %.3e, max|ref| = %.3e"
+              % (D, B, p, overlap, name, (a - c).abs().max().item(), c.abs().max().item()))
+    for name, a, c in zip(names, split, whole):
+        assert torch.isfinite(c).all() and c.abs().max().item() > 0, name + ": the whole backward wrote nothing to compare"
+        assert torch.equal(a, c), "D=%d B=%d p=%g overlap=%d: %s of the split backward differs from temp_rgcn_bwd" % (D, B, p, overlap, name)

@@ -2,6 +2,7 @@
 //   hipcc --offload-arch=gfx950 -O3 -std=c++17 -Iinclude -Itemp_amd/csrc tools/wres_probe.hip -o tools/wres_probe
 #include "common.hpp"
 #include "gemm_wres.hpp"
+#include "../temp_amd/csrc/runtime.hip"
 #include "../temp_amd/csrc/gemm_kernels.hip"
 #include "../temp_amd/csrc/gru_kernels.hip"
 #include <cstdio>
