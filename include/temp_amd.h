@@ -601,7 +601,8 @@ int temp_scatter_add_rows(int n, int d, const float* src, const int32_t* idx, fl
  * seg_ptr [n_seg+1] / order [n_rows] = the gather indices grouped by table row (built once on the host;
  * ids < 0 are left out, so n_rows may be smaller than the gather).  n_rows must be EXACTLY the length of `order`
  * (= seg_ptr[n_seg]): the piece kernels size their partials from it (a smaller value would drop the trailing rows).
- * No atomics; d % 4 == 0, d <= 256.  Tables with very long segments (>= 512 rows per segment on average, e.g. the
+ * No atomics; d % 4 == 0 (else TEMP_E_UNSUPPORTED).  d <= 256 takes the routes below; wider rows are summed by one wave per
+ * segment, 256 columns at a time, whatever the segment lengths (workspace 0).  Tables with very long segments (>= 512 rows per segment on average, e.g. the
  * relation table under the loss) are reduced in two deterministic stages through `workspace`; segmentations of 2-32 rows per
  * segment on average are summed over fixed 32-row pieces of `order` (skew-proof: a hub entity's thousands of rows are many
  * pieces, not one wave's loop) with the piece partials in `workspace`

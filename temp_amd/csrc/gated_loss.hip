@@ -291,7 +291,7 @@ int temp_gather_ce_mix_bwd(int P, int C, int N, const float* s_a, const float* s
     return launch_status();
   }
   const size_t lds = (size_t)N * sizeof(int);
-  if (lds > 65536) {
+  if (lds + 64 > 65536) {                               // (the kernel's static `red` counts towards the default 64 KB)
     if (hipFuncSetAttribute((const void*)k_gather_ce_mix_bwd, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess) return TEMP_E_LAUNCH;
   }
   TEMP_LAUNCH(K_GATHER_CE_MIX, k_gather_ce_mix_bwd, dim3(P), dim3(256), lds, (hipStream_t)stream, C, N, s_a, s_b, w, cand, lse_rows, scale, inv_rows,

@@ -359,9 +359,13 @@ int temp_gather_ce_fwd(int P, int C, int N, const float* scores, const int32_t* 
   if (P == 0) return TEMP_OK;
   if (2 * (long long)C >= N && N <= 1024)
     TEMP_LAUNCH(K_GATHER_CE, k_gather_ce_fwd_cnt_w, dim3(ceil_div(P, 4)), dim3(256), (size_t)4 * N * sizeof(int), (hipStream_t)stream, P, C, N, scores, cand, loss_rows, lse_rows);
-  else if (2 * (long long)C >= N && (size_t)N * sizeof(int) <= 64 * 1024)
-    TEMP_LAUNCH(K_GATHER_CE, k_gather_ce_fwd_cnt, dim3(P), dim3(256), (size_t)N * sizeof(int), (hipStream_t)stream, C, N, scores, cand, loss_rows, lse_rows);
-  else
+  else if (2 * (long long)C >= N && (size_t)N * sizeof(int) <= 64 * 1024) {
+    const size_t lds = (size_t)N * sizeof(int);
+    if (lds + 64 > 65536) {                             // with the kernel's static `red` the workgroup is past the default 64 KB
+      if (hipFuncSetAttribute((const void*)k_gather_ce_fwd_cnt, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess) return TEMP_E_LAUNCH;
+    }
+    TEMP_LAUNCH(K_GATHER_CE, k_gather_ce_fwd_cnt, dim3(P), dim3(256), lds, (hipStream_t)stream, C, N, scores, cand, loss_rows, lse_rows);
+  } else
     TEMP_LAUNCH(K_GATHER_CE, k_gather_ce_fwd, dim3(P), dim3(256), 0, (hipStream_t)stream, C, N, scores, cand, loss_rows, lse_rows);
   return launch_status();
 }

@@ -30,44 +30,49 @@ __global__ void __launch_bounds__(256) k_scatter_add_rows(int n, int d, const fl
 // replacement of the atomic scatter for hot tables: GDELT has 500 entities and ~100 k gathered rows per step,
 // i.e. ~200 atomic adds per table element.  One wave per segment, one float4 per lane, 4 row loads in flight;
 // the d/4-lane groups of a wave (LPR lanes each) take every (64/LPR)-th row and are summed by shuffles.
-template <int LPR>
+// WIDE (d4 > 64, LPR = 64): the wave walks the segment once per 64 float4 columns.
+template <int LPR, bool WIDE = false>
 __global__ void __launch_bounds__(256) k_segment_sum_rows(int n_seg, int d4, const int32_t* __restrict__ seg_ptr,
                                                           const int32_t* __restrict__ order, const float4* __restrict__ src,
                                                           const int32_t* __restrict__ row_mask, const float4* __restrict__ relu_of,
                                                           float4* __restrict__ out) {
   constexpr int G = 64 / LPR;
-  const int lane = threadIdx.x & 63, grp = lane / LPR, lr = lane - grp * LPR;
+  static_assert(!WIDE || LPR == 64, "the column loop is for rows wider than a wave");
+  const int lane = threadIdx.x & 63, grp = lane / LPR, lr0 = lane - grp * LPR;
   const int wave = (blockIdx.x * blockDim.x + threadIdx.x) >> 6, nwaves = (gridDim.x * blockDim.x) >> 6;
-  const bool col_ok = lr < d4;
   for (int s = wave; s < n_seg; s += nwaves) {
     const int beg = seg_ptr[s], end = seg_ptr[s + 1];
-    float4 acc = zero4();
-    int j = beg + grp;
-    for (; j + 3 * G < end; j += 4 * G) {
-      const int r0 = order[j], r1 = order[j + G], r2 = order[j + 2 * G], r3 = order[j + 3 * G];
-      const bool m0 = !row_mask || row_mask[r0] > 0, m1 = !row_mask || row_mask[r1] > 0, m2 = !row_mask || row_mask[r2] > 0,
-                 m3 = !row_mask || row_mask[r3] > 0;          // masked rows were never written by their producer
-      float4 v0 = zero4(), v1 = zero4(), v2 = zero4(), v3 = zero4();
-      if (col_ok) {
-        if (m0) v0 = src[(size_t)r0 * d4 + lr];
-        if (m1) v1 = src[(size_t)r1 * d4 + lr];
-        if (m2) v2 = src[(size_t)r2 * d4 + lr];
-        if (m3) v3 = src[(size_t)r3 * d4 + lr];
+    for (int c0 = 0; c0 < (WIDE ? d4 : 1); c0 += LPR) {                   // (one trip unless WIDE)
+      const int lr = c0 + lr0;
+      const bool col_ok = lr < d4;
+      float4 acc = zero4();
+      int j = beg + grp;
+      for (; j + 3 * G < end; j += 4 * G) {
+        const int r0 = order[j], r1 = order[j + G], r2 = order[j + 2 * G], r3 = order[j + 3 * G];
+        const bool m0 = !row_mask || row_mask[r0] > 0, m1 = !row_mask || row_mask[r1] > 0, m2 = !row_mask || row_mask[r2] > 0,
+                   m3 = !row_mask || row_mask[r3] > 0;          // masked rows were never written by their producer
+        float4 v0 = zero4(), v1 = zero4(), v2 = zero4(), v3 = zero4();
+        if (col_ok) {
+          if (m0) v0 = src[(size_t)r0 * d4 + lr];
+          if (m1) v1 = src[(size_t)r1 * d4 + lr];
+          if (m2) v2 = src[(size_t)r2 * d4 + lr];
+          if (m3) v3 = src[(size_t)r3 * d4 + lr];
+        }
+        acc = add4(add4(acc, v0), add4(v1, add4(v2, v3)));
       }
-      acc = add4(add4(acc, v0), add4(v1, add4(v2, v3)));
-    }
-    for (; j < end; j += G) {
-      const int r = order[j];
-      if (col_ok && (!row_mask || row_mask[r] > 0)) acc = add4(acc, src[(size_t)r * d4 + lr]);
-    }
+      for (; j < end; j += G) {
+        const int r = order[j];
+        if (col_ok && (!row_mask || row_mask[r] > 0)) acc = add4(acc, src[(size_t)r * d4 + lr]);
+      }
 #pragma unroll
-    for (int m = LPR; m < 64; m <<= 1) acc = add4(acc, shfl_xor4(acc, m));
-    if (grp == 0 && col_ok) out[(size_t)s * d4 + lr] = relu_of ? relu_gate4(relu_of[(size_t)s * d4 + lr], acc) : acc;
+      for (int m = LPR; m < 64; m <<= 1) acc = add4(acc, shfl_xor4(acc, m));
+      if (grp == 0 && col_ok) out[(size_t)s * d4 + lr] = relu_of ? relu_gate4(relu_of[(size_t)s * d4 + lr], acc) : acc;
+    }
   }
 }
 
 // The same for segments of one or two rows (the adjoint of a gather whose rows are mostly distinct).
-template <int LPR>
+template <int LPR, bool WIDE = false>
 __global__ void __launch_bounds__(256) k_segment_sum_rows_short(int n_seg, int d4, const int32_t* __restrict__ seg_ptr,
                                                           const int32_t* __restrict__ order, const float4* __restrict__ src,
                                                           const int32_t* __restrict__ row_mask, const float4* __restrict__ relu_of,
@@ -76,9 +81,9 @@ __global__ void __launch_bounds__(256) k_segment_sum_rows_short(int n_seg, int d
   // (seg_ptr -> order -> row) are then shared by four segments instead of paid by each (the gather adjoints have 1-2 rows per
   // segment: the walk is all latency).
   constexpr int G = 64 / LPR, U = 4;
-  const int lane = threadIdx.x & 63, grp = lane / LPR, lr = lane - grp * LPR;
+  static_assert(!WIDE || LPR == 64, "the column loop is for rows wider than a wave");
+  const int lane = threadIdx.x & 63, grp = lane / LPR, lr0 = lane - grp * LPR;
   const int wave = (blockIdx.x * blockDim.x + threadIdx.x) >> 6, nwaves = (gridDim.x * blockDim.x) >> 6;
-  const bool col_ok = lr < d4;
   for (int s0 = wave * U; s0 < n_seg; s0 += nwaves * U) {
     int beg[U], len[U], maxlen = 0;
 #pragma unroll
@@ -88,28 +93,32 @@ __global__ void __launch_bounds__(256) k_segment_sum_rows_short(int n_seg, int d
       len[u] = ok ? seg_ptr[s0 + u + 1] - beg[u] : 0;
       maxlen = max(maxlen, len[u]);
     }
-    float4 acc[U];
+    for (int c0 = 0; c0 < (WIDE ? d4 : 1); c0 += LPR) {                   // (one trip unless WIDE)
+      const int lr = c0 + lr0;
+      const bool col_ok = lr < d4;
+      float4 acc[U];
 #pragma unroll
-    for (int u = 0; u < U; ++u) acc[u] = zero4();
-    for (int k = grp; k < maxlen; k += G) {
-      int r[U];
+      for (int u = 0; u < U; ++u) acc[u] = zero4();
+      for (int k = grp; k < maxlen; k += G) {
+        int r[U];
 #pragma unroll
-      for (int u = 0; u < U; ++u) r[u] = k < len[u] ? order[beg[u] + k] : -1;
-      float4 v[U];
+        for (int u = 0; u < U; ++u) r[u] = k < len[u] ? order[beg[u] + k] : -1;
+        float4 v[U];
 #pragma unroll
-      for (int u = 0; u < U; ++u) {
-        v[u] = zero4();
-        if (r[u] >= 0 && col_ok && (!row_mask || row_mask[r[u]] > 0)) v[u] = src[(size_t)r[u] * d4 + lr];   // masked rows were never written
+        for (int u = 0; u < U; ++u) {
+          v[u] = zero4();
+          if (r[u] >= 0 && col_ok && (!row_mask || row_mask[r[u]] > 0)) v[u] = src[(size_t)r[u] * d4 + lr];   // masked rows were never written
+        }
+#pragma unroll
+        for (int u = 0; u < U; ++u) acc[u] = add4(acc[u], v[u]);
       }
 #pragma unroll
-      for (int u = 0; u < U; ++u) acc[u] = add4(acc[u], v[u]);
-    }
+      for (int u = 0; u < U; ++u) {
 #pragma unroll
-    for (int u = 0; u < U; ++u) {
-#pragma unroll
-      for (int m = LPR; m < 64; m <<= 1) acc[u] = add4(acc[u], shfl_xor4(acc[u], m));
-      if (grp == 0 && col_ok && s0 + u < n_seg)
-        out[(size_t)(s0 + u) * d4 + lr] = relu_of ? relu_gate4(relu_of[(size_t)(s0 + u) * d4 + lr], acc[u]) : acc[u];
+        for (int m = LPR; m < 64; m <<= 1) acc[u] = add4(acc[u], shfl_xor4(acc[u], m));
+        if (grp == 0 && col_ok && s0 + u < n_seg)
+          out[(size_t)(s0 + u) * d4 + lr] = relu_of ? relu_gate4(relu_of[(size_t)(s0 + u) * d4 + lr], acc[u]) : acc[u];
+      }
     }
   }
 }
@@ -353,6 +362,7 @@ static int segsum_splits(int n_seg, long long n_rows) {
 }
 
 size_t segment_sum_rows_workspace(int n_seg, long long n_rows, int d) {
+  if (d / 4 > 64) return 0;                                  // wider than a wave of float4: a wave per segment, no workspace
   const int S = segsum_splits(n_seg, n_rows);
   if (S > 1) return (size_t)n_seg * S * d * sizeof(float);
   if (segsum_pieces(n_seg, n_rows, d / 4)) return (size_t)ceil_div(n_rows, (long long)SEGSUM_PIECE) * 2 * d * sizeof(float);
@@ -390,14 +400,17 @@ int segment_sum_rows(int n_seg, int d, const int32_t* seg_ptr, const int32_t* or
   const bool short_segs = n_rows_hint > 0 && n_rows_hint <= 2LL * n_seg;      // four segments per wave in lockstep
   int grid = ceil_div(n_seg, short_segs ? 16 : 4);
   if (grid > 2048) grid = 2048;
-#define TEMP_SEGSUM(L)                                                                                                                      \
+#define TEMP_SEGSUM(...)                                                                                                                     \
   do {                                                                                                                                      \
-    if (short_segs) TEMP_LAUNCH(K_SEGMENT_SUM, (k_segment_sum_rows_short<L>), dim3(grid), dim3(256), 0, st, n_seg, d4, seg_ptr, order,      \
+    if (short_segs) TEMP_LAUNCH(K_SEGMENT_SUM, (k_segment_sum_rows_short<__VA_ARGS__>), dim3(grid), dim3(256), 0, st, n_seg, d4, seg_ptr, order,      \
                                 (const float4*)src, row_mask, relu_of, (float4*)out);                                                       \
-    else TEMP_LAUNCH(K_SEGMENT_SUM, (k_segment_sum_rows<L>), dim3(grid), dim3(256), 0, st, n_seg, d4, seg_ptr, order, (const float4*)src,   \
+    else TEMP_LAUNCH(K_SEGMENT_SUM, (k_segment_sum_rows<__VA_ARGS__>), dim3(grid), dim3(256), 0, st, n_seg, d4, seg_ptr, order, (const float4*)src,   \
                      row_mask, relu_of, (float4*)out);                                                                                      \
   } while (0)
-  if (d4 <= 8) TEMP_SEGSUM(8); else if (d4 <= 16) TEMP_SEGSUM(16); else if (d4 <= 32) TEMP_SEGSUM(32); else TEMP_SEGSUM(64);
+  // d4 > 64: the lanes of the block, split and piece kernels are the columns of a row, so wider rows come here whatever the segment
+  // lengths, and the wave walks its segment once per 64 columns
+  if (d4 <= 8) TEMP_SEGSUM(8); else if (d4 <= 16) TEMP_SEGSUM(16); else if (d4 <= 32) TEMP_SEGSUM(32); else if (d4 <= 64) TEMP_SEGSUM(64);
+  else TEMP_SEGSUM(64, true);
 #undef TEMP_SEGSUM
   return launch_status();
 }
@@ -431,12 +444,14 @@ size_t temp_segment_sum_rows_workspace(int n_seg, int n_rows, int d) { return (n
 int temp_segment_sum_rows(int n_seg, int n_rows, int d, const int32_t* seg_ptr, const int32_t* order, const float* src, float* out,
                           void* workspace, size_t workspace_bytes, void* stream) {
   if (n_seg < 0 || d <= 0 || (n_seg > 0 && (!seg_ptr || !src || !out))) return TEMP_E_BADARG;
+  if (d % 4) return TEMP_E_UNSUPPORTED;
   return segment_sum_rows(n_seg, d, seg_ptr, order, src, nullptr, out, (hipStream_t)stream, n_rows, workspace, workspace_bytes);
 }
 
 int temp_segment_sum_rows_relu(int n_seg, int n_rows, int d, const int32_t* seg_ptr, const int32_t* order, const float* src, const float* relu_of,
                                float* out, void* workspace, size_t workspace_bytes, void* stream) {
   if (n_seg < 0 || d <= 0 || (n_seg > 0 && (!seg_ptr || !src || !out || !relu_of))) return TEMP_E_BADARG;
+  if (d % 4) return TEMP_E_UNSUPPORTED;
   return segment_sum_rows(n_seg, d, seg_ptr, order, src, nullptr, out, (hipStream_t)stream, n_rows, workspace, workspace_bytes, relu_of);
 }
 

@@ -158,6 +158,12 @@ def test_gated_loss_definition_and_quirks_gpu(kind, bi):
     PA.check_gated_loss_definition(DEV, kind, bi)
 
 
+@pytest.mark.parametrize("kind,bi", [("complex", True), ("distmult", False)])
+def test_gated_loss_definition_wide_embeddings_gpu(kind, bi):
+    """embed_size 320: the node's three segment sums run past 256 columns (more float4 columns than a wave has lanes)."""
+    PA.check_gated_loss_definition(DEV, kind, bi, windows=3, P=37, C=21, D=320)
+
+
 def test_gated_loss_definition_full_size_gpu():
     PA.check_gated_loss_definition(DEV, "complex", True, windows=3, P=1000, C=51, D=200, full_bar=True)
 
