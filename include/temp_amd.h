@@ -114,6 +114,31 @@ long long temp_f16_launches(void);
 long long temp_tile_launches(void);
 /* Diagnostic: calls of temp_rgcn_pair_fwd / temp_rgcn_pair_bwd that launched their kernels. */
 long long temp_pair_launches(void);
+/* Diagnostic: which dense-product kernel ran.  Every launch site of the dense-product dispatcher (launch_gemm_panel_multi behind
+ * temp_linear*, the self-loop / isolated / GRU products; the two extra branches of temp_linear_multi; the single-product fp32
+ * weight-gradient kernel behind temp_linear_tn -- not the several-products launch of temp_linear_tn_multi nor the split-operand
+ * weight-gradient kernels) adds one to the cell [route][width] when it launches its kernel; the trace names all of them
+ * k_gemm_panel<...> / k_gemm_tn.  `width` is the kernel's template width (0 for the routes that have none, always < 8).
+ * temp_gemm_route_launches returns the launches so far in this process, -1 for a route or width outside the table. */
+enum {
+  TEMP_ROUTE_PANEL = 0,       /* k_gemm_panel<NT>: fp32 MFMA row panels                                   width NT = 1..4  */
+  TEMP_ROUTE_WRES = 1,        /* k_gemm_wres<NTS>: fp32 MFMA, weights resident, every block walks all problems  NTS = 1..3  */
+  TEMP_ROUTE_WRES_SPLIT = 2,  /* k_gemm_wres<NTS>, `split`: every block serves one problem                      NTS = 1..3  */
+  TEMP_ROUTE_BXP = 3,         /* k_gemm_bxp<G>: bf16 x6, packed weights from a scratch slot                       G = 1..7  */
+  TEMP_ROUTE_BX = 4,          /* k_gemm_bx<G, 0>: bf16 x6, the block splits B[k][n] itself                        G = 1..7  */
+  TEMP_ROUTE_BX_T = 5,        /* k_gemm_bx<G, 1>: the same for B stored [n][k]                                    G = 1..7  */
+  TEMP_ROUTE_HXP = 6,         /* k_gemm_hxp<G>: f16 x3, slab-staged                                               G = 1..7  */
+  TEMP_ROUTE_BXR = 7,         /* k_gemm_bxr: bf16 x6, weights resident                                            width 0   */
+  TEMP_ROUTE_HXR = 8,         /* k_gemm_hxr: f16 x3, weights resident                                             width 0   */
+  TEMP_ROUTE_KSLICE = 9,      /* temp_linear_multi: k-slices of k_gemm_panel<1> + one reduction (K >= 4096)       width 0   */
+  TEMP_ROUTE_LINEAR_T = 10,   /* temp_linear_multi: C^T = B . A^T on k_gemm_bxr (trans_b, N >= 2048); its launch also counts
+                                 as TEMP_ROUTE_BXR                                                                width 0   */
+  TEMP_ROUTE_TN_W7 = 11,      /* k_gemm_tn<NT, 7, 1>: fp32 weight gradient, 7-wave blocks                   NT = 1, 2, 4, 7 */
+  TEMP_ROUTE_TN_W8 = 12,      /* k_gemm_tn<NT, 8, 1>                                                        NT = 1, 2, 4, 7 */
+  TEMP_ROUTE_TN_SPLIT = 13,   /* k_gemm_tn<7, 8, 2>: 4 row tiles x (4 + 3) column tiles (TEMP_OPT_TN_SPLIT)        NT = 7   */
+  TEMP_ROUTE_COUNT = 14
+};
+long long temp_gemm_route_launches(int route, int width);
 /* Development only: a device buffer of `words` int64 into which instrumented kernels write cycle-counter stamps (NULL: off).
  * Not used by the product path or the tests. */
 void temp_set_debug_buffer(void* device_ptr, size_t words);

@@ -661,6 +661,7 @@ static inline bool bx_pack_batch(const PanelBatch<Epi>& batch, int count, const 
 template <int G, class Epi>
 static inline void launch_bx_g(int kid, const PanelBatch<Epi>& batch, int count, const BxGeom& g, hipStream_t st, const BxPacked* pk) {
   dim3 grid(8 * g.per_xcd * g.n_groups, count);
+  gemm_route_count(pk ? TEMP_ROUTE_BXP : (g.trans_b ? TEMP_ROUTE_BX_T : TEMP_ROUTE_BX), G);
   if (pk) {
     TEMP_LAUNCH(kid, (k_gemm_bxp<G, Epi>), grid, dim3(BX_THREADS), 0, st, batch, g, *pk);
     return;
@@ -688,6 +689,7 @@ static inline bool launch_bxr(int kid, const PanelBatch<Epi>& batch, int count, 
   static const bool granted = hipFuncSetAttribute(reinterpret_cast<const void*>(k_gemm_bxr<Epi>), hipFuncAttributeMaxDynamicSharedMemorySize, BXR_LDS_BYTES) == hipSuccess;
   if (!granted) { (void)hipGetLastError(); return false; }
   const size_t lds = (size_t)rg.n_slabs * BXR_G * 192 * 16 + BXR_BIAS_BYTES;
+  gemm_route_count(TEMP_ROUTE_BXR, 0);
   TEMP_LAUNCH(kid, (k_gemm_bxr<Epi>), dim3(256, count), dim3(BXR_WAVES * 64), lds, st, batch, rg, pk);
   return true;
 }

@@ -314,6 +314,7 @@ static inline bool hx_fill_keys(PanelBatch<Epi>& batch, int count, int K, int ld
 template <int G, class Epi>
 static inline void launch_hxp_g(int kid, const PanelBatch<Epi>& batch, int count, const BxGeom& g, hipStream_t st, const HxPacked& pk, int keys_by_out) {
   dim3 grid(8 * g.per_xcd * g.n_groups, count);
+  gemm_route_count(TEMP_ROUTE_HXP, G);
   TEMP_LAUNCH(kid, (k_gemm_hxp<G, Epi>), grid, dim3(BX_THREADS), 0, st, batch, g, pk, keys_by_out);
 }
 
@@ -388,6 +389,7 @@ static inline bool launch_hxr(int kid, const PanelBatch<Epi>& batch_in, int coun
     for (int i = 0; i < count; ++i) if (batch.p[i].M > 0) { for (int j = 0; j < PANEL_MAXP; ++j) if (!batch.p[j].a_keys) batch.p[j].a_keys = batch.p[i].a_keys; break; }
   }
   const size_t lds = (size_t)rg.n_slabs * BXR_G * 128 * 16 + 3 * BXR_BIAS_BYTES;
+  gemm_route_count(TEMP_ROUTE_HXR, 0);
   TEMP_LAUNCH(kid, (k_gemm_hxr<Epi>), dim3(256, count), dim3(BXR_WAVES * 64), lds, st, batch, rg, kbo);
   hx_count();
   return true;

@@ -377,9 +377,11 @@ static void launch_tn(const TnCfg& c, int M, int Ka, int Nb, const float* A, int
                       float* bpart, hipStream_t st) {
   dim3 grid(c.kab, c.nbb, c.slices);
   if (c.split == 2) {
+    if constexpr (NT == 7) gemm_route_count(TEMP_ROUTE_TN_SPLIT, 7);
     if constexpr (NT == 7) TEMP_LAUNCH(K_GEMM_TN, (k_gemm_tn<7, 8, 2>), grid, dim3(8 * 64), 0, st, M, Ka, Nb, A, lda, B, ldb, rps, 0, part, bpart);
     return;
   }
+  gemm_route_count(c.wpb == 7 ? TEMP_ROUTE_TN_W7 : TEMP_ROUTE_TN_W8, NT);
   if (c.wpb == 7) TEMP_LAUNCH(K_GEMM_TN, (k_gemm_tn<NT, 7>), grid, dim3(7 * 64), 0, st, M, Ka, Nb, A, lda, B, ldb, rps, 0, part, bpart);
   else TEMP_LAUNCH(K_GEMM_TN, (k_gemm_tn<NT, 8>), grid, dim3(8 * 64), 0, st, M, Ka, Nb, A, lda, B, ldb, rps, 0, part, bpart);
 }
@@ -799,6 +801,7 @@ int temp_linear_multi(int count, const TempLinearProblem* probs, int N, int K, i
                                                     EpiPartialStore{part[i], ldc, adjacent ? (size_t)rows * ldc : (size_t)M * ldc, kc, ntiles}};
             off += adjacent ? (size_t)M * ldc : (size_t)S * M * ldc;
           }
+          gemm_route_count(TEMP_ROUTE_KSLICE, 0);
           TEMP_LAUNCH(K_GEMM_LINEAR, (k_gemm_panel<1, EpiPartialStore>), dim3(ceil_div(max_m, 128), ntiles * S, n), dim3(256), 0,
                       (hipStream_t)stream, pb, N, K, lda, ldb, trans_b, 0);
           if (adjacent) {
@@ -831,6 +834,7 @@ int temp_linear_multi(int count, const TempLinearProblem* probs, int N, int K, i
           tb.p[i] = PanelProblem<EpiPlainStoreT>{i < n ? N : 0, q.B, nullptr, q.A, EpiPlainStoreT{q.C, ldc, q.M}};
         }
         if (launch_bxr(K_GEMM_LINEAR, tb, n, bg, (hipStream_t)stream, nullptr)) {
+          gemm_route_count(TEMP_ROUTE_LINEAR_T, 0);
           if (launch_status() != TEMP_OK) return TEMP_E_LAUNCH;
           continue;
         }

@@ -203,6 +203,7 @@ template <int NT, class Epi>
 static inline void launch_panel_nt(int kid, const PanelBatch<Epi>& batch, int count, int max_m, int N, int K, int lda, int ldb, int trans_b,
                                    int n_base, int col_blocks, hipStream_t st) {
   dim3 grid(ceil_div(max_m, 128), col_blocks, count);
+  gemm_route_count(TEMP_ROUTE_PANEL, NT);
   TEMP_LAUNCH(kid, (k_gemm_panel<NT, Epi>), grid, dim3(256), 0, st, batch, N, K, lda, ldb, trans_b, n_base);
 }
 

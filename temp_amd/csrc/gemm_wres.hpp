@@ -102,12 +102,16 @@ __global__ void __launch_bounds__(256, 2) k_gemm_wres(PanelBatch<Epi> batch, int
   const int nch = g.kpad / (8 * QC);
 
   if constexpr (VAR & 8) batch.p[0].epi.stamp(0, __builtin_amdgcn_s_memtime());
+  // the B whose slice is in LDS: the one this block STAGED last (not the previous problem's -- that one may have been empty and
+  // skipped: [M = 0, B0], [M > 0, B0] must still stage B0, and [B0], [M = 0, B1], [B1] must replace B0)
+  const float* staged = nullptr;
   for (int z = 0; z < count; ++z) {
     const PanelProblem<Epi>& pb = batch.p[z];
     const int M = pb.M;
     if (M <= 0 || (zsel >= 0 && z != zsel)) continue;
-    if (zsel >= 0 || z == 0 || pb.B != batch.p[z - 1].B) {
-      if (zsel < 0 && z > 0) __syncthreads();
+    if (pb.B != staged) {
+      if (staged) __syncthreads();                               // every wave is done with the slice that is being replaced
+      staged = pb.B;
       // ---- prologue: this block's slice of B -> LDS as [col][k] (k contiguous), zero padded.
       // Loads are issued in batches of WRES_PRO per thread (a 96 x 200 slice = 19 float4 per thread: ONE batch, i.e. one
       // memory round trip) before the first LDS store of the batch.
@@ -313,6 +317,7 @@ int launch_wres_one(int kid, const PanelBatch<Epi>& batch, int count, const Wres
   for (int i = 0; i < count; ++i) max_m = batch.p[i].M > max_m ? batch.p[i].M : max_m;
   const int need = ceil_div(ceil_div(ceil_div(max_m, 32), 8), 4);
   if (bps > need) bps = need < 1 ? 1 : need;
+  gemm_route_count(g.split ? TEMP_ROUTE_WRES_SPLIT : TEMP_ROUTE_WRES, NTS);
   TEMP_LAUNCH(kid, (k_gemm_wres<NTS, Epi>), dim3(roles * bps * 8), dim3(256), lds, st, batch, count, g, bps);
   return launch_status();
 }
@@ -324,8 +329,23 @@ int launch_gemm_wres(int kid, const PanelBatch<Epi>& batch, int count, const Wre
   return launch_wres_one<1, Epi>(kid, batch, count, g, st);
 }
 
-// Dispatcher used by every call site: weights-resident kernel when the shape allows, else the
-// streaming row-panel kernel.  temp_set_option(TEMP_OPT_GEMM_STREAM, 1) forces the latter (A/B runs).
+// Dispatcher used by every call site.  With rows = the sum of M over the launch's problems it takes the first route that applies
+// (every launch site counts itself: temp_gemm_route_launches, TEMP_ROUTE_* of include/temp_amd.h; tests/gemm_route_cases.py pins
+// each line below):
+//   rows >= 16384 (BX_MIN_ROWS), K % 8 == 0, K >= 16, N % 4 == 0, TEMP_OPT_MFMA_BF16X3 = 1, plain (non-grouped) epilogue:
+//     k_gemm_hxr            f16 x3, weights resident   72 <= K <= 208, N <= 1024, and row keys given, or N >= 512 (16 tiles), or
+//                                                      K >= 400 (hx_supported: otherwise the key pass over A costs more than it saves)
+//     k_gemm_bxr            bf16 x6, weights resident  the same K and N range, the rest (TEMP_OPT_GEMM_RESIDENT = 1; not the dropout
+//                                                      epilogue)
+//     k_gemm_hxp<G=1..7>    f16 x3, slab-staged        hx_supported as above; also K % 8 == 4 (the only split kernel that takes it)
+//     k_gemm_bxp<G=1..7>    bf16 x6, packed weights in a scratch slot
+//     k_gemm_bx<G,trans_b>  bf16 x6, the block splits B itself (pack over 3 MB, or no slot)
+//     G = tiles per column group, by bx_plan's cost estimate; the last group is shifted left when G does not divide the tiles
+//   rows >= 4096 (WRES_MIN_ROWS), K >= 8, at most 16 slices, a slice fits 80 KB, TEMP_OPT_GEMM_STREAM = 0:
+//     k_gemm_wres<NTS=1..3> fp32 MFMA, weights resident; `split` (a block serves one problem) when consecutive problems' B all differ
+//   otherwise:
+//     k_gemm_panel<NT=1..4> fp32 MFMA row panels: a `full` launch of NT = 4 / 2 / 1 plus a `rem` launch of the 1..3 tiles left over
+// temp_linear_multi tries two routes of its own first: k-slices + reduction (K >= 4096, N <= 256), transposed bxr (trans_b, N >= 2048).
 inline bool wres_disabled() { return option(TEMP_OPT_GEMM_STREAM) != 0; }
 
 template <class Epi>

@@ -98,6 +98,14 @@ int option(int key) { return (key >= 0 && key < TEMP_OPT_COUNT) ? g_options[key]
 static std::atomic<long long> g_hx_launches{0};
 void hx_count() { g_hx_launches.fetch_add(1, std::memory_order_relaxed); }
 long long hx_launches() { return g_hx_launches.load(std::memory_order_relaxed); }
+static std::atomic<long long> g_gemm_routes[TEMP_ROUTE_COUNT][8];       // (static storage: zero)
+void gemm_route_count(int route, int width) {
+  if (route >= 0 && route < TEMP_ROUTE_COUNT && width >= 0 && width < 8) g_gemm_routes[route][width].fetch_add(1, std::memory_order_relaxed);
+}
+long long gemm_route_launches(int route, int width) {
+  if (route < 0 || route >= TEMP_ROUTE_COUNT || width < 0 || width >= 8) return -1;
+  return g_gemm_routes[route][width].load(std::memory_order_relaxed);
+}
 }  // namespace temp
 
 extern "C" {
@@ -123,6 +131,7 @@ int temp_set_option(int key, int value) {
 }
 int temp_get_option(int key) { return temp::option(key); }
 long long temp_f16_launches(void) { return temp::hx_launches(); }
+long long temp_gemm_route_launches(int route, int width) { return temp::gemm_route_launches(route, width); }
 
 const char* temp_error_string(int code) {
   switch (code) {

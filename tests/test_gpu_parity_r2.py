@@ -702,7 +702,12 @@ def _wide(shape, seed, scale):
 ])
 def test_split_operand_gemm_vs_fp64(M, K, N, trans_b):
     """The error of the split-operand product against fp64 stays at the level of ONE fp32 rounding per product (the fp32 MFMA
-    kernels measure 4e-7 of sum |a||b| on the same data, tools/bx_probe.hip); bar 1e-6."""
+    kernels measure 4e-7 of sum |a||b| on the same data, tools/bx_probe.hip); bar 1e-6.
+
+    The shapes were chosen for the bf16 kernels; since the f16 split became the default (TEMP_OPT_MFMA_F16X2 = 1) they take, with
+    no caller keys (temp_gemm_route_launches): 20000x200x600 k_gemm_hxr (N >= 512), 20000x600x200 k_gemm_hxp<3> (K >= 400),
+    16500x200x7128 k_gemm_bx<G,1> (no pack fits 3 MB), 17000x64x40 and 16384x24x36 k_gemm_bxp<1>, 33333x208x132 k_gemm_bxr.  Every
+    route and width has its own case, over all elements, in tests/test_gpu_gemm_routes.py."""
     be = TB.get_backend()
     a = _wide((M, K), 11, 1.0)
     b = _wide((N, K) if trans_b else (K, N), 12, 0.2)
