@@ -139,6 +139,44 @@ enum {
   TEMP_ROUTE_COUNT = 14
 };
 long long temp_gemm_route_launches(int route, int width);
+/* Diagnostic: which edge kernel ran.  Every launch site of the RGCN edge-kernel dispatcher (csrc/rgcn_kernels.hip: launch_agg_tile,
+ * launch_agg, run_agg, launch_dw_tile, launch_dw_hybrid, run_dw, launch_fixup -- behind temp_rgcn_fwd / _bwd / _bwd_dh /
+ * _bwd_weights / _table_fwd / _table_bwd; the pair route's own kernels are not counted, its k_fixup launch is) adds one to the
+ * cell [route][s] when it launches its kernel; the trace names all of them k_rgcn_agg<...> / k_rgcn_dw / k_fixup.  `s` is the block
+ * size of the relation weights the kernel is instantiated for (1, 2 or 4), 0 for the routes that have none (generic, fix-up).
+ * temp_rgcn_route_launches returns the launches so far in this process, -1 for a route or s outside the table. */
+enum {
+  /* aggregation (MODE_FWD, by-dst view) */
+  TEMP_RGCN_FWD_TILE8 = 0,        /* k_rgcn_agg_t<S, FWD, unsigned char>: member rows in LDS, n_rel_rows <= 256        s = 1, 2, 4 */
+  TEMP_RGCN_FWD_TILE16 = 1,       /* k_rgcn_agg_t<S, FWD, unsigned short>: the same, 16-bit relation ids               s = 1, 2, 4 */
+  TEMP_RGCN_FWD_LDS_SCALAR = 2,   /* k_rgcn_agg_s<S, FWD, true>: relation table in LDS, per-edge scalars (D > 128)     s = 1, 2, 4 */
+  TEMP_RGCN_FWD_LDS_PERMUTE = 3,  /* k_rgcn_agg<S, FWD, true>: relation table in LDS, lane groups                      s = 1, 2, 4 */
+  TEMP_RGCN_FWD_SCALAR = 4,       /* k_rgcn_agg_s<S, FWD, false>: weights through L2 (D > 128)                         s = 1, 2, 4 */
+  TEMP_RGCN_FWD_PERMUTE = 5,      /* k_rgcn_agg<S, FWD, false>                                                         s = 1, 2, 4 */
+  TEMP_RGCN_FWD_GENERIC = 6,      /* k_rgcn_agg_generic<FWD>: any si, so                                               s = 0       */
+  /* d/dh (MODE_DX, by-src view): the same kernels, transposed blocks */
+  TEMP_RGCN_DX_TILE8 = 7,
+  TEMP_RGCN_DX_TILE16 = 8,
+  TEMP_RGCN_DX_LDS_SCALAR = 9,
+  TEMP_RGCN_DX_LDS_PERMUTE = 10,
+  TEMP_RGCN_DX_SCALAR = 11,       /* k_rgcn_agg_s<S, DX, false>: only for a table beyond 64 KB (relation runs)                     */
+  TEMP_RGCN_DX_PERMUTE = 12,
+  TEMP_RGCN_DX_GENERIC = 13,
+  /* weight gradient (by-rel view) */
+  TEMP_RGCN_DW_HYBRID = 14,       /* k_rgcn_dw_h<S>: gradient rows in LDS, x rows through L2 (TEMP_OPT_RGCN_TILE = 3)  s = 1, 2, 4 */
+  TEMP_RGCN_DW_TILE = 15,         /* k_rgcn_dw_t<S>: both row sets in LDS (TEMP_OPT_RGCN_TILE = 2)                     s = 1, 2, 4 */
+  TEMP_RGCN_DW_SCALAR = 16,       /* k_rgcn_dw_s<S> (D > 128)                                                          s = 1, 2, 4 */
+  TEMP_RGCN_DW_PERMUTE = 17,      /* k_rgcn_dw<S>                                                                      s = 1, 2, 4 */
+  TEMP_RGCN_DW_GENERIC = 18,      /* k_rgcn_dw_generic                                                                 s = 0       */
+  /* fix-up of the segments that span several chunks (any view) */
+  TEMP_RGCN_FIX_FEW = 19,         /* k_fixup<16, 1, 32>: at most 1 024 (entry, column block) items                     s = 0       */
+  TEMP_RGCN_FIX_MANY = 20,        /* k_fixup<4, 4, 256>                                                                s = 0       */
+  TEMP_RGCN_FIX_FEW_SPLIT = 21,   /* k_fixup<16, 1, 32, true>: views of 32 768 and more partial rows                   s = 0       */
+  TEMP_RGCN_FIX_MANY_SPLIT = 22,  /* k_fixup<4, 4, 256, true>                                                          s = 0       */
+  TEMP_RGCN_FIX_SPLIT2 = 23,      /* k_fixup_split: second level behind either split launch                            s = 0       */
+  TEMP_RGCN_ROUTE_COUNT = 24
+};
+long long temp_rgcn_route_launches(int route, int s);
 /* Development only: a device buffer of `words` int64 into which instrumented kernels write cycle-counter stamps (NULL: off).
  * Not used by the product path or the tests. */
 void temp_set_debug_buffer(void* device_ptr, size_t words);

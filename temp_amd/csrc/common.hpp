@@ -117,6 +117,7 @@ __device__ __forceinline__ float4 drop4(const DropSpec& d, unsigned row, unsigne
 int option(int key);
 void hx_count();                            // diagnostic counter of f16-split kernel launches (temp_f16_launches)
 void gemm_route_count(int route, int width);   // diagnostic: one launch of dense-product kernel TEMP_ROUTE_* <width> (temp_gemm_route_launches)
+void rgcn_route_count(int route, int s);       // diagnostic: one launch of edge kernel TEMP_RGCN_* <s> (temp_rgcn_route_launches)
 
 inline int ceil_div(long long a, long long b) { return (int)((a + b - 1) / b); }
 inline size_t align_up(size_t x, size_t a) { return (x + a - 1) / a * a; }

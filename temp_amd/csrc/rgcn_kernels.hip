@@ -684,16 +684,18 @@ static bool launch_agg_tile(const TempEdgeView& v, const TileArgs& t, const floa
   const int grid = 8 * ceil_div(t.n_members, 8) * t.n_slices;
   TileArgs tp = t;
   if (g_debug_words.load() >= (size_t)grid * 8) tp.prof = g_debug_buf.load();
+  const int route = (MODE == MODE_FWD ? TEMP_RGCN_FWD_TILE8 : TEMP_RGCN_DX_TILE8) + (sizeof(BT) == 1 ? 0 : 1);
   if constexpr (S == 2 && MODE == MODE_FWD && sizeof(BT) == 1) {          // development ablations (TEMP_OPT_DEBUG), never set by the product
     const int var = option(TEMP_OPT_DEBUG);
 #define TILE_VAR(V) if (var == V) { static const bool ok = tile_grant_lds(k_rgcn_agg_t<S, MODE, BT, V>, TILE_LDS_MAX); (void)ok; \
-    TEMP_LAUNCH(K_RGCN_AGG_FWD, (k_rgcn_agg_t<S, MODE, BT, V>), dim3(grid), dim3(TILE_THREADS), t.lds_bytes, st, v, tp, feat, ldf, ids, W, n_rel_rows, nnorm, D, out, partial); return true; }
+    TEMP_LAUNCH(K_RGCN_AGG_FWD, (k_rgcn_agg_t<S, MODE, BT, V>), dim3(grid), dim3(TILE_THREADS), t.lds_bytes, st, v, tp, feat, ldf, ids, W, n_rel_rows, nnorm, D, out, partial); rgcn_route_count(route, S); return true; }
     TILE_VAR(1) TILE_VAR(2) TILE_VAR(3) TILE_VAR(4) TILE_VAR(7) TILE_VAR(8)
 #undef TILE_VAR
   }
   TEMP_LAUNCH((MODE == MODE_FWD ? K_RGCN_AGG_FWD : K_RGCN_AGG_DX), (k_rgcn_agg_t<S, MODE, BT>), dim3(grid), dim3(TILE_THREADS), t.lds_bytes, st, v, tp, feat, ldf, ids,
               W, n_rel_rows, nnorm, D, out, partial);
   g_tile_launches.fetch_add(1, std::memory_order_relaxed);
+  rgcn_route_count(route, S);
   return true;
 }
 
@@ -712,24 +714,30 @@ static bool launch_agg(const TempEdgeView& v, const TempMembers* mb, int view, c
   if (wbytes <= 65536 && v.n_chunks >= 4096) {
     // whole relation table in LDS; 1024-thread persistent blocks, 2 per CU (2 x 64 KB of 160 KB)
     const int grid = 512;
-    if (lpr == 64 && !rgcn_scalar_off())
+    if (lpr == 64 && !rgcn_scalar_off()) {
       TEMP_LAUNCH((MODE == MODE_FWD ? K_RGCN_AGG_FWD : K_RGCN_AGG_DX), (k_rgcn_agg_s<S, MODE, true>), dim3(grid), dim3(1024), wbytes, st, v, feat, ldf, ids, W, n_rel_rows,
                   nnorm, D, out, partial);
-    else
+      rgcn_route_count(MODE == MODE_FWD ? TEMP_RGCN_FWD_LDS_SCALAR : TEMP_RGCN_DX_LDS_SCALAR, S);
+    } else {
       TEMP_LAUNCH((MODE == MODE_FWD ? K_RGCN_AGG_FWD : K_RGCN_AGG_DX), (k_rgcn_agg<S, MODE, true>), dim3(grid), dim3(1024), wbytes, st, v, feat, ldf, ids, W, n_rel_rows, nnorm, D,
                        lpr, out, partial);
+      rgcn_route_count(MODE == MODE_FWD ? TEMP_RGCN_FWD_LDS_PERMUTE : TEMP_RGCN_DX_LDS_PERMUTE, S);
+    }
   } else {
     int grid = (v.n_chunks + 3) / 4;
     grid = grid < 8 ? 8 : (grid > 2048 ? 2048 : (grid + 7) / 8 * 8);
     // (measured on the S-hbm shape before the relation runs: the forward gains 3 %, d/dh loses 14 %: 3.32 against 2.91 ms; with a
     // table beyond LDS the scalar kernel walks relation runs, which the generic one cannot: TEMP_OPT_DEBUG 101 keeps d/dh generic)
     const bool runs = wbytes > 65536 && option(TEMP_OPT_DEBUG) != 101;
-    if (lpr == 64 && (MODE == MODE_FWD || runs) && !rgcn_scalar_off())
+    if (lpr == 64 && (MODE == MODE_FWD || runs) && !rgcn_scalar_off()) {
       TEMP_LAUNCH((MODE == MODE_FWD ? K_RGCN_AGG_FWD : K_RGCN_AGG_DX), (k_rgcn_agg_s<S, MODE, false>), dim3(grid), dim3(256), 0, st, v, feat, ldf, ids, W, n_rel_rows, nnorm, D,
                   out, partial);
-    else
+      rgcn_route_count(MODE == MODE_FWD ? TEMP_RGCN_FWD_SCALAR : TEMP_RGCN_DX_SCALAR, S);
+    } else {
       TEMP_LAUNCH((MODE == MODE_FWD ? K_RGCN_AGG_FWD : K_RGCN_AGG_DX), (k_rgcn_agg<S, MODE, false>), dim3(grid), dim3(256), 0, st, v, feat, ldf, ids, W, n_rel_rows, nnorm, D, lpr,
                        out, partial);
+      rgcn_route_count(MODE == MODE_FWD ? TEMP_RGCN_FWD_PERMUTE : TEMP_RGCN_DX_PERMUTE, S);
+    }
   }
   return false;
 }
@@ -753,14 +761,17 @@ static void launch_fixup(const TempEdgeView& v, const float* partial, int width,
   if (items <= 1024) {                                          // few entries: one 16-wave block each
     if (split) TEMP_LAUNCH(K_FIXUP, (k_fixup<16, 1, 32, true>), dim3((int)items), dim3(16 * 64), 0, st, v.n_fix, v.fix_seg, v.fix_slot, v.fix_cnt, partial, width, out, ctl, huge);
     else TEMP_LAUNCH(K_FIXUP, (k_fixup<16, 1, 32>), dim3((int)items), dim3(16 * 64), 0, st, v.n_fix, v.fix_seg, v.fix_slot, v.fix_cnt, partial, width, out, ctl, huge);
+    rgcn_route_count(split ? TEMP_RGCN_FIX_FEW_SPLIT : TEMP_RGCN_FIX_FEW, 0);
   } else {
     const long long blocks = (items + 3) / 4;
     int grid = (int)(blocks > 4096 ? 4096 : blocks);
     if (split) TEMP_LAUNCH(K_FIXUP, (k_fixup<4, 4, 256, true>), dim3(grid), dim3(4 * 64), 0, st, v.n_fix, v.fix_seg, v.fix_slot, v.fix_cnt, partial, width, out, ctl, huge);
     else TEMP_LAUNCH(K_FIXUP, (k_fixup<4, 4, 256>), dim3(grid), dim3(4 * 64), 0, st, v.n_fix, v.fix_seg, v.fix_slot, v.fix_cnt, partial, width, out, ctl, huge);
+    rgcn_route_count(split ? TEMP_RGCN_FIX_MANY_SPLIT : TEMP_RGCN_FIX_MANY, 0);
   }
   if (split) {
     TEMP_LAUNCH(K_FIXUP, k_fixup_split, dim3(1024), dim3(256), 0, st, v.fix_seg, v.fix_slot, v.fix_cnt, partial, width, out, ctl, cap, scratch);
+    rgcn_route_count(TEMP_RGCN_FIX_SPLIT2, 0);
   }
 }
 
@@ -787,6 +798,7 @@ static int run_agg(int mode, const TempEdgeView& v, const TempMembers* mb, const
     else
       TEMP_LAUNCH(K_RGCN_AGG_DX, (k_rgcn_agg_generic<MODE_DX>), dim3(grid), dim3(256), 0, st, v, feat, ldf, ids, W, nnorm, d_in, d_out, si, so,
                          out, partial);
+    rgcn_route_count(mode == MODE_FWD ? TEMP_RGCN_FWD_GENERIC : TEMP_RGCN_DX_GENERIC, 0);
   }
   if (!fixed) launch_fixup(v, partial, wres, out, st);
   return launch_status();
@@ -800,6 +812,7 @@ static bool launch_dw_tile(const TempEdgeView& v, const TileArgs& t, const float
   const int grid = 8 * ceil_div(t.n_members, 8) * t.n_slices;
   TEMP_LAUNCH(K_RGCN_DW, (k_rgcn_dw_t<S>), dim3(grid), dim3(TILE_THREADS), t.lds_bytes, st, v, t, x, x_ids, dz, nnorm, D, dW, partial);
   g_tile_launches.fetch_add(1, std::memory_order_relaxed);
+  rgcn_route_count(TEMP_RGCN_DW_TILE, S);
   return true;
 }
 
@@ -811,6 +824,7 @@ static bool launch_dw_hybrid(const TempEdgeView& v, const TileArgs& t, const flo
   const int grid = 8 * ceil_div(t.n_members, 8) * t.n_slices;
   TEMP_LAUNCH(K_RGCN_DW, (k_rgcn_dw_h<S>), dim3(grid), dim3(TILE_THREADS), t.lds_bytes, st, v, t, x, x_ids, dz, nnorm, D, dW, partial);
   g_tile_launches.fetch_add(1, std::memory_order_relaxed);
+  rgcn_route_count(TEMP_RGCN_DW_HYBRID, S);
   return true;
 }
 
@@ -844,13 +858,18 @@ static int run_dw(const TempEdgeView& v, const TempMembers* mb, const float* x, 
       if (S == 1) TEMP_LAUNCH(K_RGCN_DW, (k_rgcn_dw_s<1>), dim3(grid), dim3(256), 0, st, v, x, x_ids, dz, nnorm, d_in, dW, partial);
       else if (S == 2) TEMP_LAUNCH(K_RGCN_DW, (k_rgcn_dw_s<2>), dim3(grid), dim3(256), 0, st, v, x, x_ids, dz, nnorm, d_in, dW, partial);
       else TEMP_LAUNCH(K_RGCN_DW, (k_rgcn_dw_s<4>), dim3(grid), dim3(256), 0, st, v, x, x_ids, dz, nnorm, d_in, dW, partial);
-    } else if (S == 1) TEMP_LAUNCH(K_RGCN_DW, (k_rgcn_dw<1>), dim3(grid), dim3(256), 0, st, v, x, x_ids, dz, nnorm, d_in, lpr, dW, partial);
-    else if (S == 2) TEMP_LAUNCH(K_RGCN_DW, (k_rgcn_dw<2>), dim3(grid), dim3(256), 0, st, v, x, x_ids, dz, nnorm, d_in, lpr, dW, partial);
-    else TEMP_LAUNCH(K_RGCN_DW, (k_rgcn_dw<4>), dim3(grid), dim3(256), 0, st, v, x, x_ids, dz, nnorm, d_in, lpr, dW, partial);
+      rgcn_route_count(TEMP_RGCN_DW_SCALAR, S);
+    } else {
+      if (S == 1) TEMP_LAUNCH(K_RGCN_DW, (k_rgcn_dw<1>), dim3(grid), dim3(256), 0, st, v, x, x_ids, dz, nnorm, d_in, lpr, dW, partial);
+      else if (S == 2) TEMP_LAUNCH(K_RGCN_DW, (k_rgcn_dw<2>), dim3(grid), dim3(256), 0, st, v, x, x_ids, dz, nnorm, d_in, lpr, dW, partial);
+      else TEMP_LAUNCH(K_RGCN_DW, (k_rgcn_dw<4>), dim3(grid), dim3(256), 0, st, v, x, x_ids, dz, nnorm, d_in, lpr, dW, partial);
+      rgcn_route_count(TEMP_RGCN_DW_PERMUTE, S);
+    }
   } else {
     int grid = (v.n_chunks + 3) / 4;
     if (grid > 4096) grid = 4096;
     TEMP_LAUNCH(K_RGCN_DW, k_rgcn_dw_generic, dim3(grid), dim3(256), 0, st, v, x, x_ids, dz, nnorm, d_in, d_out, si, so, dW, partial);
+    rgcn_route_count(TEMP_RGCN_DW_GENERIC, 0);
   }
   launch_fixup(v, partial, (int)wrow, dW, st);
   return launch_status();

@@ -106,6 +106,14 @@ long long gemm_route_launches(int route, int width) {
   if (route < 0 || route >= TEMP_ROUTE_COUNT || width < 0 || width >= 8) return -1;
   return g_gemm_routes[route][width].load(std::memory_order_relaxed);
 }
+static std::atomic<long long> g_rgcn_routes[TEMP_RGCN_ROUTE_COUNT][5];  // (static storage: zero)
+void rgcn_route_count(int route, int s) {
+  if (route >= 0 && route < TEMP_RGCN_ROUTE_COUNT && s >= 0 && s < 5) g_rgcn_routes[route][s].fetch_add(1, std::memory_order_relaxed);
+}
+long long rgcn_route_launches(int route, int s) {
+  if (route < 0 || route >= TEMP_RGCN_ROUTE_COUNT || s < 0 || s >= 5) return -1;
+  return g_rgcn_routes[route][s].load(std::memory_order_relaxed);
+}
 }  // namespace temp
 
 extern "C" {
@@ -132,6 +140,7 @@ int temp_set_option(int key, int value) {
 int temp_get_option(int key) { return temp::option(key); }
 long long temp_f16_launches(void) { return temp::hx_launches(); }
 long long temp_gemm_route_launches(int route, int width) { return temp::gemm_route_launches(route, width); }
+long long temp_rgcn_route_launches(int route, int s) { return temp::rgcn_route_launches(route, s); }
 
 const char* temp_error_string(int code) {
   switch (code) {

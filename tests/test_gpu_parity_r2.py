@@ -1005,14 +1005,24 @@ def test_split_fixup_large_hubs_gpu(hip_backend):
         torch.cuda.synchronize()
         return [out] + [x for x in grads if x is not None]
 
+    from tests import rgcn_route_cases as RC
+    split_routes = [RC.ROUTES.index(r) for r in ("fix_few_split", "fix_many_split", "fix_split2")]
+    counts = lambda: [lib.temp_rgcn_route_launches(r, 0) for r in split_routes]
     prev = lib.temp_set_option(_lib.OPT_DEBUG, 0)
     try:
+        n0 = counts()
         a = run()
         b = run()
+        n1 = counts()
         lib.temp_set_option(_lib.OPT_DEBUG, 100)
         c = run()
+        n2 = counts()
     finally:
         lib.temp_set_option(_lib.OPT_DEBUG, prev)
+    # every fix-up of the two runs took a split first level (few or many entries) and the second level behind it
+    first, second = (n1[0] - n0[0]) + (n1[1] - n0[1]), n1[2] - n0[2]
+    assert first > 0 and second == first, ("split fix-up launches", n0, n1)
+    assert n2 == n1, ("TEMP_OPT_DEBUG = 100 still launched the split fix-up", n1, n2)
     for i, (x, y, z) in enumerate(zip(a, b, c)):
         assert torch.isfinite(x).all()
         assert torch.equal(x, y), ("split fix-up not repeatable", i)
