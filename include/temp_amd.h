@@ -725,19 +725,54 @@ int temp_gather_ce_bwd(int P, int C, int N, const float* scores, const int32_t* 
                        float inv_rows, const float* row_scale /* nullable [P]: per-row weight instead of inv_rows */, float* d_scores, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
- * Folded query of the bilinear scorers, row gathers fused in (utils/scores.py:4-12 distmult, :26-44 complex;
+ * Folded query of the scorers, row gathers fused in (utils/scores.py:4-12 distmult, :26-44 complex, :46-55 transE;
  * the s / r / o row selections of train_link_prediction, models/TKG_Module.py:202-213):
  *   k = ent_rows[known_idx[p]], r = rel[rel_idx[p]]          (both [*, d] row-major, d % 4 == 0; complex: d % 8 == 0)
- *   q[p] such that  score(p, candidate c) = <q[p], c>;  is_tail[p] != 0: k is the subject and candidates are
- *   objects (mode 'tail'), else k is the object and candidates are subjects (mode 'head'; ignored by distmult).
- *   bwd: per-row gradients d_known_rows[p], d_rel_rows[p] (the caller sums them over the index lists).
+ *   is_tail[p] != 0: k is the subject and candidates are objects (mode 'tail'), else k is the object and candidates are
+ *   subjects (mode 'head'; ignored by distmult).
+ *   distmult / complex: q[p] such that  score(p, candidate c) = <q[p], c>  (an inner-product query);
+ *   transE:             q[p] = k + r (tail) or k - r (head), a translation query:  score(p, c) = -|q[p] - c|_1.  One IEEE
+ *                       add / subtract per element, bit-equal to the tensor expression.
+ *   bwd: per-row gradients d_known_rows[p], d_rel_rows[p] (the caller sums them over the index lists); transE: d_q and +-d_q.
  * ---------------------------------------------------------------------------------------------- */
 #define TEMP_SCORE_DISTMULT 0
 #define TEMP_SCORE_COMPLEX 1
+#define TEMP_SCORE_TRANSE 2
 int temp_bilinear_query_fwd(int P, int d, int kind, const float* ent_rows, const int32_t* known_idx, const float* rel, const int32_t* rel_idx,
                             const int32_t* is_tail, float* q, void* stream);
 int temp_bilinear_query_bwd(int P, int d, int kind, const float* ent_rows, const int32_t* known_idx, const float* rel, const int32_t* rel_idx,
                             const int32_t* is_tail, const float* d_q, float* d_known_rows, float* d_rel_rows, void* stream);
+
+/* ------------------------------------------------------------------------------------------------
+ * TransE loss and scores (utils/scores.py:46-55 with the translation query q above):  score(p, c) = -sum_d |q[p,d] - c[d]|.
+ * Not bilinear, so no GEMM: the loss reads the score at the C = 1 + negative_rate candidates of every row only (a gather of
+ * P C d elements; the dense matrix is N / C times more), the ranking takes a dense VALU-tiled pass.
+ *
+ * temp_l1_ce_fwd: cross-entropy with label 0 over cand[P, C] (column 0 = the true entity):
+ *   s_out[p,k] = -sum_d |q[p,d] - table[base[p] + cand[p,k], d]|     (base NULL = 0.  One launch covers all windows of a batch:
+ *                table = the (B N, d) stack of the windows' all-entity matrices, base[p] = b N for a row of window b)
+ *   lse_rows[p] = logsumexp_k s_out[p,k];   loss_rows[p] = lse_rows[p] - s_out[p,0].      C == 1: loss exactly 0.
+ * temp_l1_ce_bwd_q:
+ *   g_out[p,k] = scale[0] * (row_scale ? row_scale[p] : inv_rows) * (exp(s[p,k] - lse_rows[p]) - [k == 0])   (as temp_gather_ce_bwd)
+ *   d_q[p,:]   = -sum_k g_out[p,k] sgn(q[p,:] - e_k),  sgn(0) = 0 (torch.abs's gradient), e_k the candidate's table row;
+ *                duplicate candidates each count, a weight-0 row gives zeros.
+ * temp_l1_ce_bwd_table: the candidate-side adjoint, without atomics:
+ *   slot[P C] = the flat positions p C + k sorted by their table row base[p] + cand[p,k], ascending within a row (a stable sort);
+ *   slot_ptr[n_rows + 1] = the CSR over table rows;
+ *   d_table[n,:] = sum_{i in [slot_ptr[n], slot_ptr[n+1])} g[slot[i]] sgn(q[slot[i] / C, :] - table[n,:]);  zeros for a row without slots.
+ * temp_l1_scores: scores[p,n] = -|q[p] - table[n]|_1 for n < N, -inf for N <= n < ld  ([P, ld]: feeds temp_filtered_rank directly).
+ *
+ * d % 4 == 0, P C < 2^31, ld % 4 == 0, else TEMP_E_UNSUPPORTED; P == 0 (n_rows == 0) returns success without a launch.  fp32,
+ * all outputs fully written, no workspace, no floating-point atomics; every sum has a fixed order: results are bit-repeatable.
+ * ---------------------------------------------------------------------------------------------- */
+int temp_l1_ce_fwd(int P, int C, int d, const float* q, const float* table, const int32_t* base /* nullable [P] */, const int32_t* cand,
+                   float* s_out, float* loss_rows, float* lse_rows, void* stream);
+int temp_l1_ce_bwd_q(int P, int C, int d, const float* q, const float* table, const int32_t* base /* nullable [P] */, const int32_t* cand,
+                     const float* s, const float* lse_rows, const float* scale /* device float */, float inv_rows,
+                     const float* row_scale /* nullable [P] */, float* g_out, float* d_q, void* stream);
+int temp_l1_ce_bwd_table(int n_rows, int d, int C, const float* q, const float* table, const int32_t* slot_ptr, const int32_t* slot,
+                         const float* g, float* d_table, void* stream);
+int temp_l1_scores(int P, int N, int d, const float* q, const float* table, int ld, float* scores, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
  * Gated loss of the post-aggregation models (PostDynamicRGCN / PostBiDynamicRGCN.train_link_prediction,
@@ -833,13 +868,15 @@ int temp_corrupt_sample(int R, int K, int N, uint64_t seed, const int32_t* truth
 /* ------------------------------------------------------------------------------------------------
  * Filtered ranking (EvaluationFilter.calc_metrics_single_graph / perturb_and_get_rank / sort_and_rank,
  * utils/evaluation.py:40-106).  scores [P, ld] = the P test triples scored against ALL N entities
- * (temp_linear with the folded query, trans_b = 1).  The reference overwrites the scores of the other
+ * (temp_linear with the folded query, trans_b = 1; temp_l1_scores for transE).  The reference overwrites the scores of the other
  * entities known to be true for the same (relation, known entity) with -10e6, applies a sigmoid and takes
  * the index of the target in a descending torch.sort.  Here:
  *   ranks[p] = 1 + #{ j : v_j > v_t  or  (v_j == v_t and j < target[p]) },
  *   v_j = sigmoid(scores[p,j]),  or 0 for j in the row's filter list  filt_ids[filt_ptr[p] .. filt_ptr[p+1])
  * (unique global ids; an entry equal to target[p] is ignored) -- the position in a STABLE descending order,
  * so exact sigmoid ties resolve by entity id where the reference's unstable sort leaves them arbitrary.
+ * (TransE scores are negative L1 distances: below about -104 the fp32 sigmoid underflows to 0, as in the reference, and those
+ * entities tie -- by entity id here.)
  * filt_ptr may be NULL (raw ranking); filt_ids may be NULL only when every list is empty.  ld % 4 == 0, ld >= N.  Integer output, deterministic.
  * ---------------------------------------------------------------------------------------------- */
 int temp_filtered_rank(int P, int N, int ld, const float* scores, const int32_t* target, const int32_t* filt_ptr,

@@ -715,6 +715,54 @@ class HipBackend:
         _lib.check(rc, "temp_bilinear_query_bwd")
         return dk, dr
 
+    # ---- TransE: candidate loss and dense scores over L1 distances (include/temp_amd.h: temp_l1_ce_fwd ...) ----
+    def l1_ce_fwd(self, q, table, base, cand):
+        """-> (s [P, C], loss_rows [P], lse [P]) of the candidate CE over s[p,k] = -|q[p] - table[base[p] + cand[p,k]]|_1 (base None = 0)."""
+        q, table, base, cand = _f32(q, "q"), _f32(table, "table"), _i32(base, "base"), _i32(cand, "cand")
+        P, d = q.shape
+        C = cand.shape[1]
+        s = torch.empty(P, C, dtype=torch.float32, device=q.device)
+        loss = torch.empty(P, dtype=torch.float32, device=q.device)
+        lse = torch.empty(P, dtype=torch.float32, device=q.device)
+        rc = self.lib.temp_l1_ce_fwd(P, C, d, _ptr(q), _ptr(table), _ptr(base), _ptr(cand), _ptr(s), _ptr(loss), _ptr(lse), _stream())
+        _lib.check(rc, "temp_l1_ce_fwd")
+        return s, loss, lse
+
+    def l1_ce_bwd_q(self, q, table, base, cand, s, lse, scale, inv_rows, row_scale=None):
+        """-> (g [P, C], d_q [P, d]): the softmax gradient at the candidates and the query side of its adjoint."""
+        q, table, base, cand = _f32(q, "q"), _f32(table, "table"), _i32(base, "base"), _i32(cand, "cand")
+        s, lse, scale, row_scale = _f32(s, "s"), _f32(lse, "lse"), _f32(scale, "scale"), _f32(row_scale, "row_scale")
+        P, d = q.shape
+        g = torch.empty_like(s)
+        d_q = torch.empty_like(q)
+        rc = self.lib.temp_l1_ce_bwd_q(P, cand.shape[1], d, _ptr(q), _ptr(table), _ptr(base), _ptr(cand), _ptr(s), _ptr(lse), _ptr(scale),
+                                       float(inv_rows), _ptr(row_scale), _ptr(g), _ptr(d_q), _stream())
+        _lib.check(rc, "temp_l1_ce_bwd_q")
+        return g, d_q
+
+    def l1_ce_bwd_table(self, q, table, slot_ptr, slot, g):
+        """-> d_table [rows, d]: the candidate side of the adjoint over the slot lists (functional.l1_slots)."""
+        q, table, g = _f32(q, "q"), _f32(table, "table"), _f32(g, "g")
+        slot_ptr, slot = _i32(slot_ptr, "slot_ptr"), _i32(slot, "slot")
+        n_rows, d = table.shape
+        if slot_ptr.shape[0] != n_rows + 1 or slot.numel() != g.numel():
+            raise ValueError("l1_ce_bwd_table: slot lists do not match the table / the candidate matrix")
+        d_table = torch.empty_like(table)
+        rc = self.lib.temp_l1_ce_bwd_table(n_rows, d, g.shape[1], _ptr(q), _ptr(table), _ptr(slot_ptr), _ptr(slot), _ptr(g), _ptr(d_table), _stream())
+        _lib.check(rc, "temp_l1_ce_bwd_table")
+        return d_table
+
+    def l1_scores(self, q, table):
+        """-> scores [P, ld], ld = N rounded up to a multiple of 4: -|q[p] - table[n]|_1, the pad columns -inf (what filtered_rank takes)."""
+        q, table = _f32(q, "q"), _f32(table, "table")
+        P, d = q.shape
+        N = table.shape[0]
+        ld = (N + 3) // 4 * 4
+        out = torch.empty(P, ld, dtype=torch.float32, device=q.device)
+        rc = self.lib.temp_l1_scores(P, N, d, _ptr(q), _ptr(table), ld, _ptr(out), _stream())
+        _lib.check(rc, "temp_l1_scores")
+        return out
+
     def gated_query_fwd(self, kind, a_rows, a_idx, b_rows, b_idx, w, rel, rel_idx, is_tail):
         """Folded query of the mixed known rows w * a_rows[a_idx] + (1 - w) * b_rows[b_idx] (a_idx < 0: b_rows[b_idx] alone)."""
         a_rows, b_rows, w, rel = _f32(a_rows, "a_rows"), _f32(b_rows, "b_rows"), _f32(w, "w"), _f32(rel, "rel")

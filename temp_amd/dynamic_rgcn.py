@@ -380,8 +380,9 @@ class DynamicRGCN(TKG_Module):
         """Host half of the fused loss, done with the rest of `prepare` (i.e. by the prefetch thread): positives, operand
         index lists, known-true slices for the device sampler, static inverses, all-entity row maps."""
         wb.loss_plan = None
+        name = self.args.score_function
         if not (self.plan_loss_in_prepare and getattr(self, "use_device_sampler", True) and self.fused_loss
-                and self.args.score_function in ("distmult", "complex")):
+                and (name in ("distmult", "complex") or (name == "transE" and TF.translation_supported()))):
             return
         from .sampling import TrueSetStore, plan_batch_loss
         dev = self._device()

@@ -9,6 +9,8 @@ Restructured for the device:
     on the device;
   * DistMult / ComplEx are bilinear, so the P x N score matrix is ONE GEMM of the folded query against the
     all-entity table (`temp_linear`), never a (P, N, D) broadcast;
+  * TransE is not bilinear: its P x N matrix of negative L1 distances is one register-tiled pass (`temp_l1_scores`) over the
+    translation query, in place of the (100, N, D) broadcast per chunk of 100 triples;
   * the rank is the target's position in a stable descending order, computed by counting
     (`temp_filtered_rank`) instead of sorting."""
 import numpy as np
@@ -16,6 +18,16 @@ import torch
 
 from . import scores as S
 from .backend import get_backend
+
+
+def _l1_route(name, be, d):
+    """TransE scores come from the dense L1 kernel: a backend that has it, rows of whole float4s."""
+    return name == "transE" and hasattr(be, "l1_scores") and d % 4 == 0
+
+
+def _translation_query(known, r, mode):
+    """q with transE(known, r, c) = -|q - c|_1: s + r for the tail mode, o - r for the head mode."""
+    return (known + r if mode == "tail" else known - r).contiguous()
 
 
 class EvaluationFilter:
@@ -88,6 +100,7 @@ class EvaluationFilter:
                 return torch.zeros(0, dtype=torch.int64, device=dev)
             name = getattr(self.args, "score_function", None)
             fused = name in ("distmult", "complex") and num_ent % 4 == 0 and all_ent_embeds.shape[1] % 4 == 0
+            l1 = _l1_route(name, get_backend(), all_ent_embeds.shape[1])
             out = {}
             for mode in ("head", "tail"):
                 target, ptr, ids = self._mode_inputs(mode, samples, graph, time, num_ent, dev)
@@ -96,6 +109,10 @@ class EvaluationFilter:
                 if fused:
                     q = S.bilinear_query(name, known, r, mode).contiguous()
                     score = get_backend().linear(q, all_ent_embeds.contiguous(), True)
+                    out[mode] = get_backend().filtered_rank(score, target, ptr, ids)
+                    continue
+                if l1:                                     # one pass over all P triples, the pad columns already -inf
+                    score = get_backend().l1_scores(_translation_query(known, r, mode), all_ent_embeds.contiguous())
                     out[mode] = get_backend().filtered_rank(score, target, ptr, ids)
                     continue
                 ranks = []
@@ -129,6 +146,8 @@ class _MixedRankFilter(EvaluationFilter):
         if name in ("distmult", "complex") and num_ent % 4 == 0 and all_embeds.shape[1] % 4 == 0:
             q = S.bilinear_query(name, known, r, mode).contiguous()
             return get_backend().linear(q, all_embeds.contiguous(), True)
+        if _l1_route(name, get_backend(), all_embeds.shape[1]):
+            return get_backend().l1_scores(_translation_query(known, r, mode), all_embeds.contiguous())[:, :num_ent]
         rows = []
         for a in range(0, P, eval_bz):
             b = min(P, a + eval_bz)

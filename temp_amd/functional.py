@@ -588,9 +588,99 @@ def gated_link_prediction(loc, rec, rel, all_loc, all_rec, triplets, neg_tail, n
     return batched_gated_link_prediction(loc, rec, rel, all_loc, all_rec, w_known, w_cand, kind, inp)
 
 
+# -- TransE: the candidate loss over L1 distances ------------------------------------------------------------------------------
+_L1_METHODS = ("l1_ce_fwd", "l1_ce_bwd_q", "l1_ce_bwd_table", "l1_scores")
+
+
+def translation_supported(be=None):
+    """True when the installed backend has the L1 (TransE) kernels; a backend without them keeps the tensor path."""
+    be = get_backend() if be is None else be
+    return all(hasattr(be, m) for m in _L1_METHODS)
+
+
+def l1_slots(cand, base, n_rows):
+    """The slot lists of temp_l1_ce_bwd_table, built on the device: (slot_ptr int32 [n_rows + 1], slot int32 [P * C]) = the flat
+    positions p * C + k of `cand` grouped by their table row base[p] + cand[p, k] (base None = 0), ascending within a row (one
+    stable sort of the int32 row keys; the CSR by a binary search of the sorted keys: no host round trip)."""
+    keys = (cand if base is None else cand + base.view(-1, 1)).reshape(-1)
+    skeys, order = torch.sort(keys, stable=True)
+    edges = torch.arange(n_rows + 1, dtype=keys.dtype, device=keys.device)
+    return torch.searchsorted(skeys, edges, out_int32=True), order.to(torch.int32)
+
+
+def _cached_l1_slots(holder, cand, base, n_rows):
+    """l1_slots kept in `holder` = the loss inputs of a sample set (TKG_Module.loss_inputs documents the key; per_sample_set keeps
+    the dict for as long as the caller injects the same samples).  The entry is valid for the candidate matrix and the table size
+    it was built from: `base` is holder["window"] times the entities per window, so it follows from those two.  Fresh negatives
+    are a new candidate tensor and sort again every step."""
+    c = holder.get("_l1_slots")
+    if c is None or c[0] is not cand or c[1] != n_rows:
+        c = holder["_l1_slots"] = (cand, n_rows) + l1_slots(cand, base, n_rows)
+    return c[2], c[3]
+
+
+class _TranslationCEFn(torch.autograd.Function):
+    """mean_p CE(-|q[p] - all_embeds[cand[p, :]]|_1, label 0) without materialising (P, C, D)."""
+
+    @staticmethod
+    def forward(ctx, q, all_embeds, cand):
+        s, loss_rows, lse = get_backend().l1_ce_fwd(q, all_embeds, None, cand)
+        ctx.save_for_backward(q, all_embeds, cand, s, lse)
+        return loss_rows.mean()
+
+    @staticmethod
+    def backward(ctx, d_loss):
+        q, all_embeds, cand, s, lse = ctx.saved_tensors
+        be = get_backend()
+        g, d_q = be.l1_ce_bwd_q(q, all_embeds, None, cand, s, lse, d_loss.reshape(1).contiguous(), 1.0 / max(q.shape[0], 1))
+        slot_ptr, slot = l1_slots(cand, None, all_embeds.shape[0])
+        return d_q, be.l1_ce_bwd_table(q, all_embeds, slot_ptr, slot, g), None
+
+
+def translation_cross_entropy(q, all_embeds, cand):
+    """F.cross_entropy(transE score of the translation query q = s + r (tail) / o - r (head) against all_embeds[cand], 0)
+    (utils/scores.py:46-55).  cand: int32 (P, C), column 0 is the true entity."""
+    return _TranslationCEFn.apply(q.contiguous(), all_embeds.contiguous(), cand)
+
+
+class _BatchedTranslationLinkPredictionFn(torch.autograd.Function):
+    """_BatchedLinkPredictionFn for TransE, one autograd node:
+        q    = ent_rows[known] +- rel[rel_idx]                                         (temp_bilinear_query_fwd, kind transE)
+        s    = -|q[row] - big[window(row) * N + cand[row, :]]|_1  for ALL windows' rows    (temp_l1_ce_fwd, one launch)
+        loss = sum_rows w_row * CE(s[row, :], label 0)
+    The backward: the softmax gradient and d_q (temp_l1_ce_bwd_q), the candidate side into d_big over the slot lists
+    (temp_l1_ce_bwd_table), the query adjoint and the deterministic segment sums over the static index lists."""
+
+    @staticmethod
+    def forward(ctx, ent_rows, rel, big, inp):
+        be = get_backend()
+        N = big.shape[0] // len(inp["splits"])
+        q = be.bilinear_query_fwd("transE", ent_rows, inp["known"], rel, inp["rel"], inp["is_tail"])
+        base = inp["window"] * N
+        s, loss_rows, lse = be.l1_ce_fwd(q, big, base, inp["cand"])
+        ctx.save_for_backward(ent_rows, rel, big, q, s, lse, base)
+        ctx.inp = inp
+        return (loss_rows * inp["weights"]).sum()
+
+    @staticmethod
+    def backward(ctx, d_loss):
+        ent_rows, rel, big, q, s, lse, base = ctx.saved_tensors
+        inp = ctx.inp
+        be = get_backend()
+        g, d_q = be.l1_ce_bwd_q(q, big, base, inp["cand"], s, lse, d_loss.reshape(1).contiguous(), 1.0, inp["weights"])
+        slot_ptr, slot = _cached_l1_slots(inp, inp["cand"], base, big.shape[0])
+        d_big = be.l1_ce_bwd_table(q, big, slot_ptr, slot, g)
+        dk, dr = be.bilinear_query_bwd("transE", ent_rows, inp["known"], rel, inp["rel"], inp["is_tail"], d_q)
+        d_ent = be.segment_sum_rows(dk, inp["known_inv"][0], inp["known_inv"][1], ent_rows.shape[0])
+        d_rel = be.segment_sum_rows(dr, inp["rel_inv"][0], inp["rel_inv"][1], rel.shape[0])
+        return d_ent, d_rel, d_big, None
+
+
 def batched_link_prediction(ent_rows, rel, big, kind, inputs):
-    """sum over windows of CE_tail + CE_head (models/DynamicRGCN.py:186-193) for a bilinear scorer `kind`
-    ('distmult' | 'complex'); `inputs` = TKG_Module.loss_inputs(...)."""
+    """sum over windows of CE_tail + CE_head (models/DynamicRGCN.py:186-193) for scorer `kind` ('distmult' | 'complex': the GEMM
+    node; 'transE': the L1 node); `inputs` = TKG_Module.loss_inputs(...)."""
+    if kind == "transE":
+        return _BatchedTranslationLinkPredictionFn.apply(ent_rows, rel, big, inputs)
     return _BatchedLinkPredictionFn.apply(ent_rows, rel, big, kind, inputs)
 
 

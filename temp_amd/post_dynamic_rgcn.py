@@ -281,7 +281,7 @@ class _PostWindowMixin:
         """The ensemble loss of ALL windows as one fused node (functional.batched_ensemble_link_prediction), or None when the scorer
         / shapes need the per-window path.  locs / recs: per-window target rows of the two streams; alls: see _stacked_alls;
         weights: per window (weight_subject (P, 1), weight_object (P, 1))."""
-        if not self.fused_loss_ok(self.embed_size):
+        if not self.bilinear_loss_ok(self.embed_size):          # (the score-level mix of two TransE streams keeps the per-window path)
             return None
         inp = self.cached_loss_inputs(wb, "_ens_inputs", samples, wb.target.sizes, head_as_tail=self.head_scored_as_tail)
         if inp is None:
@@ -542,7 +542,7 @@ class _PostAggregationMixin(_TwoStreamMixin):
         return w, w
 
     def _gated_fused_ok(self):
-        return self.fused_loss_ok(self.embed_size)
+        return self.bilinear_loss_ok(self.embed_size)           # (the candidate mix is not linear for TransE's L1: the literal route)
 
     def batched_gated_loss(self, wb, locs, recs, alls, samples, gates):
         """The gated loss of ALL windows as one fused node, or None when the scorer / shapes need the per-window path.

@@ -171,7 +171,7 @@ def plan_batch_loss(store, times, graphs, row_offsets, num_pos_facts, rng, n_row
     (no device round trip) and uploaded once: per target graph the P = min(E, num_pos_facts) positives (a random subset
     when E is larger, utils/CorrptTriples.py:37-40), stacked as [tail-corruption rows ; head-corruption rows]:
       known / rel / is_tail   operands of the folded query      truth, lo, hi    inputs of temp_corrupt_sample
-      weights (1 / P), splits, known_inv / rel_inv (static inverses for the deterministic backward), triples (host, per graph)."""
+      weights (1 / P), window (the graph of every row), splits, known_inv / rel_inv (static inverses for the deterministic backward), triples (host, per graph)."""
     from . import _hostlib
     from . import functional as TF
     ptrs, idxs = [], []
@@ -192,4 +192,5 @@ def plan_batch_loss(store, times, graphs, row_offsets, num_pos_facts, rng, n_row
     dev_i = _lib.to_device(packed, device)                       # ONE upload for the six index vectors
     return dict(known=dev_i[0], rel=dev_i[1], is_tail=dev_i[2], truth=dev_i[3], lo=dev_i[4], hi=dev_i[5], ids=store.ids,
                 weights=_lib.to_device(weights, device), splits=splits, triples=triples,
+                window=_lib.to_device(np.repeat(np.arange(len(block), dtype=np.int32), block), device),
                 known_inv=TF.gather_inverse(packed[0], n_rows, device), rel_inv=TF.gather_inverse(packed[1], n_rel_rows, device))

@@ -82,9 +82,9 @@ class StaticRGCN(TKG_Module):
         return ranks, (float(np.mean(losses)) if losses else float("nan"))
 
     def _fused_loss_ok(self):
-        return (self.use_device_sampler and self.fused_loss and self.args.score_function in ("distmult", "complex")
-                and not self.ent_encoder.use_time_embedding and not getattr(self.args, "use_embed_for_non_active", False)
-                and self.num_ents % 4 == 0)
+        # (the rows this model scores are hidden_size wide: fused_loss_ok holds the scorer's alignment conditions)
+        return (self.use_device_sampler and self.fused_loss_ok(self.hidden_size)
+                and not self.ent_encoder.use_time_embedding and not getattr(self.args, "use_embed_for_non_active", False))
 
     def _fused_plan(self, ts, g_list):
         """Host half of the fused loss of a batch (static for the batch): the row map that assembles every window's all-entity
@@ -160,7 +160,7 @@ class StaticRGCN(TKG_Module):
         """Encoder + fused loss on a prepared batch (cand: fixed negatives, e.g. the draw of an earlier call: self._last_plan[1])."""
         rows = self.run(wb)
         if wb.fused is None:
-            raise NotImplementedError("run_loss needs the fused loss (bilinear scorer, no time embedding); use forward()")
+            raise NotImplementedError("run_loss needs the fused loss (a scorer with a fused node, no time embedding); use forward()")
         return self._fused_loss(wb.fused, rows, cand)
 
     def forward(self, t_list, target_edge_ids=None, samples=None):

@@ -79,8 +79,15 @@ class TKG_Module(nn.Module):
     def train_link_prediction(self, ent_embed, triplets, neg_samples, labels, all_embeds_g, corrupt_tail=True):
         """models/TKG_Module.py:202-213.  DistMult / ComplEx take the fused path: ONE GEMM of the
         folded query against all entities + a candidate cross-entropy kernel, instead of gathering
-        a (P, 1+neg, D) tensor; other scorers use the tensor-algebra path."""
+        a (P, 1+neg, D) tensor; TransE its L1 candidate kernels (functional.translation_cross_entropy) on a backend that
+        has them; anything else the tensor-algebra path."""
         name = self.args.score_function
+        if self.translation_loss_ok(ent_embed.shape[1]) and triplets.shape[0] > 0:
+            from . import functional as TF
+            t32 = triplets.to(torch.int32)
+            r = TF.gather_rows(self.rel_embeds, t32[:, 1].contiguous())
+            known = TF.gather_rows(ent_embed, (t32[:, 0] if corrupt_tail else t32[:, 2]).contiguous())
+            return TF.translation_cross_entropy(known + r if corrupt_tail else known - r, all_embeds_g, neg_samples.to(torch.int32).contiguous())
         if self.fused_loss and name in ("distmult", "complex") and all_embeds_g.shape[0] % 4 == 0 and triplets.shape[0] > 0:
             from . import functional as TF
             t32 = triplets.to(torch.int32)
@@ -103,6 +110,13 @@ class TKG_Module(nn.Module):
         operand (both halves have P rows, so the sum of the two means is twice the mean over the stack)."""
         name = self.args.score_function
         P = triplets.shape[0]
+        if self.translation_loss_ok(ent_embed.shape[1]) and P > 0:
+            from . import functional as TF
+            t32 = triplets.to(torch.int32)
+            r = TF.gather_rows(self.rel_embeds, t32[:, 1].contiguous())
+            known = TF.gather_rows(ent_embed, torch.cat([t32[:, 0], t32[:, 2]]).contiguous())
+            cand = torch.cat([neg_tail, neg_head], dim=0).to(torch.int32).contiguous()
+            return 2.0 * TF.translation_cross_entropy(torch.cat([known[:P] + r, known[P:] - r], dim=0), all_embeds_g, cand)
         if self.fused_loss and name in ("distmult", "complex") and all_embeds_g.shape[0] % 4 == 0 and P > 0:
             from . import functional as TF
             t32 = triplets.to(torch.int32)
@@ -118,8 +132,11 @@ class TKG_Module(nn.Module):
     def loss_inputs(row_offsets, samples, dev, n_rows=None, n_rel_rows=None, head_as_tail=False):
         """Index tensors of the batched loss for one set of samples (static for a prepared batch, so callers cache it):
         per graph the stacked operand is [tail queries (P rows); head queries (P rows)].  `n_rows` / `n_rel_rows` (the row
-        counts of the target-embedding stack and of rel_embeds) add the inverse maps the deterministic backward reduces over."""
-        known, rel, tail, cand, splits, weights = [], [], [], [], [], []
+        counts of the target-embedding stack and of rel_embeds) add the inverse maps the deterministic backward reduces over.
+        `window` is the graph of every row (the TransE node turns it into the row's offset into the all-entity stack).  The TransE
+        node also keeps its slot lists in this dict under "_l1_slots" (functional._cached_l1_slots): callers cache the dict per
+        sample set (per_sample_set), so the lists live exactly as long as the samples they were sorted from."""
+        known, rel, tail, cand, splits, weights, window = [], [], [], [], [], [], []
         row = 0
         for b, (trip, neg_tail, neg_head) in enumerate(samples):
             P = trip.shape[0]
@@ -136,12 +153,13 @@ class TKG_Module(nn.Module):
             cand.append(neg_tail.to(dev)); cand.append(neg_head.to(dev))
             splits.append((row, row + 2 * P))
             weights.append(torch.full((2 * P,), 1.0 / P, dtype=torch.float32, device=dev))
+            window.append(torch.full((2 * P,), b, dtype=torch.int32, device=dev))
             row += 2 * P
         if row == 0:
             return None
         out = dict(known=torch.cat(known).to(torch.int32).contiguous(), rel=torch.cat(rel).to(torch.int32).contiguous(),
                    is_tail=torch.cat(tail).contiguous(), cand=torch.cat(cand, dim=0).to(torch.int32).contiguous(), splits=splits,
-                   weights=torch.cat(weights))
+                   weights=torch.cat(weights), window=torch.cat(window))
         if n_rows is not None:
             from . import functional as TF
             out["known_inv"] = TF.gather_inverse(out["known"].cpu().numpy(), n_rows, dev)
@@ -170,16 +188,27 @@ class TKG_Module(nn.Module):
             return inp if finish is None else finish(inp, n_rows, dev)
         return self.per_sample_set(wb, attr, samples, build)
 
-    def fused_loss_ok(self, D):
-        """The batched loss nodes apply: a bilinear scorer, and shapes inside the kernels' alignment (D = width of the query rows)."""
+    def bilinear_loss_ok(self, D):
+        """The GEMM loss nodes apply: a bilinear scorer, and shapes inside the kernels' alignment (D = width of the query rows)."""
         name = self.args.score_function
         return self.fused_loss and name in ("distmult", "complex") and self.num_ents % 4 == 0 and D % (8 if name == "complex" else 4) == 0
+
+    def translation_loss_ok(self, D):
+        """The L1 loss nodes apply: TransE, a backend with the L1 kernels, D % 4 == 0 (no condition on num_ents: no GEMM)."""
+        if not (self.fused_loss and self.args.score_function == "transE" and D % 4 == 0):
+            return False
+        from . import functional as TF
+        return TF.translation_supported()
+
+    def fused_loss_ok(self, D):
+        """One of the batched loss nodes of functional.batched_link_prediction applies (D = width of the query rows)."""
+        return self.bilinear_loss_ok(D) or self.translation_loss_ok(D)
 
     def batched_link_prediction(self, ent_rows, inputs, all_embeds):
         """Sum over the target graphs of loss_tail + loss_head (models/DynamicRGCN.py:186-193) as one fused node
         (functional.batched_link_prediction): `ent_rows` is the concatenation of the per-graph target embeddings,
         `inputs` = loss_inputs(..., n_rows, n_rel_rows), `all_embeds` the (B * N_ents, D) stack of the windows' all-entity
-        matrices (or a list of B (N_ents, D) matrices).  Returns None when the scorer is not bilinear or the shapes are
+        matrices (or a list of B (N_ents, D) matrices).  Returns None when no fused node takes the scorer or the shapes are
         outside the kernels' alignment (the caller takes the per-graph path)."""
         name = self.args.score_function
         D = ent_rows.shape[1]

@@ -1,0 +1,357 @@
+"""The TransE (L1) kernels on the GPU against the fp64 references and derived tolerances of tests/transe_cases.py: the candidate
+loss kernels, the translation query, the dense scores, the filtered rank over them, the model-level loss against the tensor path
+and the evaluation route against the chunked one."""
+import numpy as np
+import pytest
+import torch
+
+from temp_amd import backend as TB
+from temp_amd import functional as TF
+from temp_amd import scores as SC
+from tests import transe_cases as TC
+from tests.golden_util import assert_close
+
+pytestmark = pytest.mark.gpu
+DEV = torch.device("cuda:0") if torch.cuda.is_available() else None
+
+
+def dv(t):
+    return None if t is None else t.to(DEV)
+
+
+def within(got, want, tol, what):
+    """|got - want| <= tol element by element (tol a tensor or a number); a shape mismatch or a non-finite element fails."""
+    g, w = got.detach().cpu().double(), want.double()
+    assert g.shape == w.shape, "%s: shape %s vs %s" % (what, tuple(g.shape), tuple(w.shape))
+    assert bool(torch.isfinite(g).all()), "%s: non-finite output" % what
+    err = (g - w).abs()
+    bad = err > tol
+    if bool(bad.any()):
+        i = int(torch.argmax((err - tol).reshape(-1)))
+        t = tol.reshape(-1)[i] if torch.is_tensor(tol) else tol
+        raise AssertionError("%s: %d of %d outside the bound; worst |err| %.3e against %.3e (want %.6e)"
+                             % (what, int(bad.sum()), bad.numel(), float(err.reshape(-1)[i]), float(t), float(w.reshape(-1)[i])))
+    print("%s: max |err| / bound = %.3f" % (what, float((err / (tol + 1e-300)).max())))
+
+
+def run_candidate(case, use_row_scale):
+    be = TB.get_backend()
+    q, table, base, cand = dv(case["q"]), dv(case["table"]), dv(case["base"]), dv(case["cand"])
+    s, loss, lse = be.l1_ce_fwd(q, table, base, cand)
+    g, d_q = be.l1_ce_bwd_q(q, table, base, cand, s, lse, dv(case["scale"]), case["inv_rows"], dv(case["row_scale"]) if use_row_scale else None)
+    slot_ptr, slot = TF.l1_slots(cand, base, case["n_rows"])
+    d_table = be.l1_ce_bwd_table(q, table, slot_ptr, slot, g)
+    return dict(s=s, loss=loss, lse=lse, g=g, d_q=d_q, d_table=d_table, slot_ptr=slot_ptr, slot=slot)
+
+
+@pytest.mark.parametrize("d,C,P,rows,windows", TC.CANDIDATE_CASES)
+def test_candidate_kernels_against_fp64(d, C, P, rows, windows):
+    """temp_l1_ce_fwd / _bwd_q / _bwd_table: scores, loss, softmax gradient and both adjoints inside the derived bounds, with the
+    per-row weights (one of them 0) and with the uniform one; bit-equal when run again; C == 1 gives exact zeros."""
+    case = TC.candidate_case(d, C, P, rows, windows)
+    want_ptr, want_slot = TC.slot_lists(case)
+    for use_rs in (True, False):
+        ref = TC.candidate_reference(case, use_rs)
+        a = run_candidate(case, use_rs)
+        b = run_candidate(case, use_rs)
+        for k in a:
+            assert torch.equal(a[k], b[k]), "%s is not bit-repeatable" % k
+        assert torch.equal(a["slot_ptr"].cpu(), want_ptr) and torch.equal(a["slot"].cpu(), want_slot), "slot lists"
+        what = "d=%d C=%d P=%d rows=%d windows=%d row_scale=%s " % (d, C, P, rows, windows, use_rs)
+        within(a["s"], ref["s"], ref["tol_s"], what + "scores")
+        within(a["lse"], ref["lse"], ref["tol_loss"], what + "lse")
+        within(a["loss"], ref["loss"], ref["tol_loss"], what + "loss")
+        eps = ref["eps"]
+        within(a["g"], ref["g"], eps * ref["a_g"], what + "g")
+        within(a["d_q"], ref["d_q"], eps * ref["a_q"], what + "d_q")
+        within(a["d_table"], ref["d_table"], eps * ref["a_table"], what + "d_table")
+        if use_rs:                                           # the weight-0 row: nothing of it anywhere
+            assert float(a["g"][P - 1].abs().max()) == 0.0 and float(a["d_q"][P - 1].abs().max()) == 0.0
+        if C == 1:
+            assert float(a["loss"].abs().max()) == 0.0, "C == 1: the loss must be exactly 0"
+            assert float(a["g"].abs().max()) == 0.0 and float(a["d_q"].abs().max()) == 0.0 and float(a["d_table"].abs().max()) == 0.0
+
+
+def test_candidate_kernels_empty_and_unsupported():
+    """P == 0 succeeds without output; d % 4 != 0 is refused."""
+    from temp_amd import _lib
+    be = TB.get_backend()
+    q, table = torch.zeros(0, 8, device=DEV), torch.zeros(7, 8, device=DEV)
+    s, loss, lse = be.l1_ce_fwd(q, table, None, torch.zeros(0, 3, dtype=torch.int32, device=DEV))
+    assert s.shape == (0, 3) and loss.shape == (0,)
+    assert be.l1_scores(q, table).shape == (0, 8)
+    with pytest.raises(_lib.TempAmdError):
+        be.l1_ce_fwd(torch.zeros(2, 6, device=DEV), torch.zeros(7, 6, device=DEV), None, torch.zeros(2, 3, dtype=torch.int32, device=DEV))
+    with pytest.raises(_lib.TempAmdError):
+        be.l1_scores(torch.zeros(2, 6, device=DEV), torch.zeros(7, 6, device=DEV))
+
+
+@pytest.mark.parametrize("d", [8, 200])
+def test_translation_query_bit_equal(d):
+    """kind transE of temp_bilinear_query_fwd / _bwd: q bit-equal to torch's k + r / k - r under mixed is_tail; the backward exact."""
+    g = torch.Generator().manual_seed(d)
+    P = 133
+    ent, rel = torch.randn(40, d, generator=g).to(DEV), torch.randn(9, d, generator=g).to(DEV)
+    known = torch.randint(0, 40, (P,), generator=g).int().to(DEV)
+    ridx = torch.randint(0, 9, (P,), generator=g).int().to(DEV)
+    is_tail = (torch.arange(P) % 3 != 0).int().to(DEV)
+    be = TB.get_backend()
+    q = be.bilinear_query_fwd("transE", ent, known, rel, ridx, is_tail)
+    k, r = ent[known.long()], rel[ridx.long()]
+    want = torch.where(is_tail.view(-1, 1) != 0, k + r, k - r)
+    assert torch.equal(q, want) and torch.equal(q.cpu(), torch.where(is_tail.cpu().view(-1, 1) != 0, k.cpu() + r.cpu(), k.cpu() - r.cpu()))
+    d_q = torch.randn(P, d, generator=g).to(DEV)
+    dk, dr = be.bilinear_query_bwd("transE", ent, known, rel, ridx, is_tail, d_q)
+    assert torch.equal(dk, d_q) and torch.equal(dr, torch.where(is_tail.view(-1, 1) != 0, d_q, -d_q))
+
+
+@pytest.mark.parametrize("P,N,d,ld", TC.SCORE_CASES)
+def test_dense_scores_against_fp64(P, N, d, ld):
+    """temp_l1_scores inside (d + 2) u |s64|; the pad columns -inf; bit-repeatable."""
+    c = TC.score_case(P, N, d)
+    be = TB.get_backend()
+    out = be.l1_scores(dv(c["q"]), dv(c["table"]))
+    assert out.shape == (P, ld) and torch.equal(out, be.l1_scores(dv(c["q"]), dv(c["table"])))
+    within(out[:, :N], c["s64"], c["tol"], "l1_scores P=%d N=%d d=%d" % (P, N, d))
+    assert ld == N or bool((out[:, N:] == float("-inf")).all()), "pad columns"
+
+
+@pytest.mark.parametrize("P,N,d,ld", TC.SCORE_CASES[:2])
+@pytest.mark.parametrize("filtered", [False, True])
+def test_ranks_inside_fp64_band(P, N, d, ld, filtered):
+    """temp_filtered_rank over temp_l1_scores: every row's rank inside the fp64 band; at most 25 % of the rows have a band wider
+    than one rank (a condition on the inputs, checked without a GPU in tests/test_transe_cpu.py as well)."""
+    c = TC.score_case(P, N, d)
+    target, ptr, ids = TC.rank_inputs(P, N)
+    if not filtered:
+        ptr = ids = None
+    lo, hi = TC.rank_band(c["s64"], c["tol"], target, ptr, ids)
+    assert float((lo != hi).float().mean()) <= 0.25
+    be = TB.get_backend()
+    ranks = be.filtered_rank(be.l1_scores(dv(c["q"]), dv(c["table"])), dv(target), dv(ptr), dv(ids)).cpu()
+    print("ranks: %d of %d rows ambiguous" % (int((lo != hi).sum()), P))
+    assert bool(((ranks >= lo) & (ranks <= hi)).all()), (ranks, lo, hi)
+
+
+# ---- model level -----------------------------------------------------------------------------------------------------------------
+class _Recorder:
+    """Backend view that keeps the operands of the loss node's query and candidate launches (for the input condition below)."""
+
+    def __init__(self, be):
+        self._be, self.query, self.ce = be, None, None
+
+    def __getattr__(self, name):
+        return getattr(self._be, name)
+
+    def bilinear_query_fwd(self, kind, ent_rows, known_idx, rel, rel_idx, is_tail):
+        self.query = (ent_rows.detach(), known_idx, rel.detach(), rel_idx, is_tail)
+        return self._be.bilinear_query_fwd(kind, ent_rows, known_idx, rel, rel_idx, is_tail)
+
+    def l1_ce_fwd(self, q, table, base, cand):
+        self.ce = (table.detach(), base, cand)
+        return self._be.l1_ce_fwd(q, table, base, cand)
+
+
+def _near_zero_head_slots(rec, device):
+    """(P_head, C) bool over the recorded operands, 256 rows at a time: the (head row, candidate) slots with a component of
+    c + r - o inside the band of TC.near_zero_mask.  Head rows come in the stacked order: graph by graph, after its tail rows."""
+    ent_rows, known, rel, rel_idx, is_tail = rec.query
+    table, base, cand = rec.ce
+    head = torch.nonzero(is_tail == 0).view(-1)
+    out = []
+    for rows in head.split(256):
+        o = ent_rows[known[rows].long()].to(device)
+        r = rel[rel_idx[rows].long()].to(device)
+        c = table[(cand[rows].long() + base[rows].long().view(-1, 1))].to(device)
+        out.append(TC.near_zero_mask(c, r, o).any(dim=-1).cpu())
+    return torch.cat(out)
+
+
+def _recorded_forward(model, wb, samples):
+    rec = _Recorder(TB.get_backend())
+    TB.set_backend(rec)
+    try:
+        with torch.no_grad():
+            model.run_loss(wb, samples)
+    finally:
+        TB.set_backend(rec._be)
+    return rec
+
+
+def _condition_samples(model, wb, samples, device, rounds=8):
+    """Seeded samples that meet the input condition of the head-mode comparison.  The tensor path computes c + (r - o), the
+    kernels (o - r) - c; the comparison wants inputs on which no sign can hinge on a rounding: no component of c + r - o within
+    2^-20 (|c| + |r| + |o|) of zero unless it is exactly zero.  Random draws do not give that by themselves at full size (313
+    of 3.2e8 components measured on the S-gdelt model), so the draw is conditioned: a negative whose slot has such a component
+    is replaced by the next entity id, a positive whose TRUE candidate has one by the graph's next positive, until none is left.
+    The caller asserts the condition on the result."""
+    N = model.num_ents
+    for _ in range(rounds):
+        bad = _near_zero_head_slots(_recorded_forward(model, wb, samples), device)
+        if not bool(bad.any()):
+            break
+        out, row = [], 0
+        for trip, neg_tail, neg_head in samples:
+            P = trip.shape[0]
+            b = bad[row:row + P].to(neg_head.device)
+            row += P
+            trip, neg_tail, neg_head = trip.clone(), neg_tail.clone(), neg_head.clone()
+            redraw = b.clone()
+            redraw[:, 0] = False
+            neg_head[redraw] = (neg_head[redraw] + 1) % N
+            for i in torch.nonzero(b[:, 0]).view(-1).tolist():
+                j = (i + 1) % P
+                trip[i], neg_tail[i], neg_head[i] = trip[j], neg_tail[j], neg_head[j]
+            out.append((trip, neg_tail, neg_head))
+        samples = out
+    return samples
+
+
+def _switch_to_transe(model):
+    model.args.score_function = "transE"
+    model.calc_score = SC.transE
+
+
+def _loss_properties(model, wb, samples, rows, enc_weight, cond_device):
+    """fused (the L1 node) against fused_loss = False (the tensor path) on the same samples: the input condition of the head mode
+    (see _condition_samples) asserted on them, loss, gradients, repeatability, and the peak memory of the fused loss, taken with
+    torch.cuda.max_memory_allocated around run_loss: below the tensor path's peak, and below the byte size of one (rows, C, D)
+    tensor."""
+    C, D = model.args.negative_rate + 1, model.embed_size
+
+    def run(fused):
+        model.fused_loss = fused
+        for p in model.parameters():
+            p.grad = None
+        torch.cuda.synchronize()
+        torch.cuda.reset_peak_memory_stats()
+        before = torch.cuda.memory_allocated()
+        loss = model.run_loss(wb, samples)
+        torch.cuda.synchronize()
+        peak = torch.cuda.max_memory_allocated() - before
+        loss.backward()
+        return (loss.detach().clone(), model.ent_embeds.grad.clone(), model.rel_embeds.grad.clone(), enc_weight.grad.clone()), peak
+
+    near = int(_near_zero_head_slots(_recorded_forward(model, wb, samples), cond_device).sum())
+    print("head-mode slots with a component within 2^-20 of zero: %d" % near)
+    assert near == 0, "input condition: %d head-mode slots have a component within rounding of zero" % near
+    a, _ = run(True)                                         # (first call: the caches of the sample set fill)
+    b, peak = run(True)
+    assert all(torch.equal(x, y) for x, y in zip(a, b)), "fused loss is not bitwise repeatable"
+    r, peak_ref = run(False)
+    model.fused_loss = True
+    one_tensor = rows * C * D * 4
+    print("peak delta around run_loss: fused %.1f MB, tensor path %.1f MB; one (rows, C, D) tensor %.1f MB"
+          % (peak / 2 ** 20, peak_ref / 2 ** 20, one_tensor / 2 ** 20))
+    assert peak < peak_ref, "the fused loss does not allocate less than the tensor path"
+    assert peak < one_tensor, "the fused loss allocates as much as a (rows, C, D) tensor"
+    assert abs(a[0].item() - r[0].item()) < 2e-5 * abs(r[0].item()), (a[0].item(), r[0].item())
+    for x, y, what in zip(a[1:], r[1:], ("d ent_embeds", "d rel_embeds", "d encoder weight")):
+        assert_close(x, y, 1e-4, 1e-5 * float(y.abs().max()), what + ", fused vs tensor path")
+
+
+def _plan_samples(model, wb, seed):
+    plan = wb.loss_plan
+    assert plan is not None, "TransE must get the planned loss"
+    cand = TB.get_backend().corrupt_sample(seed, plan["truth"], plan["lo"], plan["hi"], plan["ids"], model.args.negative_rate, model.num_ents)
+    samples = []
+    for b, (a0, a1) in enumerate(plan["splits"]):
+        P = plan["triples"][b].shape[0]                      # (a block may end in weight-0 padding rows)
+        samples.append((torch.from_numpy(plan["triples"][b]), cand[a0:a0 + P].long(), cand[a0 + P:a0 + 2 * P].long()))
+    return samples, sum(2 * plan["triples"][b].shape[0] for b in range(len(samples)))
+
+
+def test_window_model_transe_loss_gpu():
+    """G10_bi_grrgcn_rol switched to transE: the properties of _loss_properties, and the planned path (samples=None: one sampler
+    launch + the fused node) equal to the injected-samples path on the same candidates."""
+    from tests.golden_util import load
+    from tests.window_cases import build_window_model
+    z = load("G10_bi_grrgcn_rol")
+    m = build_window_model(z, DEV)
+    _switch_to_transe(m)
+    # 500 negatives per positive: a (rows, C, D) tensor is then larger than what the encoder of this small model allocates, so
+    # the memory bounds of _loss_properties say something about the loss
+    m.args.negative_rate = m.negative_rate = 500
+    t_list = torch.tensor([int(t) for t in z["t_list"]])
+    m.sample_rng = np.random.default_rng(3)
+    wb = m.prepare(t_list, int(z["L"]), train=True)
+    m.seed_rng = np.random.default_rng(7)
+    loss1 = m.run_loss(wb)
+    m.seed_rng = np.random.default_rng(7)
+    samples, rows = _plan_samples(m, wb, int(m.seed_rng.integers(1 << 62)))
+    loss2 = m.run_loss(wb, samples)
+    assert abs(loss1.item() - loss2.item()) < 2e-5 * max(1.0, abs(loss2.item()))
+    samples = _condition_samples(m, wb, samples, torch.device("cpu"))
+    _loss_properties(m, wb, samples, rows, m.ent_encoder.layer_1.loop_weight, torch.device("cpu"))
+
+
+def test_full_size_transe_loss_gpu():
+    """The S-gdelt bench model with num_pos_facts = 400 and transE (8 windows, 500 entities, negative_rate 500): see
+    _loss_properties.  (The input condition runs over 3.2e8 components: in fp64 on the device.)"""
+    import bench
+    from temp_amd import synthetic
+    w = synthetic.workload("S-gdelt", seed=0)
+    model = bench.build_model(w, DEV)
+    _switch_to_transe(model)
+    model.args.num_pos_facts = 400
+    targets = synthetic.default_targets(w["num_times"], w["L"], w["bsz"], 0)
+    model.sample_rng = np.random.default_rng(2)
+    wb = model.prepare(targets, w["L"], train=True)
+    samples, rows = _plan_samples(model, wb, 99)
+    assert rows == 8 * 2 * 400
+    model.seed_rng = np.random.default_rng(7)
+    assert torch.isfinite(model.run_loss(wb)).all()          # the planned path
+    samples = _condition_samples(model, wb, samples, DEV)
+    _loss_properties(model, wb, samples, rows, model.ent_encoder.layer_1.loop_weight, DEV)
+
+
+# ---- evaluation ------------------------------------------------------------------------------------------------------------------
+class _NoL1:
+    """Backend view without the L1 kernels: what forces the chunked tensor route."""
+
+    def __init__(self, be):
+        self._be = be
+
+    def __getattr__(self, name):
+        if name in TF._L1_METHODS:
+            raise AttributeError(name)
+        return getattr(self._be, name)
+
+
+def test_evaluation_route_against_chunked_gpu():
+    """EvaluationFilter.calc_metrics_single_graph with transE on the icews14 slice: the l1_scores route against the chunked
+    broadcast route -- equal ranks on every row the fp64 band marks unambiguous, inside the band elsewhere, at most 25 % ambiguous."""
+    from temp_amd.evaluation import EvaluationFilter
+    from tests.window_cases import make_args, slice_snapshots
+    s = slice_snapshots()
+    t = s["times"][14]
+    g = s["va"][t]
+    N, D = s["num_e"], 16
+    torch.manual_seed(5)
+    all_e = torch.randn(N, D) * 0.5
+    rel = torch.randn(2 * s["num_r"], D) * 0.5
+    ent = all_e[torch.from_numpy(g.gids)]
+    samples = torch.from_numpy(np.stack([g.src, g.rel, g.dst], axis=1))
+    ev = EvaluationFilter(make_args(score_function="transE"), SC.transE, s["tr"], s["va"], s["te"])
+    be = TB.get_backend()
+    new = ev.calc_metrics_single_graph(dv(ent), dv(rel), dv(all_e), dv(samples), g, t).cpu()
+    TB.set_backend(_NoL1(be))
+    try:
+        old = ev.calc_metrics_single_graph(dv(ent), dv(rel), dv(all_e), dv(samples), g, t).cpu()
+    finally:
+        TB.set_backend(be)
+    P = samples.shape[0]
+    lo, hi = [], []
+    for mode in ("head", "tail"):                            # (the reference's order: subject-corruption ranks first)
+        target, ptr, ids = (x.cpu() for x in ev._mode_inputs(mode, dv(samples), g, int(t), N, DEV))
+        known, r = ent[samples[:, 0] if mode == "tail" else samples[:, 2]], rel[samples[:, 1]]
+        q = known + r if mode == "tail" else known - r      # fp32, bit-equal to the kernels' query
+        s64 = -torch.cdist(q.double(), all_e.double(), p=1)
+        a, b = TC.rank_band(s64, (D + 2) * TC.U * s64.abs(), target, ptr, ids)
+        lo.append(a); hi.append(b)
+    lo, hi = torch.cat(lo), torch.cat(hi)
+    sure = lo == hi
+    print("evaluation: %d of %d rows ambiguous" % (int((~sure).sum()), 2 * P))
+    assert float((~sure).float().mean()) <= 0.25
+    assert torch.equal(new[sure], old[sure]) and torch.equal(new[sure], lo[sure])
+    assert bool(((new >= lo) & (new <= hi)).all()) and bool(((old >= lo) & (old <= hi)).all())
