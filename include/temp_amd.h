@@ -784,10 +784,14 @@ int temp_l1_scores(int P, int N, int d, const float* q, const float* table, int 
  *   known[p] = w[p] * A[ia[p]] + (1 - w[p]) * B[ib[p]]          when ia[p] >= 0
  *   known[p] = B[ib[p]]  (exactly; w[p] is not read)            when ia[p] <  0   -- TEMPORAL-ONLY row: the reference's head rows,
  *            whose "local" known object is the temporal row too (models/PostDynamicRGCN.py:276-277), so w[p] has no effect
- *   q[p]     = fold(known[p], rel[rel_idx[p]]) for kind / is_tail as in temp_bilinear_query_fwd.
+ *   q[p]     = fold(known[p], rel[rel_idx[p]]) for kind / is_tail as in temp_bilinear_query_fwd; kind TEMP_SCORE_TRANSE gives the
+ *              translation query known[p] + r (tail) / known[p] - r (head): one IEEE add / subtract after the mix (is_tail required).
+ *   The mix is the one expression fmaf(w, a, (1 - w) * b) in every gated kernel, forward and backward (csrc/mix.hpp): for finite
+ *   rows w == 1 gives a and w == 0 gives b bit-exactly.
  *   bwd (d_k = the gradient of known[p] from d_q[p]):
  *     d_a_rows[p] = w[p] d_k, d_b_rows[p] = (1 - w[p]) d_k, d_w[p] = <d_k, A[ia[p]] - B[ib[p]]>     (ia[p] >= 0)
  *     d_a_rows[p] = 0,        d_b_rows[p] = d_k,            d_w[p] = 0                            (ia[p] <  0)
+ *     transE: d_k = d_q[p] and d_rel_rows[p] = +-d_q[p].
  *     d_rel_rows[p] = the relation row's gradient.  All outputs fully written ([P, d] and [P]); the caller sums the rows over the
  *     index lists (temp_segment_sum_rows; ia's negative entries are left out of its segmentation).
  *   d % 4 == 0 (complex: d % 8 == 0), else TEMP_E_UNSUPPORTED.  One wave per row; d_w is a wave reduction in fixed order.
@@ -811,6 +815,38 @@ int temp_gather_ce_mix_fwd(int P, int C, int N, const float* s_a, const float* s
 int temp_gather_ce_mix_bwd(int P, int C, int N, const float* s_a, const float* s_b, const float* w, const int32_t* cand, const float* lse_rows,
                            const float* scale, float inv_rows, const float* row_scale /* nullable [P] */, float* d_s_a, float* d_s_b,
                            float* d_w, void* stream);
+
+/* ------------------------------------------------------------------------------------------------
+ * Gated TransE loss and scores of the post-aggregation models (models/PostDynamicRGCN.py:261-282, utils/post_evaluation.py:32-69 with
+ * utils/scores.py:46-55).  The candidate of row p is the mix of the two all-entity tables with the row's candidate weight,
+ *   e[p,k] = mix(w[p], table_a[base[p] + cand[p,k]], table_b[base[p] + cand[p,k]]),    mix(w, a, b) = fmaf(w, a, (1 - w) * b),
+ * and |q - e|_1 is not linear in e, so the mix cannot be taken on two score matrices as for the bilinear scorers: these are the
+ * temp_l1_* calls above reading both table rows of a candidate and mixing in registers (table_a, table_b: the same shape, e.g. the
+ * (B N, d) stacks of the windows' local and temporal all-entity matrices; q from temp_gated_query_fwd, kind TEMP_SCORE_TRANSE).
+ *
+ * temp_l1_mix_ce_fwd:   s_out[p,k] = -sum_d |q[p,d] - e[p,k,d]|;  lse_rows, loss_rows as temp_l1_ce_fwd (C == 1: loss exactly 0).
+ * temp_l1_mix_ce_bwd_q: g_out as temp_l1_ce_bwd_q;  d_q[p,:] = -sum_k g_out[p,k] sgn(q[p,:] - e[p,k,:])  (sgn(0) = 0);
+ *                       d_w[p] = sum_k g_out[p,k] sum_d sgn(q[p,d] - e[p,k,d]) (table_a - table_b)[row, d]     ([P], same pass).
+ * temp_l1_mix_ce_bwd_table (slot lists as temp_l1_ce_bwd_table, over the shared row index of both tables):
+ *   d_table_a[n,:] = sum_slots w[p] g[slot] sgn(q[p,:] - e),  d_table_b[n,:] = sum_slots (1 - w[p]) g[slot] sgn(q[p,:] - e),  p = slot / C;
+ *   one pass over the row's slots writes both; zeros for a row without slots.
+ * temp_l1_mix_scores:   scores[p,n] = -|q[p] - mix(w[p], table_a[n], table_b[n])|_1 for n < N, -inf for N <= n < ld (feeds
+ *                       temp_filtered_rank: the ranking pass of PostEvaluationFilter).
+ *
+ * The contract of the temp_l1_* calls: d % 4 == 0, P C < 2^31, ld % 4 == 0, else TEMP_E_UNSUPPORTED; P == 0 (n_rows == 0) returns
+ * success without a launch.  fp32, all outputs fully written, no workspace, no floating-point atomics; every sum has a fixed
+ * order: results are bit-repeatable.
+ * ---------------------------------------------------------------------------------------------- */
+int temp_l1_mix_ce_fwd(int P, int C, int d, const float* q, const float* table_a, const float* table_b, const float* w,
+                       const int32_t* base /* nullable [P] */, const int32_t* cand, float* s_out, float* loss_rows, float* lse_rows, void* stream);
+int temp_l1_mix_ce_bwd_q(int P, int C, int d, const float* q, const float* table_a, const float* table_b, const float* w,
+                         const int32_t* base /* nullable [P] */, const int32_t* cand, const float* s, const float* lse_rows,
+                         const float* scale /* device float */, float inv_rows, const float* row_scale /* nullable [P] */, float* g_out,
+                         float* d_q, float* d_w, void* stream);
+int temp_l1_mix_ce_bwd_table(int n_rows, int d, int C, const float* q, const float* table_a, const float* table_b, const float* w,
+                             const int32_t* slot_ptr, const int32_t* slot, const float* g, float* d_table_a, float* d_table_b, void* stream);
+int temp_l1_mix_scores(int P, int N, int d, const float* q, const float* table_a, const float* table_b, const float* w, int ld,
+                       float* scores, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
  * Snapshot store (build_interpolation_graphs / get_train_val_test_graph_at_t keep one DGL graph per timestamp,

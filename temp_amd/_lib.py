@@ -209,6 +209,10 @@ SYMBOLS = {
     "temp_gated_query_bwd": (_I, [_I, _I, _I, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp]),
     "temp_gather_ce_mix_fwd": (_I, [_I, _I, _I, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp]),
     "temp_gather_ce_mix_bwd": (_I, [_I, _I, _I, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, _F, c_vp, c_vp, c_vp, c_vp, c_vp]),
+    "temp_l1_mix_ce_fwd": (_I, [_I, _I, _I, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp]),
+    "temp_l1_mix_ce_bwd_q": (_I, [_I, _I, _I, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, _F, c_vp, c_vp, c_vp, c_vp, c_vp]),
+    "temp_l1_mix_ce_bwd_table": (_I, [_I, _I, _I, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp]),
+    "temp_l1_mix_scores": (_I, [_I, _I, _I, c_vp, c_vp, c_vp, c_vp, _I, c_vp, c_vp]),
     "temp_assemble_views": (_I, [_I, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp]),
     "temp_subsample_views": (_I, [_I, ctypes.POINTER(TempSubsampleJob), c_vp]),
     "temp_corrupt_sample": (_I, [_I, _I, _I, ctypes.c_uint64, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp]),

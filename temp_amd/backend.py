@@ -786,6 +786,65 @@ class HipBackend:
         _lib.check(rc, "temp_gated_query_bwd")
         return da, db, dr, dw
 
+    # ---- gated TransE: the L1 calls over the per-row mix of two tables (include/temp_amd.h: temp_l1_mix_ce_fwd ...) ----
+    def l1_mix_ce_fwd(self, q, table_a, table_b, w, base, cand):
+        """-> (s [P, C], loss_rows [P], lse [P]) over s[p,k] = -|q[p] - mix(w[p], table_a[row], table_b[row])|_1, row = base[p] + cand[p,k]."""
+        q, table_a, table_b, w = _f32(q, "q"), _f32(table_a, "table_a"), _f32(table_b, "table_b"), _f32(w, "w")
+        base, cand = _i32(base, "base"), _i32(cand, "cand")
+        P, d = q.shape
+        C = cand.shape[1]
+        if table_a.shape != table_b.shape or w.numel() != P:
+            raise ValueError("l1_mix_ce_fwd: the two tables must have one shape and w one entry per row")
+        s = torch.empty(P, C, dtype=torch.float32, device=q.device)
+        loss = torch.empty(P, dtype=torch.float32, device=q.device)
+        lse = torch.empty(P, dtype=torch.float32, device=q.device)
+        rc = self.lib.temp_l1_mix_ce_fwd(P, C, d, _ptr(q), _ptr(table_a), _ptr(table_b), _ptr(w), _ptr(base), _ptr(cand), _ptr(s), _ptr(loss),
+                                         _ptr(lse), _stream())
+        _lib.check(rc, "temp_l1_mix_ce_fwd")
+        return s, loss, lse
+
+    def l1_mix_ce_bwd_q(self, q, table_a, table_b, w, base, cand, s, lse, scale, inv_rows, row_scale=None):
+        """-> (g [P, C], d_q [P, d], d_w [P]): the softmax gradient, the query side of its adjoint and the candidate weight's."""
+        q, table_a, table_b, w = _f32(q, "q"), _f32(table_a, "table_a"), _f32(table_b, "table_b"), _f32(w, "w")
+        base, cand = _i32(base, "base"), _i32(cand, "cand")
+        s, lse, scale, row_scale = _f32(s, "s"), _f32(lse, "lse"), _f32(scale, "scale"), _f32(row_scale, "row_scale")
+        P, d = q.shape
+        if table_a.shape != table_b.shape or w.numel() != P:
+            raise ValueError("l1_mix_ce_bwd_q: the two tables must have one shape and w one entry per row")
+        g = torch.empty_like(s)
+        d_q = torch.empty_like(q)
+        d_w = torch.empty(P, dtype=torch.float32, device=q.device)
+        rc = self.lib.temp_l1_mix_ce_bwd_q(P, cand.shape[1], d, _ptr(q), _ptr(table_a), _ptr(table_b), _ptr(w), _ptr(base), _ptr(cand), _ptr(s),
+                                           _ptr(lse), _ptr(scale), float(inv_rows), _ptr(row_scale), _ptr(g), _ptr(d_q), _ptr(d_w), _stream())
+        _lib.check(rc, "temp_l1_mix_ce_bwd_q")
+        return g, d_q, d_w
+
+    def l1_mix_ce_bwd_table(self, q, table_a, table_b, w, slot_ptr, slot, g):
+        """-> (d_table_a, d_table_b) [rows, d]: the candidate side of the adjoint over the slot lists (functional.l1_slots)."""
+        q, table_a, table_b, w, g = _f32(q, "q"), _f32(table_a, "table_a"), _f32(table_b, "table_b"), _f32(w, "w"), _f32(g, "g")
+        slot_ptr, slot = _i32(slot_ptr, "slot_ptr"), _i32(slot, "slot")
+        n_rows, d = table_a.shape
+        if table_a.shape != table_b.shape or slot_ptr.shape[0] != n_rows + 1 or slot.numel() != g.numel() or w.numel() != g.shape[0]:
+            raise ValueError("l1_mix_ce_bwd_table: slot lists / weights do not match the tables / the candidate matrix")
+        d_a, d_b = torch.empty_like(table_a), torch.empty_like(table_b)
+        rc = self.lib.temp_l1_mix_ce_bwd_table(n_rows, d, g.shape[1], _ptr(q), _ptr(table_a), _ptr(table_b), _ptr(w), _ptr(slot_ptr), _ptr(slot),
+                                               _ptr(g), _ptr(d_a), _ptr(d_b), _stream())
+        _lib.check(rc, "temp_l1_mix_ce_bwd_table")
+        return d_a, d_b
+
+    def l1_mix_scores(self, q, table_a, table_b, w):
+        """-> scores [P, ld], ld = N rounded up to a multiple of 4: -|q[p] - mix(w[p], table_a[n], table_b[n])|_1, the pad columns -inf."""
+        q, table_a, table_b, w = _f32(q, "q"), _f32(table_a, "table_a"), _f32(table_b, "table_b"), _f32(w, "w")
+        P, d = q.shape
+        N = table_a.shape[0]
+        if table_a.shape != table_b.shape or w.numel() != P:
+            raise ValueError("l1_mix_scores: the two tables must have one shape and w one entry per row")
+        ld = (N + 3) // 4 * 4
+        out = torch.empty(P, ld, dtype=torch.float32, device=q.device)
+        rc = self.lib.temp_l1_mix_scores(P, N, d, _ptr(q), _ptr(table_a), _ptr(table_b), _ptr(w), ld, _ptr(out), _stream())
+        _lib.check(rc, "temp_l1_mix_scores")
+        return out
+
     def gather_ce_mix_fwd(self, s_a, s_b, w, cand):
         """Candidate CE over the mixed scores w * s_a + (1 - w) * s_b (w [P]) -> (loss_rows, lse)."""
         s_a, s_b, w, cand = _f32(s_a, "s_a"), _f32(s_b, "s_b"), _f32(w, "w"), _i32(cand, "cand")

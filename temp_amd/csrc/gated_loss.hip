@@ -11,6 +11,7 @@
 //                         as in k_gather_ce_bwd) and d_w = sum_e G (s_a - s_b) in the same pass
 // No floating-point atomics and no workspace: every output element has one writer and every sum a fixed order.
 #include "common.hpp"
+#include "mix.hpp"
 
 namespace temp {
 namespace {
@@ -34,11 +35,7 @@ __device__ __forceinline__ float block_sum_256(float v, float* red) {
   return (red[0] + red[1]) + (red[2] + red[3]);
 }
 
-// the one mixing expression of the forward and backward passes (the backward recomputes the forward's value bit for bit)
-__device__ __forceinline__ float mix1(float w, float a, float b) { return fmaf(w, a, (1.f - w) * b); }
-__device__ __forceinline__ float4 mix4(float w, float4 a, float4 b) {
-  return make_float4(mix1(w, a.x, b.x), mix1(w, a.y, b.y), mix1(w, a.z, b.z), mix1(w, a.w, b.w));
-}
+// (the mixing expression mix1 / mix4 of the forward and backward passes: mix.hpp)
 __device__ __forceinline__ float4 sub4(float4 a, float4 b) { return make_float4(a.x - b.x, a.y - b.y, a.z - b.z, a.w - b.w); }
 __device__ __forceinline__ float4 mul4(float4 a, float4 b) { return make_float4(a.x * b.x, a.y * b.y, a.z * b.z, a.w * b.w); }
 
@@ -47,6 +44,8 @@ __device__ __forceinline__ float4 mul4(float4 a, float4 b) { return make_float4(
 //   DistMult            q = known * r
 //   ComplEx, tail mode  q = [re_k re_r - im_k im_r | re_k im_r + im_k re_r]
 //   ComplEx, head mode  q = [re_r re_k + im_r im_k | re_r im_k - im_r re_k]
+//   TransE              q = known + r (tail) / known - r (head): one IEEE add / subtract after the mix (the translation query of
+//                       k_bilinear_query); backward d_k = d_q, d_rel = +-d_q
 // Backward (d_k = the adjoint of the fold, as in k_bilinear_query):  o0 = d_A rows = w d_k (0 on temporal-only rows),
 // o1 = d_B rows = (1 - w) d_k (d_k), o2 = d_rel rows, dw[p] = <d_k, A[ia] - B[ib]> (0).
 // ---------------------------------------------------------------------------------------------
@@ -70,6 +69,19 @@ __global__ void __launch_bounds__(256) k_gated_query(int P, int d, int kind, con
     for (int j = lane * 4; j < d; j += 256) {
       const float4 bv = ld4(brow + j), av = gated ? ld4(arow + j) : bv;
       const float4 kv = gated ? mix4(wp, av, bv) : bv, rv = ld4(rrow + j);
+      if (kind == TEMP_SCORE_TRANSE) {
+        const float sg = is_tail[p] ? 1.f : -1.f;       // sg * r is exact: known + sg * r rounds once, as known + r / known - r
+        if (!BWD) {
+          st4(o0 + o + j, make_float4(kv.x + sg * rv.x, kv.y + sg * rv.y, kv.z + sg * rv.z, kv.w + sg * rv.w));
+          continue;
+        }
+        const float4 dk = ld4(dq + o + j);
+        st4(o0 + o + j, gated ? scale4(dk, wp) : zero4());
+        st4(o1 + o + j, gated ? scale4(dk, 1.f - wp) : dk);
+        st4(o2 + o + j, scale4(dk, sg));
+        if (gated) acc += dot4(dk, sub4(av, bv));
+        continue;
+      }
       if (!BWD) {
         st4(o0 + o + j, mul4(kv, rv));
         continue;
@@ -233,9 +245,9 @@ __global__ void __launch_bounds__(256) k_gather_ce_mix_bwd(int C, int N, const f
 
 int gated_query_args(int P, int d, int kind, const void* A, const void* ia, const void* B, const void* ib, const void* w, const void* rel,
                      const void* rel_idx, const void* is_tail) {
-  if (P < 0 || d <= 0 || (kind != TEMP_SCORE_DISTMULT && kind != TEMP_SCORE_COMPLEX)) return TEMP_E_BADARG;
+  if (P < 0 || d <= 0 || (kind != TEMP_SCORE_DISTMULT && kind != TEMP_SCORE_COMPLEX && kind != TEMP_SCORE_TRANSE)) return TEMP_E_BADARG;
   if (kind == TEMP_SCORE_COMPLEX ? d % 8 : d % 4) return TEMP_E_UNSUPPORTED;
-  if (P > 0 && (!A || !ia || !B || !ib || !w || !rel || !rel_idx || (kind == TEMP_SCORE_COMPLEX && !is_tail))) return TEMP_E_BADARG;
+  if (P > 0 && (!A || !ia || !B || !ib || !w || !rel || !rel_idx || (kind != TEMP_SCORE_DISTMULT && !is_tail))) return TEMP_E_BADARG;
   return TEMP_OK;
 }
 

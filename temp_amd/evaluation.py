@@ -186,7 +186,8 @@ class PostEvaluationFilter(_MixedRankFilter):
     """utils/post_evaluation.py:7-60: EMBEDDING-level ensemble with four per-triple weights.  The known entity is mixed as
     w * local + (1 - w) * temporal; every candidate likewise with the other weight.  distmult / complex are linear in the
     candidate, so the candidate mix is applied to the two score matrices instead of materialising (P, N_ents, D) candidates;
-    any other scorer takes the reference's literal route."""
+    transE is not: its scores are one dense pass that mixes the two all-entity rows per (triple, entity) in registers
+    (`temp_l1_mix_scores`); any other scorer, or a backend without that kernel, takes the reference's literal route."""
 
     def calc_metrics_single_graph(self, ent_embed_loc, ent_embed_rec, rel_enc_means, all_embeds_g_loc, all_embeds_g_rec, samples,
                                   weight_subject_query_subject_embed, weight_subject_query_object_embed,
@@ -204,7 +205,12 @@ class PostEvaluationFilter(_MixedRankFilter):
                 sel = samples[:, 0] if mode == "tail" else samples[:, 2]
                 w_known, w_cand = (ws, wo) if mode == "tail" else (wo, ws)     # tail: subject known; head: object known
                 known = w_known * ent_embed_loc[sel] + (1 - w_known) * ent_embed_rec[sel]
-                if name in ("distmult", "complex"):
+                be = get_backend()
+                if _l1_route(name, be, all_embeds_g_loc.shape[1]) and hasattr(be, "l1_mix_scores"):
+                    # one pass over all P triples: the candidate mix formed inside the dense L1 kernel, the pad columns already -inf
+                    score = be.l1_mix_scores(_translation_query(known, r, mode), all_embeds_g_loc.contiguous(), all_embeds_g_rec.contiguous(),
+                                             w_cand.contiguous())
+                elif name in ("distmult", "complex"):
                     score = w_cand * self._score_matrix(known, r, all_embeds_g_loc, mode, eval_bz) \
                         + (1 - w_cand) * self._score_matrix(known, r, all_embeds_g_rec, mode, eval_bz)
                 else:

@@ -463,8 +463,12 @@ class _BatchedEnsembleLinkPredictionFn(torch.autograd.Function):
 def batched_ensemble_link_prediction(loc_rows, rec_rows, rel, big_loc, big_rec, w, kind, inputs):
     """sum over windows of the ensemble CE_tail + CE_head; `w` (rows, 1) = weight of the LOCAL stream of every stacked query row
     (per window: [tail rows: weight_object ; head rows: weight_subject]); `inputs` = TKG_Module.loss_inputs(...)."""
+    w = w.reshape(-1, 1).to(loc_rows.dtype).contiguous()
+    if kind == "transE":
+        return _BatchedEnsembleTranslationLinkPredictionFn.apply(loc_rows.contiguous(), rec_rows.contiguous(), rel, big_loc.contiguous(),
+                                                                 big_rec.contiguous(), w, inputs)
     return _BatchedEnsembleLinkPredictionFn.apply(loc_rows.contiguous(), rec_rows.contiguous(), rel, big_loc.contiguous(), big_rec.contiguous(),
-                                                  w.reshape(-1, 1).to(loc_rows.dtype).contiguous(), kind, inputs)
+                                                  w, kind, inputs)
 
 
 def _gated_query_fwd(be, kind, a_rows, a_idx, b_rows, b_idx, w, rel, rel_idx, is_tail):
@@ -568,8 +572,12 @@ def gated_loss_inputs(inp, n_loc_rows, device):
 def batched_gated_link_prediction(loc_rows, rec_rows, rel, big_loc, big_rec, w_known, w_cand, kind, inputs):
     """sum over windows of the post-aggregation CE_tail + CE_head (see _BatchedGatedLinkPredictionFn).  w_known / w_cand (rows, 1):
     per window [tail rows: w_oqs / w_oqo ; head rows: w_sqo / w_sqs]; `inputs` = gated_loss_inputs(TKG_Module.loss_inputs(...)).
-    big_loc / big_rec: the (B * N_ents, D) stacks of the windows' all-entity matrices."""
+    big_loc / big_rec: the (B * N_ents, D) stacks of the windows' all-entity matrices.  kind 'distmult' | 'complex': the score-matrix
+    node; 'transE': the L1 node over the mixed candidate rows (_BatchedGatedTranslationLinkPredictionFn)."""
     f = lambda t: t.reshape(-1, 1).to(loc_rows.dtype).contiguous()
+    if kind == "transE":
+        return _BatchedGatedTranslationLinkPredictionFn.apply(loc_rows.contiguous(), rec_rows.contiguous(), rel, big_loc.contiguous(),
+                                                              big_rec.contiguous(), f(w_known), f(w_cand), inputs)
     return _BatchedGatedLinkPredictionFn.apply(loc_rows.contiguous(), rec_rows.contiguous(), rel, big_loc.contiguous(), big_rec.contiguous(),
                                                f(w_known), f(w_cand), kind, inputs)
 
@@ -674,6 +682,100 @@ class _BatchedTranslationLinkPredictionFn(torch.autograd.Function):
         d_ent = be.segment_sum_rows(dk, inp["known_inv"][0], inp["known_inv"][1], ent_rows.shape[0])
         d_rel = be.segment_sum_rows(dr, inp["rel_inv"][0], inp["rel_inv"][1], rel.shape[0])
         return d_ent, d_rel, d_big, None
+
+
+_L1_MIX_METHODS = ("l1_mix_ce_fwd", "l1_mix_ce_bwd_q", "l1_mix_ce_bwd_table", "l1_mix_scores")
+
+
+def gated_translation_supported(be=None):
+    """True when the installed backend has the gated L1 (post-aggregation TransE) kernels; without them the tensor path stays."""
+    be = get_backend() if be is None else be
+    return all(hasattr(be, m) for m in _L1_MIX_METHODS)
+
+
+class _BatchedGatedTranslationLinkPredictionFn(torch.autograd.Function):
+    """_BatchedGatedLinkPredictionFn for TransE, one autograd node over ALL windows' rows:
+        q    = (w_known * loc_rows[known_a] + (1 - w_known) * rec_rows[known]) +- rel[rel_idx]     (temp_gated_query_fwd, kind transE;
+                                                                                                  known_a < 0: the temporal row alone)
+        e    = w_cand[row] * big_loc[window(row) * N + cand[row, :]] + (1 - w_cand[row]) * big_rec[...]   (formed in registers)
+        s    = -|q[row] - e|_1,   loss = sum_rows w_row * CE(s[row, :], label 0)                    (temp_l1_mix_ce_fwd, one launch)
+    |q - e|_1 is not linear in the candidate, so unlike the bilinear node the mix cannot live on two score matrices: the kernels read
+    both all-entity rows of every candidate.  The backward: the softmax gradient, d_q and d_w_cand (temp_l1_mix_ce_bwd_q), both
+    tables' adjoints in one pass over the slot lists (temp_l1_mix_ce_bwd_table), one gated-query pass and three segment sums."""
+
+    @staticmethod
+    def forward(ctx, loc_rows, rec_rows, rel, big_loc, big_rec, w_known, w_cand, inp):
+        be = get_backend()
+        N = big_loc.shape[0] // len(inp["splits"])
+        q = _gated_query_fwd(be, "transE", loc_rows, inp["known_a"], rec_rows, inp["known"], w_known, rel, inp["rel"], inp["is_tail"])
+        base = inp["window"] * N
+        s, loss_rows, lse = be.l1_mix_ce_fwd(q, big_loc, big_rec, w_cand, base, inp["cand"])
+        ctx.save_for_backward(loc_rows, rec_rows, rel, big_loc, big_rec, w_known, w_cand, q, s, lse, base)
+        ctx.inp = inp
+        return (loss_rows * inp["weights"]).sum()
+
+    @staticmethod
+    def backward(ctx, d_loss):
+        loc_rows, rec_rows, rel, big_loc, big_rec, w_known, w_cand, q, s, lse, base = ctx.saved_tensors
+        inp = ctx.inp
+        be = get_backend()
+        g, d_q, d_wc = be.l1_mix_ce_bwd_q(q, big_loc, big_rec, w_cand, base, inp["cand"], s, lse, d_loss.reshape(1).contiguous(), 1.0,
+                                          inp["weights"])
+        slot_ptr, slot = _cached_l1_slots(inp, inp["cand"], base, big_loc.shape[0])
+        d_big_loc, d_big_rec = be.l1_mix_ce_bwd_table(q, big_loc, big_rec, w_cand, slot_ptr, slot, g)
+        da, db, dr, d_wk = _gated_query_bwd(be, "transE", loc_rows, inp["known_a"], rec_rows, inp["known"], w_known, rel, inp["rel"],
+                                            inp["is_tail"], d_q)
+        d_loc = be.segment_sum_rows(da, inp["known_a_inv"][0], inp["known_a_inv"][1], loc_rows.shape[0])
+        d_rec = be.segment_sum_rows(db, inp["known_inv"][0], inp["known_inv"][1], rec_rows.shape[0])
+        d_rel = be.segment_sum_rows(dr, inp["rel_inv"][0], inp["rel_inv"][1], rel.shape[0])
+        return (d_loc, d_rec, d_rel, d_big_loc, d_big_rec, d_wk.reshape(w_known.shape) if ctx.needs_input_grad[5] else None,
+                d_wc.reshape(w_cand.shape) if ctx.needs_input_grad[6] else None, None)
+
+
+class _BatchedEnsembleTranslationLinkPredictionFn(torch.autograd.Function):
+    """_BatchedEnsembleLinkPredictionFn for TransE (the score-level ensemble of the post-ensemble models): each stream scores its own
+    translation query against its own all-entity stack at the candidates (temp_l1_ce_fwd; its lse and loss are not used), the
+    mixed score m = w s_loc + (1 - w) s_rec and its logsumexp are (rows, C) torch passes.  The backward hands the kernels the MIXED
+    softmax: temp_l1_ce_bwd_q with s = m, lse = lse_m and row_scale = weights * w (resp. weights * (1 - w)) gives each stream's
+    score gradient and d_q, temp_l1_ce_bwd_table its table adjoint; d_w = sum_k G_k (s_loc - s_rec) with G the unsplit gradient."""
+
+    @staticmethod
+    def forward(ctx, loc_rows, rec_rows, rel, big_loc, big_rec, w, inp):
+        be = get_backend()
+        N = big_loc.shape[0] // len(inp["splits"])
+        base = inp["window"] * N
+        qs, sc = [], []
+        for rows, big in ((loc_rows, big_loc), (rec_rows, big_rec)):
+            q = be.bilinear_query_fwd("transE", rows, inp["known"], rel, inp["rel"], inp["is_tail"])
+            qs.append(q)
+            sc.append(be.l1_ce_fwd(q, big, base, inp["cand"])[0])
+        mixed = torch.lerp(sc[1], sc[0], w)                          # w (rows, 1): w * local + (1 - w) * temporal
+        lse = torch.logsumexp(mixed, dim=1)
+        ctx.save_for_backward(loc_rows, rec_rows, rel, big_loc, big_rec, w, qs[0], qs[1], sc[0], sc[1], mixed, lse, base)
+        ctx.inp = inp
+        return ((lse - mixed[:, 0]) * inp["weights"]).sum()
+
+    @staticmethod
+    def backward(ctx, d_loss):
+        loc_rows, rec_rows, rel, big_loc, big_rec, w, q_l, q_r, s_l, s_r, mixed, lse, base = ctx.saved_tensors
+        inp = ctx.inp
+        be = get_backend()
+        scale = d_loss.reshape(1).contiguous()
+        wv = w.reshape(-1)
+        slot_ptr, slot = _cached_l1_slots(inp, inp["cand"], base, big_loc.shape[0])
+        outs, d_rel, gs = [], None, []
+        for rows, big, q, rs in ((loc_rows, big_loc, q_l, inp["weights"] * wv), (rec_rows, big_rec, q_r, inp["weights"] * (1 - wv))):
+            g, d_q = be.l1_ce_bwd_q(q, big, base, inp["cand"], mixed, lse, scale, 1.0, rs.contiguous())
+            gs.append(g)
+            d_big = be.l1_ce_bwd_table(q, big, slot_ptr, slot, g)
+            dk, dr = be.bilinear_query_bwd("transE", rows, inp["known"], rel, inp["rel"], inp["is_tail"], d_q)
+            outs.append((be.segment_sum_rows(dk, inp["known_inv"][0], inp["known_inv"][1], rows.shape[0]), d_big))
+            d_rel = dr if d_rel is None else d_rel + dr
+        d_rel = be.segment_sum_rows(d_rel, inp["rel_inv"][0], inp["rel_inv"][1], rel.shape[0])
+        d_w = None
+        if ctx.needs_input_grad[5]:
+            d_w = ((gs[0] + gs[1]) * (s_l - s_r)).sum(dim=1, keepdim=True)           # g_loc + g_rec = the unsplit mixed-score gradient
+        return outs[0][0], outs[1][0], d_rel, outs[0][1], outs[1][1], d_w, None
 
 
 def batched_link_prediction(ent_rows, rel, big, kind, inputs):

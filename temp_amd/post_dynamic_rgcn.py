@@ -281,7 +281,7 @@ class _PostWindowMixin:
         """The ensemble loss of ALL windows as one fused node (functional.batched_ensemble_link_prediction), or None when the scorer
         / shapes need the per-window path.  locs / recs: per-window target rows of the two streams; alls: see _stacked_alls;
         weights: per window (weight_subject (P, 1), weight_object (P, 1))."""
-        if not self.bilinear_loss_ok(self.embed_size):          # (the score-level mix of two TransE streams keeps the per-window path)
+        if not self.fused_loss_ok(self.embed_size):             # (TransE: the L1 node per stream, the mix on the (rows, C) scores)
             return None
         inp = self.cached_loss_inputs(wb, "_ens_inputs", samples, wb.target.sizes, head_as_tail=self.head_scored_as_tail)
         if inp is None:
@@ -312,6 +312,14 @@ class _PostWindowMixin:
             w = torch.cat([w_object.reshape(-1, 1), w_subject.reshape(-1, 1)], dim=0)
             cand = torch.cat([neg_tail, neg_head], dim=0).to(torch.int32).contiguous()
             return 2.0 * TF.candidate_cross_entropy_mixed(qs[0], all_loc, qs[1], all_rec, w, cand)
+        if self.translation_loss_ok(self.embed_size) and P > 0:
+            # TransE: the one-window form of the batched node (the L1 candidate kernels per stream, the mix on the (2P, C) scores)
+            from .tkg_module import TKG_Module
+            dev = loc.device
+            inp = TKG_Module.loss_inputs([0], [(triplets.to(torch.int64), neg_tail, neg_head)], dev, loc.shape[0], self.rel_embeds.shape[0],
+                                         head_as_tail=self.head_scored_as_tail)
+            w = torch.cat([w_object.reshape(-1, 1), w_subject.reshape(-1, 1)], dim=0)
+            return TF.batched_ensemble_link_prediction(loc, rec, self.rel_embeds, all_loc, all_rec, w, name, inp)
         labels = torch.zeros(triplets.shape[0], dtype=torch.int64, device=triplets.device)
         out = 0
         for neg, tail, w in ((neg_tail, True, w_object), (neg_head, False, w_subject)):
@@ -486,8 +494,9 @@ class _PostAggregationMixin(_TwoStreamMixin):
       tail rows: known subject w_oqs * s_loc + (1 - w_oqs) * s_rec, candidates w_oqo * all_loc[c] + (1 - w_oqo) * all_rec[c]
       head rows: known object = the TEMPORAL row alone (the reference's o_loc = o_rec = ent_embed_rec[o], :276-277: w_sqo has no
                  effect and no gradient), candidates w_sqs * all_loc[c] + (1 - w_sqs) * all_rec[c]
-    Both scorers are linear in the candidate: the fused node (functional.batched_gated_link_prediction) mixes the two score matrices
-    at the candidate columns.  Reference quirk kept: w_sqo comes from subject_query_SUBJECT_embed_linear and w_oqo from
+    DistMult and ComplEx are linear in the candidate: their fused node (functional.batched_gated_link_prediction) mixes the two score
+    matrices at the candidate columns.  TransE's L1 distance is not: its node reads both all-entity rows of every candidate and
+    mixes them in registers (temp_l1_mix_ce_fwd / _bwd_q / _bwd_table).  Reference quirk kept: w_sqo comes from subject_query_SUBJECT_embed_linear and w_oqo from
     object_query_SUBJECT_embed_linear (calc_ensemble_ratio, :284-321), so the two *_object_embed_linear MLPs never get a gradient."""
     _evaluater = "PostEvaluationFilter"
 
@@ -541,8 +550,15 @@ class _PostAggregationMixin(_TwoStreamMixin):
         w = torch.cat([w_o, w_s]).index_select(0, perm)
         return w, w
 
+    def _gated_translation_ok(self):
+        """TransE takes the gated L1 node: the L1 condition (translation_loss_ok) and a backend with the gated L1 kernels.  No
+        condition on num_ents: nothing is a GEMM."""
+        return self.translation_loss_ok(self.embed_size) and TF.gated_translation_supported()
+
     def _gated_fused_ok(self):
-        return self.bilinear_loss_ok(self.embed_size)           # (the candidate mix is not linear for TransE's L1: the literal route)
+        """A fused gated node applies: the score-matrix node of the bilinear scorers, or the L1 node of TransE (whose candidate mix
+        is not linear, so it is formed inside the kernels)."""
+        return self.bilinear_loss_ok(self.embed_size) or self._gated_translation_ok()
 
     def batched_gated_loss(self, wb, locs, recs, alls, samples, gates):
         """The gated loss of ALL windows as one fused node, or None when the scorer / shapes need the per-window path.
@@ -565,7 +581,7 @@ class _PostAggregationMixin(_TwoStreamMixin):
 
     def gated_loss(self, loc, rec, all_loc, all_rec, triplets, neg_tail, neg_head, w_sqs, w_sqo, w_oqs, w_oqo):
         """loss_tail + loss_head of one target graph, models/PostDynamicRGCN.py:200-202 + train_link_prediction :261-282."""
-        if self._gated_fused_ok() and triplets.shape[0] > 0 and all_loc.shape[0] % 4 == 0:
+        if triplets.shape[0] > 0 and (self._gated_translation_ok() or (self._gated_fused_ok() and all_loc.shape[0] % 4 == 0)):
             return TF.gated_link_prediction(loc, rec, self.rel_embeds, all_loc, all_rec, triplets, neg_tail, neg_head,
                                             w_sqs, w_sqo, w_oqs, w_oqo, self.args.score_function)
         labels = torch.zeros(triplets.shape[0], dtype=torch.int64, device=triplets.device)
