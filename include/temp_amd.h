@@ -178,7 +178,10 @@ enum {
 };
 long long temp_rgcn_route_launches(int route, int s);
 /* Development only: a device buffer of `words` int64 into which instrumented kernels write cycle-counter stamps (NULL: off).
- * Not used by the product path or the tests. */
+ * The edge kernels stamp 8 words per block into its first 32768 words (launches of more than 4096 blocks do not stamp).  A buffer of
+ * 32768 + 4096 words or more also switches the f16 chain launchers to their stamped instantiations, which write words 32768 .. 36863
+ * (csrc/gru_chain_hx.hpp: CHX_STAMP_WORDS; tools/chain_phases.py reads them); a smaller buffer leaves the chain kernels as they are.
+ * Not used by the product path. */
 void temp_set_debug_buffer(void* device_ptr, size_t words);
 
 /* ------------------------------------------------------------------------------------------------

@@ -116,6 +116,12 @@ __device__ __forceinline__ float4 drop4(const DropSpec& d, unsigned row, unsigne
 // process-wide kernel-selection switches (include/temp_amd.h: temp_set_option); definition in runtime.hip
 int option(int key);
 void hx_count();                            // diagnostic counter of f16-split kernel launches (temp_f16_launches)
+// development only (temp_set_debug_buffer): the buffer's first DEBUG_EDGE_WORDS int64 belong to the edge kernels (8 stamps per block),
+// what lies behind them to the chain kernels.  debug_buffer_chain(words): the region behind the edge kernels' when the buffer holds
+// DEBUG_EDGE_WORDS + words or more, else nullptr -- a buffer set for the edge kernels alone never switches the chain launchers to
+// their stamped instantiations, and neither side can write into the other's words (definition in rgcn_kernels.hip)
+#define DEBUG_EDGE_WORDS (8 * 4096)
+long long* debug_buffer_chain(size_t words);
 void gemm_route_count(int route, int width);   // diagnostic: one launch of dense-product kernel TEMP_ROUTE_* <width> (temp_gemm_route_launches)
 void rgcn_route_count(int route, int s);       // diagnostic: one launch of edge kernel TEMP_RGCN_* <s> (temp_rgcn_route_launches)
 

@@ -41,6 +41,7 @@ struct ChainArgs {
   size_t plane;
   ChainRnn rnn[TEMP_CHAIN_MAX_RNN];
   float* d_arg;                          // nullable (backward, learnable decay): [N_total] dL / d(w dt + b) of every row with a previous state
+  long long* stamp;                      // development only (temp_set_debug_buffer): cycle stamps of the f16 kernels' DEV instantiations, else nullptr
 };
 struct ChainUps { const float* p[TEMP_CHAIN_MAX_UP]; };
 
@@ -753,7 +754,7 @@ static ChainArgs chain_args(const TempGruChain* c, const TempChainDecay* decay =
   const ChainGeom g = chain_geom(c->d);
   a.D = c->d; a.n_panels = c->n_panels; a.max_steps = c->max_steps; a.panel = c->panel; a.rows = c->rows; a.sinfo = c->sinfo; a.dt = c->dt;
   a.layout = c->pack_layout;
-  a.n_rnn_keys = c->n_rnn; a.lambda = c->lambda; a.plane = c->saved_plane; a.gi_index = c->gi_index; a.dbg = option(TEMP_OPT_DEBUG) >> 8;      // development A/B switches (bit 6: no per-block rotation of the slab walk); 0 in every product run
+  a.n_rnn_keys = c->n_rnn; a.lambda = c->lambda; a.plane = c->saved_plane; a.gi_index = c->gi_index; a.dbg = option(TEMP_OPT_DEBUG) >> 8; a.stamp = debug_buffer_chain(CHX_STAMP_WORDS);      // development A/B switches (bit 6: no per-block rotation of the slab walk); 0 in every product run
   for (int i = 0; i < c->n_rnn; ++i) {
     a.rnn[i].wf = (const float4*)c->packed[i];
     a.rnn[i].wb = (const float4*)c->packed[i] + (a.layout == TEMP_CHAIN_PACK_BX ? (size_t)(g.NQ >> 1) * g.NT * 192 : (size_t)g.NT * g.NQ * 64);
@@ -861,6 +862,12 @@ static int launch_chain_bwd(const ChainArgs& a, const ChainUps& ups, const float
       static bool attr_5 = false;
       auto kernel = k_gru_chain_bwd_hx<VARIANT, TPWB, 8, G4, 4, 5>;
       int rc = chain_lds_attr(kernel, lds_hx, &attr_5);
+      if (rc) return rc;
+      TEMP_LAUNCH(K_GRU_CHAIN_BWD, kernel, dim3(a.n_panels), dim3(768), lds_hx, st, a, ups, saved, dgi, dgh, row_keys, col_keys);
+    } else if (cfg != 2 && a.stamp && VARIANT == TEMP_GRU_TORCH && TPWB == 2 && G4 == 1) {     // (development: the headline instantiation with cycle stamps)
+      static bool attr_dev = false;
+      auto kernel = k_gru_chain_bwd_hx<TEMP_GRU_TORCH, 2, 8, 1, 4, 4, 1>;
+      int rc = chain_lds_attr(kernel, lds_hx, &attr_dev);
       if (rc) return rc;
       TEMP_LAUNCH(K_GRU_CHAIN_BWD, kernel, dim3(a.n_panels), dim3(768), lds_hx, st, a, ups, saved, dgi, dgh, row_keys, col_keys);
     } else if (cfg != 2) {
@@ -1076,25 +1083,22 @@ static int chain_fwd_x(const TempGruChain* c, const TempChainDecay* decay, const
     X.b_ih[i] = b_ih[i];
     X.wi[i] = reinterpret_cast<const hx_u32x4*>(c->packed[i] + chain_x_ih_offset(c->d));
   }
-  static bool attr = false;
   const size_t lds = chain_lds_fwd_x(c->d, c->max_steps);
   // 8 + 8 waves as k_gru_chain_fwd_hx's default configuration: two matrix waves per SIMD, 128 registers each
   hipStream_t st = (hipStream_t)stream;
-  if ((gx.NT + 7) / 8 == 3) {
-    auto kernel = k_gru_chain_fwd_x<3, 8, 8>;
-    if ((rc = chain_lds_attr(kernel, lds, &attr))) return rc;
+  // the development instantiation (cycle stamps, the switches of a.dbg) only where a debug buffer or TEMP_DEBUG asks for it
+  const bool dev = a.stamp || (a.dbg & (1 | 2 | 4 | 64 | 2048 | 4096));
+  const int tpw = (gx.NT + 7) / 8;
+  auto launch = [&](auto kernel, bool* granted) {
+    if ((rc = chain_lds_attr(kernel, lds, granted))) return rc;
     TEMP_LAUNCH(K_GRU_CHAIN_FWD, kernel, dim3(a.n_panels), dim3(1024), lds, st, a, X, h_out, saved);
-  } else if ((gx.NT + 7) / 8 == 2) {
-    static bool attr2 = false;
-    auto kernel = k_gru_chain_fwd_x<2, 8, 8>;
-    if ((rc = chain_lds_attr(kernel, lds, &attr2))) return rc;
-    TEMP_LAUNCH(K_GRU_CHAIN_FWD, kernel, dim3(a.n_panels), dim3(1024), lds, st, a, X, h_out, saved);
-  } else {
-    static bool attr1 = false;
-    auto kernel = k_gru_chain_fwd_x<1, 8, 8>;
-    if ((rc = chain_lds_attr(kernel, lds, &attr1))) return rc;
-    TEMP_LAUNCH(K_GRU_CHAIN_FWD, kernel, dim3(a.n_panels), dim3(1024), lds, st, a, X, h_out, saved);
-  }
+    return (int)TEMP_OK;
+  };
+  static bool attr3 = false, attr2 = false, attr1 = false, attr3d = false, attr2d = false, attr1d = false;
+  if (tpw == 3) rc = dev ? launch(k_gru_chain_fwd_x<3, 8, 8, 1>, &attr3d) : launch(k_gru_chain_fwd_x<3, 8, 8>, &attr3);
+  else if (tpw == 2) rc = dev ? launch(k_gru_chain_fwd_x<2, 8, 8, 1>, &attr2d) : launch(k_gru_chain_fwd_x<2, 8, 8>, &attr2);
+  else rc = dev ? launch(k_gru_chain_fwd_x<1, 8, 8, 1>, &attr1d) : launch(k_gru_chain_fwd_x<1, 8, 8>, &attr1);
+  if (rc) return rc;
   hx_count();
   g_fwd_x_launches.fetch_add(1, std::memory_order_relaxed);
   return launch_status();

@@ -22,6 +22,29 @@ namespace temp {
 #define CHX_STATE_SCALE 16384.f
 #define CHX_STATE_INV (1.f / 16384.f)
 
+// Development only: cycle stamps of k_gru_chain_fwd_x and k_gru_chain_bwd_hx (their DEV = 1 instantiations, launched when a debug
+// buffer is set: temp_set_debug_buffer; tools/chain_phases.py prints them).  Lane 0 of the first wave of each role stamps the first
+// panel of block 0 and of the mid-grid block: [kernel fwd, bwd][block 0, mid][role matrix, memory][position < CH_MAX_STEPS][8 events].
+//   forward   matrix: 0 position begins (behind B / Q)  1 h walk done  2 at A  3 past A  4 x walk done, at B  5 past B
+//             memory: 0 position begins  1 x split done, at A  2 past A  3 x loads issued, gates begin  4 gates done, at B  5 past B
+//   backward  matrix: 0 at A  1 past A  2 walk done  3 d_prev stored, at B  4 past B
+//             memory: 0 gates begin  1 gates done, at A  2 past A  3 prefetch issued, at B  4 past B
+#define CHX_STAMP_EVENTS 8
+#define CHX_STAMP_BLOCK (2 * CH_MAX_STEPS * CHX_STAMP_EVENTS)
+#define CHX_STAMP_WORDS (2 * 2 * CHX_STAMP_BLOCK)
+// the stamp rows of this wave (nullptr: none): kernel 0 = forward, 1 = backward; role 0 = matrix, 1 = memory
+template <int DEV>
+__device__ __forceinline__ long long* chx_stamp_rows(long long* stamp, int kernel, int role, bool first_wave, int lane) {
+  if constexpr (DEV) {
+    if (!stamp || !first_wave || lane != 0) return nullptr;
+    const int mid = (int)(gridDim.x >> 1);
+    const int sel = blockIdx.x == 0 ? 0 : ((int)blockIdx.x == mid ? 1 : -1);
+    return sel < 0 ? nullptr : stamp + ((size_t)(kernel * 2 + sel) * 2 + role) * (CH_MAX_STEPS * CHX_STAMP_EVENTS);
+  }
+  return nullptr;
+}
+#define CHX_STAMP(s, k) do { if constexpr (DEV) { if (stp) stp[(s) * CHX_STAMP_EVENTS + (k)] = (long long)__builtin_readcyclecounter(); } } while (0)
+
 struct ChainGeomHx {
   int NT, NS;        // forward: tiles of 32 gate columns (3d), slabs of 16 k (d)
   int NTb, NSb;      // backward: tiles of 32 state columns (d), slabs of 16 k (3d) rounded up to a multiple of 8 (zero slabs)
@@ -295,7 +318,8 @@ inline size_t chain_lds_fwd_x(int D, int ms) {
 }
 // NMW matrix waves with TPW tiles each (NMW * TPW >= NT), MW memory waves; one register set of weight planes (two matrix waves
 // per SIMD cover each other's L2 latency)
-template <int TPW, int MW, int NMW>
+// DEV = 1: the development instantiation (cycle stamps, see CHX_STAMP)
+template <int TPW, int MW, int NMW, int DEV = 0>
 __global__ void __launch_bounds__(64 * (NMW + MW)) k_gru_chain_fwd_x(ChainArgs a, ChainX X, float* __restrict__ H, float* __restrict__ saved) {
   extern __shared__ __attribute__((aligned(16))) float lds[];
   constexpr int PASSES = CH_SLOTS / MW;
@@ -313,6 +337,7 @@ __global__ void __launch_bounds__(64 * (NMW + MW)) k_gru_chain_fwd_x(ChainArgs a
   int* flagb = (int*)(decb + CH_SLOTS * a.max_steps);            // [ms] step flags
   const int tid = threadIdx.x, wave = __builtin_amdgcn_readfirstlane(tid >> 6), lane = tid & 63;
   const size_t plane = a.plane;
+  const int dbg = DEV ? a.dbg : 0;                               // (the development switches exist in the DEV instantiation only, but for bit 1: see the gate passes)
 
   // (each role runs its own panel loop: the loop invariants of one role are not hoisted above the role branch next to the
   //  other's, where both sets would be live at once)
@@ -345,23 +370,27 @@ __global__ void __launch_bounds__(64 * (NMW + MW)) k_gru_chain_fwd_x(ChainArgs a
       hx_u32x4 w[2][TPW] = {};                                   // [plane h, l][tile]: one slab of the stream being walked
       const std::integral_constant<int, 0> P0;
       const std::integral_constant<int, 1> P1;
-      auto wload = [&](const hx_u32x4* wp, int sl, auto pl_c) __attribute__((always_inline)) {
+      // ln: the lane index (a walk hands in a copy the compiler cannot tell from a fresh value, so that the lane-dependent
+      // addresses of a walk are formed at its head instead of living -- spilled -- across the whole position)
+      auto wload = [&](const hx_u32x4* wp, int sl, auto pl_c, int ln) __attribute__((always_inline)) {
         constexpr int pl = decltype(pl_c)::value;
 #pragma unroll
         for (int j = 0; j < TPW; ++j)
-          if (tval[j]) w[pl][j] = *reinterpret_cast<const hx_u32x4*>(reinterpret_cast<const char*>(wp) + (unsigned)((((sl * NT + tidx[j]) * 2 + pl) * 64 + lane) * 16));
+          if (tval[j]) w[pl][j] = *reinterpret_cast<const hx_u32x4*>(reinterpret_cast<const char*>(wp) + (unsigned)((((sl * NT + tidx[j]) * 2 + pl) * 64 + ln) * 16));
       };
-      const int rot = (a.dbg & 64) ? 0 : (int)(blockIdx.x >> 3) % NS;
+      const int rot = (dbg & 64) ? 0 : (int)(blockIdx.x >> 3) % NS;
       auto at = [&](int j) { const int v = rot + j; return v < NS ? v : v - NS; };
       // the walks issue ahead of the memory waves' gate arithmetic on the same SIMD (dbg bit 12: development A/B, equal priority)
-      const bool prio = !(a.dbg & 4096);
+      const bool prio = !(dbg & 4096);
       // a walk over the NS slabs of one stream (wcur) with the fragments of `pl0` (the state or the x planes); behind its last slab
       // the registers are refilled with the first slab of the stream walked next (wnext)
       bool holds_ih = true;
-      wload(wpi, rot, P0); wload(wpi, rot, P1);
+      wload(wpi, rot, P0, lane); wload(wpi, rot, P1, lane);
       // prod = false (development probe, dbg bits 0 / 11): the weights stream, no products issue
       auto walk = [&](const bool prod, const char* pl0, const hx_u32x4* wcur, const hx_u32x4* wnext) __attribute__((always_inline)) {
-        const char* arow = pl0 + (size_t)li * ldp + 16 * hh;
+        int ln = lane;
+        asm volatile("" : "+v"(ln));
+        const char* arow = pl0 + (size_t)(ln & 31) * ldp + 16 * (ln >> 5);
         const int pl1 = CH_SLOTS * ldp;
         hx_u32x4 FH = *reinterpret_cast<const hx_u32x4*>(arow + 32 * rot), FL = *reinterpret_cast<const hx_u32x4*>(arow + pl1 + 32 * rot), NH, NL;
         if (prio) __builtin_amdgcn_s_setprio(2);
@@ -379,7 +408,7 @@ __global__ void __launch_bounds__(64 * (NMW + MW)) k_gru_chain_fwd_x(ChainArgs a
             else asm volatile("" : : "v"(w[1][t]));
           }
           __builtin_amdgcn_sched_barrier(0);
-          wload(wn, sn, P1);
+          wload(wn, sn, P1, ln);
           __builtin_amdgcn_sched_barrier(0);
           if (prod) {
 #pragma unroll
@@ -391,15 +420,15 @@ __global__ void __launch_bounds__(64 * (NMW + MW)) k_gru_chain_fwd_x(ChainArgs a
             for (int t = 0; t < TPW; ++t) asm volatile("" : : "v"(w[0][t]));
           }
           __builtin_amdgcn_sched_barrier(0);
-          wload(wn, sn, P0);
+          wload(wn, sn, P0, ln);
           FH = NH; FL = NL;
         }
         if (prio) __builtin_amdgcn_s_setprio(0);
       };
       // x . W_ih of the next position into acc, then into the units the rest of the position expects
       auto xprod = [&]() __attribute__((always_inline)) {
-        if (!holds_ih) { wload(wpi, rot, P0); wload(wpi, rot, P1); }
-        walk(!(a.dbg & (1 | 2048)), xpl, wpi, wph);
+        if (!holds_ih) { wload(wpi, rot, P0, lane); wload(wpi, rot, P1, lane); }
+        walk(!(dbg & (1 | 2048)), xpl, wpi, wph);
         holds_ih = false;
         const float f = hx_inv_scale(xkey[li]) * CHX_STATE_SCALE;       // (x . s_row) -> (x . 2^14): the units of the state's planes
 #pragma unroll
@@ -407,6 +436,7 @@ __global__ void __launch_bounds__(64 * (NMW + MW)) k_gru_chain_fwd_x(ChainArgs a
 #pragma unroll
           for (int r = 0; r < 16; ++r) acc[j][r] *= f;
       };
+      long long* stp = p == (int)blockIdx.x ? chx_stamp_rows<DEV>(a.stamp, 0, 0, wave == 0, lane) : nullptr;
       if (ns > 0) {
         __syncthreads();      // P: the x planes of position 0 are in LDS
         xprod();
@@ -414,6 +444,7 @@ __global__ void __launch_bounds__(64 * (NMW + MW)) k_gru_chain_fwd_x(ChainArgs a
       }
       for (int s = 0; s < ns; ++s) {
         const int flags = flagb[s];
+        CHX_STAMP(s, 0);
         // gi_n of position s -> gin, out of the accumulators
 #pragma unroll
         for (int j = 0; j < TPW; ++j) {
@@ -426,11 +457,12 @@ __global__ void __launch_bounds__(64 * (NMW + MW)) k_gru_chain_fwd_x(ChainArgs a
             acc[j][4 * qq] = 0.f; acc[j][4 * qq + 1] = 0.f; acc[j][4 * qq + 2] = 0.f; acc[j][4 * qq + 3] = 0.f;
           }
         }
-        if ((flags & 1) && !(a.dbg & 1)) {
-          if (holds_ih) { wload(wph, rot, P0); wload(wph, rot, P1); }
+        if ((flags & 1) && !(dbg & 1)) {
+          if (holds_ih) { wload(wph, rot, P0, lane); wload(wph, rot, P1, lane); }
           walk(true, hpl, wph, wpi);
           holds_ih = true;
         }
+        CHX_STAMP(s, 1);
         // lane (li, hh) owns track li and, per register quad qq, gate columns tile*32 + 8qq + 4hh .. +3
 #pragma unroll
         for (int j = 0; j < TPW; ++j) {
@@ -442,9 +474,13 @@ __global__ void __launch_bounds__(64 * (NMW + MW)) k_gru_chain_fwd_x(ChainArgs a
             acc[j][4 * qq] = 0.f; acc[j][4 * qq + 1] = 0.f; acc[j][4 * qq + 2] = 0.f; acc[j][4 * qq + 3] = 0.f;
           }
         }
+        CHX_STAMP(s, 2);
         __syncthreads();      // A: products of position s (and gin) are in LDS; the x planes of s + 1 too
+        CHX_STAMP(s, 3);
         if (s + 1 < ns) xprod();
+        CHX_STAMP(s, 4);
         __syncthreads();      // B: the split (decayed) state of position s is in LDS
+        CHX_STAMP(s, 5);
       }
     __syncthreads();          // LDS is re-initialised for the next panel
   }
@@ -478,15 +514,32 @@ __global__ void __launch_bounds__(64 * (NMW + MW)) k_gru_chain_fwd_x(ChainArgs a
       }
       float4 hdr[PASSES];                                        // dec(s + 1) . h(s) of this lane's columns of its tracks (the fp32 state)
       float4 xr[PASSES];                                         // x rows of a coming position
+      int xi[PASSES];                                            // their x row indices (-1: idle track), wave-uniform: scalar registers
 #pragma unroll
       for (int ps = 0; ps < PASSES; ++ps) hdr[ps] = zero4();
-      auto xload = [&](int s) __attribute__((always_inline)) {
+      // The x row of a chain row goes through x_index: a load that the row load depends on.  A wave's track entries are the same in
+      // every lane, so the indices of a position are read with scalar loads, all passes at once, ONE POSITION AHEAD of the row
+      // loads that use them -- xload() then issues its rows without waiting for anything (four dependent L2 round trips per
+      // position in front of the gate passes otherwise).  x_index is not written during the launch: the constant address space
+      // lets the compiler keep the loads scalar beside the kernel's stores.
+      typedef const int32_t __attribute__((address_space(4))) * chx_const_idx;
+      const chx_const_idx xidx = (chx_const_idx)(uintptr_t)X.x_index;
+      auto xindex = [&](int s) __attribute__((always_inline)) {
+        int e[PASSES];
+#pragma unroll
+        for (int ps = 0; ps < PASSES; ++ps) e[ps] = tabb[s * CH_SLOTS + ps * MW + mw];
+        __builtin_amdgcn_sched_barrier(0);                       // (all the table reads, then all the index loads: one wait each)
 #pragma unroll
         for (int ps = 0; ps < PASSES; ++ps) {
-          const int e = tabb[s * CH_SLOTS + ps * MW + mw];
-          const bool ok = e >= 0 && cact && !(a.dbg & 4);       // (dbg bit 2: development ablation, no x loads)
-          const size_t xrow = ok ? (size_t)X.x_index[e & CH_ROW_MASK] : 0;
-          xr[ps] = ok ? ld4(X.x + xrow * D + col) : zero4();
+          const int es = __builtin_amdgcn_readfirstlane(e[ps]);
+          xi[ps] = (es >= 0 && !(dbg & 4)) ? xidx[es & CH_ROW_MASK] : -1;     // (dbg bit 2: development ablation, no x loads)
+        }
+      };
+      auto xload = [&]() __attribute__((always_inline)) {
+#pragma unroll
+        for (int ps = 0; ps < PASSES; ++ps) {
+          xr[ps] = zero4();
+          if (xi[ps] >= 0 && cact) xr[ps] = ld4(X.x + (size_t)xi[ps] * D + col);
         }
       };
       // the loaded rows -> the x planes (scaled per row) and their keys
@@ -505,18 +558,30 @@ __global__ void __launch_bounds__(64 * (NMW + MW)) k_gru_chain_fwd_x(ChainArgs a
           if (lane == 0) xkey[slot] = key;
         }
       };
+      long long* stp = p == (int)blockIdx.x ? chx_stamp_rows<DEV>(a.stamp, 0, 1, mw == 0, lane) : nullptr;
       if (ns > 0) {
-        xload(0);
+        xindex(0);
+        xload();
+        if (ns > 1) xindex(1);
         xsplit();
         __syncthreads();      // P
-        if (ns > 1) xload(1);
+        if (ns > 1) xload();
         __syncthreads();      // Q
       }
       for (int s = 0; s < ns; ++s) {
         const int flags = flagb[s];
+        CHX_STAMP(s, 0);
+        if (s + 2 < ns) xindex(s + 2);                           // (issued here: they land while the matrix waves walk position s)
         if (s + 1 < ns) xsplit();                                // x(s + 1) for the matrix waves' window behind A
+        CHX_STAMP(s, 1);
         __syncthreads();      // A
-        if (s + 2 < ns) xload(s + 2);                            // in flight during the gates of s
+        CHX_STAMP(s, 2);
+        if (s + 2 < ns) xload();                                 // x(s + 2): in flight during the gates of s
+        // (the passes' LDS addresses are formed here, per position, from a copy of the column the compiler cannot tell from a fresh
+        //  value: hoisted out of the position loop they were spilled, and reloaded with a vmcnt(0) inside the gate passes)
+        int colv = col;
+        asm volatile("" : "+v"(colv));
+        CHX_STAMP(s, 3);
 #pragma unroll
         for (int ps = 0; ps < PASSES; ++ps) {
           const int slot = ps * MW + mw;
@@ -529,8 +594,8 @@ __global__ void __launch_bounds__(64 * (NMW + MW)) k_gru_chain_fwd_x(ChainArgs a
           if (e >= 0) {
             const size_t row = (size_t)(e & CH_ROW_MASK);
             const bool hp = (e & CH_HAS_PREV) != 0;
-            const float* ab = accb + (size_t)slot * lda + col;
-            const float4 pr = ld4(ab), pz = ld4(ab + D), pn = ld4(ab + 2 * D), gn = ld4(gin + (size_t)slot * ldn + col);
+            const float* ab = accb + (size_t)slot * lda + colv;
+            const float4 pr = ld4(ab), pz = ld4(ab + D), pn = ld4(ab + 2 * D), gn = ld4(gin + (size_t)slot * ldn + colv);
             const float4 hd = hp ? hdr[ps] : zero4();
             float o_h[4], o_r[4], o_z[4], o_n[4], o_hn[4];
             const float prv[4] = {pr.x, pr.y, pr.z, pr.w}, pzv[4] = {pz.x, pz.y, pz.z, pz.w}, pnv[4] = {pn.x, pn.y, pn.z, pn.w};
@@ -549,7 +614,10 @@ __global__ void __launch_bounds__(64 * (NMW + MW)) k_gru_chain_fwd_x(ChainArgs a
             }
             h4 = make_float4(o_h[0], o_h[1], o_h[2], o_h[3]);
             const size_t o = row * D + col;
-            if (!(a.dbg & 2)) {                                  // (development ablation: no global stores)
+            // (a.dbg bit 1, development ablation: no global stores.  The one switch read in every instantiation: with the stores in a
+            //  block of their own hipcc fuses the gate arithmetic above exactly as it did before the switches left the kernel --
+            //  without the test it forms two more packed FMAs per pass and the results move by an ulp)
+            if (!(a.dbg & 2)) {
               if (flags & 2) st4(H + o, h4);
               st4(saved + o, make_float4(o_r[0], o_r[1], o_r[2], o_r[3]));
               st4(saved + plane + o, make_float4(o_z[0], o_z[1], o_z[2], o_z[3]));
@@ -562,12 +630,14 @@ __global__ void __launch_bounds__(64 * (NMW + MW)) k_gru_chain_fwd_x(ChainArgs a
             hdr[ps] = hpn ? scale4(h4, decb[(s + 1) * CH_SLOTS + slot]) : zero4();
             hx_u32x2 SH, SL;
             hx_split4(hdr[ps], CHX_STATE_SCALE, SH, SL);
-            char* hdst = hpl + (size_t)slot * ldp + 2 * col;
+            char* hdst = hpl + (size_t)slot * ldp + 2 * colv;
             *reinterpret_cast<hx_u32x2*>(hdst) = SH;
             *reinterpret_cast<hx_u32x2*>(hdst + CH_SLOTS * ldp) = SL;
           }
         }
+        CHX_STAMP(s, 4);
         __syncthreads();      // B
+        CHX_STAMP(s, 5);
       }
     __syncthreads();          // LDS is re-initialised for the next panel
   }
@@ -578,7 +648,8 @@ __global__ void __launch_bounds__(64 * (NMW + MW)) k_gru_chain_fwd_x(ChainArgs a
 // row_keys (nullable): [N_total] key of max |[dr dz dn_i]| of every row; col_keys (nullable): [n_rnn + n_panels][4d]: the kernel writes row
 // n_rnn + p (panel p's column maxima), k_keys_reduce (hx_pack.hpp) reduces them into rows 0 .. n_rnn - 1
 // NMW matrix waves (4 or 8: one or two per SIMD) with TPWB = ceil(NTb / NMW) tiles each; RING = slabs of W_hh held in registers
-template <int VARIANT, int TPWB, int MW, int G4, int NMW = 4, int RING = 4>
+// DEV = 1: the development instantiation (cycle stamps, see CHX_STAMP)
+template <int VARIANT, int TPWB, int MW, int G4, int NMW = 4, int RING = 4, int DEV = 0>
 __global__ void __launch_bounds__(64 * (NMW + MW)) k_gru_chain_bwd_hx(ChainArgs a, ChainUps ups, const float* __restrict__ saved,
                                                                      float* __restrict__ dgi, float* __restrict__ dgh,
                                                                      unsigned* __restrict__ row_keys, unsigned* __restrict__ col_keys) {
@@ -639,9 +710,12 @@ __global__ void __launch_bounds__(64 * (NMW + MW)) k_gru_chain_bwd_hx(ChainArgs 
       for (int q = 0; q < RING; ++q) { wload(wh[q], rot + q, 0); wload(wl[q], rot + q, 1); }
       const char* arow = apl + (size_t)li * ldpa + 16 * hh;      // + plane * 32 ldpa + 32 slab
       const int pl1 = CH_SLOTS * ldpa;
+      long long* stp = p == (int)blockIdx.x ? chx_stamp_rows<DEV>(a.stamp, 1, 0, wave == 0, lane) : nullptr;
       for (int s = ns - 1; s >= 0; --s) {
         const int flags = flagb[s];
+        CHX_STAMP(s, 0);
         __syncthreads();      // A: the split gate gradients / dh*z / row scales of position s are in LDS
+        CHX_STAMP(s, 1);
         if ((flags & 1) && !(a.dbg & 1)) {                      // (dbg bit 0: development ablation, no products)
           hx_u32x4 FH = *reinterpret_cast<const hx_u32x4*>(arow + 32 * rot), FL = *reinterpret_cast<const hx_u32x4*>(arow + pl1 + 32 * rot), NH, NL;
           for (int j = 0, sl = rot; j < NSb; j += RING) {
@@ -668,6 +742,7 @@ __global__ void __launch_bounds__(64 * (NMW + MW)) k_gru_chain_bwd_hx(ChainArgs 
             }
             sl = base2;
           }
+          CHX_STAMP(s, 2);
           const float dec = decb[s * CH_SLOTS + li], ri = rinv[li];
 #pragma unroll
           for (int j = 0; j < TPWB; ++j) {
@@ -683,7 +758,9 @@ __global__ void __launch_bounds__(64 * (NMW + MW)) k_gru_chain_bwd_hx(ChainArgs 
             }
           }
         }
+        CHX_STAMP(s, 3);
         __syncthreads();      // B: d_prev of position s is in LDS
+        CHX_STAMP(s, 4);
       }
     } else {
       // ------------------------------------------------------------------ memory role: gate gradients
@@ -710,8 +787,10 @@ __global__ void __launch_bounds__(64 * (NMW + MW)) k_gru_chain_bwd_hx(ChainArgs 
           shd[ps] = ld4(src + 4 * plane);
         }
       };
+      long long* stp = p == (int)blockIdx.x ? chx_stamp_rows<DEV>(a.stamp, 1, 1, mw == 0, lane) : nullptr;
       prefetch(ns - 1);
       for (int s = ns - 1; s >= 0; --s) {
+        CHX_STAMP(s, 0);
         const int up_sel = upb[2 * s], up_row0 = upb[2 * s + 1];       // (staged in LDS: two dependent global loads per step otherwise)
         const float* upp = up_sel >= 0 ? ups.p[up_sel] : nullptr;
 #pragma unroll
@@ -783,9 +862,13 @@ __global__ void __launch_bounds__(64 * (NMW + MW)) k_gru_chain_bwd_hx(ChainArgs 
             }
           }
         }
+        CHX_STAMP(s, 1);
         __syncthreads();      // A
+        CHX_STAMP(s, 2);
         if (s > 0) prefetch(s - 1);            // issued behind the barrier (the matrix waves start at once), in flight while they
+        CHX_STAMP(s, 3);
         __syncthreads();      // B             // run position s
+        CHX_STAMP(s, 4);
       }
       if (col_keys && cact && NMW <= 4) {      // this lane's column maxima -> the panel's (LDS integer maxima over the eight waves)
 #pragma unroll

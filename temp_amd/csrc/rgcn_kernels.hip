@@ -668,6 +668,11 @@ static bool view_ok(const TempEdgeView& v) {
 static bool rgcn_tile_on() { return option(TEMP_OPT_RGCN_TILE) != 0; }
 static std::atomic<long long*> g_debug_buf{nullptr};         // development only (temp_set_debug_buffer)
 static std::atomic<size_t> g_debug_words{0};
+long long* debug_buffer_chain(size_t words) {
+  const size_t have = g_debug_words.load();
+  long long* buf = g_debug_buf.load();
+  return (buf && have >= (size_t)DEBUG_EDGE_WORDS + words) ? buf + DEBUG_EDGE_WORDS : nullptr;
+}
 static std::atomic<long long> g_tile_launches{0};           // diagnostic (temp_tile_launches): edge-kernel launches that took the LDS-tiled path
 
 // dynamic LDS beyond 64 KB must be granted per kernel function
@@ -683,7 +688,7 @@ static bool launch_agg_tile(const TempEdgeView& v, const TileArgs& t, const floa
   if (!granted) { (void)hipGetLastError(); return false; }
   const int grid = 8 * ceil_div(t.n_members, 8) * t.n_slices;
   TileArgs tp = t;
-  if (g_debug_words.load() >= (size_t)grid * 8) tp.prof = g_debug_buf.load();
+  if ((size_t)grid * 8 <= DEBUG_EDGE_WORDS && g_debug_words.load() >= (size_t)grid * 8) tp.prof = g_debug_buf.load();      // (the words behind: debug_buffer_chain)
   const int route = (MODE == MODE_FWD ? TEMP_RGCN_FWD_TILE8 : TEMP_RGCN_DX_TILE8) + (sizeof(BT) == 1 ? 0 : 1);
   if constexpr (S == 2 && MODE == MODE_FWD && sizeof(BT) == 1) {          // development ablations (TEMP_OPT_DEBUG), never set by the product
     const int var = option(TEMP_OPT_DEBUG);
