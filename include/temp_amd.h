@@ -634,6 +634,35 @@ int temp_gru_chain_bwd_decay(const TempGruChain* c, const TempChainDecay* decay,
 size_t temp_gru_chain_decay_reduce_workspace(const TempGruChain* c);
 int temp_gru_chain_decay_reduce(const TempGruChain* c, const float* d_arg, float* d_wb, void* ws, size_t ws_bytes, void* stream);
 long long temp_gru_chain_decay_launches(void);
+/* State offset (--use-time-embedding; models/RRGCN.py:192-204, models/BiRRGCN.py:228-240): the state a row hands on is
+ *   s_rho = GRU(x_rho, dec . s_prev) + table[index[rho]]
+ * -- the add follows the cell and becomes part of the recurrent state, so |s| is not bounded by 1.  table: DEVICE [n_rows][d], shared
+ * by all GRUs of the chain (layer_2.time_embed); index: DEVICE int32 [N_total], an entry outside [0, n_rows) (-1) = no offset.
+ * Pointers only, no host read: capturable.  The same launch code as the calls above, which are its offset == NULL case; `decay` is
+ * nullable (NULL = exp(-dt lambda)), so both compose.
+ *   Layout: the f16 kernels (TEMP_CHAIN_PACK_HX, _HX_X) split the state with the constant scale 2^14, which needs |state| < 4: an
+ *     offset chain runs on the TEMP_CHAIN_PACK_BX kernels (exact three-way bf16 split, any range), or _F32 where d % 8 != 0 or the
+ *     bf16 route is off.  temp_gru_chain_offset_layout(d) names that layout; temp_gru_chain_pack_multi_layout writes a given layout
+ *     (F32 / BX / HX) whatever the options select (temp_gru_chain_pack_multi = the layout temp_gru_chain_pack_layout(d) names).  An
+ *     offset with c->pack_layout HX / HX_X: TEMP_E_UNSUPPORTED, nothing launched.
+ *   temp_gru_chain_fwd_offset: h_out and the state kept for the next position are the sum; saved[4] stays the decayed previous
+ *     state (now dec . s_prev), so the gate arithmetic and the weight gradients are those of the calls above.  Consumers of saved[4]
+ *     must not assume |hdec| < 4 (temp_gru_grads_g4, not _g4_keys).
+ *   temp_gru_chain_bwd_offset: g4 == NULL: (dgi, dgh) as temp_gru_chain_bwd; g4 with dgi == dgh == NULL: temp_gru_chain_bwd_g4.
+ *     d_arg: required with `decay`, NULL without.  d_state (nullable) [N_total][d]: the total gradient reaching every row's state
+ *     (its upstream gradient + d_prev of its successor; ds/dh = I, so the gate gradients are unchanged); every row is written exactly
+ *     once with plain stores.  d_table is then the adjoint of the row gather table[index] applied to d_state (temp_gather_rows'
+ *     backward with a static inverse): no atomics, bit-repeatable.
+ *   temp_gru_chain_offset_launches: chain forward / backward launches with an offset since the library was loaded (diagnostic). */
+typedef struct TempChainOffset { const float* table; const int32_t* index; int32_t n_rows; } TempChainOffset;
+int temp_gru_chain_offset_supported(int d, int variant);
+int temp_gru_chain_offset_layout(int d);
+int temp_gru_chain_pack_multi_layout(int layout, int count, int d, const float* const* w_hh, float* const* packed, void* stream);
+int temp_gru_chain_fwd_offset(const TempGruChain* c, const TempChainDecay* decay, const TempChainOffset* offset, const float* gi, float* h_out,
+                              float* saved, void* stream);
+int temp_gru_chain_bwd_offset(const TempGruChain* c, const TempChainDecay* decay, const TempChainOffset* offset, const float* saved, int n_up,
+                              const float* const* up, float* dgi, float* dgh, float* g4, float* d_arg, float* d_state, void* stream);
+long long temp_gru_chain_offset_launches(void);
 
 /* ------------------------------------------------------------------------------------------------
  * Row gather / scatter helpers of the window loop

@@ -75,6 +75,10 @@ class TempChainDecay(ctypes.Structure):
     _fields_ = [("wb", c_vp * CHAIN_MAX_RNN)]      # device {w, b} of every GRU's learnable decay
 
 
+class TempChainOffset(ctypes.Structure):
+    _fields_ = [("table", c_vp), ("index", c_vp), ("n_rows", ctypes.c_int32)]      # device [n_rows, d] table, int32 [N_total] row of every chain row (-1: none)
+
+
 class TempSubsampleJob(ctypes.Structure):
     _fields_ = [("n_nodes", ctypes.c_int32), ("n_edges", ctypes.c_int32), ("keep", ctypes.c_int32), ("seed", ctypes.c_uint64),
                 ("parent", c_vp), ("child", c_vp), ("eid", c_vp),
@@ -177,6 +181,13 @@ SYMBOLS = {
     "temp_gru_chain_decay_reduce_workspace": (_SZ, [ctypes.POINTER(TempGruChain)]),
     "temp_gru_chain_decay_reduce": (_I, [ctypes.POINTER(TempGruChain), c_vp, c_vp, c_vp, _SZ, c_vp]),
     "temp_gru_chain_decay_launches": (ctypes.c_longlong, []),
+    "temp_gru_chain_offset_supported": (_I, [_I, _I]),
+    "temp_gru_chain_offset_layout": (_I, [_I]),
+    "temp_gru_chain_pack_multi_layout": (_I, [_I, _I, _I, ctypes.POINTER(c_vp), ctypes.POINTER(c_vp), c_vp]),
+    "temp_gru_chain_fwd_offset": (_I, [ctypes.POINTER(TempGruChain), ctypes.POINTER(TempChainDecay), ctypes.POINTER(TempChainOffset), c_vp, c_vp, c_vp, c_vp]),
+    "temp_gru_chain_bwd_offset": (_I, [ctypes.POINTER(TempGruChain), ctypes.POINTER(TempChainDecay), ctypes.POINTER(TempChainOffset), c_vp, _I,
+                                       ctypes.POINTER(c_vp), c_vp, c_vp, c_vp, c_vp, c_vp, c_vp]),
+    "temp_gru_chain_offset_launches": (ctypes.c_longlong, []),
     "temp_gru_grads_g4_keys": (_I, [_I, c_vp, _I, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, ctypes.c_size_t, c_vp]),
     "temp_gru_grads_g4_workspace": (ctypes.c_size_t, [_I, c_vp, _I]),
     "temp_gru_grads_g4": (_I, [_I, c_vp, _I, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, ctypes.c_size_t, c_vp]),

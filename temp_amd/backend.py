@@ -394,14 +394,18 @@ class HipBackend:
         out.chain_pack_layout = layout                   # (TempGruChain.pack_layout: the kernels follow the pack, not the options)
         return out
 
-    def gru_chain_pack_multi(self, w_hhs):
-        """gru_chain_pack of several GRUs' W_hh (same width) in ONE launch -> list of packed tensors (views of one buffer)."""
+    def gru_chain_pack_multi(self, w_hhs, layout=None):
+        """gru_chain_pack of several GRUs' W_hh (same width) in ONE launch -> list of packed tensors (views of one buffer).
+        layout: None = what the options select, or the _lib.CHAIN_PACK_* layout to write (temp_gru_chain_pack_multi_layout)."""
         w_hhs = [_f32(w, "w_hh") for w in w_hhs]
         d = w_hhs[0].shape[1]
         n = self.lib.temp_gru_chain_pack_floats(d)
         buf = torch.empty(len(w_hhs), n, dtype=torch.float32, device=w_hhs[0].device)
         src = (ctypes.c_void_p * len(w_hhs))(*[w.data_ptr() for w in w_hhs])
         dst = (ctypes.c_void_p * len(w_hhs))(*[buf[i].data_ptr() for i in range(len(w_hhs))])
+        if layout is not None:
+            _lib.check(self.lib.temp_gru_chain_pack_multi_layout(int(layout), len(w_hhs), d, src, dst, _stream()), "temp_gru_chain_pack_multi_layout")
+            return self._tagged([buf[i] for i in range(len(w_hhs))], int(layout))
         layout = self.lib.temp_gru_chain_pack_layout(d)
         _lib.check(self.lib.temp_gru_chain_pack_multi(len(w_hhs), d, src, dst, _stream()), "temp_gru_chain_pack_multi")
         return self._tagged([buf[i] for i in range(len(w_hhs))], layout)
@@ -457,12 +461,39 @@ class HipBackend:
         _lib.check(self.lib.temp_gru_chain_decay_reduce(ctypes.byref(c), _ptr(d_arg), _ptr(out), _ptr(ws), nb, _stream()), "temp_gru_chain_decay_reduce")
         return out
 
-    def gru_chain_fwd(self, tabs, gi, lam, variant, packs, b_hhs, h_out, saved_all, gi_index=None, decay=None):
+    # State offset (include/temp_amd.h: TempChainOffset): `offset` = (table float32 [T, d], index int32 [N_total], -1 = none); the
+    # states handed out and carried on are GRU(...) + table[index].  The packs must be in gru_chain_offset_layout(d)
+    # (gru_chain_pack_multi(layout=...)); the backward also takes `d_state` float32 [N_total, d] for the gradient reaching every state.
+    def gru_chain_offset_supported(self, d, variant):
+        return bool(self.lib.temp_gru_chain_offset_supported(int(d), int(variant)))
+
+    def gru_chain_offset_layout(self, d):
+        return int(self.lib.temp_gru_chain_offset_layout(int(d)))
+
+    def gru_chain_offset_launches(self):
+        return int(self.lib.temp_gru_chain_offset_launches())
+
+    @staticmethod
+    def _chain_offset(offset, n_total, d):
+        table, index = _f32(offset[0], "offset table"), _i32(offset[1], "offset index")
+        assert table.dim() == 2 and table.shape[1] == d and index.numel() == n_total
+        co = _lib.TempChainOffset()
+        co.table, co.index, co.n_rows = table.data_ptr(), index.data_ptr(), table.shape[0]
+        return co, (table, index)
+
+    def gru_chain_fwd(self, tabs, gi, lam, variant, packs, b_hhs, h_out, saved_all, gi_index=None, decay=None, offset=None):
         d = saved_all.shape[2]
         c, keep = self._chain_desc(tabs, d, variant, lam, saved_all.shape[1] * d, packs, b_hhs)
         if gi_index is not None:
             assert gi_index.shape[0] == saved_all.shape[1]
             c.gi_index = _i32(gi_index, "gi_index").data_ptr()
+        if offset is not None:
+            co, keep_o = self._chain_offset(offset, saved_all.shape[1], d)
+            cd = self._chain_decay(decay, len(packs)) if decay is not None else None
+            rc = self.lib.temp_gru_chain_fwd_offset(ctypes.byref(c), ctypes.byref(cd) if cd is not None else None, ctypes.byref(co), _ptr(_f32(gi, "gi")),
+                                                    _ptr(h_out), _ptr(saved_all), _stream())
+            _lib.check(rc, "temp_gru_chain_fwd_offset")
+            return
         if decay is not None:
             cd = self._chain_decay(decay, len(packs))
             rc = self.lib.temp_gru_chain_fwd_decay(ctypes.byref(c), ctypes.byref(cd), _ptr(_f32(gi, "gi")), _ptr(h_out), _ptr(saved_all), _stream())
@@ -506,11 +537,24 @@ class HipBackend:
         rc = self.lib.temp_gru_chain_fwd_x(ctypes.byref(c), _ptr(x), _ptr(_i32(x_index, "x_index")), barr, _ptr(h_out), _ptr(saved_all), _stream())
         _lib.check(rc, "temp_gru_chain_fwd_x")
 
-    def gru_chain_bwd(self, tabs, saved_all, ups, lam, variant, packs, b_hhs, dgi, dgh, decay=None, d_arg=None):
+    def _chain_bwd_offset(self, c, ups, arr, saved_all, packs, dgi, dgh, g4, decay, d_arg, offset, d_state):
+        d = saved_all.shape[2]
+        co, keep_o = self._chain_offset(offset, saved_all.shape[1], d)
+        cd = self._chain_decay(decay, len(packs)) if decay is not None else None
+        if d_state is not None:
+            assert d_state.dtype == torch.float32 and d_state.is_contiguous() and d_state.shape == saved_all.shape[1:]
+        rc = self.lib.temp_gru_chain_bwd_offset(ctypes.byref(c), ctypes.byref(cd) if cd is not None else None, ctypes.byref(co), _ptr(saved_all), len(ups), arr,
+                                                _ptr(dgi), _ptr(dgh), _ptr(g4), _ptr(_f32(d_arg, "d_arg")) if d_arg is not None else None, _ptr(d_state),
+                                                _stream())
+        _lib.check(rc, "temp_gru_chain_bwd_offset")
+
+    def gru_chain_bwd(self, tabs, saved_all, ups, lam, variant, packs, b_hhs, dgi, dgh, decay=None, d_arg=None, offset=None, d_state=None):
         d = saved_all.shape[2]
         c, keep = self._chain_desc(tabs, d, variant, lam, saved_all.shape[1] * d, packs, b_hhs)
         ups = [_f32(u, "upstream") if u is not None else None for u in ups]      # (None: that block of rows has no upstream gradient)
         arr = (ctypes.c_void_p * max(len(ups), 1))(*[u.data_ptr() if u is not None else None for u in ups])
+        if offset is not None:
+            return self._chain_bwd_offset(c, ups, arr, saved_all, packs, dgi, dgh, None, decay, d_arg, offset, d_state)
         if decay is not None:
             cd = self._chain_decay(decay, len(packs))
             rc = self.lib.temp_gru_chain_bwd_decay(ctypes.byref(c), ctypes.byref(cd), _ptr(saved_all), len(ups), arr, _ptr(dgi), _ptr(dgh), None, None, None,
@@ -524,7 +568,7 @@ class HipBackend:
         """True when the chain backward of this width hands out the row / column keys of g4 (f16 two-way split selected)."""
         return bool(self.lib.temp_gru_chain_keys_supported(int(d)))
 
-    def gru_chain_bwd_g4(self, tabs, saved_all, ups, lam, variant, packs, b_hhs, g4, keys=None, decay=None, d_arg=None):
+    def gru_chain_bwd_g4(self, tabs, saved_all, ups, lam, variant, packs, b_hhs, g4, keys=None, decay=None, d_arg=None, offset=None, d_state=None):
         """The chain backward with the gate gradients written once: g4 [N, 4d] = [dr | dz | dn_i | dn_h] (include/temp_amd.h:
         temp_gru_chain_bwd_g4; nn.GRU gate layout).  keys = (row_keys int32 [N], col_keys int32 [n_rnn + n_panels, 4d]; rows 0 .. n_rnn - 1 are the result): also the
         magnitude keys the consumers of g4 split it with (temp_gru_chain_bwd_g4_keys)."""
@@ -536,6 +580,9 @@ class HipBackend:
             row_keys, col_keys = keys
             assert row_keys.dtype == torch.int32 and col_keys.dtype == torch.int32 and col_keys.is_contiguous()
             assert row_keys.numel() == saved_all.shape[1] and col_keys.numel() == (len(packs) + tabs["n_panels"]) * 4 * d
+        if offset is not None:
+            assert keys is None, "an offset chain hands out no keys (its states are not bounded by the f16 split's constant scale)"
+            return self._chain_bwd_offset(c, ups, arr, saved_all, packs, None, None, g4, decay, d_arg, offset, d_state)
         if decay is not None:
             cd = self._chain_decay(decay, len(packs))
             rk, ck = (_ptr(keys[0]), _ptr(keys[1])) if keys is not None else (None, None)

@@ -14,7 +14,7 @@ from . import snapshot as S
 from .birrgcn import BiGRRGCNLayer, BiRRGCN
 from .dynamic_rgcn import DynamicRGCN, WindowBatch
 from .gru_cell import GRUCell
-from .gru_chain import GruInstance, GruProgram, gru_chain, chain_kernels_usable
+from .gru_chain import GruInstance, GruProgram, gru_chain, chain_kernels_usable, offset_tables
 from .rrgcn import run_rnn
 from .window import ChainPlan, Step, window_times
 
@@ -109,8 +109,10 @@ class BiDynamicRGCN(DynamicRGCN):
             else:
                 wb.last_x = TF.gather_rows(y2, wb.chain_rows, wb.chain_inv, relu_table=fold)      # GRU input rows in chain order
             got = dict(zip(want, gru_chain(wb.last_x, prog, [l2.forward_rnn, l2.backward_rnn], lam,
-                                           isinstance(l2.forward_rnn, GRUCell), want=want, x_keys=x_keys, decay=dec)))
+                                           isinstance(l2.forward_rnn, GRUCell), want=want, x_keys=x_keys, decay=dec, offset=self._chain_offset(wb))))
             out = got[wb.out_inst[0]] + got[wb.out_inst[1]]
+            if enc.use_time_embedding:                        # the centre step adds it ONCE to h_f + h_b (models/BiRRGCN.py:221-225)
+                out = out + TF.gather_rows(l2.time_embed, wb.target_time[0], wb.target_time[1])
             Hf, Hb = got.get(wb.hist_inst[0]), got.get(wb.hist_inst[1])
             return out, ((Hf, Hf), (Hb, Hb))
         y2 = l2.conv(wb.g_all, y1)                            # ReLU fused (models/BiRRGCN.py:202-203)
@@ -151,6 +153,13 @@ class BiDynamicRGCN(DynamicRGCN):
 
     def _chain_want(self, wb):
         return [i for i in (wb.out_inst[0], wb.out_inst[1], wb.hist_inst[0], wb.hist_inst[1]) if i >= 0]
+
+    def _chain_offset_index(self, wb):
+        """Program order [forward history | target | backward history | target]: the history rows of each direction add their own
+        position's row (forward_one_direction, models/BiRRGCN.py:236-239); the two centre cells add none -- their sum gets it once."""
+        plan_f, plan_b = wb.plan
+        none = np.full(wb.target.n_rows, -1, dtype=np.int64)
+        return np.concatenate([self._step_time_rows(st) for st in plan_f.steps] + [none] + [self._step_time_rows(st) for st in plan_b.steps] + [none])
 
     def _visit_rows_on_device(self):
         return not self._can_chain()              # the chain program gathers by its own row list (chain_rows, _build_program)
@@ -221,6 +230,8 @@ class BiDynamicRGCN(DynamicRGCN):
         _lib.pause_point()
         if wb.program is None:
             wb.target_b.tensors(dev)
+        elif self.ent_encoder.use_time_embedding:
+            wb.target_time = offset_tables(self._step_time_rows(wb.target), self.ent_encoder.layer_2.time_embed.shape[0], dev)
         if train:
             self._plan_loss(wb)
         return wb

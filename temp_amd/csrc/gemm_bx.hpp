@@ -362,9 +362,11 @@ static __global__ void __launch_bounds__(256) k_bx_pack_multi(BxPackJobs jobs) {
   bx_u32x4* d = jb.out + (size_t)st * 192 + lane;
   d[0] = H; d[64] = Mi; d[128] = L;
 }
-inline void bx_pack_jobs_add(BxPackJobs& jobs, const float* B, bx_u32x4* out, int K, int N, int ldb, int trans) {
+// n_slabs: slabs of 16 k to write when the reader walks more than ceil(K / 16) of them (the chain backward rounds its walk up to an
+// even count: the slabs past K must hold zeros, not whatever the buffer held)
+inline void bx_pack_jobs_add(BxPackJobs& jobs, const float* B, bx_u32x4* out, int K, int N, int ldb, int trans, int n_slabs = 0) {
   BxPackJob& j = jobs.j[jobs.count++];
-  j.B = B; j.out = out; j.K = K; j.N = N; j.n_tiles = ceil_div(N, 32); j.n_slabs = ceil_div(K, 16); j.ldb = ldb; j.trans = trans;
+  j.B = B; j.out = out; j.K = K; j.N = N; j.n_tiles = ceil_div(N, 32); j.n_slabs = n_slabs > 0 ? n_slabs : ceil_div(K, 16); j.ldb = ldb; j.trans = trans;
   j.unit0 = jobs.total_units;
   jobs.total_units += j.n_tiles * j.n_slabs;
 }

@@ -41,6 +41,10 @@ struct ChainArgs {
   size_t plane;
   ChainRnn rnn[TEMP_CHAIN_MAX_RNN];
   float* d_arg;                          // nullable (backward, learnable decay): [N_total] dL / d(w dt + b) of every row with a previous state
+  // State offset (TempChainOffset; --use-time-embedding): row rho leaves s = h + off_table[off_index[rho]] (an index outside
+  // [0, off_rows) = no offset).  All nullable; k_gru_chain_fwd / _bwd only (the f16 kernels split the state with a constant scale).
+  const float* off_table; const int32_t* off_index; int off_rows;
+  float* d_state;                        // nullable (backward): [N_total][d] the total gradient reaching every row's state
   long long* stamp;                      // development only (temp_set_debug_buffer): cycle stamps of the f16 kernels' DEV instantiations, else nullptr
 };
 struct ChainUps { const float* p[TEMP_CHAIN_MAX_UP]; };
@@ -69,7 +73,8 @@ inline size_t chain_lds_bwd(int D, int ms) { ChainGeom g = chain_geom(D); return
 // arg = w dt_rho + b, so dL/d arg_rho = -[arg_rho > 0] <d_hd . dec, h_pi> = -[arg_rho > 0] <d_prev_rho, h_pi>  (d_prev_rho is what the
 // matrix waves left in dpb; h_pi = (1 - z) n + z hd from the saved planes of pi -- both cells' output equation).  Every lane of the
 // wave hands in its partial dot product; the 64 partials are summed in a fixed order (a DPP butterfly inside each row of 16 lanes,
-// then the four rows), so the result is bit-repeatable.
+// then the four rows), so the result is bit-repeatable.  (With a state offset the decayed state is h_pi + offset_pi: k_gru_chain_bwd<OFS> adds
+// <d_prev_rho, offset_pi> to the lanes' partials.)
 __device__ __forceinline__ float chain_wave_sum(float v) {
   auto dpp = [](float x, auto ctrl) { return __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(x), decltype(ctrl)::value, 0xf, 0xf, true)); };
   v += dpp(v, std::integral_constant<int, 0xB1>());     // quad_perm [1, 0, 3, 2]
@@ -126,7 +131,9 @@ __global__ void __launch_bounds__(256) k_gru_chain_pack(int D, const float* __re
 // TPW = tiles per matrix wave (ceil(NT / 4)), MW = memory waves (4 or 8).
 // BX = 1: the products run on the bf16 matrix pipe as six products of the exact three-way operand split (gemm_bx.hpp): W_hh
 // arrives pre-split (k_bx_pack: three planes in fragment order), the state fragment is split by the matrix wave itself.
-template <int VARIANT, int TPW, int MW, int BX>
+// OFS = 1: the state offset of ChainArgs (off_table / off_index).  An instantiation of its own: held as a run-time branch, the
+// offset rows' registers cost the offset-free kernels 34 VGPRs and three of them their scratch-free allocation.
+template <int VARIANT, int TPW, int MW, int BX, int OFS = 0>
 __global__ void __launch_bounds__(256 + 64 * MW) k_gru_chain_fwd(ChainArgs a, const float* __restrict__ gi, float* __restrict__ H,
                                                                   float* __restrict__ saved) {
   extern __shared__ __attribute__((aligned(16))) float lds[];
@@ -321,6 +328,7 @@ __global__ void __launch_bounds__(256 + 64 * MW) k_gru_chain_fwd(ChainArgs a, co
       if (cact) { bhr = ld4(R.b_hh + col); bhz = ld4(R.b_hh + D + col); bhn = ld4(R.b_hh + 2 * D + col); }
       int erow[PASSES];
       float4 g0[PASSES], g1[PASSES], g2[PASSES];
+      float4 ofs[OFS ? PASSES : 1];            // OFS: the rows' state offsets
       auto prefetch = [&](int s) {
 #pragma unroll
         for (int ps = 0; ps < PASSES; ++ps) {
@@ -331,6 +339,10 @@ __global__ void __launch_bounds__(256 + 64 * MW) k_gru_chain_fwd(ChainArgs a, co
           const float* src = gi + (ok ? (size_t)(a.gi_index ? a.gi_index[er] : er) * G + col : 0);
           if (VARIANT == TEMP_GRU_TORCH) { g0[ps] = ld4(src); g1[ps] = ld4(src + (ok ? D : 0)); g2[ps] = ld4(src + (ok ? 2 * D : 0)); }
           else { g0[ps] = zero4(); g1[ps] = zero4(); g2[ps] = ld4(src); }
+          if constexpr (OFS) {                 // travels with the position's input gates: off the per-position critical path
+            const int k = ok ? a.off_index[er] : -1;
+            ofs[ps] = (k >= 0 && k < a.off_rows) ? ld4(a.off_table + (size_t)k * D + col) : zero4();
+          }
         }
       };
       prefetch(0);
@@ -370,7 +382,8 @@ __global__ void __launch_bounds__(256 + 64 * MW) k_gru_chain_fwd(ChainArgs a, co
             o_h[k] = (VARIANT == TEMP_GRU_TORCH) ? ((1.f - zg) * ng + zg * hdv[k]) : (ng + zg * (hdv[k] - ng));
             o_r[k] = rg; o_z[k] = zg; o_n[k] = ng; o_hn[k] = hn;
           }
-          const float4 h4 = make_float4(o_h[0], o_h[1], o_h[2], o_h[3]);
+          float4 h4 = make_float4(o_h[0], o_h[1], o_h[2], o_h[3]);
+          if constexpr (OFS) h4 = add4(h4, ofs[ps]);    // the sum is the state: h_out and what the next position decays
           st4(hnext + (size_t)slot * ldh + col, h4);
           const size_t o = row * D + col;
           if (flags & 2) st4(H + o, h4);
@@ -393,7 +406,8 @@ __global__ void __launch_bounds__(256 + 64 * MW) k_gru_chain_fwd(ChainArgs a, co
 // ---- backward -------------------------------------------------------------------------------------------------------
 // G4 = 1 (nn.GRU gate layout): the gate gradients are written ONCE, as dgi = [n][4d] = [dr | dz | dn_i | dn_h] (dgh unused) -- two
 // thirds of dgh repeat dgi; the weight-gradient and d_x kernels address their columns of the one matrix (gru_wgrad.hpp).
-template <int VARIANT, int TPWB, int MW, int BX, int G4 = 0>
+// OFS = 1: the state offset (d_state out; the offset rows in the learnable decay's d_arg), an instantiation of its own as in the forward.
+template <int VARIANT, int TPWB, int MW, int BX, int G4 = 0, int OFS = 0>
 __global__ void __launch_bounds__(256 + 64 * MW) k_gru_chain_bwd(ChainArgs a, ChainUps ups, const float* __restrict__ saved,
                                                                   float* __restrict__ dgi, float* __restrict__ dgh) {
   extern __shared__ __attribute__((aligned(16))) float lds[];
@@ -627,13 +641,25 @@ __global__ void __launch_bounds__(256 + 64 * MW) k_gru_chain_bwd(ChainArgs a, Ch
           const int e = erow[ps];
           if (e < 0) continue;                 // idle track: whatever its LDS rows hold only reaches its own, unread, d_prev row
           if (a.d_arg && enx[ps] >= 0) {       // (wave-uniform; lanes past the width take part in the sum with zeros)
-            const float part = cact ? chain_dot_prev(ld4(dpb + (size_t)slot * ldz + col), sz[ps], sn[ps], shd[ps]) : 0.f;
+            float part = 0.f;
+            if (cact) {
+              const float4 dp = ld4(dpb + (size_t)slot * ldz + col);
+              part = chain_dot_prev(dp, sz[ps], sn[ps], shd[ps]);
+              if constexpr (OFS) {             // the state the successor decayed is h + offset (loaded on demand: decay and offset together)
+                const int k = a.off_index[e & CH_ROW_MASK];
+                if (k >= 0 && k < a.off_rows) {
+                  const float4 o = ld4(a.off_table + (size_t)k * D + col);
+                  part += (dp.x * o.x + dp.y * o.y) + (dp.z * o.z + dp.w * o.w);
+                }
+              }
+            }
             chain_store_d_arg(a, R, enx[ps], part, lane);
           }
           if (!cact) continue;
           const size_t row = (size_t)(e & CH_ROW_MASK);
           float4 gd = upp ? ld4(upp + (row - (size_t)up_row0) * D + col) : zero4();
           if (enx[ps] >= 0) gd = add4(gd, ld4(dpb + (size_t)slot * ldz + col));
+          if constexpr (OFS) if (a.d_state) st4(a.d_state + row * D + col, gd);      // ds/dh = I: what reaches the state reaches its offset row (every row once)
           const float4 rg = sr[ps], zg = sz[ps], ng = sn[ps], hn = shn[ps], hd = shd[ps];
           float4 dr_pre, dz_pre, dn_pre, dhn, gz;
 #define TEMP_GATE(c)                                          \
@@ -748,9 +774,13 @@ static bool chain_layout_ok(int layout, int d) {
 static bool layout_hx(int layout) { return layout == TEMP_CHAIN_PACK_HX || layout == TEMP_CHAIN_PACK_HX_X; }
 
 // decay: nullable -- the learnable decay of every GRU of the chain (c->lambda is not read then); d_arg: nullable, backward only
-static ChainArgs chain_args(const TempGruChain* c, const TempChainDecay* decay = nullptr, float* d_arg = nullptr) {
+// offset: nullable -- the state offset of every row (TempChainOffset); d_state: nullable, backward only
+static ChainArgs chain_args(const TempGruChain* c, const TempChainDecay* decay = nullptr, float* d_arg = nullptr,
+                            const TempChainOffset* offset = nullptr, float* d_state = nullptr) {
   ChainArgs a = {};
   a.d_arg = d_arg;
+  if (offset) { a.off_table = offset->table; a.off_index = offset->index; a.off_rows = offset->n_rows; }
+  a.d_state = d_state;
   const ChainGeom g = chain_geom(c->d);
   a.D = c->d; a.n_panels = c->n_panels; a.max_steps = c->max_steps; a.panel = c->panel; a.rows = c->rows; a.sinfo = c->sinfo; a.dt = c->dt;
   a.layout = c->pack_layout;
@@ -819,6 +849,16 @@ static int launch_chain_fwd(const ChainArgs& a, const float* gi, float* h, float
     return launch_status();
   }
   const size_t lds = chain_lds_fwd(a.D, a.max_steps);
+  if (a.off_table) {                                            // state offset: the instantiations of their own (chain_offset_check: never an f16 layout)
+    static bool attr_o = false, attr_bx_o = false;
+    auto launch = [&](auto kernel, bool* granted) {
+      int rc = chain_lds_attr(kernel, lds, granted);
+      if (rc) return rc;
+      TEMP_LAUNCH(K_GRU_CHAIN_FWD, kernel, dim3(a.n_panels), dim3(512), lds, st, a, gi, h, saved);
+      return launch_status();
+    };
+    return a.layout == TEMP_CHAIN_PACK_BX ? launch(k_gru_chain_fwd<VARIANT, TPW, 4, 1, 1>, &attr_bx_o) : launch(k_gru_chain_fwd<VARIANT, TPW, 4, 0, 1>, &attr_o);
+  }
   if (a.layout == TEMP_CHAIN_PACK_BX) {
     auto kernel = k_gru_chain_fwd<VARIANT, TPW, 4, 1>;
     int rc = chain_lds_attr(kernel, lds, &attr_bx);
@@ -888,6 +928,16 @@ static int launch_chain_bwd(const ChainArgs& a, const ChainUps& ups, const float
   }
   if (row_keys || col_keys) return TEMP_E_UNSUPPORTED;          // (only the f16 kernels produce keys: ask temp_gru_chain_keys_supported first)
   const size_t lds = chain_lds_bwd(a.D, a.max_steps);
+  if (a.off_table) {
+    static bool attr_o = false, attr_bx_o = false;
+    auto launch = [&](auto kernel, bool* granted) {
+      int rc = chain_lds_attr(kernel, lds, granted);
+      if (rc) return rc;
+      TEMP_LAUNCH(K_GRU_CHAIN_BWD, kernel, dim3(a.n_panels), dim3(768), lds, st, a, ups, saved, dgi, dgh);
+      return launch_status();
+    };
+    return a.layout == TEMP_CHAIN_PACK_BX ? launch(k_gru_chain_bwd<VARIANT, TPWB, 8, 1, G4, 1>, &attr_bx_o) : launch(k_gru_chain_bwd<VARIANT, TPWB, 8, 0, G4, 1>, &attr_o);
+  }
   if (a.layout == TEMP_CHAIN_PACK_BX) {
     auto kernel = k_gru_chain_bwd<VARIANT, TPWB, 8, 1, G4>;
     int rc = chain_lds_attr(kernel, lds, &attr_bx);
@@ -924,12 +974,10 @@ size_t temp_gru_chain_pack_floats(int d) {
   return m > hx ? m : hx;                              // any arithmetic (TEMP_MFMA) fits the caller's buffer
 }
 
-int temp_gru_chain_pack(int d, const float* w_hh, float* packed, void* stream) {
-  if (d <= 0 || !w_hh || !packed) return TEMP_E_BADARG;
-  if (d % 4) return TEMP_E_UNSUPPORTED;
+// one W_hh in the F32 or BX layout
+static int chain_pack_one(int layout, int d, const float* w_hh, float* packed, void* stream) {
   const ChainGeom g = chain_geom(d);
-  if (chain_hx(d)) return temp_gru_chain_pack_multi(1, d, &w_hh, &packed, stream);
-  if (chain_bx(d)) {
+  if (layout == TEMP_CHAIN_PACK_BX) {
     // forward: gate column x k = W_hh as stored ([3d][d], k contiguous); backward: k = gate column, state column = W_hh as [K][N]
     const int nsf = g.NQ >> 1, nsb = g.NQb >> 1;
     bx_u32x4* pf = reinterpret_cast<bx_u32x4*>(packed);
@@ -947,11 +995,24 @@ int temp_gru_chain_pack(int d, const float* w_hh, float* packed, void* stream) {
   return launch_status();
 }
 
+int temp_gru_chain_pack(int d, const float* w_hh, float* packed, void* stream) {
+  if (d <= 0 || !w_hh || !packed) return TEMP_E_BADARG;
+  if (d % 4) return TEMP_E_UNSUPPORTED;
+  if (chain_hx(d)) return temp_gru_chain_pack_multi(1, d, &w_hh, &packed, stream);
+  return chain_pack_one(chain_pack_layout(d), d, w_hh, packed, stream);
+}
+
 int temp_gru_chain_pack_multi(int count, int d, const float* const* w_hh, float* const* packed, void* stream) {
+  return temp_gru_chain_pack_multi_layout(d > 0 ? chain_pack_layout(d) : 0, count, d, w_hh, packed, stream);
+}
+
+int temp_gru_chain_pack_multi_layout(int layout, int count, int d, const float* const* w_hh, float* const* packed, void* stream) {
   if (count <= 0 || count > TEMP_CHAIN_MAX_RNN || d <= 0 || !w_hh || !packed) return TEMP_E_BADARG;
   for (int i = 0; i < count; ++i) if (!w_hh[i] || !packed[i]) return TEMP_E_BADARG;
   if (d % 4) return TEMP_E_UNSUPPORTED;
-  if (chain_hx(d)) {
+  if (layout != TEMP_CHAIN_PACK_F32 && layout != TEMP_CHAIN_PACK_BX && layout != TEMP_CHAIN_PACK_HX) return TEMP_E_BADARG;
+  if (!chain_layout_ok(layout, d)) return TEMP_E_UNSUPPORTED;
+  if (layout == TEMP_CHAIN_PACK_HX) {
     // two f16 planes with per-column scales: forward (gate column x k: W_hh as stored), backward (k = gate column, state column:
     // W_hh as [K][N], its slab count rounded up to the kernel's multiple of four), then the keys of both
     const ChainGeomHx gx = chain_geom_hx(d);
@@ -967,8 +1028,8 @@ int temp_gru_chain_pack_multi(int count, int d, const float* const* w_hh, float*
     hx_pack_launch(jobs, K_GRU_CHAIN_PACK, (hipStream_t)stream);
     return launch_status();
   }
-  if (!chain_bx(d) || 2 * count > BX_PACK_JOBS) {
-    for (int i = 0; i < count; ++i) { const int rc = temp_gru_chain_pack(d, w_hh[i], packed[i], stream); if (rc) return rc; }
+  if (layout != TEMP_CHAIN_PACK_BX || 2 * count > BX_PACK_JOBS) {
+    for (int i = 0; i < count; ++i) { const int rc = chain_pack_one(layout, d, w_hh[i], packed[i], stream); if (rc) return rc; }
     return TEMP_OK;
   }
   const ChainGeom g = chain_geom(d);
@@ -976,7 +1037,7 @@ int temp_gru_chain_pack_multi(int count, int d, const float* const* w_hh, float*
   for (int i = 0; i < count; ++i) {                           // forward planes (W_hh as stored: [3d][d], k contiguous), then backward planes (W_hh as [K][N])
     bx_u32x4* pf = reinterpret_cast<bx_u32x4*>(packed[i]);
     bx_pack_jobs_add(jobs, w_hh[i], pf, d, 3 * d, d, 1);
-    bx_pack_jobs_add(jobs, w_hh[i], pf + (size_t)(g.NQ >> 1) * g.NT * 192, 3 * d, d, d, 0);
+    bx_pack_jobs_add(jobs, w_hh[i], pf + (size_t)(g.NQ >> 1) * g.NT * 192, 3 * d, d, d, 0, g.NQb >> 1);      // (the backward kernel's slab count, as chain_pack_one)
   }
   TEMP_LAUNCH(K_GRU_CHAIN_PACK, k_bx_pack_multi, dim3(ceil_div(jobs.total_units, 4)), dim3(256), 0, (hipStream_t)stream, jobs);
   return launch_status();
@@ -992,14 +1053,26 @@ static int chain_decay_check(const TempGruChain* c, const TempChainDecay* decay)
   return temp_gru_chain_decay_supported(c->d, c->variant) ? TEMP_OK : TEMP_E_UNSUPPORTED;
 }
 
-static int chain_fwd(const TempGruChain* c, const TempChainDecay* decay, const float* gi, float* h_out, float* saved, void* stream) {
+// launches of a chain forward / backward kernel with a state offset since the library was loaded (diagnostic)
+static std::atomic<long long> g_offset_launches{0};
+static int chain_offset_check(const TempGruChain* c, const TempChainOffset* offset) {
+  if (!offset) return TEMP_OK;
+  if (!offset->table || !offset->index || offset->n_rows <= 0) return TEMP_E_BADARG;
+  if (!temp_gru_chain_offset_supported(c->d, c->variant)) return TEMP_E_UNSUPPORTED;
+  return layout_hx(c->pack_layout) ? TEMP_E_UNSUPPORTED : TEMP_OK;      // (the f16 kernels split the state with the constant scale 2^14: |state| < 4)
+}
+
+static int chain_fwd(const TempGruChain* c, const TempChainDecay* decay, const TempChainOffset* offset, const float* gi, float* h_out, float* saved,
+                     void* stream) {
   int rc = chain_check(c);
   if (rc) return rc;
   if ((rc = chain_decay_check(c, decay))) return rc;
+  if ((rc = chain_offset_check(c, offset))) return rc;
   if (c->n_panels == 0) return TEMP_OK;
   if (!gi || !h_out || !saved) return TEMP_E_BADARG;
-  const ChainArgs a = chain_args(c, decay);
+  const ChainArgs a = chain_args(c, decay, nullptr, offset);
   if (decay) g_decay_launches.fetch_add(1, std::memory_order_relaxed);
+  if (offset) g_offset_launches.fetch_add(1, std::memory_order_relaxed);
   hipStream_t st = (hipStream_t)stream;
   const int tpw = ceil_div(chain_geom(c->d).NT, 4);
 #define TEMP_CHAIN_FWD(V)                                                            \
@@ -1020,12 +1093,22 @@ static int chain_fwd(const TempGruChain* c, const TempChainDecay* decay, const f
 extern "C" {
 
 int temp_gru_chain_fwd(const TempGruChain* c, const float* gi, float* h_out, float* saved, void* stream) {
-  return chain_fwd(c, nullptr, gi, h_out, saved, stream);
+  return chain_fwd(c, nullptr, nullptr, gi, h_out, saved, stream);
 }
 int temp_gru_chain_fwd_decay(const TempGruChain* c, const TempChainDecay* decay, const float* gi, float* h_out, float* saved, void* stream) {
   if (!decay) return TEMP_E_BADARG;
-  return chain_fwd(c, decay, gi, h_out, saved, stream);
+  return chain_fwd(c, decay, nullptr, gi, h_out, saved, stream);
 }
+int temp_gru_chain_fwd_offset(const TempGruChain* c, const TempChainDecay* decay, const TempChainOffset* offset, const float* gi, float* h_out,
+                              float* saved, void* stream) {
+  if (!offset) return TEMP_E_BADARG;
+  return chain_fwd(c, decay, offset, gi, h_out, saved, stream);
+}
+int temp_gru_chain_offset_supported(int d, int variant) {
+  return (variant == TEMP_GRU_TORCH || variant == TEMP_GRU_TYPE1) && temp_gru_chain_supported(d) ? 1 : 0;
+}
+int temp_gru_chain_offset_layout(int d) { return d > 0 ? (chain_bx(d) ? TEMP_CHAIN_PACK_BX : TEMP_CHAIN_PACK_F32) : 0; }
+long long temp_gru_chain_offset_launches(void) { return g_offset_launches.load(std::memory_order_relaxed); }
 int temp_gru_chain_decay_supported(int d, int variant) {
   return (variant == TEMP_GRU_TORCH || variant == TEMP_GRU_TYPE1) && temp_gru_chain_supported(d) ? 1 : 0;
 }
@@ -1124,18 +1207,22 @@ long long temp_gru_chain_fwd_x_launches(void) { return g_fwd_x_launches.load(std
 // learnable decay and its per-row gradient (both or neither).
 enum { CH_BWD_GATES, CH_BWD_G4, CH_BWD_G4_KEYS };
 static int chain_bwd(int route, const TempGruChain* c, const TempChainDecay* decay, const float* saved, int n_up, const float* const* up, float* dgi,
-                     float* dgh, float* g4, uint32_t* row_keys, uint32_t* col_keys, float* d_arg, void* stream) {
+                     float* dgh, float* g4, uint32_t* row_keys, uint32_t* col_keys, float* d_arg, void* stream,
+                     const TempChainOffset* offset = nullptr, float* d_state = nullptr) {
   int rc = chain_check(c);
   if (rc) return rc;
   if ((rc = chain_decay_check(c, decay))) return rc;
+  if ((rc = chain_offset_check(c, offset))) return rc;
+  if (d_state && !offset) return TEMP_E_BADARG;
   if (n_up < 0 || n_up > TEMP_CHAIN_MAX_UP || (n_up > 0 && !up)) return TEMP_E_BADARG;
   if ((decay != nullptr) != (d_arg != nullptr)) return TEMP_E_BADARG;
   if (route != CH_BWD_GATES && c->variant != TEMP_GRU_TORCH) return TEMP_E_UNSUPPORTED;    // (the type-1 cell's dgi is [n, d])
   if (route == CH_BWD_G4_KEYS && !layout_hx(c->pack_layout)) return TEMP_E_UNSUPPORTED;
   if (c->n_panels == 0) return TEMP_OK;
   if (!saved || (route == CH_BWD_GATES ? (!dgi || !dgh) : !g4)) return TEMP_E_BADARG;
-  const ChainArgs a = chain_args(c, decay, d_arg);
+  const ChainArgs a = chain_args(c, decay, d_arg, offset, d_state);
   if (decay) g_decay_launches.fetch_add(1, std::memory_order_relaxed);
+  if (offset) g_offset_launches.fetch_add(1, std::memory_order_relaxed);
   ChainUps ups = {};
   for (int i = 0; i < n_up; ++i) ups.p[i] = up[i];
   hipStream_t st = (hipStream_t)stream;
@@ -1179,6 +1266,12 @@ int temp_gru_chain_bwd_decay(const TempGruChain* c, const TempChainDecay* decay,
   if (!decay || !d_arg || (g4 && (dgi || dgh))) return TEMP_E_BADARG;
   const int route = !g4 ? CH_BWD_GATES : (row_keys || col_keys) ? CH_BWD_G4_KEYS : CH_BWD_G4;
   return chain_bwd(route, c, decay, saved, n_up, up, dgi, dgh, g4, row_keys, col_keys, d_arg, stream);
+}
+
+int temp_gru_chain_bwd_offset(const TempGruChain* c, const TempChainDecay* decay, const TempChainOffset* offset, const float* saved, int n_up,
+                              const float* const* up, float* dgi, float* dgh, float* g4, float* d_arg, float* d_state, void* stream) {
+  if (!offset || (g4 && (dgi || dgh))) return TEMP_E_BADARG;
+  return chain_bwd(g4 ? CH_BWD_G4 : CH_BWD_GATES, c, decay, saved, n_up, up, dgi, dgh, g4, nullptr, nullptr, d_arg, stream, offset, d_state);
 }
 
 size_t temp_gru_chain_decay_reduce_workspace(const TempGruChain* c) {

@@ -249,6 +249,8 @@ class SnapshotShardedEncoder:
         assert model._can_batch() and model._can_chain(), "snapshot sharding needs the batched GRU + rec-only-last-layer path"
         assert model.ent_encoder.layer_2.decay_spec() is None, \
             "snapshot sharding runs the fixed decay only: --learnable-lambda (a learnable decay) is not sharded"
+        assert not model.ent_encoder.use_time_embedding, \
+            "snapshot sharding adds no per-position time embedding: --use-time-embedding is not sharded"
 
     # ---------------------------------------------------------------------------------------------
     def prepare(self, t_list, seq_len, train=True, target_edge_ids=None):

@@ -21,7 +21,8 @@ from . import _hostlib
 from . import snapshot as S
 from .rrgcn import RRGCN, GRRGCNLayer, run_rnn
 from .tkg_module import TKG_Module
-from .gru_chain import GruInstance, GruProgram, chain_decay_usable, gru_chain, prepare_program, program_on_chain_kernels, zero_state_program
+from .gru_chain import (GruInstance, GruProgram, chain_decay_usable, chain_offset_usable, gru_chain, offset_tables, prepare_program,
+                        program_on_chain_kernels, zero_state_program)
 from .gru_cell import GRUCell
 from .window import ChainPlan, Step, concat_steps, concat_steps_dedup, window_times
 
@@ -177,13 +178,19 @@ class DynamicRGCN(TKG_Module):
     # ---------------------------------------------------------------------------------------------
     # batched path
     # ---------------------------------------------------------------------------------------------
+    # --use-time-embedding on the chain kernels and in the batched all-entity pass: DynamicRGCN / BiDynamicRGCN proper.  The
+    # Impute* / Post* classes (a local stream beside the temporal one) and SelfAttentionRGCN switch it off and keep their paths.
+    _chain_time_embedding = True
+
     def _can_chain(self):
-        """The whole recurrence as one autograd node (gru_chain): single GRU layer, no per-position time embedding; a
-        learnable decay (--learnable-lambda) only where the backend's chain kernels take one (a backend without
-        gru_chain_decay_supported keeps the per-position loop for it)."""
+        """The whole recurrence as one autograd node (gru_chain): single GRU layer; a learnable decay (--learnable-lambda) or
+        the per-position time embedding (--use-time-embedding: a state offset of the chain) only where the backend's chain
+        kernels take one (a backend without gru_chain_decay_supported / gru_chain_offset_supported keeps the per-position loop)."""
         enc = self.ent_encoder
         l2 = enc.layer_2
-        if not (self.use_gru_chain and not enc.use_time_embedding and getattr(l2, "num_layers", 1) == 1):
+        if not (self.use_gru_chain and getattr(l2, "num_layers", 1) == 1):
+            return False
+        if enc.use_time_embedding and not self._chain_takes_offset():
             return False
         return l2.decay_spec() is None or self._chain_takes_decay()
 
@@ -193,6 +200,29 @@ class DynamicRGCN(TKG_Module):
     def _chain_takes_decay(self):
         rnns = self._chain_rnns()
         return chain_decay_usable(self.embed_size, _lib.GRU_TYPE1 if isinstance(rnns[0], GRUCell) else _lib.GRU_TORCH, len(rnns))
+
+    def _chain_takes_offset(self):
+        """s_p = GRU(x_p, dec . s_{p-1}) + time_embed_2[t_p] (models/RRGCN.py:192-204) as the chain's state offset: this class
+        (see _chain_time_embedding), only the last layer recurrent, a GRU cell, and chain kernels that take an offset."""
+        if not (self._chain_time_embedding and self._can_batch()):
+            return False
+        rnns = self._chain_rnns()
+        return chain_offset_usable(self.embed_size, _lib.GRU_TYPE1 if isinstance(rnns[0], GRUCell) else _lib.GRU_TORCH, len(rnns))
+
+    @staticmethod
+    def _step_time_rows(st):
+        """The time-embedding row of every row of a step (RGCNLayer.get_time_embedding: the step's graphs in order)."""
+        return np.repeat(np.array([int(t) for t in st.times], dtype=np.int64), [int(n) for n in st.sizes])
+
+    def _chain_offset_index(self, wb):
+        """Time-embedding row of every chain row, in program order: every position adds its own, the target included."""
+        return np.concatenate([self._step_time_rows(st) for st in wb.steps]) if wb.steps else np.zeros(0, np.int64)
+
+    def _chain_offset(self, wb):
+        """gru_chain's `offset` under --use-time-embedding (the tables are built in `prepare`), else None."""
+        if not self.ent_encoder.use_time_embedding:
+            return None
+        return (self.ent_encoder.layer_2.time_embed,) + wb.chain_offset
 
     def _visit_rows_on_device(self):
         return True
@@ -220,7 +250,8 @@ class DynamicRGCN(TKG_Module):
         wb.last_x = y2                                # GRU input rows of the step (= the "local" states of the post models)
         if wb.program is not None:
             want = self._chain_want(wb)
-            got = gru_chain(y2, wb.program, [l2.rnn], l2.inv_temperature, isinstance(l2.rnn, GRUCell), want=want, decay=l2.decay_spec())
+            got = gru_chain(y2, wb.program, [l2.rnn], l2.inv_temperature, isinstance(l2.rnn, GRUCell), want=want, decay=l2.decay_spec(),
+                            offset=self._chain_offset(wb))
             hist = got[1] if wb.hist_inst >= 0 else None
             return got[0], (hist, hist)
         H, hist = None, None
@@ -293,13 +324,17 @@ class DynamicRGCN(TKG_Module):
                 self._build_program(wb)
                 _lib.pause_point()
                 prepare_program(wb.program, dev, self.embed_size, len(wb.out_inst), self._chain_want(wb))
-                # a learnable decay runs on the chain kernels only: a program they refuse (no chain tables, a panel longer than
-                # their step limit) stays on the per-position loop -- decided here, not in `run`
-                if self.ent_encoder.layer_2.decay_spec() is not None and not program_on_chain_kernels(wb.program, dev, self._chain_want(wb)):
+                # a learnable decay and the time embedding run on the chain kernels only: a program they refuse (no chain tables, a
+                # panel longer than their step limit) stays on the per-position loop -- decided here, not in `run`
+                enc = self.ent_encoder
+                if ((enc.layer_2.decay_spec() is not None or enc.use_time_embedding)
+                        and not program_on_chain_kernels(wb.program, dev, self._chain_want(wb))):
                     wb.program = None
                     if wb.visit_rows_host is not None and wb.visit_rows is None:      # (the loop gathers by the visit rows on the device)
                         wb.visit_rows = _lib.to_device(wb.visit_rows_host, dev)
                         wb.visit_inv = TF.gather_inverse(wb.visit_rows_host, int(wb.g_all.n), dev)
+                elif enc.use_time_embedding:
+                    wb.chain_offset = offset_tables(self._chain_offset_index(wb), enc.layer_2.time_embed.shape[0], dev)
         else:
             for st in wb.steps:
                 st.batched().device_graph(dev, 2 * self.num_rels)
@@ -467,6 +502,12 @@ class DynamicRGCN(TKG_Module):
             for b, g in enumerate(wb.graphs):
                 act[b, g.gids] = True
             wb.n_inactive = int(B * N - act.sum())
+            wb.all_time = None
+            if self.ent_encoder.use_time_embedding and self._chain_time_embedding and wb.n_inactive:
+                # forward_isolated adds time_embed_2[t_b] to all rows of window b, then the active rows are overwritten with the
+                # encoder's (models/RRGCN.py:214-216, models/DynamicRGCN.py:60-63): the inactive rows' table row, -1 on the active ones
+                rows_t = np.where(act, -1, np.array([int(r[-1]) for r in wb.rows], dtype=np.int64)[:, None]).reshape(-1)
+                wb.all_time = offset_tables(rows_t, self.ent_encoder.layer_2.time_embed.shape[0], dev)
             host, meta = {}, []
             for d, plan in enumerate(plans):
                 _lib.pause_point()
@@ -529,8 +570,9 @@ class DynamicRGCN(TKG_Module):
         enc = self.ent_encoder
         # (while the self-loop dropout draws the isolated pass runs over (window, entity) rows, every window with its own mask:
         #  _all_rep / _all_maps -- the reference's default is dropout 0.1, utils/args.py:17)
-        plain = (not enc.use_time_embedding and not getattr(self.args, "use_embed_for_non_active", False)
-                 and getattr(enc.layer_2, "num_layers", 1) == 1)
+        # (--use-time-embedding: on the batched path of the classes whose all_embeds_batched adds it, see _chain_time_embedding)
+        temb = not enc.use_time_embedding or (wb.batched and self._chain_time_embedding)
+        plain = temb and not getattr(self.args, "use_embed_for_non_active", False) and getattr(enc.layer_2, "num_layers", 1) == 1
         if wb.batched:
             return plain
         return (plain and self.use_batched_path and not isinstance(wb.plan, tuple) and isinstance(enc.layer_1, GRRGCNLayer)
@@ -587,6 +629,8 @@ class DynamicRGCN(TKG_Module):
             parts.append(self._zero_state_rows(rnn, x, l2))                      # GRU(x_e, 0): one row per entity, every window
             g = TF.gather_rows(torch.cat(parts, dim=0), m["asm"], m["asm_inv"])
             big = g if big is None else big + g
+        if enc.use_time_embedding:                   # once per window, after the directions are summed; the active rows carry it from `out`
+            big = big + TF.gather_rows(l2.time_embed, wb.all_time[0], wb.all_time[1])
         return big.view(B, N, big.shape[1])
 
     def run_loss(self, wb, samples=None):

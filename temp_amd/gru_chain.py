@@ -299,7 +299,7 @@ class GruProgram:
 
 class _GruChainFn(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, x_all, prog, lam, variant, n_rnn, want, x_keys, dec_w, dec_b, *weights):
+    def forward(ctx, x_all, prog, lam, variant, n_rnn, want, x_keys, dec_w, dec_b, off_table, off_index, off_inverse, *weights):
         be = get_backend()
         dev = x_all.device
         d = x_all.shape[1]
@@ -321,9 +321,22 @@ class _GruChainFn(torch.autograd.Function):
                     "instances): use the per-position loop (run_rnn with decay_spec())" % (_lib.CHAIN_MAX_STEPS, _lib.CHAIN_MAX_UP)))
             dk = dict(decay=torch.cat([dec_w.detach().reshape(1), dec_b.detach().reshape(1)]).to(torch.float32))
         ctx.decay = dk
+        # state offset (off_table [T, d], off_index int32 [n_total], -1 = none): row i leaves GRU(...) + off_table[off_index[i]], which
+        # is also what the next position decays -- inside the chain kernels (pointers only, no host read)
+        ofk = {}
+        if off_table is not None:
+            if tabs is None or not chain_offset_usable(d, variant, n_rnn):
+                raise _lib.TempAmdError("gru_chain: a state offset runs on the persistent chain kernels only, and %s" % (
+                    "this backend / width / cell has none that take it" if not chain_offset_usable(d, variant, n_rnn) else
+                    "they refuse this program (not a set of one-GRU chains, a panel longer than %d steps, or more than %d consumed "
+                    "instances): use the per-position loop" % (_lib.CHAIN_MAX_STEPS, _lib.CHAIN_MAX_UP)))
+            assert off_table.shape[1] == d and off_index.dtype == torch.int32 and off_index.numel() == N
+            ofk = dict(offset=(off_table.detach().contiguous(), off_index))
+        ctx.offset, ctx.off_inverse, ctx.off_rows = ofk, off_inverse, (off_table.shape[0] if off_table is not None else 0)
         # nn.GRU cells on the f16 route: the chain forward computes the input gates itself from the x rows (temp_gru_chain_fwd_x) --
         # no gi, no gate GEMM.  (Independent of x_src: a labelled and an unlabelled program take the same kernel.)
-        fused = bool(tabs is not None and FUSED_INPUT_GATES and variant == _lib.GRU_TORCH and hasattr(be, "gru_chain_fwd_x")
+        # (an offset chain's states leave the range of the f16 state split: it keeps the gi route and the bf16 / fp32 chain kernels)
+        fused = bool(tabs is not None and not ofk and FUSED_INPUT_GATES and variant == _lib.GRU_TORCH and hasattr(be, "gru_chain_fwd_x")
                      and be.gru_chain_fwd_x_supported(d, variant, tabs["max_steps"]))
         share = prog.gi_shared(dev) if (tabs is not None and not fused) else None        # gates once per distinct x row (chain kernels only)
         # x_keys = (row keys [x rows], column keys [d]) of x_all from its producer (functional.gather_rows(keys=True)): the input-gate
@@ -358,6 +371,9 @@ class _GruChainFn(torch.autograd.Function):
             packs = be.gru_chain_pack_x_multi([W[r][1] for r in range(n_rnn)], [W[r][0] for r in range(n_rnn)])
             be.gru_chain_fwd_x(tabs, x_all, prog.x_index(dev), lam, variant, packs, [W[r][3] for r in range(n_rnn)], [W[r][2] for r in range(n_rnn)],
                                H, saved, **dk)
+        elif ofk:                                      # packed for the kernels an offset chain runs on, whatever the options select
+            packs = be.gru_chain_pack_multi([W[r][1] for r in range(n_rnn)], layout=be.gru_chain_offset_layout(d))
+            be.gru_chain_fwd(tabs, gi, lam, variant, packs, [W[r][3] for r in range(n_rnn)], H, saved, gi_index=gi_index, **dk, **ofk)
         elif tabs is not None:
             packs = be.gru_chain_pack_multi([W[r][1] for r in range(n_rnn)]) if hasattr(be, "gru_chain_pack_multi") else \
                 [be.gru_chain_pack(W[r][1]) for r in range(n_rnn)]
@@ -413,6 +429,15 @@ class _GruChainFn(torch.autograd.Function):
                 return None, None
             d_wb = be.gru_chain_decay_reduce(ctx.tabs, d, variant, dk["d_arg"], ctx.n_rnn)        # [n_rnn, 2]: all GRUs share the one Linear
             return d_wb[:, 0].sum().reshape(1, 1), d_wb[:, 1].sum().reshape(1)
+        # state offset: the chain backward also writes the gradient reaching every row's state; the table's gradient is the adjoint
+        # of the row gather table[index] applied to it (a segment sum over the static inverse: no atomics)
+        ofk = dict(ctx.offset, d_state=torch.empty(N, d, dtype=torch.float32, device=dev)) if ctx.offset else {}
+
+        def offset_grads():
+            if not ofk:
+                return None, None, None
+            seg_ptr, order = ctx.off_inverse
+            return be.segment_sum_rows(ofk["d_state"], seg_ptr, order, ctx.off_rows), None, None
         zero_state = [all(it.prev < 0 for it in prog.inst if it.group == gi) for gi in range(len(groups))]    # hdec = 0 on every row
         # GRUs with disjoint x rows (the two directions of a bidirectional chain, or the one GRU of a uni-directional one): ONE
         # weight-gradient launch for all d_W_ih / d_W_hh products, ONE reduction and ONE d_x launch
@@ -427,9 +452,10 @@ class _GruChainFn(torch.autograd.Function):
             ups = [dH] if ctx.want is None else [given.get(i) for i in ctx.want]
             # (f16 arithmetic: the chain backward also hands out the magnitude keys of g4 -- per row, per GRU and column -- that the
             #  weight-gradient and d_x products split it with; integer maxima, so bit-repeatable)
-            keyed = bool(KEYED_GRADS and hasattr(be, "gru_chain_keys_supported") and be.gru_chain_keys_supported(d))
+            #  An offset chain hands out none: saved[4] = dec . s_prev is not bounded by the keyed products' constant state scale.
+            keyed = bool(KEYED_GRADS and not ofk and hasattr(be, "gru_chain_keys_supported") and be.gru_chain_keys_supported(d))
             keys = (torch.empty(N, dtype=torch.int32, device=dev), torch.empty(ctx.n_rnn + ctx.tabs["n_panels"], 4 * d, dtype=torch.int32, device=dev)) if keyed else None
-            be.gru_chain_bwd_g4(ctx.tabs, saved, ups, lam, variant, ctx.packs, [W[r][3] for r in range(ctx.n_rnn)], g4, **({"keys": keys} if keyed else {}), **dk)
+            be.gru_chain_bwd_g4(ctx.tabs, saved, ups, lam, variant, ctx.packs, [W[r][3] for r in range(ctx.n_rnn)], g4, **({"keys": keys} if keyed else {}), **dk, **ofk)
             d_x_all = torch.empty_like(x_all)
             xsl = [slice(g["x0"], g["x1"]) for g in groups]
             hsl = [slice(g["h0"], g["h1"]) for g in groups]
@@ -446,12 +472,12 @@ class _GruChainFn(torch.autograd.Function):
                     grads[4 * g["rnn"] + k] = gw[k]
             if not covered.all():
                 d_x_all[torch.from_numpy(~covered).to(dev)] = 0
-            return (d_x_all, None, None, None, None, None, None) + decay_grads() + tuple(grads)
+            return (d_x_all, None, None, None, None, None, None) + decay_grads() + offset_grads() + tuple(grads)
         dgi = torch.empty(N, G, dtype=torch.float32, device=dev)
         dgh = torch.empty(N, 3 * d, dtype=torch.float32, device=dev)
         if ctx.tabs is not None:
             ups = [dH] if ctx.want is None else [given.get(i) for i in ctx.want]
-            be.gru_chain_bwd(ctx.tabs, saved, ups, lam, variant, ctx.packs, [W[r][3] for r in range(ctx.n_rnn)], dgi, dgh, **dk)
+            be.gru_chain_bwd(ctx.tabs, saved, ups, lam, variant, ctx.packs, [W[r][3] for r in range(ctx.n_rnn)], dgi, dgh, **dk, **ofk)
         else:
             tens = prog.upload(dev)
             decv = torch.empty(N, dtype=torch.float32, device=dev)
@@ -497,7 +523,7 @@ class _GruChainFn(torch.autograd.Function):
                 grads[j] = gw[k] if grads[j] is None else grads[j] + gw[k]
         if not written.all():
             d_x_all[torch.from_numpy(~written).to(dev)] = 0
-        return (d_x_all, None, None, None, None, None, None) + decay_grads() + tuple(grads)
+        return (d_x_all, None, None, None, None, None, None) + decay_grads() + offset_grads() + tuple(grads)
 
 
 def chain_kernels_usable(d, n_rnn=1):
@@ -510,6 +536,20 @@ def chain_decay_usable(d, variant, n_rnn=1):
     """True when the chain kernels of this backend, width and cell variant take a learnable decay (gru_chain(decay=...))."""
     be = get_backend()
     return bool(chain_kernels_usable(d, n_rnn) and hasattr(be, "gru_chain_decay_supported") and be.gru_chain_decay_supported(d, variant))
+
+
+def chain_offset_usable(d, variant, n_rnn=1):
+    """True when the chain kernels of this backend, width and cell variant take a state offset (gru_chain(offset=...))."""
+    be = get_backend()
+    return bool(chain_kernels_usable(d, n_rnn) and hasattr(be, "gru_chain_offset_supported") and be.gru_chain_offset_supported(d, variant))
+
+
+def offset_tables(index_np, n_rows, device):
+    """Device half of gru_chain's `offset` for a static row list: (index int32 [n_total], inverse) -- the inverse is
+    functional.gather_inverse's (seg_ptr, order), the deterministic adjoint of the gather table[index].  Built once per prepared batch."""
+    from .functional import gather_inverse
+    index_np = np.asarray(index_np).reshape(-1)
+    return _lib.to_device(index_np.astype(np.int32), device), gather_inverse(index_np, int(n_rows), device)
 
 
 def program_on_chain_kernels(prog, device, want):
@@ -535,8 +575,11 @@ def zero_state_program(n):
     return GruProgram([GruInstance(n, 0, 0, -1, np.full(n, -1, dtype=np.int32), np.zeros(n, dtype=np.float32))])
 
 
-def gru_chain(x_all, prog, rnns, lam, type1=False, want=None, x_keys=None, decay=None):
-    """Run a GruProgram.  decay: None = exp(-dt lam), or the layer's decay_spec() = (weight (1, 1), bias (1,)) of --learnable-lambda:
+def gru_chain(x_all, prog, rnns, lam, type1=False, want=None, x_keys=None, decay=None, offset=None):
+    """Run a GruProgram.  offset: None, or (table [T, d], index) / (table, index, inverse) of --use-time-embedding: row i leaves
+    s_i = GRU(x_i, dec . s_prev) + table[index[i]] (index: int32 [n_total] on x_all's device, -1 = no offset), the states returned and
+    carried on include it and `table` receives its gradient; (index, inverse) = offset_tables(...) -- without `inverse` it is built
+    here from a host copy of `index` (a sync: prepare it instead).  Chain kernels only: anything they refuse raises.  decay: None = exp(-dt lam), or the layer's decay_spec() = (weight (1, 1), bias (1,)) of --learnable-lambda:
     exp(-max(w dt + b, 0)), shared by all `rnns` (`lam` is not read; chain kernels only: anything they refuse raises).  x_keys: (row keys, column keys) of x_all from functional.gather_rows(keys=True), or None.  `rnns`: list of modules holding (weight_ih, weight_hh, bias_ih, bias_hh)
     (nn.GRU layer 0 or the type-1 GRUCell).  Returns H_all (prog.n_total, d), or -- with `want` = a list of instance ids --
     the states of just those instances (a tuple of (n_i, d) tensors; instances with 0 rows give empty tensors)."""
@@ -546,6 +589,11 @@ def gru_chain(x_all, prog, rnns, lam, type1=False, want=None, x_keys=None, decay
             ws += [r.weight_ih, r.weight_hh, r.bias_ih, r.bias_hh]
         else:
             ws += [r.weight_ih_l0, r.weight_hh_l0, r.bias_ih_l0, r.bias_hh_l0]
+    off = (None, None, None)
+    if offset is not None:
+        table, index = offset[0], offset[1]
+        inverse = offset[2] if len(offset) > 2 else offset_tables(index.detach().cpu().numpy(), table.shape[0], index.device)[1]
+        off = (table, index, inverse)
     return _GruChainFn.apply(x_all, prog, float(lam), _lib.GRU_TYPE1 if type1 else _lib.GRU_TORCH, len(rnns),
                              tuple(want) if want is not None else None, x_keys, decay[0] if decay is not None else None,
-                             decay[1] if decay is not None else None, *ws)
+                             decay[1] if decay is not None else None, *off, *ws)

@@ -74,6 +74,7 @@ class _PostWindowMixin:
     _window_base = None                   # DynamicRGCN | BiDynamicRGCN: the window model whose batched all-entity pass applies
     _evaluater = "EvaluationFilter"       # the class of temp_amd.evaluation that ranks for evaluate()
     _two_stream = False                   # get_all_embeds_Gt takes (local, temporal) target rows and returns both matrices
+    _chain_time_embedding = False         # --use-time-embedding also shifts the local stream: these models keep the per-position loop for it
 
     def _chain_input_rows(self, wb, inst_id=None, step=None):
         """GRU-input rows (= local layer-2 states) of one chain instance / step of a batched run."""

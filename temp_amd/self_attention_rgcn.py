@@ -29,6 +29,7 @@ from .window import window_times
 
 class SelfAttentionRGCN(DynamicRGCN):
     bidirectional = False
+    _chain_time_embedding = False         # no GRU chain here: the attention path adds the time embedding itself
 
     def __init__(self, args, num_ents, num_rels, graph_dict_train, graph_dict_val, graph_dict_test, evaluater_type=None):
         super().__init__(args, num_ents, num_rels, graph_dict_train, graph_dict_val, graph_dict_test, evaluater_type)
