@@ -503,7 +503,7 @@ int temp_gru_weight_grads_multi(int count, const int* ns, int d, int variant, co
                                 const float* const* dgis, const float* const* dghs, const float* const* w_ihs, float* const* d_xs,
                                 float* d_w, float* d_b, void* workspace, size_t workspace_bytes, void* stream);
 
-/* Weight / bias gradients and d_x of `count` <= 4 GRUs from their gate-gradient matrices g4s[i] = [ns[i]][4d] (temp_gru_chain_bwd_g4):
+/* Weight / bias gradients and d_x of `count` <= 4 GRUs from their gate-gradient matrices g4s[i] = [ns[i]][4d] (temp_gru_chain_bwd's g4):
  *   d_W_ih = [dr dz dn_i]^T x,  d_W_hh = [dr dz dn_h]^T hdec,  d_b_* = the column sums,  d_x = [dr dz dn_i] . W_ih
  * (the backward of the GRU step, models/RRGCN.py:84) -- ONE weight-gradient launch (k_gru_wgrad: both products of every GRU read
  * their columns of the one matrix through a column map; the row-wise sums take their fragments through LDS transpose reads, no
@@ -516,7 +516,7 @@ size_t temp_gru_grads_g4_workspace(int count, const int* ns, int d);
 int temp_gru_grads_g4(int count, const int* ns, int d, const float* const* xs, const float* const* hdecs, const float* const* g4s,
                       const float* const* w_ihs, float* const* d_xs, float* d_w, float* d_b, void* workspace, size_t workspace_bytes,
                       void* stream);
-/* Round 6: the same with the keys temp_gru_chain_bwd_g4_keys hands out (HOST arrays of `count` device pointers; NULL arrays or
+/* Round 6: the same with the keys temp_gru_chain_bwd hands out (HOST arrays of `count` device pointers; NULL arrays or
  * TEMP_OPT_MFMA_F16X2 = 0: exactly temp_gru_grads_g4).  g4_col_keys[i]: [4d] keys bounding the column magnitudes of g4s[i];
  * g4_row_keys[i]: [ns[i]] keys of the rows' max |[dr dz dn_i]|.  With them the products run as three f16 MFMA products of the
  * scaled two-way split (split_f16.hpp) instead of six bf16 products; hdecs must be decayed GRU states (|hdec| < 4: they are split
@@ -547,13 +547,28 @@ int temp_gru_grads_g4_keys(int count, const int* ns, int d, const float* const* 
  *                           up: index into `up` of the upstream gradient block of the step's rows or -1,
  *                           up_row0: first row of that block in the [N_total] row space, 0 }
  * Steps of a panel are consecutive table rows in chain order.  gi / saved / dgi / dgh / h: as for temp_gru_cell_*.
- * The calls below decay the previous state by exp(-dt lambda) (c->lambda); the temp_gru_chain_*_decay calls further down take a
- * learnable decay instead.  d % 4 == 0 and d <= TEMP_CHAIN_MAX_D (LDS), else TEMP_E_UNSUPPORTED.
+ * The previous state of a row with time gap dt is scaled by exp(-dt lambda) (c->lambda), or by a learnable decay (c->decay); a state
+ * offset (c->offset) is added behind the cell.  d % 4 == 0 and d <= TEMP_CHAIN_MAX_D (LDS), else TEMP_E_UNSUPPORTED.
  * ---------------------------------------------------------------------------------------------- */
 #define TEMP_CHAIN_HAS_PREV (1 << 30)
 #define TEMP_CHAIN_TRACKS 32
 #define TEMP_CHAIN_MAX_RNN 4
 #define TEMP_CHAIN_MAX_UP 8
+/* Learnable decay (--learnable-lambda; RGCNLayer.decay_hidden, models/RGCN.py:106-107): exp(-max(w dt + b, 0)) instead of
+ * exp(-dt lambda); c->lambda is not read.  wb[i]: DEVICE {w, b} of GRU i (no host read, no sync: capturable); GRUs may share one pair. */
+typedef struct TempChainDecay { const float* wb[TEMP_CHAIN_MAX_RNN]; } TempChainDecay;
+/* State offset (--use-time-embedding; models/RRGCN.py:192-204, models/BiRRGCN.py:228-240): the state a row hands on is
+ *   s_rho = GRU(x_rho, dec . s_prev) + table[index[rho]]
+ * -- the add follows the cell and becomes part of the recurrent state, so |s| is not bounded by 1.  table: DEVICE [n_rows][d], shared
+ * by all GRUs of the chain (layer_2.time_embed); index: DEVICE int32 [N_total], an entry outside [0, n_rows) (-1) = no offset.
+ * Pointers only, no host read: capturable.  Composes with either decay.
+ *   Layout: the f16 kernels (TEMP_CHAIN_PACK_HX, _HX_X) split the state with the constant scale 2^14, which needs |state| < 4: an
+ *     offset chain runs on the TEMP_CHAIN_PACK_BX kernels (exact three-way bf16 split, any range), or _F32 where d % 8 != 0 or the
+ *     bf16 route is off.  temp_gru_chain_offset_layout(d) names that layout; temp_gru_chain_pack_multi_layout writes it.
+ *   Forward: h_out and the state kept for the next position are the sum; saved[4] stays the decayed previous state (now
+ *     dec . s_prev), so the gate arithmetic and the weight gradients are those of a chain without offset.  Consumers of saved[4] must
+ *     not assume |hdec| < 4 (temp_gru_grads_g4, not _g4_keys). */
+typedef struct TempChainOffset { const float* table; const int32_t* index; int32_t n_rows; } TempChainOffset;
 typedef struct TempGruChain {
   int32_t d, variant, n_panels, n_steps;
   int32_t max_steps;                     /* longest panel (<= 64): sizes the per-panel tables the kernels stage in LDS */
@@ -571,6 +586,8 @@ typedef struct TempGruChain {
                                           * time of temp_gru_chain_pack / _pack_multi, TEMP_CHAIN_PACK_HX_X for temp_gru_chain_pack_x_multi.
                                           * The kernels follow it (not the options at launch time); a layout this width cannot have:
                                           * TEMP_E_BADARG. */
+  const TempChainDecay* decay;           /* nullable: NULL = the fixed c->lambda */
+  const TempChainOffset* offset;         /* nullable: NULL = no state offset */
 } TempGruChain;
 enum { TEMP_CHAIN_PACK_F32 = 1, TEMP_CHAIN_PACK_BX = 2, TEMP_CHAIN_PACK_HX = 3, TEMP_CHAIN_PACK_HX_X = 4 };
 /* the layout temp_gru_chain_pack / _pack_multi write for width d under the current options (TEMP_OPT_MFMA_*) */
@@ -579,90 +596,69 @@ int temp_gru_chain_supported(int d);
 size_t temp_gru_chain_pack_floats(int d);                                   /* floats of one packed W_hh */
 int temp_gru_chain_pack(int d, const float* w_hh, float* packed, void* stream);
 /* count <= TEMP_CHAIN_MAX_RNN matrices in one launch (w_hh / packed: HOST arrays of device pointers; each packed[i] holds
- * temp_gru_chain_pack_floats(d) floats) */
+ * temp_gru_chain_pack_floats(d) floats), in the layout temp_gru_chain_pack_layout(d) names / in a given layout (F32 / BX / HX) */
 int temp_gru_chain_pack_multi(int count, int d, const float* const* w_hh, float* const* packed, void* stream);
-int temp_gru_chain_fwd(const TempGruChain* c, const float* gi, float* h_out, float* saved, void* stream);
-/* The forward with the input gates computed inside (nn.GRU gate layout, f16 arithmetic): x rows instead of gi, no gate GEMM.
- *   x [x rows][d], x_index [N_total]: x row of chain row i; b_ih: HOST array of n_rnn device pointers; c->packed[i] from
- *   temp_gru_chain_pack_x_multi (W_hh laid out as temp_gru_chain_pack_multi lays it out -- the backward takes the same buffer --
- *   followed by W_ih's planes).  h_out / saved as temp_gru_chain_fwd (saved[4] = the decayed previous state, as there).
- * temp_gru_chain_fwd_x_supported: 1 when this entry takes the width, variant and c->max_steps (the f16 route is selected, the
- * LDS images fit, TEMP_DEBUG bit 22 -- the A/B switch to the gi route -- is clear); otherwise the call returns TEMP_E_UNSUPPORTED.
- * temp_gru_chain_fwd_x_launches: launches of the kernel since the library was loaded (diagnostic). */
-int temp_gru_chain_fwd_x_supported(int d, int variant, int max_steps);
+int temp_gru_chain_pack_multi_layout(int layout, int count, int d, const float* const* w_hh, float* const* packed, void* stream);
+/* x route: W_hh laid out as temp_gru_chain_pack_multi lays it out (the backward takes the same buffer), followed by W_ih's planes */
 size_t temp_gru_chain_pack_x_floats(int d);
 int temp_gru_chain_pack_x_multi(int count, int d, const float* const* w_hh, const float* const* w_ih, float* const* packed, void* stream);
-int temp_gru_chain_fwd_x(const TempGruChain* c, const float* x, const int32_t* x_index, const float* const* b_ih, float* h_out, float* saved,
-                         void* stream);
+/* The forward.  gi route: the input gates `gi` (c->gi_index applies).  x route (x != NULL): the input gates computed inside (nn.GRU
+ * gate layout, f16 arithmetic) -- x [x rows][d], x_index [N_total]: x row of chain row i, b_ih: HOST array of n_rnn device pointers,
+ * c->packed[i] from temp_gru_chain_pack_x_multi; no gate GEMM.  h_out / saved as temp_gru_cell_fwd (saved[4] = the decayed state). */
+typedef struct TempChainFwd {
+  const float* gi; const float* x; const int32_t* x_index; const float* const* b_ih;
+  float* h_out; float* saved;
+} TempChainFwd;
+int temp_gru_chain_fwd(const TempGruChain* c, const TempChainFwd* io, void* stream);
+/* The backward.  up: HOST array of n_up device pointers (sinfo's `up`).  Three output routes:
+ *   gates (g4 == NULL): dgi and dgh, as temp_gru_cell_bwd.
+ *   g4 (nn.GRU gate layout only): the gate gradients written ONCE, g4 [n_rows][4d] = [dr | dz | dn_i | dn_h] -- dgi = columns
+ *     0 .. 3d-1, dgh = columns 0 .. 2d-1 and 3d .. 4d-1 (two thirds of dgh repeated dgi).  Bit-identical values; for temp_gru_grads_g4.
+ *   g4 with keys (each nullable; HX / HX_X packs only): also what temp_gru_grads_g4_keys needs to split g4 for the f16 pipe --
+ *     row_keys [N_total]: per row the largest magnitude of [dr dz dn_i] as an unsigned key (the fp32 bits with the sign cleared;
+ *       integer order = magnitude order)
+ *     col_keys [n_rnn + n_panels][4d]: rows 0 .. n_rnn - 1 = per GRU and column of g4 a key that BOUNDS the column's largest magnitude
+ *       (integer maxima: order-independent, bit-repeatable); the n_panels rows behind them are scratch (every panel's own maxima,
+ *       reduced by a second small launch); no initialisation needed
+ * d_arg [N_total] (exactly with c->decay) = dL / d(w dt + b) of every row that has a previous state (0 where the clamp is active; the
+ *   other rows are not written):  d_arg[rho] = -[w dt_rho + b > 0] <d_prev_rho, h_pi>,  pi = the row of the same track one position earlier.
+ * d_state [N_total][d] (nullable, only with c->offset): the total gradient reaching every row's state (upstream + d_prev of its
+ *   successor; ds/dh = I, so the gate gradients are unchanged), every row written once with plain stores.  d_table is then the adjoint
+ *   of the row gather table[index] applied to d_state (temp_gather_rows' backward with a static inverse): no atomics, bit-repeatable. */
+typedef struct TempChainBwd {
+  const float* saved; int32_t n_up; const float* const* up;
+  float* dgi; float* dgh; float* g4; uint32_t* row_keys; uint32_t* col_keys;
+  float* d_arg; float* d_state;
+} TempChainBwd;
+int temp_gru_chain_bwd(const TempGruChain* c, const TempChainBwd* io, void* stream);
+/* Return contract of both calls, checked in this order; nothing is launched on an error:
+ *   1. descriptor -- NULL c / io, sizes, variant, n_rnn, max_steps, a NULL packed[i] / b_hh[i]: BADARG; a width the chain does not
+ *      take: UNSUPPORTED; a pack_layout the width cannot have: BADARG
+ *   2. c->decay -- a NULL wb[i]: BADARG; not temp_gru_chain_decay_supported: UNSUPPORTED
+ *   3. c->offset -- NULL table / index, n_rows <= 0: BADARG; not temp_gru_chain_offset_supported, or HX / HX_X packs: UNSUPPORTED
+ *   4. route, BADARG -- both gi and x; x with pack_layout != HX_X; d_state without c->offset; n_up outside [0, TEMP_CHAIN_MAX_UP] or
+ *      n_up > 0 with up NULL; (c->decay != NULL) != (d_arg != NULL); g4 together with dgi or dgh; row_keys / col_keys without g4
+ *      route, UNSUPPORTED -- x with the type-1 cell or a panel too long for its LDS images; g4 with the type-1 cell (its dgi is
+ *      [n, d]); keys with packs other than HX / HX_X (hence keys with an offset)
+ *   5. n_panels == 0: TEMP_OK;  6. only then a NULL buffer of the route (gi | x, x_index, b_ih[i]; h_out; saved; dgi, dgh | g4): BADARG
+ * "Both gi and x" and "keys without g4" are stricter than the per-feature entries before this pair (inexpressible / ignored there).
+ * temp_gru_chain_fwd_x_supported: 1 when callers should take the x route (the f16 route is selected, the LDS images fit this width
+ *   and max_steps, TEMP_DEBUG bit 22 -- the A/B switch to the gi route -- is clear).  temp_gru_chain_keys_supported: 1 when the
+ *   kernels of this width produce keys (f16 arithmetic selected and its LDS images fit).
+ * temp_gru_chain_{fwd_x,decay,offset}_launches (diagnostic, since the library was loaded): launches of the x route's kernel; chain
+ *   forward / backward launches with a learnable decay; with an offset. */
+int temp_gru_chain_fwd_x_supported(int d, int variant, int max_steps);
 long long temp_gru_chain_fwd_x_launches(void);
-int temp_gru_chain_bwd(const TempGruChain* c, const float* saved, int n_up, const float* const* up /* HOST array of device pointers */,
-                       float* dgi, float* dgh, void* stream);
-/* The same backward with the gate gradients written ONCE (round 5; nn.GRU gate layout only):
- *   g4 [n_rows][4d] = [dr | dz | dn_i | dn_h]  -- dgi = columns 0 .. 3d-1, dgh = columns 0 .. 2d-1 and 3d .. 4d-1 (two thirds of dgh
- * repeated dgi: 1 600 bytes per row less to write at d = 200).  Bit-identical values.  Consumed by temp_gru_grads_g4. */
-int temp_gru_chain_bwd_g4(const TempGruChain* c, const float* saved, int n_up, const float* const* up /* HOST array of device pointers */,
-                          float* g4, void* stream);
-/* Round 6: the same, also handing out what the consumers of g4 need to split it for the f16 pipe (temp_gru_grads_g4_keys):
- *   row_keys [N_total]    : per row the largest magnitude of [dr dz dn_i] as an unsigned key (the fp32 bits with the sign cleared;
- *                           integer order = magnitude order)
- *   col_keys [n_rnn + n_panels][4d] : rows 0 .. n_rnn - 1 = per GRU and column of g4 a key that BOUNDS the column's largest magnitude
- *                           (integer maxima: order-independent, bit-repeatable); the n_panels rows behind them are scratch (every
- *                           panel's own maxima, reduced by a second small launch); no initialisation needed
- * temp_gru_chain_keys_supported(d): 1 when the chain kernels of this width produce keys (f16 arithmetic selected and its LDS
- * images fit); otherwise this call returns TEMP_E_UNSUPPORTED and the caller uses temp_gru_chain_bwd_g4. */
 int temp_gru_chain_keys_supported(int d);
-int temp_gru_chain_bwd_g4_keys(const TempGruChain* c, const float* saved, int n_up, const float* const* up, float* g4,
-                               uint32_t* row_keys, uint32_t* col_keys, void* stream);
-/* Learnable decay (--learnable-lambda; RGCNLayer.decay_hidden, models/RGCN.py:106-107): the previous state of a row with time gap dt
- * is scaled by exp(-max(w dt + b, 0)) instead of exp(-dt lambda); c->lambda is not read.  wb[i]: DEVICE {w, b} of GRU i (no host
- * read, no sync: capturable); the GRUs may share one pair.  The same launch code as the calls above, which are its decay == NULL case.
- *   temp_gru_chain_decay_supported: 1 where the chain kernels of this width and cell variant take a learnable decay.
- *   temp_gru_chain_bwd_decay: the three backward routes in one call -- g4 == NULL: (dgi, dgh) as temp_gru_chain_bwd; g4 with dgi ==
- *     dgh == NULL: temp_gru_chain_bwd_g4, or with row_keys / col_keys temp_gru_chain_bwd_g4_keys.  Also writes
- *     d_arg [N_total] = dL / d(w dt + b) of every row that has a previous state (0 where the clamp is active; the other rows are
- *     not written):  d_arg[rho] = -[w dt_rho + b > 0] <d_prev_rho, h_pi>,  pi = the row of the same track one position earlier.
- *   temp_gru_chain_decay_reduce: d_wb [n_rnn][2] = per GRU { sum d_arg dt, sum d_arg } over its rows with a previous state, in a
- *     fixed order (per-panel partials in `ws`, temp_gru_chain_decay_reduce_workspace(c) bytes; no atomics: bit-repeatable).
- *   temp_gru_chain_decay_launches: chain forward / backward launches with a learnable decay since the library was loaded (diagnostic). */
-typedef struct TempChainDecay { const float* wb[TEMP_CHAIN_MAX_RNN]; } TempChainDecay;
 int temp_gru_chain_decay_supported(int d, int variant);
-int temp_gru_chain_fwd_decay(const TempGruChain* c, const TempChainDecay* decay, const float* gi, float* h_out, float* saved, void* stream);
-int temp_gru_chain_fwd_x_decay(const TempGruChain* c, const TempChainDecay* decay, const float* x, const int32_t* x_index,
-                               const float* const* b_ih, float* h_out, float* saved, void* stream);
-int temp_gru_chain_bwd_decay(const TempGruChain* c, const TempChainDecay* decay, const float* saved, int n_up, const float* const* up,
-                             float* dgi, float* dgh, float* g4, uint32_t* row_keys, uint32_t* col_keys, float* d_arg, void* stream);
-size_t temp_gru_chain_decay_reduce_workspace(const TempGruChain* c);
-int temp_gru_chain_decay_reduce(const TempGruChain* c, const float* d_arg, float* d_wb, void* ws, size_t ws_bytes, void* stream);
 long long temp_gru_chain_decay_launches(void);
-/* State offset (--use-time-embedding; models/RRGCN.py:192-204, models/BiRRGCN.py:228-240): the state a row hands on is
- *   s_rho = GRU(x_rho, dec . s_prev) + table[index[rho]]
- * -- the add follows the cell and becomes part of the recurrent state, so |s| is not bounded by 1.  table: DEVICE [n_rows][d], shared
- * by all GRUs of the chain (layer_2.time_embed); index: DEVICE int32 [N_total], an entry outside [0, n_rows) (-1) = no offset.
- * Pointers only, no host read: capturable.  The same launch code as the calls above, which are its offset == NULL case; `decay` is
- * nullable (NULL = exp(-dt lambda)), so both compose.
- *   Layout: the f16 kernels (TEMP_CHAIN_PACK_HX, _HX_X) split the state with the constant scale 2^14, which needs |state| < 4: an
- *     offset chain runs on the TEMP_CHAIN_PACK_BX kernels (exact three-way bf16 split, any range), or _F32 where d % 8 != 0 or the
- *     bf16 route is off.  temp_gru_chain_offset_layout(d) names that layout; temp_gru_chain_pack_multi_layout writes a given layout
- *     (F32 / BX / HX) whatever the options select (temp_gru_chain_pack_multi = the layout temp_gru_chain_pack_layout(d) names).  An
- *     offset with c->pack_layout HX / HX_X: TEMP_E_UNSUPPORTED, nothing launched.
- *   temp_gru_chain_fwd_offset: h_out and the state kept for the next position are the sum; saved[4] stays the decayed previous
- *     state (now dec . s_prev), so the gate arithmetic and the weight gradients are those of the calls above.  Consumers of saved[4]
- *     must not assume |hdec| < 4 (temp_gru_grads_g4, not _g4_keys).
- *   temp_gru_chain_bwd_offset: g4 == NULL: (dgi, dgh) as temp_gru_chain_bwd; g4 with dgi == dgh == NULL: temp_gru_chain_bwd_g4.
- *     d_arg: required with `decay`, NULL without.  d_state (nullable) [N_total][d]: the total gradient reaching every row's state
- *     (its upstream gradient + d_prev of its successor; ds/dh = I, so the gate gradients are unchanged); every row is written exactly
- *     once with plain stores.  d_table is then the adjoint of the row gather table[index] applied to d_state (temp_gather_rows'
- *     backward with a static inverse): no atomics, bit-repeatable.
- *   temp_gru_chain_offset_launches: chain forward / backward launches with an offset since the library was loaded (diagnostic). */
-typedef struct TempChainOffset { const float* table; const int32_t* index; int32_t n_rows; } TempChainOffset;
 int temp_gru_chain_offset_supported(int d, int variant);
 int temp_gru_chain_offset_layout(int d);
-int temp_gru_chain_pack_multi_layout(int layout, int count, int d, const float* const* w_hh, float* const* packed, void* stream);
-int temp_gru_chain_fwd_offset(const TempGruChain* c, const TempChainDecay* decay, const TempChainOffset* offset, const float* gi, float* h_out,
-                              float* saved, void* stream);
-int temp_gru_chain_bwd_offset(const TempGruChain* c, const TempChainDecay* decay, const TempChainOffset* offset, const float* saved, int n_up,
-                              const float* const* up, float* dgi, float* dgh, float* g4, float* d_arg, float* d_state, void* stream);
 long long temp_gru_chain_offset_launches(void);
+/* d_wb [n_rnn][2] = per GRU { sum d_arg dt, sum d_arg } over its rows with a previous state, in a fixed order (per-panel partials in
+ * `ws`, temp_gru_chain_decay_reduce_workspace(c) bytes; no atomics: bit-repeatable).  Reads c's tables and n_rnn only. */
+size_t temp_gru_chain_decay_reduce_workspace(const TempGruChain* c);
+int temp_gru_chain_decay_reduce(const TempGruChain* c, const float* d_arg, float* d_wb, void* ws, size_t ws_bytes, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
  * Row gather / scatter helpers of the window loop

@@ -64,19 +64,28 @@ CHAIN_MAX_STEPS = 64
 CHAIN_PACK_F32, CHAIN_PACK_BX, CHAIN_PACK_HX, CHAIN_PACK_HX_X = 1, 2, 3, 4     # TempGruChain.pack_layout
 
 
-class TempGruChain(ctypes.Structure):
-    _fields_ = [("d", ctypes.c_int32), ("variant", ctypes.c_int32), ("n_panels", ctypes.c_int32), ("n_steps", ctypes.c_int32),
-                ("max_steps", ctypes.c_int32), ("panel", c_vp), ("rows", c_vp), ("sinfo", c_vp), ("dt", c_vp), ("lambda_", ctypes.c_float),
-                ("saved_plane", ctypes.c_size_t), ("n_rnn", ctypes.c_int32), ("packed", c_vp * CHAIN_MAX_RNN), ("b_hh", c_vp * CHAIN_MAX_RNN),
-                ("gi_index", c_vp), ("pack_layout", ctypes.c_int32)]
-
-
 class TempChainDecay(ctypes.Structure):
     _fields_ = [("wb", c_vp * CHAIN_MAX_RNN)]      # device {w, b} of every GRU's learnable decay
 
 
 class TempChainOffset(ctypes.Structure):
     _fields_ = [("table", c_vp), ("index", c_vp), ("n_rows", ctypes.c_int32)]      # device [n_rows, d] table, int32 [N_total] row of every chain row (-1: none)
+
+
+class TempGruChain(ctypes.Structure):
+    _fields_ = [("d", ctypes.c_int32), ("variant", ctypes.c_int32), ("n_panels", ctypes.c_int32), ("n_steps", ctypes.c_int32),
+                ("max_steps", ctypes.c_int32), ("panel", c_vp), ("rows", c_vp), ("sinfo", c_vp), ("dt", c_vp), ("lambda_", ctypes.c_float),
+                ("saved_plane", ctypes.c_size_t), ("n_rnn", ctypes.c_int32), ("packed", c_vp * CHAIN_MAX_RNN), ("b_hh", c_vp * CHAIN_MAX_RNN),
+                ("gi_index", c_vp), ("pack_layout", ctypes.c_int32),
+                ("decay", ctypes.POINTER(TempChainDecay)), ("offset", ctypes.POINTER(TempChainOffset))]      # nullable
+
+
+class TempChainFwd(ctypes.Structure):
+    _fields_ = [(n, c_vp) for n in ("gi", "x", "x_index", "b_ih", "h_out", "saved")]
+
+
+class TempChainBwd(ctypes.Structure):
+    _fields_ = [("saved", c_vp), ("n_up", ctypes.c_int32), ("up", c_vp)] + [(n, c_vp) for n in ("dgi", "dgh", "g4", "row_keys", "col_keys", "d_arg", "d_state")]
 
 
 class TempSubsampleJob(ctypes.Structure):
@@ -162,31 +171,21 @@ SYMBOLS = {
     "temp_gru_chain_pack_floats": (_SZ, [_I]),
     "temp_gru_chain_pack": (_I, [_I, c_vp, c_vp, c_vp]),
     "temp_gru_chain_pack_multi": (_I, [_I, _I, ctypes.POINTER(c_vp), ctypes.POINTER(c_vp), c_vp]),
-    "temp_gru_chain_fwd": (_I, [ctypes.POINTER(TempGruChain), c_vp, c_vp, c_vp, c_vp]),
+    "temp_gru_chain_fwd": (_I, [ctypes.POINTER(TempGruChain), ctypes.POINTER(TempChainFwd), c_vp]),
     "temp_gru_chain_pack_layout": (_I, [_I]),
     "temp_gru_chain_fwd_x_supported": (_I, [_I, _I, _I]),
     "temp_gru_chain_pack_x_floats": (_SZ, [_I]),
     "temp_gru_chain_pack_x_multi": (_I, [_I, _I, ctypes.POINTER(c_vp), ctypes.POINTER(c_vp), ctypes.POINTER(c_vp), c_vp]),
-    "temp_gru_chain_fwd_x": (_I, [ctypes.POINTER(TempGruChain), c_vp, c_vp, ctypes.POINTER(c_vp), c_vp, c_vp, c_vp]),
     "temp_gru_chain_fwd_x_launches": (ctypes.c_longlong, []),
-    "temp_gru_chain_bwd": (_I, [ctypes.POINTER(TempGruChain), c_vp, _I, ctypes.POINTER(c_vp), c_vp, c_vp, c_vp]),
-    "temp_gru_chain_bwd_g4": (_I, [ctypes.POINTER(TempGruChain), c_vp, _I, ctypes.POINTER(c_vp), c_vp, c_vp]),
+    "temp_gru_chain_bwd": (_I, [ctypes.POINTER(TempGruChain), ctypes.POINTER(TempChainBwd), c_vp]),
     "temp_gru_chain_keys_supported": (_I, [_I]),
-    "temp_gru_chain_bwd_g4_keys": (_I, [ctypes.POINTER(TempGruChain), c_vp, _I, ctypes.POINTER(c_vp), c_vp, c_vp, c_vp, c_vp]),
     "temp_gru_chain_decay_supported": (_I, [_I, _I]),
-    "temp_gru_chain_fwd_decay": (_I, [ctypes.POINTER(TempGruChain), ctypes.POINTER(TempChainDecay), c_vp, c_vp, c_vp, c_vp]),
-    "temp_gru_chain_fwd_x_decay": (_I, [ctypes.POINTER(TempGruChain), ctypes.POINTER(TempChainDecay), c_vp, c_vp, ctypes.POINTER(c_vp), c_vp, c_vp, c_vp]),
-    "temp_gru_chain_bwd_decay": (_I, [ctypes.POINTER(TempGruChain), ctypes.POINTER(TempChainDecay), c_vp, _I, ctypes.POINTER(c_vp), c_vp, c_vp, c_vp, c_vp, c_vp,
-                                      c_vp, c_vp]),
     "temp_gru_chain_decay_reduce_workspace": (_SZ, [ctypes.POINTER(TempGruChain)]),
     "temp_gru_chain_decay_reduce": (_I, [ctypes.POINTER(TempGruChain), c_vp, c_vp, c_vp, _SZ, c_vp]),
     "temp_gru_chain_decay_launches": (ctypes.c_longlong, []),
     "temp_gru_chain_offset_supported": (_I, [_I, _I]),
     "temp_gru_chain_offset_layout": (_I, [_I]),
     "temp_gru_chain_pack_multi_layout": (_I, [_I, _I, _I, ctypes.POINTER(c_vp), ctypes.POINTER(c_vp), c_vp]),
-    "temp_gru_chain_fwd_offset": (_I, [ctypes.POINTER(TempGruChain), ctypes.POINTER(TempChainDecay), ctypes.POINTER(TempChainOffset), c_vp, c_vp, c_vp, c_vp]),
-    "temp_gru_chain_bwd_offset": (_I, [ctypes.POINTER(TempGruChain), ctypes.POINTER(TempChainDecay), ctypes.POINTER(TempChainOffset), c_vp, _I,
-                                       ctypes.POINTER(c_vp), c_vp, c_vp, c_vp, c_vp, c_vp, c_vp]),
     "temp_gru_chain_offset_launches": (ctypes.c_longlong, []),
     "temp_gru_grads_g4_keys": (_I, [_I, c_vp, _I, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, ctypes.c_size_t, c_vp]),
     "temp_gru_grads_g4_workspace": (ctypes.c_size_t, [_I, c_vp, _I]),

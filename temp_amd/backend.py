@@ -416,44 +416,52 @@ class HipBackend:
             pk.chain_pack_layout = layout
         return packs
 
-    def _chain_desc(self, tabs, d, variant, lam, plane, packs, b_hhs):
+    def _chain_desc(self, tabs, d, variant, lam=0.0, plane=0, packs=(), b_hhs=(), decay=None, offset=None, n_rnn=None):
+        """-> (TempGruChain, the objects it points to: hold both until the call has returned).  plane = N_total * d.  Without packs:
+        the tables and n_rnn alone (gru_chain_decay_reduce).
+        decay (include/temp_amd.h: TempChainDecay) = a float32 device tensor {w, b} shared by all GRUs of the chain (`lam` is not read
+        then); offset (TempChainOffset) = (table float32 [T, d], index int32 [N_total], -1 = none): the states handed out and carried
+        on are GRU(...) + table[index]; the packs must be in gru_chain_offset_layout(d) (gru_chain_pack_multi(layout=...))."""
         c = _lib.TempGruChain()
         c.d, c.variant, c.n_panels, c.n_steps, c.max_steps = d, variant, tabs["n_panels"], tabs["n_steps"], tabs["max_steps"]
         c.panel, c.rows, c.sinfo, c.dt = (_i32(tabs[k], k).data_ptr() for k in ("panel", "rows", "sinfo", "dt_bits"))
-        c.lambda_, c.saved_plane, c.n_rnn = float(lam), plane, len(packs)
-        layouts = {getattr(pk, "chain_pack_layout", None) for pk in packs}
-        assert len(layouts) == 1 and None not in layouts, "chain packs without one common layout tag (gru_chain_pack*)"
-        c.pack_layout = layouts.pop()
+        c.lambda_, c.saved_plane, c.n_rnn = float(lam), plane, len(packs) or n_rnn
         keep = []
+        if packs:
+            layouts = {getattr(pk, "chain_pack_layout", None) for pk in packs}
+            assert len(layouts) == 1 and None not in layouts, "chain packs without one common layout tag (gru_chain_pack*)"
+            c.pack_layout = layouts.pop()
         for i, (pk, b) in enumerate(zip(packs, b_hhs)):
             pk, b = _f32(pk, "packed"), _f32(b, "b_hh")
             keep += [pk, b]
             c.packed[i], c.b_hh[i] = pk.data_ptr(), b.data_ptr()
+        if decay is not None:
+            decay = _f32(decay, "decay")
+            assert decay.numel() == 2
+            cd = _lib.TempChainDecay()
+            for i in range(c.n_rnn):
+                cd.wb[i] = decay.data_ptr()
+            c.decay = ctypes.pointer(cd)
+            keep += [cd, decay]
+        if offset is not None:
+            table, index = _f32(offset[0], "offset table"), _i32(offset[1], "offset index")
+            assert table.dim() == 2 and table.shape[1] == d and index.numel() * d == plane
+            co = _lib.TempChainOffset()
+            co.table, co.index, co.n_rows = table.data_ptr(), index.data_ptr(), table.shape[0]
+            c.offset = ctypes.pointer(co)
+            keep += [co, table, index]
         return c, keep
 
-    # Learnable decay (include/temp_amd.h: TempChainDecay): `decay` = a float32 device tensor {w, b} shared by all GRUs of the chain
-    # (`lam` is not read then); the backward also takes `d_arg` float32 [N_total] for the per-row gradient of w dt + b.
     def gru_chain_decay_supported(self, d, variant):
         return bool(self.lib.temp_gru_chain_decay_supported(int(d), int(variant)))
 
     def gru_chain_decay_launches(self):
         return int(self.lib.temp_gru_chain_decay_launches())
 
-    @staticmethod
-    def _chain_decay(decay, n_rnn):
-        decay = _f32(decay, "decay")
-        assert decay.numel() == 2
-        cd = _lib.TempChainDecay()
-        for i in range(n_rnn):
-            cd.wb[i] = decay.data_ptr()
-        return cd
-
     def gru_chain_decay_reduce(self, tabs, d, variant, d_arg, n_rnn):
         """d_arg [N_total] of gru_chain_bwd*(decay=, d_arg=) -> float32 [n_rnn, 2]: per GRU (sum d_arg dt, sum d_arg) over its rows
         with a previous state, in a fixed order (temp_gru_chain_decay_reduce)."""
-        c = _lib.TempGruChain()
-        c.d, c.variant, c.n_panels, c.n_steps, c.max_steps, c.n_rnn = d, variant, tabs["n_panels"], tabs["n_steps"], tabs["max_steps"], n_rnn
-        c.panel, c.rows, c.sinfo, c.dt = (_i32(tabs[k], k).data_ptr() for k in ("panel", "rows", "sinfo", "dt_bits"))
+        c, keep = self._chain_desc(tabs, d, variant, n_rnn=n_rnn)
         d_arg = _f32(d_arg, "d_arg")
         out = torch.empty(n_rnn, 2, dtype=torch.float32, device=d_arg.device)
         nb = int(self.lib.temp_gru_chain_decay_reduce_workspace(ctypes.byref(c)))
@@ -461,9 +469,6 @@ class HipBackend:
         _lib.check(self.lib.temp_gru_chain_decay_reduce(ctypes.byref(c), _ptr(d_arg), _ptr(out), _ptr(ws), nb, _stream()), "temp_gru_chain_decay_reduce")
         return out
 
-    # State offset (include/temp_amd.h: TempChainOffset): `offset` = (table float32 [T, d], index int32 [N_total], -1 = none); the
-    # states handed out and carried on are GRU(...) + table[index].  The packs must be in gru_chain_offset_layout(d)
-    # (gru_chain_pack_multi(layout=...)); the backward also takes `d_state` float32 [N_total, d] for the gradient reaching every state.
     def gru_chain_offset_supported(self, d, variant):
         return bool(self.lib.temp_gru_chain_offset_supported(int(d), int(variant)))
 
@@ -473,43 +478,24 @@ class HipBackend:
     def gru_chain_offset_launches(self):
         return int(self.lib.temp_gru_chain_offset_launches())
 
-    @staticmethod
-    def _chain_offset(offset, n_total, d):
-        table, index = _f32(offset[0], "offset table"), _i32(offset[1], "offset index")
-        assert table.dim() == 2 and table.shape[1] == d and index.numel() == n_total
-        co = _lib.TempChainOffset()
-        co.table, co.index, co.n_rows = table.data_ptr(), index.data_ptr(), table.shape[0]
-        return co, (table, index)
-
     def gru_chain_fwd(self, tabs, gi, lam, variant, packs, b_hhs, h_out, saved_all, gi_index=None, decay=None, offset=None):
         d = saved_all.shape[2]
-        c, keep = self._chain_desc(tabs, d, variant, lam, saved_all.shape[1] * d, packs, b_hhs)
+        c, keep = self._chain_desc(tabs, d, variant, lam, saved_all.shape[1] * d, packs, b_hhs, decay, offset)
         if gi_index is not None:
             assert gi_index.shape[0] == saved_all.shape[1]
             c.gi_index = _i32(gi_index, "gi_index").data_ptr()
-        if offset is not None:
-            co, keep_o = self._chain_offset(offset, saved_all.shape[1], d)
-            cd = self._chain_decay(decay, len(packs)) if decay is not None else None
-            rc = self.lib.temp_gru_chain_fwd_offset(ctypes.byref(c), ctypes.byref(cd) if cd is not None else None, ctypes.byref(co), _ptr(_f32(gi, "gi")),
-                                                    _ptr(h_out), _ptr(saved_all), _stream())
-            _lib.check(rc, "temp_gru_chain_fwd_offset")
-            return
-        if decay is not None:
-            cd = self._chain_decay(decay, len(packs))
-            rc = self.lib.temp_gru_chain_fwd_decay(ctypes.byref(c), ctypes.byref(cd), _ptr(_f32(gi, "gi")), _ptr(h_out), _ptr(saved_all), _stream())
-            _lib.check(rc, "temp_gru_chain_fwd_decay")
-            return
-        rc = self.lib.temp_gru_chain_fwd(ctypes.byref(c), _ptr(_f32(gi, "gi")), _ptr(h_out), _ptr(saved_all), _stream())
-        _lib.check(rc, "temp_gru_chain_fwd")
+        gi = _f32(gi, "gi")
+        io = _lib.TempChainFwd(gi=gi.data_ptr(), h_out=h_out.data_ptr(), saved=saved_all.data_ptr())
+        _lib.check(self.lib.temp_gru_chain_fwd(ctypes.byref(c), ctypes.byref(io), _stream()), "temp_gru_chain_fwd")
 
     def gru_chain_fwd_x_supported(self, d, variant, max_steps):
-        """True when temp_gru_chain_fwd_x takes this width, variant and longest panel (the input gates computed inside the chain
-        forward; TEMP_DEBUG bit 22 turns it off)."""
+        """True when temp_gru_chain_fwd's x route takes this width, variant and longest panel (the input gates computed inside the
+        chain forward; TEMP_DEBUG bit 22 turns it off)."""
         return bool(self.lib.temp_gru_chain_fwd_x_supported(int(d), int(variant), int(max_steps)))
 
     def gru_chain_pack_x_multi(self, w_hhs, w_ihs):
-        """W_hh and W_ih of several GRUs -> temp_gru_chain_fwd_x's packed weights in ONE launch (list of views of one buffer; the
-        chain backward takes them like gru_chain_pack_multi's)."""
+        """W_hh and W_ih of several GRUs -> the packed weights of temp_gru_chain_fwd's x route in ONE launch (list of views of one
+        buffer; the chain backward takes them like gru_chain_pack_multi's)."""
         w_hhs, w_ihs = [_f32(w, "w_hh") for w in w_hhs], [_f32(w, "w_ih") for w in w_ihs]
         d = w_hhs[0].shape[1]
         k = len(w_hhs)
@@ -521,48 +507,32 @@ class HipBackend:
         return self._tagged([buf[i] for i in range(k)], _lib.CHAIN_PACK_HX_X)
 
     def gru_chain_fwd_x(self, tabs, x, x_index, lam, variant, packs, b_hhs, b_ihs, h_out, saved_all, decay=None):
-        """The chain forward from the x rows (x_index: int32 [N_total], x row of every chain row): no gi (temp_gru_chain_fwd_x)."""
+        """The chain forward from the x rows (x_index: int32 [N_total], x row of every chain row): no gi (temp_gru_chain_fwd's x route)."""
         d = saved_all.shape[2]
-        c, keep = self._chain_desc(tabs, d, variant, lam, saved_all.shape[1] * d, packs, b_hhs)
-        x = _f32(x, "x")
+        c, keep = self._chain_desc(tabs, d, variant, lam, saved_all.shape[1] * d, packs, b_hhs, decay)
+        x, x_index = _f32(x, "x"), _i32(x_index, "x_index")
         assert x.shape[1] == d and x_index.shape[0] == saved_all.shape[1]
         b_ihs = [_f32(b, "b_ih") for b in b_ihs]
         barr = (ctypes.c_void_p * len(b_ihs))(*[b.data_ptr() for b in b_ihs])
-        if decay is not None:
-            cd = self._chain_decay(decay, len(packs))
-            rc = self.lib.temp_gru_chain_fwd_x_decay(ctypes.byref(c), ctypes.byref(cd), _ptr(x), _ptr(_i32(x_index, "x_index")), barr, _ptr(h_out),
-                                                     _ptr(saved_all), _stream())
-            _lib.check(rc, "temp_gru_chain_fwd_x_decay")
-            return
-        rc = self.lib.temp_gru_chain_fwd_x(ctypes.byref(c), _ptr(x), _ptr(_i32(x_index, "x_index")), barr, _ptr(h_out), _ptr(saved_all), _stream())
-        _lib.check(rc, "temp_gru_chain_fwd_x")
+        io = _lib.TempChainFwd(x=x.data_ptr(), x_index=x_index.data_ptr(), b_ih=ctypes.addressof(barr), h_out=h_out.data_ptr(), saved=saved_all.data_ptr())
+        _lib.check(self.lib.temp_gru_chain_fwd(ctypes.byref(c), ctypes.byref(io), _stream()), "temp_gru_chain_fwd (x route)")
 
-    def _chain_bwd_offset(self, c, ups, arr, saved_all, packs, dgi, dgh, g4, decay, d_arg, offset, d_state):
+    def _chain_bwd(self, tabs, saved_all, ups, lam, variant, packs, b_hhs, decay, d_arg, offset, d_state, **out):
+        """One temp_gru_chain_bwd call; out: the members of TempChainBwd the route writes (dgi, dgh | g4, row_keys, col_keys)."""
         d = saved_all.shape[2]
-        co, keep_o = self._chain_offset(offset, saved_all.shape[1], d)
-        cd = self._chain_decay(decay, len(packs)) if decay is not None else None
-        if d_state is not None:
-            assert d_state.dtype == torch.float32 and d_state.is_contiguous() and d_state.shape == saved_all.shape[1:]
-        rc = self.lib.temp_gru_chain_bwd_offset(ctypes.byref(c), ctypes.byref(cd) if cd is not None else None, ctypes.byref(co), _ptr(saved_all), len(ups), arr,
-                                                _ptr(dgi), _ptr(dgh), _ptr(g4), _ptr(_f32(d_arg, "d_arg")) if d_arg is not None else None, _ptr(d_state),
-                                                _stream())
-        _lib.check(rc, "temp_gru_chain_bwd_offset")
-
-    def gru_chain_bwd(self, tabs, saved_all, ups, lam, variant, packs, b_hhs, dgi, dgh, decay=None, d_arg=None, offset=None, d_state=None):
-        d = saved_all.shape[2]
-        c, keep = self._chain_desc(tabs, d, variant, lam, saved_all.shape[1] * d, packs, b_hhs)
+        c, keep = self._chain_desc(tabs, d, variant, lam, saved_all.shape[1] * d, packs, b_hhs, decay, offset)
         ups = [_f32(u, "upstream") if u is not None else None for u in ups]      # (None: that block of rows has no upstream gradient)
         arr = (ctypes.c_void_p * max(len(ups), 1))(*[u.data_ptr() if u is not None else None for u in ups])
-        if offset is not None:
-            return self._chain_bwd_offset(c, ups, arr, saved_all, packs, dgi, dgh, None, decay, d_arg, offset, d_state)
-        if decay is not None:
-            cd = self._chain_decay(decay, len(packs))
-            rc = self.lib.temp_gru_chain_bwd_decay(ctypes.byref(c), ctypes.byref(cd), _ptr(saved_all), len(ups), arr, _ptr(dgi), _ptr(dgh), None, None, None,
-                                                   _ptr(_f32(d_arg, "d_arg")), _stream())
-            _lib.check(rc, "temp_gru_chain_bwd_decay")
-            return
-        rc = self.lib.temp_gru_chain_bwd(ctypes.byref(c), _ptr(saved_all), len(ups), arr, _ptr(dgi), _ptr(dgh), _stream())
-        _lib.check(rc, "temp_gru_chain_bwd")
+        d_arg = _f32(d_arg, "d_arg")
+        if d_state is not None:
+            assert d_state.dtype == torch.float32 and d_state.is_contiguous() and d_state.shape == saved_all.shape[1:]
+        io = _lib.TempChainBwd(saved=saved_all.data_ptr(), n_up=len(ups), up=ctypes.addressof(arr))
+        for name, t in dict(out, d_arg=d_arg, d_state=d_state).items():
+            setattr(io, name, t.data_ptr() if t is not None else None)
+        _lib.check(self.lib.temp_gru_chain_bwd(ctypes.byref(c), ctypes.byref(io), _stream()), "temp_gru_chain_bwd")
+
+    def gru_chain_bwd(self, tabs, saved_all, ups, lam, variant, packs, b_hhs, dgi, dgh, decay=None, d_arg=None, offset=None, d_state=None):
+        self._chain_bwd(tabs, saved_all, ups, lam, variant, packs, b_hhs, decay, d_arg, offset, d_state, dgi=dgi, dgh=dgh)
 
     def gru_chain_keys_supported(self, d):
         """True when the chain backward of this width hands out the row / column keys of g4 (f16 two-way split selected)."""
@@ -570,33 +540,14 @@ class HipBackend:
 
     def gru_chain_bwd_g4(self, tabs, saved_all, ups, lam, variant, packs, b_hhs, g4, keys=None, decay=None, d_arg=None, offset=None, d_state=None):
         """The chain backward with the gate gradients written once: g4 [N, 4d] = [dr | dz | dn_i | dn_h] (include/temp_amd.h:
-        temp_gru_chain_bwd_g4; nn.GRU gate layout).  keys = (row_keys int32 [N], col_keys int32 [n_rnn + n_panels, 4d]; rows 0 .. n_rnn - 1 are the result): also the
-        magnitude keys the consumers of g4 split it with (temp_gru_chain_bwd_g4_keys)."""
-        d = saved_all.shape[2]
-        c, keep = self._chain_desc(tabs, d, variant, lam, saved_all.shape[1] * d, packs, b_hhs)
-        ups = [_f32(u, "upstream") if u is not None else None for u in ups]
-        arr = (ctypes.c_void_p * max(len(ups), 1))(*[u.data_ptr() if u is not None else None for u in ups])
+        TempChainBwd.g4; nn.GRU gate layout).  keys = (row_keys int32 [N], col_keys int32 [n_rnn + n_panels, 4d]; rows 0 .. n_rnn - 1 are
+        the result): also the magnitude keys the consumers of g4 split it with."""
+        row_keys, col_keys = keys if keys is not None else (None, None)
         if keys is not None:
-            row_keys, col_keys = keys
+            assert offset is None, "an offset chain hands out no keys (its states are not bounded by the f16 split's constant scale)"
             assert row_keys.dtype == torch.int32 and col_keys.dtype == torch.int32 and col_keys.is_contiguous()
-            assert row_keys.numel() == saved_all.shape[1] and col_keys.numel() == (len(packs) + tabs["n_panels"]) * 4 * d
-        if offset is not None:
-            assert keys is None, "an offset chain hands out no keys (its states are not bounded by the f16 split's constant scale)"
-            return self._chain_bwd_offset(c, ups, arr, saved_all, packs, None, None, g4, decay, d_arg, offset, d_state)
-        if decay is not None:
-            cd = self._chain_decay(decay, len(packs))
-            rk, ck = (_ptr(keys[0]), _ptr(keys[1])) if keys is not None else (None, None)
-            rc = self.lib.temp_gru_chain_bwd_decay(ctypes.byref(c), ctypes.byref(cd), _ptr(saved_all), len(ups), arr, None, None, _ptr(g4), rk, ck,
-                                                   _ptr(_f32(d_arg, "d_arg")), _stream())
-            _lib.check(rc, "temp_gru_chain_bwd_decay")
-            return
-        if keys is not None:
-            rc = self.lib.temp_gru_chain_bwd_g4_keys(ctypes.byref(c), _ptr(saved_all), len(ups), arr, _ptr(g4), _ptr(row_keys), _ptr(col_keys),
-                                                     _stream())
-            _lib.check(rc, "temp_gru_chain_bwd_g4_keys")
-            return
-        rc = self.lib.temp_gru_chain_bwd_g4(ctypes.byref(c), _ptr(saved_all), len(ups), arr, _ptr(g4), _stream())
-        _lib.check(rc, "temp_gru_chain_bwd_g4")
+            assert row_keys.numel() == saved_all.shape[1] and col_keys.numel() == (len(packs) + tabs["n_panels"]) * 4 * saved_all.shape[2]
+        self._chain_bwd(tabs, saved_all, ups, lam, variant, packs, b_hhs, decay, d_arg, offset, d_state, g4=g4, row_keys=row_keys, col_keys=col_keys)
 
     def gru_grads_g4_supported(self, ns, d, variant):
         """True when gru_grads_g4 takes GRUs of these row counts and this width (then the chain backward should write g4)."""

@@ -773,13 +773,11 @@ static bool chain_layout_ok(int layout, int d) {
 }
 static bool layout_hx(int layout) { return layout == TEMP_CHAIN_PACK_HX || layout == TEMP_CHAIN_PACK_HX_X; }
 
-// decay: nullable -- the learnable decay of every GRU of the chain (c->lambda is not read then); d_arg: nullable, backward only
-// offset: nullable -- the state offset of every row (TempChainOffset); d_state: nullable, backward only
-static ChainArgs chain_args(const TempGruChain* c, const TempChainDecay* decay = nullptr, float* d_arg = nullptr,
-                            const TempChainOffset* offset = nullptr, float* d_state = nullptr) {
+// c->decay / c->offset: nullable (TempChainDecay: c->lambda is not read then; TempChainOffset); d_arg / d_state: nullable, backward only
+static ChainArgs chain_args(const TempGruChain* c, float* d_arg = nullptr, float* d_state = nullptr) {
   ChainArgs a = {};
   a.d_arg = d_arg;
-  if (offset) { a.off_table = offset->table; a.off_index = offset->index; a.off_rows = offset->n_rows; }
+  if (c->offset) { a.off_table = c->offset->table; a.off_index = c->offset->index; a.off_rows = c->offset->n_rows; }
   a.d_state = d_state;
   const ChainGeom g = chain_geom(c->d);
   a.D = c->d; a.n_panels = c->n_panels; a.max_steps = c->max_steps; a.panel = c->panel; a.rows = c->rows; a.sinfo = c->sinfo; a.dt = c->dt;
@@ -789,7 +787,7 @@ static ChainArgs chain_args(const TempGruChain* c, const TempChainDecay* decay =
     a.rnn[i].wf = (const float4*)c->packed[i];
     a.rnn[i].wb = (const float4*)c->packed[i] + (a.layout == TEMP_CHAIN_PACK_BX ? (size_t)(g.NQ >> 1) * g.NT * 192 : (size_t)g.NT * g.NQ * 64);
     a.rnn[i].b_hh = c->b_hh[i];
-    a.rnn[i].decay_wb = decay ? decay->wb[i] : nullptr;
+    a.rnn[i].decay_wb = c->decay ? c->decay->wb[i] : nullptr;
     a.rnn[i].kf = a.rnn[i].kb = nullptr;
     if (layout_hx(a.layout)) {
       const ChainGeomHx gx = chain_geom_hx(c->d);
@@ -1045,44 +1043,46 @@ int temp_gru_chain_pack_multi_layout(int layout, int count, int d, const float* 
 
 }  // extern "C"
 
-// launches of a chain forward / backward kernel with a learnable decay since the library was loaded (diagnostic)
+// launches of a chain forward / backward kernel with a learnable decay / a state offset since the library was loaded (diagnostic)
 static std::atomic<long long> g_decay_launches{0};
-static int chain_decay_check(const TempGruChain* c, const TempChainDecay* decay) {
-  if (!decay) return TEMP_OK;
-  for (int i = 0; i < c->n_rnn; ++i) if (!decay->wb[i]) return TEMP_E_BADARG;
+static std::atomic<long long> g_offset_launches{0};
+static void chain_count(const TempGruChain* c) {
+  if (c->decay) g_decay_launches.fetch_add(1, std::memory_order_relaxed);
+  if (c->offset) g_offset_launches.fetch_add(1, std::memory_order_relaxed);
+}
+static int chain_decay_check(const TempGruChain* c) {
+  if (!c->decay) return TEMP_OK;
+  for (int i = 0; i < c->n_rnn; ++i) if (!c->decay->wb[i]) return TEMP_E_BADARG;
   return temp_gru_chain_decay_supported(c->d, c->variant) ? TEMP_OK : TEMP_E_UNSUPPORTED;
 }
-
-// launches of a chain forward / backward kernel with a state offset since the library was loaded (diagnostic)
-static std::atomic<long long> g_offset_launches{0};
-static int chain_offset_check(const TempGruChain* c, const TempChainOffset* offset) {
-  if (!offset) return TEMP_OK;
-  if (!offset->table || !offset->index || offset->n_rows <= 0) return TEMP_E_BADARG;
+static int chain_offset_check(const TempGruChain* c) {
+  if (!c->offset) return TEMP_OK;
+  if (!c->offset->table || !c->offset->index || c->offset->n_rows <= 0) return TEMP_E_BADARG;
   if (!temp_gru_chain_offset_supported(c->d, c->variant)) return TEMP_E_UNSUPPORTED;
   return layout_hx(c->pack_layout) ? TEMP_E_UNSUPPORTED : TEMP_OK;      // (the f16 kernels split the state with the constant scale 2^14: |state| < 4)
 }
+// the checks both directions and both forward routes start with (include/temp_amd.h: return contract, 1 - 3)
+static int chain_desc_check(const TempGruChain* c, const void* io) {
+  int rc = io ? chain_check(c) : TEMP_E_BADARG;
+  if (!rc) rc = chain_decay_check(c);
+  if (!rc) rc = chain_offset_check(c);
+  return rc;
+}
 
-static int chain_fwd(const TempGruChain* c, const TempChainDecay* decay, const TempChainOffset* offset, const float* gi, float* h_out, float* saved,
-                     void* stream) {
-  int rc = chain_check(c);
-  if (rc) return rc;
-  if ((rc = chain_decay_check(c, decay))) return rc;
-  if ((rc = chain_offset_check(c, offset))) return rc;
+static int chain_fwd_gi(const TempGruChain* c, const TempChainFwd* io, hipStream_t st) {
   if (c->n_panels == 0) return TEMP_OK;
-  if (!gi || !h_out || !saved) return TEMP_E_BADARG;
-  const ChainArgs a = chain_args(c, decay, nullptr, offset);
-  if (decay) g_decay_launches.fetch_add(1, std::memory_order_relaxed);
-  if (offset) g_offset_launches.fetch_add(1, std::memory_order_relaxed);
-  hipStream_t st = (hipStream_t)stream;
+  if (!io->gi || !io->h_out || !io->saved) return TEMP_E_BADARG;
+  const ChainArgs a = chain_args(c);
+  chain_count(c);
   const int tpw = ceil_div(chain_geom(c->d).NT, 4);
 #define TEMP_CHAIN_FWD(V)                                                            \
   switch (tpw) {                                                                     \
-    case 1: return launch_chain_fwd<V, 1>(a, gi, h_out, saved, st);                  \
-    case 2: return launch_chain_fwd<V, 2>(a, gi, h_out, saved, st);                  \
-    case 3: return launch_chain_fwd<V, 3>(a, gi, h_out, saved, st);                  \
-    case 4: return launch_chain_fwd<V, 4>(a, gi, h_out, saved, st);                  \
-    case 5: return launch_chain_fwd<V, 5>(a, gi, h_out, saved, st);                  \
-    case 6: return launch_chain_fwd<V, 6>(a, gi, h_out, saved, st);                  \
+    case 1: return launch_chain_fwd<V, 1>(a, io->gi, io->h_out, io->saved, st);      \
+    case 2: return launch_chain_fwd<V, 2>(a, io->gi, io->h_out, io->saved, st);      \
+    case 3: return launch_chain_fwd<V, 3>(a, io->gi, io->h_out, io->saved, st);      \
+    case 4: return launch_chain_fwd<V, 4>(a, io->gi, io->h_out, io->saved, st);      \
+    case 5: return launch_chain_fwd<V, 5>(a, io->gi, io->h_out, io->saved, st);      \
+    case 6: return launch_chain_fwd<V, 6>(a, io->gi, io->h_out, io->saved, st);      \
     default: return TEMP_E_UNSUPPORTED;                                              \
   }
   if (c->variant == TEMP_GRU_TORCH) { TEMP_CHAIN_FWD(TEMP_GRU_TORCH) }
@@ -1090,20 +1090,88 @@ static int chain_fwd(const TempGruChain* c, const TempChainDecay* decay, const T
 #undef TEMP_CHAIN_FWD
 }
 
+// the x route: a kernel of its own (gru_chain_hx.hpp: k_gru_chain_fwd_x)
+static int chain_fwd_x(const TempGruChain* c, const TempChainFwd* io, hipStream_t st) {
+  if (c->pack_layout != TEMP_CHAIN_PACK_HX_X) return TEMP_E_BADARG;        // (the W_ih planes sit behind temp_gru_chain_pack_x_multi's packs only)
+  if (c->variant != TEMP_GRU_TORCH || !chain_fwd_x_fits(c->d, c->max_steps)) return TEMP_E_UNSUPPORTED;
+  if (c->n_panels == 0) return TEMP_OK;
+  if (!io->x_index || !io->b_ih || !io->h_out || !io->saved) return TEMP_E_BADARG;
+  for (int i = 0; i < c->n_rnn; ++i) if (!io->b_ih[i]) return TEMP_E_BADARG;
+  const ChainArgs a = chain_args(c);
+  chain_count(c);
+  int rc = TEMP_OK;
+  ChainX X = {};
+  X.x = io->x; X.x_index = io->x_index;
+  const ChainGeomHx gx = chain_geom_hx(c->d);
+  for (int i = 0; i < c->n_rnn; ++i) {
+    X.b_ih[i] = io->b_ih[i];
+    X.wi[i] = reinterpret_cast<const hx_u32x4*>(c->packed[i] + chain_x_ih_offset(c->d));
+  }
+  const size_t lds = chain_lds_fwd_x(c->d, c->max_steps);
+  // 8 + 8 waves as k_gru_chain_fwd_hx's default configuration: two matrix waves per SIMD, 128 registers each
+  // the development instantiation (cycle stamps, the switches of a.dbg) only where a debug buffer or TEMP_DEBUG asks for it
+  const bool dev = a.stamp || (a.dbg & (1 | 2 | 4 | 64 | 2048 | 4096));
+  const int tpw = (gx.NT + 7) / 8;
+  auto launch = [&](auto kernel, bool* granted) {
+    if ((rc = chain_lds_attr(kernel, lds, granted))) return rc;
+    TEMP_LAUNCH(K_GRU_CHAIN_FWD, kernel, dim3(a.n_panels), dim3(1024), lds, st, a, X, io->h_out, io->saved);
+    return (int)TEMP_OK;
+  };
+  static bool attr3 = false, attr2 = false, attr1 = false, attr3d = false, attr2d = false, attr1d = false;
+  if (tpw == 3) rc = dev ? launch(k_gru_chain_fwd_x<3, 8, 8, 1>, &attr3d) : launch(k_gru_chain_fwd_x<3, 8, 8>, &attr3);
+  else if (tpw == 2) rc = dev ? launch(k_gru_chain_fwd_x<2, 8, 8, 1>, &attr2d) : launch(k_gru_chain_fwd_x<2, 8, 8>, &attr2);
+  else rc = dev ? launch(k_gru_chain_fwd_x<1, 8, 8, 1>, &attr1d) : launch(k_gru_chain_fwd_x<1, 8, 8>, &attr1);
+  if (rc) return rc;
+  hx_count();
+  g_fwd_x_launches.fetch_add(1, std::memory_order_relaxed);
+  return launch_status();
+}
+
+// The three backward routes in one place: g4 == NULL -> (dgi, dgh); g4 -> the gate gradients written once (nn.GRU layout); g4 with
+// row_keys / col_keys (each nullable) -> the same on the f16 kernels, which also hand out the keys.
+static int chain_bwd(const TempGruChain* c, const TempChainBwd* io, hipStream_t st) {
+  const bool keys = io->row_keys || io->col_keys;
+  if (io->d_state && !c->offset) return TEMP_E_BADARG;
+  if (io->n_up < 0 || io->n_up > TEMP_CHAIN_MAX_UP || (io->n_up > 0 && !io->up)) return TEMP_E_BADARG;
+  if ((c->decay != nullptr) != (io->d_arg != nullptr)) return TEMP_E_BADARG;
+  if (io->g4 ? (io->dgi || io->dgh) : keys) return TEMP_E_BADARG;
+  if (io->g4 && c->variant != TEMP_GRU_TORCH) return TEMP_E_UNSUPPORTED;    // (the type-1 cell's dgi is [n, d])
+  if (keys && !layout_hx(c->pack_layout)) return TEMP_E_UNSUPPORTED;
+  if (c->n_panels == 0) return TEMP_OK;
+  if (!io->saved || (!io->g4 && (!io->dgi || !io->dgh))) return TEMP_E_BADARG;
+  const ChainArgs a = chain_args(c, io->d_arg, io->d_state);
+  chain_count(c);
+  ChainUps ups = {};
+  for (int i = 0; i < io->n_up; ++i) ups.p[i] = io->up[i];
+  const int tpw = ceil_div(chain_geom(c->d).NTb, 4);
+  if (io->g4) {
+    if (tpw == 1) return launch_chain_bwd<TEMP_GRU_TORCH, 1, 1>(a, ups, io->saved, io->g4, nullptr, st, io->row_keys, io->col_keys);
+    if (tpw == 2) return launch_chain_bwd<TEMP_GRU_TORCH, 2, 1>(a, ups, io->saved, io->g4, nullptr, st, io->row_keys, io->col_keys);
+    return TEMP_E_UNSUPPORTED;
+  }
+  if (c->variant == TEMP_GRU_TORCH) {
+    if (tpw == 1) return launch_chain_bwd<TEMP_GRU_TORCH, 1>(a, ups, io->saved, io->dgi, io->dgh, st);
+    if (tpw == 2) return launch_chain_bwd<TEMP_GRU_TORCH, 2>(a, ups, io->saved, io->dgi, io->dgh, st);
+  } else {
+    if (tpw == 1) return launch_chain_bwd<TEMP_GRU_TYPE1, 1>(a, ups, io->saved, io->dgi, io->dgh, st);
+    if (tpw == 2) return launch_chain_bwd<TEMP_GRU_TYPE1, 2>(a, ups, io->saved, io->dgi, io->dgh, st);
+  }
+  return TEMP_E_UNSUPPORTED;
+}
+
 extern "C" {
 
-int temp_gru_chain_fwd(const TempGruChain* c, const float* gi, float* h_out, float* saved, void* stream) {
-  return chain_fwd(c, nullptr, nullptr, gi, h_out, saved, stream);
+int temp_gru_chain_fwd(const TempGruChain* c, const TempChainFwd* io, void* stream) {
+  const int rc = chain_desc_check(c, io);
+  if (rc) return rc;
+  if (io->gi && io->x) return TEMP_E_BADARG;
+  return io->x ? chain_fwd_x(c, io, (hipStream_t)stream) : chain_fwd_gi(c, io, (hipStream_t)stream);
 }
-int temp_gru_chain_fwd_decay(const TempGruChain* c, const TempChainDecay* decay, const float* gi, float* h_out, float* saved, void* stream) {
-  if (!decay) return TEMP_E_BADARG;
-  return chain_fwd(c, decay, nullptr, gi, h_out, saved, stream);
+int temp_gru_chain_bwd(const TempGruChain* c, const TempChainBwd* io, void* stream) {
+  const int rc = chain_desc_check(c, io);
+  return rc ? rc : chain_bwd(c, io, (hipStream_t)stream);
 }
-int temp_gru_chain_fwd_offset(const TempGruChain* c, const TempChainDecay* decay, const TempChainOffset* offset, const float* gi, float* h_out,
-                              float* saved, void* stream) {
-  if (!offset) return TEMP_E_BADARG;
-  return chain_fwd(c, decay, offset, gi, h_out, saved, stream);
-}
+
 int temp_gru_chain_offset_supported(int d, int variant) {
   return (variant == TEMP_GRU_TORCH || variant == TEMP_GRU_TYPE1) && temp_gru_chain_supported(d) ? 1 : 0;
 }
@@ -1113,6 +1181,9 @@ int temp_gru_chain_decay_supported(int d, int variant) {
   return (variant == TEMP_GRU_TORCH || variant == TEMP_GRU_TYPE1) && temp_gru_chain_supported(d) ? 1 : 0;
 }
 long long temp_gru_chain_decay_launches(void) { return g_decay_launches.load(std::memory_order_relaxed); }
+long long temp_gru_chain_fwd_x_launches(void) { return g_fwd_x_launches.load(std::memory_order_relaxed); }
+int temp_gru_chain_pack_layout(int d) { return d > 0 ? chain_pack_layout(d) : 0; }
+int temp_gru_chain_keys_supported(int d) { return d > 0 && chain_hx(d) ? 1 : 0; }
 
 int temp_gru_chain_fwd_x_supported(int d, int variant, int max_steps) {
   return d > 0 && d % 8 == 0 && variant == TEMP_GRU_TORCH && chain_fwd_x_ok(d, max_steps) ? 1 : 0;
@@ -1143,135 +1214,6 @@ int temp_gru_chain_pack_x_multi(int count, int d, const float* const* w_hh, cons
   }
   hx_pack_launch(jobs, K_GRU_CHAIN_PACK, (hipStream_t)stream);
   return launch_status();
-}
-
-}  // extern "C"
-
-static int chain_fwd_x(const TempGruChain* c, const TempChainDecay* decay, const float* x, const int32_t* x_index, const float* const* b_ih, float* h_out,
-                       float* saved, void* stream) {
-  int rc = chain_check(c);
-  if (rc) return rc;
-  if ((rc = chain_decay_check(c, decay))) return rc;
-  if (c->pack_layout != TEMP_CHAIN_PACK_HX_X) return TEMP_E_BADARG;        // (the W_ih planes sit behind temp_gru_chain_pack_x_multi's packs only)
-  if (c->variant != TEMP_GRU_TORCH || !chain_fwd_x_fits(c->d, c->max_steps)) return TEMP_E_UNSUPPORTED;
-  if (c->n_panels == 0) return TEMP_OK;
-  if (!x || !x_index || !b_ih || !h_out || !saved) return TEMP_E_BADARG;
-  for (int i = 0; i < c->n_rnn; ++i) if (!b_ih[i]) return TEMP_E_BADARG;
-  const ChainArgs a = chain_args(c, decay);
-  if (decay) g_decay_launches.fetch_add(1, std::memory_order_relaxed);
-  ChainX X = {};
-  X.x = x; X.x_index = x_index;
-  const ChainGeomHx gx = chain_geom_hx(c->d);
-  for (int i = 0; i < c->n_rnn; ++i) {
-    X.b_ih[i] = b_ih[i];
-    X.wi[i] = reinterpret_cast<const hx_u32x4*>(c->packed[i] + chain_x_ih_offset(c->d));
-  }
-  const size_t lds = chain_lds_fwd_x(c->d, c->max_steps);
-  // 8 + 8 waves as k_gru_chain_fwd_hx's default configuration: two matrix waves per SIMD, 128 registers each
-  hipStream_t st = (hipStream_t)stream;
-  // the development instantiation (cycle stamps, the switches of a.dbg) only where a debug buffer or TEMP_DEBUG asks for it
-  const bool dev = a.stamp || (a.dbg & (1 | 2 | 4 | 64 | 2048 | 4096));
-  const int tpw = (gx.NT + 7) / 8;
-  auto launch = [&](auto kernel, bool* granted) {
-    if ((rc = chain_lds_attr(kernel, lds, granted))) return rc;
-    TEMP_LAUNCH(K_GRU_CHAIN_FWD, kernel, dim3(a.n_panels), dim3(1024), lds, st, a, X, h_out, saved);
-    return (int)TEMP_OK;
-  };
-  static bool attr3 = false, attr2 = false, attr1 = false, attr3d = false, attr2d = false, attr1d = false;
-  if (tpw == 3) rc = dev ? launch(k_gru_chain_fwd_x<3, 8, 8, 1>, &attr3d) : launch(k_gru_chain_fwd_x<3, 8, 8>, &attr3);
-  else if (tpw == 2) rc = dev ? launch(k_gru_chain_fwd_x<2, 8, 8, 1>, &attr2d) : launch(k_gru_chain_fwd_x<2, 8, 8>, &attr2);
-  else rc = dev ? launch(k_gru_chain_fwd_x<1, 8, 8, 1>, &attr1d) : launch(k_gru_chain_fwd_x<1, 8, 8>, &attr1);
-  if (rc) return rc;
-  hx_count();
-  g_fwd_x_launches.fetch_add(1, std::memory_order_relaxed);
-  return launch_status();
-}
-
-extern "C" {
-
-int temp_gru_chain_fwd_x(const TempGruChain* c, const float* x, const int32_t* x_index, const float* const* b_ih, float* h_out, float* saved, void* stream) {
-  return chain_fwd_x(c, nullptr, x, x_index, b_ih, h_out, saved, stream);
-}
-int temp_gru_chain_fwd_x_decay(const TempGruChain* c, const TempChainDecay* decay, const float* x, const int32_t* x_index, const float* const* b_ih,
-                               float* h_out, float* saved, void* stream) {
-  if (!decay) return TEMP_E_BADARG;
-  return chain_fwd_x(c, decay, x, x_index, b_ih, h_out, saved, stream);
-}
-
-long long temp_gru_chain_fwd_x_launches(void) { return g_fwd_x_launches.load(std::memory_order_relaxed); }
-
-}  // extern "C"
-
-// The three backward routes in one place: CH_BWD_GATES -> (dgi, dgh); CH_BWD_G4 -> the gate gradients written once (nn.GRU layout);
-// CH_BWD_G4_KEYS -> the same on the f16 kernels, which also hand out row_keys / col_keys (each nullable).  decay / d_arg: the
-// learnable decay and its per-row gradient (both or neither).
-enum { CH_BWD_GATES, CH_BWD_G4, CH_BWD_G4_KEYS };
-static int chain_bwd(int route, const TempGruChain* c, const TempChainDecay* decay, const float* saved, int n_up, const float* const* up, float* dgi,
-                     float* dgh, float* g4, uint32_t* row_keys, uint32_t* col_keys, float* d_arg, void* stream,
-                     const TempChainOffset* offset = nullptr, float* d_state = nullptr) {
-  int rc = chain_check(c);
-  if (rc) return rc;
-  if ((rc = chain_decay_check(c, decay))) return rc;
-  if ((rc = chain_offset_check(c, offset))) return rc;
-  if (d_state && !offset) return TEMP_E_BADARG;
-  if (n_up < 0 || n_up > TEMP_CHAIN_MAX_UP || (n_up > 0 && !up)) return TEMP_E_BADARG;
-  if ((decay != nullptr) != (d_arg != nullptr)) return TEMP_E_BADARG;
-  if (route != CH_BWD_GATES && c->variant != TEMP_GRU_TORCH) return TEMP_E_UNSUPPORTED;    // (the type-1 cell's dgi is [n, d])
-  if (route == CH_BWD_G4_KEYS && !layout_hx(c->pack_layout)) return TEMP_E_UNSUPPORTED;
-  if (c->n_panels == 0) return TEMP_OK;
-  if (!saved || (route == CH_BWD_GATES ? (!dgi || !dgh) : !g4)) return TEMP_E_BADARG;
-  const ChainArgs a = chain_args(c, decay, d_arg, offset, d_state);
-  if (decay) g_decay_launches.fetch_add(1, std::memory_order_relaxed);
-  if (offset) g_offset_launches.fetch_add(1, std::memory_order_relaxed);
-  ChainUps ups = {};
-  for (int i = 0; i < n_up; ++i) ups.p[i] = up[i];
-  hipStream_t st = (hipStream_t)stream;
-  const int tpw = ceil_div(chain_geom(c->d).NTb, 4);
-  if (route != CH_BWD_GATES) {
-    if (tpw == 1) return launch_chain_bwd<TEMP_GRU_TORCH, 1, 1>(a, ups, saved, g4, nullptr, st, row_keys, col_keys);
-    if (tpw == 2) return launch_chain_bwd<TEMP_GRU_TORCH, 2, 1>(a, ups, saved, g4, nullptr, st, row_keys, col_keys);
-    return TEMP_E_UNSUPPORTED;
-  }
-  if (c->variant == TEMP_GRU_TORCH) {
-    if (tpw == 1) return launch_chain_bwd<TEMP_GRU_TORCH, 1>(a, ups, saved, dgi, dgh, st);
-    if (tpw == 2) return launch_chain_bwd<TEMP_GRU_TORCH, 2>(a, ups, saved, dgi, dgh, st);
-  } else {
-    if (tpw == 1) return launch_chain_bwd<TEMP_GRU_TYPE1, 1>(a, ups, saved, dgi, dgh, st);
-    if (tpw == 2) return launch_chain_bwd<TEMP_GRU_TYPE1, 2>(a, ups, saved, dgi, dgh, st);
-  }
-  return TEMP_E_UNSUPPORTED;
-}
-
-extern "C" {
-
-int temp_gru_chain_bwd_g4(const TempGruChain* c, const float* saved, int n_up, const float* const* up, float* g4, void* stream) {
-  return chain_bwd(CH_BWD_G4, c, nullptr, saved, n_up, up, nullptr, nullptr, g4, nullptr, nullptr, nullptr, stream);
-}
-
-int temp_gru_chain_pack_layout(int d) { return d > 0 ? chain_pack_layout(d) : 0; }
-
-int temp_gru_chain_keys_supported(int d) { return d > 0 && chain_hx(d) ? 1 : 0; }
-
-int temp_gru_chain_bwd_g4_keys(const TempGruChain* c, const float* saved, int n_up, const float* const* up, float* g4, uint32_t* row_keys,
-                               uint32_t* col_keys, void* stream) {
-  return chain_bwd(CH_BWD_G4_KEYS, c, nullptr, saved, n_up, up, nullptr, nullptr, g4, row_keys, col_keys, nullptr, stream);
-}
-
-int temp_gru_chain_bwd(const TempGruChain* c, const float* saved, int n_up, const float* const* up, float* dgi, float* dgh, void* stream) {
-  return chain_bwd(CH_BWD_GATES, c, nullptr, saved, n_up, up, dgi, dgh, nullptr, nullptr, nullptr, nullptr, stream);
-}
-
-int temp_gru_chain_bwd_decay(const TempGruChain* c, const TempChainDecay* decay, const float* saved, int n_up, const float* const* up, float* dgi,
-                             float* dgh, float* g4, uint32_t* row_keys, uint32_t* col_keys, float* d_arg, void* stream) {
-  if (!decay || !d_arg || (g4 && (dgi || dgh))) return TEMP_E_BADARG;
-  const int route = !g4 ? CH_BWD_GATES : (row_keys || col_keys) ? CH_BWD_G4_KEYS : CH_BWD_G4;
-  return chain_bwd(route, c, decay, saved, n_up, up, dgi, dgh, g4, row_keys, col_keys, d_arg, stream);
-}
-
-int temp_gru_chain_bwd_offset(const TempGruChain* c, const TempChainDecay* decay, const TempChainOffset* offset, const float* saved, int n_up,
-                              const float* const* up, float* dgi, float* dgh, float* g4, float* d_arg, float* d_state, void* stream) {
-  if (!offset || (g4 && (dgi || dgh))) return TEMP_E_BADARG;
-  return chain_bwd(g4 ? CH_BWD_G4 : CH_BWD_GATES, c, decay, saved, n_up, up, dgi, dgh, g4, nullptr, nullptr, d_arg, stream, offset, d_state);
 }
 
 size_t temp_gru_chain_decay_reduce_workspace(const TempGruChain* c) {

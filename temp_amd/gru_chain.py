@@ -24,7 +24,7 @@ CHAIN_KERNELS = True        # A/B switch: False keeps the per-position launches 
 WEIGHT_GRADS_MULTI = True   # A/B switch: False computes each GRU's weight gradients with its own launches (temp_gru_weight_grads)
 KEYED_GRADS = True          # A/B switch: False keeps the consumers of g4 on the six-product bf16 split (no keys from the chain backward)
 GATE_GRADS_ONCE = True      # A/B switch: False keeps dgi + dgh as two matrices (temp_gru_chain_bwd + temp_gru_weight_grads_multi)
-FUSED_INPUT_GATES = True    # A/B switch: False keeps the gate GEMM + gi route where temp_gru_chain_fwd_x applies (so does TEMP_DEBUG bit 22)
+FUSED_INPUT_GATES = True    # A/B switch: False keeps the gate GEMM + gi route where temp_gru_chain_fwd's x route applies (so does TEMP_DEBUG bit 22)
 
 
 class GruInstance:
@@ -333,7 +333,7 @@ class _GruChainFn(torch.autograd.Function):
             assert off_table.shape[1] == d and off_index.dtype == torch.int32 and off_index.numel() == N
             ofk = dict(offset=(off_table.detach().contiguous(), off_index))
         ctx.offset, ctx.off_inverse, ctx.off_rows = ofk, off_inverse, (off_table.shape[0] if off_table is not None else 0)
-        # nn.GRU cells on the f16 route: the chain forward computes the input gates itself from the x rows (temp_gru_chain_fwd_x) --
+        # nn.GRU cells on the f16 route: the chain forward computes the input gates itself from the x rows (temp_gru_chain_fwd's x route) --
         # no gi, no gate GEMM.  (Independent of x_src: a labelled and an unlabelled program take the same kernel.)
         # (an offset chain's states leave the range of the f16 state split: it keeps the gi route and the bf16 / fp32 chain kernels)
         fused = bool(tabs is not None and not ofk and FUSED_INPUT_GATES and variant == _lib.GRU_TORCH and hasattr(be, "gru_chain_fwd_x")

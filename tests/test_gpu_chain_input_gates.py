@@ -1,4 +1,4 @@
-"""The chain forward with the input gates computed inside (temp_gru_chain_fwd_x): x rows in, no gi, no gate GEMM.
+"""The chain forward with the input gates computed inside (temp_gru_chain_fwd's x route): x rows in, no gi, no gate GEMM.
 
 Against the gi route it replaces (the gate GEMM + temp_gru_chain_fwd, forced with gru_chain.FUSED_INPUT_GATES = False or TEMP_DEBUG
 bit 22) and against the CPU panel reference of the test backend."""

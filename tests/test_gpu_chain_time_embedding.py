@@ -1,5 +1,5 @@
 """--use-time-embedding windows on the persistent chain kernels: row rho leaves s = GRU(x, dec . s_prev) + table[index[rho]], the sum
-is the state the next position decays (temp_gru_chain_fwd_offset), the backward also writes the gradient reaching every row's state
+is the state the next position decays (temp_gru_chain_fwd with TempGruChain.offset), the backward also writes the gradient reaching every row's state
 (d_state) and the table's gradient is the deterministic adjoint of the row gather.
 
 Kernels against a float64 autograd loop over the program's instances (written here), a range-stress table (states up to 14, past the

@@ -220,7 +220,7 @@ def test_gru_grads_g4_keys_vs_fp64_gpu(rows, d, data, hip_backend):
 
 @pytest.mark.parametrize("d", [200, 104, 32])
 def test_chain_bwd_keys_gpu(d, hip_backend):
-    """temp_gru_chain_bwd_g4_keys: the same g4 bit for bit, row keys = the bits of max |[dr dz dn_i]| of every row, column keys =
+    """temp_gru_chain_bwd with keys: the same g4 bit for bit, row keys = the bits of max |[dr dz dn_i]| of every row, column keys =
     per GRU the bits of every column's largest magnitude over that GRU's rows; twice the same."""
     from tests.chain_cases import random_program
     from tests.test_gpu_gate_grads import _chain_forward

@@ -1,4 +1,4 @@
-"""Round 5: the window-chain backward writes its gate gradients ONCE, g4 = [dr | dz | dn_i | dn_h] (temp_gru_chain_bwd_g4), and
+"""Round 5: the window-chain backward writes its gate gradients ONCE, g4 = [dr | dz | dn_i | dn_h] (temp_gru_chain_bwd's g4 route), and
 temp_gru_grads_g4 forms both weight gradients, the bias gradients and d_x from that one matrix (k_gru_wgrad: LDS transpose reads,
 column map) -- the backward of the GRU step of GRRGCNLayer.forward (models/RRGCN.py:84), nn.GRU gate layout."""
 import ctypes

@@ -75,7 +75,7 @@ def weight_grads_ab(steps=200):
 
 
 def gate_grads_ab(steps=200):
-    """Gate gradients written once (temp_gru_chain_bwd_g4 + temp_gru_grads_g4: k_gru_wgrad) against dgi + dgh (temp_gru_chain_bwd +
+    """Gate gradients written once (temp_gru_chain_bwd's g4 route + temp_gru_grads_g4: k_gru_wgrad) against dgi + dgh (temp_gru_chain_bwd +
     temp_gru_weight_grads_multi): the whole step as a HIP graph, alternating, on this box; then the kernels of an eager step."""
     from temp_amd import _lib, gru_chain as GC, synthetic
     lib = _lib.load()
