@@ -12,28 +12,10 @@
 // No floating-point atomics and no workspace: every output element has one writer and every sum a fixed order.
 #include "common.hpp"
 #include "mix.hpp"
+#include "reduce.hpp"
 
 namespace temp {
 namespace {
-
-__device__ __forceinline__ float wave_sum(float v) {
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off);
-  return v;
-}
-__device__ __forceinline__ float wave_max(float v) {
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) v = fmaxf(v, __shfl_xor(v, off));
-  return v;
-}
-// 256-thread reduction (four waves); `red` may be reused right after: the leading barrier orders it against the last read
-__device__ __forceinline__ float block_sum_256(float v, float* red) {
-  v = wave_sum(v);
-  __syncthreads();
-  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
-  __syncthreads();
-  return (red[0] + red[1]) + (red[2] + red[3]);
-}
 
 // (the mixing expression mix1 / mix4 of the forward and backward passes: mix.hpp)
 __device__ __forceinline__ float4 sub4(float4 a, float4 b) { return make_float4(a.x - b.x, a.y - b.y, a.z - b.z, a.w - b.w); }
@@ -173,12 +155,8 @@ __global__ void __launch_bounds__(256) k_gather_ce_mix_bwd_w(int P, int C, int N
   extern __shared__ int cnt_all[];
   const int p = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
   if (p >= P) return;
-  int* cnt = cnt_all + (threadIdx.x >> 6) * N;
   const int32_t* crow = cand + (size_t)p * C;
-  for (int i = lane; i < N; i += 64) cnt[i] = 0;
-  asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-  for (int k = lane; k < C; k += 64) atomicAdd(&cnt[crow[k]], 1);
-  asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+  const int* cnt = gather_ce_wave_counts(cnt_all, N, C, crow);
   const float* ra = s_a + (size_t)p * N;
   const float* rb = s_b + (size_t)p * N;
   const float wp = w[p], lse = lse_rows[p];

@@ -19,7 +19,10 @@ U = 2.0 ** -24
 
 # (d, C, P, table rows per window, windows): windows == 1 runs with base = NULL, 2 with two stacked windows.  Every value of each
 # axis appears (d: below one lane group / the workload's 200 / the 256 line / past it; C: 1, 2, 101, 1025; P: 1, 5, 67; rows 7, 515)
-# and (d = 260, C = 1025) together.
+# and (d = 260, C = 1025) together.  The forward keeps the query in 1 to 4 float4 per lane for d <= 64, 128, 192, 256 and re-reads it
+# beyond: d = 8, 100, 132, 200 / 256 and 260 take the five routes in that order.  The two cases at d = 100 and d = 132 also end in
+# a partial float4 pass (d mod 64 != 0), and their C = 33 and C = 17 leave a 16-lane group with a paired second candidate
+# (k0 + 16 < C) and with a dangling one.
 CANDIDATE_CASES = [
     (8, 1, 1, 7, 1),
     (8, 2, 5, 7, 2),
@@ -31,6 +34,8 @@ CANDIDATE_CASES = [
     (256, 2, 67, 515, 1),
     (260, 1025, 67, 515, 2),
     (260, 101, 1, 7, 1),
+    (100, 33, 5, 7, 2),
+    (132, 17, 5, 7, 1),
 ]
 
 # (P, N, d, ld) of the dense scores; the first two also carry the rank tests (a larger N at d = 200 makes the band uninformative)
