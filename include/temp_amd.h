@@ -977,6 +977,24 @@ int temp_sa_attn_bwd(const TempAttn* p, const float* out, const float* score, co
  * maps of a prepared batch) and ds_ws [n * heads * T] scratch.  Then d_kh / d_vh rows [0, n_table) are each written once
  * by a second pass over the table (no atomics, no zero-fill needed).  With inv_ptr = NULL the atomic form above is used. */
 
+/* Split current row.  Where the current state of query row i is a SUM of two rows -- an entity row that no window changes and a
+ * per-window time row (the all-entity pass of the post-aggregation attention models) -- the (q | k | v) projection, being linear,
+ * is taken of the two small tables once, and the kernel forms
+ *   (q | k | v)[i] = pa[ia[i]] + pb[ib[i]]          (3D floats per row; one fp32 addition per element)
+ * itself instead of reading a materialised [n, 3D] buffer.  p->q / kc / vc are not read (may be NULL); everything else of
+ * TempAttn, the shape limits, out / score / lse and the two backward forms are those of temp_sa_attn_fwd / _bwd, with which the
+ * results are bit-equal when those are fed the fp32 sums.  ia / ib [n]: rows of pa / pb (repeats allowed, every entry in range);
+ * lda, ldb >= 3D.  bwd writes d_qkv [n, ld_dqkv >= 3D] = the gradient of the SUMMED row (d_q | d_k | d_v), fully written; the
+ * caller reduces it over ia and over ib (temp_segment_sum_rows) for d_pa and d_pb. */
+typedef struct TempAttnSplit {
+  const float* pa; const int32_t* ia; int32_t lda;
+  const float* pb; const int32_t* ib; int32_t ldb;
+} TempAttnSplit;
+int temp_sa_attn_split_fwd(const TempAttn* p, const TempAttnSplit* s, float* out, float* score, float* lse, void* stream);
+int temp_sa_attn_split_bwd(const TempAttn* p, const TempAttnSplit* s, const float* out, const float* score, const float* lse,
+                           const float* d_out, float* d_qkv, int ld_dqkv, float* d_kh, float* d_vh, int ld_dh, float* d_decay,
+                           int n_table, const int32_t* inv_ptr, const int32_t* inv_ref, float* ds_ws, void* stream);
+
 /* Device-memory bandwidth probe used by bench.py to calibrate the achievable HBM peak
  * (float4 copy of `bytes` bytes, dst and src must not overlap). */
 int temp_copy_probe(const void* src, void* dst, size_t bytes, void* stream);

@@ -107,6 +107,10 @@ class TempAttn(ctypes.Structure):
                 ("kc", c_vp), ("vc", c_vp), ("ldc", ctypes.c_int32), ("idx", c_vp), ("decay", c_vp)]
 
 
+class TempAttnSplit(ctypes.Structure):
+    _fields_ = [("pa", c_vp), ("ia", c_vp), ("lda", ctypes.c_int32), ("pb", c_vp), ("ib", c_vp), ("ldb", ctypes.c_int32)]
+
+
 class TempLinearProblem(ctypes.Structure):
     _fields_ = [("M", ctypes.c_int32), ("A", c_vp), ("B", c_vp), ("C", c_vp)]
 
@@ -229,6 +233,9 @@ SYMBOLS = {
     "temp_filtered_rank": (_I, [_I, _I, _I, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp]),
     "temp_sa_attn_fwd": (_I, [ctypes.POINTER(TempAttn), c_vp, c_vp, c_vp, c_vp]),
     "temp_sa_attn_bwd": (_I, [ctypes.POINTER(TempAttn), c_vp, c_vp, c_vp, c_vp, c_vp, _I, c_vp, c_vp, _I, c_vp, c_vp, _I, c_vp, _I, c_vp, c_vp, c_vp, c_vp]),
+    "temp_sa_attn_split_fwd": (_I, [ctypes.POINTER(TempAttn), ctypes.POINTER(TempAttnSplit), c_vp, c_vp, c_vp, c_vp]),
+    "temp_sa_attn_split_bwd": (_I, [ctypes.POINTER(TempAttn), ctypes.POINTER(TempAttnSplit), c_vp, c_vp, c_vp, c_vp, c_vp, _I, c_vp, c_vp, _I, c_vp,
+                                    _I, c_vp, c_vp, c_vp, c_vp]),
     "temp_copy_probe": (_I, [c_vp, c_vp, _SZ, c_vp]),
     "temp_trace_begin": (_I, [_I]),
     "temp_trace_end": (_I, [c_i32p, c_f32p, _I, c_i32p]),

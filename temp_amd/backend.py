@@ -1001,6 +1001,64 @@ class HipBackend:
         _lib.check(rc, "temp_sa_attn_bwd")
         return d_qkv, d_hist, d_decay
 
+    def _attn_split_desc(self, pa, ia, pb, ib, kv_hist, idx, decay):
+        """(TempAttn of the history side, TempAttnSplit, n, D, T): row i's (q | k | v) = pa[ia[i]] + pb[ib[i]]."""
+        n, D3 = ia.shape[0], pa.shape[1]
+        D = D3 // 3
+        T = idx.shape[1] + 1
+        if pb.shape[1] != D3 or D3 != 3 * D or ib.shape[0] != n or idx.shape[0] != n:
+            raise _lib.TempAmdError("split attention: pa / pb must be [*, 3D] and ia / ib / idx must list the same n rows")
+        if n > 0 and (pa.shape[0] == 0 or pb.shape[0] == 0):
+            raise _lib.TempAmdError("split attention: empty pa / pb table")
+        if T > 1 and kv_hist.shape[1] != 2 * D:
+            raise _lib.TempAmdError("kv_hist must be [R, 2D]")
+        a = _lib.TempAttn()
+        a.n, a.D, a.heads, a.T = n, D, 8, T
+        if T > 1:
+            hb = kv_hist.data_ptr()
+            a.kh, a.vh, a.ldh = hb, hb + 4 * D, 2 * D
+        a.idx = idx.data_ptr() if T > 1 else None
+        a.decay = decay.data_ptr() if decay is not None else None
+        sp = _lib.TempAttnSplit()
+        sp.pa, sp.ia, sp.lda = pa.data_ptr(), ia.data_ptr(), D3
+        sp.pb, sp.ib, sp.ldb = pb.data_ptr(), ib.data_ptr(), D3
+        return a, sp, n, D, T
+
+    def sa_attn_split_fwd(self, pa, ia, pb, ib, kv_hist, idx, decay):
+        """sa_attn_fwd with the current rows given in two parts: pa [Na,3D], pb [Nb,3D] = (q | k | v) projections of two small
+        tables, ia / ib [n] int32 their rows; row i attends as pa[ia[i]] + pb[ib[i]] (formed in the kernel) -> (out, score, lse)."""
+        pa, pb, kv_hist, decay = _f32(pa, "pa"), _f32(pb, "pb"), _f32(kv_hist, "kv_hist"), _f32(decay, "decay")
+        ia, ib, idx = _i32(ia, "ia"), _i32(ib, "ib"), _i32(idx, "idx")
+        a, sp, n, D, T = self._attn_split_desc(pa, ia, pb, ib, kv_hist, idx, decay)
+        out = torch.empty(n, D, dtype=torch.float32, device=pa.device)
+        score = torch.empty(n, 8, T, dtype=torch.float32, device=pa.device)
+        lse = torch.empty(n, 8, dtype=torch.float32, device=pa.device)
+        rc = self.lib.temp_sa_attn_split_fwd(ctypes.byref(a), ctypes.byref(sp), _ptr(out), _ptr(score), _ptr(lse), _stream())
+        _lib.check(rc, "temp_sa_attn_split_fwd")
+        return out, score, lse
+
+    def sa_attn_split_bwd(self, pa, ia, pb, ib, kv_hist, idx, decay, out, score, lse, d_out, inverse=None):
+        """-> (d_qkv [n,3D] = gradient of the SUMMED current rows, d_kv_hist [R,2D], d_decay [T] or None); `inverse` as in
+        sa_attn_bwd.  The caller sums d_qkv over ia / ib for d_pa / d_pb (segment_sum_rows)."""
+        pa, pb, kv_hist, decay = _f32(pa, "pa"), _f32(pb, "pb"), _f32(kv_hist, "kv_hist"), _f32(decay, "decay")
+        ia, ib, idx, d_out = _i32(ia, "ia"), _i32(ib, "ib"), _i32(idx, "idx"), _f32(d_out, "d_out")
+        a, sp, n, D, T = self._attn_split_desc(pa, ia, pb, ib, kv_hist, idx, decay)
+        d_qkv = torch.empty(n, 3 * D, dtype=torch.float32, device=pa.device)
+        use_inv = inverse is not None and T > 1
+        d_hist = torch.empty_like(kv_hist) if use_inv else torch.zeros_like(kv_hist)
+        d_decay = torch.zeros(T, dtype=torch.float32, device=pa.device) if decay is not None else None
+        dh = d_hist.data_ptr()
+        vp = ctypes.c_void_p
+        inv_ptr = inv_ref = ds_ws = None
+        if use_inv:
+            inv_ptr, inv_ref = _i32(inverse[0], "inv_ptr"), _i32(inverse[1], "inv_ref")
+            ds_ws = torch.empty(n * 8 * T, dtype=torch.float32, device=pa.device)
+        rc = self.lib.temp_sa_attn_split_bwd(ctypes.byref(a), ctypes.byref(sp), _ptr(out), _ptr(score), _ptr(lse), _ptr(d_out),
+                                             _ptr(d_qkv), 3 * D, vp(dh), vp(dh + 4 * D), 2 * D, _ptr(d_decay), kv_hist.shape[0],
+                                             _ptr(inv_ptr), _ptr(inv_ref), _ptr(ds_ws), _stream())
+        _lib.check(rc, "temp_sa_attn_split_bwd")
+        return d_qkv, d_hist, d_decay
+
     # ---- row gather / scatter ---------------------------------------------------------------------
     def gather_rows(self, table, idx):
         table, idx = _f32(table, "table"), _i32(idx, "idx")

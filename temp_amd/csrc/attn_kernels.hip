@@ -12,6 +12,11 @@
 // columns head*d_k + j + 8*i (i < MAXC) of q / K / V, so a head's dot product is a 3-step xor
 // reduction inside its 8-lane group and no LDS is needed.  HBM-bound gather: algorithmic bytes per
 // row = (1 + 2 * active positions) * D * 4 read + D * 4 written.
+//
+// Split current row (temp_sa_attn_split_fwd / _bwd): the projection is linear, so a current row that is the sum of two rows
+// (an entity row that no window changes + a per-window time row) is projected as two small tables pa / pb, and the wave forms
+// (q | k | v)[i] = pa[ia[i]] + pb[ib[i]] itself -- one fp32 addition per element, then the same arithmetic.  Every kernel is
+// written once; SPLIT selects where the current row comes from (CurRow).
 #include "common.hpp"
 
 namespace temp {
@@ -24,6 +29,30 @@ struct AttnArgs {
   const int32_t* idx;
   const float* decay;
   float sqrt_dk;     // sqrt(d_k): scores are DIVIDED by it like the reference
+  const float* pa; const int32_t* ia; int lda;     // SPLIT: row i's (q | k | v) = pa[ia[i]] + pb[ib[i]], 3D floats each
+  const float* pb; const int32_t* ib; int ldb;
+};
+
+// (q | k | v) of query row `row`: three strided rows, or -- SPLIT -- the sum of one row of each small table.  ia / ib are
+// wave-uniform (one wave per row) and read the way idx is.
+template <bool SPLIT>
+struct CurRow {
+  const float *x, *y, *z;      // plain: q, kc, vc rows;  SPLIT: pa row, pb row, unused
+  int D;
+  __device__ __forceinline__ CurRow(const AttnArgs& a, int row) : D(a.D) {
+    if (SPLIT) {
+      x = a.pa + (size_t)__builtin_amdgcn_readfirstlane(a.ia[row]) * a.lda;
+      y = a.pb + (size_t)__builtin_amdgcn_readfirstlane(a.ib[row]) * a.ldb;
+      z = nullptr;
+    } else {
+      x = a.q + (size_t)row * a.ldq;
+      y = a.kc + (size_t)row * a.ldc;
+      z = a.vc + (size_t)row * a.ldc;
+    }
+  }
+  __device__ __forceinline__ float q(int c) const { return SPLIT ? x[c] + y[c] : x[c]; }
+  __device__ __forceinline__ float k(int c) const { return SPLIT ? x[D + c] + y[D + c] : y[c]; }
+  __device__ __forceinline__ float v(int c) const { return SPLIT ? x[2 * D + c] + y[2 * D + c] : z[c]; }
 };
 
 __device__ __forceinline__ float reduce8(float v) {
@@ -33,12 +62,13 @@ __device__ __forceinline__ float reduce8(float v) {
   return v;
 }
 
-template <int MAXC>
+template <int MAXC, bool SPLIT>
 __global__ __launch_bounds__(256) void k_sa_attn_fwd(AttnArgs a, float* __restrict__ out, float* __restrict__ score,
                                                       float* __restrict__ lse) {
   const int lane = threadIdx.x & 63, head = lane >> 3, j = lane & 7;
   const int row = blockIdx.x * 4 + (threadIdx.x >> 6);
   if (row >= a.n) return;
+  const CurRow<SPLIT> cur(a, row);
   int col[MAXC];
   bool ok[MAXC];
   float qv[MAXC], acc[MAXC];
@@ -47,7 +77,7 @@ __global__ __launch_bounds__(256) void k_sa_attn_fwd(AttnArgs a, float* __restri
     const int d = j + 8 * i;
     ok[i] = d < a.dk;
     col[i] = head * a.dk + (ok[i] ? d : 0);
-    qv[i] = ok[i] ? a.q[(size_t)row * a.ldq + col[i]] : 0.f;
+    qv[i] = ok[i] ? cur.q(col[i]) : 0.f;
     acc[i] = 0.f;
   }
   float m = -INFINITY, ssum = 0.f;
@@ -64,14 +94,19 @@ __global__ __launch_bounds__(256) void k_sa_attn_fwd(AttnArgs a, float* __restri
       kp = a.kh + (size_t)r * a.ldh;
       vp = a.vh + (size_t)r * a.ldh;
     } else {
-      kp = a.kc + (size_t)row * a.ldc;
-      vp = a.vc + (size_t)row * a.ldc;
+      kp = SPLIT ? nullptr : cur.y;
+      vp = SPLIT ? nullptr : cur.z;
     }
     float kv[MAXC], vv[MAXC];
 #pragma unroll
     for (int i = 0; i < MAXC; ++i) {
-      kv[i] = ok[i] ? kp[col[i]] : 0.f;
-      vv[i] = ok[i] ? vp[col[i]] : 0.f;
+      if (SPLIT && t == Th) {
+        kv[i] = ok[i] ? cur.k(col[i]) : 0.f;
+        vv[i] = ok[i] ? cur.v(col[i]) : 0.f;
+      } else {
+        kv[i] = ok[i] ? kp[col[i]] : 0.f;
+        vv[i] = ok[i] ? vp[col[i]] : 0.f;
+      }
     }
     float part = 0.f;
 #pragma unroll
@@ -101,7 +136,7 @@ struct AttnGrads {
   float* ds;            // [n, 8, T] score gradients for the table pass; when set, no atomics are issued here
 };
 
-template <int MAXC>
+template <int MAXC, bool SPLIT>
 __global__ __launch_bounds__(256) void k_sa_attn_bwd(AttnArgs a, const float* __restrict__ out, const float* __restrict__ score,
                                                       const float* __restrict__ lse, const float* __restrict__ d_out, AttnGrads g) {
   __shared__ float s_decay[64];
@@ -113,6 +148,7 @@ __global__ __launch_bounds__(256) void k_sa_attn_bwd(AttnArgs a, const float* __
   const int lane = threadIdx.x & 63, head = lane >> 3, j = lane & 7;
   const int row = blockIdx.x * 4 + (threadIdx.x >> 6);
   if (row < a.n) {
+    const CurRow<SPLIT> cur(a, row);
     int col[MAXC];
     bool ok[MAXC];
     float qv[MAXC], dov[MAXC], dq[MAXC];
@@ -122,7 +158,7 @@ __global__ __launch_bounds__(256) void k_sa_attn_bwd(AttnArgs a, const float* __
       const int d = j + 8 * i;
       ok[i] = d < a.dk;
       col[i] = head * a.dk + (ok[i] ? d : 0);
-      qv[i] = ok[i] ? a.q[(size_t)row * a.ldq + col[i]] : 0.f;
+      qv[i] = ok[i] ? cur.q(col[i]) : 0.f;
       const size_t oc = (size_t)row * a.D + (size_t)(ok[i] ? d : 0) * 8 + head;
       dov[i] = ok[i] ? d_out[oc] : 0.f;
       dl = fmaf(dov[i], ok[i] ? out[oc] : 0.f, dl);
@@ -144,16 +180,21 @@ __global__ __launch_bounds__(256) void k_sa_attn_bwd(AttnArgs a, const float* __
         dkp = g.d_kh + (size_t)r * g.ld_dh;
         dvp = g.d_vh + (size_t)r * g.ld_dh;
       } else {
-        kp = a.kc + (size_t)row * a.ldc;
-        vp = a.vc + (size_t)row * a.ldc;
+        kp = SPLIT ? nullptr : cur.y;
+        vp = SPLIT ? nullptr : cur.z;
         dkp = g.d_kc + (size_t)row * g.ld_dc;
         dvp = g.d_vc + (size_t)row * g.ld_dc;
       }
       float kv[MAXC], vv[MAXC];
 #pragma unroll
       for (int i = 0; i < MAXC; ++i) {
-        kv[i] = ok[i] ? kp[col[i]] : 0.f;
-        vv[i] = ok[i] ? vp[col[i]] : 0.f;
+        if (SPLIT && !hist) {
+          kv[i] = ok[i] ? cur.k(col[i]) : 0.f;
+          vv[i] = ok[i] ? cur.v(col[i]) : 0.f;
+        } else {
+          kv[i] = ok[i] ? kp[col[i]] : 0.f;
+          vv[i] = ok[i] ? vp[col[i]] : 0.f;
+        }
       }
       float part = 0.f;
 #pragma unroll
@@ -194,7 +235,7 @@ __global__ __launch_bounds__(256) void k_sa_attn_bwd(AttnArgs a, const float* __
 // pairs that attended to it (inv_ptr / inv_ref = idx grouped by table row, ref = i * (T-1) + t, built on the
 // host) and accumulates  dK[r] = sum ds/sqrt(dk) * q[i],  dV[r] = sum p * dO[i]  in a fixed order -- every table
 // row is written exactly once, no atomics, no zero-fill.
-template <int MAXC>
+template <int MAXC, bool SPLIT>
 __global__ __launch_bounds__(256) void k_sa_attn_bwd_table(AttnArgs a, int n_table, const int32_t* __restrict__ inv_ptr,
                                                             const int32_t* __restrict__ inv_ref, const float* __restrict__ score,
                                                             const float* __restrict__ lse, const float* __restrict__ ds,
@@ -221,10 +262,11 @@ __global__ __launch_bounds__(256) void k_sa_attn_bwd_table(AttnArgs a, int n_tab
     const size_t sidx = ((size_t)row * 8 + head) * a.T + t;
     const float p = __expf(score[sidx] - lse[(size_t)row * 8 + head]);
     const float gs = ds[sidx] / a.sqrt_dk;
+    const CurRow<SPLIT> cur(a, row);
 #pragma unroll
     for (int i = 0; i < MAXC; ++i) {
       if (ok[i]) {
-        ak[i] = fmaf(gs, a.q[(size_t)row * a.ldq + col[i]], ak[i]);
+        ak[i] = fmaf(gs, cur.q(col[i]), ak[i]);
         av[i] = fmaf(p, d_out[(size_t)row * a.D + (size_t)(j + 8 * i) * 8 + head], av[i]);
       }
     }
@@ -234,15 +276,20 @@ __global__ __launch_bounds__(256) void k_sa_attn_bwd_table(AttnArgs a, int n_tab
     if (ok[i]) { d_kh[(size_t)r * ld_dh + col[i]] = ak[i]; d_vh[(size_t)r * ld_dh + col[i]] = av[i]; }
 }
 
-static int attn_check(const TempAttn* p) {
+static int attn_check(const TempAttn* p, const TempAttnSplit* s, bool split) {
   if (!p || p->n < 0 || p->D <= 0 || p->T < 1) return TEMP_E_BADARG;
   if (p->heads != 8 || p->D % 8 || p->D / 8 > 64 || p->T > 64) return TEMP_E_UNSUPPORTED;
-  if (p->n > 0 && (!p->q || !p->kc || !p->vc)) return TEMP_E_BADARG;
+  if (split) {
+    if (!s) return TEMP_E_BADARG;
+    if (p->n > 0 && (!s->pa || !s->ia || !s->pb || !s->ib || s->lda < 3 * p->D || s->ldb < 3 * p->D)) return TEMP_E_BADARG;
+  } else if (p->n > 0 && (!p->q || !p->kc || !p->vc)) {
+    return TEMP_E_BADARG;
+  }
   if (p->n > 0 && p->T > 1 && (!p->idx || !p->kh || !p->vh)) return TEMP_E_BADARG;
   return TEMP_OK;
 }
 
-static AttnArgs to_args(const TempAttn* p) {
+static AttnArgs to_args(const TempAttn* p, const TempAttnSplit* s) {
   AttnArgs a;
   a.n = p->n; a.D = p->D; a.dk = p->D / 8; a.T = p->T;
   a.q = p->q; a.ldq = p->ldq;
@@ -250,7 +297,56 @@ static AttnArgs to_args(const TempAttn* p) {
   a.kc = p->kc; a.vc = p->vc; a.ldc = p->ldc;
   a.idx = p->idx; a.decay = p->decay;
   a.sqrt_dk = sqrtf((float)a.dk);
+  a.pa = s ? s->pa : nullptr; a.ia = s ? s->ia : nullptr; a.lda = s ? s->lda : 0;
+  a.pb = s ? s->pb : nullptr; a.ib = s ? s->ib : nullptr; a.ldb = s ? s->ldb : 0;
   return a;
+}
+
+// one launch of kernel K<MAXC, SPLIT> with MAXC = the per-lane column count that covers d_k
+#define TEMP_ATTN_LAUNCH(KID, K, SPLIT, grid, ...)                                                   \
+  do {                                                                                                \
+    if (mc <= 1) TEMP_LAUNCH(KID, (K<1, SPLIT>), grid, block, 0, st, __VA_ARGS__);                    \
+    else if (mc <= 2) TEMP_LAUNCH(KID, (K<2, SPLIT>), grid, block, 0, st, __VA_ARGS__);               \
+    else if (mc <= 4) TEMP_LAUNCH(KID, (K<4, SPLIT>), grid, block, 0, st, __VA_ARGS__);               \
+    else TEMP_LAUNCH(KID, (K<8, SPLIT>), grid, block, 0, st, __VA_ARGS__);                            \
+  } while (0)
+
+template <bool SPLIT>
+static int attn_fwd(const TempAttn* p, const TempAttnSplit* s, float* out, float* score, float* lse, void* stream) {
+  int rc = attn_check(p, s, SPLIT);
+  if (rc != TEMP_OK) return rc;
+  if (p->n == 0) return TEMP_OK;
+  if (!out || !score || !lse) return TEMP_E_BADARG;
+  const AttnArgs a = to_args(p, s);
+  const dim3 grid(ceil_div(p->n, 4)), block(256);
+  hipStream_t st = (hipStream_t)stream;
+  const int mc = (a.dk + 7) / 8;
+  TEMP_ATTN_LAUNCH(K_SA_ATTN_FWD, k_sa_attn_fwd, SPLIT, grid, a, out, score, lse);
+  return launch_status();
+}
+
+template <bool SPLIT>
+static int attn_bwd(const TempAttn* p, const TempAttnSplit* s, const float* out, const float* score, const float* lse, const float* d_out,
+                    float* d_q, int ld_dq, float* d_kh, float* d_vh, int ld_dh, float* d_kc, float* d_vc, int ld_dc,
+                    float* d_decay, int n_table, const int32_t* inv_ptr, const int32_t* inv_ref, float* ds_ws, void* stream) {
+  int rc = attn_check(p, s, SPLIT);
+  if (rc != TEMP_OK) return rc;
+  if (p->n == 0) return TEMP_OK;
+  if (!out || !score || !lse || !d_out || !d_q || !d_kc || !d_vc) return TEMP_E_BADARG;
+  if (p->T > 1 && (!d_kh || !d_vh)) return TEMP_E_BADARG;
+  const bool table_pass = inv_ptr != nullptr && p->T > 1;
+  if (table_pass && (!ds_ws || !inv_ref || n_table <= 0)) return TEMP_E_BADARG;
+  const AttnArgs a = to_args(p, s);
+  AttnGrads g{d_q, ld_dq, d_kh, d_vh, ld_dh, d_kc, d_vc, ld_dc, d_decay, table_pass ? ds_ws : nullptr};
+  const dim3 grid(ceil_div(p->n, 4)), block(256);
+  hipStream_t st = (hipStream_t)stream;
+  const int mc = (a.dk + 7) / 8;
+  TEMP_ATTN_LAUNCH(K_SA_ATTN_BWD, k_sa_attn_bwd, SPLIT, grid, a, out, score, lse, d_out, g);
+  if (table_pass) {
+    const dim3 tg(ceil_div(n_table, 4));
+    TEMP_ATTN_LAUNCH(K_SA_ATTN_BWD, k_sa_attn_bwd_table, SPLIT, tg, a, n_table, inv_ptr, inv_ref, score, lse, ds_ws, d_out, d_kh, d_vh, ld_dh);
+  }
+  return launch_status();
 }
 
 }  // namespace temp
@@ -260,47 +356,27 @@ using namespace temp;
 extern "C" {
 
 int temp_sa_attn_fwd(const TempAttn* p, float* out, float* score, float* lse, void* stream) {
-  int rc = attn_check(p);
-  if (rc != TEMP_OK) return rc;
-  if (p->n == 0) return TEMP_OK;
-  if (!out || !score || !lse) return TEMP_E_BADARG;
-  const AttnArgs a = to_args(p);
-  const dim3 grid(ceil_div(p->n, 4)), block(256);
-  hipStream_t st = (hipStream_t)stream;
-  const int mc = (a.dk + 7) / 8;
-  if (mc <= 1) TEMP_LAUNCH(K_SA_ATTN_FWD, k_sa_attn_fwd<1>, grid, block, 0, st, a, out, score, lse);
-  else if (mc <= 2) TEMP_LAUNCH(K_SA_ATTN_FWD, k_sa_attn_fwd<2>, grid, block, 0, st, a, out, score, lse);
-  else if (mc <= 4) TEMP_LAUNCH(K_SA_ATTN_FWD, k_sa_attn_fwd<4>, grid, block, 0, st, a, out, score, lse);
-  else TEMP_LAUNCH(K_SA_ATTN_FWD, k_sa_attn_fwd<8>, grid, block, 0, st, a, out, score, lse);
-  return launch_status();
+  return attn_fwd<false>(p, nullptr, out, score, lse, stream);
 }
 
 int temp_sa_attn_bwd(const TempAttn* p, const float* out, const float* score, const float* lse, const float* d_out,
                      float* d_q, int ld_dq, float* d_kh, float* d_vh, int ld_dh, float* d_kc, float* d_vc, int ld_dc,
                      float* d_decay, int n_table, const int32_t* inv_ptr, const int32_t* inv_ref, float* ds_ws, void* stream) {
-  int rc = attn_check(p);
-  if (rc != TEMP_OK) return rc;
-  if (p->n == 0) return TEMP_OK;
-  if (!out || !score || !lse || !d_out || !d_q || !d_kc || !d_vc) return TEMP_E_BADARG;
-  if (p->T > 1 && (!d_kh || !d_vh)) return TEMP_E_BADARG;
-  const bool table_pass = inv_ptr != nullptr && p->T > 1;
-  if (table_pass && (!ds_ws || n_table <= 0)) return TEMP_E_BADARG;
-  const AttnArgs a = to_args(p);
-  AttnGrads g{d_q, ld_dq, d_kh, d_vh, ld_dh, d_kc, d_vc, ld_dc, d_decay, table_pass ? ds_ws : nullptr};
-  const dim3 grid(ceil_div(p->n, 4)), block(256);
-  hipStream_t st = (hipStream_t)stream;
-  const int mc = (a.dk + 7) / 8;
-  if (mc <= 1) TEMP_LAUNCH(K_SA_ATTN_BWD, k_sa_attn_bwd<1>, grid, block, 0, st, a, out, score, lse, d_out, g);
-  else if (mc <= 2) TEMP_LAUNCH(K_SA_ATTN_BWD, k_sa_attn_bwd<2>, grid, block, 0, st, a, out, score, lse, d_out, g);
-  else if (mc <= 4) TEMP_LAUNCH(K_SA_ATTN_BWD, k_sa_attn_bwd<4>, grid, block, 0, st, a, out, score, lse, d_out, g);
-  else TEMP_LAUNCH(K_SA_ATTN_BWD, k_sa_attn_bwd<8>, grid, block, 0, st, a, out, score, lse, d_out, g);
-  if (table_pass) {
-    const dim3 tg(ceil_div(n_table, 4));
-#define TEMP_TBL(M) TEMP_LAUNCH(K_SA_ATTN_BWD, k_sa_attn_bwd_table<M>, tg, block, 0, st, a, n_table, inv_ptr, inv_ref, score, lse, ds_ws, d_out, d_kh, d_vh, ld_dh)
-    if (mc <= 1) TEMP_TBL(1); else if (mc <= 2) TEMP_TBL(2); else if (mc <= 4) TEMP_TBL(4); else TEMP_TBL(8);
-#undef TEMP_TBL
-  }
-  return launch_status();
+  return attn_bwd<false>(p, nullptr, out, score, lse, d_out, d_q, ld_dq, d_kh, d_vh, ld_dh, d_kc, d_vc, ld_dc, d_decay, n_table, inv_ptr,
+                         inv_ref, ds_ws, stream);
+}
+
+int temp_sa_attn_split_fwd(const TempAttn* p, const TempAttnSplit* s, float* out, float* score, float* lse, void* stream) {
+  return attn_fwd<true>(p, s, out, score, lse, stream);
+}
+
+int temp_sa_attn_split_bwd(const TempAttn* p, const TempAttnSplit* s, const float* out, const float* score, const float* lse,
+                           const float* d_out, float* d_qkv, int ld_dqkv, float* d_kh, float* d_vh, int ld_dh, float* d_decay,
+                           int n_table, const int32_t* inv_ptr, const int32_t* inv_ref, float* ds_ws, void* stream) {
+  if (p && (p->D <= 0 || ld_dqkv < 3 * p->D)) return TEMP_E_BADARG;
+  const int D = p ? p->D : 0;
+  return attn_bwd<true>(p, s, out, score, lse, d_out, d_qkv, ld_dqkv, d_kh, d_vh, ld_dh, d_qkv ? d_qkv + D : nullptr,
+                        d_qkv ? d_qkv + 2 * D : nullptr, ld_dqkv, d_decay, n_table, inv_ptr, inv_ref, ds_ws, stream);
 }
 
 }  // extern "C"

@@ -7,6 +7,7 @@ Each Function is one reference op with its hand-written backward:
   gather_rows     ent_embeds[id] / history gather   models/DynamicRGCN.py:41-43,93
   linear          nn.Linear without bias (q/k/v projections)   models/SARGCN.py:16-18,32-34
   history_attention   SARGCNLayer.attention over the active history rows   models/SARGCN.py:25-53
+  split_history_attention  the same for current rows that are a sum of two table rows (post-aggregation attention models)
 """
 import numpy as np
 import torch
@@ -922,6 +923,47 @@ def history_attention(qkv, kv_hist, idx, decay=None, inverse=None):
     inverse = attention_inverse(idx, R): static maps that make the backward deterministic (no atomics).
     Returns (n,D) in the reference's feature order (d * 8 + head)."""
     return _HistoryAttentionFn.apply(qkv, kv_hist, idx, decay, inverse)
+
+
+class _SplitHistoryAttentionFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, pa, pb, kv_hist, ia, ib, idx, decay, inverse, inv_a, inv_b):
+        out, score, lse = get_backend().sa_attn_split_fwd(pa, ia, pb, ib, kv_hist, idx, decay)
+        ctx.save_for_backward(pa, pb, kv_hist, ia, ib, idx, decay if decay is not None else pa.new_zeros(0), out, score, lse)
+        ctx.has_decay = decay is not None
+        ctx.inverse, ctx.inv_a, ctx.inv_b = inverse, inv_a, inv_b
+        return out
+
+    @staticmethod
+    def backward(ctx, d_out):
+        pa, pb, kv_hist, ia, ib, idx, decay, out, score, lse = ctx.saved_tensors
+        be = get_backend()
+        d_qkv, d_hist, d_decay = be.sa_attn_split_bwd(pa, ia, pb, ib, kv_hist, idx, decay if ctx.has_decay else None, out, score, lse,
+                                                      d_out.contiguous(), ctx.inverse)
+        # d_pa[r] = sum of d_qkv over the rows with ia == r (d_pb alike): the rows are summed as their three D-wide thirds
+        # (split_row_inverse), which keeps the common widths on the segment-sum kernels' piece / two-stage routes
+        D = d_qkv.shape[1] // 3
+        thirds = d_qkv.view(-1, D)
+        d_pa = be.segment_sum_rows(thirds, ctx.inv_a[0], ctx.inv_a[1], 3 * pa.shape[0]).view(pa.shape[0], 3 * D)
+        d_pb = be.segment_sum_rows(thirds, ctx.inv_b[0], ctx.inv_b[1], 3 * pb.shape[0]).view(pb.shape[0], 3 * D)
+        return d_pa, d_pb, d_hist, None, None, None, d_decay, None, None, None
+
+
+def split_history_attention(pa, ia, pb, ib, kv_hist, idx, decay=None, inverse=None, inv_a=None, inv_b=None):
+    """history_attention for current rows that are sums of two rows: row i attends with (q | k | v) = pa[ia[i]] + pb[ib[i]]
+    (pa (Na,3D), pb (Nb,3D): the projections of two small tables; ia / ib (n,) int32), formed inside the kernel -- the (n,3D)
+    buffer of the summed rows is never written and the projection runs over Na + Nb rows instead of n.
+    inv_a / inv_b = split_row_inverse(ia, Na) / (ib, Nb): the static maps of the deterministic sums into d_pa / d_pb (required)."""
+    if inv_a is None or inv_b is None:
+        raise ValueError("split_history_attention needs inv_a / inv_b (split_row_inverse of ia / ib)")
+    return _SplitHistoryAttentionFn.apply(pa, pb, kv_hist, ia, ib, idx, decay, inverse, inv_a, inv_b)
+
+
+def split_row_inverse(idx_np, n_rows, device):
+    """gather_inverse of a split-attention row list over the THIRDS of its rows: third c of query row i belongs to segment
+    3 * idx[i] + c of the (3 * n_rows, D) view of the (n_rows, 3D) table gradient."""
+    idx = np.asarray(idx_np, dtype=np.int64).reshape(-1, 1)
+    return gather_inverse((3 * idx + np.arange(3, dtype=np.int64)[None, :]).reshape(-1), 3 * int(n_rows), device)
 
 
 def attention_inverse(idx_np, n_table, device):

@@ -34,8 +34,9 @@ class SARGCNLayer(RGCNLayer):
             raise ValueError("SARGCNLayer needs in_feat divisible by its 8 heads (models/SARGCN.py:21-22)")
         self.post_aggregation = getattr(args, "post_aggregation", False)
         self.post_ensemble = getattr(args, "post_ensemble", False)
-        if self.post_aggregation or self.post_ensemble:
-            raise NotImplementedError("--post-aggregation / --post-ensemble are outside the hot-path scope (SURVEY section 8)")
+        if self.post_ensemble:
+            raise NotImplementedError("--post-ensemble with the attention encoder: the reference has no such model (main.py:74-79 routes "
+                                      "only --post-aggregation to the attention classes)")
 
     # -- table formulation (what the window models call) ----------------------------------------------
     def project_kv(self, rows):
@@ -57,6 +58,14 @@ class SARGCNLayer(RGCNLayer):
         if kv_hist.shape[0] == 0:
             kv_hist, inverse = cur.new_zeros(1, 2 * self.in_feat), None
         return TF.history_attention(self.project_qkv(cur), kv_hist, idx, self.decay_bias(time_diff), inverse)
+
+    def attend_split(self, p_a, ia, p_b, ib, kv_hist, idx, time_diff, inverse, inv_a, inv_b):
+        """`attend` for current rows cur[i] = a[ia[i]] + b[ib[i]] given by the PROJECTIONS of the two small tables
+        (p_a = project_qkv(a), p_b = project_qkv(b); the projection is linear): the kernel forms the row's (q | k | v) itself.
+        inv_a / inv_b = TF.split_row_inverse(ia / ib): the static maps of the sums into the two tables' gradients."""
+        if kv_hist.shape[0] == 0:
+            kv_hist, inverse = p_a.new_zeros(1, 2 * self.in_feat), None
+        return TF.split_history_attention(p_a, ia, p_b, ib, kv_hist, idx, self.decay_bias(time_diff), inverse, inv_a, inv_b)
 
     # -- reference (dense) API ----------------------------------------------------------------------------
     def calc_result(self, cur_embeddings, prev_embeddings, time_diff, local_attn_mask):

@@ -29,6 +29,7 @@ from .window import window_times
 
 class SelfAttentionRGCN(DynamicRGCN):
     bidirectional = False
+    _post_aggregation_model = False       # the --post-aggregation classes (post_self_attention_rgcn.py) set it
     _chain_time_embedding = False         # no GRU chain here: the attention path adds the time embedding itself
 
     def __init__(self, args, num_ents, num_rels, graph_dict_train, graph_dict_val, graph_dict_test, evaluater_type=None):
@@ -36,6 +37,9 @@ class SelfAttentionRGCN(DynamicRGCN):
         self.EMA = getattr(args, "EMA", False)
         if self.EMA:
             raise NotImplementedError("--EMA (models/SARGCN.py:64-81 stops in pdb.set_trace()) is outside the hot-path scope")
+        if self.post_aggregation and not self._post_aggregation_model:
+            raise NotImplementedError("--post-aggregation with the attention encoder is PostSelfAttentionRGCN / PostBiSelfAttentionRGCN "
+                                      "(main.py:74-79), not this class")
 
     def build_model(self):
         self.ent_encoder = SARGCN(self.args, self.hidden_size, self.embed_size, self.num_rels, self.total_time)
@@ -124,6 +128,7 @@ class SelfAttentionRGCN(DynamicRGCN):
         for b, g in enumerate(wb.graphs):
             asm[b, g.gids] = off_out[b] + np.arange(g.n)
             asm[b, inact[b]] = n_out + off_in[b] + np.arange(len(inact[b]))
+        wb.inactive_host = inact
         wb.inactive_ent = as_dev(np.concatenate(inact), np.int32)
         wb.n_inactive = int(off_in[-1])
         wb.assemble = as_dev(asm.reshape(-1), np.int32)
