@@ -708,6 +708,20 @@ int temp_segment_sum_rows(int n_seg, int n_rows, int d, const int32_t* seg_ptr, 
 int temp_segment_sum_rows_relu(int n_seg, int n_rows, int d, const int32_t* seg_ptr, const int32_t* order, const float* src, const float* relu_of,
                                float* out, void* workspace, size_t workspace_bytes, void* stream);
 
+/* The diachronic entity table (baselines/DiachronicEmbedding.py:22-28) for B timestamps at once, and its adjoint:
+ *   out[(b N + j), c] = ent[j, c]                                             c <  ds = d / 2   (integer division)
+ *                     = ent[j, c] * sin(t[b] * w[j, c - ds] + b[j, c - ds])   c >= ds
+ * ent [N, d], w and b [N, d - ds], t [B] in DEVICE memory, out / d_out [B N, d].  The argument is formed as torch forms it -- the
+ * product and the sum are two rounded fp32 operations, never a fused multiply-add -- and goes through the range-reducing
+ * sinf / cosf (t w reaches the thousands).  The backward keeps nothing from the forward and OVERWRITES
+ *   d_ent = sum_b d_out (1 | sin)      d_b = sum_b d_out ent cos      d_w = sum_b d_out ent cos t[b]
+ * with the B terms added in ascending b in registers: no atomics, no workspace, one launch, bit-repeatable.
+ * Any B >= 1, N >= 1, d >= 2 (else TEMP_E_BADARG): float4 on every stream when d % 4 == 0 and ds % 4 == 0, one column per thread
+ * otherwise.  A pure stream: 2 N d floats read and B N d written forward, the mirror image backward. */
+int temp_diachronic_rows_fwd(int B, int N, int d, const float* ent, const float* w, const float* b, const float* t, float* out, void* stream);
+int temp_diachronic_rows_bwd(int B, int N, int d, const float* ent, const float* w, const float* b, const float* t, const float* d_out, float* d_ent,
+                             float* d_w, float* d_b, void* stream);
+
 /* ------------------------------------------------------------------------------------------------
  * Plain fp32 MFMA GEMMs (the extra (n,D)@(D,D) terms of the linear-recurrence layers,
  * models/RRGCN.py:141, models/BiRRGCN.py:128-129; the all-entity score matrix below).

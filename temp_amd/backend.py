@@ -380,6 +380,29 @@ class HipBackend:
         _lib.check(self.lib.temp_decay_rows(x.shape[0], x.shape[1], _ptr(x), _ptr(dt), float(lam), _ptr(out), _stream()), "temp_decay_rows")
         return out
 
+    # ---- the diachronic entity table (include/temp_amd.h: temp_diachronic_rows_fwd / _bwd) --------
+    def diachronic_rows_fwd(self, ent, w, b, t):
+        """-> (B N, d) stack of ent * [1 | sin(t_b w + b)] for the B device-resident times `t` (one launch)."""
+        ent, w, b, t = _f32(ent, "ent"), _f32(w, "w"), _f32(b, "b"), _f32(t, "t")
+        N, d = ent.shape
+        if tuple(w.shape) != (N, d - d // 2) or w.shape != b.shape or t.dim() != 1:
+            raise _lib.TempAmdError("diachronic_rows: ent (N, d), w / b (N, d - d // 2), t (B,) expected")
+        out = torch.empty(t.shape[0] * N, d, dtype=torch.float32, device=ent.device)
+        _lib.check(self.lib.temp_diachronic_rows_fwd(t.shape[0], N, d, _ptr(ent), _ptr(w), _ptr(b), _ptr(t), _ptr(out), _stream()),
+                   "temp_diachronic_rows_fwd")
+        return out
+
+    def diachronic_rows_bwd(self, ent, w, b, t, d_out):
+        """-> (d_ent, d_w, d_b), each overwritten whole by one launch (no zero-fill, no atomics)."""
+        ent, w, b, t, d_out = _f32(ent, "ent"), _f32(w, "w"), _f32(b, "b"), _f32(t, "t"), _f32(d_out, "d_out")
+        N, d = ent.shape
+        if tuple(d_out.shape) != (t.shape[0] * N, d):
+            raise _lib.TempAmdError("diachronic_rows_bwd: d_out must be (B N, d)")
+        d_ent, d_w, d_b = torch.empty_like(ent), torch.empty_like(w), torch.empty_like(b)
+        _lib.check(self.lib.temp_diachronic_rows_bwd(t.shape[0], N, d, _ptr(ent), _ptr(w), _ptr(b), _ptr(t), _ptr(d_out), _ptr(d_ent), _ptr(d_w),
+                                                     _ptr(d_b), _stream()), "temp_diachronic_rows_bwd")
+        return d_ent, d_w, d_b
+
     # ---- persistent window chain (include/temp_amd.h: TempGruChain) -------------------------------
     def gru_chain_supported(self, d):
         return bool(self.lib.temp_gru_chain_supported(int(d)))

@@ -414,6 +414,101 @@ int segment_sum_rows(int n_seg, int d, const int32_t* seg_ptr, const int32_t* or
 #undef TEMP_SEGSUM
   return launch_status();
 }
+// ---- the diachronic entity table (DE: ent * [1 | sin(t w + b)]) and its adjoint ------------------------------------------------
+// out[(b N + j), c] = ent[j, c]                                            c <  ds = d / 2
+//                   = ent[j, c] * sin(t_b * w[j, c - ds] + b[j, c - ds])   c >= ds
+// One thread owns one entity and V columns (V = 4: float4 on every stream; V = 1 for the widths float4 does not divide) and walks
+// the B timestamps: ent / w / b are read once, the adjoint sums its B terms in registers in ascending b and OVERWRITES d_ent /
+// d_w / d_b -- no atomics, no workspace, no second launch.  Nothing is kept between the passes: the backward forms sin / cos anew.
+template <int V> struct alignas(4 * V) DeVec { float v[V]; };
+
+// The argument as torch forms it: t * w and + b are TWO rounded fp32 operations.  At t ~ 4e3 a fused multiply-add moves the
+// argument by up to half an ulp of a number in the thousands, i.e. the sine by 1e-5 .. 1e-4.  Contraction is switched off for
+// exactly these two operations (the build's default contracts a * b + c wherever it sees one).
+__device__ __forceinline__ float de_arg(float t, float w, float b) {
+#pragma clang fp contract(off)
+  const float p = t * w;
+  return p + b;
+}
+
+template <int V>
+__global__ void __launch_bounds__(256) k_diachronic_fwd(int B, int N, int d, const float* __restrict__ ent, const float* __restrict__ w,
+                                                        const float* __restrict__ bias, const float* __restrict__ t, float* __restrict__ out) {
+  using Vec = DeVec<V>;
+  const int dv = d / V, dsv = (d / 2) / V, dtv = dv - dsv;
+  const size_t plane = (size_t)N * dv;                           // Vecs per timestamp
+  const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= plane) return;
+  const int j = (int)(i / dv), c = (int)(i - (size_t)j * dv);
+  const Vec e = ((const Vec*)ent)[i];
+  Vec* __restrict__ o = (Vec*)out;
+  if (c < dsv) {                                                 // the static half is a copy
+    for (int b = 0; b < B; ++b) o[(size_t)b * plane + i] = e;
+    return;
+  }
+  const size_t k = (size_t)j * dtv + (c - dsv);
+  const Vec wv = ((const Vec*)w)[k], bv = ((const Vec*)bias)[k];
+  for (int b = 0; b < B; ++b) {
+    const float tb = t[b];
+    Vec r;
+#pragma unroll
+    for (int u = 0; u < V; ++u) r.v[u] = e.v[u] * sinf(de_arg(tb, wv.v[u], bv.v[u]));
+    o[(size_t)b * plane + i] = r;
+  }
+}
+
+template <int V>
+__global__ void __launch_bounds__(256) k_diachronic_bwd(int B, int N, int d, const float* __restrict__ ent, const float* __restrict__ w,
+                                                        const float* __restrict__ bias, const float* __restrict__ t,
+                                                        const float* __restrict__ d_out, float* __restrict__ d_ent, float* __restrict__ d_w,
+                                                        float* __restrict__ d_b) {
+  using Vec = DeVec<V>;
+  const int dv = d / V, dsv = (d / 2) / V, dtv = dv - dsv;
+  const size_t plane = (size_t)N * dv;
+  const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= plane) return;
+  const int j = (int)(i / dv), c = (int)(i - (size_t)j * dv);
+  const Vec* __restrict__ g = (const Vec*)d_out;
+  Vec ae;
+#pragma unroll
+  for (int u = 0; u < V; ++u) ae.v[u] = 0.f;
+  if (c < dsv) {
+#pragma unroll 4
+    for (int b = 0; b < B; ++b) {
+      const Vec gv = g[(size_t)b * plane + i];
+#pragma unroll
+      for (int u = 0; u < V; ++u) ae.v[u] += gv.v[u];
+    }
+    ((Vec*)d_ent)[i] = ae;
+    return;
+  }
+  const size_t k = (size_t)j * dtv + (c - dsv);
+  const Vec e = ((const Vec*)ent)[i], wv = ((const Vec*)w)[k], bv = ((const Vec*)bias)[k];
+  Vec aw = ae, ab = ae;
+#pragma unroll 4
+  for (int b = 0; b < B; ++b) {
+    const Vec gv = g[(size_t)b * plane + i];
+    const float tb = t[b];
+#pragma unroll
+    for (int u = 0; u < V; ++u) {
+      float sn, cs;
+      sincosf(de_arg(tb, wv.v[u], bv.v[u]), &sn, &cs);
+      const float gc = gv.v[u] * e.v[u] * cs;                    // d_out * ent * cos
+      ae.v[u] += gv.v[u] * sn;
+      ab.v[u] += gc;
+      aw.v[u] += gc * tb;
+    }
+  }
+  ((Vec*)d_ent)[i] = ae;
+  ((Vec*)d_w)[k] = aw;
+  ((Vec*)d_b)[k] = ab;
+}
+
+// float4 on every stream needs both halves of a row to start on a 16-byte boundary: d % 4 == 0 and (d / 2) % 4 == 0
+static bool diachronic_vec(int d) { return d % 4 == 0 && (d / 2) % 4 == 0; }
+static bool diachronic_args_ok(int B, int N, int d) {
+  return B >= 1 && N >= 1 && d >= 2 && ((long long)N * d + 255) / 256 <= 0x7fffffffLL;       // (the grid: one thread per V columns)
+}
 }  // namespace temp
 
 using namespace temp;
@@ -460,6 +555,27 @@ int temp_gather_rows_keys(int n, int d, const float* table, const int32_t* idx, 
   if (d % 4 || d > 256) return TEMP_E_UNSUPPORTED;
   if (n == 0) return TEMP_OK;
   launch_gather_rows_keys(n, d, table, idx, out, row_keys, col_keys, col_keys ? col_keys + d : nullptr, (hipStream_t)stream);
+  return launch_status();
+}
+
+int temp_diachronic_rows_fwd(int B, int N, int d, const float* ent, const float* w, const float* b, const float* t, float* out, void* stream) {
+  if (!diachronic_args_ok(B, N, d) || !ent || !w || !b || !t || !out) return TEMP_E_BADARG;
+  if (diachronic_vec(d))
+    TEMP_LAUNCH(K_DIACHRONIC_FWD, k_diachronic_fwd<4>, dim3(ceil_div((long long)N * (d / 4), 256)), dim3(256), 0, (hipStream_t)stream, B, N, d, ent, w, b, t, out);
+  else
+    TEMP_LAUNCH(K_DIACHRONIC_FWD, k_diachronic_fwd<1>, dim3(ceil_div((long long)N * d, 256)), dim3(256), 0, (hipStream_t)stream, B, N, d, ent, w, b, t, out);
+  return launch_status();
+}
+
+int temp_diachronic_rows_bwd(int B, int N, int d, const float* ent, const float* w, const float* b, const float* t, const float* d_out, float* d_ent,
+                             float* d_w, float* d_b, void* stream) {
+  if (!diachronic_args_ok(B, N, d) || !ent || !w || !b || !t || !d_out || !d_ent || !d_w || !d_b) return TEMP_E_BADARG;
+  if (diachronic_vec(d))
+    TEMP_LAUNCH(K_DIACHRONIC_BWD, k_diachronic_bwd<4>, dim3(ceil_div((long long)N * (d / 4), 256)), dim3(256), 0, (hipStream_t)stream, B, N, d, ent, w, b, t,
+                d_out, d_ent, d_w, d_b);
+  else
+    TEMP_LAUNCH(K_DIACHRONIC_BWD, k_diachronic_bwd<1>, dim3(ceil_div((long long)N * d, 256)), dim3(256), 0, (hipStream_t)stream, B, N, d, ent, w, b, t,
+                d_out, d_ent, d_w, d_b);
   return launch_status();
 }
 

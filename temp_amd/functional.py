@@ -898,6 +898,30 @@ def decay_rows(x, dt, lam):
     return _DecayRowsFn.apply(x, dt, float(lam))
 
 
+class _DiachronicRowsFn(torch.autograd.Function):
+    """The (B N, D) stack of diachronic entity tables ent * [1 | sin(t_b w + b)] (temp_diachronic_rows_fwd); the backward recomputes
+    the sines from the parameters and reduces the stack's gradient over b in the same launch (temp_diachronic_rows_bwd)."""
+
+    @staticmethod
+    def forward(ctx, ent, w, b, t):
+        ctx.save_for_backward(ent, w, b, t)
+        return get_backend().diachronic_rows_fwd(ent, w, b, t)
+
+    @staticmethod
+    def backward(ctx, d_out):
+        ent, w, b, t = ctx.saved_tensors
+        return get_backend().diachronic_rows_bwd(ent, w, b, t, d_out.contiguous()) + (None,)
+
+
+def diachronic_rows(ent, w, b, t):
+    """Rows b N + j of the result = DE(t[b])[j] = ent[j] * [1 (first D // 2 columns) | sin(t[b] * w[j] + b[j])]
+    (baselines/DiachronicEmbedding.py:22-28, the argument rounded twice as torch rounds it).  ent (N, D), w / b (N, D - D // 2),
+    t float32 (B,) on the parameters' device; t gets no gradient."""
+    if t.dtype != torch.float32 or t.dim() != 1:
+        raise ValueError("diachronic_rows: t must be a float32 vector (B,)")
+    return _DiachronicRowsFn.apply(ent.contiguous(), w.contiguous(), b.contiguous(), t.contiguous())
+
+
 class _HistoryAttentionFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, qkv, kv_hist, idx, decay, inverse):

@@ -1,0 +1,179 @@
+"""The embedding-only baselines of the paper's tables, with the reference's interface: `--module Static` (baselines/Static.py) and
+`--module DE`, the diachronic embedding (baselines/DiachronicEmbedding.py), both on baselines/TKG_Non_Recurrent.py.  No message
+passing: the all-entity table of timestamp t is a function of the parameters and t alone,
+
+    Static               ent_embeds
+    DiachronicEmbedding  ent_embeds * [1 (first D // 2 columns) | sin(t * w_temp_ent_embeds + b_temp_ent_embeds)]
+
+so a batch of B timestamps is ONE (B N, D) stack (functional.diachronic_rows: one launch forward, one backward that already sums
+over the timestamps) scored by ONE fused loss node (TKG_Module.batched_link_prediction) -- the loss, the sampler and the filtered
+ranking are the ones the RGCN models use."""
+import math
+
+import numpy as np
+import torch
+import torch.nn as nn
+
+from . import _lib
+from . import functional as TF
+from .tkg_module import TKG_Module
+
+
+class TKG_Non_Recurrent(TKG_Module):
+    """baselines/TKG_Non_Recurrent.py:8-32.  Subclasses give `table_stack(times)`: the (B N, D) stack of the all-entity tables of the
+    float32 device vector `times`; rows b N + gids of it are the target rows of graph b (get_per_graph_ent_embeds)."""
+
+    def __init__(self, args, num_ents, num_rels, graph_dict_train, graph_dict_val, graph_dict_test):
+        super().__init__(args, num_ents, num_rels, graph_dict_train, graph_dict_val, graph_dict_test)
+        self.ent_embeds = nn.Parameter(torch.Tensor(self.num_ents, self.embed_size))
+        self.rel_embeds = nn.Parameter(torch.Tensor(self.num_rels * 2, self.embed_size))
+        nn.init.xavier_uniform_(self.ent_embeds, gain=nn.init.calculate_gain('relu'))
+        nn.init.xavier_uniform_(self.rel_embeds, gain=nn.init.calculate_gain('relu'))
+        self.sample_rng = np.random.default_rng(getattr(args, "seed", None))
+        self.seed_rng = np.random.default_rng(None if getattr(args, "seed", None) is None else int(args.seed) + 1)
+        self.use_device_sampler = True
+
+    def build_model(self):
+        pass
+
+    def table_stack(self, times):
+        raise NotImplementedError
+
+    def _times(self, ts):
+        return _lib.to_device(np.asarray(ts, dtype=np.float32), self.ent_embeds.device)
+
+    def _gids(self, g):
+        return torch.from_numpy(g.gids).to(self.ent_embeds.device)
+
+    def get_all_embeds_Gt(self, t):
+        return self.table_stack(self._times([int(t)]))
+
+    def get_per_graph_ent_embeds(self, t, g):
+        """The rows of the graph's entities (the reference gathers the parameters and applies the same element-wise map)."""
+        return self.get_all_embeds_Gt(t)[self._gids(g)]
+
+    # -- evaluation (models/TKG_Module.py:253-274) ---------------------------------------------------------------------------
+    def evaluate(self, t_list, val=True):
+        """Filtered ranks of the valid / test triples + the mean classification loss; all B tables from one table_stack call,
+        empty graphs skipped."""
+        from .evaluation import EvaluationFilter
+        if not hasattr(self, "evaluater"):
+            self.evaluater = EvaluationFilter(self.args, self.calc_score, self.graph_dict_train, self.graph_dict_val, self.graph_dict_test)
+        graph_dict = self.graph_dict_val if val else self.graph_dict_test
+        dev, N = self.ent_embeds.device, self.num_ents
+        ts = [int(t) for t in t_list]
+        ranks, losses = [], []
+        with torch.no_grad():
+            stack = self.table_stack(self._times(ts))
+            for b, t in enumerate(ts):
+                g = graph_dict[t]
+                if g.number_of_edges() == 0:
+                    continue
+                all_embeds_g = stack[b * N:(b + 1) * N]
+                ent_embed = all_embeds_g[self._gids(g)]
+                index_sample = torch.from_numpy(np.stack([g.src, g.rel, g.dst], axis=1)).to(dev)
+                label = torch.ones(index_sample.shape[0], device=dev)
+                ranks.append(self.evaluater.calc_metrics_single_graph(ent_embed, self.rel_embeds, all_embeds_g, index_sample, g, t))
+                losses.append(self.link_classification_loss(ent_embed, self.rel_embeds, index_sample, label).item())
+        ranks = torch.cat(ranks) if ranks else torch.zeros(0, dtype=torch.int64, device=dev)
+        return ranks, (float(np.mean(losses)) if losses else float("nan"))
+
+    # -- the fused batch loss ------------------------------------------------------------------------------------------------
+    def _fused_loss_ok(self):
+        return self.use_device_sampler and self.fused_loss_ok(self.embed_size)
+
+    def _fused_plan(self, ts, g_list):
+        """Host half of the fused loss of a batch, uploaded once: the times, the positives / operand indices / known-true slices
+        (sampling.plan_batch_loss).  The known rows point INTO the table stack: local id i of graph b -> row b N + gids_b[i]."""
+        from .sampling import TrueSetStore, plan_batch_loss
+        dev, N, B = self.ent_embeds.device, self.num_ents, len(g_list)
+        off = np.concatenate([[0], np.cumsum([g.n for g in g_list])])
+        row_map = np.concatenate([b * N + g.gids.astype(np.int64) for b, g in enumerate(g_list)]) if B else np.zeros(0, np.int64)
+        store = getattr(self, "_true_store", None)
+        if store is None or store.device != dev:
+            store = self._true_store = TrueSetStore(self.graph_dict_train, N, dev)
+        plan = plan_batch_loss(store, ts, g_list, off[:-1], self.args.num_pos_facts, self.sample_rng, B * N, int(self.rel_embeds.shape[0]), dev,
+                               row_map=row_map)
+        return dict(plan=plan, B=B, times=self._times(ts))
+
+    def _fused_loss(self, fp, cand=None):
+        """sum_b loss_tail + loss_head as one table_stack node and one batched_link_prediction node: the stack is both the
+        all-entity operand and the source of the known rows, so its gradient arrives once; the negatives of all graphs come from
+        one launch (`cand`: a fixed draw to reuse, else a fresh one per call)."""
+        from .backend import get_backend
+        plan = fp["plan"]
+        if plan is None:
+            return self.ent_embeds.sum() * 0.0
+        stack = self.table_stack(fp["times"])
+        if cand is None:
+            cand = get_backend().corrupt_sample(int(self.seed_rng.integers(1 << 62)), plan["truth"], plan["lo"], plan["hi"], plan["ids"],
+                                                self.args.negative_rate, self.num_ents)
+        self._last_plan = (plan, cand)
+        return self.batched_link_prediction(stack, dict(plan, cand=cand), stack)
+
+    def prepare(self, t_list):
+        """-> a prepared batch: graphs, times on the device and -- when a fused loss node takes the scorer -- the loss plan.  A step
+        on it (run_loss) uploads nothing."""
+        wb = type("NonRecurrentBatch", (), {})()
+        wb.ts = [int(t) for t in t_list]
+        wb.g_list = [self.graph_dict_train[t] for t in wb.ts]
+        wb.fused = self._fused_plan(wb.ts, wb.g_list) if self._fused_loss_ok() else None
+        return wb
+
+    def run_loss(self, wb, cand=None):
+        """Table stack + fused loss on a prepared batch (cand: fixed negatives, e.g. the draw of an earlier call: self._last_plan[1])."""
+        if wb.fused is None:
+            raise NotImplementedError("run_loss needs the fused loss (a scorer and a width with a fused node); use forward()")
+        return self._fused_loss(wb.fused, cand)
+
+    def forward(self, t_list, samples=None):
+        """baselines/TKG_Non_Recurrent.py:21-32.  samples: per graph (triplets, neg_tail, neg_head) to use instead of a draw; they,
+        or a scorer / width without a fused node, take the reference-granular loop -- over slices of the same one table stack."""
+        dev, N = self.ent_embeds.device, self.num_ents
+        ts = [int(t) for t in t_list]
+        g_list = [self.graph_dict_train[t] for t in ts]
+        if samples is None and self._fused_loss_ok():
+            return self._fused_loss(self._fused_plan(ts, g_list))
+        stack = self.table_stack(self._times(ts))
+        loss = 0
+        for b, (t, g) in enumerate(zip(ts, g_list)):
+            if samples is not None:
+                triplets, neg_tail, neg_head = samples[b]
+                labels = torch.zeros(triplets.shape[0], dtype=torch.int64)
+            else:
+                triplets, neg_tail, neg_head, labels = self.corrupter.single_graph_negative_sampling(t, g, N)
+            if triplets.shape[0] == 0:
+                continue
+            triplets, neg_tail, neg_head, labels = triplets.to(dev), neg_tail.to(dev), neg_head.to(dev), labels.to(dev)
+            all_embeds_g = stack[b * N:(b + 1) * N]
+            loss = loss + self.train_link_prediction_both(all_embeds_g[self._gids(g)], triplets, neg_tail, neg_head, labels, all_embeds_g)
+        return loss
+
+
+class Static(TKG_Non_Recurrent):
+    """baselines/Static.py: one time-independent table."""
+
+    def get_all_embeds_Gt(self, t):
+        return self.ent_embeds
+
+    def table_stack(self, times):
+        """B times the same table, as an EXPANDED VIEW of ent_embeds made contiguous: both loss nodes address window b's table at
+        row b N of their operand (functional._window_scores slices it, the L1 node adds window * N to every candidate), so neither
+        takes a per-row base of 0 and the windows cannot share one copy; the view's adjoint sums the B blocks."""
+        B = times.shape[0]
+        return self.ent_embeds.unsqueeze(0).expand(B, self.num_ents, self.embed_size).reshape(B * self.num_ents, self.embed_size)
+
+
+class DiachronicEmbedding(TKG_Non_Recurrent):
+    """baselines/DiachronicEmbedding.py: the second half of every entity row is modulated by sin(t w + b)."""
+
+    def build_model(self):
+        self.static_embed_size = math.floor(0.5 * self.embed_size)
+        self.temporal_embed_size = self.embed_size - self.static_embed_size
+        self.w_temp_ent_embeds = nn.Parameter(torch.Tensor(self.num_ents, self.temporal_embed_size))
+        self.b_temp_ent_embeds = nn.Parameter(torch.Tensor(self.num_ents, self.temporal_embed_size))
+        nn.init.xavier_uniform_(self.w_temp_ent_embeds, gain=nn.init.calculate_gain('relu'))
+        nn.init.xavier_uniform_(self.b_temp_ent_embeds, gain=nn.init.calculate_gain('relu'))
+
+    def table_stack(self, times):
+        return TF.diachronic_rows(self.ent_embeds, self.w_temp_ent_embeds, self.b_temp_ent_embeds, times)
