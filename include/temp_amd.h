@@ -961,6 +961,31 @@ int temp_filtered_rank(int P, int N, int ld, const float* scores, const int32_t*
                        const int32_t* filt_ids, int32_t* ranks, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * Filtered top-k selection: the answer list of a query (s, r, ?, t) or (?, r, o, t), where temp_filtered_rank only locates one
+ * known answer.  scores [P, ld] = P queries scored against the N entities col0 .. col0 + N - 1 (the same producers: temp_linear with
+ * the folded query, temp_l1_scores); column j < N is the score of entity col0 + j, columns >= N never reach the result.
+ *   entity e = col0 + j is ADMISSIBLE for row p  <=>  scores[p,j] > -inf  and  (e is not in the row's filter list
+ *                                                     filt_ids[filt_ptr[p] .. filt_ptr[p+1])  or  e == keep[p])
+ *   ORDER: higher score first, among equal scores the smaller entity id first -- total, the stable-descending convention of
+ *          temp_filtered_rank, but on the RAW scores: the rank kernel's sigmoid saturates (every score above ~17 becomes 1.0f,
+ *          every one below ~-104 becomes 0) and so manufactures ties, which is the reference's rank definition and useless for
+ *          listing answers.  +inf is an ordinary score; NaN is unspecified.
+ *   top_val / top_idx [P, k]: row p = the first min(k, #admissible) admissible entities in that order (score, global id), the
+ *          remaining slots (-inf, -1).  Fully written.
+ * carry = 0 starts fresh.  carry = 1 merges into the lists already in top_val / top_idx, which must be the result of earlier calls
+ * over entity ranges disjoint from [col0, col0 + N): the result equals ONE call over the union of the ranges, bit for bit and in
+ * any panel order (the selection is a function of the total order alone), so [P, N] never has to exist at once.
+ * filt_ptr nullable [P+1] (NULL: nothing filtered); filt_ids = GLOBAL entity ids, unique and ascending within a row
+ * (EvaluationFilter.filter_lists), NULL only when every list is empty; keep nullable [P], -1 = none.
+ * 1 <= k <= TEMP_TOPK_MAX, N > 0, ld >= N, col0 >= 0 (else TEMP_E_BADARG); ld % 4 == 0 and scores 16-byte aligned (else
+ * TEMP_E_UNSUPPORTED) -- a column slice base + c of a wider matrix, c % 4 == 0, with the wide ld qualifies.  P == 0 succeeds without a
+ * launch.  No workspace, no floating-point atomics: bit-repeatable.
+ * ---------------------------------------------------------------------------------------------- */
+#define TEMP_TOPK_MAX 256
+int temp_filtered_topk(int P, int N, int ld, int k, int col0, const float* scores, const int32_t* filt_ptr, const int32_t* filt_ids,
+                       const int32_t* keep, int carry, float* top_val, int32_t* top_idx, void* stream);
+
+/* ------------------------------------------------------------------------------------------------
  * History attention of the self-attention encoder (SARGCNLayer.calc_result + attention,
  * models/SARGCN.py:25-53; callers models/SARGCN.py:39-62, models/SelfAttentionRGCN.py:88-96).
  * The reference builds a dense (n, T, D) tensor [history ..., current] (zero rows + a -10e9 additive

@@ -117,6 +117,7 @@ class TempLinearProblem(ctypes.Structure):
 
 ASSEMBLE_PIECE = 4096
 SCORE_KINDS = {"distmult": 0, "complex": 1, "transE": 2}
+TOPK_MAX = 256             # include/temp_amd.h: TEMP_TOPK_MAX (the longest answer list temp_filtered_topk keeps)
 
 # name -> (restype, argtypes); mirrors include/temp_amd.h one to one
 _G = ctypes.POINTER(TempGraph)
@@ -233,6 +234,7 @@ SYMBOLS = {
     "temp_subsample_views": (_I, [_I, ctypes.POINTER(TempSubsampleJob), c_vp]),
     "temp_corrupt_sample": (_I, [_I, _I, _I, ctypes.c_uint64, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp]),
     "temp_filtered_rank": (_I, [_I, _I, _I, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp]),
+    "temp_filtered_topk": (_I, [_I, _I, _I, _I, _I, c_vp, c_vp, c_vp, c_vp, _I, c_vp, c_vp, c_vp]),
     "temp_sa_attn_fwd": (_I, [ctypes.POINTER(TempAttn), c_vp, c_vp, c_vp, c_vp]),
     "temp_sa_attn_bwd": (_I, [ctypes.POINTER(TempAttn), c_vp, c_vp, c_vp, c_vp, c_vp, _I, c_vp, c_vp, _I, c_vp, c_vp, _I, c_vp, _I, c_vp, c_vp, c_vp, c_vp]),
     "temp_sa_attn_split_fwd": (_I, [ctypes.POINTER(TempAttn), ctypes.POINTER(TempAttnSplit), c_vp, c_vp, c_vp, c_vp]),

@@ -971,6 +971,44 @@ class HipBackend:
         _lib.check(rc, "temp_filtered_rank")
         return ranks.long()
 
+    def filtered_topk(self, scores, k, filt_ptr=None, filt_ids=None, keep=None, col0=0, n=None, carry=None):
+        """-> (top_val [P, k] float32, top_idx [P, k] int64): the best k admissible entities of every row of scores [P, ld] (see
+        temp_filtered_topk).  Column j < n (default: every column) is entity col0 + j.  `scores` may be a column slice of a wider
+        row-major matrix (row stride % 4 == 0, first element 16-byte aligned).  `carry` = the pair an earlier call returned over
+        other entities: the result is then the selection over both ranges."""
+        if scores.dim() != 2 or not scores.is_cuda or scores.dtype != torch.float32:
+            raise _lib.TempAmdError("filtered_topk: scores must be a float32 [P, ld] GPU matrix")
+        scores = scores.detach()
+        P, width = scores.shape
+        n = width if n is None else int(n)
+        ld = scores.stride(0) if P > 1 else max(scores.stride(0), width)
+        if scores.stride(1) != 1 and width > 1:
+            raise ValueError("filtered_topk: the score rows must be contiguous")
+        if not 1 <= k <= _lib.TOPK_MAX:
+            raise ValueError("filtered_topk: k must lie in [1, %d]" % _lib.TOPK_MAX)
+        if not 0 < n <= width or col0 < 0:
+            raise ValueError("filtered_topk: n must lie in (0, row length] and col0 must not be negative")
+        if ld % 4 or scores.data_ptr() % 16:
+            raise ValueError("filtered_topk: the row stride must be a multiple of 4 and the first score 16-byte aligned")
+        if filt_ptr is not None:
+            filt_ptr, filt_ids = _i32(filt_ptr, "filt_ptr"), _i32(filt_ids, "filt_ids")
+            if filt_ptr.shape[0] != P + 1:
+                raise ValueError("filtered_topk: filt_ptr must have one entry per row plus one")
+        keep = _i32(keep, "keep")
+        if keep is not None and keep.shape[0] != P:
+            raise ValueError("filtered_topk: keep must have one entry per row")
+        if carry is None:
+            top_val = torch.empty(P, k, dtype=torch.float32, device=scores.device)
+            top_idx = torch.empty(P, k, dtype=torch.int32, device=scores.device)
+        else:
+            top_val, top_idx = _f32(carry[0], "carry values").clone(), carry[1].to(dtype=torch.int32, copy=True).contiguous()
+            if top_val.shape != (P, k) or top_idx.shape != (P, k):
+                raise ValueError("filtered_topk: carry must be the (top_val, top_idx) [P, k] of an earlier call")
+        rc = self.lib.temp_filtered_topk(P, n, ld, int(k), int(col0), _ptr(scores), _ptr(filt_ptr), _ptr(filt_ids), _ptr(keep),
+                                         int(carry is not None), _ptr(top_val), _ptr(top_idx), _stream())
+        _lib.check(rc, "temp_filtered_topk")
+        return top_val, top_idx.long()
+
     # ---- history attention (self-attention encoder) ------------------------------------------------------
     def _attn_desc(self, qkv, kv_hist, idx, decay):
         n, D3 = qkv.shape

@@ -375,6 +375,17 @@ class DynamicRGCN(TKG_Module):
         gid = torch.from_numpy(g.gids).to(dev)
         return all_embeds.index_copy(0, gid, convoluted_embeds)
 
+    def all_entity_tables(self, t_list):
+        """TKG_Module.predict's hook: the embedding half of evaluate() -- the window on the full train graphs at test_seq_len, every
+        window's all-entity matrix assembled over the target graph the encoder ran on."""
+        wb = self.prepare(t_list, self.test_seq_len, train=False)
+        out, hist = self.run(wb)
+        per_graph = list(out.split(wb.target.sizes))
+        all_b = self.all_embeds_batched(wb, out, hist) if self._fused_all_entity_ok(wb) else None
+        for i, ent_embed in enumerate(per_graph):
+            t = wb.rows[i][-1]
+            yield t, (all_b[i] if all_b is not None else self.get_all_embeds_Gt(ent_embed, wb.graphs[i], t, wb.plan, i, hist))
+
     def evaluate(self, t_list, val=True):
         """models/DynamicRGCN.py:118-144,196-220: window encoder on the full train graphs, then filtered
         ranks of the valid (or test) triples of every target timestamp + their classification loss.

@@ -12,12 +12,19 @@ Restructured for the device:
   * TransE is not bilinear: its P x N matrix of negative L1 distances is one register-tiled pass (`temp_l1_scores`) over the
     translation query, in place of the (100, N, D) broadcast per chunk of 100 triples;
   * the rank is the target's position in a stable descending order, computed by counting
-    (`temp_filtered_rank`) instead of sorting."""
+    (`temp_filtered_rank`) instead of sorting;
+  * the ANSWERS of a query (s, r, ?, t) / (?, r, o, t) -- `topk_single_graph`, which the reference has no counterpart of -- are
+    one selection pass over the same score rows (`temp_filtered_topk`): filter, total order (score, then entity id) and a
+    list that is carried across column panels, so the Q x N matrix never has to exist at once."""
 import numpy as np
 import torch
 
+from . import _lib
 from . import scores as S
 from .backend import get_backend
+
+# topk_single_graph scores all N entities in one matrix while Q * ld * 4 bytes stay under this; above it, panels of this many bytes
+TOPK_PANEL_BYTES = 256 << 20
 
 
 def _l1_route(name, be, d):
@@ -30,12 +37,41 @@ def _translation_query(known, r, mode):
     return (known + r if mode == "tail" else known - r).contiguous()
 
 
+def topk_composite(scores, k, filt_ptr=None, filt_ids=None, keep=None, col0=0, n=None, carry=None):
+    """The contract of `temp_filtered_topk` in plain torch: mask to -inf, stable descending sort.  -> (top_val [P, k] in the dtype
+    of `scores`, top_idx [P, k] int64).  The reference of the kernel's tests, and the route of a backend without `filtered_topk` or
+    of a k above TEMP_TOPK_MAX."""
+    s = scores.detach()
+    n = s.shape[1] if n is None else int(n)
+    s = s[:, :n].clone()
+    P, dev = s.shape[0], s.device
+    if filt_ptr is not None and filt_ids is not None and filt_ids.numel():
+        ptr, fid = filt_ptr.long(), filt_ids.long()
+        rows = torch.repeat_interleave(torch.arange(P, device=dev), ptr[1:] - ptr[:-1])
+        m = (fid >= col0) & (fid < col0 + n)
+        if keep is not None:
+            m &= fid != keep.long()[rows]
+        s[rows[m], fid[m] - col0] = float("-inf")
+    idx = (col0 + torch.arange(n, device=dev)).view(1, n).expand(P, n)
+    if carry is not None:                                   # ids no longer ascend along the row: order by id first, then by score
+        s, idx = torch.cat([carry[0].to(s.dtype), s], dim=1), torch.cat([carry[1].long(), idx], dim=1)
+        idx, o = torch.sort(idx, dim=1, stable=True)
+        s = s.gather(1, o)
+    val, o = torch.sort(s, dim=1, descending=True, stable=True)
+    idx = idx.gather(1, o).masked_fill(val == float("-inf"), -1)
+    if val.shape[1] < k:
+        val = torch.cat([val, val.new_full((P, k - val.shape[1]), float("-inf"))], dim=1)
+        idx = torch.cat([idx, idx.new_full((P, k - idx.shape[1]), -1)], dim=1)
+    return val[:, :k].contiguous(), idx[:, :k].contiguous()
+
+
 class EvaluationFilter:
     def __init__(self, args, calc_score, graph_dict_train, graph_dict_val, graph_dict_test):
         self.args = args
         self.calc_score = calc_score
         self.graph_dicts = (graph_dict_train, graph_dict_val, graph_dict_test)
         self._keys = {}
+        self._global_keys = {}
 
     def _true_keys(self, time, num_ent):
         """Sorted keys (h*R + r)*N + global(t) and (t*R + r)*N + global(h) over the three splits at `time`."""
@@ -48,6 +84,20 @@ class EvaluationFilter:
             tails = np.unique((trip[:, 0] * R + trip[:, 1]) * num_ent + gid[trip[:, 2]])
             heads = np.unique((trip[:, 2] * R + trip[:, 1]) * num_ent + gid[trip[:, 0]])
             k = self._keys[time] = (R, tails, heads)
+        return k
+
+    def _true_keys_global(self, time, num_ent):
+        """_true_keys with the known side in GLOBAL entity ids as well: sorted (global(h)*R + r)*N + global(t) and
+        (global(t)*R + r)*N + global(h) -- what a query that names its entity by global id is looked up in."""
+        k = self._global_keys.get(time)
+        if k is None:
+            trip = [np.stack([g[time].gids[g[time].src], g[time].rel, g[time].gids[g[time].dst]], axis=1).astype(np.int64)
+                    for g in self.graph_dicts if time in g]
+            trip = np.concatenate(trip, axis=0) if trip else np.zeros((0, 3), np.int64)
+            R = int(trip[:, 1].max()) + 1 if trip.shape[0] else 1
+            tails = np.unique((trip[:, 0] * R + trip[:, 1]) * num_ent + trip[:, 2])
+            heads = np.unique((trip[:, 2] * R + trip[:, 1]) * num_ent + trip[:, 0])
+            k = self._global_keys[time] = (R, tails, heads)
         return k
 
     @staticmethod
@@ -126,6 +176,66 @@ class EvaluationFilter:
                     ranks.append(get_backend().filtered_rank(_pad4(score), target[a:b], ptr[a:b + 1] - lo, ids[lo:hi]))
                 out[mode] = torch.cat(ranks)
             return torch.cat([out["head"], out["tail"]])
+
+    def topk_single_graph(self, all_ent_embeds, rel_enc_means, known, rel, mode, time, k, filtered=True, keep=None, panel=None):
+        """The k best answers of Q queries at `time`: (known[i], rel[i], ?) for mode "tail", (?, rel[i], known[i]) for "head".
+        -> (ids [Q, k] int64 global entity ids, scores [Q, k] float32), best first: higher score, then smaller id; rows with fewer
+        than k admissible entities end in (-1, -inf).
+
+        `known` holds GLOBAL entity ids -- their rows are read from `all_ent_embeds` [N, D], which already carries the convolved rows
+        of the active entities -- and `rel` rows of `rel_enc_means`.  filtered: every entity that completes a known triple with
+        (known, rel) at `time` in train + valid + test is left out, except the row's `keep` id (nullable [Q], -1 = none); a known
+        entity or a relation that never occurs at `time` has nothing to leave out.  The scores come from the routes of
+        calc_metrics_single_graph; `panel` (a multiple of 4) scores that many entities at a time and carries the lists, None does so
+        only when the whole [Q, N] matrix would pass TOPK_PANEL_BYTES."""
+        if mode not in ("head", "tail"):
+            raise ValueError("topk_single_graph: mode must be 'head' or 'tail'")
+        with torch.no_grad():
+            dev, (num_ent, d) = all_ent_embeds.device, all_ent_embeds.shape
+            known = torch.as_tensor(known, dtype=torch.int64, device=dev).reshape(-1)
+            rel = torch.as_tensor(rel, dtype=torch.int64, device=dev).reshape(-1)
+            Q = known.shape[0]
+            if Q == 0:
+                return torch.zeros(0, k, dtype=torch.int64, device=dev), torch.zeros(0, k, dtype=torch.float32, device=dev)
+            ptr = ids = None
+            if filtered:
+                R, tails, heads = self._true_keys_global(int(time), num_ent)
+                known_np, rel_np = known.cpu().numpy(), rel.cpu().numpy()
+                prefix = np.where((rel_np >= 0) & (rel_np < R), known_np * R + rel_np, -1)      # a relation unseen at `time`: no key below 0
+                ptr, ids = self.filter_lists(prefix, tails if mode == "tail" else heads, num_ent)
+                ptr, ids = torch.from_numpy(ptr).to(dev), torch.from_numpy(ids).to(dev)
+            if keep is not None:
+                keep = torch.as_tensor(keep, device=dev).to(torch.int32).reshape(-1)
+            be = get_backend()
+            name = getattr(self.args, "score_function", None)
+            kn, r = all_ent_embeds[known], rel_enc_means[rel]
+            fused = name in ("distmult", "complex") and num_ent % 4 == 0 and d % 4 == 0
+            l1 = _l1_route(name, be, d)
+            if fused:
+                q = S.bilinear_query(name, kn, r, mode).contiguous()
+            elif l1:
+                q = _translation_query(kn, r, mode)
+            ld = (num_ent + 3) // 4 * 4
+            if panel is None:
+                panel = ld if Q * ld * 4 <= TOPK_PANEL_BYTES else max(4, TOPK_PANEL_BYTES // (4 * Q) // 4 * 4)
+            if panel <= 0 or panel % 4:
+                raise ValueError("topk_single_graph: panel must be a positive multiple of 4")
+            select = be.filtered_topk if hasattr(be, "filtered_topk") and k <= _lib.TOPK_MAX else topk_composite
+            carry = None
+            for c0 in range(0, num_ent, panel):
+                table = all_ent_embeds[c0:min(num_ent, c0 + panel)].contiguous()
+                if fused:
+                    score = be.linear(q, table, True)
+                elif l1:
+                    score = be.l1_scores(q, table)                       # the pad columns already -inf
+                else:
+                    rows = []
+                    for a in range(0, Q, 100):
+                        rows.append(self.calc_score(kn[a:a + 100], r[a:a + 100], table, mode="tail") if mode == "tail"
+                                    else self.calc_score(table, r[a:a + 100], kn[a:a + 100], mode="head"))
+                    score = _pad4(torch.cat(rows))
+                carry = select(score, k, ptr, ids, keep, col0=c0, n=table.shape[0], carry=carry)
+            return carry[1], carry[0].float()
 
 
 def _w_col(w, P, like):

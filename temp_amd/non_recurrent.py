@@ -52,6 +52,13 @@ class TKG_Non_Recurrent(TKG_Module):
         """The rows of the graph's entities (the reference gathers the parameters and applies the same element-wise map)."""
         return self.get_all_embeds_Gt(t)[self._gids(g)]
 
+    def all_entity_tables(self, t_list):
+        """TKG_Module.predict's hook: all tables from one table_stack call."""
+        ts, N = [int(t) for t in t_list], self.num_ents
+        stack = self.table_stack(self._times(ts))
+        for b, t in enumerate(ts):
+            yield t, stack[b * N:(b + 1) * N]
+
     # -- evaluation (models/TKG_Module.py:253-274) ---------------------------------------------------------------------------
     def evaluate(self, t_list, val=True):
         """Filtered ranks of the valid / test triples + the mean classification loss; all B tables from one table_stack call,

@@ -25,6 +25,10 @@ class _FrequencyGateMixin:
             self.evaluater = cls(self.args, self.calc_score, self.graph_dict_train, self.graph_dict_val, self.graph_dict_test)
         return self.evaluater
 
+    def all_entity_tables(self, t_list):
+        raise NotImplementedError("%s scores against two all-entity tables (local, temporal) mixed by per-triple gates: predict() covers the "
+                                  "single-table models only" % type(self).__name__)
+
     def frequency_tables(self):
         ft = getattr(self, "_freq_tables", None)
         if ft is None:

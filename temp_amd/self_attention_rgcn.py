@@ -225,6 +225,13 @@ class SelfAttentionRGCN(DynamicRGCN):
             loss = loss + self.train_link_prediction_both(ent_embed, triplets, neg_tail, neg_head, labels, all_list[i])
         return loss
 
+    def all_entity_tables(self, t_list):
+        """TKG_Module.predict's hook: the embedding half of evaluate()."""
+        per_graph, wb, tables = self.encode(t_list, self.test_seq_len, train=False)
+        all_list = self.all_embeds_batched(wb, torch.cat(per_graph, dim=0), tables)
+        for i in range(len(per_graph)):
+            yield wb.rows[i][-1], all_list[i]
+
     def evaluate(self, t_list, val=True):
         """models/SelfAttentionRGCN.py:142-180 (Bi: models/BiSelfAttentionRGCN.py:71-95)."""
         from .evaluation import EvaluationFilter

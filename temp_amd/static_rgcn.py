@@ -57,6 +57,13 @@ class StaticRGCN(TKG_Module):
         gid = torch.from_numpy(g.gids).to(self.ent_embeds.device)
         return all_embeds.index_copy(0, gid, convoluted_embeds)
 
+    def all_entity_tables(self, t_list):
+        """TKG_Module.predict's hook: the embedding half of evaluate() -- the full train graphs' rows over the isolated pass."""
+        ts = [int(t) for t in t_list]
+        g_list = [self.graph_dict_train[t] for t in ts]
+        for t, g, ent_embed in zip(ts, g_list, self.get_per_graph_ent_embeds(ts, g_list, val=True)):
+            yield t, self.get_all_embeds_Gt(t, g, ent_embed)
+
     def evaluate(self, t_list, val=True):
         """baselines/StaticRGCN.py:20-34,91-113: full train graphs -> embeddings, filtered ranks of the
         valid/test triples + classification loss."""

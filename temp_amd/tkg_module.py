@@ -224,6 +224,40 @@ class TKG_Module(nn.Module):
         score = self.calc_score(ent_embed[triplets[:, 0]], rel_embeds[triplets[:, 1]], ent_embed[triplets[:, 2]])
         return F.binary_cross_entropy_with_logits(score, labels)
 
+    # -- prediction: the answers of a query (no counterpart in the reference, which only ranks known test triples) -----------------
+    predict_batch = 8           # timestamps encoded per all_entity_tables call
+
+    def all_entity_tables(self, t_list):
+        """Per-family hook of `predict`: yields (t, table [N_ents, D]) for every timestamp of `t_list` -- the all-entity matrix the
+        family's evaluate() ranks against."""
+        raise NotImplementedError("%s has no single all-entity table per timestamp: predict() is not available" % type(self).__name__)
+
+    def predict(self, queries, mode="tail", k=10, filtered=True):
+        """The k best answers of every query.  queries: int [Q, 3] rows (timestamp, known GLOBAL entity id, relation row of
+        rel_embeds); mode "tail" answers (known, relation, ?), "head" (?, relation, known).  -> (ids [Q, k] int64 global entity
+        ids, scores [Q, k] float32), rows in query order, best first (higher score, then smaller id; see
+        EvaluationFilter.topk_single_graph).  filtered: entities that already complete a train / valid / test triple with the
+        query at its timestamp are left out."""
+        from .evaluation import EvaluationFilter
+        if mode not in ("head", "tail"):
+            raise ValueError("predict: mode must be 'head' or 'tail'")
+        q = queries.detach().cpu().numpy() if torch.is_tensor(queries) else np.asarray(queries)
+        q = q.astype(np.int64).reshape(-1, 3)
+        if not hasattr(self, "evaluater"):
+            self.evaluater = EvaluationFilter(self.args, self.calc_score, self.graph_dict_train, self.graph_dict_val, self.graph_dict_test)
+        dev = self.rel_embeds.device
+        ids = torch.full((q.shape[0], k), -1, dtype=torch.int64, device=dev)
+        vals = torch.full((q.shape[0], k), float("-inf"), dtype=torch.float32, device=dev)
+        ts = sorted(set(int(t) for t in q[:, 0]))
+        with torch.no_grad():
+            for a in range(0, len(ts), self.predict_batch):
+                for t, table in self.all_entity_tables(ts[a:a + self.predict_batch]):
+                    rows = np.nonzero(q[:, 0] == int(t))[0]
+                    i, v = self.evaluater.topk_single_graph(table, self.rel_embeds, q[rows, 1], q[rows, 2], mode, int(t), k, filtered)
+                    sel = torch.from_numpy(rows).to(dev)
+                    ids[sel], vals[sel] = i, v
+        return ids, vals
+
     # -- window construction (models/TKG_Module.py:232-250) --------------------------------------------
     def get_batch_graph_list(self, t_list, seq_len, graph_dict):
         from .window import window_times
