@@ -986,6 +986,49 @@ int temp_filtered_topk(int P, int N, int ld, int k, int col0, const float* score
                        const int32_t* keep, int carry, float* top_val, int32_t* top_idx, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * Clipped Adam: the reference trainer's optimizer step, Trainer(gradient_clip_val) -> clip_grad_norm_(parameters, max_norm)
+ * (main.py:128-129, utils/args.py:26) followed by Adam(lr, weight_decay = 1e-4) (models/TKG_Module.py:154-160), as one
+ * deterministic multi-tensor pass over a DEVICE table with one row per tensor that has a gradient:
+ *   1. norm = sqrt(sum g^2) over every row                                    (temp_grad_norm_clip)
+ *   2. r = max_norm / (norm + 1e-6);  coef = r if (r < 1 or r != r) else 1     (a NaN passes, as through torch's clamp)
+ *   3. per element, in place and in fp32, with the row's scalars               (temp_adam_clip_step)
+ *        g' = coef g + weight_decay p
+ *        m += one_minus_beta1 (g' - m)
+ *        v  = beta2 v + one_minus_beta2 g' g'
+ *        p -= step_size m / (sqrt(v) inv_bias2_sqrt + eps)
+ *      step_size = lr / (1 - beta1^t), inv_bias2_sqrt = 1 / sqrt(1 - beta2^t): the caller computes every scalar in double from its
+ *      host-side step count t and rounds once.
+ * Non-finite gradients get no special case: one inf element gives norm = inf and coef = 0 (that element becomes NaN, every other
+ * one takes a decay-only step); one NaN element gives coef = NaN and NaN in every updated element.
+ * A CHUNK is TEMP_ADAM_CHUNK consecutive elements of one tensor (its last chunk may be short) and is owned by one workgroup;
+ * chunks are numbered through the table in row order: first_chunk[0] = 0, first_chunk[t + 1] = first_chunk[t] +
+ * ceil(n[t] / TEMP_ADAM_CHUNK), n_chunks = the total.  The table lives in device memory; the library cannot check its contents:
+ * the pointers must cover n elements each and the chunk numbering must be exact.  p / g / m / v need 4-byte alignment only; a row
+ * whose four pointers are 16-byte aligned moves float4s.  Rows must not overlap each other.
+ *
+ * temp_grad_norm_clip: norm_coef[0] = (float) norm, norm_coef[1] = (float) coef, both from double.  Every chunk stores one
+ * double sum of squares to the workspace (temp_grad_norm_workspace(n_chunks) bytes, 8-byte aligned) and one workgroup adds them:
+ * accumulation in double from the lane up, every order fixed by the table, no atomics -- bit-repeatable.  Two launches (one when
+ * n_chunks == 0: norm 0, coef 1).  g is read with the default cache policy: the update reads it again.
+ * temp_adam_clip_step: one launch; norm_coef as written by temp_grad_norm_clip on the same stream, or NULL for coef = 1 (no
+ * clipping).  n_chunks == 0 succeeds without a launch.
+ * Negative counts, a NULL table with n_chunks > 0, a NULL norm_coef in temp_grad_norm_clip: TEMP_E_BADARG; a missing or short
+ * workspace: TEMP_E_WORKSPACE; nothing is launched in either case.
+ * Neither call allocates, copies or synchronises.
+ * ---------------------------------------------------------------------------------------------- */
+#define TEMP_ADAM_CHUNK 4096
+typedef struct TempAdamTensor {
+  float* p; const float* g; float* m; float* v;     /* parameter, gradient, exp_avg, exp_avg_sq: n floats each */
+  int64_t n;
+  float step_size, inv_bias2_sqrt, one_minus_beta1, beta2, one_minus_beta2, eps, weight_decay;
+  int32_t first_chunk;
+} TempAdamTensor;                                   /* 72 bytes */
+size_t temp_grad_norm_workspace(int n_chunks);
+int temp_grad_norm_clip(int n_tensors, int n_chunks, const TempAdamTensor* table, double max_norm, void* ws, size_t ws_bytes,
+                        float* norm_coef, void* stream);
+int temp_adam_clip_step(int n_tensors, int n_chunks, const TempAdamTensor* table, const float* norm_coef, void* stream);
+
+/* ------------------------------------------------------------------------------------------------
  * History attention of the self-attention encoder (SARGCNLayer.calc_result + attention,
  * models/SARGCN.py:25-53; callers models/SARGCN.py:39-62, models/SelfAttentionRGCN.py:88-96).
  * The reference builds a dense (n, T, D) tensor [history ..., current] (zero rows + a -10e9 additive

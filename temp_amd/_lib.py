@@ -115,8 +115,15 @@ class TempLinearProblem(ctypes.Structure):
     _fields_ = [("M", ctypes.c_int32), ("A", c_vp), ("B", c_vp), ("C", c_vp)]
 
 
+class TempAdamTensor(ctypes.Structure):
+    _fields_ = [("p", c_vp), ("g", c_vp), ("m", c_vp), ("v", c_vp), ("n", ctypes.c_int64)] + \
+               [(n, ctypes.c_float) for n in ("step_size", "inv_bias2_sqrt", "one_minus_beta1", "beta2", "one_minus_beta2", "eps", "weight_decay")] + \
+               [("first_chunk", ctypes.c_int32)]
+
+
 ASSEMBLE_PIECE = 4096
 SCORE_KINDS = {"distmult": 0, "complex": 1, "transE": 2}
+ADAM_CHUNK = 4096         # include/temp_amd.h: TEMP_ADAM_CHUNK (elements of one tensor that one workgroup of the optimizer passes owns)
 TOPK_MAX = 256             # include/temp_amd.h: TEMP_TOPK_MAX (the longest answer list temp_filtered_topk keeps)
 
 # name -> (restype, argtypes); mirrors include/temp_amd.h one to one
@@ -235,6 +242,9 @@ SYMBOLS = {
     "temp_corrupt_sample": (_I, [_I, _I, _I, ctypes.c_uint64, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp]),
     "temp_filtered_rank": (_I, [_I, _I, _I, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp]),
     "temp_filtered_topk": (_I, [_I, _I, _I, _I, _I, c_vp, c_vp, c_vp, c_vp, _I, c_vp, c_vp, c_vp]),
+    "temp_grad_norm_workspace": (_SZ, [_I]),
+    "temp_grad_norm_clip": (_I, [_I, _I, c_vp, ctypes.c_double, c_vp, _SZ, c_vp, c_vp]),
+    "temp_adam_clip_step": (_I, [_I, _I, c_vp, c_vp, c_vp]),
     "temp_sa_attn_fwd": (_I, [ctypes.POINTER(TempAttn), c_vp, c_vp, c_vp, c_vp]),
     "temp_sa_attn_bwd": (_I, [ctypes.POINTER(TempAttn), c_vp, c_vp, c_vp, c_vp, c_vp, _I, c_vp, c_vp, _I, c_vp, c_vp, _I, c_vp, _I, c_vp, c_vp, c_vp, c_vp]),
     "temp_sa_attn_split_fwd": (_I, [ctypes.POINTER(TempAttn), ctypes.POINTER(TempAttnSplit), c_vp, c_vp, c_vp, c_vp]),

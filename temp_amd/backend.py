@@ -1009,6 +1009,47 @@ class HipBackend:
         _lib.check(rc, "temp_filtered_topk")
         return top_val, top_idx.long()
 
+    # ---- optimizer (clipped Adam over a device table of tensors) ----------------------------------------------
+    @staticmethod
+    def _adam_table(table, n_tensors, n_chunks, what):
+        if not torch.is_tensor(table) or not table.is_cuda or table.dtype != torch.uint8 or not table.is_contiguous():
+            raise _lib.TempAmdError("%s: the table must be a contiguous uint8 GPU tensor of TempAdamTensor records" % what)
+        if n_tensors < 0 or n_chunks < 0 or (n_chunks > 0 and n_tensors == 0):
+            raise ValueError("%s: tensor and chunk counts must not be negative, and chunks need tensors" % what)
+        if table.numel() < n_tensors * ctypes.sizeof(_lib.TempAdamTensor) or table.data_ptr() % 8:
+            raise ValueError("%s: the table must hold one 72-byte record per tensor at an 8-byte aligned address" % what)
+
+    def grad_norm_workspace(self, n_chunks):
+        return int(self.lib.temp_grad_norm_workspace(int(n_chunks)))
+
+    def grad_norm_clip(self, table, n_tensors, n_chunks, max_norm, ws, norm_coef):
+        """norm_coef[0:2] (float32, device) = (sqrt(sum g^2) over the table's tensors, the clip coefficient for max_norm) -- see
+        temp_grad_norm_clip.  table: uint8 device tensor of TempAdamTensor records (one per tensor, chunks numbered in row order),
+        ws: uint8 device workspace of grad_norm_workspace(n_chunks) bytes.  Nothing is allocated and nothing waits."""
+        n_tensors, n_chunks = int(n_tensors), int(n_chunks)
+        self._adam_table(table, n_tensors, n_chunks, "grad_norm_clip")
+        if not torch.is_tensor(norm_coef) or not norm_coef.is_cuda or norm_coef.dtype != torch.float32 or norm_coef.numel() < 2 \
+                or not norm_coef.is_contiguous():
+            raise _lib.TempAmdError("grad_norm_clip: norm_coef must be a contiguous float32 GPU tensor of two elements")
+        if not torch.is_tensor(ws) or not ws.is_cuda or ws.dtype != torch.uint8 or ws.numel() < self.grad_norm_workspace(n_chunks):
+            raise ValueError("grad_norm_clip: the workspace must be a uint8 GPU tensor of grad_norm_workspace(n_chunks) bytes")
+        if not float(max_norm) > 0.0:
+            raise ValueError("grad_norm_clip: max_norm must be positive")
+        rc = self.lib.temp_grad_norm_clip(n_tensors, n_chunks, _ptr(table), float(max_norm), _ptr(ws), ws.numel(), _ptr(norm_coef), _stream())
+        _lib.check(rc, "temp_grad_norm_clip")
+        return norm_coef
+
+    def adam_clip_step(self, table, n_tensors, n_chunks, norm_coef=None):
+        """One in-place Adam step of every tensor of the table, the gradients scaled by norm_coef[1] (None: not scaled) -- see
+        temp_adam_clip_step."""
+        n_tensors, n_chunks = int(n_tensors), int(n_chunks)
+        self._adam_table(table, n_tensors, n_chunks, "adam_clip_step")
+        if norm_coef is not None and (not norm_coef.is_cuda or norm_coef.dtype != torch.float32 or norm_coef.numel() < 2
+                                      or not norm_coef.is_contiguous()):
+            raise _lib.TempAmdError("adam_clip_step: norm_coef must be a contiguous float32 GPU tensor of two elements")
+        rc = self.lib.temp_adam_clip_step(n_tensors, n_chunks, _ptr(table), _ptr(norm_coef), _stream())
+        _lib.check(rc, "temp_adam_clip_step")
+
     # ---- history attention (self-attention encoder) ------------------------------------------------------
     def _attn_desc(self, qkv, kv_hist, idx, decay):
         n, D3 = qkv.shape

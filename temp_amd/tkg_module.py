@@ -75,6 +75,18 @@ class TKG_Module(nn.Module):
         fused = bool(params) and all(p.is_cuda and p.dtype == torch.float32 for p in params)
         return torch.optim.Adam(params, lr=self.args.lr, weight_decay=0.0001, fused=fused)
 
+    def configure_clipped_optimizer(self, max_norm=None):
+        """The reference's whole optimizer step as one object: main.py:128-129 trains under Trainer(gradient_clip_val=
+        args.gradient_clip_val) (default 1.0, utils/args.py:26), i.e. clip_grad_norm_(parameters, gradient_clip_val) before every
+        step of configure_optimizers()'s Adam.  -> optim.ClippedAdam(lr, weight_decay = 1e-4, max_norm).  `max_norm` defaults to
+        args.gradient_clip_val (1.0 when the attribute is missing); a value <= 0 means no clipping -- the trainer's rule, stated here
+        because the trainer is not part of this package."""
+        from .optim import ClippedAdam
+        if max_norm is None:
+            max_norm = getattr(self.args, "gradient_clip_val", 1.0)
+        max_norm = float(max_norm) if max_norm is not None and float(max_norm) > 0.0 else None
+        return ClippedAdam(self.parameters(), lr=self.args.lr, weight_decay=0.0001, max_norm=max_norm)
+
     # -- loss (models/TKG_Module.py:202-221) ----------------------------------------------------------
     def train_link_prediction(self, ent_embed, triplets, neg_samples, labels, all_embeds_g, corrupt_tail=True):
         """models/TKG_Module.py:202-213.  DistMult / ComplEx take the fused path: ONE GEMM of the
