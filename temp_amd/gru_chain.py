@@ -297,109 +297,214 @@ class GruProgram:
         return t
 
 
+def _require_chain_kernels(what, tabs, usable, advice=""):
+    """A learnable decay and a state offset run on the persistent chain kernels only: anything those refuse raises."""
+    if tabs is None or not usable:
+        raise _lib.TempAmdError("gru_chain: a %s runs on the persistent chain kernels only, and %s" % (
+            what, "this backend / width / cell has none that take it" if not usable else
+            "they refuse this program (not a set of one-GRU chains, a panel longer than %d steps, or more than %d consumed "
+            "instances): use the per-position loop%s" % (_lib.CHAIN_MAX_STEPS, _lib.CHAIN_MAX_UP, advice)))
+
+
+def _group_rows(groups):
+    """-> (the slice of x rows, the slice of chain rows) of every group."""
+    return [slice(g["x0"], g["x1"]) for g in groups], [slice(g["h0"], g["h1"]) for g in groups]
+
+
+def _input_gates(be, prog, x_all, W, variant, fused, share, x_keys):
+    """gi = x . W_ih^T + b_ih -> (gi, gi_index).  gi_index: the gi row of every chain row where the gates are computed once per distinct
+    x row (`share`), else None (gi row = chain row).  (None, None) on the fused route: the chain forward computes the gates itself."""
+    if fused:
+        return None, None
+    groups, (xsl, hsl) = prog.groups, _group_rows(prog.groups)
+    xs, w_ih, b_ih = [x_all[a] for a in xsl], [W[g["rnn"]][0] for g in groups], [W[g["rnn"]][2] for g in groups]
+    gi = torch.empty(prog.n_total if share is None else share["rows"], W[0][0].shape[0], dtype=torch.float32, device=x_all.device)
+    kw = dict(x_keys=[x_keys[0][a] for a in xsl]) if x_keys is not None else {}
+    if share is not None:
+        cut = share["g0"] + [share["rows"]]
+        be.gru_input_gates_multi(xs, w_ih, b_ih, variant, [gi[cut[i]:cut[i + 1]] for i in range(len(groups))], x_idx=share["rep"], **kw)
+        return gi, share["gi_index"]
+    if len(groups) > 1:                                        # both directions' input gates in one launch
+        be.gru_input_gates_multi(xs, w_ih, b_ih, variant, [gi[b] for b in hsl], **kw)
+    else:
+        for x, w, b, rows in zip(xs, w_ih, b_ih, hsl):
+            be.gru_input_gates(x, w, b, variant, gi[rows])
+    return gi, None
+
+
+def _chain_forward(be, prog, tabs, x_all, gi, gi_index, W, lam, variant, fused, decay, offset, H, saved):
+    """Pack the recurrent weights and run ALL positions in one launch -> the packs (the chain backward takes them as they are)."""
+    w_ih, w_hh, b_ih, b_hh = ([w[k] for w in W] for k in range(4))
+    if fused:
+        packs = be.gru_chain_pack_x_multi(w_hh, w_ih)
+        be.gru_chain_fwd_x(tabs, x_all, prog.x_index(x_all.device), lam, variant, packs, b_hh, b_ih, H, saved, **decay)
+        return packs
+    if offset:                                                 # packed for the kernels an offset chain runs on, whatever the options select
+        packs = be.gru_chain_pack_multi(w_hh, layout=be.gru_chain_offset_layout(x_all.shape[1]))
+    else:
+        packs = be.gru_chain_pack_multi(w_hh) if hasattr(be, "gru_chain_pack_multi") else [be.gru_chain_pack(w) for w in w_hh]
+    be.gru_chain_fwd(tabs, gi, lam, variant, packs, b_hh, H, saved, gi_index=gi_index, **decay, **offset)
+    return packs
+
+
+def _position_forward(be, prog, gi, W, lam, variant, H, saved):
+    """One launch per level of the program (the instances at the same distance from their chain start); no packs: -> None."""
+    tens = prog.upload(H.device)
+    _, none_idx = prog.constants(H.device, H.shape[1])
+    for level in prog.levels:
+        cells = []
+        for i in level:
+            it = prog.inst[i]
+            p = prog.inst[it.prev] if it.prev >= 0 else None      # None = no history yet: every previous state is zero (pointwise cell)
+            cells.append(dict(gi=gi[it.h0:it.h0 + it.n], prev=H[p.h0:p.h0 + p.n] if p is not None else None,
+                              prev_idx=tens[i][0] if p is not None else none_idx[:it.n], dt=tens[i][2], w_hh=W[it.rnn][1], b_hh=W[it.rnn][3],
+                              h_out=H[it.h0:it.h0 + it.n], row0=it.h0))
+        be.gru_cell_fwd_multi(cells, lam, variant, saved)
+
+
+def _gate_grads_g4(be, ctx, saved, ups, W, decay, offset):
+    """The chain backward with its gate gradients written ONCE, g4 = [dr | dz | dn_i | dn_h] (two thirds of dgh repeat dgi) -> (g4, keys).
+    keys (f16 arithmetic): the magnitude keys of g4 -- per row, per GRU and column -- that the weight-gradient and d_x products split it
+    with (integer maxima, so bit-repeatable), or None.  An offset chain hands out none: saved[4] = dec . s_prev is not bounded by the
+    keyed products' constant state scale."""
+    N, d, dev = saved.shape[1], saved.shape[2], saved.device
+    g4 = torch.empty(N, 4 * d, dtype=torch.float32, device=dev)
+    keys = None
+    if KEYED_GRADS and not offset and hasattr(be, "gru_chain_keys_supported") and be.gru_chain_keys_supported(d):
+        keys = (torch.empty(N, dtype=torch.int32, device=dev), torch.empty(ctx.n_rnn + ctx.tabs["n_panels"], 4 * d, dtype=torch.int32, device=dev))
+    be.gru_chain_bwd_g4(ctx.tabs, saved, ups, ctx.lam, ctx.variant, ctx.packs, [w[3] for w in W], g4,
+                        **({"keys": keys} if keys is not None else {}), **decay, **offset)
+    return g4, keys
+
+
+def _gate_grads_chain(be, ctx, saved, ups, W, decay, offset, dgi, dgh):
+    """The chain backward writing the two matrices dgi [N, G] and dgh [N, 3d]."""
+    be.gru_chain_bwd(ctx.tabs, saved, ups, ctx.lam, ctx.variant, ctx.packs, [w[3] for w in W], dgi, dgh, **decay, **offset)
+
+
+def _gate_grads_positions(be, ctx, saved, ups, W, dgi, dgh):
+    """dgi and dgh with one launch per level, last level first; d_prev carries the state gradients from position to position."""
+    prog, dev = ctx.prog, saved.device
+    tens = prog.upload(dev)
+    decv = torch.empty(prog.n_total, dtype=torch.float32, device=dev)
+    d_prev = torch.empty(prog.n_total, saved.shape[2], dtype=torch.float32, device=dev)
+    given = dict(zip(ctx.want, ups)) if ctx.want is not None else None
+    for level in reversed(prog.levels):
+        cells = []
+        for i in level:
+            it = prog.inst[i]
+            nxt = prog.inst[it.next] if (it.next >= 0 and prog.inst[it.next].n > 0) else None
+            sl = slice(it.h0, it.h0 + it.n)
+            cells.append(dict(row0=it.h0, n=it.n, dh_up=ups[0][sl] if given is None else given.get(i),
+                              d_prev_next=d_prev[nxt.h0:nxt.h0 + nxt.n] if nxt is not None else None, next_idx=tens[i][1] if nxt is not None else None,
+                              dt=tens[i][2], w_hh=W[it.rnn][1], dgi=dgi[sl], dgh=dgh[sl], decv=decv[sl], d_prev=d_prev[sl], no_prev=it.prev < 0))
+        be.gru_cell_bwd_multi(cells, ctx.lam, ctx.variant, saved)
+
+
+# the weight-gradient strategies: each -> (d_w_ih, d_w_hh, d_b_ih, d_b_hh) per group, with the d_x of the group's rows written to d_x_all
+def _weight_grads_g4(be, ctx, x_all, saved, g4, keys, W, d_x_all):
+    """ONE launch for all products, from g4 (temp_gru_grads_g4; on the f16 pipe where the chain backward handed out keys)."""
+    groups, (xsl, hsl) = ctx.prog.groups, _group_rows(ctx.prog.groups)
+    kw = dict(row_keys=[keys[0][b] for b in hsl], col_keys=[keys[1][g["rnn"]] for g in groups]) if keys is not None else {}
+    if keys is not None and ctx.x_keys is not None:
+        kw["x_col_keys"] = [ctx.x_keys[1]] * len(groups)       # (a bound over ALL rows of x_all bounds every group's rows)
+    return be.gru_grads_g4([x_all[a] for a in xsl], [saved[4, b] for b in hsl], [g4[b] for b in hsl], [W[g["rnn"]][0] for g in groups],
+                           [d_x_all[a] for a in xsl], **kw)
+
+
+def _weight_grads_multi(be, ctx, x_all, saved, dgi, dgh, W, d_x_all):
+    """ONE product launch, ONE reduction and ONE d_x launch from dgi and dgh; None (nothing launched): a shape left to the per-GRU call."""
+    xsl, hsl = _group_rows(ctx.prog.groups)
+    return be.gru_weight_grads_multi([x_all[a] for a in xsl], [saved[4, b] for b in hsl], [dgi[b] for b in hsl], [dgh[b] for b in hsl],
+                                     [W[g["rnn"]][0] for g in ctx.prog.groups], ctx.variant, [d_x_all[a] for a in xsl])
+
+
+def _weight_grads_per_group(be, ctx, x_all, saved, dgi, dgh, W, zero_state, d_x_all):
+    """Every group with launches of its own (temp_gru_weight_grads).  Groups may share x rows (the two centre cells of a bi-directional
+    window): the first one writes their d_x, a later one adds to it."""
+    written, out = np.zeros(x_all.shape[0], dtype=bool), []
+    for g, zero, xs, hs in zip(ctx.prog.groups, zero_state, *_group_rows(ctx.prog.groups)):
+        first = not written[xs].any()
+        assert first or written[xs].all()
+        tgt = d_x_all[xs] if first else torch.empty_like(d_x_all[xs])
+        out.append(be.gru_weight_grads(x_all[xs], None if zero else saved[4, hs], dgi[hs], dgh[hs], W[g["rnn"]][0], ctx.variant, tgt))
+        if not first:
+            d_x_all[xs] += tgt
+        written[xs] = True
+    return out
+
+
+def _scatter_grads(ctx, per_group, d_x_all):
+    """Per-group results -> the 4 * n_rnn gradients in weight order, the groups of one GRU summed; x rows that no group reads get d_x = 0."""
+    grads, covered = [None] * (4 * ctx.n_rnn), np.zeros(d_x_all.shape[0], dtype=bool)
+    for g, gw in zip(ctx.prog.groups, per_group):
+        covered[g["x0"]:g["x1"]] = True
+        for k in range(4):
+            j = 4 * g["rnn"] + k
+            grads[j] = gw[k] if grads[j] is None else grads[j] + gw[k]
+    if not covered.all():
+        d_x_all[torch.from_numpy(~covered).to(d_x_all.device)] = 0
+    return grads
+
+
+def _backward_result(be, ctx, d_x_all, grads, decay, offset):
+    """The gradient of every input of _GruChainFn.forward, in its order."""
+    d_dec, d_off = (None, None), (None, None, None)
+    if decay:        # d_arg = dL / d(w dt + b) per row, reduced to (d_w, d_b) per GRU [n_rnn, 2]: all GRUs share the one Linear
+        d_wb = be.gru_chain_decay_reduce(ctx.tabs, d_x_all.shape[1], ctx.variant, decay["d_arg"], ctx.n_rnn)
+        d_dec = (d_wb[:, 0].sum().reshape(1, 1), d_wb[:, 1].sum().reshape(1))
+    if offset:       # d_state = the gradient reaching every row's state: the table's gradient is the adjoint of the row gather table[index]
+        seg_ptr, order = ctx.off_inverse             # applied to it (a segment sum over the static inverse: no atomics)
+        d_off = (be.segment_sum_rows(offset["d_state"], seg_ptr, order, ctx.off_rows), None, None)
+    return (d_x_all, None, None, None, None, None, None) + d_dec + d_off + tuple(grads)
+
+
 class _GruChainFn(torch.autograd.Function):
+    """forward() decides the route once and keeps it on ctx as plain values: tabs (the chain kernels' tables; None = the per-position
+    launches), fused (the chain forward reads x: no gi), share (input gates once per distinct x row) and the decay / offset keyword dicts,
+    which reach the backend only when present (one without them never sees the keywords).  W = [(w_ih, w_hh, b_ih, b_hh)] per GRU."""
+
     @staticmethod
     def forward(ctx, x_all, prog, lam, variant, n_rnn, want, x_keys, dec_w, dec_b, off_table, off_index, off_inverse, *weights):
         be = get_backend()
-        dev = x_all.device
-        d = x_all.shape[1]
-        G = weights[0].shape[0]                      # 3d (torch) or d (type-1)
-        N = prog.n_total
+        dev, d, N = x_all.device, x_all.shape[1], prog.n_total
         x_all = x_all.detach().contiguous()
-        W = [tuple(w.detach().contiguous() for w in weights[4 * r:4 * r + 4]) for r in range(n_rnn)]   # (w_ih, w_hh, b_ih, b_hh)
+        W = [tuple(w.detach().contiguous() for w in weights[4 * r:4 * r + 4]) for r in range(n_rnn)]
         # persistent chain kernels (one launch for ALL positions) when the backend has them and the program is a set of chains
-        tabs = None
-        if CHAIN_KERNELS and hasattr(be, "gru_chain_fwd") and n_rnn <= _lib.CHAIN_MAX_RNN and be.gru_chain_supported(d):
-            tabs = prog.chain_tables(dev, want)
+        tabs = prog.chain_tables(dev, want) if chain_kernels_usable(d, n_rnn) else None
         # learnable decay (dec_w, dec_b = the layer's Linear(1, 1)): the chain kernels read {w, b} from device memory -- no host read
-        dk = {}
+        decay = {}
         if dec_w is not None:
-            if tabs is None or not chain_decay_usable(d, variant, n_rnn):
-                raise _lib.TempAmdError("gru_chain: a learnable decay runs on the persistent chain kernels only, and %s" % (
-                    "this backend / width / cell has none that take it" if not chain_decay_usable(d, variant, n_rnn) else
-                    "they refuse this program (not a set of one-GRU chains, a panel longer than %d steps, or more than %d consumed "
-                    "instances): use the per-position loop (run_rnn with decay_spec())" % (_lib.CHAIN_MAX_STEPS, _lib.CHAIN_MAX_UP)))
-            dk = dict(decay=torch.cat([dec_w.detach().reshape(1), dec_b.detach().reshape(1)]).to(torch.float32))
-        ctx.decay = dk
+            _require_chain_kernels("learnable decay", tabs, chain_decay_usable(d, variant, n_rnn), " (run_rnn with decay_spec())")
+            decay = dict(decay=torch.cat([dec_w.detach().reshape(1), dec_b.detach().reshape(1)]).to(torch.float32))
         # state offset (off_table [T, d], off_index int32 [n_total], -1 = none): row i leaves GRU(...) + off_table[off_index[i]], which
         # is also what the next position decays -- inside the chain kernels (pointers only, no host read)
-        ofk = {}
+        offset = {}
         if off_table is not None:
-            if tabs is None or not chain_offset_usable(d, variant, n_rnn):
-                raise _lib.TempAmdError("gru_chain: a state offset runs on the persistent chain kernels only, and %s" % (
-                    "this backend / width / cell has none that take it" if not chain_offset_usable(d, variant, n_rnn) else
-                    "they refuse this program (not a set of one-GRU chains, a panel longer than %d steps, or more than %d consumed "
-                    "instances): use the per-position loop" % (_lib.CHAIN_MAX_STEPS, _lib.CHAIN_MAX_UP)))
+            _require_chain_kernels("state offset", tabs, chain_offset_usable(d, variant, n_rnn))
             assert off_table.shape[1] == d and off_index.dtype == torch.int32 and off_index.numel() == N
-            ofk = dict(offset=(off_table.detach().contiguous(), off_index))
-        ctx.offset, ctx.off_inverse, ctx.off_rows = ofk, off_inverse, (off_table.shape[0] if off_table is not None else 0)
-        # nn.GRU cells on the f16 route: the chain forward computes the input gates itself from the x rows (temp_gru_chain_fwd's x route) --
-        # no gi, no gate GEMM.  (Independent of x_src: a labelled and an unlabelled program take the same kernel.)
-        # (an offset chain's states leave the range of the f16 state split: it keeps the gi route and the bf16 / fp32 chain kernels)
-        fused = bool(tabs is not None and not ofk and FUSED_INPUT_GATES and variant == _lib.GRU_TORCH and hasattr(be, "gru_chain_fwd_x")
+            offset = dict(offset=(off_table.detach().contiguous(), off_index))
+        # nn.GRU cells on the f16 route: the chain forward computes the input gates itself from the x rows (temp_gru_chain_fwd's x route):
+        # no gi, no gate GEMM.  Independent of x_src (a labelled and an unlabelled program take the same kernel); not for an offset chain,
+        # whose states leave the range of the f16 state split (it keeps the gi route and the bf16 / fp32 chain kernels)
+        fused = bool(tabs is not None and not offset and FUSED_INPUT_GATES and variant == _lib.GRU_TORCH and hasattr(be, "gru_chain_fwd_x")
                      and be.gru_chain_fwd_x_supported(d, variant, tabs["max_steps"]))
         share = prog.gi_shared(dev) if (tabs is not None and not fused) else None        # gates once per distinct x row (chain kernels only)
         # x_keys = (row keys [x rows], column keys [d]) of x_all from its producer (functional.gather_rows(keys=True)): the input-gate
         # product and the weight gradients then run on the f16 pipe without a pass over x of their own
-        ctx.x_keys = x_keys if (x_keys is not None and tabs is not None) else None
-        gk = (lambda: dict(x_keys=[ctx.x_keys[0][g["x0"]:g["x1"]] for g in prog.groups])) if ctx.x_keys is not None else dict
-        gi_index = None
-        if fused:
-            gi = None
-        elif share is not None:
-            gi_index = share["gi_index"]
-            gi = torch.empty(share["rows"], G, dtype=torch.float32, device=dev)
-            cut = share["g0"] + [share["rows"]]
-            be.gru_input_gates_multi([x_all[g["x0"]:g["x1"]] for g in prog.groups], [W[g["rnn"]][0] for g in prog.groups],
-                                     [W[g["rnn"]][2] for g in prog.groups], variant, [gi[cut[i]:cut[i + 1]] for i in range(len(prog.groups))],
-                                     x_idx=share["rep"], **gk())
+        x_keys = x_keys if tabs is not None else None
+        gi, gi_index = _input_gates(be, prog, x_all, W, variant, fused, share, x_keys)
+        H, saved = torch.empty(N, d, dtype=torch.float32, device=dev), torch.empty(5, N, d, dtype=torch.float32, device=dev)
+        if tabs is not None:
+            packs = _chain_forward(be, prog, tabs, x_all, gi, gi_index, W, lam, variant, fused, decay, offset, H, saved)
         else:
-            gi = torch.empty(N, G, dtype=torch.float32, device=dev)
-        if share is not None or fused:
-            pass
-        elif len(prog.groups) > 1 and hasattr(be, "gru_input_gates_multi"):    # both directions' input gates in one launch
-            be.gru_input_gates_multi([x_all[g["x0"]:g["x1"]] for g in prog.groups], [W[g["rnn"]][0] for g in prog.groups],
-                                     [W[g["rnn"]][2] for g in prog.groups], variant, [gi[g["h0"]:g["h1"]] for g in prog.groups], **gk())
-        else:
-            for g in prog.groups:
-                w_ih, _, b_ih, _ = W[g["rnn"]]
-                be.gru_input_gates(x_all[g["x0"]:g["x1"]], w_ih, b_ih, variant, gi[g["h0"]:g["h1"]])
-        H = torch.empty(N, d, dtype=torch.float32, device=dev)
-        saved = torch.empty(5, N, d, dtype=torch.float32, device=dev)
-        packs = None
-        if fused:
-            packs = be.gru_chain_pack_x_multi([W[r][1] for r in range(n_rnn)], [W[r][0] for r in range(n_rnn)])
-            be.gru_chain_fwd_x(tabs, x_all, prog.x_index(dev), lam, variant, packs, [W[r][3] for r in range(n_rnn)], [W[r][2] for r in range(n_rnn)],
-                               H, saved, **dk)
-        elif ofk:                                      # packed for the kernels an offset chain runs on, whatever the options select
-            packs = be.gru_chain_pack_multi([W[r][1] for r in range(n_rnn)], layout=be.gru_chain_offset_layout(d))
-            be.gru_chain_fwd(tabs, gi, lam, variant, packs, [W[r][3] for r in range(n_rnn)], H, saved, gi_index=gi_index, **dk, **ofk)
-        elif tabs is not None:
-            packs = be.gru_chain_pack_multi([W[r][1] for r in range(n_rnn)]) if hasattr(be, "gru_chain_pack_multi") else \
-                [be.gru_chain_pack(W[r][1]) for r in range(n_rnn)]
-            be.gru_chain_fwd(tabs, gi, lam, variant, packs, [W[r][3] for r in range(n_rnn)], H, saved, gi_index=gi_index, **dk)
-        else:
-            tens = prog.upload(dev)
-            zero, none_idx = prog.constants(dev, d)
-        for level in (prog.levels if tabs is None else ()):
-            cells = []
-            for i in level:
-                it = prog.inst[i]
-                pi, _, dt = tens[i]
-                _, w_hh, _, b_hh = W[it.rnn]
-                if it.prev >= 0:
-                    p = prog.inst[it.prev]
-                    prev, pidx = H[p.h0:p.h0 + p.n], pi
-                else:                                 # no history yet: every previous state is zero (pointwise cell)
-                    prev, pidx = None, none_idx[:it.n]
-                cells.append(dict(gi=gi[it.h0:it.h0 + it.n], prev=prev, prev_idx=pidx, dt=dt, w_hh=w_hh, b_hh=b_hh,
-                                  h_out=H[it.h0:it.h0 + it.n], row0=it.h0))
-            be.gru_cell_fwd_multi(cells, lam, variant, saved)
+            packs = _position_forward(be, prog, gi, W, lam, variant, H, saved)
         ctx.set_materialize_grads(False)             # states nobody differentiates (the history handed to the all-entity pass in an
                                                      # encoder-only step) come back as None, not as zero-filled (n, d) tensors
         ctx.save_for_backward(x_all, saved, *[w for ws in W for w in ws])
-        ctx.prog, ctx.lam, ctx.variant, ctx.n_rnn, ctx.G, ctx.want = prog, lam, variant, n_rnn, G, want
-        ctx.tabs, ctx.packs = tabs, packs
+        ctx.prog, ctx.lam, ctx.variant, ctx.n_rnn, ctx.G, ctx.want = prog, lam, variant, n_rnn, weights[0].shape[0], want    # G: 3d or d (type-1)
+        ctx.tabs, ctx.fused, ctx.share, ctx.decay, ctx.offset, ctx.x_keys, ctx.packs = tabs, fused, share, decay, offset, x_keys, packs
+        ctx.off_inverse, ctx.off_rows = off_inverse, (off_table.shape[0] if off_table is not None else 0)
         if want is None:
             return H
         # only these instances' states are consumed downstream: hand them out as row ranges of H, so that the backward receives
@@ -410,126 +515,46 @@ class _GruChainFn(torch.autograd.Function):
     def backward(ctx, *d_outs):
         be = get_backend()
         x_all, saved = ctx.saved_tensors[:2]
-        flat = ctx.saved_tensors[2:]
-        W = [flat[4 * r:4 * r + 4] for r in range(ctx.n_rnn)]
-        prog, lam, variant, G = ctx.prog, ctx.lam, ctx.variant, ctx.G
-        dev, d, N = x_all.device, x_all.shape[1], prog.n_total
+        W = [ctx.saved_tensors[2 + 4 * r:6 + 4 * r] for r in range(ctx.n_rnn)]
+        prog, groups = ctx.prog, ctx.prog.groups
+        new = lambda *shape: torch.empty(*shape, dtype=torch.float32, device=x_all.device)
+        d, N = x_all.shape[1], prog.n_total
+        # upstream gradients: one dense dH (want = None), else one per wanted instance (None: none for that instance's rows)
         if ctx.want is None:
-            dH = d_outs[0].contiguous() if d_outs[0] is not None else torch.zeros(N, d, dtype=torch.float32, device=dev)
-            up = lambda i, it: dH[it.h0:it.h0 + it.n]
+            ups = [d_outs[0].contiguous() if d_outs[0] is not None else torch.zeros(N, d, dtype=torch.float32, device=x_all.device)]
         else:
             given = {i: g.contiguous() for i, g in zip(ctx.want, d_outs) if g is not None}
-            up = lambda i, it: given.get(i)                  # None: no upstream gradient for this instance's rows
-        groups = list(prog.groups)
-        # learnable decay: the chain backward also writes dL / d(w dt + b) per row, reduced to (d_w, d_b) per GRU afterwards
-        dk = dict(ctx.decay, d_arg=torch.empty(N, dtype=torch.float32, device=dev)) if ctx.decay else {}
-
-        def decay_grads():
-            if not dk:
-                return None, None
-            d_wb = be.gru_chain_decay_reduce(ctx.tabs, d, variant, dk["d_arg"], ctx.n_rnn)        # [n_rnn, 2]: all GRUs share the one Linear
-            return d_wb[:, 0].sum().reshape(1, 1), d_wb[:, 1].sum().reshape(1)
-        # state offset: the chain backward also writes the gradient reaching every row's state; the table's gradient is the adjoint
-        # of the row gather table[index] applied to it (a segment sum over the static inverse: no atomics)
-        ofk = dict(ctx.offset, d_state=torch.empty(N, d, dtype=torch.float32, device=dev)) if ctx.offset else {}
-
-        def offset_grads():
-            if not ofk:
-                return None, None, None
-            seg_ptr, order = ctx.off_inverse
-            return be.segment_sum_rows(ofk["d_state"], seg_ptr, order, ctx.off_rows), None, None
+            ups = [given.get(i) for i in ctx.want]
+        # what the chain backward writes besides the gate gradients, for _backward_result
+        decay = dict(ctx.decay, d_arg=new(N)) if ctx.decay else {}
+        offset = dict(ctx.offset, d_state=new(N, d)) if ctx.offset else {}
         zero_state = [all(it.prev < 0 for it in prog.inst if it.group == gi) for gi in range(len(groups))]    # hdec = 0 on every row
-        # GRUs with disjoint x rows (the two directions of a bidirectional chain, or the one GRU of a uni-directional one): ONE
-        # weight-gradient launch for all d_W_ih / d_W_hh products, ONE reduction and ONE d_x launch
+        # GRUs with disjoint x rows (the two directions of a bidirectional chain, or the one GRU of a uni-directional one) take a
+        # one-launch strategy -- with the gate gradients written once where the library takes these shapes
         disjoint = all(groups[a]["x1"] <= groups[b]["x0"] or groups[b]["x1"] <= groups[a]["x0"] for a in range(len(groups)) for b in range(a))
         one_launch = bool(groups and disjoint and not any(zero_state) and len({g["rnn"] for g in groups}) == len(groups) and WEIGHT_GRADS_MULTI)
-        # ... and when the library takes these shapes, the chain backward writes its gate gradients ONCE, [dr | dz | dn_i | dn_h]
-        # (two thirds of dgh repeat dgi), for temp_gru_grads_g4
-        once = bool(one_launch and GATE_GRADS_ONCE and ctx.tabs is not None and hasattr(be, "gru_grads_g4")
-                    and be.gru_grads_g4_supported([g["h1"] - g["h0"] for g in groups], d, variant))
+        once = one_launch and GATE_GRADS_ONCE and ctx.tabs is not None and be.gru_grads_g4_supported([g["h1"] - g["h0"] for g in groups], d, ctx.variant)
         if once:
-            g4 = torch.empty(N, 4 * d, dtype=torch.float32, device=dev)
-            ups = [dH] if ctx.want is None else [given.get(i) for i in ctx.want]
-            # (f16 arithmetic: the chain backward also hands out the magnitude keys of g4 -- per row, per GRU and column -- that the
-            #  weight-gradient and d_x products split it with; integer maxima, so bit-repeatable)
-            #  An offset chain hands out none: saved[4] = dec . s_prev is not bounded by the keyed products' constant state scale.
-            keyed = bool(KEYED_GRADS and not ofk and hasattr(be, "gru_chain_keys_supported") and be.gru_chain_keys_supported(d))
-            keys = (torch.empty(N, dtype=torch.int32, device=dev), torch.empty(ctx.n_rnn + ctx.tabs["n_panels"], 4 * d, dtype=torch.int32, device=dev)) if keyed else None
-            be.gru_chain_bwd_g4(ctx.tabs, saved, ups, lam, variant, ctx.packs, [W[r][3] for r in range(ctx.n_rnn)], g4, **({"keys": keys} if keyed else {}), **dk, **ofk)
+            g4, keys = _gate_grads_g4(be, ctx, saved, ups, W, decay, offset)
             d_x_all = torch.empty_like(x_all)
-            xsl = [slice(g["x0"], g["x1"]) for g in groups]
-            hsl = [slice(g["h0"], g["h1"]) for g in groups]
-            kw = dict(row_keys=[keys[0][b] for b in hsl], col_keys=[keys[1][g["rnn"]] for g in groups]) if keyed else {}
-            if keyed and ctx.x_keys is not None:
-                kw["x_col_keys"] = [ctx.x_keys[1]] * len(groups)   # (a bound over ALL rows of x_all bounds every group's rows)
-            multi = be.gru_grads_g4([x_all[a] for a in xsl], [saved[4, b] for b in hsl], [g4[b] for b in hsl], [W[g["rnn"]][0] for g in groups],
-                                    [d_x_all[a] for a in xsl], **kw)
-            grads = [None] * (4 * ctx.n_rnn)
-            covered = np.zeros(x_all.shape[0], dtype=bool)
-            for g, gw in zip(groups, multi):
-                covered[g["x0"]:g["x1"]] = True
-                for k in range(4):
-                    grads[4 * g["rnn"] + k] = gw[k]
-            if not covered.all():
-                d_x_all[torch.from_numpy(~covered).to(dev)] = 0
-            return (d_x_all, None, None, None, None, None, None) + decay_grads() + offset_grads() + tuple(grads)
-        dgi = torch.empty(N, G, dtype=torch.float32, device=dev)
-        dgh = torch.empty(N, 3 * d, dtype=torch.float32, device=dev)
-        if ctx.tabs is not None:
-            ups = [dH] if ctx.want is None else [given.get(i) for i in ctx.want]
-            be.gru_chain_bwd(ctx.tabs, saved, ups, lam, variant, ctx.packs, [W[r][3] for r in range(ctx.n_rnn)], dgi, dgh, **dk, **ofk)
+            per_group = _weight_grads_g4(be, ctx, x_all, saved, g4, keys, W, d_x_all)
         else:
-            tens = prog.upload(dev)
-            decv = torch.empty(N, dtype=torch.float32, device=dev)
-            d_prev = torch.empty(N, d, dtype=torch.float32, device=dev)
-        for level in (reversed(prog.levels) if ctx.tabs is None else ()):
-            cells = []
-            for i in level:
-                it = prog.inst[i]
-                _, ni, dt = tens[i]
-                nxt = prog.inst[it.next] if (it.next >= 0 and prog.inst[it.next].n > 0) else None
-                sl = slice(it.h0, it.h0 + it.n)
-                cells.append(dict(row0=it.h0, n=it.n, dh_up=up(i, it), d_prev_next=d_prev[nxt.h0:nxt.h0 + nxt.n] if nxt is not None else None,
-                                  next_idx=ni if nxt is not None else None, dt=dt, w_hh=W[it.rnn][1], dgi=dgi[sl], dgh=dgh[sl],
-                                  decv=decv[sl], d_prev=d_prev[sl], no_prev=it.prev < 0))
-            be.gru_cell_bwd_multi(cells, lam, variant, saved)
-        d_x_all = torch.empty_like(x_all)
-        written = np.zeros(x_all.shape[0], dtype=bool)
-        grads = [None] * (4 * ctx.n_rnn)
-        multi = None
-        if one_launch and hasattr(be, "gru_weight_grads_multi"):
-            xsl = [slice(g["x0"], g["x1"]) for g in groups]
-            hsl = [slice(g["h0"], g["h1"]) for g in groups]
-            multi = be.gru_weight_grads_multi([x_all[a] for a in xsl], [saved[4, b] for b in hsl], [dgi[b] for b in hsl], [dgh[b] for b in hsl],
-                                              [W[g["rnn"]][0] for g in groups], variant, [d_x_all[a] for a in xsl])
-        if multi is not None:
-            for g, gw in zip(groups, multi):
-                written[g["x0"]:g["x1"]] = True
-                for k in range(4):
-                    grads[4 * g["rnn"] + k] = gw[k]
-            groups = []
-        for g in groups:
-            gi_ = prog.groups.index(g)
-            xs, hs = slice(g["x0"], g["x1"]), slice(g["h0"], g["h1"])
-            first = not written[xs].any()
-            assert first or written[xs].all()
-            tgt = d_x_all[xs] if first else torch.empty(g["x1"] - g["x0"], d, dtype=torch.float32, device=dev)
-            gw = be.gru_weight_grads(x_all[xs], None if zero_state[gi_] else saved[4, hs], dgi[hs], dgh[hs], W[g["rnn"]][0], variant, tgt)
-            if not first:
-                d_x_all[xs] += tgt
-            written[xs] = True
-            for k in range(4):                         # (d_w_ih, d_w_hh, d_b_ih, d_b_hh) -> weight order (w_ih, w_hh, b_ih, b_hh)
-                j = 4 * g["rnn"] + k
-                grads[j] = gw[k] if grads[j] is None else grads[j] + gw[k]
-        if not written.all():
-            d_x_all[torch.from_numpy(~written).to(dev)] = 0
-        return (d_x_all, None, None, None, None, None, None) + decay_grads() + offset_grads() + tuple(grads)
+            dgi, dgh = new(N, ctx.G), new(N, 3 * d)
+            if ctx.tabs is not None:
+                _gate_grads_chain(be, ctx, saved, ups, W, decay, offset, dgi, dgh)
+            else:
+                _gate_grads_positions(be, ctx, saved, ups, W, dgi, dgh)
+            d_x_all = torch.empty_like(x_all)
+            per_group = _weight_grads_multi(be, ctx, x_all, saved, dgi, dgh, W, d_x_all) if one_launch else None
+            if per_group is None:
+                per_group = _weight_grads_per_group(be, ctx, x_all, saved, dgi, dgh, W, zero_state, d_x_all)
+        return _backward_result(be, ctx, d_x_all, _scatter_grads(ctx, per_group, d_x_all), decay, offset)
 
 
 def chain_kernels_usable(d, n_rnn=1):
     """True when gru_chain() will run a program of this width through the persistent chain kernels."""
     be = get_backend()
-    return bool(CHAIN_KERNELS and hasattr(be, "gru_chain_fwd") and n_rnn <= _lib.CHAIN_MAX_RNN and be.gru_chain_supported(d))
+    return bool(CHAIN_KERNELS and n_rnn <= _lib.CHAIN_MAX_RNN and be.gru_chain_supported(d))
 
 
 def chain_decay_usable(d, variant, n_rnn=1):

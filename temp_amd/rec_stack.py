@@ -76,10 +76,10 @@ class _RecStackFn(torch.autograd.Function):
         tens = prog.upload(dev)
         d_w2 = d_loop2 = d_bias2 = None
         # RGCN_2's weight / bias gradients are sums over ALL positions: with the union graph of the positions at hand (row order =
-        # program order) and a backend that has the split backward, the loop computes d_h1 only and keeps every position's masked
-        # output gradient; ONE pass over the union afterwards forms the weight gradients (per position it took a relation-weight
-        # kernel, its fix-up, two reductions, a column sum and three additions)
-        hoist = ctx.g_union is not None and hasattr(be, "rgcn_bwd_dh")
+        # program order) the loop computes d_h1 only and keeps every position's masked output gradient; ONE pass over the union
+        # afterwards forms the weight gradients (per position it took a relation-weight kernel, its fix-up, two reductions, a column
+        # sum and three additions)
+        hoist = ctx.g_union is not None
         if hoist:
             # the ONE pass over the union reads H1 / DZ by the union's node order: it must be the program's row order, position by
             # position (a mismatch would give wrong d_W silently)
@@ -130,7 +130,7 @@ class _RecStackFn(torch.autograd.Function):
         d_y1 = torch.empty_like(y1)
         zero_state = all(it.prev < 0 for it in prog.inst)                            # hdec = 0 on every row
         multi = None
-        if not zero_state and hasattr(be, "gru_weight_grads_multi"):               # both GRUs in one weight-gradient launch
+        if not zero_state:             # both GRUs in one weight-gradient launch (None, nothing launched: a shape left to the per-GRU call)
             multi = be.gru_weight_grads_multi([y1, Y2], [saved1[4], saved2[4]], [dgi1, dgi2], [dgh1, dgh2], [wi1, wi2], variant, [d_y1, None])
         if multi is not None:
             gw1, gw2 = multi

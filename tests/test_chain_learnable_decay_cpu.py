@@ -243,3 +243,18 @@ def test_gru_chain_refuses_a_decay_it_cannot_run(decay_backend):
     prog2, n_x = random_program(33, n_chain=2, K=6, E=90, lo=20, hi=70)
     with pytest.raises(_lib.TempAmdError, match="learnable decay"):
         GC.gru_chain(torch.randn(n_x, 32), prog2, rnns, 0.1, False, None, decay=spec)
+
+
+# recorded on the commit before _GruChainFn was split into one function per route (tests/chain_route_cases.py), never on the code under test
+DECAY_LAUNCHES = [('gru_input_gates_multi', (), ()),
+                  ('gru_chain_pack', ((96, 32),), ()),
+                  ('gru_chain_pack', ((96, 32),), ()),
+                  ('gru_chain_fwd', ((553, 96), (553, 32), (5, 553, 32)), ('decay',)),
+                  ('gru_chain_bwd_g4', ((5, 553, 32), (553, 128)), ('d_arg', 'decay')),
+                  ('gru_grads_g4', (), ()),
+                  ('gru_chain_decay_reduce', ((553,),), ())]
+
+
+def test_decay_route_launches(decay_backend):
+    from tests.chain_route_cases import DECAY_CASE, run_route
+    assert run_route(DECAY_CASE, CPU)[0] == DECAY_LAUNCHES

@@ -324,3 +324,17 @@ def test_gru_chain_refuses_an_offset_it_cannot_run(offset_backend):
     off2 = (table,) + GC.offset_tables(offset_index(prog2), T_ROWS, CPU)
     with pytest.raises(_lib.TempAmdError, match="state offset"):
         GC.gru_chain(torch.randn(n_x, 32), prog2, rnns, 0.1, False, None, offset=off2)
+
+
+# recorded on the commit before _GruChainFn was split into one function per route (tests/chain_route_cases.py), never on the code under test
+OFFSET_LAUNCHES = [('gru_input_gates_multi', (), ()),
+                   ('gru_chain_pack_multi', (), ('layout',)),
+                   ('gru_chain_fwd', ((553, 96), (553, 32), (5, 553, 32)), ('offset',)),
+                   ('gru_chain_bwd_g4', ((5, 553, 32), (553, 128)), ('d_state', 'offset')),
+                   ('gru_grads_g4', (), ()),
+                   ('segment_sum_rows', ((553, 32), (8,), (491,)), ())]
+
+
+def test_offset_route_launches(offset_backend):
+    from tests.chain_route_cases import OFFSET_CASE, run_route
+    assert run_route(OFFSET_CASE, CPU)[0] == OFFSET_LAUNCHES
