@@ -762,7 +762,7 @@ class HipBackend:
         return g, d_q
 
     def l1_ce_bwd_table(self, q, table, slot_ptr, slot, g):
-        """-> d_table [rows, d]: the candidate side of the adjoint over the slot lists (functional.l1_slots)."""
+        """-> d_table [rows, d]: the candidate side of the adjoint over the slot lists (link_loss.l1_slots)."""
         q, table, g = _f32(q, "q"), _f32(table, "table"), _f32(g, "g")
         slot_ptr, slot = _i32(slot_ptr, "slot_ptr"), _i32(slot, "slot")
         n_rows, d = table.shape
@@ -841,7 +841,7 @@ class HipBackend:
         return g, d_q, d_w
 
     def l1_mix_ce_bwd_table(self, q, table_a, table_b, w, slot_ptr, slot, g):
-        """-> (d_table_a, d_table_b) [rows, d]: the candidate side of the adjoint over the slot lists (functional.l1_slots)."""
+        """-> (d_table_a, d_table_b) [rows, d]: the candidate side of the adjoint over the slot lists (link_loss.l1_slots)."""
         q, table_a, table_b, w, g = _f32(q, "q"), _f32(table_a, "table_a"), _f32(table_b, "table_b"), _f32(w, "w"), _f32(g, "g")
         slot_ptr, slot = _i32(slot_ptr, "slot_ptr"), _i32(slot, "slot")
         n_rows, d = table_a.shape

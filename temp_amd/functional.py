@@ -278,561 +278,12 @@ def gather_inverse(idx_np, n_rows, device):
     return dev[:n_rows + 1], dev[n_rows + 1:]
 
 
-class _CandidateCEFn(torch.autograd.Function):
-    """mean_p CE(query[p] . all_embeds[cand[p, :]]^T, label 0) without materialising (P, C, D)."""
-
-    @staticmethod
-    def forward(ctx, query, all_embeds, cand):
-        be = get_backend()
-        scores = be.linear(query, all_embeds, True)                  # (P, N): every positive against ALL entities
-        loss_rows, lse = be.gather_ce_fwd(scores, cand)
-        ctx.save_for_backward(query, all_embeds, scores, lse, cand)
-        return loss_rows.mean()
-
-    @staticmethod
-    def backward(ctx, d_loss):
-        query, all_embeds, scores, lse, cand = ctx.saved_tensors
-        be = get_backend()
-        d_scores = be.gather_ce_bwd(scores, cand, lse, d_loss.reshape(1).contiguous(), 1.0 / max(scores.shape[0], 1))
-        d_query = be.linear(d_scores, all_embeds, False)             # (P,N) . (N,D)
-        d_all = be.linear_tn(d_scores, query)                        # (N,P) . (P,D)
-        return d_query, d_all, None
-
-
-class _BatchedCandidateCEFn(torch.autograd.Function):
-    """sum_b mean_{rows of window b} CE(query[p] . all_embeds_b[cand[p, :]]^T, label 0): the row-wise work (candidate CE
-    forward / backward) runs once over ALL windows' rows; only the three GEMMs are per window, because every window scores
-    against its own all-entity matrix."""
-
-    @staticmethod
-    def forward(ctx, query, cand, splits, row_w, *all_embeds):
-        be = get_backend()
-        scores = torch.cat([be.linear(query[a:b], e, True) for (a, b), e in zip(splits, all_embeds)], dim=0)    # (sum P, N)
-        loss_rows, lse = be.gather_ce_fwd(scores, cand)
-        ctx.save_for_backward(query, scores, lse, cand, row_w, *all_embeds)
-        ctx.splits = splits
-        return (loss_rows * row_w).sum()
-
-    @staticmethod
-    def backward(ctx, d_loss):
-        query, scores, lse, cand, row_w = ctx.saved_tensors[:5]
-        all_embeds = ctx.saved_tensors[5:]
-        be = get_backend()
-        d_scores = be.gather_ce_bwd(scores, cand, lse, d_loss.reshape(1).contiguous(), 1.0, row_w)
-        d_query = torch.cat([be.linear(d_scores[a:b], e, False) for (a, b), e in zip(ctx.splits, all_embeds)], dim=0)
-        d_all = tuple(be.linear_tn(d_scores[a:b], query[a:b]) for (a, b) in ctx.splits)
-        return (d_query, None, None, None) + d_all
-
-
-# Entity-major score GEMMs (see forward): 10 % less device time on ICEWS-shaped steps (3.51 -> 3.18 ms under graph replay), but
-# ~30 more launches per step, which makes an eager, host-bound training loop SLOWER (5.7 -> 6.8 ms/step measured).  Off unless
-# TEMP_LOSS_TALL=1.
-_TALL_SCORES = __import__("os").environ.get("TEMP_LOSS_TALL", "0") == "1"
-
-
-# -- the per-window products of the three batched loss nodes ------------------------------------------------------------------
-# `big` is the (B * N, D) stack of the windows' all-entity matrices, `splits` the [row_begin, row_end) of every window's block of
-# the stacked query rows, `live` the windows that have rows.
-def _live_windows(splits):
-    return [(b, a0, a1) for b, (a0, a1) in enumerate(splits) if a1 > a0]
-
-
-def _window_scores(be, q, big, live, N):
-    """scores = q[rows of window b] . big_b^T for every live window -> (rows, N), one multi-problem launch."""
-    scores = torch.empty(q.shape[0], N, dtype=torch.float32, device=q.device)
-    be.linear_multi([q[a0:a1] for _, a0, a1 in live], [big[b * N:(b + 1) * N] for b, _, _ in live], True, scores)
-    return scores
-
-
-def _window_dq(be, d_s, big, live, N, like):
-    """d_q = d_scores_b . big_b for every live window, one launch."""
-    d_q = torch.empty_like(like)
-    be.linear_multi([d_s[a0:a1] for _, a0, a1 in live], [big[b * N:(b + 1) * N] for b, _, _ in live], False, d_q)
-    return d_q
-
-
-def _dbig_like(big, live, n_windows):
-    """The gradient buffer of `big`: every live window's block is written whole, so only a batch with an empty window needs zeros."""
-    return torch.empty_like(big) if len(live) == n_windows else torch.zeros_like(big)
-
-
-def _window_dbig(be, d_s, q, big, live, N, n_windows):
-    """d_big_b = d_scores_b^T . q_b for every live window."""
-    d_big = _dbig_like(big, live, n_windows)
-    if hasattr(be, "linear_tn_multi"):                                                        # one launch
-        be.linear_tn_multi([d_s[a0:a1] for _, a0, a1 in live], [q[a0:a1] for _, a0, a1 in live], [d_big[b * N:(b + 1) * N] for b, _, _ in live])
-    else:
-        for b, a0, a1 in live:
-            be.linear_tn(d_s[a0:a1], q[a0:a1], out=d_big[b * N:(b + 1) * N])
-    return d_big
-
-
-class _BatchedLinkPredictionFn(torch.autograd.Function):
-    """The whole batched link-prediction loss as ONE autograd node:
-        q      = bilinear_query(ent_rows[known], rel[rel_idx])                 (gathers fused, temp_bilinear_query_fwd)
-        scores = q[rows of window b] . all_b^T   for every window b             (temp_linear_multi, 4 windows per launch)
-        loss   = sum_rows w_row * CE(scores[row, cand[row, :]], label 0)        (temp_gather_ce_fwd)
-    `big` is the (B * N, D) stack of the windows' all-entity matrices.  The backward mirrors it and reduces the per-row
-    gradients of the gathered operands with deterministic segment sums over the static index lists."""
-
-    @staticmethod
-    def forward(ctx, ent_rows, rel, big, kind, inp):
-        be = get_backend()
-        N = big.shape[0] // len(inp["splits"])
-        q = be.bilinear_query_fwd(kind, ent_rows, inp["known"], rel, inp["rel"], inp["is_tail"])
-        live = _live_windows(inp["splits"])
-        # few positives against many entities (ICEWS-like: ~200 rows x 10 000 entities per window): the ENTITY axis is made the
-        # tall one of every GEMM -- scores = (all_b . q_b^T)^T through a transposed-store epilogue, and the backward products
-        # from d_scores^T.  (The planner pads every window's block to a multiple of 4 rows so it can be an N / K extent.)
-        tall = _TALL_SCORES and all((a1 - a0) % 4 == 0 and 8 * (a1 - a0) <= N for _, a0, a1 in live)
-        if tall:
-            scores = torch.empty(q.shape[0], N, dtype=torch.float32, device=q.device)
-            for b, a0, a1 in live:
-                be.linear_t(big[b * N:(b + 1) * N], q[a0:a1], True, scores[a0:a1])
-        else:
-            scores = _window_scores(be, q, big, live, N)
-        loss_rows, lse = be.gather_ce_fwd(scores, inp["cand"])
-        ctx.save_for_backward(ent_rows, rel, big, q, scores, lse)
-        ctx.kind, ctx.inp, ctx.live, ctx.N, ctx.tall = kind, inp, live, N, tall
-        return (loss_rows * inp["weights"]).sum()
-
-    @staticmethod
-    def backward(ctx, d_loss):
-        ent_rows, rel, big, q, scores, lse = ctx.saved_tensors
-        inp, live, N = ctx.inp, ctx.live, ctx.N
-        be = get_backend()
-        d_scores = be.gather_ce_bwd(scores, inp["cand"], lse, d_loss.reshape(1).contiguous(), 1.0, inp["weights"])
-        if ctx.tall:
-            d_q = torch.empty_like(q)
-            d_big = _dbig_like(big, live, len(inp["splits"]))
-            for b, a0, a1 in live:
-                dst = d_scores[a0:a1].t().contiguous()                                        # (N, rows of window b)
-                be.linear_tn(dst, big[b * N:(b + 1) * N], out=d_q[a0:a1])                     # d_q   = d_scores . all_b
-                d_big[b * N:(b + 1) * N].copy_(be.linear(dst, q[a0:a1], False))               # d_all = d_scores^T . q
-        else:
-            d_q = _window_dq(be, d_scores, big, live, N, q)
-            d_big = _window_dbig(be, d_scores, q, big, live, N, len(inp["splits"]))
-        dk, dr = be.bilinear_query_bwd(ctx.kind, ent_rows, inp["known"], rel, inp["rel"], inp["is_tail"], d_q)
-        d_ent = be.segment_sum_rows(dk, inp["known_inv"][0], inp["known_inv"][1], ent_rows.shape[0])
-        d_rel = be.segment_sum_rows(dr, inp["rel_inv"][0], inp["rel_inv"][1], rel.shape[0])
-        return d_ent, d_rel, d_big, None, None
-
-
-class _BatchedEnsembleLinkPredictionFn(torch.autograd.Function):
-    """_BatchedLinkPredictionFn for the score-level ensemble of the post-ensemble models (combined_scores,
-    models/PostDynamicRGCN.py:404-406, 425-428): TWO streams (local = pre-GRU, temporal = post-GRU) score against their own
-    all-entity stacks, the scores are mixed row by row with w (local) and 1 - w (temporal) on the (rows, N) matrices, then the
-    candidate cross-entropy.  Same launches per stream as the plain node (folded query, score GEMMs of all windows as
-    multi-problem launches -- k-sliced where the rows are few against 10 000 entities -- one candidate CE), one mix pass."""
-
-    @staticmethod
-    def forward(ctx, loc_rows, rec_rows, rel, big_loc, big_rec, w, kind, inp):
-        be = get_backend()
-        N = big_loc.shape[0] // len(inp["splits"])
-        live = _live_windows(inp["splits"])
-        qs, sc = [], []
-        for rows, big in ((loc_rows, big_loc), (rec_rows, big_rec)):
-            q = be.bilinear_query_fwd(kind, rows, inp["known"], rel, inp["rel"], inp["is_tail"])
-            qs.append(q)
-            sc.append(_window_scores(be, q, big, live, N))
-        mixed = torch.lerp(sc[1], sc[0], w)                          # w (rows, 1): w * local + (1 - w) * temporal
-        loss_rows, lse = be.gather_ce_fwd(mixed, inp["cand"])
-        ctx.save_for_backward(loc_rows, rec_rows, rel, big_loc, big_rec, w, qs[0], qs[1], sc[0], sc[1], mixed, lse)
-        ctx.kind, ctx.inp, ctx.live, ctx.N = kind, inp, live, N
-        return (loss_rows * inp["weights"]).sum()
-
-    @staticmethod
-    def backward(ctx, d_loss):
-        loc_rows, rec_rows, rel, big_loc, big_rec, w, q_l, q_r, s_l, s_r, mixed, lse = ctx.saved_tensors
-        inp, live, N = ctx.inp, ctx.live, ctx.N
-        be = get_backend()
-        d_m = be.gather_ce_bwd(mixed, inp["cand"], lse, d_loss.reshape(1).contiguous(), 1.0, inp["weights"])
-        d_sl = d_m * w
-        d_sr = d_m - d_sl
-        d_w = (d_m * (s_l - s_r)).sum(dim=1, keepdim=True) if ctx.needs_input_grad[5] else None
-        outs, d_rel = [], None
-        for rows, big, q, d_s in ((loc_rows, big_loc, q_l, d_sl), (rec_rows, big_rec, q_r, d_sr)):
-            d_q = _window_dq(be, d_s, big, live, N, q)
-            d_big = _window_dbig(be, d_s, q, big, live, N, len(inp["splits"]))
-            dk, dr = be.bilinear_query_bwd(ctx.kind, rows, inp["known"], rel, inp["rel"], inp["is_tail"], d_q)
-            outs.append((be.segment_sum_rows(dk, inp["known_inv"][0], inp["known_inv"][1], rows.shape[0]), d_big))
-            d_rel = dr if d_rel is None else d_rel + dr
-        d_rel = be.segment_sum_rows(d_rel, inp["rel_inv"][0], inp["rel_inv"][1], rel.shape[0])
-        return outs[0][0], outs[1][0], d_rel, outs[0][1], outs[1][1], d_w, None, None
-
-
-def batched_ensemble_link_prediction(loc_rows, rec_rows, rel, big_loc, big_rec, w, kind, inputs):
-    """sum over windows of the ensemble CE_tail + CE_head; `w` (rows, 1) = weight of the LOCAL stream of every stacked query row
-    (per window: [tail rows: weight_object ; head rows: weight_subject]); `inputs` = TKG_Module.loss_inputs(...)."""
-    w = w.reshape(-1, 1).to(loc_rows.dtype).contiguous()
-    if kind == "transE":
-        return _BatchedEnsembleTranslationLinkPredictionFn.apply(loc_rows.contiguous(), rec_rows.contiguous(), rel, big_loc.contiguous(),
-                                                                 big_rec.contiguous(), w, inputs)
-    return _BatchedEnsembleLinkPredictionFn.apply(loc_rows.contiguous(), rec_rows.contiguous(), rel, big_loc.contiguous(), big_rec.contiguous(),
-                                                  w, kind, inputs)
-
-
-def _gated_query_fwd(be, kind, a_rows, a_idx, b_rows, b_idx, w, rel, rel_idx, is_tail):
-    if hasattr(be, "gated_query_fwd"):
-        return be.gated_query_fwd(kind, a_rows, a_idx, b_rows, b_idx, w, rel, rel_idx, is_tail)
-    # backends without the gated kernels (the CPU test backend): the mix in torch, the fold through bilinear_query
-    known = _gated_known(a_rows, a_idx, b_rows, b_idx, w)[0]
-    rows = torch.arange(known.shape[0], dtype=torch.int32, device=known.device)
-    return be.bilinear_query_fwd(kind, known, rows, rel, rel_idx, is_tail)
-
-
-def _gated_known(a_rows, a_idx, b_rows, b_idx, w):
-    gated = (a_idx >= 0).view(-1, 1)
-    b = b_rows[b_idx.long()]
-    a = a_rows[a_idx.long().clamp(min=0)]
-    wc = w.reshape(-1, 1)
-    return torch.where(gated, wc * a + (1 - wc) * b, b), a, b, gated
-
-
-def _gated_query_bwd(be, kind, a_rows, a_idx, b_rows, b_idx, w, rel, rel_idx, is_tail, d_q):
-    if hasattr(be, "gated_query_bwd"):
-        return be.gated_query_bwd(kind, a_rows, a_idx, b_rows, b_idx, w, rel, rel_idx, is_tail, d_q)
-    known, a, b, gated = _gated_known(a_rows, a_idx, b_rows, b_idx, w)
-    rows = torch.arange(known.shape[0], dtype=torch.int32, device=known.device)
-    dk, dr = be.bilinear_query_bwd(kind, known, rows, rel, rel_idx, is_tail, d_q)
-    wc = w.reshape(-1, 1)
-    zero = torch.zeros_like(dk)
-    return (torch.where(gated, wc * dk, zero), torch.where(gated, (1 - wc) * dk, dk), dr,
-            torch.where(gated, dk * (a - b), zero).sum(dim=1))
-
-
-def _gather_ce_mix_fwd(be, s_a, s_b, w, cand):
-    if hasattr(be, "gather_ce_mix_fwd"):
-        return be.gather_ce_mix_fwd(s_a, s_b, w, cand)
-    return be.gather_ce_fwd(torch.lerp(s_b, s_a, w.reshape(-1, 1)), cand)
-
-
-def _gather_ce_mix_bwd(be, s_a, s_b, w, cand, lse, scale, inv_rows, row_scale):
-    if hasattr(be, "gather_ce_mix_bwd"):
-        return be.gather_ce_mix_bwd(s_a, s_b, w, cand, lse, scale, inv_rows, row_scale)
-    wc = w.reshape(-1, 1)
-    g = be.gather_ce_bwd(torch.lerp(s_b, s_a, wc), cand, lse, scale, inv_rows, row_scale)
-    d_a = g * wc
-    return d_a, g - d_a, (g * (s_a - s_b)).sum(dim=1)
-
-
-class _BatchedGatedLinkPredictionFn(torch.autograd.Function):
-    """The embedding-level gated loss of the post-aggregation models (PostDynamicRGCN / PostBiDynamicRGCN.train_link_prediction,
-    models/PostDynamicRGCN.py:261-282) over ALL windows as one autograd node:
-        q      = fold(w_known * loc_rows[known_a] + (1 - w_known) * rec_rows[known], rel)      (temp_gated_query_fwd; known_a < 0:
-                                                                                             the temporal row alone -- the head rows)
-        s_a/b  = q[rows of window b] . big_loc_b^T / big_rec_b^T                             (temp_linear_multi, same q for both)
-        loss   = sum_rows w_row * CE(w_cand * s_a + (1 - w_cand) * s_b at cand, label 0)     (temp_gather_ce_mix_fwd)
-    The candidate mix is linear in the candidate, so it lives on the two score matrices; the backward is one mixed-CE pass (both
-    score gradients and d_w_cand), two d_q products, two d_big products, one gated-query pass and three deterministic segment sums."""
-
-    @staticmethod
-    def forward(ctx, loc_rows, rec_rows, rel, big_loc, big_rec, w_known, w_cand, kind, inp):
-        be = get_backend()
-        N = big_loc.shape[0] // len(inp["splits"])
-        live = _live_windows(inp["splits"])
-        q = _gated_query_fwd(be, kind, loc_rows, inp["known_a"], rec_rows, inp["known"], w_known, rel, inp["rel"], inp["is_tail"])
-        sc = [_window_scores(be, q, big, live, N) for big in (big_loc, big_rec)]
-        loss_rows, lse = _gather_ce_mix_fwd(be, sc[0], sc[1], w_cand, inp["cand"])
-        ctx.save_for_backward(loc_rows, rec_rows, rel, big_loc, big_rec, w_known, w_cand, q, sc[0], sc[1], lse)
-        ctx.kind, ctx.inp, ctx.live, ctx.N = kind, inp, live, N
-        return (loss_rows * inp["weights"]).sum()
-
-    @staticmethod
-    def backward(ctx, d_loss):
-        loc_rows, rec_rows, rel, big_loc, big_rec, w_known, w_cand, q, s_a, s_b, lse = ctx.saved_tensors
-        inp, live, N = ctx.inp, ctx.live, ctx.N
-        be = get_backend()
-        d_sa, d_sb, d_wc = _gather_ce_mix_bwd(be, s_a, s_b, w_cand, inp["cand"], lse, d_loss.reshape(1).contiguous(), 1.0, inp["weights"])
-        d_q = _window_dq(be, d_sa, big_loc, live, N, q)
-        d_q2 = _window_dq(be, d_sb, big_rec, live, N, q)
-        d_q += d_q2
-        d_bigs = [_window_dbig(be, d_s, q, big, live, N, len(inp["splits"])) for big, d_s in ((big_loc, d_sa), (big_rec, d_sb))]
-        da, db, dr, d_wk = _gated_query_bwd(be, ctx.kind, loc_rows, inp["known_a"], rec_rows, inp["known"], w_known, rel, inp["rel"],
-                                            inp["is_tail"], d_q)
-        d_loc = be.segment_sum_rows(da, inp["known_a_inv"][0], inp["known_a_inv"][1], loc_rows.shape[0])
-        d_rec = be.segment_sum_rows(db, inp["known_inv"][0], inp["known_inv"][1], rec_rows.shape[0])
-        d_rel = be.segment_sum_rows(dr, inp["rel_inv"][0], inp["rel_inv"][1], rel.shape[0])
-        return (d_loc, d_rec, d_rel, d_bigs[0], d_bigs[1], d_wk.reshape(w_known.shape) if ctx.needs_input_grad[5] else None,
-                d_wc.reshape(w_cand.shape) if ctx.needs_input_grad[6] else None, None, None)
-
-
-def gated_loss_inputs(inp, n_loc_rows, device):
-    """The loss inputs of TKG_Module.loss_inputs (head rows NOT scored as tails) completed for the gated node: known_a = the row of
-    the LOCAL stream every query row mixes in -- the known subject's for tail rows, -1 (temporal only) for head rows, whose known
-    object is the temporal row alone in the reference (models/PostDynamicRGCN.py:276-277) -- and its segment-sum inverse."""
-    if inp is None:
-        return None
-    out = dict(inp)
-    ka = torch.where(inp["is_tail"] != 0, inp["known"], torch.full_like(inp["known"], -1)).contiguous()
-    out["known_a"] = ka
-    out["known_a_inv"] = gather_inverse(ka.cpu().numpy(), n_loc_rows, device)
-    return out
-
-
-def batched_gated_link_prediction(loc_rows, rec_rows, rel, big_loc, big_rec, w_known, w_cand, kind, inputs):
-    """sum over windows of the post-aggregation CE_tail + CE_head (see _BatchedGatedLinkPredictionFn).  w_known / w_cand (rows, 1):
-    per window [tail rows: w_oqs / w_oqo ; head rows: w_sqo / w_sqs]; `inputs` = gated_loss_inputs(TKG_Module.loss_inputs(...)).
-    big_loc / big_rec: the (B * N_ents, D) stacks of the windows' all-entity matrices.  kind 'distmult' | 'complex': the score-matrix
-    node; 'transE': the L1 node over the mixed candidate rows (_BatchedGatedTranslationLinkPredictionFn)."""
-    f = lambda t: t.reshape(-1, 1).to(loc_rows.dtype).contiguous()
-    if kind == "transE":
-        return _BatchedGatedTranslationLinkPredictionFn.apply(loc_rows.contiguous(), rec_rows.contiguous(), rel, big_loc.contiguous(),
-                                                              big_rec.contiguous(), f(w_known), f(w_cand), inputs)
-    return _BatchedGatedLinkPredictionFn.apply(loc_rows.contiguous(), rec_rows.contiguous(), rel, big_loc.contiguous(), big_rec.contiguous(),
-                                               f(w_known), f(w_cand), kind, inputs)
-
-
-def gated_link_prediction(loc, rec, rel, all_loc, all_rec, triplets, neg_tail, neg_head, w_sqs, w_sqo, w_oqs, w_oqo, kind):
-    """loss_tail + loss_head of ONE target graph (models/PostDynamicRGCN.py:200-202): the per-window form of
-    batched_gated_link_prediction for the unbatched path (one window, its own all-entity matrices)."""
-    from .tkg_module import TKG_Module
-    dev = loc.device
-    smp = [(triplets.to(torch.int64), neg_tail, neg_head)]
-    inp = gated_loss_inputs(TKG_Module.loss_inputs([0], smp, dev, loc.shape[0], rel.shape[0]), loc.shape[0], dev)
-    if inp is None:
-        return loc.sum() * 0.0
-    w_known = torch.cat([w_oqs.reshape(-1, 1), w_sqo.reshape(-1, 1)])
-    w_cand = torch.cat([w_oqo.reshape(-1, 1), w_sqs.reshape(-1, 1)])
-    return batched_gated_link_prediction(loc, rec, rel, all_loc, all_rec, w_known, w_cand, kind, inp)
-
-
-# -- TransE: the candidate loss over L1 distances ------------------------------------------------------------------------------
-_L1_METHODS = ("l1_ce_fwd", "l1_ce_bwd_q", "l1_ce_bwd_table", "l1_scores")
-
-
-def translation_supported(be=None):
-    """True when the installed backend has the L1 (TransE) kernels; a backend without them keeps the tensor path."""
-    be = get_backend() if be is None else be
-    return all(hasattr(be, m) for m in _L1_METHODS)
-
-
-def l1_slots(cand, base, n_rows):
-    """The slot lists of temp_l1_ce_bwd_table, built on the device: (slot_ptr int32 [n_rows + 1], slot int32 [P * C]) = the flat
-    positions p * C + k of `cand` grouped by their table row base[p] + cand[p, k] (base None = 0), ascending within a row (one
-    stable sort of the int32 row keys; the CSR by a binary search of the sorted keys: no host round trip)."""
-    keys = (cand if base is None else cand + base.view(-1, 1)).reshape(-1)
-    skeys, order = torch.sort(keys, stable=True)
-    edges = torch.arange(n_rows + 1, dtype=keys.dtype, device=keys.device)
-    return torch.searchsorted(skeys, edges, out_int32=True), order.to(torch.int32)
-
-
-def _cached_l1_slots(holder, cand, base, n_rows):
-    """l1_slots kept in `holder` = the loss inputs of a sample set (TKG_Module.loss_inputs documents the key; per_sample_set keeps
-    the dict for as long as the caller injects the same samples).  The entry is valid for the candidate matrix and the table size
-    it was built from: `base` is holder["window"] times the entities per window, so it follows from those two.  Fresh negatives
-    are a new candidate tensor and sort again every step."""
-    c = holder.get("_l1_slots")
-    if c is None or c[0] is not cand or c[1] != n_rows:
-        c = holder["_l1_slots"] = (cand, n_rows) + l1_slots(cand, base, n_rows)
-    return c[2], c[3]
-
-
-class _TranslationCEFn(torch.autograd.Function):
-    """mean_p CE(-|q[p] - all_embeds[cand[p, :]]|_1, label 0) without materialising (P, C, D)."""
-
-    @staticmethod
-    def forward(ctx, q, all_embeds, cand):
-        s, loss_rows, lse = get_backend().l1_ce_fwd(q, all_embeds, None, cand)
-        ctx.save_for_backward(q, all_embeds, cand, s, lse)
-        return loss_rows.mean()
-
-    @staticmethod
-    def backward(ctx, d_loss):
-        q, all_embeds, cand, s, lse = ctx.saved_tensors
-        be = get_backend()
-        g, d_q = be.l1_ce_bwd_q(q, all_embeds, None, cand, s, lse, d_loss.reshape(1).contiguous(), 1.0 / max(q.shape[0], 1))
-        slot_ptr, slot = l1_slots(cand, None, all_embeds.shape[0])
-        return d_q, be.l1_ce_bwd_table(q, all_embeds, slot_ptr, slot, g), None
-
-
-def translation_cross_entropy(q, all_embeds, cand):
-    """F.cross_entropy(transE score of the translation query q = s + r (tail) / o - r (head) against all_embeds[cand], 0)
-    (utils/scores.py:46-55).  cand: int32 (P, C), column 0 is the true entity."""
-    return _TranslationCEFn.apply(q.contiguous(), all_embeds.contiguous(), cand)
-
-
-class _BatchedTranslationLinkPredictionFn(torch.autograd.Function):
-    """_BatchedLinkPredictionFn for TransE, one autograd node:
-        q    = ent_rows[known] +- rel[rel_idx]                                         (temp_bilinear_query_fwd, kind transE)
-        s    = -|q[row] - big[window(row) * N + cand[row, :]]|_1  for ALL windows' rows    (temp_l1_ce_fwd, one launch)
-        loss = sum_rows w_row * CE(s[row, :], label 0)
-    The backward: the softmax gradient and d_q (temp_l1_ce_bwd_q), the candidate side into d_big over the slot lists
-    (temp_l1_ce_bwd_table), the query adjoint and the deterministic segment sums over the static index lists."""
-
-    @staticmethod
-    def forward(ctx, ent_rows, rel, big, inp):
-        be = get_backend()
-        N = big.shape[0] // len(inp["splits"])
-        q = be.bilinear_query_fwd("transE", ent_rows, inp["known"], rel, inp["rel"], inp["is_tail"])
-        base = inp["window"] * N
-        s, loss_rows, lse = be.l1_ce_fwd(q, big, base, inp["cand"])
-        ctx.save_for_backward(ent_rows, rel, big, q, s, lse, base)
-        ctx.inp = inp
-        return (loss_rows * inp["weights"]).sum()
-
-    @staticmethod
-    def backward(ctx, d_loss):
-        ent_rows, rel, big, q, s, lse, base = ctx.saved_tensors
-        inp = ctx.inp
-        be = get_backend()
-        g, d_q = be.l1_ce_bwd_q(q, big, base, inp["cand"], s, lse, d_loss.reshape(1).contiguous(), 1.0, inp["weights"])
-        slot_ptr, slot = _cached_l1_slots(inp, inp["cand"], base, big.shape[0])
-        d_big = be.l1_ce_bwd_table(q, big, slot_ptr, slot, g)
-        dk, dr = be.bilinear_query_bwd("transE", ent_rows, inp["known"], rel, inp["rel"], inp["is_tail"], d_q)
-        d_ent = be.segment_sum_rows(dk, inp["known_inv"][0], inp["known_inv"][1], ent_rows.shape[0])
-        d_rel = be.segment_sum_rows(dr, inp["rel_inv"][0], inp["rel_inv"][1], rel.shape[0])
-        return d_ent, d_rel, d_big, None
-
-
-_L1_MIX_METHODS = ("l1_mix_ce_fwd", "l1_mix_ce_bwd_q", "l1_mix_ce_bwd_table", "l1_mix_scores")
-
-
-def gated_translation_supported(be=None):
-    """True when the installed backend has the gated L1 (post-aggregation TransE) kernels; without them the tensor path stays."""
-    be = get_backend() if be is None else be
-    return all(hasattr(be, m) for m in _L1_MIX_METHODS)
-
-
-class _BatchedGatedTranslationLinkPredictionFn(torch.autograd.Function):
-    """_BatchedGatedLinkPredictionFn for TransE, one autograd node over ALL windows' rows:
-        q    = (w_known * loc_rows[known_a] + (1 - w_known) * rec_rows[known]) +- rel[rel_idx]     (temp_gated_query_fwd, kind transE;
-                                                                                                  known_a < 0: the temporal row alone)
-        e    = w_cand[row] * big_loc[window(row) * N + cand[row, :]] + (1 - w_cand[row]) * big_rec[...]   (formed in registers)
-        s    = -|q[row] - e|_1,   loss = sum_rows w_row * CE(s[row, :], label 0)                    (temp_l1_mix_ce_fwd, one launch)
-    |q - e|_1 is not linear in the candidate, so unlike the bilinear node the mix cannot live on two score matrices: the kernels read
-    both all-entity rows of every candidate.  The backward: the softmax gradient, d_q and d_w_cand (temp_l1_mix_ce_bwd_q), both
-    tables' adjoints in one pass over the slot lists (temp_l1_mix_ce_bwd_table), one gated-query pass and three segment sums."""
-
-    @staticmethod
-    def forward(ctx, loc_rows, rec_rows, rel, big_loc, big_rec, w_known, w_cand, inp):
-        be = get_backend()
-        N = big_loc.shape[0] // len(inp["splits"])
-        q = _gated_query_fwd(be, "transE", loc_rows, inp["known_a"], rec_rows, inp["known"], w_known, rel, inp["rel"], inp["is_tail"])
-        base = inp["window"] * N
-        s, loss_rows, lse = be.l1_mix_ce_fwd(q, big_loc, big_rec, w_cand, base, inp["cand"])
-        ctx.save_for_backward(loc_rows, rec_rows, rel, big_loc, big_rec, w_known, w_cand, q, s, lse, base)
-        ctx.inp = inp
-        return (loss_rows * inp["weights"]).sum()
-
-    @staticmethod
-    def backward(ctx, d_loss):
-        loc_rows, rec_rows, rel, big_loc, big_rec, w_known, w_cand, q, s, lse, base = ctx.saved_tensors
-        inp = ctx.inp
-        be = get_backend()
-        g, d_q, d_wc = be.l1_mix_ce_bwd_q(q, big_loc, big_rec, w_cand, base, inp["cand"], s, lse, d_loss.reshape(1).contiguous(), 1.0,
-                                          inp["weights"])
-        slot_ptr, slot = _cached_l1_slots(inp, inp["cand"], base, big_loc.shape[0])
-        d_big_loc, d_big_rec = be.l1_mix_ce_bwd_table(q, big_loc, big_rec, w_cand, slot_ptr, slot, g)
-        da, db, dr, d_wk = _gated_query_bwd(be, "transE", loc_rows, inp["known_a"], rec_rows, inp["known"], w_known, rel, inp["rel"],
-                                            inp["is_tail"], d_q)
-        d_loc = be.segment_sum_rows(da, inp["known_a_inv"][0], inp["known_a_inv"][1], loc_rows.shape[0])
-        d_rec = be.segment_sum_rows(db, inp["known_inv"][0], inp["known_inv"][1], rec_rows.shape[0])
-        d_rel = be.segment_sum_rows(dr, inp["rel_inv"][0], inp["rel_inv"][1], rel.shape[0])
-        return (d_loc, d_rec, d_rel, d_big_loc, d_big_rec, d_wk.reshape(w_known.shape) if ctx.needs_input_grad[5] else None,
-                d_wc.reshape(w_cand.shape) if ctx.needs_input_grad[6] else None, None)
-
-
-class _BatchedEnsembleTranslationLinkPredictionFn(torch.autograd.Function):
-    """_BatchedEnsembleLinkPredictionFn for TransE (the score-level ensemble of the post-ensemble models): each stream scores its own
-    translation query against its own all-entity stack at the candidates (temp_l1_ce_fwd; its lse and loss are not used), the
-    mixed score m = w s_loc + (1 - w) s_rec and its logsumexp are (rows, C) torch passes.  The backward hands the kernels the MIXED
-    softmax: temp_l1_ce_bwd_q with s = m, lse = lse_m and row_scale = weights * w (resp. weights * (1 - w)) gives each stream's
-    score gradient and d_q, temp_l1_ce_bwd_table its table adjoint; d_w = sum_k G_k (s_loc - s_rec) with G the unsplit gradient."""
-
-    @staticmethod
-    def forward(ctx, loc_rows, rec_rows, rel, big_loc, big_rec, w, inp):
-        be = get_backend()
-        N = big_loc.shape[0] // len(inp["splits"])
-        base = inp["window"] * N
-        qs, sc = [], []
-        for rows, big in ((loc_rows, big_loc), (rec_rows, big_rec)):
-            q = be.bilinear_query_fwd("transE", rows, inp["known"], rel, inp["rel"], inp["is_tail"])
-            qs.append(q)
-            sc.append(be.l1_ce_fwd(q, big, base, inp["cand"])[0])
-        mixed = torch.lerp(sc[1], sc[0], w)                          # w (rows, 1): w * local + (1 - w) * temporal
-        lse = torch.logsumexp(mixed, dim=1)
-        ctx.save_for_backward(loc_rows, rec_rows, rel, big_loc, big_rec, w, qs[0], qs[1], sc[0], sc[1], mixed, lse, base)
-        ctx.inp = inp
-        return ((lse - mixed[:, 0]) * inp["weights"]).sum()
-
-    @staticmethod
-    def backward(ctx, d_loss):
-        loc_rows, rec_rows, rel, big_loc, big_rec, w, q_l, q_r, s_l, s_r, mixed, lse, base = ctx.saved_tensors
-        inp = ctx.inp
-        be = get_backend()
-        scale = d_loss.reshape(1).contiguous()
-        wv = w.reshape(-1)
-        slot_ptr, slot = _cached_l1_slots(inp, inp["cand"], base, big_loc.shape[0])
-        outs, d_rel, gs = [], None, []
-        for rows, big, q, rs in ((loc_rows, big_loc, q_l, inp["weights"] * wv), (rec_rows, big_rec, q_r, inp["weights"] * (1 - wv))):
-            g, d_q = be.l1_ce_bwd_q(q, big, base, inp["cand"], mixed, lse, scale, 1.0, rs.contiguous())
-            gs.append(g)
-            d_big = be.l1_ce_bwd_table(q, big, slot_ptr, slot, g)
-            dk, dr = be.bilinear_query_bwd("transE", rows, inp["known"], rel, inp["rel"], inp["is_tail"], d_q)
-            outs.append((be.segment_sum_rows(dk, inp["known_inv"][0], inp["known_inv"][1], rows.shape[0]), d_big))
-            d_rel = dr if d_rel is None else d_rel + dr
-        d_rel = be.segment_sum_rows(d_rel, inp["rel_inv"][0], inp["rel_inv"][1], rel.shape[0])
-        d_w = None
-        if ctx.needs_input_grad[5]:
-            d_w = ((gs[0] + gs[1]) * (s_l - s_r)).sum(dim=1, keepdim=True)           # g_loc + g_rec = the unsplit mixed-score gradient
-        return outs[0][0], outs[1][0], d_rel, outs[0][1], outs[1][1], d_w, None
-
-
-def batched_link_prediction(ent_rows, rel, big, kind, inputs):
-    """sum over windows of CE_tail + CE_head (models/DynamicRGCN.py:186-193) for scorer `kind` ('distmult' | 'complex': the GEMM
-    node; 'transE': the L1 node); `inputs` = TKG_Module.loss_inputs(...)."""
-    if kind == "transE":
-        return _BatchedTranslationLinkPredictionFn.apply(ent_rows, rel, big, inputs)
-    return _BatchedLinkPredictionFn.apply(ent_rows, rel, big, kind, inputs)
-
-
-def candidate_cross_entropy_batched(query, cand, splits, row_w, all_embeds):
-    """query (R, D), cand (R, C) int32, splits = [(row_begin, row_end)] per window, row_w (R,) = weight of every row's loss
-    (1 / P_b for a mean per window and direction), all_embeds = list of (N, D) per window."""
-    return _BatchedCandidateCEFn.apply(query, cand, splits, row_w, *all_embeds)
-
-
-class _MixedCandidateCEFn(torch.autograd.Function):
-    """mean_p CE( w_p * (q_loc[p] . A_loc[cand[p, :]]^T) + (1 - w_p) * (q_rec[p] . A_rec[cand[p, :]]^T), label 0 ): the score-level
-    ensemble of the post-ensemble models (combined_scores, models/PostDynamicRGCN.py:404-406, 425-428) without the
-    (P, 1 + neg, D) gathers: both streams score against ALL entities (two small GEMMs), the mix is one pass over the (P, N) score
-    matrices, the candidate CE reads the mixed matrix."""
-
-    @staticmethod
-    def forward(ctx, q_loc, all_loc, q_rec, all_rec, w, cand):
-        be = get_backend()
-        s_loc = be.linear(q_loc, all_loc, True)                      # (P, N)
-        s_rec = be.linear(q_rec, all_rec, True)
-        mixed = torch.lerp(s_rec, s_loc, w)                          # w (P, 1): w * loc + (1 - w) * rec
-        loss_rows, lse = be.gather_ce_fwd(mixed, cand)
-        ctx.save_for_backward(q_loc, all_loc, q_rec, all_rec, w, cand, s_loc, s_rec, mixed, lse)
-        return loss_rows.mean()
-
-    @staticmethod
-    def backward(ctx, d_loss):
-        q_loc, all_loc, q_rec, all_rec, w, cand, s_loc, s_rec, mixed, lse = ctx.saved_tensors
-        be = get_backend()
-        d_mixed = be.gather_ce_bwd(mixed, cand, lse, d_loss.reshape(1).contiguous(), 1.0 / max(mixed.shape[0], 1))
-        d_loc = d_mixed * w
-        d_rec = d_mixed - d_loc
-        d_w = (d_mixed * (s_loc - s_rec)).sum(dim=1, keepdim=True) if ctx.needs_input_grad[4] else None
-        return (be.linear(d_loc, all_loc, False), be.linear_tn(d_loc, q_loc), be.linear(d_rec, all_rec, False), be.linear_tn(d_rec, q_rec),
-                d_w, None)
-
-
-def candidate_cross_entropy_mixed(q_loc, all_loc, q_rec, all_rec, w, cand):
-    """Score-level ensemble CE (see _MixedCandidateCEFn).  w: (P, 1) mixing weight of the local stream; cand: int32 (P, C), column
-    0 is the true entity."""
-    return _MixedCandidateCEFn.apply(q_loc.contiguous(), all_loc.contiguous(), q_rec.contiguous(), all_rec.contiguous(),
-                                     w.reshape(-1, 1).to(q_loc.dtype).contiguous(), cand)
-
-
-def candidate_cross_entropy(query, all_embeds, cand):
-    """F.cross_entropy(score(query, all_embeds[cand]), 0) for scorers that are bilinear in
-    (query, candidate) -- DistMult and ComplEx (utils/scores.py:4-44).  cand: int32 (P, C), column 0
-    is the true entity."""
-    return _CandidateCEFn.apply(query, all_embeds, cand)
+# The link-prediction loss (its autograd nodes, scorers and private switches) is temp_amd.link_loss; the functions callers reach
+# through this module are re-exported.  _TALL_SCORES, _L1_METHODS, _L1_MIX_METHODS and _cached_l1_slots are NOT: a copy of a switch
+# here would be one nobody reads.
+from .link_loss import (batched_ensemble_link_prediction, batched_gated_link_prediction, batched_link_prediction,  # noqa: E402,F401
+                        candidate_cross_entropy, candidate_cross_entropy_mixed, gated_link_prediction, gated_loss_inputs,
+                        gated_translation_supported, l1_slots, translation_cross_entropy, translation_supported)
 
 
 class _LinearFn(torch.autograd.Function):

@@ -1,0 +1,548 @@
+"""The link-prediction loss: torch.autograd nodes around the loss kernels (through temp_amd.backend).  temp_amd.functional re-exports
+the public functions; the private names (_TALL_SCORES, _L1_METHODS, _L1_MIX_METHODS, _cached_l1_slots, the node classes) live here.
+
+Three batched nodes, each written once over a scorer (_GemmScorer: distmult / complex, scores against ALL entities of a window;
+_L1Scorer: transE, distances to the candidates alone).  The backend calls of every node x scorer, forward | backward:
+
+  _BatchedLinkPredictionFn            sum over windows of CE_tail + CE_head (models/DynamicRGCN.py:186-193)
+    both     bilinear_query_fwd                                  | ... bilinear_query_bwd, segment_sum_rows x 2 (known, rel)
+    GEMM     linear_multi, gather_ce_fwd                         | gather_ce_bwd, linear_multi, linear_tn_multi
+             (TEMP_LOSS_TALL=1: linear_t per window)             |   (tall: linear_tn + linear per window)
+    L1       l1_ce_fwd                                           | l1_ce_bwd_q, l1_ce_bwd_table
+  _BatchedEnsembleLinkPredictionFn    score-level ensemble of two streams (models/PostDynamicRGCN.py:404-406, 425-428)
+    both     per stream: bilinear_query_fwd + its scores         | per stream: ..., bilinear_query_bwd, segment_sum_rows (known);
+             (mix = one torch.lerp)                              |   then segment_sum_rows (rel) of the streams' sum
+    GEMM     linear_multi per stream, gather_ce_fwd of the mix   | gather_ce_bwd once; per stream linear_multi, linear_tn_multi
+    L1       l1_ce_fwd per stream (logsumexp of the mix: torch)  | per stream l1_ce_bwd_q (the MIXED softmax, row_scale = weights * w
+                                                                 |   resp. weights * (1 - w)), l1_ce_bwd_table
+  _BatchedGatedLinkPredictionFn       embedding-level gate of the post-aggregation models (models/PostDynamicRGCN.py:261-282)
+    both     gated_query_fwd                                     | ... gated_query_bwd, segment_sum_rows x 3 (known_a, known, rel)
+    GEMM     linear_multi x 2 (one q), gather_ce_mix_fwd         | gather_ce_mix_bwd, linear_multi x 2, linear_tn_multi x 2
+    L1       l1_mix_ce_fwd                                       | l1_mix_ce_bwd_q, l1_mix_ce_bwd_table
+
+(linear_tn_multi: one linear_tn per live window on a backend without it; gated_query_* / gather_ce_mix_*: through bilinear_query_* /
+gather_ce_* and torch on a backend without them -- the CPU test backend.)  `big` is the (B * N, D) stack of the windows' all-entity
+matrices, inp = TKG_Module.loss_inputs(...) (gated_loss_inputs for the gated node); every gradient of a gathered operand is a
+deterministic segment sum over the static index lists.  The unbatched nodes (one target graph, the query rows given):
+  _CandidateCEFn       linear, gather_ce_fwd | gather_ce_bwd, linear, linear_tn
+  _MixedCandidateCEFn  linear x 2, gather_ce_fwd | gather_ce_bwd, (linear, linear_tn) x 2
+  _TranslationCEFn     l1_ce_fwd | l1_ce_bwd_q, l1_ce_bwd_table
+"""
+import os
+
+import torch
+
+from .backend import get_backend
+
+# Entity-major score GEMMs of the plain node (_GemmScorer.ce_fwd): 10 % less device time on ICEWS-shaped steps (3.51 -> 3.18 ms under
+# graph replay), but ~30 more launches per step, which makes an eager, host-bound training loop SLOWER (5.7 -> 6.8 ms/step measured).
+# Off unless TEMP_LOSS_TALL=1.
+_TALL_SCORES = os.environ.get("TEMP_LOSS_TALL", "0") == "1"
+
+_L1_METHODS = ("l1_ce_fwd", "l1_ce_bwd_q", "l1_ce_bwd_table", "l1_scores")
+_L1_MIX_METHODS = ("l1_mix_ce_fwd", "l1_mix_ce_bwd_q", "l1_mix_ce_bwd_table", "l1_mix_scores")
+
+
+def translation_supported(be=None):
+    """True when the installed backend has the L1 (TransE) kernels; a backend without them keeps the tensor path."""
+    be = get_backend() if be is None else be
+    return all(hasattr(be, m) for m in _L1_METHODS)
+
+
+def gated_translation_supported(be=None):
+    """True when the installed backend has the gated L1 (post-aggregation TransE) kernels; without them the tensor path stays."""
+    be = get_backend() if be is None else be
+    return all(hasattr(be, m) for m in _L1_MIX_METHODS)
+
+
+def l1_slots(cand, base, n_rows):
+    """The slot lists of temp_l1_ce_bwd_table, built on the device: (slot_ptr int32 [n_rows + 1], slot int32 [P * C]) = the flat
+    positions p * C + k of `cand` grouped by their table row base[p] + cand[p, k] (base None = 0), ascending within a row (one
+    stable sort of the int32 row keys; the CSR by a binary search of the sorted keys: no host round trip)."""
+    keys = (cand if base is None else cand + base.view(-1, 1)).reshape(-1)
+    skeys, order = torch.sort(keys, stable=True)
+    edges = torch.arange(n_rows + 1, dtype=keys.dtype, device=keys.device)
+    return torch.searchsorted(skeys, edges, out_int32=True), order.to(torch.int32)
+
+
+def _cached_l1_slots(holder, cand, base, n_rows):
+    """l1_slots kept in `holder` = the loss inputs of a sample set (TKG_Module.loss_inputs documents the key; per_sample_set keeps
+    the dict for as long as the caller injects the same samples).  The entry is valid for the candidate matrix and the table size
+    it was built from: `base` is holder["window"] times the entities per window, so it follows from those two.  Fresh negatives
+    are a new candidate tensor and sort again every step."""
+    c = holder.get("_l1_slots")
+    if c is None or c[0] is not cand or c[1] != n_rows:
+        c = holder["_l1_slots"] = (cand, n_rows) + l1_slots(cand, base, n_rows)
+    return c[2], c[3]
+
+
+# -- stages every node shares ---------------------------------------------------------------------------------------------------
+def _scale(d_loss):
+    return d_loss.reshape(1).contiguous()
+
+
+def _segment_sum(be, rows, inverse, n):
+    return be.segment_sum_rows(rows, inverse[0], inverse[1], n)
+
+
+def _query_fwd(be, kind, rows, rel, inp):
+    return be.bilinear_query_fwd(kind, rows, inp["known"], rel, inp["rel"], inp["is_tail"])
+
+
+def _query_bwd(be, kind, rows, rel, inp, d_q):
+    """-> (d_rows: the known rows' gradient summed over the static index list, the per-row gradient of the relation rows)."""
+    dk, dr = be.bilinear_query_bwd(kind, rows, inp["known"], rel, inp["rel"], inp["is_tail"], d_q)
+    return _segment_sum(be, dk, inp["known_inv"], rows.shape[0]), dr
+
+
+def _mix_adjoint(d_m, w):
+    """The adjoint of lerp(s_rec, s_loc, w) on the two score matrices."""
+    d_sl = d_m * w
+    return d_sl, d_m - d_sl
+
+
+def _mix_weight_grad(G, s_l, s_r):
+    """d_w = sum_k G_k (s_loc - s_rec), G the gradient of the mixed scores."""
+    return (G * (s_l - s_r)).sum(dim=1, keepdim=True)
+
+
+# -- the gated stages on a backend without the gated kernels (the CPU test backend) -----------------------------------------------
+def _gated_query_fwd(be, kind, a_rows, a_idx, b_rows, b_idx, w, rel, rel_idx, is_tail):
+    if hasattr(be, "gated_query_fwd"):
+        return be.gated_query_fwd(kind, a_rows, a_idx, b_rows, b_idx, w, rel, rel_idx, is_tail)
+    # the mix in torch, the fold through bilinear_query
+    known = _gated_known(a_rows, a_idx, b_rows, b_idx, w)[0]
+    rows = torch.arange(known.shape[0], dtype=torch.int32, device=known.device)
+    return be.bilinear_query_fwd(kind, known, rows, rel, rel_idx, is_tail)
+
+
+def _gated_known(a_rows, a_idx, b_rows, b_idx, w):
+    gated = (a_idx >= 0).view(-1, 1)
+    b = b_rows[b_idx.long()]
+    a = a_rows[a_idx.long().clamp(min=0)]
+    wc = w.reshape(-1, 1)
+    return torch.where(gated, wc * a + (1 - wc) * b, b), a, b, gated
+
+
+def _gated_query_bwd(be, kind, a_rows, a_idx, b_rows, b_idx, w, rel, rel_idx, is_tail, d_q):
+    if hasattr(be, "gated_query_bwd"):
+        return be.gated_query_bwd(kind, a_rows, a_idx, b_rows, b_idx, w, rel, rel_idx, is_tail, d_q)
+    known, a, b, gated = _gated_known(a_rows, a_idx, b_rows, b_idx, w)
+    rows = torch.arange(known.shape[0], dtype=torch.int32, device=known.device)
+    dk, dr = be.bilinear_query_bwd(kind, known, rows, rel, rel_idx, is_tail, d_q)
+    wc = w.reshape(-1, 1)
+    zero = torch.zeros_like(dk)
+    return (torch.where(gated, wc * dk, zero), torch.where(gated, (1 - wc) * dk, dk), dr,
+            torch.where(gated, dk * (a - b), zero).sum(dim=1))
+
+
+def _gather_ce_mix_fwd(be, s_a, s_b, w, cand):
+    if hasattr(be, "gather_ce_mix_fwd"):
+        return be.gather_ce_mix_fwd(s_a, s_b, w, cand)
+    return be.gather_ce_fwd(torch.lerp(s_b, s_a, w.reshape(-1, 1)), cand)
+
+
+def _gather_ce_mix_bwd(be, s_a, s_b, w, cand, lse, scale, inv_rows, row_scale):
+    if hasattr(be, "gather_ce_mix_bwd"):
+        return be.gather_ce_mix_bwd(s_a, s_b, w, cand, lse, scale, inv_rows, row_scale)
+    wc = w.reshape(-1, 1)
+    g = be.gather_ce_bwd(torch.lerp(s_b, s_a, wc), cand, lse, scale, inv_rows, row_scale)
+    d_a = g * wc
+    return d_a, g - d_a, (g * (s_a - s_b)).sum(dim=1)
+
+
+# -- the two scorers ------------------------------------------------------------------------------------------------------------
+# A scorer is made in a node's forward from the loss inputs and the all-entity stack and kept on the node (the one tensor it holds,
+# the L1 scorer's `base`, is saved by the node as well).  Every *_fwd also returns what the node saves for the matching *_bwd (`saved`).
+class _GemmScorer:
+    """distmult / complex: the score is bilinear in (query, candidate), so every live window's rows are scored against ALL its
+    entities (one multi-problem launch over the windows) and the candidate CE reads the (rows, N) matrix."""
+
+    def __init__(self, kind, inp, big):
+        self.kind, self.inp, self.tall = kind, inp, False
+        self.N = big.shape[0] // len(inp["splits"])
+        self.live = [(b, a0, a1) for b, (a0, a1) in enumerate(inp["splits"]) if a1 > a0]     # the windows that have rows
+
+    def _rows(self, x):
+        return [x[a0:a1] for _, a0, a1 in self.live]
+
+    def _blocks(self, big):
+        return [big[b * self.N:(b + 1) * self.N] for b, _, _ in self.live]
+
+    def _dbig_like(self, big):
+        """The gradient buffer of `big`: every live window's block is written whole, so only a batch with an empty window needs zeros."""
+        return torch.empty_like(big) if len(self.live) == len(self.inp["splits"]) else torch.zeros_like(big)
+
+    def scores(self, be, q, big):
+        """scores = q[rows of window b] . big_b^T for every live window -> (rows, N), one launch."""
+        scores = torch.empty(q.shape[0], self.N, dtype=torch.float32, device=q.device)
+        be.linear_multi(self._rows(q), self._blocks(big), True, scores)
+        return scores
+
+    def dq(self, be, d_s, q, big):
+        """d_q = d_scores_b . big_b for every live window, one launch."""
+        d_q = torch.empty_like(q)
+        be.linear_multi(self._rows(d_s), self._blocks(big), False, d_q)
+        return d_q
+
+    def dbig(self, be, d_s, q, big):
+        """d_big_b = d_scores_b^T . q_b for every live window."""
+        d_big = self._dbig_like(big)
+        if hasattr(be, "linear_tn_multi"):                                                    # one launch
+            be.linear_tn_multi(self._rows(d_s), self._rows(q), self._blocks(d_big))
+        else:
+            for (_, a0, a1), dst in zip(self.live, self._blocks(d_big)):
+                be.linear_tn(d_s[a0:a1], q[a0:a1], out=dst)
+        return d_big
+
+    def ce_fwd(self, be, q, big):
+        # few positives against many entities (ICEWS-like: ~200 rows x 10 000 entities per window): the ENTITY axis is made the
+        # tall one of every GEMM -- scores = (all_b . q_b^T)^T through a transposed-store epilogue, and the backward products
+        # from d_scores^T.  (The planner pads every window's block to a multiple of 4 rows so it can be an N / K extent.)
+        self.tall = _TALL_SCORES and all((a1 - a0) % 4 == 0 and 8 * (a1 - a0) <= self.N for _, a0, a1 in self.live)
+        if self.tall:
+            scores = torch.empty(q.shape[0], self.N, dtype=torch.float32, device=q.device)
+            for (_, a0, a1), all_b in zip(self.live, self._blocks(big)):
+                be.linear_t(all_b, q[a0:a1], True, scores[a0:a1])
+        else:
+            scores = self.scores(be, q, big)
+        loss_rows, lse = be.gather_ce_fwd(scores, self.inp["cand"])
+        return loss_rows, (scores, lse)
+
+    def ce_bwd(self, be, q, big, saved, scale):
+        scores, lse = saved
+        d_scores = be.gather_ce_bwd(scores, self.inp["cand"], lse, scale, 1.0, self.inp["weights"])
+        if not self.tall:
+            return self.dq(be, d_scores, q, big), self.dbig(be, d_scores, q, big)
+        d_q = torch.empty_like(q)
+        d_big = self._dbig_like(big)
+        for (_, a0, a1), all_b, d_all in zip(self.live, self._blocks(big), self._blocks(d_big)):
+            dst = d_scores[a0:a1].t().contiguous()                                        # (N, rows of window b)
+            be.linear_tn(dst, all_b, out=d_q[a0:a1])                                      # d_q   = d_scores . all_b
+            d_all.copy_(be.linear(dst, q[a0:a1], False))                                  # d_all = d_scores^T . q
+        return d_q, d_big
+
+    def mixed_ce_fwd(self, be, mixed):
+        loss_rows, lse = be.gather_ce_fwd(mixed, self.inp["cand"])
+        return loss_rows, lse, ()
+
+    def mixed_ce_bwd(self, be, mixed, lse, w, saved, scale):
+        """-> (the gradient of the mixed scores, each stream's share of it)."""
+        d_m = be.gather_ce_bwd(mixed, self.inp["cand"], lse, scale, 1.0, self.inp["weights"])
+        return d_m, _mix_adjoint(d_m, w)
+
+    def stream_bwd(self, be, q, big, d_s, mixed, lse, saved, scale):
+        return None, self.dq(be, d_s, q, big), self.dbig(be, d_s, q, big)
+
+    def mixed_grad(self, d_m, gs):
+        return d_m
+
+    def gated_ce_fwd(self, be, q, big_loc, big_rec, w_cand):
+        # the candidate mix is linear in the candidate, so it lives on the two score matrices (the same q for both)
+        s_a, s_b = [self.scores(be, q, big) for big in (big_loc, big_rec)]
+        loss_rows, lse = _gather_ce_mix_fwd(be, s_a, s_b, w_cand, self.inp["cand"])
+        return loss_rows, (s_a, s_b, lse)
+
+    def gated_ce_bwd(self, be, q, big_loc, big_rec, w_cand, saved, scale):
+        s_a, s_b, lse = saved
+        d_sa, d_sb, d_wc = _gather_ce_mix_bwd(be, s_a, s_b, w_cand, self.inp["cand"], lse, scale, 1.0, self.inp["weights"])
+        d_q = self.dq(be, d_sa, q, big_loc)
+        d_q2 = self.dq(be, d_sb, q, big_rec)
+        d_q += d_q2
+        return d_q, self.dbig(be, d_sa, q, big_loc), self.dbig(be, d_sb, q, big_rec), d_wc
+
+
+class _L1Scorer:
+    """transE: s = -|q[row] - big[window(row) * N + cand[row, :]]|_1 at the candidates alone, ALL windows' rows in one launch; the
+    candidate side of the adjoint runs over the slot lists (_cached_l1_slots).  |q - e|_1 is not linear in the candidate, so the gated
+    mix cannot live on two score matrices: the mix kernels read both all-entity rows of every candidate."""
+
+    def __init__(self, kind, inp, big):
+        self.kind, self.inp, self.n_rows = kind, inp, big.shape[0]
+        self.base = inp["window"] * (big.shape[0] // len(inp["splits"]))             # every row's offset into the all-entity stack
+
+    def _slots(self, base):
+        return _cached_l1_slots(self.inp, self.inp["cand"], base, self.n_rows)
+
+    def ce_fwd(self, be, q, big):
+        s, loss_rows, lse = be.l1_ce_fwd(q, big, self.base, self.inp["cand"])
+        return loss_rows, (s, lse, self.base)
+
+    def ce_bwd(self, be, q, big, saved, scale):
+        s, lse, base = saved
+        g, d_q = be.l1_ce_bwd_q(q, big, base, self.inp["cand"], s, lse, scale, 1.0, self.inp["weights"])
+        slot_ptr, slot = self._slots(base)
+        return d_q, be.l1_ce_bwd_table(q, big, slot_ptr, slot, g)
+
+    def scores(self, be, q, big):
+        return be.l1_ce_fwd(q, big, self.base, self.inp["cand"])[0]               # (its lse and loss are not used)
+
+    def mixed_ce_fwd(self, be, mixed):
+        lse = torch.logsumexp(mixed, dim=1)
+        return lse - mixed[:, 0], lse, (self.base,)
+
+    def mixed_ce_bwd(self, be, mixed, lse, w, saved, scale):
+        """-> (nothing yet, each stream's row scale): the kernels get the MIXED softmax, so row_scale = weights * w resp.
+        weights * (1 - w) gives each stream's score gradient."""
+        wv = w.reshape(-1)
+        self._slots(saved[0])                                                        # (sorted here, before the first stream)
+        return None, (self.inp["weights"] * wv, self.inp["weights"] * (1 - wv))
+
+    def stream_bwd(self, be, q, big, rs, mixed, lse, saved, scale):
+        base, = saved
+        g, d_q = be.l1_ce_bwd_q(q, big, base, self.inp["cand"], mixed, lse, scale, 1.0, rs.contiguous())
+        slot_ptr, slot = self._slots(base)
+        return g, d_q, be.l1_ce_bwd_table(q, big, slot_ptr, slot, g)
+
+    def mixed_grad(self, _, gs):
+        return gs[0] + gs[1]                                                         # g_loc + g_rec = the unsplit mixed-score gradient
+
+    def gated_ce_fwd(self, be, q, big_loc, big_rec, w_cand):
+        s, loss_rows, lse = be.l1_mix_ce_fwd(q, big_loc, big_rec, w_cand, self.base, self.inp["cand"])
+        return loss_rows, (s, lse, self.base)
+
+    def gated_ce_bwd(self, be, q, big_loc, big_rec, w_cand, saved, scale):
+        s, lse, base = saved
+        g, d_q, d_wc = be.l1_mix_ce_bwd_q(q, big_loc, big_rec, w_cand, base, self.inp["cand"], s, lse, scale, 1.0, self.inp["weights"])
+        slot_ptr, slot = self._slots(base)
+        d_big_loc, d_big_rec = be.l1_mix_ce_bwd_table(q, big_loc, big_rec, w_cand, slot_ptr, slot, g)
+        return d_q, d_big_loc, d_big_rec, d_wc
+
+
+def _scorer(kind, inp, big):
+    return (_L1Scorer if kind == "transE" else _GemmScorer)(kind, inp, big)
+
+
+# -- the batched nodes ----------------------------------------------------------------------------------------------------------
+class _BatchedLinkPredictionFn(torch.autograd.Function):
+    """The whole batched link-prediction loss as ONE autograd node:
+        q    = bilinear_query(ent_rows[known], rel[rel_idx])                     (gathers fused, temp_bilinear_query_fwd)
+        loss = sum_rows w_row * CE(score(q[row], candidates of the row), label 0)     (the scorer's ce_fwd)
+    The backward mirrors it and reduces the per-row gradients of the gathered operands with deterministic segment sums."""
+
+    @staticmethod
+    def forward(ctx, ent_rows, rel, big, kind, inp):
+        be = get_backend()
+        sc = _scorer(kind, inp, big)
+        q = _query_fwd(be, kind, ent_rows, rel, inp)
+        loss_rows, saved = sc.ce_fwd(be, q, big)
+        ctx.save_for_backward(ent_rows, rel, big, q, *saved)
+        ctx.scorer = sc
+        return (loss_rows * inp["weights"]).sum()
+
+    @staticmethod
+    def backward(ctx, d_loss):
+        ent_rows, rel, big, q = ctx.saved_tensors[:4]
+        sc, be = ctx.scorer, get_backend()
+        d_q, d_big = sc.ce_bwd(be, q, big, ctx.saved_tensors[4:], _scale(d_loss))
+        d_ent, dr = _query_bwd(be, sc.kind, ent_rows, rel, sc.inp, d_q)
+        return d_ent, _segment_sum(be, dr, sc.inp["rel_inv"], rel.shape[0]), d_big, None, None
+
+
+class _BatchedEnsembleLinkPredictionFn(torch.autograd.Function):
+    """_BatchedLinkPredictionFn for the score-level ensemble of the post-ensemble models (combined_scores,
+    models/PostDynamicRGCN.py:404-406, 425-428): TWO streams (local = pre-GRU, temporal = post-GRU) score their own query against
+    their own all-entity stack with the plain node's launches, the scores are mixed row by row with w (local) and 1 - w
+    (temporal), then the candidate cross-entropy of the mix."""
+
+    @staticmethod
+    def forward(ctx, loc_rows, rec_rows, rel, big_loc, big_rec, w, kind, inp):
+        be = get_backend()
+        sc = _scorer(kind, inp, big_loc)
+        qs, ss = [], []
+        for rows, big in ((loc_rows, big_loc), (rec_rows, big_rec)):
+            qs.append(_query_fwd(be, kind, rows, rel, inp))
+            ss.append(sc.scores(be, qs[-1], big))
+        mixed = torch.lerp(ss[1], ss[0], w)                          # w (rows, 1): w * local + (1 - w) * temporal
+        loss_rows, lse, saved = sc.mixed_ce_fwd(be, mixed)
+        ctx.save_for_backward(loc_rows, rec_rows, rel, big_loc, big_rec, w, qs[0], qs[1], ss[0], ss[1], mixed, lse, *saved)
+        ctx.scorer = sc
+        return (loss_rows * inp["weights"]).sum()
+
+    @staticmethod
+    def backward(ctx, d_loss):
+        loc_rows, rec_rows, rel, big_loc, big_rec, w, q_l, q_r, s_l, s_r, mixed, lse = ctx.saved_tensors[:12]
+        saved = ctx.saved_tensors[12:]
+        sc, be = ctx.scorer, get_backend()
+        scale = _scale(d_loss)
+        d_m, parts = sc.mixed_ce_bwd(be, mixed, lse, w, saved, scale)
+        outs, d_rel, gs = [], None, []
+        for rows, big, q, part in ((loc_rows, big_loc, q_l, parts[0]), (rec_rows, big_rec, q_r, parts[1])):
+            g, d_q, d_big = sc.stream_bwd(be, q, big, part, mixed, lse, saved, scale)
+            gs.append(g)
+            d_rows, dr = _query_bwd(be, sc.kind, rows, rel, sc.inp, d_q)
+            outs.append((d_rows, d_big))
+            d_rel = dr if d_rel is None else d_rel + dr
+        d_rel = _segment_sum(be, d_rel, sc.inp["rel_inv"], rel.shape[0])
+        d_w = _mix_weight_grad(sc.mixed_grad(d_m, gs), s_l, s_r) if ctx.needs_input_grad[5] else None
+        return outs[0][0], outs[1][0], d_rel, outs[0][1], outs[1][1], d_w, None, None
+
+
+class _BatchedGatedLinkPredictionFn(torch.autograd.Function):
+    """The embedding-level gated loss of the post-aggregation models (PostDynamicRGCN / PostBiDynamicRGCN.train_link_prediction,
+    models/PostDynamicRGCN.py:261-282) over ALL windows as one autograd node:
+        q    = fold(w_known * loc_rows[known_a] + (1 - w_known) * rec_rows[known], rel)      (temp_gated_query_fwd; known_a < 0:
+                                                                                           the temporal row alone -- the head rows)
+        loss = sum_rows w_row * CE(score(q[row], w_cand * big_loc[c] + (1 - w_cand) * big_rec[c]) over the row's candidates c, label 0)
+    The backward: the scorer's gated_ce_bwd (d_q, both stacks' gradients, d_w_cand), one gated-query pass, three segment sums."""
+
+    @staticmethod
+    def forward(ctx, loc_rows, rec_rows, rel, big_loc, big_rec, w_known, w_cand, kind, inp):
+        be = get_backend()
+        sc = _scorer(kind, inp, big_loc)
+        q = _gated_query_fwd(be, kind, loc_rows, inp["known_a"], rec_rows, inp["known"], w_known, rel, inp["rel"], inp["is_tail"])
+        loss_rows, saved = sc.gated_ce_fwd(be, q, big_loc, big_rec, w_cand)
+        ctx.save_for_backward(loc_rows, rec_rows, rel, big_loc, big_rec, w_known, w_cand, q, *saved)
+        ctx.scorer = sc
+        return (loss_rows * inp["weights"]).sum()
+
+    @staticmethod
+    def backward(ctx, d_loss):
+        loc_rows, rec_rows, rel, big_loc, big_rec, w_known, w_cand, q = ctx.saved_tensors[:8]
+        sc, be = ctx.scorer, get_backend()
+        inp = sc.inp
+        d_q, d_big_loc, d_big_rec, d_wc = sc.gated_ce_bwd(be, q, big_loc, big_rec, w_cand, ctx.saved_tensors[8:], _scale(d_loss))
+        da, db, dr, d_wk = _gated_query_bwd(be, sc.kind, loc_rows, inp["known_a"], rec_rows, inp["known"], w_known, rel, inp["rel"],
+                                            inp["is_tail"], d_q)
+        d_loc = _segment_sum(be, da, inp["known_a_inv"], loc_rows.shape[0])
+        d_rec = _segment_sum(be, db, inp["known_inv"], rec_rows.shape[0])
+        d_rel = _segment_sum(be, dr, inp["rel_inv"], rel.shape[0])
+        return (d_loc, d_rec, d_rel, d_big_loc, d_big_rec, d_wk.reshape(w_known.shape) if ctx.needs_input_grad[5] else None,
+                d_wc.reshape(w_cand.shape) if ctx.needs_input_grad[6] else None, None, None)
+
+
+def batched_link_prediction(ent_rows, rel, big, kind, inputs):
+    """sum over windows of CE_tail + CE_head (models/DynamicRGCN.py:186-193) for scorer `kind` ('distmult' | 'complex': the GEMM
+    scorer; 'transE': the L1 scorer); `inputs` = TKG_Module.loss_inputs(...)."""
+    return _BatchedLinkPredictionFn.apply(ent_rows, rel, big, kind, inputs)
+
+
+def batched_ensemble_link_prediction(loc_rows, rec_rows, rel, big_loc, big_rec, w, kind, inputs):
+    """sum over windows of the ensemble CE_tail + CE_head; `w` (rows, 1) = weight of the LOCAL stream of every stacked query row
+    (per window: [tail rows: weight_object ; head rows: weight_subject]); `inputs` = TKG_Module.loss_inputs(...)."""
+    w = w.reshape(-1, 1).to(loc_rows.dtype).contiguous()
+    return _BatchedEnsembleLinkPredictionFn.apply(loc_rows.contiguous(), rec_rows.contiguous(), rel, big_loc.contiguous(), big_rec.contiguous(),
+                                                  w, kind, inputs)
+
+
+def gated_loss_inputs(inp, n_loc_rows, device):
+    """The loss inputs of TKG_Module.loss_inputs (head rows NOT scored as tails) completed for the gated node: known_a = the row of
+    the LOCAL stream every query row mixes in -- the known subject's for tail rows, -1 (temporal only) for head rows, whose known
+    object is the temporal row alone in the reference (models/PostDynamicRGCN.py:276-277) -- and its segment-sum inverse."""
+    if inp is None:
+        return None
+    from .functional import gather_inverse
+    out = dict(inp)
+    ka = torch.where(inp["is_tail"] != 0, inp["known"], torch.full_like(inp["known"], -1)).contiguous()
+    out["known_a"] = ka
+    out["known_a_inv"] = gather_inverse(ka.cpu().numpy(), n_loc_rows, device)
+    return out
+
+
+def batched_gated_link_prediction(loc_rows, rec_rows, rel, big_loc, big_rec, w_known, w_cand, kind, inputs):
+    """sum over windows of the post-aggregation CE_tail + CE_head (see _BatchedGatedLinkPredictionFn).  w_known / w_cand (rows, 1):
+    per window [tail rows: w_oqs / w_oqo ; head rows: w_sqo / w_sqs]; `inputs` = gated_loss_inputs(TKG_Module.loss_inputs(...)).
+    big_loc / big_rec: the (B * N_ents, D) stacks of the windows' all-entity matrices.  kind 'distmult' | 'complex' | 'transE'."""
+    f = lambda t: t.reshape(-1, 1).to(loc_rows.dtype).contiguous()
+    return _BatchedGatedLinkPredictionFn.apply(loc_rows.contiguous(), rec_rows.contiguous(), rel, big_loc.contiguous(), big_rec.contiguous(),
+                                               f(w_known), f(w_cand), kind, inputs)
+
+
+def gated_link_prediction(loc, rec, rel, all_loc, all_rec, triplets, neg_tail, neg_head, w_sqs, w_sqo, w_oqs, w_oqo, kind):
+    """loss_tail + loss_head of ONE target graph (models/PostDynamicRGCN.py:200-202): the per-window form of
+    batched_gated_link_prediction for the unbatched path (one window, its own all-entity matrices)."""
+    from .tkg_module import TKG_Module
+    dev = loc.device
+    smp = [(triplets.to(torch.int64), neg_tail, neg_head)]
+    inp = gated_loss_inputs(TKG_Module.loss_inputs([0], smp, dev, loc.shape[0], rel.shape[0]), loc.shape[0], dev)
+    if inp is None:
+        return loc.sum() * 0.0
+    w_known = torch.cat([w_oqs.reshape(-1, 1), w_sqo.reshape(-1, 1)])
+    w_cand = torch.cat([w_oqo.reshape(-1, 1), w_sqs.reshape(-1, 1)])
+    return batched_gated_link_prediction(loc, rec, rel, all_loc, all_rec, w_known, w_cand, kind, inp)
+
+
+# -- the unbatched nodes: one target graph, the query rows given -------------------------------------------------------------------
+class _CandidateCEFn(torch.autograd.Function):
+    """mean_p CE(query[p] . all_embeds[cand[p, :]]^T, label 0) without materialising (P, C, D)."""
+
+    @staticmethod
+    def forward(ctx, query, all_embeds, cand):
+        be = get_backend()
+        scores = be.linear(query, all_embeds, True)                  # (P, N): every positive against ALL entities
+        loss_rows, lse = be.gather_ce_fwd(scores, cand)
+        ctx.save_for_backward(query, all_embeds, scores, lse, cand)
+        return loss_rows.mean()
+
+    @staticmethod
+    def backward(ctx, d_loss):
+        query, all_embeds, scores, lse, cand = ctx.saved_tensors
+        be = get_backend()
+        d_scores = be.gather_ce_bwd(scores, cand, lse, _scale(d_loss), 1.0 / max(scores.shape[0], 1))
+        d_query = be.linear(d_scores, all_embeds, False)             # (P,N) . (N,D)
+        d_all = be.linear_tn(d_scores, query)                        # (N,P) . (P,D)
+        return d_query, d_all, None
+
+
+def candidate_cross_entropy(query, all_embeds, cand):
+    """F.cross_entropy(score(query, all_embeds[cand]), 0) for scorers that are bilinear in (query, candidate) -- DistMult and ComplEx
+    (utils/scores.py:4-44).  cand: int32 (P, C), column 0 is the true entity."""
+    return _CandidateCEFn.apply(query, all_embeds, cand)
+
+
+class _MixedCandidateCEFn(torch.autograd.Function):
+    """mean_p CE( w_p * (q_loc[p] . A_loc[cand[p, :]]^T) + (1 - w_p) * (q_rec[p] . A_rec[cand[p, :]]^T), label 0 ): the score-level
+    ensemble of the post-ensemble models (combined_scores, models/PostDynamicRGCN.py:404-406, 425-428) without the
+    (P, 1 + neg, D) gathers: both streams score against ALL entities (two small GEMMs), the mix is one pass over the (P, N) score
+    matrices, the candidate CE reads the mixed matrix."""
+
+    @staticmethod
+    def forward(ctx, q_loc, all_loc, q_rec, all_rec, w, cand):
+        be = get_backend()
+        s_loc = be.linear(q_loc, all_loc, True)                      # (P, N)
+        s_rec = be.linear(q_rec, all_rec, True)
+        mixed = torch.lerp(s_rec, s_loc, w)                          # w (P, 1): w * loc + (1 - w) * rec
+        loss_rows, lse = be.gather_ce_fwd(mixed, cand)
+        ctx.save_for_backward(q_loc, all_loc, q_rec, all_rec, w, cand, s_loc, s_rec, mixed, lse)
+        return loss_rows.mean()
+
+    @staticmethod
+    def backward(ctx, d_loss):
+        q_loc, all_loc, q_rec, all_rec, w, cand, s_loc, s_rec, mixed, lse = ctx.saved_tensors
+        be = get_backend()
+        d_mixed = be.gather_ce_bwd(mixed, cand, lse, _scale(d_loss), 1.0 / max(mixed.shape[0], 1))
+        d_loc, d_rec = _mix_adjoint(d_mixed, w)
+        d_w = _mix_weight_grad(d_mixed, s_loc, s_rec) if ctx.needs_input_grad[4] else None
+        return (be.linear(d_loc, all_loc, False), be.linear_tn(d_loc, q_loc), be.linear(d_rec, all_rec, False), be.linear_tn(d_rec, q_rec),
+                d_w, None)
+
+
+def candidate_cross_entropy_mixed(q_loc, all_loc, q_rec, all_rec, w, cand):
+    """Score-level ensemble CE (see _MixedCandidateCEFn).  w: (P, 1) mixing weight of the local stream; cand: int32 (P, C), column
+    0 is the true entity."""
+    return _MixedCandidateCEFn.apply(q_loc.contiguous(), all_loc.contiguous(), q_rec.contiguous(), all_rec.contiguous(),
+                                     w.reshape(-1, 1).to(q_loc.dtype).contiguous(), cand)
+
+
+class _TranslationCEFn(torch.autograd.Function):
+    """mean_p CE(-|q[p] - all_embeds[cand[p, :]]|_1, label 0) without materialising (P, C, D)."""
+
+    @staticmethod
+    def forward(ctx, q, all_embeds, cand):
+        s, loss_rows, lse = get_backend().l1_ce_fwd(q, all_embeds, None, cand)
+        ctx.save_for_backward(q, all_embeds, cand, s, lse)
+        return loss_rows.mean()
+
+    @staticmethod
+    def backward(ctx, d_loss):
+        q, all_embeds, cand, s, lse = ctx.saved_tensors
+        be = get_backend()
+        g, d_q = be.l1_ce_bwd_q(q, all_embeds, None, cand, s, lse, _scale(d_loss), 1.0 / max(q.shape[0], 1))
+        slot_ptr, slot = l1_slots(cand, None, all_embeds.shape[0])
+        return d_q, be.l1_ce_bwd_table(q, all_embeds, slot_ptr, slot, g), None
+
+
+def translation_cross_entropy(q, all_embeds, cand):
+    """F.cross_entropy(transE score of the translation query q = s + r (tail) / o - r (head) against all_embeds[cand], 0)
+    (utils/scores.py:46-55).  cand: int32 (P, C), column 0 is the true entity."""
+    return _TranslationCEFn.apply(q.contiguous(), all_embeds.contiguous(), cand)

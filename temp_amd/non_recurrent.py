@@ -165,7 +165,7 @@ class Static(TKG_Non_Recurrent):
 
     def table_stack(self, times):
         """B times the same table, as an EXPANDED VIEW of ent_embeds made contiguous: both loss nodes address window b's table at
-        row b N of their operand (functional._window_scores slices it, the L1 node adds window * N to every candidate), so neither
+        row b N of their operand (link_loss._GemmScorer slices it, _L1Scorer adds window * N to every candidate), so neither
         takes a per-row base of 0 and the windows cannot share one copy; the view's adjoint sums the B blocks."""
         B = times.shape[0]
         return self.ent_embeds.unsqueeze(0).expand(B, self.num_ents, self.embed_size).reshape(B * self.num_ents, self.embed_size)

@@ -273,7 +273,7 @@ class _PostWindowMixin(_FrequencyGateMixin):
         P = triplets.shape[0]
         if self.fused_loss and name in ("distmult", "complex") and all_loc.shape[0] % 4 == 0 and P > 0:
             # both corruption directions stacked into one (2P)-row operand per stream; the two streams share the candidate lists and
-            # the per-row mixing weights, so the mix happens on the (2P, N) score matrices (functional._MixedCandidateCEFn)
+            # the per-row mixing weights, so the mix happens on the (2P, N) score matrices (link_loss._MixedCandidateCEFn)
             from . import scores
             t32 = triplets.to(torch.int32)
             r = TF.gather_rows(self.rel_embeds, t32[:, 1].contiguous())

@@ -146,7 +146,7 @@ class TKG_Module(nn.Module):
         per graph the stacked operand is [tail queries (P rows); head queries (P rows)].  `n_rows` / `n_rel_rows` (the row
         counts of the target-embedding stack and of rel_embeds) add the inverse maps the deterministic backward reduces over.
         `window` is the graph of every row (the TransE node turns it into the row's offset into the all-entity stack).  The TransE
-        node also keeps its slot lists in this dict under "_l1_slots" (functional._cached_l1_slots): callers cache the dict per
+        node also keeps its slot lists in this dict under "_l1_slots" (link_loss._cached_l1_slots): callers cache the dict per
         sample set (per_sample_set), so the lists live exactly as long as the samples they were sorted from."""
         known, rel, tail, cand, splits, weights, window = [], [], [], [], [], [], []
         row = 0

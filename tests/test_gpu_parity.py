@@ -821,8 +821,10 @@ def test_linear_t_transposed_store(M, N, K):
 
 def test_fused_loss_entity_major_variant_matches(monkeypatch):
     """The opt-in entity-major formulation of the fused loss (TEMP_LOSS_TALL=1: scores through temp_linear_t, backward from
-    d_scores^T) equals the default one on an ICEWS-shaped batch."""
-    from temp_amd import functional as TF
+    d_scores^T) equals the default one on an ICEWS-shaped batch -- and really is another route: the switch is patched in the module
+    that owns it, and only the tall arm calls linear_t."""
+    from temp_amd import link_loss as LL
+    from tests.post_attention_cases import recording
     from tests.window_cases import build_window_model
     from tests.golden_util import load
     z = load("G10_bi_grrgcn_rol")
@@ -832,12 +834,14 @@ def test_fused_loss_entity_major_variant_matches(monkeypatch):
     wb = m.prepare(t_list, int(z["L"]), train=True)
     res = []
     for tall in (False, True):
-        monkeypatch.setattr(TF, "_TALL_SCORES", tall)
+        monkeypatch.setattr(LL, "_TALL_SCORES", tall)
         for p in m.parameters():
             p.grad = None
         m.seed_rng = np.random.default_rng(7)
-        loss = m.run_loss(wb)
-        loss.backward()
+        with recording() as rec:
+            loss = m.run_loss(wb)
+            loss.backward()
+        assert (rec.count("linear_t") > 0) == tall and (rec.count("linear_multi") > 0) != tall
         res.append((loss.detach().clone(), m.ent_embeds.grad.clone(), m.rel_embeds.grad.clone()))
     assert abs(res[0][0].item() - res[1][0].item()) < 2e-5 * abs(res[0][0].item())
     assert_close(res[1][1], res[0][1], 1e-4, 1e-5 * float(res[0][1].abs().max()), "d ent_embeds")

@@ -714,7 +714,7 @@ def check_dropout_visits_self_attention(device, p=0.1):
 
 
 def check_fused_ensemble_loss(device, head_as_tail):
-    """ensemble_loss through the fused node (functional._MixedCandidateCEFn: scores of both streams against ALL entities, mixed on
+    """ensemble_loss through the fused node (link_loss._MixedCandidateCEFn: scores of both streams against ALL entities, mixed on
     the score matrices) against the reference-shaped formulation (gather (P, 1 + neg, D) candidates per stream, mix, CE;
     models/PostDynamicRGCN.py:335-349, 404-406): value and every gradient, incl. the mixing weights'."""
     from temp_amd.post_dynamic_rgcn import PostEnsembleBiDynamicRGCN, PostEnsembleDynamicRGCN

@@ -14,7 +14,7 @@ import torch
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import bench  # noqa: E402
 from temp_amd import backend as TB  # noqa: E402
-from temp_amd import functional as TF  # noqa: E402
+from temp_amd import link_loss as LL  # noqa: E402
 from temp_amd import scores as SC  # noqa: E402
 from temp_amd import synthetic  # noqa: E402
 from temp_amd.evaluation import EvaluationFilter  # noqa: E402
@@ -34,7 +34,7 @@ class NoL1:
         self._be = be
 
     def __getattr__(self, name):
-        if name in TF._L1_METHODS:
+        if name in LL._L1_METHODS:
             raise AttributeError(name)
         return getattr(self._be, name)
 
