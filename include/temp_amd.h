@@ -526,6 +526,19 @@ int temp_gru_grads_g4_keys(int count, const int* ns, int d, const float* const* 
                            const uint32_t* const* g4_col_keys, const uint32_t* const* x_col_keys /* nullable (array or entries): [d] keys
                            bounding the column magnitudes of xs[i], e.g. from temp_gather_rows_keys; else taken here with one pass */,
                            void* workspace, size_t workspace_bytes, void* stream);
+/* temp_gru_grads_g4_keys with the GRUs' input rows read IN PLACE: row m of GRU i's x is table[x_rows[i][m]] (table: [table_rows][d];
+ * x_rows: HOST array of `count` device int32 lists of ns[i] entries, each 0 <= r < table_rows -- not checked on the device).  No
+ * copy of the rows in GRU order is needed (k_gru_wgrad_hx_rows forms each staged row's offset from its entry, loaded ahead of the
+ * row).  The keys are required, x_col_keys[i] included (keys bounding the table's columns bound any selection of its rows); the
+ * results equal temp_gru_grads_g4_keys on the gathered copy with the same keys bit for bit.  d_xs as there (GRU row order).
+ * TEMP_E_UNSUPPORTED (nothing launched) where temp_gru_grads_g4_rows_supported returns 0: shapes temp_gru_grads_g4 refuses,
+ * TEMP_OPT_MFMA_F16X2 = 0, table_rows . d . 4 or ns[i] . d . 4 >= 2^32 (32-bit lane offsets), or a row slice whose row list does not
+ * fit LDS behind the slab buffers (more than about 14 000 rows per slice: GRUs of several hundred thousand rows).  Same workspace. */
+int temp_gru_grads_g4_rows_supported(int count, const int* ns, int d, int table_rows);
+int temp_gru_grads_g4_rows(int count, const int* ns, int d, const float* table, int table_rows, const int32_t* const* x_rows,
+                           const float* const* hdecs, const float* const* g4s, const float* const* w_ihs, float* const* d_xs, float* d_w,
+                           float* d_b, const uint32_t* const* g4_row_keys, const uint32_t* const* g4_col_keys,
+                           const uint32_t* const* x_col_keys, void* workspace, size_t workspace_bytes, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
  * Persistent window chain: ALL positions of the recurrence in ONE launch per direction of time.

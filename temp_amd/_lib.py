@@ -200,6 +200,8 @@ SYMBOLS = {
     "temp_gru_chain_pack_multi_layout": (_I, [_I, _I, _I, ctypes.POINTER(c_vp), ctypes.POINTER(c_vp), c_vp]),
     "temp_gru_chain_offset_launches": (ctypes.c_longlong, []),
     "temp_gru_grads_g4_keys": (_I, [_I, c_vp, _I, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, ctypes.c_size_t, c_vp]),
+    "temp_gru_grads_g4_rows_supported": (_I, [_I, c_vp, _I, _I]),
+    "temp_gru_grads_g4_rows": (_I, [_I, c_vp, _I, c_vp, _I, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, ctypes.c_size_t, c_vp]),
     "temp_gru_grads_g4_workspace": (ctypes.c_size_t, [_I, c_vp, _I]),
     "temp_gru_grads_g4": (_I, [_I, c_vp, _I, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, ctypes.c_size_t, c_vp]),
     "temp_gather_rows": (_I, [_I, _I, c_vp, c_vp, c_vp, c_vp]),

@@ -616,6 +616,39 @@ class HipBackend:
         _lib.check(rc, "temp_gru_grads_g4")
         return [(d_w[2 * i], d_w[2 * i + 1], d_b[2 * i], d_b[2 * i + 1]) for i in range(k)]
 
+    def gru_grads_g4_rows_supported(self, ns, d, variant, table_rows):
+        """True when gru_grads_g4_rows takes GRUs of these row counts and this width over a table of `table_rows` rows."""
+        k = len(ns)
+        if k < 1 or k > 4 or variant != _lib.GRU_TORCH:
+            return False
+        return bool(self.lib.temp_gru_grads_g4_rows_supported(k, (ctypes.c_int * k)(*[int(n) for n in ns]), int(d), int(table_rows)))
+
+    def gru_grads_g4_rows(self, table, x_rows, hdecs, g4s, w_ihs, d_xs, row_keys, col_keys, x_col_keys):
+        """gru_grads_g4 on the f16 pipe with every GRU's input rows read in place: row m of GRU i's x is table[x_rows[i][m]] (x_rows:
+        int32 device lists, 0 <= r < table rows; include/temp_amd.h: temp_gru_grads_g4_rows) -- bit for bit what gru_grads_g4 gives on
+        the gathered rows with the same keys, all of which are required.  d_xs: in GRU row order."""
+        table = _f32(table, "table")
+        k, d, dev = len(x_rows), table.shape[1], table.device
+        ns = (ctypes.c_int * k)(*[r.shape[0] for r in x_rows])
+        nb = self.lib.temp_gru_grads_g4_workspace(k, ns, d)
+        if nb == 0:
+            raise ValueError("temp_gru_grads_g4_rows: unsupported shape (check gru_grads_g4_supported first)")
+        x_rows = [_i32(r, "x_rows") for r in x_rows]
+        keep = [[_f32(t, "operand") for t in ts] for ts in (hdecs, w_ihs)]
+        for g, r, h, rk, ck, xk in zip(g4s, x_rows, keep[0], row_keys, col_keys, x_col_keys):
+            assert g.dtype == torch.float32 and g.is_contiguous() and g.shape == (r.shape[0], 4 * d) and h.shape == (r.shape[0], d)
+            assert all(t.dtype == torch.int32 and t.is_contiguous() for t in (rk, ck, xk))
+            assert rk.numel() == r.shape[0] and ck.numel() == 4 * d and xk.numel() == d
+        arr = lambda ts: (ctypes.c_void_p * k)(*[t.data_ptr() for t in ts])
+        dx = (ctypes.c_void_p * k)(*[None if t is None else t.data_ptr() for t in d_xs])
+        d_w = torch.empty(2 * k, 3 * d, d, dtype=torch.float32, device=dev)
+        d_b = torch.empty(2 * k, 3 * d, dtype=torch.float32, device=dev)
+        ws = self._ws(nb, dev)
+        rc = self.lib.temp_gru_grads_g4_rows(k, ns, d, _ptr(table), table.shape[0], arr(x_rows), arr(keep[0]), arr(g4s), arr(keep[1]), dx,
+                                             _ptr(d_w), _ptr(d_b), arr(row_keys), arr(col_keys), arr(x_col_keys), _ptr(ws), ws.numel(), _stream())
+        _lib.check(rc, "temp_gru_grads_g4_rows")
+        return [(d_w[2 * i], d_w[2 * i + 1], d_b[2 * i], d_b[2 * i + 1]) for i in range(k)]
+
     def gru_weight_grads(self, x, hdec, dgi, dgh, w_ih, variant, d_x):
         n, d = x.shape
         w_ih = _f32(w_ih, "w_ih")

@@ -14,7 +14,7 @@ from . import snapshot as S
 from .birrgcn import BiGRRGCNLayer, BiRRGCN
 from .dynamic_rgcn import DynamicRGCN, WindowBatch
 from .gru_cell import GRUCell
-from .gru_chain import GruInstance, GruProgram, gru_chain, chain_kernels_usable, offset_tables
+from .gru_chain import GruInstance, GruProgram, gru_chain, chain_kernels_usable, offset_tables, rows_in_place_usable
 from .rrgcn import run_rnn
 from .window import ChainPlan, Step, window_times
 
@@ -104,12 +104,19 @@ class BiDynamicRGCN(DynamicRGCN):
             # (the gather also hands out the magnitude keys of the rows it writes: the f16 products of the chain scale x by them)
             keyed = TF.gather_keys_supported(y2.shape[1]) and chain_kernels_usable(y2.shape[1], 2)
             x_keys = None
-            if keyed:
+            type1, off = isinstance(l2.forward_rnn, GRUCell), self._chain_offset(wb)
+            if keyed and self.rows_in_place and rows_in_place_usable(prog, y2, wb.chain_inv, 2, type1, want, dec, off):
+                # the chain reads its rows of y2 where they lie: no copy into chain order (and none in wb.last_x)
+                wb.last_x = None
+                got = dict(zip(want, gru_chain(None, prog, [l2.forward_rnn, l2.backward_rnn], lam, type1, want=want,
+                                               table=(y2, wb.chain_rows, wb.chain_inv, fold))))
+            elif keyed:
                 wb.last_x, x_keys = TF.gather_rows(y2, wb.chain_rows, wb.chain_inv, relu_table=fold, keys=True)
             else:
                 wb.last_x = TF.gather_rows(y2, wb.chain_rows, wb.chain_inv, relu_table=fold)      # GRU input rows in chain order
-            got = dict(zip(want, gru_chain(wb.last_x, prog, [l2.forward_rnn, l2.backward_rnn], lam,
-                                           isinstance(l2.forward_rnn, GRUCell), want=want, x_keys=x_keys, decay=dec, offset=self._chain_offset(wb))))
+            if wb.last_x is not None:
+                got = dict(zip(want, gru_chain(wb.last_x, prog, [l2.forward_rnn, l2.backward_rnn], lam, type1, want=want, x_keys=x_keys,
+                                               decay=dec, offset=off)))
             out = got[wb.out_inst[0]] + got[wb.out_inst[1]]
             if enc.use_time_embedding:                        # the centre step adds it ONCE to h_f + h_b (models/BiRRGCN.py:221-225)
                 out = out + TF.gather_rows(l2.time_embed, wb.target_time[0], wb.target_time[1])
@@ -147,6 +154,9 @@ class BiDynamicRGCN(DynamicRGCN):
             out = out + l2.get_time_embedding(tf.times, tf.sizes)
         return out, ((Hf, Hf), (Hb, Hb))
 
+    def _chain_rows_host(self, wb):
+        return wb.chain_rows_np
+
     def _chain_rnns(self):
         l2 = self.ent_encoder.layer_2
         return [l2.forward_rnn, l2.backward_rnn]
@@ -183,6 +193,7 @@ class BiDynamicRGCN(DynamicRGCN):
         t_rows = base[tf.row0:tf.row0 + nt]
         chain = np.concatenate([f_rows, t_rows, b_rows, t_rows])
         wb.chain_rows = _lib.to_device(chain.astype(np.int32), self._device())
+        wb.chain_rows_np = chain
         wb.chain_inv = TF.gather_inverse(chain, int(wb.g_all.n), self._device())
         _lib.pause_point()
         inst = []

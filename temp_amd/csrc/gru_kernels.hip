@@ -561,6 +561,17 @@ static int launch_gru_wgrad_hx(const WgArgs& a, const WgxKeys& keys, hipStream_t
 }
 
 template <int NT>
+static int launch_gru_wgrad_hx_rows(const WgArgs& a, const WgxKeys& keys, const WgxRows& rows, hipStream_t st) {
+  const size_t lds = wgx_rows_lds_bytes(NT, a.rows_per_slice);   // (the slab buffers + the row list of a slice)
+  if (lds > WGX_LDS_MAX) return TEMP_E_UNSUPPORTED;
+  static const bool granted = hipFuncSetAttribute(reinterpret_cast<const void*>(k_gru_wgrad_hx_rows<NT>), hipFuncAttributeMaxDynamicSharedMemorySize, WGX_LDS_MAX) == hipSuccess;
+  if (!granted) { (void)hipGetLastError(); return TEMP_E_UNSUPPORTED; }
+  TEMP_LAUNCH(K_GRU_WGRAD, (k_gru_wgrad_hx_rows<NT>), dim3(8 * a.per_xcd * a.P), dim3(WG_THREADS), lds, st, a, keys, rows);
+  hx_count();
+  return TEMP_OK;
+}
+
+template <int NT>
 static int launch_gru_wgrad(const WgArgs& a, hipStream_t st) {
   static const bool granted = hipFuncSetAttribute(reinterpret_cast<const void*>(k_gru_wgrad<NT>), hipFuncAttributeMaxDynamicSharedMemorySize, wg_lds_bytes(NT)) == hipSuccess;
   if (!granted) { (void)hipGetLastError(); return TEMP_E_UNSUPPORTED; }
@@ -913,10 +924,12 @@ int temp_gru_grads_g4(int count, const int* ns, int d, const float* const* xs, c
   return temp_gru_grads_g4_keys(count, ns, d, xs, hdecs, g4s, w_ihs, d_xs, d_w, d_b, nullptr, nullptr, nullptr, workspace, workspace_bytes, stream);
 }
 
-int temp_gru_grads_g4_keys(int count, const int* ns, int d, const float* const* xs, const float* const* hdecs, const float* const* g4s,
-                           const float* const* w_ihs, float* const* d_xs, float* d_w, float* d_b, const uint32_t* const* g4_row_keys,
-                           const uint32_t* const* g4_col_keys, const uint32_t* const* x_col_keys, void* workspace, size_t workspace_bytes,
-                           void* stream) {
+// x_rows = nullptr: xs[i] are the GRUs' input rows.  Else (temp_gru_grads_g4_rows): every xs[i] is the one table and x_rows[i][m] the
+// table row that is row m of GRU i's input; keyed f16 arithmetic with the caller's x column keys only.
+static int gru_grads_g4_impl(int count, const int* ns, int d, const float* const* xs, const int32_t* const* x_rows, const float* const* hdecs,
+                             const float* const* g4s, const float* const* w_ihs, float* const* d_xs, float* d_w, float* d_b,
+                             const uint32_t* const* g4_row_keys, const uint32_t* const* g4_col_keys, const uint32_t* const* x_col_keys,
+                             void* workspace, size_t workspace_bytes, void* stream) {
   if (count <= 0 || count > WG_MAXG || !ns || !xs || !hdecs || !g4s || !w_ihs || !d_xs || !d_w || !d_b) return TEMP_E_BADARG;
   WgArgs a = {};
   if (!grads_g4_plan(count, ns, d, &a)) return TEMP_E_UNSUPPORTED;
@@ -933,6 +946,8 @@ int temp_gru_grads_g4_keys(int count, const int* ns, int d, const float* const* 
   int rc;
   bool hx = hx_enabled() && g4_col_keys != nullptr;
   for (int i = 0; i < count && hx; ++i) hx = g4_col_keys[i] != nullptr;
+  // (rows in place: the f16 kernel only, and a slice's row list must fit LDS behind the slab buffers -- nothing launched otherwise)
+  if (x_rows && (!hx || wgx_rows_lds_bytes(wg_col_tiles(d) < 8 ? wg_col_tiles(d) : 8, a.rows_per_slice) > WGX_LDS_MAX)) return TEMP_E_UNSUPPORTED;
   // d_x = [dr dz dn_i] . W_ih: the first 3d columns of a g4 row (row stride 4d).  It reads g4 and W_ih only -- nothing the weight
   // gradients write -- so it MAY run on the side stream beside them (side_stream.hpp; a parallel branch of a captured graph).
   // Measured (same-box A/B, S-gdelt): 4 us of a 1.97-ms step -- two matrix-pipe kernels at the power cap share the pipe, only the
@@ -959,6 +974,20 @@ int temp_gru_grads_g4_keys(int count, const int* ns, int d, const float* const* 
       keys.x[i] = xk + (size_t)i * d;
       launch_absmax_keys(ns[i], d, xs[i], d, nullptr, xk + (size_t)i * d, xk + (size_t)count * d + (size_t)i * ABSMAX_BLOCKS * d, st);
     }
+    if (x_rows) {
+      WgxRows rows = {};
+      for (int i = 0; i < count; ++i) rows.r[i] = x_rows[i];
+      switch (wg_col_tiles(d)) {
+        case 1: rc = launch_gru_wgrad_hx_rows<1>(a, keys, rows, st); break;
+        case 2: rc = launch_gru_wgrad_hx_rows<2>(a, keys, rows, st); break;
+        case 3: rc = launch_gru_wgrad_hx_rows<3>(a, keys, rows, st); break;
+        case 4: rc = launch_gru_wgrad_hx_rows<4>(a, keys, rows, st); break;
+        case 5: rc = launch_gru_wgrad_hx_rows<5>(a, keys, rows, st); break;
+        case 6: rc = launch_gru_wgrad_hx_rows<6>(a, keys, rows, st); break;
+        case 7: rc = launch_gru_wgrad_hx_rows<7>(a, keys, rows, st); break;
+        default: rc = launch_gru_wgrad_hx_rows<8>(a, keys, rows, st); break;
+      }
+    } else
     switch (wg_col_tiles(d)) {
       case 1: rc = launch_gru_wgrad_hx<1>(a, keys, st); break;
       case 2: rc = launch_gru_wgrad_hx<2>(a, keys, st); break;
@@ -992,6 +1021,38 @@ int temp_gru_grads_g4_keys(int count, const int* ns, int d, const float* const* 
   }
   if (nx > 0) rc = launch_gemm_panel_multi(K_GEMM_GRU_DX, batch, nx, d, 3 * d, 4 * d, d, 0, st);
   return rc ? rc : launch_status();
+}
+
+int temp_gru_grads_g4_keys(int count, const int* ns, int d, const float* const* xs, const float* const* hdecs, const float* const* g4s,
+                           const float* const* w_ihs, float* const* d_xs, float* d_w, float* d_b, const uint32_t* const* g4_row_keys,
+                           const uint32_t* const* g4_col_keys, const uint32_t* const* x_col_keys, void* workspace, size_t workspace_bytes,
+                           void* stream) {
+  return gru_grads_g4_impl(count, ns, d, xs, nullptr, hdecs, g4s, w_ihs, d_xs, d_w, d_b, g4_row_keys, g4_col_keys, x_col_keys, workspace,
+                           workspace_bytes, stream);
+}
+
+int temp_gru_grads_g4_rows_supported(int count, const int* ns, int d, int table_rows) {
+  WgArgs a = {};
+  if (table_rows <= 0 || !hx_enabled() || !grads_g4_plan(count, ns, d, &a)) return 0;
+  if ((unsigned long long)table_rows * (unsigned long long)d * 4ull >= (1ull << 32)) return 0;
+  for (int i = 0; i < count; ++i)
+    if ((unsigned long long)ns[i] * (unsigned long long)d * 4ull >= (1ull << 32)) return 0;
+  return wgx_rows_lds_bytes(wg_col_tiles(d) < 8 ? wg_col_tiles(d) : 8, a.rows_per_slice) <= WGX_LDS_MAX ? 1 : 0;
+}
+
+int temp_gru_grads_g4_rows(int count, const int* ns, int d, const float* table, int table_rows, const int32_t* const* x_rows,
+                           const float* const* hdecs, const float* const* g4s, const float* const* w_ihs, float* const* d_xs, float* d_w,
+                           float* d_b, const uint32_t* const* g4_row_keys, const uint32_t* const* g4_col_keys,
+                           const uint32_t* const* x_col_keys, void* workspace, size_t workspace_bytes, void* stream) {
+  if (count <= 0 || count > WG_MAXG || !table || table_rows <= 0 || !x_rows || !g4_row_keys || !g4_col_keys || !x_col_keys) return TEMP_E_BADARG;
+  if (!ns || !temp_gru_grads_g4_rows_supported(count, ns, d, table_rows)) return TEMP_E_UNSUPPORTED;   // (32-bit lane offsets, LDS row list)
+  const float* xs[WG_MAXG];
+  for (int i = 0; i < count; ++i) {
+    if (!x_rows[i] || !g4_col_keys[i] || !x_col_keys[i]) return TEMP_E_BADARG;
+    xs[i] = table;
+  }
+  return gru_grads_g4_impl(count, ns, d, xs, x_rows, hdecs, g4s, w_ihs, d_xs, d_w, d_b, g4_row_keys, g4_col_keys, x_col_keys, workspace,
+                           workspace_bytes, stream);
 }
 
 }  // extern "C"

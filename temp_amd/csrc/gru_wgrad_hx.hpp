@@ -23,11 +23,17 @@ namespace temp {
 #endif
 
 struct WgxKeys { const unsigned* g[WG_MAXG]; const unsigned* x[WG_MAXG]; };      // per GRU: column keys of g4 [4d] and of x [d]
+// k_gru_wgrad_hx_rows: the x operand of every GRU is read IN PLACE from one table -- G.x is the table, r[i][m] its row for row m of
+// GRU i (the caller's: 0 <= r < table rows, table rows . d . 4 < 2^32) -- instead of from a copy in row order
+struct WgxRows { const int32_t* r[WG_MAXG]; };
 
 __host__ __device__ constexpr int wgx_a_bytes() { return 8 * 2 * 1024; }
 __host__ __device__ constexpr int wgx_b_bytes(int NT) { return 2 * 16 * wg_bs(NT); }
 __host__ __device__ constexpr int wgx_buf_bytes(int NT) { return wgx_a_bytes() + 2 * wgx_b_bytes(NT); }
 __host__ __device__ constexpr int wgx_lds_bytes(int NT) { return 2 * wgx_buf_bytes(NT); }
+#define WGX_LDS_MAX (160 * 1024)
+// k_gru_wgrad_hx_rows: + one int per row of a slice (rows_per_slice is a multiple of 16; the tail shares are shorter)
+inline size_t wgx_rows_lds_bytes(int NT, int rows_per_slice) { return (size_t)wgx_lds_bytes(NT) + 4 * (size_t)rows_per_slice; }
 
 // two consecutive elements with their own scales
 __device__ __forceinline__ void hx_split_pair2(float x0, float x1, float s0, float s1, unsigned& H, unsigned& L) {
@@ -41,10 +47,17 @@ __device__ __forceinline__ void hx_split_pair2(float x0, float x1, float s0, flo
 
 // The body is compiled four times -- MIXED (the workgroup stages x AND hdec) x ACTIVE (the wave has a tile) -- so that inside a
 // slab there is NO branch (gru_wgrad.hpp).
-template <int NT, bool MIXED>
+// XR (k_gru_wgrad_hx_rows): the pieces of x come from table row xrows[m] instead of row m of a copy.  The table's base stays the
+// wave-uniform scalar; the lane offset of a piece is (row . d + column) . 4.  The rows of a call's whole row range are put into LDS
+// once, before its first slab (4 bytes per row behind the slab buffers: wgx_rows_lds_bytes), and a fetch reads its row in the staging
+// step before it: no global index load sits in the slab loop's load queue (the wait counts in front of the staging stay what they
+// are), and no register lives across a slab for it -- this kernel has none to give (256, 8 waves).  Rows past the range read its last
+// row, as the copy route does.
+template <int NT, bool MIXED, bool XR = false>
 __device__ __forceinline__ void wgx_body(const WgArgs& a, const unsigned* __restrict__ gkeys, const unsigned* __restrict__ xkeys, char* wg_lds,
                                          const WgGroup& G, const int mbeg, const int mend_, const WgOut out, const int b, const int prod, const int vt,
-                                         const float* __restrict__ bsrc0, const float* __restrict__ bsrc1, const bool b0_is_x) {
+                                         const float* __restrict__ bsrc0, const float* __restrict__ bsrc1, const bool b0_is_x,
+                                         const int32_t* __restrict__ xrows = nullptr) {
   constexpr int BS = wg_bs(NT), ABYTES = wgx_a_bytes(), BBYTES = wgx_b_bytes(NT), BUF = wgx_buf_bytes(NT);
   const int d = a.d, Ka = 3 * d;
   const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
@@ -88,6 +101,23 @@ __device__ __forceinline__ void wgx_body(const WgArgs& a, const unsigned* __rest
   float4 ra_[2][2];
   float4 rb_[BSTG][MIXED ? 4 : 2];                               // [stage][operand * 2 + piece]
   const size_t ld_g4 = (size_t)4 * d;
+  // XR: the rows of the first operand for this call's row range, behind the two slab buffers in LDS: entry j = the row of bsrc0 that
+  // is row mbeg + j of the operand -- xrows[mbeg + j] where the operand is x, mbeg + j itself for a workgroup that stages hdec only (no
+  // branch inside a slab).  Entries past the range hold its last row.  A fetch takes its entry in the staging step before it (xr_next).
+  int* const xr_lds = reinterpret_cast<int*>(wg_lds + 2 * BUF);
+  int xr_next = 0;
+  auto xr_peek = [&](int i, int s, auto ragged_c) {
+    int j = 16 * s + (b_lds[i] - ABYTES) / BS;
+    if constexpr (decltype(ragged_c)::value) j = min(j, 16 * nslabs - 1);       // (slabs past the end: the last entry)
+    return xr_lds[j];
+  };
+  if constexpr (XR) {
+    for (int j = threadIdx.x; j < 16 * nslabs; j += WG_THREADS) {
+      const int m = min(mbeg + j, mend - 1);
+      xr_lds[j] = b0_is_x ? xrows[m] : m;
+    }
+    __syncthreads();
+  }
   auto fetch1 = [&](auto stage_c, int k, int s, auto ragged_c) {
     constexpr int STG = decltype(stage_c)::value;
     constexpr bool RAG = decltype(ragged_c)::value;
@@ -104,6 +134,14 @@ __device__ __forceinline__ void wgx_body(const WgArgs& a, const unsigned* __rest
     } else {
       constexpr int BS_ = STG % BSTG;
       const int i = (k - 2) & 1;
+      if constexpr (XR) {
+        if (k < 4) {                                             // (the first operand, x or hdec: row xr_next of bsrc0)
+          const int br = (b_lds[i] - ABYTES) / BS;
+          const unsigned cb = (unsigned)(b_lds[i] - ABYTES - br * BS) * 2u;       // (b_lds = ABYTES + br BS + 8 bq: 16 bq)
+          rb_[BS_][k - 2] = wg_ld16(wg_uniform(bsrc0), (unsigned)xr_next * (unsigned)(4 * d) + cb);
+          return;
+        }
+      }
       wg_gchar* base = wg_uniform((k < 4 ? bsrc0 : bsrc1) + (size_t)m0 * d);
       unsigned off = b_voff[i];
       if constexpr (RAG) {                                       // rows past the slice: its last row
@@ -162,15 +200,19 @@ __device__ __forceinline__ void wgx_body(const WgArgs& a, const unsigned* __rest
 #pragma unroll
     for (int r = 0; r < 16; ++r) acc[t][r] = 0.f;
 
+  auto fetch = [&](auto stage_c, int k, int s, auto ragged_c) {   // fetch1 with its row taken just before it (prologue)
+    if constexpr (XR) { if (k >= 2 && k < 4) xr_next = xr_peek((k - 2) & 1, s, ragged_c); }
+    fetch1(stage_c, k, s, ragged_c);
+  };
   if (nslabs > 0) {
 #pragma unroll
-    for (int k = 0; k < NLOADS; ++k) fetch1(st0_t(), k, 0, rag_t());
+    for (int k = 0; k < NLOADS; ++k) fetch(st0_t(), k, 0, rag_t());
 #pragma unroll
     for (int c = 0; c < NLOADS; ++c) chunk(st0_t(), c, 0, 0, rag_t());
 #pragma unroll
-    for (int k = 0; k < NLOADS; ++k) fetch1(st1_t(), k, 1, rag_t());      // (past the end: clamped re-reads, never used)
+    for (int k = 0; k < NLOADS; ++k) fetch(st1_t(), k, 1, rag_t());       // (past the end: clamped re-reads, never used)
 #pragma unroll
-    for (int k = 0; k < (BSTG == 2 ? NLOADS : 2); ++k) fetch1(st0_t(), k, 2, rag_t());
+    for (int k = 0; k < (BSTG == 2 ? NLOADS : 2); ++k) fetch(st0_t(), k, 2, rag_t());
   }
   __syncthreads();
 
@@ -183,7 +225,10 @@ __device__ __forceinline__ void wgx_body(const WgArgs& a, const unsigned* __rest
     auto stage_step = [&](int i) {
       const int k = i >> 1;
       if (i & 1) fetch1(cur_c, k, (k < 2 || BSTG == 2) ? s + 3 : s + 2, ragged_c);      // (into the register chunk k freed)
-      else chunk(cur_c, k, (s + 1) & 1, s + 1, ragged_c);
+      else {                                                      // (XR: first the row of the fetch that follows -- the split below hides the LDS latency)
+        if constexpr (XR) { if (k >= 2 && k < 4) xr_next = xr_peek((k - 2) & 1, BSTG == 2 ? s + 3 : s + 2, ragged_c); }
+        chunk(cur_c, k, (s + 1) & 1, s + 1, ragged_c);
+      }
     };
     if constexpr (!ACTIVE) {                                      // a wave without a tile (mixed / left-over workgroups): staging only
 #pragma unroll
@@ -312,6 +357,51 @@ __global__ void __launch_bounds__(WG_THREADS) k_gru_wgrad_hx(WgArgs a, WgxKeys k
     const size_t pslot2 = ((size_t)slice * a.P + b) * (2 * a.count) + 2 * grp;
     const WgOut out2 = {a.part2 + pslot2 * ((size_t)Rt * a.d), (size_t)Rt * a.d, a.bpart2 + pslot2 * Rt, (size_t)Rt, R0};
     wgx_body<NT, true>(a, gkeys, xkeys, wg_lds, G, m2, min(m2 + a.rows_per_tail, mbeg + a.rows_per_slice), out2, 2 * a.fb, t2.prod, t2.vt, G.x, G.hdec, true);
+  }
+}
+
+// k_gru_wgrad_hx with the x rows read in place from a table (WgxRows; the bodies' XR): the same decomposition, word for word
+template <int NT>
+__global__ void __launch_bounds__(WG_THREADS) k_gru_wgrad_hx_rows(WgArgs a, WgxKeys keys, WgxRows rows) {
+  extern __shared__ __attribute__((aligned(16))) char wg_lds[];
+  constexpr int BS = wg_bs(NT), ABYTES = wgx_a_bytes(), BBYTES = wgx_b_bytes(NT), BUF = wgx_buf_bytes(NT);
+  // ---- which (GRU, slice) pair, which workgroup of the pair
+  const int xcd = blockIdx.x & 7, q = blockIdx.x >> 3;
+  const int pi = q / a.P, b = q - pi * a.P;
+  const int u = xcd * a.per_xcd + pi;
+  if (pi >= a.per_xcd || u >= a.count * a.S) return;            // uniform
+  const int grp = u / a.S, slice = u - grp * a.S;
+  const WgGroup G = a.g[grp];
+  const unsigned* gkeys = keys.g[grp];
+  const unsigned* xkeys = keys.x[grp];
+  const int32_t* xrows = rows.r[grp];
+  const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  const WgTile tl = wg_tile(a, b, wave);
+  const bool mixed = b >= 2 * a.fb && a.mixed;                   // (never with a.tail: P = 2 fb then)
+  const int bprod = b < a.fb ? 0 : (b < 2 * a.fb ? 1 : b - 2 * a.fb);      // the product whose fp32 operand a single-operand workgroup stages
+  // ---- LDS: zero both buffers once (padding columns are never written again), then the column of ones (bias sums): column d
+  // of the h plane of both x / hdec images, every row
+  for (int i = threadIdx.x; i < 2 * BUF / 16; i += WG_THREADS) reinterpret_cast<hx_u32x4*>(wg_lds)[i] = hx_u32x4{0u, 0u, 0u, 0u};
+  __syncthreads();
+  if (threadIdx.x < 64) {                                        // (buffer, operand, row)
+    const int buf = threadIdx.x >> 5, op = (threadIdx.x >> 4) & 1, row = threadIdx.x & 15;
+    *reinterpret_cast<unsigned short*>(wg_lds + buf * BUF + ABYTES + op * BBYTES + row * BS + 2 * a.d) = 0x3c00;   // f16 1.0
+  }
+  const int Ka = 3 * a.d;
+  const int mbeg = slice * a.rows_per_slice;
+  const size_t pslot = (size_t)slice * (2 * a.count) + 2 * grp;
+  const WgOut out = {a.part + pslot * ((size_t)Ka * a.d), (size_t)Ka * a.d, a.bpart + pslot * Ka, (size_t)Ka, 0};
+  if (mixed) wgx_body<NT, true, true>(a, gkeys, xkeys, wg_lds, G, mbeg, mbeg + a.rows_per_slice, out, b, tl.prod, tl.vt, G.x, G.hdec, true, xrows);
+  else wgx_body<NT, false, true>(a, gkeys, xkeys, wg_lds, G, mbeg, mbeg + a.rows_per_slice, out, b, tl.prod, tl.vt, bprod ? G.hdec : G.x, nullptr, bprod == 0, xrows);
+  if (a.tail) {
+    // the left-over tiles of both products (what a mixed workgroup would take) over this workgroup's share of the slice's rows
+    __syncthreads();
+    const int R0 = 256 * a.fb, Rt = Ka - R0;
+    const WgTile t2 = wg_tile(a, 2 * a.fb, wave);
+    const int m2 = mbeg + b * a.rows_per_tail;
+    const size_t pslot2 = ((size_t)slice * a.P + b) * (2 * a.count) + 2 * grp;
+    const WgOut out2 = {a.part2 + pslot2 * ((size_t)Rt * a.d), (size_t)Rt * a.d, a.bpart2 + pslot2 * Rt, (size_t)Rt, R0};
+    wgx_body<NT, true, true>(a, gkeys, xkeys, wg_lds, G, m2, min(m2 + a.rows_per_tail, mbeg + a.rows_per_slice), out2, 2 * a.fb, t2.prod, t2.vt, G.x, G.hdec, true, xrows);
   }
 }
 

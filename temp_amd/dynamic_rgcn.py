@@ -21,7 +21,7 @@ from . import _hostlib
 from . import snapshot as S
 from .rrgcn import RRGCN, GRRGCNLayer, run_rnn
 from .tkg_module import TKG_Module
-from .gru_chain import (GruInstance, GruProgram, chain_decay_usable, chain_offset_usable, gru_chain, offset_tables, prepare_program,
+from .gru_chain import (GruInstance, GruProgram, chain_decay_usable, chain_offset_usable, gru_chain, offset_tables, prepare_program, rows_in_place_usable,
                         program_on_chain_kernels, zero_state_program)
 from .gru_cell import GRUCell
 from .window import ChainPlan, Step, concat_steps, concat_steps_dedup, window_times
@@ -240,13 +240,29 @@ class DynamicRGCN(TKG_Module):
         """Instances whose states leave the chain: the target position and the last history position."""
         return [wb.out_inst[0]] + ([wb.hist_inst] if wb.hist_inst >= 0 else [])
 
+    # the chain reads its input rows where layer 2 wrote them (gru_chain(table=...)) instead of from a copy in visit order; False in
+    # the models that read the copy themselves (wb.last_x: the post-* models)
+    rows_in_place = True
+
+    def _chain_rows_host(self, wb):
+        """The host list `rows` with GRU input = y2[rows] for the chain program (None: the input is y2 itself)."""
+        return wb.visit_rows_host if wb.visit_rows is not None else None
+
     def _run_batched(self, wb):
         enc, dev = self.ent_encoder, self._device()
         y1 = enc.layer_1.conv_table(wb.g_all, self.ent_embeds, wb.ids_all, wb.ids_inv)
         y2 = enc.layer_2.conv(wb.g_all, y1)
+        l2 = enc.layer_2
+        if wb.program is not None and wb.visit_rows is not None and self.rows_in_place:
+            want, inv, type1 = self._chain_want(wb), getattr(wb, "visit_inv", None), isinstance(l2.rnn, GRUCell)
+            dec, off = l2.decay_spec(), self._chain_offset(wb)
+            if rows_in_place_usable(wb.program, y2, inv, 1, type1, want, dec, off):
+                wb.last_x = None                      # (no copy of the GRU input rows in visit order exists on this route)
+                got = gru_chain(None, wb.program, [l2.rnn], l2.inv_temperature, type1, want=want, table=(y2, wb.visit_rows, inv, False))
+                hist = got[1] if wb.hist_inst >= 0 else None
+                return got[0], (hist, hist)
         if wb.visit_rows is not None:                 # distinct-snapshot rows -> visit rows
             y2 = TF.gather_rows(y2, wb.visit_rows, getattr(wb, "visit_inv", None))
-        l2 = enc.layer_2
         wb.last_x = y2                                # GRU input rows of the step (= the "local" states of the post models)
         if wb.program is not None:
             want = self._chain_want(wb)
@@ -323,7 +339,7 @@ class DynamicRGCN(TKG_Module):
             elif self._can_chain():
                 self._build_program(wb)
                 _lib.pause_point()
-                prepare_program(wb.program, dev, self.embed_size, len(wb.out_inst), self._chain_want(wb))
+                prepare_program(wb.program, dev, self.embed_size, len(wb.out_inst), self._chain_want(wb), chain_rows=self._chain_rows_host(wb))
                 # a learnable decay and the time embedding run on the chain kernels only: a program they refuse (no chain tables, a
                 # panel longer than their step limit) stays on the per-position loop -- decided here, not in `run`
                 enc = self.ent_encoder

@@ -25,6 +25,7 @@ WEIGHT_GRADS_MULTI = True   # A/B switch: False computes each GRU's weight gradi
 KEYED_GRADS = True          # A/B switch: False keeps the consumers of g4 on the six-product bf16 split (no keys from the chain backward)
 GATE_GRADS_ONCE = True      # A/B switch: False keeps dgi + dgh as two matrices (temp_gru_chain_bwd + temp_gru_weight_grads_multi)
 FUSED_INPUT_GATES = True    # A/B switch: False keeps the gate GEMM + gi route where temp_gru_chain_fwd's x route applies (so does TEMP_DEBUG bit 22)
+ROWS_IN_PLACE = True        # A/B switch: False keeps the copy into chain order (gather_rows(keys=True)) where gru_chain(table=...) could read the rows in place
 
 
 class GruInstance:
@@ -264,6 +265,25 @@ class GruProgram:
             c = self._x_index = (str(device), _lib.to_device(idx, device))
         return c[1]
 
+    def x_rows(self, device, chain_rows=None):
+        """int32 device table [n_total]: the TABLE row of every chain row when the x rows are a selection of a table's rows,
+        x_all = table[chain_rows] (gru_chain(table=...)): x_rows[i] = chain_rows[x_index[i]].  `chain_rows`: the host row list, given
+        once (by whoever prepares the program); afterwards the cached table is returned.  None: never given, or the list holds a
+        negative entry (a zero row: there is no table row to read in place)."""
+        if chain_rows is not None:
+            rows, idx = np.asarray(chain_rows).reshape(-1), np.zeros(self.n_total, dtype=np.int64)
+            for it in self.inst:
+                idx[it.h0:it.h0 + it.n] = it.x0 + np.arange(it.n, dtype=np.int64)
+            tab = None
+            if rows.size == 0 or int(rows.min()) >= 0:
+                tab = _lib.to_device(rows[idx].astype(np.int32), device)
+            self._x_rows = (str(device), tab, int(rows.shape[0]), int(rows.max()) + 1 if rows.size else 0)
+        c = getattr(self, "_x_rows", None)
+        return c[1] if c is not None and c[0] == str(device) else None
+
+    x_rows_count = property(lambda self: self._x_rows[2], doc="rows of the chain_rows list x_rows was composed from (= x rows)")
+    x_rows_max = property(lambda self: self._x_rows[3], doc="1 + the largest table row in it")
+
     def constants(self, device, d):
         """(zero previous-state row, all -1 row map long enough for any first-position instance), created once per program."""
         key = (str(device), int(d))
@@ -459,6 +479,18 @@ def _backward_result(be, ctx, d_x_all, grads, decay, offset):
     return (d_x_all, None, None, None, None, None, None) + d_dec + d_off + tuple(grads)
 
 
+def _grads_strategy(be, prog, d, variant, on_chain):
+    """-> (zero_state per group, one_launch, once): which weight-gradient strategy a program takes.  GRUs with disjoint x rows (the two
+    directions of a bidirectional chain, or the one GRU of a uni-directional one) take a one-launch strategy -- with the gate gradients
+    written once where the library takes these shapes."""
+    groups = prog.groups
+    zero_state = [all(it.prev < 0 for it in prog.inst if it.group == gi) for gi in range(len(groups))]    # hdec = 0 on every row
+    disjoint = all(groups[a]["x1"] <= groups[b]["x0"] or groups[b]["x1"] <= groups[a]["x0"] for a in range(len(groups)) for b in range(a))
+    one_launch = bool(groups and disjoint and not any(zero_state) and len({g["rnn"] for g in groups}) == len(groups) and WEIGHT_GRADS_MULTI)
+    once = one_launch and GATE_GRADS_ONCE and on_chain and be.gru_grads_g4_supported([g["h1"] - g["h0"] for g in groups], d, variant)
+    return zero_state, one_launch, once
+
+
 class _GruChainFn(torch.autograd.Function):
     """forward() decides the route once and keeps it on ctx as plain values: tabs (the chain kernels' tables; None = the per-position
     launches), fused (the chain forward reads x: no gi), share (input gates once per distinct x row) and the decay / offset keyword dicts,
@@ -528,12 +560,7 @@ class _GruChainFn(torch.autograd.Function):
         # what the chain backward writes besides the gate gradients, for _backward_result
         decay = dict(ctx.decay, d_arg=new(N)) if ctx.decay else {}
         offset = dict(ctx.offset, d_state=new(N, d)) if ctx.offset else {}
-        zero_state = [all(it.prev < 0 for it in prog.inst if it.group == gi) for gi in range(len(groups))]    # hdec = 0 on every row
-        # GRUs with disjoint x rows (the two directions of a bidirectional chain, or the one GRU of a uni-directional one) take a
-        # one-launch strategy -- with the gate gradients written once where the library takes these shapes
-        disjoint = all(groups[a]["x1"] <= groups[b]["x0"] or groups[b]["x1"] <= groups[a]["x0"] for a in range(len(groups)) for b in range(a))
-        one_launch = bool(groups and disjoint and not any(zero_state) and len({g["rnn"] for g in groups}) == len(groups) and WEIGHT_GRADS_MULTI)
-        once = one_launch and GATE_GRADS_ONCE and ctx.tabs is not None and be.gru_grads_g4_supported([g["h1"] - g["h0"] for g in groups], d, ctx.variant)
+        zero_state, one_launch, once = _grads_strategy(be, prog, d, ctx.variant, ctx.tabs is not None)
         if once:
             g4, keys = _gate_grads_g4(be, ctx, saved, ups, W, decay, offset)
             d_x_all = torch.empty_like(x_all)
@@ -549,6 +576,79 @@ class _GruChainFn(torch.autograd.Function):
             if per_group is None:
                 per_group = _weight_grads_per_group(be, ctx, x_all, saved, dgi, dgh, W, zero_state, d_x_all)
         return _backward_result(be, ctx, d_x_all, _scatter_grads(ctx, per_group, d_x_all), decay, offset)
+
+
+class _GruChainRowsFn(torch.autograd.Function):
+    """The fused-forward, keyed-gradient route of _GruChainFn with the x rows read IN PLACE: x_all = table[chain_rows] is never
+    written.  The chain forward reads table rows through prog.x_rows (its x route takes any row table), the weight gradients through
+    the same table (gru_grads_g4_rows), and the column keys of x are those of the table (one columns-only pass: every table row is a
+    chain row in the models' batches, and a bound over more rows is a bound).  d_x is still written in chain order; the table's
+    gradient is the segment sum over `inverse` that the gather's backward runs (functional._GatherRowsFn), ReLU fold included.
+    Taken only where rows_in_place_usable() says so: no decision is left to make here."""
+
+    @staticmethod
+    def forward(ctx, table, prog, inverse, relu_table, lam, variant, n_rnn, want, *weights):
+        be = get_backend()
+        dev, d, N = table.device, table.shape[1], prog.n_total
+        table = table.detach().contiguous()
+        W = [tuple(w.detach().contiguous() for w in weights[4 * r:4 * r + 4]) for r in range(n_rnn)]
+        tabs, x_rows = prog.chain_tables(dev, want), prog.x_rows(dev)
+        x_col_keys = be.absmax_keys(table, rows=False)[1]
+        H, saved = torch.empty(N, d, dtype=torch.float32, device=dev), torch.empty(5, N, d, dtype=torch.float32, device=dev)
+        w_ih, w_hh, b_ih, b_hh = ([w[k] for w in W] for k in range(4))
+        packs = be.gru_chain_pack_x_multi(w_hh, w_ih)
+        be.gru_chain_fwd_x(tabs, table, x_rows, lam, variant, packs, b_hh, b_ih, H, saved)
+        ctx.set_materialize_grads(False)
+        ctx.save_for_backward(table, saved, x_rows, x_col_keys, *[w for ws in W for w in ws])
+        ctx.prog, ctx.lam, ctx.variant, ctx.n_rnn, ctx.want, ctx.tabs, ctx.packs = prog, lam, variant, n_rnn, want, tabs, packs
+        ctx.inverse, ctx.relu_table = inverse, relu_table
+        if want is None:
+            return H
+        return tuple(H[prog.inst[i].h0:prog.inst[i].h0 + prog.inst[i].n] for i in want)
+
+    @staticmethod
+    def backward(ctx, *d_outs):
+        be = get_backend()
+        table, saved, x_rows, x_col_keys = ctx.saved_tensors[:4]
+        W = [ctx.saved_tensors[4 + 4 * r:8 + 4 * r] for r in range(ctx.n_rnn)]
+        prog, groups = ctx.prog, ctx.prog.groups
+        d, N = table.shape[1], prog.n_total
+        if ctx.want is None:
+            ups = [d_outs[0].contiguous() if d_outs[0] is not None else torch.zeros(N, d, dtype=torch.float32, device=table.device)]
+        else:
+            given = {i: g.contiguous() for i, g in zip(ctx.want, d_outs) if g is not None}
+            ups = [given.get(i) for i in ctx.want]
+        g4, keys = _gate_grads_g4(be, ctx, saved, ups, W, {}, {})
+        xsl, hsl = _group_rows(groups)
+        d_x_all = torch.empty(prog.x_rows_count, d, dtype=torch.float32, device=table.device)
+        per_group = be.gru_grads_g4_rows(table, [x_rows[b] for b in hsl], [saved[4, b] for b in hsl], [g4[b] for b in hsl],
+                                         [W[g["rnn"]][0] for g in groups], [d_x_all[a] for a in xsl], row_keys=[keys[0][b] for b in hsl],
+                                         col_keys=[keys[1][g["rnn"]] for g in groups], x_col_keys=[x_col_keys] * len(groups))
+        grads = _scatter_grads(ctx, per_group, d_x_all)
+        seg_ptr, order = ctx.inverse
+        d_table = be.segment_sum_rows(d_x_all, seg_ptr, order, table.shape[0], relu_of=table if ctx.relu_table else None)
+        return (d_table, None, None, None, None, None, None, None) + tuple(grads)
+
+
+def rows_in_place_usable(prog, table, inverse, n_rnn, type1=False, want=None, decay=None, offset=None):
+    """True when gru_chain(None, prog, ..., table=(table, chain_rows, inverse, .)) reads the table's rows in place (_GruChainRowsFn)
+    instead of copying them into chain order first: the program's row table has been composed (GruProgram.x_rows), the chain runs on
+    the fused x forward and hands out keys, the weight gradients are the one keyed launch, there is neither a learnable decay nor a
+    state offset, and the table's byte offsets fit 32 bits."""
+    be = get_backend()
+    dev, d = table.device, table.shape[1]
+    variant = _lib.GRU_TYPE1 if type1 else _lib.GRU_TORCH
+    if not (ROWS_IN_PLACE and hasattr(be, "gru_grads_g4_rows") and decay is None and offset is None and variant == _lib.GRU_TORCH):
+        return False
+    if inverse is None or d % 4 or d > 256 or table.shape[0] * d * 4 >= 2 ** 32 or prog.x_rows(dev) is None or prog.x_rows_max > table.shape[0]:
+        return False
+    tabs = prog.chain_tables(dev, tuple(want) if want is not None else None) if chain_kernels_usable(d, n_rnn) else None
+    if tabs is None or not (FUSED_INPUT_GATES and hasattr(be, "gru_chain_fwd_x") and be.gru_chain_fwd_x_supported(d, variant, tabs["max_steps"])):
+        return False
+    if not (KEYED_GRADS and hasattr(be, "gru_chain_keys_supported") and be.gru_chain_keys_supported(d) and be.keys_supported(d)):
+        return False
+    return bool(_grads_strategy(be, prog, d, variant, True)[2]
+                and be.gru_grads_g4_rows_supported([g["h1"] - g["h0"] for g in prog.groups], d, variant, table.shape[0]))
 
 
 def chain_kernels_usable(d, n_rnn=1):
@@ -582,14 +682,17 @@ def program_on_chain_kernels(prog, device, want):
     return prog.chain_tables(device, tuple(want) if want is not None else None) is not None
 
 
-def prepare_program(prog, device, d, n_rnn, want):
+def prepare_program(prog, device, d, n_rnn, want, chain_rows=None):
     """Host + upload half of a program, done once per prepared batch (by the prefetch thread when there is one): the chain
     kernels' panel tables for the `want` set the run will ask for, or -- when the program goes through the per-position
-    launches -- the row maps of every instance."""
+    launches -- the row maps of every instance.  chain_rows: the host row list when the x rows will be table[chain_rows]
+    (gru_chain(table=...)): the composed row table is built here as well."""
     if chain_kernels_usable(d, n_rnn) and prog.chain_tables(device, tuple(want) if want is not None else None) is not None:
         _lib.pause_point()
         prog.gi_shared(device)
         prog.x_index(device)
+        if chain_rows is not None:
+            prog.x_rows(device, chain_rows)
         return
     prog.upload(device)
 
@@ -600,8 +703,11 @@ def zero_state_program(n):
     return GruProgram([GruInstance(n, 0, 0, -1, np.full(n, -1, dtype=np.int32), np.zeros(n, dtype=np.float32))])
 
 
-def gru_chain(x_all, prog, rnns, lam, type1=False, want=None, x_keys=None, decay=None, offset=None):
-    """Run a GruProgram.  offset: None, or (table [T, d], index) / (table, index, inverse) of --use-time-embedding: row i leaves
+def gru_chain(x_all, prog, rnns, lam, type1=False, want=None, x_keys=None, decay=None, offset=None, table=None):
+    """Run a GruProgram.  table: None, or (table [T, d], chain_rows int32 [x rows], inverse, relu_table) with x_all = None: the x rows
+    are table[chain_rows] -- the arguments of functional.gather_rows, whose result (with its keys, where they are of use) is what runs
+    otherwise -- and where rows_in_place_usable() holds they are read where they lie, never copied; the table then receives its
+    gradient as the gather's backward would hand it out.  offset: None, or (table [T, d], index) / (table, index, inverse) of --use-time-embedding: row i leaves
     s_i = GRU(x_i, dec . s_prev) + table[index[i]] (index: int32 [n_total] on x_all's device, -1 = no offset), the states returned and
     carried on include it and `table` receives its gradient; (index, inverse) = offset_tables(...) -- without `inverse` it is built
     here from a host copy of `index` (a sync: prepare it instead).  Chain kernels only: anything they refuse raises.  decay: None = exp(-dt lam), or the layer's decay_spec() = (weight (1, 1), bias (1,)) of --learnable-lambda:
@@ -614,11 +720,22 @@ def gru_chain(x_all, prog, rnns, lam, type1=False, want=None, x_keys=None, decay
             ws += [r.weight_ih, r.weight_hh, r.bias_ih, r.bias_hh]
         else:
             ws += [r.weight_ih_l0, r.weight_hh_l0, r.bias_ih_l0, r.bias_hh_l0]
+    if table is not None:
+        assert x_all is None and x_keys is None, "table=...: the x rows are the table's"
+        y, chain_rows, y_inv, relu_table = table
+        if rows_in_place_usable(prog, y, y_inv, len(rnns), type1, want, decay, offset):
+            return _GruChainRowsFn.apply(y, prog, y_inv, bool(relu_table), float(lam), _lib.GRU_TORCH, len(rnns),
+                                         tuple(want) if want is not None else None, *ws)
+        from .functional import gather_keys_supported, gather_rows
+        if gather_keys_supported(y.shape[1]) and chain_kernels_usable(y.shape[1], len(rnns)):
+            x_all, x_keys = gather_rows(y, chain_rows, y_inv, relu_table=relu_table, keys=True)
+        else:
+            x_all = gather_rows(y, chain_rows, y_inv, relu_table=relu_table)
     off = (None, None, None)
     if offset is not None:
-        table, index = offset[0], offset[1]
-        inverse = offset[2] if len(offset) > 2 else offset_tables(index.detach().cpu().numpy(), table.shape[0], index.device)[1]
-        off = (table, index, inverse)
+        off_table, index = offset[0], offset[1]
+        inverse = offset[2] if len(offset) > 2 else offset_tables(index.detach().cpu().numpy(), off_table.shape[0], index.device)[1]
+        off = (off_table, index, inverse)
     return _GruChainFn.apply(x_all, prog, float(lam), _lib.GRU_TYPE1 if type1 else _lib.GRU_TORCH, len(rnns),
                              tuple(want) if want is not None else None, x_keys, decay[0] if decay is not None else None,
                              decay[1] if decay is not None else None, *off, *ws)

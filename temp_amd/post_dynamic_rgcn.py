@@ -76,6 +76,7 @@ class _PostWindowMixin(_FrequencyGateMixin):
     _window_base = None                   # DynamicRGCN | BiDynamicRGCN: the window model whose batched all-entity pass applies
     _two_stream = False                   # get_all_embeds_Gt takes (local, temporal) target rows and returns both matrices
     _chain_time_embedding = False         # --use-time-embedding also shifts the local stream: these models keep the per-position loop for it
+    rows_in_place = False                 # the local stream IS the copy of the GRU input rows (wb.last_x): these models keep the gather
 
     def _chain_input_rows(self, wb, inst_id=None, step=None):
         """GRU-input rows (= local layer-2 states) of one chain instance / step of a batched run."""
