@@ -999,6 +999,26 @@ int temp_filtered_topk(int P, int N, int ld, int k, int col0, const float* score
                        const int32_t* keep, int carry, float* top_val, int32_t* top_idx, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * Filtered top-k selection over a MIXED score row: the answer list of a query on the two-table post models, which score against a
+ * local and a temporal all-entity table and mix the two by a per-query gate.  The contract is temp_filtered_topk's, word for word,
+ * on the row's mixed score
+ *   m[p,j] = w[p] * a[p,j] + (1 - w[p]) * b[p,j],  evaluated as fmaf(w, a, (1 - w) * b) (csrc/mix.hpp: the one mixing expression of
+ *            every gated kernel), formed in registers: the mixed matrix is neither written nor read.
+ *   entity e = col0 + j is ADMISSIBLE for row p  <=>  a[p,j] > -inf  and  b[p,j] > -inf  and  (e is not in the row's filter list
+ *                                                     or  e == keep[p])
+ * The -inf test is made on the RAW operands, before the mix: w in {0, 1} would otherwise turn a -inf into 0 * inf = NaN or into a
+ * finite score.  The pad columns of temp_l1_scores are -inf in both matrices and stay out.  Operands of +inf are OUTSIDE the
+ * contract (fmaf(0, +inf, b) is NaN), unlike in temp_filtered_topk; NaN is unspecified.
+ * scores_a, scores_b [P, ld] share ld; ld % 4 == 0 and both 16-byte aligned (else TEMP_E_UNSUPPORTED).  w [P] fp32, not
+ * range-checked.  k, N, col0, carry and P == 0 are checked and behave as in temp_filtered_topk; NULL scores_a, scores_b or w with
+ * P > 0 is TEMP_E_BADARG.  With w == 1 and finite b the mix returns a bit for bit (w == 0 and finite a: b), so carry = 1 merges
+ * with lists of either entry point.  No workspace, no floating-point atomics: bit-repeatable.
+ * ---------------------------------------------------------------------------------------------- */
+int temp_filtered_topk_mix(int P, int N, int ld, int k, int col0, const float* scores_a, const float* scores_b, const float* w,
+                           const int32_t* filt_ptr, const int32_t* filt_ids, const int32_t* keep, int carry, float* top_val,
+                           int32_t* top_idx, void* stream);
+
+/* ------------------------------------------------------------------------------------------------
  * Clipped Adam: the reference trainer's optimizer step, Trainer(gradient_clip_val) -> clip_grad_norm_(parameters, max_norm)
  * (main.py:128-129, utils/args.py:26) followed by Adam(lr, weight_decay = 1e-4) (models/TKG_Module.py:154-160), as one
  * deterministic multi-tensor pass over a DEVICE table with one row per tensor that has a gradient:

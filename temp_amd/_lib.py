@@ -244,6 +244,7 @@ SYMBOLS = {
     "temp_corrupt_sample": (_I, [_I, _I, _I, ctypes.c_uint64, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp]),
     "temp_filtered_rank": (_I, [_I, _I, _I, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp]),
     "temp_filtered_topk": (_I, [_I, _I, _I, _I, _I, c_vp, c_vp, c_vp, c_vp, _I, c_vp, c_vp, c_vp]),
+    "temp_filtered_topk_mix": (_I, [_I, _I, _I, _I, _I, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, _I, c_vp, c_vp, c_vp]),
     "temp_grad_norm_workspace": (_SZ, [_I]),
     "temp_grad_norm_clip": (_I, [_I, _I, c_vp, ctypes.c_double, c_vp, _SZ, c_vp, c_vp]),
     "temp_adam_clip_step": (_I, [_I, _I, c_vp, c_vp, c_vp]),

@@ -1004,42 +1004,74 @@ class HipBackend:
         _lib.check(rc, "temp_filtered_rank")
         return ranks.long()
 
-    def filtered_topk(self, scores, k, filt_ptr=None, filt_ids=None, keep=None, col0=0, n=None, carry=None):
-        """-> (top_val [P, k] float32, top_idx [P, k] int64): the best k admissible entities of every row of scores [P, ld] (see
-        temp_filtered_topk).  Column j < n (default: every column) is entity col0 + j.  `scores` may be a column slice of a wider
-        row-major matrix (row stride % 4 == 0, first element 16-byte aligned).  `carry` = the pair an earlier call returned over
-        other entities: the result is then the selection over both ranges."""
+    @staticmethod
+    def _topk_args(what, scores, k, filt_ptr, filt_ids, keep, col0, n, carry):
+        """The checks and output buffers both selection entry points share -> (scores, P, n, ld, filt_ptr, filt_ids, keep, top_val,
+        top_idx)."""
         if scores.dim() != 2 or not scores.is_cuda or scores.dtype != torch.float32:
-            raise _lib.TempAmdError("filtered_topk: scores must be a float32 [P, ld] GPU matrix")
+            raise _lib.TempAmdError("%s: scores must be a float32 [P, ld] GPU matrix" % what)
         scores = scores.detach()
         P, width = scores.shape
         n = width if n is None else int(n)
         ld = scores.stride(0) if P > 1 else max(scores.stride(0), width)
         if scores.stride(1) != 1 and width > 1:
-            raise ValueError("filtered_topk: the score rows must be contiguous")
+            raise ValueError("%s: the score rows must be contiguous" % what)
         if not 1 <= k <= _lib.TOPK_MAX:
-            raise ValueError("filtered_topk: k must lie in [1, %d]" % _lib.TOPK_MAX)
+            raise ValueError("%s: k must lie in [1, %d]" % (what, _lib.TOPK_MAX))
         if not 0 < n <= width or col0 < 0:
-            raise ValueError("filtered_topk: n must lie in (0, row length] and col0 must not be negative")
+            raise ValueError("%s: n must lie in (0, row length] and col0 must not be negative" % what)
         if ld % 4 or scores.data_ptr() % 16:
-            raise ValueError("filtered_topk: the row stride must be a multiple of 4 and the first score 16-byte aligned")
+            raise ValueError("%s: the row stride must be a multiple of 4 and the first score 16-byte aligned" % what)
         if filt_ptr is not None:
             filt_ptr, filt_ids = _i32(filt_ptr, "filt_ptr"), _i32(filt_ids, "filt_ids")
             if filt_ptr.shape[0] != P + 1:
-                raise ValueError("filtered_topk: filt_ptr must have one entry per row plus one")
+                raise ValueError("%s: filt_ptr must have one entry per row plus one" % what)
         keep = _i32(keep, "keep")
         if keep is not None and keep.shape[0] != P:
-            raise ValueError("filtered_topk: keep must have one entry per row")
+            raise ValueError("%s: keep must have one entry per row" % what)
         if carry is None:
             top_val = torch.empty(P, k, dtype=torch.float32, device=scores.device)
             top_idx = torch.empty(P, k, dtype=torch.int32, device=scores.device)
         else:
             top_val, top_idx = _f32(carry[0], "carry values").clone(), carry[1].to(dtype=torch.int32, copy=True).contiguous()
             if top_val.shape != (P, k) or top_idx.shape != (P, k):
-                raise ValueError("filtered_topk: carry must be the (top_val, top_idx) [P, k] of an earlier call")
+                raise ValueError("%s: carry must be the (top_val, top_idx) [P, k] of an earlier call" % what)
+        return scores, P, n, ld, filt_ptr, filt_ids, keep, top_val, top_idx
+
+    def filtered_topk(self, scores, k, filt_ptr=None, filt_ids=None, keep=None, col0=0, n=None, carry=None):
+        """-> (top_val [P, k] float32, top_idx [P, k] int64): the best k admissible entities of every row of scores [P, ld] (see
+        temp_filtered_topk).  Column j < n (default: every column) is entity col0 + j.  `scores` may be a column slice of a wider
+        row-major matrix (row stride % 4 == 0, first element 16-byte aligned).  `carry` = the pair an earlier call returned over
+        other entities: the result is then the selection over both ranges."""
+        scores, P, n, ld, filt_ptr, filt_ids, keep, top_val, top_idx = self._topk_args("filtered_topk", scores, k, filt_ptr, filt_ids, keep,
+                                                                                       col0, n, carry)
         rc = self.lib.temp_filtered_topk(P, n, ld, int(k), int(col0), _ptr(scores), _ptr(filt_ptr), _ptr(filt_ids), _ptr(keep),
                                          int(carry is not None), _ptr(top_val), _ptr(top_idx), _stream())
         _lib.check(rc, "temp_filtered_topk")
+        return top_val, top_idx.long()
+
+    def filtered_topk_mix(self, scores_a, scores_b, w, k, filt_ptr=None, filt_ids=None, keep=None, col0=0, n=None, carry=None):
+        """filtered_topk over the rows w[p] * scores_a[p] + (1 - w[p]) * scores_b[p], formed inside the kernel (see
+        temp_filtered_topk_mix): an entity whose score is -inf in EITHER matrix is inadmissible whatever w is.  The two matrices have
+        equal shapes and strides (column slices of two equally wide matrices qualify), w has one entry per row; `carry` may come from
+        either entry point."""
+        what = "filtered_topk_mix"
+        if not torch.is_tensor(scores_b) or scores_b.dim() != 2 or not scores_b.is_cuda or scores_b.dtype != torch.float32:
+            raise _lib.TempAmdError("%s: scores_b must be a float32 [P, ld] GPU matrix" % what)
+        scores_a, P, n, ld, filt_ptr, filt_ids, keep, top_val, top_idx = self._topk_args(what, scores_a, k, filt_ptr, filt_ids, keep, col0, n, carry)
+        scores_b = scores_b.detach()
+        if scores_b.shape != scores_a.shape or scores_b.stride() != scores_a.stride() or scores_b.device != scores_a.device:
+            raise ValueError("%s: the two score matrices must have equal shapes and strides" % what)
+        if scores_b.data_ptr() % 16:
+            raise ValueError("%s: the first score of scores_b must be 16-byte aligned" % what)
+        if w is None:
+            raise ValueError("%s: w must have one entry per row" % what)
+        w = _f32(w.detach().reshape(-1), "w")
+        if w.shape[0] != P or w.device != scores_a.device:
+            raise ValueError("%s: w must have one entry per row" % what)
+        rc = self.lib.temp_filtered_topk_mix(P, n, ld, int(k), int(col0), _ptr(scores_a), _ptr(scores_b), _ptr(w), _ptr(filt_ptr), _ptr(filt_ids),
+                                             _ptr(keep), int(carry is not None), _ptr(top_val), _ptr(top_idx), _stream())
+        _lib.check(rc, "temp_filtered_topk_mix")
         return top_val, top_idx.long()
 
     # ---- optimizer (clipped Adam over a device table of tensors) ----------------------------------------------

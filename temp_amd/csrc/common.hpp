@@ -147,7 +147,8 @@ enum KernelId {
   K_GEMM_ISO, K_GEMM_GRU_GI, K_GEMM_LINEAR, K_GATHER_CE, K_SA_ATTN_FWD, K_SA_ATTN_BWD, K_GRU_CHAIN_FWD, K_GRU_CHAIN_BWD,
   K_GRU_CHAIN_PACK, K_BX_PACK, K_GEMM_TN_BX8, K_GEMM_TN_BX, K_GRU_WGRAD, K_SEGMENT_SUM, K_KEYS, K_GATED_QUERY, K_GATHER_CE_MIX,
   K_PAIR_MSG, K_PAIR_GATHER_FWD, K_PAIR_FIX_EPI, K_PAIR_GATHER_BWD, K_PAIR_TAIL,
-  K_DIACHRONIC_FWD, K_DIACHRONIC_BWD, K_FILTERED_TOPK, K_ADAM_GRAD_NORM, K_ADAM_NORM_FINISH, K_ADAM_CLIP_STEP, K_COUNT
+  K_DIACHRONIC_FWD, K_DIACHRONIC_BWD, K_FILTERED_TOPK, K_ADAM_GRAD_NORM, K_ADAM_NORM_FINISH, K_ADAM_CLIP_STEP, K_FILTERED_TOPK_MIX,
+  K_COUNT
 };
 int trace_open(int kernel_id, hipStream_t st);       // -> slot or -1
 void trace_close(int slot, hipStream_t st);

@@ -24,7 +24,15 @@
 // The selection depends on the total order alone: the order in which survivors land in the buffer (the LDS counter) does not
 // reach the result, so the output is bit-repeatable, and a list carried over from other column panels merges to the same list in
 // any panel order.
+//
+// The MIXED instantiation (temp_filtered_topk_mix) selects over m = mix1(w[p], a, b) of two score rows -- the two-table post models'
+// gated score -- without the mixed matrix ever existing: both rows are streamed with the same loads and the same one-chunk
+// prefetch, and where the prefetched registers become the current chunk's values they are folded into ONE value per column,
+// -inf when either operand is -inf (tested on the raw operands: w in {0, 1} would otherwise turn a -inf into 0 * inf = NaN or
+// into a finite score), else mix1.  From there on the kernel is the plain one: a folded -inf fails the admissibility compare like
+// a plain -inf.  The extra live state is the second prefetch set.
 #include "common.hpp"
+#include "mix.hpp"
 
 namespace temp {
 namespace {
@@ -59,10 +67,23 @@ __device__ __forceinline__ float4 topk_load(const float* srow, int j, int N) {
   return j < N ? ld4_nt(srow + j) : make_float4(ninf, ninf, ninf, ninf);
 }
 
+// one column of the mixed row: inadmissible (-inf) when either raw operand is
+__device__ __forceinline__ float topk_fold1(float w, float a, float b) {
+  const float ninf = -__builtin_inff();
+  return ((a > ninf) & (b > ninf)) ? mix1(w, a, b) : ninf;
+}
+__device__ __forceinline__ float4 topk_fold(float w, float4 a, float4 b) {
+  return make_float4(topk_fold1(w, a.x, b.x), topk_fold1(w, a.y, b.y), topk_fold1(w, a.z, b.z), topk_fold1(w, a.w, b.w));
+}
+
+// MIX = false: rows of `scores`; scores_b and w are not read (they come last, so every other argument keeps its kernarg offset and
+// the plain instantiation compiles to the instructions it had before the template).  MIX = true: rows of mix1(w[p], scores, scores_b).
+template <bool MIX>
 __global__ void __launch_bounds__(TOPK_THREADS) k_filtered_topk(int N, int ld, int k, int col0, const float* __restrict__ scores,
                                                                 const int32_t* __restrict__ filt_ptr, const int32_t* __restrict__ filt_ids,
                                                                 const int32_t* __restrict__ keep, int carry, float* __restrict__ top_val,
-                                                                int32_t* __restrict__ top_idx) {
+                                                                int32_t* __restrict__ top_idx, const float* __restrict__ scores_b,
+                                                                const float* __restrict__ w) {
   extern __shared__ __attribute__((aligned(16))) char topk_smem[];
   float* cv = reinterpret_cast<float*>(topk_smem);
   int* ci = reinterpret_cast<int*>(topk_smem + TOPK_OFF_CI);
@@ -72,6 +93,8 @@ __global__ void __launch_bounds__(TOPK_THREADS) k_filtered_topk(int N, int ld, i
   const float ninf = -__builtin_inff();
   const int p = blockIdx.x, tid = threadIdx.x;
   const float* srow = scores + (size_t)p * ld;
+  const float* brow = MIX ? scores_b + (size_t)p * ld : nullptr;
+  const float wp = MIX ? w[p] : 0.f;
   const size_t out = (size_t)p * k;
 
   if (tid < k) {
@@ -86,18 +109,26 @@ __global__ void __launch_bounds__(TOPK_THREADS) k_filtered_topk(int N, int ld, i
   int cur = 0;                                                     // which list buffer is current (wave-uniform)
   float thr_v = lv[k - 1];
   int thr_i = li[k - 1];
-  float4 nx[TOPK_VEC];
+  float4 nx[TOPK_VEC], nb[MIX ? TOPK_VEC : 1];
 #pragma unroll
-  for (int u = 0; u < TOPK_VEC; ++u) nx[u] = topk_load(srow, (u * TOPK_THREADS + tid) * 4, N);
+  for (int u = 0; u < TOPK_VEC; ++u) {
+    nx[u] = topk_load(srow, (u * TOPK_THREADS + tid) * 4, N);
+    if constexpr (MIX) nb[u] = topk_load(brow, (u * TOPK_THREADS + tid) * 4, N);
+  }
 
   int it = 0;
   for (int base = 0; base < N; base += TOPK_CHUNK, ++it) {
     float4 x[TOPK_VEC];
 #pragma unroll
-    for (int u = 0; u < TOPK_VEC; ++u) x[u] = nx[u];
+    for (int u = 0; u < TOPK_VEC; ++u) {
+      if constexpr (MIX) x[u] = topk_fold(wp, nx[u], nb[u]); else x[u] = nx[u];
+    }
     if (base + TOPK_CHUNK < N) {                                   // the next chunk's loads fly over this chunk's compares and barrier
 #pragma unroll
-      for (int u = 0; u < TOPK_VEC; ++u) nx[u] = topk_load(srow, base + TOPK_CHUNK + (u * TOPK_THREADS + tid) * 4, N);
+      for (int u = 0; u < TOPK_VEC; ++u) {
+        nx[u] = topk_load(srow, base + TOPK_CHUNK + (u * TOPK_THREADS + tid) * 4, N);
+        if constexpr (MIX) nb[u] = topk_load(brow, base + TOPK_CHUNK + (u * TOPK_THREADS + tid) * 4, N);
+      }
     }
     // two counters, by chunk parity: a fast wave that appends for chunk it + 1 cannot disturb the count a slow wave still has to
     // read for chunk it (it cannot pass the barrier of chunk it + 1 without that wave)
@@ -223,17 +254,43 @@ __global__ void __launch_bounds__(TOPK_THREADS) k_filtered_topk(int N, int ld, i
 
 using namespace temp;
 
+namespace {
+
+// the argument checks of both entry points (include/temp_amd.h); TEMP_OK with *launch = false for P == 0
+int topk_check(int P, int N, int ld, int k, int col0, const float* a, const float* b, const float* w, bool mix, const float* top_val,
+               const int32_t* top_idx, bool* launch) {
+  *launch = false;
+  if (P < 0 || N <= 0 || ld < N || k < 1 || k > TEMP_TOPK_MAX || col0 < 0 || (long long)col0 + N > 0x7fffffffLL) return TEMP_E_BADARG;
+  if (ld % 4) return TEMP_E_UNSUPPORTED;
+  if (P == 0) return TEMP_OK;
+  if (!a || !top_val || !top_idx || (mix && (!b || !w))) return TEMP_E_BADARG;
+  if (reinterpret_cast<uintptr_t>(a) % 16 || (mix && reinterpret_cast<uintptr_t>(b) % 16)) return TEMP_E_UNSUPPORTED;
+  *launch = true;
+  return TEMP_OK;
+}
+
+}  // namespace
+
 extern "C" {
 
 int temp_filtered_topk(int P, int N, int ld, int k, int col0, const float* scores, const int32_t* filt_ptr, const int32_t* filt_ids,
                        const int32_t* keep, int carry, float* top_val, int32_t* top_idx, void* stream) {
-  if (P < 0 || N <= 0 || ld < N || k < 1 || k > TEMP_TOPK_MAX || col0 < 0 || (long long)col0 + N > 0x7fffffffLL) return TEMP_E_BADARG;
-  if (ld % 4) return TEMP_E_UNSUPPORTED;
-  if (P == 0) return TEMP_OK;
-  if (!scores || !top_val || !top_idx) return TEMP_E_BADARG;
-  if (reinterpret_cast<uintptr_t>(scores) % 16) return TEMP_E_UNSUPPORTED;
-  TEMP_LAUNCH(K_FILTERED_TOPK, k_filtered_topk, dim3(P), dim3(TOPK_THREADS), TOPK_LDS, (hipStream_t)stream, N, ld, k, col0, scores, filt_ptr, filt_ids,
-              keep, carry, top_val, top_idx);
+  bool launch;
+  const int rc = topk_check(P, N, ld, k, col0, scores, nullptr, nullptr, false, top_val, top_idx, &launch);
+  if (!launch) return rc;
+  TEMP_LAUNCH(K_FILTERED_TOPK, k_filtered_topk<false>, dim3(P), dim3(TOPK_THREADS), TOPK_LDS, (hipStream_t)stream, N, ld, k, col0, scores,
+              filt_ptr, filt_ids, keep, carry, top_val, top_idx, (const float*)nullptr, (const float*)nullptr);
+  return launch_status();
+}
+
+int temp_filtered_topk_mix(int P, int N, int ld, int k, int col0, const float* scores_a, const float* scores_b, const float* w,
+                           const int32_t* filt_ptr, const int32_t* filt_ids, const int32_t* keep, int carry, float* top_val,
+                           int32_t* top_idx, void* stream) {
+  bool launch;
+  const int rc = topk_check(P, N, ld, k, col0, scores_a, scores_b, w, true, top_val, top_idx, &launch);
+  if (!launch) return rc;
+  TEMP_LAUNCH(K_FILTERED_TOPK_MIX, k_filtered_topk<true>, dim3(P), dim3(TOPK_THREADS), TOPK_LDS, (hipStream_t)stream, N, ld, k, col0, scores_a,
+              filt_ptr, filt_ids, keep, carry, top_val, top_idx, scores_b, w);
   return launch_status();
 }
 

@@ -15,7 +15,10 @@ Restructured for the device:
     (`temp_filtered_rank`) instead of sorting;
   * the ANSWERS of a query (s, r, ?, t) / (?, r, o, t) -- `topk_single_graph`, which the reference has no counterpart of -- are
     one selection pass over the same score rows (`temp_filtered_topk`): filter, total order (score, then entity id) and a
-    list that is carried across column panels, so the Q x N matrix never has to exist at once."""
+    list that is carried across column panels, so the Q x N matrix never has to exist at once;
+  * the two-table post models score against a local and a temporal all-entity table and mix by per-query gates: their
+    `topk_single_graph` hands the selection both score matrices and the weights (`temp_filtered_topk_mix`), and the mix happens
+    in registers."""
 import numpy as np
 import torch
 
@@ -63,6 +66,30 @@ def topk_composite(scores, k, filt_ptr=None, filt_ids=None, keep=None, col0=0, n
         val = torch.cat([val, val.new_full((P, k - val.shape[1]), float("-inf"))], dim=1)
         idx = torch.cat([idx, idx.new_full((P, k - idx.shape[1]), -1)], dim=1)
     return val[:, :k].contiguous(), idx[:, :k].contiguous()
+
+
+def mixed_scores(a, b, w):
+    """The mixed score rows of `temp_filtered_topk_mix` in plain torch: w[p] a[p, j] + (1 - w[p]) b[p, j], and -inf wherever EITHER
+    operand is -inf -- masked before the arithmetic, so a weight of 0 or 1 never meets an infinity (0 * inf = NaN).  With
+    topk_composite it is the route of a backend without `filtered_topk_mix` or of a k above TEMP_TOPK_MAX, and the reference of
+    the kernel's tests.  -> [P, ld] in the dtype of `a`."""
+    a, b = a.detach(), b.detach()
+    dead = (a == float("-inf")) | (b == float("-inf"))
+    wc = torch.as_tensor(w, dtype=a.dtype, device=a.device).reshape(-1, 1)
+    m = wc * a.masked_fill(dead, 0.0) + (1 - wc) * b.masked_fill(dead, 0.0)
+    return m.masked_fill(dead, float("-inf"))
+
+
+def _select(be, k):
+    """The plain selection of topk_single_graph: the backend's kernel up to TEMP_TOPK_MAX answers, else the composite."""
+    return be.filtered_topk if hasattr(be, "filtered_topk") and k <= _lib.TOPK_MAX else topk_composite
+
+
+def _select_mixed(be, k):
+    """select(s_a, s_b, w, k, ...) over mix(w, s_a, s_b): the backend's mixed kernel, else the composite on mixed_scores."""
+    if hasattr(be, "filtered_topk_mix") and k <= _lib.TOPK_MAX:
+        return be.filtered_topk_mix
+    return lambda s_a, s_b, w, k, *args, **kw: topk_composite(mixed_scores(s_a, s_b, w), k, *args, **kw)
 
 
 class EvaluationFilter:
@@ -188,24 +215,12 @@ class EvaluationFilter:
         entity or a relation that never occurs at `time` has nothing to leave out.  The scores come from the routes of
         calc_metrics_single_graph; `panel` (a multiple of 4) scores that many entities at a time and carries the lists, None does so
         only when the whole [Q, N] matrix would pass TOPK_PANEL_BYTES."""
-        if mode not in ("head", "tail"):
-            raise ValueError("topk_single_graph: mode must be 'head' or 'tail'")
         with torch.no_grad():
             dev, (num_ent, d) = all_ent_embeds.device, all_ent_embeds.shape
-            known = torch.as_tensor(known, dtype=torch.int64, device=dev).reshape(-1)
-            rel = torch.as_tensor(rel, dtype=torch.int64, device=dev).reshape(-1)
+            known, rel, ptr, ids, keep = self._topk_queries(dev, num_ent, known, rel, mode, time, filtered, keep)
             Q = known.shape[0]
             if Q == 0:
-                return torch.zeros(0, k, dtype=torch.int64, device=dev), torch.zeros(0, k, dtype=torch.float32, device=dev)
-            ptr = ids = None
-            if filtered:
-                R, tails, heads = self._true_keys_global(int(time), num_ent)
-                known_np, rel_np = known.cpu().numpy(), rel.cpu().numpy()
-                prefix = np.where((rel_np >= 0) & (rel_np < R), known_np * R + rel_np, -1)      # a relation unseen at `time`: no key below 0
-                ptr, ids = self.filter_lists(prefix, tails if mode == "tail" else heads, num_ent)
-                ptr, ids = torch.from_numpy(ptr).to(dev), torch.from_numpy(ids).to(dev)
-            if keep is not None:
-                keep = torch.as_tensor(keep, device=dev).to(torch.int32).reshape(-1)
+                return _topk_empty(k, dev)
             be = get_backend()
             name = getattr(self.args, "score_function", None)
             kn, r = all_ent_embeds[known], rel_enc_means[rel]
@@ -215,12 +230,8 @@ class EvaluationFilter:
                 q = S.bilinear_query(name, kn, r, mode).contiguous()
             elif l1:
                 q = _translation_query(kn, r, mode)
-            ld = (num_ent + 3) // 4 * 4
-            if panel is None:
-                panel = ld if Q * ld * 4 <= TOPK_PANEL_BYTES else max(4, TOPK_PANEL_BYTES // (4 * Q) // 4 * 4)
-            if panel <= 0 or panel % 4:
-                raise ValueError("topk_single_graph: panel must be a positive multiple of 4")
-            select = be.filtered_topk if hasattr(be, "filtered_topk") and k <= _lib.TOPK_MAX else topk_composite
+            panel = _topk_panel(panel, Q, num_ent, 1)
+            select = _select(be, k)
             carry = None
             for c0 in range(0, num_ent, panel):
                 table = all_ent_embeds[c0:min(num_ent, c0 + panel)].contiguous()
@@ -229,13 +240,53 @@ class EvaluationFilter:
                 elif l1:
                     score = be.l1_scores(q, table)                       # the pad columns already -inf
                 else:
-                    rows = []
-                    for a in range(0, Q, 100):
-                        rows.append(self.calc_score(kn[a:a + 100], r[a:a + 100], table, mode="tail") if mode == "tail"
-                                    else self.calc_score(table, r[a:a + 100], kn[a:a + 100], mode="head"))
-                    score = _pad4(torch.cat(rows))
+                    score = self._literal_scores(kn, r, table, mode)
                 carry = select(score, k, ptr, ids, keep, col0=c0, n=table.shape[0], carry=carry)
             return carry[1], carry[0].float()
+
+    def _topk_queries(self, dev, num_ent, known, rel, mode, time, filtered, keep):
+        """The front half of every topk_single_graph: -> (known [Q] int64, rel [Q] int64, filt_ptr, filt_ids, keep) on `dev` -- the
+        queries' GLOBAL ids, their filter lists out of _true_keys_global (None, None when not filtered) and the int32 keep ids."""
+        if mode not in ("head", "tail"):
+            raise ValueError("topk_single_graph: mode must be 'head' or 'tail'")
+        known = torch.as_tensor(known, dtype=torch.int64, device=dev).reshape(-1)
+        rel = torch.as_tensor(rel, dtype=torch.int64, device=dev).reshape(-1)
+        ptr = ids = None
+        if filtered and known.shape[0]:
+            R, tails, heads = self._true_keys_global(int(time), num_ent)
+            known_np, rel_np = known.cpu().numpy(), rel.cpu().numpy()
+            prefix = np.where((rel_np >= 0) & (rel_np < R), known_np * R + rel_np, -1)      # a relation unseen at `time`: no key below 0
+            ptr, ids = self.filter_lists(prefix, tails if mode == "tail" else heads, num_ent)
+            ptr, ids = torch.from_numpy(ptr).to(dev), torch.from_numpy(ids).to(dev)
+        if keep is not None:
+            keep = torch.as_tensor(keep, device=dev).to(torch.int32).reshape(-1)
+        return known, rel, ptr, ids, keep
+
+    def _literal_scores(self, kn, r, table, mode):
+        """calc_score of every query against the rows of `table` ([n, D], or [Q, n, D]: its own candidates per query), 100 queries at
+        a time, padded to whole float4s with -inf."""
+        rows = []
+        for a in range(0, kn.shape[0], 100):
+            cand = table if table.dim() == 2 else table[a:a + 100]
+            rows.append(self.calc_score(kn[a:a + 100], r[a:a + 100], cand, mode="tail") if mode == "tail"
+                        else self.calc_score(cand, r[a:a + 100], kn[a:a + 100], mode="head"))
+        return _pad4(torch.cat(rows))
+
+
+def _topk_empty(k, dev):
+    return torch.zeros(0, k, dtype=torch.int64, device=dev), torch.zeros(0, k, dtype=torch.float32, device=dev)
+
+
+def _topk_panel(panel, Q, num_ent, matrices):
+    """Columns scored per selection call.  `panel` as the caller gave it (a positive multiple of 4); None: all N at once while the
+    `matrices` [Q, ld] score matrices alive at that moment stay at or under TOPK_PANEL_BYTES, else as many columns as do."""
+    ld = (num_ent + 3) // 4 * 4
+    if panel is None:
+        per = 4 * Q * matrices
+        panel = ld if per * ld <= TOPK_PANEL_BYTES else max(4, TOPK_PANEL_BYTES // per // 4 * 4)
+    if panel <= 0 or panel % 4:
+        raise ValueError("topk_single_graph: panel must be a positive multiple of 4")
+    return panel
 
 
 def _w_col(w, P, like):
@@ -250,20 +301,39 @@ class _MixedRankFilter(EvaluationFilter):
     """Shared part of the two post-ensemble filters: for one corruption mode, the score matrix of the mixed (local, temporal)
     representation, then the filtered rank (the filter list replaces the reference's -10e6 overwrite, as in the base class)."""
 
-    def _score_matrix(self, known, r, all_embeds, mode, eval_bz):
+    def _score_matrix(self, known, r, all_embeds, mode, eval_bz, padded=False):
+        """[P, N] scores of the known rows against every row of all_embeds; padded: [P, N rounded up to a multiple of 4], the pad
+        columns -inf (what the selection kernels take)."""
         name = getattr(self.args, "score_function", None)
         P, num_ent = known.shape[0], all_embeds.shape[0]
         if name in ("distmult", "complex") and num_ent % 4 == 0 and all_embeds.shape[1] % 4 == 0:
             q = S.bilinear_query(name, known, r, mode).contiguous()
             return get_backend().linear(q, all_embeds.contiguous(), True)
         if _l1_route(name, get_backend(), all_embeds.shape[1]):
-            return get_backend().l1_scores(_translation_query(known, r, mode), all_embeds.contiguous())[:, :num_ent]
+            score = get_backend().l1_scores(_translation_query(known, r, mode), all_embeds.contiguous())
+            return score if padded else score[:, :num_ent]
         rows = []
         for a in range(0, P, eval_bz):
             b = min(P, a + eval_bz)
             rows.append(self.calc_score(known[a:b], r[a:b], all_embeds, mode="tail") if mode == "tail"
                         else self.calc_score(all_embeds, r[a:b], known[a:b], mode="head"))
-        return torch.cat(rows)
+        return _pad4(torch.cat(rows)) if padded else torch.cat(rows)
+
+    def _mixed_topk(self, known_loc, known_rec, r, all_loc, all_rec, w, mode, k, ptr, ids, keep, panel):
+        """The selection over mix(w, score(known_loc, all_loc), score(known_rec, all_rec)), the two score matrices from the routes
+        of _score_matrix panel by panel.  Two matrices are alive at once: all N columns in one go while 2 Q ld 4 bytes stay at or
+        under TOPK_PANEL_BYTES, else panels with the carry."""
+        Q, num_ent = known_loc.shape[0], all_loc.shape[0]
+        panel = _topk_panel(panel, Q, num_ent, 2)
+        select = _select_mixed(get_backend(), k)
+        w = w.reshape(-1).contiguous()
+        carry = None
+        for c0 in range(0, num_ent, panel):
+            c1 = min(num_ent, c0 + panel)
+            s_loc = self._score_matrix(known_loc, r, all_loc[c0:c1], mode, 100, padded=True)
+            s_rec = self._score_matrix(known_rec, r, all_rec[c0:c1], mode, 100, padded=True)
+            carry = select(s_loc, s_rec, w, k, ptr, ids, keep, col0=c0, n=c1 - c0, carry=carry)
+        return carry[1], carry[0].float()
 
     def _rank(self, score, mode, samples, graph, time, num_ent, dev):
         target, ptr, ids = self._mode_inputs(mode, samples, graph, time, num_ent, dev)
@@ -290,6 +360,22 @@ class PostEnsembleEvaluationFilter(_MixedRankFilter):
                 wc = _w_col(w, P, s_loc)
                 out[mode] = self._rank(wc * s_loc + (1 - wc) * s_tmp, mode, samples, graph, time, num_ent, dev)
             return torch.cat([out["head"], out["tail"]])
+
+    def topk_single_graph(self, all_loc, all_rec, rel_enc_means, known, rel, w, mode, time, k, filtered=True, keep=None, panel=None):
+        """EvaluationFilter.topk_single_graph for the score-level ensemble: the k best answers under
+        w[i] * score(all_loc[known[i]], rel[i], all_loc[e]) + (1 - w[i]) * score(all_rec[known[i]], rel[i], all_rec[e]),
+        w [Q] the queries' mixing weights.  all_loc / all_rec [N, D] are the local and the temporal all-entity table; `known` holds
+        GLOBAL ids, and the filter lists, `keep`, `panel` and the returned (ids [Q, k] int64, scores [Q, k] float32) are the base
+        class's.  The mix is formed inside the selection (`temp_filtered_topk_mix`): the mixed [Q, N] matrix is never written."""
+        with torch.no_grad():
+            dev, num_ent = all_loc.device, all_loc.shape[0]
+            known, rel, ptr, ids, keep = self._topk_queries(dev, num_ent, known, rel, mode, time, filtered, keep)
+            if known.shape[0] == 0:
+                return _topk_empty(k, dev)
+            w = torch.as_tensor(w, dtype=torch.float32, device=dev).reshape(-1)
+            if w.shape[0] != known.shape[0]:
+                raise ValueError("topk_single_graph: w must have one entry per query")
+            return self._mixed_topk(all_loc[known], all_rec[known], rel_enc_means[rel], all_loc, all_rec, w, mode, k, ptr, ids, keep, panel)
 
 
 class PostEvaluationFilter(_MixedRankFilter):
@@ -333,6 +419,47 @@ class PostEvaluationFilter(_MixedRankFilter):
                     score = torch.cat(rows)
                 out[mode] = self._rank(score, mode, samples, graph, time, num_ent, dev)
             return torch.cat([out["head"], out["tail"]])
+
+    def topk_single_graph(self, all_loc, all_rec, rel_enc_means, known, rel, w_known, w_cand, mode, time, k, filtered=True, keep=None,
+                          panel=None):
+        """EvaluationFilter.topk_single_graph for the embedding-level gate, as in calc_metrics_single_graph: the known row is
+        w_known[i] * all_loc[known[i]] + (1 - w_known[i]) * all_rec[known[i]], candidate e is w_cand[i] * all_loc[e] +
+        (1 - w_cand[i]) * all_rec[e]; w_known, w_cand [Q].  distmult / complex are linear in the candidate: the ONE folded query
+        against both tables gives two score matrices and the selection mixes them in registers (`temp_filtered_topk_mix`); transE
+        takes `temp_l1_mix_scores` and the plain selection; any other scorer, or a backend without that kernel, the literal
+        calc_score route over the mixed candidates.  Everything else is the base class's."""
+        with torch.no_grad():
+            dev, (num_ent, d) = all_loc.device, all_loc.shape
+            known, rel, ptr, ids, keep = self._topk_queries(dev, num_ent, known, rel, mode, time, filtered, keep)
+            Q = known.shape[0]
+            if Q == 0:
+                return _topk_empty(k, dev)
+            w_known = torch.as_tensor(w_known, dtype=torch.float32, device=dev).reshape(-1, 1)
+            w_cand = torch.as_tensor(w_cand, dtype=torch.float32, device=dev).reshape(-1, 1)
+            if w_known.shape[0] != Q or w_cand.shape[0] != Q:
+                raise ValueError("topk_single_graph: w_known and w_cand must have one entry per query")
+            kn = w_known * all_loc[known] + (1 - w_known) * all_rec[known]
+            r = rel_enc_means[rel]
+            name = getattr(self.args, "score_function", None)
+            if name in ("distmult", "complex"):
+                return self._mixed_topk(kn, kn, r, all_loc, all_rec, w_cand, mode, k, ptr, ids, keep, panel)
+            be = get_backend()
+            l1 = _l1_route(name, be, d) and hasattr(be, "l1_mix_scores")
+            if l1:
+                q = _translation_query(kn, r, mode)
+            # one score matrix at a time; the literal route also holds the [Q, panel, D] mixed candidates
+            panel = _topk_panel(panel, Q, num_ent, 1 if l1 else 1 + d)
+            select = _select(be, k)
+            carry = None
+            for c0 in range(0, num_ent, panel):
+                t_loc, t_rec = all_loc[c0:min(num_ent, c0 + panel)].contiguous(), all_rec[c0:min(num_ent, c0 + panel)].contiguous()
+                if l1:
+                    score = be.l1_mix_scores(q, t_loc, t_rec, w_cand.contiguous())       # the pad columns already -inf
+                else:
+                    score = self._literal_scores(kn, r, w_cand.unsqueeze(-1) * t_loc.unsqueeze(0) + (1 - w_cand).unsqueeze(-1) * t_rec.unsqueeze(0),
+                                                 mode)
+                carry = select(score, k, ptr, ids, keep, col0=c0, n=t_loc.shape[0], carry=carry)
+            return carry[1], carry[0].float()
 
 
 def _pad4(score):

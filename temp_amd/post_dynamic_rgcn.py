@@ -395,6 +395,16 @@ class _TwoStreamMixin:
         gid = _gids_dev(g, self._device())
         return a_loc.index_copy(0, gid, convoluted_loc), a_rec.index_copy(0, gid, convoluted_rec)
 
+    def all_entity_table_pairs(self, t_list):
+        """predict_gated's hook (post_gates._FrequencyGateMixin): the embedding half of evaluate() -- the window with the local
+        history stream on the full train graphs at test_seq_len, then every window's (all_loc, all_rec) assembled over the target
+        graph the encoder ran on, as DynamicRGCN.all_entity_tables does for one table."""
+        wb = self.prepare(t_list, self.test_seq_len, train=False)
+        out, hist = self.run(wb)
+        for i, (loc, rec) in enumerate(zip(wb.out_loc.split(wb.target.sizes), out.split(wb.target.sizes))):
+            t = wb.rows[i][-1]
+            yield (t,) + tuple(self.get_all_embeds_Gt(loc, rec, wb.graphs[i], t, wb.plan, i, hist, wb.hist_loc))
+
     def run_loss(self, wb, samples=None, weights=None):
         """PostEnsembleDynamicRGCN.forward, models/PostDynamicRGCN.py:375-397; PostEnsembleBiDynamicRGCN.forward,
         models/PostBiDynamicRGCN.py:329-354; Post(Bi)DynamicRGCN.forward, models/PostDynamicRGCN.py:189-208 /
@@ -427,6 +437,16 @@ class _PostEnsembleMixin(_TwoStreamMixin):
     """The score-level ensemble (models/PostDynamicRGCN.py:323-461, models/PostBiDynamicRGCN.py:283-372): the two MLPs and the
     losses are _PostWindowMixin's (init_freq_mlp, calc_ensemble_ratio, batched_ensemble_loss, ensemble_loss)."""
     _evaluater = "PostEnsembleEvaluationFilter"
+    _gate_count = 1
+
+    def _query_gates(self, t, known, rel, mode):
+        """(w,) [Q] of queries, paired as in ensemble_loss: the tail scores of a training triple are mixed by weight_object =
+        object_linear(object features), the head scores by weight_subject = subject_linear(subject features), and a query has
+        exactly those features of its known side.  (The reference's evaluate() crosses the two -- object-corruption ranks under
+        weight_subject, PostEnsembleEvaluationFilter -- which takes the features of the ANSWER's side: only a ranking of known
+        triples can do that, so it is not copied here.)"""
+        mlp = self.object_linear if mode == "tail" else self.subject_linear
+        return (torch.sigmoid(mlp(self.query_features(t, known, rel, mode))).reshape(-1),)
 
     def _step_weights(self, wb, samples, ensemble_weights):
         dev = self._device()

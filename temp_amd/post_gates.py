@@ -29,6 +29,58 @@ class _FrequencyGateMixin:
         raise NotImplementedError("%s scores against two all-entity tables (local, temporal) mixed by per-triple gates: predict() covers the "
                                   "single-table models only" % type(self).__name__)
 
+    # -- prediction through the gates -----------------------------------------------------------------------------------------
+    _gate_count = 0                       # weights a query carries: 1 (score-level ensemble), 2 (embedding-level gate: known, candidates)
+
+    def all_entity_table_pairs(self, t_list):
+        """Per-family hook of `predict_gated`: yields (t, all_loc [N_ents, D], all_rec [N_ents, D]) for every timestamp of `t_list`
+        -- the embedding half of the family's evaluate(): the window at test_seq_len on the full train graphs (train=False) and the
+        two all-entity matrices over the target graph the encoder ran on."""
+        raise NotImplementedError("%s has one all-entity table and no gates: predict_gated() covers the two-table post models" % type(self).__name__)
+
+    def query_features(self, t, known, rel, mode):
+        """Frequency features of the KNOWN side of queries at timestamp t (global ids), all a query has -> (Q, 3) on the device.
+        tail (s, r, ?): the object features [agg_sub[s], agg_rel[r], agg_sub_rel[(s, r)]]; head (?, r, o): the subject features
+        [agg_obj[o], agg_rel[r], agg_obj_rel[(o, r)]] -- the rows a training triple's object / subject MLP sees."""
+        sub_f, obj_f = self.frequency_tables().features(int(t), known, rel, known)
+        return torch.from_numpy(obj_f if mode == "tail" else sub_f).to(self._device())
+
+    def _query_gates(self, t, known, rel, mode):
+        """-> the `_gate_count` weights [Q] of the queries from the model's own frequency MLPs."""
+        raise NotImplementedError
+
+    def predict_gated(self, queries, mode="tail", k=10, filtered=True, weights=None):
+        """`predict` for the models that score against two all-entity tables: the k best answers of every query under the gated
+        score.  queries, mode, k, filtered and the returned (ids [Q, k] int64, scores [Q, k] float32, rows in query order) are
+        TKG_Module.predict's.  weights: None for the model's own frequency MLPs on the known side of the query -- the pairing of the
+        training loss: a tail query is gated by the object MLP(s), a head query by the subject MLP(s) (see _query_gates) -- or
+        injected weights, the counterpart of forward(..., ensemble_weights= / gate_weights=): a [Q] tensor for the score-level
+        ensemble, a pair (w_known [Q], w_cand [Q]) for the embedding-level gate.  The scorer is evaluate()'s (the real head / tail
+        mode; head_scored_as_tail is a quirk of the training loss alone).  Adds no parameters or buffers."""
+        if mode not in ("head", "tail"):
+            raise ValueError("predict_gated: mode must be 'head' or 'tail'")
+        q = queries.detach().cpu().numpy() if torch.is_tensor(queries) else np.asarray(queries)
+        q = q.astype(np.int64).reshape(-1, 3)
+        dev = self._device()
+        if weights is not None:
+            weights = (weights,) if torch.is_tensor(weights) else tuple(weights)
+            if len(weights) != self._gate_count or any(not torch.is_tensor(w) or w.numel() != q.shape[0] for w in weights):
+                raise ValueError("predict_gated: weights must be %s" % ("a [Q] tensor" if self._gate_count == 1 else "a pair (w_known [Q], w_cand [Q])"))
+            weights = tuple(w.detach().to(dev, torch.float32).reshape(-1) for w in weights)
+        ranker = self._ranker()
+        ids = torch.full((q.shape[0], k), -1, dtype=torch.int64, device=dev)
+        vals = torch.full((q.shape[0], k), float("-inf"), dtype=torch.float32, device=dev)
+        ts = sorted(set(int(t) for t in q[:, 0]))
+        with torch.no_grad():
+            for a in range(0, len(ts), self.predict_batch):
+                for t, all_loc, all_rec in self.all_entity_table_pairs(ts[a:a + self.predict_batch]):
+                    rows = np.nonzero(q[:, 0] == int(t))[0]
+                    sel = torch.from_numpy(rows).to(dev)
+                    gates = self._query_gates(int(t), q[rows, 1], q[rows, 2], mode) if weights is None else tuple(w[sel] for w in weights)
+                    i, v = ranker.topk_single_graph(all_loc, all_rec, self.rel_embeds, q[rows, 1], q[rows, 2], *gates, mode, int(t), k, filtered)
+                    ids[sel], vals[sel] = i, v
+        return ids, vals
+
     def frequency_tables(self):
         ft = getattr(self, "_freq_tables", None)
         if ft is None:
@@ -88,6 +140,16 @@ class _GatedLossMixin(_FrequencyGateMixin):
         w_oqs = torch.sigmoid(self.object_query_subject_embed_linear(obj_f))
         w_oqo = torch.sigmoid(self.object_query_subject_embed_linear(obj_f))      # (sic)
         return w_sqs, w_sqo, w_oqs, w_oqo
+
+    _gate_count = 2
+
+    def _query_gates(self, t, known, rel, mode):
+        """(w_known, w_cand) [Q] of queries, paired as in gated_loss: a tail query's known subject takes w_oqs and its candidates
+        w_oqo, a head query's known object w_sqo and its candidates w_sqs -- with calc_ensemble_ratio's quirk, both weights of a
+        mode are the *_subject_embed_linear MLP on the same features, hence one tensor."""
+        mlp = self.object_query_subject_embed_linear if mode == "tail" else self.subject_query_subject_embed_linear
+        w = torch.sigmoid(mlp(self.query_features(t, known, rel, mode))).reshape(-1)
+        return w, w
 
     def _agg_features(self, wb, samples):
         """Per window the frequency feature rows of the sampled triples, computed and uploaded ONCE per (prepared batch, sample set):

@@ -121,6 +121,15 @@ class PostSelfAttentionRGCN(_GatedLossMixin, SelfAttentionRGCN):
         wb = self.prepare(t_list, self.train_seq_len, True, target_edge_ids)
         return self.run_loss(wb, samples, gate_weights)
 
+    def all_entity_table_pairs(self, t_list):
+        """predict_gated's hook (post_gates._FrequencyGateMixin): the embedding half of evaluate() -- the encoder on the full train
+        graphs at test_seq_len, then both all-entity matrices of every window."""
+        wb = self.prepare(t_list, self.test_seq_len, train=False)
+        (loc, rec), kv2 = self.run(wb)
+        all_loc, all_rec = self.all_embeds_post(wb, loc, rec, kv2)
+        for i in range(len(wb.graphs)):
+            yield wb.rows[i][-1], all_loc[i], all_rec[i]
+
     # -- evaluate ------------------------------------------------------------------------------------------------------------
     def evaluate(self, t_list, val=True):
         """models/PostSelfAttentionRGCN.py:96-123 (Bi: :189-208): the encoder on the full train graphs, both all-entity matrices,
