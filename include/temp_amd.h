@@ -735,6 +735,31 @@ int temp_diachronic_rows_fwd(int B, int N, int d, const float* ent, const float*
 int temp_diachronic_rows_bwd(int B, int N, int d, const float* ent, const float* w, const float* b, const float* t, const float* d_out, float* d_ent,
                              float* d_w, float* d_b, void* stream);
 
+/* The hyperplane projection of a table for B normals (HyTE, baselines/Hyte.py:18-27: every entity row and every relation row of
+ * timestamp b is projected onto the hyperplane whose normal is that timestamp's time row), and its adjoint.  With n_b = w_b / |w_b|_2:
+ *   out[b N + i, :] = table[i, :] - n_b (n_b . table[i, :])
+ * table [N, d], w [B, d] (the B time rows, already gathered), out / d_out [B N, d], all 16-byte aligned.  One launch: the normals
+ * are normalised inside it (each wave forms them from w, TEMP_HYPERPLANE_CHUNK = 8 at a time in registers; a table row is read once
+ * per chunk, i.e. once for B <= 8), a stream of N d floats read and B N d written.
+ * The backward keeps nothing from the forward and OVERWRITES, with G = d_out,
+ *   d_table[i] = sum_b (G_bi - n_b (n_b . G_bi))                              the B terms added in ascending b
+ *   d_n_b      = -sum_i [(n_b . e_i) G_bi + (n_b . G_bi) e_i]                 e_i = table[i]
+ *   d_w_b      = (d_n_b - n_b (n_b . d_n_b)) / |w_b|
+ * in two launches and without floating-point atomics.  The sum over i runs over FIXED tiles of TEMP_HYPERPLANE_TILE_ROWS = 32
+ * consecutive rows (tile t = rows [32 t, 32 t + 32) whatever the device or the grid): the first launch writes every tile's partial
+ * of every normal into `workspace` ([tiles, B, d] floats, each written once: no zero fill), the second adds them in ascending
+ * tile order and applies the normalisation Jacobian.  Results are bit-repeatable.
+ *   workspace bytes = ceil(N / TEMP_HYPERPLANE_TILE_ROWS) * B * d * 4       (= temp_hyperplane_rows_bwd_workspace(B, N, d))
+ * A smaller or NULL workspace returns TEMP_E_BADARG and launches nothing.  Any B >= 1, N >= 1, d >= 1 (else TEMP_E_BADARG):
+ * float4 columns when d % 4 == 0, one float per lane otherwise; rows of more than 64 such columns are walked by a column loop.
+ * A zero time row gives non-finite values, as the reference's division does. */
+#define TEMP_HYPERPLANE_TILE_ROWS 32
+#define TEMP_HYPERPLANE_CHUNK 8
+size_t temp_hyperplane_rows_bwd_workspace(int B, int N, int d);
+int temp_hyperplane_rows_fwd(int B, int N, int d, const float* table, const float* w, float* out, void* stream);
+int temp_hyperplane_rows_bwd(int B, int N, int d, const float* table, const float* w, const float* d_out, float* d_table, float* d_w,
+                             void* workspace, size_t workspace_bytes, void* stream);
+
 /* ------------------------------------------------------------------------------------------------
  * Plain fp32 MFMA GEMMs (the extra (n,D)@(D,D) terms of the linear-recurrence layers,
  * models/RRGCN.py:141, models/BiRRGCN.py:128-129; the all-entity score matrix below).

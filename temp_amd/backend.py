@@ -403,6 +403,31 @@ class HipBackend:
                                                      _ptr(d_b), _stream()), "temp_diachronic_rows_bwd")
         return d_ent, d_w, d_b
 
+    # ---- the hyperplane projection of a table (include/temp_amd.h: temp_hyperplane_rows_fwd / _bwd) --------
+    def hyperplane_rows_fwd(self, table, w):
+        """-> (B N, d) stack of table - n_b (n_b . table), n_b = w_b / |w_b|, for the B rows of `w` (one launch)."""
+        table, w = _f32(table, "table"), _f32(w, "w")
+        if table.dim() != 2 or w.dim() != 2 or w.shape[1] != table.shape[1]:
+            raise _lib.TempAmdError("hyperplane_rows: table (N, d) and w (B, d) expected")
+        N, d = table.shape
+        out = torch.empty(w.shape[0] * N, d, dtype=torch.float32, device=table.device)
+        _lib.check(self.lib.temp_hyperplane_rows_fwd(w.shape[0], N, d, _ptr(table), _ptr(w), _ptr(out), _stream()), "temp_hyperplane_rows_fwd")
+        return out
+
+    def hyperplane_rows_bwd(self, table, w, d_out):
+        """-> (d_table, d_w), each overwritten whole (two launches, no atomics; the tile partials go through the backend's workspace)."""
+        table, w, d_out = _f32(table, "table"), _f32(w, "w"), _f32(d_out, "d_out")
+        N, d = table.shape
+        B = w.shape[0]
+        if tuple(d_out.shape) != (B * N, d):
+            raise _lib.TempAmdError("hyperplane_rows_bwd: d_out must be (B N, d)")
+        d_table, d_w = torch.empty_like(table), torch.empty_like(w)
+        nb = self.lib.temp_hyperplane_rows_bwd_workspace(B, N, d)
+        ws = self._ws(nb, table.device)
+        _lib.check(self.lib.temp_hyperplane_rows_bwd(B, N, d, _ptr(table), _ptr(w), _ptr(d_out), _ptr(d_table), _ptr(d_w), _ptr(ws), nb, _stream()),
+                   "temp_hyperplane_rows_bwd")
+        return d_table, d_w
+
     # ---- persistent window chain (include/temp_amd.h: TempGruChain) -------------------------------
     def gru_chain_supported(self, d):
         return bool(self.lib.temp_gru_chain_supported(int(d)))

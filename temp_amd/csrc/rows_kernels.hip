@@ -509,6 +509,396 @@ static bool diachronic_vec(int d) { return d % 4 == 0 && (d / 2) % 4 == 0; }
 static bool diachronic_args_ok(int B, int N, int d) {
   return B >= 1 && N >= 1 && d >= 2 && ((long long)N * d + 255) / 256 <= 0x7fffffffLL;       // (the grid: one thread per V columns)
 }
+
+// ---- the hyperplane projection of a table for B normals (HyTE: e - n_b (n_b . e), n_b = w_b / |w_b|) and its adjoint --------------
+// One BLOCK of four waves owns one tile of HP_TILE_ROWS consecutive table rows (tile t = rows [32 t, 32 t + 32) whatever the grid:
+// the blocks stride over the tiles), wave v its rows [8 v, 8 v + 8), and walks the B normals HP_CHUNK at a time.  LPR lanes share a
+// row, one V-column vector each (d / V <= LPR), so a wave has G = 64 / LPR rows in flight and group g takes rows g, g + G, ... of the
+// wave's eight; the row dots are xor butterflies over the LPR lanes (every lane of the group ends with the same bits).  (A wave per
+// tile walked 32 / G rows one after the other: at N = 7 128 that is 223 waves on 256 CUs, each waiting out 16 - 32 load round
+// trips.)  The chunk's normals live in registers: each wave forms them from w itself -- sum of squares by the same butterfly,
+// n = w * (1 / sqrt) -- so there is no pre-kernel; LDS holds only the backward's four per-wave sums of a tile.
+// Rows wider than 64 vectors take the *_wide kernels: one row per wave at a time, the lanes loop over the columns, and what the
+// register kernels keep in registers (the normals, the running sums) is re-read from w / written through to its destination; there
+// a wave owns a tile.
+#define HP_TILE_ROWS TEMP_HYPERPLANE_TILE_ROWS
+#define HP_CHUNK TEMP_HYPERPLANE_CHUNK                             // normals held on chip at a time
+
+template <int LPR>
+__device__ __forceinline__ float hp_group_sum(float v) {
+#pragma unroll
+  for (int m = 1; m < LPR; m <<= 1) v += __shfl_xor(v, m);
+  return v;
+}
+
+// the chunk's normals [b0, b0 + HP_CHUNK) at this lane's columns (zero past B and past the row's width)
+template <int V, int LPR>
+__device__ __forceinline__ void hp_normals(int B, int dv, int b0, int col, bool col_ok, const DeVec<V>* __restrict__ w, DeVec<V> (&nrm)[HP_CHUNK]) {
+#pragma unroll
+  for (int k = 0; k < HP_CHUNK; ++k) {
+    const int b = b0 + k;
+    DeVec<V> wv;
+#pragma unroll
+    for (int u = 0; u < V; ++u) wv.v[u] = 0.f;
+    if (col_ok && b < B) wv = w[(size_t)b * dv + col];
+    float ss = 0.f;
+#pragma unroll
+    for (int u = 0; u < V; ++u) ss = fmaf(wv.v[u], wv.v[u], ss);
+    ss = hp_group_sum<LPR>(ss);
+    const float inv = b < B ? 1.0f / sqrtf(ss) : 0.f;
+#pragma unroll
+    for (int u = 0; u < V; ++u) nrm[k].v[u] = wv.v[u] * inv;
+  }
+}
+
+template <int V, int LPR>
+__global__ void __launch_bounds__(256) k_hyperplane_fwd(int B, int N, int d, const float* __restrict__ table, const float* __restrict__ w,
+                                                        float* __restrict__ out) {
+  using Vec = DeVec<V>;
+  constexpr int G = 64 / LPR, WROWS = HP_TILE_ROWS / 4, RPG = WROWS / G;     // rows per wave, rows per group
+  const int dv = d / V;
+  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6, grp = lane / LPR, col = lane - grp * LPR;
+  const bool col_ok = col < dv;
+  const int n_tiles = (int)(((long long)N + HP_TILE_ROWS - 1) / HP_TILE_ROWS);
+  const size_t plane = (size_t)N * dv;
+  Vec* __restrict__ o = (Vec*)out;
+  for (int t = blockIdx.x; t < n_tiles; t += gridDim.x) {
+    for (int b0 = 0; b0 < B; b0 += HP_CHUNK) {
+      Vec nrm[HP_CHUNK];
+      hp_normals<V, LPR>(B, dv, b0, col, col_ok, (const Vec*)w, nrm);
+      for (int j = 0; j < RPG; ++j) {
+        const long long i = (long long)t * HP_TILE_ROWS + wv * WROWS + j * G + grp;
+        const bool ok = col_ok && i < N;
+        Vec e;
+#pragma unroll
+        for (int u = 0; u < V; ++u) e.v[u] = 0.f;
+        if (ok) e = ((const Vec*)table)[(size_t)i * dv + col];
+        float dot[HP_CHUNK];
+#pragma unroll
+        for (int k = 0; k < HP_CHUNK; ++k) {
+          float a = 0.f;
+#pragma unroll
+          for (int u = 0; u < V; ++u) a = fmaf(nrm[k].v[u], e.v[u], a);
+          dot[k] = a;
+        }
+#pragma unroll
+        for (int k = 0; k < HP_CHUNK; ++k) dot[k] = hp_group_sum<LPR>(dot[k]);
+#pragma unroll
+        for (int k = 0; k < HP_CHUNK; ++k) {
+          if (ok && b0 + k < B) {
+            Vec r;
+#pragma unroll
+            for (int u = 0; u < V; ++u) r.v[u] = fmaf(-nrm[k].v[u], dot[k], e.v[u]);
+            o[(size_t)(b0 + k) * plane + (size_t)i * dv + col] = r;
+          }
+        }
+      }
+    }
+  }
+}
+
+// Adjoint, first launch.  Per row i and normal b: s = n_b . G_bi, p = n_b . e_i;  d_table[i] += G_bi - n_b s (ascending b: in
+// registers within a chunk, through d_table itself -- the same lane re-reads what it wrote -- from one chunk to the next) and the
+// tile's share of -d_n_b, sum_i p G_bi + s e_i: a group adds its rows in ascending order, the G groups of a wave meet in a butterfly,
+// the four waves in LDS in wave order, and wave 0 writes part[t][b][:].  Every (t, b) is written exactly once, so the workspace
+// needs no zero fill.
+template <int V, int LPR>
+__global__ void __launch_bounds__(256) k_hyperplane_bwd(int B, int N, int d, const float* __restrict__ table, const float* __restrict__ w,
+                                                        const float* __restrict__ d_out, float* d_table, float* __restrict__ part) {
+  using Vec = DeVec<V>;
+  constexpr int G = 64 / LPR, WROWS = HP_TILE_ROWS / 4, RPG = WROWS / G;     // rows per wave, rows per group
+  const int dv = d / V;
+  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6, grp = lane / LPR, col = lane - grp * LPR;
+  const bool col_ok = col < dv;
+  const int n_tiles = (int)(((long long)N + HP_TILE_ROWS - 1) / HP_TILE_ROWS);
+  const size_t plane = (size_t)N * dv;
+  const Vec* __restrict__ gp = (const Vec*)d_out;
+  Vec* dt = (Vec*)d_table;
+  __shared__ Vec red[4][HP_CHUNK][LPR];                                     // the four waves' sums of the chunk: 32 KB at V = 4, LPR = 64
+  for (int t = blockIdx.x; t < n_tiles; t += gridDim.x) {                 // (block-uniform: the barriers below are reached by all)
+    for (int b0 = 0; b0 < B; b0 += HP_CHUNK) {
+      Vec nrm[HP_CHUNK], acc[HP_CHUNK];
+      hp_normals<V, LPR>(B, dv, b0, col, col_ok, (const Vec*)w, nrm);
+#pragma unroll
+      for (int k = 0; k < HP_CHUNK; ++k)
+#pragma unroll
+        for (int u = 0; u < V; ++u) acc[k].v[u] = 0.f;
+#pragma unroll 1
+      for (int j = 0; j < RPG; ++j) {
+        const long long i = (long long)t * HP_TILE_ROWS + wv * WROWS + j * G + grp;
+        const bool ok = col_ok && i < N;
+        const size_t at_i = (size_t)i * dv + col;
+        Vec e, at, g[HP_CHUNK];
+#pragma unroll
+        for (int u = 0; u < V; ++u) e.v[u] = at.v[u] = 0.f;
+        if (ok) e = ((const Vec*)table)[at_i];
+        if (ok && b0 > 0) at = dt[at_i];
+#pragma unroll
+        for (int k = 0; k < HP_CHUNK; ++k) {
+#pragma unroll
+          for (int u = 0; u < V; ++u) g[k].v[u] = 0.f;
+          if (ok && b0 + k < B) g[k] = gp[(size_t)(b0 + k) * plane + at_i];
+        }
+        float s[HP_CHUNK], p[HP_CHUNK];
+#pragma unroll
+        for (int k = 0; k < HP_CHUNK; ++k) {
+          float a = 0.f, c = 0.f;
+#pragma unroll
+          for (int u = 0; u < V; ++u) { a = fmaf(nrm[k].v[u], g[k].v[u], a); c = fmaf(nrm[k].v[u], e.v[u], c); }
+          s[k] = a; p[k] = c;
+        }
+#pragma unroll
+        for (int k = 0; k < HP_CHUNK; ++k) { s[k] = hp_group_sum<LPR>(s[k]); p[k] = hp_group_sum<LPR>(p[k]); }
+#pragma unroll
+        for (int k = 0; k < HP_CHUNK; ++k) {
+#pragma unroll
+          for (int u = 0; u < V; ++u) {
+            at.v[u] += fmaf(-nrm[k].v[u], s[k], g[k].v[u]);
+            acc[k].v[u] += fmaf(p[k], g[k].v[u], s[k] * e.v[u]);
+          }
+        }
+        if (ok) dt[at_i] = at;
+      }
+#pragma unroll
+      for (int k = 0; k < HP_CHUNK; ++k) {
+#pragma unroll
+        for (int u = 0; u < V; ++u)
+#pragma unroll
+          for (int m = LPR; m < 64; m <<= 1) acc[k].v[u] += __shfl_xor(acc[k].v[u], m);
+        if (grp == 0) red[wv][k][col] = acc[k];
+      }
+      __syncthreads();
+      if (wv == 0 && grp == 0 && col_ok) {
+#pragma unroll
+        for (int k = 0; k < HP_CHUNK; ++k) {
+          if (b0 + k < B) {
+            Vec r;
+#pragma unroll
+            for (int u = 0; u < V; ++u) r.v[u] = ((red[0][k][col].v[u] + red[1][k][col].v[u]) + red[2][k][col].v[u]) + red[3][k][col].v[u];
+            ((Vec*)part)[((size_t)t * B + (b0 + k)) * dv + col] = r;
+          }
+        }
+      }
+      __syncthreads();                                                     // red is rewritten by the next chunk / tile
+    }
+  }
+}
+
+template <int V>
+__global__ void __launch_bounds__(256) k_hyperplane_fwd_wide(int B, int N, int d, const float* __restrict__ table, const float* __restrict__ w,
+                                                             float* __restrict__ out) {
+  using Vec = DeVec<V>;
+  const int dv = d / V;
+  const int lane = threadIdx.x & 63;
+  const int wave = (blockIdx.x * blockDim.x + threadIdx.x) >> 6, nwaves = (gridDim.x * blockDim.x) >> 6;
+  const int n_tiles = (int)(((long long)N + HP_TILE_ROWS - 1) / HP_TILE_ROWS);
+  const size_t plane = (size_t)N * dv;
+  const Vec* __restrict__ wp = (const Vec*)w;
+  const Vec* __restrict__ tp = (const Vec*)table;
+  Vec* __restrict__ o = (Vec*)out;
+  for (int t = wave; t < n_tiles; t += nwaves) {
+    for (int b0 = 0; b0 < B; b0 += HP_CHUNK) {
+      const int nb = min(HP_CHUNK, B - b0);
+      float inv[HP_CHUNK];
+#pragma unroll
+      for (int k = 0; k < HP_CHUNK; ++k) {
+        float ss = 0.f;
+        if (k < nb)
+          for (int c = lane; c < dv; c += 64) {
+            const Vec wv = wp[(size_t)(b0 + k) * dv + c];
+#pragma unroll
+            for (int u = 0; u < V; ++u) ss = fmaf(wv.v[u], wv.v[u], ss);
+          }
+        ss = hp_group_sum<64>(ss);
+        inv[k] = k < nb ? 1.0f / sqrtf(ss) : 0.f;
+      }
+      for (int r = 0; r < HP_TILE_ROWS; ++r) {
+        const long long i = (long long)t * HP_TILE_ROWS + r;
+        if (i >= N) break;                                           // (wave-uniform)
+        float dot[HP_CHUNK];
+#pragma unroll
+        for (int k = 0; k < HP_CHUNK; ++k) dot[k] = 0.f;
+        for (int c = lane; c < dv; c += 64) {
+          const Vec e = tp[(size_t)i * dv + c];
+#pragma unroll
+          for (int k = 0; k < HP_CHUNK; ++k)
+            if (k < nb) {
+              const Vec wv = wp[(size_t)(b0 + k) * dv + c];
+#pragma unroll
+              for (int u = 0; u < V; ++u) dot[k] = fmaf(wv.v[u] * inv[k], e.v[u], dot[k]);
+            }
+        }
+#pragma unroll
+        for (int k = 0; k < HP_CHUNK; ++k) dot[k] = hp_group_sum<64>(dot[k]);
+        for (int c = lane; c < dv; c += 64) {
+          const Vec e = tp[(size_t)i * dv + c];
+#pragma unroll
+          for (int k = 0; k < HP_CHUNK; ++k)
+            if (k < nb) {
+              const Vec wv = wp[(size_t)(b0 + k) * dv + c];
+              Vec q;
+#pragma unroll
+              for (int u = 0; u < V; ++u) q.v[u] = fmaf(-(wv.v[u] * inv[k]), dot[k], e.v[u]);
+              o[(size_t)(b0 + k) * plane + (size_t)i * dv + c] = q;
+            }
+        }
+      }
+    }
+  }
+}
+
+// (the running sums go through their destinations: part[t][b][c] is overwritten by the tile's first row and added to by the same
+// lane for the later ones, d_table[i][c] by the first chunk and the later ones -- the order of the additions is that of the
+// register kernels: rows ascending, b ascending)
+template <int V>
+__global__ void __launch_bounds__(256) k_hyperplane_bwd_wide(int B, int N, int d, const float* __restrict__ table, const float* __restrict__ w,
+                                                             const float* __restrict__ d_out, float* d_table, float* part) {
+  using Vec = DeVec<V>;
+  const int dv = d / V;
+  const int lane = threadIdx.x & 63;
+  const int wave = (blockIdx.x * blockDim.x + threadIdx.x) >> 6, nwaves = (gridDim.x * blockDim.x) >> 6;
+  const int n_tiles = (int)(((long long)N + HP_TILE_ROWS - 1) / HP_TILE_ROWS);
+  const size_t plane = (size_t)N * dv;
+  const Vec* __restrict__ wp = (const Vec*)w;
+  const Vec* __restrict__ tp = (const Vec*)table;
+  const Vec* __restrict__ gp = (const Vec*)d_out;
+  Vec* dt = (Vec*)d_table;
+  Vec* pp = (Vec*)part;
+  for (int t = wave; t < n_tiles; t += nwaves) {
+    for (int b0 = 0; b0 < B; b0 += HP_CHUNK) {
+      const int nb = min(HP_CHUNK, B - b0);
+      float inv[HP_CHUNK];
+#pragma unroll
+      for (int k = 0; k < HP_CHUNK; ++k) {
+        float ss = 0.f;
+        if (k < nb)
+          for (int c = lane; c < dv; c += 64) {
+            const Vec wv = wp[(size_t)(b0 + k) * dv + c];
+#pragma unroll
+            for (int u = 0; u < V; ++u) ss = fmaf(wv.v[u], wv.v[u], ss);
+          }
+        ss = hp_group_sum<64>(ss);
+        inv[k] = k < nb ? 1.0f / sqrtf(ss) : 0.f;
+      }
+      for (int r = 0; r < HP_TILE_ROWS; ++r) {
+        const long long i = (long long)t * HP_TILE_ROWS + r;
+        if (i >= N) break;                                           // (wave-uniform)
+        float s[HP_CHUNK], p[HP_CHUNK];
+#pragma unroll
+        for (int k = 0; k < HP_CHUNK; ++k) s[k] = p[k] = 0.f;
+        for (int c = lane; c < dv; c += 64) {
+          const Vec e = tp[(size_t)i * dv + c];
+#pragma unroll
+          for (int k = 0; k < HP_CHUNK; ++k)
+            if (k < nb) {
+              const Vec wv = wp[(size_t)(b0 + k) * dv + c];
+              const Vec g = gp[(size_t)(b0 + k) * plane + (size_t)i * dv + c];
+#pragma unroll
+              for (int u = 0; u < V; ++u) {
+                const float n = wv.v[u] * inv[k];
+                s[k] = fmaf(n, g.v[u], s[k]);
+                p[k] = fmaf(n, e.v[u], p[k]);
+              }
+            }
+        }
+#pragma unroll
+        for (int k = 0; k < HP_CHUNK; ++k) { s[k] = hp_group_sum<64>(s[k]); p[k] = hp_group_sum<64>(p[k]); }
+        for (int c = lane; c < dv; c += 64) {
+          const size_t at_i = (size_t)i * dv + c;
+          const Vec e = tp[at_i];
+          Vec at;
+#pragma unroll
+          for (int u = 0; u < V; ++u) at.v[u] = 0.f;
+          if (b0 > 0) at = dt[at_i];
+#pragma unroll
+          for (int k = 0; k < HP_CHUNK; ++k)
+            if (k < nb) {
+              const Vec wv = wp[(size_t)(b0 + k) * dv + c];
+              const Vec g = gp[(size_t)(b0 + k) * plane + at_i];
+              const size_t at_p = ((size_t)t * B + (b0 + k)) * dv + c;
+              Vec a;
+#pragma unroll
+              for (int u = 0; u < V; ++u) a.v[u] = 0.f;
+              if (r > 0) a = pp[at_p];
+#pragma unroll
+              for (int u = 0; u < V; ++u) {
+                const float n = wv.v[u] * inv[k];
+                at.v[u] += fmaf(-n, s[k], g.v[u]);
+                a.v[u] += fmaf(p[k], g.v[u], s[k] * e.v[u]);
+              }
+              pp[at_p] = a;
+            }
+          dt[at_i] = at;
+        }
+      }
+    }
+  }
+}
+
+// Adjoint, second launch: block b adds the tiles' partials of -d_n_b in ascending tile order (one column per thread, 32 loads in
+// flight, the additions in order), parks the sums in d_w while the block forms |w_b|^2 and w_b . sum (wave butterflies, then the
+// four waves in wave order), and applies the Jacobian of w -> w / |w|:  d_w_b = (d_n_b - n_b (n_b . d_n_b)) / |w_b|.
+__global__ void __launch_bounds__(256) k_hyperplane_bwd_finish(int B, int n_tiles, int d, const float* __restrict__ w, const float* __restrict__ part,
+                                                               float* d_w) {
+  __shared__ float red[2][4];
+  const int b = blockIdx.x, lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const size_t stride = (size_t)B * d;
+  float ss = 0.f, wa = 0.f;
+  for (int c = threadIdx.x; c < d; c += 256) {
+    const float* __restrict__ p = part + (size_t)b * d + c;
+    float acc = 0.f;
+    int t = 0;
+    for (; t + 32 <= n_tiles; t += 32) {
+      float q[32];
+#pragma unroll
+      for (int u = 0; u < 32; ++u) q[u] = p[(size_t)(t + u) * stride];
+#pragma unroll
+      for (int u = 0; u < 32; ++u) acc += q[u];
+    }
+    for (; t < n_tiles; ++t) acc += p[(size_t)t * stride];
+    const float wv = w[(size_t)b * d + c];
+    d_w[(size_t)b * d + c] = acc;
+    ss = fmaf(wv, wv, ss);
+    wa = fmaf(wv, acc, wa);
+  }
+  ss = hp_group_sum<64>(ss);
+  wa = hp_group_sum<64>(wa);
+  if (lane == 0) { red[0][wave] = ss; red[1][wave] = wa; }
+  __syncthreads();
+  ss = ((red[0][0] + red[0][1]) + red[0][2]) + red[0][3];
+  wa = ((red[1][0] + red[1][1]) + red[1][2]) + red[1][3];
+  const float inv = 1.0f / sqrtf(ss);
+  const float na = wa * inv;                                          // n_b . acc  (acc = -d_n_b)
+  for (int c = threadIdx.x; c < d; c += 256) {
+    const float n = w[(size_t)b * d + c] * inv;
+    const float acc = d_w[(size_t)b * d + c];                          // (this thread's own store)
+    d_w[(size_t)b * d + c] = fmaf(n, na, -acc) * inv;
+  }
+}
+
+static bool hyperplane_args_ok(int B, int N, int d) { return B >= 1 && N >= 1 && d >= 1; }
+static int hyperplane_tiles(int N) { return (int)(((long long)N + HP_TILE_ROWS - 1) / HP_TILE_ROWS); }
+static int hyperplane_grid(int N, bool wide) {                      // a block per tile; a wave per tile in the column-loop kernels
+  const int g = wide ? ceil_div(hyperplane_tiles(N), 4) : hyperplane_tiles(N);
+  return g > 8192 ? 8192 : g;
+}
+// kernel<V, LPR> for rows of up to 16 / 32 / 64 vectors, kernel_wide<V> beyond; V = 4 when float4 divides the row
+#define TEMP_HYPERPLANE(KID, kern, ...)                                                                                                  \
+  do {                                                                                                                                   \
+    const int dv = d % 4 == 0 ? d / 4 : d;                                                                                               \
+    const dim3 grid(hyperplane_grid(N, dv > 64)), block(256);                                                                            \
+    if (d % 4 == 0) {                                                                                                                    \
+      if (dv <= 16) TEMP_LAUNCH(KID, (kern<4, 16>), grid, block, 0, st, __VA_ARGS__);                                                    \
+      else if (dv <= 32) TEMP_LAUNCH(KID, (kern<4, 32>), grid, block, 0, st, __VA_ARGS__);                                               \
+      else if (dv <= 64) TEMP_LAUNCH(KID, (kern<4, 64>), grid, block, 0, st, __VA_ARGS__);                                               \
+      else TEMP_LAUNCH(KID, (kern##_wide<4>), grid, block, 0, st, __VA_ARGS__);                                                          \
+    } else {                                                                                                                             \
+      if (dv <= 16) TEMP_LAUNCH(KID, (kern<1, 16>), grid, block, 0, st, __VA_ARGS__);                                                    \
+      else if (dv <= 32) TEMP_LAUNCH(KID, (kern<1, 32>), grid, block, 0, st, __VA_ARGS__);                                               \
+      else if (dv <= 64) TEMP_LAUNCH(KID, (kern<1, 64>), grid, block, 0, st, __VA_ARGS__);                                               \
+      else TEMP_LAUNCH(KID, (kern##_wide<1>), grid, block, 0, st, __VA_ARGS__);                                                          \
+    }                                                                                                                                    \
+  } while (0)
 }  // namespace temp
 
 using namespace temp;
@@ -576,6 +966,28 @@ int temp_diachronic_rows_bwd(int B, int N, int d, const float* ent, const float*
   else
     TEMP_LAUNCH(K_DIACHRONIC_BWD, k_diachronic_bwd<1>, dim3(ceil_div((long long)N * d, 256)), dim3(256), 0, (hipStream_t)stream, B, N, d, ent, w, b, t,
                 d_out, d_ent, d_w, d_b);
+  return launch_status();
+}
+
+size_t temp_hyperplane_rows_bwd_workspace(int B, int N, int d) {
+  return hyperplane_args_ok(B, N, d) ? (size_t)hyperplane_tiles(N) * (size_t)B * (size_t)d * sizeof(float) : 0;
+}
+
+int temp_hyperplane_rows_fwd(int B, int N, int d, const float* table, const float* w, float* out, void* stream) {
+  if (!hyperplane_args_ok(B, N, d) || !table || !w || !out) return TEMP_E_BADARG;
+  hipStream_t st = (hipStream_t)stream;
+  TEMP_HYPERPLANE(K_HYPERPLANE_FWD, k_hyperplane_fwd, B, N, d, table, w, out);
+  return launch_status();
+}
+
+int temp_hyperplane_rows_bwd(int B, int N, int d, const float* table, const float* w, const float* d_out, float* d_table, float* d_w,
+                             void* workspace, size_t workspace_bytes, void* stream) {
+  if (!hyperplane_args_ok(B, N, d) || !table || !w || !d_out || !d_table || !d_w || !workspace) return TEMP_E_BADARG;
+  if (workspace_bytes < temp_hyperplane_rows_bwd_workspace(B, N, d)) return TEMP_E_BADARG;
+  hipStream_t st = (hipStream_t)stream;
+  float* part = (float*)workspace;
+  TEMP_HYPERPLANE(K_HYPERPLANE_BWD, k_hyperplane_bwd, B, N, d, table, w, d_out, d_table, part);
+  TEMP_LAUNCH(K_HYPERPLANE_BWD_FINISH, k_hyperplane_bwd_finish, dim3(B), dim3(256), 0, st, B, hyperplane_tiles(N), d, w, (const float*)part, d_w);
   return launch_status();
 }
 

@@ -373,6 +373,29 @@ def diachronic_rows(ent, w, b, t):
     return _DiachronicRowsFn.apply(ent.contiguous(), w.contiguous(), b.contiguous(), t.contiguous())
 
 
+class _HyperplaneRowsFn(torch.autograd.Function):
+    """The (B N, D) stack of `table` projected onto the B hyperplanes with normals w_b / |w_b| (temp_hyperplane_rows_fwd); the
+    backward keeps nothing but its inputs and sums d_w over the N rows in a fixed order (temp_hyperplane_rows_bwd)."""
+
+    @staticmethod
+    def forward(ctx, table, w):
+        ctx.save_for_backward(table, w)
+        return get_backend().hyperplane_rows_fwd(table, w)
+
+    @staticmethod
+    def backward(ctx, d_out):
+        table, w = ctx.saved_tensors
+        return get_backend().hyperplane_rows_bwd(table, w, d_out.contiguous())
+
+
+def hyperplane_rows(table, w):
+    """Rows b N + i of the result = table[i] - n_b (n_b . table[i]), n_b = w[b] / |w[b]|_2 (baselines/Hyte.py:22-26 for B time rows at
+    once).  table (N, D), w (B, D) float32 on one device; both get gradients."""
+    if table.dim() != 2 or w.dim() != 2 or w.shape[1] != table.shape[1] or w.shape[0] < 1:
+        raise ValueError("hyperplane_rows: table (N, D) and w (B >= 1, D) expected")
+    return _HyperplaneRowsFn.apply(table.contiguous(), w.contiguous())
+
+
 class _HistoryAttentionFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, qkv, kv_hist, idx, decay, inverse):

@@ -1,13 +1,15 @@
-"""The embedding-only baselines of the paper's tables, with the reference's interface: `--module Static` (baselines/Static.py) and
-`--module DE`, the diachronic embedding (baselines/DiachronicEmbedding.py), both on baselines/TKG_Non_Recurrent.py.  No message
-passing: the all-entity table of timestamp t is a function of the parameters and t alone,
+"""The embedding-only baselines of the paper's tables, with the reference's interface: `--module Static` (baselines/Static.py),
+`--module DE`, the diachronic embedding (baselines/DiachronicEmbedding.py), and `--module Hyte` (baselines/Hyte.py), all on
+baselines/TKG_Non_Recurrent.py.  No message passing: the all-entity table of timestamp t is a function of the parameters and t alone,
 
     Static               ent_embeds
     DiachronicEmbedding  ent_embeds * [1 (first D // 2 columns) | sin(t * w_temp_ent_embeds + b_temp_ent_embeds)]
+    Hyte                 ent_embeds - n_t (n_t . ent_embeds),  n_t = time_embeddings[t] / |time_embeddings[t]|   (rel_embeds likewise)
 
-so a batch of B timestamps is ONE (B N, D) stack (functional.diachronic_rows: one launch forward, one backward that already sums
-over the timestamps) scored by ONE fused loss node (TKG_Module.batched_link_prediction) -- the loss, the sampler and the filtered
-ranking are the ones the RGCN models use."""
+so a batch of B timestamps is ONE (B N, D) stack (functional.diachronic_rows / hyperplane_rows: one launch forward, a backward that
+already sums over the timestamps) scored by ONE fused loss node (TKG_Module.batched_link_prediction) -- the loss, the sampler and the
+filtered ranking are the ones the RGCN models use.  Hyte's relation rows depend on the timestamp too: its (B 2R, D) relation stack
+is the loss node's relation operand (sampling.plan_batch_loss(rel_stride=2R))."""
 import math
 
 import numpy as np
@@ -33,11 +35,28 @@ class TKG_Non_Recurrent(TKG_Module):
         self.seed_rng = np.random.default_rng(None if getattr(args, "seed", None) is None else int(args.seed) + 1)
         self.use_device_sampler = True
 
+    rel_stride = None           # rows between the windows' relation tables in relation_stack(); None: one table for all windows
+
     def build_model(self):
         pass
 
     def table_stack(self, times):
         raise NotImplementedError
+
+    def relation_stack(self, times):
+        """The (B 2R, D) stack of the timestamps' relation tables, or None when all timestamps share self.rel_embeds."""
+        return None
+
+    def stacks(self, times):
+        """(table_stack, relation_stack) of one batch."""
+        return self.table_stack(times), self.relation_stack(times)
+
+    def _rel_rows(self, rel_stack, b):
+        """The relation table of batch position b."""
+        if rel_stack is None:
+            return self.rel_embeds
+        n = int(self.rel_embeds.shape[0])
+        return rel_stack[b * n:(b + 1) * n]
 
     def _times(self, ts):
         return _lib.to_device(np.asarray(ts, dtype=np.float32), self.ent_embeds.device)
@@ -71,7 +90,8 @@ class TKG_Non_Recurrent(TKG_Module):
         ts = [int(t) for t in t_list]
         ranks, losses = [], []
         with torch.no_grad():
-            stack = self.table_stack(self._times(ts))
+            times = self._times(ts)
+            stack, rel_stack = self.stacks(times)
             for b, t in enumerate(ts):
                 g = graph_dict[t]
                 if g.number_of_edges() == 0:
@@ -80,8 +100,9 @@ class TKG_Non_Recurrent(TKG_Module):
                 ent_embed = all_embeds_g[self._gids(g)]
                 index_sample = torch.from_numpy(np.stack([g.src, g.rel, g.dst], axis=1)).to(dev)
                 label = torch.ones(index_sample.shape[0], device=dev)
-                ranks.append(self.evaluater.calc_metrics_single_graph(ent_embed, self.rel_embeds, all_embeds_g, index_sample, g, t))
-                losses.append(self.link_classification_loss(ent_embed, self.rel_embeds, index_sample, label).item())
+                rel_embed = self._rel_rows(rel_stack, b)
+                ranks.append(self.evaluater.calc_metrics_single_graph(ent_embed, rel_embed, all_embeds_g, index_sample, g, t))
+                losses.append(self.link_classification_loss(ent_embed, rel_embed, index_sample, label).item())
         ranks = torch.cat(ranks) if ranks else torch.zeros(0, dtype=torch.int64, device=dev)
         return ranks, (float(np.mean(losses)) if losses else float("nan"))
 
@@ -100,7 +121,7 @@ class TKG_Non_Recurrent(TKG_Module):
         if store is None or store.device != dev:
             store = self._true_store = TrueSetStore(self.graph_dict_train, N, dev)
         plan = plan_batch_loss(store, ts, g_list, off[:-1], self.args.num_pos_facts, self.sample_rng, B * N, int(self.rel_embeds.shape[0]), dev,
-                               row_map=row_map)
+                               row_map=row_map, rel_stride=self.rel_stride)
         return dict(plan=plan, B=B, times=self._times(ts))
 
     def _fused_loss(self, fp, cand=None):
@@ -111,12 +132,12 @@ class TKG_Non_Recurrent(TKG_Module):
         plan = fp["plan"]
         if plan is None:
             return self.ent_embeds.sum() * 0.0
-        stack = self.table_stack(fp["times"])
+        stack, rel_stack = self.stacks(fp["times"])
         if cand is None:
             cand = get_backend().corrupt_sample(int(self.seed_rng.integers(1 << 62)), plan["truth"], plan["lo"], plan["hi"], plan["ids"],
                                                 self.args.negative_rate, self.num_ents)
         self._last_plan = (plan, cand)
-        return self.batched_link_prediction(stack, dict(plan, cand=cand), stack)
+        return self.batched_link_prediction(stack, dict(plan, cand=cand), stack, rel=rel_stack)
 
     def prepare(self, t_list):
         """-> a prepared batch: graphs, times on the device and -- when a fused loss node takes the scorer -- the loss plan.  A step
@@ -141,7 +162,8 @@ class TKG_Non_Recurrent(TKG_Module):
         g_list = [self.graph_dict_train[t] for t in ts]
         if samples is None and self._fused_loss_ok():
             return self._fused_loss(self._fused_plan(ts, g_list))
-        stack = self.table_stack(self._times(ts))
+        times = self._times(ts)
+        stack, rel_stack = self.stacks(times)
         loss = 0
         for b, (t, g) in enumerate(zip(ts, g_list)):
             if samples is not None:
@@ -153,7 +175,8 @@ class TKG_Non_Recurrent(TKG_Module):
                 continue
             triplets, neg_tail, neg_head, labels = triplets.to(dev), neg_tail.to(dev), neg_head.to(dev), labels.to(dev)
             all_embeds_g = stack[b * N:(b + 1) * N]
-            loss = loss + self.train_link_prediction_both(all_embeds_g[self._gids(g)], triplets, neg_tail, neg_head, labels, all_embeds_g)
+            loss = loss + self.train_link_prediction_both(all_embeds_g[self._gids(g)], triplets, neg_tail, neg_head, labels, all_embeds_g,
+                                                          rel=self._rel_rows(rel_stack, b))
         return loss
 
 
@@ -184,3 +207,71 @@ class DiachronicEmbedding(TKG_Non_Recurrent):
 
     def table_stack(self, times):
         return TF.diachronic_rows(self.ent_embeds, self.w_temp_ent_embeds, self.b_temp_ent_embeds, times)
+
+
+class _TimeRows:
+    """Hyte's `times`: the rows of time_embeddings of a batch on the device (int32 for gather_rows, int64 for plain indexing) and the
+    static inverse that makes the gather's adjoint the deterministic segment sum."""
+
+    def __init__(self, rows, n_rows, device):
+        rows = np.asarray(rows, dtype=np.int32)
+        self.shape = rows.shape
+        self.idx = _lib.to_device(rows, device)
+        self.idx64 = self.idx.long()
+        self.inv = TF.gather_inverse(rows, n_rows, device)
+
+
+class Hyte(TKG_Non_Recurrent):
+    """baselines/Hyte.py: at timestamp t every entity row and every relation row is projected onto the hyperplane whose normal is
+    time_embeddings[t]; the projected rows are scored with TransE.  The time row of timestamp t is its position among the training
+    timestamps (list(graph_dict_train.keys())), which is the reference's time_embeddings[t] wherever its indexing is in range."""
+
+    def __init__(self, args, num_ents, num_rels, graph_dict_train, graph_dict_val, graph_dict_test):
+        args.score_function = 'transE'                              # baselines/Hyte.py:10
+        super().__init__(args, num_ents, num_rels, graph_dict_train, graph_dict_val, graph_dict_test)
+
+    def build_model(self):
+        self.time_embeddings = nn.Parameter(torch.Tensor(len(self.graph_dict_train.keys()), self.embed_size))
+        nn.init.xavier_uniform_(self.time_embeddings, gain=nn.init.calculate_gain('relu'))
+        self._time_row = {int(t): i for i, t in enumerate(self.graph_dict_train.keys())}
+
+    @property
+    def rel_stride(self):
+        return int(self.rel_embeds.shape[0])
+
+    def _times(self, ts):
+        try:
+            rows = [self._time_row[int(t)] for t in ts]
+        except KeyError as e:
+            raise KeyError("Hyte: timestamp %s is not a training timestamp: it has no time row" % e.args[0])
+        return _TimeRows(rows, int(self.time_embeddings.shape[0]), self.ent_embeds.device)
+
+    def time_rows(self, times):
+        """w (B, D) = time_embeddings[rows]: the HIP row gather with its deterministic adjoint where its width limits allow."""
+        D = self.embed_size
+        if D % 4 == 0 and D <= 256:
+            return TF.gather_rows(self.time_embeddings, times.idx, times.inv)
+        return self.time_embeddings[times.idx64]
+
+    def table_stack(self, times):
+        return TF.hyperplane_rows(self.ent_embeds, self.time_rows(times))
+
+    def relation_stack(self, times):
+        return TF.hyperplane_rows(self.rel_embeds, self.time_rows(times))
+
+    def stacks(self, times):
+        """Both projections from ONE gather of the time rows: autograd adds their two d_w before the gather's adjoint."""
+        w = self.time_rows(times)
+        return TF.hyperplane_rows(self.ent_embeds, w), TF.hyperplane_rows(self.rel_embeds, w)
+
+    def relation_table(self, t):
+        return self.relation_stack(self._times([int(t)]))
+
+    def get_per_graph_embeds(self, t, g):
+        """baselines/Hyte.py:18-27 -> (projected rows of the graph's entities, projected relation rows)."""
+        ent, rel = self.stacks(self._times([int(t)]))
+        return ent[self._gids(g)], rel
+
+
+# main.py:42-55: the `--module` names of the embedding-only baselines
+MODULES = {"Static": Static, "DE": DiachronicEmbedding, "Hyte": Hyte}

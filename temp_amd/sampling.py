@@ -166,14 +166,17 @@ class TrueSetStore:
         return s
 
 
-def plan_batch_loss(store, times, graphs, row_offsets, num_pos_facts, rng, n_rows, n_rel_rows, device, row_map=None):
+def plan_batch_loss(store, times, graphs, row_offsets, num_pos_facts, rng, n_rows, n_rel_rows, device, row_map=None, rel_stride=None):
     """Everything of a window batch's link-prediction loss that does not depend on the negative draws, built on the host
     (no device round trip) and uploaded once: per target graph the P = min(E, num_pos_facts) positives (a random subset
     when E is larger, utils/CorrptTriples.py:37-40), stacked as [tail-corruption rows ; head-corruption rows]:
       known / rel / is_tail   operands of the folded query      truth, lo, hi    inputs of temp_corrupt_sample
       weights (1 / P), window (the graph of every row), splits, known_inv / rel_inv (static inverses for the deterministic backward), triples (host, per graph).
     `row_map` (host int array over the rows that `row_offsets` address): the known rows are row_map[known] among `n_rows` rows -- for a
-    model whose target rows are rows of a larger stack (non_recurrent: row b N + global id of the all-entity stack)."""
+    model whose target rows are rows of a larger stack (non_recurrent: row b N + global id of the all-entity stack).
+    `rel_stride`: every window has a relation table of its own, stacked `rel_stride` rows apart (Hyte: the relation rows projected
+    at the window's timestamp) -- the relation row of a query row is window * rel_stride + rel, and rel_inv is built over
+    n_rel_rows = B * rel_stride whatever the caller passed."""
     from . import _hostlib
     from . import functional as TF
     ptrs, idxs = [], []
@@ -188,6 +191,9 @@ def plan_batch_loss(store, times, graphs, row_offsets, num_pos_facts, rng, n_row
         return None
     if row_map is not None:
         packed[0] = np.asarray(row_map)[packed[0]]
+    if rel_stride is not None:
+        packed[1] += np.repeat(np.arange(len(block), dtype=packed.dtype), block) * int(rel_stride)
+        n_rel_rows = len(block) * int(rel_stride)
     _lib.pause_point()
     ends = np.cumsum(block)                                     # a graph's block = 2 P rows (+ weight-0 padding to a multiple of 4)
     splits = [(int(e - k), int(e)) for e, k in zip(ends, block)]

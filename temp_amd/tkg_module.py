@@ -88,16 +88,18 @@ class TKG_Module(nn.Module):
         return ClippedAdam(self.parameters(), lr=self.args.lr, weight_decay=0.0001, max_norm=max_norm)
 
     # -- loss (models/TKG_Module.py:202-221) ----------------------------------------------------------
-    def train_link_prediction(self, ent_embed, triplets, neg_samples, labels, all_embeds_g, corrupt_tail=True):
+    def train_link_prediction(self, ent_embed, triplets, neg_samples, labels, all_embeds_g, corrupt_tail=True, rel=None):
         """models/TKG_Module.py:202-213.  DistMult / ComplEx take the fused path: ONE GEMM of the
         folded query against all entities + a candidate cross-entropy kernel, instead of gathering
         a (P, 1+neg, D) tensor; TransE its L1 candidate kernels (functional.translation_cross_entropy) on a backend that
-        has them; anything else the tensor-algebra path."""
+        has them; anything else the tensor-algebra path.  `rel`: the relation table to use instead of self.rel_embeds (a model
+        whose relation rows depend on the timestamp)."""
         name = self.args.score_function
+        rel_embeds = self.rel_embeds if rel is None else rel
         if self.translation_loss_ok(ent_embed.shape[1]) and triplets.shape[0] > 0:
             from . import functional as TF
             t32 = triplets.to(torch.int32)
-            r = TF.gather_rows(self.rel_embeds, t32[:, 1].contiguous())
+            r = TF.gather_rows(rel_embeds, t32[:, 1].contiguous())
             known = TF.gather_rows(ent_embed, (t32[:, 0] if corrupt_tail else t32[:, 2]).contiguous())
             return TF.translation_cross_entropy(known + r if corrupt_tail else known - r, all_embeds_g, neg_samples.to(torch.int32).contiguous())
         if self.fused_loss and name in ("distmult", "complex") and all_embeds_g.shape[0] % 4 == 0 and triplets.shape[0] > 0:
@@ -105,40 +107,42 @@ class TKG_Module(nn.Module):
             t32 = triplets.to(torch.int32)
             # row gathers through the HIP kernel: its backward is one atomic scatter-add instead of
             # torch's sort-based index_put (the single largest cost of the loss path otherwise)
-            r = TF.gather_rows(self.rel_embeds, t32[:, 1].contiguous())
+            r = TF.gather_rows(rel_embeds, t32[:, 1].contiguous())
             known = TF.gather_rows(ent_embed, (t32[:, 0] if corrupt_tail else t32[:, 2]).contiguous())
             q = scores.bilinear_query(name, known, r, "tail" if corrupt_tail else "head")
             return TF.candidate_cross_entropy(q.contiguous(), all_embeds_g.contiguous(), neg_samples.to(torch.int32).contiguous())
-        r = self.rel_embeds[triplets[:, 1]]
+        r = rel_embeds[triplets[:, 1]]
         if corrupt_tail:
             score = self.calc_score(ent_embed[triplets[:, 0]], r, all_embeds_g[neg_samples], mode='tail')
         else:
             score = self.calc_score(all_embeds_g[neg_samples], r, ent_embed[triplets[:, 2]], mode='head')
         return F.cross_entropy(score, labels)
 
-    def train_link_prediction_both(self, ent_embed, triplets, neg_tail, neg_head, labels, all_embeds_g):
+    def train_link_prediction_both(self, ent_embed, triplets, neg_tail, neg_head, labels, all_embeds_g, rel=None):
         """loss_tail + loss_head of one target graph (models/DynamicRGCN.py:189-192).  On the fused path the
         two directions share the score GEMM against all entities: their queries are stacked into one (2P, D)
-        operand (both halves have P rows, so the sum of the two means is twice the mean over the stack)."""
+        operand (both halves have P rows, so the sum of the two means is twice the mean over the stack).  `rel`: as in
+        train_link_prediction."""
         name = self.args.score_function
+        rel_embeds = self.rel_embeds if rel is None else rel
         P = triplets.shape[0]
         if self.translation_loss_ok(ent_embed.shape[1]) and P > 0:
             from . import functional as TF
             t32 = triplets.to(torch.int32)
-            r = TF.gather_rows(self.rel_embeds, t32[:, 1].contiguous())
+            r = TF.gather_rows(rel_embeds, t32[:, 1].contiguous())
             known = TF.gather_rows(ent_embed, torch.cat([t32[:, 0], t32[:, 2]]).contiguous())
             cand = torch.cat([neg_tail, neg_head], dim=0).to(torch.int32).contiguous()
             return 2.0 * TF.translation_cross_entropy(torch.cat([known[:P] + r, known[P:] - r], dim=0), all_embeds_g, cand)
         if self.fused_loss and name in ("distmult", "complex") and all_embeds_g.shape[0] % 4 == 0 and P > 0:
             from . import functional as TF
             t32 = triplets.to(torch.int32)
-            r = TF.gather_rows(self.rel_embeds, t32[:, 1].contiguous())
+            r = TF.gather_rows(rel_embeds, t32[:, 1].contiguous())
             known = TF.gather_rows(ent_embed, torch.cat([t32[:, 0], t32[:, 2]]).contiguous())
             q = torch.cat([scores.bilinear_query(name, known[:P], r, "tail"), scores.bilinear_query(name, known[P:], r, "head")], dim=0)
             cand = torch.cat([neg_tail, neg_head], dim=0).to(torch.int32).contiguous()
             return 2.0 * TF.candidate_cross_entropy(q.contiguous(), all_embeds_g.contiguous(), cand)
-        return (self.train_link_prediction(ent_embed, triplets, neg_tail, labels, all_embeds_g, corrupt_tail=True)
-                + self.train_link_prediction(ent_embed, triplets, neg_head, labels, all_embeds_g, corrupt_tail=False))
+        return (self.train_link_prediction(ent_embed, triplets, neg_tail, labels, all_embeds_g, corrupt_tail=True, rel=rel)
+                + self.train_link_prediction(ent_embed, triplets, neg_head, labels, all_embeds_g, corrupt_tail=False, rel=rel))
 
     @staticmethod
     def loss_inputs(row_offsets, samples, dev, n_rows=None, n_rel_rows=None, head_as_tail=False):
@@ -216,12 +220,13 @@ class TKG_Module(nn.Module):
         """One of the batched loss nodes of functional.batched_link_prediction applies (D = width of the query rows)."""
         return self.bilinear_loss_ok(D) or self.translation_loss_ok(D)
 
-    def batched_link_prediction(self, ent_rows, inputs, all_embeds):
+    def batched_link_prediction(self, ent_rows, inputs, all_embeds, rel=None):
         """Sum over the target graphs of loss_tail + loss_head (models/DynamicRGCN.py:186-193) as one fused node
         (functional.batched_link_prediction): `ent_rows` is the concatenation of the per-graph target embeddings,
         `inputs` = loss_inputs(..., n_rows, n_rel_rows), `all_embeds` the (B * N_ents, D) stack of the windows' all-entity
         matrices (or a list of B (N_ents, D) matrices).  Returns None when no fused node takes the scorer or the shapes are
-        outside the kernels' alignment (the caller takes the per-graph path)."""
+        outside the kernels' alignment (the caller takes the per-graph path).  `rel`: the relation table that inputs["rel"]
+        indexes, instead of self.rel_embeds (one table per window: sampling.plan_batch_loss(rel_stride=...))."""
         name = self.args.score_function
         D = ent_rows.shape[1]
         if not self.fused_loss_ok(D):
@@ -230,7 +235,7 @@ class TKG_Module(nn.Module):
             return ent_rows.sum() * 0.0
         from . import functional as TF
         big = all_embeds if torch.is_tensor(all_embeds) else torch.cat(list(all_embeds), dim=0)
-        return TF.batched_link_prediction(ent_rows, self.rel_embeds, big.reshape(-1, D).contiguous(), name, inputs)
+        return TF.batched_link_prediction(ent_rows, self.rel_embeds if rel is None else rel, big.reshape(-1, D).contiguous(), name, inputs)
 
     def link_classification_loss(self, ent_embed, rel_embeds, triplets, labels):
         score = self.calc_score(ent_embed[triplets[:, 0]], rel_embeds[triplets[:, 1]], ent_embed[triplets[:, 2]])
@@ -243,6 +248,10 @@ class TKG_Module(nn.Module):
         """Per-family hook of `predict`: yields (t, table [N_ents, D]) for every timestamp of `t_list` -- the all-entity matrix the
         family's evaluate() ranks against."""
         raise NotImplementedError("%s has no single all-entity table per timestamp: predict() is not available" % type(self).__name__)
+
+    def relation_table(self, t):
+        """Per-family hook of `predict`: the relation rows that timestamp t's queries are scored with."""
+        return self.rel_embeds
 
     def predict(self, queries, mode="tail", k=10, filtered=True):
         """The k best answers of every query.  queries: int [Q, 3] rows (timestamp, known GLOBAL entity id, relation row of
@@ -265,7 +274,7 @@ class TKG_Module(nn.Module):
             for a in range(0, len(ts), self.predict_batch):
                 for t, table in self.all_entity_tables(ts[a:a + self.predict_batch]):
                     rows = np.nonzero(q[:, 0] == int(t))[0]
-                    i, v = self.evaluater.topk_single_graph(table, self.rel_embeds, q[rows, 1], q[rows, 2], mode, int(t), k, filtered)
+                    i, v = self.evaluater.topk_single_graph(table, self.relation_table(int(t)), q[rows, 1], q[rows, 2], mode, int(t), k, filtered)
                     sel = torch.from_numpy(rows).to(dev)
                     ids[sel], vals[sel] = i, v
         return ids, vals
