@@ -13,7 +13,6 @@ Two execution paths, same results:
 """
 import numpy as np
 import torch
-import torch.nn as nn
 
 from . import functional as TF
 from . import _lib
@@ -27,8 +26,6 @@ from .gru_cell import GRUCell
 from .window import ChainPlan, Step, concat_steps, concat_steps_dedup, window_times
 
 
-from .backend import get_backend  # noqa: E402
-
 class WindowBatch:
     """Everything `run` needs for one batch of windows (plans, batched graphs, device index tensors)."""
     pass
@@ -40,18 +37,13 @@ class DynamicRGCN(TKG_Module):
         self.train_seq_len = args.train_seq_len
         self.test_seq_len = args.train_seq_len            # --test-seq-len is ignored by the reference too (F10)
         super().__init__(args, num_ents, num_rels, graph_dict_train, graph_dict_val, graph_dict_test, evaluater_type)
-        self.ent_embeds = nn.Parameter(torch.Tensor(self.num_ents, self.embed_size))
-        self.rel_embeds = nn.Parameter(torch.Tensor(self.num_rels * 2, self.embed_size))
         self.edge_dropout = getattr(args, "edge_dropout", False)
         self.post_aggregation = getattr(args, "post_aggregation", False)
         self.random_dropout = getattr(args, "random_dropout", False)
         if self.edge_dropout:
             raise NotImplementedError("--edge-dropout: the reference's DropEdge.sample_subgraph reads drop_rate_cache, which is never built "
                                       "(utils/DropEdge.py:31-32,126); not on the hot path (SURVEY section 2)")
-        nn.init.xavier_uniform_(self.ent_embeds, gain=nn.init.calculate_gain('relu'))
-        nn.init.xavier_uniform_(self.rel_embeds, gain=nn.init.calculate_gain('relu'))
-        self.sample_rng = np.random.default_rng(getattr(args, "seed", None))
-        self.seed_rng = np.random.default_rng(None if getattr(args, "seed", None) is None else int(args.seed) + 1)   # per-step sampler seeds (main thread)
+        self.init_embeddings()
         self.plan_loss_in_prepare = True
         self.use_batched_path = True
         self.use_gru_chain = True
@@ -65,9 +57,6 @@ class DynamicRGCN(TKG_Module):
     # ---------------------------------------------------------------------------------------------
     # shared helpers
     # ---------------------------------------------------------------------------------------------
-    def _device(self):
-        return self.ent_embeds.device
-
     def _dropout_active(self, train=True):
         """The self-loop dropout of the RGCN layers (models/RGCN.py:57-59) draws in this pass: training mode, p > 0."""
         return bool(train and self.training and float(getattr(self.args, "dropout", 0.0) or 0.0) > 0.0)
@@ -391,46 +380,17 @@ class DynamicRGCN(TKG_Module):
         gid = torch.from_numpy(g.gids).to(dev)
         return all_embeds.index_copy(0, gid, convoluted_embeds)
 
-    def all_entity_tables(self, t_list):
-        """TKG_Module.predict's hook: the embedding half of evaluate() -- the window on the full train graphs at test_seq_len, every
-        window's all-entity matrix assembled over the target graph the encoder ran on."""
+    def evaluation_targets(self, t_list):
+        """models/DynamicRGCN.py:118-144,196-220: the window on the full train graphs at test_seq_len; all windows' all-entity
+        matrices in one batched pass when the model allows it (same classes as the training loss), else per window over the graph
+        that is asked for."""
         wb = self.prepare(t_list, self.test_seq_len, train=False)
         out, hist = self.run(wb)
-        per_graph = list(out.split(wb.target.sizes))
         all_b = self.all_embeds_batched(wb, out, hist) if self._fused_all_entity_ok(wb) else None
-        for i, ent_embed in enumerate(per_graph):
+        for i, ent_embed in enumerate(out.split(wb.target.sizes)):
             t = wb.rows[i][-1]
-            yield t, (all_b[i] if all_b is not None else self.get_all_embeds_Gt(ent_embed, wb.graphs[i], t, wb.plan, i, hist))
-
-    def evaluate(self, t_list, val=True):
-        """models/DynamicRGCN.py:118-144,196-220: window encoder on the full train graphs, then filtered
-        ranks of the valid (or test) triples of every target timestamp + their classification loss.
-        (The reference skips graphs without triples WITHOUT advancing its history index; here the index
-        always follows the window.)"""
-        from .evaluation import EvaluationFilter
-        if not hasattr(self, "evaluater"):
-            self.evaluater = EvaluationFilter(self.args, self.calc_score, self.graph_dict_train, self.graph_dict_val, self.graph_dict_test)
-        graph_dict = self.graph_dict_val if val else self.graph_dict_test
-        dev = self._device()
-        with torch.no_grad():
-            wb = self.prepare(t_list, self.test_seq_len, train=False)
-            out, hist = self.run(wb)
-            per_graph, plan, rows = list(out.split(wb.target.sizes)), wb.plan, wb.rows
-            # all windows' all-entity matrices in one batched pass when the model allows it (same classes as the training loss)
-            all_b = self.all_embeds_batched(wb, out, hist) if self._fused_all_entity_ok(wb) else None
-            ranks, losses = [], []
-            for i, ent_embed in enumerate(per_graph):
-                t = rows[i][-1]
-                g = graph_dict[t]
-                if g.number_of_edges() == 0:
-                    continue
-                all_embeds_g = all_b[i] if all_b is not None else self.get_all_embeds_Gt(ent_embed, g, t, plan, i, hist)
-                index_sample = torch.from_numpy(np.stack([g.src, g.rel, g.dst], axis=1)).to(dev)
-                label = torch.ones(index_sample.shape[0], device=dev)
-                ranks.append(self.evaluater.calc_metrics_single_graph(ent_embed, self.rel_embeds, all_embeds_g, index_sample, g, t))
-                losses.append(self.link_classification_loss(ent_embed, self.rel_embeds, index_sample, label))
-        ranks = torch.cat(ranks) if ranks else torch.zeros(0, dtype=torch.int64, device=dev)
-        return ranks, (float(torch.stack(losses).mean().item()) if losses else float("nan"))     # ONE device->host sync per batch
+            yield t, ent_embed, (lambda g, i=i, t=t, ent_embed=ent_embed:
+                                 all_b[i] if all_b is not None else self.get_all_embeds_Gt(ent_embed, g, t, wb.plan, i, hist))
 
     def forward(self, t_list, reverse=False, target_edge_ids=None, samples=None):
         """models/DynamicRGCN.py:176-194.  `target_edge_ids` / `samples` inject the random draws
@@ -446,15 +406,11 @@ class DynamicRGCN(TKG_Module):
         if not (self.plan_loss_in_prepare and getattr(self, "use_device_sampler", True) and self.fused_loss
                 and (name in ("distmult", "complex") or (name == "transE" and TF.translation_supported()))):
             return
-        from .sampling import TrueSetStore, plan_batch_loss
+        from .sampling import plan_batch_loss
         dev = self._device()
-        with _lib.create_lock:
-            store = getattr(self, "_true_store", None)
-            if store is None or store.device != dev:
-                store = self._true_store = TrueSetStore(self.graph_dict_train, self.num_ents, dev)
         sizes = self._target_sizes(wb)
         offs = np.concatenate([[0], np.cumsum(sizes)])[:-1]
-        wb.loss_plan = plan_batch_loss(store, [r[-1] for r in wb.rows], wb.graphs, offs, self.args.num_pos_facts, self.sample_rng,
+        wb.loss_plan = plan_batch_loss(self.true_sets(), [r[-1] for r in wb.rows], wb.graphs, offs, self.args.num_pos_facts, self.sample_rng,
                                        int(sum(sizes)), int(self.rel_embeds.shape[0]), dev)
         _lib.pause_point()
         if self._fused_all_entity_ok(wb):
@@ -465,17 +421,13 @@ class DynamicRGCN(TKG_Module):
 
     def _sampled_loss(self, wb, out, all_embeds):
         """Fused loss on fresh negatives: ONE sampler launch (temp_corrupt_sample) + the fused link-prediction node."""
-        plan = wb.loss_plan
-        cand = get_backend().corrupt_sample(int(self.seed_rng.integers(1 << 62)), plan["truth"], plan["lo"], plan["hi"], plan["ids"],
-                                            self.args.negative_rate, self.num_ents)
-        return self.batched_link_prediction(out, dict(plan, cand=cand), all_embeds)
+        return self.batched_link_prediction(out, dict(wb.loss_plan, cand=self.draw_candidates(wb.loss_plan)), all_embeds)
 
     def _samples_from_plan(self, wb):
         """Reference-shaped samples [(triples, neg_tail, neg_head)] per target graph from the batch's loss plan: the negatives
         of all graphs come from ONE temp_corrupt_sample launch (the per-graph torch-op sampler costs ~1.4 ms per graph)."""
         plan = wb.loss_plan
-        cand = get_backend().corrupt_sample(int(self.seed_rng.integers(1 << 62)), plan["truth"], plan["lo"], plan["hi"], plan["ids"],
-                                            self.args.negative_rate, self.num_ents)
+        cand = self.draw_candidates(plan)
         out = []
         for trip, (a0, _) in zip(plan["triples"], plan["splits"]):
             P = trip.shape[0]
@@ -662,7 +614,6 @@ class DynamicRGCN(TKG_Module):
 
     def run_loss(self, wb, samples=None):
         """Encoder pass + the per-window link-prediction losses (summed, as the reference does)."""
-        dev = self._device()
         out, hist = self.run(wb)
         per_graph = list(out.split(wb.target.sizes))
         batched = self._fused_all_entity_ok(wb)
@@ -677,12 +628,6 @@ class DynamicRGCN(TKG_Module):
             fused = self.batched_link_prediction(out, self.cached_loss_inputs(wb, "_loss_inputs", samples, wb.target.sizes), all_list)
             if fused is not None:
                 return fused
-        loss = 0
-        for i, (g, ent_embed) in enumerate(zip(wb.graphs, per_graph)):
-            t = wb.rows[i][-1]
-            triplets, neg_tail, neg_head = samples[i]
-            triplets, neg_tail, neg_head = triplets.to(dev), neg_tail.to(dev), neg_head.to(dev)
-            labels = torch.zeros(triplets.shape[0], dtype=torch.int64, device=dev)
-            all_embeds_g = all_list[i] if batched else self.get_all_embeds_Gt(ent_embed, g, t, wb.plan, i, hist)
-            loss = loss + self.train_link_prediction_both(ent_embed, triplets, neg_tail, neg_head, labels, all_embeds_g)
-        return loss
+        times = [r[-1] for r in wb.rows]
+        return self.per_graph_loss(times, wb.graphs, samples, per_graph.__getitem__, lambda i: (
+            all_list[i] if batched else self.get_all_embeds_Gt(per_graph[i], wb.graphs[i], times[i], wb.plan, i, hist)))

@@ -27,12 +27,7 @@ class TKG_Non_Recurrent(TKG_Module):
 
     def __init__(self, args, num_ents, num_rels, graph_dict_train, graph_dict_val, graph_dict_test):
         super().__init__(args, num_ents, num_rels, graph_dict_train, graph_dict_val, graph_dict_test)
-        self.ent_embeds = nn.Parameter(torch.Tensor(self.num_ents, self.embed_size))
-        self.rel_embeds = nn.Parameter(torch.Tensor(self.num_rels * 2, self.embed_size))
-        nn.init.xavier_uniform_(self.ent_embeds, gain=nn.init.calculate_gain('relu'))
-        nn.init.xavier_uniform_(self.rel_embeds, gain=nn.init.calculate_gain('relu'))
-        self.sample_rng = np.random.default_rng(getattr(args, "seed", None))
-        self.seed_rng = np.random.default_rng(None if getattr(args, "seed", None) is None else int(args.seed) + 1)
+        self.init_embeddings()
         self.use_device_sampler = True
 
     rel_stride = None           # rows between the windows' relation tables in relation_stack(); None: one table for all windows
@@ -59,10 +54,10 @@ class TKG_Non_Recurrent(TKG_Module):
         return rel_stack[b * n:(b + 1) * n]
 
     def _times(self, ts):
-        return _lib.to_device(np.asarray(ts, dtype=np.float32), self.ent_embeds.device)
+        return _lib.to_device(np.asarray(ts, dtype=np.float32), self._device())
 
     def _gids(self, g):
-        return torch.from_numpy(g.gids).to(self.ent_embeds.device)
+        return torch.from_numpy(g.gids).to(self._device())
 
     def get_all_embeds_Gt(self, t):
         return self.table_stack(self._times([int(t)]))
@@ -71,40 +66,17 @@ class TKG_Non_Recurrent(TKG_Module):
         """The rows of the graph's entities (the reference gathers the parameters and applies the same element-wise map)."""
         return self.get_all_embeds_Gt(t)[self._gids(g)]
 
-    def all_entity_tables(self, t_list):
-        """TKG_Module.predict's hook: all tables from one table_stack call."""
-        ts, N = [int(t) for t in t_list], self.num_ents
-        stack = self.table_stack(self._times(ts))
-        for b, t in enumerate(ts):
-            yield t, stack[b * N:(b + 1) * N]
-
     # -- evaluation (models/TKG_Module.py:253-274) ---------------------------------------------------------------------------
-    def evaluate(self, t_list, val=True):
-        """Filtered ranks of the valid / test triples + the mean classification loss; all B tables from one table_stack call,
-        empty graphs skipped."""
-        from .evaluation import EvaluationFilter
-        if not hasattr(self, "evaluater"):
-            self.evaluater = EvaluationFilter(self.args, self.calc_score, self.graph_dict_train, self.graph_dict_val, self.graph_dict_test)
-        graph_dict = self.graph_dict_val if val else self.graph_dict_test
-        dev, N = self.ent_embeds.device, self.num_ents
-        ts = [int(t) for t in t_list]
-        ranks, losses = [], []
-        with torch.no_grad():
-            times = self._times(ts)
-            stack, rel_stack = self.stacks(times)
-            for b, t in enumerate(ts):
-                g = graph_dict[t]
-                if g.number_of_edges() == 0:
-                    continue
-                all_embeds_g = stack[b * N:(b + 1) * N]
-                ent_embed = all_embeds_g[self._gids(g)]
-                index_sample = torch.from_numpy(np.stack([g.src, g.rel, g.dst], axis=1)).to(dev)
-                label = torch.ones(index_sample.shape[0], device=dev)
-                rel_embed = self._rel_rows(rel_stack, b)
-                ranks.append(self.evaluater.calc_metrics_single_graph(ent_embed, rel_embed, all_embeds_g, index_sample, g, t))
-                losses.append(self.link_classification_loss(ent_embed, rel_embed, index_sample, label).item())
-        ranks = torch.cat(ranks) if ranks else torch.zeros(0, dtype=torch.int64, device=dev)
-        return ranks, (float(np.mean(losses)) if losses else float("nan"))
+    def evaluation_targets(self, t_list):
+        """All B tables (and relation tables) from one stacks() call.  A graph's own rows are rows of its table, so what
+        _graph_metrics takes from here is the batch position's relation table."""
+        ts, N = [int(t) for t in t_list], self.num_ents
+        stack, rel_stack = self.stacks(self._times(ts))
+        for b, t in enumerate(ts):
+            yield t, self._rel_rows(rel_stack, b), lambda g, b=b: stack[b * N:(b + 1) * N]
+
+    def _graph_metrics(self, rel_embed, all_embeds_g, index_sample, g, t):
+        return super()._graph_metrics(all_embeds_g[self._gids(g)], all_embeds_g, index_sample, g, t, rel=rel_embed)
 
     # -- the fused batch loss ------------------------------------------------------------------------------------------------
     def _fused_loss_ok(self):
@@ -113,14 +85,11 @@ class TKG_Non_Recurrent(TKG_Module):
     def _fused_plan(self, ts, g_list):
         """Host half of the fused loss of a batch, uploaded once: the times, the positives / operand indices / known-true slices
         (sampling.plan_batch_loss).  The known rows point INTO the table stack: local id i of graph b -> row b N + gids_b[i]."""
-        from .sampling import TrueSetStore, plan_batch_loss
-        dev, N, B = self.ent_embeds.device, self.num_ents, len(g_list)
+        from .sampling import plan_batch_loss
+        dev, N, B = self._device(), self.num_ents, len(g_list)
         off = np.concatenate([[0], np.cumsum([g.n for g in g_list])])
         row_map = np.concatenate([b * N + g.gids.astype(np.int64) for b, g in enumerate(g_list)]) if B else np.zeros(0, np.int64)
-        store = getattr(self, "_true_store", None)
-        if store is None or store.device != dev:
-            store = self._true_store = TrueSetStore(self.graph_dict_train, N, dev)
-        plan = plan_batch_loss(store, ts, g_list, off[:-1], self.args.num_pos_facts, self.sample_rng, B * N, int(self.rel_embeds.shape[0]), dev,
+        plan = plan_batch_loss(self.true_sets(), ts, g_list, off[:-1], self.args.num_pos_facts, self.sample_rng, B * N, int(self.rel_embeds.shape[0]), dev,
                                row_map=row_map, rel_stride=self.rel_stride)
         return dict(plan=plan, B=B, times=self._times(ts))
 
@@ -128,14 +97,11 @@ class TKG_Non_Recurrent(TKG_Module):
         """sum_b loss_tail + loss_head as one table_stack node and one batched_link_prediction node: the stack is both the
         all-entity operand and the source of the known rows, so its gradient arrives once; the negatives of all graphs come from
         one launch (`cand`: a fixed draw to reuse, else a fresh one per call)."""
-        from .backend import get_backend
         plan = fp["plan"]
         if plan is None:
             return self.ent_embeds.sum() * 0.0
         stack, rel_stack = self.stacks(fp["times"])
-        if cand is None:
-            cand = get_backend().corrupt_sample(int(self.seed_rng.integers(1 << 62)), plan["truth"], plan["lo"], plan["hi"], plan["ids"],
-                                                self.args.negative_rate, self.num_ents)
+        cand = self.draw_candidates(plan, cand)
         self._last_plan = (plan, cand)
         return self.batched_link_prediction(stack, dict(plan, cand=cand), stack, rel=rel_stack)
 
@@ -157,27 +123,14 @@ class TKG_Non_Recurrent(TKG_Module):
     def forward(self, t_list, samples=None):
         """baselines/TKG_Non_Recurrent.py:21-32.  samples: per graph (triplets, neg_tail, neg_head) to use instead of a draw; they,
         or a scorer / width without a fused node, take the reference-granular loop -- over slices of the same one table stack."""
-        dev, N = self.ent_embeds.device, self.num_ents
-        ts = [int(t) for t in t_list]
+        ts, N = [int(t) for t in t_list], self.num_ents
         g_list = [self.graph_dict_train[t] for t in ts]
         if samples is None and self._fused_loss_ok():
             return self._fused_loss(self._fused_plan(ts, g_list))
-        times = self._times(ts)
-        stack, rel_stack = self.stacks(times)
-        loss = 0
-        for b, (t, g) in enumerate(zip(ts, g_list)):
-            if samples is not None:
-                triplets, neg_tail, neg_head = samples[b]
-                labels = torch.zeros(triplets.shape[0], dtype=torch.int64)
-            else:
-                triplets, neg_tail, neg_head, labels = self.corrupter.single_graph_negative_sampling(t, g, N)
-            if triplets.shape[0] == 0:
-                continue
-            triplets, neg_tail, neg_head, labels = triplets.to(dev), neg_tail.to(dev), neg_head.to(dev), labels.to(dev)
-            all_embeds_g = stack[b * N:(b + 1) * N]
-            loss = loss + self.train_link_prediction_both(all_embeds_g[self._gids(g)], triplets, neg_tail, neg_head, labels, all_embeds_g,
-                                                          rel=self._rel_rows(rel_stack, b))
-        return loss
+        stack, rel_stack = self.stacks(self._times(ts))
+        tables = [stack[b * N:(b + 1) * N] for b in range(len(ts))]
+        return self.per_graph_loss(ts, g_list, samples, lambda b: tables[b][self._gids(g_list[b])], tables.__getitem__,
+                                   rel=lambda b: self._rel_rows(rel_stack, b))
 
 
 class Static(TKG_Non_Recurrent):
@@ -244,7 +197,7 @@ class Hyte(TKG_Non_Recurrent):
             rows = [self._time_row[int(t)] for t in ts]
         except KeyError as e:
             raise KeyError("Hyte: timestamp %s is not a training timestamp: it has no time row" % e.args[0])
-        return _TimeRows(rows, int(self.time_embeddings.shape[0]), self.ent_embeds.device)
+        return _TimeRows(rows, int(self.time_embeddings.shape[0]), self._device())
 
     def time_rows(self, times):
         """w (B, D) = time_embeddings[rows]: the HIP row gather with its deterministic adjoint where its width limits allow."""

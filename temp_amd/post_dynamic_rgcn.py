@@ -70,7 +70,7 @@ def _rows_or_zero(rows, idx_t, n, d, like):
 
 class _PostWindowMixin(_FrequencyGateMixin):
     """What the uni- and bidirectional post models share: slicing the local stream out of a batched run, the impute models' loss,
-    all-entity pass and evaluate(), and the score-level ensemble loss.  A direction is one ChainPlan: the bidirectional classes
+    all-entity pass and evaluation_targets(), and the score-level ensemble loss.  A direction is one ChainPlan: the bidirectional classes
     carry a pair of everything that is per plan (wb.plan, the histories, wb.hist_loc)."""
 
     _window_base = None                   # DynamicRGCN | BiDynamicRGCN: the window model whose batched all-entity pass applies
@@ -136,19 +136,13 @@ class _PostWindowMixin(_FrequencyGateMixin):
     def run_loss(self, wb, samples=None):
         """ImputeDynamicRGCN.forward, models/PostDynamicRGCN.py:80-96; ImputeBiDynamicRGCN.forward,
         models/PostBiDynamicRGCN.py:103-124."""
-        dev = self._device()
         out, hist = self.run(wb)
         per_graph = list(out.split(wb.target.sizes))
         if samples is None:
             samples = self.draw_samples(wb)
-        loss = 0
-        for i, (g, ent_embed) in enumerate(zip(wb.graphs, per_graph)):
-            t = wb.rows[i][-1]
-            triplets, neg_tail, neg_head = (x.to(dev) for x in samples[i])
-            labels = torch.zeros(triplets.shape[0], dtype=torch.int64, device=dev)
-            all_embeds_g = self.get_all_embeds_Gt(ent_embed, g, t, wb.plan, i, hist, wb.hist_loc)
-            loss = loss + self.train_link_prediction_both(ent_embed, triplets, neg_tail, neg_head, labels, all_embeds_g)
-        return loss
+        times = [r[-1] for r in wb.rows]
+        return self.per_graph_loss(times, wb.graphs, samples, per_graph.__getitem__, lambda i: (
+            self.get_all_embeds_Gt(per_graph[i], wb.graphs[i], times[i], wb.plan, i, hist, wb.hist_loc)))
 
     def encode_post(self, t_list, seq_len, train=True, target_edge_ids=None):
         """-> (per-window local embeddings, per-window temporal embeddings, prepared batch, final histories)."""
@@ -156,43 +150,24 @@ class _PostWindowMixin(_FrequencyGateMixin):
         out, hist = self.run(wb)
         return list(wb.out_loc.split(wb.target.sizes)), list(out.split(wb.target.sizes)), wb, hist
 
-    def evaluate(self, t_list, val=True):
-        """The window loop with the local history stream on the full train graphs, the all-entity matrices of every target
-        timestamp that has valid (or test) triples, then the family's filtered ranks (_graph_metrics):
+    def evaluation_targets(self, t_list):
+        """The window loop with the local history stream on the full train graphs at test_seq_len; per target timestamp the
+        temporal rows (impute) or the (local, temporal) rows (_two_stream), and get_all_embeds_Gt over the graph that is asked
+        for.  What ranks them is the family's _graph_metrics:
           impute         ImputeDynamicRGCN.evaluate / calc_metrics, models/PostDynamicRGCN.py:101-143 (bidirectional:
-                         models/PostBiDynamicRGCN.py:126-176)
+                         models/PostBiDynamicRGCN.py:126-176): the IMPUTED all-entity matrix under the standard filter
           post-ensemble  PostEnsemble(Bi)DynamicRGCN.evaluate / calc_metrics, models/PostDynamicRGCN.py:367-423,
                          models/PostBiDynamicRGCN.py:297-360
           post-aggregation  Post(Bi)DynamicRGCN.evaluate / calc_metrics, models/PostDynamicRGCN.py:224-259,
                          models/PostBiDynamicRGCN.py:244-282
         As in the reference only the impute models compute a classification loss (nan otherwise)."""
-        self._ranker()
-        graph_dict = self.graph_dict_val if val else self.graph_dict_test
-        dev = self._device()
-        with torch.no_grad():
-            wb = self.prepare(t_list, self.test_seq_len, train=False)
-            out, hist = self.run(wb)
-            ranks, losses = [], []
-            for i, (loc, rec) in enumerate(zip(wb.out_loc.split(wb.target.sizes), out.split(wb.target.sizes))):
-                t = wb.rows[i][-1]
-                g = graph_dict[t]
-                if g.number_of_edges() == 0:
-                    continue
-                alls = self.get_all_embeds_Gt(*((loc, rec) if self._two_stream else (rec,)), g, t, wb.plan, i, hist, wb.hist_loc)
-                index_sample = torch.from_numpy(np.stack([g.src, g.rel, g.dst], axis=1)).to(dev)
-                r, loss = self._graph_metrics(loc, rec, alls, index_sample, g, t)
-                ranks.append(r)
-                if loss is not None:
-                    losses.append(loss)
-        ranks = torch.cat(ranks) if ranks else torch.zeros(0, dtype=torch.int64, device=dev)
-        return ranks, (float(torch.stack(losses).mean().item()) if losses else float("nan"))
-
-    def _graph_metrics(self, loc, rec, all_embeds_g, index_sample, g, t):
-        """-> (ranks, classification loss | None) of one target graph: the IMPUTED all-entity matrix, the standard filtered ranks
-        (temp_amd.evaluation.EvaluationFilter) and the classification loss of the valid (or test) triples."""
-        label = torch.ones(index_sample.shape[0], device=index_sample.device)
-        return (self.evaluater.calc_metrics_single_graph(rec, self.rel_embeds, all_embeds_g, index_sample, g, t),
-                self.link_classification_loss(rec, self.rel_embeds, index_sample, label))
+        wb = self.prepare(t_list, self.test_seq_len, train=False)
+        out, hist = self.run(wb)
+        for i, (loc, rec) in enumerate(zip(wb.out_loc.split(wb.target.sizes), out.split(wb.target.sizes))):
+            t = wb.rows[i][-1]
+            own = (loc, rec) if self._two_stream else (rec,)
+            yield t, (own if self._two_stream else rec), (lambda g, i=i, t=t, own=own:
+                                                          self.get_all_embeds_Gt(*own, g, t, wb.plan, i, hist, wb.hist_loc))
 
     # Reference quirk kept for parity (pinned by golden G19_post_ratio_bi): PostEnsembleBiDynamicRGCN.train_link_prediction forwards
     # to the uni-directional class with `corrupt_tail=True` hard-coded (models/PostBiDynamicRGCN.py:294-295), so its "head" scores
@@ -395,16 +370,6 @@ class _TwoStreamMixin:
         gid = _gids_dev(g, self._device())
         return a_loc.index_copy(0, gid, convoluted_loc), a_rec.index_copy(0, gid, convoluted_rec)
 
-    def all_entity_table_pairs(self, t_list):
-        """predict_gated's hook (post_gates._FrequencyGateMixin): the embedding half of evaluate() -- the window with the local
-        history stream on the full train graphs at test_seq_len, then every window's (all_loc, all_rec) assembled over the target
-        graph the encoder ran on, as DynamicRGCN.all_entity_tables does for one table."""
-        wb = self.prepare(t_list, self.test_seq_len, train=False)
-        out, hist = self.run(wb)
-        for i, (loc, rec) in enumerate(zip(wb.out_loc.split(wb.target.sizes), out.split(wb.target.sizes))):
-            t = wb.rows[i][-1]
-            yield (t,) + tuple(self.get_all_embeds_Gt(loc, rec, wb.graphs[i], t, wb.plan, i, hist, wb.hist_loc))
-
     def run_loss(self, wb, samples=None, weights=None):
         """PostEnsembleDynamicRGCN.forward, models/PostDynamicRGCN.py:375-397; PostEnsembleBiDynamicRGCN.forward,
         models/PostBiDynamicRGCN.py:329-354; Post(Bi)DynamicRGCN.forward, models/PostDynamicRGCN.py:189-208 /
@@ -465,9 +430,10 @@ class _PostEnsembleMixin(_TwoStreamMixin):
             loss = loss + self.ensemble_loss(locs[i], recs[i], a_loc, a_rec, triplets, neg_tail, neg_head, ws.to(dev), wo.to(dev))
         return loss
 
-    def _graph_metrics(self, loc, rec, alls, index_sample, g, t):
+    def _graph_metrics(self, rows, alls, index_sample, g, t):
         """Score-level ensemble ranks (PostEnsembleEvaluationFilter) of the (local, temporal) all-entity matrices.  The mixing
         weights come from calc_ensemble_ratio(index_sample, t, g) (frequency MLPs).  As in the reference no classification loss."""
+        loc, rec = rows
         w_subject, w_object = self.calc_ensemble_ratio(index_sample, t, g)
         return self.evaluater.calc_metrics_single_graph(loc, rec, self.rel_embeds, alls[0], alls[1], w_subject, w_object,
                                                         index_sample, g, t), None

@@ -12,18 +12,8 @@ from . import functional as TF
 
 
 class _FrequencyGateMixin:
-    """Per-timestamp frequency features of a triple (temp_amd/frequency.py), the choice of the class that ranks for evaluate(),
-    and the stacking of per-window all-entity matrices for a fused loss node."""
-
-    _evaluater = "EvaluationFilter"       # the class of temp_amd.evaluation that ranks for evaluate()
-
-    def _ranker(self):
-        """The model's evaluation filter (`_evaluater`), built on first use."""
-        from . import evaluation
-        cls = getattr(evaluation, self._evaluater)
-        if not isinstance(getattr(self, "evaluater", None), cls):
-            self.evaluater = cls(self.args, self.calc_score, self.graph_dict_train, self.graph_dict_val, self.graph_dict_test)
-        return self.evaluater
+    """Per-timestamp frequency features of a triple (temp_amd/frequency.py), prediction through the gates, and the stacking of
+    per-window all-entity matrices for a fused loss node."""
 
     def all_entity_tables(self, t_list):
         raise NotImplementedError("%s scores against two all-entity tables (local, temporal) mixed by per-triple gates: predict() covers the "
@@ -33,10 +23,13 @@ class _FrequencyGateMixin:
     _gate_count = 0                       # weights a query carries: 1 (score-level ensemble), 2 (embedding-level gate: known, candidates)
 
     def all_entity_table_pairs(self, t_list):
-        """Per-family hook of `predict_gated`: yields (t, all_loc [N_ents, D], all_rec [N_ents, D]) for every timestamp of `t_list`
-        -- the embedding half of the family's evaluate(): the window at test_seq_len on the full train graphs (train=False) and the
-        two all-entity matrices over the target graph the encoder ran on."""
-        raise NotImplementedError("%s has one all-entity table and no gates: predict_gated() covers the two-table post models" % type(self).__name__)
+        """What `predict_gated` selects from: yields (t, all_loc [N_ents, D], all_rec [N_ents, D]) for every timestamp of `t_list`
+        -- the two all-entity matrices the family's evaluate() ranks against (evaluation_targets), assembled over the train graph
+        the encoder ran on."""
+        if not self._gate_count:
+            raise NotImplementedError("%s has one all-entity table and no gates: predict_gated() covers the two-table post models" % type(self).__name__)
+        for t, _, all_embeds in self.evaluation_targets(t_list):
+            yield (t,) + tuple(all_embeds(self.graph_dict_train[t]))
 
     def query_features(self, t, known, rel, mode):
         """Frequency features of the KNOWN side of queries at timestamp t (global ids), all a query has -> (Q, 3) on the device.
@@ -57,10 +50,7 @@ class _FrequencyGateMixin:
         injected weights, the counterpart of forward(..., ensemble_weights= / gate_weights=): a [Q] tensor for the score-level
         ensemble, a pair (w_known [Q], w_cand [Q]) for the embedding-level gate.  The scorer is evaluate()'s (the real head / tail
         mode; head_scored_as_tail is a quirk of the training loss alone).  Adds no parameters or buffers."""
-        if mode not in ("head", "tail"):
-            raise ValueError("predict_gated: mode must be 'head' or 'tail'")
-        q = queries.detach().cpu().numpy() if torch.is_tensor(queries) else np.asarray(queries)
-        q = q.astype(np.int64).reshape(-1, 3)
+        q = self.query_rows("predict_gated", queries, mode)
         dev = self._device()
         if weights is not None:
             weights = (weights,) if torch.is_tensor(weights) else tuple(weights)
@@ -68,18 +58,11 @@ class _FrequencyGateMixin:
                 raise ValueError("predict_gated: weights must be %s" % ("a [Q] tensor" if self._gate_count == 1 else "a pair (w_known [Q], w_cand [Q])"))
             weights = tuple(w.detach().to(dev, torch.float32).reshape(-1) for w in weights)
         ranker = self._ranker()
-        ids = torch.full((q.shape[0], k), -1, dtype=torch.int64, device=dev)
-        vals = torch.full((q.shape[0], k), float("-inf"), dtype=torch.float32, device=dev)
-        ts = sorted(set(int(t) for t in q[:, 0]))
-        with torch.no_grad():
-            for a in range(0, len(ts), self.predict_batch):
-                for t, all_loc, all_rec in self.all_entity_table_pairs(ts[a:a + self.predict_batch]):
-                    rows = np.nonzero(q[:, 0] == int(t))[0]
-                    sel = torch.from_numpy(rows).to(dev)
-                    gates = self._query_gates(int(t), q[rows, 1], q[rows, 2], mode) if weights is None else tuple(w[sel] for w in weights)
-                    i, v = ranker.topk_single_graph(all_loc, all_rec, self.rel_embeds, q[rows, 1], q[rows, 2], *gates, mode, int(t), k, filtered)
-                    ids[sel], vals[sel] = i, v
-        return ids, vals
+
+        def select(t, tables, known, rel, sel):
+            gates = self._query_gates(t, known, rel, mode) if weights is None else tuple(w[sel] for w in weights)
+            return ranker.topk_single_graph(*tables, self.rel_embeds, known, rel, *gates, mode, t, k, filtered)
+        return self.select_per_timestamp(q, k, self.all_entity_table_pairs, select)
 
     def frequency_tables(self):
         ft = getattr(self, "_freq_tables", None)
@@ -245,9 +228,10 @@ class _GatedLossMixin(_FrequencyGateMixin):
             loss = loss + self.gated_loss(locs[i], recs[i], a_loc, a_rec, triplets, neg_tail, neg_head, *gw)
         return loss
 
-    def _graph_metrics(self, loc, rec, alls, index_sample, g, t):
+    def _graph_metrics(self, rows, alls, index_sample, g, t):
         """Embedding-level gated ranks (PostEvaluationFilter, which mixes the known object of the head rows with its own local
         row) of the (local, temporal) all-entity matrices.  No classification loss."""
+        loc, rec = rows
         w_sqs, w_sqo, w_oqs, w_oqo = self.calc_ensemble_ratio(index_sample, t, g)
         return self.evaluater.calc_metrics_single_graph(loc, rec, self.rel_embeds, alls[0], alls[1], index_sample,
                                                         w_sqs, w_sqo, w_oqs, w_oqo, g, t), None

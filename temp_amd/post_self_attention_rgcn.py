@@ -24,7 +24,6 @@ product sees N_ents + B rows instead of B * N_inactive, and the (B * N_inactive,
 Refused at construction: rec_only_last_layer = False (the reference cannot run it: forward_isolated_post_ensemble calls
 layer_1.forward_isolated(ent_embeds, time) on a SARGCNLayer, a TypeError, models/SARGCN.py:143-146) and --EMA."""
 import numpy as np
-import torch
 
 from . import _lib
 from . import functional as TF
@@ -121,37 +120,16 @@ class PostSelfAttentionRGCN(_GatedLossMixin, SelfAttentionRGCN):
         wb = self.prepare(t_list, self.train_seq_len, True, target_edge_ids)
         return self.run_loss(wb, samples, gate_weights)
 
-    def all_entity_table_pairs(self, t_list):
-        """predict_gated's hook (post_gates._FrequencyGateMixin): the embedding half of evaluate() -- the encoder on the full train
-        graphs at test_seq_len, then both all-entity matrices of every window."""
+    # -- evaluate ------------------------------------------------------------------------------------------------------------
+    def evaluation_targets(self, t_list):
+        """models/PostSelfAttentionRGCN.py:96-123 (Bi: :189-208): the encoder on the full train graphs at test_seq_len, both
+        all-entity matrices of every window from the one batched pass; the embedding-level gated ranks are _graph_metrics (no
+        classification loss, as in the reference)."""
         wb = self.prepare(t_list, self.test_seq_len, train=False)
         (loc, rec), kv2 = self.run(wb)
         all_loc, all_rec = self.all_embeds_post(wb, loc, rec, kv2)
-        for i in range(len(wb.graphs)):
-            yield wb.rows[i][-1], all_loc[i], all_rec[i]
-
-    # -- evaluate ------------------------------------------------------------------------------------------------------------
-    def evaluate(self, t_list, val=True):
-        """models/PostSelfAttentionRGCN.py:96-123 (Bi: :189-208): the encoder on the full train graphs, both all-entity matrices,
-        then the embedding-level gated ranks of the valid (or test) triples (_graph_metrics).  No classification loss, as in the
-        reference (nan).  (The history index always follows the window; cf. DynamicRGCN.evaluate.)"""
-        self._ranker()
-        graph_dict = self.graph_dict_val if val else self.graph_dict_test
-        dev = self._device()
-        with torch.no_grad():
-            wb = self.prepare(t_list, self.test_seq_len, train=False)
-            (loc, rec), kv2 = self.run(wb)
-            all_loc, all_rec = self.all_embeds_post(wb, loc, rec, kv2)
-            ranks = []
-            for i, (lo, re) in enumerate(zip(loc.split(wb.target_sizes), rec.split(wb.target_sizes))):
-                t = wb.rows[i][-1]
-                g = graph_dict[t]
-                if g.number_of_edges() == 0:
-                    continue
-                index_sample = torch.from_numpy(np.stack([g.src, g.rel, g.dst], axis=1)).to(dev)
-                ranks.append(self._graph_metrics(lo, re, (all_loc[i], all_rec[i]), index_sample, g, t)[0])
-        ranks = torch.cat(ranks) if ranks else torch.zeros(0, dtype=torch.int64, device=dev)
-        return ranks, float("nan")
+        for i, rows in enumerate(zip(loc.split(wb.target_sizes), rec.split(wb.target_sizes))):
+            yield wb.rows[i][-1], rows, lambda g, i=i: (all_loc[i], all_rec[i])
 
 
 class PostBiSelfAttentionRGCN(PostSelfAttentionRGCN):

@@ -205,7 +205,6 @@ class SelfAttentionRGCN(DynamicRGCN):
         return list(out.split(wb.target_sizes)), wb, tables
 
     def run_loss(self, wb, samples=None):
-        dev = self._device()
         out, tables = self.run(wb)
         per_graph = list(out.split(wb.target_sizes))
         all_list = self.all_embeds_batched(wb, out, tables)
@@ -218,42 +217,15 @@ class SelfAttentionRGCN(DynamicRGCN):
         fused = self.batched_link_prediction(out, self.cached_loss_inputs(wb, "_loss_inputs", samples, wb.target_sizes), all_list)
         if fused is not None:
             return fused
-        loss = 0
-        for i, ent_embed in enumerate(per_graph):
-            triplets, neg_tail, neg_head = (x.to(dev) for x in samples[i])
-            labels = torch.zeros(triplets.shape[0], dtype=torch.int64, device=dev)
-            loss = loss + self.train_link_prediction_both(ent_embed, triplets, neg_tail, neg_head, labels, all_list[i])
-        return loss
+        return self.per_graph_loss(wb.target_times, wb.graphs, samples, per_graph.__getitem__, all_list.__getitem__)
 
-    def all_entity_tables(self, t_list):
-        """TKG_Module.predict's hook: the embedding half of evaluate()."""
+    def evaluation_targets(self, t_list):
+        """models/SelfAttentionRGCN.py:142-180 (Bi: models/BiSelfAttentionRGCN.py:71-95): the encoder on the full train graphs at
+        test_seq_len, every window's all-entity matrix from the one batched pass."""
         per_graph, wb, tables = self.encode(t_list, self.test_seq_len, train=False)
         all_list = self.all_embeds_batched(wb, torch.cat(per_graph, dim=0), tables)
-        for i in range(len(per_graph)):
-            yield wb.rows[i][-1], all_list[i]
-
-    def evaluate(self, t_list, val=True):
-        """models/SelfAttentionRGCN.py:142-180 (Bi: models/BiSelfAttentionRGCN.py:71-95)."""
-        from .evaluation import EvaluationFilter
-        if not hasattr(self, "evaluater"):
-            self.evaluater = EvaluationFilter(self.args, self.calc_score, self.graph_dict_train, self.graph_dict_val, self.graph_dict_test)
-        graph_dict = self.graph_dict_val if val else self.graph_dict_test
-        dev = self._device()
-        with torch.no_grad():
-            per_graph, wb, tables = self.encode(t_list, self.test_seq_len, train=False)
-            all_list = self.all_embeds_batched(wb, torch.cat(per_graph, dim=0), tables)
-            ranks, losses = [], []
-            for i, ent_embed in enumerate(per_graph):
-                t = wb.rows[i][-1]
-                g = graph_dict[t]
-                if g.number_of_edges() == 0:
-                    continue
-                index_sample = torch.from_numpy(np.stack([g.src, g.rel, g.dst], axis=1)).to(dev)
-                label = torch.ones(index_sample.shape[0], device=dev)
-                ranks.append(self.evaluater.calc_metrics_single_graph(ent_embed, self.rel_embeds, all_list[i], index_sample, g, t))
-                losses.append(self.link_classification_loss(ent_embed, self.rel_embeds, index_sample, label).item())
-        ranks = torch.cat(ranks) if ranks else torch.zeros(0, dtype=torch.int64, device=dev)
-        return ranks, (float(np.mean(losses)) if losses else float("nan"))
+        for i, ent_embed in enumerate(per_graph):
+            yield wb.rows[i][-1], ent_embed, lambda g, i=i: all_list[i]
 
 
 class BiSelfAttentionRGCN(SelfAttentionRGCN):

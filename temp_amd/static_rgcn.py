@@ -3,7 +3,6 @@
 50 % edge subsample of each target snapshot, no history."""
 import numpy as np
 import torch
-import torch.nn as nn
 
 from . import _hostlib
 from . import _lib
@@ -16,12 +15,7 @@ from .tkg_module import TKG_Module
 class StaticRGCN(TKG_Module):
     def __init__(self, args, num_ents, num_rels, graph_dict_train, graph_dict_val, graph_dict_test, evaluater_type=None):
         super().__init__(args, num_ents, num_rels, graph_dict_train, graph_dict_val, graph_dict_test, evaluater_type)
-        self.ent_embeds = nn.Parameter(torch.Tensor(self.num_ents, self.embed_size))
-        self.rel_embeds = nn.Parameter(torch.Tensor(self.num_rels * 2, self.embed_size))
-        nn.init.xavier_uniform_(self.ent_embeds, gain=nn.init.calculate_gain('relu'))
-        nn.init.xavier_uniform_(self.rel_embeds, gain=nn.init.calculate_gain('relu'))
-        self.sample_rng = np.random.default_rng(getattr(args, "seed", None))
-        self.seed_rng = np.random.default_rng(None if getattr(args, "seed", None) is None else int(args.seed) + 1)
+        self.init_embeddings()
         self.use_device_sampler = True
 
     def build_model(self):
@@ -57,36 +51,12 @@ class StaticRGCN(TKG_Module):
         gid = torch.from_numpy(g.gids).to(self.ent_embeds.device)
         return all_embeds.index_copy(0, gid, convoluted_embeds)
 
-    def all_entity_tables(self, t_list):
-        """TKG_Module.predict's hook: the embedding half of evaluate() -- the full train graphs' rows over the isolated pass."""
+    def evaluation_targets(self, t_list):
+        """baselines/StaticRGCN.py:20-34,91-113: the full train graphs' rows; the isolated pass over the graph that is asked for."""
         ts = [int(t) for t in t_list]
-        g_list = [self.graph_dict_train[t] for t in ts]
-        for t, g, ent_embed in zip(ts, g_list, self.get_per_graph_ent_embeds(ts, g_list, val=True)):
-            yield t, self.get_all_embeds_Gt(t, g, ent_embed)
-
-    def evaluate(self, t_list, val=True):
-        """baselines/StaticRGCN.py:20-34,91-113: full train graphs -> embeddings, filtered ranks of the
-        valid/test triples + classification loss."""
-        from .evaluation import EvaluationFilter
-        if not hasattr(self, "evaluater"):
-            self.evaluater = EvaluationFilter(self.args, self.calc_score, self.graph_dict_train, self.graph_dict_val, self.graph_dict_test)
-        graph_dict = self.graph_dict_val if val else self.graph_dict_test
-        dev = self.ent_embeds.device
-        ts = [int(t) for t in t_list]
-        with torch.no_grad():
-            per_graph = self.get_per_graph_ent_embeds(ts, [self.graph_dict_train[t] for t in ts], val=True)
-            ranks, losses = [], []
-            for t, ent_embed in zip(ts, per_graph):
-                g = graph_dict[t]
-                if g.number_of_edges() == 0:
-                    continue
-                all_embeds_g = self.get_all_embeds_Gt(t, g, ent_embed)
-                index_sample = torch.from_numpy(np.stack([g.src, g.rel, g.dst], axis=1)).to(dev)
-                label = torch.ones(index_sample.shape[0], device=dev)
-                ranks.append(self.evaluater.calc_metrics_single_graph(ent_embed, self.rel_embeds, all_embeds_g, index_sample, g, t))
-                losses.append(self.link_classification_loss(ent_embed, self.rel_embeds, index_sample, label).item())
-        ranks = torch.cat(ranks) if ranks else torch.zeros(0, dtype=torch.int64, device=dev)
-        return ranks, (float(np.mean(losses)) if losses else float("nan"))
+        per_graph = self.get_per_graph_ent_embeds(ts, [self.graph_dict_train[t] for t in ts], val=True)
+        for t, ent_embed in zip(ts, per_graph):
+            yield t, ent_embed, lambda g, t=t, ent_embed=ent_embed: self.get_all_embeds_Gt(t, g, ent_embed)
 
     def _fused_loss_ok(self):
         # (the rows this model scores are hidden_size wide: fused_loss_ok holds the scorer's alignment conditions)
@@ -96,8 +66,8 @@ class StaticRGCN(TKG_Module):
     def _fused_plan(self, ts, g_list):
         """Host half of the fused loss of a batch (static for the batch): the row map that assembles every window's all-entity
         matrix from [its graph's rows ; the isolated table], positives / operand indices / known-true slices."""
-        from .sampling import TrueSetStore, plan_batch_loss
-        dev = self.ent_embeds.device
+        from .sampling import plan_batch_loss
+        dev = self._device()
         N, B = self.num_ents, len(g_list)
         sizes = [g.n for g in g_list]
         n_out = int(sum(sizes))
@@ -105,10 +75,7 @@ class StaticRGCN(TKG_Module):
         asm = np.broadcast_to(n_out + np.arange(N, dtype=np.int64)[None, :], (B, N)).copy()
         for b, g in enumerate(g_list):
             asm[b, g.gids] = off_out[b] + np.arange(g.n)
-        store = getattr(self, "_true_store", None)
-        if store is None or store.device != dev:
-            store = self._true_store = TrueSetStore(self.graph_dict_train, N, dev)
-        plan = plan_batch_loss(store, ts, g_list, off_out[:-1], self.args.num_pos_facts, self.sample_rng, n_out, int(self.rel_embeds.shape[0]), dev)
+        plan = plan_batch_loss(self.true_sets(), ts, g_list, off_out[:-1], self.args.num_pos_facts, self.sample_rng, n_out, int(self.rel_embeds.shape[0]), dev)
         return dict(plan=plan, asm=_lib.to_device(asm.reshape(-1).astype(np.int32), dev), asm_inv=TF.gather_inverse(asm.reshape(-1), n_out + N, dev),
                     B=B, t0=ts[0])
 
@@ -117,16 +84,13 @@ class StaticRGCN(TKG_Module):
         pass RGCN.forward_isolated(ent_embeds) does not depend on the window (no time embedding), so it runs once; every
         window's all-entity matrix is [its graph's rows ; the table] through one static row map; the negatives of all graphs
         come from one launch (`cand`: a fixed draw to reuse, else a fresh one per call)."""
-        from .backend import get_backend
         plan = fp["plan"]
         if plan is None:
             return out.sum() * 0.0
         N = self.num_ents
         table = self.ent_encoder.forward_isolated(self.ent_embeds, fp["t0"])
         big = TF.gather_rows(torch.cat([out, table], dim=0), fp["asm"], fp["asm_inv"])
-        if cand is None:
-            cand = get_backend().corrupt_sample(int(self.seed_rng.integers(1 << 62)), plan["truth"], plan["lo"], plan["hi"], plan["ids"],
-                                                self.args.negative_rate, N)
+        cand = self.draw_candidates(plan, cand)
         self._last_plan = (plan, cand)
         return self.batched_link_prediction(out, dict(plan, cand=cand), big.view(fp["B"], N, big.shape[1]))
 
@@ -172,7 +136,6 @@ class StaticRGCN(TKG_Module):
 
     def forward(self, t_list, target_edge_ids=None, samples=None):
         """baselines/StaticRGCN.py:36-46."""
-        dev = self.ent_embeds.device
         ts = [int(t) for t in t_list]
         g_list = [self.graph_dict_train[t] for t in ts]
         per_graph = self.get_per_graph_ent_embeds(ts, g_list, edge_ids=target_edge_ids)
@@ -180,14 +143,4 @@ class StaticRGCN(TKG_Module):
             fused = self._fused_forward(ts, g_list, self._last_rows)
             if fused is not None:
                 return fused
-        loss = 0
-        for i, (t, g, ent_embed) in enumerate(zip(ts, g_list, per_graph)):
-            if samples is not None:
-                triplets, neg_tail, neg_head = samples[i]
-                labels = torch.zeros(triplets.shape[0], dtype=torch.int64)
-            else:
-                triplets, neg_tail, neg_head, labels = self.corrupter.single_graph_negative_sampling(t, g, self.num_ents)
-            triplets, neg_tail, neg_head, labels = triplets.to(dev), neg_tail.to(dev), neg_head.to(dev), labels.to(dev)
-            all_embeds_g = self.get_all_embeds_Gt(t, g, ent_embed)
-            loss = loss + self.train_link_prediction_both(ent_embed, triplets, neg_tail, neg_head, labels, all_embeds_g)
-        return loss
+        return self.per_graph_loss(ts, g_list, samples, per_graph.__getitem__, lambda i: self.get_all_embeds_Gt(ts[i], g_list[i], per_graph[i]))

@@ -360,6 +360,12 @@ def test_self_attention_evaluate_gpu(name):
     check_sa_evaluate(name, DEV)
 
 
+@pytest.mark.parametrize("kind", ["StaticRGCN", "SelfAttentionRGCN", "BiSelfAttentionRGCN"])
+def test_evaluate_is_its_composition_gpu(kind):
+    from tests.window_cases import check_evaluate_composition
+    check_evaluate_composition(kind, DEV)
+
+
 @pytest.mark.parametrize("rows,n,d", [(500, 100000, 200), (7128, 1800, 200), (64, 999, 32), (10, 0, 16), (3, 5000, 256),
                                        (40, 48000, 200), (1, 30000, 128)])      # the last two: split (two-stage) reduction
 def test_segment_sum_matches_scatter_and_is_deterministic(rows, n, d, hip_backend):

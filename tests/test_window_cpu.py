@@ -12,7 +12,7 @@ from temp_amd.window import ChainPlan, window_times
 from tests.cpu_backend import CpuTestBackend
 from tests.golden_util import load
 from tests.window_cases import (check_batched_equals_generic, check_dropout_visits_are_independent, check_dropout_visits_self_attention, check_fused_ensemble_loss, check_static_prepare_split, check_wide_batched_equals_generic, check_evaluate, check_sa_dense_api, check_sa_evaluate, check_sa_window,
-                                check_static, check_window, slice_snapshots)
+                                check_static, check_window, slice_snapshots, EVALUATE_COMPOSED, check_evaluate_composition)
 from oracle import temp_oracle as O
 
 
@@ -115,6 +115,11 @@ def test_self_attention_dense_api():
 @pytest.mark.parametrize("name", ["G14_sa_uni", "G14_sa_bi_rol"])
 def test_self_attention_evaluate(name):
     check_sa_evaluate(name, torch.device("cpu"))
+
+
+@pytest.mark.parametrize("kind", EVALUATE_COMPOSED)
+def test_evaluate_is_its_composition(kind):
+    check_evaluate_composition(kind, torch.device("cpu"))
 
 
 def test_batch_prefetcher_yields_prepared_batches_in_order():

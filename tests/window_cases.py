@@ -334,6 +334,66 @@ def check_sa_evaluate(name, device):
             assert_close(all_list[i], O.sa_all_embeds(model, cfg, gd["train"], i, tt[i], b, hist, mask, td), 1e-5, 2e-6, name + " all embeds")
 
 
+EVALUATE_COMPOSED = ("StaticRGCN", "SelfAttentionRGCN", "BiSelfAttentionRGCN")
+
+
+def check_evaluate_composition(kind, device):
+    """evaluate() of the families without a reference fixture for it (StaticRGCN, the attention models) against the composition it
+    stands for, written out: the family's public per-graph calls, EvaluationFilter.calc_metrics_single_graph,
+    link_classification_loss and the float64 mean of the graphs' float32 losses.  Ranks torch.equal, loss exactly equal.  Three
+    target timestamps of the slice, the middle one's validation graph replaced by an empty one: the skip, and -- evaluated alone --
+    the all-skipped return (empty int64 ranks, nan)."""
+    import copy
+    from temp_amd.evaluation import EvaluationFilter
+    s = slice_snapshots()
+    if kind == "StaticRGCN":
+        z = load("G12_static_rgcn")
+        torch.manual_seed(3)
+        m = StaticRGCN(make_args(module="SRGCN", embed_size=int(z["D"]), hidden_size=int(z["D"]), n_bases=int(z["B"])),
+                       s["num_e"], s["num_r"], s["tr"], s["va"], s["te"]).to(device)
+    else:
+        z = load("G14_sa_uni" if kind == "SelfAttentionRGCN" else "G14_sa_bi_rol")
+        m = build_sa_model(z, device)[0]
+    assert type(m).__name__ == kind
+    ts = sorted(int(t) for t in load("G14_sa_uni")["t_list"])[:3]
+    assert len(ts) == 3 and all(s["va"][t].number_of_edges() > 0 for t in ts)
+    g_empty = copy.copy(s["va"][ts[1]])
+    g_empty.__dict__.pop("_filter_lists", None)
+    keep = np.zeros(0, dtype=np.int64)
+    g_empty.src, g_empty.rel, g_empty.dst = g_empty.src[keep], g_empty.rel[keep], g_empty.dst[keep]
+    assert g_empty.number_of_edges() == 0
+    m.graph_dict_val = dict(m.graph_dict_val)
+    m.graph_dict_val[ts[1]] = g_empty
+
+    ranks, loss = m.evaluate(torch.tensor(ts), val=True)
+
+    ev = EvaluationFilter(m.args, m.calc_score, m.graph_dict_train, m.graph_dict_val, m.graph_dict_test)
+    with torch.no_grad():
+        if kind == "StaticRGCN":
+            rows = m.get_per_graph_ent_embeds(ts, [s["tr"][t] for t in ts], val=True)
+            graphs = [(t, e, lambda g, t=t, e=e: m.get_all_embeds_Gt(t, g, e)) for t, e in zip(ts, rows)]
+        else:
+            per_graph, wb, tables = m.encode(torch.tensor(ts), m.test_seq_len, train=False)
+            all_list = m.all_embeds_batched(wb, torch.cat(per_graph, dim=0), tables)
+            graphs = [(int(wb.rows[i][-1]), e, lambda g, i=i: all_list[i]) for i, e in enumerate(per_graph)]
+        assert sorted(t for t, _, _ in graphs) == ts
+        want_ranks, want_losses = [], []
+        for t, e, all_embeds in graphs:
+            g = m.graph_dict_val[t]
+            if g.number_of_edges() == 0:
+                continue
+            index_sample = torch.from_numpy(np.stack([g.src, g.rel, g.dst], axis=1)).to(device)
+            want_ranks.append(ev.calc_metrics_single_graph(e, m.rel_embeds, all_embeds(g), index_sample, g, t))
+            want_losses.append(m.link_classification_loss(e, m.rel_embeds, index_sample, torch.ones(index_sample.shape[0], device=device)))
+    assert len(want_ranks) == 2 and all(x.dtype == torch.float32 for x in want_losses)
+    want_loss = float(np.mean(np.array([x.item() for x in want_losses], dtype=np.float64)))
+    print("%s evaluate(): %d ranks, loss %.17g (composition %.17g)" % (kind, ranks.numel(), loss, want_loss))
+    assert ranks.dtype == torch.int64 and torch.equal(ranks, torch.cat(want_ranks))
+    assert loss == want_loss
+    none, nan = m.evaluate([ts[1]], val=True)
+    assert none.dtype == torch.int64 and none.numel() == 0 and none.device.type == torch.device(device).type and np.isnan(nan)
+
+
 # ---------------------------------------------------------------------------------------------------------------------
 # config 3: post-ensemble / impute window models (G15)
 # ---------------------------------------------------------------------------------------------------------------------
