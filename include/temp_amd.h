@@ -760,6 +760,17 @@ int temp_hyperplane_rows_fwd(int B, int N, int d, const float* table, const floa
 int temp_hyperplane_rows_bwd(int B, int N, int d, const float* table, const float* w, const float* d_out, float* d_table, float* d_w,
                              void* workspace, size_t workspace_bytes, void* stream);
 
+/* The pair table of two tables for B windows (SimplE, baselines/Simple.py: every entity and every relation has a forward and an inverse
+ * row), and its adjoint:
+ *   out[b N + i, :] = [a[i, :] | a_inv[i, :]]                 b = 0 .. B - 1
+ * a, a_inv [N, d], out / d_out [B N, 2 d] row-major.  One launch: a thread reads its columns of a and a_inv once and writes them B
+ * times (2 N d floats read, 2 B N d written).  The backward OVERWRITES both outputs whole,
+ *   d_a[i] = sum_b d_out[b N + i, :d],   d_a_inv[i] = sum_b d_out[b N + i, d:]        the B terms added in ascending b in fp32,
+ * in one launch, without atomics and without a workspace: results are bit-repeatable.  float4 columns when d % 4 == 0, one float per
+ * thread otherwise.  B, N, d <= 0 or a NULL pointer: TEMP_E_BADARG, nothing is launched.  (B = 1: a relation pair table.) */
+int temp_pair_rows_fwd(int B, int N, int d, const float* a, const float* a_inv, float* out, void* stream);
+int temp_pair_rows_bwd(int B, int N, int d, const float* d_out, float* d_a, float* d_a_inv, void* stream);
+
 /* ------------------------------------------------------------------------------------------------
  * Plain fp32 MFMA GEMMs (the extra (n,D)@(D,D) terms of the linear-recurrence layers,
  * models/RRGCN.py:141, models/BiRRGCN.py:128-129; the all-entity score matrix below).
@@ -813,11 +824,18 @@ int temp_gather_ce_bwd(int P, int C, int N, const float* scores, const int32_t* 
  *   distmult / complex: q[p] such that  score(p, candidate c) = <q[p], c>  (an inner-product query);
  *   transE:             q[p] = k + r (tail) or k - r (head), a translation query:  score(p, c) = -|q[p] - c|_1.  One IEEE
  *                       add / subtract per element, bit-equal to the tensor expression.
+ *   simple (SimplE, utils/scores.py:14-24): the rows are PAIR rows of width d = 2 h, d % 8 == 0 -- k = [e | e_inv], r = [rel | rel_inv],
+ *                       a candidate c = [o | o_inv] (temp_pair_rows_fwd builds such tables) -- and
+ *                         q[p] = 1/2 [k[h:] r[h:] | k[:h] r[:h]]  (tail)      q[p] = 1/2 [k[h:] r[:h] | k[:h] r[h:]]  (head)
+ *                       so that <q[p], c> = 1/2 (<s r, o_inv> + <s_inv r_inv, o>) resp. 1/2 (<s, r o_inv> + <s_inv, r_inv o>): an
+ *                       inner-product query like distmult / complex.  The factor 1/2 is exact: every element of q and of the
+ *                       gradients is one rounded product.  is_tail is required.  temp_gated_query_* do not take this kind.
  *   bwd: per-row gradients d_known_rows[p], d_rel_rows[p] (the caller sums them over the index lists); transE: d_q and +-d_q.
  * ---------------------------------------------------------------------------------------------- */
 #define TEMP_SCORE_DISTMULT 0
 #define TEMP_SCORE_COMPLEX 1
 #define TEMP_SCORE_TRANSE 2
+#define TEMP_SCORE_SIMPLE 3
 int temp_bilinear_query_fwd(int P, int d, int kind, const float* ent_rows, const int32_t* known_idx, const float* rel, const int32_t* rel_idx,
                             const int32_t* is_tail, float* q, void* stream);
 int temp_bilinear_query_bwd(int P, int d, int kind, const float* ent_rows, const int32_t* known_idx, const float* rel, const int32_t* rel_idx,

@@ -10,6 +10,6 @@ from .rgcn import RGCN, RGCNLayer  # noqa: F401
 from .rrgcn import GRRGCNLayer, RRGCN, RRGCNLayer  # noqa: F401
 from .birrgcn import BiGRRGCNLayer, BiRRGCN, BiRRGCNLayer  # noqa: F401
 from .gru_cell import GRUCell  # noqa: F401
-from .non_recurrent import Hyte  # noqa: F401
+from .non_recurrent import Hyte, SimplE  # noqa: F401
 
 __version__ = "0.1.0"

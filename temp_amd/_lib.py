@@ -122,7 +122,7 @@ class TempAdamTensor(ctypes.Structure):
 
 
 ASSEMBLE_PIECE = 4096
-SCORE_KINDS = {"distmult": 0, "complex": 1, "transE": 2}
+SCORE_KINDS = {"distmult": 0, "complex": 1, "transE": 2, "simple": 3}
 ADAM_CHUNK = 4096         # include/temp_amd.h: TEMP_ADAM_CHUNK (elements of one tensor that one workgroup of the optimizer passes owns)
 TOPK_MAX = 256             # include/temp_amd.h: TEMP_TOPK_MAX (the longest answer list temp_filtered_topk keeps)
 
@@ -219,6 +219,8 @@ SYMBOLS = {
     "temp_hyperplane_rows_bwd_workspace": (_SZ, [_I, _I, _I]),
     "temp_hyperplane_rows_fwd": (_I, [_I, _I, _I, c_vp, c_vp, c_vp, c_vp]),
     "temp_hyperplane_rows_bwd": (_I, [_I, _I, _I, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, _SZ, c_vp]),
+    "temp_pair_rows_fwd": (_I, [_I, _I, _I, c_vp, c_vp, c_vp, c_vp]),
+    "temp_pair_rows_bwd": (_I, [_I, _I, _I, c_vp, c_vp, c_vp, c_vp]),
     "temp_linear": (_I, [_I, _I, _I, c_vp, _I, c_vp, _I, _I, c_vp, _I, c_vp]),
     "temp_linear_t": (_I, [_I, _I, _I, c_vp, _I, c_vp, _I, _I, c_vp, _I, c_vp]),
     "temp_linear_multi": (_I, [_I, ctypes.POINTER(TempLinearProblem), _I, _I, _I, _I, _I, _I, c_vp]),

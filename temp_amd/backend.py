@@ -428,6 +428,30 @@ class HipBackend:
                    "temp_hyperplane_rows_bwd")
         return d_table, d_w
 
+    # ---- the pair table of two tables (include/temp_amd.h: temp_pair_rows_fwd / _bwd) ----------------------
+    def pair_rows_fwd(self, a, a_inv, B):
+        """-> (B N, 2 d) stack of [a | a_inv], the same table for each of the B windows (one launch)."""
+        a, a_inv = _f32(a, "a"), _f32(a_inv, "a_inv")
+        if a.dim() != 2 or a.shape != a_inv.shape or int(B) < 1:
+            raise _lib.TempAmdError("pair_rows: a and a_inv (N, d) of one shape and B >= 1 expected")
+        N, d = a.shape
+        out = torch.empty(int(B) * N, 2 * d, dtype=torch.float32, device=a.device)
+        _lib.check(self.lib.temp_pair_rows_fwd(int(B), N, d, _ptr(a), _ptr(a_inv), _ptr(out), _stream()), "temp_pair_rows_fwd")
+        return out
+
+    def pair_rows_bwd(self, d_out, B):
+        """-> (d_a, d_a_inv): the two halves of d_out (B N, 2 d) summed over the B windows in ascending order, each overwritten whole
+        (one launch, no atomics, no workspace)."""
+        d_out = _f32(d_out, "d_out")
+        B = int(B)
+        if d_out.dim() != 2 or B < 1 or d_out.shape[0] % B or d_out.shape[1] % 2:
+            raise _lib.TempAmdError("pair_rows_bwd: d_out must be (B N, 2 d)")
+        N, d = d_out.shape[0] // B, d_out.shape[1] // 2
+        d_a = torch.empty(N, d, dtype=torch.float32, device=d_out.device)
+        d_a_inv = torch.empty_like(d_a)
+        _lib.check(self.lib.temp_pair_rows_bwd(B, N, d, _ptr(d_out), _ptr(d_a), _ptr(d_a_inv), _stream()), "temp_pair_rows_bwd")
+        return d_a, d_a_inv
+
     # ---- persistent window chain (include/temp_amd.h: TempGruChain) -------------------------------
     def gru_chain_supported(self, d):
         return bool(self.lib.temp_gru_chain_supported(int(d)))

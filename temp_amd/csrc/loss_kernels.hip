@@ -161,7 +161,11 @@ __global__ void __launch_bounds__(256) k_gather_ce_bwd(int C, int N, const float
 //   ComplEx, head mode  q = [re_r re_k + im_r im_k | re_r im_k - im_r re_k]      (k is the object, candidates are subjects)
 // so that score(candidate c) = <q, c>, and the translation query of TransE (utils/scores.py:46-55)
 //   TransE, tail mode   q = k + r         TransE, head mode   q = k - r           score(candidate c) = -|q - c|_1
-// (one IEEE add / subtract per element: bit-equal to the tensor expression).  One thread per float4 of the half width; the backward writes the per-row
+// (one IEEE add / subtract per element: bit-equal to the tensor expression), and the pair fold of SimplE (utils/scores.py:14-24) over
+// PAIR rows k = [e | e_inv], r = [rel | rel_inv] of width d = 2 h, candidates c = [o | o_inv]:
+//   SimplE, tail mode   q = 1/2 [k_inv r_inv | k_fwd r_fwd]      SimplE, head mode   q = 1/2 [k_inv r_fwd | k_fwd r_inv]
+// so that <q, c> is the mean of the two DistMult directions (the factor 1/2 is exact: every element is ONE rounded product).
+// One thread per float4 of the half width; the backward writes the per-row
 // gradients of k and r (the caller reduces them over the static index lists with temp_segment_sum_rows).
 // ---------------------------------------------------------------------------------------------
 template <bool BWD>
@@ -169,7 +173,7 @@ __global__ void __launch_bounds__(256) k_bilinear_query(int P, int d, int kind, 
                                                         const float* __restrict__ rel, const int32_t* __restrict__ rel_idx,
                                                         const int32_t* __restrict__ is_tail, const float* __restrict__ dq, float* __restrict__ o0,
                                                         float* __restrict__ o1) {
-  const int half = kind == TEMP_SCORE_COMPLEX ? d / 2 : d;
+  const int half = (kind == TEMP_SCORE_COMPLEX || kind == TEMP_SCORE_SIMPLE) ? d / 2 : d;
   const int g4 = half / 4;
   const size_t total = (size_t)P * g4;
   for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (size_t)gridDim.x * blockDim.x) {
@@ -186,6 +190,23 @@ __global__ void __launch_bounds__(256) k_bilinear_query(int P, int d, int kind, 
         const float4 g = ld4(dq + o);
         st4(o0 + o, g);
         st4(o1 + o, make_float4(sg * g.x, sg * g.y, sg * g.z, sg * g.w));
+      }
+      continue;
+    }
+    if (kind == TEMP_SCORE_SIMPLE) {
+      // q[:h] = 1/2 k[h:] rx, q[h:] = 1/2 k[:h] ry with (rx, ry) = (r[h:], r[:h]) for the tail mode and (r[:h], r[h:]) for the head mode
+      const int tail = is_tail[p];
+      const int ox = tail ? half : 0, oy = half - ox;               // where rx / ry sit in the relation row
+      const float4 kf = ld4(k), ki = ld4(k + half), rx = ld4(r + ox), ry = ld4(r + oy);
+      if (!BWD) {
+        st4(o0 + o, make_float4(0.5f * (ki.x * rx.x), 0.5f * (ki.y * rx.y), 0.5f * (ki.z * rx.z), 0.5f * (ki.w * rx.w)));
+        st4(o0 + o + half, make_float4(0.5f * (kf.x * ry.x), 0.5f * (kf.y * ry.y), 0.5f * (kf.z * ry.z), 0.5f * (kf.w * ry.w)));
+      } else {
+        const float4 a = ld4(dq + o), b = ld4(dq + o + half);
+        st4(o0 + o, make_float4(0.5f * (b.x * ry.x), 0.5f * (b.y * ry.y), 0.5f * (b.z * ry.z), 0.5f * (b.w * ry.w)));                 // d k[:h]
+        st4(o0 + o + half, make_float4(0.5f * (a.x * rx.x), 0.5f * (a.y * rx.y), 0.5f * (a.z * rx.z), 0.5f * (a.w * rx.w)));          // d k[h:]
+        st4(o1 + o + ox, make_float4(0.5f * (a.x * ki.x), 0.5f * (a.y * ki.y), 0.5f * (a.z * ki.z), 0.5f * (a.w * ki.w)));            // d rx
+        st4(o1 + o + oy, make_float4(0.5f * (b.x * kf.x), 0.5f * (b.y * kf.y), 0.5f * (b.z * kf.z), 0.5f * (b.w * kf.w)));            // d ry
       }
       continue;
     }
@@ -308,8 +329,9 @@ using namespace temp;
 extern "C" {
 
 static int bilinear_query_args(int P, int d, int kind, const void* a, const void* b, const void* c, const void* e, const void* f) {
-  if (P < 0 || d <= 0 || (kind != TEMP_SCORE_DISTMULT && kind != TEMP_SCORE_COMPLEX && kind != TEMP_SCORE_TRANSE)) return TEMP_E_BADARG;
-  if (kind == TEMP_SCORE_COMPLEX ? d % 8 : d % 4) return TEMP_E_UNSUPPORTED;
+  if (P < 0 || d <= 0 || (kind != TEMP_SCORE_DISTMULT && kind != TEMP_SCORE_COMPLEX && kind != TEMP_SCORE_TRANSE && kind != TEMP_SCORE_SIMPLE))
+    return TEMP_E_BADARG;
+  if ((kind == TEMP_SCORE_COMPLEX || kind == TEMP_SCORE_SIMPLE) ? d % 8 : d % 4) return TEMP_E_UNSUPPORTED;
   if (P > 0 && (!a || !b || !c || !e || (kind != TEMP_SCORE_DISTMULT && !f))) return TEMP_E_BADARG;
   return TEMP_OK;
 }

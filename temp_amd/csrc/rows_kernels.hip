@@ -899,6 +899,55 @@ static int hyperplane_grid(int N, bool wide) {                      // a block p
       else TEMP_LAUNCH(KID, (kern##_wide<1>), grid, block, 0, st, __VA_ARGS__);                                                          \
     }                                                                                                                                    \
   } while (0)
+
+// ---- the pair table of two tables for B windows (SimplE: [a | a_inv]) and its adjoint ------------------------------------------
+// out[(b N + i), :] = [a[i, :] | a_inv[i, :]], rows of width 2 d.  As in the diachronic pass one thread owns one row and V columns of
+// BOTH halves (V = 4: float4 on every stream -- d % 4 == 0 puts both halves of an output row on 16-byte boundaries; V = 1 otherwise)
+// and walks the B windows: a / a_inv are read once; the adjoint adds its B terms in registers in ascending b and OVERWRITES d_a /
+// d_a_inv -- no atomics, no workspace, no second launch.
+template <int V>
+__global__ void __launch_bounds__(256) k_pair_rows_fwd(int B, int N, int d, const float* __restrict__ a, const float* __restrict__ a_inv,
+                                                       float* __restrict__ out) {
+  using Vec = DeVec<V>;
+  const int dv = d / V;
+  const size_t plane = (size_t)N * dv;                           // Vecs per table
+  const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= plane) return;
+  const size_t j = i / dv, c = i - j * dv;
+  const Vec x = ((const Vec*)a)[i], y = ((const Vec*)a_inv)[i];
+  Vec* __restrict__ o = (Vec*)out + j * 2 * dv + c;
+  for (int b = 0; b < B; ++b) {
+    o[(size_t)b * 2 * plane] = x;
+    o[(size_t)b * 2 * plane + dv] = y;
+  }
+}
+
+template <int V>
+__global__ void __launch_bounds__(256) k_pair_rows_bwd(int B, int N, int d, const float* __restrict__ d_out, float* __restrict__ d_a,
+                                                       float* __restrict__ d_a_inv) {
+  using Vec = DeVec<V>;
+  const int dv = d / V;
+  const size_t plane = (size_t)N * dv;
+  const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= plane) return;
+  const size_t j = i / dv, c = i - j * dv;
+  const Vec* __restrict__ g = (const Vec*)d_out + j * 2 * dv + c;
+  Vec sx, sy;
+#pragma unroll
+  for (int u = 0; u < V; ++u) sx.v[u] = sy.v[u] = 0.f;
+#pragma unroll 4
+  for (int b = 0; b < B; ++b) {
+    const Vec gx = g[(size_t)b * 2 * plane], gy = g[(size_t)b * 2 * plane + dv];
+#pragma unroll
+    for (int u = 0; u < V; ++u) { sx.v[u] += gx.v[u]; sy.v[u] += gy.v[u]; }
+  }
+  ((Vec*)d_a)[i] = sx;
+  ((Vec*)d_a_inv)[i] = sy;
+}
+
+static bool pair_rows_args_ok(int B, int N, int d) {
+  return B >= 1 && N >= 1 && d >= 1 && ((long long)N * d + 255) / 256 <= 0x7fffffffLL;        // (the grid: one thread per V columns)
+}
 }  // namespace temp
 
 using namespace temp;
@@ -988,6 +1037,24 @@ int temp_hyperplane_rows_bwd(int B, int N, int d, const float* table, const floa
   float* part = (float*)workspace;
   TEMP_HYPERPLANE(K_HYPERPLANE_BWD, k_hyperplane_bwd, B, N, d, table, w, d_out, d_table, part);
   TEMP_LAUNCH(K_HYPERPLANE_BWD_FINISH, k_hyperplane_bwd_finish, dim3(B), dim3(256), 0, st, B, hyperplane_tiles(N), d, w, (const float*)part, d_w);
+  return launch_status();
+}
+
+int temp_pair_rows_fwd(int B, int N, int d, const float* a, const float* a_inv, float* out, void* stream) {
+  if (!pair_rows_args_ok(B, N, d) || !a || !a_inv || !out) return TEMP_E_BADARG;
+  if (d % 4 == 0)
+    TEMP_LAUNCH(K_PAIR_ROWS_FWD, k_pair_rows_fwd<4>, dim3(ceil_div((long long)N * (d / 4), 256)), dim3(256), 0, (hipStream_t)stream, B, N, d, a, a_inv, out);
+  else
+    TEMP_LAUNCH(K_PAIR_ROWS_FWD, k_pair_rows_fwd<1>, dim3(ceil_div((long long)N * d, 256)), dim3(256), 0, (hipStream_t)stream, B, N, d, a, a_inv, out);
+  return launch_status();
+}
+
+int temp_pair_rows_bwd(int B, int N, int d, const float* d_out, float* d_a, float* d_a_inv, void* stream) {
+  if (!pair_rows_args_ok(B, N, d) || !d_out || !d_a || !d_a_inv) return TEMP_E_BADARG;
+  if (d % 4 == 0)
+    TEMP_LAUNCH(K_PAIR_ROWS_BWD, k_pair_rows_bwd<4>, dim3(ceil_div((long long)N * (d / 4), 256)), dim3(256), 0, (hipStream_t)stream, B, N, d, d_out, d_a, d_a_inv);
+  else
+    TEMP_LAUNCH(K_PAIR_ROWS_BWD, k_pair_rows_bwd<1>, dim3(ceil_div((long long)N * d, 256)), dim3(256), 0, (hipStream_t)stream, B, N, d, d_out, d_a, d_a_inv);
   return launch_status();
 }
 

@@ -176,7 +176,7 @@ class EvaluationFilter:
             if P == 0:
                 return torch.zeros(0, dtype=torch.int64, device=dev)
             name = getattr(self.args, "score_function", None)
-            fused = name in ("distmult", "complex") and num_ent % 4 == 0 and all_ent_embeds.shape[1] % 4 == 0
+            fused = name in S.BILINEAR and num_ent % 4 == 0 and all_ent_embeds.shape[1] % 4 == 0
             l1 = _l1_route(name, get_backend(), all_ent_embeds.shape[1])
             out = {}
             for mode in ("head", "tail"):
@@ -224,7 +224,7 @@ class EvaluationFilter:
             be = get_backend()
             name = getattr(self.args, "score_function", None)
             kn, r = all_ent_embeds[known], rel_enc_means[rel]
-            fused = name in ("distmult", "complex") and num_ent % 4 == 0 and d % 4 == 0
+            fused = name in S.BILINEAR and num_ent % 4 == 0 and d % 4 == 0
             l1 = _l1_route(name, be, d)
             if fused:
                 q = S.bilinear_query(name, kn, r, mode).contiguous()
@@ -306,7 +306,7 @@ class _MixedRankFilter(EvaluationFilter):
         columns -inf (what the selection kernels take)."""
         name = getattr(self.args, "score_function", None)
         P, num_ent = known.shape[0], all_embeds.shape[0]
-        if name in ("distmult", "complex") and num_ent % 4 == 0 and all_embeds.shape[1] % 4 == 0:
+        if name in S.BILINEAR and num_ent % 4 == 0 and all_embeds.shape[1] % 4 == 0:
             q = S.bilinear_query(name, known, r, mode).contiguous()
             return get_backend().linear(q, all_embeds.contiguous(), True)
         if _l1_route(name, get_backend(), all_embeds.shape[1]):
@@ -406,7 +406,7 @@ class PostEvaluationFilter(_MixedRankFilter):
                     # one pass over all P triples: the candidate mix formed inside the dense L1 kernel, the pad columns already -inf
                     score = be.l1_mix_scores(_translation_query(known, r, mode), all_embeds_g_loc.contiguous(), all_embeds_g_rec.contiguous(),
                                              w_cand.contiguous())
-                elif name in ("distmult", "complex"):
+                elif name in S.BILINEAR:
                     score = w_cand * self._score_matrix(known, r, all_embeds_g_loc, mode, eval_bz) \
                         + (1 - w_cand) * self._score_matrix(known, r, all_embeds_g_rec, mode, eval_bz)
                 else:
@@ -441,7 +441,7 @@ class PostEvaluationFilter(_MixedRankFilter):
             kn = w_known * all_loc[known] + (1 - w_known) * all_rec[known]
             r = rel_enc_means[rel]
             name = getattr(self.args, "score_function", None)
-            if name in ("distmult", "complex"):
+            if name in S.BILINEAR:
                 return self._mixed_topk(kn, kn, r, all_loc, all_rec, w_cand, mode, k, ptr, ids, keep, panel)
             be = get_backend()
             l1 = _l1_route(name, be, d) and hasattr(be, "l1_mix_scores")

@@ -396,6 +396,38 @@ def hyperplane_rows(table, w):
     return _HyperplaneRowsFn.apply(table.contiguous(), w.contiguous())
 
 
+class _PairRowsFn(torch.autograd.Function):
+    """The (B N, 2 D) stack of pair rows [a | a_inv] (temp_pair_rows_fwd); the backward sums the stack's gradient over the B windows
+    in ascending order and splits the halves in the same launch (temp_pair_rows_bwd)."""
+
+    @staticmethod
+    def forward(ctx, a, a_inv, B):
+        ctx.B = B
+        return get_backend().pair_rows_fwd(a, a_inv, B)
+
+    @staticmethod
+    def backward(ctx, d_out):
+        return get_backend().pair_rows_bwd(d_out.contiguous(), ctx.B) + (None,)
+
+
+def pair_rows_torch(a, a_inv, B):
+    """pair_rows as the torch composition: one concatenation, B - 1 more copies out of an expanded view."""
+    N, D = a.shape
+    return torch.cat([a, a_inv], dim=1).unsqueeze(0).expand(B, N, 2 * D).reshape(B * N, 2 * D)
+
+
+def pair_rows(a, a_inv, B):
+    """Rows b N + i of the result = [a[i] | a_inv[i]] for b < B (SimplE's pair layout: an entity's -- or, with B = 1, a relation's --
+    forward and inverse row side by side).  a, a_inv (N, D) float32 on one device; both get gradients.  A backend without the pass
+    (the CPU test backend) takes the torch composition."""
+    B = int(B)
+    if a.dim() != 2 or a.shape != a_inv.shape or B < 1:
+        raise ValueError("pair_rows: a and a_inv (N, D) of one shape and B >= 1 expected")
+    if not hasattr(get_backend(), "pair_rows_fwd"):
+        return pair_rows_torch(a, a_inv, B)
+    return _PairRowsFn.apply(a.contiguous(), a_inv.contiguous(), B)
+
+
 class _HistoryAttentionFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, qkv, kv_hist, idx, decay, inverse):

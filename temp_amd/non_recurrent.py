@@ -1,15 +1,17 @@
 """The embedding-only baselines of the paper's tables, with the reference's interface: `--module Static` (baselines/Static.py),
-`--module DE`, the diachronic embedding (baselines/DiachronicEmbedding.py), and `--module Hyte` (baselines/Hyte.py), all on
-baselines/TKG_Non_Recurrent.py.  No message passing: the all-entity table of timestamp t is a function of the parameters and t alone,
+`--module DE`, the diachronic embedding (baselines/DiachronicEmbedding.py), `--module Hyte` (baselines/Hyte.py) and `--module Simple`
+(baselines/Simple.py), all on baselines/TKG_Non_Recurrent.py.  No message passing: the all-entity table of timestamp t is a function of
+the parameters and t alone,
 
     Static               ent_embeds
     DiachronicEmbedding  ent_embeds * [1 (first D // 2 columns) | sin(t * w_temp_ent_embeds + b_temp_ent_embeds)]
     Hyte                 ent_embeds - n_t (n_t . ent_embeds),  n_t = time_embeddings[t] / |time_embeddings[t]|   (rel_embeds likewise)
+    SimplE               [ent_embeds | ent_embeds_inv], rows of width 2 D                      (rel_embeds | rel_embeds_inv likewise)
 
 so a batch of B timestamps is ONE (B N, D) stack (functional.diachronic_rows / hyperplane_rows: one launch forward, a backward that
 already sums over the timestamps) scored by ONE fused loss node (TKG_Module.batched_link_prediction) -- the loss, the sampler and the
 filtered ranking are the ones the RGCN models use.  Hyte's relation rows depend on the timestamp too: its (B 2R, D) relation stack
-is the loss node's relation operand (sampling.plan_batch_loss(rel_stride=2R))."""
+is the loss node's relation operand (sampling.plan_batch_loss(rel_stride=2R)); SimplE's ONE (2R, 2D) pair table serves all windows."""
 import math
 
 import numpy as np
@@ -79,8 +81,12 @@ class TKG_Non_Recurrent(TKG_Module):
         return super()._graph_metrics(all_embeds_g[self._gids(g)], all_embeds_g, index_sample, g, t, rel=rel_embed)
 
     # -- the fused batch loss ------------------------------------------------------------------------------------------------
+    def row_width(self):
+        """The width of the rows of table_stack(): what the loss nodes take as the query width."""
+        return self.embed_size
+
     def _fused_loss_ok(self):
-        return self.use_device_sampler and self.fused_loss_ok(self.embed_size)
+        return self.use_device_sampler and self.fused_loss_ok(self.row_width())
 
     def _fused_plan(self, ts, g_list):
         """Host half of the fused loss of a batch, uploaded once: the times, the positives / operand indices / known-true slices
@@ -226,5 +232,44 @@ class Hyte(TKG_Non_Recurrent):
         return ent[self._gids(g)], rel
 
 
+class SimplE(TKG_Non_Recurrent):
+    """baselines/Simple.py: every entity and every relation has a forward and an inverse row, and a triple's score is the mean of the
+    two DistMult directions <s r, o_inv> and <s_inv r_inv, o> (scores.simple).  In the PAIR layout -- entity e is the row
+    [ent_embeds[e] | ent_embeds_inv[e]], relation r the row [rel_embeds[r] | rel_embeds_inv[r]], both of width 2 D -- that score is
+    bilinear in (folded query, candidate row) like DistMult's (scores.bilinear_query("simple"), scores.simple_pair), so the pair tables
+    go through the loss nodes, the filtered rank and predict() as any other table.  The relation pair table does not depend on the
+    timestamp: ONE (2R, 2D) table is the relation operand of every window (rel_stride stays None)."""
+
+    def __init__(self, args, num_ents, num_rels, graph_dict_train, graph_dict_val, graph_dict_test):
+        args.score_function = 'simple'                              # the score the reference's train_link_prediction computes
+        super().__init__(args, num_ents, num_rels, graph_dict_train, graph_dict_val, graph_dict_test)
+        self.ent_embeds_inv = nn.Parameter(torch.Tensor(self.num_ents, self.embed_size))           # baselines/Simple.py:70-75: after
+        self.rel_embeds_inv = nn.Parameter(torch.Tensor(self.num_rels * 2, self.embed_size))       # the base tables, in this order
+        nn.init.xavier_uniform_(self.ent_embeds_inv, gain=nn.init.calculate_gain('relu'))
+        nn.init.xavier_uniform_(self.rel_embeds_inv, gain=nn.init.calculate_gain('relu'))
+
+    def row_width(self):
+        return 2 * self.embed_size
+
+    def table_stack(self, times):
+        return TF.pair_rows(self.ent_embeds, self.ent_embeds_inv, times.shape[0])
+
+    def relation_stack(self, times):
+        """The one (2R, 2D) relation pair table (one launch whatever the number of windows)."""
+        return TF.pair_rows(self.rel_embeds, self.rel_embeds_inv, 1)
+
+    def _rel_rows(self, rel_stack, b):
+        return rel_stack                                            # shared by all windows: nothing to slice
+
+    def relation_table(self, t):
+        return self.relation_stack(None)
+
+    def get_per_graph_ent_embeds(self, g_list):
+        """baselines/Simple.py:80-85 -> (the graphs' rows of ent_embeds, the graphs' rows of ent_embeds_inv), one tensor per graph."""
+        ids = torch.cat([self._gids(g) for g in g_list])
+        sizes = [int(g.n) for g in g_list]
+        return self.ent_embeds[ids].split(sizes), self.ent_embeds_inv[ids].split(sizes)
+
+
 # main.py:42-55: the `--module` names of the embedding-only baselines
-MODULES = {"Static": Static, "DE": DiachronicEmbedding, "Hyte": Hyte}
+MODULES = {"Static": Static, "DE": DiachronicEmbedding, "Hyte": Hyte, "Simple": SimplE}

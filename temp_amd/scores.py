@@ -63,6 +63,20 @@ def simple(head, head_inv, rel, rel_inv, tail, tail_inv, mode='tail'):
     return (a + b) / 2
 
 
+def simple_pair(s, r, o, mode='single'):
+    """SimplE as a three-argument scorer on PAIR rows [x | x_inv] of width 2 D (subject, relation and object alike): `simple` on the
+    halves.  With pair tables every consumer of calc_score(s, r, o, mode) applies to SimplE as it stands."""
+    s_fwd, s_inv = _split(s)
+    r_fwd, r_inv = _split(r)
+    o_fwd, o_inv = _split(o)
+    return simple(s_fwd, s_inv, r_fwd, r_inv, o_fwd, o_inv, mode=mode)
+
+
+# the scorers that are bilinear in (folded query, candidate): bilinear_query gives their query, one GEMM against the all-entity table
+# their scores.  ("simple": over pair rows, see simple_pair.)
+BILINEAR = ("distmult", "complex", "simple")
+
+
 def bilinear_query(name, known, relation, mode):
     """Fold the known entity and the relation into ONE query vector q such that
     score(candidate) = <q, candidate>.  `known` is the subject for mode='tail' (candidates are
@@ -75,4 +89,12 @@ def bilinear_query(name, known, relation, mode):
         if mode == "head":
             return torch.cat([re_r * re_k + im_r * im_k, re_r * im_k - im_r * re_k], dim=-1)
         return torch.cat([re_k * re_r - im_k * im_r, re_k * im_r + im_k * re_r], dim=-1)
+    if name == "simple":
+        # pair rows: <q, [c | c_inv]> = 1/2 (<k r, c_inv> + <k_inv r_inv, c>) for the tail mode, 1/2 (<c, r k_inv> + <c_inv, r_inv k>)
+        # for the head mode -- the half that meets c is the one made of the INVERSE known row
+        k_fwd, k_inv = _split(known)
+        r_fwd, r_inv = _split(relation)
+        if mode == "head":
+            return torch.cat([0.5 * (k_inv * r_fwd), 0.5 * (k_fwd * r_inv)], dim=-1)
+        return torch.cat([0.5 * (k_inv * r_inv), 0.5 * (k_fwd * r_fwd)], dim=-1)
     return None

@@ -31,7 +31,8 @@ class TKG_Module(nn.Module):
         self.use_cuda = getattr(args, "use_cuda", False)
         self.num_pos_facts = args.num_pos_facts
         self.negative_rate = args.negative_rate
-        self.calc_score = {'distmult': scores.distmult, 'complex': scores.complex, 'transE': scores.transE}[args.score_function]
+        self.calc_score = {'distmult': scores.distmult, 'complex': scores.complex, 'transE': scores.transE,
+                           'simple': scores.simple_pair}[args.score_function]
         self.fused_loss = True
         self.build_model()
         if not getattr(args, "debug", False):
@@ -118,7 +119,7 @@ class TKG_Module(nn.Module):
             r = TF.gather_rows(rel_embeds, t32[:, 1].contiguous())
             known = TF.gather_rows(ent_embed, (t32[:, 0] if corrupt_tail else t32[:, 2]).contiguous())
             return TF.translation_cross_entropy(known + r if corrupt_tail else known - r, all_embeds_g, neg_samples.to(torch.int32).contiguous())
-        if self.fused_loss and name in ("distmult", "complex") and all_embeds_g.shape[0] % 4 == 0 and triplets.shape[0] > 0:
+        if self.fused_loss and self._graph_gemm_ok(name, ent_embed.shape[1]) and all_embeds_g.shape[0] % 4 == 0 and triplets.shape[0] > 0:
             from . import functional as TF
             t32 = triplets.to(torch.int32)
             # row gathers through the HIP kernel: its backward is one atomic scatter-add instead of
@@ -149,7 +150,7 @@ class TKG_Module(nn.Module):
             known = TF.gather_rows(ent_embed, torch.cat([t32[:, 0], t32[:, 2]]).contiguous())
             cand = torch.cat([neg_tail, neg_head], dim=0).to(torch.int32).contiguous()
             return 2.0 * TF.translation_cross_entropy(torch.cat([known[:P] + r, known[P:] - r], dim=0), all_embeds_g, cand)
-        if self.fused_loss and name in ("distmult", "complex") and all_embeds_g.shape[0] % 4 == 0 and P > 0:
+        if self.fused_loss and self._graph_gemm_ok(name, ent_embed.shape[1]) and all_embeds_g.shape[0] % 4 == 0 and P > 0:
             from . import functional as TF
             t32 = triplets.to(torch.int32)
             r = TF.gather_rows(rel_embeds, t32[:, 1].contiguous())
@@ -223,7 +224,14 @@ class TKG_Module(nn.Module):
     def bilinear_loss_ok(self, D):
         """The GEMM loss nodes apply: a bilinear scorer, and shapes inside the kernels' alignment (D = width of the query rows)."""
         name = self.args.score_function
-        return self.fused_loss and name in ("distmult", "complex") and self.num_ents % 4 == 0 and D % (8 if name == "complex" else 4) == 0
+        return self.fused_loss and name in scores.BILINEAR and self.num_ents % 4 == 0 and D % (4 if name == "distmult" else 8) == 0
+
+    @staticmethod
+    def _graph_gemm_ok(name, D):
+        """One target graph's loss goes through the folded query and the score GEMM: a bilinear scorer (distmult / complex: no
+        condition on the width here, as before); SimplE only at pair rows the fold kernel takes, D = 2 embed_size with D % 8 == 0 --
+        its other widths stay on the literal route through scores.simple_pair."""
+        return name in scores.BILINEAR and (name != "simple" or D % 8 == 0)
 
     def translation_loss_ok(self, D):
         """The L1 loss nodes apply: TransE, a backend with the L1 kernels, D % 4 == 0 (no condition on num_ents: no GEMM)."""
