@@ -915,6 +915,28 @@ int temp_gather_ce_mix_bwd(int P, int C, int N, const float* s_a, const float* s
                            float* d_w, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * Frozen-ensemble candidate cross-entropy (Aggregator, models/aggregator.py:200-206, 339-342): two FROZEN streams score the same
+ * candidate lists from their own tables, possibly of different widths, and a per-row weight mixes the scores.  cand [P, C] int32,
+ * column 0 = the true entity, holds ROW indices of both tables (the (B N_ents, D) stacks of the windows' all-entity matrices, the
+ * window offset already added); row offsets are formed in 64 bits.
+ *   kind TEMP_FROZEN_DOT: a_c = <q_a[p], T_a[cand[p,c]]>      (the folded bilinear query of temp_bilinear_query_fwd: distmult, complex)
+ *   kind TEMP_FROZEN_L1:  a_c = -|q_a[p] - T_a[cand[p,c]]|_1  (the translation query: transE)
+ *   b_c the same on (q_b, T_b);   x_c = mix(w[p], a_c, b_c) = fmaf(w, a_c, (1 - w) * b_c)   (csrc/mix.hpp: w == 1 gives a_c, w == 0 b_c)
+ *   loss_rows[p] = logsumexp_c x_c - x_0                                                      (unscaled, as temp_gather_ce_mix_fwd)
+ *   d_w[p]       = (row_scale ? row_scale[p] : inv_rows) * (sum_c softmax_c (a_c - b_c) - (a_0 - b_0))
+ * A candidate listed twice counts twice.  Nothing else has a gradient, so there is no backward call and nothing is saved.  ONE launch
+ * (one wave per row; an online logsumexp per group of 16 lanes, merged in a fixed order), no (P, N) score matrix, no workspace, no
+ * atomics: results are bit-repeatable.  C == 1: the loss and d_w are exactly 0.
+ * Da, Db: multiples of 4 in [4, 512], else TEMP_E_UNSUPPORTED before any launch (outputs untouched).  P == 0 succeeds without a launch;
+ * P < 0, C <= 0, an unknown kind, or a NULL pointer (row_scale excepted) with P > 0: TEMP_E_BADARG.
+ * ---------------------------------------------------------------------------------------------- */
+#define TEMP_FROZEN_DOT 0
+#define TEMP_FROZEN_L1 1
+int temp_frozen_mix_ce(int P, int C, int Da, int Db, int kind, const float* q_a, const float* T_a, const float* q_b, const float* T_b,
+                       const float* w, const int32_t* cand, const float* row_scale /* nullable [P] */, float inv_rows, float* loss_rows,
+                       float* d_w, void* stream);
+
+/* ------------------------------------------------------------------------------------------------
  * Gated TransE loss and scores of the post-aggregation models (models/PostDynamicRGCN.py:261-282, utils/post_evaluation.py:32-69 with
  * utils/scores.py:46-55).  The candidate of row p is the mix of the two all-entity tables with the row's candidate weight,
  *   e[p,k] = mix(w[p], table_a[base[p] + cand[p,k]], table_b[base[p] + cand[p,k]]),    mix(w, a, b) = fmaf(w, a, (1 - w) * b),

@@ -11,5 +11,6 @@ from .rrgcn import GRRGCNLayer, RRGCN, RRGCNLayer  # noqa: F401
 from .birrgcn import BiGRRGCNLayer, BiRRGCN, BiRRGCNLayer  # noqa: F401
 from .gru_cell import GRUCell  # noqa: F401
 from .non_recurrent import Hyte, SimplE  # noqa: F401
+from .aggregator import Aggregator  # noqa: F401
 
 __version__ = "0.1.0"

@@ -123,6 +123,7 @@ class TempAdamTensor(ctypes.Structure):
 
 ASSEMBLE_PIECE = 4096
 SCORE_KINDS = {"distmult": 0, "complex": 1, "transE": 2, "simple": 3}
+FROZEN_KINDS = {"dot": 0, "l1": 1}     # include/temp_amd.h: TEMP_FROZEN_DOT / TEMP_FROZEN_L1 (temp_frozen_mix_ce)
 ADAM_CHUNK = 4096         # include/temp_amd.h: TEMP_ADAM_CHUNK (elements of one tensor that one workgroup of the optimizer passes owns)
 TOPK_MAX = 256             # include/temp_amd.h: TEMP_TOPK_MAX (the longest answer list temp_filtered_topk keeps)
 
@@ -240,6 +241,7 @@ SYMBOLS = {
     "temp_gated_query_bwd": (_I, [_I, _I, _I, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp]),
     "temp_gather_ce_mix_fwd": (_I, [_I, _I, _I, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp]),
     "temp_gather_ce_mix_bwd": (_I, [_I, _I, _I, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, _F, c_vp, c_vp, c_vp, c_vp, c_vp]),
+    "temp_frozen_mix_ce": (_I, [_I, _I, _I, _I, _I, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, _F, c_vp, c_vp, c_vp]),
     "temp_l1_mix_ce_fwd": (_I, [_I, _I, _I, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp]),
     "temp_l1_mix_ce_bwd_q": (_I, [_I, _I, _I, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, _F, c_vp, c_vp, c_vp, c_vp, c_vp]),
     "temp_l1_mix_ce_bwd_table": (_I, [_I, _I, _I, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp]),

@@ -970,6 +970,28 @@ class HipBackend:
         _lib.check(rc, "temp_gather_ce_mix_bwd")
         return d_a, d_b, d_w
 
+    def frozen_mix_ce(self, q_a, T_a, q_b, T_b, w, cand, row_scale=None, inv_rows=None, kind="dot"):
+        """Candidate CE of two frozen streams mixed by w [P] (include/temp_amd.h: temp_frozen_mix_ce) -> (loss_rows [P] unscaled,
+        d_w [P] scaled by row_scale[p], else by inv_rows (None: 1 / P)).  q_a [P, Da] / T_a [rows, Da] and q_b [P, Db] / T_b [rows, Db]
+        may differ in width; cand [P, C] int32 holds rows of both tables, column 0 the truth.  kind "dot" | "l1".  One launch."""
+        q_a, T_a, q_b, T_b, w = _f32(q_a, "q_a"), _f32(T_a, "T_a"), _f32(q_b, "q_b"), _f32(T_b, "T_b"), _f32(w, "w")
+        cand, row_scale = _i32(cand, "cand"), _f32(row_scale, "row_scale")
+        if kind not in _lib.FROZEN_KINDS:
+            raise ValueError("frozen_mix_ce: kind must be 'dot' or 'l1'")
+        P, Da = q_a.shape
+        Db = q_b.shape[1]
+        if (q_b.shape[0] != P or cand.dim() != 2 or cand.shape[0] != P or w.numel() != P or T_a.shape[1] != Da or T_b.shape[1] != Db
+                or T_a.shape[0] != T_b.shape[0] or (row_scale is not None and row_scale.numel() != P)):
+            raise ValueError("frozen_mix_ce: q_a / q_b / w / cand / row_scale must have one row per query, the tables one row count and "
+                             "their query's width")
+        loss = torch.empty(P, dtype=torch.float32, device=q_a.device)
+        d_w = torch.empty(P, dtype=torch.float32, device=q_a.device)
+        inv = 1.0 / max(P, 1) if inv_rows is None else float(inv_rows)
+        rc = self.lib.temp_frozen_mix_ce(P, cand.shape[1], Da, Db, _lib.FROZEN_KINDS[kind], _ptr(q_a), _ptr(T_a), _ptr(q_b), _ptr(T_b), _ptr(w),
+                                         _ptr(cand), _ptr(row_scale), inv, _ptr(loss), _ptr(d_w), _stream())
+        _lib.check(rc, "temp_frozen_mix_ce")
+        return loss, d_w
+
     def linear_tn(self, a, b, out=None):
         """a[M,Ka]^T . b[M,Nb] -> [Ka,Nb] (written into `out`, a contiguous (Ka, Nb) view, when given)."""
         a, b = _f32(a, "a"), _f32(b, "b")

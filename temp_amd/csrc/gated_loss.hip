@@ -9,6 +9,7 @@
 //   k_gather_ce_mix_fwd   one wave per row over the candidate list: logsumexp of the mixed candidate scores
 //   k_gather_ce_mix_bwd*  the mixed-score gradient G written through both weights over the full row (multiplicities counted
 //                         as in k_gather_ce_bwd) and d_w = sum_e G (s_a - s_b) in the same pass
+//   k_frozen_mix_ce       frozen streams (Aggregator): the candidates scored straight from the two tables, loss rows and d_w in one launch
 // No floating-point atomics and no workspace: every output element has one writer and every sum a fixed order.
 #include "common.hpp"
 #include "mix.hpp"
@@ -221,6 +222,141 @@ __global__ void __launch_bounds__(256) k_gather_ce_mix_bwd(int C, int N, const f
   if (threadIdx.x == 0) d_w[p] = acc;
 }
 
+// ---------------------------------------------------------------------------------------------
+// Frozen-ensemble candidate cross-entropy (Aggregator, models/aggregator.py:200-206, 339-342): both streams are frozen, so the only
+// gradient is d loss / d w[p], and it has a closed form in the quantities of the forward:
+//   x_c = mix1(w, a_c, b_c),   loss = logsumexp_c x_c - x_0,   d_w = scale (sum_c softmax_c (a_c - b_c) - (a_0 - b_0)).
+// The candidate scores come straight from the tables (gather-dot / gather-L1): no (P, N) matrix, no saved tensor, no backward launch.
+// One wave per row, four rows per workgroup.  The 64 lanes are four groups of 16: a group scores one candidate at a time, lane l of
+// it holding the float4 slices l, l + 16, ... of the row's two queries in registers (NJ slices: widths up to 64 NJ) and reading the
+// gathered table row as 16 x float4 per step; the 16 partial sums meet in DPP row rotations.  Every group runs its own online
+// (m, s, u), u = sum_c e^(x_c - m) (a_c - b_c), over the candidates k = 4 i + group in ascending i, two candidates per step so that
+// the second row's loads are in flight under the first one's reduction; the four triples are merged once, (0 + 1) + (2 + 3).  No LDS,
+// no atomics: results are bit-repeatable.
+// ---------------------------------------------------------------------------------------------
+template <int CTRL>
+__device__ __forceinline__ float dpp_row(float v) {
+  return __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), CTRL, 0xf, 0xf, false));
+}
+// sum over the 16 lanes of a DPP row (= one lane group), every lane of the row gets the same bits: row_ror 8, 4, 2, 1
+__device__ __forceinline__ float row16_sum(float v) {
+  v += dpp_row<0x128>(v);
+  v += dpp_row<0x124>(v);
+  v += dpp_row<0x122>(v);
+  v += dpp_row<0x121>(v);
+  return v;
+}
+
+struct OnlineMix {
+  float m, s, u;
+  __device__ __forceinline__ void add(float x, float dlt) {
+    if (x > m) {                                        // (m = -inf at the start: e^(-inf) = 0 and s = u = 0)
+      const float r = expf(m - x);
+      s = fmaf(s, r, 1.f);
+      u = fmaf(u, r, dlt);
+      m = x;
+    } else {                                            // (a NaN score lands here and poisons s and u)
+      const float e = expf(x - m);
+      s += e;
+      u = fmaf(e, dlt, u);
+    }
+  }
+};
+
+template <int KIND, int NJ>
+__device__ __forceinline__ float frozen_score(const float4 (&q)[NJ], const float* __restrict__ trow, int d, int l) {
+  float4 t[NJ];
+#pragma unroll
+  for (int j = 0; j < NJ; ++j)
+    if (j * 64 + l * 4 < d) t[j] = ld4(trow + j * 64 + l * 4);
+  float acc = 0.f;
+#pragma unroll
+  for (int j = 0; j < NJ; ++j)
+    if (j * 64 + l * 4 < d) {
+      if (KIND == TEMP_FROZEN_DOT) {
+        acc = fmaf(q[j].x, t[j].x, acc); acc = fmaf(q[j].y, t[j].y, acc); acc = fmaf(q[j].z, t[j].z, acc); acc = fmaf(q[j].w, t[j].w, acc);
+      } else {
+        acc += fabsf(q[j].x - t[j].x); acc += fabsf(q[j].y - t[j].y); acc += fabsf(q[j].z - t[j].z); acc += fabsf(q[j].w - t[j].w);
+      }
+    }
+  acc = row16_sum(acc);
+  return KIND == TEMP_FROZEN_DOT ? acc : -acc;
+}
+
+template <int KIND, int NJ>
+__global__ void __launch_bounds__(256) k_frozen_mix_ce(int P, int C, int Da, int Db, const float* __restrict__ q_a, const float* __restrict__ T_a,
+                                                       const float* __restrict__ q_b, const float* __restrict__ T_b, const float* __restrict__ w,
+                                                       const int32_t* __restrict__ cand, const float* __restrict__ row_scale, float inv_rows,
+                                                       float* __restrict__ loss_rows, float* __restrict__ d_w) {
+  const int p = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
+  if (p >= P) return;
+  const int grp = lane >> 4, l = lane & 15;
+  float4 qa[NJ], qb[NJ];
+#pragma unroll
+  for (int j = 0; j < NJ; ++j) {
+    if (j * 64 + l * 4 < Da) qa[j] = ld4(q_a + (size_t)p * Da + j * 64 + l * 4);
+    if (j * 64 + l * 4 < Db) qb[j] = ld4(q_b + (size_t)p * Db + j * 64 + l * 4);
+  }
+  const int32_t* crow = cand + (size_t)p * C;
+  const float wp = w[p];
+  OnlineMix om{-INFINITY, 0.f, 0.f};
+  float x0 = 0.f, dlt0 = 0.f;                           // the truth's mixed score and a_0 - b_0 (group 0 meets candidate 0 first)
+  for (int k0 = 0; k0 < C; k0 += 64) {
+    const int mine = k0 + lane < C ? crow[k0 + lane] : 0;       // 64 candidate ids per load, handed to the groups by shuffles
+    const int steps = min(16, (C - k0 + 3) >> 2);
+    for (int i = 0; i < steps; i += 2) {
+      const int r0 = __shfl(mine, i * 4 + grp), r1 = __shfl(mine, min(i + 1, 15) * 4 + grp);
+      const bool v0 = k0 + i * 4 + grp < C, v1 = i + 1 < 16 && k0 + (i + 1) * 4 + grp < C;
+      float a0 = 0.f, b0 = 0.f, a1 = 0.f, b1 = 0.f;
+      if (v0) {
+        a0 = frozen_score<KIND, NJ>(qa, T_a + (size_t)r0 * Da, Da, l);
+        b0 = frozen_score<KIND, NJ>(qb, T_b + (size_t)r0 * Db, Db, l);
+      }
+      if (v1) {
+        a1 = frozen_score<KIND, NJ>(qa, T_a + (size_t)r1 * Da, Da, l);
+        b1 = frozen_score<KIND, NJ>(qb, T_b + (size_t)r1 * Db, Db, l);
+      }
+      if (v0) {
+        const float x = mix1(wp, a0, b0);
+        if (k0 == 0 && i == 0) { x0 = x; dlt0 = a0 - b0; }
+        om.add(x, a0 - b0);
+      }
+      if (v1) om.add(mix1(wp, a1, b1), a1 - b1);
+    }
+  }
+  // merge the four groups' triples in a fixed order; a group without candidates (C < 4) carries (-inf, 0, 0) and adds 0
+  float gm[4], gs[4], gu[4];
+#pragma unroll
+  for (int g = 0; g < 4; ++g) { gm[g] = __shfl(om.m, g * 16); gs[g] = __shfl(om.s, g * 16); gu[g] = __shfl(om.u, g * 16); }
+  float M = gm[0];                                      // (group 0 always has candidate 0; a NaN there stays: fmaxf is not used on it)
+#pragma unroll
+  for (int g = 1; g < 4; ++g) M = gm[g] > M ? gm[g] : M;
+  float e[4];
+#pragma unroll
+  for (int g = 0; g < 4; ++g) e[g] = expf(gm[g] - M);
+  const float S = (gs[0] * e[0] + gs[1] * e[1]) + (gs[2] * e[2] + gs[3] * e[3]);
+  const float U = (gu[0] * e[0] + gu[1] * e[1]) + (gu[2] * e[2] + gu[3] * e[3]);
+  x0 = __shfl(x0, 0);
+  dlt0 = __shfl(dlt0, 0);
+  if (lane == 0) {
+    loss_rows[p] = (M + logf(S)) - x0;
+    d_w[p] = (row_scale ? row_scale[p] : inv_rows) * (U / S - dlt0);
+  }
+}
+
+template <int KIND>
+void launch_frozen_mix_ce(int nj, int P, int C, int Da, int Db, const float* q_a, const float* T_a, const float* q_b, const float* T_b, const float* w,
+                          const int32_t* cand, const float* row_scale, float inv_rows, float* loss_rows, float* d_w, hipStream_t st) {
+#define TEMP_FROZEN_CASE(NJ)                                                                                                             \
+  TEMP_LAUNCH(K_FROZEN_MIX_CE, (k_frozen_mix_ce<KIND, NJ>), dim3(ceil_div(P, 4)), dim3(256), 0, st, P, C, Da, Db, q_a, T_a, q_b, T_b, w, cand, \
+              row_scale, inv_rows, loss_rows, d_w)
+  if (nj <= 1) TEMP_FROZEN_CASE(1);
+  else if (nj <= 2) TEMP_FROZEN_CASE(2);
+  else if (nj <= 4) TEMP_FROZEN_CASE(4);
+  else TEMP_FROZEN_CASE(8);
+#undef TEMP_FROZEN_CASE
+}
+
 int gated_query_args(int P, int d, int kind, const void* A, const void* ia, const void* B, const void* ib, const void* w, const void* rel,
                      const void* rel_idx, const void* is_tail) {
   if (P < 0 || d <= 0 || (kind != TEMP_SCORE_DISTMULT && kind != TEMP_SCORE_COMPLEX && kind != TEMP_SCORE_TRANSE)) return TEMP_E_BADARG;
@@ -286,6 +422,20 @@ int temp_gather_ce_mix_bwd(int P, int C, int N, const float* s_a, const float* s
   }
   TEMP_LAUNCH(K_GATHER_CE_MIX, k_gather_ce_mix_bwd, dim3(P), dim3(256), lds, (hipStream_t)stream, C, N, s_a, s_b, w, cand, lse_rows, scale, inv_rows,
               row_scale, d_s_a, d_s_b, d_w);
+  return launch_status();
+}
+
+int temp_frozen_mix_ce(int P, int C, int Da, int Db, int kind, const float* q_a, const float* T_a, const float* q_b, const float* T_b,
+                       const float* w, const int32_t* cand, const float* row_scale, float inv_rows, float* loss_rows, float* d_w, void* stream) {
+  if (P < 0 || C <= 0 || Da <= 0 || Db <= 0 || (kind != TEMP_FROZEN_DOT && kind != TEMP_FROZEN_L1)) return TEMP_E_BADARG;
+  if (Da % 4 || Db % 4 || Da > 512 || Db > 512) return TEMP_E_UNSUPPORTED;
+  if (P == 0) return TEMP_OK;
+  if (!q_a || !T_a || !q_b || !T_b || !w || !cand || !loss_rows || !d_w) return TEMP_E_BADARG;
+  const int nj = ceil_div(Da > Db ? Da : Db, 64);
+  if (kind == TEMP_FROZEN_DOT)
+    launch_frozen_mix_ce<TEMP_FROZEN_DOT>(nj, P, C, Da, Db, q_a, T_a, q_b, T_b, w, cand, row_scale, inv_rows, loss_rows, d_w, (hipStream_t)stream);
+  else
+    launch_frozen_mix_ce<TEMP_FROZEN_L1>(nj, P, C, Da, Db, q_a, T_a, q_b, T_b, w, cand, row_scale, inv_rows, loss_rows, d_w, (hipStream_t)stream);
   return launch_status();
 }
 

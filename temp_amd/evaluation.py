@@ -319,10 +319,10 @@ class _MixedRankFilter(EvaluationFilter):
                         else self.calc_score(all_embeds, r[a:b], known[a:b], mode="head"))
         return _pad4(torch.cat(rows)) if padded else torch.cat(rows)
 
-    def _mixed_topk(self, known_loc, known_rec, r, all_loc, all_rec, w, mode, k, ptr, ids, keep, panel):
+    def _mixed_topk(self, known_loc, known_rec, r, all_loc, all_rec, w, mode, k, ptr, ids, keep, panel, r_rec=None):
         """The selection over mix(w, score(known_loc, all_loc), score(known_rec, all_rec)), the two score matrices from the routes
         of _score_matrix panel by panel.  Two matrices are alive at once: all N columns in one go while 2 Q ld 4 bytes stay at or
-        under TOPK_PANEL_BYTES, else panels with the carry."""
+        under TOPK_PANEL_BYTES, else panels with the carry.  r_rec: the second stream's own relation rows (two models), else `r`."""
         Q, num_ent = known_loc.shape[0], all_loc.shape[0]
         panel = _topk_panel(panel, Q, num_ent, 2)
         select = _select_mixed(get_backend(), k)
@@ -331,7 +331,7 @@ class _MixedRankFilter(EvaluationFilter):
         for c0 in range(0, num_ent, panel):
             c1 = min(num_ent, c0 + panel)
             s_loc = self._score_matrix(known_loc, r, all_loc[c0:c1], mode, 100, padded=True)
-            s_rec = self._score_matrix(known_rec, r, all_rec[c0:c1], mode, 100, padded=True)
+            s_rec = self._score_matrix(known_rec, r if r_rec is None else r_rec, all_rec[c0:c1], mode, 100, padded=True)
             carry = select(s_loc, s_rec, w, k, ptr, ids, keep, col0=c0, n=c1 - c0, carry=carry)
         return carry[1], carry[0].float()
 
@@ -343,30 +343,35 @@ class _MixedRankFilter(EvaluationFilter):
 class PostEnsembleEvaluationFilter(_MixedRankFilter):
     """utils/post_evaluation.py:63-134: SCORE-level ensemble.  score = w * score(local) + (1 - w) * score(temporal), per triple
     (the reference masks each score matrix before mixing; both masked values are -10e6, so filtering after the mix is the
-    same).  As in the reference, the object-corruption ranks use `weight_subject`, the subject-corruption ranks `weight_object`."""
+    same).  As in the reference, the object-corruption ranks use `weight_subject`, the subject-corruption ranks `weight_object`.
+    rel_enc_temporal: the temporal stream's own relation table when the streams are two models (Aggregator,
+    models/aggregator.py:259-296; the two tables may differ in width); None, the default, scores both streams with `rel_enc_mean`."""
 
     def calc_metrics_single_graph(self, ent_embed_local, ent_embed_temporal, rel_enc_mean, all_embeds_g_local, all_embeds_g_temporal,
-                                  weight_subject, weight_object, samples, graph, time, eval_bz=100):
+                                  weight_subject, weight_object, samples, graph, time, eval_bz=100, rel_enc_temporal=None):
         with torch.no_grad():
             dev, num_ent, time, P = all_embeds_g_local.device, all_embeds_g_local.shape[0], int(time), samples.shape[0]
             if P == 0:
                 return torch.zeros(0, dtype=torch.int64, device=dev)
             r = rel_enc_mean[samples[:, 1]]
+            r_tmp = r if rel_enc_temporal is None else rel_enc_temporal[samples[:, 1]]
             out = {}
             for mode, w in (("head", weight_object), ("tail", weight_subject)):
                 sel = samples[:, 0] if mode == "tail" else samples[:, 2]
                 s_loc = self._score_matrix(ent_embed_local[sel], r, all_embeds_g_local, mode, eval_bz)
-                s_tmp = self._score_matrix(ent_embed_temporal[sel], r, all_embeds_g_temporal, mode, eval_bz)
+                s_tmp = self._score_matrix(ent_embed_temporal[sel], r_tmp, all_embeds_g_temporal, mode, eval_bz)
                 wc = _w_col(w, P, s_loc)
                 out[mode] = self._rank(wc * s_loc + (1 - wc) * s_tmp, mode, samples, graph, time, num_ent, dev)
             return torch.cat([out["head"], out["tail"]])
 
-    def topk_single_graph(self, all_loc, all_rec, rel_enc_means, known, rel, w, mode, time, k, filtered=True, keep=None, panel=None):
+    def topk_single_graph(self, all_loc, all_rec, rel_enc_means, known, rel, w, mode, time, k, filtered=True, keep=None, panel=None,
+                          rel_enc_temporal=None):
         """EvaluationFilter.topk_single_graph for the score-level ensemble: the k best answers under
         w[i] * score(all_loc[known[i]], rel[i], all_loc[e]) + (1 - w[i]) * score(all_rec[known[i]], rel[i], all_rec[e]),
         w [Q] the queries' mixing weights.  all_loc / all_rec [N, D] are the local and the temporal all-entity table; `known` holds
         GLOBAL ids, and the filter lists, `keep`, `panel` and the returned (ids [Q, k] int64, scores [Q, k] float32) are the base
-        class's.  The mix is formed inside the selection (`temp_filtered_topk_mix`): the mixed [Q, N] matrix is never written."""
+        class's.  The mix is formed inside the selection (`temp_filtered_topk_mix`): the mixed [Q, N] matrix is never written.
+        rel_enc_temporal: as in calc_metrics_single_graph (the second term then uses rel_enc_temporal[rel[i]])."""
         with torch.no_grad():
             dev, num_ent = all_loc.device, all_loc.shape[0]
             known, rel, ptr, ids, keep = self._topk_queries(dev, num_ent, known, rel, mode, time, filtered, keep)
@@ -375,7 +380,8 @@ class PostEnsembleEvaluationFilter(_MixedRankFilter):
             w = torch.as_tensor(w, dtype=torch.float32, device=dev).reshape(-1)
             if w.shape[0] != known.shape[0]:
                 raise ValueError("topk_single_graph: w must have one entry per query")
-            return self._mixed_topk(all_loc[known], all_rec[known], rel_enc_means[rel], all_loc, all_rec, w, mode, k, ptr, ids, keep, panel)
+            return self._mixed_topk(all_loc[known], all_rec[known], rel_enc_means[rel], all_loc, all_rec, w, mode, k, ptr, ids, keep, panel,
+                                    None if rel_enc_temporal is None else rel_enc_temporal[rel])
 
 
 class PostEvaluationFilter(_MixedRankFilter):

@@ -19,6 +19,9 @@ _L1Scorer: transE, distances to the candidates alone).  The backend calls of eve
     both     gated_query_fwd                                     | ... gated_query_bwd, segment_sum_rows x 3 (known_a, known, rel)
     GEMM     linear_multi x 2 (one q), gather_ce_mix_fwd         | gather_ce_mix_bwd, linear_multi x 2, linear_tn_multi x 2
     L1       l1_mix_ce_fwd                                       | l1_mix_ce_bwd_q, l1_mix_ce_bwd_table
+  _FrozenMixCEFn                      score-level ensemble of two FROZEN models (models/aggregator.py:185-208): two relation tables,
+    both     bilinear_query_fwd x 2, frozen_mix_ce               | (nothing: d_w came out of the forward launch)
+             (no (rows, N) matrix; frozen_mix_ce_rows in torch on a backend without the kernel)
 
 (linear_tn_multi: one linear_tn per live window on a backend without it; gated_query_* / gather_ce_mix_*: through bilinear_query_* /
 gather_ce_* and torch on a backend without them -- the CPU test backend.)  `big` is the (B * N, D) stack of the windows' all-entity
@@ -460,6 +463,105 @@ def gated_link_prediction(loc, rec, rel, all_loc, all_rec, triplets, neg_tail, n
     w_known = torch.cat([w_oqs.reshape(-1, 1), w_sqo.reshape(-1, 1)])
     w_cand = torch.cat([w_oqo.reshape(-1, 1), w_sqs.reshape(-1, 1)])
     return batched_gated_link_prediction(loc, rec, rel, all_loc, all_rec, w_known, w_cand, kind, inp)
+
+
+# -- two FROZEN streams: the only gradient is the mixing weight's ---------------------------------------------------------------------
+FROZEN_KIND = {"distmult": "dot", "complex": "dot", "transE": "l1"}       # scorer -> the candidate score of frozen_mix_ce
+
+
+def frozen_mix_ce_rows(q_a, T_a, q_b, T_b, w, cand, kind="dot", chunk=1 << 22):
+    """The formula of temp_frozen_mix_ce in plain torch, differentiable and in the dtype of its inputs -> loss_rows [P]:
+    a = score(q_a, T_a[cand]) ("dot": the inner product, "l1": -|q - row|_1), b likewise, CE(w a + (1 - w) b, label 0) per row.  The
+    candidate rows are gathered `chunk` elements of (rows, C, D) at a time.  The route of a backend without `frozen_mix_ce` and the
+    reference of the kernel's tests (in float64, with autograd for d_w)."""
+    if kind not in ("dot", "l1"):
+        raise ValueError("frozen_mix_ce_rows: kind must be 'dot' or 'l1'")
+    P, C = cand.shape
+    idx = cand.long()
+    wc = w.reshape(-1, 1)
+    out = []
+    step = max(1, chunk // max(1, C * max(T_a.shape[1], T_b.shape[1])))
+    for p0 in range(0, P, step):
+        sl = slice(p0, p0 + step)
+        ss = []
+        for q, T in ((q_a, T_a), (q_b, T_b)):
+            rows = T[idx[sl]]                                                        # (rows, C, D)
+            qs = q[sl].unsqueeze(1)
+            ss.append((qs * rows).sum(dim=-1) if kind == "dot" else -(qs - rows).abs().sum(dim=-1))
+        x = wc[sl] * ss[0] + (1 - wc[sl]) * ss[1]
+        out.append(torch.nn.functional.cross_entropy(x, torch.zeros(x.shape[0], dtype=torch.int64, device=x.device), reduction="none"))
+    return torch.cat(out) if out else w.new_zeros(0)
+
+
+def frozen_mix_ce(be, q_a, T_a, q_b, T_b, w, cand, row_scale=None, inv_rows=None, kind="dot"):
+    """-> (loss_rows [P] unscaled, d_w [P] = scale_p * d loss_rows[p] / d w[p]): the backend's one-launch kernel, or -- on a backend
+    without `frozen_mix_ce`, the CPU test backend -- frozen_mix_ce_rows and its autograd."""
+    if hasattr(be, "frozen_mix_ce"):
+        return be.frozen_mix_ce(q_a, T_a, q_b, T_b, w, cand, row_scale, inv_rows, kind)
+    scale = row_scale if row_scale is not None else (1.0 / max(cand.shape[0], 1) if inv_rows is None else float(inv_rows))
+    with torch.enable_grad():
+        wv = w.detach().reshape(-1).clone().requires_grad_(True)
+        loss_rows = frozen_mix_ce_rows(q_a.detach(), T_a.detach(), q_b.detach(), T_b.detach(), wv, cand, kind)
+        d_w, = torch.autograd.grad((loss_rows * scale).sum(), wv)
+    return loss_rows.detach(), d_w
+
+
+def _frozen_cand(inp, n_ents):
+    """The candidate lists of the loss inputs as rows of the (B * n_ents, D) stacks: cand + window * n_ents, kept in the dict (which
+    callers cache per sample set) for the candidate tensor and the table size it was built from."""
+    c = inp.get("_frozen_cand")
+    if c is None or c[0] is not inp["cand"] or c[1] != n_ents:
+        c = inp["_frozen_cand"] = (inp["cand"], n_ents, (inp["cand"] + (inp["window"] * n_ents).view(-1, 1)).contiguous())
+    return c[2]
+
+
+def _frozen_query(be, kind, rows, rel, inp):
+    """The folded query of one frozen stream: the bilinear fold through the backend; the translation query known + r (tail) /
+    known - r (head) as the tensor expression it is bit-equal to (one IEEE add or subtract), so that a backend without the L1
+    kernels serves TransE too."""
+    if kind != "transE":
+        return _query_fwd(be, kind, rows, rel, inp)
+    known, r = be.gather_rows(rows, inp["known"]), be.gather_rows(rel, inp["rel"])
+    return torch.where(inp["is_tail"].view(-1, 1) != 0, known + r, known - r).contiguous()
+
+
+class _FrozenMixCEFn(torch.autograd.Function):
+    """The ensemble loss of two FROZEN streams (Aggregator, models/aggregator.py:185-208) over ALL windows as one node:
+        q_x  = fold(rows_x[known], rel_x[rel])        per stream x in (a = local, b = temporal), its own relation table and width
+        loss = sum_rows w_row * CE(mix(w, score(q_a, big_a[c]), score(q_b, big_b[c])) over the row's candidates c, label 0)
+    Forward: bilinear_query_fwd x 2, frozen_mix_ce (ONE launch: the loss rows and d loss / d w together).  Backward: grad_out * d_w,
+    no backend call -- nothing else has a gradient."""
+
+    @staticmethod
+    def forward(ctx, rows_a, rel_a, big_a, rows_b, rel_b, big_b, w, kind, inp):
+        be = get_backend()
+        q_a = _frozen_query(be, kind, rows_a, rel_a, inp)
+        q_b = _frozen_query(be, kind, rows_b, rel_b, inp)
+        cand = _frozen_cand(inp, big_a.shape[0] // len(inp["splits"]))
+        loss_rows, d_w = frozen_mix_ce(be, q_a, big_a, q_b, big_b, w.reshape(-1), cand, inp["weights"], None, FROZEN_KIND[kind])
+        ctx.save_for_backward(d_w)
+        ctx.w_shape = w.shape
+        return (loss_rows * inp["weights"]).sum()
+
+    @staticmethod
+    def backward(ctx, d_loss):
+        d_w, = ctx.saved_tensors
+        return None, None, None, None, None, None, (d_loss * d_w).reshape(ctx.w_shape), None, None
+
+
+def frozen_ensemble_link_prediction(rows_a, rel_a, big_a, rows_b, rel_b, big_b, w, kind, inputs):
+    """sum over windows of the ensemble CE_tail + CE_head of two frozen models (see _FrozenMixCEFn).  rows_x: the concatenation of
+    the per-graph target rows of stream x, rel_x its relation table, big_x the (B * N_ents, D_x) stack of its all-entity matrices
+    (the two streams may differ in width); `w` (rows, 1) = weight of stream a of every stacked query row (per window: [tail rows:
+    weight_object ; head rows: weight_subject]); kind 'distmult' | 'complex' | 'transE'; `inputs` = TKG_Module.loss_inputs(...).
+    None of the six row / table arguments may require grad: the node returns no gradient for them."""
+    if kind not in FROZEN_KIND:
+        raise ValueError("frozen_ensemble_link_prediction: no frozen node for the scorer %r" % (kind,))
+    for name, t in (("rows_a", rows_a), ("rel_a", rel_a), ("big_a", big_a), ("rows_b", rows_b), ("rel_b", rel_b), ("big_b", big_b)):
+        assert not t.requires_grad, "frozen_ensemble_link_prediction: %s requires grad, but both streams are frozen" % name
+    w = w.reshape(-1, 1).to(rows_a.dtype).contiguous()
+    return _FrozenMixCEFn.apply(rows_a.contiguous(), rel_a.contiguous(), big_a.contiguous(), rows_b.contiguous(), rel_b.contiguous(),
+                                big_b.contiguous(), w, kind, inputs)
 
 
 # -- the unbatched nodes: one target graph, the query rows given -------------------------------------------------------------------

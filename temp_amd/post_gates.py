@@ -61,8 +61,13 @@ class _FrequencyGateMixin:
 
         def select(t, tables, known, rel, sel):
             gates = self._query_gates(t, known, rel, mode) if weights is None else tuple(w[sel] for w in weights)
-            return ranker.topk_single_graph(*tables, self.rel_embeds, known, rel, *gates, mode, t, k, filtered)
+            return ranker.topk_single_graph(*tables, self.rel_embeds, known, rel, *gates, mode, t, k, filtered, **self._topk_relation_kw())
         return self.select_per_timestamp(q, k, self.all_entity_table_pairs, select)
+
+    def _topk_relation_kw(self):
+        """Keyword arguments of the ranker's topk_single_graph beyond self.rel_embeds: a second relation table where the two streams
+        are two models (Aggregator)."""
+        return {}
 
     def frequency_tables(self):
         ft = getattr(self, "_freq_tables", None)

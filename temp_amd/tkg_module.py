@@ -102,7 +102,11 @@ class TKG_Module(nn.Module):
         if max_norm is None:
             max_norm = getattr(self.args, "gradient_clip_val", 1.0)
         max_norm = float(max_norm) if max_norm is not None and float(max_norm) > 0.0 else None
-        return ClippedAdam(self.parameters(), lr=self.args.lr, weight_decay=0.0001, max_norm=max_norm)
+        return ClippedAdam(self.optimizer_parameters(), lr=self.args.lr, weight_decay=0.0001, max_norm=max_norm)
+
+    def optimizer_parameters(self):
+        """The parameters configure_clipped_optimizer() trains: all of them, unless a class freezes some (Aggregator)."""
+        return self.parameters()
 
     # -- loss (models/TKG_Module.py:202-221) ----------------------------------------------------------
     def train_link_prediction(self, ent_embed, triplets, neg_samples, labels, all_embeds_g, corrupt_tail=True, rel=None):
