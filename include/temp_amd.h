@@ -816,6 +816,40 @@ int temp_gather_ce_bwd(int P, int C, int N, const float* scores, const int32_t* 
                        float inv_rows, const float* row_scale /* nullable [P]: per-row weight instead of inv_rows */, float* d_scores, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * All-entity ("1-vs-all") link-prediction loss: softmax cross-entropy of the true entity against EVERY entity outside the row's
+ * known-true list -- the limit of temp_corrupt_sample + temp_gather_ce_* as negative_rate grows: each admissible entity exactly once,
+ * no candidate matrix, no draws.  (No counterpart in the reference, which only samples.)
+ * scores [P, ld] = P query rows scored against the N entities col0 .. col0 + N - 1 (column j < N is entity col0 + j; the producers of
+ * temp_gather_ce_fwd).  The filter list of row p is ids[lo[p] .. hi[p]): GLOBAL entity ids, unique and ascending -- the arrays
+ * temp_corrupt_sample takes, as they are (no CSR rebuild); lo == NULL (then hi == NULL): nothing is filtered.
+ *   entity e is ADMISSIBLE for row p  <=>  e == truth[p]  or  e is not in the row's list
+ * A filtered entity never enters the sum (it is excluded, not subtracted afterwards: the known-true entities are the ones with the
+ * largest scores, and one of them may hold the row's maximum).
+ *   fwd: an online softmax over the admissible columns of this panel.  carry = 0 starts the row state (run_max, run_sum,
+ *        truth_score) [P each] fresh: (max, sum_j exp(s_j - max)) over the panel's admissible columns, (-inf, 0) when there is none,
+ *        truth_score = scores[p, truth[p] - col0] when the truth lies in the panel, else 0.  carry = 1 merges into the state earlier
+ *        calls left over DISJOINT entity ranges; a panel without an admissible column for a row leaves that row's state unchanged,
+ *        bit for bit.  After every call  lse_rows = run_max + log(run_sum),  loss_rows = lse_rows - truth_score  (unscaled; meaningful
+ *        once every panel has been seen; -inf, never NaN, while nothing admissible has).  Over panels the result equals ONE call over
+ *        the union up to rounding.
+ *   bwd: d_scores[p,j] = scale[0] * (row_scale ? row_scale[p] : inv_rows) * (exp(scores[p,j] - lse_rows[p]) - [col0 + j == truth[p]])
+ *        for admissible columns, exactly 0 for filtered columns and for the pad columns N <= j < ld; a row whose factor is 0 is
+ *        exactly 0.  d_scores [P, ld] is fully written.  `scale` is a DEVICE float, as in temp_gather_ce_bwd.
+ * The row is STREAMED (float4 loads, 256 columns per wave and step), the list walked beside it 64 entries at a time in the wave's
+ * registers: no LDS ceiling on N (temp_gather_ce_bwd refuses N > 40 704), any list length.  Dispatch, both calls: N <= 1024 one WAVE
+ * per row, four rows per workgroup (no barrier); above that one 256-thread workgroup per row.
+ * P >= 0, N > 0, ld >= N, col0 >= 0, col0 + ld + 256 < 2^31, carry in {0, 1} (else TEMP_E_BADARG); ld % 4 == 0 and scores (d_scores)
+ * 16-byte aligned (else TEMP_E_UNSUPPORTED).  P == 0 succeeds without a launch.  No workspace, no floating-point atomics, one
+ * reduction order per launch shape: bit-repeatable.  +inf and NaN scores are unspecified.
+ * ---------------------------------------------------------------------------------------------- */
+int temp_filtered_ce_fwd(int P, int N, int ld, int col0, const float* scores, const int32_t* truth, const int32_t* lo, const int32_t* hi,
+                         const int32_t* ids, int carry, float* run_max, float* run_sum, float* truth_score, float* lse_rows, float* loss_rows,
+                         void* stream);
+int temp_filtered_ce_bwd(int P, int N, int ld, int col0, const float* scores, const int32_t* truth, const int32_t* lo, const int32_t* hi,
+                         const int32_t* ids, const float* lse_rows, const float* scale, float inv_rows,
+                         const float* row_scale /* nullable [P] */, float* d_scores, void* stream);
+
+/* ------------------------------------------------------------------------------------------------
  * Folded query of the scorers, row gathers fused in (utils/scores.py:4-12 distmult, :26-44 complex, :46-55 transE;
  * the s / r / o row selections of train_link_prediction, models/TKG_Module.py:202-213):
  *   k = ent_rows[known_idx[p]], r = rel[rel_idx[p]]          (both [*, d] row-major, d % 4 == 0; complex: d % 8 == 0)

@@ -248,6 +248,8 @@ SYMBOLS = {
     "temp_l1_mix_scores": (_I, [_I, _I, _I, c_vp, c_vp, c_vp, c_vp, _I, c_vp, c_vp]),
     "temp_assemble_views": (_I, [_I, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp]),
     "temp_subsample_views": (_I, [_I, ctypes.POINTER(TempSubsampleJob), c_vp]),
+    "temp_filtered_ce_fwd": (_I, [_I, _I, _I, _I, c_vp, c_vp, c_vp, c_vp, c_vp, _I, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp]),
+    "temp_filtered_ce_bwd": (_I, [_I, _I, _I, _I, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, _F, c_vp, c_vp, c_vp]),
     "temp_corrupt_sample": (_I, [_I, _I, _I, ctypes.c_uint64, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp]),
     "temp_filtered_rank": (_I, [_I, _I, _I, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp]),
     "temp_filtered_topk": (_I, [_I, _I, _I, _I, _I, c_vp, c_vp, c_vp, c_vp, _I, c_vp, c_vp, c_vp]),

@@ -69,6 +69,7 @@ class Aggregator(_FrequencyGateMixin, TKG_Module):
     """models/aggregator.py:22-361.  state_dict keys, in order: temporal_model.*, spatial_model.*, subject_linear.{0,2}.*, object_linear.{0,2}.*."""
     _evaluater = "PostEnsembleEvaluationFilter"
     _gate_count = 1
+    _all_entity_loss_refusal = "its loss mixes the scores of two frozen models' tables; the all-entity node takes one table"
 
     def __init__(self, args, num_ents, num_rels, graph_dict_train, graph_dict_val, graph_dict_test, spatial_model=None, temporal_model=None):
         super().__init__(args, num_ents, num_rels, graph_dict_train, graph_dict_val, graph_dict_test)

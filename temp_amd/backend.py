@@ -1044,6 +1044,56 @@ class HipBackend:
         _lib.check(rc, "temp_gather_ce_bwd")
         return d
 
+    @staticmethod
+    def _filtered_ce_args(what, scores, truth, lo, hi, ids, n):
+        """The checks both all-entity CE entry points share -> (scores, P, n, ld, truth, lo, hi, ids)."""
+        scores, truth = _f32(scores, "scores"), _i32(truth, "truth")
+        if scores.dim() != 2 or truth.shape[0] != scores.shape[0]:
+            raise ValueError("%s: scores must be [P, ld] with one truth per row" % what)
+        P, ld = scores.shape
+        n = ld if n is None else int(n)
+        if not 0 < n <= ld:
+            raise ValueError("%s: n must lie in (0, row length]" % what)
+        if ld % 4:
+            raise ValueError("%s: the score row length must be a multiple of 4" % what)
+        if (lo is None) != (hi is None):
+            raise ValueError("%s: lo and hi come together" % what)
+        if lo is not None:
+            lo, hi, ids = _i32(lo, "lo"), _i32(hi, "hi"), _i32(ids, "ids")
+            if lo.shape[0] != P or hi.shape[0] != P:
+                raise ValueError("%s: lo / hi must have one entry per row" % what)
+        return scores, P, n, ld, truth, lo, hi, (ids if lo is not None else None)
+
+    def filtered_ce_fwd(self, scores, truth, lo=None, hi=None, ids=None, col0=0, n=None, carry=None):
+        """All-entity cross-entropy of the rows of scores [P, ld] under each row's known-true filter (include/temp_amd.h:
+        temp_filtered_ce_fwd) -> (loss_rows [P] unscaled, lse_rows [P], state).  Column j < n (default: every column) is entity
+        col0 + j.  `carry` = the state an earlier call returned over OTHER entities: the result is then that of both ranges; the
+        state is updated in place and returned again."""
+        scores, P, n, ld, truth, lo, hi, ids = self._filtered_ce_args("filtered_ce_fwd", scores, truth, lo, hi, ids, n)
+        state = carry if carry is not None else torch.empty(3, P, dtype=torch.float32, device=scores.device)
+        if state.shape != (3, P) or state.dtype != torch.float32 or not state.is_contiguous() or state.device != scores.device:
+            raise ValueError("filtered_ce_fwd: carry must be the state of an earlier call over the same rows")
+        out = torch.empty(2, P, dtype=torch.float32, device=scores.device)
+        rc = self.lib.temp_filtered_ce_fwd(P, n, ld, int(col0), _ptr(scores), _ptr(truth), _ptr(lo), _ptr(hi), _ptr(ids), int(carry is not None),
+                                           _ptr(state[0]), _ptr(state[1]), _ptr(state[2]), _ptr(out[1]), _ptr(out[0]), _stream())
+        _lib.check(rc, "temp_filtered_ce_fwd")
+        return out[0], out[1], state
+
+    def filtered_ce_bwd(self, scores, truth, lo, hi, ids, lse, scale, inv_rows, row_scale=None, col0=0, n=None, out=None):
+        """-> d_scores [P, ld] of the all-entity cross-entropy (include/temp_amd.h: temp_filtered_ce_bwd), fully written: 0 at the
+        filtered columns and at the pad columns n <= j < ld.  `out`: a contiguous [P, ld] buffer to write instead of a new one."""
+        scores, P, n, ld, truth, lo, hi, ids = self._filtered_ce_args("filtered_ce_bwd", scores, truth, lo, hi, ids, n)
+        lse, scale, row_scale = _f32(lse, "lse"), _f32(scale, "scale"), _f32(row_scale, "row_scale")
+        if lse.shape[0] != P or (row_scale is not None and row_scale.shape[0] != P):
+            raise ValueError("filtered_ce_bwd: lse and row_scale must have one entry per row")
+        d = torch.empty_like(scores) if out is None else out
+        if d.shape != scores.shape or not d.is_contiguous() or d.dtype != torch.float32 or d.device != scores.device:
+            raise ValueError("filtered_ce_bwd: out must be a contiguous float32 matrix of the shape of scores")
+        rc = self.lib.temp_filtered_ce_bwd(P, n, ld, int(col0), _ptr(scores), _ptr(truth), _ptr(lo), _ptr(hi), _ptr(ids), _ptr(lse), _ptr(scale),
+                                           float(inv_rows), _ptr(row_scale), _ptr(d), _stream())
+        _lib.check(rc, "temp_filtered_ce_bwd")
+        return d
+
     def assemble_views(self, piece_desc, piece_start, descs, table, out):
         """One launch of temp_assemble_views; all arguments are device tensors (descs: raw bytes of TempCopyDesc records)."""
         rc = self.lib.temp_assemble_views(int(piece_desc.shape[0]), _ptr(piece_desc), _ptr(piece_start), _ptr(descs), _ptr(table), _ptr(out), _stream())

@@ -1,6 +1,6 @@
 // Loss and evaluation kernels: candidate-list cross-entropy, the folded query of the scorers (TransE's translation query among
-// them; its L1 candidate loss and dense scores are in l1_loss.hip), filtered negative sampling and the filtered rank, with their
-// entry points.
+// them; its L1 candidate loss and dense scores are in l1_loss.hip), filtered negative sampling, the filtered rank and the all-entity
+// cross-entropy under the same filter, with their entry points.
 #include "common.hpp"
 #include "reduce.hpp"
 
@@ -322,6 +322,138 @@ __global__ void __launch_bounds__(256) k_filtered_rank(int N, int ld, const floa
   if (threadIdx.x == 0) ranks[p] = red[0] + red[1] + red[2] + red[3] + 1;
 }
 
+// ---------------------------------------------------------------------------------------------
+// All-entity cross-entropy under the row's known-true filter (include/temp_amd.h: temp_filtered_ce_*): every admissible entity
+// of the row exactly once -- the truth, and whatever is not in ids[lo[p] .. hi[p]).  The score row is STREAMED: a wave takes 256
+// consecutive columns per step (one float4 per lane), so nothing is counted in LDS and N has no ceiling.
+// Dispatch (both kernels): N <= FCE_WAVE_MAX_N (1024) -- one WAVE per row, four rows per workgroup, steps of 256 columns, no
+// barrier; above it one 256-thread workgroup per row, wave w on the steps w, w + 4, ... and one cross-wave reduction at the end.
+// The filter EXCLUDES: a listed entity gets the weight 0 before anything is summed (sum-then-subtract would cancel -- the listed
+// entities are the best-scored ones).  The ascending list is walked beside the ascending column steps, 64 entries at a time in
+// the wave's registers (one entry per lane): the entries inside the step's 256-entity window are found by one ballot, and each
+// is handed to the lane that owns its column.  A list of <= 64 entries (all but hub rows) is loaded once; a hub row's list is
+// reloaded 64 further entries at a time as the steps pass it.  Every wave of a workgroup walks the list on its own.
+// ---------------------------------------------------------------------------------------------
+#define FCE_WAVE_MAX_N 1024
+#define FCE_NO_ENTRY 0x7fffffff
+
+struct RowFilter {
+  const int32_t* ids;
+  int pos, end;                 // the 64 entries in the registers are ids[pos .. pos + 64) (clipped to end)
+  int v;                        // this lane's entry, FCE_NO_ENTRY past the end
+};
+__device__ __forceinline__ void filter_load(RowFilter& f, int lane) { f.v = f.pos + lane < f.end ? f.ids[f.pos + lane] : FCE_NO_ENTRY; }
+__device__ __forceinline__ RowFilter filter_open(const int32_t* __restrict__ lo, const int32_t* __restrict__ hi, const int32_t* __restrict__ ids, int p, int lane) {
+  RowFilter f;
+  f.ids = ids;
+  f.pos = lo ? lo[p] : 0;
+  f.end = lo ? hi[p] : 0;
+  filter_load(f, lane);
+  return f;
+}
+// Bit u set <=> entity w0 + 4 * lane + u is in the list; w0 = the first entity of the wave's step.  Called by all 64 lanes, with
+// w0 ascending from call to call.
+__device__ __forceinline__ unsigned filter_mask(RowFilter& f, int w0, int lane) {
+  unsigned mask = 0;
+  for (;;) {
+    unsigned long long hit = __ballot(f.v >= w0 && f.v < w0 + 256);
+    while (hit) {
+      const int i = __builtin_ctzll(hit);
+      hit &= hit - 1;
+      const int t = __shfl(f.v, i) - w0;
+      if ((t >> 2) == lane) mask |= 1u << (t & 3);
+    }
+    if (f.pos + 64 >= f.end || __shfl(f.v, 63) >= w0 + 256) break;       // the list, or this window, ends inside these 64 entries
+    f.pos += 64;
+    filter_load(f, lane);
+  }
+  return mask;
+}
+// -> the lane's four scores with everything inadmissible (listed and not the truth, or a pad column j >= N) replaced by `fill`
+__device__ __forceinline__ float4 filter_select(float4 x, unsigned mask, int e0, int truth, int left, float fill) {
+  const unsigned t = (unsigned)(truth - e0);
+  if (t < 4u) mask &= ~(1u << t);
+  if (left < 4) mask |= 0xfu << left;                                     // left >= 1 columns of the four lie below N
+  return make_float4((mask & 1u) ? fill : x.x, (mask & 2u) ? fill : x.y, (mask & 4u) ? fill : x.z, (mask & 8u) ? fill : x.w);
+}
+
+template <bool GROUP>
+__global__ void __launch_bounds__(256) k_filtered_ce_fwd(int P, int N, int ld, int col0, const float* __restrict__ scores, const int32_t* __restrict__ truth,
+                                                         const int32_t* __restrict__ lo, const int32_t* __restrict__ hi, const int32_t* __restrict__ ids,
+                                                         int carry, float* __restrict__ run_max, float* __restrict__ run_sum,
+                                                         float* __restrict__ truth_score, float* __restrict__ lse_rows, float* __restrict__ loss_rows) {
+  __shared__ float red[4];
+  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+  const int p = GROUP ? blockIdx.x : blockIdx.x * 4 + w;
+  if (!GROUP && p >= P) return;                                           // (a whole wave: the wave route has no barrier)
+  const float* srow = scores + (size_t)p * ld;
+  const int tr = truth[p];
+  RowFilter f = filter_open(lo, hi, ids, p, lane);
+  float m = -INFINITY, s = 0.f;                                           // this lane's running (max, sum exp(. - max))
+  for (int c = GROUP ? w * 256 : 0; c < N; c += GROUP ? 1024 : 256) {
+    const unsigned mask = filter_mask(f, col0 + c, lane);
+    const int j = c + lane * 4;
+    if (j < N) {
+      const float4 x = filter_select(ld4(srow + j), mask, col0 + j, tr, N - j, -INFINITY);
+      const float mn = fmaxf(fmaxf(m, fmaxf(x.x, x.y)), fmaxf(x.z, x.w));
+      if (mn > -INFINITY) {                                               // (else nothing admissible so far: no -inf - -inf)
+        s = s * expf(m - mn) + ((expf(x.x - mn) + expf(x.y - mn)) + (expf(x.z - mn) + expf(x.w - mn)));
+        m = mn;
+      }
+    }
+  }
+  const float M = GROUP ? block_max_256(m, red) : wave_max(m);
+  const float part = m > -INFINITY ? s * expf(m - M) : 0.f;
+  const float S = GROUP ? block_sum_256(part, red) : wave_sum(part);
+  if (GROUP ? threadIdx.x == 0 : lane == 0) {
+    float rm = M, rs = S;
+    if (carry) {
+      const float om = run_max[p], os = run_sum[p];
+      rm = fmaxf(om, M);
+      rs = (om > -INFINITY ? os * expf(om - rm) : 0.f) + (M > -INFINITY ? S * expf(M - rm) : 0.f);     // expf(0) = 1: an empty panel changes nothing
+    }
+    const int jt = tr - col0;
+    const float ts = (jt >= 0 && jt < N) ? srow[jt] : (carry ? truth_score[p] : 0.f);
+    const float lse = rm + logf(rs);
+    run_max[p] = rm;
+    run_sum[p] = rs;
+    truth_score[p] = ts;
+    lse_rows[p] = lse;
+    loss_rows[p] = lse - ts;
+  }
+}
+
+template <bool GROUP>
+__global__ void __launch_bounds__(256) k_filtered_ce_bwd(int P, int N, int ld, int col0, const float* __restrict__ scores, const int32_t* __restrict__ truth,
+                                                         const int32_t* __restrict__ lo, const int32_t* __restrict__ hi, const int32_t* __restrict__ ids,
+                                                         const float* __restrict__ lse_rows, const float* __restrict__ scale_ptr, float inv_rows,
+                                                         const float* __restrict__ row_scale, float* __restrict__ d_scores) {
+  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+  const int p = GROUP ? blockIdx.x : blockIdx.x * 4 + w;
+  if (!GROUP && p >= P) return;
+  const float* srow = scores + (size_t)p * ld;
+  float* drow = d_scores + (size_t)p * ld;
+  const int tr = truth[p];
+  const float lse = lse_rows[p];
+  const float scale = scale_ptr[0] * (row_scale ? row_scale[p] : inv_rows);
+  RowFilter f = filter_open(lo, hi, ids, p, lane);
+  for (int c = GROUP ? w * 256 : 0; c < ld; c += GROUP ? 1024 : 256) {     // (to ld: the pad columns are written too)
+    const unsigned mask = c < N ? filter_mask(f, col0 + c, lane) : 0u;     // (c is the same in all 64 lanes)
+    const int j = c + lane * 4;
+    if (j >= ld) continue;
+    float4 g = zero4();
+    if (j < N && scale != 0.f) {                                          // a weight-0 row is exactly 0 whatever its lse
+      const float4 x = filter_select(ld4(srow + j), mask, col0 + j, tr, N - j, -INFINITY);
+      const unsigned t = (int)(tr - col0 - j) < N - j ? (unsigned)(tr - col0 - j) : 4u;        // the truth's place among the four, if it is there
+      g = make_float4(x.x > -INFINITY ? expf(x.x - lse) : 0.f, x.y > -INFINITY ? expf(x.y - lse) : 0.f,      // filtered and pad columns: 0
+                      x.z > -INFINITY ? expf(x.z - lse) : 0.f, x.w > -INFINITY ? expf(x.w - lse) : 0.f);
+      g = make_float4(g.x - (t == 0u ? 1.f : 0.f), g.y - (t == 1u ? 1.f : 0.f), g.z - (t == 2u ? 1.f : 0.f), g.w - (t == 3u ? 1.f : 0.f));
+      g = scale4(g, scale);
+    }
+    st4(drow + j, g);
+  }
+}
+
 }  // namespace temp
 
 using namespace temp;
@@ -391,6 +523,43 @@ int temp_gather_ce_bwd(int P, int C, int N, const float* scores, const int32_t* 
     if (hipFuncSetAttribute((const void*)k_gather_ce_bwd, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess) return TEMP_E_LAUNCH;
   }
   TEMP_LAUNCH(K_GATHER_CE, k_gather_ce_bwd, dim3(P), dim3(256), lds, (hipStream_t)stream, C, N, scores, cand, lse_rows, scale, inv_rows, row_scale, d_scores);
+  return launch_status();
+}
+
+static int filtered_ce_args(int P, int N, int ld, int col0, const void* scores, const void* truth, const void* lo, const void* hi, const void* out) {
+  if (P < 0 || N <= 0 || ld < N || col0 < 0 || (long long)col0 + ld + 256 >= 0x7fffffffLL || ((lo != nullptr) != (hi != nullptr))) return TEMP_E_BADARG;
+  if (P > 0 && (!scores || !truth || !out)) return TEMP_E_BADARG;
+  if (ld % 4 || (uintptr_t)scores % 16 || (uintptr_t)out % 16) return TEMP_E_UNSUPPORTED;
+  return TEMP_OK;
+}
+
+int temp_filtered_ce_fwd(int P, int N, int ld, int col0, const float* scores, const int32_t* truth, const int32_t* lo, const int32_t* hi,
+                         const int32_t* ids, int carry, float* run_max, float* run_sum, float* truth_score, float* lse_rows, float* loss_rows,
+                         void* stream) {
+  int rc = filtered_ce_args(P, N, ld, col0, scores, truth, lo, hi, scores);
+  if (rc == TEMP_OK && ((carry != 0 && carry != 1) || (P > 0 && (!run_max || !run_sum || !truth_score || !lse_rows || !loss_rows)))) rc = TEMP_E_BADARG;
+  if (rc != TEMP_OK || P == 0) return rc;
+  if (N <= FCE_WAVE_MAX_N)
+    TEMP_LAUNCH(K_FILTERED_CE_FWD, k_filtered_ce_fwd<false>, dim3(ceil_div(P, 4)), dim3(256), 0, (hipStream_t)stream, P, N, ld, col0, scores, truth, lo, hi, ids,
+                carry, run_max, run_sum, truth_score, lse_rows, loss_rows);
+  else
+    TEMP_LAUNCH(K_FILTERED_CE_FWD, k_filtered_ce_fwd<true>, dim3(P), dim3(256), 0, (hipStream_t)stream, P, N, ld, col0, scores, truth, lo, hi, ids, carry,
+                run_max, run_sum, truth_score, lse_rows, loss_rows);
+  return launch_status();
+}
+
+int temp_filtered_ce_bwd(int P, int N, int ld, int col0, const float* scores, const int32_t* truth, const int32_t* lo, const int32_t* hi,
+                         const int32_t* ids, const float* lse_rows, const float* scale, float inv_rows, const float* row_scale, float* d_scores,
+                         void* stream) {
+  int rc = filtered_ce_args(P, N, ld, col0, scores, truth, lo, hi, d_scores);
+  if (rc == TEMP_OK && (!scale || (P > 0 && !lse_rows))) rc = TEMP_E_BADARG;
+  if (rc != TEMP_OK || P == 0) return rc;
+  if (N <= FCE_WAVE_MAX_N)
+    TEMP_LAUNCH(K_FILTERED_CE_BWD, k_filtered_ce_bwd<false>, dim3(ceil_div(P, 4)), dim3(256), 0, (hipStream_t)stream, P, N, ld, col0, scores, truth, lo, hi, ids,
+                lse_rows, scale, inv_rows, row_scale, d_scores);
+  else
+    TEMP_LAUNCH(K_FILTERED_CE_BWD, k_filtered_ce_bwd<true>, dim3(P), dim3(256), 0, (hipStream_t)stream, P, N, ld, col0, scores, truth, lo, hi, ids, lse_rows,
+                scale, inv_rows, row_scale, d_scores);
   return launch_status();
 }
 

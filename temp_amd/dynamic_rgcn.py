@@ -428,6 +428,8 @@ class DynamicRGCN(TKG_Module):
         of all graphs come from ONE temp_corrupt_sample launch (the per-graph torch-op sampler costs ~1.4 ms per graph)."""
         plan = wb.loss_plan
         cand = self.draw_candidates(plan)
+        if cand is None:                             # --all-entity-loss: the positives alone
+            return [(torch.from_numpy(trip), None, None) for trip in plan["triples"]]
         out = []
         for trip, (a0, _) in zip(plan["triples"], plan["splits"]):
             P = trip.shape[0]

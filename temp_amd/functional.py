@@ -281,8 +281,9 @@ def gather_inverse(idx_np, n_rows, device):
 # The link-prediction loss (its autograd nodes, scorers and private switches) is temp_amd.link_loss; the functions callers reach
 # through this module are re-exported.  _TALL_SCORES, _L1_METHODS, _L1_MIX_METHODS and _cached_l1_slots are NOT: a copy of a switch
 # here would be one nobody reads.
-from .link_loss import (batched_ensemble_link_prediction, batched_gated_link_prediction, batched_link_prediction,  # noqa: E402,F401
-                        candidate_cross_entropy, candidate_cross_entropy_mixed, frozen_ensemble_link_prediction, frozen_mix_ce_rows,
+from .link_loss import (batched_all_entity_link_prediction, batched_ensemble_link_prediction, batched_gated_link_prediction,  # noqa: E402,F401
+                        batched_link_prediction, candidate_cross_entropy, candidate_cross_entropy_mixed, filtered_ce_rows_torch,
+                        frozen_ensemble_link_prediction, frozen_mix_ce_rows,
                         gated_link_prediction, gated_loss_inputs,
                         gated_translation_supported, l1_slots, translation_cross_entropy, translation_supported)
 

@@ -9,6 +9,10 @@ _L1Scorer: transE, distances to the candidates alone).  The backend calls of eve
     GEMM     linear_multi, gather_ce_fwd                         | gather_ce_bwd, linear_multi, linear_tn_multi
              (TEMP_LOSS_TALL=1: linear_t per window)             |   (tall: linear_tn + linear per window)
     L1       l1_ce_fwd                                           | l1_ce_bwd_q, l1_ce_bwd_table
+  _BatchedAllEntityLinkPredictionFn   the same sum with EVERY entity outside the row's known-true list as a negative ("1-vs-all",
+    GEMM     bilinear_query_fwd; per column panel linear_multi,  | per panel (linear_multi again unless the panel is the whole row),
+    only     filtered_ce_fwd with the carry                      |   filtered_ce_bwd, linear_multi, linear_tn_multi; bilinear_query_bwd,
+             (filtered_ce_rows_torch on a backend without them)  |   segment_sum_rows x 2.  No candidate lists: reads the plan's truth / lo / hi / ids
   _BatchedEnsembleLinkPredictionFn    score-level ensemble of two streams (models/PostDynamicRGCN.py:404-406, 425-428)
     both     per stream: bilinear_query_fwd + its scores         | per stream: ..., bilinear_query_bwd, segment_sum_rows (known);
              (mix = one torch.lerp)                              |   then segment_sum_rows (rel) of the streams' sum
@@ -169,32 +173,34 @@ class _GemmScorer:
     def _rows(self, x):
         return [x[a0:a1] for _, a0, a1 in self.live]
 
-    def _blocks(self, big):
-        return [big[b * self.N:(b + 1) * self.N] for b, _, _ in self.live]
+    def _blocks(self, big, cols=None):
+        """Every live window's block of the stack; cols = (c0, c1): its entities c0 .. c1 - 1 alone (a column panel of the scores)."""
+        c0, c1 = (0, self.N) if cols is None else cols
+        return [big[b * self.N + c0:b * self.N + c1] for b, _, _ in self.live]
 
     def _dbig_like(self, big):
         """The gradient buffer of `big`: every live window's block is written whole, so only a batch with an empty window needs zeros."""
         return torch.empty_like(big) if len(self.live) == len(self.inp["splits"]) else torch.zeros_like(big)
 
-    def scores(self, be, q, big):
-        """scores = q[rows of window b] . big_b^T for every live window -> (rows, N), one launch."""
-        scores = torch.empty(q.shape[0], self.N, dtype=torch.float32, device=q.device)
-        be.linear_multi(self._rows(q), self._blocks(big), True, scores)
+    def scores(self, be, q, big, cols=None):
+        """scores = q[rows of window b] . big_b^T for every live window -> (rows, N), one launch (cols: (rows, c1 - c0), see _blocks)."""
+        scores = torch.empty(q.shape[0], self.N if cols is None else cols[1] - cols[0], dtype=torch.float32, device=q.device)
+        be.linear_multi(self._rows(q), self._blocks(big, cols), True, scores)
         return scores
 
-    def dq(self, be, d_s, q, big):
-        """d_q = d_scores_b . big_b for every live window, one launch."""
+    def dq(self, be, d_s, q, big, cols=None):
+        """d_q = d_scores_b . big_b for every live window, one launch (cols: the panel's share of it)."""
         d_q = torch.empty_like(q)
-        be.linear_multi(self._rows(d_s), self._blocks(big), False, d_q)
+        be.linear_multi(self._rows(d_s), self._blocks(big, cols), False, d_q)
         return d_q
 
-    def dbig(self, be, d_s, q, big):
-        """d_big_b = d_scores_b^T . q_b for every live window."""
-        d_big = self._dbig_like(big)
+    def dbig(self, be, d_s, q, big, cols=None, out=None):
+        """d_big_b = d_scores_b^T . q_b for every live window (cols: the panel's rows of every block, written into `out`)."""
+        d_big = self._dbig_like(big) if out is None else out
         if hasattr(be, "linear_tn_multi"):                                                    # one launch
-            be.linear_tn_multi(self._rows(d_s), self._rows(q), self._blocks(d_big))
+            be.linear_tn_multi(self._rows(d_s), self._rows(q), self._blocks(d_big, cols))
         else:
-            for (_, a0, a1), dst in zip(self.live, self._blocks(d_big)):
+            for (_, a0, a1), dst in zip(self.live, self._blocks(d_big, cols)):
                 be.linear_tn(d_s[a0:a1], q[a0:a1], out=dst)
         return d_big
 
@@ -418,6 +424,146 @@ def batched_link_prediction(ent_rows, rel, big, kind, inputs):
     """sum over windows of CE_tail + CE_head (models/DynamicRGCN.py:186-193) for scorer `kind` ('distmult' | 'complex': the GEMM
     scorer; 'transE': the L1 scorer); `inputs` = TKG_Module.loss_inputs(...)."""
     return _BatchedLinkPredictionFn.apply(ent_rows, rel, big, kind, inputs)
+
+
+# -- the all-entity ("1-vs-all") objective ------------------------------------------------------------------------------------------
+# A live (rows, N) score matrix of the all-entity node stays at or under this many bytes (evaluation.TOPK_PANEL_BYTES, the project's
+# bound for one); above it the node works in column panels with the carry of temp_filtered_ce_fwd.
+ALL_ENTITY_PANEL_BYTES = 256 << 20
+
+
+def _filtered_columns(P, n, truth, lo, hi, ids, col0, device):
+    """bool (P, n): column j of row p is FILTERED -- entity col0 + j is in ids[lo[p] .. hi[p]) and is not truth[p]."""
+    mask = torch.zeros(P, n, dtype=torch.bool, device=device)
+    if lo is not None and P:
+        cnt = (hi - lo).long()
+        row = torch.repeat_interleave(torch.arange(P, device=device), cnt)
+        first = torch.cumsum(cnt, 0) - cnt
+        pos = lo.long()[row] + torch.arange(row.shape[0], device=device) - first[row]
+        col = ids.long()[pos] - col0
+        ok = (col >= 0) & (col < n) & (ids.long()[pos] != truth.long()[row])
+        mask[row[ok], col[ok]] = True
+    return mask
+
+
+def filtered_ce_rows_torch(scores, truth, lo, hi, ids, col0=0, n=None):
+    """The contract of temp_filtered_ce_fwd (one call, carry = 0) in plain torch, differentiable and in the dtype of `scores`
+    -> (loss_rows [P], lse_rows [P]): the filtered columns (in the row's list ids[lo[p] .. hi[p]) and not the truth; lo None: none)
+    and the columns from n on masked to -inf, logsumexp, minus the truth's score (0 when the truth lies outside col0 .. col0 + n - 1).
+    The reference of the kernels' tests (in float64, with autograd for d_scores) and, through _filtered_ce_fwd / _filtered_ce_bwd,
+    the route of a backend without them."""
+    P, n = scores.shape[0], scores.shape[1] if n is None else int(n)
+    x = scores[:, :n].masked_fill(_filtered_columns(P, n, truth, lo, hi, ids, col0, scores.device), float("-inf"))
+    lse = torch.logsumexp(x, dim=1)
+    jt = truth.long() - col0
+    inside = (jt >= 0) & (jt < n)
+    ts = torch.where(inside, scores.gather(1, jt.clamp(0, n - 1).view(-1, 1)).view(-1), torch.zeros_like(lse))
+    return lse - ts, lse
+
+
+def _filtered_ce_fwd(be, scores, truth, lo, hi, ids, col0, carry):
+    """backend.filtered_ce_fwd, or -- on a backend without it, the CPU test backend -- its contract in torch, the carry included."""
+    if hasattr(be, "filtered_ce_fwd"):
+        return be.filtered_ce_fwd(scores, truth, lo, hi, ids, col0=col0, carry=carry)
+    scores = scores.detach()
+    P, n = scores.shape
+    x = scores.masked_fill(_filtered_columns(P, n, truth, lo, hi, ids, col0, scores.device), float("-inf"))
+    m = x.max(dim=1).values if n else x.new_full((P,), float("-inf"))
+    s = torch.where(m > float("-inf"), torch.exp(x - m.clamp(min=torch.finfo(x.dtype).min).view(-1, 1)).sum(dim=1), torch.zeros_like(m))
+    jt = truth.long() - col0
+    inside = (jt >= 0) & (jt < n)
+    here = scores.gather(1, jt.clamp(0, n - 1).view(-1, 1)).view(-1)
+    if carry is None:
+        ts = torch.where(inside, here, torch.zeros_like(here))
+    else:
+        om, os_, ots = carry[0], carry[1], carry[2]
+        nm = torch.maximum(om, m)
+        ref = nm.clamp(min=torch.finfo(x.dtype).min)
+        s = (torch.where(om > float("-inf"), os_ * torch.exp(om - ref), torch.zeros_like(s))
+             + torch.where(m > float("-inf"), s * torch.exp(m - ref), torch.zeros_like(s)))
+        m, ts = nm, torch.where(inside, here, ots)
+    lse = m + torch.log(s)
+    return lse - ts, lse, torch.stack([m, s, ts])
+
+
+def _filtered_ce_bwd(be, scores, truth, lo, hi, ids, col0, lse, scale, row_scale):
+    if hasattr(be, "filtered_ce_bwd"):
+        return be.filtered_ce_bwd(scores, truth, lo, hi, ids, lse, scale, 1.0, row_scale, col0=col0)
+    scores = scores.detach()
+    P, n = scores.shape
+    filt = _filtered_columns(P, n, truth, lo, hi, ids, col0, scores.device)
+    g = torch.exp(scores - lse.view(-1, 1)).masked_fill(filt, 0.0)
+    jt = truth.long() - col0
+    inside = ((jt >= 0) & (jt < n)).nonzero().view(-1)
+    g[inside, jt[inside]] -= 1.0
+    w = (scale.reshape(-1)[0] * row_scale).view(-1, 1)
+    return torch.where(w != 0, g * w, torch.zeros_like(g))
+
+
+def all_entity_panel(panel, rows, N):
+    """Columns per pass of the all-entity node: `panel` when given (a positive multiple of 4), else all N while the (rows, N)
+    score matrix stays at or under ALL_ENTITY_PANEL_BYTES, else as many columns as do."""
+    if panel is None:
+        per = 4 * max(rows, 1)
+        panel = N if per * N <= ALL_ENTITY_PANEL_BYTES else max(4, ALL_ENTITY_PANEL_BYTES // per // 4 * 4)
+    if panel <= 0 or panel % 4:
+        raise ValueError("batched_all_entity_link_prediction: panel must be a positive multiple of 4")
+    return min(int(panel), N)
+
+
+class _BatchedAllEntityLinkPredictionFn(torch.autograd.Function):
+    """_BatchedLinkPredictionFn with the all-entity objective in the place of the candidate lists:
+        q    = bilinear_query(ent_rows[known], rel[rel_idx])
+        loss = sum_rows w_row * CE(score(q[row], e) over EVERY entity e of the row's window outside its known-true list, label = truth)
+    (temp_filtered_ce_*: the row's list is the plan's ids[lo .. hi), the truth stays in).  Per column panel, forward and backward in
+    the same order: linear_multi over the live windows' sub-blocks, filtered_ce_fwd with the carry | the panel's scores again (kept
+    when the panel is the whole row), filtered_ce_bwd, d_q += linear_multi (a plain add, panel by panel), d_big[panel] =
+    linear_tn_multi; then bilinear_query_bwd and the two segment sums.  Nothing is drawn: same inputs, same bits."""
+
+    @staticmethod
+    def forward(ctx, ent_rows, rel, big, kind, inp, panel):
+        be = get_backend()
+        sc = _GemmScorer(kind, inp, big)
+        if sc.N % 4:
+            raise ValueError("batched_all_entity_link_prediction: the entity count must be a multiple of 4")
+        q = _query_fwd(be, kind, ent_rows, rel, inp)
+        panel = all_entity_panel(panel, q.shape[0], sc.N)
+        state = kept = None
+        for c0 in range(0, sc.N, panel):
+            cols = (c0, min(sc.N, c0 + panel))
+            kept = sc.scores(be, q, big, cols)
+            loss_rows, lse, state = _filtered_ce_fwd(be, kept, inp["truth"], inp["lo"], inp["hi"], inp["ids"], c0, state)
+        whole = panel >= sc.N
+        ctx.save_for_backward(ent_rows, rel, big, q, lse, *([kept] if whole else []))
+        ctx.scorer, ctx.panel = sc, panel
+        return (loss_rows * inp["weights"]).sum()
+
+    @staticmethod
+    def backward(ctx, d_loss):
+        ent_rows, rel, big, q, lse = ctx.saved_tensors[:5]
+        sc, be, panel = ctx.scorer, get_backend(), ctx.panel
+        inp, scale = sc.inp, _scale(d_loss)
+        d_big, d_q = sc._dbig_like(big), None
+        for c0 in range(0, sc.N, panel):
+            cols = (c0, min(sc.N, c0 + panel))
+            s = ctx.saved_tensors[5] if len(ctx.saved_tensors) > 5 else sc.scores(be, q, big, cols)
+            d_s = _filtered_ce_bwd(be, s, inp["truth"], inp["lo"], inp["hi"], inp["ids"], c0, lse, scale, inp["weights"])
+            part = sc.dq(be, d_s, q, big, cols)
+            d_q = part if d_q is None else d_q.add_(part)
+            sc.dbig(be, d_s, q, big, cols, out=d_big)
+        d_ent, dr = _query_bwd(be, sc.kind, ent_rows, rel, inp, d_q)
+        return d_ent, _segment_sum(be, dr, inp["rel_inv"], rel.shape[0]), d_big, None, None, None
+
+
+def batched_all_entity_link_prediction(ent_rows, rel, big, kind, inputs, panel=None):
+    """sum over windows of CE_tail + CE_head against ALL entities outside each row's known-true list ("1-vs-all", see
+    _BatchedAllEntityLinkPredictionFn) for a bilinear scorer `kind` (scores.BILINEAR); `inputs` = sampling.plan_batch_loss(...):
+    known / rel / is_tail / weights / splits / the inverses, and truth, lo, hi, ids in the place of candidate lists.  `panel`: score
+    columns per pass (a multiple of 4; default all_entity_panel)."""
+    from .scores import BILINEAR
+    if kind not in BILINEAR:
+        raise ValueError("batched_all_entity_link_prediction: no all-entity node for the scorer %r" % (kind,))
+    return _BatchedAllEntityLinkPredictionFn.apply(ent_rows, rel, big, kind, inputs, panel)
 
 
 def batched_ensemble_link_prediction(loc_rows, rec_rows, rel, big_loc, big_rec, w, kind, inputs):

@@ -358,6 +358,7 @@ class _TwoStreamMixin:
     Impute* class.  A family adds its frequency MLPs (init_freq_mlp, calc_ensemble_ratio) and its loss: _step_weights (what is
     computed before the all-entity pass), _fused_windows_loss (all windows as one node, or None) and _window_losses."""
     _two_stream = True
+    _all_entity_loss_refusal = "the model scores against a local AND a temporal all-entity table; the all-entity node takes one"
 
     def __init__(self, args, num_ents, num_rels, graph_dict_train, graph_dict_val, graph_dict_test, evaluater_type=None):
         super().__init__(args, num_ents, num_rels, graph_dict_train, graph_dict_val, graph_dict_test, evaluater_type)

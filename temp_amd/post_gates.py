@@ -106,6 +106,7 @@ class _GatedLossMixin(_FrequencyGateMixin):
     matrices at the candidate columns.  TransE's L1 distance is not: its node reads both all-entity rows of every candidate and
     mixes them in registers (temp_l1_mix_ce_fwd / _bwd_q / _bwd_table).  Reference quirk kept: w_sqo comes from subject_query_SUBJECT_embed_linear and w_oqo from
     object_query_SUBJECT_embed_linear (calc_ensemble_ratio, :284-321), so the two *_object_embed_linear MLPs never get a gradient."""
+    _all_entity_loss_refusal = "the model gates a local AND a temporal all-entity table per candidate; the all-entity node takes one table"
     _evaluater = "PostEvaluationFilter"
 
     def init_freq_mlp(self):

@@ -34,11 +34,27 @@ class TKG_Module(nn.Module):
         self.calc_score = {'distmult': scores.distmult, 'complex': scores.complex, 'transE': scores.transE,
                            'simple': scores.simple_pair}[args.score_function]
         self.fused_loss = True
+        # --all-entity-loss: softmax cross-entropy against EVERY entity outside the row's known-true set ("1-vs-all") in the place of
+        # the 1 + negative_rate sampled candidates; negative_rate is then ignored, num_pos_facts still subsamples the positives
+        self.all_entity_loss = bool(getattr(args, "all_entity_loss", False))
+        if self.all_entity_loss:
+            self._check_all_entity_loss()
         self.build_model()
         if not getattr(args, "debug", False):
             self.corrupter = CorruptTriples(self.args, graph_dict_train)
             if evaluater_type is not None:
                 self.evaluater = evaluater_type(args, self.calc_score, graph_dict_train, graph_dict_val, graph_dict_test)
+
+    _all_entity_loss_refusal = None       # a class whose loss no all-entity node covers says why here
+
+    def _check_all_entity_loss(self):
+        """--all-entity-loss covers the models whose loss is the plain batched node over ONE all-entity table and a bilinear scorer."""
+        why = self._all_entity_loss_refusal
+        if why is None and self.args.score_function not in scores.BILINEAR:
+            why = ("the scorer %r is not bilinear: the dense L1 adjoint of a TransE row against all entities is an O(P N D) pass of its "
+                   "own, which no kernel here does" % self.args.score_function)
+        if why is not None:
+            raise NotImplementedError("%s: --all-entity-loss is not available: %s" % (type(self).__name__, why))
 
     # `sample_rng` draws the training-time edge / positive subsets inside `prepare`.  A prefetch worker that prepares batches
     # out of order (temp_amd.prefetch.BatchPrefetcher with several workers) installs a generator of its own for the batch it
@@ -165,6 +181,40 @@ class TKG_Module(nn.Module):
         return (self.train_link_prediction(ent_embed, triplets, neg_tail, labels, all_embeds_g, corrupt_tail=True, rel=rel)
                 + self.train_link_prediction(ent_embed, triplets, neg_head, labels, all_embeds_g, corrupt_tail=False, rel=rel))
 
+    def all_entity_link_prediction_both(self, ent_embed, triplets, g, all_embeds_g, rel=None, chunk=1 << 24):
+        """loss_tail + loss_head of one target graph under --all-entity-loss, literally: calc_score of every positive against
+        all_embeds_g in 'tail' resp. 'head' mode (`chunk` elements of (rows, N, D) at a time), the train snapshot's other known-true
+        tails of (h, r) resp. heads of (r, t) -- the entities the sampler never draws (utils/CorrptTriples.py:87-106) -- masked to
+        -inf, the truth kept, logsumexp minus the truth's score, the mean over the positives.  The lists come from the graph's edge
+        arrays here, not from the resident store: this is the step the fused node is tested against."""
+        dev = ent_embed.device
+        rel_embeds = self.rel_embeds if rel is None else rel
+        N, D = all_embeds_g.shape
+        P = triplets.shape[0]
+        f = lambda a: torch.from_numpy(np.asarray(a).astype(np.int64)).to(dev)
+        src, erel, dst, gid = f(g.src), f(g.rel), f(g.dst), f(g.gids)
+        R = int(rel_embeds.shape[0])
+        step = max(1, chunk // max(1, N * D))
+        cand = all_embeds_g.unsqueeze(0)
+        loss = 0
+        for mode, known_col, ans_col, e_known, e_ans in (("tail", 0, 2, src, dst), ("head", 2, 0, dst, src)):
+            e_key, rows_sum = e_known * R + erel, 0
+            for a in range(0, P, step):
+                t = triplets[a:a + step]
+                known, r = ent_embed[t[:, known_col]], rel_embeds[t[:, 1]]
+                score = self.calc_score(known, r, cand, mode=mode) if mode == "tail" else self.calc_score(cand, r, known, mode=mode)
+                hit = (t[:, known_col] * R + t[:, 1]).view(-1, 1) == e_key.view(1, -1)                  # (rows, E): edge e shares the row's (known, relation)
+                rows_i, e_i = hit.nonzero(as_tuple=True)
+                mask = torch.zeros(t.shape[0], N, dtype=torch.bool, device=dev)
+                mask[rows_i, gid[e_ans[e_i]]] = True
+                truth = gid[t[:, ans_col]]
+                here = torch.arange(t.shape[0], device=dev)
+                mask[here, truth] = False
+                lse = torch.logsumexp(score.masked_fill(mask, float("-inf")), dim=1)
+                rows_sum = rows_sum + (lse - score[here, truth]).sum()
+            loss = loss + rows_sum / P
+        return loss
+
     @staticmethod
     def loss_inputs(row_offsets, samples, dev, n_rows=None, n_rel_rows=None, head_as_tail=False):
         """Index tensors of the batched loss for one set of samples (static for a prepared batch, so callers cache it):
@@ -216,7 +266,12 @@ class TKG_Module(nn.Module):
 
     def cached_loss_inputs(self, wb, attr, samples, sizes, finish=None, **kw):
         """loss_inputs(...) of a prepared batch whose target graphs have `sizes` rows, cached per sample set (per_sample_set);
-        **kw goes to loss_inputs (head_as_tail), `finish(inputs, n_rows, device)` completes them for the node that reads them."""
+        **kw goes to loss_inputs (head_as_tail), `finish(inputs, n_rows, device)` completes them for the node that reads them.
+        Under --all-entity-loss injected samples carry positives alone and no known-true lists: {} -- no batched node takes it
+        (batched_link_prediction returns None), and the per-graph route builds the lists itself."""
+        if self.all_entity_loss:
+            return {}
+
         def build():
             dev = self.rel_embeds.device
             offs = np.concatenate([[0], np.cumsum(sizes)])[:-1]
@@ -254,7 +309,9 @@ class TKG_Module(nn.Module):
         `inputs` = loss_inputs(..., n_rows, n_rel_rows), `all_embeds` the (B * N_ents, D) stack of the windows' all-entity
         matrices (or a list of B (N_ents, D) matrices).  Returns None when no fused node takes the scorer or the shapes are
         outside the kernels' alignment (the caller takes the per-graph path).  `rel`: the relation table that inputs["rel"]
-        indexes, instead of self.rel_embeds (one table per window: sampling.plan_batch_loss(rel_stride=...))."""
+        indexes, instead of self.rel_embeds (one table per window: sampling.plan_batch_loss(rel_stride=...)).  Under
+        --all-entity-loss the node is functional.batched_all_entity_link_prediction and `inputs` the loss plan itself (its truth, lo,
+        hi, ids in the place of candidate lists); inputs without them -- built from injected samples -- give None."""
         name = self.args.score_function
         D = ent_rows.shape[1]
         if not self.fused_loss_ok(D):
@@ -263,6 +320,10 @@ class TKG_Module(nn.Module):
             return ent_rows.sum() * 0.0
         from . import functional as TF
         big = all_embeds if torch.is_tensor(all_embeds) else torch.cat(list(all_embeds), dim=0)
+        if self.all_entity_loss:                     # `inputs` is then the loss plan itself: truth, lo, hi, ids instead of candidates
+            if "truth" not in inputs:
+                return None                          # loss inputs built from injected samples: the per-graph route
+            return TF.batched_all_entity_link_prediction(ent_rows, self.rel_embeds if rel is None else rel, big.reshape(-1, D).contiguous(), name, inputs)
         return TF.batched_link_prediction(ent_rows, self.rel_embeds if rel is None else rel, big.reshape(-1, D).contiguous(), name, inputs)
 
     def true_sets(self):
@@ -278,7 +339,7 @@ class TKG_Module(nn.Module):
     def draw_candidates(self, plan, cand=None):
         """The candidate lists [true id, negatives] of every row of a loss plan (sampling.plan_batch_loss): ONE sampler launch
         (temp_corrupt_sample) on one fresh seed of seed_rng.  `cand`: a fixed draw to use instead; nothing is drawn then."""
-        if cand is not None:
+        if cand is not None or self.all_entity_loss:        # (the all-entity loss reads the plan's lists itself: nothing to draw)
             return cand
         return get_backend().corrupt_sample(int(self.seed_rng.integers(1 << 62)), plan["truth"], plan["lo"], plan["hi"], plan["ids"],
                                             self.args.negative_rate, self.num_ents)
@@ -293,6 +354,9 @@ class TKG_Module(nn.Module):
         for i, (t, g) in enumerate(zip(times, graphs)):
             triplets, neg_tail, neg_head = samples[i] if samples is not None else self.corrupter.single_graph_negative_sampling(t, g, self.num_ents)[:3]
             if triplets.shape[0] == 0:
+                continue
+            if self.all_entity_loss:                 # the positives alone: the negatives are all the other entities
+                loss = loss + self.all_entity_link_prediction_both(rows(i), triplets.to(dev), g, all_embeds(i), rel=None if rel is None else rel(i))
                 continue
             triplets, neg_tail, neg_head = triplets.to(dev), neg_tail.to(dev), neg_head.to(dev)
             labels = torch.zeros(triplets.shape[0], dtype=torch.int64, device=dev)
