@@ -1073,6 +1073,43 @@ int temp_filtered_rank(int P, int N, int ld, const float* scores, const int32_t*
                        const int32_t* filt_ids, int32_t* ranks, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * Streamed filtered ranking: temp_filtered_rank on a COLUMN PANEL of the score rows, with a carry, so that the [P, N] matrix of an
+ * evaluation never has to exist at once; the _mix form ranks the mixed row of the two-table post models without writing it.
+ * scores [P, ld] = the P rows scored against the entities col0 .. col0 + N - 1: column j < N is entity e = col0 + j.  target and
+ * filt_ids hold GLOBAL entity ids; filt_ptr [P+1] / filt_ids as EvaluationFilter.filter_lists makes them (unique and ascending
+ * within a row), nullable as for temp_filtered_rank.
+ *   value of e:  0 for a listed entity that is not the row's target -- it is NOT excluded, and is ahead of a target whose own
+ *                value is 0 when its id is smaller (TransE below about -104);  else v = sigmoid(x), temp_filtered_rank's own,
+ *                x = scores[p,j]  (plain)   or   fmaf(w[p], a[p,j], (1 - w[p]) * b[p,j])  (mix: csrc/mix.hpp, in registers)
+ *   e is AHEAD of the target  <=>  v > ts  or  (v == ts and e < target[p]);  the target itself is never ahead (its column goes
+ *                through the same expressions as ts)
+ *   columns j >= N are not entities and never count, whatever they hold (garbage, +inf): they are left out by index.
+ * Operands at j < N are finite; +-inf and NaN there are OUTSIDE the contract (the mix of an infinity by a weight of 0 is NaN).
+ * mode:
+ *   TEMP_RANK_WHOLE        the panel holds every row's target: ts from the row itself, ranks[p] = 1 + #ahead.  target_score and count
+ *                          may be NULL; only ranks is written.  The plain form returns temp_filtered_rank's ranks exactly.
+ *   TEMP_RANK_COLLECT      rows whose target lies in [col0, col0 + N) write the raw (mixed) score of the target's column to
+ *                          target_score[p]; other rows are not touched; nothing is counted (ranks and count may be NULL).
+ *   TEMP_RANK_COUNT_FIRST  ts = sigmoid(target_score[p]);  count[p] = the panel's #ahead;  ranks[p] = count[p] + 1.
+ *   TEMP_RANK_COUNT_ADD    the same with count[p] += the panel's #ahead.
+ * A COLLECT sweep over disjoint panels that cover all entities, then a COUNT_FIRST / COUNT_ADD sweep over the same panels in any
+ * order, equals ONE TEMP_RANK_WHOLE call over the concatenated row exactly (an integer sum).  count and ranks are int32.
+ * P >= 0, N > 0, ld >= N, col0 >= 0, col0 + ld + 256 < 2^31, a known mode (else TEMP_E_BADARG); a NULL scores (scores_a, scores_b,
+ * w), target, or output of the mode with P > 0: TEMP_E_BADARG; ld % 4 == 0 and the score matrices 16-byte aligned (else
+ * TEMP_E_UNSUPPORTED) -- a column slice of a wider matrix with the wide ld qualifies.  P == 0 succeeds without a launch.  One wave
+ * per row for N <= 1024, one workgroup per row above; no workspace, no atomics, bit-repeatable.
+ * ---------------------------------------------------------------------------------------------- */
+#define TEMP_RANK_WHOLE 0
+#define TEMP_RANK_COLLECT 1
+#define TEMP_RANK_COUNT_FIRST 2
+#define TEMP_RANK_COUNT_ADD 3
+int temp_filtered_rank_stream(int P, int N, int ld, int col0, const float* scores, const int32_t* target, const int32_t* filt_ptr,
+                              const int32_t* filt_ids, int mode, float* target_score, int32_t* count, int32_t* ranks, void* stream);
+int temp_filtered_rank_stream_mix(int P, int N, int ld, int col0, const float* scores_a, const float* scores_b, const float* w,
+                                  const int32_t* target, const int32_t* filt_ptr, const int32_t* filt_ids, int mode, float* target_score,
+                                  int32_t* count, int32_t* ranks, void* stream);
+
+/* ------------------------------------------------------------------------------------------------
  * Filtered top-k selection: the answer list of a query (s, r, ?, t) or (?, r, o, t), where temp_filtered_rank only locates one
  * known answer.  scores [P, ld] = P queries scored against the N entities col0 .. col0 + N - 1 (the same producers: temp_linear with
  * the folded query, temp_l1_scores); column j < N is the score of entity col0 + j, columns >= N never reach the result.

@@ -125,7 +125,8 @@ ASSEMBLE_PIECE = 4096
 SCORE_KINDS = {"distmult": 0, "complex": 1, "transE": 2, "simple": 3}
 FROZEN_KINDS = {"dot": 0, "l1": 1}     # include/temp_amd.h: TEMP_FROZEN_DOT / TEMP_FROZEN_L1 (temp_frozen_mix_ce)
 ADAM_CHUNK = 4096         # include/temp_amd.h: TEMP_ADAM_CHUNK (elements of one tensor that one workgroup of the optimizer passes owns)
-TOPK_MAX = 256             # include/temp_amd.h: TEMP_TOPK_MAX (the longest answer list temp_filtered_topk keeps)
+RANK_WHOLE, RANK_COLLECT, RANK_COUNT_FIRST, RANK_COUNT_ADD = range(4)      # include/temp_amd.h: TEMP_RANK_* (temp_filtered_rank_stream)
+TOPK_MAX = 256           # include/temp_amd.h: TEMP_TOPK_MAX (the longest answer list temp_filtered_topk keeps)
 
 # name -> (restype, argtypes); mirrors include/temp_amd.h one to one
 _G = ctypes.POINTER(TempGraph)
@@ -252,6 +253,8 @@ SYMBOLS = {
     "temp_filtered_ce_bwd": (_I, [_I, _I, _I, _I, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, _F, c_vp, c_vp, c_vp]),
     "temp_corrupt_sample": (_I, [_I, _I, _I, ctypes.c_uint64, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp]),
     "temp_filtered_rank": (_I, [_I, _I, _I, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp]),
+    "temp_filtered_rank_stream": (_I, [_I, _I, _I, _I, c_vp, c_vp, c_vp, c_vp, _I, c_vp, c_vp, c_vp, c_vp]),
+    "temp_filtered_rank_stream_mix": (_I, [_I, _I, _I, _I, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, _I, c_vp, c_vp, c_vp, c_vp]),
     "temp_filtered_topk": (_I, [_I, _I, _I, _I, _I, c_vp, c_vp, c_vp, c_vp, _I, c_vp, c_vp, c_vp]),
     "temp_filtered_topk_mix": (_I, [_I, _I, _I, _I, _I, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, _I, c_vp, c_vp, c_vp]),
     "temp_grad_norm_workspace": (_SZ, [_I]),

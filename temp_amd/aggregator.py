@@ -237,4 +237,5 @@ class Aggregator(_FrequencyGateMixin, TKG_Module):
         object-corruption ranks use weight_subject and the subject-corruption ranks weight_object."""
         w_subject, w_object = self.calc_ensemble_ratio(index_sample, t, g)
         return self.evaluater.calc_metrics_single_graph(rows[0], rows[1], self.spatial_model.rel_embeds, alls[0], alls[1], w_subject, w_object,
-                                                        index_sample, g, t, rel_enc_temporal=self.temporal_model.rel_embeds), None
+                                                        index_sample, g, t, rel_enc_temporal=self.temporal_model.rel_embeds,
+                                                        **self._panel_kw()), None

@@ -1126,6 +1126,86 @@ class HipBackend:
         return ranks.long()
 
     @staticmethod
+    def _rank_stream_args(what, scores, target, filt_ptr, filt_ids, mode, col0, n, carry):
+        """The checks and buffers both streamed-rank entry points share -> (scores, P, n, ld, target, filt_ptr, filt_ids, carry,
+        ranks).  carry = (target_score [P] float32, count [P] int32): made here by a TEMP_RANK_COLLECT call without one, demanded by
+        the counting modes, written in place by the kernel."""
+        if scores.dim() != 2 or not scores.is_cuda or scores.dtype != torch.float32:
+            raise _lib.TempAmdError("%s: scores must be a float32 [P, ld] GPU matrix" % what)
+        scores, target = scores.detach(), _i32(target, "target")
+        P, width = scores.shape
+        n = width if n is None else int(n)
+        ld = scores.stride(0) if P > 1 else max(scores.stride(0), width)
+        if scores.stride(1) != 1 and width > 1:
+            raise ValueError("%s: the score rows must be contiguous" % what)
+        if mode not in (_lib.RANK_WHOLE, _lib.RANK_COLLECT, _lib.RANK_COUNT_FIRST, _lib.RANK_COUNT_ADD):
+            raise ValueError("%s: mode must be one of the four TEMP_RANK_* modes" % what)
+        if not 0 < n <= width or col0 < 0:
+            raise ValueError("%s: n must lie in (0, row length] and col0 must not be negative" % what)
+        if ld % 4 or scores.data_ptr() % 16:
+            raise ValueError("%s: the row stride must be a multiple of 4 and the first score 16-byte aligned" % what)
+        if target.shape[0] != P:
+            raise ValueError("%s: target must have one entry per row" % what)
+        if filt_ptr is not None:
+            filt_ptr, filt_ids = _i32(filt_ptr, "filt_ptr"), _i32(filt_ids, "filt_ids")
+            if filt_ptr.shape[0] != P + 1:
+                raise ValueError("%s: filt_ptr must have one entry per row plus one" % what)
+        if mode == _lib.RANK_WHOLE:
+            carry = None
+        elif carry is None:
+            if mode != _lib.RANK_COLLECT:
+                raise ValueError("%s: the counting modes need the carry of the TEMP_RANK_COLLECT sweep" % what)
+            carry = (torch.zeros(P, dtype=torch.float32, device=scores.device), torch.zeros(P, dtype=torch.int32, device=scores.device))
+        else:
+            ts, cnt = carry
+            if ts.shape != (P,) or cnt.shape != (P,) or ts.dtype != torch.float32 or cnt.dtype != torch.int32 or ts.device != scores.device \
+                    or cnt.device != scores.device or not ts.is_contiguous() or not cnt.is_contiguous():
+                raise ValueError("%s: carry must be the (target_score, count) of an earlier call over the same rows" % what)
+        ranks = None if mode == _lib.RANK_COLLECT else torch.empty(P, dtype=torch.int32, device=scores.device)
+        return scores, P, n, ld, target, filt_ptr, filt_ids, carry, ranks
+
+    def filtered_rank_stream(self, scores, target, filt_ptr=None, filt_ids=None, mode=_lib.RANK_WHOLE, col0=0, n=None, carry=None):
+        """The filtered rank on a column panel (see temp_filtered_rank_stream) -> (ranks [P] int64 | None, carry).  Column j < n
+        (default: every column) of scores [P, ld] is entity col0 + j; `scores` may be a column slice of a wider row-major matrix (row
+        stride % 4 == 0, first element 16-byte aligned).  mode RANK_WHOLE: the panel holds every target -> (ranks, None).
+        RANK_COLLECT: the targets' scores go into the carry -> (None, carry), allocated when none is given.  RANK_COUNT_FIRST /
+        RANK_COUNT_ADD: the panel's count is written / added to the carry -> (the ranks so far, carry).  The carry is updated in
+        place and handed back."""
+        what = "filtered_rank_stream"
+        scores, P, n, ld, target, filt_ptr, filt_ids, carry, ranks = self._rank_stream_args(what, scores, target, filt_ptr, filt_ids, mode, col0, n, carry)
+        ts, cnt = carry if carry is not None else (None, None)
+        rc = self.lib.temp_filtered_rank_stream(P, n, ld, int(col0), _ptr(scores), _ptr(target), _ptr(filt_ptr), _ptr(filt_ids), int(mode), _ptr(ts),
+                                                _ptr(cnt), _ptr(ranks), _stream())
+        _lib.check(rc, "temp_filtered_rank_stream")
+        return (None if ranks is None else ranks.long()), carry
+
+    def filtered_rank_stream_mix(self, scores_a, scores_b, w, target, filt_ptr=None, filt_ids=None, mode=_lib.RANK_WHOLE, col0=0, n=None,
+                                 carry=None):
+        """filtered_rank_stream over the rows w[p] * scores_a[p] + (1 - w[p]) * scores_b[p], formed inside the kernel (see
+        temp_filtered_rank_stream_mix).  The two matrices have equal shapes and strides, w has one entry per row; the carry holds the
+        targets' MIXED scores."""
+        what = "filtered_rank_stream_mix"
+        if not torch.is_tensor(scores_b) or scores_b.dim() != 2 or not scores_b.is_cuda or scores_b.dtype != torch.float32:
+            raise _lib.TempAmdError("%s: scores_b must be a float32 [P, ld] GPU matrix" % what)
+        scores_a, P, n, ld, target, filt_ptr, filt_ids, carry, ranks = self._rank_stream_args(what, scores_a, target, filt_ptr, filt_ids, mode, col0, n,
+                                                                                             carry)
+        scores_b = scores_b.detach()
+        if scores_b.shape != scores_a.shape or scores_b.stride() != scores_a.stride() or scores_b.device != scores_a.device:
+            raise ValueError("%s: the two score matrices must have equal shapes and strides" % what)
+        if scores_b.data_ptr() % 16:
+            raise ValueError("%s: the first score of scores_b must be 16-byte aligned" % what)
+        if w is None:
+            raise ValueError("%s: w must have one entry per row" % what)
+        w = _f32(w.detach().reshape(-1), "w")
+        if w.shape[0] != P or w.device != scores_a.device:
+            raise ValueError("%s: w must have one entry per row" % what)
+        ts, cnt = carry if carry is not None else (None, None)
+        rc = self.lib.temp_filtered_rank_stream_mix(P, n, ld, int(col0), _ptr(scores_a), _ptr(scores_b), _ptr(w), _ptr(target), _ptr(filt_ptr),
+                                                    _ptr(filt_ids), int(mode), _ptr(ts), _ptr(cnt), _ptr(ranks), _stream())
+        _lib.check(rc, "temp_filtered_rank_stream_mix")
+        return (None if ranks is None else ranks.long()), carry
+
+    @staticmethod
     def _topk_args(what, scores, k, filt_ptr, filt_ids, keep, col0, n, carry):
         """The checks and output buffers both selection entry points share -> (scores, P, n, ld, filt_ptr, filt_ids, keep, top_val,
         top_idx)."""

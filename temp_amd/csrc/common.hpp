@@ -149,7 +149,7 @@ enum KernelId {
   K_PAIR_MSG, K_PAIR_GATHER_FWD, K_PAIR_FIX_EPI, K_PAIR_GATHER_BWD, K_PAIR_TAIL,
   K_DIACHRONIC_FWD, K_DIACHRONIC_BWD, K_FILTERED_TOPK, K_ADAM_GRAD_NORM, K_ADAM_NORM_FINISH, K_ADAM_CLIP_STEP, K_FILTERED_TOPK_MIX,
   K_HYPERPLANE_FWD, K_HYPERPLANE_BWD, K_HYPERPLANE_BWD_FINISH, K_PAIR_ROWS_FWD, K_PAIR_ROWS_BWD, K_FROZEN_MIX_CE,
-  K_FILTERED_CE_FWD, K_FILTERED_CE_BWD,
+  K_FILTERED_CE_FWD, K_FILTERED_CE_BWD, K_FILTERED_RANK_STREAM, K_FILTERED_RANK_STREAM_MIX,
   K_COUNT
 };
 int trace_open(int kernel_id, hipStream_t st);       // -> slot or -1

@@ -1,8 +1,11 @@
 // Loss and evaluation kernels: candidate-list cross-entropy, the folded query of the scorers (TransE's translation query among
-// them; its L1 candidate loss and dense scores are in l1_loss.hip), filtered negative sampling, the filtered rank and the all-entity
-// cross-entropy under the same filter, with their entry points.
+// them; its L1 candidate loss and dense scores are in l1_loss.hip), filtered negative sampling, the filtered rank (whole rows, and
+// streamed over column panels with a carry, plain and gate-mixed) and the all-entity cross-entropy under the same filter, with
+// their entry points.
 #include "common.hpp"
+#include "mix.hpp"
 #include "reduce.hpp"
+#include "row_filter.hpp"
 
 namespace temp {
 
@@ -330,52 +333,9 @@ __global__ void __launch_bounds__(256) k_filtered_rank(int N, int ld, const floa
 // barrier; above it one 256-thread workgroup per row, wave w on the steps w, w + 4, ... and one cross-wave reduction at the end.
 // The filter EXCLUDES: a listed entity gets the weight 0 before anything is summed (sum-then-subtract would cancel -- the listed
 // entities are the best-scored ones).  The ascending list is walked beside the ascending column steps, 64 entries at a time in
-// the wave's registers (one entry per lane): the entries inside the step's 256-entity window are found by one ballot, and each
-// is handed to the lane that owns its column.  A list of <= 64 entries (all but hub rows) is loaded once; a hub row's list is
-// reloaded 64 further entries at a time as the steps pass it.  Every wave of a workgroup walks the list on its own.
+// the wave's registers (row_filter.hpp, shared with the streamed rank below).
 // ---------------------------------------------------------------------------------------------
 #define FCE_WAVE_MAX_N 1024
-#define FCE_NO_ENTRY 0x7fffffff
-
-struct RowFilter {
-  const int32_t* ids;
-  int pos, end;                 // the 64 entries in the registers are ids[pos .. pos + 64) (clipped to end)
-  int v;                        // this lane's entry, FCE_NO_ENTRY past the end
-};
-__device__ __forceinline__ void filter_load(RowFilter& f, int lane) { f.v = f.pos + lane < f.end ? f.ids[f.pos + lane] : FCE_NO_ENTRY; }
-__device__ __forceinline__ RowFilter filter_open(const int32_t* __restrict__ lo, const int32_t* __restrict__ hi, const int32_t* __restrict__ ids, int p, int lane) {
-  RowFilter f;
-  f.ids = ids;
-  f.pos = lo ? lo[p] : 0;
-  f.end = lo ? hi[p] : 0;
-  filter_load(f, lane);
-  return f;
-}
-// Bit u set <=> entity w0 + 4 * lane + u is in the list; w0 = the first entity of the wave's step.  Called by all 64 lanes, with
-// w0 ascending from call to call.
-__device__ __forceinline__ unsigned filter_mask(RowFilter& f, int w0, int lane) {
-  unsigned mask = 0;
-  for (;;) {
-    unsigned long long hit = __ballot(f.v >= w0 && f.v < w0 + 256);
-    while (hit) {
-      const int i = __builtin_ctzll(hit);
-      hit &= hit - 1;
-      const int t = __shfl(f.v, i) - w0;
-      if ((t >> 2) == lane) mask |= 1u << (t & 3);
-    }
-    if (f.pos + 64 >= f.end || __shfl(f.v, 63) >= w0 + 256) break;       // the list, or this window, ends inside these 64 entries
-    f.pos += 64;
-    filter_load(f, lane);
-  }
-  return mask;
-}
-// -> the lane's four scores with everything inadmissible (listed and not the truth, or a pad column j >= N) replaced by `fill`
-__device__ __forceinline__ float4 filter_select(float4 x, unsigned mask, int e0, int truth, int left, float fill) {
-  const unsigned t = (unsigned)(truth - e0);
-  if (t < 4u) mask &= ~(1u << t);
-  if (left < 4) mask |= 0xfu << left;                                     // left >= 1 columns of the four lie below N
-  return make_float4((mask & 1u) ? fill : x.x, (mask & 2u) ? fill : x.y, (mask & 4u) ? fill : x.z, (mask & 8u) ? fill : x.w);
-}
 
 template <bool GROUP>
 __global__ void __launch_bounds__(256) k_filtered_ce_fwd(int P, int N, int ld, int col0, const float* __restrict__ scores, const int32_t* __restrict__ truth,
@@ -451,6 +411,70 @@ __global__ void __launch_bounds__(256) k_filtered_ce_bwd(int P, int N, int ld, i
       g = scale4(g, scale);
     }
     st4(drow + j, g);
+  }
+}
+
+// ---------------------------------------------------------------------------------------------
+// Streamed filtered rank (include/temp_amd.h: temp_filtered_rank_stream*): k_filtered_rank's definition on a COLUMN PANEL of the
+// row, entities col0 .. col0 + N - 1, with the target's score and the count carried from panel to panel.  The row is streamed as
+// in k_filtered_ce_fwd (one float4 per lane, 256 columns per wave step; MIX: two float4 and mix4 in registers) with the filter
+// list walked beside it: a listed entity that is not the target gets -inf, which rank_sigmoid turns into exactly 0 -- its VALUE,
+// it is still compared -- and a column j >= N is left out BY INDEX (`left`), whatever it holds: in a panel that is not the last
+// its would-be id lies below later targets.  No second pass, no random access into the row but the one read of the target's
+// column.  The target's own column goes through the same mix1 and rank_sigmoid as `ts`, compares equal and is not ahead.
+// Dispatch as the filtered cross-entropy's; TEMP_RANK_COLLECT reads one column per row and always takes the wave route.
+// ---------------------------------------------------------------------------------------------
+template <bool MIX>
+__device__ __forceinline__ float rank_stream_score(const float* __restrict__ arow, const float* __restrict__ brow, float w, int j) {
+  return MIX ? mix1(w, arow[j], brow[j]) : arow[j];
+}
+
+template <bool MIX, bool GROUP>
+__global__ void __launch_bounds__(256) k_filtered_rank_stream(int P, int N, int ld, int col0, const float* __restrict__ scores_a,
+                                                              const float* __restrict__ scores_b, const float* __restrict__ wrow,
+                                                              const int32_t* __restrict__ target, const int32_t* __restrict__ filt_ptr,
+                                                              const int32_t* __restrict__ filt_ids, int mode, float* __restrict__ target_score,
+                                                              int32_t* __restrict__ count, int32_t* __restrict__ ranks) {
+  __shared__ int red[4];
+  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+  const int p = GROUP ? blockIdx.x : blockIdx.x * 4 + w;
+  if (!GROUP && p >= P) return;                                           // (a whole wave: the wave route has no barrier)
+  const float* arow = scores_a + (size_t)p * ld;
+  const float* brow = MIX ? scores_b + (size_t)p * ld : nullptr;
+  const float wp = MIX ? wrow[p] : 0.f;
+  const int tgt = target[p];
+  const int jt = tgt - col0;
+  const bool inside = jt >= 0 && jt < N;
+  if (mode == TEMP_RANK_COLLECT) {
+    if (inside && lane == 0 && (!GROUP || w == 0)) target_score[p] = rank_stream_score<MIX>(arow, brow, wp, jt);
+    return;
+  }
+  // (TEMP_RANK_WHOLE with a target outside the panel breaks the contract: nothing is read out of bounds, the rank is that of a score of -inf)
+  const float ts = rank_sigmoid(mode == TEMP_RANK_WHOLE ? (inside ? rank_stream_score<MIX>(arow, brow, wp, jt) : -INFINITY) : target_score[p]);
+  RowFilter f = filter_open(filt_ptr, filt_ptr ? filt_ptr + 1 : nullptr, filt_ids, p, lane);
+  int cnt = 0;
+  for (int c = GROUP ? w * 256 : 0; c < N; c += GROUP ? 1024 : 256) {
+    const unsigned mask = filter_mask(f, col0 + c, lane);
+    const int j = c + lane * 4;
+    if (j < N) {
+      const int left = N - j, e = col0 + j;
+      const float4 raw = MIX ? mix4(wp, ld4(arow + j), ld4(brow + j)) : ld4(arow + j);
+      const float4 x = filter_select(raw, mask, e, tgt, left, -INFINITY);
+      cnt += rank_ahead(rank_sigmoid(x.x), e, ts, tgt) + ((left > 1) & rank_ahead(rank_sigmoid(x.y), e + 1, ts, tgt))
+           + ((left > 2) & rank_ahead(rank_sigmoid(x.z), e + 2, ts, tgt)) + ((left > 3) & rank_ahead(rank_sigmoid(x.w), e + 3, ts, tgt));
+    }
+  }
+#pragma unroll
+  for (int off = 32; off > 0; off >>= 1) cnt += __shfl_xor(cnt, off);
+  if (GROUP) {
+    if (lane == 0) red[w] = cnt;
+    __syncthreads();
+    cnt = (red[0] + red[1]) + (red[2] + red[3]);
+  }
+  if (GROUP ? threadIdx.x == 0 : lane == 0) {
+    if (mode == TEMP_RANK_COUNT_ADD) cnt += count[p];
+    if (mode != TEMP_RANK_WHOLE) count[p] = cnt;
+    ranks[p] = cnt + 1;
   }
 }
 
@@ -581,5 +605,52 @@ int temp_filtered_rank(int P, int N, int ld, const float* scores, const int32_t*
   TEMP_LAUNCH(K_GATHER_CE, k_filtered_rank, dim3(P), dim3(256), 0, (hipStream_t)stream, N, ld, scores, target, filt_ptr, filt_ids, ranks);
   return launch_status();
 }
+
+// the argument checks of both streamed-rank entry points (include/temp_amd.h); TEMP_OK with *launch = false for P == 0
+static int rank_stream_check(int P, int N, int ld, int col0, const float* a, const float* b, const float* w, bool mix, const void* target, int mode,
+                             const void* target_score, const void* count, const void* ranks, bool* launch) {
+  *launch = false;
+  if (P < 0 || N <= 0 || ld < N || col0 < 0 || (long long)col0 + ld + 256 >= 0x7fffffffLL || mode < TEMP_RANK_WHOLE || mode > TEMP_RANK_COUNT_ADD)
+    return TEMP_E_BADARG;
+  if (P > 0) {
+    if (!a || !target || (mix && (!b || !w))) return TEMP_E_BADARG;
+    if (mode == TEMP_RANK_COLLECT ? !target_score : !ranks) return TEMP_E_BADARG;
+    if ((mode == TEMP_RANK_COUNT_FIRST || mode == TEMP_RANK_COUNT_ADD) && (!target_score || !count)) return TEMP_E_BADARG;
+  }
+  if (ld % 4 || (uintptr_t)a % 16 || (mix && (uintptr_t)b % 16)) return TEMP_E_UNSUPPORTED;
+  *launch = P > 0;
+  return TEMP_OK;
+}
+
+#define RANK_STREAM_LAUNCH(KID, MIX)                                                                                                              \
+  do {                                                                                                                                            \
+    if (N <= FCE_WAVE_MAX_N || mode == TEMP_RANK_COLLECT)                                                                                         \
+      TEMP_LAUNCH(KID, (k_filtered_rank_stream<MIX, false>), dim3(ceil_div(P, 4)), dim3(256), 0, (hipStream_t)stream, P, N, ld, col0, scores_a,   \
+                  scores_b, w, target, filt_ptr, filt_ids, mode, target_score, count, ranks);                                                     \
+    else                                                                                                                                          \
+      TEMP_LAUNCH(KID, (k_filtered_rank_stream<MIX, true>), dim3(P), dim3(256), 0, (hipStream_t)stream, P, N, ld, col0, scores_a, scores_b, w,    \
+                  target, filt_ptr, filt_ids, mode, target_score, count, ranks);                                                                  \
+  } while (0)
+
+int temp_filtered_rank_stream(int P, int N, int ld, int col0, const float* scores, const int32_t* target, const int32_t* filt_ptr,
+                              const int32_t* filt_ids, int mode, float* target_score, int32_t* count, int32_t* ranks, void* stream) {
+  bool launch;
+  const int rc = rank_stream_check(P, N, ld, col0, scores, nullptr, nullptr, false, target, mode, target_score, count, ranks, &launch);
+  if (!launch) return rc;
+  const float *scores_a = scores, *scores_b = nullptr, *w = nullptr;
+  RANK_STREAM_LAUNCH(K_FILTERED_RANK_STREAM, false);
+  return launch_status();
+}
+
+int temp_filtered_rank_stream_mix(int P, int N, int ld, int col0, const float* scores_a, const float* scores_b, const float* w,
+                                  const int32_t* target, const int32_t* filt_ptr, const int32_t* filt_ids, int mode, float* target_score,
+                                  int32_t* count, int32_t* ranks, void* stream) {
+  bool launch;
+  const int rc = rank_stream_check(P, N, ld, col0, scores_a, scores_b, w, true, target, mode, target_score, count, ranks, &launch);
+  if (!launch) return rc;
+  RANK_STREAM_LAUNCH(K_FILTERED_RANK_STREAM_MIX, true);
+  return launch_status();
+}
+#undef RANK_STREAM_LAUNCH
 
 }  // extern "C"

@@ -12,7 +12,9 @@ Restructured for the device:
   * TransE is not bilinear: its P x N matrix of negative L1 distances is one register-tiled pass (`temp_l1_scores`) over the
     translation query, in place of the (100, N, D) broadcast per chunk of 100 triples;
   * the rank is the target's position in a stable descending order, computed by counting
-    (`temp_filtered_rank`) instead of sorting;
+    (`temp_filtered_rank`) instead of sorting; with `panel=` the count is carried across column panels
+    (`temp_filtered_rank_stream`, `_mix` for the two-table models: the gate mix happens in registers), so the P x N matrix never
+    exists at once -- every panel is then scored twice, once for the targets' scores and once for the count;
   * the ANSWERS of a query (s, r, ?, t) / (?, r, o, t) -- `topk_single_graph`, which the reference has no counterpart of -- are
     one selection pass over the same score rows (`temp_filtered_topk`): filter, total order (score, then entity id) and a
     list that is carried across column panels, so the Q x N matrix never has to exist at once;
@@ -92,6 +94,91 @@ def _select_mixed(be, k):
     return lambda s_a, s_b, w, k, *args, **kw: topk_composite(mixed_scores(s_a, s_b, w), k, *args, **kw)
 
 
+def rank_stream_torch(scores, target, filt_ptr=None, filt_ids=None, mode=_lib.RANK_WHOLE, col0=0, n=None, carry=None, scores_b=None, w=None):
+    """The contract of `temp_filtered_rank_stream` (scores_b, w given: of `temp_filtered_rank_stream_mix`, on w a + (1 - w) b) in
+    plain torch, all four modes -> (ranks [P] int64 | None, carry), carry = (target_score [P], count [P] int32) updated in place as by
+    the backend's entry points.  The other known-true entities of the panel get -10e6 before torch.sigmoid (tests/cpu_backend.py's
+    filtered_rank: their value is 0 and they are still compared), columns >= n are dropped by index.  The reference of the kernel's
+    tests, and the route of a backend without `filtered_rank_stream`."""
+    s = scores.detach()
+    n = s.shape[1] if n is None else int(n)
+    s = s[:, :n]
+    if scores_b is not None:
+        wc = torch.as_tensor(w, dtype=s.dtype, device=s.device).reshape(-1, 1)
+        s = wc * s + (1 - wc) * scores_b.detach()[:, :n]
+    P, dev = s.shape[0], s.device
+    tgt = target.long()
+    inside = (tgt >= col0) & (tgt < col0 + n)
+    if mode == _lib.RANK_COLLECT:
+        if carry is None:
+            carry = (torch.zeros(P, dtype=s.dtype, device=dev), torch.zeros(P, dtype=torch.int32, device=dev))
+        rows = torch.nonzero(inside).reshape(-1)
+        carry[0][rows] = s[rows, tgt[rows] - col0]
+        return None, carry
+    if mode == _lib.RANK_WHOLE:
+        if not bool(inside.all()):
+            raise ValueError("rank_stream_torch: TEMP_RANK_WHOLE needs every row's target inside the panel")
+        raw, carry = s.gather(1, (tgt - col0).view(-1, 1)), None
+    else:
+        if carry is None:
+            raise ValueError("rank_stream_torch: the counting modes need the carry of the TEMP_RANK_COLLECT sweep")
+        raw = carry[0].view(-1, 1)
+    s = s.clone()
+    if filt_ptr is not None and filt_ids is not None and filt_ids.numel():
+        ptr, fid = filt_ptr.long(), filt_ids.long()
+        rows = torch.repeat_interleave(torch.arange(P, device=dev), ptr[1:] - ptr[:-1])
+        m = (fid >= col0) & (fid < col0 + n) & (fid != tgt[rows])
+        s[rows[m], fid[m] - col0] = -10e6
+    # the sigmoid of every distinct score ONCE: equal scores must tie, and torch.sigmoid on the CPU rounds an element of a vector
+    # body and one of a scalar tail differently in the last bit -- the target's score is not where its column is
+    vals, inv = torch.unique(torch.cat([s.reshape(-1), raw.reshape(-1)]), return_inverse=True)
+    sig = torch.sigmoid(vals)[inv]
+    v, tv = sig[:s.numel()].view_as(s), sig[s.numel():].view(-1, 1)
+    ent = col0 + torch.arange(n, device=dev).view(1, n)
+    ahead = ((v > tv) | ((v == tv) & (ent < tgt.view(-1, 1)))).sum(dim=1)
+    if mode == _lib.RANK_WHOLE:
+        return ahead + 1, None
+    if mode == _lib.RANK_COUNT_FIRST:
+        carry[1].copy_(ahead)
+    else:
+        carry[1].add_(ahead.to(carry[1].dtype))
+    return carry[1].long() + 1, carry
+
+
+def _rank_plain(be):
+    """rank(scores, target, ptr, ids, mode=, col0=, n=, carry=): the backend's streamed rank, else its contract in torch."""
+    return be.filtered_rank_stream if hasattr(be, "filtered_rank_stream") else rank_stream_torch
+
+
+def _rank_mixed(be):
+    """rank(s_a, s_b, w, target, ptr, ids, mode=, col0=, n=, carry=) over mix(w, s_a, s_b): the backend's mixed kernel, else torch."""
+    if hasattr(be, "filtered_rank_stream_mix"):
+        return be.filtered_rank_stream_mix
+    return lambda s_a, s_b, w, *args, **kw: rank_stream_torch(s_a, *args, scores_b=s_b, w=w, **kw)
+
+
+def _rank_panel(panel, P, num_ent, matrices):
+    """Columns per pass of the streamed rank: `panel` as the caller gave it, "auto" as _topk_panel(None, ...) sizes it."""
+    return _topk_panel(None if isinstance(panel, str) and panel == "auto" else panel, P, num_ent, matrices)
+
+
+def _streamed_rank(rank, produce, num_ent, panel, target, ptr, ids):
+    """The filtered ranks of rows whose scores exist one column panel at a time.  produce(c0, c1) -> the leading operands of `rank`
+    for the entities c0 .. c1 - 1: (scores,) or (scores_a, scores_b, w), [P, ld] with c1 - c0 <= ld.  One panel: TEMP_RANK_WHOLE.
+    More: a TEMP_RANK_COLLECT sweep for the targets' scores, then a counting sweep that scores every panel AGAIN -- by the same
+    calls on the same inputs, so the target's column has the bits the first sweep saw."""
+    spans = [(c0, min(num_ent, c0 + panel)) for c0 in range(0, num_ent, panel)]
+    if len(spans) == 1:
+        return rank(*produce(0, num_ent), target, ptr, ids, mode=_lib.RANK_WHOLE, col0=0, n=num_ent)[0]
+    carry = None
+    for c0, c1 in spans:
+        carry = rank(*produce(c0, c1), target, ptr, ids, mode=_lib.RANK_COLLECT, col0=c0, n=c1 - c0, carry=carry)[1]
+    for i, (c0, c1) in enumerate(spans):
+        ranks, carry = rank(*produce(c0, c1), target, ptr, ids, mode=_lib.RANK_COUNT_ADD if i else _lib.RANK_COUNT_FIRST, col0=c0, n=c1 - c0,
+                            carry=carry)
+    return ranks
+
+
 class EvaluationFilter:
     def __init__(self, args, calc_score, graph_dict_train, graph_dict_val, graph_dict_test):
         self.args = args
@@ -166,8 +253,12 @@ class EvaluationFilter:
         assert target.shape[0] == samples.shape[0] and ptr.shape[0] == samples.shape[0] + 1, "filter lists do not match the samples"
         return target, ptr, ids
 
-    def calc_metrics_single_graph(self, ent_mean, rel_enc_means, all_ent_embeds, samples, graph, time, eval_bz=100):
-        """-> ranks (2P,) int64, subject-corruption ranks first, then object-corruption (reference order)."""
+    def calc_metrics_single_graph(self, ent_mean, rel_enc_means, all_ent_embeds, samples, graph, time, eval_bz=100, panel=None):
+        """-> ranks (2P,) int64, subject-corruption ranks first, then object-corruption (reference order).
+        panel: None scores all N entities at once and ranks with `temp_filtered_rank`.  A positive multiple of 4, or "auto" (the
+        widest panel that keeps the live score matrix at or under TOPK_PANEL_BYTES), takes the streamed rank (_streamed_rank) over
+        that many entities per pass: the [P, N] matrix never exists at once, at the price of scoring every panel twice when there
+        is more than one."""
         with torch.no_grad():
             dev = all_ent_embeds.device
             num_ent = all_ent_embeds.shape[0]
@@ -183,6 +274,18 @@ class EvaluationFilter:
                 target, ptr, ids = self._mode_inputs(mode, samples, graph, time, num_ent, dev)
                 known = ent_mean[samples[:, 0] if mode == "tail" else samples[:, 2]]
                 r = rel_enc_means[samples[:, 1]]
+                if panel is not None:
+                    be = get_backend()
+                    if fused:
+                        q = S.bilinear_query(name, known, r, mode).contiguous()
+                        produce = lambda c0, c1: (be.linear(q, all_ent_embeds[c0:c1].contiguous(), True),)
+                    elif l1:
+                        q = _translation_query(known, r, mode)
+                        produce = lambda c0, c1: (be.l1_scores(q, all_ent_embeds[c0:c1].contiguous()),)
+                    else:
+                        produce = lambda c0, c1: (self._literal_scores(known, r, all_ent_embeds[c0:c1], mode),)
+                    out[mode] = _streamed_rank(_rank_plain(be), produce, num_ent, _rank_panel(panel, P, num_ent, 1), target, ptr, ids)
+                    continue
                 if fused:
                     q = S.bilinear_query(name, known, r, mode).contiguous()
                     score = get_backend().linear(q, all_ent_embeds.contiguous(), True)
@@ -339,6 +442,16 @@ class _MixedRankFilter(EvaluationFilter):
         target, ptr, ids = self._mode_inputs(mode, samples, graph, time, num_ent, dev)
         return get_backend().filtered_rank(_pad4(score), target, ptr, ids)
 
+    def _mixed_rank_streamed(self, known_loc, known_rec, r, r_rec, all_loc, all_rec, w, mode, eval_bz, panel, inputs):
+        """The streamed rank over mix(w, score(known_loc, all_loc), score(known_rec, all_rec)): both panel matrices, from the routes of
+        _score_matrix, and the gate go to the mixed entry (`temp_filtered_rank_stream_mix`), so the mixed matrix is never written.
+        Two matrices are alive at once (what "auto" sizes the panel by)."""
+        P, num_ent = known_loc.shape[0], all_loc.shape[0]
+        w = w.reshape(-1).contiguous()
+        produce = lambda c0, c1: (self._score_matrix(known_loc, r, all_loc[c0:c1], mode, eval_bz, padded=True),
+                                  self._score_matrix(known_rec, r_rec, all_rec[c0:c1], mode, eval_bz, padded=True), w)
+        return _streamed_rank(_rank_mixed(get_backend()), produce, num_ent, _rank_panel(panel, P, num_ent, 2), *inputs)
+
 
 class PostEnsembleEvaluationFilter(_MixedRankFilter):
     """utils/post_evaluation.py:63-134: SCORE-level ensemble.  score = w * score(local) + (1 - w) * score(temporal), per triple
@@ -348,7 +461,9 @@ class PostEnsembleEvaluationFilter(_MixedRankFilter):
     models/aggregator.py:259-296; the two tables may differ in width); None, the default, scores both streams with `rel_enc_mean`."""
 
     def calc_metrics_single_graph(self, ent_embed_local, ent_embed_temporal, rel_enc_mean, all_embeds_g_local, all_embeds_g_temporal,
-                                  weight_subject, weight_object, samples, graph, time, eval_bz=100, rel_enc_temporal=None):
+                                  weight_subject, weight_object, samples, graph, time, eval_bz=100, rel_enc_temporal=None, panel=None):
+        """-> ranks (2P,) int64 as the base class's.  panel: as in EvaluationFilter.calc_metrics_single_graph; the streamed route
+        hands both streams' panel matrices and the weights to the mixed rank, so no mixed matrix is written."""
         with torch.no_grad():
             dev, num_ent, time, P = all_embeds_g_local.device, all_embeds_g_local.shape[0], int(time), samples.shape[0]
             if P == 0:
@@ -358,6 +473,11 @@ class PostEnsembleEvaluationFilter(_MixedRankFilter):
             out = {}
             for mode, w in (("head", weight_object), ("tail", weight_subject)):
                 sel = samples[:, 0] if mode == "tail" else samples[:, 2]
+                if panel is not None:
+                    out[mode] = self._mixed_rank_streamed(ent_embed_local[sel], ent_embed_temporal[sel], r, r_tmp, all_embeds_g_local, all_embeds_g_temporal,
+                                                          _w_col(w, P, all_embeds_g_local), mode, eval_bz, panel,
+                                                          self._mode_inputs(mode, samples, graph, time, num_ent, dev))
+                    continue
                 s_loc = self._score_matrix(ent_embed_local[sel], r, all_embeds_g_local, mode, eval_bz)
                 s_tmp = self._score_matrix(ent_embed_temporal[sel], r_tmp, all_embeds_g_temporal, mode, eval_bz)
                 wc = _w_col(w, P, s_loc)
@@ -393,7 +513,10 @@ class PostEvaluationFilter(_MixedRankFilter):
 
     def calc_metrics_single_graph(self, ent_embed_loc, ent_embed_rec, rel_enc_means, all_embeds_g_loc, all_embeds_g_rec, samples,
                                   weight_subject_query_subject_embed, weight_subject_query_object_embed,
-                                  weight_object_query_subject_embed, weight_object_query_object_embed, graph, time, eval_bz=100):
+                                  weight_object_query_subject_embed, weight_object_query_object_embed, graph, time, eval_bz=100, panel=None):
+        """-> ranks (2P,) int64 as the base class's.  panel: as in EvaluationFilter.calc_metrics_single_graph.  On the streamed route
+        the bilinear scorers hand the ONE folded query's two panel matrices and the candidate gate to the mixed rank; transE scores
+        each panel through `temp_l1_mix_scores` and takes the plain rank, as does the literal route over the mixed candidates."""
         with torch.no_grad():
             dev, num_ent, time, P = all_embeds_g_loc.device, all_embeds_g_loc.shape[0], int(time), samples.shape[0]
             if P == 0:
@@ -408,6 +531,10 @@ class PostEvaluationFilter(_MixedRankFilter):
                 w_known, w_cand = (ws, wo) if mode == "tail" else (wo, ws)     # tail: subject known; head: object known
                 known = w_known * ent_embed_loc[sel] + (1 - w_known) * ent_embed_rec[sel]
                 be = get_backend()
+                if panel is not None:
+                    out[mode] = self._gated_rank_streamed(be, name, known, r, all_embeds_g_loc, all_embeds_g_rec, w_cand, mode, eval_bz, panel,
+                                                          self._mode_inputs(mode, samples, graph, time, num_ent, dev))
+                    continue
                 if _l1_route(name, be, all_embeds_g_loc.shape[1]) and hasattr(be, "l1_mix_scores"):
                     # one pass over all P triples: the candidate mix formed inside the dense L1 kernel, the pad columns already -inf
                     score = be.l1_mix_scores(_translation_query(known, r, mode), all_embeds_g_loc.contiguous(), all_embeds_g_rec.contiguous(),
@@ -425,6 +552,22 @@ class PostEvaluationFilter(_MixedRankFilter):
                     score = torch.cat(rows)
                 out[mode] = self._rank(score, mode, samples, graph, time, num_ent, dev)
             return torch.cat([out["head"], out["tail"]])
+
+    def _gated_rank_streamed(self, be, name, known, r, all_loc, all_rec, w_cand, mode, eval_bz, panel, inputs):
+        """The streamed rank of the mixed known rows against the candidates w_cand all_loc + (1 - w_cand) all_rec, panel by panel, by
+        the score routes of topk_single_graph."""
+        P, (num_ent, d) = known.shape[0], all_loc.shape
+        if name in S.BILINEAR:
+            return self._mixed_rank_streamed(known, known, r, r, all_loc, all_rec, w_cand, mode, eval_bz, panel, inputs)
+        l1 = _l1_route(name, be, d) and hasattr(be, "l1_mix_scores")
+        if l1:
+            q, wc = _translation_query(known, r, mode), w_cand.contiguous()
+            produce = lambda c0, c1: (be.l1_mix_scores(q, all_loc[c0:c1].contiguous(), all_rec[c0:c1].contiguous(), wc),)       # the pad columns -inf
+        else:
+            wc = w_cand.unsqueeze(-1)
+            produce = lambda c0, c1: (self._literal_scores(known, r, wc * all_loc[c0:c1].unsqueeze(0) + (1 - wc) * all_rec[c0:c1].unsqueeze(0), mode),)
+        # one score matrix at a time; the literal route also holds the [P, panel, D] mixed candidates
+        return _streamed_rank(_rank_plain(be), produce, num_ent, _rank_panel(panel, P, num_ent, 1 if l1 else 1 + d), *inputs)
 
     def topk_single_graph(self, all_loc, all_rec, rel_enc_means, known, rel, w_known, w_cand, mode, time, k, filtered=True, keep=None,
                           panel=None):

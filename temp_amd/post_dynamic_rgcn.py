@@ -437,7 +437,7 @@ class _PostEnsembleMixin(_TwoStreamMixin):
         loc, rec = rows
         w_subject, w_object = self.calc_ensemble_ratio(index_sample, t, g)
         return self.evaluater.calc_metrics_single_graph(loc, rec, self.rel_embeds, alls[0], alls[1], w_subject, w_object,
-                                                        index_sample, g, t), None
+                                                        index_sample, g, t, **self._panel_kw()), None
 
 
 class PostEnsembleDynamicRGCN(_PostEnsembleMixin, ImputeDynamicRGCN):

@@ -240,4 +240,4 @@ class _GatedLossMixin(_FrequencyGateMixin):
         loc, rec = rows
         w_sqs, w_sqo, w_oqs, w_oqo = self.calc_ensemble_ratio(index_sample, t, g)
         return self.evaluater.calc_metrics_single_graph(loc, rec, self.rel_embeds, alls[0], alls[1], index_sample,
-                                                        w_sqs, w_sqo, w_oqs, w_oqo, g, t), None
+                                                        w_sqs, w_sqo, w_oqs, w_oqo, g, t, **self._panel_kw()), None

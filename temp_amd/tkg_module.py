@@ -371,6 +371,12 @@ class TKG_Module(nn.Module):
 
     # -- evaluation (models/TKG_Module.py:253-274) ---------------------------------------------------------------------------------
     _evaluater = "EvaluationFilter"       # the class of temp_amd.evaluation that ranks for this family
+    # evaluate() ranks against all entities at once (None), or in column panels of this many entities / of "auto" size
+    # (calc_metrics_single_graph's `panel`); handed on only when set, so an installed evaluater without the keyword keeps working
+    eval_panel = None
+
+    def _panel_kw(self):
+        return {} if self.eval_panel is None else {"panel": self.eval_panel}
 
     def _ranker(self):
         """The model's evaluation filter: the one the constructor built from `evaluater_type` or a caller installed as
@@ -394,7 +400,7 @@ class TKG_Module(nn.Module):
         train_link_prediction."""
         rel = self.rel_embeds if rel is None else rel
         label = torch.ones(index_sample.shape[0], device=index_sample.device)
-        return (self.evaluater.calc_metrics_single_graph(rows, rel, all_embeds_g, index_sample, g, t),
+        return (self.evaluater.calc_metrics_single_graph(rows, rel, all_embeds_g, index_sample, g, t, **self._panel_kw()),
                 self.link_classification_loss(rows, rel, index_sample, label))
 
     def evaluate(self, t_list, val=True):
