@@ -61,12 +61,22 @@ def assert_close(a, b, rtol=1e-5, atol=1e-6, what=""):
     assert a.shape == b.shape, "%s: shape %s vs %s" % (what, tuple(a.shape), tuple(b.shape))
     if a.numel() == 0:
         return
+    # Non-finite-strict.  Where `want` is finite, `got` must be finite and within atol + rtol |want| (written `~(err <= tol)`: a NaN
+    # error fails, where `err > tol` let it pass); where `want` is an infinity, `got` must be the same one; a NaN in `want` fails --
+    # a test that means "unspecified here" masks those elements itself and says why.
+    assert not torch.isnan(b).any(), ("%s: the reference itself is not finite (NaN) in %d/%d elements; mask what is unspecified "
+                                      "explicitly" % (what, int(torch.isnan(b).sum()), b.numel()))
+    fin = torch.isfinite(b)
     err = (a - b).abs()
     tol = atol + rtol * b.abs()
-    bad = err > tol
+    bad = torch.where(fin, ~(torch.isfinite(a) & (err <= tol)), a != b)
     if bad.any():
-        i = int(torch.argmax(err - tol))
+        # worst element: the largest excess over the bar, every non-finite mismatch counting as infinitely far out (NaN-free argmax)
+        excess = torch.where(bad, torch.where(fin & torch.isfinite(a), err - tol, torch.full_like(err, float("inf"))),
+                             torch.full_like(err, -float("inf")))
+        i = int(torch.argmax(excess))
         raise AssertionError("%s: %d/%d elements out of tolerance (rtol=%g atol=%g); worst |err|=%.3e at flat %d "
-                             "(got %.8g, want %.8g); max|want|=%.3e" %
-                             (what, int(bad.sum()), a.numel(), rtol, atol, float(err.view(-1)[i]), i,
-                              float(a.view(-1)[i]), float(b.view(-1)[i]), float(b.abs().max())))
+                             "(got %.8g, want %.8g); max|want|=%.3e; %d non-finite in got" %
+                             (what, int(bad.sum()), a.numel(), rtol, atol, float(err.reshape(-1)[i]), i,
+                              float(a.reshape(-1)[i]), float(b.reshape(-1)[i]), float(b.abs().max()),
+                              int((~torch.isfinite(a)).sum())))

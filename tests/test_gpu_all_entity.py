@@ -12,8 +12,9 @@ from temp_amd import backend as TB
 from tests import all_entity_cases as AC
 from tests.chain_route_cases import Launches
 from tests.test_gpu_row_loss_routes import _ce_bars, _traced, assert_close_strict
+from tests.poison import poisoned_allocations_fixture  # noqa: F401  (registers the fixture)
 
-pytestmark = pytest.mark.gpu
+pytestmark = [pytest.mark.gpu, pytest.mark.usefixtures("poisoned_allocations")]
 DEV = torch.device("cuda:0")
 
 

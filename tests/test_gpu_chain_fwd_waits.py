@@ -13,8 +13,9 @@ from temp_amd import _lib
 from temp_amd.gru_chain import GruInstance, GruProgram
 from tests.chain_cases import make_rnns, random_program
 from tests.test_gpu_chain_input_gates import DEV, _close, _cpu, _launches, _run, _x
+from tests.poison import poisoned_allocations_fixture  # noqa: F401  (registers the fixture)
 
-pytestmark = pytest.mark.gpu
+pytestmark = [pytest.mark.gpu, pytest.mark.usefixtures("poisoned_allocations")]
 
 # (d, random_program arguments, panel lengths the program must contain).  lo = 1 (5 for the longest panel): positions of a single row
 # up to full ones, so whole waves of a pass are idle and tracks start mid-chain; with K >= 4 the second chain has a position with no

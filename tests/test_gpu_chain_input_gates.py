@@ -12,8 +12,9 @@ from temp_amd import gru_chain as GC
 from temp_amd.gru_chain import GruInstance, GruProgram
 from tests.chain_cases import make_rnns, random_program
 from tests.golden_util import assert_close
+from tests.poison import poisoned_allocations_fixture  # noqa: F401  (registers the fixture)
 
-pytestmark = pytest.mark.gpu
+pytestmark = [pytest.mark.gpu, pytest.mark.usefixtures("poisoned_allocations")]
 DEV = torch.device("cuda:0")
 FWD_X_OFF = 1 << 22          # TEMP_DEBUG bit: callers take the gi route
 

@@ -21,8 +21,9 @@ from temp_amd import gru_chain as GC
 from temp_amd.backend import get_backend
 from tests.chain_cases import make_rnns, random_program
 from tests.golden_util import assert_close, load
+from tests.poison import poisoned_allocations_fixture  # noqa: F401  (registers the fixture)
 
-pytestmark = pytest.mark.gpu
+pytestmark = [pytest.mark.gpu, pytest.mark.usefixtures("poisoned_allocations")]
 DEV = torch.device("cuda:0")
 WB = (0.3, -0.7)             # dt in {1, 2, 3, 4} -> w dt + b in {-0.4, -0.1, 0.2, 0.5}: two clamped, two active, none 0
 SHAPES = [(200, False, dict(n_chain=2, K=6, E=90, lo=20, hi=70)),       # f16 route, fused forward, two GRUs sharing the decay

@@ -9,8 +9,9 @@ import torch
 
 from temp_amd import backend as TB
 from tests.chain_route_cases import GPU_CASES, run_route
+from tests.poison import poisoned_allocations_fixture  # noqa: F401  (registers the fixture)
 
-pytestmark = pytest.mark.gpu
+pytestmark = [pytest.mark.gpu, pytest.mark.usefixtures("poisoned_allocations")]
 
 EXPECTED = {
     "chain": [('gru_chain_pack_x_multi', (), ()),

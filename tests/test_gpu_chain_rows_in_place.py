@@ -13,8 +13,9 @@ from temp_amd import functional as TF
 from temp_amd import gru_chain as GC
 from tests.chain_cases import make_rnns
 from tests.chain_route_cases import GPU_CASES, QUERIES, recorded
+from tests.poison import poisoned_allocations_fixture  # noqa: F401  (registers the fixture)
 
-pytestmark = pytest.mark.gpu
+pytestmark = [pytest.mark.gpu, pytest.mark.usefixtures("poisoned_allocations")]
 DEV = torch.device("cuda:0") if torch.cuda.is_available() else torch.device("cpu")
 
 

@@ -36,8 +36,9 @@ from tests.chain_cases import make_rnns, random_program
 from tests.golden_util import assert_close, load
 from tests.test_gpu_chain_learnable_decay import (SHAPES, WB, _err, _out_insts, _params, _want, _x, check_decay_grads, has_prev_rows, loss_weights,
                                                    row_dt)
+from tests.poison import poisoned_allocations_fixture  # noqa: F401  (registers the fixture)
 
-pytestmark = pytest.mark.gpu
+pytestmark = [pytest.mark.gpu, pytest.mark.usefixtures("poisoned_allocations")]
 DEV = torch.device("cuda:0")
 T_ROWS = 7                   # timestamps of the table
 UNUSED = 4                   # ... of which no row uses this one: its d_table row must be exactly 0

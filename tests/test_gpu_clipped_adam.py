@@ -11,8 +11,9 @@ from temp_amd import backend as TB
 from temp_amd.optim import ClippedAdam
 from tests import clipped_adam_cases as AC
 from tests.golden_util import load
+from tests.poison import poisoned_allocations_fixture  # noqa: F401  (registers the fixture)
 
-pytestmark = pytest.mark.gpu
+pytestmark = [pytest.mark.gpu, pytest.mark.usefixtures("poisoned_allocations")]
 DEV = torch.device("cuda:0")
 E_BADARG, E_WORKSPACE = 1, 3
 

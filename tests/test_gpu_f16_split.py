@@ -10,8 +10,9 @@ import torch
 
 from temp_amd import _lib
 from temp_amd import backend as TB
+from tests.poison import poisoned_allocations_fixture  # noqa: F401  (registers the fixture)
 
-pytestmark = pytest.mark.gpu
+pytestmark = [pytest.mark.gpu, pytest.mark.usefixtures("poisoned_allocations")]
 DEV = torch.device("cuda:0") if torch.cuda.is_available() else torch.device("cpu")
 
 

@@ -13,8 +13,9 @@ import torch
 from temp_amd import _lib
 from temp_amd import backend as TB
 from temp_amd import functional as TF
+from tests.poison import poisoned_allocations_fixture  # noqa: F401  (registers the fixture)
 
-pytestmark = pytest.mark.gpu
+pytestmark = [pytest.mark.gpu, pytest.mark.usefixtures("poisoned_allocations")]
 DEV = torch.device("cuda:0")
 DOT, L1 = 0, 1
 KIND_NAME = {DOT: "dot", L1: "l1"}

@@ -15,8 +15,9 @@ from tests import transe_cases as TC
 from tests.golden_util import assert_close, load
 from tests.test_gpu_transe import _near_zero_head_slots, dv, within
 from tests.window_cases import build_post_model, make_args, slice_snapshots, window_inputs
+from tests.poison import poisoned_allocations_fixture  # noqa: F401  (registers the fixture)
 
-pytestmark = pytest.mark.gpu
+pytestmark = [pytest.mark.gpu, pytest.mark.usefixtures("poisoned_allocations")]
 DEV = torch.device("cuda:0") if torch.cuda.is_available() else None
 U = GC.U
 

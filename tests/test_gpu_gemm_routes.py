@@ -19,8 +19,9 @@ import torch
 from temp_amd import _lib
 from temp_amd import backend as TB
 from tests import gemm_route_cases as GC
+from tests.poison import poisoned_allocations_fixture  # noqa: F401  (registers the fixture)
 
-pytestmark = pytest.mark.gpu
+pytestmark = [pytest.mark.gpu, pytest.mark.usefixtures("poisoned_allocations")]
 DEV = torch.device("cuda:0")
 NAN = float("nan")
 NAN_BITS = 0x7FC00000          # what torch.full(..., nan) writes

@@ -12,8 +12,9 @@ from temp_amd import pair_view as PV
 from temp_amd import snapshot as S
 from temp_amd.snapshot import Snapshot
 from tests.golden_util import assert_close
+from tests.poison import poisoned_allocations_fixture  # noqa: F401  (registers the fixture)
 
-pytestmark = pytest.mark.gpu
+pytestmark = [pytest.mark.gpu, pytest.mark.usefixtures("poisoned_allocations")]
 DEV = torch.device("cuda:0")
 
 

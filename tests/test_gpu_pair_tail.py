@@ -14,8 +14,9 @@ from temp_amd import functional as TF
 from temp_amd import pair_view as PV
 from temp_amd.snapshot import Snapshot
 from tests.test_gpu_pair_route import compare_routes, pair_view
+from tests.poison import poisoned_allocations_fixture  # noqa: F401  (registers the fixture)
 
-pytestmark = pytest.mark.gpu
+pytestmark = [pytest.mark.gpu, pytest.mark.usefixtures("poisoned_allocations")]
 DEV = torch.device("cuda:0")
 DROP = (0.3, 0x5EED1234)
 

@@ -15,8 +15,9 @@ from tests.cpu_backend import CpuTestBackend
 from oracle import temp_oracle as O           # checker only (oracle/temp_oracle.py: the restatement pinned by the reference's goldens)
 from tests.encoder_cases import check_G2, check_G4, check_G6, check_G7
 from tests.golden_util import assert_close
+from tests.poison import poisoned_allocations_fixture  # noqa: F401  (registers the fixture)
 
-pytestmark = pytest.mark.gpu
+pytestmark = [pytest.mark.gpu, pytest.mark.usefixtures("poisoned_allocations")]
 DEV = torch.device("cuda:0")
 
 

@@ -18,8 +18,9 @@ import torch
 from oracle import temp_oracle as O
 from temp_amd import backend as TB
 from tests.golden_util import T, assert_close, load
+from tests.poison import poisoned_allocations_fixture  # noqa: F401  (registers the fixture)
 
-pytestmark = pytest.mark.gpu
+pytestmark = [pytest.mark.gpu, pytest.mark.usefixtures("poisoned_allocations")]
 DEV = torch.device("cuda:0")
 
 

@@ -11,8 +11,9 @@ from temp_amd import _lib
 from temp_amd import backend as TB
 from tests import post_aggregation_cases as PA
 from tests.golden_util import assert_close
+from tests.poison import poisoned_allocations_fixture  # noqa: F401  (registers the fixture)
 
-pytestmark = pytest.mark.gpu
+pytestmark = [pytest.mark.gpu, pytest.mark.usefixtures("poisoned_allocations")]
 DEV = torch.device("cuda:0")
 
 

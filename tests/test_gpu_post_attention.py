@@ -14,8 +14,9 @@ from temp_amd import functional as TF
 from tests import post_attention_cases as PC
 from tests.cpu_backend import CpuTestBackend
 from tests.golden_util import assert_close
+from tests.poison import poisoned_allocations_fixture  # noqa: F401  (registers the fixture)
 
-pytestmark = pytest.mark.gpu
+pytestmark = [pytest.mark.gpu, pytest.mark.usefixtures("poisoned_allocations")]
 DEV = torch.device("cuda:0")
 E_BADARG, E_UNSUPPORTED = 1, 2
 

@@ -12,8 +12,9 @@ from temp_amd import _lib
 from temp_amd import backend as TB
 from temp_amd import functional as TF
 from temp_amd.snapshot import Snapshot
+from tests.poison import poisoned_allocations_fixture  # noqa: F401  (registers the fixture)
 
-pytestmark = pytest.mark.gpu
+pytestmark = [pytest.mark.gpu, pytest.mark.usefixtures("poisoned_allocations")]
 DEV = torch.device("cuda:0")
 TEMP_OK = 0                                                 # include/temp_amd.h
 

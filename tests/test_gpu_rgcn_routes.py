@@ -26,8 +26,9 @@ from temp_amd import _lib
 from temp_amd import backend as TB
 from temp_amd import functional as TF
 from tests import rgcn_route_cases as RC
+from tests.poison import poisoned_allocations_fixture  # noqa: F401  (registers the fixture)
 
-pytestmark = pytest.mark.gpu
+pytestmark = [pytest.mark.gpu, pytest.mark.usefixtures("poisoned_allocations")]
 DEV = torch.device("cuda:0")
 NAN = float("nan")
 NAN_BITS = 0x7FC00000          # what torch.full(..., nan) writes

@@ -17,8 +17,9 @@ from temp_amd import backend as TB
 from temp_amd import functional as TF
 from tests import row_loss_route_cases as RC
 from tests.cpu_backend import CpuTestBackend
+from tests.poison import poisoned_allocations_fixture  # noqa: F401  (registers the fixture)
 
-pytestmark = pytest.mark.gpu
+pytestmark = [pytest.mark.gpu, pytest.mark.usefixtures("poisoned_allocations")]
 DEV = torch.device("cuda:0")
 NAN = float("nan")
 

@@ -11,8 +11,9 @@ from temp_amd import link_loss as LL
 from temp_amd import scores as SC
 from tests import transe_cases as TC
 from tests.golden_util import assert_close
+from tests.poison import poisoned_allocations_fixture  # noqa: F401  (registers the fixture)
 
-pytestmark = pytest.mark.gpu
+pytestmark = [pytest.mark.gpu, pytest.mark.usefixtures("poisoned_allocations")]
 DEV = torch.device("cuda:0") if torch.cuda.is_available() else None
 
 
