@@ -67,7 +67,7 @@ inline size_t chain_lds_fwd_hx(int D, int ms) {
 }
 inline size_t chain_lds_bwd_hx(int D, int ms) {
   const ChainGeomHx g = chain_geom_hx(D);
-  return 2 * (size_t)CH_SLOTS * g.ldpa + 2 * (size_t)CH_SLOTS * g.ldz * 4 + (2 * CH_SLOTS + 3) * (size_t)ms * 4 + CH_SLOTS * 4 + 4 * (size_t)D * 4;
+  return 2 * (size_t)CH_SLOTS * g.ldpa + 2 * (size_t)CH_SLOTS * g.ldz * 4 + (2 * CH_SLOTS + 3) * (size_t)ms * 4 + CH_SLOTS * 4 + 4 * (size_t)D * 4 + (size_t)g.NTb * 32 * 4;
 }
 // packed W_hh of one GRU (16-byte items): [forward planes | backward planes | forward keys (NT * 32) | backward keys (NTb * 32)]
 inline size_t chain_hx_fwd_items(int D) { const ChainGeomHx g = chain_geom_hx(D); return (size_t)g.NS * g.NT * 128; }
@@ -355,19 +355,26 @@ __global__ void __launch_bounds__(64 * (NMW + MW)) k_gru_chain_fwd_x(ChainArgs a
     __syncthreads();
 
       // ------------------------------------------------------------------ matrix role
+      // Compiled once per number of valid tiles NV of the wave (TPW or TPW - 1: the launcher instantiates TPW = ceil(NT / NMW)) and
+      // dispatched once per panel: with a validity flag per tile every plane load of a walk sat in a wave-uniform branch and the
+      // compiler put `s_waitcnt vmcnt(0)` at the head of every slab -- a wait that also covered the plane loaded three products
+      // earlier.  Straight-line slabs get counted waits (NV = 3: vmcnt(5), (4), (3) in front of a plane's three first products: the
+      // other plane's loads stay in flight).  Loading the clamped tile instead (as k_gru_chain_bwd_hx does, for a reason this kernel
+      // does not share: its roles run separate panel loops) would stream 5 of 24 tile columns twice at d = 200.
+      auto role = [&](auto nv_c) __attribute__((always_inline)) {
+      constexpr int NV = decltype(nv_c)::value, NVA = NV > 0 ? NV : 1;
       const int li = lane & 31, hh = lane >> 5;
-      bool tval[TPW];
-      int tidx[TPW];
+      int tidx[NVA];
 #pragma unroll
-      for (int j = 0; j < TPW; ++j) { tidx[j] = wave + NMW * j; tval[j] = tidx[j] < NT; if (!tval[j]) tidx[j] = NT - 1; }
-      f32x16 acc[TPW];
+      for (int j = 0; j < NVA; ++j) tidx[j] = wave + NMW * j < NT ? wave + NMW * j : NT - 1;         // (never clamped for j < NV)
+      f32x16 acc[NVA];
 #pragma unroll
-      for (int j = 0; j < TPW; ++j)
+      for (int j = 0; j < NVA; ++j)
 #pragma unroll
         for (int r = 0; r < 16; ++r) acc[j][r] = 0.f;
       const hx_u32x4* wph = reinterpret_cast<const hx_u32x4*>(R.wf);
       const hx_u32x4* wpi = X.wi[rnn_id];
-      hx_u32x4 w[2][TPW] = {};                                   // [plane h, l][tile]: one slab of the stream being walked
+      hx_u32x4 w[2][NVA] = {};                                   // [plane h, l][tile]: one slab of the stream being walked
       const std::integral_constant<int, 0> P0;
       const std::integral_constant<int, 1> P1;
       // ln: the lane index (a walk hands in a copy the compiler cannot tell from a fresh value, so that the lane-dependent
@@ -375,8 +382,8 @@ __global__ void __launch_bounds__(64 * (NMW + MW)) k_gru_chain_fwd_x(ChainArgs a
       auto wload = [&](const hx_u32x4* wp, int sl, auto pl_c, int ln) __attribute__((always_inline)) {
         constexpr int pl = decltype(pl_c)::value;
 #pragma unroll
-        for (int j = 0; j < TPW; ++j)
-          if (tval[j]) w[pl][j] = *reinterpret_cast<const hx_u32x4*>(reinterpret_cast<const char*>(wp) + (unsigned)((((sl * NT + tidx[j]) * 2 + pl) * 64 + ln) * 16));
+        for (int j = 0; j < NV; ++j)
+          w[pl][j] = *reinterpret_cast<const hx_u32x4*>(reinterpret_cast<const char*>(wp) + (unsigned)((((sl * NT + tidx[j]) * 2 + pl) * 64 + ln) * 16));
       };
       const int rot = (dbg & 64) ? 0 : (int)(blockIdx.x >> 3) % NS;
       auto at = [&](int j) { const int v = rot + j; return v < NS ? v : v - NS; };
@@ -385,9 +392,21 @@ __global__ void __launch_bounds__(64 * (NMW + MW)) k_gru_chain_fwd_x(ChainArgs a
       // a walk over the NS slabs of one stream (wcur) with the fragments of `pl0` (the state or the x planes); behind its last slab
       // the registers are refilled with the first slab of the stream walked next (wnext)
       bool holds_ih = true;
-      wload(wpi, rot, P0, lane); wload(wpi, rot, P1, lane);
+      // the first slab of a stream, loaded in the order a walk uses and refills the planes (l, then h) and kept in it: the wait at the
+      // head of a walk is the weaker of what the ways into it ask for, and with h in front of l this one asked for vmcnt(0)
+      auto prime = [&](const hx_u32x4* wp) __attribute__((always_inline)) {
+        int ln = lane;
+        asm volatile("" : "+v"(ln));
+        __builtin_amdgcn_sched_barrier(0);
+        wload(wp, rot, P1, ln);
+        __builtin_amdgcn_sched_barrier(0);
+        wload(wp, rot, P0, ln);
+        __builtin_amdgcn_sched_barrier(0);
+      };
+      prime(wpi);
       // prod = false (development probe, dbg bits 0 / 11): the weights stream, no products issue
       auto walk = [&](const bool prod, const char* pl0, const hx_u32x4* wcur, const hx_u32x4* wnext) __attribute__((always_inline)) {
+        if constexpr (NV == 0) return;                           // (a wave without a tile only keeps the barriers)
         int ln = lane;
         asm volatile("" : "+v"(ln));
         const char* arow = pl0 + (size_t)(ln & 31) * ldp + 16 * (ln >> 5);
@@ -403,7 +422,7 @@ __global__ void __launch_bounds__(64 * (NMW + MW)) k_gru_chain_fwd_x(ChainArgs a
           const hx_f16x8 ah = hx_frag(FH), al = hx_frag(FL);
           __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
-          for (int t = 0; t < TPW; ++t) {
+          for (int t = 0; t < NV; ++t) {
             if (prod) acc[t] = __builtin_amdgcn_mfma_f32_32x32x16_f16(hx_frag(w[1][t]), ah, acc[t], 0, 0, 0);
             else asm volatile("" : : "v"(w[1][t]));
           }
@@ -412,12 +431,12 @@ __global__ void __launch_bounds__(64 * (NMW + MW)) k_gru_chain_fwd_x(ChainArgs a
           __builtin_amdgcn_sched_barrier(0);
           if (prod) {
 #pragma unroll
-            for (int t = 0; t < TPW; ++t) acc[t] = __builtin_amdgcn_mfma_f32_32x32x16_f16(hx_frag(w[0][t]), al, acc[t], 0, 0, 0);
+            for (int t = 0; t < NV; ++t) acc[t] = __builtin_amdgcn_mfma_f32_32x32x16_f16(hx_frag(w[0][t]), al, acc[t], 0, 0, 0);
 #pragma unroll
-            for (int t = 0; t < TPW; ++t) acc[t] = __builtin_amdgcn_mfma_f32_32x32x16_f16(hx_frag(w[0][t]), ah, acc[t], 0, 0, 0);
+            for (int t = 0; t < NV; ++t) acc[t] = __builtin_amdgcn_mfma_f32_32x32x16_f16(hx_frag(w[0][t]), ah, acc[t], 0, 0, 0);
           } else {
 #pragma unroll
-            for (int t = 0; t < TPW; ++t) asm volatile("" : : "v"(w[0][t]));
+            for (int t = 0; t < NV; ++t) asm volatile("" : : "v"(w[0][t]));
           }
           __builtin_amdgcn_sched_barrier(0);
           wload(wn, sn, P0, ln);
@@ -427,12 +446,12 @@ __global__ void __launch_bounds__(64 * (NMW + MW)) k_gru_chain_fwd_x(ChainArgs a
       };
       // x . W_ih of the next position into acc, then into the units the rest of the position expects
       auto xprod = [&]() __attribute__((always_inline)) {
-        if (!holds_ih) { wload(wpi, rot, P0, lane); wload(wpi, rot, P1, lane); }
+        if (!holds_ih) prime(wpi);
         walk(!(dbg & (1 | 2048)), xpl, wpi, wph);
         holds_ih = false;
         const float f = hx_inv_scale(xkey[li]) * CHX_STATE_SCALE;       // (x . s_row) -> (x . 2^14): the units of the state's planes
 #pragma unroll
-        for (int j = 0; j < TPW; ++j)
+        for (int j = 0; j < NV; ++j)
 #pragma unroll
           for (int r = 0; r < 16; ++r) acc[j][r] *= f;
       };
@@ -447,8 +466,7 @@ __global__ void __launch_bounds__(64 * (NMW + MW)) k_gru_chain_fwd_x(ChainArgs a
         CHX_STAMP(s, 0);
         // gi_n of position s -> gin, out of the accumulators
 #pragma unroll
-        for (int j = 0; j < TPW; ++j) {
-          if (!tval[j]) continue;
+        for (int j = 0; j < NV; ++j) {
 #pragma unroll
           for (int qq = 0; qq < 4; ++qq) {
             const int c = tidx[j] * 32 + 8 * qq + 4 * hh;
@@ -458,15 +476,14 @@ __global__ void __launch_bounds__(64 * (NMW + MW)) k_gru_chain_fwd_x(ChainArgs a
           }
         }
         if ((flags & 1) && !(dbg & 1)) {
-          if (holds_ih) { wload(wph, rot, P0, lane); wload(wph, rot, P1, lane); }
+          if (holds_ih) prime(wph);
           walk(true, hpl, wph, wpi);
           holds_ih = true;
         }
         CHX_STAMP(s, 1);
         // lane (li, hh) owns track li and, per register quad qq, gate columns tile*32 + 8qq + 4hh .. +3
 #pragma unroll
-        for (int j = 0; j < TPW; ++j) {
-          if (!tval[j]) continue;
+        for (int j = 0; j < NV; ++j) {
           float* dst = accb + (size_t)li * lda + tidx[j] * 32 + 4 * hh;
 #pragma unroll
           for (int qq = 0; qq < 4; ++qq) {
@@ -482,6 +499,9 @@ __global__ void __launch_bounds__(64 * (NMW + MW)) k_gru_chain_fwd_x(ChainArgs a
         __syncthreads();      // B: the split (decayed) state of position s is in LDS
         CHX_STAMP(s, 5);
       }
+      };
+      if (wave + NMW * (TPW - 1) < NT) role(std::integral_constant<int, TPW>());
+      else role(std::integral_constant<int, TPW - 1>());
     __syncthreads();          // LDS is re-initialised for the next panel
   }
   } else {
@@ -661,7 +681,8 @@ __global__ void __launch_bounds__(64 * (NMW + MW)) k_gru_chain_bwd_hx(ChainArgs 
   char* apl = (char*)lds;                                        // [2 planes][32][ldpa bytes]  [dr | dz | dn_h] of the position, scaled per row, split
   float* gzb = (float*)(apl + 2 * CH_SLOTS * ldpa);              // [32][ldz]  dh * z
   float* dpb = gzb + CH_SLOTS * ldz;                             // [32][ldz]  d_prev of the position just processed
-  int* tabb = (int*)(dpb + CH_SLOTS * ldz);                      // [ms][32] the panel's row table
+  float* kinv = dpb + CH_SLOTS * ldz;                            // [NTb * 32] 1 / column scale of the panel's W_hh planes (the d_prev epilogue: see there; 16-byte aligned)
+  int* tabb = (int*)(kinv + NTb * 32);                           // [ms][32] the panel's row table
   float* decb = (float*)(tabb + CH_SLOTS * a.max_steps);         // [ms][32]
   int* flagb = (int*)(decb + CH_SLOTS * a.max_steps);            // [ms]
   int* upb = flagb + a.max_steps;                                // [ms][2] upstream block and its first row of every step
@@ -675,6 +696,7 @@ __global__ void __launch_bounds__(64 * (NMW + MW)) k_gru_chain_bwd_hx(ChainArgs 
     const ChainRnn R = a.rnn[rnn_id];
     for (int i = tid; i < 2 * CH_SLOTS * ldpa / 16; i += blockDim.x) reinterpret_cast<hx_u32x4*>(apl)[i] = hx_u32x4{0u, 0u, 0u, 0u};   // k padding
     for (int i = tid; i < 4 * D; i += blockDim.x) ckey[i] = 0u;
+    for (int i = tid; i < NTb * 32; i += blockDim.x) kinv[i] = hx_inv_scale(R.kb[i]);
     if (tid < ns) { upb[2 * tid] = a.sinfo[4 * (size_t)(s0 + tid) + 1]; upb[2 * tid + 1] = a.sinfo[4 * (size_t)(s0 + tid) + 2]; }
     for (int i = tid; i < ns * CH_SLOTS; i += blockDim.x) {
       const int e = a.rows[(size_t)s0 * CH_SLOTS + i];
@@ -686,7 +708,11 @@ __global__ void __launch_bounds__(64 * (NMW + MW)) k_gru_chain_bwd_hx(ChainArgs 
 
     if (wave < NMW) {
       // ------------------------------------------------------------------ matrix role: d_prev = (dgh . W_hh + dh*z) * decay
-      const int li = lane & 31, hh = lane >> 5;
+      // (the role's lane-dependent values are formed per panel, from a copy of the lane index the compiler cannot tell from a fresh
+      //  value: hoisted above the panel loop they are live -- and take registers -- throughout the memory role's gate passes)
+      int rl = lane;
+      asm volatile("" : "+v"(rl));
+      const int li = rl & 31, hh = rl >> 5;
       bool tval[TPWB];
       int tidx[TPWB];
 #pragma unroll
@@ -697,17 +723,39 @@ __global__ void __launch_bounds__(64 * (NMW + MW)) k_gru_chain_bwd_hx(ChainArgs 
 #pragma unroll
         for (int r = 0; r < 16; ++r) acc[j][r] = 0.f;
       // W_hh planes of FOUR slabs in registers (a slab is only 3 TPWB products): set q holds slab 4 i + q and is refilled with slab
-      // 4 i + q + 4 as its planes fall free -- three slabs (18 products at TPWB = 2) of L2 latency cover.  NSb is a multiple of 4.
+      // 4 i + q + 4 as its planes fall free, so a plane has the products of three slabs (18 at TPWB = 2) to arrive in.  NSb is a
+      // multiple of 4.  That cover exists only while the compiler can COUNT the loads in flight: the vector-memory counter is in
+      // order, and the wait in front of a plane's first product must let the 14 loads younger than it (TPWB = 2) stay out.
+      //  * The loads are unconditional.  A tile this wave does not own (tval[j] false) streams the clamped tile NTb - 1 into its
+      //    registers; its products are never stored.  With `if (tval[j])` around each load every reload sat in a wave-uniform branch
+      //    of its own, the number of loads in flight differed by path, and the wait insertion fell back to ONE `s_waitcnt vmcnt(0)`
+      //    at the head of every group of four slabs: a full L2 round trip exposed per group, no cover from the ring at all.
+      //    Specialising the role on the wave's number of valid tiles was built first (no byte streamed twice).  It puts two copies of
+      //    the role into the kernel, and at the 168 registers this kernel is held to the MEMORY role's gate passes then came out with
+      //    two scratch reloads and five scalar reloads of kernel arguments inside the position loop.  The clamped loads leave the
+      //    memory role's code as it was; what they cost at d = 200 is one of eight tile streams read twice, by the neighbour wave of
+      //    the one that owns it and at the same slab, out of the same cache lines.
+      //  * The ring is primed in the order the walk uses and refills it (l, then h, slab by slab), and the priming stays in that
+      //    order: the wait at the head of the walk is the weaker of what the ways into it ask for, and with the priming's loads in
+      //    another order (the compiler's, without the barriers below) every group waited `vmcnt(1)`.
       const hx_u32x4* wp = reinterpret_cast<const hx_u32x4*>(R.wb);
       hx_u32x4 wh[RING][TPWB] = {}, wl[RING][TPWB] = {};
       auto wload = [&](hx_u32x4 (&w)[TPWB], int sl, int pl) {
 #pragma unroll
-        for (int j = 0; j < TPWB; ++j)
-          if (tval[j]) w[j] = wp[((size_t)(sl * NTb + tidx[j]) * 2 + pl) * 64 + lane];
+        for (int j = 0; j < TPWB; ++j) w[j] = wp[((size_t)(sl * NTb + tidx[j]) * 2 + pl) * 64 + rl];         // (tidx[j] <= NTb - 1: inside the pack)
       };
       const int rot = (a.dbg & 64) ? 0 : RING * ((int)(blockIdx.x >> 3) % (NSb / RING));     // per-block start of the slab walk (NSb % RING == 0)
+      // (a wave without any tile -- widths with NTb < NMW -- loads and multiplies nothing; it still keeps barriers A and B below)
+      const bool walks = tval[0];
+      if (walks) {
 #pragma unroll
-      for (int q = 0; q < RING; ++q) { wload(wh[q], rot + q, 0); wload(wl[q], rot + q, 1); }
+        for (int q = 0; q < RING; ++q) {
+          wload(wl[q], rot + q, 1);
+          __builtin_amdgcn_sched_barrier(0);
+          wload(wh[q], rot + q, 0);
+          __builtin_amdgcn_sched_barrier(0);
+        }
+      }
       const char* arow = apl + (size_t)li * ldpa + 16 * hh;      // + plane * 32 ldpa + 32 slab
       const int pl1 = CH_SLOTS * ldpa;
       long long* stp = p == (int)blockIdx.x ? chx_stamp_rows<DEV>(a.stamp, 1, 0, wave == 0, lane) : nullptr;
@@ -716,7 +764,7 @@ __global__ void __launch_bounds__(64 * (NMW + MW)) k_gru_chain_bwd_hx(ChainArgs 
         CHX_STAMP(s, 0);
         __syncthreads();      // A: the split gate gradients / dh*z / row scales of position s are in LDS
         CHX_STAMP(s, 1);
-        if ((flags & 1) && !(a.dbg & 1)) {                      // (dbg bit 0: development ablation, no products)
+        if (walks && (flags & 1) && !(a.dbg & 1)) {             // (dbg bit 0: development ablation, no products)
           hx_u32x4 FH = *reinterpret_cast<const hx_u32x4*>(arow + 32 * rot), FL = *reinterpret_cast<const hx_u32x4*>(arow + pl1 + 32 * rot), NH, NL;
           for (int j = 0, sl = rot; j < NSb; j += RING) {
             const int base2 = sl + RING < NSb ? sl + RING : 0;          // (after the walk's last group: the first group of the NEXT position)
@@ -751,7 +799,10 @@ __global__ void __launch_bounds__(64 * (NMW + MW)) k_gru_chain_bwd_hx(ChainArgs 
             for (int qq = 0; qq < 4; ++qq) {
               const int c = tidx[j] * 32 + 8 * qq + 4 * hh;
               const float4 gz = ld4(gzb + (size_t)li * ldz + c);
-              const float i0 = hx_inv_scale(R.kb[c]) * ri, i1 = hx_inv_scale(R.kb[c + 1]) * ri, i2 = hx_inv_scale(R.kb[c + 2]) * ri, i3 = hx_inv_scale(R.kb[c + 3]) * ri;
+              // (the inverse column scales come out of LDS: read from global memory here, each of the eight reads waited, in order,
+              //  behind the sixteen reloads the walk has just issued for the NEXT position -- 6 900 cycles where the parent took 2 300)
+              const float4 kv = ld4(kinv + c);
+              const float i0 = kv.x * ri, i1 = kv.y * ri, i2 = kv.z * ri, i3 = kv.w * ri;
               st4(dpb + (size_t)li * ldz + c, make_float4((acc[j][4 * qq] * i0 + gz.x) * dec, (acc[j][4 * qq + 1] * i1 + gz.y) * dec,
                                                            (acc[j][4 * qq + 2] * i2 + gz.z) * dec, (acc[j][4 * qq + 3] * i3 + gz.w) * dec));
               acc[j][4 * qq] = 0.f; acc[j][4 * qq + 1] = 0.f; acc[j][4 * qq + 2] = 0.f; acc[j][4 * qq + 3] = 0.f;
