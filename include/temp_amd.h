@@ -1003,6 +1003,50 @@ int temp_l1_mix_scores(int P, int N, int d, const float* q, const float* table_a
                        float* scores, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * Candidate-gather loss of the bilinear scorers (distmult / complex / simple with the inner-product query q of temp_bilinear_query_fwd
+ * or temp_gated_query_fwd):  score(p, c) = +sum_d q[p,d] c[d], read at the C = 1 + negative_rate candidates of every row straight
+ * from the table(s) -- the temp_l1_* calls above with a dot product where the L1 distance stands, argument for argument.  No (P, N)
+ * score matrix and no LDS ceiling on the entity count (temp_gather_ce_bwd / temp_gather_ce_mix_bwd refuse N > 40704).
+ *
+ * temp_dot_ce_fwd:       s_out[p,k] = sum_d q[p,d] table[base[p] + cand[p,k], d]   (base NULL = 0; one launch covers all windows, as
+ *                        temp_l1_ce_fwd);  lse_rows[p] = logsumexp_k s_out[p,k];  loss_rows[p] = lse_rows[p] - s_out[p,0].
+ *                        C == 1: loss exactly 0.
+ * temp_dot_ce_bwd_q:     g_out[p,k] = scale[0] * (row_scale ? row_scale[p] : inv_rows) * (exp(s[p,k] - lse_rows[p]) - [k == 0]);
+ *                        d_q[p,:] = sum_k g_out[p,k] e_k,  e_k the candidate's table row.  Duplicate candidates each count; a
+ *                        weight-0 row gives exact zeros in g_out and d_q (finite tables).
+ * temp_dot_ce_bwd_table: slot / slot_ptr as temp_l1_ce_bwd_table;
+ *                        d_table[n,:] = sum_{i in [slot_ptr[n], slot_ptr[n+1])} g[slot[i]] q[slot[i] / C, :];  zeros for a row without
+ *                        slots.  `table` is checked but not read.
+ * Gated (two tables, the row's candidate weight):  e[p,k] = mix(w[p], table_a[row], table_b[row]),  mix(w, a, b) = fmaf(w, a, (1 - w) * b),
+ * formed in registers from both rows (w == 1 / w == 0 give the one-table scores of table_a / table_b):
+ * temp_dot_mix_ce_fwd:       s_out[p,k] = sum_d q[p,d] e[p,k,d];  lse_rows, loss_rows as above.
+ * temp_dot_mix_ce_bwd_q:     g_out as above;  d_q[p,:] = sum_k g_out[p,k] e[p,k,:];
+ *                            d_w[p] = sum_k g_out[p,k] sum_d q[p,d] (table_a - table_b)[row, d]     ([P], same pass).
+ * temp_dot_mix_ce_bwd_table: d_table_a[n,:] = sum_slots w[p] g[slot] q[p,:],  d_table_b[n,:] = sum_slots (1 - w[p]) g[slot] q[p,:],
+ *                            p = slot / C;  one pass over the row's slots writes both; zeros for a row without slots.
+ *
+ * P < 0 (n_rows < 0), C <= 0, d <= 0: TEMP_E_BADARG;  d % 4 != 0 or P C >= 2^31: TEMP_E_UNSUPPORTED;  P == 0 (n_rows == 0) returns
+ * success without a launch, before the pointer checks; with work, a NULL pointer where one is required is TEMP_E_BADARG (base and
+ * row_scale are nullable; q, w, slot and g of a bwd_table call whose lists are all empty are not read).  fp32, all outputs fully
+ * written, no workspace, no floating-point atomics; every sum has a fixed order: results are bit-repeatable.
+ * ---------------------------------------------------------------------------------------------- */
+int temp_dot_ce_fwd(int P, int C, int d, const float* q, const float* table, const int32_t* base /* nullable [P] */, const int32_t* cand,
+                    float* s_out, float* loss_rows, float* lse_rows, void* stream);
+int temp_dot_ce_bwd_q(int P, int C, int d, const float* q, const float* table, const int32_t* base /* nullable [P] */, const int32_t* cand,
+                      const float* s, const float* lse_rows, const float* scale /* device float */, float inv_rows,
+                      const float* row_scale /* nullable [P] */, float* g_out, float* d_q, void* stream);
+int temp_dot_ce_bwd_table(int n_rows, int d, int C, const float* q, const float* table, const int32_t* slot_ptr, const int32_t* slot,
+                          const float* g, float* d_table, void* stream);
+int temp_dot_mix_ce_fwd(int P, int C, int d, const float* q, const float* table_a, const float* table_b, const float* w,
+                        const int32_t* base /* nullable [P] */, const int32_t* cand, float* s_out, float* loss_rows, float* lse_rows, void* stream);
+int temp_dot_mix_ce_bwd_q(int P, int C, int d, const float* q, const float* table_a, const float* table_b, const float* w,
+                          const int32_t* base /* nullable [P] */, const int32_t* cand, const float* s, const float* lse_rows,
+                          const float* scale /* device float */, float inv_rows, const float* row_scale /* nullable [P] */, float* g_out,
+                          float* d_q, float* d_w, void* stream);
+int temp_dot_mix_ce_bwd_table(int n_rows, int d, int C, const float* q, const float* table_a, const float* table_b, const float* w,
+                              const int32_t* slot_ptr, const int32_t* slot, const float* g, float* d_table_a, float* d_table_b, void* stream);
+
+/* ------------------------------------------------------------------------------------------------
  * Snapshot store (build_interpolation_graphs / get_train_val_test_graph_at_t keep one DGL graph per timestamp,
  * utils/dataset.py:151-232,268-305; dgl.batch rebuilds the union every call, models/DynamicRGCN.py:92).  Here every
  * snapshot's sorted / chunked edge views stay resident on the device; a batch's TempGraph arrays are assembled from them

@@ -43,6 +43,9 @@ class TempPairView(ctypes.Structure):
 
 
 ABI_VERSION = 2            # include/temp_amd.h: TEMP_ABI_VERSION (2: TempGraph.members, chain pipeline option)
+# include/temp_amd.h, the gated candidate cross-entropy: "N * 4 bytes must fit the LDS (N <= 40704), else TEMP_E_UNSUPPORTED" -- the entity
+# count per window above which temp_gather_ce_bwd / temp_gather_ce_mix_bwd refuse (link_loss._scorer leaves the GEMM route there)
+GATHER_CE_BWD_MAX_N = 40704
 OPT_MFMA_BF16X3, OPT_TN_SPLIT, OPT_RGCN_SCALAR, OPT_GEMM_STREAM, OPT_GRU_STREAM, OPT_RGCN_TILE, OPT_DEBUG, OPT_OVERLAP, OPT_GEMM_RESIDENT, OPT_MFMA_F16X2, OPT_RGCN_PAIR = range(11)
 
 
@@ -247,6 +250,12 @@ SYMBOLS = {
     "temp_l1_mix_ce_bwd_q": (_I, [_I, _I, _I, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, _F, c_vp, c_vp, c_vp, c_vp, c_vp]),
     "temp_l1_mix_ce_bwd_table": (_I, [_I, _I, _I, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp]),
     "temp_l1_mix_scores": (_I, [_I, _I, _I, c_vp, c_vp, c_vp, c_vp, _I, c_vp, c_vp]),
+    "temp_dot_ce_fwd": (_I, [_I, _I, _I, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp]),
+    "temp_dot_ce_bwd_q": (_I, [_I, _I, _I, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, _F, c_vp, c_vp, c_vp, c_vp]),
+    "temp_dot_ce_bwd_table": (_I, [_I, _I, _I, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp]),
+    "temp_dot_mix_ce_fwd": (_I, [_I, _I, _I, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp]),
+    "temp_dot_mix_ce_bwd_q": (_I, [_I, _I, _I, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, _F, c_vp, c_vp, c_vp, c_vp, c_vp]),
+    "temp_dot_mix_ce_bwd_table": (_I, [_I, _I, _I, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp]),
     "temp_assemble_views": (_I, [_I, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp]),
     "temp_subsample_views": (_I, [_I, ctypes.POINTER(TempSubsampleJob), c_vp]),
     "temp_filtered_ce_fwd": (_I, [_I, _I, _I, _I, c_vp, c_vp, c_vp, c_vp, c_vp, _I, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp]),

@@ -818,42 +818,67 @@ class HipBackend:
         _lib.check(rc, "temp_bilinear_query_bwd")
         return dk, dr
 
-    # ---- TransE: candidate loss and dense scores over L1 distances (include/temp_amd.h: temp_l1_ce_fwd ...) ----
-    def l1_ce_fwd(self, q, table, base, cand):
-        """-> (s [P, C], loss_rows [P], lse [P]) of the candidate CE over s[p,k] = -|q[p] - table[base[p] + cand[p,k]]|_1 (base None = 0)."""
+    # ---- candidate-gather loss, one table: L1 distances (TransE; include/temp_amd.h: temp_l1_ce_fwd ...) and inner products (the
+    # bilinear scorers' gather route; temp_dot_ce_fwd ...).  `op` = "l1" | "dot" picks the entry point; shapes and checks are shared ----
+    def _cand_ce_fwd(self, op, q, table, base, cand):
         q, table, base, cand = _f32(q, "q"), _f32(table, "table"), _i32(base, "base"), _i32(cand, "cand")
         P, d = q.shape
         C = cand.shape[1]
         s = torch.empty(P, C, dtype=torch.float32, device=q.device)
         loss = torch.empty(P, dtype=torch.float32, device=q.device)
         lse = torch.empty(P, dtype=torch.float32, device=q.device)
-        rc = self.lib.temp_l1_ce_fwd(P, C, d, _ptr(q), _ptr(table), _ptr(base), _ptr(cand), _ptr(s), _ptr(loss), _ptr(lse), _stream())
-        _lib.check(rc, "temp_l1_ce_fwd")
+        name = "temp_%s_ce_fwd" % op
+        rc = getattr(self.lib, name)(P, C, d, _ptr(q), _ptr(table), _ptr(base), _ptr(cand), _ptr(s), _ptr(loss), _ptr(lse), _stream())
+        _lib.check(rc, name)
         return s, loss, lse
 
-    def l1_ce_bwd_q(self, q, table, base, cand, s, lse, scale, inv_rows, row_scale=None):
-        """-> (g [P, C], d_q [P, d]): the softmax gradient at the candidates and the query side of its adjoint."""
+    def _cand_ce_bwd_q(self, op, q, table, base, cand, s, lse, scale, inv_rows, row_scale):
         q, table, base, cand = _f32(q, "q"), _f32(table, "table"), _i32(base, "base"), _i32(cand, "cand")
         s, lse, scale, row_scale = _f32(s, "s"), _f32(lse, "lse"), _f32(scale, "scale"), _f32(row_scale, "row_scale")
         P, d = q.shape
         g = torch.empty_like(s)
         d_q = torch.empty_like(q)
-        rc = self.lib.temp_l1_ce_bwd_q(P, cand.shape[1], d, _ptr(q), _ptr(table), _ptr(base), _ptr(cand), _ptr(s), _ptr(lse), _ptr(scale),
-                                       float(inv_rows), _ptr(row_scale), _ptr(g), _ptr(d_q), _stream())
-        _lib.check(rc, "temp_l1_ce_bwd_q")
+        name = "temp_%s_ce_bwd_q" % op
+        rc = getattr(self.lib, name)(P, cand.shape[1], d, _ptr(q), _ptr(table), _ptr(base), _ptr(cand), _ptr(s), _ptr(lse), _ptr(scale),
+                                     float(inv_rows), _ptr(row_scale), _ptr(g), _ptr(d_q), _stream())
+        _lib.check(rc, name)
         return g, d_q
 
-    def l1_ce_bwd_table(self, q, table, slot_ptr, slot, g):
-        """-> d_table [rows, d]: the candidate side of the adjoint over the slot lists (link_loss.l1_slots)."""
+    def _cand_ce_bwd_table(self, op, q, table, slot_ptr, slot, g):
         q, table, g = _f32(q, "q"), _f32(table, "table"), _f32(g, "g")
         slot_ptr, slot = _i32(slot_ptr, "slot_ptr"), _i32(slot, "slot")
         n_rows, d = table.shape
         if slot_ptr.shape[0] != n_rows + 1 or slot.numel() != g.numel():
-            raise ValueError("l1_ce_bwd_table: slot lists do not match the table / the candidate matrix")
+            raise ValueError("%s_ce_bwd_table: slot lists do not match the table / the candidate matrix" % op)
         d_table = torch.empty_like(table)
-        rc = self.lib.temp_l1_ce_bwd_table(n_rows, d, g.shape[1], _ptr(q), _ptr(table), _ptr(slot_ptr), _ptr(slot), _ptr(g), _ptr(d_table), _stream())
-        _lib.check(rc, "temp_l1_ce_bwd_table")
+        name = "temp_%s_ce_bwd_table" % op
+        rc = getattr(self.lib, name)(n_rows, d, g.shape[1], _ptr(q), _ptr(table), _ptr(slot_ptr), _ptr(slot), _ptr(g), _ptr(d_table), _stream())
+        _lib.check(rc, name)
         return d_table
+
+    def l1_ce_fwd(self, q, table, base, cand):
+        """-> (s [P, C], loss_rows [P], lse [P]) of the candidate CE over s[p,k] = -|q[p] - table[base[p] + cand[p,k]]|_1 (base None = 0)."""
+        return self._cand_ce_fwd("l1", q, table, base, cand)
+
+    def l1_ce_bwd_q(self, q, table, base, cand, s, lse, scale, inv_rows, row_scale=None):
+        """-> (g [P, C], d_q [P, d]): the softmax gradient at the candidates and the query side of its adjoint."""
+        return self._cand_ce_bwd_q("l1", q, table, base, cand, s, lse, scale, inv_rows, row_scale)
+
+    def l1_ce_bwd_table(self, q, table, slot_ptr, slot, g):
+        """-> d_table [rows, d]: the candidate side of the adjoint over the slot lists (link_loss.l1_slots)."""
+        return self._cand_ce_bwd_table("l1", q, table, slot_ptr, slot, g)
+
+    def dot_ce_fwd(self, q, table, base, cand):
+        """-> (s [P, C], loss_rows [P], lse [P]) of the candidate CE over s[p,k] = <q[p], table[base[p] + cand[p,k]]> (base None = 0)."""
+        return self._cand_ce_fwd("dot", q, table, base, cand)
+
+    def dot_ce_bwd_q(self, q, table, base, cand, s, lse, scale, inv_rows, row_scale=None):
+        """-> (g [P, C], d_q [P, d] = sum_k g[p,k] table[row]): the softmax gradient at the candidates and the query side of its adjoint."""
+        return self._cand_ce_bwd_q("dot", q, table, base, cand, s, lse, scale, inv_rows, row_scale)
+
+    def dot_ce_bwd_table(self, q, table, slot_ptr, slot, g):
+        """-> d_table [rows, d] = sum over a row's slots of g[slot] q[slot // C] (link_loss.l1_slots); `table` gives the shape only."""
+        return self._cand_ce_bwd_table("dot", q, table, slot_ptr, slot, g)
 
     def l1_scores(self, q, table):
         """-> scores [P, ld], ld = N rounded up to a multiple of 4: -|q[p] - table[n]|_1, the pad columns -inf (what filtered_rank takes)."""
@@ -889,51 +914,76 @@ class HipBackend:
         _lib.check(rc, "temp_gated_query_bwd")
         return da, db, dr, dw
 
-    # ---- gated TransE: the L1 calls over the per-row mix of two tables (include/temp_amd.h: temp_l1_mix_ce_fwd ...) ----
-    def l1_mix_ce_fwd(self, q, table_a, table_b, w, base, cand):
-        """-> (s [P, C], loss_rows [P], lse [P]) over s[p,k] = -|q[p] - mix(w[p], table_a[row], table_b[row])|_1, row = base[p] + cand[p,k]."""
+    # ---- the same calls over the per-row mix of two tables: gated TransE (include/temp_amd.h: temp_l1_mix_ce_fwd ...) and the gated
+    # bilinear scorers' gather route (temp_dot_mix_ce_fwd ...) ----
+    def _cand_mix_ce_fwd(self, op, q, table_a, table_b, w, base, cand):
         q, table_a, table_b, w = _f32(q, "q"), _f32(table_a, "table_a"), _f32(table_b, "table_b"), _f32(w, "w")
         base, cand = _i32(base, "base"), _i32(cand, "cand")
         P, d = q.shape
         C = cand.shape[1]
         if table_a.shape != table_b.shape or w.numel() != P:
-            raise ValueError("l1_mix_ce_fwd: the two tables must have one shape and w one entry per row")
+            raise ValueError("%s_mix_ce_fwd: the two tables must have one shape and w one entry per row" % op)
         s = torch.empty(P, C, dtype=torch.float32, device=q.device)
         loss = torch.empty(P, dtype=torch.float32, device=q.device)
         lse = torch.empty(P, dtype=torch.float32, device=q.device)
-        rc = self.lib.temp_l1_mix_ce_fwd(P, C, d, _ptr(q), _ptr(table_a), _ptr(table_b), _ptr(w), _ptr(base), _ptr(cand), _ptr(s), _ptr(loss),
-                                         _ptr(lse), _stream())
-        _lib.check(rc, "temp_l1_mix_ce_fwd")
+        name = "temp_%s_mix_ce_fwd" % op
+        rc = getattr(self.lib, name)(P, C, d, _ptr(q), _ptr(table_a), _ptr(table_b), _ptr(w), _ptr(base), _ptr(cand), _ptr(s), _ptr(loss),
+                                     _ptr(lse), _stream())
+        _lib.check(rc, name)
         return s, loss, lse
 
-    def l1_mix_ce_bwd_q(self, q, table_a, table_b, w, base, cand, s, lse, scale, inv_rows, row_scale=None):
-        """-> (g [P, C], d_q [P, d], d_w [P]): the softmax gradient, the query side of its adjoint and the candidate weight's."""
+    def _cand_mix_ce_bwd_q(self, op, q, table_a, table_b, w, base, cand, s, lse, scale, inv_rows, row_scale):
         q, table_a, table_b, w = _f32(q, "q"), _f32(table_a, "table_a"), _f32(table_b, "table_b"), _f32(w, "w")
         base, cand = _i32(base, "base"), _i32(cand, "cand")
         s, lse, scale, row_scale = _f32(s, "s"), _f32(lse, "lse"), _f32(scale, "scale"), _f32(row_scale, "row_scale")
         P, d = q.shape
         if table_a.shape != table_b.shape or w.numel() != P:
-            raise ValueError("l1_mix_ce_bwd_q: the two tables must have one shape and w one entry per row")
+            raise ValueError("%s_mix_ce_bwd_q: the two tables must have one shape and w one entry per row" % op)
         g = torch.empty_like(s)
         d_q = torch.empty_like(q)
         d_w = torch.empty(P, dtype=torch.float32, device=q.device)
-        rc = self.lib.temp_l1_mix_ce_bwd_q(P, cand.shape[1], d, _ptr(q), _ptr(table_a), _ptr(table_b), _ptr(w), _ptr(base), _ptr(cand), _ptr(s),
-                                           _ptr(lse), _ptr(scale), float(inv_rows), _ptr(row_scale), _ptr(g), _ptr(d_q), _ptr(d_w), _stream())
-        _lib.check(rc, "temp_l1_mix_ce_bwd_q")
+        name = "temp_%s_mix_ce_bwd_q" % op
+        rc = getattr(self.lib, name)(P, cand.shape[1], d, _ptr(q), _ptr(table_a), _ptr(table_b), _ptr(w), _ptr(base), _ptr(cand), _ptr(s),
+                                     _ptr(lse), _ptr(scale), float(inv_rows), _ptr(row_scale), _ptr(g), _ptr(d_q), _ptr(d_w), _stream())
+        _lib.check(rc, name)
         return g, d_q, d_w
 
-    def l1_mix_ce_bwd_table(self, q, table_a, table_b, w, slot_ptr, slot, g):
-        """-> (d_table_a, d_table_b) [rows, d]: the candidate side of the adjoint over the slot lists (link_loss.l1_slots)."""
+    def _cand_mix_ce_bwd_table(self, op, q, table_a, table_b, w, slot_ptr, slot, g):
         q, table_a, table_b, w, g = _f32(q, "q"), _f32(table_a, "table_a"), _f32(table_b, "table_b"), _f32(w, "w"), _f32(g, "g")
         slot_ptr, slot = _i32(slot_ptr, "slot_ptr"), _i32(slot, "slot")
         n_rows, d = table_a.shape
         if table_a.shape != table_b.shape or slot_ptr.shape[0] != n_rows + 1 or slot.numel() != g.numel() or w.numel() != g.shape[0]:
-            raise ValueError("l1_mix_ce_bwd_table: slot lists / weights do not match the tables / the candidate matrix")
+            raise ValueError("%s_mix_ce_bwd_table: slot lists / weights do not match the tables / the candidate matrix" % op)
         d_a, d_b = torch.empty_like(table_a), torch.empty_like(table_b)
-        rc = self.lib.temp_l1_mix_ce_bwd_table(n_rows, d, g.shape[1], _ptr(q), _ptr(table_a), _ptr(table_b), _ptr(w), _ptr(slot_ptr), _ptr(slot),
-                                               _ptr(g), _ptr(d_a), _ptr(d_b), _stream())
-        _lib.check(rc, "temp_l1_mix_ce_bwd_table")
+        name = "temp_%s_mix_ce_bwd_table" % op
+        rc = getattr(self.lib, name)(n_rows, d, g.shape[1], _ptr(q), _ptr(table_a), _ptr(table_b), _ptr(w), _ptr(slot_ptr), _ptr(slot),
+                                     _ptr(g), _ptr(d_a), _ptr(d_b), _stream())
+        _lib.check(rc, name)
         return d_a, d_b
+
+    def l1_mix_ce_fwd(self, q, table_a, table_b, w, base, cand):
+        """-> (s [P, C], loss_rows [P], lse [P]) over s[p,k] = -|q[p] - mix(w[p], table_a[row], table_b[row])|_1, row = base[p] + cand[p,k]."""
+        return self._cand_mix_ce_fwd("l1", q, table_a, table_b, w, base, cand)
+
+    def l1_mix_ce_bwd_q(self, q, table_a, table_b, w, base, cand, s, lse, scale, inv_rows, row_scale=None):
+        """-> (g [P, C], d_q [P, d], d_w [P]): the softmax gradient, the query side of its adjoint and the candidate weight's."""
+        return self._cand_mix_ce_bwd_q("l1", q, table_a, table_b, w, base, cand, s, lse, scale, inv_rows, row_scale)
+
+    def l1_mix_ce_bwd_table(self, q, table_a, table_b, w, slot_ptr, slot, g):
+        """-> (d_table_a, d_table_b) [rows, d]: the candidate side of the adjoint over the slot lists (link_loss.l1_slots)."""
+        return self._cand_mix_ce_bwd_table("l1", q, table_a, table_b, w, slot_ptr, slot, g)
+
+    def dot_mix_ce_fwd(self, q, table_a, table_b, w, base, cand):
+        """-> (s [P, C], loss_rows [P], lse [P]) over s[p,k] = <q[p], mix(w[p], table_a[row], table_b[row])>, row = base[p] + cand[p,k]."""
+        return self._cand_mix_ce_fwd("dot", q, table_a, table_b, w, base, cand)
+
+    def dot_mix_ce_bwd_q(self, q, table_a, table_b, w, base, cand, s, lse, scale, inv_rows, row_scale=None):
+        """-> (g [P, C], d_q [P, d], d_w [P]): the softmax gradient, the query side of its adjoint and the candidate weight's."""
+        return self._cand_mix_ce_bwd_q("dot", q, table_a, table_b, w, base, cand, s, lse, scale, inv_rows, row_scale)
+
+    def dot_mix_ce_bwd_table(self, q, table_a, table_b, w, slot_ptr, slot, g):
+        """-> (d_table_a, d_table_b) [rows, d] = sum over a row's slots of (w, 1 - w)[p] g[slot] q[p], p = slot // C."""
+        return self._cand_mix_ce_bwd_table("dot", q, table_a, table_b, w, slot_ptr, slot, g)
 
     def l1_mix_scores(self, q, table_a, table_b, w):
         """-> scores [P, ld], ld = N rounded up to a multiple of 4: -|q[p] - mix(w[p], table_a[n], table_b[n])|_1, the pad columns -inf."""

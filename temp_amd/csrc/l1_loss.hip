@@ -1,7 +1,20 @@
-// L1 (TransE, utils/scores.py:46-55) candidate loss and dense scores, plain over one table and gated over two all-entity tables
-// (the post-aggregation models), with their entry points.
+// Candidate-gather loss kernels: the score of a row at its own candidates alone, read straight from the all-entity table(s).  Two
+// scoring operations -- L1 (TransE, utils/scores.py:46-55) and the inner product of a folded bilinear query (distmult / complex /
+// simple, utils/scores.py:4-44) -- each plain over one table and gated over two all-entity tables (the post-aggregation models),
+// with their entry points; and the dense L1 scores of the ranking.
 //
-// TransE is not bilinear: score(p, c) = -sum_d |q[p,d] - c[d]| with the translation query q of k_bilinear_query / k_gated_query,
+// The three candidate kernels (k_cand_ce_fwd / _bwd_q / _bwd_table below) are written once over TWO policies: the candidate SOURCE
+// (further down) and the scoring OPERATION,
+//   L1Op    score -sum |q - e|;  d_q = -sum_k g_k sgn(q - e_k);  d_table[n] = +sum_slots g sgn(q - table[n]).  What follows in this
+//           comment describes it; its instantiations are the k_l1_ce_* kernels (temp_l1_*), arithmetic unchanged.
+//   DotOp   score +sum q e;  d_q = sum_k g_k e_k;  d_table[n] = sum_slots g[slot] q[slot / C] -- the table row is not read by the
+//           plain bwd_table.  The mix stays linear in the candidate here, but is still formed in registers (one pass reads both rows):
+//           d_w[p] = sum_k g_k sum_d q_d (TA - TB)[row, d],  d_TA = sum w g q,  d_TB = sum (1 - w) g q.  These are the k_dot_ce_* /
+//           k_dot_mix_ce_* launches (temp_dot_*): the gather route of the bilinear scorers, which has no ceiling on the entity count
+//           (temp_gather_ce_bwd keeps N counters in LDS) and never forms a (rows, N) matrix.
+// Everything else -- work split, load order, reduction orders, no atomics, outputs fully written -- is shared.
+//
+// The L1 form (k_l1_ce_x = k_cand_ce_x<L1Op, .>).  TransE is not bilinear: score(p, c) = -sum_d |q[p,d] - c[d]| with the translation query q of k_bilinear_query / k_gated_query,
 // so no GEMM carries it.  The training loss needs the score at the 1 + negative_rate candidates of a row only -- a gather of
 // P C d elements, N / C times fewer than the dense matrix -- and never as a (P, C, D) tensor:
 //   k_l1_ce_fwd        one workgroup per row; a 16-lane group owns a candidate (float4 per lane, ceil(d / 64) passes, four xor
@@ -64,9 +77,28 @@ __device__ __forceinline__ float l1_4(float4 a, float4 b) { return (fabsf(a.x - 
 __device__ __forceinline__ float sgnf(float x) { return (float)((x > 0.f) - (x < 0.f)); }
 __device__ __forceinline__ float4 sgn4(float4 a, float4 b) { return make_float4(sgnf(a.x - b.x), sgnf(a.y - b.y), sgnf(a.z - b.z), sgnf(a.w - b.w)); }
 
+__device__ __forceinline__ float dot4(float4 a, float4 b) { return fmaf(a.w, b.w, fmaf(a.z, b.z, fmaf(a.y, b.y, a.x * b.x))); }
+
+// The scoring OPERATION of the three candidate kernels: what one float4 column adds to a candidate's sum (term), how the sum becomes
+// the score, and -- in the backward kernels, under `if constexpr (Op::kDot)` -- the adjoints of that score.  role: 0 fwd, 1 bwd_q,
+// 2 bwd_table; the L1 kernels keep the launch tags they had, the dot kernels have one of their own per entry point.
+struct L1Op {
+  static constexpr bool kDot = false;
+  template <class Src> static constexpr int tag(int) { return Src::kLaunchTag; }
+  static __device__ __forceinline__ float term(float4 q, float4 e) { return l1_4(q, e); }
+  static __device__ __forceinline__ float score(float a) { return -a; }
+};
+
+struct DotOp {
+  static constexpr bool kDot = true;
+  template <class Src> static constexpr int tag(int role) { return (Src::kMixed ? K_DOT_MIX_CE_FWD : K_DOT_CE_FWD) + role; }
+  static __device__ __forceinline__ float term(float4 q, float4 e) { return dot4(q, e); }
+  static __device__ __forceinline__ float score(float a) { return a; }
+};
+
 // NP > 0: d <= 64 NP and q[p] stays in registers; NP == 0: any d, q[p] is re-read per candidate (it stays in the L1).
-template <int NP, class Src>
-__global__ void __launch_bounds__(256) k_l1_ce_fwd(int C, int d, const float* __restrict__ q, Src src, const int32_t* __restrict__ base,
+template <int NP, class Op, class Src>
+__global__ void __launch_bounds__(256) k_cand_ce_fwd(int C, int d, const float* __restrict__ q, Src src, const int32_t* __restrict__ base,
                                                    const int32_t* __restrict__ cand, float* s_out, float* __restrict__ loss_rows,
                                                    float* __restrict__ lse_rows) {
   using Raw = typename Src::Raw;
@@ -93,20 +125,20 @@ __global__ void __launch_bounds__(256) k_l1_ce_fwd(int C, int d, const float* __
         x1[u] = j < d ? src.load(r1 + j) : Src::none();
       }
 #pragma unroll
-      for (int u = 0; u < NP; ++u) { a0 += l1_4(qv[u], Src::value(wp, x0[u])); a1 += l1_4(qv[u], Src::value(wp, x1[u])); }
+      for (int u = 0; u < NP; ++u) { a0 += Op::term(qv[u], Src::value(wp, x0[u])); a1 += Op::term(qv[u], Src::value(wp, x1[u])); }
     } else {
       for (int j = l * 4; j < d; j += 64) {
         const float4 qq = ld4(qrow + j);
         const Raw x0 = src.load(r0 + j), x1 = src.load(r1 + j);
-        a0 += l1_4(qq, Src::value(wp, x0));
-        a1 += l1_4(qq, Src::value(wp, x1));
+        a0 += Op::term(qq, Src::value(wp, x0));
+        a1 += Op::term(qq, Src::value(wp, x1));
       }
     }
     a0 = group16_sum(a0);
     a1 = group16_sum(a1);
     if (l == 0) {
-      srow[k0] = -a0;
-      if (k1 < C) srow[k1] = -a1;
+      srow[k0] = Op::score(a0);
+      if (k1 < C) srow[k1] = Op::score(a1);
     }
   }
   __syncthreads();                                       // the row's scores, written by this workgroup, are read back below
@@ -123,8 +155,8 @@ __global__ void __launch_bounds__(256) k_l1_ce_fwd(int C, int d, const float* __
 }
 
 // d_w is written by the mixed source only (NULL otherwise)
-template <class Src>
-__global__ void __launch_bounds__(256) k_l1_ce_bwd_q(int C, int d, const float* __restrict__ q, Src src, const int32_t* __restrict__ base,
+template <class Op, class Src>
+__global__ void __launch_bounds__(256) k_cand_ce_bwd_q(int C, int d, const float* __restrict__ q, Src src, const int32_t* __restrict__ base,
                                                      const int32_t* __restrict__ cand, const float* __restrict__ s,
                                                      const float* __restrict__ lse_rows, const float* __restrict__ scale_ptr, float inv_rows,
                                                      const float* __restrict__ row_scale, float* g_out, float* __restrict__ d_q,
@@ -152,11 +184,19 @@ __global__ void __launch_bounds__(256) k_l1_ce_bwd_q(int C, int d, const float* 
       const size_t r = (b + (size_t)crow[k]) * d;
       if (act) {
         const typename Src::Raw e = src.load(r + j);
-        const float4 sg = sgn4(qv, Src::value(wp, e));
-        acc.x -= gk * sg.x; acc.y -= gk * sg.y; acc.z -= gk * sg.z; acc.w -= gk * sg.w;
-        if constexpr (Src::kMixed) {
-          const float4 x = e.x, y = e.y;
-          wacc += gk * ((sg.x * (x.x - y.x) + sg.y * (x.y - y.y)) + (sg.z * (x.z - y.z) + sg.w * (x.w - y.w)));
+        if constexpr (Op::kDot) {
+          acc = fma4(gk, Src::value(wp, e), acc);
+          if constexpr (Src::kMixed) {
+            const float4 x = e.x, y = e.y;
+            wacc += gk * ((qv.x * (x.x - y.x) + qv.y * (x.y - y.y)) + (qv.z * (x.z - y.z) + qv.w * (x.w - y.w)));
+          }
+        } else {
+          const float4 sg = sgn4(qv, Src::value(wp, e));
+          acc.x -= gk * sg.x; acc.y -= gk * sg.y; acc.z -= gk * sg.z; acc.w -= gk * sg.w;
+          if constexpr (Src::kMixed) {
+            const float4 x = e.x, y = e.y;
+            wacc += gk * ((sg.x * (x.x - y.x) + sg.y * (x.y - y.y)) + (sg.z * (x.z - y.z) + sg.w * (x.w - y.w)));
+          }
         }
       }
     }
@@ -170,9 +210,10 @@ __global__ void __launch_bounds__(256) k_l1_ce_bwd_q(int C, int d, const float* 
   }
 }
 
-// d_a is the table's adjoint, or TA's with d_b TB's (NULL otherwise); the slot's row weight enters only when mixed
-template <class Src>
-__global__ void __launch_bounds__(256) k_l1_ce_bwd_table(int d, int C, const float* __restrict__ q, Src src, const int32_t* __restrict__ slot_ptr,
+// d_a is the table's adjoint, or TA's with d_b TB's (NULL otherwise); the slot's row weight enters only when mixed.  The dot
+// adjoint sum g q does not depend on the table row: it is not loaded.
+template <class Op, class Src>
+__global__ void __launch_bounds__(256) k_cand_ce_bwd_table(int d, int C, const float* __restrict__ q, Src src, const int32_t* __restrict__ slot_ptr,
                                                          const int32_t* __restrict__ slot, const float* __restrict__ g, float* __restrict__ d_a,
                                                          float* __restrict__ d_b) {
   __shared__ __attribute__((aligned(16))) float part[3][256];
@@ -182,7 +223,7 @@ __global__ void __launch_bounds__(256) k_l1_ce_bwd_table(int d, int C, const flo
   for (int j0 = 0; j0 < d; j0 += 256) {
     const int j = j0 + lane * 4;
     const bool act = j < d;
-    const typename Src::Raw tv = act ? src.load(n * d + j) : Src::none();
+    const typename Src::Raw tv = !Op::kDot && act ? src.load(n * d + j) : Src::none();
     float4 aa = zero4(), ab = zero4();
 #pragma unroll 4
     for (int i = s0 + wv; i < s1; i += 4) {
@@ -191,13 +232,24 @@ __global__ void __launch_bounds__(256) k_l1_ce_bwd_table(int d, int C, const flo
       const float gk = g[sl], wp = src.weight(p);
       const float* qr = q + (size_t)p * d;
       if (act) {
-        const float4 sg = sgn4(ld4(qr + j), Src::value(wp, tv));
-        if constexpr (Src::kMixed) {
-          const float4 t = scale4(sg, gk);                // g sgn: exact
-          aa = fma4(wp, t, aa);
-          ab = fma4(1.f - wp, t, ab);
+        if constexpr (Op::kDot) {
+          const float4 qq = ld4(qr + j);
+          if constexpr (Src::kMixed) {
+            const float4 t = scale4(qq, gk);              // g q: one rounding
+            aa = fma4(wp, t, aa);
+            ab = fma4(1.f - wp, t, ab);
+          } else {
+            aa = fma4(gk, qq, aa);
+          }
         } else {
-          aa = fma4(gk, sg, aa);                          // (the product is exact: one rounding, fused or not)
+          const float4 sg = sgn4(ld4(qr + j), Src::value(wp, tv));
+          if constexpr (Src::kMixed) {
+            const float4 t = scale4(sg, gk);                // g sgn: exact
+            aa = fma4(wp, t, aa);
+            ab = fma4(1.f - wp, t, ab);
+          } else {
+            aa = fma4(gk, sg, aa);                          // (the product is exact: one rounding, fused or not)
+          }
         }
       }
     }
@@ -283,20 +335,20 @@ __global__ void __launch_bounds__(256) k_l1_scores(int P, int N, int d, const fl
   }
 }
 
-// ---- host side: one launcher per role; the entry points below are its two instantiations ----
+// ---- host side: one launcher per role; the entry points below are its instantiations (operation x source) ----
 int l1_ce_args(int P, int C, int d) {
   if (P < 0 || C <= 0 || d <= 0) return TEMP_E_BADARG;
   if (d % 4 || (long long)P * C >= (1ll << 31)) return TEMP_E_UNSUPPORTED;
   return TEMP_OK;
 }
 
-template <class Src>
-int l1_ce_fwd(int P, int C, int d, const float* q, Src src, const int32_t* base, const int32_t* cand, float* s_out, float* loss_rows,
+template <class Op, class Src>
+int cand_ce_fwd(int P, int C, int d, const float* q, Src src, const int32_t* base, const int32_t* cand, float* s_out, float* loss_rows,
               float* lse_rows, void* stream) {
   const int rc = l1_ce_args(P, C, d);
   if (rc != TEMP_OK || P == 0) return rc;
   if (!q || !src.has_tables() || !src.has_weights() || !cand || !s_out || !loss_rows || !lse_rows) return TEMP_E_BADARG;
-#define L1_FWD(NP) TEMP_LAUNCH(Src::kLaunchTag, (k_l1_ce_fwd<NP, Src>), dim3(P), dim3(256), 0, (hipStream_t)stream, C, d, q, src, base, cand, s_out, loss_rows, lse_rows)
+#define L1_FWD(NP) TEMP_LAUNCH(Op::template tag<Src>(0), (k_cand_ce_fwd<NP, Op, Src>), dim3(P), dim3(256), 0, (hipStream_t)stream, C, d, q, src, base, cand, s_out, loss_rows, lse_rows)
   if (d <= 64) L1_FWD(1);
   else if (d <= 128) L1_FWD(2);
   else if (d <= 192) L1_FWD(3);
@@ -306,27 +358,27 @@ int l1_ce_fwd(int P, int C, int d, const float* q, Src src, const int32_t* base,
   return launch_status();
 }
 
-template <class Src>
-int l1_ce_bwd_q(int P, int C, int d, const float* q, Src src, const int32_t* base, const int32_t* cand, const float* s, const float* lse_rows,
+template <class Op, class Src>
+int cand_ce_bwd_q(int P, int C, int d, const float* q, Src src, const int32_t* base, const int32_t* cand, const float* s, const float* lse_rows,
                 const float* scale, float inv_rows, const float* row_scale, float* g_out, float* d_q, float* d_w, void* stream) {
   const int rc = l1_ce_args(P, C, d);
   if (rc != TEMP_OK) return rc;
   if (!scale) return TEMP_E_BADARG;
   if (P == 0) return TEMP_OK;
   if (!q || !src.has_tables() || !src.has_weights() || !cand || !s || !lse_rows || !g_out || !d_q || (Src::kMixed && !d_w)) return TEMP_E_BADARG;
-  TEMP_LAUNCH(Src::kLaunchTag, k_l1_ce_bwd_q<Src>, dim3(P), dim3(256), 0, (hipStream_t)stream, C, d, q, src, base, cand, s, lse_rows, scale, inv_rows,
+  TEMP_LAUNCH(Op::template tag<Src>(1), (k_cand_ce_bwd_q<Op, Src>), dim3(P), dim3(256), 0, (hipStream_t)stream, C, d, q, src, base, cand, s, lse_rows, scale, inv_rows,
               row_scale, g_out, d_q, d_w);
   return launch_status();
 }
 
-template <class Src>
-int l1_ce_bwd_table(int n_rows, int d, int C, const float* q, Src src, const int32_t* slot_ptr, const int32_t* slot, const float* g, float* d_a,
+template <class Op, class Src>
+int cand_ce_bwd_table(int n_rows, int d, int C, const float* q, Src src, const int32_t* slot_ptr, const int32_t* slot, const float* g, float* d_a,
                     float* d_b, void* stream) {
   if (n_rows < 0 || C <= 0 || d <= 0) return TEMP_E_BADARG;
   if (d % 4) return TEMP_E_UNSUPPORTED;
   if (n_rows == 0) return TEMP_OK;
   if (!src.has_tables() || !slot_ptr || !d_a || (Src::kMixed && !d_b)) return TEMP_E_BADARG;   // q, w, slot and g may be NULL when every list is empty
-  TEMP_LAUNCH(Src::kLaunchTag, k_l1_ce_bwd_table<Src>, dim3(n_rows), dim3(256), 0, (hipStream_t)stream, d, C, q, src, slot_ptr, slot, g, d_a, d_b);
+  TEMP_LAUNCH(Op::template tag<Src>(2), (k_cand_ce_bwd_table<Op, Src>), dim3(n_rows), dim3(256), 0, (hipStream_t)stream, d, C, q, src, slot_ptr, slot, g, d_a, d_b);
   return launch_status();
 }
 
@@ -350,33 +402,64 @@ extern "C" {
 
 int temp_l1_ce_fwd(int P, int C, int d, const float* q, const float* table, const int32_t* base, const int32_t* cand, float* s_out,
                    float* loss_rows, float* lse_rows, void* stream) {
-  return l1_ce_fwd(P, C, d, q, OneTable{table}, base, cand, s_out, loss_rows, lse_rows, stream);
+  return cand_ce_fwd<L1Op>(P, C, d, q, OneTable{table}, base, cand, s_out, loss_rows, lse_rows, stream);
 }
 
 int temp_l1_mix_ce_fwd(int P, int C, int d, const float* q, const float* table_a, const float* table_b, const float* w, const int32_t* base,
                        const int32_t* cand, float* s_out, float* loss_rows, float* lse_rows, void* stream) {
-  return l1_ce_fwd(P, C, d, q, TwoTables{table_a, table_b, w}, base, cand, s_out, loss_rows, lse_rows, stream);
+  return cand_ce_fwd<L1Op>(P, C, d, q, TwoTables{table_a, table_b, w}, base, cand, s_out, loss_rows, lse_rows, stream);
 }
 
 int temp_l1_ce_bwd_q(int P, int C, int d, const float* q, const float* table, const int32_t* base, const int32_t* cand, const float* s,
                      const float* lse_rows, const float* scale, float inv_rows, const float* row_scale, float* g_out, float* d_q, void* stream) {
-  return l1_ce_bwd_q(P, C, d, q, OneTable{table}, base, cand, s, lse_rows, scale, inv_rows, row_scale, g_out, d_q, nullptr, stream);
+  return cand_ce_bwd_q<L1Op>(P, C, d, q, OneTable{table}, base, cand, s, lse_rows, scale, inv_rows, row_scale, g_out, d_q, nullptr, stream);
 }
 
 int temp_l1_mix_ce_bwd_q(int P, int C, int d, const float* q, const float* table_a, const float* table_b, const float* w, const int32_t* base,
                          const int32_t* cand, const float* s, const float* lse_rows, const float* scale, float inv_rows, const float* row_scale,
                          float* g_out, float* d_q, float* d_w, void* stream) {
-  return l1_ce_bwd_q(P, C, d, q, TwoTables{table_a, table_b, w}, base, cand, s, lse_rows, scale, inv_rows, row_scale, g_out, d_q, d_w, stream);
+  return cand_ce_bwd_q<L1Op>(P, C, d, q, TwoTables{table_a, table_b, w}, base, cand, s, lse_rows, scale, inv_rows, row_scale, g_out, d_q, d_w, stream);
 }
 
 int temp_l1_ce_bwd_table(int n_rows, int d, int C, const float* q, const float* table, const int32_t* slot_ptr, const int32_t* slot, const float* g,
                          float* d_table, void* stream) {
-  return l1_ce_bwd_table(n_rows, d, C, q, OneTable{table}, slot_ptr, slot, g, d_table, nullptr, stream);
+  return cand_ce_bwd_table<L1Op>(n_rows, d, C, q, OneTable{table}, slot_ptr, slot, g, d_table, nullptr, stream);
 }
 
 int temp_l1_mix_ce_bwd_table(int n_rows, int d, int C, const float* q, const float* table_a, const float* table_b, const float* w,
                              const int32_t* slot_ptr, const int32_t* slot, const float* g, float* d_table_a, float* d_table_b, void* stream) {
-  return l1_ce_bwd_table(n_rows, d, C, q, TwoTables{table_a, table_b, w}, slot_ptr, slot, g, d_table_a, d_table_b, stream);
+  return cand_ce_bwd_table<L1Op>(n_rows, d, C, q, TwoTables{table_a, table_b, w}, slot_ptr, slot, g, d_table_a, d_table_b, stream);
+}
+
+int temp_dot_ce_fwd(int P, int C, int d, const float* q, const float* table, const int32_t* base, const int32_t* cand, float* s_out,
+                   float* loss_rows, float* lse_rows, void* stream) {
+  return cand_ce_fwd<DotOp>(P, C, d, q, OneTable{table}, base, cand, s_out, loss_rows, lse_rows, stream);
+}
+
+int temp_dot_mix_ce_fwd(int P, int C, int d, const float* q, const float* table_a, const float* table_b, const float* w, const int32_t* base,
+                       const int32_t* cand, float* s_out, float* loss_rows, float* lse_rows, void* stream) {
+  return cand_ce_fwd<DotOp>(P, C, d, q, TwoTables{table_a, table_b, w}, base, cand, s_out, loss_rows, lse_rows, stream);
+}
+
+int temp_dot_ce_bwd_q(int P, int C, int d, const float* q, const float* table, const int32_t* base, const int32_t* cand, const float* s,
+                     const float* lse_rows, const float* scale, float inv_rows, const float* row_scale, float* g_out, float* d_q, void* stream) {
+  return cand_ce_bwd_q<DotOp>(P, C, d, q, OneTable{table}, base, cand, s, lse_rows, scale, inv_rows, row_scale, g_out, d_q, nullptr, stream);
+}
+
+int temp_dot_mix_ce_bwd_q(int P, int C, int d, const float* q, const float* table_a, const float* table_b, const float* w, const int32_t* base,
+                         const int32_t* cand, const float* s, const float* lse_rows, const float* scale, float inv_rows, const float* row_scale,
+                         float* g_out, float* d_q, float* d_w, void* stream) {
+  return cand_ce_bwd_q<DotOp>(P, C, d, q, TwoTables{table_a, table_b, w}, base, cand, s, lse_rows, scale, inv_rows, row_scale, g_out, d_q, d_w, stream);
+}
+
+int temp_dot_ce_bwd_table(int n_rows, int d, int C, const float* q, const float* table, const int32_t* slot_ptr, const int32_t* slot, const float* g,
+                         float* d_table, void* stream) {
+  return cand_ce_bwd_table<DotOp>(n_rows, d, C, q, OneTable{table}, slot_ptr, slot, g, d_table, nullptr, stream);
+}
+
+int temp_dot_mix_ce_bwd_table(int n_rows, int d, int C, const float* q, const float* table_a, const float* table_b, const float* w,
+                             const int32_t* slot_ptr, const int32_t* slot, const float* g, float* d_table_a, float* d_table_b, void* stream) {
+  return cand_ce_bwd_table<DotOp>(n_rows, d, C, q, TwoTables{table_a, table_b, w}, slot_ptr, slot, g, d_table_a, d_table_b, stream);
 }
 
 int temp_l1_scores(int P, int N, int d, const float* q, const float* table, int ld, float* scores, void* stream) {

@@ -129,7 +129,8 @@ const char* temp_trace_kernel_name(int id) {
                                 "k_pair_tail", "k_diachronic_fwd", "k_diachronic_bwd", "k_filtered_topk", "k_adam_grad_norm", "k_adam_norm_finish",
                                 "k_adam_clip_step", "k_filtered_topk_mix", "k_hyperplane_fwd", "k_hyperplane_bwd", "k_hyperplane_bwd_finish",
                                 "k_pair_rows_fwd", "k_pair_rows_bwd", "k_frozen_mix_ce", "k_filtered_ce_fwd", "k_filtered_ce_bwd",
-                                "k_filtered_rank_stream", "k_filtered_rank_stream_mix"};
+                                "k_filtered_rank_stream", "k_filtered_rank_stream_mix", "k_dot_ce_fwd", "k_dot_ce_bwd_q",
+                                "k_dot_ce_bwd_table", "k_dot_mix_ce_fwd", "k_dot_mix_ce_bwd_q", "k_dot_mix_ce_bwd_table"};
   static_assert(sizeof(names) / sizeof(names[0]) == K_COUNT, "one name per KernelId");
   return (id >= 0 && id < K_COUNT) ? names[id] : "?";
 }

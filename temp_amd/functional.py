@@ -282,7 +282,8 @@ def gather_inverse(idx_np, n_rows, device):
 # through this module are re-exported.  _TALL_SCORES, _L1_METHODS, _L1_MIX_METHODS and _cached_l1_slots are NOT: a copy of a switch
 # here would be one nobody reads.
 from .link_loss import (batched_all_entity_link_prediction, batched_ensemble_link_prediction, batched_gated_link_prediction,  # noqa: E402,F401
-                        batched_link_prediction, candidate_cross_entropy, candidate_cross_entropy_mixed, filtered_ce_rows_torch,
+                        batched_link_prediction, bilinear_route, candidate_cross_entropy, candidate_cross_entropy_mixed,
+                        dot_ce_rows_torch, dot_gather_supported, filtered_ce_rows_torch,
                         frozen_ensemble_link_prediction, frozen_mix_ce_rows,
                         gated_link_prediction, gated_loss_inputs,
                         gated_translation_supported, l1_slots, translation_cross_entropy, translation_supported)

@@ -1,14 +1,17 @@
 """The link-prediction loss: torch.autograd nodes around the loss kernels (through temp_amd.backend).  temp_amd.functional re-exports
 the public functions; the private names (_TALL_SCORES, _L1_METHODS, _L1_MIX_METHODS, _cached_l1_slots, the node classes) live here.
 
-Three batched nodes, each written once over a scorer (_GemmScorer: distmult / complex, scores against ALL entities of a window;
-_L1Scorer: transE, distances to the candidates alone).  The backend calls of every node x scorer, forward | backward:
+Three batched nodes, each written once over a scorer (_GemmScorer: distmult / complex / simple, scores against ALL entities of a
+window; _GatherScorer: the score at the candidates alone, as _L1Scorer -- transE, L1 distances -- and as _DotGatherScorer -- the
+bilinear scorers' route "gather", inner products; bilinear_route picks between GEMM and DOT: None = GEMM up to the LDS ceiling of
+temp_gather_ce_bwd, DOT above it).  The backend calls of every node x scorer, forward | backward:
 
   _BatchedLinkPredictionFn            sum over windows of CE_tail + CE_head (models/DynamicRGCN.py:186-193)
     both     bilinear_query_fwd                                  | ... bilinear_query_bwd, segment_sum_rows x 2 (known, rel)
     GEMM     linear_multi, gather_ce_fwd                         | gather_ce_bwd, linear_multi, linear_tn_multi
              (TEMP_LOSS_TALL=1: linear_t per window)             |   (tall: linear_tn + linear per window)
     L1       l1_ce_fwd                                           | l1_ce_bwd_q, l1_ce_bwd_table
+    DOT      dot_ce_fwd                                          | dot_ce_bwd_q, dot_ce_bwd_table
   _BatchedAllEntityLinkPredictionFn   the same sum with EVERY entity outside the row's known-true list as a negative ("1-vs-all",
     GEMM     bilinear_query_fwd; per column panel linear_multi,  | per panel (linear_multi again unless the panel is the whole row),
     only     filtered_ce_fwd with the carry                      |   filtered_ce_bwd, linear_multi, linear_tn_multi; bilinear_query_bwd,
@@ -19,26 +22,31 @@ _L1Scorer: transE, distances to the candidates alone).  The backend calls of eve
     GEMM     linear_multi per stream, gather_ce_fwd of the mix   | gather_ce_bwd once; per stream linear_multi, linear_tn_multi
     L1       l1_ce_fwd per stream (logsumexp of the mix: torch)  | per stream l1_ce_bwd_q (the MIXED softmax, row_scale = weights * w
                                                                  |   resp. weights * (1 - w)), l1_ce_bwd_table
+    DOT      the L1 rows with dot_ce_fwd                         | ... dot_ce_bwd_q, dot_ce_bwd_table
   _BatchedGatedLinkPredictionFn       embedding-level gate of the post-aggregation models (models/PostDynamicRGCN.py:261-282)
     both     gated_query_fwd                                     | ... gated_query_bwd, segment_sum_rows x 3 (known_a, known, rel)
     GEMM     linear_multi x 2 (one q), gather_ce_mix_fwd         | gather_ce_mix_bwd, linear_multi x 2, linear_tn_multi x 2
     L1       l1_mix_ce_fwd                                       | l1_mix_ce_bwd_q, l1_mix_ce_bwd_table
+    DOT      dot_mix_ce_fwd                                      | dot_mix_ce_bwd_q, dot_mix_ce_bwd_table
   _FrozenMixCEFn                      score-level ensemble of two FROZEN models (models/aggregator.py:185-208): two relation tables,
     both     bilinear_query_fwd x 2, frozen_mix_ce               | (nothing: d_w came out of the forward launch)
              (no (rows, N) matrix; frozen_mix_ce_rows in torch on a backend without the kernel)
 
 (linear_tn_multi: one linear_tn per live window on a backend without it; gated_query_* / gather_ce_mix_*: through bilinear_query_* /
-gather_ce_* and torch on a backend without them -- the CPU test backend.)  `big` is the (B * N, D) stack of the windows' all-entity
+gather_ce_* and torch on a backend without them; dot_*: dot_ce_rows_torch and its hand-written adjoints -- the CPU test backend.)  `big` is the (B * N, D) stack of the windows' all-entity
 matrices, inp = TKG_Module.loss_inputs(...) (gated_loss_inputs for the gated node); every gradient of a gathered operand is a
 deterministic segment sum over the static index lists.  The unbatched nodes (one target graph, the query rows given):
   _CandidateCEFn       linear, gather_ce_fwd | gather_ce_bwd, linear, linear_tn
+                       (route "gather": dot_ce_fwd | dot_ce_bwd_q, dot_ce_bwd_table, base = None)
   _MixedCandidateCEFn  linear x 2, gather_ce_fwd | gather_ce_bwd, (linear, linear_tn) x 2
+                       (route "gather": dot_ce_fwd x 2, the mix and its logsumexp in torch | (dot_ce_bwd_q, dot_ce_bwd_table) x 2)
   _TranslationCEFn     l1_ce_fwd | l1_ce_bwd_q, l1_ce_bwd_table
 """
 import os
 
 import torch
 
+from ._lib import GATHER_CE_BWD_MAX_N
 from .backend import get_backend
 
 # Entity-major score GEMMs of the plain node (_GemmScorer.ce_fwd): 10 % less device time on ICEWS-shaped steps (3.51 -> 3.18 ms under
@@ -48,6 +56,8 @@ _TALL_SCORES = os.environ.get("TEMP_LOSS_TALL", "0") == "1"
 
 _L1_METHODS = ("l1_ce_fwd", "l1_ce_bwd_q", "l1_ce_bwd_table", "l1_scores")
 _L1_MIX_METHODS = ("l1_mix_ce_fwd", "l1_mix_ce_bwd_q", "l1_mix_ce_bwd_table", "l1_mix_scores")
+_DOT_METHODS = ("dot_ce_fwd", "dot_ce_bwd_q", "dot_ce_bwd_table")
+_DOT_MIX_METHODS = ("dot_mix_ce_fwd", "dot_mix_ce_bwd_q", "dot_mix_ce_bwd_table")
 
 
 def translation_supported(be=None):
@@ -158,6 +168,81 @@ def _gather_ce_mix_bwd(be, s_a, s_b, w, cand, lse, scale, inv_rows, row_scale):
     return d_a, g - d_a, (g * (s_a - s_b)).sum(dim=1)
 
 
+# -- the dot candidate calls on a backend without them (the CPU test backend): the kernels' contract in torch -----------------------
+def _cand_rows(base, cand):
+    return cand.long() if base is None else cand.long() + base.long().view(-1, 1)
+
+
+def dot_ce_rows_torch(q, table, base, cand, table_b=None, w=None):
+    """The contract of temp_dot_ce_fwd (table_b and w given: temp_dot_mix_ce_fwd, table = table_a) in plain torch, differentiable and
+    in the dtype of its inputs -> (s [P, C], loss_rows [P], lse [P]).  The reference of the kernels' tests (in float64, with autograd)
+    and, with the hand-written adjoints below, the gather route of a backend without the dot methods."""
+    rows = _cand_rows(base, cand)
+    e = table[rows]                                                                   # (P, C, d)
+    if table_b is not None:
+        wc = w.reshape(-1, 1, 1)
+        e = wc * e + (1 - wc) * table_b[rows]
+    s = (q.unsqueeze(1) * e).sum(dim=-1)
+    lse = torch.logsumexp(s, dim=1)
+    return s, lse - s[:, 0], lse
+
+
+def _dot_g(s, lse, scale, inv_rows, row_scale):
+    g = torch.exp(s - lse.view(-1, 1))
+    g[:, 0] -= 1.0
+    f = scale.reshape(-1)[0] * (row_scale if row_scale is not None else torch.full_like(lse, float(inv_rows)))
+    return g * f.view(-1, 1)
+
+
+def _torch_dot_ce_fwd(q, table, base, cand):
+    return dot_ce_rows_torch(q.detach(), table.detach(), base, cand)
+
+
+def _torch_dot_mix_ce_fwd(q, table_a, table_b, w, base, cand):
+    return dot_ce_rows_torch(q.detach(), table_a.detach(), base, cand, table_b.detach(), w.detach())
+
+
+def _torch_dot_ce_bwd_q(q, table, base, cand, s, lse, scale, inv_rows, row_scale=None):
+    g = _dot_g(s, lse, scale, inv_rows, row_scale)
+    return g, torch.einsum("pk,pkd->pd", g, table.detach()[_cand_rows(base, cand)])
+
+
+def _torch_dot_mix_ce_bwd_q(q, table_a, table_b, w, base, cand, s, lse, scale, inv_rows, row_scale=None):
+    g = _dot_g(s, lse, scale, inv_rows, row_scale)
+    rows, wc = _cand_rows(base, cand), w.detach().reshape(-1, 1, 1)
+    ea, eb = table_a.detach()[rows], table_b.detach()[rows]
+    d_q = torch.einsum("pk,pkd->pd", g, wc * ea + (1 - wc) * eb)
+    return g, d_q, (g * torch.einsum("pd,pkd->pk", q.detach(), ea - eb)).sum(dim=1)
+
+
+def _slot_terms(q, n_rows, slot_ptr, slot, g):
+    """Per slot, in list order: (its table row, its query row p = slot // C, g[slot] q[p])."""
+    sl = slot.long()
+    p = sl // g.shape[1]
+    row = torch.repeat_interleave(torch.arange(n_rows, device=q.device), (slot_ptr[1:] - slot_ptr[:-1]).long())
+    return row, p, g.reshape(-1)[sl].view(-1, 1) * q.detach()[p]
+
+
+def _torch_dot_ce_bwd_table(q, table, slot_ptr, slot, g):
+    row, _, t = _slot_terms(q, table.shape[0], slot_ptr, slot, g)
+    return torch.zeros_like(table).index_add_(0, row, t)
+
+
+def _torch_dot_mix_ce_bwd_table(q, table_a, table_b, w, slot_ptr, slot, g):
+    row, p, t = _slot_terms(q, table_a.shape[0], slot_ptr, slot, g)
+    wp = w.detach().reshape(-1)[p].view(-1, 1)
+    return torch.zeros_like(table_a).index_add_(0, row, wp * t), torch.zeros_like(table_b).index_add_(0, row, (1 - wp) * t)
+
+
+_DOT_TORCH = {f.__name__[len("_torch_"):]: f for f in (_torch_dot_ce_fwd, _torch_dot_ce_bwd_q, _torch_dot_ce_bwd_table, _torch_dot_mix_ce_fwd,
+                                                       _torch_dot_mix_ce_bwd_q, _torch_dot_mix_ce_bwd_table)}
+
+
+def _dot_fn(be, name):
+    """The backend's dot candidate method `name`, or its torch form on a backend without it."""
+    return getattr(be, name) if hasattr(be, name) else _DOT_TORCH[name]
+
+
 # -- the two scorers ------------------------------------------------------------------------------------------------------------
 # A scorer is made in a node's forward from the loss inputs and the all-entity stack and kept on the node (the one tensor it holds,
 # the L1 scorer's `base`, is saved by the node as well).  Every *_fwd also returns what the node saves for the matching *_bwd (`saved`).
@@ -261,30 +346,38 @@ class _GemmScorer:
         return d_q, self.dbig(be, d_sa, q, big_loc), self.dbig(be, d_sb, q, big_rec), d_wc
 
 
-class _L1Scorer:
-    """transE: s = -|q[row] - big[window(row) * N + cand[row, :]]|_1 at the candidates alone, ALL windows' rows in one launch; the
-    candidate side of the adjoint runs over the slot lists (_cached_l1_slots).  |q - e|_1 is not linear in the candidate, so the gated
-    mix cannot live on two score matrices: the mix kernels read both all-entity rows of every candidate."""
+class _GatherScorer:
+    """The score at the candidates alone, s[row, k] = op(q[row], big[window(row) * N + cand[row, k]]), ALL windows' rows in one launch;
+    the candidate side of the adjoint runs over the slot lists (_cached_l1_slots).  op "l1": transE, -|q - e|_1, which is not linear in
+    the candidate, so the gated mix cannot live on two score matrices: the mix kernels read both all-entity rows of every candidate.
+    op "dot": the bilinear scorers' <q, e> through the same three kernels (route "gather"): no (rows, N) matrix and no ceiling on N."""
+    op = "l1"
 
     def __init__(self, kind, inp, big):
         self.kind, self.inp, self.n_rows = kind, inp, big.shape[0]
         self.base = inp["window"] * (big.shape[0] // len(inp["splits"]))             # every row's offset into the all-entity stack
 
+    def _fn(self, be, name):
+        """The backend's method of this operation (l1_ce_fwd, dot_mix_ce_bwd_q, ...); the dot form on a backend without it -- the
+        CPU test backend -- is the same contract in torch (dot_ce_rows_torch and its adjoints, below)."""
+        m = "%s_%s" % (self.op, name)
+        return _dot_fn(be, m) if self.op == "dot" else getattr(be, m)
+
     def _slots(self, base):
         return _cached_l1_slots(self.inp, self.inp["cand"], base, self.n_rows)
 
     def ce_fwd(self, be, q, big):
-        s, loss_rows, lse = be.l1_ce_fwd(q, big, self.base, self.inp["cand"])
+        s, loss_rows, lse = self._fn(be, "ce_fwd")(q, big, self.base, self.inp["cand"])
         return loss_rows, (s, lse, self.base)
 
     def ce_bwd(self, be, q, big, saved, scale):
         s, lse, base = saved
-        g, d_q = be.l1_ce_bwd_q(q, big, base, self.inp["cand"], s, lse, scale, 1.0, self.inp["weights"])
+        g, d_q = self._fn(be, "ce_bwd_q")(q, big, base, self.inp["cand"], s, lse, scale, 1.0, self.inp["weights"])
         slot_ptr, slot = self._slots(base)
-        return d_q, be.l1_ce_bwd_table(q, big, slot_ptr, slot, g)
+        return d_q, self._fn(be, "ce_bwd_table")(q, big, slot_ptr, slot, g)
 
     def scores(self, be, q, big):
-        return be.l1_ce_fwd(q, big, self.base, self.inp["cand"])[0]               # (its lse and loss are not used)
+        return self._fn(be, "ce_fwd")(q, big, self.base, self.inp["cand"])[0]               # (its lse and loss are not used)
 
     def mixed_ce_fwd(self, be, mixed):
         lse = torch.logsumexp(mixed, dim=1)
@@ -299,27 +392,59 @@ class _L1Scorer:
 
     def stream_bwd(self, be, q, big, rs, mixed, lse, saved, scale):
         base, = saved
-        g, d_q = be.l1_ce_bwd_q(q, big, base, self.inp["cand"], mixed, lse, scale, 1.0, rs.contiguous())
+        g, d_q = self._fn(be, "ce_bwd_q")(q, big, base, self.inp["cand"], mixed, lse, scale, 1.0, rs.contiguous())
         slot_ptr, slot = self._slots(base)
-        return g, d_q, be.l1_ce_bwd_table(q, big, slot_ptr, slot, g)
+        return g, d_q, self._fn(be, "ce_bwd_table")(q, big, slot_ptr, slot, g)
 
     def mixed_grad(self, _, gs):
         return gs[0] + gs[1]                                                         # g_loc + g_rec = the unsplit mixed-score gradient
 
     def gated_ce_fwd(self, be, q, big_loc, big_rec, w_cand):
-        s, loss_rows, lse = be.l1_mix_ce_fwd(q, big_loc, big_rec, w_cand, self.base, self.inp["cand"])
+        s, loss_rows, lse = self._fn(be, "mix_ce_fwd")(q, big_loc, big_rec, w_cand, self.base, self.inp["cand"])
         return loss_rows, (s, lse, self.base)
 
     def gated_ce_bwd(self, be, q, big_loc, big_rec, w_cand, saved, scale):
         s, lse, base = saved
-        g, d_q, d_wc = be.l1_mix_ce_bwd_q(q, big_loc, big_rec, w_cand, base, self.inp["cand"], s, lse, scale, 1.0, self.inp["weights"])
+        g, d_q, d_wc = self._fn(be, "mix_ce_bwd_q")(q, big_loc, big_rec, w_cand, base, self.inp["cand"], s, lse, scale, 1.0, self.inp["weights"])
         slot_ptr, slot = self._slots(base)
-        d_big_loc, d_big_rec = be.l1_mix_ce_bwd_table(q, big_loc, big_rec, w_cand, slot_ptr, slot, g)
+        d_big_loc, d_big_rec = self._fn(be, "mix_ce_bwd_table")(q, big_loc, big_rec, w_cand, slot_ptr, slot, g)
         return d_q, d_big_loc, d_big_rec, d_wc
 
 
-def _scorer(kind, inp, big):
-    return (_L1Scorer if kind == "transE" else _GemmScorer)(kind, inp, big)
+class _L1Scorer(_GatherScorer):
+    """transE (the L1 kernels)."""
+
+
+class _DotGatherScorer(_GatherScorer):
+    """distmult / complex / simple on the gather route (the dot kernels)."""
+    op = "dot"
+
+
+ROUTES = (None, "gemm", "gather")
+
+
+def dot_gather_supported(be=None):
+    """True when the installed backend has the inner-product candidate kernels (the gather route's own launches)."""
+    be = get_backend() if be is None else be
+    return all(hasattr(be, m) for m in _DOT_METHODS + _DOT_MIX_METHODS)
+
+
+def bilinear_route(route, n_ents, be=None):
+    """The route of a bilinear scorer's sampled loss: "gemm" (scores against all entities, _GemmScorer) or "gather" (the candidates
+    alone, _DotGatherScorer).  None = auto: "gemm" unless the per-window entity count is above the LDS ceiling of temp_gather_ce_bwd
+    (_lib.GATHER_CE_BWD_MAX_N) and the backend has the dot kernels."""
+    if route not in ROUTES:
+        raise ValueError("route must be None, 'gemm' or 'gather', not %r" % (route,))
+    if route is None:
+        return "gather" if n_ents > GATHER_CE_BWD_MAX_N and dot_gather_supported(be) else "gemm"
+    return route
+
+
+def _scorer(kind, inp, big, route=None):
+    if kind == "transE":
+        return _L1Scorer(kind, inp, big)
+    gather = bilinear_route(route, big.shape[0] // len(inp["splits"])) == "gather"
+    return (_DotGatherScorer if gather else _GemmScorer)(kind, inp, big)
 
 
 # -- the batched nodes ----------------------------------------------------------------------------------------------------------
@@ -330,9 +455,9 @@ class _BatchedLinkPredictionFn(torch.autograd.Function):
     The backward mirrors it and reduces the per-row gradients of the gathered operands with deterministic segment sums."""
 
     @staticmethod
-    def forward(ctx, ent_rows, rel, big, kind, inp):
+    def forward(ctx, ent_rows, rel, big, kind, inp, route=None):
         be = get_backend()
-        sc = _scorer(kind, inp, big)
+        sc = _scorer(kind, inp, big, route)
         q = _query_fwd(be, kind, ent_rows, rel, inp)
         loss_rows, saved = sc.ce_fwd(be, q, big)
         ctx.save_for_backward(ent_rows, rel, big, q, *saved)
@@ -345,7 +470,7 @@ class _BatchedLinkPredictionFn(torch.autograd.Function):
         sc, be = ctx.scorer, get_backend()
         d_q, d_big = sc.ce_bwd(be, q, big, ctx.saved_tensors[4:], _scale(d_loss))
         d_ent, dr = _query_bwd(be, sc.kind, ent_rows, rel, sc.inp, d_q)
-        return d_ent, _segment_sum(be, dr, sc.inp["rel_inv"], rel.shape[0]), d_big, None, None
+        return d_ent, _segment_sum(be, dr, sc.inp["rel_inv"], rel.shape[0]), d_big, None, None, None
 
 
 class _BatchedEnsembleLinkPredictionFn(torch.autograd.Function):
@@ -355,9 +480,9 @@ class _BatchedEnsembleLinkPredictionFn(torch.autograd.Function):
     (temporal), then the candidate cross-entropy of the mix."""
 
     @staticmethod
-    def forward(ctx, loc_rows, rec_rows, rel, big_loc, big_rec, w, kind, inp):
+    def forward(ctx, loc_rows, rec_rows, rel, big_loc, big_rec, w, kind, inp, route=None):
         be = get_backend()
-        sc = _scorer(kind, inp, big_loc)
+        sc = _scorer(kind, inp, big_loc, route)
         qs, ss = [], []
         for rows, big in ((loc_rows, big_loc), (rec_rows, big_rec)):
             qs.append(_query_fwd(be, kind, rows, rel, inp))
@@ -384,7 +509,7 @@ class _BatchedEnsembleLinkPredictionFn(torch.autograd.Function):
             d_rel = dr if d_rel is None else d_rel + dr
         d_rel = _segment_sum(be, d_rel, sc.inp["rel_inv"], rel.shape[0])
         d_w = _mix_weight_grad(sc.mixed_grad(d_m, gs), s_l, s_r) if ctx.needs_input_grad[5] else None
-        return outs[0][0], outs[1][0], d_rel, outs[0][1], outs[1][1], d_w, None, None
+        return outs[0][0], outs[1][0], d_rel, outs[0][1], outs[1][1], d_w, None, None, None
 
 
 class _BatchedGatedLinkPredictionFn(torch.autograd.Function):
@@ -396,9 +521,9 @@ class _BatchedGatedLinkPredictionFn(torch.autograd.Function):
     The backward: the scorer's gated_ce_bwd (d_q, both stacks' gradients, d_w_cand), one gated-query pass, three segment sums."""
 
     @staticmethod
-    def forward(ctx, loc_rows, rec_rows, rel, big_loc, big_rec, w_known, w_cand, kind, inp):
+    def forward(ctx, loc_rows, rec_rows, rel, big_loc, big_rec, w_known, w_cand, kind, inp, route=None):
         be = get_backend()
-        sc = _scorer(kind, inp, big_loc)
+        sc = _scorer(kind, inp, big_loc, route)
         q = _gated_query_fwd(be, kind, loc_rows, inp["known_a"], rec_rows, inp["known"], w_known, rel, inp["rel"], inp["is_tail"])
         loss_rows, saved = sc.gated_ce_fwd(be, q, big_loc, big_rec, w_cand)
         ctx.save_for_backward(loc_rows, rec_rows, rel, big_loc, big_rec, w_known, w_cand, q, *saved)
@@ -417,13 +542,14 @@ class _BatchedGatedLinkPredictionFn(torch.autograd.Function):
         d_rec = _segment_sum(be, db, inp["known_inv"], rec_rows.shape[0])
         d_rel = _segment_sum(be, dr, inp["rel_inv"], rel.shape[0])
         return (d_loc, d_rec, d_rel, d_big_loc, d_big_rec, d_wk.reshape(w_known.shape) if ctx.needs_input_grad[5] else None,
-                d_wc.reshape(w_cand.shape) if ctx.needs_input_grad[6] else None, None, None)
+                d_wc.reshape(w_cand.shape) if ctx.needs_input_grad[6] else None, None, None, None)
 
 
-def batched_link_prediction(ent_rows, rel, big, kind, inputs):
-    """sum over windows of CE_tail + CE_head (models/DynamicRGCN.py:186-193) for scorer `kind` ('distmult' | 'complex': the GEMM
-    scorer; 'transE': the L1 scorer); `inputs` = TKG_Module.loss_inputs(...)."""
-    return _BatchedLinkPredictionFn.apply(ent_rows, rel, big, kind, inputs)
+def batched_link_prediction(ent_rows, rel, big, kind, inputs, route=None):
+    """sum over windows of CE_tail + CE_head (models/DynamicRGCN.py:186-193) for scorer `kind` ('distmult' | 'complex' | 'simple': the
+    GEMM scorer or, by `route` (bilinear_route: None | 'gemm' | 'gather'), the candidate-gather scorer; 'transE': the L1 scorer);
+    `inputs` = TKG_Module.loss_inputs(...)."""
+    return _BatchedLinkPredictionFn.apply(ent_rows, rel, big, kind, inputs, route)
 
 
 # -- the all-entity ("1-vs-all") objective ------------------------------------------------------------------------------------------
@@ -566,12 +692,13 @@ def batched_all_entity_link_prediction(ent_rows, rel, big, kind, inputs, panel=N
     return _BatchedAllEntityLinkPredictionFn.apply(ent_rows, rel, big, kind, inputs, panel)
 
 
-def batched_ensemble_link_prediction(loc_rows, rec_rows, rel, big_loc, big_rec, w, kind, inputs):
+def batched_ensemble_link_prediction(loc_rows, rec_rows, rel, big_loc, big_rec, w, kind, inputs, route=None):
     """sum over windows of the ensemble CE_tail + CE_head; `w` (rows, 1) = weight of the LOCAL stream of every stacked query row
-    (per window: [tail rows: weight_object ; head rows: weight_subject]); `inputs` = TKG_Module.loss_inputs(...)."""
+    (per window: [tail rows: weight_object ; head rows: weight_subject]); `inputs` = TKG_Module.loss_inputs(...); `route` as in
+    batched_link_prediction."""
     w = w.reshape(-1, 1).to(loc_rows.dtype).contiguous()
     return _BatchedEnsembleLinkPredictionFn.apply(loc_rows.contiguous(), rec_rows.contiguous(), rel, big_loc.contiguous(), big_rec.contiguous(),
-                                                  w, kind, inputs)
+                                                  w, kind, inputs, route)
 
 
 def gated_loss_inputs(inp, n_loc_rows, device):
@@ -588,16 +715,17 @@ def gated_loss_inputs(inp, n_loc_rows, device):
     return out
 
 
-def batched_gated_link_prediction(loc_rows, rec_rows, rel, big_loc, big_rec, w_known, w_cand, kind, inputs):
+def batched_gated_link_prediction(loc_rows, rec_rows, rel, big_loc, big_rec, w_known, w_cand, kind, inputs, route=None):
     """sum over windows of the post-aggregation CE_tail + CE_head (see _BatchedGatedLinkPredictionFn).  w_known / w_cand (rows, 1):
     per window [tail rows: w_oqs / w_oqo ; head rows: w_sqo / w_sqs]; `inputs` = gated_loss_inputs(TKG_Module.loss_inputs(...)).
-    big_loc / big_rec: the (B * N_ents, D) stacks of the windows' all-entity matrices.  kind 'distmult' | 'complex' | 'transE'."""
+    big_loc / big_rec: the (B * N_ents, D) stacks of the windows' all-entity matrices.  kind 'distmult' | 'complex' | 'transE';
+    `route` as in batched_link_prediction."""
     f = lambda t: t.reshape(-1, 1).to(loc_rows.dtype).contiguous()
     return _BatchedGatedLinkPredictionFn.apply(loc_rows.contiguous(), rec_rows.contiguous(), rel, big_loc.contiguous(), big_rec.contiguous(),
-                                               f(w_known), f(w_cand), kind, inputs)
+                                               f(w_known), f(w_cand), kind, inputs, route)
 
 
-def gated_link_prediction(loc, rec, rel, all_loc, all_rec, triplets, neg_tail, neg_head, w_sqs, w_sqo, w_oqs, w_oqo, kind):
+def gated_link_prediction(loc, rec, rel, all_loc, all_rec, triplets, neg_tail, neg_head, w_sqs, w_sqo, w_oqs, w_oqo, kind, route=None):
     """loss_tail + loss_head of ONE target graph (models/PostDynamicRGCN.py:200-202): the per-window form of
     batched_gated_link_prediction for the unbatched path (one window, its own all-entity matrices)."""
     from .tkg_module import TKG_Module
@@ -608,7 +736,7 @@ def gated_link_prediction(loc, rec, rel, all_loc, all_rec, triplets, neg_tail, n
         return loc.sum() * 0.0
     w_known = torch.cat([w_oqs.reshape(-1, 1), w_sqo.reshape(-1, 1)])
     w_cand = torch.cat([w_oqo.reshape(-1, 1), w_sqs.reshape(-1, 1)])
-    return batched_gated_link_prediction(loc, rec, rel, all_loc, all_rec, w_known, w_cand, kind, inp)
+    return batched_gated_link_prediction(loc, rec, rel, all_loc, all_rec, w_known, w_cand, kind, inp, route)
 
 
 # -- two FROZEN streams: the only gradient is the mixing weight's ---------------------------------------------------------------------
@@ -715,10 +843,14 @@ class _CandidateCEFn(torch.autograd.Function):
     """mean_p CE(query[p] . all_embeds[cand[p, :]]^T, label 0) without materialising (P, C, D)."""
 
     @staticmethod
-    def forward(ctx, query, all_embeds, cand):
+    def forward(ctx, query, all_embeds, cand, route=None):
         be = get_backend()
-        scores = be.linear(query, all_embeds, True)                  # (P, N): every positive against ALL entities
-        loss_rows, lse = be.gather_ce_fwd(scores, cand)
+        ctx.gather = bilinear_route(route, all_embeds.shape[0], be) == "gather"
+        if ctx.gather:                                               # the candidates alone: the dot kernels with base = None
+            scores, loss_rows, lse = _dot_fn(be, "dot_ce_fwd")(query, all_embeds, None, cand)
+        else:
+            scores = be.linear(query, all_embeds, True)              # (P, N): every positive against ALL entities
+            loss_rows, lse = be.gather_ce_fwd(scores, cand)
         ctx.save_for_backward(query, all_embeds, scores, lse, cand)
         return loss_rows.mean()
 
@@ -726,16 +858,21 @@ class _CandidateCEFn(torch.autograd.Function):
     def backward(ctx, d_loss):
         query, all_embeds, scores, lse, cand = ctx.saved_tensors
         be = get_backend()
+        if ctx.gather:
+            g, d_query = _dot_fn(be, "dot_ce_bwd_q")(query, all_embeds, None, cand, scores, lse, _scale(d_loss), 1.0 / max(query.shape[0], 1))
+            slot_ptr, slot = l1_slots(cand, None, all_embeds.shape[0])
+            return d_query, _dot_fn(be, "dot_ce_bwd_table")(query, all_embeds, slot_ptr, slot, g), None, None
         d_scores = be.gather_ce_bwd(scores, cand, lse, _scale(d_loss), 1.0 / max(scores.shape[0], 1))
         d_query = be.linear(d_scores, all_embeds, False)             # (P,N) . (N,D)
         d_all = be.linear_tn(d_scores, query)                        # (N,P) . (P,D)
-        return d_query, d_all, None
+        return d_query, d_all, None, None
 
 
-def candidate_cross_entropy(query, all_embeds, cand):
+def candidate_cross_entropy(query, all_embeds, cand, route=None):
     """F.cross_entropy(score(query, all_embeds[cand]), 0) for scorers that are bilinear in (query, candidate) -- DistMult and ComplEx
-    (utils/scores.py:4-44).  cand: int32 (P, C), column 0 is the true entity."""
-    return _CandidateCEFn.apply(query, all_embeds, cand)
+    (utils/scores.py:4-44).  cand: int32 (P, C), column 0 is the true entity.  `route` (bilinear_route): scores against all entities
+    ('gemm') or at the candidates alone ('gather'; None: above the LDS ceiling of temp_gather_ce_bwd)."""
+    return _CandidateCEFn.apply(query, all_embeds, cand, route)
 
 
 class _MixedCandidateCEFn(torch.autograd.Function):
@@ -745,12 +882,20 @@ class _MixedCandidateCEFn(torch.autograd.Function):
     matrices, the candidate CE reads the mixed matrix."""
 
     @staticmethod
-    def forward(ctx, q_loc, all_loc, q_rec, all_rec, w, cand):
+    def forward(ctx, q_loc, all_loc, q_rec, all_rec, w, cand, route=None):
         be = get_backend()
-        s_loc = be.linear(q_loc, all_loc, True)                      # (P, N)
-        s_rec = be.linear(q_rec, all_rec, True)
-        mixed = torch.lerp(s_rec, s_loc, w)                          # w (P, 1): w * loc + (1 - w) * rec
-        loss_rows, lse = be.gather_ce_fwd(mixed, cand)
+        ctx.gather = bilinear_route(route, all_loc.shape[0], be) == "gather"
+        if ctx.gather:                                               # per-stream dot scores at the candidates, the mix in torch
+            s_loc = _dot_fn(be, "dot_ce_fwd")(q_loc, all_loc, None, cand)[0]           # (P, C)
+            s_rec = _dot_fn(be, "dot_ce_fwd")(q_rec, all_rec, None, cand)[0]
+            mixed = torch.lerp(s_rec, s_loc, w)
+            lse = torch.logsumexp(mixed, dim=1)
+            loss_rows = lse - mixed[:, 0]
+        else:
+            s_loc = be.linear(q_loc, all_loc, True)                  # (P, N)
+            s_rec = be.linear(q_rec, all_rec, True)
+            mixed = torch.lerp(s_rec, s_loc, w)                      # w (P, 1): w * loc + (1 - w) * rec
+            loss_rows, lse = be.gather_ce_fwd(mixed, cand)
         ctx.save_for_backward(q_loc, all_loc, q_rec, all_rec, w, cand, s_loc, s_rec, mixed, lse)
         return loss_rows.mean()
 
@@ -758,18 +903,28 @@ class _MixedCandidateCEFn(torch.autograd.Function):
     def backward(ctx, d_loss):
         q_loc, all_loc, q_rec, all_rec, w, cand, s_loc, s_rec, mixed, lse = ctx.saved_tensors
         be = get_backend()
+        if ctx.gather:                                               # the MIXED softmax into each stream's kernels, row_scale = w / P resp. (1 - w) / P
+            inv, wv, scale = 1.0 / max(mixed.shape[0], 1), w.reshape(-1), _scale(d_loss)
+            slot_ptr, slot = l1_slots(cand, None, all_loc.shape[0])
+            outs, gs = [], []
+            for q, table, rs in ((q_loc, all_loc, wv * inv), (q_rec, all_rec, (1 - wv) * inv)):
+                g, d_q = _dot_fn(be, "dot_ce_bwd_q")(q, table, None, cand, mixed, lse, scale, 1.0, rs.contiguous())
+                outs += [d_q, _dot_fn(be, "dot_ce_bwd_table")(q, table, slot_ptr, slot, g)]
+                gs.append(g)
+            d_w = _mix_weight_grad(gs[0] + gs[1], s_loc, s_rec) if ctx.needs_input_grad[4] else None
+            return outs[0], outs[1], outs[2], outs[3], d_w, None, None
         d_mixed = be.gather_ce_bwd(mixed, cand, lse, _scale(d_loss), 1.0 / max(mixed.shape[0], 1))
         d_loc, d_rec = _mix_adjoint(d_mixed, w)
         d_w = _mix_weight_grad(d_mixed, s_loc, s_rec) if ctx.needs_input_grad[4] else None
         return (be.linear(d_loc, all_loc, False), be.linear_tn(d_loc, q_loc), be.linear(d_rec, all_rec, False), be.linear_tn(d_rec, q_rec),
-                d_w, None)
+                d_w, None, None)
 
 
-def candidate_cross_entropy_mixed(q_loc, all_loc, q_rec, all_rec, w, cand):
+def candidate_cross_entropy_mixed(q_loc, all_loc, q_rec, all_rec, w, cand, route=None):
     """Score-level ensemble CE (see _MixedCandidateCEFn).  w: (P, 1) mixing weight of the local stream; cand: int32 (P, C), column
-    0 is the true entity."""
+    0 is the true entity; `route` as in candidate_cross_entropy."""
     return _MixedCandidateCEFn.apply(q_loc.contiguous(), all_loc.contiguous(), q_rec.contiguous(), all_rec.contiguous(),
-                                     w.reshape(-1, 1).to(q_loc.dtype).contiguous(), cand)
+                                     w.reshape(-1, 1).to(q_loc.dtype).contiguous(), cand, route)
 
 
 class _TranslationCEFn(torch.autograd.Function):

@@ -241,7 +241,7 @@ class _PostWindowMixin(_FrequencyGateMixin):
                        if smp[0].shape[0] > 0]).to(self._device())
         big_loc, big_rec = self._stacked_alls(alls)
         return TF.batched_ensemble_link_prediction(torch.cat(locs), torch.cat(recs), self.rel_embeds, big_loc, big_rec, w,
-                                                   self.args.score_function, inp)
+                                                   self.args.score_function, inp, self.candidate_route)
 
     def ensemble_loss(self, loc, rec, all_loc, all_rec, triplets, neg_tail, neg_head, w_subject, w_object):
         """loss_tail + loss_head of one target graph, models/PostDynamicRGCN.py:335-349 + combined_scores :404-406."""
@@ -262,7 +262,7 @@ class _PostWindowMixin(_FrequencyGateMixin):
                 qs.append(torch.cat([scores.bilinear_query(name, known[:P], r, "tail"), scores.bilinear_query(name, known[P:], r, head_mode)], dim=0))
             w = torch.cat([w_object.reshape(-1, 1), w_subject.reshape(-1, 1)], dim=0)
             cand = torch.cat([neg_tail, neg_head], dim=0).to(torch.int32).contiguous()
-            return 2.0 * TF.candidate_cross_entropy_mixed(qs[0], all_loc, qs[1], all_rec, w, cand)
+            return 2.0 * TF.candidate_cross_entropy_mixed(qs[0], all_loc, qs[1], all_rec, w, cand, self.candidate_route)
         if self.translation_loss_ok(self.embed_size) and P > 0:
             # TransE: the one-window form of the batched node (the L1 candidate kernels per stream, the mix on the (2P, C) scores)
             from .tkg_module import TKG_Module
@@ -270,7 +270,7 @@ class _PostWindowMixin(_FrequencyGateMixin):
             inp = TKG_Module.loss_inputs([0], [(triplets.to(torch.int64), neg_tail, neg_head)], dev, loc.shape[0], self.rel_embeds.shape[0],
                                          head_as_tail=self.head_scored_as_tail)
             w = torch.cat([w_object.reshape(-1, 1), w_subject.reshape(-1, 1)], dim=0)
-            return TF.batched_ensemble_link_prediction(loc, rec, self.rel_embeds, all_loc, all_rec, w, name, inp)
+            return TF.batched_ensemble_link_prediction(loc, rec, self.rel_embeds, all_loc, all_rec, w, name, inp, self.candidate_route)
         labels = torch.zeros(triplets.shape[0], dtype=torch.int64, device=triplets.device)
         out = 0
         for neg, tail, w in ((neg_tail, True, w_object), (neg_head, False, w_subject)):

@@ -196,13 +196,13 @@ class _GatedLossMixin(_FrequencyGateMixin):
             w_cand = torch.cat([torch.cat([oqo.reshape(-1, 1), sqs.reshape(-1, 1)]) for sqs, sqo, oqs, oqo in live]).to(dev)
         big_loc, big_rec = self._stacked_alls(alls)
         return TF.batched_gated_link_prediction(torch.cat(locs), torch.cat(recs), self.rel_embeds, big_loc, big_rec, w_known, w_cand,
-                                                self.args.score_function, inp)
+                                                self.args.score_function, inp, self.candidate_route)
 
     def gated_loss(self, loc, rec, all_loc, all_rec, triplets, neg_tail, neg_head, w_sqs, w_sqo, w_oqs, w_oqo):
         """loss_tail + loss_head of one target graph, models/PostDynamicRGCN.py:200-202 + train_link_prediction :261-282."""
         if triplets.shape[0] > 0 and (self._gated_translation_ok() or (self._gated_fused_ok() and all_loc.shape[0] % 4 == 0)):
             return TF.gated_link_prediction(loc, rec, self.rel_embeds, all_loc, all_rec, triplets, neg_tail, neg_head,
-                                            w_sqs, w_sqo, w_oqs, w_oqo, self.args.score_function)
+                                            w_sqs, w_sqo, w_oqs, w_oqo, self.args.score_function, self.candidate_route)
         labels = torch.zeros(triplets.shape[0], dtype=torch.int64, device=triplets.device)
         r = self.rel_embeds[triplets[:, 1]]
         s = w_oqs * loc[triplets[:, 0]] + (1 - w_oqs) * rec[triplets[:, 0]]

@@ -47,6 +47,11 @@ class TKG_Module(nn.Module):
 
     _all_entity_loss_refusal = None       # a class whose loss no all-entity node covers says why here
 
+    # The route of a bilinear scorer's sampled loss (link_loss.bilinear_route), handed to every loss node: None = the score GEMMs against
+    # all entities up to the LDS ceiling of temp_gather_ce_bwd and the candidate-gather kernels above it; "gemm" / "gather" force one.
+    # Set it on a model (m.candidate_route = "gather"); the class default serves every model that does not.
+    candidate_route = None
+
     def _check_all_entity_loss(self):
         """--all-entity-loss covers the models whose loss is the plain batched node over ONE all-entity table and a bilinear scorer."""
         why = self._all_entity_loss_refusal
@@ -147,7 +152,8 @@ class TKG_Module(nn.Module):
             r = TF.gather_rows(rel_embeds, t32[:, 1].contiguous())
             known = TF.gather_rows(ent_embed, (t32[:, 0] if corrupt_tail else t32[:, 2]).contiguous())
             q = scores.bilinear_query(name, known, r, "tail" if corrupt_tail else "head")
-            return TF.candidate_cross_entropy(q.contiguous(), all_embeds_g.contiguous(), neg_samples.to(torch.int32).contiguous())
+            return TF.candidate_cross_entropy(q.contiguous(), all_embeds_g.contiguous(), neg_samples.to(torch.int32).contiguous(),
+                                              self.candidate_route)
         r = rel_embeds[triplets[:, 1]]
         if corrupt_tail:
             score = self.calc_score(ent_embed[triplets[:, 0]], r, all_embeds_g[neg_samples], mode='tail')
@@ -177,7 +183,7 @@ class TKG_Module(nn.Module):
             known = TF.gather_rows(ent_embed, torch.cat([t32[:, 0], t32[:, 2]]).contiguous())
             q = torch.cat([scores.bilinear_query(name, known[:P], r, "tail"), scores.bilinear_query(name, known[P:], r, "head")], dim=0)
             cand = torch.cat([neg_tail, neg_head], dim=0).to(torch.int32).contiguous()
-            return 2.0 * TF.candidate_cross_entropy(q.contiguous(), all_embeds_g.contiguous(), cand)
+            return 2.0 * TF.candidate_cross_entropy(q.contiguous(), all_embeds_g.contiguous(), cand, self.candidate_route)
         return (self.train_link_prediction(ent_embed, triplets, neg_tail, labels, all_embeds_g, corrupt_tail=True, rel=rel)
                 + self.train_link_prediction(ent_embed, triplets, neg_head, labels, all_embeds_g, corrupt_tail=False, rel=rel))
 
@@ -324,7 +330,8 @@ class TKG_Module(nn.Module):
             if "truth" not in inputs:
                 return None                          # loss inputs built from injected samples: the per-graph route
             return TF.batched_all_entity_link_prediction(ent_rows, self.rel_embeds if rel is None else rel, big.reshape(-1, D).contiguous(), name, inputs)
-        return TF.batched_link_prediction(ent_rows, self.rel_embeds if rel is None else rel, big.reshape(-1, D).contiguous(), name, inputs)
+        return TF.batched_link_prediction(ent_rows, self.rel_embeds if rel is None else rel, big.reshape(-1, D).contiguous(), name, inputs,
+                                          self.candidate_route)
 
     def true_sets(self):
         """The known-true lists of the train snapshots on the model's device (sampling.TrueSetStore), created on first use --
