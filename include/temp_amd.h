@@ -177,6 +177,23 @@ enum {
   TEMP_RGCN_ROUTE_COUNT = 24
 };
 long long temp_rgcn_route_launches(int route, int s);
+/* Diagnostic: which per-position GRU cell kernel ran.  The forward kernels all trace as k_gru_fwd and every instantiation of the
+ * gate-gradient kernel as k_gru_bwd_gates; each launch site of csrc/gru_kernels.hip (launch_gru_fwd_wres, launch_gru_fwd_batch,
+ * temp_gru_cell_fwd_multi's zero-state launch, launch_gru_gates_batch) adds one to its route when it launches its kernel.  The
+ * weights-resident forward also counts as (TEMP_ROUTE_WRES_SPLIT, 3) of temp_gemm_route_launches.
+ * temp_gru_route_launches returns the launches so far in this process, -1 for a route outside the table. */
+enum {
+  TEMP_GRU_FWD_WRES = 0,            /* k_gemm_wres<3, EpiGruCell<V>>: hoisted gates, d % 8 == 0, three gate tiles fit 80 KB of LDS */
+  TEMP_GRU_FWD_STREAM_HOISTED = 1,  /* k_gru_fwd<V, true>: hoisted gates, the widths the resident kernel refuses, TEMP_OPT_GRU_STREAM */
+  TEMP_GRU_FWD_STREAM_FUSED = 2,    /* k_gru_fwd<V, false>: x . W_ih^T computed inside (temp_gru_fwd)                              */
+  TEMP_GRU_FWD_ZERO = 3,            /* k_gru_fwd_zero<V>: cells of temp_gru_cell_fwd_multi whose prev is NULL                      */
+  TEMP_GRU_GATES_LPR8 = 4,          /* k_gru_bwd_gates<V, 8>: d <= 32                                                              */
+  TEMP_GRU_GATES_LPR16 = 5,         /* k_gru_bwd_gates<V, 16>: d <= 64                                                             */
+  TEMP_GRU_GATES_LPR32 = 6,         /* k_gru_bwd_gates<V, 32>: d <= 128                                                            */
+  TEMP_GRU_GATES_LPR64 = 7,         /* k_gru_bwd_gates<V, 64>: wider (a lane makes a second pass beyond d = 256)                   */
+  TEMP_GRU_ROUTE_COUNT = 8
+};
+long long temp_gru_route_launches(int route);
 /* Development only: a device buffer of `words` int64 into which instrumented kernels write cycle-counter stamps (NULL: off).
  * The edge kernels stamp 8 words per block into its first 32768 words (launches of more than 4096 blocks do not stamp).  A buffer of
  * 32768 + 4096 words or more also switches the f16 chain launchers to their stamped instantiations, which write words 32768 .. 36863

@@ -144,6 +144,7 @@ SYMBOLS = {
     "temp_f16_launches": (ctypes.c_longlong, []),
     "temp_gemm_route_launches": (ctypes.c_longlong, [_I, _I]),
     "temp_rgcn_route_launches": (ctypes.c_longlong, [_I, _I]),
+    "temp_gru_route_launches": (ctypes.c_longlong, [_I]),
     "temp_tile_launches": (ctypes.c_longlong, []),
     "temp_set_debug_buffer": (None, [c_vp, _SZ]),
     "temp_rgcn_fwd_workspace": (_SZ, [_G, _I]),

@@ -124,6 +124,7 @@ void hx_count();                            // diagnostic counter of f16-split k
 long long* debug_buffer_chain(size_t words);
 void gemm_route_count(int route, int width);   // diagnostic: one launch of dense-product kernel TEMP_ROUTE_* <width> (temp_gemm_route_launches)
 void rgcn_route_count(int route, int s);       // diagnostic: one launch of edge kernel TEMP_RGCN_* <s> (temp_rgcn_route_launches)
+void gru_route_count(int route);               // diagnostic: one launch of per-position GRU cell kernel TEMP_GRU_* (temp_gru_route_launches)
 
 inline int ceil_div(long long a, long long b) { return (int)((a + b - 1) / b); }
 inline size_t align_up(size_t x, size_t a) { return (x + a - 1) / a * a; }

@@ -384,6 +384,7 @@ static int launch_gru_fwd_wres(const GruFwdBatch& batch, int count, int d, float
   if ((size_t)96 * g.ldk * 4 > WRES_LDS_BYTES) return TEMP_E_UNSUPPORTED;
   g.tps = 3; g.n_slices = ceil_div(d, 32); g.tail_store = 3; g.gate_stride = d; g.split = 1;
   // two blocks per CU: two waves per SIMD interleave, one wave's MFMAs covering the other's loads / epilogue
+  gru_route_count(TEMP_GRU_FWD_WRES);
   return launch_wres_one<3, Epi>(K_GRU_FWD, pb, count, g, st, 64);
 }
 
@@ -598,6 +599,7 @@ static int launch_gru_fwd_batch(const GruFwdBatch& batch, int count, int d, int 
   if (variant == TEMP_GRU_TORCH) { if (hoisted) TEMP_GRU_FWD(TEMP_GRU_TORCH, true); else TEMP_GRU_FWD(TEMP_GRU_TORCH, false); }
   else { if (hoisted) TEMP_GRU_FWD(TEMP_GRU_TYPE1, true); else TEMP_GRU_FWD(TEMP_GRU_TYPE1, false); }
 #undef TEMP_GRU_FWD
+  gru_route_count(hoisted ? TEMP_GRU_FWD_STREAM_HOISTED : TEMP_GRU_FWD_STREAM_FUSED);
   return launch_status();
 }
 
@@ -624,6 +626,7 @@ static int launch_gru_gates_batch(const GruGatesBatch& batch, int count, int d, 
   if (variant == TEMP_GRU_TORCH) TEMP_GATES_V(TEMP_GRU_TORCH); else TEMP_GATES_V(TEMP_GRU_TYPE1);
 #undef TEMP_GATES_V
 #undef TEMP_GATES
+  gru_route_count(lpr == 8 ? TEMP_GRU_GATES_LPR8 : (lpr == 16 ? TEMP_GRU_GATES_LPR16 : (lpr == 32 ? TEMP_GRU_GATES_LPR32 : TEMP_GRU_GATES_LPR64)));
   return launch_status();
 }
 
@@ -817,6 +820,7 @@ int temp_gru_cell_fwd_multi(int count, const TempGruCellFwd* cells, int d, int v
     if (gx > 2048) gx = 2048;
     if (variant == TEMP_GRU_TORCH) TEMP_LAUNCH(K_GRU_FWD, k_gru_fwd_zero<TEMP_GRU_TORCH>, dim3(gx, n_zero), dim3(256), 0, st, zb, d, saved_plane);
     else TEMP_LAUNCH(K_GRU_FWD, k_gru_fwd_zero<TEMP_GRU_TYPE1>, dim3(gx, n_zero), dim3(256), 0, st, zb, d, saved_plane);
+    gru_route_count(TEMP_GRU_FWD_ZERO);
     const int rc = launch_status();
     if (rc) return rc;
   }

@@ -114,6 +114,14 @@ long long rgcn_route_launches(int route, int s) {
   if (route < 0 || route >= TEMP_RGCN_ROUTE_COUNT || s < 0 || s >= 5) return -1;
   return g_rgcn_routes[route][s].load(std::memory_order_relaxed);
 }
+static std::atomic<long long> g_gru_routes[TEMP_GRU_ROUTE_COUNT];       // (static storage: zero)
+void gru_route_count(int route) {
+  if (route >= 0 && route < TEMP_GRU_ROUTE_COUNT) g_gru_routes[route].fetch_add(1, std::memory_order_relaxed);
+}
+long long gru_route_launches(int route) {
+  if (route < 0 || route >= TEMP_GRU_ROUTE_COUNT) return -1;
+  return g_gru_routes[route].load(std::memory_order_relaxed);
+}
 }  // namespace temp
 
 extern "C" {
@@ -145,6 +153,7 @@ int temp_get_option(int key) { return temp::option(key); }
 long long temp_f16_launches(void) { return temp::hx_launches(); }
 long long temp_gemm_route_launches(int route, int width) { return temp::gemm_route_launches(route, width); }
 long long temp_rgcn_route_launches(int route, int s) { return temp::rgcn_route_launches(route, s); }
+long long temp_gru_route_launches(int route) { return temp::gru_route_launches(route); }
 
 const char* temp_error_string(int code) {
   switch (code) {
