@@ -691,6 +691,45 @@ size_t temp_gru_chain_decay_reduce_workspace(const TempGruChain* c);
 int temp_gru_chain_decay_reduce(const TempGruChain* c, const float* d_arg, float* d_wb, void* ws, size_t ws_bytes, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * Persistent window chain of the LINEAR recurrence (--module RRGCN / BiRRGCN; models/RRGCN.py:120-167, models/BiRRGCN.py:102-185):
+ *   hdec[rho] = exp(-lambda dt[rho]) . h[pi]            (0 without TEMP_CHAIN_HAS_PREV; pi = the row of the same track one step earlier)
+ *   h[rho]    = act(x[x_index ? x_index[rho] : rho] + hdec[rho] . W_i)        W_i stored (in, out), i = panel[.][0]
+ * ALL positions in ONE launch on TempGruChain's tables (panel / rows / sinfo as described there, read unchanged): a workgroup owns a
+ * panel of TEMP_CHAIN_TRACKS tracks, keeps their states in LDS and walks its steps.  Per step one 32 x d x d product on the fp32 MFMA
+ * pipe, W_i streamed from L2 in fragment order (temp_lin_chain_pack_multi: `count` <= TEMP_CHAIN_MAX_RNN matrices in one launch, w /
+ * packed HOST arrays of device pointers, temp_lin_chain_pack_floats(d) floats each).  fp32 arithmetic throughout: the state is not bounded.
+ * The decay is applied BEFORE the product (BiRRGCNLayer.forward's order; RRGCNLayer applies it behind: the same value up to rounding).
+ *   forward:  EVERY row of h and hdec [N_total][d] is written (sinfo's write flag is not read: the backward needs all of h and the
+ *             weight gradient all of hdec).
+ *   backward: positions in reverse.  g = the upstream block of the step (sinfo's up / up_row0; up: HOST array of n_up device pointers,
+ *             a NULL entry = no gradient for that block) + d_prev handed back by the successor;  d_pre[rho] = g . [h[rho] > 0] (act = 1)
+ *             or g (act = 0), every row written;  d_prev of pi = dec(rho) . (d_pre[rho] . W_i^T), kept in LDS.
+ *             d_pre is d_x (through the adjoint of x_index) and the left factor of d_W_i = hdec_i^T . d_pre_i over weight i's rows
+ *             (temp_linear_tn / _multi).  No atomics, one reduction order per launch shape: bit-repeatable.
+ * Device pointers only, no host read: capturable.  Return contract of _fwd / _bwd, in this order; nothing is launched on an error:
+ *   NULL c, d <= 0, negative counts, n_w outside 1 .. TEMP_CHAIN_MAX_RNN, act outside {0, 1}, a NULL packed[i], NULL tables or
+ *   max_steps == 0 with n_panels > 0: BADARG;  d % 4 != 0, d > TEMP_CHAIN_MAX_D or max_steps > 64: UNSUPPORTED;  (bwd) n_up outside
+ *   0 .. TEMP_CHAIN_MAX_UP or n_up > 0 with up NULL: BADARG;  n_panels == 0: TEMP_OK without a launch;  then a NULL x / h / hdec / d_pre:
+ *   BADARG.  temp_lin_chain_launches (diagnostic): forward + backward launches since the library was loaded.
+ * ---------------------------------------------------------------------------------------------- */
+#define TEMP_CHAIN_MAX_D 256
+typedef struct TempLinChain {
+  int32_t d, n_panels, n_steps, max_steps;
+  const int32_t* panel; const int32_t* rows; const int32_t* sinfo;   /* TempGruChain's tables; panel[.][0] = weight index */
+  const float* dt; float lambda;                                    /* [N_total]; dec = exp(-dt lambda) */
+  int32_t n_w; const float* packed[TEMP_CHAIN_MAX_RNN];             /* temp_lin_chain_pack_multi of each W (in, out) */
+  int32_t act;                                                      /* 0 none, 1 ReLU */
+} TempLinChain;
+int temp_lin_chain_supported(int d, int max_steps);
+size_t temp_lin_chain_pack_floats(int d);
+int temp_lin_chain_pack_multi(int count, int d, const float* const* w, float* const* packed, void* stream);
+int temp_lin_chain_fwd(const TempLinChain* c, const float* x, const int32_t* x_index /* nullable [N_total] */,
+                       float* h /* [N_total][d] */, float* hdec /* [N_total][d] */, void* stream);
+int temp_lin_chain_bwd(const TempLinChain* c, const float* h, int32_t n_up, const float* const* up /* HOST array */,
+                       float* d_pre /* [N_total][d] */, void* stream);
+long long temp_lin_chain_launches(void);
+
+/* ------------------------------------------------------------------------------------------------
  * Row gather / scatter helpers of the window loop
  * (get_prev_embeddings / update_time_diff_hist_embeddings / ent_embeds[id],
  *  models/DynamicRGCN.py:35-54,93).

@@ -64,6 +64,7 @@ CHAIN_TRACKS = 32
 CHAIN_MAX_RNN = 4
 CHAIN_MAX_UP = 8
 CHAIN_MAX_STEPS = 64
+CHAIN_MAX_D = 256           # include/temp_amd.h: TEMP_CHAIN_MAX_D
 CHAIN_PACK_F32, CHAIN_PACK_BX, CHAIN_PACK_HX, CHAIN_PACK_HX_X = 1, 2, 3, 4     # TempGruChain.pack_layout
 
 
@@ -89,6 +90,12 @@ class TempChainFwd(ctypes.Structure):
 
 class TempChainBwd(ctypes.Structure):
     _fields_ = [("saved", c_vp), ("n_up", ctypes.c_int32), ("up", c_vp)] + [(n, c_vp) for n in ("dgi", "dgh", "g4", "row_keys", "col_keys", "d_arg", "d_state")]
+
+
+class TempLinChain(ctypes.Structure):
+    _fields_ = [("d", ctypes.c_int32), ("n_panels", ctypes.c_int32), ("n_steps", ctypes.c_int32), ("max_steps", ctypes.c_int32),
+                ("panel", c_vp), ("rows", c_vp), ("sinfo", c_vp), ("dt", c_vp), ("lambda_", ctypes.c_float),
+                ("n_w", ctypes.c_int32), ("packed", c_vp * CHAIN_MAX_RNN), ("act", ctypes.c_int32)]
 
 
 class TempSubsampleJob(ctypes.Structure):
@@ -205,6 +212,12 @@ SYMBOLS = {
     "temp_gru_chain_offset_layout": (_I, [_I]),
     "temp_gru_chain_pack_multi_layout": (_I, [_I, _I, _I, ctypes.POINTER(c_vp), ctypes.POINTER(c_vp), c_vp]),
     "temp_gru_chain_offset_launches": (ctypes.c_longlong, []),
+    "temp_lin_chain_supported": (_I, [_I, _I]),
+    "temp_lin_chain_pack_floats": (_SZ, [_I]),
+    "temp_lin_chain_pack_multi": (_I, [_I, _I, ctypes.POINTER(c_vp), ctypes.POINTER(c_vp), c_vp]),
+    "temp_lin_chain_fwd": (_I, [ctypes.POINTER(TempLinChain), c_vp, c_vp, c_vp, c_vp, c_vp]),
+    "temp_lin_chain_bwd": (_I, [ctypes.POINTER(TempLinChain), c_vp, ctypes.c_int32, ctypes.POINTER(c_vp), c_vp, c_vp]),
+    "temp_lin_chain_launches": (ctypes.c_longlong, []),
     "temp_gru_grads_g4_keys": (_I, [_I, c_vp, _I, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, ctypes.c_size_t, c_vp]),
     "temp_gru_grads_g4_rows_supported": (_I, [_I, c_vp, _I, _I]),
     "temp_gru_grads_g4_rows": (_I, [_I, c_vp, _I, c_vp, _I, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, ctypes.c_size_t, c_vp]),

@@ -621,6 +621,54 @@ class HipBackend:
             assert row_keys.numel() == saved_all.shape[1] and col_keys.numel() == (len(packs) + tabs["n_panels"]) * 4 * saved_all.shape[2]
         self._chain_bwd(tabs, saved_all, ups, lam, variant, packs, b_hhs, decay, d_arg, offset, d_state, g4=g4, row_keys=row_keys, col_keys=col_keys)
 
+    # ---- persistent window chain of the linear recurrence (include/temp_amd.h: TempLinChain) ------
+    def lin_chain_supported(self, d, max_steps=0):
+        return bool(self.lib.temp_lin_chain_supported(int(d), int(max_steps)))
+
+    def lin_chain_launches(self):
+        return int(self.lib.temp_lin_chain_launches())
+
+    def lin_chain_pack_multi(self, ws):
+        """W (in, out) of several linear cells -> the chain kernels' fragment order in ONE launch (list of views of one buffer)."""
+        ws = [_f32(w, "w") for w in ws]
+        d, k = ws[0].shape[0], len(ws)
+        assert all(tuple(w.shape) == (d, d) for w in ws)
+        buf = torch.empty(k, self.lib.temp_lin_chain_pack_floats(d), dtype=torch.float32, device=ws[0].device)
+        arr = lambda ts: (ctypes.c_void_p * k)(*[t.data_ptr() for t in ts])
+        _lib.check(self.lib.temp_lin_chain_pack_multi(k, d, arr(ws), arr([buf[i] for i in range(k)]), _stream()), "temp_lin_chain_pack_multi")
+        return [buf[i] for i in range(k)]
+
+    def _lin_desc(self, tabs, d, lam, packs, act):
+        c = _lib.TempLinChain()
+        c.d, c.n_panels, c.n_steps, c.max_steps = d, tabs["n_panels"], tabs["n_steps"], tabs["max_steps"]
+        c.panel, c.rows, c.sinfo, c.dt = (_i32(tabs[k], k).data_ptr() for k in ("panel", "rows", "sinfo", "dt_bits"))
+        c.lambda_, c.n_w, c.act = float(lam), len(packs), int(act)
+        keep = [_f32(pk, "packed") for pk in packs]
+        for i, pk in enumerate(keep):
+            c.packed[i] = pk.data_ptr()
+        return c, keep
+
+    def lin_chain_fwd(self, tabs, x, x_index, lam, packs, act, h, hdec):
+        """ALL positions of the linear recurrence in one launch: h = act(x[x_index] + hdec . W), hdec = dec . h_prev; h and hdec
+        (N_total, d) are written whole.  x_index: int32 [N_total] or None (x row = chain row)."""
+        x, x_index = _f32(x, "x"), _i32(x_index, "x_index")
+        d = x.shape[1]
+        assert h.shape == hdec.shape and h.shape[1] == d and h.is_contiguous() and hdec.is_contiguous() and h.dtype == hdec.dtype == torch.float32
+        assert (x_index.shape[0] if x_index is not None else x.shape[0]) == h.shape[0]
+        c, keep = self._lin_desc(tabs, d, lam, packs, act)
+        _lib.check(self.lib.temp_lin_chain_fwd(ctypes.byref(c), _ptr(x), _ptr(x_index), _ptr(h), _ptr(hdec), _stream()), "temp_lin_chain_fwd")
+
+    def lin_chain_bwd(self, tabs, h, ups, lam, packs, act, d_pre):
+        """The backward of lin_chain_fwd in one launch: d_pre (N_total, d) = the gradient in front of the activation of every row (= d_x
+        in chain order, and the left factor of the weight gradients).  ups: one upstream gradient per block of sinfo (None: none)."""
+        h = _f32(h, "h")
+        d = h.shape[1]
+        assert d_pre.shape == h.shape and d_pre.is_contiguous() and d_pre.dtype == torch.float32
+        ups = [_f32(u, "upstream") if u is not None else None for u in ups]
+        arr = (ctypes.c_void_p * max(len(ups), 1))(*[u.data_ptr() if u is not None else None for u in ups])
+        c, keep = self._lin_desc(tabs, d, lam, packs, act)
+        _lib.check(self.lib.temp_lin_chain_bwd(ctypes.byref(c), _ptr(h), len(ups), arr, _ptr(d_pre), _stream()), "temp_lin_chain_bwd")
+
     def gru_grads_g4_supported(self, ns, d, variant):
         """True when gru_grads_g4 takes GRUs of these row counts and this width (then the chain backward should write g4)."""
         k = len(ns)

@@ -11,10 +11,11 @@ import torch
 from . import functional as TF
 from . import _lib
 from . import snapshot as S
-from .birrgcn import BiGRRGCNLayer, BiRRGCN
+from .birrgcn import BiGRRGCNLayer, BiRRGCN, BiRRGCNLayer
 from .dynamic_rgcn import DynamicRGCN, WindowBatch
 from .gru_cell import GRUCell
 from .gru_chain import GruInstance, GruProgram, gru_chain, chain_kernels_usable, offset_tables, rows_in_place_usable
+from .lin_chain import linear_chain
 from .rrgcn import run_rnn
 from .window import ChainPlan, Step, window_times
 
@@ -23,9 +24,15 @@ class BiDynamicRGCN(DynamicRGCN):
     def build_model(self):
         self.ent_encoder = BiRRGCN(self.args, self.hidden_size, self.embed_size, self.num_rels, self.total_time)
 
+    _linear_layer_class = BiRRGCNLayer
+
     def _can_batch(self):
         enc = self.ent_encoder
-        return (self.use_batched_path and enc.rec_only_last_layer and isinstance(enc.layer_2, BiGRRGCNLayer)
+        if not (self.use_batched_path and enc.rec_only_last_layer):
+            return False
+        if self._linear_layer():                  # --module BiRRGCN: DynamicRGCN._can_batch_linear's conditions
+            return self._can_batch_linear()
+        return (isinstance(enc.layer_2, BiGRRGCNLayer)
                 and not (enc.layer_2.post_aggregation or enc.layer_2.post_ensemble or enc.layer_2.impute))
 
     @staticmethod
@@ -86,7 +93,53 @@ class BiDynamicRGCN(DynamicRGCN):
         return out, (hf, hb)
 
     # -- batched path --------------------------------------------------------------------------------------
+    def _chain_weights(self):
+        l2 = self.ent_encoder.layer_2
+        return [l2.time_weight_forward, l2.time_weight_backward]
+
+    def _run_batched_linear(self, wb):
+        """--module BiRRGCN: layer 2's aggregation + self-loop of every visit at once, both directions' history positions as ONE
+        linear_chain node (forward history on weight 0, backward history on weight 1, ReLU), and the centre position on the per-row
+        operators: out = relu(pre_t + decay(Hf[pf] . W_f) + decay(Hb[pb] . W_b)) -- the ReLU follows the sum, so the centre is not
+        two cells of the chain whose outputs could be added."""
+        enc, dev = self.ent_encoder, self._device()
+        plan_f, plan_b = wb.plan
+        tf, tb = wb.target, wb.target_b
+        l2 = enc.layer_2
+        y1 = enc.layer_1.conv_table(wb.g_all, self.ent_embeds, wb.ids_all, wb.ids_inv)
+        y2 = l2.pre(wb.g_all, y1)
+        if wb.visit_rows is not None:                         # distinct-snapshot rows -> visit rows
+            y2 = TF.gather_rows(y2, wb.visit_rows, getattr(wb, "visit_inv", None))
+        wb.last_x = None
+        if wb.program is not None:
+            x_hist, pre_t = TF.row_spans(y2, [(0, tf.row0), (tf.row0, tf.n_rows)])
+            want = self._chain_want(wb)
+            got = {}
+            if want:
+                got = dict(zip(want, linear_chain(x_hist, wb.program, self._chain_weights(), l2.inv_temperature, 1 if l2.relu_fused() else 0,
+                                                  want=want)))
+            Hf, Hb = got.get(wb.hist_inst[0]), got.get(wb.hist_inst[1])
+        else:
+            order = sorted([(st.row0, st.n_rows) for st in list(plan_f.steps) + list(plan_b.steps)] + [(tf.row0, tf.n_rows)])
+            x_of = dict(zip(order, TF.row_spans(y2, order)))
+
+            def chain(plan, forward):
+                H = None
+                for st in plan.steps:
+                    _, pidx, dt = st.tensors(dev)
+                    H = l2.finish_rows(x_of[(st.row0, st.n_rows)], H, pidx, dt, forward)
+                return H
+
+            Hf, Hb = chain(plan_f, True), chain(plan_b, False)
+            pre_t = x_of[(tf.row0, tf.n_rows)]
+        _, pf, dtf = tf.tensors(dev)
+        _, pb, dtb = tb.tensors(dev)
+        out = l2.centre_rows(pre_t, Hf, pf, dtf, Hb, pb, dtb)
+        return out, ((Hf, Hf), (Hb, Hb))
+
     def _run_batched(self, wb):
+        if self._linear_layer():
+            return self._run_batched_linear(wb)
         enc, dev = self.ent_encoder, self._device()
         plan_f, plan_b = wb.plan
         tf, tb = wb.target, wb.target_b
@@ -172,7 +225,24 @@ class BiDynamicRGCN(DynamicRGCN):
         return np.concatenate([self._step_time_rows(st) for st in plan_f.steps] + [none] + [self._step_time_rows(st) for st in plan_b.steps] + [none])
 
     def _visit_rows_on_device(self):
-        return not self._can_chain()              # the chain program gathers by its own row list (chain_rows, _build_program)
+        # the GRU chain program gathers by its own row list (chain_rows, _build_program); the linear one reads the visit rows
+        return self._linear_layer() or not self._can_chain()
+
+    def _build_program_linear(self, wb):
+        """--module BiRRGCN: the history positions of both directions, forward on weight 0 and backward on weight 1, in visit order
+        [forward history | backward history] (x row = chain row); the centre position stays outside the chain (_run_batched_linear)."""
+        plan_f, plan_b = wb.plan
+        assert wb.target.row0 == sum(st.n_rows for st in plan_f.steps) + sum(st.n_rows for st in plan_b.steps)
+        inst, hist = [], []
+        for w, plan in enumerate((plan_f, plan_b)):
+            last = -1
+            for st in plan.steps:
+                inst.append(GruInstance(st.n_rows, st.row0, w, last, st.prev_idx, st.dt, st.next_idx))
+                last = len(inst) - 1
+            hist.append(last)
+        wb.program = GruProgram(inst)
+        wb.out_inst = [-1, -1]
+        wb.hist_inst = hist
 
     def _build_program(self, wb):
         """Chain program with ONE contiguous row range per direction: x rows are laid out
@@ -180,6 +250,8 @@ class BiDynamicRGCN(DynamicRGCN):
         same order, so each direction's input-gate GEMM, d_x GEMM and weight-gradient GEMMs run once over
         all of its 15 positions (the copy costs one row gather; its gradient is summed by the gather's
         backward)."""
+        if self._linear_layer():
+            return self._build_program_linear(wb)
         plan_f, plan_b = wb.plan
         tf, tb = wb.target, wb.target_b
         nf = sum(st.n_rows for st in plan_f.steps)
@@ -239,7 +311,8 @@ class BiDynamicRGCN(DynamicRGCN):
         _lib.pause_point()
         self._upload(wb, dev, train)
         _lib.pause_point()
-        if wb.program is None:
+        if wb.program is None or self._linear_layer():      # (the centre of the linear model runs on the per-row operators)
+            wb.target.tensors(dev)
             wb.target_b.tensors(dev)
         elif self.ent_encoder.use_time_embedding:
             wb.target_time = offset_tables(self._step_time_rows(wb.target), self.ent_encoder.layer_2.time_embed.shape[0], dev)
@@ -260,7 +333,9 @@ class BiDynamicRGCN(DynamicRGCN):
     # -- reference-default flags (both layers recurrent): all-entity pass of all windows at once -------------------
     def _fused_all_entity_ok(self, wb):
         if wb.batched:
-            return super()._fused_all_entity_ok(wb)
+            # --module BiRRGCN: the ReLU follows the sum of the two directions' terms, so the pair sets of the directions interact and a
+            # batched pass needs a union map in _all_maps: its all-entity pass stays per window, its loss per graph
+            return not self._linear_layer() and super()._fused_all_entity_ok(wb)
         enc = self.ent_encoder
         # (this variant keeps ONE isolated pass per entity: not while the self-loop dropout draws -- every window then needs its own mask)
         return (self.use_batched_path and not enc.use_time_embedding and not getattr(self.args, "use_embed_for_non_active", False)

@@ -95,6 +95,29 @@ class BiRRGCNLayer(RGCNLayer):
         dg = g.device_graph(h.device, self.num_rels)
         return TF.rgcn_layer(h, dg, self.weight, self.loop_weight, None, self.num_bases, None, self._drop())
 
+    # -- the pieces the window models' batched path composes (bi_dynamic_rgcn.py) -----------------
+    def pre(self, g, h):
+        """Aggregation + self-loop on graph `g`, no bias, no activation: what the recurrent terms are added to."""
+        return self._core(g, h)
+
+    def _rec(self, prev, prev_idx, dt, weight):
+        """decay(prev[prev_idx] . W) of one direction (forward_one_direction's order: the decay behind the product)."""
+        return TF.decay_rows(TF.linear_nt(TF.gather_rows(prev, prev_idx), weight), dt, self.inv_temperature)
+
+    def finish_rows(self, pre, prev, prev_idx, dt, forward):
+        """One history position of one direction on rows `pre` (forward_one_direction); prev None: no previous state."""
+        weight = self.time_weight_forward if forward else self.time_weight_backward
+        return self._finish(pre + self._rec(prev, prev_idx, dt, weight) if prev is not None else pre)
+
+    def centre_rows(self, pre, prev_f, idx_f, dt_f, prev_b, idx_b, dt_b):
+        """The centre position: act(pre + both directions' recurrent terms) -- the activation follows the SUM, so the centre is not
+        two cells whose outputs could be added."""
+        if prev_f is not None:
+            pre = pre + self._rec(prev_f, idx_f, dt_f, self.time_weight_forward)
+        if prev_b is not None:
+            pre = pre + self._rec(prev_b, idx_b, dt_b, self.time_weight_backward)
+        return self._finish(pre)
+
     def forward(self, g, prev_graph_embeds_forward, time_diff_tensor_forward, prev_graph_embeds_backward,
                 time_diff_tensor_backward, time_batched_list_t, node_sizes):
         g = g.local_var()

@@ -1,0 +1,332 @@
+// Persistent window chain of the LINEAR recurrence on gfx950 (include/temp_amd.h: TempLinChain).
+//
+//   h_p = act(x_p + (exp(-lambda dt) h_{p-1}) . W)        RRGCNLayer / BiRRGCNLayer (models/RRGCN.py:120-167, models/BiRRGCN.py:102-185)
+//
+// The structure is that of gru_chain.hip and the tables are its tables, unchanged: a workgroup owns a PANEL of 32 entity tracks, keeps
+// their states in LDS and walks every step of the panel inside one launch.  Per step the product is 32 x d x d (one third of the GRU's,
+// no gates) on v_mfma_f32_32x32x2_f32, W streamed from L2 in fragment order (k_lin_chain_pack).  All arithmetic is fp32: there is no
+// tanh, so the state has no bound a constant-scale f16 split could use.
+//
+// 256 threads (four waves), no role split: a step is three phases of the whole workgroup with two barriers,
+//   1  rows     every thread owns fixed (track, 4 columns) items: the decayed state (forward) / d_pre (backward) of the step is formed,
+//               written to global memory row-contiguously and left in LDS as the B operand (k padded with zeros);
+//   2  product  wave w owns column tiles w, w + 4 (two independent accumulators); raw products go back to LDS;
+//   3  rows     (forward only) x + product, activation, h to global memory and to LDS as the next step's state -- by the thread
+//               that reads it in phase 1 of the next step, so no barrier separates the two.
+// The backward needs no third phase: d_prev stays raw in LDS and the successor's decay is applied where phase 1 of the step before adds
+// it to the upstream gradient.  No atomics; every sum has one order per launch shape, so results are bit-repeatable.  Several
+// workgroups share a CU (60 KB of LDS at d = 200), which is what hides the L2 latency of the weight stream in this plain version.
+#include <atomic>
+#include "common.hpp"
+
+namespace temp {
+
+#define LC_TRACKS TEMP_CHAIN_TRACKS
+#define LC_HAS_PREV TEMP_CHAIN_HAS_PREV
+#define LC_ROW_MASK (TEMP_CHAIN_HAS_PREV - 1)
+#define LC_MAX_STEPS 64
+#define LC_THREADS 256
+#define LC_LDS_LIMIT (160 * 1024)
+
+struct LinGeom {
+  int NT, NQ;        // tiles of 32 columns, k-groups of 8 (both over d: the matrix is square)
+  int ldo, ldk;      // LDS strides (floats): product / state rows, B-operand rows; (stride / 4) odd: conflict-free b128 accesses across rows
+};
+__host__ __device__ inline LinGeom lin_geom(int D) {
+  LinGeom g;
+  g.NT = (D + 31) >> 5; g.NQ = (D + 7) >> 3;
+  g.ldo = g.NT * 32 + 4; g.ldk = g.NQ * 8 + 4;
+  return g;
+}
+inline size_t lin_lds_fwd(int D, int ms) { LinGeom g = lin_geom(D); return ((size_t)LC_TRACKS * (g.ldo + g.ldk) + (2 * LC_TRACKS + 1) * (size_t)ms) * 4; }
+inline size_t lin_lds_bwd(int D, int ms) { LinGeom g = lin_geom(D); return ((size_t)LC_TRACKS * (g.ldo + g.ldk) + (2 * LC_TRACKS + 3) * (size_t)ms) * 4; }
+
+struct LinArgs {
+  int D, n_panels, max_steps, act;
+  const int32_t* panel; const int32_t* rows; const int32_t* sinfo;
+  const float* dt;
+  float lambda;
+  const float4* wf[TEMP_CHAIN_MAX_RNN];      // forward pieces of every W
+  const float4* wb[TEMP_CHAIN_MAX_RNN];      // backward pieces
+};
+struct LinUps { int n; const float* p[TEMP_CHAIN_MAX_UP]; };
+struct LinPackJobs { int count; const float* w[TEMP_CHAIN_MAX_RNN]; float4* out[TEMP_CHAIN_MAX_RNN]; };
+
+// ---- W (in, out) -> fragment order -----------------------------------------------------------------------------------
+// forward  piece (tile, q, lane): float4 e -> W[8q + 4hh + e][tile*32 + li]      (k = input column, n = output column)
+// backward piece (tile, q, lane): float4 e -> W[tile*32 + li][8q + 4hh + e]      (n = input column, k = output column)
+// zero outside the matrix.  li = lane & 31, hh = lane >> 5: the A-operand layout of v_mfma_f32_32x32x2_f32 (lane supplies
+// A[i = li][k = hh]); one float4 feeds 4 consecutive MFMAs, the B fragment is read in the same k order.  blockIdx.y = the matrix.
+__global__ void __launch_bounds__(256) k_lin_chain_pack(int D, LinPackJobs jobs) {
+  const LinGeom g = lin_geom(D);
+  const float* __restrict__ W = jobs.w[blockIdx.y];
+  float4* __restrict__ out = jobs.out[blockIdx.y];
+  const int half = g.NT * g.NQ * 64;
+  for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < 2 * half; i += gridDim.x * blockDim.x) {
+    const bool fwd = i < half;
+    const int j = fwd ? i : i - half;
+    const int lane = j & 63, rest = j >> 6;
+    const int tile = rest / g.NQ, q = rest - tile * g.NQ;
+    const int n = tile * 32 + (lane & 31), k = 8 * q + 4 * (lane >> 5);
+    float v[4];
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
+      const bool in = n < D && k + e < D;
+      v[e] = !in ? 0.f : fwd ? W[(size_t)(k + e) * D + n] : W[(size_t)n * D + k + e];
+    }
+    out[i] = make_float4(v[0], v[1], v[2], v[3]);
+  }
+}
+
+// out[track][tile*32 ..] = sum_k piece(tile, k) . kb[track][k] for the wave's tiles (wave, wave + 4): two independent accumulators
+__device__ __forceinline__ void lin_product(const float4* __restrict__ w, const float* kb, float* ob, const LinGeom& g, int wave, int lane) {
+  const int li = lane & 31, hh = lane >> 5;
+  const float* krow = kb + li * g.ldk + 4 * hh;
+  for (int t0 = wave; t0 < g.NT; t0 += 8) {
+    const int t1 = t0 + 4;
+    const bool two = t1 < g.NT;
+    const float4* w0 = w + (size_t)t0 * g.NQ * 64 + lane;
+    const float4* w1 = w + (size_t)(two ? t1 : t0) * g.NQ * 64 + lane;
+    f32x16 a0, a1;
+#pragma unroll
+    for (int r = 0; r < 16; ++r) { a0[r] = 0.f; a1[r] = 0.f; }
+#pragma unroll 2
+    for (int q = 0; q < g.NQ; ++q) {
+      const float4 x0 = w0[(size_t)q * 64], x1 = w1[(size_t)q * 64];
+      const float4 h4 = ld4(krow + 8 * q);
+      a0 = __builtin_amdgcn_mfma_f32_32x32x2f32(x0.x, h4.x, a0, 0, 0, 0);
+      a1 = __builtin_amdgcn_mfma_f32_32x32x2f32(x1.x, h4.x, a1, 0, 0, 0);
+      a0 = __builtin_amdgcn_mfma_f32_32x32x2f32(x0.y, h4.y, a0, 0, 0, 0);
+      a1 = __builtin_amdgcn_mfma_f32_32x32x2f32(x1.y, h4.y, a1, 0, 0, 0);
+      a0 = __builtin_amdgcn_mfma_f32_32x32x2f32(x0.z, h4.z, a0, 0, 0, 0);
+      a1 = __builtin_amdgcn_mfma_f32_32x32x2f32(x1.z, h4.z, a1, 0, 0, 0);
+      a0 = __builtin_amdgcn_mfma_f32_32x32x2f32(x0.w, h4.w, a0, 0, 0, 0);
+      a1 = __builtin_amdgcn_mfma_f32_32x32x2f32(x1.w, h4.w, a1, 0, 0, 0);
+    }
+    // lane (li, hh) owns track li and, per register quad qq, columns tile*32 + 8qq + 4hh .. +3
+    float* d0 = ob + li * g.ldo + t0 * 32 + 4 * hh;
+#pragma unroll
+    for (int qq = 0; qq < 4; ++qq) st4(d0 + 8 * qq, make_float4(a0[4 * qq], a0[4 * qq + 1], a0[4 * qq + 2], a0[4 * qq + 3]));
+    if (two) {
+      float* d1 = ob + li * g.ldo + t1 * 32 + 4 * hh;
+#pragma unroll
+      for (int qq = 0; qq < 4; ++qq) st4(d1 + 8 * qq, make_float4(a1[4 * qq], a1[4 * qq + 1], a1[4 * qq + 2], a1[4 * qq + 3]));
+    }
+  }
+}
+
+__device__ __forceinline__ float4 relu4(float4 v) { return make_float4(fmaxf(v.x, 0.f), fmaxf(v.y, 0.f), fmaxf(v.z, 0.f), fmaxf(v.w, 0.f)); }
+
+// ---- forward ----------------------------------------------------------------------------------------------------------
+__global__ void __launch_bounds__(LC_THREADS) k_lin_chain_fwd(LinArgs a, const float* __restrict__ x, const int32_t* __restrict__ x_index,
+                                                              float* __restrict__ H, float* __restrict__ HD) {
+  extern __shared__ __attribute__((aligned(16))) float lds[];
+  const int D = a.D, D4 = D >> 2;
+  const LinGeom g = lin_geom(D);
+  float* sb = lds;                                          // [32][ldo] the tracks' states; raw products between phases 2 and 3
+  float* kb = sb + LC_TRACKS * g.ldo;                       // [32][ldk] decayed states of the step (B operand)
+  int* tabb = (int*)(kb + LC_TRACKS * g.ldk);               // [ms][32] the panel's row table
+  float* decb = (float*)(tabb + LC_TRACKS * a.max_steps);   // [ms][32] decay factor of every row
+  int* flagb = (int*)(decb + LC_TRACKS * a.max_steps);      // [ms] step flags
+  const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
+  const int items = LC_TRACKS * D4;
+
+  for (int p = blockIdx.x; p < a.n_panels; p += gridDim.x) {
+    const int wi = a.panel[4 * p], s0 = a.panel[4 * p + 1], ns = a.panel[4 * p + 2];
+    __syncthreads();                                        // (the panel before this one is done with the tables)
+    for (int i = tid; i < LC_TRACKS * g.ldk; i += LC_THREADS) kb[i] = 0.f;        // the k padding must be 0, not stale LDS
+    for (int i = tid; i < ns * LC_TRACKS; i += LC_THREADS) {
+      const int e = a.rows[(size_t)s0 * LC_TRACKS + i];
+      tabb[i] = e;
+      decb[i] = e >= 0 ? expf(-a.dt[e & LC_ROW_MASK] * a.lambda) : 0.f;
+    }
+    for (int i = tid; i < ns; i += LC_THREADS) flagb[i] = a.sinfo[4 * (size_t)(s0 + i)];
+    __syncthreads();
+
+    for (int s = 0; s < ns; ++s) {
+      const bool any_prev = (flagb[s] & 1) != 0;
+      // 1: hdec = dec . (the track's state), 0 for a row without a previous state (a select: stale LDS is never multiplied)
+      for (int i = tid; i < items; i += LC_THREADS) {
+        const int t = i / D4, c = (i - t * D4) << 2;
+        const int e = tabb[s * LC_TRACKS + t];
+        float4 hd = zero4();
+        if (e >= 0) {
+          if (e & LC_HAS_PREV) hd = scale4(ld4(sb + t * g.ldo + c), decb[s * LC_TRACKS + t]);
+          st4(HD + (size_t)(e & LC_ROW_MASK) * D + c, hd);
+        }
+        st4(kb + t * g.ldk + c, hd);
+      }
+      __syncthreads();
+      // 2: hdec . W (skipped where no track of the step carries a state: the product is 0)
+      if (any_prev) lin_product(a.wf[wi], kb, sb, g, wave, lane);
+      __syncthreads();
+      // 3: h = act(x + product)
+      for (int i = tid; i < items; i += LC_THREADS) {
+        const int t = i / D4, c = (i - t * D4) << 2;
+        const int e = tabb[s * LC_TRACKS + t];
+        if (e < 0) continue;
+        const int row = e & LC_ROW_MASK;
+        const size_t xr = x_index ? (size_t)x_index[row] : (size_t)row;
+        float4 v = ld4(x + xr * D + c);
+        if (any_prev) v = add4(v, ld4(sb + t * g.ldo + c));
+        if (a.act) v = relu4(v);
+        st4(H + (size_t)row * D + c, v);
+        st4(sb + t * g.ldo + c, v);
+      }
+    }
+  }
+}
+
+// ---- backward ---------------------------------------------------------------------------------------------------------
+__global__ void __launch_bounds__(LC_THREADS) k_lin_chain_bwd(LinArgs a, LinUps ups, const float* __restrict__ H, float* __restrict__ DP) {
+  extern __shared__ __attribute__((aligned(16))) float lds[];
+  const int D = a.D, D4 = D >> 2;
+  const LinGeom g = lin_geom(D);
+  float* pb = lds;                                          // [32][ldo] raw d_pre . W^T of the step walked before (the successor's)
+  float* kb = pb + LC_TRACKS * g.ldo;                       // [32][ldk] d_pre of the step (B operand)
+  int* tabb = (int*)(kb + LC_TRACKS * g.ldk);
+  float* decb = (float*)(tabb + LC_TRACKS * a.max_steps);
+  int* infob = (int*)(decb + LC_TRACKS * a.max_steps);      // [ms][3] flags, up, up_row0
+  const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
+  const int items = LC_TRACKS * D4;
+
+  for (int p = blockIdx.x; p < a.n_panels; p += gridDim.x) {
+    const int wi = a.panel[4 * p], s0 = a.panel[4 * p + 1], ns = a.panel[4 * p + 2];
+    __syncthreads();
+    for (int i = tid; i < LC_TRACKS * g.ldk; i += LC_THREADS) kb[i] = 0.f;
+    for (int i = tid; i < ns * LC_TRACKS; i += LC_THREADS) {
+      const int e = a.rows[(size_t)s0 * LC_TRACKS + i];
+      tabb[i] = e;
+      decb[i] = e >= 0 ? expf(-a.dt[e & LC_ROW_MASK] * a.lambda) : 0.f;
+    }
+    for (int i = tid; i < 3 * ns; i += LC_THREADS) { const int s = i / 3; infob[i] = a.sinfo[4 * (size_t)(s0 + s) + (i - 3 * s)]; }
+    __syncthreads();
+
+    for (int s = ns - 1; s >= 0; --s) {
+      const int flags = infob[3 * s], up = infob[3 * s + 1], up0 = infob[3 * s + 2];
+      const float* upp = ((flags & 2) && up >= 0 && up < ups.n) ? ups.p[up] : nullptr;
+      const bool succ = s + 1 < ns;
+      // 1: g = upstream + dec(successor) . d_prev(successor);  d_pre = g . [h > 0]
+      for (int i = tid; i < items; i += LC_THREADS) {
+        const int t = i / D4, c = (i - t * D4) << 2;
+        const int e = tabb[s * LC_TRACKS + t];
+        float4 gv = zero4();
+        if (e >= 0) {
+          const int row = e & LC_ROW_MASK;
+          if (upp) gv = ld4(upp + (size_t)(row - up0) * D + c);
+          if (succ) {
+            const int en = tabb[(s + 1) * LC_TRACKS + t];
+            if (en >= 0 && (en & LC_HAS_PREV)) gv = fma4(decb[(s + 1) * LC_TRACKS + t], ld4(pb + t * g.ldo + c), gv);
+          }
+          if (a.act) gv = relu_gate4(ld4(H + (size_t)row * D + c), gv);
+          st4(DP + (size_t)row * D + c, gv);
+        }
+        st4(kb + t * g.ldk + c, gv);
+      }
+      __syncthreads();
+      // 2: d_pre . W^T, read by the step before this one (only rows with a previous state hand a gradient back)
+      if (flags & 1) lin_product(a.wb[wi], kb, pb, g, wave, lane);
+      __syncthreads();
+    }
+  }
+}
+
+template <class K>
+static int lin_lds_attr(K kernel, bool* done) {
+  if (*done) return TEMP_OK;
+  if (hipFuncSetAttribute((const void*)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, LC_LDS_LIMIT) != hipSuccess) return TEMP_E_LAUNCH;
+  *done = true;
+  return TEMP_OK;
+}
+
+static std::atomic<long long> g_lin_launches{0};
+
+}  // namespace temp
+
+using namespace temp;
+
+extern "C" {
+
+int temp_lin_chain_supported(int d, int max_steps) {
+  if (d <= 0 || d % 4 || d > TEMP_CHAIN_MAX_D || max_steps < 0 || max_steps > LC_MAX_STEPS) return 0;
+  return lin_lds_fwd(d, LC_MAX_STEPS) <= LC_LDS_LIMIT && lin_lds_bwd(d, LC_MAX_STEPS) <= LC_LDS_LIMIT;
+}
+
+size_t temp_lin_chain_pack_floats(int d) {
+  if (d <= 0) return 0;
+  const LinGeom g = lin_geom(d);
+  return (size_t)2 * g.NT * g.NQ * 64 * 4;
+}
+
+int temp_lin_chain_pack_multi(int count, int d, const float* const* w, float* const* packed, void* stream) {
+  if (count <= 0 || count > TEMP_CHAIN_MAX_RNN || d <= 0 || !w || !packed) return TEMP_E_BADARG;
+  for (int i = 0; i < count; ++i) if (!w[i] || !packed[i]) return TEMP_E_BADARG;
+  if (!temp_lin_chain_supported(d, 0)) return TEMP_E_UNSUPPORTED;
+  const LinGeom g = lin_geom(d);
+  LinPackJobs jobs = {};
+  jobs.count = count;
+  for (int i = 0; i < count; ++i) { jobs.w[i] = w[i]; jobs.out[i] = (float4*)packed[i]; }
+  TEMP_LAUNCH(K_LIN_CHAIN_PACK, k_lin_chain_pack, dim3(ceil_div((long long)2 * g.NT * g.NQ * 64, 256), count), dim3(256), 0, (hipStream_t)stream, d, jobs);
+  return launch_status();
+}
+
+}  // extern "C"
+
+// descriptor checks shared by both calls; *launch = 0 where the call succeeds without one (no panels)
+static int lin_check(const TempLinChain* c, LinArgs* a, int* launch) {
+  *launch = 0;
+  if (!c || c->d <= 0 || c->n_panels < 0 || c->n_steps < 0 || c->max_steps < 0) return TEMP_E_BADARG;
+  if (c->n_w < 1 || c->n_w > TEMP_CHAIN_MAX_RNN || (c->act != 0 && c->act != 1)) return TEMP_E_BADARG;
+  for (int i = 0; i < c->n_w; ++i) if (!c->packed[i]) return TEMP_E_BADARG;
+  if (c->n_panels > 0 && (!c->panel || !c->rows || !c->sinfo || !c->dt || c->max_steps == 0)) return TEMP_E_BADARG;
+  if (!temp_lin_chain_supported(c->d, c->max_steps)) return TEMP_E_UNSUPPORTED;
+  if (c->n_panels == 0) return TEMP_OK;
+  const LinGeom g = lin_geom(c->d);
+  LinArgs r = {};
+  r.D = c->d; r.n_panels = c->n_panels; r.max_steps = c->max_steps; r.act = c->act;
+  r.panel = c->panel; r.rows = c->rows; r.sinfo = c->sinfo; r.dt = c->dt; r.lambda = c->lambda;
+  for (int i = 0; i < c->n_w; ++i) {
+    r.wf[i] = (const float4*)c->packed[i];
+    r.wb[i] = r.wf[i] + (size_t)g.NT * g.NQ * 64;
+  }
+  *a = r;
+  *launch = 1;
+  return TEMP_OK;
+}
+
+extern "C" {
+
+int temp_lin_chain_fwd(const TempLinChain* c, const float* x, const int32_t* x_index, float* h, float* hdec, void* stream) {
+  LinArgs a;
+  int launch;
+  const int rc = lin_check(c, &a, &launch);
+  if (rc || !launch) return rc;
+  if (!x || !h || !hdec) return TEMP_E_BADARG;
+  static bool attr = false;
+  if (lin_lds_attr(k_lin_chain_fwd, &attr)) return TEMP_E_LAUNCH;
+  g_lin_launches.fetch_add(1, std::memory_order_relaxed);
+  TEMP_LAUNCH(K_LIN_CHAIN_FWD, k_lin_chain_fwd, dim3(a.n_panels), dim3(LC_THREADS), lin_lds_fwd(a.D, a.max_steps), (hipStream_t)stream, a, x, x_index, h, hdec);
+  return launch_status();
+}
+
+int temp_lin_chain_bwd(const TempLinChain* c, const float* h, int32_t n_up, const float* const* up, float* d_pre, void* stream) {
+  LinArgs a;
+  int launch;
+  const int rc = lin_check(c, &a, &launch);
+  if (rc) return rc;
+  if (n_up < 0 || n_up > TEMP_CHAIN_MAX_UP || (n_up > 0 && !up)) return TEMP_E_BADARG;
+  if (!launch) return TEMP_OK;
+  if (!h || !d_pre) return TEMP_E_BADARG;
+  LinUps ups = {};
+  ups.n = n_up;
+  for (int i = 0; i < n_up; ++i) ups.p[i] = up[i];
+  static bool attr = false;
+  if (lin_lds_attr(k_lin_chain_bwd, &attr)) return TEMP_E_LAUNCH;
+  g_lin_launches.fetch_add(1, std::memory_order_relaxed);
+  TEMP_LAUNCH(K_LIN_CHAIN_BWD, k_lin_chain_bwd, dim3(a.n_panels), dim3(LC_THREADS), lin_lds_bwd(a.D, a.max_steps), (hipStream_t)stream, a, ups, h, d_pre);
+  return launch_status();
+}
+
+long long temp_lin_chain_launches(void) { return g_lin_launches.load(std::memory_order_relaxed); }
+
+}  // extern "C"

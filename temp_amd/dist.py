@@ -247,6 +247,7 @@ class SnapshotShardedEncoder:
         self.world = dist.get_world_size(group)
         self.rank = dist.get_rank(group)
         assert model._can_batch() and model._can_chain(), "snapshot sharding needs the batched GRU + rec-only-last-layer path"
+        assert not model._linear_layer(), "snapshot sharding runs the GRU chain only: --module RRGCN / BiRRGCN (the linear chain) is not sharded"
         assert model.ent_encoder.layer_2.decay_spec() is None, \
             "snapshot sharding runs the fixed decay only: --learnable-lambda (a learnable decay) is not sharded"
         assert not model.ent_encoder.use_time_embedding, \

@@ -9,7 +9,8 @@ Two execution paths, same results:
   * batched (GRU module + --rec-only-last-layer, the paper's recommended mode): the two RGCN layers
     of EVERY visit of the step run as ONE launch each over a block-diagonal union of all visited
     snapshots, and only the fused decay+GRU kernel walks the window positions, reading its
-    previous state through `prev_idx`.
+    previous state through `prev_idx`.  --module RRGCN (the linear recurrence) takes the same path in its plain form
+    (_can_batch_linear): layer 2's aggregation + self-loop of every visit at once, then lin_chain.linear_chain.
 """
 import numpy as np
 import torch
@@ -18,11 +19,12 @@ from . import functional as TF
 from . import _lib
 from . import _hostlib
 from . import snapshot as S
-from .rrgcn import RRGCN, GRRGCNLayer, run_rnn
+from .rrgcn import RRGCN, GRRGCNLayer, RRGCNLayer, run_rnn
 from .tkg_module import TKG_Module
 from .gru_chain import (GruInstance, GruProgram, chain_decay_usable, chain_offset_usable, gru_chain, offset_tables, prepare_program, rows_in_place_usable,
                         program_on_chain_kernels, zero_state_program)
 from .gru_cell import GRUCell
+from .lin_chain import linear_chain, prepare_linear_program
 from .window import ChainPlan, Step, concat_steps, concat_steps_dedup, window_times
 
 
@@ -67,9 +69,32 @@ class DynamicRGCN(TKG_Module):
         layer-1 rows that differ per visit -- nothing of a visit is shared then.  (Round-4 verdict: de-duplication ignored it.)"""
         return self.dedup_snapshots and not self._dropout_active(train)
 
+    # --module RRGCN / BiRRGCN (the linear recurrence) on the batched path: the whole recurrence as one linear_chain node.  False keeps
+    # the per-position loop reachable ON the batched path (linear_nt + decay_rows per position), for A/B runs and tests
+    use_lin_chain = True
+    _linear_model_classes = ("DynamicRGCN", "BiDynamicRGCN")      # the window models proper: the Impute* / Post* / attention classes keep their paths
+    _linear_layer_class = RRGCNLayer                               # (BiDynamicRGCN: BiRRGCNLayer)
+
+    def _linear_layer(self):
+        """Layer 2 is a linear-recurrence layer (RRGCNLayer / BiRRGCNLayer: a `time_weight*` matrix instead of a GRU)."""
+        return isinstance(self.ent_encoder.layer_2, self._linear_layer_class)
+
+    def _can_batch_linear(self):
+        """--module RRGCN / BiRRGCN with --rec-only-last-layer takes the batched path in its plain form only: fixed decay, no time
+        embedding, no impute / post-* stream, no bias on layer 2, one layer, an activation the kernels know (none, or the fused ReLU)."""
+        enc, args = self.ent_encoder, self.args
+        l2 = enc.layer_2
+        return (type(self).__name__ in self._linear_model_classes and self._linear_layer() and l2.decay_spec() is None
+                and not enc.use_time_embedding and not l2.impute and not getattr(args, "post_aggregation", False)
+                and not getattr(args, "post_ensemble", False) and not l2.bias and getattr(l2, "num_layers", 1) == 1 and l2._post_act is None)
+
     def _can_batch(self):
         enc = self.ent_encoder
-        return (self.use_batched_path and enc.rec_only_last_layer and isinstance(enc.layer_2, GRRGCNLayer)
+        if not (self.use_batched_path and enc.rec_only_last_layer):
+            return False
+        if self._linear_layer():
+            return self._can_batch_linear()
+        return (isinstance(enc.layer_2, GRRGCNLayer)
                 and not (enc.layer_2.post_aggregation or enc.layer_2.post_ensemble or enc.layer_2.impute))
 
     def _can_stack(self):
@@ -177,6 +202,8 @@ class DynamicRGCN(TKG_Module):
         kernels take one (a backend without gru_chain_decay_supported / gru_chain_offset_supported keeps the per-position loop)."""
         enc = self.ent_encoder
         l2 = enc.layer_2
+        if self._linear_layer():                     # the linear recurrence: one linear_chain node (lin_chain.py)
+            return bool(self.use_lin_chain)
         if not (self.use_gru_chain and getattr(l2, "num_layers", 1) == 1):
             return False
         if enc.use_time_embedding and not self._chain_takes_offset():
@@ -237,7 +264,41 @@ class DynamicRGCN(TKG_Module):
         """The host list `rows` with GRU input = y2[rows] for the chain program (None: the input is y2 itself)."""
         return wb.visit_rows_host if wb.visit_rows is not None else None
 
+    def _chain_weights(self):
+        """The `time_weight` matrices of the linear recurrence, in the order of the program's weight indices."""
+        return [self.ent_encoder.layer_2.time_weight]
+
+    def _run_batched_linear(self, wb):
+        """--module RRGCN: layer 2's aggregation + self-loop of EVERY visit in one launch group (no bias, no activation: the
+        activation follows the recurrent term), then h_p = act(pre_p + dec . h_{p-1} . W) over all positions as one linear_chain node."""
+        enc, dev = self.ent_encoder, self._device()
+        l2 = enc.layer_2
+        y1 = enc.layer_1.conv_table(wb.g_all, self.ent_embeds, wb.ids_all, wb.ids_inv)
+        y2 = l2.pre(wb.g_all, y1)
+        act = 1 if l2.relu_fused() else 0
+        wb.last_x = None
+        if wb.program is not None:
+            want = self._chain_want(wb)
+            if wb.visit_rows is not None:             # distinct-snapshot rows -> visit rows, gathered by the node
+                got = linear_chain(None, wb.program, self._chain_weights(), l2.inv_temperature, act, want=want,
+                                   table=(y2, wb.visit_rows, getattr(wb, "visit_inv", None), False))
+            else:
+                got = linear_chain(y2, wb.program, self._chain_weights(), l2.inv_temperature, act, want=want)
+            hist = got[1] if wb.hist_inst >= 0 else None
+            return got[0], (hist, hist)
+        if wb.visit_rows is not None:
+            y2 = TF.gather_rows(y2, wb.visit_rows, getattr(wb, "visit_inv", None))
+        H, hist = None, None
+        for st, x in zip(wb.steps, TF.row_spans(y2, [(st.row0, st.n_rows) for st in wb.steps])):
+            _, pidx, dt = st.tensors(dev)
+            H = l2.finish_rows(x, H, pidx, dt)
+            if st is not wb.target:
+                hist = H
+        return H, (hist, hist)
+
     def _run_batched(self, wb):
+        if self._linear_layer():
+            return self._run_batched_linear(wb)
         enc, dev = self.ent_encoder, self._device()
         y1 = enc.layer_1.conv_table(wb.g_all, self.ent_embeds, wb.ids_all, wb.ids_inv)
         y2 = enc.layer_2.conv(wb.g_all, y1)
@@ -325,6 +386,10 @@ class DynamicRGCN(TKG_Module):
                 self._build_program(wb)
                 wb.program.upload(dev)
                 wb.program.constants(dev, self.embed_size)
+            elif self._can_chain() and self._linear_layer():
+                self._build_program(wb)
+                _lib.pause_point()
+                prepare_linear_program(wb.program, dev, self.embed_size, len(self._chain_weights()), self._chain_want(wb))
             elif self._can_chain():
                 self._build_program(wb)
                 _lib.pause_point()
@@ -590,6 +655,8 @@ class DynamicRGCN(TKG_Module):
         B, N = len(wb.graphs), self.num_ents
         if wb.n_inactive == 0:
             return TF.gather_rows(out, maps[0]["asm"], maps[0]["asm_inv"]).view(B, N, out.shape[1])
+        if self._linear_layer():
+            return self._all_embeds_batched_linear(wb, out, hist, maps)
         l1_rec = isinstance(l1, GRRGCNLayer)
         E = TF.gather_rows(self.ent_embeds, wb.all_rep_ids, wb.all_rep_inv) if wb.all_rep else self.ent_embeds      # (window, entity) rows
         iso1 = l1.conv_isolated(E)
@@ -612,6 +679,27 @@ class DynamicRGCN(TKG_Module):
             big = g if big is None else big + g
         if enc.use_time_embedding:                   # once per window, after the directions are summed; the active rows carry it from `out`
             big = big + TF.gather_rows(l2.time_embed, wb.all_time[0], wb.all_time[1])
+        return big.view(B, N, big.shape[1])
+
+    def _all_embeds_batched_linear(self, wb, out, hist, maps):
+        """The isolated pass of the linear recurrence (RRGCNLayer.forward_isolated) for all windows at once: x = pre2(Iso1(E)) once per
+        entity (per (window, entity) while the dropout draws); an inactive entity without a previous state gets act(x[e]), a (window,
+        entity) pair with one act(x[e] + decay_rows(linear_nt(H[idx], W), dt, lam)); the active rows come from `out`."""
+        enc = self.ent_encoder
+        l1, l2 = enc.layer_1, enc.layer_2
+        B, N = len(wb.graphs), self.num_ents
+        (m,), H = maps, hist[1]
+        E = TF.gather_rows(self.ent_embeds, wb.all_rep_ids, wb.all_rep_inv) if wb.all_rep else self.ent_embeds
+        x = l2.pre_isolated(l1.conv_isolated(E))
+        parts = [out]
+        if m["n_prev"]:
+            inv = m.setdefault("_gather_inv", {})
+            if H.shape[0] not in inv:                     # static per prepared batch: the deterministic adjoint of the history gather
+                inv[H.shape[0]] = TF.gather_inverse(m["idx_host"], H.shape[0], H.device)
+            prev = TF.gather_rows(H, m["idx"], inv[H.shape[0]])
+            parts.append(l2.finish_rows(TF.gather_rows(x, m["ent"], m["ent_inv"]), prev, None, m["dt"]))
+        parts.append(l2.finish_rows(x, None, None, None))
+        big = TF.gather_rows(torch.cat(parts, dim=0), m["asm"], m["asm_inv"])
         return big.view(B, N, big.shape[1])
 
     def run_loss(self, wb, samples=None):

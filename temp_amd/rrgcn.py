@@ -78,7 +78,7 @@ class RRGCNLayer(RGCNLayer):
         nn.init.xavier_uniform_(self.time_weight, gain=nn.init.calculate_gain('relu'))
 
     def _finish(self, pre, rec):
-        out = pre + rec
+        out = pre + rec if rec is not None else pre
         if self.bias:
             out = out + self.h_bias
         if self.activation:
@@ -88,6 +88,25 @@ class RRGCNLayer(RGCNLayer):
     def _linear_core(self, g, h):
         dg = g.device_graph(h.device, self.num_rels)
         return TF.rgcn_layer(h, dg, self.weight, self.loop_weight, None, self.num_bases, None, self._drop())
+
+    # -- the pieces the window models' batched path composes (dynamic_rgcn.py) --------------------
+    def pre(self, g, h):
+        """Aggregation + self-loop on graph `g`, no bias, no activation: what the recurrent term is added to (conv() would apply the
+        activation in front of it)."""
+        return self._linear_core(g, h)
+
+    def pre_isolated(self, e):
+        return TF.rgcn_isolated(e, self.loop_weight, None, None, self._drop())
+
+    def finish_rows(self, pre, prev, prev_idx, dt):
+        """One position on rows `pre`: act(pre + decay(prev[prev_idx] . W_time) [+ bias]).  prev None: no previous state (the
+        recurrent term is 0); prev_idx None: `prev` is already aligned with the rows."""
+        rec = None
+        if prev is not None:
+            if prev_idx is not None:
+                prev = TF.gather_rows(prev, prev_idx)
+            rec = TF.decay_rows(TF.linear_nt(prev, self.time_weight), dt, self.inv_temperature)
+        return self._finish(pre, rec)
 
     def forward(self, g, prev_graph_embeds, time_diff_tensor, time_batched_list_t, node_sizes):
         g = g.local_var()
