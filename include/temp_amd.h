@@ -728,6 +728,25 @@ int temp_lin_chain_fwd(const TempLinChain* c, const float* x, const int32_t* x_i
 int temp_lin_chain_bwd(const TempLinChain* c, const float* h, int32_t n_up, const float* const* up /* HOST array */,
                        float* d_pre /* [N_total][d] */, void* stream);
 long long temp_lin_chain_launches(void);
+/* ONE position of the same recurrence on gathered rows, without the track tables (the (window, entity) pair rows of the batched
+ * all-entity pass, where both layers of --module RRGCN are recurrent):
+ *   fwd:  hdec[i] = exp(-lambda dt[i]) H[h_rows[i]]   (0 where h_rows[i] < 0);   out[i] = act(x[x_rows ? x_rows[i] : i] + hdec[i] . W)
+ *         (a negative x_rows[i] reads a zero row);
+ *   bwd:  d_pre[i] = up[i] . [out[i] > 0] (act = 1) or up[i];   d_hrows[i] = exp(-lambda dt[i]) (d_pre[i] . W^T)   (0 where h_rows[i] < 0).
+ * A workgroup of 256 threads owns 32 rows and runs the chain's three phases once (gather + decay, the 32 x d x d fp32 MFMA product, the
+ * epilogue); fp32 throughout, the decay in front of the product as in the chain; no atomics, one summation order: bit-repeatable.  All
+ * n rows of out, hdec, d_pre and d_hrows are written.  pack_fwd / pack_bwd: the first / second half of W's temp_lin_chain_pack_multi
+ * buffer (temp_lin_chain_pack_floats(d) / 2 floats each).  The caller finishes the backward: d_H and d_x are the segment sums of
+ * d_hrows / d_pre through the inverses of h_rows / x_rows, d_W = hdec^T . d_pre (temp_linear_tn).  Device pointers only: capturable.
+ * Return contract, in this order; nothing is launched on an error: n < 0, d <= 0 or act outside {0, 1}: BADARG;  a width
+ * temp_lin_rows_supported refuses (temp_lin_chain_supported's rule): UNSUPPORTED;  n == 0: TEMP_OK without a launch;  then a NULL
+ * x / H / h_rows / dt / pack / out / hdec (fwd), up / h_rows / dt / pack / d_pre / d_hrows or, with act = 1, out (bwd): BADARG. */
+int temp_lin_rows_supported(int d);
+int temp_lin_rows_fwd(int n, int d, const float* x, const int32_t* x_rows /* nullable [n] */, const float* H, const int32_t* h_rows /* [n] */,
+                      const float* dt /* [n] */, float lambda, const float* pack_fwd, int act, float* out /* [n][d] */, float* hdec /* [n][d] */,
+                      void* stream);
+int temp_lin_rows_bwd(int n, int d, const float* out, const float* up, const int32_t* h_rows, const float* dt, float lambda,
+                      const float* pack_bwd, int act, float* d_pre /* [n][d] */, float* d_hrows /* [n][d] */, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
  * Row gather / scatter helpers of the window loop

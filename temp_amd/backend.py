@@ -669,6 +669,39 @@ class HipBackend:
         c, keep = self._lin_desc(tabs, d, lam, packs, act)
         _lib.check(self.lib.temp_lin_chain_bwd(ctypes.byref(c), _ptr(h), len(ups), arr, _ptr(d_pre), _stream()), "temp_lin_chain_bwd")
 
+    # ---- one position of the linear recurrence on gathered rows (include/temp_amd.h: temp_lin_rows_fwd / _bwd) ------
+    def lin_rows_supported(self, d):
+        return bool(self.lib.temp_lin_rows_supported(int(d)))
+
+    def _lin_rows_pack(self, pack, d, backward):
+        """The forward / backward half of one matrix's lin_chain_pack_multi buffer."""
+        pack, half = _f32(pack, "packed"), self.lib.temp_lin_chain_pack_floats(d) // 2
+        assert pack.numel() == 2 * half
+        return pack.view(-1)[half:] if backward else pack.view(-1)[:half]
+
+    def lin_rows_fwd(self, x, x_rows, H, h_rows, dt, lam, pack, act, out, hdec):
+        """out = act(x[x_rows] + hdec . W), hdec = exp(-lam dt) H[h_rows] (0 where h_rows < 0), one launch; out and hdec (n, d) are
+        written whole.  x_rows: int32 [n] or None (row i reads x[i]); pack: lin_chain_pack_multi([W])[0]."""
+        x, H, dt = _f32(x, "x"), _f32(H, "H"), _f32(dt, "dt")
+        x_rows, h_rows = _i32(x_rows, "x_rows"), _i32(h_rows, "h_rows")
+        n, d = h_rows.shape[0], x.shape[1]
+        assert H.shape[1] == d and dt.numel() == n and (x_rows.shape[0] if x_rows is not None else x.shape[0]) == n
+        for t in (out, hdec):
+            assert tuple(t.shape) == (n, d) and t.is_contiguous() and t.dtype == torch.float32
+        _lib.check(self.lib.temp_lin_rows_fwd(n, d, _ptr(x), _ptr(x_rows), _ptr(H), _ptr(h_rows), _ptr(dt), float(lam),
+                                              _ptr(self._lin_rows_pack(pack, d, False)), int(act), _ptr(out), _ptr(hdec), _stream()), "temp_lin_rows_fwd")
+
+    def lin_rows_bwd(self, out, up, h_rows, dt, lam, pack, act, d_pre, d_hrows):
+        """The backward of lin_rows_fwd in one launch: d_pre = up . [out > 0] (act = 1) or up, d_hrows = exp(-lam dt) (d_pre . W^T) (0
+        where h_rows < 0); both (n, d) are written whole."""
+        out, up, dt, h_rows = _f32(out, "out"), _f32(up, "up"), _f32(dt, "dt"), _i32(h_rows, "h_rows")
+        n, d = up.shape
+        assert out.shape == up.shape and h_rows.shape[0] == n and dt.numel() == n
+        for t in (d_pre, d_hrows):
+            assert tuple(t.shape) == (n, d) and t.is_contiguous() and t.dtype == torch.float32
+        _lib.check(self.lib.temp_lin_rows_bwd(n, d, _ptr(out), _ptr(up), _ptr(h_rows), _ptr(dt), float(lam), _ptr(self._lin_rows_pack(pack, d, True)),
+                                              int(act), _ptr(d_pre), _ptr(d_hrows), _stream()), "temp_lin_rows_bwd")
+
     def gru_grads_g4_supported(self, ns, d, variant):
         """True when gru_grads_g4 takes GRUs of these row counts and this width (then the chain backward should write g4)."""
         k = len(ns)

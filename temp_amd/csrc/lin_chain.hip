@@ -16,6 +16,9 @@
 // The backward needs no third phase: d_prev stays raw in LDS and the successor's decay is applied where phase 1 of the step before adds
 // it to the upstream gradient.  No atomics; every sum has one order per launch shape, so results are bit-repeatable.  Several
 // workgroups share a CU (60 KB of LDS at d = 200), which is what hides the L2 latency of the weight stream in this plain version.
+//
+// k_lin_rows_fwd / _bwd (temp_lin_rows_*) are ONE such step on gathered rows, without the tables: the (window, entity) pair rows of the
+// batched all-entity pass.
 #include <atomic>
 #include "common.hpp"
 
@@ -231,6 +234,109 @@ __global__ void __launch_bounds__(LC_THREADS) k_lin_chain_bwd(LinArgs a, LinUps 
   }
 }
 
+// ---- one position on gathered rows (temp_lin_rows_fwd / _bwd) -----------------------------------------------------------
+// The pair rows of the batched all-entity pass: one step of the chain without the track tables.  A workgroup owns rows
+// 32 b .. 32 b + 31 and runs the three phases once; a row past n is a zero row of the B operand and is never stored.
+#define LR_ROWS LC_TRACKS
+inline size_t lin_lds_rows(int D) { LinGeom g = lin_geom(D); return ((size_t)LR_ROWS * (g.ldo + g.ldk) + 2 * LR_ROWS) * 4; }
+
+__global__ void __launch_bounds__(LC_THREADS) k_lin_rows_fwd(int n, int D, int act, const float* __restrict__ x, const int32_t* __restrict__ x_rows,
+                                                             const float* __restrict__ H, const int32_t* __restrict__ h_rows,
+                                                             const float* __restrict__ dt, float lambda, const float4* __restrict__ wf,
+                                                             float* __restrict__ out, float* __restrict__ HD) {
+  extern __shared__ __attribute__((aligned(16))) float lds[];
+  const int D4 = D >> 2;
+  const LinGeom g = lin_geom(D);
+  float* sb = lds;                                          // [32][ldo] raw products
+  float* kb = sb + LR_ROWS * g.ldo;                         // [32][ldk] decayed rows (B operand)
+  int* hrb = (int*)(kb + LR_ROWS * g.ldk);                  // [32] H row of every row (-1: none, or past n)
+  float* decb = (float*)(hrb + LR_ROWS);                    // [32] decay factor
+  const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
+  const int items = LR_ROWS * D4;
+  const long long row0 = (long long)blockIdx.x * LR_ROWS;
+
+  for (int i = tid; i < LR_ROWS * g.ldk; i += LC_THREADS) kb[i] = 0.f;            // the k padding must be 0, not stale LDS
+  if (tid < LR_ROWS) {
+    const long long row = row0 + tid;
+    const int hr = row < n ? h_rows[row] : -1;
+    hrb[tid] = hr;
+    decb[tid] = hr >= 0 ? expf(-dt[row] * lambda) : 0.f;
+  }
+  __syncthreads();
+  // 1: hdec = dec . H[h_rows], 0 for a row without a previous state
+  for (int i = tid; i < items; i += LC_THREADS) {
+    const int t = i / D4, c = (i - t * D4) << 2;
+    const long long row = row0 + t;
+    const int hr = hrb[t];
+    float4 hd = zero4();
+    if (hr >= 0) hd = scale4(ld4(H + (size_t)hr * D + c), decb[t]);
+    if (row < n) st4(HD + (size_t)row * D + c, hd);
+    st4(kb + t * g.ldk + c, hd);
+  }
+  __syncthreads();
+  // 2: hdec . W
+  lin_product(wf, kb, sb, g, wave, lane);
+  __syncthreads();
+  // 3: out = act(x + product)
+  for (int i = tid; i < items; i += LC_THREADS) {
+    const int t = i / D4, c = (i - t * D4) << 2;
+    const long long row = row0 + t;
+    if (row >= n) continue;
+    const long long xr = x_rows ? (long long)x_rows[row] : row;
+    float4 v = ld4(sb + t * g.ldo + c);
+    if (xr >= 0) v = add4(v, ld4(x + (size_t)xr * D + c));
+    if (act) v = relu4(v);
+    st4(out + (size_t)row * D + c, v);
+  }
+}
+
+__global__ void __launch_bounds__(LC_THREADS) k_lin_rows_bwd(int n, int D, int act, const float* __restrict__ out, const float* __restrict__ up,
+                                                             const int32_t* __restrict__ h_rows, const float* __restrict__ dt, float lambda,
+                                                             const float4* __restrict__ wb, float* __restrict__ DP, float* __restrict__ DH) {
+  extern __shared__ __attribute__((aligned(16))) float lds[];
+  const int D4 = D >> 2;
+  const LinGeom g = lin_geom(D);
+  float* pb = lds;                                          // [32][ldo] raw d_pre . W^T
+  float* kb = pb + LR_ROWS * g.ldo;                         // [32][ldk] d_pre (B operand)
+  int* hrb = (int*)(kb + LR_ROWS * g.ldk);
+  float* decb = (float*)(hrb + LR_ROWS);
+  const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
+  const int items = LR_ROWS * D4;
+  const long long row0 = (long long)blockIdx.x * LR_ROWS;
+
+  for (int i = tid; i < LR_ROWS * g.ldk; i += LC_THREADS) kb[i] = 0.f;
+  if (tid < LR_ROWS) {
+    const long long row = row0 + tid;
+    const int hr = row < n ? h_rows[row] : -1;
+    hrb[tid] = hr;
+    decb[tid] = hr >= 0 ? expf(-dt[row] * lambda) : 0.f;
+  }
+  __syncthreads();
+  // 1: d_pre = upstream . [out > 0]
+  for (int i = tid; i < items; i += LC_THREADS) {
+    const int t = i / D4, c = (i - t * D4) << 2;
+    const long long row = row0 + t;
+    float4 gv = zero4();
+    if (row < n) {
+      gv = ld4(up + (size_t)row * D + c);
+      if (act) gv = relu_gate4(ld4(out + (size_t)row * D + c), gv);
+      st4(DP + (size_t)row * D + c, gv);
+    }
+    st4(kb + t * g.ldk + c, gv);
+  }
+  __syncthreads();
+  // 2: d_pre . W^T
+  lin_product(wb, kb, pb, g, wave, lane);
+  __syncthreads();
+  // 3: d_hrows = dec . product, 0 for a row without a previous state (a select: the product of such a row is not read)
+  for (int i = tid; i < items; i += LC_THREADS) {
+    const int t = i / D4, c = (i - t * D4) << 2;
+    const long long row = row0 + t;
+    if (row >= n) continue;
+    st4(DH + (size_t)row * D + c, hrb[t] >= 0 ? scale4(ld4(pb + t * g.ldo + c), decb[t]) : zero4());
+  }
+}
+
 template <class K>
 static int lin_lds_attr(K kernel, bool* done) {
   if (*done) return TEMP_OK;
@@ -328,5 +434,33 @@ int temp_lin_chain_bwd(const TempLinChain* c, const float* h, int32_t n_up, cons
 }
 
 long long temp_lin_chain_launches(void) { return g_lin_launches.load(std::memory_order_relaxed); }
+
+int temp_lin_rows_supported(int d) { return temp_lin_chain_supported(d, 0); }
+
+int temp_lin_rows_fwd(int n, int d, const float* x, const int32_t* x_rows, const float* H, const int32_t* h_rows, const float* dt, float lambda,
+                      const float* pack_fwd, int act, float* out, float* hdec, void* stream) {
+  if (n < 0 || d <= 0 || (act != 0 && act != 1)) return TEMP_E_BADARG;
+  if (!temp_lin_rows_supported(d)) return TEMP_E_UNSUPPORTED;
+  if (n == 0) return TEMP_OK;
+  if (!x || !H || !h_rows || !dt || !pack_fwd || !out || !hdec) return TEMP_E_BADARG;
+  static bool attr = false;
+  if (lin_lds_attr(k_lin_rows_fwd, &attr)) return TEMP_E_LAUNCH;
+  TEMP_LAUNCH(K_LIN_ROWS_FWD, k_lin_rows_fwd, dim3(ceil_div(n, LR_ROWS)), dim3(LC_THREADS), lin_lds_rows(d), (hipStream_t)stream, n, d, act, x, x_rows, H,
+              h_rows, dt, lambda, (const float4*)pack_fwd, out, hdec);
+  return launch_status();
+}
+
+int temp_lin_rows_bwd(int n, int d, const float* out, const float* up, const int32_t* h_rows, const float* dt, float lambda, const float* pack_bwd,
+                      int act, float* d_pre, float* d_hrows, void* stream) {
+  if (n < 0 || d <= 0 || (act != 0 && act != 1)) return TEMP_E_BADARG;
+  if (!temp_lin_rows_supported(d)) return TEMP_E_UNSUPPORTED;
+  if (n == 0) return TEMP_OK;
+  if ((act && !out) || !up || !h_rows || !dt || !pack_bwd || !d_pre || !d_hrows) return TEMP_E_BADARG;
+  static bool attr = false;
+  if (lin_lds_attr(k_lin_rows_bwd, &attr)) return TEMP_E_LAUNCH;
+  TEMP_LAUNCH(K_LIN_ROWS_BWD, k_lin_rows_bwd, dim3(ceil_div(n, LR_ROWS)), dim3(LC_THREADS), lin_lds_rows(d), (hipStream_t)stream, n, d, act, out, up,
+              h_rows, dt, lambda, (const float4*)pack_bwd, d_pre, d_hrows);
+  return launch_status();
+}
 
 }  // extern "C"

@@ -10,7 +10,8 @@ Two execution paths, same results:
     of EVERY visit of the step run as ONE launch each over a block-diagonal union of all visited
     snapshots, and only the fused decay+GRU kernel walks the window positions, reading its
     previous state through `prev_idx`.  --module RRGCN (the linear recurrence) takes the same path in its plain form
-    (_can_batch_linear): layer 2's aggregation + self-loop of every visit at once, then lin_chain.linear_chain.
+    (_can_batch_linear): layer 2's aggregation + self-loop of every visit at once, then lin_chain.linear_chain; with BOTH layers
+    recurrent (its grid flags) one such pass and one chain per layer over the same program (_run_lin_stack).
 """
 import numpy as np
 import torch
@@ -79,19 +80,40 @@ class DynamicRGCN(TKG_Module):
         """Layer 2 is a linear-recurrence layer (RRGCNLayer / BiRRGCNLayer: a `time_weight*` matrix instead of a GRU)."""
         return isinstance(self.ent_encoder.layer_2, self._linear_layer_class)
 
+    def _plain_linear_layer(self, layer):
+        """A linear-recurrence layer in the form the chain takes: no impute, no bias, one layer, an activation the kernels know (none,
+        or the fused ReLU).  --learnable-lambda does not matter: the linear layers never read `exponential_decay` (models/RRGCN.py:141,161
+        decay by inv_temperature whatever the flag says), so it stays in the state dict and gets no gradient on any path."""
+        return not layer.impute and not layer.bias and getattr(layer, "num_layers", 1) == 1 and layer._post_act is None
+
     def _can_batch_linear(self):
-        """--module RRGCN / BiRRGCN with --rec-only-last-layer takes the batched path in its plain form only: fixed decay, no time
-        embedding, no impute / post-* stream, no bias on layer 2, one layer, an activation the kernels know (none, or the fused ReLU)."""
+        """--module RRGCN / BiRRGCN with --rec-only-last-layer takes the batched path in its plain form only: no time embedding, no
+        impute / post-* stream, layer 2 a _plain_linear_layer."""
         enc, args = self.ent_encoder, self.args
-        l2 = enc.layer_2
-        return (type(self).__name__ in self._linear_model_classes and self._linear_layer() and l2.decay_spec() is None
-                and not enc.use_time_embedding and not l2.impute and not getattr(args, "post_aggregation", False)
-                and not getattr(args, "post_ensemble", False) and not l2.bias and getattr(l2, "num_layers", 1) == 1 and l2._post_act is None)
+        return (type(self).__name__ in self._linear_model_classes and self._linear_layer()
+                and not enc.use_time_embedding and not getattr(args, "post_aggregation", False)
+                and not getattr(args, "post_ensemble", False) and self._plain_linear_layer(enc.layer_2))
+
+    # --module RRGCN with BOTH layers recurrent (the reference's grid flags: no --rec-only-last-layer) on the batched path: layer 1's
+    # recurrence does not read layer 2, so the window is two linear_chain nodes over ONE program (_run_lin_stack).  False keeps the
+    # reference-granular path for A/B runs and tests
+    use_lin_stack = True
+
+    def _can_stack_linear(self):
+        """Both layers RRGCNLayer in the chain's plain form on DynamicRGCN itself, one decay rate; the route is the chain node's alone
+        (use_lin_chain = False has no per-position form of it)."""
+        enc = self.ent_encoder
+        l1, l2 = enc.layer_1, enc.layer_2
+        return (type(self) is DynamicRGCN and self.use_lin_stack and self.use_lin_chain and not enc.rec_only_last_layer
+                and isinstance(l1, RRGCNLayer) and isinstance(l2, RRGCNLayer) and self._can_batch_linear()
+                and self._plain_linear_layer(l1) and l1.inv_temperature == l2.inv_temperature)
 
     def _can_batch(self):
         enc = self.ent_encoder
-        if not (self.use_batched_path and enc.rec_only_last_layer):
+        if not self.use_batched_path:
             return False
+        if not enc.rec_only_last_layer:
+            return self._can_stack_linear()
         if self._linear_layer():
             return self._can_batch_linear()
         return (isinstance(enc.layer_2, GRRGCNLayer)
@@ -268,9 +290,34 @@ class DynamicRGCN(TKG_Module):
         """The `time_weight` matrices of the linear recurrence, in the order of the program's weight indices."""
         return [self.ent_encoder.layer_2.time_weight]
 
+    def _run_lin_stack(self, wb):
+        """--module RRGCN, both layers recurrent:
+            h1_p = act(pre1(E on G_p) + dec . h1_{p-1}[prev] . Wt1)       h2_p = act(pre2(h1_p on G_p) + dec . h2_{p-1}[prev] . Wt2)
+        pre1 of every visit in one launch group (over the distinct snapshots where visits share them), chain 1 handing out EVERY row
+        (they feed layer 2), pre2 of every visit over the visit-level union, chain 2 over the same program.
+        -> (target rows of chain 2, (h1, h2) rows of the last history position: the pair DenseHistory keeps for this module)."""
+        enc = self.ent_encoder
+        l1, l2 = enc.layer_1, enc.layer_2
+        lam, prog = l2.inv_temperature, wb.program
+        act1, act2 = (1 if l.relu_fused() else 0 for l in (l1, l2))
+        y1 = l1.pre_table(wb.g_all, self.ent_embeds, wb.ids_all, wb.ids_inv)
+        wb.last_x = None
+        if wb.visit_rows is not None:                 # distinct-snapshot rows -> visit rows, gathered by the node
+            H1 = linear_chain(None, prog, [l1.time_weight], lam, act1, want=None, table=(y1, wb.visit_rows, wb.visit_inv, False))
+        else:
+            H1 = linear_chain(y1, prog, [l1.time_weight], lam, act1, want=None)
+        y2 = l2.pre(wb.g_visits, H1)
+        got = linear_chain(y2, prog, [l2.time_weight], lam, act2, want=self._chain_want(wb))
+        if wb.hist_inst < 0:
+            return got[0], (None, None)
+        it = prog.inst[wb.hist_inst]
+        return got[0], (H1[it.h0:it.h0 + it.n], got[1])
+
     def _run_batched_linear(self, wb):
         """--module RRGCN: layer 2's aggregation + self-loop of EVERY visit in one launch group (no bias, no activation: the
         activation follows the recurrent term), then h_p = act(pre_p + dec . h_{p-1} . W) over all positions as one linear_chain node."""
+        if getattr(wb, "lin_stack", False):
+            return self._run_lin_stack(wb)
         enc, dev = self.ent_encoder, self._device()
         l2 = enc.layer_2
         y1 = enc.layer_1.conv_table(wb.g_all, self.ent_embeds, wb.ids_all, wb.ids_inv)
@@ -361,6 +408,7 @@ class DynamicRGCN(TKG_Module):
         wb.program = None
         wb.visit_rows = wb.visit_rows_host = None
         wb.shared_visits = self._share_visits(train)
+        wb.lin_stack = bool(wb.batched and self._linear_layer() and not self.ent_encoder.rec_only_last_layer)
         if wb.batched or getattr(wb, "stack", False):
             if wb.shared_visits:
                 wb.g_all, vr, wb.total_rows = concat_steps_dedup(wb.steps)
@@ -386,6 +434,16 @@ class DynamicRGCN(TKG_Module):
                 self._build_program(wb)
                 wb.program.upload(dev)
                 wb.program.constants(dev, self.embed_size)
+            elif wb.lin_stack:
+                # layer 2 reads states, which differ between two windows' visits of one snapshot: the union of ALL visits in program
+                # row order (the layer-1 graph itself when no snapshot is shared); ONE program serves both chains -- chain 1 hands out
+                # every row, chain 2 the usual two instances
+                wb.g_visits = wb.g_all if wb.visit_rows_host is None else concat_steps(wb.steps)[0]
+                wb.g_visits.device_graph(dev, 2 * self.num_rels)
+                self._build_program(wb)
+                _lib.pause_point()
+                for want in (None, self._chain_want(wb)):
+                    prepare_linear_program(wb.program, dev, self.embed_size, 1, want)
             elif self._can_chain() and self._linear_layer():
                 self._build_program(wb)
                 _lib.pause_point()
@@ -684,18 +742,27 @@ class DynamicRGCN(TKG_Module):
     def _all_embeds_batched_linear(self, wb, out, hist, maps):
         """The isolated pass of the linear recurrence (RRGCNLayer.forward_isolated) for all windows at once: x = pre2(Iso1(E)) once per
         entity (per (window, entity) while the dropout draws); an inactive entity without a previous state gets act(x[e]), a (window,
-        entity) pair with one act(x[e] + decay_rows(linear_nt(H[idx], W), dt, lam)); the active rows come from `out`."""
+        entity) pair with one act(x[e] + decay_rows(linear_nt(H[idx], W), dt, lam)); the active rows come from `out`.  With both layers
+        recurrent a pair runs through both: y1p = act(Iso1(E)[e] + dec (h1[idx] . Wt1)), then act(pre_isolated2(y1p) + dec (h2[idx] . Wt2))."""
         enc = self.ent_encoder
         l1, l2 = enc.layer_1, enc.layer_2
         B, N = len(wb.graphs), self.num_ents
         (m,), H = maps, hist[1]
+        l1_rec = isinstance(l1, RRGCNLayer)               # both layers recurrent (_run_lin_stack): hist = (h1, h2) of the last history position
         E = TF.gather_rows(self.ent_embeds, wb.all_rep_ids, wb.all_rep_inv) if wb.all_rep else self.ent_embeds
-        x = l2.pre_isolated(l1.conv_isolated(E))
+        iso1 = l1.pre_isolated(E) if l1_rec else None
+        x = l2.pre_isolated(l1.finish_rows(iso1, None, None, None) if l1_rec else l1.conv_isolated(E))
         parts = [out]
         if m["n_prev"]:
             inv = m.setdefault("_gather_inv", {})
             if H.shape[0] not in inv:                     # static per prepared batch: the deterministic adjoint of the history gather
                 inv[H.shape[0]] = TF.gather_inverse(m["idx_host"], H.shape[0], H.device)
+        if m["n_prev"] and l1_rec:
+            # the pair's own first-layer state, then the second layer on it: one lin_step_rows node per layer (one map serves both)
+            act1, act2 = (1 if l.relu_fused() else 0 for l in (l1, l2))
+            y1p = TF.lin_step_rows(iso1, m["ent"], hist[0], m["idx"], m["dt"], l1.inv_temperature, l1.time_weight, act1, m["ent_inv"], inv[H.shape[0]])
+            parts.append(TF.lin_step_rows(l2.pre_isolated(y1p), None, H, m["idx"], m["dt"], l2.inv_temperature, l2.time_weight, act2, None, inv[H.shape[0]]))
+        elif m["n_prev"]:
             prev = TF.gather_rows(H, m["idx"], inv[H.shape[0]])
             parts.append(l2.finish_rows(TF.gather_rows(x, m["ent"], m["ent_inv"]), prev, None, m["dt"]))
         parts.append(l2.finish_rows(x, None, None, None))

@@ -6,6 +6,7 @@ Each Function is one reference op with its hand-written backward:
   gru_step        decay + single GRU step      models/RRGCN.py:79-85, models/GRU_cell.py:18-30
   gather_rows     ent_embeds[id] / history gather   models/DynamicRGCN.py:41-43,93
   linear          nn.Linear without bias (q/k/v projections)   models/SARGCN.py:16-18,32-34
+  lin_step_rows   the recurrent term of RRGCNLayer.forward_isolated on gathered rows   models/RRGCN.py:152-167
   history_attention   SARGCNLayer.attention over the active history rows   models/SARGCN.py:25-53
   split_history_attention  the same for current rows that are a sum of two table rows (post-aggregation attention models)
 """
@@ -350,6 +351,78 @@ class _DecayRowsFn(torch.autograd.Function):
 
 def decay_rows(x, dt, lam):
     return _DecayRowsFn.apply(x, dt, float(lam))
+
+
+LIN_ROWS_KERNEL = True      # A/B switch: False keeps lin_step_rows on the composition of the row operators
+
+
+def lin_rows_usable(d):
+    """True when lin_step_rows runs rows of this width through temp_lin_rows_fwd / _bwd."""
+    be = get_backend()
+    return bool(LIN_ROWS_KERNEL and hasattr(be, "lin_rows_fwd") and be.lin_rows_supported(d))
+
+
+def _gather_adjoint(be, src, idx, inverse, rows):
+    """The adjoint of out = table[idx] on the rows `src`: the deterministic segment sum through `inverse`, else zero fill + atomic scatter."""
+    if inverse is not None:
+        return be.segment_sum_rows(src, inverse[0], inverse[1], rows)
+    d_table = torch.zeros(rows, src.shape[1], dtype=src.dtype, device=src.device)
+    be.scatter_add_rows(src, idx, d_table)
+    return d_table
+
+
+class _LinStepRowsFn(torch.autograd.Function):
+    """The kernel route of lin_step_rows: saves out (the ReLU mask is the kernel's own out > 0) and hdec (the left factor of d_W)."""
+
+    @staticmethod
+    def forward(ctx, x, H, W, x_rows, h_rows, dt, lam, act, x_inv, h_inv):
+        be = get_backend()
+        x, H = x.detach().contiguous(), H.detach().contiguous()
+        dt = dt.detach().contiguous().view(-1)
+        n, d = h_rows.shape[0], x.shape[1]
+        pack = be.lin_chain_pack_multi([W.detach().contiguous()])[0]
+        out = torch.empty(n, d, dtype=torch.float32, device=x.device)
+        hdec = torch.empty(n, d, dtype=torch.float32, device=x.device)
+        be.lin_rows_fwd(x, x_rows, H, h_rows, dt, lam, pack, act, out, hdec)
+        ctx.save_for_backward(out, hdec, pack, dt)
+        ctx.x_rows, ctx.h_rows, ctx.x_inv, ctx.h_inv, ctx.lam, ctx.act, ctx.n_x, ctx.n_h = x_rows, h_rows, x_inv, h_inv, lam, act, x.shape[0], H.shape[0]
+        return out
+
+    @staticmethod
+    def backward(ctx, d_out):
+        be = get_backend()
+        out, hdec, pack, dt = ctx.saved_tensors
+        d_pre, d_hrows = torch.empty_like(out), torch.empty_like(out)
+        be.lin_rows_bwd(out, d_out.contiguous(), ctx.h_rows, dt, ctx.lam, pack, ctx.act, d_pre, d_hrows)
+        d_x = d_H = d_W = None
+        if ctx.needs_input_grad[0]:
+            d_x = d_pre if ctx.x_rows is None else _gather_adjoint(be, d_pre, ctx.x_rows, ctx.x_inv, ctx.n_x)
+        if ctx.needs_input_grad[1]:
+            d_H = _gather_adjoint(be, d_hrows, ctx.h_rows, ctx.h_inv, ctx.n_h)
+        if ctx.needs_input_grad[2]:
+            d_W = be.linear_tn(hdec, d_pre)
+        return d_x, d_H, d_W, None, None, None, None, None, None, None
+
+
+def lin_step_rows_torch(x, x_rows, H, h_rows, dt, lam, W, act, x_inv=None, h_inv=None):
+    """lin_step_rows as the composition of the row operators, each its own autograd node (RRGCNLayer.finish_rows' order: the decay
+    behind the product -- the same value up to rounding)."""
+    rec = decay_rows(linear_nt(gather_rows(H, h_rows, h_inv), W), dt, lam)
+    out = (gather_rows(x, x_rows, x_inv) if x_rows is not None else x) + rec
+    return torch.relu(out) if act else out
+
+
+def lin_step_rows(x, x_rows, H, h_rows, dt, lam, W, act, x_inv=None, h_inv=None):
+    """One position of the linear recurrence on gathered rows, ONE autograd node (temp_lin_rows_fwd / _bwd):
+        out[i] = act(x[x_rows[i]] + (exp(-lam dt[i]) H[h_rows[i]]) . W)         (the recurrent term 0 where h_rows[i] < 0)
+    x (., d) and H (., d) float32; x_rows int32 [n] or None (row i reads x[i]); h_rows int32 [n]; dt float32 (n,) or (n, 1); W (in, out);
+    act 0 none, 1 ReLU.  x_inv / h_inv = gather_inverse of the two static row lists: with them the gathers' adjoints are deterministic
+    segment sums (without, atomic scatters).  A backend without the kernel (the CPU test backend), LIN_ROWS_KERNEL = False, a width it
+    refuses and n = 0 take lin_step_rows_torch."""
+    act = int(bool(act))
+    if h_rows.shape[0] == 0 or not lin_rows_usable(x.shape[1]):
+        return lin_step_rows_torch(x, x_rows, H, h_rows, dt, float(lam), W, act, x_inv, h_inv)
+    return _LinStepRowsFn.apply(x, H, W, x_rows, h_rows, dt, float(lam), act, x_inv, h_inv)
 
 
 class _DiachronicRowsFn(torch.autograd.Function):

@@ -95,6 +95,13 @@ class RRGCNLayer(RGCNLayer):
         activation in front of it)."""
         return self._linear_core(g, h)
 
+    def pre_table(self, g, table, ids, inverse):
+        """pre(g, table[ids]) for a layer fed straight from an embedding table (RGCNLayer.conv_table without bias and activation)."""
+        if inverse is None or self.in_feat > 256 or self.out_feat > 256:
+            return self.pre(g, TF.gather_rows(table, ids))
+        dg = g.device_graph(table.device, self.num_rels)
+        return TF.rgcn_layer_table(table, ids, inverse, dg, self.weight, self.loop_weight, None, self.num_bases, None, self._drop())
+
     def pre_isolated(self, e):
         return TF.rgcn_isolated(e, self.loop_weight, None, None, self._drop())
 
