@@ -747,6 +747,31 @@ int temp_lin_rows_fwd(int n, int d, const float* x, const int32_t* x_rows /* nul
                       void* stream);
 int temp_lin_rows_bwd(int n, int d, const float* out, const float* up, const int32_t* h_rows, const float* dt, float lambda,
                       const float* pack_bwd, int act, float* d_pre /* [n][d] */, float* d_hrows /* [n][d] */, void* stream);
+/* ONE position of the BIDIRECTIONAL linear recurrence on gathered rows (BiRRGCNLayer's centre position and the union (window, entity)
+ * pair rows of its batched all-entity pass): both directions' recurrent terms in front of ONE activation.  For s in {f, b}:
+ *   fwd:  hdec_s[i] = exp(-lambda dt_s[i]) H_s[rows_s[i]]   (0 where rows_s[i] < 0);
+ *         out[i] = act(x[x_rows ? x_rows[i] : i] + hdec_f[i] . W_f + hdec_b[i] . W_b)   (a negative x_rows[i] reads a zero row);
+ *   bwd:  d_pre[i] = up[i] . [out[i] > 0] (act = 1) or up[i];   d_hrows_s[i] = exp(-lambda dt_s[i]) (d_pre[i] . W_s^T)   (0 where rows_s[i] < 0).
+ * temp_lin_rows' launch shape: a workgroup of 256 threads owns 32 rows and runs the three phases once.  The forward gathers and decays
+ * both sources into LDS and accumulates both products into one accumulator set (a K = 2 d walk over [hdec_f | hdec_b] against the two
+ * packed weights); the backward reads the one d_pre tile against W_f^T and against W_b^T.  fp32 throughout, the decay in front of the
+ * product; no atomics, one summation order: bit-repeatable.  All n rows of out, hdec_f, hdec_b, d_pre, d_hrows_f and d_hrows_b are
+ * written.  pack_fwd_s / pack_bwd_s: the first / second half of W_s's temp_lin_chain_pack_multi buffer.  The caller finishes the
+ * backward: d_H_s and d_x are the segment sums of d_hrows_s / d_pre through the inverses of rows_s / x_rows, d_W_s = hdec_s^T . d_pre
+ * (temp_linear_tn).  Device pointers only: capturable.  A direction without any state passes rows_s all -1 (H_s is then never read,
+ * but must not be NULL).
+ * Return contract, in this order; nothing is launched on an error: n < 0, d <= 0 or act outside {0, 1}: BADARG;  a width
+ * temp_lin_rows2_supported refuses (temp_lin_chain_supported's rule: d % 4 == 0, d <= 256; 100 352 bytes of LDS at d = 256):
+ * UNSUPPORTED;  n == 0: TEMP_OK without a launch;  then a NULL x / H_s / rows_s / dt_s / pack / out / hdec_s (fwd), up / rows_s / dt_s /
+ * pack / d_pre / d_hrows_s or, with act = 1, out (bwd): BADARG. */
+int temp_lin_rows2_supported(int d);
+int temp_lin_rows2_fwd(int n, int d, const float* x, const int32_t* x_rows /* nullable [n] */, const float* H_f, const int32_t* rows_f /* [n] */,
+                       const float* dt_f /* [n] */, const float* H_b, const int32_t* rows_b /* [n] */, const float* dt_b /* [n] */, float lambda,
+                       const float* pack_fwd_f, const float* pack_fwd_b, int act, float* out /* [n][d] */, float* hdec_f /* [n][d] */,
+                       float* hdec_b /* [n][d] */, void* stream);
+int temp_lin_rows2_bwd(int n, int d, const float* out, const float* up, const int32_t* rows_f, const float* dt_f, const int32_t* rows_b,
+                       const float* dt_b, float lambda, const float* pack_bwd_f, const float* pack_bwd_b, int act, float* d_pre /* [n][d] */,
+                       float* d_hrows_f /* [n][d] */, float* d_hrows_b /* [n][d] */, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
  * Row gather / scatter helpers of the window loop

@@ -221,6 +221,9 @@ SYMBOLS = {
     "temp_lin_rows_supported": (_I, [_I]),
     "temp_lin_rows_fwd": (_I, [_I, _I, c_vp, c_vp, c_vp, c_vp, c_vp, ctypes.c_float, c_vp, _I, c_vp, c_vp, c_vp]),
     "temp_lin_rows_bwd": (_I, [_I, _I, c_vp, c_vp, c_vp, c_vp, ctypes.c_float, c_vp, _I, c_vp, c_vp, c_vp]),
+    "temp_lin_rows2_supported": (_I, [_I]),
+    "temp_lin_rows2_fwd": (_I, [_I, _I] + [c_vp] * 8 + [ctypes.c_float, c_vp, c_vp, _I, c_vp, c_vp, c_vp, c_vp]),
+    "temp_lin_rows2_bwd": (_I, [_I, _I] + [c_vp] * 6 + [ctypes.c_float, c_vp, c_vp, _I, c_vp, c_vp, c_vp, c_vp]),
     "temp_gru_grads_g4_keys": (_I, [_I, c_vp, _I, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, ctypes.c_size_t, c_vp]),
     "temp_gru_grads_g4_rows_supported": (_I, [_I, c_vp, _I, _I]),
     "temp_gru_grads_g4_rows": (_I, [_I, c_vp, _I, c_vp, _I, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, ctypes.c_size_t, c_vp]),

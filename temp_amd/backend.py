@@ -702,6 +702,37 @@ class HipBackend:
         _lib.check(self.lib.temp_lin_rows_bwd(n, d, _ptr(out), _ptr(up), _ptr(h_rows), _ptr(dt), float(lam), _ptr(self._lin_rows_pack(pack, d, True)),
                                               int(act), _ptr(d_pre), _ptr(d_hrows), _stream()), "temp_lin_rows_bwd")
 
+    # ---- one position of the bidirectional linear recurrence on gathered rows (include/temp_amd.h: temp_lin_rows2_fwd / _bwd) ------
+    def lin_rows2_supported(self, d):
+        return bool(self.lib.temp_lin_rows2_supported(int(d)))
+
+    def lin_rows2_fwd(self, x, x_rows, Hf, rows_f, dt_f, Hb, rows_b, dt_b, lam, pack_f, pack_b, act, out, hdec_f, hdec_b):
+        """out = act(x[x_rows] + hdec_f . W_f + hdec_b . W_b), hdec_s = exp(-lam dt_s) H_s[rows_s] (0 where rows_s < 0), one launch; out,
+        hdec_f and hdec_b (n, d) are written whole.  x_rows: int32 [n] or None (row i reads x[i]); pack_s: lin_chain_pack_multi([W_s])[0]."""
+        x, Hf, Hb, dt_f, dt_b = (_f32(t, k) for t, k in ((x, "x"), (Hf, "Hf"), (Hb, "Hb"), (dt_f, "dt_f"), (dt_b, "dt_b")))
+        x_rows, rows_f, rows_b = _i32(x_rows, "x_rows"), _i32(rows_f, "rows_f"), _i32(rows_b, "rows_b")
+        n, d = rows_f.shape[0], x.shape[1]
+        assert Hf.shape[1] == d and Hb.shape[1] == d and rows_b.shape[0] == n and dt_f.numel() == n and dt_b.numel() == n
+        assert (x_rows.shape[0] if x_rows is not None else x.shape[0]) == n
+        for t in (out, hdec_f, hdec_b):
+            assert tuple(t.shape) == (n, d) and t.is_contiguous() and t.dtype == torch.float32
+        _lib.check(self.lib.temp_lin_rows2_fwd(n, d, _ptr(x), _ptr(x_rows), _ptr(Hf), _ptr(rows_f), _ptr(dt_f), _ptr(Hb), _ptr(rows_b), _ptr(dt_b),
+                                               float(lam), _ptr(self._lin_rows_pack(pack_f, d, False)), _ptr(self._lin_rows_pack(pack_b, d, False)),
+                                               int(act), _ptr(out), _ptr(hdec_f), _ptr(hdec_b), _stream()), "temp_lin_rows2_fwd")
+
+    def lin_rows2_bwd(self, out, up, rows_f, dt_f, rows_b, dt_b, lam, pack_f, pack_b, act, d_pre, d_hrows_f, d_hrows_b):
+        """The backward of lin_rows2_fwd in one launch: d_pre = up . [out > 0] (act = 1) or up, d_hrows_s = exp(-lam dt_s) (d_pre . W_s^T)
+        (0 where rows_s < 0); all three (n, d) are written whole."""
+        out, up, dt_f, dt_b = _f32(out, "out"), _f32(up, "up"), _f32(dt_f, "dt_f"), _f32(dt_b, "dt_b")
+        rows_f, rows_b = _i32(rows_f, "rows_f"), _i32(rows_b, "rows_b")
+        n, d = up.shape
+        assert out.shape == up.shape and rows_f.shape[0] == n and rows_b.shape[0] == n and dt_f.numel() == n and dt_b.numel() == n
+        for t in (d_pre, d_hrows_f, d_hrows_b):
+            assert tuple(t.shape) == (n, d) and t.is_contiguous() and t.dtype == torch.float32
+        _lib.check(self.lib.temp_lin_rows2_bwd(n, d, _ptr(out), _ptr(up), _ptr(rows_f), _ptr(dt_f), _ptr(rows_b), _ptr(dt_b), float(lam),
+                                               _ptr(self._lin_rows_pack(pack_f, d, True)), _ptr(self._lin_rows_pack(pack_b, d, True)), int(act),
+                                               _ptr(d_pre), _ptr(d_hrows_f), _ptr(d_hrows_b), _stream()), "temp_lin_rows2_bwd")
+
     def gru_grads_g4_supported(self, ns, d, variant):
         """True when gru_grads_g4 takes GRUs of these row counts and this width (then the chain backward should write g4)."""
         k = len(ns)

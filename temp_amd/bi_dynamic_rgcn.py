@@ -134,8 +134,35 @@ class BiDynamicRGCN(DynamicRGCN):
             pre_t = x_of[(tf.row0, tf.n_rows)]
         _, pf, dtf = tf.tensors(dev)
         _, pb, dtb = tb.tensors(dev)
-        out = l2.centre_rows(pre_t, Hf, pf, dtf, Hb, pb, dtb)
+        if self._bi_pair(wb):                                 # both gathers, products and decays, the sum and the ReLU as ONE node
+            inv = self._centre_inverses(wb, Hf, Hb)
+            out = TF.lin_step_rows2(pre_t, None, Hf, pf, dtf, Hb, pb, dtb, l2.inv_temperature, l2.time_weight_forward, l2.time_weight_backward,
+                                    1 if l2.relu_fused() else 0, None, inv[0], inv[1])
+        else:
+            out = l2.centre_rows(pre_t, Hf, pf, dtf, Hb, pb, dtb)
         return out, ((Hf, Hf), (Hb, Hb))
+
+    # --module BiRRGCN on the batched linear path: the all-entity pass of all windows at once over the UNION of (window, entity) pairs
+    # with a previous state in either direction (_union_maps), the fused loss node and the batched evaluation path that go with it, and
+    # the centre position as one lin_step_rows2 node.  Off by default: the per-window call lists of the existing suites pin that route
+    bi_pair_pass = False
+
+    def _bi_pair(self, wb):
+        return bool(getattr(self, "bi_pair_pass", False) and wb.batched and self._linear_layer())
+
+    @staticmethod
+    def _rows_inverse(cache, key, idx_host, H):
+        """gather_inverse of a static history-row list over the rows of H, built on first use and kept with the prepared batch."""
+        if H is None:
+            return None
+        k = (key, int(H.shape[0]))
+        if k not in cache:
+            cache[k] = TF.gather_inverse(idx_host, H.shape[0], H.device)
+        return cache[k]
+
+    def _centre_inverses(self, wb, Hf, Hb):
+        cache = wb.__dict__.setdefault("_centre_inv", {})
+        return (self._rows_inverse(cache, "f", wb.target.prev_idx, Hf), self._rows_inverse(cache, "b", wb.target_b.prev_idx, Hb))
 
     def _run_batched(self, wb):
         if self._linear_layer():
@@ -334,8 +361,9 @@ class BiDynamicRGCN(DynamicRGCN):
     def _fused_all_entity_ok(self, wb):
         if wb.batched:
             # --module BiRRGCN: the ReLU follows the sum of the two directions' terms, so the pair sets of the directions interact and a
-            # batched pass needs a union map in _all_maps: its all-entity pass stays per window, its loss per graph
-            return not self._linear_layer() and super()._fused_all_entity_ok(wb)
+            # batched pass needs the union map (_union_maps): with bi_pair_pass the parent's rule, without it the
+            # all-entity pass stays per window and the loss per graph
+            return (self._bi_pair(wb) or not self._linear_layer()) and super()._fused_all_entity_ok(wb)
         enc = self.ent_encoder
         # (this variant keeps ONE isolated pass per entity: not while the self-loop dropout draws -- every window then needs its own mask)
         return (self.use_batched_path and not enc.use_time_embedding and not getattr(self.args, "use_embed_for_non_active", False)
@@ -348,7 +376,7 @@ class BiDynamicRGCN(DynamicRGCN):
         -- a previous state in either direction -- each with its two history rows (-1 = zero state in that direction); every
         other inactive entity takes its row of the once-per-entity table."""
         if wb.batched:
-            return super()._all_maps(wb)
+            return self._union_maps(wb) if self._bi_pair(wb) else super()._all_maps(wb)
         if getattr(wb, "all_maps", None) is None:
             dev = self._device()
             N, B = self.num_ents, len(wb.graphs)
@@ -382,7 +410,81 @@ class BiDynamicRGCN(DynamicRGCN):
                                 asm_inv=TF.gather_inverse(asm.reshape(-1), n_out + n_prev + N if wb.n_inactive else n_out, dev))]
         return wb.all_maps
 
+    def _union_maps(self, wb):
+        """bi_pair_pass: ONE map over the union pairs -- inactive (window, entity) pairs with a previous state in EITHER direction,
+        window-major, each with its two history rows (-1: no state in that direction) and time gaps; every other inactive entity
+        takes its row of the table (one row per entity; per (window, entity) while the self-loop dropout draws, as in
+        DynamicRGCN._all_maps: `ent` then indexes those rows).  asm assembles [encoder output ; pair rows ; table]."""
+        rep = self._all_rep()
+        if getattr(wb, "all_maps", None) is None or getattr(wb, "all_rep", False) != rep:
+            dev = self._device()
+            N, B = self.num_ents, len(wb.graphs)
+            plan_f, plan_b = wb.plan
+            L = plan_f.seq_len
+            T = B * N if rep else N
+            tab = (np.arange(B * N, dtype=np.int64).reshape(B, N) if rep else np.broadcast_to(np.arange(N, dtype=np.int64)[None, :], (B, N)))
+            wb.all_rep = rep
+            if rep:
+                ids = np.tile(np.arange(N, dtype=np.int32), B)
+                wb.all_rep_ids = _lib.to_device(ids, dev)
+                wb.all_rep_inv = TF.gather_inverse(ids, N, dev)
+            act = np.zeros((B, N), dtype=bool)
+            sizes = [g.n for g in wb.graphs]
+            n_out = int(sum(sizes))
+            off_out = np.concatenate([[0], np.cumsum(sizes)])
+            for b, g in enumerate(wb.graphs):
+                act[b, g.gids] = True
+            wb.n_inactive = int(B * N - act.sum())
+            wb.all_time = None
+            _lib.pause_point()
+            fin_f = [plan_f.final_all(b, L - 1) for b in range(B)]
+            fin_b = [plan_b.final_all(b, L - 1) for b in range(B)]
+            rf, gf = np.stack([f[0] for f in fin_f]), np.stack([f[1] for f in fin_f])
+            rb, gb = np.stack([f[0] for f in fin_b]), np.stack([f[1] for f in fin_b])
+            has = ~act & ((rf >= 0) | (rb >= 0))
+            bb, ee = np.nonzero(has)                                       # window-major
+            n_prev = int(bb.shape[0])
+            asm = (n_out + n_prev + tab).copy()
+            asm[has] = n_out + np.arange(n_prev)
+            for b, g in enumerate(wb.graphs):
+                asm[b, g.gids] = off_out[b] + np.arange(g.n)
+            ent = bb * N + ee if rep else ee                               # the pair's row of the table
+            host = dict(ent=ent, idx_f=rf[bb, ee], idx_b=rb[bb, ee], asm=asm.reshape(-1),
+                        dt_f=gf[bb, ee].astype(np.float32).view(np.int32), dt_b=gb[bb, ee].astype(np.float32).view(np.int32))
+            _lib.pause_point()
+            d = S.upload_packed(host, dev, np.int32)
+            f32 = lambda t: t.view(torch.float32).view(-1, 1)
+            wb.all_maps = [dict(n_prev=n_prev, ent=d["ent"], idx_f=d["idx_f"], idx_b=d["idx_b"], dt_f=f32(d["dt_f"]), dt_b=f32(d["dt_b"]),
+                                idx_f_host=host["idx_f"], idx_b_host=host["idx_b"], asm=d["asm"],
+                                ent_inv=TF.gather_inverse(ent, T, dev) if n_prev else None,
+                                asm_inv=TF.gather_inverse(asm.reshape(-1), n_out + n_prev + T if wb.n_inactive else n_out, dev))]
+        return wb.all_maps
+
+    def _all_embeds_batched_union(self, wb, out, hist):
+        """BiRRGCNLayer.forward_isolated for all windows at once: x = pre_isolated2(conv_isolated1(E)) once per entity (per (window,
+        entity) while the dropout draws); an inactive entity without a previous state in either direction gets act(x[e]), a union pair
+        act(x[e] + both directions' recurrent terms) through ONE lin_step_rows2 node; the active rows come from `out`."""
+        l1, l2 = self.ent_encoder.layer_1, self.ent_encoder.layer_2
+        (m,) = self._all_maps(wb)
+        B, N = len(wb.graphs), self.num_ents
+        if wb.n_inactive == 0:
+            return TF.gather_rows(out, m["asm"], m["asm_inv"]).view(B, N, out.shape[1])
+        (Hf, _), (Hb, _) = hist
+        E = TF.gather_rows(self.ent_embeds, wb.all_rep_ids, wb.all_rep_inv) if wb.all_rep else self.ent_embeds
+        x = l2.pre_isolated(l1.conv_isolated(E))
+        parts = [out]
+        if m["n_prev"]:
+            cache = m.setdefault("_gather_inv", {})
+            parts.append(TF.lin_step_rows2(x, m["ent"], Hf, m["idx_f"], m["dt_f"], Hb, m["idx_b"], m["dt_b"], l2.inv_temperature,
+                                           l2.time_weight_forward, l2.time_weight_backward, 1 if l2.relu_fused() else 0, m["ent_inv"],
+                                           self._rows_inverse(cache, "f", m["idx_f_host"], Hf), self._rows_inverse(cache, "b", m["idx_b_host"], Hb)))
+        parts.append(l2._finish(x))
+        big = TF.gather_rows(torch.cat(parts, dim=0), m["asm"], m["asm_inv"])
+        return big.view(B, N, big.shape[1])
+
     def all_embeds_batched(self, wb, out, hist):
+        if wb.batched and self._bi_pair(wb):
+            return self._all_embeds_batched_union(wb, out, hist)
         if wb.batched:
             return super().all_embeds_batched(wb, out, hist)
         # both layers recurrent (models/BiRRGCN.py:242-257): zero-state rows once per entity through both layers' GRU pairs,

@@ -100,6 +100,10 @@ class BiRRGCNLayer(RGCNLayer):
         """Aggregation + self-loop on graph `g`, no bias, no activation: what the recurrent terms are added to."""
         return self._core(g, h)
 
+    def pre_isolated(self, e):
+        """The self-loop of forward_isolated on rows `e`, no bias, no activation: what the recurrent terms are added to."""
+        return TF.rgcn_isolated(e, self.loop_weight, None, None, self._drop())
+
     def _rec(self, prev, prev_idx, dt, weight):
         """decay(prev[prev_idx] . W) of one direction (forward_one_direction's order: the decay behind the product)."""
         return TF.decay_rows(TF.linear_nt(TF.gather_rows(prev, prev_idx), weight), dt, self.inv_temperature)

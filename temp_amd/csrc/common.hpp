@@ -153,6 +153,7 @@ enum KernelId {
   K_FILTERED_CE_FWD, K_FILTERED_CE_BWD, K_FILTERED_RANK_STREAM, K_FILTERED_RANK_STREAM_MIX,
   K_DOT_CE_FWD, K_DOT_CE_BWD_Q, K_DOT_CE_BWD_TABLE, K_DOT_MIX_CE_FWD, K_DOT_MIX_CE_BWD_Q, K_DOT_MIX_CE_BWD_TABLE,   // (l1_loss.hip adds the role to *_FWD)
   K_LIN_CHAIN_FWD, K_LIN_CHAIN_BWD, K_LIN_CHAIN_PACK, K_LIN_ROWS_FWD, K_LIN_ROWS_BWD,
+  K_LIN_ROWS2_FWD, K_LIN_ROWS2_BWD,
   K_COUNT
 };
 int trace_open(int kernel_id, hipStream_t st);       // -> slot or -1

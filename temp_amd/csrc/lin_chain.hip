@@ -18,7 +18,8 @@
 // workgroups share a CU (60 KB of LDS at d = 200), which is what hides the L2 latency of the weight stream in this plain version.
 //
 // k_lin_rows_fwd / _bwd (temp_lin_rows_*) are ONE such step on gathered rows, without the tables: the (window, entity) pair rows of the
-// batched all-entity pass.
+// batched all-entity pass.  k_lin_rows2_fwd / _bwd (temp_lin_rows2_*) are that step with both directions' recurrent terms in front of
+// one activation: BiRRGCNLayer's centre position and its union pair rows.
 #include <atomic>
 #include "common.hpp"
 
@@ -81,30 +82,35 @@ __global__ void __launch_bounds__(256) k_lin_chain_pack(int D, LinPackJobs jobs)
   }
 }
 
-// out[track][tile*32 ..] = sum_k piece(tile, k) . kb[track][k] for the wave's tiles (wave, wave + 4): two independent accumulators
-__device__ __forceinline__ void lin_product(const float4* __restrict__ w, const float* kb, float* ob, const LinGeom& g, int wave, int lane) {
+// out[track][tile*32 ..] = sum_s sum_k piece_s(tile, k) . kb_s[track][k] for the wave's tiles (wave, wave + 4): two independent
+// accumulators; the NS sources (weight, B operand) are walked one behind the other into the same accumulators (a K = NS d product)
+template <int NS>
+__device__ __forceinline__ void lin_product_n(const float4* const (&w)[NS], const float* const (&kb)[NS], float* ob, const LinGeom& g, int wave, int lane) {
   const int li = lane & 31, hh = lane >> 5;
-  const float* krow = kb + li * g.ldk + 4 * hh;
   for (int t0 = wave; t0 < g.NT; t0 += 8) {
     const int t1 = t0 + 4;
     const bool two = t1 < g.NT;
-    const float4* w0 = w + (size_t)t0 * g.NQ * 64 + lane;
-    const float4* w1 = w + (size_t)(two ? t1 : t0) * g.NQ * 64 + lane;
     f32x16 a0, a1;
 #pragma unroll
     for (int r = 0; r < 16; ++r) { a0[r] = 0.f; a1[r] = 0.f; }
+#pragma unroll
+    for (int s = 0; s < NS; ++s) {
+      const float* krow = kb[s] + li * g.ldk + 4 * hh;
+      const float4* w0 = w[s] + (size_t)t0 * g.NQ * 64 + lane;
+      const float4* w1 = w[s] + (size_t)(two ? t1 : t0) * g.NQ * 64 + lane;
 #pragma unroll 2
-    for (int q = 0; q < g.NQ; ++q) {
-      const float4 x0 = w0[(size_t)q * 64], x1 = w1[(size_t)q * 64];
-      const float4 h4 = ld4(krow + 8 * q);
-      a0 = __builtin_amdgcn_mfma_f32_32x32x2f32(x0.x, h4.x, a0, 0, 0, 0);
-      a1 = __builtin_amdgcn_mfma_f32_32x32x2f32(x1.x, h4.x, a1, 0, 0, 0);
-      a0 = __builtin_amdgcn_mfma_f32_32x32x2f32(x0.y, h4.y, a0, 0, 0, 0);
-      a1 = __builtin_amdgcn_mfma_f32_32x32x2f32(x1.y, h4.y, a1, 0, 0, 0);
-      a0 = __builtin_amdgcn_mfma_f32_32x32x2f32(x0.z, h4.z, a0, 0, 0, 0);
-      a1 = __builtin_amdgcn_mfma_f32_32x32x2f32(x1.z, h4.z, a1, 0, 0, 0);
-      a0 = __builtin_amdgcn_mfma_f32_32x32x2f32(x0.w, h4.w, a0, 0, 0, 0);
-      a1 = __builtin_amdgcn_mfma_f32_32x32x2f32(x1.w, h4.w, a1, 0, 0, 0);
+      for (int q = 0; q < g.NQ; ++q) {
+        const float4 x0 = w0[(size_t)q * 64], x1 = w1[(size_t)q * 64];
+        const float4 h4 = ld4(krow + 8 * q);
+        a0 = __builtin_amdgcn_mfma_f32_32x32x2f32(x0.x, h4.x, a0, 0, 0, 0);
+        a1 = __builtin_amdgcn_mfma_f32_32x32x2f32(x1.x, h4.x, a1, 0, 0, 0);
+        a0 = __builtin_amdgcn_mfma_f32_32x32x2f32(x0.y, h4.y, a0, 0, 0, 0);
+        a1 = __builtin_amdgcn_mfma_f32_32x32x2f32(x1.y, h4.y, a1, 0, 0, 0);
+        a0 = __builtin_amdgcn_mfma_f32_32x32x2f32(x0.z, h4.z, a0, 0, 0, 0);
+        a1 = __builtin_amdgcn_mfma_f32_32x32x2f32(x1.z, h4.z, a1, 0, 0, 0);
+        a0 = __builtin_amdgcn_mfma_f32_32x32x2f32(x0.w, h4.w, a0, 0, 0, 0);
+        a1 = __builtin_amdgcn_mfma_f32_32x32x2f32(x1.w, h4.w, a1, 0, 0, 0);
+      }
     }
     // lane (li, hh) owns track li and, per register quad qq, columns tile*32 + 8qq + 4hh .. +3
     float* d0 = ob + li * g.ldo + t0 * 32 + 4 * hh;
@@ -116,6 +122,12 @@ __device__ __forceinline__ void lin_product(const float4* __restrict__ w, const 
       for (int qq = 0; qq < 4; ++qq) st4(d1 + 8 * qq, make_float4(a1[4 * qq], a1[4 * qq + 1], a1[4 * qq + 2], a1[4 * qq + 3]));
     }
   }
+}
+
+__device__ __forceinline__ void lin_product(const float4* __restrict__ w, const float* kb, float* ob, const LinGeom& g, int wave, int lane) {
+  const float4* const ws[1] = {w};
+  const float* const ks[1] = {kb};
+  lin_product_n<1>(ws, ks, ob, g, wave, lane);
 }
 
 __device__ __forceinline__ float4 relu4(float4 v) { return make_float4(fmaxf(v.x, 0.f), fmaxf(v.y, 0.f), fmaxf(v.z, 0.f), fmaxf(v.w, 0.f)); }
@@ -337,6 +349,134 @@ __global__ void __launch_bounds__(LC_THREADS) k_lin_rows_bwd(int n, int D, int a
   }
 }
 
+// ---- one position of the BIDIRECTIONAL recurrence on gathered rows (temp_lin_rows2_fwd / _bwd) ----------------------------
+// BiRRGCNLayer's centre / isolated form: the activation follows the SUM of both directions' recurrent terms, so the two sources of a
+// row go through one kernel.  The phases are k_lin_rows_*'s.  Forward: both decayed tiles lie in LDS side by side and the product
+// walks [hdec_f | hdec_b] against [W_f ; W_b] into one accumulator set (K = 2 d).  Backward: the one d_pre tile against W_f^T and
+// against W_b^T into two product tiles.  LDS: 32 (ldo + 2 ldk) words forward, 32 (2 ldo + ldk) backward, + 128: 100 352 bytes at
+// d = 256 (of the 160 KB a workgroup has), 81 920 / 84 992 at d = 200.
+struct LinRows2 {                                            // index 0: forward direction, 1: backward direction
+  const float* H[2]; const int32_t* rows[2]; const float* dt[2];
+  const float4* w[2];                                        // the forward (fwd kernel) / backward (bwd kernel) pieces of W_f, W_b
+};
+inline size_t lin_lds_rows2_fwd(int D) { LinGeom g = lin_geom(D); return ((size_t)LR_ROWS * (g.ldo + 2 * g.ldk) + 4 * LR_ROWS) * 4; }
+inline size_t lin_lds_rows2_bwd(int D) { LinGeom g = lin_geom(D); return ((size_t)LR_ROWS * (2 * g.ldo + g.ldk) + 4 * LR_ROWS) * 4; }
+
+// hrb[s][t] = the H row of row t in direction s (-1: none, or past n), decb[s][t] its decay factor: threads 0 .. 63
+__device__ __forceinline__ void lin_rows2_tables(const LinRows2& a, int n, long long row0, float lambda, int* hrb, float* decb, int tid) {
+  if (tid < 2 * LR_ROWS) {
+    const bool bw = tid >= LR_ROWS;
+    const long long row = row0 + (tid & (LR_ROWS - 1));
+    const int32_t* rows = bw ? a.rows[1] : a.rows[0];
+    const float* dt = bw ? a.dt[1] : a.dt[0];
+    const int hr = row < n ? rows[row] : -1;
+    hrb[tid] = hr;
+    decb[tid] = hr >= 0 ? expf(-dt[row] * lambda) : 0.f;
+  }
+}
+
+__global__ void __launch_bounds__(LC_THREADS) k_lin_rows2_fwd(int n, int D, int act, const float* __restrict__ x, const int32_t* __restrict__ x_rows,
+                                                              LinRows2 a, float lambda, float* __restrict__ out, float* __restrict__ HDf,
+                                                              float* __restrict__ HDb) {
+  extern __shared__ __attribute__((aligned(16))) float lds[];
+  const int D4 = D >> 2;
+  const LinGeom g = lin_geom(D);
+  float* sb = lds;                                          // [32][ldo] raw products
+  float* kb = sb + LR_ROWS * g.ldo;                         // [2][32][ldk] decayed rows of both directions (B operands)
+  int* hrb = (int*)(kb + 2 * LR_ROWS * g.ldk);              // [2][32]
+  float* decb = (float*)(hrb + 2 * LR_ROWS);                // [2][32]
+  const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
+  const int items = LR_ROWS * D4;
+  const long long row0 = (long long)blockIdx.x * LR_ROWS;
+
+  for (int i = tid; i < 2 * LR_ROWS * g.ldk; i += LC_THREADS) kb[i] = 0.f;        // the k padding must be 0, not stale LDS
+  lin_rows2_tables(a, n, row0, lambda, hrb, decb, tid);
+  __syncthreads();
+  // 1: hdec_s = dec_s . H_s[rows_s], 0 for a row without a previous state in that direction
+#pragma unroll
+  for (int s = 0; s < 2; ++s) {
+    const float* __restrict__ H = a.H[s];
+    float* __restrict__ HD = s ? HDb : HDf;
+    float* ks = kb + s * LR_ROWS * g.ldk;
+    for (int i = tid; i < items; i += LC_THREADS) {
+      const int t = i / D4, c = (i - t * D4) << 2;
+      const long long row = row0 + t;
+      const int hr = hrb[s * LR_ROWS + t];
+      float4 hd = zero4();
+      if (hr >= 0) hd = scale4(ld4(H + (size_t)hr * D + c), decb[s * LR_ROWS + t]);
+      if (row < n) st4(HD + (size_t)row * D + c, hd);
+      st4(ks + t * g.ldk + c, hd);
+    }
+  }
+  __syncthreads();
+  // 2: [hdec_f | hdec_b] . [W_f ; W_b]
+  {
+    const float4* const ws[2] = {a.w[0], a.w[1]};
+    const float* const ks[2] = {kb, kb + LR_ROWS * g.ldk};
+    lin_product_n<2>(ws, ks, sb, g, wave, lane);
+  }
+  __syncthreads();
+  // 3: out = act(x + product)
+  for (int i = tid; i < items; i += LC_THREADS) {
+    const int t = i / D4, c = (i - t * D4) << 2;
+    const long long row = row0 + t;
+    if (row >= n) continue;
+    const long long xr = x_rows ? (long long)x_rows[row] : row;
+    float4 v = ld4(sb + t * g.ldo + c);
+    if (xr >= 0) v = add4(v, ld4(x + (size_t)xr * D + c));
+    if (act) v = relu4(v);
+    st4(out + (size_t)row * D + c, v);
+  }
+}
+
+__global__ void __launch_bounds__(LC_THREADS) k_lin_rows2_bwd(int n, int D, int act, const float* __restrict__ out, const float* __restrict__ up,
+                                                              LinRows2 a, float lambda, float* __restrict__ DP, float* __restrict__ DHf,
+                                                              float* __restrict__ DHb) {
+  extern __shared__ __attribute__((aligned(16))) float lds[];
+  const int D4 = D >> 2;
+  const LinGeom g = lin_geom(D);
+  float* pb = lds;                                          // [2][32][ldo] raw d_pre . W_f^T, d_pre . W_b^T
+  float* kb = pb + 2 * LR_ROWS * g.ldo;                     // [32][ldk] d_pre (B operand of both products)
+  int* hrb = (int*)(kb + LR_ROWS * g.ldk);
+  float* decb = (float*)(hrb + 2 * LR_ROWS);
+  const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
+  const int items = LR_ROWS * D4;
+  const long long row0 = (long long)blockIdx.x * LR_ROWS;
+
+  for (int i = tid; i < LR_ROWS * g.ldk; i += LC_THREADS) kb[i] = 0.f;
+  lin_rows2_tables(a, n, row0, lambda, hrb, decb, tid);
+  __syncthreads();
+  // 1: d_pre = upstream . [out > 0]
+  for (int i = tid; i < items; i += LC_THREADS) {
+    const int t = i / D4, c = (i - t * D4) << 2;
+    const long long row = row0 + t;
+    float4 gv = zero4();
+    if (row < n) {
+      gv = ld4(up + (size_t)row * D + c);
+      if (act) gv = relu_gate4(ld4(out + (size_t)row * D + c), gv);
+      st4(DP + (size_t)row * D + c, gv);
+    }
+    st4(kb + t * g.ldk + c, gv);
+  }
+  __syncthreads();
+  // 2: d_pre . W_f^T and d_pre . W_b^T (one B operand, two product tiles: no barrier between them)
+  lin_product(a.w[0], kb, pb, g, wave, lane);
+  lin_product(a.w[1], kb, pb + LR_ROWS * g.ldo, g, wave, lane);
+  __syncthreads();
+  // 3: d_hrows_s = dec_s . product_s, 0 for a row without a previous state in that direction (a select)
+#pragma unroll
+  for (int s = 0; s < 2; ++s) {
+    float* __restrict__ DH = s ? DHb : DHf;
+    const float* ps = pb + s * LR_ROWS * g.ldo;
+    for (int i = tid; i < items; i += LC_THREADS) {
+      const int t = i / D4, c = (i - t * D4) << 2;
+      const long long row = row0 + t;
+      if (row >= n) continue;
+      st4(DH + (size_t)row * D + c, hrb[s * LR_ROWS + t] >= 0 ? scale4(ld4(ps + t * g.ldo + c), decb[s * LR_ROWS + t]) : zero4());
+    }
+  }
+}
+
 template <class K>
 static int lin_lds_attr(K kernel, bool* done) {
   if (*done) return TEMP_OK;
@@ -460,6 +600,40 @@ int temp_lin_rows_bwd(int n, int d, const float* out, const float* up, const int
   if (lin_lds_attr(k_lin_rows_bwd, &attr)) return TEMP_E_LAUNCH;
   TEMP_LAUNCH(K_LIN_ROWS_BWD, k_lin_rows_bwd, dim3(ceil_div(n, LR_ROWS)), dim3(LC_THREADS), lin_lds_rows(d), (hipStream_t)stream, n, d, act, out, up,
               h_rows, dt, lambda, (const float4*)pack_bwd, d_pre, d_hrows);
+  return launch_status();
+}
+
+int temp_lin_rows2_supported(int d) {
+  return temp_lin_chain_supported(d, 0) && lin_lds_rows2_fwd(d) <= LC_LDS_LIMIT && lin_lds_rows2_bwd(d) <= LC_LDS_LIMIT;
+}
+
+int temp_lin_rows2_fwd(int n, int d, const float* x, const int32_t* x_rows, const float* H_f, const int32_t* rows_f, const float* dt_f,
+                       const float* H_b, const int32_t* rows_b, const float* dt_b, float lambda, const float* pack_fwd_f, const float* pack_fwd_b,
+                       int act, float* out, float* hdec_f, float* hdec_b, void* stream) {
+  if (n < 0 || d <= 0 || (act != 0 && act != 1)) return TEMP_E_BADARG;
+  if (!temp_lin_rows2_supported(d)) return TEMP_E_UNSUPPORTED;
+  if (n == 0) return TEMP_OK;
+  if (!x || !H_f || !rows_f || !dt_f || !H_b || !rows_b || !dt_b || !pack_fwd_f || !pack_fwd_b || !out || !hdec_f || !hdec_b) return TEMP_E_BADARG;
+  static bool attr = false;
+  if (lin_lds_attr(k_lin_rows2_fwd, &attr)) return TEMP_E_LAUNCH;
+  const LinRows2 a = {{H_f, H_b}, {rows_f, rows_b}, {dt_f, dt_b}, {(const float4*)pack_fwd_f, (const float4*)pack_fwd_b}};
+  TEMP_LAUNCH(K_LIN_ROWS2_FWD, k_lin_rows2_fwd, dim3(ceil_div(n, LR_ROWS)), dim3(LC_THREADS), lin_lds_rows2_fwd(d), (hipStream_t)stream, n, d, act, x,
+              x_rows, a, lambda, out, hdec_f, hdec_b);
+  return launch_status();
+}
+
+int temp_lin_rows2_bwd(int n, int d, const float* out, const float* up, const int32_t* rows_f, const float* dt_f, const int32_t* rows_b,
+                       const float* dt_b, float lambda, const float* pack_bwd_f, const float* pack_bwd_b, int act, float* d_pre, float* d_hrows_f,
+                       float* d_hrows_b, void* stream) {
+  if (n < 0 || d <= 0 || (act != 0 && act != 1)) return TEMP_E_BADARG;
+  if (!temp_lin_rows2_supported(d)) return TEMP_E_UNSUPPORTED;
+  if (n == 0) return TEMP_OK;
+  if ((act && !out) || !up || !rows_f || !dt_f || !rows_b || !dt_b || !pack_bwd_f || !pack_bwd_b || !d_pre || !d_hrows_f || !d_hrows_b) return TEMP_E_BADARG;
+  static bool attr = false;
+  if (lin_lds_attr(k_lin_rows2_bwd, &attr)) return TEMP_E_LAUNCH;
+  const LinRows2 a = {{nullptr, nullptr}, {rows_f, rows_b}, {dt_f, dt_b}, {(const float4*)pack_bwd_f, (const float4*)pack_bwd_b}};
+  TEMP_LAUNCH(K_LIN_ROWS2_BWD, k_lin_rows2_bwd, dim3(ceil_div(n, LR_ROWS)), dim3(LC_THREADS), lin_lds_rows2_bwd(d), (hipStream_t)stream, n, d, act, out,
+              up, a, lambda, d_pre, d_hrows_f, d_hrows_b);
   return launch_status();
 }
 

@@ -139,7 +139,8 @@ const char* temp_trace_kernel_name(int id) {
                                 "k_pair_rows_fwd", "k_pair_rows_bwd", "k_frozen_mix_ce", "k_filtered_ce_fwd", "k_filtered_ce_bwd",
                                 "k_filtered_rank_stream", "k_filtered_rank_stream_mix", "k_dot_ce_fwd", "k_dot_ce_bwd_q",
                                 "k_dot_ce_bwd_table", "k_dot_mix_ce_fwd", "k_dot_mix_ce_bwd_q", "k_dot_mix_ce_bwd_table",
-                                "k_lin_chain_fwd", "k_lin_chain_bwd", "k_lin_chain_pack", "k_lin_rows_fwd", "k_lin_rows_bwd"};
+                                "k_lin_chain_fwd", "k_lin_chain_bwd", "k_lin_chain_pack", "k_lin_rows_fwd", "k_lin_rows_bwd",
+                                "k_lin_rows2_fwd", "k_lin_rows2_bwd"};
   static_assert(sizeof(names) / sizeof(names[0]) == K_COUNT, "one name per KernelId");
   return (id >= 0 && id < K_COUNT) ? names[id] : "?";
 }

@@ -7,6 +7,7 @@ Each Function is one reference op with its hand-written backward:
   gather_rows     ent_embeds[id] / history gather   models/DynamicRGCN.py:41-43,93
   linear          nn.Linear without bias (q/k/v projections)   models/SARGCN.py:16-18,32-34
   lin_step_rows   the recurrent term of RRGCNLayer.forward_isolated on gathered rows   models/RRGCN.py:152-167
+  lin_step_rows2  both recurrent terms of BiRRGCNLayer.forward / forward_isolated on gathered rows   models/BiRRGCN.py:102-185
   history_attention   SARGCNLayer.attention over the active history rows   models/SARGCN.py:25-53
   split_history_attention  the same for current rows that are a sum of two table rows (post-aggregation attention models)
 """
@@ -423,6 +424,86 @@ def lin_step_rows(x, x_rows, H, h_rows, dt, lam, W, act, x_inv=None, h_inv=None)
     if h_rows.shape[0] == 0 or not lin_rows_usable(x.shape[1]):
         return lin_step_rows_torch(x, x_rows, H, h_rows, dt, float(lam), W, act, x_inv, h_inv)
     return _LinStepRowsFn.apply(x, H, W, x_rows, h_rows, dt, float(lam), act, x_inv, h_inv)
+
+
+def lin_rows2_usable(d):
+    """True when lin_step_rows2 runs rows of this width through temp_lin_rows2_fwd / _bwd."""
+    be = get_backend()
+    return bool(LIN_ROWS_KERNEL and hasattr(be, "lin_rows2_fwd") and be.lin_rows2_supported(d))
+
+
+class _LinStepRows2Fn(torch.autograd.Function):
+    """The kernel route of lin_step_rows2: saves out (the ReLU mask is the kernel's own out > 0) and both hdec (the left factors of
+    d_W_f / d_W_b).  has = (bool, bool): a direction without history came in as a one-row zero H with rows all -1 and hands no
+    gradient to its H or W."""
+
+    @staticmethod
+    def forward(ctx, x, Hf, Hb, Wf, Wb, x_rows, rows_f, dt_f, rows_b, dt_b, lam, act, x_inv, f_inv, b_inv, has):
+        be = get_backend()
+        x, Hf, Hb = x.detach().contiguous(), Hf.detach().contiguous(), Hb.detach().contiguous()
+        dt_f, dt_b = dt_f.detach().contiguous().view(-1), dt_b.detach().contiguous().view(-1)
+        n, d = rows_f.shape[0], x.shape[1]
+        pack_f, pack_b = be.lin_chain_pack_multi([Wf.detach().contiguous(), Wb.detach().contiguous()])
+        out, hdec_f, hdec_b = (torch.empty(n, d, dtype=torch.float32, device=x.device) for _ in range(3))
+        be.lin_rows2_fwd(x, x_rows, Hf, rows_f, dt_f, Hb, rows_b, dt_b, lam, pack_f, pack_b, act, out, hdec_f, hdec_b)
+        ctx.save_for_backward(out, hdec_f, hdec_b, pack_f, pack_b, dt_f, dt_b)
+        ctx.x_rows, ctx.rows, ctx.invs, ctx.lam, ctx.act, ctx.has = x_rows, (rows_f, rows_b), (x_inv, f_inv, b_inv), lam, act, has
+        ctx.n_x, ctx.n_h = x.shape[0], (Hf.shape[0], Hb.shape[0])
+        return out
+
+    @staticmethod
+    def backward(ctx, d_out):
+        be = get_backend()
+        out, hdec_f, hdec_b, pack_f, pack_b, dt_f, dt_b = ctx.saved_tensors
+        (rows_f, rows_b), (x_inv, f_inv, b_inv) = ctx.rows, ctx.invs
+        d_pre, d_hf, d_hb = torch.empty_like(out), torch.empty_like(out), torch.empty_like(out)
+        be.lin_rows2_bwd(out, d_out.contiguous(), rows_f, dt_f, rows_b, dt_b, ctx.lam, pack_f, pack_b, ctx.act, d_pre, d_hf, d_hb)
+        need = ctx.needs_input_grad
+        d_x = d_Hf = d_Hb = d_Wf = d_Wb = None
+        if need[0]:
+            d_x = d_pre if ctx.x_rows is None else _gather_adjoint(be, d_pre, ctx.x_rows, x_inv, ctx.n_x)
+        if need[1] and ctx.has[0]:
+            d_Hf = _gather_adjoint(be, d_hf, rows_f, f_inv, ctx.n_h[0])
+        if need[2] and ctx.has[1]:
+            d_Hb = _gather_adjoint(be, d_hb, rows_b, b_inv, ctx.n_h[1])
+        if need[3] and ctx.has[0]:
+            d_Wf = be.linear_tn(hdec_f, d_pre)
+        if need[4] and ctx.has[1]:
+            d_Wb = be.linear_tn(hdec_b, d_pre)
+        return (d_x, d_Hf, d_Hb, d_Wf, d_Wb) + (None,) * 11
+
+
+def lin_step_rows2_torch(x, x_rows, Hf, rows_f, dt_f, Hb, rows_b, dt_b, lam, Wf, Wb, act, x_inv=None, f_inv=None, b_inv=None):
+    """lin_step_rows2 as the composition of the row operators, each its own autograd node, in BiRRGCNLayer.forward's order: the decay in
+    front of the product, the forward term added first.  A direction whose H is None adds nothing."""
+    out = gather_rows(x, x_rows, x_inv) if x_rows is not None else x
+    for H, rows, dt, W, inv in ((Hf, rows_f, dt_f, Wf, f_inv), (Hb, rows_b, dt_b, Wb, b_inv)):
+        if H is not None:
+            out = out + linear_nt(decay_rows(gather_rows(H, rows, inv), dt, lam), W)
+    return torch.relu(out) if act else out
+
+
+def lin_step_rows2(x, x_rows, Hf, rows_f, dt_f, Hb, rows_b, dt_b, lam, Wf, Wb, act, x_inv=None, f_inv=None, b_inv=None):
+    """One position of the bidirectional linear recurrence on gathered rows, ONE autograd node (temp_lin_rows2_fwd / _bwd):
+        out[i] = act(x[x_rows[i]] + (exp(-lam dt_f[i]) Hf[rows_f[i]]) . Wf + (exp(-lam dt_b[i]) Hb[rows_b[i]]) . Wb)
+    (a direction's term 0 where its row index is negative): BiRRGCNLayer's centre position and the union pair rows of its all-entity
+    pass.  x, Hf, Hb (., d) float32; x_rows int32 [n] or None (row i reads x[i]); rows_s int32 [n]; dt_s float32 (n,) or (n, 1); W_s (in,
+    out); act 0 none, 1 ReLU.  x_inv / f_inv / b_inv = gather_inverse of the three static row lists: with them the gathers' adjoints
+    are deterministic segment sums.  H_s None (a direction without history: windows of length 1): as if every rows_s[i] were -1; rows_s
+    and dt_s are then not read.  A backend without the kernel (the CPU test backend), LIN_ROWS_KERNEL = False, a width it refuses
+    and n = 0 take lin_step_rows2_torch."""
+    act = int(bool(act))
+    n = x_rows.shape[0] if x_rows is not None else x.shape[0]
+    if n == 0 or not lin_rows2_usable(x.shape[1]):
+        return lin_step_rows2_torch(x, x_rows, Hf, rows_f, dt_f, Hb, rows_b, dt_b, float(lam), Wf, Wb, act, x_inv, f_inv, b_inv)
+    has = (Hf is not None, Hb is not None)
+    if not all(has):
+        none, zero_dt, zero_h = torch.full((n,), -1, dtype=torch.int32, device=x.device), x.new_zeros(n), x.new_zeros(1, x.shape[1])
+        if not has[0]:
+            Hf, rows_f, dt_f, f_inv = zero_h, none, zero_dt, None
+        if not has[1]:
+            Hb, rows_b, dt_b, b_inv = zero_h, none, zero_dt, None
+    return _LinStepRows2Fn.apply(x, Hf, Hb, Wf, Wb, x_rows, rows_f, dt_f, rows_b, dt_b, float(lam), act, x_inv, f_inv, b_inv, has)
 
 
 class _DiachronicRowsFn(torch.autograd.Function):
