@@ -752,7 +752,8 @@ int temp_lin_rows_bwd(int n, int d, const float* out, const float* up, const int
  *   fwd:  hdec_s[i] = exp(-lambda dt_s[i]) H_s[rows_s[i]]   (0 where rows_s[i] < 0);
  *         out[i] = act(x[x_rows ? x_rows[i] : i] + hdec_f[i] . W_f + hdec_b[i] . W_b)   (a negative x_rows[i] reads a zero row);
  *   bwd:  d_pre[i] = up[i] . [out[i] > 0] (act = 1) or up[i];   d_hrows_s[i] = exp(-lambda dt_s[i]) (d_pre[i] . W_s^T)   (0 where rows_s[i] < 0).
- * temp_lin_rows' launch shape: a workgroup of 256 threads owns 32 rows and runs the three phases once.  The forward gathers and decays
+ * temp_lin_rows' implementation with two history sources instead of one (one kernel template per direction of the step, instantiated
+ * for both pairs of calls): a workgroup of 256 threads owns 32 rows and runs the three phases once.  The forward gathers and decays
  * both sources into LDS and accumulates both products into one accumulator set (a K = 2 d walk over [hdec_f | hdec_b] against the two
  * packed weights); the backward reads the one d_pre tile against W_f^T and against W_b^T.  fp32 throughout, the decay in front of the
  * product; no atomics, one summation order: bit-repeatable.  All n rows of out, hdec_f, hdec_b, d_pre, d_hrows_f and d_hrows_b are

@@ -669,9 +669,13 @@ class HipBackend:
         c, keep = self._lin_desc(tabs, d, lam, packs, act)
         _lib.check(self.lib.temp_lin_chain_bwd(ctypes.byref(c), _ptr(h), len(ups), arr, _ptr(d_pre), _stream()), "temp_lin_chain_bwd")
 
-    # ---- one position of the linear recurrence on gathered rows (include/temp_amd.h: temp_lin_rows_fwd / _bwd) ------
+    # ---- one position of the linear recurrence on gathered rows, one or two history sources in front of one activation
+    # (include/temp_amd.h: temp_lin_rows_fwd / _bwd, temp_lin_rows2_fwd / _bwd: one implementation, two C signatures) ------
     def lin_rows_supported(self, d):
         return bool(self.lib.temp_lin_rows_supported(int(d)))
+
+    def lin_rows2_supported(self, d):
+        return bool(self.lib.temp_lin_rows2_supported(int(d)))
 
     def _lin_rows_pack(self, pack, d, backward):
         """The forward / backward half of one matrix's lin_chain_pack_multi buffer."""
@@ -679,59 +683,52 @@ class HipBackend:
         assert pack.numel() == 2 * half
         return pack.view(-1)[half:] if backward else pack.view(-1)[:half]
 
+    def _lin_rows_call(self, which, n, d, head, srcs, lam, packs, backward, act, outs):
+        """temp_lin_rows<2>_<which>(n, d, head.., the sources' tensors source by source, lam, the packs' halves, act, outs..)."""
+        for s in srcs:
+            assert s[-2].shape[0] == n and s[-1].numel() == n                                      # (rows, dt)
+        for t in outs:
+            assert tuple(t.shape) == (n, d) and t.is_contiguous() and t.dtype == torch.float32
+        name = "temp_lin_rows%s_%s" % ("" if len(srcs) == 1 else len(srcs), which)
+        packs = [self._lin_rows_pack(p, d, backward) for p in packs]
+        _lib.check(getattr(self.lib, name)(n, d, *[_ptr(t) for t in list(head) + [t for s in srcs for t in s]], float(lam), *[_ptr(p) for p in packs],
+                                           int(act), *[_ptr(t) for t in outs], _stream()), name)
+
+    def _lin_rows_fwd(self, x, x_rows, srcs, lam, packs, act, out, hdecs):
+        """srcs: (H, rows, dt) per source."""
+        x, x_rows = _f32(x, "x"), _i32(x_rows, "x_rows")
+        srcs = [(_f32(H, "H"), _i32(rows, "rows"), _f32(dt, "dt")) for H, rows, dt in srcs]
+        n, d = srcs[0][1].shape[0], x.shape[1]
+        assert all(s[0].shape[1] == d for s in srcs) and (x_rows.shape[0] if x_rows is not None else x.shape[0]) == n
+        self._lin_rows_call("fwd", n, d, (x, x_rows), srcs, lam, packs, False, act, [out] + list(hdecs))
+
+    def _lin_rows_bwd(self, out, up, srcs, lam, packs, act, d_pre, d_hrows):
+        """srcs: (rows, dt) per source."""
+        out, up = _f32(out, "out"), _f32(up, "up")
+        srcs = [(_i32(rows, "rows"), _f32(dt, "dt")) for rows, dt in srcs]
+        n, d = up.shape
+        assert out.shape == up.shape
+        self._lin_rows_call("bwd", n, d, (out, up), srcs, lam, packs, True, act, [d_pre] + list(d_hrows))
+
     def lin_rows_fwd(self, x, x_rows, H, h_rows, dt, lam, pack, act, out, hdec):
         """out = act(x[x_rows] + hdec . W), hdec = exp(-lam dt) H[h_rows] (0 where h_rows < 0), one launch; out and hdec (n, d) are
         written whole.  x_rows: int32 [n] or None (row i reads x[i]); pack: lin_chain_pack_multi([W])[0]."""
-        x, H, dt = _f32(x, "x"), _f32(H, "H"), _f32(dt, "dt")
-        x_rows, h_rows = _i32(x_rows, "x_rows"), _i32(h_rows, "h_rows")
-        n, d = h_rows.shape[0], x.shape[1]
-        assert H.shape[1] == d and dt.numel() == n and (x_rows.shape[0] if x_rows is not None else x.shape[0]) == n
-        for t in (out, hdec):
-            assert tuple(t.shape) == (n, d) and t.is_contiguous() and t.dtype == torch.float32
-        _lib.check(self.lib.temp_lin_rows_fwd(n, d, _ptr(x), _ptr(x_rows), _ptr(H), _ptr(h_rows), _ptr(dt), float(lam),
-                                              _ptr(self._lin_rows_pack(pack, d, False)), int(act), _ptr(out), _ptr(hdec), _stream()), "temp_lin_rows_fwd")
+        self._lin_rows_fwd(x, x_rows, [(H, h_rows, dt)], lam, [pack], act, out, [hdec])
 
     def lin_rows_bwd(self, out, up, h_rows, dt, lam, pack, act, d_pre, d_hrows):
         """The backward of lin_rows_fwd in one launch: d_pre = up . [out > 0] (act = 1) or up, d_hrows = exp(-lam dt) (d_pre . W^T) (0
         where h_rows < 0); both (n, d) are written whole."""
-        out, up, dt, h_rows = _f32(out, "out"), _f32(up, "up"), _f32(dt, "dt"), _i32(h_rows, "h_rows")
-        n, d = up.shape
-        assert out.shape == up.shape and h_rows.shape[0] == n and dt.numel() == n
-        for t in (d_pre, d_hrows):
-            assert tuple(t.shape) == (n, d) and t.is_contiguous() and t.dtype == torch.float32
-        _lib.check(self.lib.temp_lin_rows_bwd(n, d, _ptr(out), _ptr(up), _ptr(h_rows), _ptr(dt), float(lam), _ptr(self._lin_rows_pack(pack, d, True)),
-                                              int(act), _ptr(d_pre), _ptr(d_hrows), _stream()), "temp_lin_rows_bwd")
-
-    # ---- one position of the bidirectional linear recurrence on gathered rows (include/temp_amd.h: temp_lin_rows2_fwd / _bwd) ------
-    def lin_rows2_supported(self, d):
-        return bool(self.lib.temp_lin_rows2_supported(int(d)))
+        self._lin_rows_bwd(out, up, [(h_rows, dt)], lam, [pack], act, d_pre, [d_hrows])
 
     def lin_rows2_fwd(self, x, x_rows, Hf, rows_f, dt_f, Hb, rows_b, dt_b, lam, pack_f, pack_b, act, out, hdec_f, hdec_b):
         """out = act(x[x_rows] + hdec_f . W_f + hdec_b . W_b), hdec_s = exp(-lam dt_s) H_s[rows_s] (0 where rows_s < 0), one launch; out,
         hdec_f and hdec_b (n, d) are written whole.  x_rows: int32 [n] or None (row i reads x[i]); pack_s: lin_chain_pack_multi([W_s])[0]."""
-        x, Hf, Hb, dt_f, dt_b = (_f32(t, k) for t, k in ((x, "x"), (Hf, "Hf"), (Hb, "Hb"), (dt_f, "dt_f"), (dt_b, "dt_b")))
-        x_rows, rows_f, rows_b = _i32(x_rows, "x_rows"), _i32(rows_f, "rows_f"), _i32(rows_b, "rows_b")
-        n, d = rows_f.shape[0], x.shape[1]
-        assert Hf.shape[1] == d and Hb.shape[1] == d and rows_b.shape[0] == n and dt_f.numel() == n and dt_b.numel() == n
-        assert (x_rows.shape[0] if x_rows is not None else x.shape[0]) == n
-        for t in (out, hdec_f, hdec_b):
-            assert tuple(t.shape) == (n, d) and t.is_contiguous() and t.dtype == torch.float32
-        _lib.check(self.lib.temp_lin_rows2_fwd(n, d, _ptr(x), _ptr(x_rows), _ptr(Hf), _ptr(rows_f), _ptr(dt_f), _ptr(Hb), _ptr(rows_b), _ptr(dt_b),
-                                               float(lam), _ptr(self._lin_rows_pack(pack_f, d, False)), _ptr(self._lin_rows_pack(pack_b, d, False)),
-                                               int(act), _ptr(out), _ptr(hdec_f), _ptr(hdec_b), _stream()), "temp_lin_rows2_fwd")
+        self._lin_rows_fwd(x, x_rows, [(Hf, rows_f, dt_f), (Hb, rows_b, dt_b)], lam, [pack_f, pack_b], act, out, [hdec_f, hdec_b])
 
     def lin_rows2_bwd(self, out, up, rows_f, dt_f, rows_b, dt_b, lam, pack_f, pack_b, act, d_pre, d_hrows_f, d_hrows_b):
         """The backward of lin_rows2_fwd in one launch: d_pre = up . [out > 0] (act = 1) or up, d_hrows_s = exp(-lam dt_s) (d_pre . W_s^T)
         (0 where rows_s < 0); all three (n, d) are written whole."""
-        out, up, dt_f, dt_b = _f32(out, "out"), _f32(up, "up"), _f32(dt_f, "dt_f"), _f32(dt_b, "dt_b")
-        rows_f, rows_b = _i32(rows_f, "rows_f"), _i32(rows_b, "rows_b")
-        n, d = up.shape
-        assert out.shape == up.shape and rows_f.shape[0] == n and rows_b.shape[0] == n and dt_f.numel() == n and dt_b.numel() == n
-        for t in (d_pre, d_hrows_f, d_hrows_b):
-            assert tuple(t.shape) == (n, d) and t.is_contiguous() and t.dtype == torch.float32
-        _lib.check(self.lib.temp_lin_rows2_bwd(n, d, _ptr(out), _ptr(up), _ptr(rows_f), _ptr(dt_f), _ptr(rows_b), _ptr(dt_b), float(lam),
-                                               _ptr(self._lin_rows_pack(pack_f, d, True)), _ptr(self._lin_rows_pack(pack_b, d, True)), int(act),
-                                               _ptr(d_pre), _ptr(d_hrows_f), _ptr(d_hrows_b), _stream()), "temp_lin_rows2_bwd")
+        self._lin_rows_bwd(out, up, [(rows_f, dt_f), (rows_b, dt_b)], lam, [pack_f, pack_b], act, d_pre, [d_hrows_f, d_hrows_b])
 
     def gru_grads_g4_supported(self, ns, d, variant):
         """True when gru_grads_g4 takes GRUs of these row counts and this width (then the chain backward should write g4)."""

@@ -150,16 +150,6 @@ class BiDynamicRGCN(DynamicRGCN):
     def _bi_pair(self, wb):
         return bool(getattr(self, "bi_pair_pass", False) and wb.batched and self._linear_layer())
 
-    @staticmethod
-    def _rows_inverse(cache, key, idx_host, H):
-        """gather_inverse of a static history-row list over the rows of H, built on first use and kept with the prepared batch."""
-        if H is None:
-            return None
-        k = (key, int(H.shape[0]))
-        if k not in cache:
-            cache[k] = TF.gather_inverse(idx_host, H.shape[0], H.device)
-        return cache[k]
-
     def _centre_inverses(self, wb, Hf, Hb):
         cache = wb.__dict__.setdefault("_centre_inv", {})
         return (self._rows_inverse(cache, "f", wb.target.prev_idx, Hf), self._rows_inverse(cache, "b", wb.target_b.prev_idx, Hb))
@@ -371,71 +361,26 @@ class BiDynamicRGCN(DynamicRGCN):
                 and getattr(enc.layer_2, "num_layers", 1) == 1 and not (enc.layer_1._extra() or enc.layer_2._extra()))
 
     def _all_maps(self, wb):
-        """Batched path: per-direction maps (DynamicRGCN._all_maps).  Reference-granular path (both layers recurrent): the
-        first layer's state of a (window, entity) pair depends on BOTH directions' previous states, so the pairs are the union
-        -- a previous state in either direction -- each with its two history rows (-1 = zero state in that direction); every
-        other inactive entity takes its row of the once-per-entity table."""
-        if wb.batched:
-            return self._union_maps(wb) if self._bi_pair(wb) else super()._all_maps(wb)
-        if getattr(wb, "all_maps", None) is None:
-            dev = self._device()
-            N, B = self.num_ents, len(wb.graphs)
-            plan_f, plan_b = wb.plan
-            L = plan_f.seq_len
-            act = np.zeros((B, N), dtype=bool)
-            sizes = [g.n for g in wb.graphs]
-            n_out = int(sum(sizes))
-            off_out = np.concatenate([[0], np.cumsum(sizes)])
-            for b, g in enumerate(wb.graphs):
-                act[b, g.gids] = True
-            wb.n_inactive = int(B * N - act.sum())
-            rf = np.stack([plan_f.final_all(b, L - 1)[0] for b in range(B)])
-            rb = np.stack([plan_b.final_all(b, L - 1)[0] for b in range(B)])
-            gf = np.stack([plan_f.final_all(b, L - 1)[1] for b in range(B)])
-            gb = np.stack([plan_b.final_all(b, L - 1)[1] for b in range(B)])
-            has = ~act & ((rf >= 0) | (rb >= 0))
-            bb, ee = np.nonzero(has)
-            n_prev = int(bb.shape[0])
-            asm = np.broadcast_to(n_out + n_prev + np.arange(N, dtype=np.int64)[None, :], (B, N)).copy()
-            asm[has] = n_out + np.arange(n_prev)
-            for b, g in enumerate(wb.graphs):
-                asm[b, g.gids] = off_out[b] + np.arange(g.n)
-            host = dict(ent=ee, idx_f=rf[bb, ee], idx_b=rb[bb, ee], asm=asm.reshape(-1),
-                        dt_f=gf[bb, ee].astype(np.float32).view(np.int32), dt_b=gb[bb, ee].astype(np.float32).view(np.int32))
-            d = S.upload_packed(host, dev, np.int32)
-            f32 = lambda t: t.view(torch.float32).view(-1, 1)
-            wb.all_maps = [dict(n_prev=n_prev, ent=d["ent"], idx_f=d["idx_f"], idx_b=d["idx_b"], dt_f=f32(d["dt_f"]), dt_b=f32(d["dt_b"]),
-                                idx_f_host=host["idx_f"], idx_b_host=host["idx_b"],
-                                asm=d["asm"], ent_inv=TF.gather_inverse(ee, N, dev) if n_prev else None,
-                                asm_inv=TF.gather_inverse(asm.reshape(-1), n_out + n_prev + N if wb.n_inactive else n_out, dev))]
-        return wb.all_maps
+        """Batched path: per-direction maps (DynamicRGCN._all_maps), with bi_pair_pass the union map.  Reference-granular path (both
+        layers recurrent): the first layer's state of a (window, entity) pair depends on BOTH directions' previous states, so the
+        pairs are the union as well (_union_maps)."""
+        if wb.batched and not self._bi_pair(wb):
+            return super()._all_maps(wb)
+        return self._union_maps(wb)
 
     def _union_maps(self, wb):
-        """bi_pair_pass: ONE map over the union pairs -- inactive (window, entity) pairs with a previous state in EITHER direction,
-        window-major, each with its two history rows (-1: no state in that direction) and time gaps; every other inactive entity
-        takes its row of the table (one row per entity; per (window, entity) while the self-loop dropout draws, as in
-        DynamicRGCN._all_maps: `ent` then indexes those rows).  asm assembles [encoder output ; pair rows ; table]."""
-        rep = self._all_rep()
+        """bi_pair_pass, and the reference-granular path: ONE map over the union pairs -- inactive (window, entity) pairs with a
+        previous state in EITHER direction, window-major, each with its two history rows (-1: no state in that direction) and time
+        gaps; every other inactive entity takes its row of the table (one row per entity; on the batched path per (window, entity)
+        while the self-loop dropout draws, as in DynamicRGCN._all_maps: `ent` then indexes those rows).  asm assembles [encoder
+        output ; pair rows ; table]."""
+        rep = wb.batched and self._all_rep()                               # (the reference-granular pass keeps one row per entity)
         if getattr(wb, "all_maps", None) is None or getattr(wb, "all_rep", False) != rep:
             dev = self._device()
             N, B = self.num_ents, len(wb.graphs)
             plan_f, plan_b = wb.plan
             L = plan_f.seq_len
-            T = B * N if rep else N
-            tab = (np.arange(B * N, dtype=np.int64).reshape(B, N) if rep else np.broadcast_to(np.arange(N, dtype=np.int64)[None, :], (B, N)))
-            wb.all_rep = rep
-            if rep:
-                ids = np.tile(np.arange(N, dtype=np.int32), B)
-                wb.all_rep_ids = _lib.to_device(ids, dev)
-                wb.all_rep_inv = TF.gather_inverse(ids, N, dev)
-            act = np.zeros((B, N), dtype=bool)
-            sizes = [g.n for g in wb.graphs]
-            n_out = int(sum(sizes))
-            off_out = np.concatenate([[0], np.cumsum(sizes)])
-            for b, g in enumerate(wb.graphs):
-                act[b, g.gids] = True
-            wb.n_inactive = int(B * N - act.sum())
-            wb.all_time = None
+            frame = act, n_out, _, _, T = self._all_frame(wb, rep)
             _lib.pause_point()
             fin_f = [plan_f.final_all(b, L - 1) for b in range(B)]
             fin_b = [plan_b.final_all(b, L - 1) for b in range(B)]
@@ -444,10 +389,7 @@ class BiDynamicRGCN(DynamicRGCN):
             has = ~act & ((rf >= 0) | (rb >= 0))
             bb, ee = np.nonzero(has)                                       # window-major
             n_prev = int(bb.shape[0])
-            asm = (n_out + n_prev + tab).copy()
-            asm[has] = n_out + np.arange(n_prev)
-            for b, g in enumerate(wb.graphs):
-                asm[b, g.gids] = off_out[b] + np.arange(g.n)
+            asm, n_src = self._all_asm(wb, has, frame)
             ent = bb * N + ee if rep else ee                               # the pair's row of the table
             host = dict(ent=ent, idx_f=rf[bb, ee], idx_b=rb[bb, ee], asm=asm.reshape(-1),
                         dt_f=gf[bb, ee].astype(np.float32).view(np.int32), dt_b=gb[bb, ee].astype(np.float32).view(np.int32))
@@ -457,7 +399,7 @@ class BiDynamicRGCN(DynamicRGCN):
             wb.all_maps = [dict(n_prev=n_prev, ent=d["ent"], idx_f=d["idx_f"], idx_b=d["idx_b"], dt_f=f32(d["dt_f"]), dt_b=f32(d["dt_b"]),
                                 idx_f_host=host["idx_f"], idx_b_host=host["idx_b"], asm=d["asm"],
                                 ent_inv=TF.gather_inverse(ent, T, dev) if n_prev else None,
-                                asm_inv=TF.gather_inverse(asm.reshape(-1), n_out + n_prev + T if wb.n_inactive else n_out, dev))]
+                                asm_inv=TF.gather_inverse(asm.reshape(-1), n_src if wb.n_inactive else n_out, dev))]
         return wb.all_maps
 
     def _all_embeds_batched_union(self, wb, out, hist):
@@ -466,12 +408,10 @@ class BiDynamicRGCN(DynamicRGCN):
         act(x[e] + both directions' recurrent terms) through ONE lin_step_rows2 node; the active rows come from `out`."""
         l1, l2 = self.ent_encoder.layer_1, self.ent_encoder.layer_2
         (m,) = self._all_maps(wb)
-        B, N = len(wb.graphs), self.num_ents
         if wb.n_inactive == 0:
-            return TF.gather_rows(out, m["asm"], m["asm_inv"]).view(B, N, out.shape[1])
+            return self._all_from_rows(wb, out, m)
         (Hf, _), (Hb, _) = hist
-        E = TF.gather_rows(self.ent_embeds, wb.all_rep_ids, wb.all_rep_inv) if wb.all_rep else self.ent_embeds
-        x = l2.pre_isolated(l1.conv_isolated(E))
+        x = l2.pre_isolated(l1.conv_isolated(self._all_table_input(wb)))
         parts = [out]
         if m["n_prev"]:
             cache = m.setdefault("_gather_inv", {})
@@ -479,8 +419,7 @@ class BiDynamicRGCN(DynamicRGCN):
                                            l2.time_weight_forward, l2.time_weight_backward, 1 if l2.relu_fused() else 0, m["ent_inv"],
                                            self._rows_inverse(cache, "f", m["idx_f_host"], Hf), self._rows_inverse(cache, "b", m["idx_b_host"], Hb)))
         parts.append(l2._finish(x))
-        big = TF.gather_rows(torch.cat(parts, dim=0), m["asm"], m["asm_inv"])
-        return big.view(B, N, big.shape[1])
+        return self._all_assemble(wb, parts, m)
 
     def all_embeds_batched(self, wb, out, hist):
         if wb.batched and self._bi_pair(wb):
@@ -492,11 +431,10 @@ class BiDynamicRGCN(DynamicRGCN):
         enc = self.ent_encoder
         l1, l2 = enc.layer_1, enc.layer_2
         (m,) = self._all_maps(wb)
-        B, N = len(wb.graphs), self.num_ents
         if wb.n_inactive == 0:
-            return TF.gather_rows(out, m["asm"], m["asm_inv"]).view(B, N, out.shape[1])
+            return self._all_from_rows(wb, out, m)
         (f1, f2), (b1, b2) = hist
-        iso1 = l1.conv_isolated(self.ent_embeds)
+        iso1 = l1.conv_isolated(self._all_table_input(wb))
         t1 = self._zero_state_rows(l1.forward_rnn, iso1, l1) + self._zero_state_rows(l1.backward_rnn, iso1, l1)
         x2 = l2.conv_isolated(t1)
         parts = [out]
@@ -513,8 +451,7 @@ class BiDynamicRGCN(DynamicRGCN):
             h1p = both(l1, TF.gather_rows(iso1, m["ent"], m["ent_inv"]), f1, b1)
             parts.append(both(l2, l2.conv_isolated(h1p), f2, b2))
         parts.append(self._zero_state_rows(l2.forward_rnn, x2, l2) + self._zero_state_rows(l2.backward_rnn, x2, l2))
-        big = TF.gather_rows(torch.cat(parts, dim=0), m["asm"], m["asm_inv"])
-        return big.view(B, N, big.shape[1])
+        return self._all_assemble(wb, parts, m)
 
     def get_all_embeds_Gt(self, convoluted_embeds, g, t, plans, b, hist):
         """models/BiDynamicRGCN.py:102-112."""

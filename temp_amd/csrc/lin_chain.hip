@@ -17,9 +17,9 @@
 // it to the upstream gradient.  No atomics; every sum has one order per launch shape, so results are bit-repeatable.  Several
 // workgroups share a CU (60 KB of LDS at d = 200), which is what hides the L2 latency of the weight stream in this plain version.
 //
-// k_lin_rows_fwd / _bwd (temp_lin_rows_*) are ONE such step on gathered rows, without the tables: the (window, entity) pair rows of the
-// batched all-entity pass.  k_lin_rows2_fwd / _bwd (temp_lin_rows2_*) are that step with both directions' recurrent terms in front of
-// one activation: BiRRGCNLayer's centre position and its union pair rows.
+// k_lin_rows_fwd<NS> / _bwd<NS> are ONE such step on gathered rows, without the tables, with NS history sources in front of one
+// activation.  NS = 1 (temp_lin_rows_*): the (window, entity) pair rows of the batched all-entity pass.  NS = 2 (temp_lin_rows2_*): both
+// directions' recurrent terms, BiRRGCNLayer's centre position and its union pair rows.
 #include <atomic>
 #include "common.hpp"
 
@@ -246,158 +246,65 @@ __global__ void __launch_bounds__(LC_THREADS) k_lin_chain_bwd(LinArgs a, LinUps 
   }
 }
 
-// ---- one position on gathered rows (temp_lin_rows_fwd / _bwd) -----------------------------------------------------------
-// The pair rows of the batched all-entity pass: one step of the chain without the track tables.  A workgroup owns rows
-// 32 b .. 32 b + 31 and runs the three phases once; a row past n is a zero row of the B operand and is never stored.
+// ---- one position on gathered rows, NS history sources in front of one activation (temp_lin_rows_* NS = 1, temp_lin_rows2_* NS = 2) ----
+// NS = 1: the pair rows of the batched all-entity pass, one step of the chain without the track tables.  NS = 2: BiRRGCNLayer's
+// centre / isolated form, where the activation follows the SUM of both directions' recurrent terms, so the two sources of a row go
+// through one kernel.  A workgroup owns rows 32 b .. 32 b + 31 and runs the three phases once; a row past n is a zero row of the B
+// operand and is never stored.  Forward: the NS decayed tiles lie in LDS side by side and the product walks [hdec_0 | .. ] against
+// [W_0 ; ..] into one accumulator set (K = NS d), source 0 first.  Backward: the one d_pre tile against every W_s^T into NS product
+// tiles.  LDS: 32 (ldo + NS ldk) words forward, 32 (NS ldo + ldk) backward, + 64 NS for the tables.  NS = 1: 55 552 / 66 816 bytes at
+// d = 200 / 256; NS = 2: 81 920 / 84 992 at d = 200, 100 352 at d = 256 (of the 160 KB a workgroup has).
 #define LR_ROWS LC_TRACKS
-inline size_t lin_lds_rows(int D) { LinGeom g = lin_geom(D); return ((size_t)LR_ROWS * (g.ldo + g.ldk) + 2 * LR_ROWS) * 4; }
-
-__global__ void __launch_bounds__(LC_THREADS) k_lin_rows_fwd(int n, int D, int act, const float* __restrict__ x, const int32_t* __restrict__ x_rows,
-                                                             const float* __restrict__ H, const int32_t* __restrict__ h_rows,
-                                                             const float* __restrict__ dt, float lambda, const float4* __restrict__ wf,
-                                                             float* __restrict__ out, float* __restrict__ HD) {
-  extern __shared__ __attribute__((aligned(16))) float lds[];
-  const int D4 = D >> 2;
-  const LinGeom g = lin_geom(D);
-  float* sb = lds;                                          // [32][ldo] raw products
-  float* kb = sb + LR_ROWS * g.ldo;                         // [32][ldk] decayed rows (B operand)
-  int* hrb = (int*)(kb + LR_ROWS * g.ldk);                  // [32] H row of every row (-1: none, or past n)
-  float* decb = (float*)(hrb + LR_ROWS);                    // [32] decay factor
-  const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
-  const int items = LR_ROWS * D4;
-  const long long row0 = (long long)blockIdx.x * LR_ROWS;
-
-  for (int i = tid; i < LR_ROWS * g.ldk; i += LC_THREADS) kb[i] = 0.f;            // the k padding must be 0, not stale LDS
-  if (tid < LR_ROWS) {
-    const long long row = row0 + tid;
-    const int hr = row < n ? h_rows[row] : -1;
-    hrb[tid] = hr;
-    decb[tid] = hr >= 0 ? expf(-dt[row] * lambda) : 0.f;
-  }
-  __syncthreads();
-  // 1: hdec = dec . H[h_rows], 0 for a row without a previous state
-  for (int i = tid; i < items; i += LC_THREADS) {
-    const int t = i / D4, c = (i - t * D4) << 2;
-    const long long row = row0 + t;
-    const int hr = hrb[t];
-    float4 hd = zero4();
-    if (hr >= 0) hd = scale4(ld4(H + (size_t)hr * D + c), decb[t]);
-    if (row < n) st4(HD + (size_t)row * D + c, hd);
-    st4(kb + t * g.ldk + c, hd);
-  }
-  __syncthreads();
-  // 2: hdec . W
-  lin_product(wf, kb, sb, g, wave, lane);
-  __syncthreads();
-  // 3: out = act(x + product)
-  for (int i = tid; i < items; i += LC_THREADS) {
-    const int t = i / D4, c = (i - t * D4) << 2;
-    const long long row = row0 + t;
-    if (row >= n) continue;
-    const long long xr = x_rows ? (long long)x_rows[row] : row;
-    float4 v = ld4(sb + t * g.ldo + c);
-    if (xr >= 0) v = add4(v, ld4(x + (size_t)xr * D + c));
-    if (act) v = relu4(v);
-    st4(out + (size_t)row * D + c, v);
-  }
-}
-
-__global__ void __launch_bounds__(LC_THREADS) k_lin_rows_bwd(int n, int D, int act, const float* __restrict__ out, const float* __restrict__ up,
-                                                             const int32_t* __restrict__ h_rows, const float* __restrict__ dt, float lambda,
-                                                             const float4* __restrict__ wb, float* __restrict__ DP, float* __restrict__ DH) {
-  extern __shared__ __attribute__((aligned(16))) float lds[];
-  const int D4 = D >> 2;
-  const LinGeom g = lin_geom(D);
-  float* pb = lds;                                          // [32][ldo] raw d_pre . W^T
-  float* kb = pb + LR_ROWS * g.ldo;                         // [32][ldk] d_pre (B operand)
-  int* hrb = (int*)(kb + LR_ROWS * g.ldk);
-  float* decb = (float*)(hrb + LR_ROWS);
-  const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
-  const int items = LR_ROWS * D4;
-  const long long row0 = (long long)blockIdx.x * LR_ROWS;
-
-  for (int i = tid; i < LR_ROWS * g.ldk; i += LC_THREADS) kb[i] = 0.f;
-  if (tid < LR_ROWS) {
-    const long long row = row0 + tid;
-    const int hr = row < n ? h_rows[row] : -1;
-    hrb[tid] = hr;
-    decb[tid] = hr >= 0 ? expf(-dt[row] * lambda) : 0.f;
-  }
-  __syncthreads();
-  // 1: d_pre = upstream . [out > 0]
-  for (int i = tid; i < items; i += LC_THREADS) {
-    const int t = i / D4, c = (i - t * D4) << 2;
-    const long long row = row0 + t;
-    float4 gv = zero4();
-    if (row < n) {
-      gv = ld4(up + (size_t)row * D + c);
-      if (act) gv = relu_gate4(ld4(out + (size_t)row * D + c), gv);
-      st4(DP + (size_t)row * D + c, gv);
-    }
-    st4(kb + t * g.ldk + c, gv);
-  }
-  __syncthreads();
-  // 2: d_pre . W^T
-  lin_product(wb, kb, pb, g, wave, lane);
-  __syncthreads();
-  // 3: d_hrows = dec . product, 0 for a row without a previous state (a select: the product of such a row is not read)
-  for (int i = tid; i < items; i += LC_THREADS) {
-    const int t = i / D4, c = (i - t * D4) << 2;
-    const long long row = row0 + t;
-    if (row >= n) continue;
-    st4(DH + (size_t)row * D + c, hrb[t] >= 0 ? scale4(ld4(pb + t * g.ldo + c), decb[t]) : zero4());
-  }
-}
-
-// ---- one position of the BIDIRECTIONAL recurrence on gathered rows (temp_lin_rows2_fwd / _bwd) ----------------------------
-// BiRRGCNLayer's centre / isolated form: the activation follows the SUM of both directions' recurrent terms, so the two sources of a
-// row go through one kernel.  The phases are k_lin_rows_*'s.  Forward: both decayed tiles lie in LDS side by side and the product
-// walks [hdec_f | hdec_b] against [W_f ; W_b] into one accumulator set (K = 2 d).  Backward: the one d_pre tile against W_f^T and
-// against W_b^T into two product tiles.  LDS: 32 (ldo + 2 ldk) words forward, 32 (2 ldo + ldk) backward, + 128: 100 352 bytes at
-// d = 256 (of the 160 KB a workgroup has), 81 920 / 84 992 at d = 200.
-struct LinRows2 {                                            // index 0: forward direction, 1: backward direction
-  const float* H[2]; const int32_t* rows[2]; const float* dt[2];
-  const float4* w[2];                                        // the forward (fwd kernel) / backward (bwd kernel) pieces of W_f, W_b
+template <int NS>
+struct LinRows {                                             // per source (NS = 2: index 0 forward direction, 1 backward direction)
+  const float* H[NS]; const int32_t* rows[NS]; const float* dt[NS];      // (H is not read by the backward)
+  const float4* w[NS];                                       // the forward (fwd kernel) / backward (bwd kernel) piece of W_s
+  float* o[NS];                                              // hdec_s (fwd kernel) / d_hrows_s (bwd kernel)
 };
-inline size_t lin_lds_rows2_fwd(int D) { LinGeom g = lin_geom(D); return ((size_t)LR_ROWS * (g.ldo + 2 * g.ldk) + 4 * LR_ROWS) * 4; }
-inline size_t lin_lds_rows2_bwd(int D) { LinGeom g = lin_geom(D); return ((size_t)LR_ROWS * (2 * g.ldo + g.ldk) + 4 * LR_ROWS) * 4; }
+inline size_t lin_lds_rows_fwd(int D, int NS) { LinGeom g = lin_geom(D); return ((size_t)LR_ROWS * (g.ldo + NS * g.ldk) + 2 * NS * LR_ROWS) * 4; }
+inline size_t lin_lds_rows_bwd(int D, int NS) { LinGeom g = lin_geom(D); return ((size_t)LR_ROWS * (NS * g.ldo + g.ldk) + 2 * NS * LR_ROWS) * 4; }
 
-// hrb[s][t] = the H row of row t in direction s (-1: none, or past n), decb[s][t] its decay factor: threads 0 .. 63
-__device__ __forceinline__ void lin_rows2_tables(const LinRows2& a, int n, long long row0, float lambda, int* hrb, float* decb, int tid) {
-  if (tid < 2 * LR_ROWS) {
-    const bool bw = tid >= LR_ROWS;
+// hrb[s][t] = the H row of row t in source s (-1: none, or past n), decb[s][t] its decay factor: threads 0 .. 32 NS - 1
+template <int NS>
+__device__ __forceinline__ void lin_rows_tables(const LinRows<NS>& a, int n, long long row0, float lambda, int* hrb, float* decb, int tid) {
+  if (tid < NS * LR_ROWS) {
     const long long row = row0 + (tid & (LR_ROWS - 1));
-    const int32_t* rows = bw ? a.rows[1] : a.rows[0];
-    const float* dt = bw ? a.dt[1] : a.dt[0];
+    const int32_t* rows = a.rows[0];
+    const float* dt = a.dt[0];
+#pragma unroll
+    for (int s = 1; s < NS; ++s)
+      if (tid >= s * LR_ROWS) { rows = a.rows[s]; dt = a.dt[s]; }
     const int hr = row < n ? rows[row] : -1;
     hrb[tid] = hr;
     decb[tid] = hr >= 0 ? expf(-dt[row] * lambda) : 0.f;
   }
 }
 
-__global__ void __launch_bounds__(LC_THREADS) k_lin_rows2_fwd(int n, int D, int act, const float* __restrict__ x, const int32_t* __restrict__ x_rows,
-                                                              LinRows2 a, float lambda, float* __restrict__ out, float* __restrict__ HDf,
-                                                              float* __restrict__ HDb) {
+template <int NS>
+__global__ void __launch_bounds__(LC_THREADS) k_lin_rows_fwd(int n, int D, int act, float lambda, LinRows<NS> a, const float* __restrict__ x,
+                                                             const int32_t* __restrict__ x_rows, float* __restrict__ out) {
   extern __shared__ __attribute__((aligned(16))) float lds[];
   const int D4 = D >> 2;
   const LinGeom g = lin_geom(D);
   float* sb = lds;                                          // [32][ldo] raw products
-  float* kb = sb + LR_ROWS * g.ldo;                         // [2][32][ldk] decayed rows of both directions (B operands)
-  int* hrb = (int*)(kb + 2 * LR_ROWS * g.ldk);              // [2][32]
-  float* decb = (float*)(hrb + 2 * LR_ROWS);                // [2][32]
+  float* kb = sb + LR_ROWS * g.ldo;                         // [NS][32][ldk] decayed rows of every source (B operands)
+  int* hrb = (int*)(kb + NS * LR_ROWS * g.ldk);             // [NS][32]
+  float* decb = (float*)(hrb + NS * LR_ROWS);               // [NS][32]
   const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
   const int items = LR_ROWS * D4;
   const long long row0 = (long long)blockIdx.x * LR_ROWS;
 
-  for (int i = tid; i < 2 * LR_ROWS * g.ldk; i += LC_THREADS) kb[i] = 0.f;        // the k padding must be 0, not stale LDS
-  lin_rows2_tables(a, n, row0, lambda, hrb, decb, tid);
+  for (int i = tid; i < NS * LR_ROWS * g.ldk; i += LC_THREADS) kb[i] = 0.f;       // the k padding must be 0, not stale LDS
+  lin_rows_tables<NS>(a, n, row0, lambda, hrb, decb, tid);
   __syncthreads();
-  // 1: hdec_s = dec_s . H_s[rows_s], 0 for a row without a previous state in that direction
+  // 1: hdec_s = dec_s . H_s[rows_s], 0 for a row without a previous state in that source
+  const float* ks[NS];
 #pragma unroll
-  for (int s = 0; s < 2; ++s) {
+  for (int s = 0; s < NS; ++s) {
     const float* __restrict__ H = a.H[s];
-    float* __restrict__ HD = s ? HDb : HDf;
-    float* ks = kb + s * LR_ROWS * g.ldk;
+    float* __restrict__ HD = a.o[s];
+    float* k = kb + s * LR_ROWS * g.ldk;
+    ks[s] = k;
     for (int i = tid; i < items; i += LC_THREADS) {
       const int t = i / D4, c = (i - t * D4) << 2;
       const long long row = row0 + t;
@@ -405,16 +312,12 @@ __global__ void __launch_bounds__(LC_THREADS) k_lin_rows2_fwd(int n, int D, int 
       float4 hd = zero4();
       if (hr >= 0) hd = scale4(ld4(H + (size_t)hr * D + c), decb[s * LR_ROWS + t]);
       if (row < n) st4(HD + (size_t)row * D + c, hd);
-      st4(ks + t * g.ldk + c, hd);
+      st4(k + t * g.ldk + c, hd);
     }
   }
   __syncthreads();
-  // 2: [hdec_f | hdec_b] . [W_f ; W_b]
-  {
-    const float4* const ws[2] = {a.w[0], a.w[1]};
-    const float* const ks[2] = {kb, kb + LR_ROWS * g.ldk};
-    lin_product_n<2>(ws, ks, sb, g, wave, lane);
-  }
+  // 2: [hdec_0 | ..] . [W_0 ; ..]
+  lin_product_n<NS>(a.w, ks, sb, g, wave, lane);
   __syncthreads();
   // 3: out = act(x + product)
   for (int i = tid; i < items; i += LC_THREADS) {
@@ -429,22 +332,22 @@ __global__ void __launch_bounds__(LC_THREADS) k_lin_rows2_fwd(int n, int D, int 
   }
 }
 
-__global__ void __launch_bounds__(LC_THREADS) k_lin_rows2_bwd(int n, int D, int act, const float* __restrict__ out, const float* __restrict__ up,
-                                                              LinRows2 a, float lambda, float* __restrict__ DP, float* __restrict__ DHf,
-                                                              float* __restrict__ DHb) {
+template <int NS>
+__global__ void __launch_bounds__(LC_THREADS) k_lin_rows_bwd(int n, int D, int act, float lambda, LinRows<NS> a, const float* __restrict__ out,
+                                                             const float* __restrict__ up, float* __restrict__ DP) {
   extern __shared__ __attribute__((aligned(16))) float lds[];
   const int D4 = D >> 2;
   const LinGeom g = lin_geom(D);
-  float* pb = lds;                                          // [2][32][ldo] raw d_pre . W_f^T, d_pre . W_b^T
-  float* kb = pb + 2 * LR_ROWS * g.ldo;                     // [32][ldk] d_pre (B operand of both products)
+  float* pb = lds;                                          // [NS][32][ldo] raw d_pre . W_s^T
+  float* kb = pb + NS * LR_ROWS * g.ldo;                    // [32][ldk] d_pre (B operand of every product)
   int* hrb = (int*)(kb + LR_ROWS * g.ldk);
-  float* decb = (float*)(hrb + 2 * LR_ROWS);
+  float* decb = (float*)(hrb + NS * LR_ROWS);
   const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
   const int items = LR_ROWS * D4;
   const long long row0 = (long long)blockIdx.x * LR_ROWS;
 
   for (int i = tid; i < LR_ROWS * g.ldk; i += LC_THREADS) kb[i] = 0.f;
-  lin_rows2_tables(a, n, row0, lambda, hrb, decb, tid);
+  lin_rows_tables<NS>(a, n, row0, lambda, hrb, decb, tid);
   __syncthreads();
   // 1: d_pre = upstream . [out > 0]
   for (int i = tid; i < items; i += LC_THREADS) {
@@ -459,14 +362,14 @@ __global__ void __launch_bounds__(LC_THREADS) k_lin_rows2_bwd(int n, int D, int 
     st4(kb + t * g.ldk + c, gv);
   }
   __syncthreads();
-  // 2: d_pre . W_f^T and d_pre . W_b^T (one B operand, two product tiles: no barrier between them)
-  lin_product(a.w[0], kb, pb, g, wave, lane);
-  lin_product(a.w[1], kb, pb + LR_ROWS * g.ldo, g, wave, lane);
-  __syncthreads();
-  // 3: d_hrows_s = dec_s . product_s, 0 for a row without a previous state in that direction (a select)
+  // 2: d_pre . W_s^T (one B operand, NS product tiles: no barrier between them)
 #pragma unroll
-  for (int s = 0; s < 2; ++s) {
-    float* __restrict__ DH = s ? DHb : DHf;
+  for (int s = 0; s < NS; ++s) lin_product(a.w[s], kb, pb + s * LR_ROWS * g.ldo, g, wave, lane);
+  __syncthreads();
+  // 3: d_hrows_s = dec_s . product_s, 0 for a row without a previous state in that source (a select: the product of such a row is not read)
+#pragma unroll
+  for (int s = 0; s < NS; ++s) {
+    float* __restrict__ DH = a.o[s];
     const float* ps = pb + s * LR_ROWS * g.ldo;
     for (int i = tid; i < items; i += LC_THREADS) {
       const int t = i / D4, c = (i - t * D4) << 2;
@@ -575,66 +478,65 @@ int temp_lin_chain_bwd(const TempLinChain* c, const float* h, int32_t n_up, cons
 
 long long temp_lin_chain_launches(void) { return g_lin_launches.load(std::memory_order_relaxed); }
 
-int temp_lin_rows_supported(int d) { return temp_lin_chain_supported(d, 0); }
+}  // extern "C"
+
+static int lin_rows_supported(int d, int ns) {
+  return temp_lin_chain_supported(d, 0) && lin_lds_rows_fwd(d, ns) <= LC_LDS_LIMIT && lin_lds_rows_bwd(d, ns) <= LC_LDS_LIMIT;
+}
+
+// The body of the four temp_lin_rows*_fwd / _bwd calls.  FWD: p0 = x, p1 = x_rows (int32, may be null), p2 = out; else p0 = out (may be
+// null without the activation), p1 = up, p2 = d_pre.
+template <int NS, bool FWD>
+static int lin_rows_run(int n, int d, int act, float lambda, const LinRows<NS>& a, const float* p0, const void* p1, float* p2, void* stream) {
+  if (n < 0 || d <= 0 || (act != 0 && act != 1)) return TEMP_E_BADARG;
+  if (!lin_rows_supported(d, NS)) return TEMP_E_UNSUPPORTED;
+  if (n == 0) return TEMP_OK;
+  bool ok = p2 && (FWD ? p0 != nullptr : p1 && (p0 || !act));
+  for (int s = 0; s < NS; ++s) ok = ok && (a.H[s] || !FWD) && a.rows[s] && a.dt[s] && a.w[s] && a.o[s];
+  if (!ok) return TEMP_E_BADARG;
+  static bool attr = false;                                  // (one per instantiation = per kernel)
+  const dim3 grid(ceil_div(n, LR_ROWS)), block(LC_THREADS);
+  if constexpr (FWD) {
+    if (lin_lds_attr(k_lin_rows_fwd<NS>, &attr)) return TEMP_E_LAUNCH;
+    TEMP_LAUNCH(NS == 1 ? K_LIN_ROWS_FWD : K_LIN_ROWS2_FWD, k_lin_rows_fwd<NS>, grid, block, lin_lds_rows_fwd(d, NS), (hipStream_t)stream, n, d, act, lambda,
+                a, p0, (const int32_t*)p1, p2);
+  } else {
+    if (lin_lds_attr(k_lin_rows_bwd<NS>, &attr)) return TEMP_E_LAUNCH;
+    TEMP_LAUNCH(NS == 1 ? K_LIN_ROWS_BWD : K_LIN_ROWS2_BWD, k_lin_rows_bwd<NS>, grid, block, lin_lds_rows_bwd(d, NS), (hipStream_t)stream, n, d, act, lambda,
+                a, p0, (const float*)p1, p2);
+  }
+  return launch_status();
+}
+
+extern "C" {
+
+int temp_lin_rows_supported(int d) { return lin_rows_supported(d, 1); }
+int temp_lin_rows2_supported(int d) { return lin_rows_supported(d, 2); }
 
 int temp_lin_rows_fwd(int n, int d, const float* x, const int32_t* x_rows, const float* H, const int32_t* h_rows, const float* dt, float lambda,
                       const float* pack_fwd, int act, float* out, float* hdec, void* stream) {
-  if (n < 0 || d <= 0 || (act != 0 && act != 1)) return TEMP_E_BADARG;
-  if (!temp_lin_rows_supported(d)) return TEMP_E_UNSUPPORTED;
-  if (n == 0) return TEMP_OK;
-  if (!x || !H || !h_rows || !dt || !pack_fwd || !out || !hdec) return TEMP_E_BADARG;
-  static bool attr = false;
-  if (lin_lds_attr(k_lin_rows_fwd, &attr)) return TEMP_E_LAUNCH;
-  TEMP_LAUNCH(K_LIN_ROWS_FWD, k_lin_rows_fwd, dim3(ceil_div(n, LR_ROWS)), dim3(LC_THREADS), lin_lds_rows(d), (hipStream_t)stream, n, d, act, x, x_rows, H,
-              h_rows, dt, lambda, (const float4*)pack_fwd, out, hdec);
-  return launch_status();
+  const LinRows<1> a = {{H}, {h_rows}, {dt}, {(const float4*)pack_fwd}, {hdec}};
+  return lin_rows_run<1, true>(n, d, act, lambda, a, x, x_rows, out, stream);
 }
 
 int temp_lin_rows_bwd(int n, int d, const float* out, const float* up, const int32_t* h_rows, const float* dt, float lambda, const float* pack_bwd,
                       int act, float* d_pre, float* d_hrows, void* stream) {
-  if (n < 0 || d <= 0 || (act != 0 && act != 1)) return TEMP_E_BADARG;
-  if (!temp_lin_rows_supported(d)) return TEMP_E_UNSUPPORTED;
-  if (n == 0) return TEMP_OK;
-  if ((act && !out) || !up || !h_rows || !dt || !pack_bwd || !d_pre || !d_hrows) return TEMP_E_BADARG;
-  static bool attr = false;
-  if (lin_lds_attr(k_lin_rows_bwd, &attr)) return TEMP_E_LAUNCH;
-  TEMP_LAUNCH(K_LIN_ROWS_BWD, k_lin_rows_bwd, dim3(ceil_div(n, LR_ROWS)), dim3(LC_THREADS), lin_lds_rows(d), (hipStream_t)stream, n, d, act, out, up,
-              h_rows, dt, lambda, (const float4*)pack_bwd, d_pre, d_hrows);
-  return launch_status();
-}
-
-int temp_lin_rows2_supported(int d) {
-  return temp_lin_chain_supported(d, 0) && lin_lds_rows2_fwd(d) <= LC_LDS_LIMIT && lin_lds_rows2_bwd(d) <= LC_LDS_LIMIT;
+  const LinRows<1> a = {{nullptr}, {h_rows}, {dt}, {(const float4*)pack_bwd}, {d_hrows}};
+  return lin_rows_run<1, false>(n, d, act, lambda, a, out, up, d_pre, stream);
 }
 
 int temp_lin_rows2_fwd(int n, int d, const float* x, const int32_t* x_rows, const float* H_f, const int32_t* rows_f, const float* dt_f,
                        const float* H_b, const int32_t* rows_b, const float* dt_b, float lambda, const float* pack_fwd_f, const float* pack_fwd_b,
                        int act, float* out, float* hdec_f, float* hdec_b, void* stream) {
-  if (n < 0 || d <= 0 || (act != 0 && act != 1)) return TEMP_E_BADARG;
-  if (!temp_lin_rows2_supported(d)) return TEMP_E_UNSUPPORTED;
-  if (n == 0) return TEMP_OK;
-  if (!x || !H_f || !rows_f || !dt_f || !H_b || !rows_b || !dt_b || !pack_fwd_f || !pack_fwd_b || !out || !hdec_f || !hdec_b) return TEMP_E_BADARG;
-  static bool attr = false;
-  if (lin_lds_attr(k_lin_rows2_fwd, &attr)) return TEMP_E_LAUNCH;
-  const LinRows2 a = {{H_f, H_b}, {rows_f, rows_b}, {dt_f, dt_b}, {(const float4*)pack_fwd_f, (const float4*)pack_fwd_b}};
-  TEMP_LAUNCH(K_LIN_ROWS2_FWD, k_lin_rows2_fwd, dim3(ceil_div(n, LR_ROWS)), dim3(LC_THREADS), lin_lds_rows2_fwd(d), (hipStream_t)stream, n, d, act, x,
-              x_rows, a, lambda, out, hdec_f, hdec_b);
-  return launch_status();
+  const LinRows<2> a = {{H_f, H_b}, {rows_f, rows_b}, {dt_f, dt_b}, {(const float4*)pack_fwd_f, (const float4*)pack_fwd_b}, {hdec_f, hdec_b}};
+  return lin_rows_run<2, true>(n, d, act, lambda, a, x, x_rows, out, stream);
 }
 
 int temp_lin_rows2_bwd(int n, int d, const float* out, const float* up, const int32_t* rows_f, const float* dt_f, const int32_t* rows_b,
                        const float* dt_b, float lambda, const float* pack_bwd_f, const float* pack_bwd_b, int act, float* d_pre, float* d_hrows_f,
                        float* d_hrows_b, void* stream) {
-  if (n < 0 || d <= 0 || (act != 0 && act != 1)) return TEMP_E_BADARG;
-  if (!temp_lin_rows2_supported(d)) return TEMP_E_UNSUPPORTED;
-  if (n == 0) return TEMP_OK;
-  if ((act && !out) || !up || !rows_f || !dt_f || !rows_b || !dt_b || !pack_bwd_f || !pack_bwd_b || !d_pre || !d_hrows_f || !d_hrows_b) return TEMP_E_BADARG;
-  static bool attr = false;
-  if (lin_lds_attr(k_lin_rows2_bwd, &attr)) return TEMP_E_LAUNCH;
-  const LinRows2 a = {{nullptr, nullptr}, {rows_f, rows_b}, {dt_f, dt_b}, {(const float4*)pack_bwd_f, (const float4*)pack_bwd_b}};
-  TEMP_LAUNCH(K_LIN_ROWS2_BWD, k_lin_rows2_bwd, dim3(ceil_div(n, LR_ROWS)), dim3(LC_THREADS), lin_lds_rows2_bwd(d), (hipStream_t)stream, n, d, act, out,
-              up, a, lambda, d_pre, d_hrows_f, d_hrows_b);
-  return launch_status();
+  const LinRows<2> a = {{nullptr, nullptr}, {rows_f, rows_b}, {dt_f, dt_b}, {(const float4*)pack_bwd_f, (const float4*)pack_bwd_b}, {d_hrows_f, d_hrows_b}};
+  return lin_rows_run<2, false>(n, d, act, lambda, a, out, up, d_pre, stream);
 }
 
 }  // extern "C"

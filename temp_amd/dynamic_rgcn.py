@@ -572,6 +572,42 @@ class DynamicRGCN(TKG_Module):
             c = dc
         return [c.single_graph_negative_sampling(wb.rows[i][-1], g, self.num_ents)[:3] for i, g in enumerate(wb.graphs)]
 
+    def _all_frame(self, wb, rep):
+        """What every map of the all-entity pass starts from -> (act (B, N) the active entities of every window, n_out and off_out the
+        encoder output's row count and window offsets, tab (B, N) every pair's row of the table, T the table's row count); sets
+        wb.all_rep, wb.all_rep_ids / all_rep_inv, wb.n_inactive and clears wb.all_time."""
+        dev = self._device()
+        N, B = self.num_ents, len(wb.graphs)
+        # rep (the self-loop dropout draws): the reference runs forward_isolated per window, each with its own mask
+        # (models/DynamicRGCN.py:56-64, models/RGCN.py:78-89), so nothing of the isolated pass is shared between windows: the
+        # once-per-entity table becomes a (window, entity) table of B * N_ents rows -- the kernels' masks are a function of
+        # (seed, row, column), so ONE launch over those rows gives every window its own mask
+        T = B * N if rep else N
+        tab = (np.arange(B * N, dtype=np.int64).reshape(B, N) if rep else np.broadcast_to(np.arange(N, dtype=np.int64)[None, :], (B, N)))
+        wb.all_rep = rep
+        if rep:
+            ids = np.tile(np.arange(N, dtype=np.int32), B)
+            wb.all_rep_ids = _lib.to_device(ids, dev)
+            wb.all_rep_inv = TF.gather_inverse(ids, N, dev)
+        act = np.zeros((B, N), dtype=bool)
+        sizes = [g.n for g in wb.graphs]
+        for b, g in enumerate(wb.graphs):
+            act[b, g.gids] = True
+        wb.n_inactive = int(B * N - act.sum())
+        wb.all_time = None
+        return act, int(sum(sizes)), np.concatenate([[0], np.cumsum(sizes)]), tab, T
+
+    def _all_asm(self, wb, has, frame):
+        """has (B, N): the (window, entity) pairs with rows of their own, window-major -> (asm (B, N), n_src): the map that assembles
+        every window's entities from the n_src rows [encoder output ; pair rows ; table]."""
+        _, n_out, off_out, tab, T = frame
+        n_prev = int(has.sum())
+        asm = (n_out + n_prev + tab).copy()
+        asm[has] = n_out + np.arange(n_prev)
+        for b, g in enumerate(wb.graphs):
+            asm[b, g.gids] = off_out[b] + np.arange(g.n)
+        return asm, n_out + n_prev + T
+
     def _all_maps(self, wb):
         """Row maps of the batched all-entity pass (get_all_embeds_Gt for every window at once), cached on the batch.
         An entity of window b falls in one of three classes:
@@ -588,25 +624,7 @@ class DynamicRGCN(TKG_Module):
             N, B = self.num_ents, len(wb.graphs)
             plans = wb.plan if isinstance(wb.plan, tuple) else (wb.plan,)
             L = plans[0].seq_len
-            # rep (the self-loop dropout draws): the reference runs forward_isolated per window, each with its own mask
-            # (models/DynamicRGCN.py:56-64, models/RGCN.py:78-89), so nothing of the isolated pass is shared between windows: the
-            # once-per-entity table becomes a (window, entity) table of B * N_ents rows -- the kernels' masks are a function of
-            # (seed, row, column), so ONE launch over those rows gives every window its own mask
-            T = B * N if rep else N
-            tab = (np.arange(B * N, dtype=np.int64).reshape(B, N) if rep else np.broadcast_to(np.arange(N, dtype=np.int64)[None, :], (B, N)))
-            wb.all_rep = rep
-            if rep:
-                ids = np.tile(np.arange(N, dtype=np.int32), B)
-                wb.all_rep_ids = _lib.to_device(ids, dev)
-                wb.all_rep_inv = TF.gather_inverse(ids, N, dev)
-            act = np.zeros((B, N), dtype=bool)
-            sizes = [g.n for g in wb.graphs]
-            n_out = int(sum(sizes))
-            off_out = np.concatenate([[0], np.cumsum(sizes)])
-            for b, g in enumerate(wb.graphs):
-                act[b, g.gids] = True
-            wb.n_inactive = int(B * N - act.sum())
-            wb.all_time = None
+            frame = act, n_out, off_out, tab, T = self._all_frame(wb, rep)
             if self.ent_encoder.use_time_embedding and self._chain_time_embedding and wb.n_inactive:
                 # forward_isolated adds time_embed_2[t_b] to all rows of window b, then the active rows are overwritten with the
                 # encoder's (models/RRGCN.py:214-216, models/DynamicRGCN.py:60-63): the inactive rows' table row, -1 on the active ones
@@ -621,11 +639,7 @@ class DynamicRGCN(TKG_Module):
                 bb, ee = np.nonzero(has)                                   # window-major
                 n_prev = int(bb.shape[0])
                 if d == 0:
-                    asm = (n_out + n_prev + tab).copy()
-                    asm[has] = n_out + np.arange(n_prev)
-                    for b, g in enumerate(wb.graphs):
-                        asm[b, g.gids] = off_out[b] + np.arange(g.n)
-                    n_src = n_out + n_prev + T
+                    asm, n_src = self._all_asm(wb, has, frame)
                 else:
                     asm = (n_prev + tab).copy()
                     asm[has] = np.arange(n_prev)
@@ -655,6 +669,29 @@ class DynamicRGCN(TKG_Module):
         if k not in c:
             c[k] = TF.injective_inverse(m[key + "_host"], prev.shape[0], prev.device)
         return c[k]
+
+    @staticmethod
+    def _rows_inverse(cache, key, idx_host, H):
+        """gather_inverse of a static history-row list over the rows of H, built on first use and kept with the prepared batch."""
+        if H is None:
+            return None
+        k = (key, int(H.shape[0]))
+        if k not in cache:
+            cache[k] = TF.gather_inverse(idx_host, H.shape[0], H.device)
+        return cache[k]
+
+    # the head and tail every all_embeds_batched variant shares (m = the first map of _all_maps)
+    def _all_from_rows(self, wb, rows, m):
+        """(B, N_ents, D) through m's assembly map from `rows` (the encoder output alone when every entity is active in its window)."""
+        big = TF.gather_rows(rows, m["asm"], m["asm_inv"])
+        return big.view(len(wb.graphs), self.num_ents, big.shape[1])
+
+    def _all_table_input(self, wb):
+        """The entity table the isolated pass starts from: one row per entity, per (window, entity) while the dropout draws."""
+        return TF.gather_rows(self.ent_embeds, wb.all_rep_ids, wb.all_rep_inv) if wb.all_rep else self.ent_embeds
+
+    def _all_assemble(self, wb, parts, m):
+        return self._all_from_rows(wb, torch.cat(parts, dim=0), m)
 
     def _assemble_all(self, wb, out, isolated):
         """-> (B, N_ents, D): per window the active rows from `out` (concatenated target rows), the rest from the
@@ -710,14 +747,12 @@ class DynamicRGCN(TKG_Module):
         enc = self.ent_encoder
         l1, l2 = enc.layer_1, enc.layer_2
         maps = self._all_maps(wb)
-        B, N = len(wb.graphs), self.num_ents
         if wb.n_inactive == 0:
-            return TF.gather_rows(out, maps[0]["asm"], maps[0]["asm_inv"]).view(B, N, out.shape[1])
+            return self._all_from_rows(wb, out, maps[0])
         if self._linear_layer():
             return self._all_embeds_batched_linear(wb, out, hist, maps)
         l1_rec = isinstance(l1, GRRGCNLayer)
-        E = TF.gather_rows(self.ent_embeds, wb.all_rep_ids, wb.all_rep_inv) if wb.all_rep else self.ent_embeds      # (window, entity) rows
-        iso1 = l1.conv_isolated(E)
+        iso1 = l1.conv_isolated(self._all_table_input(wb))
         t1 = self._zero_state_rows(l1.rnn, iso1, l1) if l1_rec else iso1
         x = l2.conv_isolated(t1)
         lam, dec = l2.inv_temperature, l2.decay_spec()
@@ -733,11 +768,11 @@ class DynamicRGCN(TKG_Module):
                     xp = TF.gather_rows(x, m["ent"], m["ent_inv"])
                 parts.append(run_rnn(rnn, xp, H, m["dt"], lam, dec, m["idx"], self._pair_inverse(m, "idx", H)))
             parts.append(self._zero_state_rows(rnn, x, l2))                      # GRU(x_e, 0): one row per entity, every window
-            g = TF.gather_rows(torch.cat(parts, dim=0), m["asm"], m["asm_inv"])
+            g = self._all_assemble(wb, parts, m)
             big = g if big is None else big + g
         if enc.use_time_embedding:                   # once per window, after the directions are summed; the active rows carry it from `out`
-            big = big + TF.gather_rows(l2.time_embed, wb.all_time[0], wb.all_time[1])
-        return big.view(B, N, big.shape[1])
+            big = big + TF.gather_rows(l2.time_embed, wb.all_time[0], wb.all_time[1]).view_as(big)
+        return big
 
     def _all_embeds_batched_linear(self, wb, out, hist, maps):
         """The isolated pass of the linear recurrence (RRGCNLayer.forward_isolated) for all windows at once: x = pre2(Iso1(E)) once per
@@ -746,28 +781,24 @@ class DynamicRGCN(TKG_Module):
         recurrent a pair runs through both: y1p = act(Iso1(E)[e] + dec (h1[idx] . Wt1)), then act(pre_isolated2(y1p) + dec (h2[idx] . Wt2))."""
         enc = self.ent_encoder
         l1, l2 = enc.layer_1, enc.layer_2
-        B, N = len(wb.graphs), self.num_ents
         (m,), H = maps, hist[1]
         l1_rec = isinstance(l1, RRGCNLayer)               # both layers recurrent (_run_lin_stack): hist = (h1, h2) of the last history position
-        E = TF.gather_rows(self.ent_embeds, wb.all_rep_ids, wb.all_rep_inv) if wb.all_rep else self.ent_embeds
+        E = self._all_table_input(wb)
         iso1 = l1.pre_isolated(E) if l1_rec else None
         x = l2.pre_isolated(l1.finish_rows(iso1, None, None, None) if l1_rec else l1.conv_isolated(E))
         parts = [out]
-        if m["n_prev"]:
-            inv = m.setdefault("_gather_inv", {})
-            if H.shape[0] not in inv:                     # static per prepared batch: the deterministic adjoint of the history gather
-                inv[H.shape[0]] = TF.gather_inverse(m["idx_host"], H.shape[0], H.device)
+        if m["n_prev"]:                                   # static per prepared batch: the deterministic adjoint of the history gather
+            inv = self._rows_inverse(m.setdefault("_gather_inv", {}), "idx", m["idx_host"], H)
         if m["n_prev"] and l1_rec:
             # the pair's own first-layer state, then the second layer on it: one lin_step_rows node per layer (one map serves both)
             act1, act2 = (1 if l.relu_fused() else 0 for l in (l1, l2))
-            y1p = TF.lin_step_rows(iso1, m["ent"], hist[0], m["idx"], m["dt"], l1.inv_temperature, l1.time_weight, act1, m["ent_inv"], inv[H.shape[0]])
-            parts.append(TF.lin_step_rows(l2.pre_isolated(y1p), None, H, m["idx"], m["dt"], l2.inv_temperature, l2.time_weight, act2, None, inv[H.shape[0]]))
+            y1p = TF.lin_step_rows(iso1, m["ent"], hist[0], m["idx"], m["dt"], l1.inv_temperature, l1.time_weight, act1, m["ent_inv"], inv)
+            parts.append(TF.lin_step_rows(l2.pre_isolated(y1p), None, H, m["idx"], m["dt"], l2.inv_temperature, l2.time_weight, act2, None, inv))
         elif m["n_prev"]:
-            prev = TF.gather_rows(H, m["idx"], inv[H.shape[0]])
+            prev = TF.gather_rows(H, m["idx"], inv)
             parts.append(l2.finish_rows(TF.gather_rows(x, m["ent"], m["ent_inv"]), prev, None, m["dt"]))
         parts.append(l2.finish_rows(x, None, None, None))
-        big = TF.gather_rows(torch.cat(parts, dim=0), m["asm"], m["asm_inv"])
-        return big.view(B, N, big.shape[1])
+        return self._all_assemble(wb, parts, m)
 
     def run_loss(self, wb, samples=None):
         """Encoder pass + the per-window link-prediction losses (summed, as the reference does)."""

@@ -373,36 +373,50 @@ def _gather_adjoint(be, src, idx, inverse, rows):
 
 
 class _LinStepRowsFn(torch.autograd.Function):
-    """The kernel route of lin_step_rows: saves out (the ReLU mask is the kernel's own out > 0) and hdec (the left factor of d_W)."""
+    """The kernel route of lin_step_rows (one source) and lin_step_rows2 (two): saves out (the ReLU mask is the kernel's own out > 0)
+    and every source's hdec (the left factor of its d_W).  meta = (x_rows, x_inv, lam, act, [(rows, dt, inv, has)] per source); the
+    tensors that may need a gradient follow: every source's H, then every source's W.  has False: a source without history, which came
+    in as a one-row zero H with rows all -1 (_absent_source) and hands no gradient to its H or W."""
 
     @staticmethod
-    def forward(ctx, x, H, W, x_rows, h_rows, dt, lam, act, x_inv, h_inv):
+    def forward(ctx, meta, x, *HW):
         be = get_backend()
-        x, H = x.detach().contiguous(), H.detach().contiguous()
-        dt = dt.detach().contiguous().view(-1)
-        n, d = h_rows.shape[0], x.shape[1]
-        pack = be.lin_chain_pack_multi([W.detach().contiguous()])[0]
-        out = torch.empty(n, d, dtype=torch.float32, device=x.device)
-        hdec = torch.empty(n, d, dtype=torch.float32, device=x.device)
-        be.lin_rows_fwd(x, x_rows, H, h_rows, dt, lam, pack, act, out, hdec)
-        ctx.save_for_backward(out, hdec, pack, dt)
-        ctx.x_rows, ctx.h_rows, ctx.x_inv, ctx.h_inv, ctx.lam, ctx.act, ctx.n_x, ctx.n_h = x_rows, h_rows, x_inv, h_inv, lam, act, x.shape[0], H.shape[0]
+        x_rows, x_inv, lam, act, srcs = meta
+        ns = len(srcs)
+        x = x.detach().contiguous()
+        Hs = [H.detach().contiguous() for H in HW[:ns]]
+        rows, dts = [s[0] for s in srcs], [s[1].detach().contiguous().view(-1) for s in srcs]
+        n, d = rows[0].shape[0], x.shape[1]
+        packs = be.lin_chain_pack_multi([W.detach().contiguous() for W in HW[ns:]])
+        out, *hdecs = (torch.empty(n, d, dtype=torch.float32, device=x.device) for _ in range(1 + ns))
+        if ns == 1:
+            be.lin_rows_fwd(x, x_rows, Hs[0], rows[0], dts[0], lam, packs[0], act, out, hdecs[0])
+        else:
+            be.lin_rows2_fwd(x, x_rows, Hs[0], rows[0], dts[0], Hs[1], rows[1], dts[1], lam, packs[0], packs[1], act, out, *hdecs)
+        ctx.save_for_backward(out, *hdecs, *packs, *dts)
+        ctx.meta, ctx.n_x, ctx.n_h = meta, x.shape[0], [H.shape[0] for H in Hs]
         return out
 
     @staticmethod
     def backward(ctx, d_out):
         be = get_backend()
-        out, hdec, pack, dt = ctx.saved_tensors
-        d_pre, d_hrows = torch.empty_like(out), torch.empty_like(out)
-        be.lin_rows_bwd(out, d_out.contiguous(), ctx.h_rows, dt, ctx.lam, pack, ctx.act, d_pre, d_hrows)
-        d_x = d_H = d_W = None
-        if ctx.needs_input_grad[0]:
-            d_x = d_pre if ctx.x_rows is None else _gather_adjoint(be, d_pre, ctx.x_rows, ctx.x_inv, ctx.n_x)
-        if ctx.needs_input_grad[1]:
-            d_H = _gather_adjoint(be, d_hrows, ctx.h_rows, ctx.h_inv, ctx.n_h)
-        if ctx.needs_input_grad[2]:
-            d_W = be.linear_tn(hdec, d_pre)
-        return d_x, d_H, d_W, None, None, None, None, None, None, None
+        x_rows, x_inv, lam, act, srcs = ctx.meta
+        ns = len(srcs)
+        out, saved = ctx.saved_tensors[0], ctx.saved_tensors[1:]
+        hdecs, packs, dts = saved[:ns], saved[ns:2 * ns], saved[2 * ns:]
+        rows = [s[0] for s in srcs]
+        d_pre, *d_h = (torch.empty_like(out) for _ in range(1 + ns))
+        if ns == 1:
+            be.lin_rows_bwd(out, d_out.contiguous(), rows[0], dts[0], lam, packs[0], act, d_pre, d_h[0])
+        else:
+            be.lin_rows2_bwd(out, d_out.contiguous(), rows[0], dts[0], rows[1], dts[1], lam, packs[0], packs[1], act, d_pre, *d_h)
+        need = ctx.needs_input_grad[1:]
+        d_x = None
+        if need[0]:
+            d_x = d_pre if x_rows is None else _gather_adjoint(be, d_pre, x_rows, x_inv, ctx.n_x)
+        d_H = [_gather_adjoint(be, d_h[s], rows[s], srcs[s][2], ctx.n_h[s]) if need[1 + s] and srcs[s][3] else None for s in range(ns)]
+        d_W = [be.linear_tn(hdecs[s], d_pre) if need[1 + ns + s] and srcs[s][3] else None for s in range(ns)]
+        return (None, d_x, *d_H, *d_W)
 
 
 def lin_step_rows_torch(x, x_rows, H, h_rows, dt, lam, W, act, x_inv=None, h_inv=None):
@@ -423,54 +437,13 @@ def lin_step_rows(x, x_rows, H, h_rows, dt, lam, W, act, x_inv=None, h_inv=None)
     act = int(bool(act))
     if h_rows.shape[0] == 0 or not lin_rows_usable(x.shape[1]):
         return lin_step_rows_torch(x, x_rows, H, h_rows, dt, float(lam), W, act, x_inv, h_inv)
-    return _LinStepRowsFn.apply(x, H, W, x_rows, h_rows, dt, float(lam), act, x_inv, h_inv)
+    return _LinStepRowsFn.apply((x_rows, x_inv, float(lam), act, [(h_rows, dt, h_inv, True)]), x, H, W)
 
 
 def lin_rows2_usable(d):
     """True when lin_step_rows2 runs rows of this width through temp_lin_rows2_fwd / _bwd."""
     be = get_backend()
     return bool(LIN_ROWS_KERNEL and hasattr(be, "lin_rows2_fwd") and be.lin_rows2_supported(d))
-
-
-class _LinStepRows2Fn(torch.autograd.Function):
-    """The kernel route of lin_step_rows2: saves out (the ReLU mask is the kernel's own out > 0) and both hdec (the left factors of
-    d_W_f / d_W_b).  has = (bool, bool): a direction without history came in as a one-row zero H with rows all -1 and hands no
-    gradient to its H or W."""
-
-    @staticmethod
-    def forward(ctx, x, Hf, Hb, Wf, Wb, x_rows, rows_f, dt_f, rows_b, dt_b, lam, act, x_inv, f_inv, b_inv, has):
-        be = get_backend()
-        x, Hf, Hb = x.detach().contiguous(), Hf.detach().contiguous(), Hb.detach().contiguous()
-        dt_f, dt_b = dt_f.detach().contiguous().view(-1), dt_b.detach().contiguous().view(-1)
-        n, d = rows_f.shape[0], x.shape[1]
-        pack_f, pack_b = be.lin_chain_pack_multi([Wf.detach().contiguous(), Wb.detach().contiguous()])
-        out, hdec_f, hdec_b = (torch.empty(n, d, dtype=torch.float32, device=x.device) for _ in range(3))
-        be.lin_rows2_fwd(x, x_rows, Hf, rows_f, dt_f, Hb, rows_b, dt_b, lam, pack_f, pack_b, act, out, hdec_f, hdec_b)
-        ctx.save_for_backward(out, hdec_f, hdec_b, pack_f, pack_b, dt_f, dt_b)
-        ctx.x_rows, ctx.rows, ctx.invs, ctx.lam, ctx.act, ctx.has = x_rows, (rows_f, rows_b), (x_inv, f_inv, b_inv), lam, act, has
-        ctx.n_x, ctx.n_h = x.shape[0], (Hf.shape[0], Hb.shape[0])
-        return out
-
-    @staticmethod
-    def backward(ctx, d_out):
-        be = get_backend()
-        out, hdec_f, hdec_b, pack_f, pack_b, dt_f, dt_b = ctx.saved_tensors
-        (rows_f, rows_b), (x_inv, f_inv, b_inv) = ctx.rows, ctx.invs
-        d_pre, d_hf, d_hb = torch.empty_like(out), torch.empty_like(out), torch.empty_like(out)
-        be.lin_rows2_bwd(out, d_out.contiguous(), rows_f, dt_f, rows_b, dt_b, ctx.lam, pack_f, pack_b, ctx.act, d_pre, d_hf, d_hb)
-        need = ctx.needs_input_grad
-        d_x = d_Hf = d_Hb = d_Wf = d_Wb = None
-        if need[0]:
-            d_x = d_pre if ctx.x_rows is None else _gather_adjoint(be, d_pre, ctx.x_rows, x_inv, ctx.n_x)
-        if need[1] and ctx.has[0]:
-            d_Hf = _gather_adjoint(be, d_hf, rows_f, f_inv, ctx.n_h[0])
-        if need[2] and ctx.has[1]:
-            d_Hb = _gather_adjoint(be, d_hb, rows_b, b_inv, ctx.n_h[1])
-        if need[3] and ctx.has[0]:
-            d_Wf = be.linear_tn(hdec_f, d_pre)
-        if need[4] and ctx.has[1]:
-            d_Wb = be.linear_tn(hdec_b, d_pre)
-        return (d_x, d_Hf, d_Hb, d_Wf, d_Wb) + (None,) * 11
 
 
 def lin_step_rows2_torch(x, x_rows, Hf, rows_f, dt_f, Hb, rows_b, dt_b, lam, Wf, Wb, act, x_inv=None, f_inv=None, b_inv=None):
@@ -481,6 +454,11 @@ def lin_step_rows2_torch(x, x_rows, Hf, rows_f, dt_f, Hb, rows_b, dt_b, lam, Wf,
         if H is not None:
             out = out + linear_nt(decay_rows(gather_rows(H, rows, inv), dt, lam), W)
     return torch.relu(out) if act else out
+
+
+def _absent_source(x, n):
+    """What the kernel reads for a source without history: a one-row zero H, rows all -1, zero dt -> (H, (rows, dt, inv, has))."""
+    return x.new_zeros(1, x.shape[1]), (torch.full((n,), -1, dtype=torch.int32, device=x.device), x.new_zeros(n), None, False)
 
 
 def lin_step_rows2(x, x_rows, Hf, rows_f, dt_f, Hb, rows_b, dt_b, lam, Wf, Wb, act, x_inv=None, f_inv=None, b_inv=None):
@@ -496,14 +474,9 @@ def lin_step_rows2(x, x_rows, Hf, rows_f, dt_f, Hb, rows_b, dt_b, lam, Wf, Wb, a
     n = x_rows.shape[0] if x_rows is not None else x.shape[0]
     if n == 0 or not lin_rows2_usable(x.shape[1]):
         return lin_step_rows2_torch(x, x_rows, Hf, rows_f, dt_f, Hb, rows_b, dt_b, float(lam), Wf, Wb, act, x_inv, f_inv, b_inv)
-    has = (Hf is not None, Hb is not None)
-    if not all(has):
-        none, zero_dt, zero_h = torch.full((n,), -1, dtype=torch.int32, device=x.device), x.new_zeros(n), x.new_zeros(1, x.shape[1])
-        if not has[0]:
-            Hf, rows_f, dt_f, f_inv = zero_h, none, zero_dt, None
-        if not has[1]:
-            Hb, rows_b, dt_b, b_inv = zero_h, none, zero_dt, None
-    return _LinStepRows2Fn.apply(x, Hf, Hb, Wf, Wb, x_rows, rows_f, dt_f, rows_b, dt_b, float(lam), act, x_inv, f_inv, b_inv, has)
+    Hs, srcs = zip(*[(H, (rows, dt, inv, True)) if H is not None else _absent_source(x, n)
+                     for H, rows, dt, inv in ((Hf, rows_f, dt_f, f_inv), (Hb, rows_b, dt_b, b_inv))])
+    return _LinStepRowsFn.apply((x_rows, x_inv, float(lam), act, list(srcs)), x, *Hs, Wf, Wb)
 
 
 class _DiachronicRowsFn(torch.autograd.Function):

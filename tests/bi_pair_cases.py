@@ -154,6 +154,56 @@ def check_absent_direction(d, device, kernel=True):
         check_quantities(res, ref, "d = %d H%s = None%s" % (d, absent, "" if kernel else " (composition)"))
 
 
+ONE_SOURCE_N, ONE_SOURCE_WIDTHS = 33, (20, 200)     # two workgroups, the second with one live row; one padded tile, seven tiles (waves
+                                                    # 0 .. 2 use their second accumulator, wave 3 does not)
+
+
+def one_source_inputs(d):
+    """rows2_inputs(33, d, x_rows given) with the forward row list redrawn: about a quarter -1; row 0 has a history row, row 1 none, row
+    32 (the second workgroup's one live row) repeats row 0's."""
+    c = rows2_inputs(ONE_SOURCE_N, d, True)
+    g = torch.Generator().manual_seed(53 + d)
+    h = torch.randint(0, HF_ROWS, (ONE_SOURCE_N,), generator=g)
+    h[torch.rand(ONE_SOURCE_N, generator=g) < 0.25] = -1
+    h[0], h[1], h[ONE_SOURCE_N - 1] = 7, -1, 7
+    assert 4 <= int((h < 0).sum()) <= 13
+    c["rows_f"] = h.int()
+    return c
+
+
+def run_one_source(c, device, two):
+    """The forward direction alone, ReLU on, under the upstream gradient c["up"]: lin_step_rows (two False) or lin_step_rows2 with
+    Hb = None (two True) -> dict(out, d_x, d_Hf, d_Wf) on the CPU."""
+    leaf = {k: c[k].clone().to(device).requires_grad_(True) for k in ("x", "Hf", "Wf", "Wb")}
+    x_rows, rows_f, dt_f = c["x_rows"].to(device), c["rows_f"].to(device), c["dt_f"].to(device).view(-1, 1)
+    x_inv = TF.gather_inverse(c["x_rows"].numpy(), c["x"].shape[0], device)
+    f_inv = TF.gather_inverse(c["rows_f"].numpy(), HF_ROWS, device)
+    if two:
+        out = TF.lin_step_rows2(leaf["x"], x_rows, leaf["Hf"], rows_f, dt_f, None, None, None, LAM, leaf["Wf"], leaf["Wb"], 1, x_inv, f_inv, None)
+    else:
+        out = TF.lin_step_rows(leaf["x"], x_rows, leaf["Hf"], rows_f, dt_f, LAM, leaf["Wf"], 1, x_inv, f_inv)
+    (out * c["up"].to(device)).sum().backward()
+    assert leaf["Wb"].grad is None or not bool(leaf["Wb"].grad.any())
+    return dict(out=out.detach().cpu(), d_x=leaf["x"].grad.cpu(), d_Hf=leaf["Hf"].grad.cpu(), d_Wf=leaf["Wf"].grad.cpu())
+
+
+def check_one_source(d, device, exact):
+    """lin_step_rows2 with the backward direction absent against lin_step_rows on the same inputs.  exact (the kernel route): equal to
+    the bit -- both kernels decay in front of the product and walk source 0 first, and the absent source adds products with exact
+    zeros, which change no finite accumulator value.  Not exact (the two torch compositions round in different orders: the decay
+    behind the product against in front of it): out inside STATE_BAR, the gradients inside GRAD_BAR."""
+    c = one_source_inputs(d)
+    one, two = run_one_source(c, device, False), run_one_source(c, device, True)
+    assert float(one["out"].abs().max()) > 0 and bool((one["out"] == 0).any()), "the ReLU cuts some elements and not all"
+    if not exact:
+        return check_quantities(two, one, "d = %d, one source: lin_step_rows2(Hb = None) against lin_step_rows" % d)
+    for k in sorted(one):
+        diff = float((two[k] - one[k]).abs().max())
+        print("d = %d, one source: %s max |lin_step_rows2(Hb = None) - lin_step_rows| = %.3g" % (d, k, diff))
+    for k in sorted(one):
+        assert torch.equal(two[k], one[k]), k
+
+
 # ---- the window model ---------------------------------------------------------------------------------------------------------
 def bi_model(device, on, dropout=0.0):
     m, _, _, z = LC.window_model(MODULE, GOLDEN, device, dropout=dropout)

@@ -19,7 +19,8 @@ One direction's H None (d = 32, 200): out 0.085, gradients 0.0061.  Composition 
 Model (D = 32, ICEWS14 slice): loss 24.35783005 with the attribute on, 24.35783386 off and in the float64 oracle (1.6e-7 relative);
 gradients on against off at most 0.00097 of the bar; all_embeds_batched against get_all_embeds_Gt 0.016 of the state bar (0.036 on
 (window, entity) rows); the union map holds 515 forward-only, 363 backward-only and 100 two-sided pairs; windows of length 1: the
-bit-same loss, gradients 0.000075 of the bar; backend calls of a step 41 against 133."""
+bit-same loss, gradients 0.000075 of the bar; backend calls of a step 41 against 133.
+lin_step_rows2 with Hb = None against lin_step_rows (d = 20, 200; n = 33): out, d_x, d_Hf, d_Wf equal to the bit (max |difference| 0)."""
 import ctypes
 from collections import Counter
 
@@ -58,6 +59,16 @@ def test_node_vs_fp64(d, n, act):
 def test_absent_direction(d):
     (_, names) = _traced(lambda: C.check_absent_direction(d, DEV))
     assert [names.count(k) for k in KERNELS] == [2, 2], names
+
+
+@pytest.mark.parametrize("d", C.ONE_SOURCE_WIDTHS)
+def test_one_source_equals_lin_step_rows(d):
+    """The two instantiations of the one row step agree to the bit where they compute the same thing: lin_step_rows2 with Hb = None
+    against lin_step_rows (n = 33, x_rows given, ReLU, about a quarter of the history rows -1) -- out, d_x, d_Hf, d_Wf under
+    torch.equal, one launch of each kernel."""
+    assert TF.lin_rows_usable(d) and TF.lin_rows2_usable(d)
+    (_, names) = _traced(lambda: C.check_one_source(d, DEV, exact=True))
+    assert [names.count(k) for k in KERNELS + ("k_lin_rows_fwd", "k_lin_rows_bwd")] == [1, 1, 1, 1], names
 
 
 def test_every_buffer_written(hip_backend):
