@@ -62,6 +62,20 @@ __device__ __forceinline__ float reduce8(float v) {
   return v;
 }
 
+// hi + lo <- (hi + lo) * c + x * y with the rounding errors of both products and of the sum kept in lo.  The forward's running sums
+// take one such step per position: rounded to fp32 at every step, `out` ends several ulps off after 64 positions, which its own
+// bar never sees but the backward does -- it takes delta = <d_out, out>, and where many positions share one table row the score
+// gradients p (dp - delta) are small differences that all carry delta's error into the same row of d_kh (and into d_q).
+__device__ __forceinline__ void scale_add2(float& hi, float& lo, float c, float x, float y) {
+#pragma clang fp contract(off)
+  const float th = hi * c, tl = fmaf(hi, c, -th) + lo * c;
+  const float ph = x * y, pl = fmaf(x, y, -ph);
+  const float s = th + ph, bb = s - th;
+  const float err = (th - (s - bb)) + (ph - bb);
+  hi = s;
+  lo = tl + pl + err;
+}
+
 template <int MAXC, bool SPLIT>
 __global__ __launch_bounds__(256) void k_sa_attn_fwd(AttnArgs a, float* __restrict__ out, float* __restrict__ score,
                                                       float* __restrict__ lse) {
@@ -71,7 +85,7 @@ __global__ __launch_bounds__(256) void k_sa_attn_fwd(AttnArgs a, float* __restri
   const CurRow<SPLIT> cur(a, row);
   int col[MAXC];
   bool ok[MAXC];
-  float qv[MAXC], acc[MAXC];
+  float qv[MAXC], acc[MAXC], acc_lo[MAXC];
 #pragma unroll
   for (int i = 0; i < MAXC; ++i) {
     const int d = j + 8 * i;
@@ -79,8 +93,9 @@ __global__ __launch_bounds__(256) void k_sa_attn_fwd(AttnArgs a, float* __restri
     col[i] = head * a.dk + (ok[i] ? d : 0);
     qv[i] = ok[i] ? cur.q(col[i]) : 0.f;
     acc[i] = 0.f;
+    acc_lo[i] = 0.f;
   }
-  float m = -INFINITY, ssum = 0.f;
+  float m = -INFINITY, ssum = 0.f, ssum_lo = 0.f;
   const int Th = a.T - 1;
   float* srow = score + ((size_t)row * 8 + head) * a.T;
   for (int t = 0; t < a.T; ++t) {
@@ -116,16 +131,16 @@ __global__ __launch_bounds__(256) void k_sa_attn_fwd(AttnArgs a, float* __restri
     if (j == 0) srow[t] = s;
     const float mn = fmaxf(m, s);
     const float c = __expf(m - mn), e = __expf(s - mn);
-    ssum = ssum * c + e;
+    scale_add2(ssum, ssum_lo, c, e, 1.0f);
 #pragma unroll
-    for (int i = 0; i < MAXC; ++i) acc[i] = fmaf(e, vv[i], acc[i] * c);
+    for (int i = 0; i < MAXC; ++i) scale_add2(acc[i], acc_lo[i], c, e, vv[i]);
     m = mn;
   }
-  const float inv = 1.0f / ssum;
+  const float den = ssum + ssum_lo;
 #pragma unroll
   for (int i = 0; i < MAXC; ++i)
-    if (ok[i]) out[(size_t)row * a.D + (size_t)(j + 8 * i) * 8 + head] = acc[i] * inv;   // reference layout: d*heads + head
-  if (j == 0) lse[(size_t)row * 8 + head] = m + __logf(ssum);
+    if (ok[i]) out[(size_t)row * a.D + (size_t)(j + 8 * i) * 8 + head] = (acc[i] + acc_lo[i]) / den;   // reference layout: d*heads + head
+  if (j == 0) lse[(size_t)row * 8 + head] = m + __logf(den);
 }
 
 struct AttnGrads {
